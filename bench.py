@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- BPE training hot path on MI355X.
 
-Contract (driver): python bench.py --gpus N --steps K --warmup W
+Contract (driver): python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1 is launched by torch.distributed.run, one rank per GPU.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`) with the workload
+and the timed region; nothing else runs on the device.  --dump-outputs DIR writes what the last timed training returns
+(merges.npy: (n, 2) float64 token ids, counts.npy: (n,) float64 counts) so that two builds can be compared output for
+output.  --full adds everything below that the headline does not need: kernel events in the timed region (`roofline`),
+the checks of the result, the pair-count scan timed on its own, the CPU baseline and the published workload.
 
 A "step" is ONE WHOLE TRAINING of the workload: mbpe_train_begin (pair-count scan, slot stream, pair
 table, first argmax) + the loop Tokenizer.h:557-589 run to the target vocabulary (31,744 merges on the
@@ -19,6 +25,7 @@ generated on the device, so it is resident in HBM before anything is timed; the 
 --config bible: BASELINE.json config 3 with the documented stand-in corpus (data/bible.txt is absent
 from the reference checkout): shakespeare.txt x 4 = 4,461,576 bytes, vocab 10,000.
 
+With --full:
 `roofline` describes the kernel that dominates the timed steps (k_fused_batch) over EVERY launch of it
 inside the timed region (HIP events on the library's stream): `achieved` prices SURVEY.md 8(d)'s
 algorithmic bytes -- 2 B per live token read + 2 B per live token written -- and `achieved_slot_bytes`
@@ -220,8 +227,15 @@ def main():
     ap.add_argument("--cpu-sample-mib", type=int, default=256)
     ap.add_argument("--cpu-merges", type=int, default=48)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-full-run", action="store_true", help="skip the untimed checks after the timed region")
+    ap.add_argument("--no-full-run", action="store_true", help="with --full: skip the untimed checks after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: kernel events and roofline, checks of the result, the pair-count scan on "
+                         "its own, CPU baseline, published workload (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the merges and counts of the last timed training to DIR/merges.npy, DIR/counts.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     import numpy as np
     import torch
@@ -287,10 +301,11 @@ def main():
     # ---- timed region: K whole trainings after W warm-up trainings
     # (HIP events around the stream kernels of every sequence, 4 records each: nothing next to a 4 ms pass; on the 4.5 MB
     #  of config 3, where a sequence takes 0.16 ms, they would be a fifth of the run -- there the kernels are timed in
-    #  one extra, untimed training)
-    events_in_timed_region = not bible
-    tr.set_option("time_kernels", 1)
-    if not events_in_timed_region:
+    #  one extra, untimed training.  Only with --full: a plain run times the trainings without kernel events)
+    events_in_timed_region = args.full and not bible
+    tr.set_option("time_kernels", 1 if events_in_timed_region else 0)
+    if args.full and not events_in_timed_region:
+        tr.set_option("time_kernels", 1)
         e0 = tr.stats()
         one_training()
         e1 = tr.stats()
@@ -309,12 +324,63 @@ def main():
     done = sum(n for n, _, _ in steps)
     per_training = steps[-1][0] if steps else 0
     last = steps[-1][2] if steps else s1
+    n_pass = sum(st["n_batches"] for _, _, st in steps)
+
+    # ---- what the last timed training returns to its caller (every rank holds the same merges)
+    if args.dump_outputs and rank == 0:
+        merges, counts = tr.train_result()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "merges.npy"), merges.astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "counts.npy"), counts.astype(np.float64))
+
+    if bible:
+        workload = ("BASELINE config 3 stand-in (data/bible.txt is absent from the reference checkout): "
+                    "shakespeare.txt x 4 = %d bytes, basic encoder (one chunk), vocab %d, lexicographic "
+                    "tie-break" % (total_bytes, vocab))
+    else:
+        workload = ("BASELINE config 4: SplitMix64(seed %d) uniform-random bytes, %d bytes whole job, basic "
+                    "encoder (one chunk), vocab %d, lexicographic tie-break" % (args.seed, total_bytes, vocab))
+    timed = {"trainings": args.steps, "merges": done, "merges_per_training": per_training,
+             "stream_passes": n_pass,
+             "seconds": elapsed, "seconds_each": [round(sec, 5) for _, sec, _ in steps],
+             "live_end": last["n_live"], "slots_end": last["n_slots"],
+             "includes": "pair-count scan, stream + table setup, every sequence, host housekeeping (compactions)"}
+    out = {
+        "metric": "bpe_train_merges_per_sec",
+        "value": done / elapsed if elapsed > 0 else 0.0,
+        "unit": "merges/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed * 1e3 / max(args.steps, 1),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "u16",
+        "data": "synthetic" if not bible else "shakespeare.txt x 4 (fixture)",
+        "config": {
+            "workload": workload + "; a step is ONE WHOLE TRAINING (pair-count scan, stream and table setup, every "
+                        "merge up to the vocabulary: %d merges)" % per_training,
+            "corpus_bytes": total_bytes,
+            "vocab_size": vocab,
+            "parallelism": "stream sharded over %d GPU(s), pair table replicated, one sum all-reduce of the "
+                           "count deltas per sequence" % world,
+        },
+        "timed_region": timed,
+        "merges_per_step": per_training,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        tr.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # ---- the dominant kernel inside the timed region.  A fused pass (k_fused_batch) reads the stream once,
     # counts the deltas of every pair of the batch and writes the merged stream to the other buffer.
     # Algorithmic bytes: 2 B x L read + 2 B x L' written, L / L' the live tokens before / after the pass;
     # physically it moves 2 B + 2 B per SLOT (holes are squeezed out only at a compaction).
-    n_pass = sum(st["n_batches"] for _, _, st in steps)
     if not events_in_timed_region:
         s0, s1 = e0, e1                          # (kernel events: the extra training above)
     n_fused = s1["fused_launches"] - s0["fused_launches"]
@@ -362,12 +428,7 @@ def main():
                            "model_ms": (no_delta_ms + delta_ms) if no_delta_ms and delta_ms else None,
                            "floor_ms": stream_ms, "measured_ms": avg_ms,
                            "sources": FLOOR_FILE + " (" + fl.get("sources", "") + ")"}
-    timed = {"trainings": args.steps, "merges": done, "merges_per_training": per_training,
-             "stream_passes": n_pass, "fused_passes": n_fused,
-             "seconds": elapsed, "seconds_each": [round(sec, 5) for _, sec, _ in steps],
-             "ms_stream_kernels": ms_all, "ms_fused_kernel": ms_fused,
-             "live_end": last["n_live"], "slots_end": last["n_slots"],
-             "includes": "pair-count scan, stream + table setup, every sequence, host housekeeping (compactions)"}
+    timed.update({"fused_passes": n_fused, "ms_stream_kernels": ms_all, "ms_fused_kernel": ms_fused})
 
     # ---- untimed: checks of the last timed training's result on the device, then a further training stopped at checkpoints
     full_run, checks = None, None
@@ -476,36 +537,7 @@ def main():
     scan_gbs = (hi - lo) / (scan_ms_avg * 1e-3) / 1e9 if scan_ms_avg > 0 else 0.0
 
     if rank == 0:
-        if bible:
-            workload = ("BASELINE config 3 stand-in (data/bible.txt is absent from the reference checkout): "
-                        "shakespeare.txt x 4 = %d bytes, basic encoder (one chunk), vocab %d, lexicographic "
-                        "tie-break" % (total_bytes, vocab))
-        else:
-            workload = ("BASELINE config 4: SplitMix64(seed %d) uniform-random bytes, %d bytes whole job, basic "
-                        "encoder (one chunk), vocab %d, lexicographic tie-break" % (args.seed, total_bytes, vocab))
-        out = {
-            "metric": "bpe_train_merges_per_sec",
-            "value": done / elapsed if elapsed > 0 else 0.0,
-            "unit": "merges/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed * 1e3 / max(args.steps, 1),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "u16",
-            "data": "synthetic" if not bible else "shakespeare.txt x 4 (fixture)",
-            "config": {
-                "workload": workload + "; a step is ONE WHOLE TRAINING (pair-count scan, stream and table setup, every "
-                            "merge up to the vocabulary: %d merges)" % per_training,
-                "corpus_bytes": total_bytes,
-                "vocab_size": vocab,
-                "parallelism": "stream sharded over %d GPU(s), pair table replicated, one sum all-reduce of the "
-                               "count deltas per sequence" % world,
-            },
-            "timed_region": timed,
-            "merges_per_step": per_training,
+        out.update({
             "pair_count_scan_MBps": scan_gbs * 1e3 * world,
             "pair_count_scan_ms": scan_ms_avg,
             "roofline": {
@@ -560,7 +592,7 @@ def main():
             "batches": {k: last[k] for k in ("n_batches", "n_fused", "n_fused_dropped", "cut_conflict", "cut_bucket",
                                              "cut_single", "cut_full", "n_validation_drops", "n_sel_fallback",
                                              "n_sel_retry", "size_hist", "n_skipped", "n_skip_cut")},
-        }
+        })
         if not args.no_cpu_baseline and world == 1:
             if bible:
                 sample = corpus.cpu().numpy()
