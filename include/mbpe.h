@@ -152,14 +152,24 @@ MBPE_API int mbpe_load_corpus_ranges(mbpe_ctx *ctx, const uint8_t *text, uint64_
  * (Tokenizer.h:127-146) with PairCountLexicalOrder::create_or_modify_pair
  * (PairCount.h:249-260) as one histogram kernel.  table65536_out (host,
  * optional) receives count[(first << 8) | second].  Test / bench
- * granularity; mbpe_train_begin runs the same kernel. */
+ * granularity; mbpe_train_begin runs the same kernel.
+ * Counts are 32-bit: when a pair occurs 2^32 times or more (its bin
+ * wraps), the call returns MBPE_ERR_OVERFLOW and the table it wrote is
+ * not valid.  Every count below 2^32 is exact.  (Not checked with
+ * "pc_repeat" > 1 and no output table: the timing launches add up.) */
 MBPE_API int mbpe_pair_count_u8(mbpe_ctx *ctx, uint32_t *table65536_out);
 
 /* ---- training ------------------------------------------------------ */
 
 /* Prepares the training loop for `vocab_size` (>= 256, Tokenizer.h:492):
  * pair-count scan, 16-bit slot stream, pair table, first argmax.
- * Corresponds to Tokenizer.h:551-556. */
+ * Corresponds to Tokenizer.h:551-556.
+ * Pair counts are int32 like the reference's: a byte pair that occurs
+ * 2^31 times or more in the corpus returns MBPE_ERR_OVERFLOW, on one GPU
+ * here and with several ranks from the exchange that finishes the begin
+ * (mbpe_comm_exchange_done; the same decision on every rank), also when
+ * the ranks' counts only reach that limit summed, or wrap 2^32 in the
+ * u32 all-reduce.  A count of 2^31 - 1 trains. */
 MBPE_API int mbpe_train_begin(mbpe_ctx *ctx, uint32_t vocab_size);
 
 /* Runs up to n_steps iterations of the loop body Tokenizer.h:557-589:

@@ -388,8 +388,10 @@ __device__ __forceinline__ void pc_sweep(uint32_t *hist, uint32_t *bp) {
 // a wave are contiguous (the LDS reads are bank-conflicted, but this runs once).
 // Two bins per lane and ONE 64-bit atomic for both: the flush is 65,536 x 256 atomic lanes on one 256-KiB table, which the
 // memory side takes at a fixed rate of wave instructions (0.115 ms of a 4 GiB scan's 0.98 ms did not scale with the
-// corpus: most of it this) -- half as many instructions.  (No carry can run from the low bin into the high one: a pair
-// count stays below 2^31, k_table_init checks.)
+// corpus: most of it this) -- half as many instructions.  (A pair that occurs 2^32 times or more wraps its 32-bit bin,
+// and when the add that crosses 2^32 is one of these 64-bit adds on the low bin of a word, the carry adds 1 to the high
+// bin, a pair that may not occur at all.  k_table_init cannot see either: the bins are then small.  k_pair_total does:
+// the 64-bit sum of the bins falls short of the number of pairs scanned by a multiple of 2^32, less 1 per carry.)
 __device__ __forceinline__ void pc_flush(const uint32_t *hist, uint32_t *bp) {
 #if MBPE_PC_FLUSH64
     unsigned long long *bp64 = reinterpret_cast<unsigned long long *>(bp);
@@ -4821,18 +4823,50 @@ __global__ void k_compose_edges(uint32_t *hdr, int rank, int n_ranks, RankEdge *
 
 // Begin of a multi-GPU run: the byte pairs that straddle two ranks' shards
 // are added to the (already all-reduced) byte-pair table by every rank alike.
-__global__ void k_boundary_pairs(uint32_t *bp, const uint32_t *hdr, int n_ranks, uint32_t endbit) {
+// (and their number to pcount[0], the low limb of the pairs the table must hold: k_pair_total)
+__global__ void k_boundary_pairs(uint32_t *bp, const uint32_t *hdr, int n_ranks, uint32_t endbit, uint32_t *pcount) {
     if (blockIdx.x || threadIdx.x) return;
     const RankEdge *all = reinterpret_cast<const RankEdge *>(hdr + 2);
-    uint32_t prev_tail = kHole;
+    uint32_t prev_tail = kHole, credited = 0;
     for (int j = 0; j < n_ranks; ++j) {
         const RankEdge e = all[j];
         if (e.head0 == kHole) continue;            // empty shard
         const bool ends = endbit == kBarrier ? prev_tail == kBarrier : (prev_tail & endbit) != 0u;
-        if (prev_tail != kHole && !ends)
+        if (prev_tail != kHole && !ends) {
             bp[((prev_tail & 0xFFu) << 8) | (e.head0 & 0xFFu)] += 1;
+            ++credited;
+        }
         prev_tail = e.tail0;
     }
+    if (pcount) pcount[0] += credited;
+}
+
+// 64-bit sum of the 65,536 byte-pair bins against the number of pairs that were counted into them: `expect` plus, when
+// `pcount` is given, the value of its four 16-bit limbs (sum_i pcount[i] << 16 i; the limbs of several ranks add up in
+// a u32 all-reduce without a carry).  A bin that wrapped past 2^32 loses a multiple of 2^32 from the sum, a carry of the
+// 64-bit flush (pc_flush) changes it by 1 - 2^32: either way the sum is not the number of pairs.  Mismatch ->
+// kErrCountRange in ctl->err (ctl != NULL); the sum itself -> *sum_out (sum_out != NULL).  One workgroup of 1,024.
+__global__ __launch_bounds__(1024) void k_pair_total(const uint32_t *__restrict__ bp, const uint32_t *pcount,
+                                                      unsigned long long expect, unsigned long long *sum_out, DevCtl *ctl) {
+    __shared__ unsigned long long total;
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    unsigned long long s = 0;
+    for (uint32_t g = threadIdx.x; g < 65536u / 4; g += blockDim.x) {
+        const uint4 v = reinterpret_cast<const uint4 *>(bp)[g];
+        s += (unsigned long long)v.x + v.y + v.z + v.w;
+    }
+    for (int d = kWave / 2; d > 0; d >>= 1) {
+        const uint32_t lo = __shfl_xor((uint32_t)s, d, kWave), hi = __shfl_xor((uint32_t)(s >> 32), d, kWave);
+        s += ((unsigned long long)hi << 32) | lo;
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) atomicAdd(&total, s);
+    __syncthreads();
+    if (threadIdx.x) return;
+    if (pcount)
+        for (int i = 0; i < 4; ++i) expect += (unsigned long long)pcount[i] << (16 * i);
+    if (sum_out) *sum_out = total;
+    if (ctl && total != expect) atomicOr(&ctl->err, kErrCountRange);
 }
 
 inline int blocks_for(uint64_t n, int threads, int max_blocks) {
@@ -5260,8 +5294,13 @@ void launch_compose_edges(hipStream_t s, uint32_t *hdr, int rank, int n_ranks, R
     hipLaunchKernelGGL(k_compose_edges, dim3(1), dim3(64), 0, s, hdr, rank, n_ranks, left, right);
 }
 
-void launch_boundary_pairs(hipStream_t s, uint32_t *bp, const uint32_t *hdr, int n_ranks, uint32_t endbit) {
-    hipLaunchKernelGGL(k_boundary_pairs, dim3(1), dim3(64), 0, s, bp, hdr, n_ranks, endbit);
+void launch_boundary_pairs(hipStream_t s, uint32_t *bp, const uint32_t *hdr, int n_ranks, uint32_t endbit, uint32_t *pcount) {
+    hipLaunchKernelGGL(k_boundary_pairs, dim3(1), dim3(64), 0, s, bp, hdr, n_ranks, endbit, pcount);
+}
+
+void launch_pair_total(hipStream_t s, const uint32_t *bp, const uint32_t *pcount, unsigned long long expect,
+                       unsigned long long *sum_out, DevCtl *ctl) {
+    hipLaunchKernelGGL(k_pair_total, dim3(1), dim3(1024), 0, s, bp, pcount, expect, sum_out, ctl);
 }
 
 }  // namespace mbpe

@@ -234,7 +234,8 @@ __host__ __device__ inline unsigned long long lr_words(uint32_t ids, uint32_t n_
 constexpr uint32_t kErrTableFull   = 1u;
 constexpr uint32_t kErrNegCount    = 2u;
 constexpr uint32_t kErrMissingPair = 4u;
-constexpr uint32_t kErrCountRange  = 8u;   // a pair count does not fit 31 bits (the table keeps a "present" flag in bit 31)
+constexpr uint32_t kErrCountRange  = 8u;   // a pair count does not fit 31 bits (the table keeps a "present" flag in bit 31),
+                                           //   or the byte-pair table does not add up to the pairs counted (k_pair_total)
 constexpr uint32_t kErrHotSkipped  = 16u;  // a pass needed the frequent-pair instantiation of a stream kernel, which the host
                                            //   had ruled out and not launched (kernels.hip: hot_mismatch)
 
@@ -384,8 +385,16 @@ void launch_rank_edge(hipStream_t s, const TileSum *sums, uint32_t n_tiles, Rank
                       uint32_t *hdr);
 // neighbours of this rank's shard from the gathered edges; clears the header
 void launch_compose_edges(hipStream_t s, uint32_t *hdr, int rank, int n_ranks, RankEdge *left, RankEdge *right);
-// begin: pairs straddling rank boundaries -> byte-pair table
-void launch_boundary_pairs(hipStream_t s, uint32_t *bp, const uint32_t *hdr, int n_ranks, uint32_t endbit);
+// the words that follow the header in the begin exchange: the number of pairs counted into the byte-pair table as four
+// 16-bit limbs, one per u32 word, so that the u32 sum over the ranks cannot carry out of a limb
+constexpr uint32_t kPairCountWords = 4;
+// begin: pairs straddling rank boundaries -> byte-pair table, and their number added to pcount[0] (pcount != NULL)
+void launch_boundary_pairs(hipStream_t s, uint32_t *bp, const uint32_t *hdr, int n_ranks, uint32_t endbit,
+                           uint32_t *pcount);
+// 64-bit sum of the byte-pair table against the number of pairs counted (expect + the limbs of pcount, when given):
+// mismatch -> kErrCountRange in ctl->err (ctl != NULL); the sum -> *sum_out (sum_out != NULL)
+void launch_pair_total(hipStream_t s, const uint32_t *bp, const uint32_t *pcount, unsigned long long expect,
+                       unsigned long long *sum_out, DevCtl *ctl);
 
 }  // namespace mbpe
 

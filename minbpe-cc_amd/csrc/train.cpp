@@ -140,7 +140,7 @@ struct mbpe_ctx {
     bool inert = false;          // whole corpus collapses to one token (NUL quirk, basic)
 
     uint32_t *pc_scratch = nullptr;   // pair-count scan: per-workgroup histogram snapshots (kept for the context's life)
-    uint32_t *pc_bp = nullptr;        // mbpe_pair_count_u8: the 65,536-entry result table
+    uint32_t *pc_bp = nullptr;        // mbpe_pair_count_u8: the 65,536-entry result table, then the 64-bit sum of its bins
     void *first_state = nullptr;      // `first` tie-break scratch (training)
     uint32_t *xf = nullptr;           // `first` on a sharded stream: every rank's earliest tied pair (hdr_words, see k_first_publish)
 
@@ -172,7 +172,8 @@ struct mbpe_ctx {
     uint32_t *hdr_m = nullptr, *hdr_adj = nullptr;   // inside xb
     uint32_t *LR = nullptr;               // xb + hdr_words + hdrb_words
     BatchState *bs = nullptr;
-    uint32_t *xb0 = nullptr;              // begin: [bp 65,536][header]
+    uint32_t *xb0 = nullptr;              // begin: [bp 65,536][header][pairs counted: kPairCountWords limbs]
+    uint32_t h_pcount[kPairCountWords] = {};   // (host source of this rank's limbs)
     uint32_t *pair_cells = nullptr;       // byte x byte cell block per pair of a batch (launch_pair_cells_fold), or NULL
     RankEdge *d_left = nullptr, *d_right = nullptr;   // composed neighbours (multi-GPU)
 
@@ -317,9 +318,10 @@ int sync_ctl(mbpe_ctx *c) {
     if (getenv("MBPE_SCAN_DIAG") || getenv("MBPE_MERGE_DIAG") || getenv("MBPE_FUSED_DIAG")) c->h_ctl.err = 0;   // timing-only kernels break the counts
 #endif
     if (c->h_ctl.err) {
-        char buf[200];
+        char buf[320];
         snprintf(buf, sizeof(buf), "device error flags 0x%x (1=pair table full, 2=negative count, 4=missing pair, "
-                                   "8=a pair occurs 2^31 times or more, 16=a stream pass was skipped)",
+                                   "8=a pair occurs 2^31 times or more, or the byte-pair counts do not add up to the "
+                                   "pairs scanned (a count reached 2^32), 16=a stream pass was skipped)",
                  c->h_ctl.err);
         mbpe_host::set_last_error(buf);
         return MBPE_ERR_OVERFLOW;
@@ -706,13 +708,20 @@ int mbpe_load_corpus_ranges(mbpe_ctx *c, const uint8_t *text, uint64_t n_bytes, 
     return mbpe_load_corpus(c, buf.data(), packed, off.data(), n_chunks, 0);
 }
 
+// the number of adjacent pairs the pair-count scan counts: every byte but the last of each chunk (the NUL-inert
+// chunks' bytes are all chunk ends in the mask; a NUL-inert one-chunk corpus is not scanned at all)
+static uint64_t pairs_scanned(const mbpe_ctx *c) {
+    if (c->chunked) return c->n_bytes - c->n_barriers;
+    return c->inert || c->n_bytes < 2 ? 0 : c->n_bytes - 1;
+}
+
 int mbpe_pair_count_u8(mbpe_ctx *c, uint32_t *table65536_out) {
     if (!c) return MBPE_ERR_ARG;
     if (!c->loaded) { mbpe_host::set_last_error("mbpe_pair_count_u8: no corpus loaded"); return MBPE_ERR_STATE; }
     HIPCHK(hipSetDevice(c->device));
     int rcs = ensure_pc_scratch(c);
     if (rcs != MBPE_OK) return rcs;
-    if (!c->pc_bp) HIPCHK(hipMalloc(&c->pc_bp, 65536 * 4));
+    if (!c->pc_bp) HIPCHK(hipMalloc(&c->pc_bp, 65536 * 4 + 16));
     uint32_t *bp = c->pc_bp;
     HIPCHK(hipMemsetAsync(bp, 0, 65536 * 4, c->stream));
     // ("pc_repeat" > 1: that many launches back to back between the two events -- the kernel's sustained duration
@@ -731,10 +740,21 @@ int mbpe_pair_count_u8(mbpe_ctx *c, uint32_t *table65536_out) {
             launch_pair_count_u8(c->stream, c->d_text, c->n_bytes, c->d_endmask, bp, c->n_cus, c->pc_scratch,
                                  c->kev[2 * r], c->kev[2 * r + 1]);
     HIPCHK(hipEventRecord(c->ev1, c->stream));
+    // (a count of 2^32 or more wrapped its bin: the 64-bit sum of the bins is then not the number of pairs scanned.
+    //  Outside ev0..ev1, so that ms_pair_count times the scan alone; not with "pc_repeat" > 1, whose table is a multiple)
+    unsigned long long *sum_dev = reinterpret_cast<unsigned long long *>(bp + 65536);
+    if (reps == 1) launch_pair_total(c->stream, bp, nullptr, 0, sum_dev, nullptr);
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess && table65536_out) e = hipMemcpy(table65536_out, bp, 65536 * 4, hipMemcpyDeviceToHost);
+    unsigned long long sum = 0;
+    if (e == hipSuccess && reps == 1) e = hipMemcpy(&sum, sum_dev, 8, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { mbpe_host::set_last_error(hip_err("pair count", e)); return MBPE_ERR_HIP; }
+    if (reps == 1 && sum != pairs_scanned(c)) {
+        mbpe_host::set_last_error("mbpe_pair_count_u8: the counts add up to " + std::to_string(sum) + " of " +
+                                  std::to_string(pairs_scanned(c)) + " pairs: a pair occurs 2^32 times or more");
+        return MBPE_ERR_OVERFLOW;
+    }
     HIPCHK(hipEventElapsedTime(&c->stats.ms_pair_count, c->ev0, c->ev1));
     c->stats.ms_pair_count /= (float)reps;
     c->stats.ms_pair_count_kernel = 0;
@@ -827,7 +847,7 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size) {
     //  later, larger "max_batch" cannot reach beyond it.  2 x max_batch_eff x lr_pitch(vocab) words: 1.05 GB at the
     //  defaults with vocab 32,000, 262 MB with several ranks or "max_batch" 1024)
     const size_t xb_words = (size_t)c->hdr_words + c->hdrb_words + lr_words(vocab_size, c->max_batch_eff) + 8;
-    const size_t xb0_words = 65536 + (size_t)c->hdr_words;
+    const size_t xb0_words = 65536 + (size_t)c->hdr_words + kPairCountWords;
     HIPCHK(tmalloc(c, &c->xb, xb_words * 4));
     HIPCHK(tmalloc(c, &c->xb0, xb0_words * 4));
     HIPCHK(hipMemsetAsync(c->xb, 0, xb_words * 4, c->stream));
@@ -905,6 +925,9 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size) {
     if (is_multi(c)) {
         uint32_t *hdr = c->xb0 + 65536;
         launch_rank_edge(c->stream, c->sums, c->n_tiles, reinterpret_cast<RankEdge *>(hdr + 2) + c->rank, c->ctl, hdr);
+        const uint64_t p = pairs_scanned(c);
+        for (uint32_t i = 0; i < kPairCountWords; ++i) c->h_pcount[i] = (uint32_t)(p >> (16 * i)) & 0xFFFFu;
+        HIPCHK(hipMemcpyAsync(hdr + c->hdr_words, c->h_pcount, sizeof(c->h_pcount), hipMemcpyHostToDevice, c->stream));
     }
     return MBPE_OK;
 }
@@ -927,10 +950,16 @@ static inline bool first_sharded(const mbpe_ctx *c) { return c->opt_first && is_
 
 static void begin_finish_a(mbpe_ctx *c) {
     const uint32_t endbit = endbit_of(c);
+    // (a pair that occurs 2^32 times or more -- on one GPU, or summed over the ranks by the u32 all-reduce -- leaves a
+    //  small count in its bin, which k_table_init cannot tell from a true one: the bins must add up to the pairs counted,
+    //  the ranks' own ones and the pairs across their boundaries.  Every rank decides on the same reduced data.)
     if (is_multi(c)) {
         uint32_t *hdr = c->xb0 + 65536;
-        launch_boundary_pairs(c->stream, c->xb0, hdr, c->n_ranks, endbit);
+        launch_boundary_pairs(c->stream, c->xb0, hdr, c->n_ranks, endbit, hdr + c->hdr_words);
         launch_compose_edges(c->stream, hdr, c->rank, c->n_ranks, c->d_left, c->d_right);
+        launch_pair_total(c->stream, c->xb0, hdr + c->hdr_words, 0, nullptr, c->ctl);
+    } else {
+        launch_pair_total(c->stream, c->xb0, nullptr, pairs_scanned(c), nullptr, c->ctl);
     }
     launch_table_init(c->stream, c->xb0, c->tab, c->ctl);
     launch_argmax(c->stream, c->tab, c->ctl, c->best, use_hier(c));
@@ -1247,7 +1276,7 @@ int mbpe_train_begin(mbpe_ctx *c, uint32_t vocab_size) {
             c->pending = 1;
             return MBPE_NEED_EXCHANGE;
         }
-        rc = comm_allreduce(c, c->xb0, 65536 + (size_t)c->hdr_words);
+        rc = comm_allreduce(c, c->xb0, 65536 + (size_t)c->hdr_words + kPairCountWords);
         if (rc != MBPE_OK) return rc;
     }
     return begin_finish(c);
@@ -1691,7 +1720,7 @@ int mbpe_train_sequences(mbpe_ctx *c, uint32_t n_sequences, uint32_t *merges_don
 int mbpe_comm_exchange_buffer(mbpe_ctx *c, void **dev_ptr_out, uint64_t *n_u32_out) {
     if (!c || !dev_ptr_out || !n_u32_out) return MBPE_ERR_ARG;
     switch (c->pending) {
-    case 1: *dev_ptr_out = c->xb0; *n_u32_out = 65536 + (uint64_t)c->hdr_words; return MBPE_OK;
+    case 1: *dev_ptr_out = c->xb0; *n_u32_out = 65536 + (uint64_t)c->hdr_words + kPairCountWords; return MBPE_OK;
     case 2: *dev_ptr_out = c->xb; *n_u32_out = step_exchange_words(c); return MBPE_OK;
     case 3:     // deltas of a batch sequence
         *dev_ptr_out = c->xb;

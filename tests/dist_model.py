@@ -21,6 +21,13 @@ def header_words(n_ranks):
     return (2 + 8 * n_ranks + 3) // 4 * 4
 
 
+PAIR_COUNT_WORDS = 4      # begin buffer: [bp 65,536][header][pairs counted, four 16-bit limbs]
+
+
+class PairCountMismatch(Exception):
+    """k_pair_total: the byte-pair bins do not add up to the pairs counted (a count reached 2^32)."""
+
+
 class Shard:
     def __init__(self, data, chunk_off, rank, world, allreduce):
         """data: this rank's bytes; chunk_off: offsets relative to the shard or None."""
@@ -107,14 +114,24 @@ class Shard:
         self.right = (r_h0, r_h1)
 
     # -- begin: pair count, exchange, boundary pairs, table ------------------
+    def pairs_scanned(self):
+        """pairs_scanned (train.cpp): every byte but the last of each chunk, from the length and the chunk ends alone."""
+        t = self.toks
+        if self.chunked:
+            return len(t) - sum(1 for v in t if v & ENDBIT)
+        return max(len(t) - 1, 0)
+
     def begin(self):
-        bp = np.zeros(65536 + self.hdr, dtype=np.int64)
+        bp = np.zeros(65536 + self.hdr + PAIR_COUNT_WORDS, dtype=np.int64)
         t = self.toks
         for i in range(len(t) - 1):
             if not (t[i] & self.endbit):
                 bp[((t[i] & 0xFF) << 8) | (t[i + 1] & 0xFF)] += 1
         base = 65536 + 2 + 8 * self.rank
         bp[base:base + 8] = self.edge()
+        pc = 65536 + self.hdr
+        p = self.pairs_scanned()
+        bp[pc:pc + PAIR_COUNT_WORDS] = [(p >> (16 * i)) & 0xFFFF for i in range(PAIR_COUNT_WORDS)]
         bp = self.allreduce(bp)
         edges = [[int(v) for v in bp[65536 + 2 + 8 * r:65536 + 10 + 8 * r]] for r in range(self.world)]
         prev_tail = HOLE                                   # k_boundary_pairs
@@ -123,7 +140,13 @@ class Shard:
                 continue
             if prev_tail != HOLE and not (prev_tail & self.endbit):
                 bp[((prev_tail & 0xFF) << 8) | (e[0] & 0xFF)] += 1
+                bp[pc] += 1
             prev_tail = e[3]
+        # k_pair_total: the bins add up to the pairs of every shard and across their boundaries
+        self.pair_total = int(bp[:65536].sum())
+        self.pairs_expected = sum(int(bp[pc + i]) << (16 * i) for i in range(PAIR_COUNT_WORDS))
+        if self.pair_total != self.pairs_expected:
+            raise PairCountMismatch("byte-pair table holds %d pairs, %d counted" % (self.pair_total, self.pairs_expected))
         for idx in np.nonzero(bp[:65536])[0]:
             self.table[((int(idx) >> 8) << 16) | (int(idx) & 0xFF)] = int(bp[idx])
         self.compose(edges)
