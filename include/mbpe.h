@@ -22,8 +22,9 @@
  * stream marks "last token of its chunk" with one slot bit; beyond that it keeps a barrier slot
  * after every chunk instead: one more slot per chunk, ids use all 16 bits).  A larger vocab_size
  * (up to MBPE_MAX_VOCAB_WIDE) trains its first merges on the slot stream and the rest on 32-bit
- * tokens with 64-bit pair keys (csrc/wide.h: one merge per pass; lexical tie-break, one GPU --
- * with the `first` tie-break or several ranks such a request still returns MBPE_ERR_VOCAB).
+ * tokens with 64-bit pair keys (csrc/wide.h: one merge per pass, one GPU).  With the `first`
+ * tie-break it does so only when the option "first_wide" is 1 (Tokenizer::train, the CLI and
+ * mbpe_tok_train set it); otherwise, and with several ranks, such a request returns MBPE_ERR_VOCAB.
  */
 #ifndef MBPE_H
 #define MBPE_H
@@ -50,7 +51,8 @@ typedef enum {
     MBPE_ERR_NO_DEVICE = -2,  /* no HIP device / extension unusable */
     MBPE_ERR_HIP       = -3,  /* a HIP runtime call failed */
     MBPE_ERR_VOCAB     = -4,  /* vocab_size beyond MBPE_MAX_VOCAB_WIDE, or beyond the 16-bit slot format where the
-                                 32-bit continuation does not apply (`first` tie-break, several ranks) */
+                                 32-bit continuation does not apply (several ranks; `first` tie-break without the
+                                 option "first_wide") */
     MBPE_ERR_STATE     = -5,  /* call order violated (e.g. steps before begin) */
     MBPE_ERR_OOM       = -6,  /* device or host allocation failed */
     MBPE_ERR_REGEX     = -7,  /* PCRE2 unavailable, compile or match error */
@@ -300,6 +302,10 @@ MBPE_API int mbpe_compact(mbpe_ctx *ctx);
  *                   atomics; read by mbpe_train_begin.  Same results.
  *   "wide_from"     tests: hand over to the 32-bit continuation after this many merges whatever the vocabulary
  *                   (-1, the default: where the 16-bit slot format ends); read by mbpe_train_begin
+ *   "first_wide"    `first` tie-break beyond the 16-bit slot format, one rank: 0 (default) = MBPE_ERR_VOCAB, 1 = the
+ *                   first vocab_size limit - 256 merges on the slot stream, the rest on 32-bit tokens with the same
+ *                   tie-break (earliest first occurrence among the pairs of maximal count), ending when no pair is
+ *                   left; read by mbpe_train_begin.  mbpe_train takes what the context says; Tokenizer::train sets 1
  */
 MBPE_API int mbpe_set_option(mbpe_ctx *ctx, const char *name, int64_t value);
 

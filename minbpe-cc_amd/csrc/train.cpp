@@ -240,6 +240,8 @@ struct mbpe_ctx {
     uint32_t vocab_total = 0;        // the caller's vocab_size (vocab_size is the 16-bit part's)
     uint32_t n_target_total = 0;     // vocab_total - 256
     int64_t opt_wide_from = -1;      // tests: hand over after this many merges whatever the vocabulary (-1: at the format's limit)
+    int64_t opt_first_wide = 0;      // 1: a `first` training may continue on 32-bit tokens too (0: MBPE_ERR_VOCAB, as before)
+    bool wfirst = false;             // the 32-bit loop takes the `first` tie-break (fixed at the conversion)
     uint32_t *wtok[2] = {nullptr, nullptr};
     int wcur = 0;
     uint32_t *wval = nullptr, *wscratch = nullptr;
@@ -247,6 +249,7 @@ struct mbpe_ctx {
     WideCtl *wctl = nullptr;
     WideBest *wbest = nullptr;
     unsigned long long *warg = nullptr;
+    WideFirst *wfs = nullptr;        // `first` tie-break scratch of the 32-bit loop
     uint64_t wn_upper = 0;           // host-side upper bound of the stream length
     uint32_t wk = 0;                 // merges of the wide loop known to the host
     WideCtl h_wctl = {};
@@ -341,7 +344,9 @@ void free_training(mbpe_ctx *c) {
     tfree(c, c->xf);
     tfree(c, c->wtok[0]); tfree(c, c->wtok[1]); tfree(c, c->wval); tfree(c, c->wscratch);
     tfree(c, c->wtab.keys); tfree(c, c->wtab.cnts); tfree(c, c->wctl); tfree(c, c->wbest); tfree(c, c->warg);
+    tfree(c, c->wfs);
     c->wtab = {};
+    c->wfirst = false;
     c->wide_active = false;
     c->wk = 0;
     c->wn_upper = 0;
@@ -560,6 +565,7 @@ int mbpe_set_option(mbpe_ctx *c, const char *name, int64_t value) {
     else if (n == "lockstep") c->opt_lockstep = value < 0 ? -1 : value != 0;
     else if (n == "pair_cells") c->opt_pair_cells = value < 0 ? -1 : value != 0;      // (read by the next mbpe_train_begin)
     else if (n == "wide_from") c->opt_wide_from = value < 0 ? -1 : value;      // (read by the next mbpe_train_begin)
+    else if (n == "first_wide") c->opt_first_wide = value != 0;                // (read by the next mbpe_train_begin)
     else if (n == "pc_repeat") c->opt_pc_repeat = std::min<int64_t>(std::max<int64_t>(1, value), 1000);
     else { mbpe_host::set_last_error("unknown option " + n); return MBPE_ERR_ARG; }
     return MBPE_OK;
@@ -1249,7 +1255,8 @@ int mbpe_train_begin(mbpe_ctx *c, uint32_t vocab_size) {
     const uint32_t vmax = !c->chunked ? MBPE_MAX_VOCAB_BASIC : c->opt_barrier == 0 ? MBPE_MAX_VOCAB_ENDBIT : MBPE_MAX_VOCAB_CHUNKED;
     c->barrier = c->chunked && (c->opt_barrier == 1 || (c->opt_barrier != 0 && vocab_size > MBPE_MAX_VOCAB_ENDBIT));
     // Beyond the 16-bit slot format (Token is a uint32_t in the reference, Tokenizer.h:37-38) the training runs its first
-    // vmax - 256 merges on the slot stream and continues on 32-bit tokens (wide.h): lexical tie-break, one GPU.
+    // vmax - 256 merges on the slot stream and continues on 32-bit tokens (wide.h): one GPU; the `first` tie-break only
+    // when the caller asks for it ("first_wide").
     const uint32_t total = vocab_size;
     c->wide = false;
     if (vocab_size > vmax || (c->opt_wide_from >= 0 && (int64_t)vocab_size - 256 > c->opt_wide_from)) {
@@ -1257,9 +1264,10 @@ int mbpe_train_begin(mbpe_ctx *c, uint32_t vocab_size) {
             mbpe_host::set_last_error("vocab_size exceeds " + std::to_string(MBPE_MAX_VOCAB_WIDE));
             return MBPE_ERR_VOCAB;
         }
-        if (c->opt_first || is_multi(c)) {
+        if ((c->opt_first && !c->opt_first_wide) || is_multi(c)) {
             mbpe_host::set_last_error("vocab_size exceeds the 16-bit slot format (" + std::to_string(vmax) +
-                                      "): the 32-bit continuation is lexical tie-break on one GPU only");
+                                      "): the 32-bit continuation runs on one GPU only, and with the `first` tie-break "
+                                      "only with the option first_wide = 1");
             return MBPE_ERR_VOCAB;
         }
         c->wide = true;
@@ -1436,6 +1444,19 @@ static int train_steps16(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_done_out
 static int wide_convert(mbpe_ctx *c);
 static int wide_steps(mbpe_ctx *c, uint32_t n_steps, uint32_t *done_out);
 
+// `first` mode: did the slot stream's share already end where the reference's loop breaks (no pair left,
+// Tokenizer.h:586-588)?  Then there is nothing to continue: the result is the merges so far, as at a smaller vocabulary.
+static int first_ran_out(mbpe_ctx *c, bool *out) {
+    *out = false;
+    if (!c->opt_first) return MBPE_OK;
+    if (c->n_target < c->vocab_size - 256) { *out = true; return MBPE_OK; }     // (the one-merge loop cut n_target there)
+    if (c->k == 0) return MBPE_OK;
+    unsigned long long last = 0;
+    HIPCHK(hipMemcpy(&last, c->best + (c->k - 1), 8, hipMemcpyDeviceToHost));
+    *out = (last >> 32) == 0;
+    return MBPE_OK;
+}
+
 int mbpe_train_steps(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_done_out) {
     if (steps_done_out) *steps_done_out = 0;
     if (!c) return MBPE_ERR_ARG;
@@ -1449,6 +1470,9 @@ int mbpe_train_steps(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_done_out) {
         int rc = train_steps16(c, n_steps, &done);
         if (steps_done_out) *steps_done_out = done;
         if (rc != MBPE_OK || done >= n_steps || c->exhausted || c->k < c->n_target) return rc;
+        bool out = false;
+        rc = first_ran_out(c, &out);
+        if (rc != MBPE_OK || out) return rc;
         rc = wide_convert(c);
         if (rc != MBPE_OK) return rc;
     }
@@ -1617,6 +1641,13 @@ static int wide_convert(mbpe_ctx *c) {
     HIPCHK(tmalloc(c, &c->wbest, ((size_t)n_wide + 2) * sizeof(WideBest)));
     HIPCHK(tmalloc(c, &c->warg, 2 * 1024 * 8));
     HIPCHK(hipMemsetAsync(c->wctl, 0, sizeof(WideCtl), c->stream));
+    c->wfirst = c->opt_first != 0;
+    if (c->wfirst) {
+        HIPCHK(tmalloc(c, &c->wfs, sizeof(WideFirst)));
+        HIPCHK(hipMemsetAsync(c->wfs, 0, sizeof(WideFirst), c->stream));
+        HIPCHK(hipMemsetAsync(&c->wfs->pos, 0xFF, sizeof(c->wfs->pos), c->stream));
+        HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->wctl->first), 1, 1, c->stream));
+    }
     const uint32_t barrier = c->barrier ? kBarrier : 0xFFFFFFFFu;
     const uint32_t endbit = c->chunked && !c->barrier ? kEndBit : 0u;
     launch_wide_from_slots(c->stream, c->tok[c->cur], n_live_slots, barrier, endbit, c->wval, c->wscratch, c->wtok[0], c->wctl);
@@ -1639,6 +1670,7 @@ static int wide_convert(mbpe_ctx *c) {
     tfree(c, c->tok[0]); tfree(c, c->tok[1]); tfree(c, c->sums); tfree(c, c->side); tfree(c, c->chg); tfree(c, c->tile_list);
     tfree(c, c->offsets); tfree(c, c->run_in); tfree(c, c->xb); tfree(c, c->pair_cells);
     tfree(c, c->tab.hslot); tfree(c, c->tab.ekey); tfree(c, c->tab.ecnt); tfree(c, c->tab.bmax); tfree(c, c->tab.smax);
+    tfree(c, c->first_state);                 // (the slot stream's `first` scratch; the 32-bit loop has its own)
     c->LR = nullptr;
     pool_trim(c);
     return MBPE_OK;
@@ -1667,6 +1699,9 @@ static int wide_steps(mbpe_ctx *c, uint32_t n_steps, uint32_t *done_out) {
         HIPCHK(hipEventRecord(c->ev0, c->stream));
         for (uint32_t g = 0; g < group; ++g) {
             launch_wide_argmax(c->stream, c->wtab, c->wctl, c->wbest, c->warg);
+            if (c->wfirst)
+                launch_wide_first(c->stream, c->wtok[c->wcur ^ (g & 1)], c->wn_upper, c->wtab, c->wctl, c->wbest, c->warg,
+                                  c->wfs);
             launch_wide_merge(c->stream, c->wtok[c->wcur ^ (g & 1)], c->wtok[c->wcur ^ (g & 1) ^ 1], c->wn_upper, c->wval,
                               c->wscratch, c->wtab, c->wctl, 256 + c->n_target);
         }
@@ -1677,7 +1712,9 @@ static int wide_steps(mbpe_ctx *c, uint32_t n_steps, uint32_t *done_out) {
         HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
         c->stats.ms_steps += ms;
         const uint32_t ran = c->h_wctl.k - c->wk;
-        if (ran == 0) break;                    // empty table (Tokenizer.h:586-588): cannot happen after a 16-bit part that merged
+        // empty table (Tokenizer.h:586-588): cannot happen after a 16-bit part that merged -- except in `first` mode, where
+        // it means no pair is left: the loop ends there, with fewer merges than the vocabulary asks for
+        if (ran == 0) break;
         c->h_wbest.resize((size_t)c->wk + ran);
         HIPCHK(hipMemcpy(c->h_wbest.data() + c->wk, c->wbest + c->wk, (size_t)ran * sizeof(WideBest), hipMemcpyDeviceToHost));
         c->wcur ^= (int)(ran & 1u);
@@ -1685,7 +1722,7 @@ static int wide_steps(mbpe_ctx *c, uint32_t n_steps, uint32_t *done_out) {
         c->wk += ran;
         done += ran;
         top = (unsigned long long)std::max(0, c->h_wbest.back().count);
-        if (c->h_wbest.back().count == 0 && done < n_steps && c->wk < n_wide) {
+        if (!c->wfirst && c->h_wbest.back().count == 0 && done < n_steps && c->wk < n_wide) {
             // The best pair no longer occurs anywhere: merging it changes nothing, the reference chooses it again and
             // again (never-erased table, PairCount.h:249-260; the loop only ends on an empty table, Tokenizer.h:586-588)
             const uint32_t fill = std::min<uint32_t>(n_steps - done, n_wide - c->wk);

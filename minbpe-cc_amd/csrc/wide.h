@@ -15,7 +15,19 @@
 //                    value every position contributes to the next stream
 //   k_wide_scatter   the list erase of :237 as a compaction into the other buffer
 //
-// One GPU, lexical tie-break.  Slower per merge than the 16-bit path (one merge per pass, ~20 B of traffic per token),
+// The `first` tie-break (PairCountInsertOrder, PairCount.h:55-181; the table rebuilt before every merge,
+// Tokenizer.h:581-585) adds three kernels between the argmax and the merge, as kernels.hip does on the slot stream:
+//
+//   k_wide_first_gather  how many pairs have the maximal count M; a bitmap of their hashed keys (the slices of the
+//                        table whose argmax partial is below M are skipped)
+//   k_wide_first_pos     only when several do: the smallest 64-bit stream position at which one of them starts -- waves
+//                        walk the 1,024-token spans in ascending order and stop at the first span beyond the best
+//                        position found so far
+//   k_wide_first_pick    the pair at that position replaces the lexical winner
+//
+// and the loop ends at M = 0 (Tokenizer.h:586-588: a rebuilt table holds no zero-count pair).
+//
+// One GPU, either tie-break.  Slower per merge than the 16-bit path (one merge per pass, ~20 B of traffic per token),
 // but it turns MBPE_ERR_VOCAB into a training for GPT-4-size vocabularies.
 #ifndef MBPE_WIDE_H
 #define MBPE_WIDE_H
@@ -50,6 +62,17 @@ struct WideCtl {
     uint32_t matches;              // matches of the merge under way
     uint32_t ran;                  // the merge under way got as far as its scan: its scatter has to run
     unsigned long long n_prev;     // length of the stream the merge under way read
+    uint32_t first;                // 1: `first` tie-break (the argmax ends the loop at count 0)
+    uint32_t pad;
+};
+
+// scratch of the `first` tie-break; pos = ~0, n_tie = 0 and the bitmap all zero between two merges
+constexpr uint32_t kWideFirstBitmapWords = 2048;      // 64 Ki bits
+struct WideFirst {
+    unsigned long long pos;        // stream position of the earliest tied pair found so far, ~0: none
+    uint32_t n_tie;                // pairs whose count is the maximum
+    uint32_t pad;
+    uint32_t bitmap[kWideFirstBitmapWords];
 };
 
 // best[k] of the wide loop: count, first, second
@@ -70,6 +93,10 @@ void launch_wide_table_clear(hipStream_t s, WideTable t);
 void launch_wide_rehash(hipStream_t s, WideTable from, WideTable to, WideCtl *ctl);
 // argmax -> ctl->a, b, count, live and best[ctl->k]; clears ctl->ran
 void launch_wide_argmax(hipStream_t s, WideTable t, WideCtl *ctl, WideBest *best, unsigned long long *scratch /* 3 * 1024 */);
+// `first` mode, after launch_wide_argmax (same scratch): among the pairs of the maximal count the one whose first
+// occurrence in the stream src (ctl->n tokens, at most n_upper) comes first replaces ctl->a, b and best[ctl->k]
+void launch_wide_first(hipStream_t s, const uint32_t *src, uint64_t n_upper, WideTable t, WideCtl *ctl, WideBest *best,
+                       const unsigned long long *scratch, WideFirst *fs);
 // one merge (ctl->a, ctl->b) -> new_id_base + ctl->k over the stream src (ctl->n tokens, at most n_upper) into dst;
 // advances ctl->k, sets ctl->n.  Does nothing when ctl->k >= ctl->k_limit or the table is empty.
 void launch_wide_merge(hipStream_t s, const uint32_t *src, uint32_t *dst, uint64_t n_upper, uint32_t *val,

@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 namespace mbpe {
 namespace {
 
@@ -118,7 +120,9 @@ __global__ __launch_bounds__(kArgBlocks) void k_wide_argmax_final(const unsigned
     Cand128 v = {(long long)part[2 * threadIdx.x], part[2 * threadIdx.x + 1]};
     v = block_best(v, sh);
     if (threadIdx.x == 0) {
-        const bool any = v.count >= 0;         // (a count can never be negative: every decrement undoes an increment)
+        // (a count can never be negative: every decrement undoes an increment.  `first`: a rebuilt table holds no
+        //  zero-count pair, so M = 0 ends the loop, Tokenizer.h:586-588)
+        const bool any = ctl->first ? v.count > 0 : v.count >= 0;
         const unsigned long long key = ~v.nkey;
         ctl->live = any ? 1u : 0u;
         ctl->a = (uint32_t)(key >> 32);
@@ -130,6 +134,112 @@ __global__ __launch_bounds__(kArgBlocks) void k_wide_argmax_final(const unsigned
             best[ctl->k] = wb;
         }
     }
+}
+
+// ---- `first` tie-break (see wide.h) ----------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t first_bit(unsigned long long key) { return wide_hash(key, 48); }   // 16 bits
+
+// count of `key`, or -1 when the pair was never inserted
+__device__ __forceinline__ int32_t wide_lookup(const WideTable &t, unsigned long long key) {
+    uint32_t h = wide_hash(key, t.shift);
+    for (uint32_t probe = 0; probe <= t.mask; ++probe) {
+        const unsigned long long k = t.keys[h];
+        if (k == key) return t.cnts[h];
+        if (k == kWideEmpty) return -1;
+        h = (h + 1) & t.mask;
+    }
+    return -1;
+}
+
+// the grid and stride of k_wide_argmax_partial: block b walks the slice whose maximum is part[2 b]
+__global__ __launch_bounds__(256) void k_wide_first_gather(WideTable t, const WideCtl *ctl,
+                                                           const unsigned long long *__restrict__ part, WideFirst *fs) {
+    if (ctl->k >= ctl->k_limit || !ctl->live) return;
+    const int32_t M = ctl->count;
+    if ((long long)part[2 * blockIdx.x] < (long long)M) return;
+    uint32_t found = 0;
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (; i <= t.mask; i += stride) {
+        if (t.cnts[i] != M) continue;
+        const unsigned long long k = t.keys[i];
+        if (k == kWideEmpty) continue;
+        const uint32_t hb = first_bit(k), bit = 1u << (hb & 31u);
+        // (thousands of tied pairs share 2,048 words: most bits are set already, skip their atomics)
+        if (!(__hip_atomic_load(&fs->bitmap[hb >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit))
+            atomicOr(&fs->bitmap[hb >> 5], bit);
+        ++found;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) found += __shfl_xor(found, d, kWave);
+    if (lane_id() == 0 && found) atomicAdd(&fs->n_tie, found);
+}
+
+constexpr int kPosBlocks = 1024;
+__global__ __launch_bounds__(kThreads) void k_wide_first_pos(const uint32_t *__restrict__ tok, WideTable t,
+                                                             const WideCtl *ctl, WideFirst *fs) {
+    __shared__ uint32_t bm[kWideFirstBitmapWords];
+    if (ctl->k >= ctl->k_limit || !ctl->live) return;
+    if (fs->n_tie <= 1) return;                               // a unique maximum: the lexical winner is it
+    const uint64_t n = ctl->n;
+    const uint64_t n_spans = (n + kWideSpan - 1) / kWideSpan;
+    const uint64_t waves_per_block = kThreads / kWave;
+    const uint64_t n_waves = (uint64_t)gridDim.x * waves_per_block;
+    const uint64_t first_span = (uint64_t)blockIdx.x * waves_per_block;
+    if (first_span >= n_spans) return;
+    const int32_t M = ctl->count;
+    for (uint32_t i = threadIdx.x; i < kWideFirstBitmapWords; i += kThreads) bm[i] = fs->bitmap[i];
+    __syncthreads();
+    const uint32_t lane = lane_id();
+    for (uint64_t span = first_span + threadIdx.x / kWave; span < n_spans; span += n_waves) {
+        const uint64_t base = span * kWideSpan;
+        // spans are visited in ascending order: nothing at or after this one can win any more
+        unsigned long long cur = __hip_atomic_load(&fs->pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        cur = __shfl(cur, 0, kWave);                          // (one decision for the whole wave)
+        if (cur < base) break;
+        bool hit_span = false;
+        for (int it = 0; it < kSpanIters; ++it) {
+            const uint64_t i = base + (uint64_t)it * kWave + lane;
+            const uint32_t tv = i < n ? tok[i] : kWideEnd;
+            // (no holes: the right neighbour of a span's last token is the next span's first)
+            uint32_t nx = __shfl_down(tv, 1, kWave);
+            if (lane == kWave - 1) nx = i + 1 < n ? tok[i + 1] : kWideEnd;
+            bool hit = false;
+            if (i + 1 < n && !(tv & kWideEnd)) {                  // a pair starts here (Tokenizer.h:135-144)
+                const unsigned long long key = ((unsigned long long)tv << 32) | (nx & kWideIdMask);
+                const uint32_t hb = first_bit(key);
+                if ((bm[hb >> 5] >> (hb & 31u)) & 1u) hit = wide_lookup(t, key) == M;
+            }
+            const unsigned long long H = __ballot(hit);
+            if (H) {
+                // lowest lane = earliest position; every later position of this wave lies behind it
+                if (lane == 0) atomicMin(&fs->pos, (unsigned long long)(base + (uint64_t)it * kWave + __builtin_ctzll(H)));
+                hit_span = true;
+                break;
+            }
+        }
+        if (hit_span) break;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_wide_first_pick(const uint32_t *__restrict__ tok, WideCtl *ctl, WideBest *best,
+                                                         WideFirst *fs) {
+    __shared__ uint32_t nt;
+    if (threadIdx.x == 0) {
+        nt = fs->n_tie;
+        const unsigned long long pos = fs->pos;
+        if (ctl->k < ctl->k_limit && ctl->live && nt > 1 && pos != ~0ull) {
+            const uint32_t a = tok[pos], b = tok[pos + 1] & kWideIdMask;      // (a: no end flag, a pair starts there)
+            ctl->a = a;
+            ctl->b = b;
+            WideBest wb = {ctl->count, a, b, 0u};
+            best[ctl->k] = wb;
+        }
+        fs->pos = ~0ull;
+        fs->n_tie = 0;
+    }
+    __syncthreads();
+    if (nt) for (uint32_t i = threadIdx.x; i < kWideFirstBitmapWords; i += blockDim.x) fs->bitmap[i] = 0;
 }
 
 // ---- scans over the spans (one workgroup, two sweeps; as in encode.hip) ---------------------------------------
@@ -390,6 +500,16 @@ void launch_wide_rehash(hipStream_t s, WideTable from, WideTable to, WideCtl *ct
 void launch_wide_argmax(hipStream_t s, WideTable t, WideCtl *ctl, WideBest *best, unsigned long long *scratch) {
     hipLaunchKernelGGL(k_wide_argmax_partial, dim3(kArgBlocks), dim3(256), 0, s, t, ctl, scratch);
     hipLaunchKernelGGL(k_wide_argmax_final, dim3(1), dim3(kArgBlocks), 0, s, scratch, ctl, best);
+}
+
+void launch_wide_first(hipStream_t s, const uint32_t *src, uint64_t n_upper, WideTable t, WideCtl *ctl, WideBest *best,
+                       const unsigned long long *scratch, WideFirst *fs) {
+    hipLaunchKernelGGL(k_wide_first_gather, dim3(kArgBlocks), dim3(256), 0, s, t, ctl, scratch, fs);
+    if (n_upper) {
+        const uint32_t blocks = std::min<uint32_t>(span_grid(n_upper), kPosBlocks);
+        hipLaunchKernelGGL(k_wide_first_pos, dim3(blocks), dim3(kThreads), 0, s, src, t, ctl, fs);
+    }
+    hipLaunchKernelGGL(k_wide_first_pick, dim3(1), dim3(256), 0, s, src, ctl, best, fs);
 }
 
 void launch_wide_merge(hipStream_t s, const uint32_t *src, uint32_t *dst, uint64_t n_upper, uint32_t *val,
