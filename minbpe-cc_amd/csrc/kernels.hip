@@ -1,7 +1,7 @@
 // HIP kernels of the BPE training hot path for gfx950 (MI355X, wave64).
 //
 // Reference path replaced (code/include/ of justinhj/minbpe-cc):
-//   calculate_freqs            Tokenizer.h:127-146   -> k_pair_count_u8 (+ k_table_init)
+//   calculate_freqs            Tokenizer.h:127-146   -> k_pair_count_u8_fast / k_pair_count_u8 (+ k_table_init)
 //   get_top_pair_count         PairCount.h:262-269   -> k_sel_scan + k_sel_pick / k_select_batch
 //                                                       (k_argmax / k_argmax_hier for one merge at a time)
 //   merge_chunks / merge_incremental
@@ -44,16 +44,12 @@ __device__ __forceinline__ uint32_t wave_from_next(uint32_t v, uint32_t edge) {
 __device__ __forceinline__ uint32_t wave_from_prev(uint32_t v, uint32_t edge) {
     return (uint32_t)__builtin_amdgcn_update_dpp((int)edge, (int)v, 0x138, 0xf, 0xf, false);     // wave_shr:1
 }
-// this lane's bit of a wave mask, as a condition (one v_cndmask at the use, no 64-bit lane arithmetic)
-__device__ __forceinline__ bool lane_of(unsigned long long mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
 
 #define MBPE_GLOBAL_AS __attribute__((address_space(1)))
 // The stream's tile loads and the fused pass's tile stores are non-temporal accesses: a pass reads and writes gigabytes
 // once each, and what profits from the caches is the count-delta block its atomics hit at random.  Same box, whole
-// training of the benchmark workload: 76,800 -> 79,100 merges/s, fused pass 5.19 -> 5.01 ms on average (0: plain, A/B).
-#ifndef MBPE_NT_STREAM
-#define MBPE_NT_STREAM 1
-#endif
+// training of the benchmark workload: 76,800 -> 79,100 merges/s, fused pass 5.19 -> 5.01 ms on average (against plain
+// loads and stores).
 // a wave-uniform address, pinned to scalar registers
 __device__ __forceinline__ uintptr_t uniform_ptr(uintptr_t p) {
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p), hi = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
@@ -344,21 +340,9 @@ constexpr int kPcVpl = 2;                  // fast loop: vectors per lane and it
 #endif
 constexpr uint32_t kPcSeg0 = MBPE_PC_SEG0;  // first segment, in fast iterations of 32 Ki pairs
 constexpr uint32_t kPcSegMax = 4096;
-// one-chunk corpora take k_pair_count_u8_fast (0: k_pair_count_u8 for every corpus, A/B)
-#ifndef MBPE_PC_FAST
-#define MBPE_PC_FAST 1
-#endif
-// the final flush adds two bins per 64-bit atomic (0: one 32-bit atomic per bin, A/B)
-#ifndef MBPE_PC_FLUSH64
-#define MBPE_PC_FLUSH64 1
-#endif
 
 __device__ __forceinline__ uint32_t pc_table_index(uint32_t hbin) {
-#ifndef MBPE_PC_NOHASH
     const uint32_t bin = hbin ^ (hbin >> 8);         // undo the bank hash
-#else
-    const uint32_t bin = hbin;
-#endif
     return ((bin & 0xFFu) << 8) | (bin >> 8);        // -> (first << 8) | second
 }
 
@@ -393,7 +377,6 @@ __device__ __forceinline__ void pc_sweep(uint32_t *hist, uint32_t *bp) {
 // bin, a pair that may not occur at all.  k_table_init cannot see either: the bins are then small.  k_pair_total does:
 // the 64-bit sum of the bins falls short of the number of pairs scanned by a multiple of 2^32, less 1 per carry.)
 __device__ __forceinline__ void pc_flush(const uint32_t *hist, uint32_t *bp) {
-#if MBPE_PC_FLUSH64
     unsigned long long *bp64 = reinterpret_cast<unsigned long long *>(bp);
     for (uint32_t o2 = threadIdx.x; o2 < 32768u; o2 += kPcThreads) {
         unsigned long long v = 0;
@@ -401,24 +384,12 @@ __device__ __forceinline__ void pc_flush(const uint32_t *hist, uint32_t *bp) {
         for (uint32_t h = 0; h < 2; ++h) {
             const uint32_t o = 2u * o2 + h;
             uint32_t bin = ((o & 0xFFu) << 8) | (o >> 8);
-#ifndef MBPE_PC_NOHASH
             bin ^= bin >> 8;
-#endif
             const uint32_t c = (hist[bin & 0x7FFFu] >> ((bin >> 15) * 16)) & 0xFFFFu;
             v |= (unsigned long long)c << (32u * h);
         }
         if (v) atomicAdd(&bp64[o2], v);
     }
-#else
-    for (uint32_t o = threadIdx.x; o < 65536u; o += kPcThreads) {
-        uint32_t bin = ((o & 0xFFu) << 8) | (o >> 8);
-#ifndef MBPE_PC_NOHASH
-        bin ^= bin >> 8;
-#endif
-        const uint32_t c = (hist[bin & 0x7FFFu] >> ((bin >> 15) * 16)) & 0xFFFFu;
-        if (c) atomicAdd(&bp[o], c);
-    }
-#endif
 }
 
 // workgroup-wide: decoded sum of all counters + `issued` summed over the threads, and the largest counter
@@ -534,24 +505,10 @@ __device__ __forceinline__ uint32_t pc_count_range(uint32_t *hist, uint32_t *__r
             const uint32_t w[5] = {cq[u].x, cq[u].y, cq[u].z, cq[u].w, nb};
             if (__ballot(valid != 0xFFFFu) == 0ull) {
                 // every pair of every lane counts: no per-pair predicate
-#if !defined(MBPE_PC_NOHASH) && !defined(MBPE_PC_PLAIN)
                 uint32_t k0xffff;
                 asm volatile("s_mov_b32 %0, 0xffff" : "=s"(k0xffff));
 #pragma unroll
                 for (int i = 0; i < 4; ++i) pc_lean_pairs(hist, w[i], w[i + 1], k0xffff);
-#else
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int wi = i >> 2, sh = 8 * (i & 3);
-                    uint32_t bin;
-                    if (sh <= 16) bin = (w[wi] >> sh) & 0xFFFFu;
-                    else bin = ((w[wi] >> 24) | (w[wi + 1] << 8)) & 0xFFFFu;
-#ifndef MBPE_PC_NOHASH
-                    bin ^= bin >> 8;
-#endif
-                    atomicAdd(&hist[bin & 0x7FFFu], 1u + (bin >> 15) * 0xFFFFu);
-                }
-#endif
             } else {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
@@ -559,9 +516,7 @@ __device__ __forceinline__ uint32_t pc_count_range(uint32_t *hist, uint32_t *__r
                     uint32_t bin;
                     if (sh <= 16) bin = (w[wi] >> sh) & 0xFFFFu;
                     else bin = ((w[wi] >> 24) | (w[wi + 1] << 8)) & 0xFFFFu;
-#ifndef MBPE_PC_NOHASH
                     bin ^= bin >> 8;
-#endif
                     const uint32_t inc = ((valid >> i) & 1u) ? 1u + (bin >> 15) * 0xFFFFu : 0u;   // invalid: add 0
                     atomicAdd(&hist[bin & 0x7FFFu], inc);
                 }
@@ -577,6 +532,7 @@ __device__ __forceinline__ uint32_t pc_count_range(uint32_t *hist, uint32_t *__r
     return issued;
 }
 
+// (chunked corpora only: one-chunk corpora take k_pair_count_u8_fast, so only MASKED = true is launched)
 template <bool MASKED>
 __global__ __launch_bounds__(kPcThreads) void k_pair_count_u8(const uint8_t *__restrict__ text, uint64_t n,
                                                               const uint8_t *__restrict__ endmask,
@@ -1652,11 +1608,7 @@ __device__ __forceinline__ TileIn tile_issue(const uint16_t *tok, __amdgpu_buffe
     // (uniform 64-bit base + 32-bit lane offset: the address then needs one VGPR, not a pair per buffer)
     const MBPE_GLOBAL_AS char *base =
         (const MBPE_GLOBAL_AS char *)uniform_ptr(reinterpret_cast<uintptr_t>(tok) + (uint64_t)tile * (kWave * 16u));
-#if MBPE_NT_STREAM
     const u32x4 q = __builtin_nontemporal_load((const MBPE_GLOBAL_AS u32x4 *)(base + lane * 16u));
-#else
-    const u32x4 q = *(const MBPE_GLOBAL_AS u32x4 *)(base + lane * 16u);
-#endif
     t.q = make_uint4(q.x, q.y, q.z, q.w);
     const uint32_t j = tile + (lane >> 2) - 1u;                // tile 0, lanes 0..3 wrap to 0xFFFFFFFF
     const uint32_t off = (lane < 12 && j < 0x0FFFFFFFu) ? j * 16u + (lane & 3u) * 4u : 0xFFFFFFF0u;
@@ -2034,24 +1986,21 @@ __global__ void k_apply(PairTable t, DevCtl *ctl, const unsigned long long *__re
 #ifndef MBPE_PRED_NUM
 #define MBPE_PRED_NUM 4      /* quarters of the measured per-dependency loss that the prediction counts on */
 #endif
-#ifndef MBPE_LUT_KEYS
-#define MBPE_LUT_KEYS 2
-#endif
-constexpr uint32_t kBucketKeys = MBPE_LUT_KEYS;          // keys per bucket: 2 (one 8-byte read), 3 (8 + 4 bytes) or 4 (16 bytes)
+constexpr uint32_t kBucketKeys = 2;          // keys per bucket: one 8-byte read
 #ifndef MBPE_LUT_BUCKETS
-#define MBPE_LUT_BUCKETS (MBPE_LUT_KEYS == 4 ? 4096 : 8192)
+#define MBPE_LUT_BUCKETS 8192
 #endif
 constexpr uint32_t kBuckets = MBPE_LUT_BUCKETS;
 static_assert((kBuckets & (kBuckets - 1u)) == 0, "the hash is masked");
 constexpr uint32_t kEmptyPair = 0xFFFEFFFEu;
-static_assert(kBucketKeys >= 2 && kBucketKeys <= 4, "bucket = an 8-byte, an 8- and a 4-byte, or a 16-byte LDS read");
 
 static_assert(kBatchMax <= 65536, "batch indices are stored in 16 bits");
 // 8192 buckets of two keys.  A batch ends when some bucket would need a third key under every hash multiplier still in
-// the race (expected overflowing buckets n^3 / (6 B^2): near 1,400 pairs with eight multipliers).  MBPE_LUT_KEYS 3 (a
-// second, 4-byte read per test: 144 KB of LDS, batches of 2,048 pairs with -DMBPE_BATCH_MAX=2048) was built and measured
+// the race (expected overflowing buckets n^3 / (6 B^2): near 1,400 pairs with eight multipliers).  Three keys per bucket (a
+// second, 4-byte read per test: 144 KB of LDS, batches of 2,048 pairs with -DMBPE_BATCH_MAX=2048) were built and measured
 // in round 3: the fused pass went from 8.3 to 10.5 ms at the same batch size -- every LDS read in the per-slot path costs
-// as much as eight vector instructions -- which the 7 passes it saved (83 -> 76) do not pay back.
+// as much as eight vector instructions -- which the 7 passes it saved (83 -> 76) do not pay back.  Four keys in 16-byte
+// buckets (round 2): 4.1 -> 6.0 ms, the wide random LDS reads conflict.
 // The other form of the table, for batches whose pairs are all pairs of raw bytes (BatchState::byte_lut): the batch index
 // of (first, second) at [first][second], 0xFFFF where there is none -- ONE 2-byte LDS read per test, no hash, no key
 // compare, no limit on the batch but kBatchMax.  Row 256 and the last column are all 0xFFFF: a first token that is no byte
@@ -2061,24 +2010,14 @@ static_assert(kBatchMax <= 65536, "batch indices are stored in 16 bits");
 constexpr uint32_t kByteCols = 256u + (uint32_t)kTTMax + 1u;         // 273: bytes, stand-ins, "no"
 constexpr uint32_t kByteRows = 257u;
 struct BatchLutHash {
-#if MBPE_LUT_KEYS == 2
     uint2 bucket[kBuckets];
     uint32_t bidx[kBuckets];     // batch index of bucket.x (low half) and bucket.y (high half)
-#elif MBPE_LUT_KEYS == 3
-    uint2 bucket[kBuckets];      // keys 0 and 1
-    uint32_t bucket2[kBuckets];  // key 2
-    uint32_t bidx[kBuckets];     // batch index of bucket.x (low half) and bucket.y (high half)
-    uint16_t bidx2[kBuckets];    // ... of bucket2
-#else
-    uint4 bucket[kBuckets];
-    uint2 bidx[kBuckets];        // batch indices of bucket.x .. bucket.w, 16 bits each
-#endif
 };
 struct BatchLutMem : BatchLutHash {             // (in LDS, one per workgroup: the hash form, or -- over the same bytes -- the byte form)
-    uint16_t byte_tail[kByteTable && kByteRows * kByteCols > sizeof(BatchLutHash) / 2 ? kByteRows * kByteCols - sizeof(BatchLutHash) / 2 : 1];
+    uint16_t byte_tail[kByteRows * kByteCols > sizeof(BatchLutHash) / 2 ? kByteRows * kByteCols - sizeof(BatchLutHash) / 2 : 1];
     __device__ __forceinline__ uint16_t *byte_tab() { return reinterpret_cast<uint16_t *>(this); }
 };
-static_assert(!kByteTable || sizeof(BatchLutMem) >= kByteRows * kByteCols * 2, "the byte table overlays the hash table");
+static_assert(sizeof(BatchLutMem) >= kByteRows * kByteCols * 2, "the byte table overlays the hash table");
 // The hash of a batch's table is second * mul + first (one v_mad_u32_u24), masked; mul is chosen per batch by the
 // selection among kHashMul so that no bucket needs a third key for as long as possible (BatchState::hash_mul) and
 // reaches the stream kernels in a scalar register.
@@ -2094,7 +2033,7 @@ struct BatchLut {
     bool bytes;                  // uniform: the byte form
     uint32_t idmask;             // 0x7FFF with chunk-end bits in the slots, else 0xFFFF (where the stand-in ids lie)
     __device__ __forceinline__ BatchLut(BatchLutMem *mem, const BatchState *bs, uint32_t idmask_)
-        : m(mem), mul(rfl(bs->hash_mul)), bytes(kByteTable && rfl(bs->byte_lut) != 0u), idmask(idmask_) {}
+        : m(mem), mul(rfl(bs->hash_mul)), bytes(rfl(bs->byte_lut) != 0u), idmask(idmask_) {}
 };
 
 // byte form: the table entry of (first, second); first: any raw slot value, second: a token id (or kHole)
@@ -2186,13 +2125,9 @@ __device__ __forceinline__ void lut_build(BatchLut &lut, const BatchState *bs, u
         return;
     }
     uint32_t *words = reinterpret_cast<uint32_t *>(lut.m->bucket);
-    constexpr uint32_t kMainKeys = kBucketKeys == 3 ? 2u : kBucketKeys;      // keys per bucket in `bucket`
-    for (uint32_t i = threadIdx.x; i < kBuckets * kMainKeys; i += blockDim.x) words[i] = kEmptyPair;
+    for (uint32_t i = threadIdx.x; i < kBuckets * kBucketKeys; i += blockDim.x) words[i] = kEmptyPair;
     uint32_t *iw = reinterpret_cast<uint32_t *>(lut.m->bidx);
-    for (uint32_t i = threadIdx.x; i < kBuckets * kMainKeys / 2; i += blockDim.x) iw[i] = 0;
-#if MBPE_LUT_KEYS == 3
-    for (uint32_t i = threadIdx.x; i < kBuckets; i += blockDim.x) { lut.m->bucket2[i] = kEmptyPair; lut.m->bidx2[i] = 0; }
-#endif
+    for (uint32_t i = threadIdx.x; i < kBuckets * kBucketKeys / 2; i += blockDim.x) iw[i] = 0;
     __syncthreads();
     if (threadIdx.x == 0) {
         uint32_t n_tt = 0;
@@ -2204,15 +2139,8 @@ __device__ __forceinline__ void lut_build(BatchLut &lut, const BatchState *bs, u
             const uint32_t h = pair_hash(lut.mul, a, b);
             const uint32_t kk = a | (b << 16);
             uint32_t r = 0;                       // first free key of the bucket (selection keeps it within kBucketKeys)
-            while (r + 1 < kMainKeys && words[h * kMainKeys + r] != kEmptyPair) ++r;
-#if MBPE_LUT_KEYS == 3
-            if (words[h * kMainKeys + r] != kEmptyPair) {      // both taken: the bucket's third key
-                lut.m->bucket2[h] = kk;
-                lut.m->bidx2[h] = (uint16_t)j;
-                continue;
-            }
-#endif
-            words[h * kMainKeys + r] = kk;
+            while (r + 1 < kBucketKeys && words[h * kBucketKeys + r] != kEmptyPair) ++r;
+            words[h * kBucketKeys + r] = kk;
             uint16_t *ix = reinterpret_cast<uint16_t *>(&lut.m->bidx[h]);
             ix[r] = (uint16_t)j;
         }
@@ -2220,111 +2148,24 @@ __device__ __forceinline__ void lut_build(BatchLut &lut, const BatchState *bs, u
     __syncthreads();
 }
 
-// is (first, second) a batch pair?  first may be any raw slot value (a hole or a
-// token with the chunk-end bit never matches), second the id of the next live token
-__device__ __forceinline__ bool pair_test(const BatchLut &lut, uint32_t first, uint32_t second) {
-    if (lut.bytes) return byte_entry<true>(lut, first, second, lut.idmask) != 0xFFFFu;
-    const uint32_t hh = pair_hash_u(lut.mul, first, second);
-    const auto bk = lut.m->bucket[hh];
-    const uint32_t kk = first | (second << 16);
-#if MBPE_LUT_KEYS == 2
-    return bk.x == kk || bk.y == kk;
-#elif MBPE_LUT_KEYS == 3
-    return bk.x == kk || bk.y == kk || lut.m->bucket2[hh] == kk;
-#else
-    return bk.x == kk || bk.y == kk || bk.z == kk || bk.w == kk;
-#endif
-}
-
-// The same test in the streaming loops, written so that it costs few VALU instructions:
-// hash with one v_mad_u32_u24, no boolean materialised.  Returns 0 iff (first, second) is a
-// batch pair, something non-zero otherwise.
-__device__ __forceinline__ uint32_t pair_miss(const BatchLut &lut, uint32_t first, uint32_t second) {
-    if (lut.bytes) return byte_entry<true>(lut, first, second, lut.idmask) ^ 0xFFFFu ? 0u : 1u;
-    uint32_t h;
-    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(h) : "v"(second), "s"(lut.mul), "v"(first));
-    const auto bk = lut.m->bucket[h & (kBuckets - 1u)];
-    const uint32_t kk = first | (second << 16);
-    const uint32_t dx = bk.x ^ kk, dy = bk.y ^ kk;
-    uint32_t d = dx < dy ? dx : dy;
-#if MBPE_LUT_KEYS == 3
-    const uint32_t dz = lut.m->bucket2[h & (kBuckets - 1u)] ^ kk;
-    d = d < dz ? d : dz;
-#endif
-#if MBPE_LUT_KEYS == 4
-    const uint32_t dz = bk.z ^ kk, dw = bk.w ^ kk;
-    const uint32_t e = dz < dw ? dz : dw;
-    d = d < e ? d : e;
-#endif
-    return d;
-}
-
-// ... and as a per-lane boolean, which the compiler keeps as a wave mask in scalar registers: one
-// compare per key, and the results combine on the scalar unit.
-__device__ __forceinline__ bool pair_hit(const BatchLut &lut, uint32_t first, uint32_t second) {
-    if (lut.bytes) return byte_entry<true>(lut, first, second, lut.idmask) != 0xFFFFu;
-    uint32_t h;
-    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(h) : "v"(second), "s"(lut.mul), "v"(first));
-    const auto bk = lut.m->bucket[h & (kBuckets - 1u)];
-    const uint32_t kk = first | (second << 16);
-#if MBPE_LUT_KEYS == 2
-    return bk.x == kk || bk.y == kk;
-#elif MBPE_LUT_KEYS == 3
-    return bk.x == kk || bk.y == kk || lut.m->bucket2[h & (kBuckets - 1u)] == kk;
-#else
-    return bk.x == kk || bk.y == kk || bk.z == kk || bk.w == kk;
-#endif
-}
-
-// ... and which of the bucket's keys matched (two-key buckets): the pair index is then ONE more LDS read (the bucket's
-// index word) instead of two -- an LDS read in the per-slot path costs as much as eight vector instructions.
+// Hash form: is (first, second) a batch pair, and which of the bucket's two keys matched?  first may be any raw slot value
+// (a hole or a token with the chunk-end bit never matches), second the id of the next live token.  Knowing the key, the
+// pair index is then ONE more LDS read (the bucket's index word) instead of two -- an LDS read in the per-slot path
+// costs as much as eight vector instructions.  The hash is one v_mad_u32_u24 with the multiplier in a scalar register.
 __device__ __forceinline__ bool pair_hit2(const BatchLut &lut, uint32_t first, uint32_t second, bool &second_key) {
     uint32_t h;
     asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(h) : "v"(second), "s"(lut.mul), "v"(first));
     const auto bk = lut.m->bucket[h & (kBuckets - 1u)];
     const uint32_t kk = first | (second << 16);
     second_key = bk.y == kk;
-#if MBPE_LUT_KEYS == 2
     return bk.x == kk || second_key;
-#elif MBPE_LUT_KEYS == 3
-    return bk.x == kk || second_key || lut.m->bucket2[h & (kBuckets - 1u)] == kk;
-#else
-    return bk.x == kk || second_key || bk.z == kk || bk.w == kk;
-#endif
-}
-
-// index of the pair (only called for pairs that passed pair_test)
-__device__ __forceinline__ int lut_index(const BatchLut &lut, uint32_t first, uint32_t second) {
-    if (lut.bytes) return (int)byte_entry<true>(lut, first, second, lut.idmask);
-    const uint32_t h = pair_hash_u(lut.mul, first, second);
-    const uint32_t kk = first | (second << 16);
-#if MBPE_LUT_KEYS == 2
-    const uint32_t ix = lut.m->bidx[h];
-    return (int)(lut.m->bucket[h].x == kk ? ix & 0xFFFFu : ix >> 16);
-#elif MBPE_LUT_KEYS == 3
-    // (a pair that is in the table and is neither of the first two keys of its bucket is the third)
-    const uint32_t ix = lut.m->bidx[h];
-    const uint32_t i3 = lut.m->bidx2[h];
-    const uint2 bk = lut.m->bucket[h];
-    return (int)(bk.x == kk ? ix & 0xFFFFu : bk.y == kk ? ix >> 16 : i3);
-#else
-    const uint4 bk = lut.m->bucket[h];
-    const uint2 i2 = lut.m->bidx[h];
-    const uint32_t w = (bk.x == kk || bk.y == kk) ? i2.x : i2.y;
-    return (int)((bk.x == kk || bk.z == kk) ? w & 0xFFFFu : w >> 16);
-#endif
 }
 
 // the same when the membership test has already told which key of the bucket matched (pair_hit2)
 __device__ __forceinline__ uint32_t lut_index_known(const BatchLut &lut, uint32_t first, uint32_t second, bool second_key) {
     if (lut.bytes) return byte_entry<true>(lut, first, second, lut.idmask);
-#if MBPE_LUT_KEYS == 2
     const uint32_t ix = lut.m->bidx[pair_hash_u(lut.mul, first, second)];
     return second_key ? ix >> 16 : ix & 0xFFFFu;
-#else
-    (void)second_key;
-    return (uint32_t)lut_index(lut, first, second);
-#endif
 }
 
 // Which pass merges a multi-pair batch: the fused one (reads the stream once, writes all of it to
@@ -2590,7 +2431,7 @@ __global__ __launch_bounds__(kPickThreads) void k_sel_pick(DevCtl *ctl, BatchSta
     // multipliers still in the race (small packed counters)
     __shared__ uint32_t set_first[2048], set_second[2048];
     __shared__ uint32_t g_first[8], g_second[8];      // the same for the 64 candidates of a bulk step (raw bytes only)
-    constexpr uint32_t kFillBits = kBucketKeys <= 3 ? 2 : 4, kFillPerWord = 32 / kFillBits;
+    constexpr uint32_t kFillBits = 2, kFillPerWord = 32 / kFillBits;      // (counts up to kBucketKeys + 1)
     __shared__ uint32_t bucket_fill[kHashSeeds][kBuckets / kFillPerWord];
     __shared__ uint16_t acc_ci[kBatchMax];         // list position of every accepted member (written out after the walk)
     const uint32_t tid = threadIdx.x;
@@ -2700,7 +2541,7 @@ __global__ __launch_bounds__(kPickThreads) void k_sel_pick(DevCtl *ctl, BatchSta
         uint32_t alive = (1u << kHashSeeds) - 1u;   // hash multipliers under which every bucket still holds its keys
         // every member so far is a pair of raw bytes (a (t,t) member: its token is): such a batch is looked up in the direct
         // byte x byte table and needs no room in the hash buckets (BatchState::byte_lut)
-        bool all_bytes = kByteTable && byte_table != 0u;
+        bool all_bytes = byte_table != 0u;
         uint32_t tracked = 0, tracked_tt = 0;       // members (and (t,t) members among them) the bucket fills know
         if (tid == 0) bs->tt_index = kNoTT;
         unsigned long long cand_next = n_l ? sp[0] : 0ull;         // (the next candidate is read one step ahead)
@@ -2873,15 +2714,6 @@ __global__ __launch_bounds__(kPickThreads) void k_sel_pick(DevCtl *ctl, BatchSta
             if (cut == 0u && accepted == limit) ctl->cut_full += 1;
             // next threshold: about 128 candidates beyond this batch, or a window twice as wide
             // when the list ended before the batch was full
-#ifndef MBPE_SEL_WINDOW
-#define MBPE_SEL_WINDOW 1
-#endif
-#ifndef MBPE_SEL_AIM_NEXT
-#define MBPE_SEL_AIM_NEXT 0      /* eighths of the list that the entries BEHIND a batch may fill (0: three quarters, batch included) */
-#endif
-#ifndef MBPE_SEL_NEXT_LIMIT
-#define MBPE_SEL_NEXT_LIMIT 1
-#endif
 #ifndef MBPE_SEL_TINY
 #define MBPE_SEL_TINY 64
 #endif
@@ -2894,7 +2726,6 @@ __global__ __launch_bounds__(kPickThreads) void k_sel_pick(DevCtl *ctl, BatchSta
 #ifndef MBPE_SEL_AHEAD
 #define MBPE_SEL_AHEAD 2        /* halves of the batch-size limit that the next candidate list should reach beyond a batch */
 #endif
-#if MBPE_SEL_WINDOW
             // the window follows the batches that are being chosen (eight times their running mean, at least 256), not only
             // the limit: on text a sequence takes a few dozen pairs and a list of thousands is sorted for nothing
             const uint32_t recent = (3u * ctl->recent_n + accepted + 3u) / 4u;
@@ -2902,13 +2733,8 @@ __global__ __launch_bounds__(kPickThreads) void k_sel_pick(DevCtl *ctl, BatchSta
             const uint32_t wide = MBPE_SEL_WINDOW_MUL * recent < MBPE_SEL_WINDOW_MIN ? MBPE_SEL_WINDOW_MIN : MBPE_SEL_WINDOW_MUL * recent;
             // (a batch that filled its limit doubles it -- k_seq_finish -- so the next batch may be twice as large)
             uint32_t adapt_next = adapt;
-#if MBPE_SEL_NEXT_LIMIT
             if (cut == 0u && accepted == limit && 2u * adapt_next <= max_batch) adapt_next *= 2u;
-#endif
             const uint32_t adapt_w = adapt_next < wide ? adapt_next : wide;
-#else
-            const uint32_t adapt_w = adapt;
-#endif
             const uint32_t want = ci + ((uint32_t)MBPE_SEL_AHEAD * (adapt_w < 16u ? 16u : adapt_w)) / 2u;
             if (n_l > want) {
                 ctl->sel_T = sp[want];          // (the full packed value: also cuts inside a run of equal counts)
@@ -2925,15 +2751,8 @@ __global__ __launch_bounds__(kPickThreads) void k_sel_pick(DevCtl *ctl, BatchSta
                     // every selection through the overflow path): extend by what that density needs
                     // (aiming at a list of want + adapt entries, but never at more than three quarters of what the list
                     //  holds: an overflowing gather costs two more scans and a worse threshold)
-#if MBPE_SEL_AIM_NEXT
-                    // (what this batch took is gone from the next list: the bound is on what comes BEHIND it)
-                    unsigned long long aim_next = (unsigned long long)(want - ci) + adapt_w;
-                    if (aim_next > (unsigned long long)MBPE_SEL_AIM_NEXT * sel_cap / 8ull) aim_next = (unsigned long long)MBPE_SEL_AIM_NEXT * sel_cap / 8ull;
-                    const unsigned long long aim = (unsigned long long)ci + aim_next;
-#else
                     unsigned long long aim = (unsigned long long)want + adapt_w;
                     if (aim > 3ull * sel_cap / 4ull) aim = 3ull * sel_cap / 4ull;
-#endif
                     const unsigned long long need = aim > (unsigned long long)n_l + 64ull ? aim - n_l : 64ull;
                     spread = (spread * need + n_l - 1) / n_l;
                     if (spread < 1) spread = 1;
@@ -3083,119 +2902,6 @@ __device__ __forceinline__ bool tt_needed(const uint32_t s[8], const uint32_t nx
     return __ballot(need) != 0ull || hneed;
 }
 
-// exact neighbours of every slot, two deep on both sides (shared by the scan
-// and rewrite passes of a batch)
-struct Neigh {
-    uint32_t p1_in, p2_in;      // live tokens before this lane's first slot
-    uint32_t n1v[8], n2v[8];    // next / second-next live token of every slot
-};
-
-__device__ __forceinline__ Neigh tile_neighbours(const uint32_t s[8], const Halo &h) {
-    const uint32_t lane = lane_id();
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    const unsigned long long gt_mask = lane == 63 ? 0ull : ~((2ull << lane) - 1ull);
-    uint32_t cnt = 0, f1 = kSent, f2 = kSent, l1 = kSent, l2 = kSent;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        if (s[j] != kHole) {
-            if (cnt == 0) f1 = s[j]; else if (cnt == 1) f2 = s[j];
-            l2 = l1; l1 = s[j];
-            ++cnt;
-        }
-    }
-    const unsigned long long m_live = __ballot(cnt > 0);
-    Neigh nb;
-    {
-        const unsigned long long lo = m_live & lt_mask;
-        const uint32_t src1 = lo ? 63u - (uint32_t)__builtin_clzll(lo) : lane;
-        const uint32_t sl1 = __shfl(l1, src1, kWave), sl2 = __shfl(l2, src1, kWave);
-        const unsigned long long lo2 = lo & ~(1ull << src1);
-        const uint32_t src2 = lo2 ? 63u - (uint32_t)__builtin_clzll(lo2) : lane;
-        const uint32_t tl1 = __shfl(l1, src2, kWave);
-        nb.p1_in = lo ? sl1 : h.p1;
-        nb.p2_in = lo ? (sl2 != kSent ? sl2 : (lo2 ? tl1 : h.p1)) : h.p2;
-    }
-    uint32_t n1_in, n2_in;
-    {
-        const unsigned long long hi = m_live & gt_mask;
-        const uint32_t src1 = hi ? (uint32_t)__builtin_ctzll(hi) : lane;
-        const uint32_t sf1 = __shfl(f1, src1, kWave), sf2 = __shfl(f2, src1, kWave);
-        const unsigned long long hi2 = hi & ~(1ull << src1);
-        const uint32_t src2 = hi2 ? (uint32_t)__builtin_ctzll(hi2) : lane;
-        const uint32_t tf1 = __shfl(f1, src2, kWave);
-        n1_in = hi ? sf1 : h.n1;
-        n2_in = hi ? (sf2 != kSent ? sf2 : (hi2 ? tf1 : h.n1)) : h.n2;
-    }
-    uint32_t x1 = n1_in, x2 = n2_in;
-#pragma unroll
-    for (int j = 7; j >= 0; --j) {
-        nb.n1v[j] = x1;
-        nb.n2v[j] = x2;
-        if (s[j] != kHole) { x2 = x1; x1 = s[j]; }
-    }
-    return nb;
-}
-
-// The counting half of a multi-pair merge on one tile: deltas per pair and the
-// tile's mark.  Nothing is rewritten.  Batch pairs cannot overlap (no token is
-// both a first and a second element), so "this token is the second of a match"
-// is simply "the previous live token started a match": one membership test per
-// live slot, everything else only where a match is.
-template <int MODE, int DIAG = 0>
-__device__ __forceinline__ void scan_tile_full(uint32_t *chg, uint32_t tile, const uint32_t s[8], const Halo h,
-                                               const BatchLut &lut, uint32_t n_keys, uint32_t *hdr_adj,
-                                               uint32_t *LR, uint32_t pitch, DeltaCache &dc, bool dc_on, bool tt_on,
-                                               TTInfo &ti, uint32_t adj_pitch) {
-    constexpr uint32_t idmask = MODE == 1 ? 0x7FFFu : 0xFFFFu;
-    constexpr uint32_t endbit = MODE == 1 ? kEndBit : 0u;
-    const Neigh nb = tile_neighbours(s, h);
-    if (DIAG == 4) {
-        asm volatile("" :: "v"(nb.p1_in), "v"(nb.p2_in));
-#pragma unroll
-        for (int j = 0; j < 8; ++j) asm volatile("" :: "v"(nb.n1v[j]), "v"(nb.n2v[j]));
-        if (lane_id() == 0) atomicOr(&chg[tile >> 5], 1u << (tile & 31u));
-        return;
-    }
-    bool any = false;
-    uint32_t p1 = nb.p1_in, p2 = nb.p2_in;
-    bool a1 = false;       // p1 started a match (so the current token is its second element)
-    bool first = true;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint32_t self = s[j];
-        if (self == kHole) continue;
-        const uint32_t n1 = nb.n1v[j], n2 = nb.n2v[j];
-        if (first) { a1 = p1 != kHole && pair_test(lut, p1, self & idmask); first = false; }
-        bool is_a = false;
-        if (a1) {                                        // second token of a match of pair (p1, self)
-            any = true;
-            if (right_open<MODE>(self, n1) && !pair_test(lut, n1, n2 & idmask)) {
-                const int jb = lut_index(lut, p1, self & idmask);
-                if (DIAG != 3) dc_add(dc, dc_on, LR, lr_idx(pitch, n1 & idmask, (uint32_t)jb, 1), 1u);
-                else asm volatile("" :: "v"(jb));
-            }
-        } else if (n1 != kHole && pair_test(lut, self, n1 & idmask)) {   // first token of a match
-            is_a = true;
-            any = true;
-            const int ja = lut_index(lut, self, n1 & idmask);
-            if (tt_on && (n1 & idmask) >= idmask - (uint32_t)kTTMax)      // a match of a (t,t) member: count it
-                atomicAdd(&ti.cnt[idmask - 1u - (n1 & idmask)], 1u);
-            if (left_open<MODE>(p1)) {
-                if (p2 != kHole && pair_test(lut, p2, p1)) {               // two matches touch
-                    const int jp = lut_index(lut, p2, p1);
-                    atomicAdd(&hdr_adj[jp * adj_pitch + ja], 1u);
-                } else {
-                    if (DIAG != 3) dc_add(dc, dc_on, LR, lr_idx(pitch, p1, (uint32_t)ja, 0), 1u);
-                    else asm volatile("" :: "v"(ja));
-                }
-            }
-        }
-        a1 = is_a;
-        p2 = p1; p1 = self;
-    }
-    if (__ballot(any) != 0ull && lane_id() == 0) atomicOr(&chg[tile >> 5], 1u << (tile & 31u));
-}
-
 // (defined with k_fused_batch; WRITE false = count and mark only)
 template <int MODE, int DIAG, bool WRITE, bool TT, class DC>
 __device__ __forceinline__ uint4 fused_tile_pf(const uint4 q_orig, const uint32_t s[8], const Halo h,
@@ -3217,7 +2923,6 @@ __global__ __launch_bounds__(kLutThreads) void k_scan_batch(const uint16_t *tok0
                                                               uint32_t *T) {
     constexpr uint32_t idmask = MODE == 1 ? 0x7FFFu : 0xFFFFu;
     __shared__ BatchLutMem lut_mem;
-    const uint32_t lane = lane_id();
     const uint32_t waves_per_block = kLutThreads / kWave;
     const uint32_t n_waves = gridDim.x * waves_per_block;
     __shared__ DeltaCache dc;
@@ -3227,7 +2932,6 @@ __global__ __launch_bounds__(kLutThreads) void k_scan_batch(const uint16_t *tok0
     __shared__ TTInfo ti;
     const uint16_t *tok = ctl->cur ? tok1 : tok0;
     const uint32_t ctl_k_done = rfl(ctl->k_done);
-    const uint32_t pitch = rfl(lr_pitch(256u + ctl_k_done));
     const uint32_t adj_pitch = rfl(ctl->adj_pitch);
     if (hot_mismatch<HOT>(bs->packed[0] >> 32, ctl, hot_launched)) return;     // (see k_merge)
     constexpr bool dc_on = HOT;
@@ -3249,15 +2953,12 @@ __global__ __launch_bounds__(kLutThreads) void k_scan_batch(const uint16_t *tok0
     TileIn t0 = tile_issue(tok, sums_rsrc, tile);
     TileIn t1 = tile_issue(tok, sums_rsrc, clamp_tile((uint64_t)tile + n_waves));
     bool v1 = (uint64_t)tile + n_waves < n_tiles;
-    const unsigned long long gt_mask = lane == 63 ? 0ull : ~((2ull << lane) - 1ull);
     for (;;) {
         const bool v2 = (uint64_t)tile + 2ull * n_waves < n_tiles;
         TileIn t2 = tile_issue(tok, sums_rsrc, clamp_tile((uint64_t)tile + 2ull * n_waves));
 
         const uint32_t me_nlive = rlane(t0.smw, 6) & 0xFFFFu;
-        if (DIAG == 1) {
-            asm volatile("" :: "v"(t0.q.x), "v"(t0.q.y), "v"(t0.q.z), "v"(t0.q.w), "v"(t0.smw));
-        } else if (me_nlive != 0) {
+        if (me_nlive != 0) {
             uint32_t s[8];
             unpack8(t0.q, s);
             Halo h;
@@ -3270,38 +2971,13 @@ __global__ __launch_bounds__(kLutThreads) void k_scan_batch(const uint16_t *tok0
             } else {
                 h = halo_slow(sin, n_tiles, tile, le, re);
             }
-            if constexpr (MBPE_FUSED_PF && DIAG == 0) {      // tiles are in prefix form: the fused pass's tile function, counting only
-                uint32_t rm_unused = 0;
-                bool ws_unused = false, no_rename = false;
-                if (TT) tt_rename<MODE>(s, h, ti, run_in[tile]);      // ((t,t) members: every tile, as the chain-walking path did)
-                fused_tile_pf<MODE, 0, false, TT>(t0.q, s, h, rlane(t0.smw, 4), rlane(t0.smw, 5), rlane(t0.smw, 6), lut,
-                                                  256u + ctl_k_done, tile, nullptr, hdr_adj, LR, dc, dc_on, rm_unused, ws_unused,
-                                                  lr_rsrc, adj_pitch, nullptr, chg, TT, &ti, no_rename, t_rsrc, use_t);
-            } else {
-            if (TT) tt_rename<MODE>(s, h, ti, run_in[tile]);
-            // first live token of the lanes after this one (exact), then the candidate
-            // test: some slot and its next live token form one of the batch pairs
-            uint32_t lf = kHole;
-#pragma unroll
-            for (int j = 7; j >= 0; --j) lf = s[j] != kHole ? s[j] : lf;
-            const unsigned long long m_live = __ballot(lf != kHole);
-            const unsigned long long hi = m_live & gt_mask;
-            const uint32_t nf = __shfl(lf, hi ? (uint32_t)__builtin_ctzll(hi) : lane, kWave);
-            uint32_t c = hi ? nf : h.n1;
-            uint32_t miss = 0xFFFFFFFFu;
-#pragma unroll
-            for (int j = 7; j >= 0; --j) {
-                const uint32_t d = pair_miss(lut, s[j], MODE == 1 ? c & idmask : c);    // (ids are 16-bit: no mask needed)
-                miss = d < miss ? d : miss;
-                c = s[j] != kHole ? s[j] : c;
-            }
-            const bool cand = miss == 0u;
-            // (also: a match whose first token is the previous tile's last live token)
-            const uint32_t tile_first = rlane(lf, (uint32_t)__builtin_ctzll(m_live | (1ull << 63)));
-            bool work = __ballot(cand) != 0ull || pair_test(lut, h.p1, tile_first & idmask);
-            if (DIAG == 2) { asm volatile("" :: "v"((uint32_t)cand)); work = false; }
-            if (work) scan_tile_full<MODE, DIAG>(chg, tile, s, h, lut, n_keys, hdr_adj, LR, pitch, dc, dc_on, TT, ti, adj_pitch);
-            }
+            // tiles are in prefix form: the fused pass's tile function, counting only
+            uint32_t rm_unused = 0;
+            bool ws_unused = false, no_rename = false;
+            if (TT) tt_rename<MODE>(s, h, ti, run_in[tile]);      // ((t,t) members: every tile, no tt_needed test first)
+            fused_tile_pf<MODE, 0, false, TT>(t0.q, s, h, rlane(t0.smw, 4), rlane(t0.smw, 5), rlane(t0.smw, 6), lut,
+                                              256u + ctl_k_done, tile, nullptr, hdr_adj, LR, dc, dc_on, rm_unused, ws_unused,
+                                              lr_rsrc, adj_pitch, nullptr, chg, TT, &ti, no_rename, t_rsrc, use_t);
         }
         if (!v1) break;
         tile += n_waves;
@@ -3326,160 +3002,14 @@ __global__ __launch_bounds__(kLutThreads) void k_scan_batch(const uint16_t *tok0
 // the other buffer is simply abandoned and k_rewrite_marked applies the
 // surviving prefix to the current buffer, exactly as after k_scan_batch.
 //
-// Matches of a batch cannot overlap, so "slot j starts a match" (mask A) is one
-// exact table test per slot, and "slot j is the second token of a match" (mask
-// B) is A moved to the next live slot.  That move, inside a lane and from lane
-// to lane over empty lanes, is a carry chain: ((A << 1 | carry_in) + holes) &
-// live.  Everything else (pair index, neighbours, deltas) is only done where a
-// match is.
-
-template <int MODE, int DIAG = 0, class DC>
-__device__ __forceinline__ uint4 fused_tile_full(const uint4 q_orig, bool tt_on, TTInfo &ti,
-                                                 const uint32_t s[8], const uint32_t cj[8],
-                                                 uint32_t Am, uint32_t Wm, bool tcin, bool tbin, unsigned long long m_live,
-                                                 uint32_t c_init, const Halo h,
-                                                 uint32_t tile_first, uint32_t old_x, uint32_t old_y,
-                                                 uint32_t old_z, const BatchLut &lut, uint32_t X0, uint32_t tile,
-                                                 TileSum *sout, uint32_t *chg, uint32_t *hdr_adj, uint32_t *LR,
-                                                 DC &dc, bool dc_on, uint32_t &wave_rm, bool &wrote_sum,
-                                                 __amdgpu_buffer_rsrc_t lr_rsrc, uint32_t adj_pitch, uint16_t *stage) {
-    constexpr uint32_t idmask = MODE == 1 ? 0x7FFFu : 0xFFFFu;
-    constexpr uint32_t endbit = MODE == 1 ? kEndBit : 0u;
-    const uint32_t pitch = lr_pitch(X0);        // uniform
-    // (plain instantiation: the delta atomics go through a buffer resource -- scalar base, 32-bit lane offset -- so
-    //  that no 64-bit address is built per match; the LR block is below 4 GB)
-    auto delta_add = [&](uint32_t idx, uint32_t delta) {
-        if (dc_on) dc_add(dc, true, LR, idx, delta);
-        else __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32((int)delta, lr_rsrc, idx << 2, 0, 0);
-    };
-    // (an opaque copy of the lane id: the 64-bit lane masks below are cheaper to rebuild per tile than
-    //  to keep in registers across the streaming loop, where the compiler would spill them)
-    uint32_t lane = lane_id();
-    asm volatile("" : "+v"(lane));
-    const unsigned long long lane_bit = 1ull << lane;
-    uint32_t Lm = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) Lm |= (s[j] != kHole ? 1u : 0u) << j;
-    const uint32_t Hm = Lm ^ 0xFFu;
-    const unsigned long long E = ~m_live;
-
-    // carry "the last live token before this lane starts a match" over empty lanes
-    const bool lastA = Am > (Lm & ~Am);
-    const unsigned long long G = __ballot(lastA);
-    const unsigned long long CIN = (((G << 1) | (tcin ? 1ull : 0ull)) + E) & m_live;
-    const uint32_t cin = lane_of(CIN) ? 1u : 0u;
-    const uint32_t Bm = (((Am << 1) | cin) + Hm) & Lm;
-    // the same for "the last live token before this lane ends a match"
-    const bool lastB = Bm > (Lm & ~Bm);
-    const unsigned long long GB = __ballot(lastB);
-    const unsigned long long BIN = (((GB << 1) | (tbin ? 1ull : 0ull)) + E) & m_live;
-    const uint32_t bin = lane_of(BIN) ? 1u : 0u;
-    const uint32_t touch = Am & ((((Bm << 1) | bin) + Hm) & Lm);     // starts a match right after another one
-
-    const unsigned long long ab = __ballot((Am | Bm) != 0u);
-    if (ab == 0ull) return q_orig;
-
-    // last live token of every lane and, where it starts a match, the index of that match
-    uint32_t ll = kHole;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ll = s[j] != kHole ? s[j] : ll;
-    uint32_t lastj = 0;
-    if (lastA) lastj = lut_index_known(lut, ll, c_init & idmask, ((Wm >> (31u - (uint32_t)__builtin_clz(Lm | 1u))) & 1u) != 0u);
-    uint32_t p1, pj;
-    const uint32_t pj_tile = tcin ? (uint32_t)lut_index(lut, h.p1, tile_first & idmask) : 0u;     // uniform
-    if (m_live == ~0ull) {                   // the previous lane is the previous live lane
-        const uint32_t got = wave_from_prev(ll | (lastj << 16), h.p1 | (pj_tile << 16));
-        p1 = got & 0xFFFFu;
-        pj = got >> 16;
-    } else {
-        const unsigned long long lo = m_live & (lane_bit - 1ull);
-        const uint32_t src = lo ? 63u - (uint32_t)__builtin_clzll(lo) : lane;
-        const uint32_t got = __shfl(ll | (lastj << 16), src, kWave);
-        p1 = lo ? (got & 0xFFFFu) : h.p1;
-        pj = lo ? (got >> 16) : pj_tile;
-    }
-    uint32_t pjb = 0;
-    // rare: the token before this lane ends a match and this lane's first live token starts one
-    if (__ballot(bin != 0u && (Am & Lm & (0u - Lm)) != 0u) != 0ull) {
-        const Neigh nb = tile_neighbours(s, h);
-        if (bin) pjb = (uint32_t)lut_index(lut, nb.p2_in, p1 & idmask);
-    }
-
-    uint32_t out[8];
-    const uint32_t ABm = Am | Bm;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint32_t self = s[j];
-        uint32_t nv = self;
-        if ((ABm >> j) & 1u) {               // one guarded region per position serves both roles
-            const bool is_a = (Am >> j) & 1u;
-            uint32_t ja = pj;
-            if (is_a) {
-                ja = lut_index_known(lut, self, cj[j] & idmask, ((Wm >> j) & 1u) != 0u);
-                if (tt_on && (cj[j] & idmask) >= idmask - (uint32_t)kTTMax)      // a match of a (t,t) member: count it
-                    atomicAdd(&ti.cnt[idmask - 1u - (cj[j] & idmask)], 1u);
-            }
-            // first token of a match: (p1, a) -> (p1, X); second token: (b, n1) -> (X, n1)
-            const uint32_t nb = is_a ? p1 : cj[j];                       // the neighbour the match loses
-            const bool counted = is_a ? left_open<MODE>(p1) : right_open<MODE>(self, cj[j]);
-            nv = is_a ? (X0 + ja) | (cj[j] & endbit) : kHole;
-            if (counted && DIAG != 2) {
-                if (is_a && ((touch >> j) & 1u)) {        // ... (a', b') (a, b): (b', a) -> (X', X)
-                    atomicAdd(&hdr_adj[pjb * adj_pitch + ja], 1u);
-                    delta_add(lr_idx(pitch, self, pjb, 1), 0xFFFFFFFFu);   // takes back the R count of (a', b')
-                } else {
-                    delta_add(lr_idx(pitch, nb & idmask, ja, is_a ? 0u : 1u), 1u);
-                }
-            }
-            pjb = is_a ? pjb : pj;
-            pj = ja;
-        }
-        p1 = self != kHole ? self : p1;
-        out[j] = nv;
-    }
-
-    if (tt_on) {                        // (every renamed token was the second token of a match; be safe)
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (out[j] != kHole && (out[j] & idmask) >= idmask - (uint32_t)kTTMax)
-                out[j] = ti.tok[idmask - 1u - (out[j] & idmask)] | (out[j] & endbit);
-    }
-    // (sum over the lanes of the set bits of an 8-bit mask with ballots: vector compares and scalar popcounts instead
-    //  of a shuffle reduction, whose six dependent ds_bpermute round trips cost more than the rest of this function)
-    uint32_t removed = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 8; ++k) removed += (uint32_t)__popcll(__ballot(((Bm >> k) & 1u) != 0u));
-    wave_rm += removed;
-    // New summary.  Heads and tails only change when a match touches one of the first two or
-    // last two live tokens; a trailing run of equal tokens (tail_run > 1) is recounted.
-    const uint32_t top = Lm ? 31u - (uint32_t)__builtin_clz(Lm) : 0u;
-    const uint32_t lb1 = Lm & (0u - Lm), r1 = Lm ^ lb1, lb2 = r1 & (0u - r1);
-    const uint32_t hb1 = Lm ? 1u << top : 0u, r2 = Lm ^ hb1, hb2 = r2 ? 1u << (31u - (uint32_t)__builtin_clz(r2)) : 0u;
-    const uint32_t F = (uint32_t)__builtin_ctzll(m_live), Hl = 63u - (uint32_t)__builtin_clzll(m_live);
-    const unsigned long long mF = m_live & (m_live - 1ull), mH = m_live & ~(1ull << Hl);
-    bool edge = rlane(ABm & (lb1 | lb2), F) != 0u || rlane(ABm & (hb1 | hb2), Hl) != 0u;
-    if (rlane(lb2, F) == 0u && mF) edge |= rlane(ABm & lb1, (uint32_t)__builtin_ctzll(mF)) != 0u;
-    if (rlane(hb2, Hl) == 0u && mH) edge |= rlane(ABm & hb1, 63u - (uint32_t)__builtin_clzll(mH)) != 0u;
-    uint4 ns;
-    if (edge || (old_z >> 16) != 1u) {
-        ns = wave_summary(out);
-    } else {
-        ns = make_uint4(old_x, old_y, (old_z & 0xFFFF0000u) | ((old_z & 0xFFFFu) - removed), 0u);
-    }
-    // (no tile mark: a fused pass writes every tile's summary to the side array, see DevCtl::marks_all)
-    if (lane == 0) reinterpret_cast<uint4 *>(sout)[tile] = ns;
-    wrote_sum = true;
-    uint32_t n_out;
-    return tile_compact(out, stage, n_out);
-}
-
-// The same for a tile in prefix form (see tile_compact; every tile, unless the slots hold barriers): the token after a
-// slot is the next slot -- the next lane's first one, the next tile's first token after the last live slot -- and the
-// token before it the previous slot, so a slot is the second token of a match iff the slot before it starts one.  No
-// chains over holes, no carries over empty lanes, no (t,t) members (their instantiation takes fused_tile_full).  The
-// batch index of the match a slot starts is looked up once per slot (byte table: the entry itself) and handed to the
-// next two slots by register / DPP: a second token counts for the pair of the slot before it, a first token right
-// after a match for the pair two slots back (ADJ).  Same deltas, same new tile, same summary as fused_tile_full.
+// Matches of a batch cannot overlap, so "slot j starts a match" is one exact table test per slot.  Tiles are in prefix
+// form (see tile_compact; every tile, unless the slots hold barriers): the token after a slot is the next slot -- the next
+// lane's first one, the next tile's first token after the last live slot -- and the token before it the previous slot,
+// so a slot is the second token of a match iff the slot before it starts one.  The batch index of the match a slot
+// starts is looked up once per slot (byte table: the entry itself) and handed to the next two slots by register / DPP:
+// a second token counts for the pair of the slot before it, a first token right after a match for the pair two slots
+// back (ADJ).  Everything else (neighbours, deltas, the new tile and its summary) is only done where a match is.
+// (t,t) members: the caller renames the tile first where a run of a member's token needs it (tt_rename; `renamed`).
 template <int MODE, int DIAG, bool WRITE, bool TT, class DC>
 __device__ __forceinline__ uint4 fused_tile_pf(const uint4 q_orig, const uint32_t s[8], const Halo h,
                                                uint32_t old_x, uint32_t old_y, uint32_t old_z, const BatchLut &lut,
@@ -3724,7 +3254,6 @@ __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) 
     __shared__ __attribute__((aligned(16))) uint16_t stage_mem[kLutThreads / kWave][kTileSlots];
     uint16_t *stage = stage_mem[threadIdx.x / kWave];
     // tiles are in prefix form and take the short tile function (fused_tile_pf); (t,t) members: renamed first where needed
-    constexpr bool PF = MBPE_FUSED_PF != 0;
     const uint16_t *tok = ctl->cur ? tok1 : tok0;
     uint16_t *dst = ctl->cur ? tok0 : tok1;
     const uint32_t X0 = 256u + ctl->k_done;
@@ -3732,7 +3261,7 @@ __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) 
     constexpr bool dc_on = HOT;
     if (dc_on) dc_init(dc);
     BatchLut lut(&lut_mem, bs, idmask);
-    lut_build(lut, bs, n_keys, idmask - 1u, TT && MBPE_FUSED_PF);
+    lut_build(lut, bs, n_keys, idmask - 1u, TT);
     if (TT) tt_build(ti, bs, n_keys, idmask - 1u);
     if (blockIdx.x == 0 && threadIdx.x == 0) ctl->marks_all = 1;
     uint32_t tile = rfl(blockIdx.x * waves_per_block + threadIdx.x / kWave);
@@ -3756,7 +3285,6 @@ __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) 
     TileIn ring[kDepth];
 #pragma unroll
     for (int d = 0; d < kDepth; ++d) ring[d] = tile_issue(tok, sums_rsrc, clamp_tile((uint64_t)tile + (uint64_t)d * n_waves));
-    const unsigned long long gt_mask = lane == 63 ? 0ull : ~((2ull << lane) - 1ull);
     for (;;) {
         const bool v1 = (uint64_t)tile + n_waves < n_tiles;
         const TileIn t_new = tile_issue(tok, sums_rsrc, clamp_tile((uint64_t)tile + (uint64_t)kDepth * n_waves));
@@ -3780,95 +3308,35 @@ __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) 
             } else {
                 h = halo_slow(sin, n_tiles, tile, le, re);
             }
-            if constexpr (PF) {
-                bool renamed = false;    // uniform: tt_rename ran on this tile (only then can stand-in ids occur in it)
-                bool need_rename = false;
-                if (TT && !lut.bytes) {
-                    // (t,t) members, hash table: does any live token equal its successor and belong to one?  (nearly
-                    // never; with the byte table the slots' own lookups tell: kTTMark)
-                    uint32_t nx[8];
+            bool renamed = false;    // uniform: tt_rename ran on this tile (only then can stand-in ids occur in it)
+            bool need_rename = false;
+            if (TT && !lut.bytes) {
+                // (t,t) members, hash table: does any live token equal its successor and belong to one?  (nearly
+                // never; with the byte table the slots' own lookups tell: kTTMark)
+                uint32_t nx[8];
 #pragma unroll
-                    for (int j = 0; j < 7; ++j) nx[j] = s[j + 1];
-                    nx[7] = wave_from_next(s[0], h.n1);
-                    const uint32_t li = (old_z & 0xFFFFu) - 1u;
-                    const bool mine = lane == (li >> 3);
+                for (int j = 0; j < 7; ++j) nx[j] = s[j + 1];
+                nx[7] = wave_from_next(s[0], h.n1);
+                const uint32_t li = (old_z & 0xFFFFu) - 1u;
+                const bool mine = lane == (li >> 3);
 #pragma unroll
-                    for (uint32_t j = 0; j < 8; ++j)
-                        if ((li & 7u) == j) nx[j] = mine ? h.n1 : nx[j];
-                    const int lrem = (int)(old_z & 0xFFFFu) - (int)(lane * 8u);
-                    const uint32_t lm = lrem >= 8 ? 0xFFu : lrem <= 0 ? 0u : (1u << lrem) - 1u;
-                    if (tt_needed<MODE>(s, nx, h, old_x & 0xFFFFu, ti, lm)) {
-                        tt_rename<MODE>(s, h, ti, run_in[tile]);
-                        renamed = true;
-                    }
-                }
-                outq = fused_tile_pf<MODE, DIAG, true, TT>(t0.q, s, h, old_x, old_y, old_z, lut, X0, tile, sout, hdr_adj, LR, dc,
-                                                           dc_on, wave_rm, wrote_sum, lr_rsrc, adj_pitch, stage, chg, renamed, &ti,
-                                                           need_rename, t_rsrc, use_t);
-                if (TT && need_rename) {             // (uniform, rare)
+                for (uint32_t j = 0; j < 8; ++j)
+                    if ((li & 7u) == j) nx[j] = mine ? h.n1 : nx[j];
+                const int lrem = (int)(old_z & 0xFFFFu) - (int)(lane * 8u);
+                const uint32_t lm = lrem >= 8 ? 0xFFu : lrem <= 0 ? 0u : (1u << lrem) - 1u;
+                if (tt_needed<MODE>(s, nx, h, old_x & 0xFFFFu, ti, lm)) {
                     tt_rename<MODE>(s, h, ti, run_in[tile]);
-                    outq = fused_tile_pf<MODE, DIAG, true, TT>(t0.q, s, h, old_x, old_y, old_z, lut, X0, tile, sout, hdr_adj, LR,
-                                                               dc, dc_on, wave_rm, wrote_sum, lr_rsrc, adj_pitch, stage, chg, true,
-                                                               &ti, need_rename, t_rsrc, use_t);
+                    renamed = true;
                 }
-            } else {
-            uint32_t lf, c_init, tile_first, cj[8];
-            unsigned long long m_live;
-            bool renamed = false;        // uniform: tt_rename ran on this tile (only then can stand-in ids occur in it)
-            // (t,t) members: the renaming changes the tile's tokens, so everything derived from them is redone
-            // after it -- for the few tiles that need it (tt_needed)
-            for (int rep = 0;; ++rep) {
-                lf = kHole;
-#pragma unroll
-                for (int j = 7; j >= 0; --j) lf = s[j] != kHole ? s[j] : lf;
-                m_live = __ballot(lf != kHole);
-                if (m_live == ~0ull) {               // every lane holds a live token (nearly always): the next lane's
-                    c_init = wave_from_next(lf, h.n1);
-                } else {
-                    const unsigned long long hi = m_live & gt_mask;
-                    const uint32_t nf = __shfl(lf, hi ? (uint32_t)__builtin_ctzll(hi) : lane, kWave);
-                    c_init = hi ? nf : h.n1;
-                }
-                tile_first = rlane(lf, (uint32_t)__builtin_ctzll(m_live | (1ull << 63)));
-                uint32_t c = c_init;
-#pragma unroll
-                for (int j = 7; j >= 0; --j) {
-                    cj[j] = c;
-                    c = s[j] != kHole ? s[j] : c;
-                }
-                if (!TT || rep || DIAG == 5 || !tt_needed<MODE>(s, cj, h, tile_first, ti)) break;
+            }
+            outq = fused_tile_pf<MODE, DIAG, true, TT>(t0.q, s, h, old_x, old_y, old_z, lut, X0, tile, sout, hdr_adj, LR, dc,
+                                                       dc_on, wave_rm, wrote_sum, lr_rsrc, adj_pitch, stage, chg, renamed, &ti,
+                                                       need_rename, t_rsrc, use_t);
+            if (TT && need_rename) {             // (uniform, rare)
                 tt_rename<MODE>(s, h, ti, run_in[tile]);
-                renamed = true;
-            }
-            // (the two tests on the tile's left edge -- does the previous tile's last token start a match with this
-            //  tile's first one, did it end one -- are uniform LDS reads; issued here they travel with the eight below
-            //  instead of costing a round trip of their own inside fused_tile_full)
-            const bool tcin = pair_test(lut, h.p1, tile_first & idmask);
-            const bool tbin = h.p2 != kHole && pair_test(lut, h.p2, h.p1 & idmask);
-            uint32_t Am = 0, Wm = 0;     // bit j: slot j starts a match / ... of the second key of its lookup bucket
-            if (lut.bytes) {             // (uniform) a batch of byte pairs: one 2-byte read of the direct table per slot
-#pragma unroll
-                for (int j = 7; j >= 0; --j) {
-                    const bool hit = byte_entry<TT>(lut, s[j], MODE == 1 ? cj[j] & idmask : cj[j], idmask) != 0xFFFFu;
-                    Am = Am + Am + (hit ? 1u : 0u);
-                }
-            } else {
-#pragma unroll
-                for (int j = 7; j >= 0; --j) {
-                    bool second_key;
-                    const bool hit = pair_hit2(lut, s[j], MODE == 1 ? cj[j] & idmask : cj[j], second_key);     // (ids are 16-bit: no mask needed)
-                    Am = Am + Am + (hit ? 1u : 0u);         // one add-with-carry, the carry being the compare mask
-                    Wm = Wm + Wm + (second_key ? 1u : 0u);
-                }
-            }
-            const bool any = Am != 0u;
-            if (DIAG == 3 || DIAG == 5) {    // timing-only build: membership tests, no merge
-                asm volatile("" :: "v"(Am));
-            } else if (__ballot(any) != 0ull || tcin) {
-                outq = fused_tile_full<MODE, DIAG>(t0.q, TT && renamed, ti, s, cj, Am, Wm, tcin, tbin, m_live, c_init, h, tile_first,
-                                                old_x, old_y, old_z, lut, X0, tile, sout, chg, hdr_adj, LR, dc, dc_on,
-                                                wave_rm, wrote_sum, lr_rsrc, adj_pitch, stage);
-            }
+                outq = fused_tile_pf<MODE, DIAG, true, TT>(t0.q, s, h, old_x, old_y, old_z, lut, X0, tile, sout, hdr_adj, LR,
+                                                           dc, dc_on, wave_rm, wrote_sum, lr_rsrc, adj_pitch, stage, chg, true,
+                                                           &ti, need_rename, t_rsrc, use_t);
             }
         }
         // every tile's summary goes to the side array (an unchanged tile's as it was): no tile marks needed
@@ -3876,11 +3344,7 @@ __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) 
         MBPE_GLOBAL_AS char *obase =
             (MBPE_GLOBAL_AS char *)uniform_ptr(reinterpret_cast<uintptr_t>(dst) + (uint64_t)tile * (kWave * 16u));
         u32x4 oq; oq.x = outq.x; oq.y = outq.y; oq.z = outq.z; oq.w = outq.w;
-#if MBPE_NT_STREAM
         __builtin_nontemporal_store(oq, (MBPE_GLOBAL_AS u32x4 *)(obase + lane * 16u));
-#else
-        *(MBPE_GLOBAL_AS u32x4 *)(obase + lane * 16u) = oq;
-#endif
 
         if (!v1) break;
         tile += n_waves;
@@ -4192,12 +3656,6 @@ __global__ void k_apply_batch(PairTable t, DevCtl *ctl, const BatchState *bs, ui
 // A new token's pairs are plain stores; their argmax bounds are raised once per wave.
 constexpr int kApplyTile = 64;
 constexpr uint32_t kApplyJParts = 16;
-#ifndef MBPE_APPLY_LOADS
-#define MBPE_APPLY_LOADS 1
-#endif
-#ifndef MBPE_APPLY_BOUNDS
-#define MBPE_APPLY_BOUNDS 0
-#endif
 #ifndef MBPE_APPLY_FLIGHT
 #define MBPE_APPLY_FLIGHT 4
 #endif
@@ -4231,9 +3689,6 @@ __device__ __forceinline__ void dense_raise_flush(const PairTable &t, RaiseList 
 __device__ __forceinline__ void dense_raise_bounds(const PairTable &t, unsigned long long p, uint32_t blk, RaiseList &rl,
                                                    uint32_t &n) {
     // p: this lane's maximum (0: none) among the cells it inserted into tile blk; one list entry per tile touched
-#ifdef MBPE_APPLY_NORAISE
-    return;                      // (timing-only build)
-#endif
     unsigned long long m = __ballot(p != 0ull);
     while (m) {
         const uint32_t blk0 = rfl(__shfl(blk, (uint32_t)__builtin_ctzll(m), kWave));
@@ -4265,7 +3720,6 @@ __global__ __launch_bounds__(256) void k_apply_batch_dense(PairTable t, DevCtl *
         if (threadIdx.x < (uint32_t)kApplyTile) keys[threadIdx.x] = j0 + threadIdx.x < n ? bs->key[j0 + threadIdx.x] : 0u;
         // load (and clear) the deltas of ids x0.. and pairs j0..: the rows L_j, R_j of LR are contiguous along x
         const uint32_t pitch = lr_pitch(X0);
-#if MBPE_APPLY_LOADS == 1
         {
             // (a wave's 32 loads are issued before its first store: the rows are independent, which the compiler cannot know)
             constexpr uint32_t kLd = kApplyTile / (256 / kWave);
@@ -4288,20 +3742,6 @@ __global__ __launch_bounds__(256) void k_apply_batch_dense(PairTable t, DevCtl *
                 tile[lane][c] = j < commit ? make_uint2(vl[u], vr[u]) : make_uint2(0, 0);
             }
         }
-#else
-        for (uint32_t c = wave; c < (uint32_t)kApplyTile; c += 256 / kWave) {
-            const uint32_t x = x0 + lane, j = j0 + c;
-            uint2 lr = make_uint2(0, 0);
-            if (x < X0 && j < n) {
-                uint32_t *cl = LR + (size_t)(2u * j) * pitch + x, *cr = cl + pitch;
-                lr = make_uint2(*cl, *cr);
-                if (lr.x) *cl = 0;
-                if (lr.y) *cr = 0;
-                if (j >= commit) lr = make_uint2(0, 0);
-            }
-            tile[lane][c] = lr;
-        }
-#endif
         __syncthreads();
         // The decrements return the old value (an absent pair or a negative count is an error worth
         // knowing about); four of them are in flight per lane before the first one is looked at.
@@ -4319,11 +3759,7 @@ __global__ __launch_bounds__(256) void k_apply_batch_dense(PairTable t, DevCtl *
                 const uint32_t r = wave + (r0 + u) * (256 / kWave), x = x0 + r;
                 l[u] = tile[r][lane].x;
                 old[u] = kPresent | l[u];
-#ifdef MBPE_APPLY_NORETURN
-                if (l[u]) atomicAdd(&t.cells[dense_index(t, (x << 16) | a)], 0u - l[u]);
-#else
                 if (l[u]) old[u] = atomicAdd(&t.cells[dense_index(t, (x << 16) | a)], 0u - l[u]);
-#endif
             }
 #pragma unroll
             for (uint32_t u = 0; u < kApplyFlight; ++u) {
@@ -4352,11 +3788,7 @@ __global__ __launch_bounds__(256) void k_apply_batch_dense(PairTable t, DevCtl *
                 const uint32_t c = wave + (c0 + u) * (256 / kWave), j = j0 + c;
                 rr[u] = j < n ? tile[lane][c].y : 0u;
                 old[u] = kPresent | rr[u];
-#ifdef MBPE_APPLY_NORETURN
-                if (rr[u]) atomicAdd(&t.cells[dense_index(t, ((keys[c] & 0xFFFFu) << 16) | xr)], 0u - rr[u]);
-#else
                 if (rr[u]) old[u] = atomicAdd(&t.cells[dense_index(t, ((keys[c] & 0xFFFFu) << 16) | xr)], 0u - rr[u]);
-#endif
             }
 #pragma unroll
             for (uint32_t u = 0; u < kApplyFlight; ++u) {
@@ -4438,7 +3870,6 @@ __global__ __launch_bounds__(kLutThreads) void k_rewrite_marked(uint16_t *tok0, 
                                                                   const RankEdge *le, const RankEdge *re,
                                                                   const uint32_t *__restrict__ run_in) {
     constexpr uint32_t idmask = MODE == 1 ? 0x7FFFu : 0xFFFFu;
-    constexpr uint32_t endbit = MODE == 1 ? kEndBit : 0u;
     __shared__ BatchLutMem lut_mem;
     if (ctl->batch_n < 2 || (ctl->fused && ctl->commit_n == ctl->batch_n)) return;
     uint16_t *tok = ctl->cur ? tok1 : tok0;
@@ -4465,8 +3896,7 @@ __global__ __launch_bounds__(kLutThreads) void k_rewrite_marked(uint16_t *tok0, 
     uint32_t tile0 = tile_at(i), tile1 = tile_at((uint64_t)i + n_waves), tile2 = tile_at((uint64_t)i + 2ull * n_waves);
     TileIn t0 = tile_issue(tok, sums_rsrc, tile0);
     TileIn t1 = tile_issue(tok, sums_rsrc, tile1);
-    uint32_t wave_rm = 0;              // per lane (chain-walking path), summed over the wave at the end
-    uint32_t wave_rm_uniform = 0;      // whole-wave count (prefix-form path)
+    uint32_t wave_rm = 0;        // uniform
     for (;;) {
         const bool has_next = (uint64_t)i + n_waves < n_list;
         const uint32_t tile3 = tile_at((uint64_t)i + 3ull * n_waves);
@@ -4485,76 +3915,30 @@ __global__ __launch_bounds__(kLutThreads) void k_rewrite_marked(uint16_t *tok0, 
         } else {
             h = halo_slow(sin, n_tiles, tile, le, re);
         }
-        if constexpr (MBPE_FUSED_PF != 0) {
-            // tiles are in prefix form: the fused pass's tile function without the count deltas, stored in place
-            // ((t,t) members: every tile renamed first, as the chain-walking path did)
-            uint32_t rm = 0;
-            bool wrote = false;          // uniform: the tile changed (its new summary is in the side array)
-            bool no_rename = false;
-            DeltaCacheSmall no_dc;       // (never touched: no deltas in this instantiation)
-            if (TT) tt_rename<MODE>(s, h, ti, run_in[tile]);
-            const uint4 qn = fused_tile_pf<MODE, 2, true, TT>(t0.q, s, h, rlane(t0.smw, 4), rlane(t0.smw, 5), rlane(t0.smw, 6), lut,
-                                                              X0, tile, sout, nullptr, nullptr, no_dc, false, rm, wrote,
-                                                              __amdgpu_buffer_rsrc_t(), 0u, stage, chg, TT, &ti, no_rename);
-            if (wrote) {
-                reinterpret_cast<uint4 *>(tok)[(uint64_t)tile * kWave + lane] = qn;
-                if (lane == 0 && marks_all) atomicOr(&chg[tile >> 5], 1u << (tile & 31u));    // (the fused pass set no marks)
-            } else if (lane == 0 && !marks_all) {
-                atomicAnd(&chg[tile >> 5], ~(1u << (tile & 31u)));    // marked for a pair that was dropped
-            }
-            wave_rm_uniform += rm;
-        } else {
+        // tiles are in prefix form: the fused pass's tile function without the count deltas, stored in place
+        // ((t,t) members: every tile renamed first)
+        uint32_t rm = 0;
+        bool wrote = false;          // uniform: the tile changed (its new summary is in the side array)
+        bool no_rename = false;
+        DeltaCacheSmall no_dc;       // (never touched: no deltas in this instantiation)
         if (TT) tt_rename<MODE>(s, h, ti, run_in[tile]);
-        const Neigh nb = tile_neighbours(s, h);
-        bool changed = false, a1 = false, first = true;
-        uint32_t p1 = nb.p1_in, my_rm = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint32_t self = s[j];
-            if (self == kHole) continue;
-            const uint32_t n1 = nb.n1v[j];
-            if (first) { a1 = p1 != kHole && pair_test(lut, p1, self & idmask); first = false; }
-            bool is_a = false;
-            if (a1) {                      // second token of a match: becomes a hole
-                s[j] = kHole;
-                changed = true;
-                ++my_rm;
-            } else if (n1 != kHole && pair_test(lut, self, n1 & idmask)) {
-                is_a = true;
-                s[j] = (X0 + (uint32_t)lut_index(lut, self, n1 & idmask)) | (n1 & endbit);
-                changed = true;
-            }
-            a1 = is_a;
-            p1 = self;
-        }
-        if (TT) {                           // (every renamed token was the second token of a match; be safe)
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (s[j] != kHole && (s[j] & idmask) >= idmask - (uint32_t)kTTMax)
-                    s[j] = ti.tok[idmask - 1u - (s[j] & idmask)] | (s[j] & endbit);
-        }
-        wave_rm += my_rm;
-        if (__ballot(changed) != 0ull) {
-            uint32_t n_out;
-            const uint4 qc = tile_compact(s, stage, n_out);
-            reinterpret_cast<uint4 *>(tok)[(uint64_t)tile * kWave + lane] = qc;
-            const uint4 ns = wave_summary(s);
-            if (lane == 0) {
-                reinterpret_cast<uint4 *>(sout)[tile] = ns;
-                if (marks_all) atomicOr(&chg[tile >> 5], 1u << (tile & 31u));    // (the fused pass set no marks)
-            }
+        const uint4 qn = fused_tile_pf<MODE, 2, true, TT>(t0.q, s, h, rlane(t0.smw, 4), rlane(t0.smw, 5), rlane(t0.smw, 6), lut,
+                                                          X0, tile, sout, nullptr, nullptr, no_dc, false, rm, wrote,
+                                                          __amdgpu_buffer_rsrc_t(), 0u, stage, chg, TT, &ti, no_rename);
+        if (wrote) {
+            reinterpret_cast<uint4 *>(tok)[(uint64_t)tile * kWave + lane] = qn;
+            if (lane == 0 && marks_all) atomicOr(&chg[tile >> 5], 1u << (tile & 31u));    // (the fused pass set no marks)
         } else if (lane == 0 && !marks_all) {
             atomicAnd(&chg[tile >> 5], ~(1u << (tile & 31u)));    // marked for a pair that was dropped
         }
-        }
+        wave_rm += rm;
 
         if (!has_next) break;
         i += n_waves;
         tile0 = tile1; tile1 = tile2; tile2 = tile3;
         t0 = t1; t1 = t2;
     }
-    const uint32_t tr = wave_sum(wave_rm) + wave_rm_uniform;
-    if (lane == 0 && tr) atomicAdd(&ctl->rm, tr);
+    if (lane == 0 && wave_rm) atomicAdd(&ctl->rm, wave_rm);
 }
 
 // last kernel of a sequence: advance the merge counter
@@ -4934,10 +4318,8 @@ void launch_pair_count_u8(hipStream_t s, const uint8_t *text, uint64_t n, const 
     if (n_workgroups < 1) n_workgroups = 1;
     if (endmask)
         hipExtLaunchKernelGGL(k_pair_count_u8<true>, dim3(n_workgroups), dim3(kPcThreads), 0, s, start, stop, 0, text, n, endmask, bp, scratch);
-    else if (MBPE_PC_FAST)
-        hipExtLaunchKernelGGL(k_pair_count_u8_fast, dim3(n_workgroups), dim3(kPcThreads), 0, s, start, stop, 0, text, n, bp, scratch);
     else
-        hipExtLaunchKernelGGL(k_pair_count_u8<false>, dim3(n_workgroups), dim3(kPcThreads), 0, s, start, stop, 0, text, n, endmask, bp, scratch);
+        hipExtLaunchKernelGGL(k_pair_count_u8_fast, dim3(n_workgroups), dim3(kPcThreads), 0, s, start, stop, 0, text, n, bp, scratch);
 }
 
 void launch_widen(hipStream_t s, const uint8_t *text, uint64_t n, const uint8_t *endmask, uint16_t *tok,
@@ -5147,20 +4529,6 @@ void launch_scan_batch(hipStream_t s, const uint16_t *tok, const uint16_t *tok1,
                                resident_blocks(k_scan_batch<1, false, false, 0>, kLutThreads),
                                resident_blocks(k_scan_batch<2, false, false, 0>, kLutThreads)};
     const dim3 grid(tile_grid(n_tiles, n_cus, occ[slot_mode(endbit)], kLutThreads)), block(kLutThreads);
-#ifdef MBPE_DIAG
-    static const int diag = getenv("MBPE_SCAN_DIAG") ? atoi(getenv("MBPE_SCAN_DIAG")) : 0;
-#define MBPE_SCAN_DIAG_CASE(D)                                                                                             \
-    if (diag == D && !endbit) {                                                                                            \
-        hipLaunchKernelGGL((k_scan_batch<0, false, false, D>), grid, block, 0, s, tok, tok1, sums, n_tiles, chg, bs,       \
-                           hdr_m, hdr_adj, LR, ctl, left_edge, right_edge, run_in, hot_possible, T);                                        \
-        return;                                                                                                            \
-    }
-    MBPE_SCAN_DIAG_CASE(1)
-    MBPE_SCAN_DIAG_CASE(2)
-    MBPE_SCAN_DIAG_CASE(3)
-    MBPE_SCAN_DIAG_CASE(4)
-#undef MBPE_SCAN_DIAG_CASE
-#endif
     MBPE_BY_MODE(endbit, {
         if (only < 0 || only == 0)
             hipLaunchKernelGGL((k_scan_batch<M, false, false, 0>), grid, block, 0, s, tok, tok1, sums, n_tiles, chg, bs, hdr_m, hdr_adj,

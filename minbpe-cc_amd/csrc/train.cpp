@@ -318,7 +318,7 @@ int sync_ctl(mbpe_ctx *c) {
     HIPCHK(hipStreamSynchronize(c->stream));
     c->cur = (int)(c->h_ctl.cur & 1u);      // a fused pass flips the live buffer on the device
 #ifdef MBPE_DIAG
-    if (getenv("MBPE_SCAN_DIAG") || getenv("MBPE_MERGE_DIAG") || getenv("MBPE_FUSED_DIAG")) c->h_ctl.err = 0;   // timing-only kernels break the counts
+    if (getenv("MBPE_MERGE_DIAG") || getenv("MBPE_FUSED_DIAG")) c->h_ctl.err = 0;   // timing-only kernels break the counts
 #endif
     if (c->h_ctl.err) {
         char buf[320];
