@@ -1,7 +1,7 @@
 /*
  * mbpe.h -- C-ABI of the MI355X-native BPE trainer hot path.
  *
- * Drop-in boundary for justinhj/minbpe-cc's training path (both tie-breaks) and its encode.
+ * Drop-in boundary for justinhj/minbpe-cc's training path (both tie-breaks), its encode and its decode.
  * The reference has no FFI layer of its own; every entry point
  * below names the reference code it replaces (paths relative to the
  * reference checkout, code/include/...).  INTEGRATION.md shows the binding a
@@ -328,6 +328,71 @@ MBPE_API int mbpe_encode_chunks(int device_id, const uint8_t *text, uint64_t n_b
                                 const uint32_t *merges, uint32_t n_merges,
                                 uint32_t *tokens_out, uint64_t cap, uint64_t *n_out,
                                 uint32_t *n_passes_out);
+
+/* The same with the result left on the device: tokens_dev_out is device memory of `device_id` for cap tokens
+ * (NULL to query the count) and receives the tokens as the passes leave them, bit 31 = last token of its chunk
+ * (mask with 0x7FFFFFFF for the id; mbpe_decode_slots with slot_bits 32 and end_bit 0x80000000 reads them as they
+ * are). */
+MBPE_API int mbpe_encode_chunks_device(int device_id, const uint8_t *text, uint64_t n_bytes,
+                                       const uint64_t *chunk_off, uint64_t n_chunks,
+                                       const uint32_t *merges, uint32_t n_merges,
+                                       uint32_t *tokens_dev_out, uint64_t cap, uint64_t *n_out,
+                                       uint32_t *n_passes_out);
+
+/* ---- decode on the device ----------------------------------------------- */
+
+/* Tokenizer::decode (Tokenizer.h:725-751) for whole token streams on HIP device `device_id`: per token a byte
+ * length, a 64-bit exclusive prefix sum, a copy of every token's bytes to its offset (csrc/decode.hip).  What a
+ * token id yields, in the reference's order:
+ *   - an id among special_ids: that special's bytes.  This test comes first: a special whose id lies below the
+ *     vocabulary size overrides the vocabulary entry (:729-733); of several specials with one id the last holds
+ *   - otherwise an id >= 256 + n_merges: nothing (the reference prints a warning and goes on, :734-737); such ids
+ *     are counted in n_invalid_out
+ *   - otherwise vocab[id], with vocab[256 + k] = vocab[a_k] ++ vocab[b_k] (:562-564), a repeated pair included.  A
+ *     side of merge k that names an id >= 256 + k contributes nothing, as in the host Tokenizer's rebuilt vocabulary
+ *     of a hand-edited model: device and host decode agree on every model the host accepts.
+ * A decoder holds, on the device, one length and one offset per id and the bytes of all entries in one blob.  The
+ * blob may hold up to MBPE_DECODER_MAX_BLOB bytes and a single entry up to MBPE_DECODER_MAX_ENTRY bytes (so that
+ * the 1,024 tokens one wave expands stay below 2^32 bytes); a vocabulary beyond either returns MBPE_ERR_OOM.
+ *   merges            2 * n_merges u32, as for mbpe_encode_chunks; n_merges <= MBPE_MAX_VOCAB_WIDE - 256
+ *   special_ids       n_special ids; special k's bytes are special_bytes[special_off[k] .. special_off[k+1])
+ *                     (special_off: n_special + 1 ascending offsets; an empty string is allowed)
+ * Arguments are checked, and the vocabulary is built, before the device is touched.  No CPU fallback:
+ * MBPE_ERR_NO_DEVICE without a HIP device.  A decoder has its own non-blocking stream and is thread-compatible
+ * like a context: one call at a time. */
+#define MBPE_DECODER_MAX_BLOB  (1ull << 30)
+#define MBPE_DECODER_MAX_ENTRY ((1u << 22) - 1u)
+typedef struct mbpe_decoder mbpe_decoder;
+MBPE_API int  mbpe_decoder_create(int device_id, const uint32_t *merges, uint32_t n_merges,
+                                  const uint32_t *special_ids, const uint8_t *special_bytes,
+                                  const uint64_t *special_off, uint32_t n_special, mbpe_decoder **out);
+MBPE_API void mbpe_decoder_destroy(mbpe_decoder *d);
+
+/* Decodes n_tokens ids.  tokens / bytes_out are host memory, or device memory of the decoder's device when
+ * tokens_on_device / out_on_device is set (device buffers are used in place: no copy).  bytes_out NULL: query.
+ * n_out always receives the decoded length; when cap is smaller the call returns MBPE_ERR_ARG and writes nothing.
+ * n_invalid_out (optional): ids that decoded to nothing.  Lengths and offsets are 64-bit throughout: an output
+ * beyond 4 GiB is a supported case. */
+MBPE_API int  mbpe_decode_tokens(mbpe_decoder *d, const uint32_t *tokens, uint64_t n_tokens, int tokens_on_device,
+                                 uint8_t *bytes_out, uint64_t cap, int out_on_device,
+                                 uint64_t *n_out, uint64_t *n_invalid_out);
+
+/* The same for n_slots device-resident slots in one of the layouts mbpe_stream_device describes (slot_bits 16 or
+ * 32, its end_bit and barrier values; an all-ones slot and a barrier slot yield nothing and are not invalid), and
+ * for the 32-bit tokens with bit 31 = chunk end that mbpe_encode_chunks_device leaves on the device. */
+MBPE_API int  mbpe_decode_slots(mbpe_decoder *d, const void *slots, uint64_t n_slots, uint32_t slot_bits,
+                                uint32_t end_bit, uint32_t barrier, uint8_t *bytes_out, uint64_t cap,
+                                int out_on_device, uint64_t *n_out, uint64_t *n_invalid_out);
+
+/* Device time of the decoder's latest call in milliseconds (HIP events on its stream around the length kernel, the
+ * scan and the copy kernel; host <-> device copies are outside). */
+MBPE_API int  mbpe_decoder_kernel_ms(const mbpe_decoder *d, float *ms_out);
+
+/* The live stream of a training context, expanded with that training's own merges so far (after
+ * mbpe_train_begin; any slot layout, and the 32-bit continuation): decode(stream) == the corpus the context
+ * trains on (the packed chunks of a corpus given as ranges; on a rank of a sharded training, that rank's shard).
+ * Same conventions for bytes_out / cap / n_out as mbpe_decode_tokens. */
+MBPE_API int  mbpe_decode_stream(mbpe_ctx *ctx, uint8_t *bytes_out, uint64_t cap, int out_on_device, uint64_t *n_out);
 
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) ---------------- */
 

@@ -58,6 +58,12 @@ MBPE_API int mbpe_tok_encode_device(mbpe_tokenizer *t, const uint8_t *text, uint
 MBPE_API int mbpe_tok_decode(mbpe_tokenizer *t, const uint32_t *tokens, uint64_t n, int verbose,
                              uint8_t *bytes_out, uint64_t cap, uint64_t *n_out);
 
+/* The same with the expansion on HIP device `device_id` (mbpe_decode_tokens, with a decoder that the tokenizer keeps
+ * until its merges or special tokens change).  An id that decodes to nothing gets the reference's warning line, as
+ * on the host.  No CPU fallback: MBPE_ERR_NO_DEVICE without a device. */
+MBPE_API int mbpe_tok_decode_device(mbpe_tokenizer *t, const uint32_t *tokens, uint64_t n, int verbose, int device_id,
+                                    uint8_t *bytes_out, uint64_t cap, uint64_t *n_out);
+
 #ifdef __cplusplus
 }
 #endif

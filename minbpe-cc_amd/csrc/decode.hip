@@ -1,0 +1,636 @@
+// Decode on the device: Tokenizer::decode (reference Tokenizer.h:725-751) for a whole token stream at once.
+//
+// The reference appends, token by token, the special's string (the reverse lookup is asked FIRST, :729-733), nothing
+// for an id beyond the vocabulary (a warning, :734-737) or vocab[id] (:738-741), where vocab[256 + k] =
+// vocab[a_k] ++ vocab[b_k] (:562-564).  That is: per token a byte length, an exclusive prefix sum of the lengths, and
+// a copy of every token's bytes to its offset.
+//
+// Device data of a decoder (built once on the host): len[E] (u32), off[E] (u64) and one flat byte blob.  Entries
+// 0 .. V-1 (V = 256 + n_merges) are the vocabulary, with the entries of ids that a special overrides patched; the
+// specials with ids >= V follow as entries V .. E-1 and are found through a small open-addressed table that is
+// probed only for ids >= V.
+//
+// A span = 1,024 consecutive tokens = the unit one wave walks, as in encode.hip and wide.hip.
+//   k_dec_len<F>     token -> length; per span the byte total (u64); ids that decode to nothing are counted
+//   k_dec_scan64     exclusive 64-bit scan of the span totals (one workgroup, 4,096 spans per step)
+//   k_dec_write<F>   per span: prefix sums of the lengths into LDS, then OUTPUT-centric copying: the span's output
+//                    range is cut at the 16-byte boundaries of the global output address, a lane owns one piece per
+//                    iteration, finds the token that holds the piece's first byte by binary search in the LDS offsets,
+//                    gathers from the blob and stores one dwordx4.  Only the first and the last piece of a span, which
+//                    it shares with its neighbours, are written byte by byte.  A token of any length costs what its
+//                    bytes cost.
+// F is how a token is read (DecFmt): all of them yield "id or nothing".
+//
+// Bytes moved per decode: the tokens twice (4 B or 2 B each), the output once; len / off / blob are gathered from
+// cache (a few hundred KB to a few MB for text vocabularies).
+#include "mbpe.h"
+#include "../host/mbpe_host.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <new>
+#include <string>
+#include <utility>
+#include <vector>
+
+namespace {
+
+constexpr int kWave = 64;
+constexpr int kSpan = 1024;
+constexpr int kSpanIters = kSpan / kWave;
+constexpr int kDecThreads = 256;           // 4 waves = 4 spans per workgroup
+constexpr int kDecWaves = kDecThreads / kWave;
+constexpr int kScanThreads = 1024;
+constexpr int kScanPer = 4;                // spans per thread and step of the scan
+constexpr uint32_t kNone = 0xFFFFFFFFu;
+constexpr uint32_t kBlobPad = 16;          // a 16-byte gather may read this far beyond an entry
+
+// how a token is read; the 16-bit layouts are those of mbpe_stream_device (mbpe.h)
+enum DecFmt {
+    kFmtU32 = 0,        // plain uint32_t ids
+    kFmtU32End = 1,     // bit 31 = last token of its chunk (encode.hip, wide.hip); all-ones = hole
+    kFmtU16 = 2,        // 16-bit slots, all-ones = hole
+    kFmtU16End = 3,     // ... bit 15 = last token of its chunk
+    kFmtU16Barrier = 4  // ... one slot value is the barrier after a chunk, no token
+};
+
+struct DecTab {
+    const uint32_t *len;                   // [n_entries]
+    const unsigned long long *off;         // [n_entries] into blob
+    const uint8_t *blob;
+    const uint32_t *sp_key;                // ids >= V that are specials (open addressing, linear probing)
+    const uint32_t *sp_ent;                // their entries; kNone = free slot
+    uint32_t V;                            // 256 + n_merges
+    uint32_t sp_mask;                      // capacity - 1
+    uint32_t sp_shift;                     // 32 - log2(capacity)
+    uint32_t sp_n;                         // 0: no such special, the table is not probed
+};
+
+__host__ __device__ inline uint32_t dec_hash(uint32_t id, uint32_t shift) { return (id * 0x9E3779B1u) >> shift; }
+
+__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (kWave - 1); }
+
+// slot i -> id; false: the slot holds no token (hole, barrier)
+template <int F>
+__device__ __forceinline__ bool dec_read(const void *__restrict__ tok, uint64_t i, uint32_t barrier, uint32_t *id) {
+    if (F == kFmtU32 || F == kFmtU32End) {
+        const uint32_t t = static_cast<const uint32_t *>(tok)[i];
+        if (F == kFmtU32End && t == kNone) return false;
+        *id = F == kFmtU32End ? (t & 0x7FFFFFFFu) : t;
+        return true;
+    }
+    const uint32_t s = static_cast<const uint16_t *>(tok)[i];
+    if (s == 0xFFFFu) return false;
+    if (F == kFmtU16Barrier && s == barrier) return false;
+    *id = F == kFmtU16End ? (s & 0x7FFFu) : s;
+    return true;
+}
+
+// id -> entry of len / off; false: the id decodes to nothing (Tokenizer.h:734-737)
+__device__ __forceinline__ bool dec_entry(const DecTab &tab, uint32_t id, uint32_t *ent) {
+    if (id < tab.V) { *ent = id; return true; }
+    if (!tab.sp_n) return false;
+    uint32_t h = dec_hash(id, tab.sp_shift);
+    for (;;) {
+        const uint32_t e = tab.sp_ent[h];
+        if (e == kNone) return false;
+        if (tab.sp_key[h] == id) { *ent = e; return true; }
+        h = (h + 1) & tab.sp_mask;
+    }
+}
+
+template <int F>
+__global__ __launch_bounds__(kDecThreads) void k_dec_len(const void *__restrict__ tok, uint64_t n, uint32_t barrier,
+                                                         DecTab tab, unsigned long long *__restrict__ span_total,
+                                                         unsigned long long *__restrict__ n_invalid) {
+    const uint64_t span = (uint64_t)blockIdx.x * kDecWaves + threadIdx.x / kWave;
+    const uint64_t base = span * kSpan;
+    if (base >= n) return;
+    const uint32_t lane = lane_id();
+    unsigned long long sum = 0;
+    uint32_t bad = 0;
+    for (int it = 0; it < kSpanIters; ++it) {
+        const uint64_t i = base + (uint64_t)it * kWave + lane;
+        uint32_t id, ent;
+        if (i < n && dec_read<F>(tok, i, barrier, &id)) {
+            if (dec_entry(tab, id, &ent)) sum += tab.len[ent];
+            else ++bad;
+        }
+    }
+    for (int d = kWave / 2; d; d >>= 1) {
+        sum += __shfl_xor(sum, d, kWave);
+        bad += __shfl_xor(bad, d, kWave);
+    }
+    if (lane == 0) {
+        span_total[span] = sum;
+        if (bad) atomicAdd(n_invalid, (unsigned long long)bad);
+    }
+}
+
+// v[s] <- sum of v[0 .. s-1], in place; *total <- the sum of all.  One workgroup walks the spans in steps of
+// kScanThreads * kScanPer with a running carry (encode.hip's scans are 32-bit and one slice per thread).
+__global__ __launch_bounds__(kScanThreads) void k_dec_scan64(unsigned long long *__restrict__ v, uint64_t n,
+                                                             unsigned long long *__restrict__ total) {
+    __shared__ unsigned long long wsum[kScanThreads / kWave];
+    const uint32_t lane = lane_id(), wave = threadIdx.x / kWave;
+    unsigned long long carry = 0;
+    for (uint64_t base = 0; base < n; base += (uint64_t)kScanThreads * kScanPer) {
+        const uint64_t i0 = base + (uint64_t)threadIdx.x * kScanPer;
+        unsigned long long x[kScanPer], t = 0;
+        for (int j = 0; j < kScanPer; ++j) {
+            x[j] = i0 + j < n ? v[i0 + j] : 0ull;
+            t += x[j];
+        }
+        unsigned long long incl = t;
+        for (int d = 1; d < kWave; d <<= 1) {
+            const unsigned long long up = __shfl_up(incl, d, kWave);
+            if (lane >= (uint32_t)d) incl += up;
+        }
+        if (lane == kWave - 1) wsum[wave] = incl;
+        __syncthreads();
+        unsigned long long before = 0, tile = 0;
+        for (uint32_t w = 0; w < kScanThreads / kWave; ++w) {
+            const unsigned long long s = wsum[w];
+            if (w < wave) before += s;
+            tile += s;
+        }
+        unsigned long long o = carry + before + incl - t;
+        for (int j = 0; j < kScanPer; ++j) {
+            if (i0 + j < n) v[i0 + j] = o;
+            o += x[j];
+        }
+        carry += tile;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// 16 bytes from any address (the blob is padded so that this never leaves it)
+__device__ __forceinline__ unsigned __int128 load16(const uint8_t *p) {
+    unsigned __int128 v;
+    __builtin_memcpy(&v, p, 16);
+    return v;
+}
+
+template <int F>
+__global__ __launch_bounds__(kDecThreads) void k_dec_write(const void *__restrict__ tok, uint64_t n, uint32_t barrier,
+                                                           DecTab tab, const unsigned long long *__restrict__ span_off,
+                                                           uint8_t *__restrict__ out) {
+    // per wave: s_off[j] = bytes of the span before its token j (s_off[kSpan] = the span's total, below 2^32:
+    // MBPE_DECODER_MAX_ENTRY), s_src[j] = where token j's bytes start in the blob (below 2^32: MBPE_DECODER_MAX_BLOB)
+    __shared__ uint32_t s_off[kDecWaves][kSpan + 1];
+    __shared__ uint32_t s_src[kDecWaves][kSpan];
+    const uint32_t w = threadIdx.x / kWave, lane = lane_id();
+    const uint64_t span = (uint64_t)blockIdx.x * kDecWaves + w;
+    const uint64_t base = span * kSpan;
+    const bool active = base < n;
+    if (active) {
+        uint32_t run = 0;
+        for (int it = 0; it < kSpanIters; ++it) {
+            const uint64_t i = base + (uint64_t)it * kWave + lane;
+            uint32_t id, ent, l = 0, src = 0;
+            if (i < n && dec_read<F>(tok, i, barrier, &id) && dec_entry(tab, id, &ent)) {
+                l = tab.len[ent];
+                src = (uint32_t)tab.off[ent];
+            }
+            uint32_t incl = l;
+            for (int d = 1; d < kWave; d <<= 1) {
+                const uint32_t up = __shfl_up(incl, d, kWave);
+                if (lane >= (uint32_t)d) incl += up;
+            }
+            s_off[w][it * kWave + lane] = run + incl - l;
+            s_src[w][it * kWave + lane] = src;
+            run += __shfl(incl, kWave - 1, kWave);
+        }
+        if (lane == 0) s_off[w][kSpan] = run;
+    }
+    __syncthreads();
+    if (!active) return;
+    const uint32_t T = s_off[w][kSpan];
+    if (T == 0) return;                              // a span that decodes to nothing
+    const uint64_t out_addr = (uint64_t)(uintptr_t)out;
+    const uint64_t A = out_addr + span_off[span];    // address of the span's first output byte
+    const uint64_t B0 = A & ~15ull;
+    const uint64_t n_pieces = (A + T - B0 + 15) >> 4;
+    for (uint64_t p = lane; p < n_pieces; p += kWave) {
+        const uint64_t B = B0 + (p << 4);
+        const uint64_t lo = B > A ? B : A;
+        const uint64_t hi = B + 16 < A + T ? B + 16 : A + T;
+        const uint32_t cnt = (uint32_t)(hi - lo);    // 1 .. 16
+        uint32_t pos = (uint32_t)(lo - A);
+        uint32_t j = 0;                              // the largest j with s_off[j] <= pos: the token that holds byte pos
+        for (uint32_t step = kSpan / 2; step; step >>= 1)
+            if (s_off[w][j + step] <= pos) j += step;
+        unsigned __int128 acc = 0;
+        uint32_t filled = 0;
+        while (filled < cnt) {                       // ends: bytes pos .. hi-A-1 lie in tokens j .. kSpan-1
+            const uint32_t avail = s_off[w][j + 1] - pos;
+            if (avail) {
+                const uint32_t take = avail < cnt - filled ? avail : cnt - filled;
+                unsigned __int128 v = load16(tab.blob + s_src[w][j] + (pos - s_off[w][j]));
+                if (take < 16) v &= ((unsigned __int128)1 << (8 * take)) - 1;
+                acc |= v << (8 * filled);
+                filled += take;
+                pos += take;
+            }
+            ++j;
+        }
+        if (cnt == 16) {
+            u32x4 q;
+            q.x = (uint32_t)acc;
+            q.y = (uint32_t)(acc >> 32);
+            q.z = (uint32_t)(acc >> 64);
+            q.w = (uint32_t)(acc >> 96);
+            *static_cast<u32x4 *>(__builtin_assume_aligned(out + (B - out_addr), 16)) = q;
+        } else {                                     // the span's first or last piece: shared with a neighbour
+            uint8_t *dst = out + (lo - out_addr);
+            for (uint32_t b = 0; b < cnt; ++b) dst[b] = (uint8_t)(acc >> (8 * b));
+        }
+    }
+}
+
+std::string hip_err(const char *what, hipError_t e) { return std::string(what) + ": " + hipGetErrorString(e); }
+
+#define DCHK(expr)                                                            \
+    do {                                                                      \
+        hipError_t e__ = (expr);                                              \
+        if (e__ != hipSuccess) {                                              \
+            mbpe_host::set_last_error(hip_err(#expr, e__));                   \
+            return e__ == hipErrorOutOfMemory ? MBPE_ERR_OOM : MBPE_ERR_HIP;  \
+        }                                                                     \
+    } while (0)
+
+int fail(int code, const char *msg) {
+    mbpe_host::set_last_error(msg);
+    return code;
+}
+
+}  // namespace
+
+struct mbpe_decoder {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    float last_ms = 0.f;
+    // the tables
+    uint32_t *d_len = nullptr, *d_spk = nullptr, *d_spe = nullptr;
+    unsigned long long *d_off = nullptr;
+    uint8_t *d_blob = nullptr;
+    DecTab tab = {};
+    // scratch, grown on demand and kept
+    unsigned long long *d_span = nullptr;     // span totals, then offsets
+    uint64_t cap_spans = 0;
+    unsigned long long *d_res = nullptr;      // [0] decoded length, [1] ids that decoded to nothing
+    void *d_tok = nullptr;                    // staging for tokens that come from the host
+    uint64_t cap_tok = 0;
+    uint8_t *d_out = nullptr;                 // staging for output that goes to the host
+    uint64_t cap_out = 0;
+};
+
+namespace {
+
+template <typename T>
+int grow(T **p, uint64_t *cap, uint64_t want_bytes) {
+    if (*cap >= want_bytes && *p) return MBPE_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    DCHK(hipMalloc(reinterpret_cast<void **>(p), want_bytes));
+    *cap = want_bytes;
+    return MBPE_OK;
+}
+
+template <int F>
+void launch_len(mbpe_decoder *d, const void *tok, uint64_t n, uint32_t barrier, uint32_t grid) {
+    hipLaunchKernelGGL(k_dec_len<F>, dim3(grid), dim3(kDecThreads), 0, d->stream, tok, n, barrier, d->tab, d->d_span,
+                       d->d_res + 1);
+}
+template <int F>
+void launch_write(mbpe_decoder *d, const void *tok, uint64_t n, uint32_t barrier, uint32_t grid, uint8_t *out) {
+    hipLaunchKernelGGL(k_dec_write<F>, dim3(grid), dim3(kDecThreads), 0, d->stream, tok, n, barrier, d->tab, d->d_span,
+                       out);
+}
+
+// lengths + scan of n device-resident tokens; ev0 is recorded in front
+int dec_measure(mbpe_decoder *d, int fmt, const void *tok, uint64_t n, uint32_t barrier, uint64_t *total,
+                uint64_t *invalid) {
+    const uint64_t n_spans = (n + kSpan - 1) / kSpan;
+    const uint32_t grid = (uint32_t)((n_spans + kDecWaves - 1) / kDecWaves);
+    int rc = grow(&d->d_span, &d->cap_spans, (n_spans + 1) * 8);
+    if (rc != MBPE_OK) return rc;
+    DCHK(hipMemsetAsync(d->d_res, 0, 16, d->stream));
+    DCHK(hipEventRecord(d->ev0, d->stream));
+    if (n) {
+        switch (fmt) {
+            case kFmtU32: launch_len<kFmtU32>(d, tok, n, barrier, grid); break;
+            case kFmtU32End: launch_len<kFmtU32End>(d, tok, n, barrier, grid); break;
+            case kFmtU16: launch_len<kFmtU16>(d, tok, n, barrier, grid); break;
+            case kFmtU16End: launch_len<kFmtU16End>(d, tok, n, barrier, grid); break;
+            default: launch_len<kFmtU16Barrier>(d, tok, n, barrier, grid); break;
+        }
+        hipLaunchKernelGGL(k_dec_scan64, dim3(1), dim3(kScanThreads), 0, d->stream, d->d_span, n_spans, d->d_res);
+    }
+    unsigned long long res[2] = {0, 0};
+    DCHK(hipMemcpyAsync(res, d->d_res, 16, hipMemcpyDeviceToHost, d->stream));
+    DCHK(hipStreamSynchronize(d->stream));
+    DCHK(hipGetLastError());
+    *total = res[0];
+    *invalid = res[1];
+    return MBPE_OK;
+}
+
+// the copy, after dec_measure of the same tokens; records ev1 and waits
+int dec_write(mbpe_decoder *d, int fmt, const void *tok, uint64_t n, uint32_t barrier, uint8_t *out_dev, bool wrote) {
+    if (wrote && n) {
+        const uint64_t n_spans = (n + kSpan - 1) / kSpan;
+        const uint32_t grid = (uint32_t)((n_spans + kDecWaves - 1) / kDecWaves);
+        switch (fmt) {
+            case kFmtU32: launch_write<kFmtU32>(d, tok, n, barrier, grid, out_dev); break;
+            case kFmtU32End: launch_write<kFmtU32End>(d, tok, n, barrier, grid, out_dev); break;
+            case kFmtU16: launch_write<kFmtU16>(d, tok, n, barrier, grid, out_dev); break;
+            case kFmtU16End: launch_write<kFmtU16End>(d, tok, n, barrier, grid, out_dev); break;
+            default: launch_write<kFmtU16Barrier>(d, tok, n, barrier, grid, out_dev); break;
+        }
+    }
+    DCHK(hipEventRecord(d->ev1, d->stream));
+    DCHK(hipStreamSynchronize(d->stream));
+    DCHK(hipGetLastError());
+    DCHK(hipEventElapsedTime(&d->last_ms, d->ev0, d->ev1));
+    return MBPE_OK;
+}
+
+// tokens / slots in any layout -> bytes; the common body of the three entry points
+int dec_run(mbpe_decoder *d, int fmt, const void *tokens, uint64_t n, int tokens_on_device, uint32_t barrier,
+            uint8_t *bytes_out, uint64_t cap, int out_on_device, uint64_t *n_out, uint64_t *n_invalid_out) {
+    *n_out = 0;
+    if (n_invalid_out) *n_invalid_out = 0;
+    if (n >> 40) return fail(MBPE_ERR_ARG, "more than 2^40 tokens");
+    DCHK(hipSetDevice(d->device));
+    const uint64_t tok_bytes = n * (fmt <= kFmtU32End ? 4 : 2);
+    const void *tok = tokens;
+    if (!tokens_on_device && n) {
+        int rc = grow(&d->d_tok, &d->cap_tok, tok_bytes);
+        if (rc != MBPE_OK) return rc;
+        DCHK(hipMemcpyAsync(d->d_tok, tokens, tok_bytes, hipMemcpyHostToDevice, d->stream));
+        tok = d->d_tok;
+    }
+    uint64_t total = 0, invalid = 0;
+    int rc = dec_measure(d, fmt, tok, n, barrier, &total, &invalid);
+    if (rc != MBPE_OK) return rc;
+    *n_out = total;
+    if (n_invalid_out) *n_invalid_out = invalid;
+    if (!bytes_out) return dec_write(d, fmt, tok, n, barrier, nullptr, false);       // the size query
+    if (cap < total) {
+        (void)dec_write(d, fmt, tok, n, barrier, nullptr, false);
+        return fail(MBPE_ERR_ARG, "bytes_out too small");
+    }
+    if (out_on_device) return dec_write(d, fmt, tok, n, barrier, bytes_out, true);
+    if (total) {
+        rc = grow(&d->d_out, &d->cap_out, total);
+        if (rc != MBPE_OK) return rc;
+    }
+    rc = dec_write(d, fmt, tok, n, barrier, d->d_out, total != 0);
+    if (rc != MBPE_OK) return rc;
+    if (total) {
+        DCHK(hipMemcpyAsync(bytes_out, d->d_out, total, hipMemcpyDeviceToHost, d->stream));
+        DCHK(hipStreamSynchronize(d->stream));
+    }
+    return MBPE_OK;
+}
+
+int slot_format(uint32_t slot_bits, uint32_t end_bit, uint32_t barrier, int *fmt) {
+    if (slot_bits == 32 && barrier == MBPE_NO_BARRIER && (end_bit == 0 || end_bit == 0x80000000u)) {
+        *fmt = end_bit ? kFmtU32End : kFmtU32;
+        return MBPE_OK;
+    }
+    if (slot_bits == 16 && barrier == MBPE_NO_BARRIER && (end_bit == 0 || end_bit == 0x8000u)) {
+        *fmt = end_bit ? kFmtU16End : kFmtU16;
+        return MBPE_OK;
+    }
+    if (slot_bits == 16 && barrier < 0xFFFFu && end_bit == 0) {
+        *fmt = kFmtU16Barrier;
+        return MBPE_OK;
+    }
+    return fail(MBPE_ERR_ARG, "no such slot layout (see mbpe_stream_device)");
+}
+
+}  // namespace
+
+namespace mbpe_host {
+
+int decode_to_string(mbpe_decoder *d, const uint32_t *tokens, uint64_t n, std::string *out, uint64_t *n_invalid) {
+    out->clear();
+    *n_invalid = 0;
+    if (!d || (!tokens && n)) return fail(MBPE_ERR_ARG, "decode_to_string: NULL argument");
+    DCHK(hipSetDevice(d->device));
+    if (n) {
+        int rc = grow(&d->d_tok, &d->cap_tok, n * 4);
+        if (rc != MBPE_OK) return rc;
+        DCHK(hipMemcpyAsync(d->d_tok, tokens, n * 4, hipMemcpyHostToDevice, d->stream));
+    }
+    uint64_t total = 0;
+    int rc = dec_measure(d, kFmtU32, d->d_tok, n, MBPE_NO_BARRIER, &total, n_invalid);
+    if (rc != MBPE_OK) return rc;
+    if (total) {
+        rc = grow(&d->d_out, &d->cap_out, total);
+        if (rc != MBPE_OK) return rc;
+    }
+    rc = dec_write(d, kFmtU32, d->d_tok, n, MBPE_NO_BARRIER, d->d_out, total != 0);
+    if (rc != MBPE_OK) return rc;
+    if (total) {
+        out->resize(total);
+        DCHK(hipMemcpyAsync(&(*out)[0], d->d_out, total, hipMemcpyDeviceToHost, d->stream));
+        DCHK(hipStreamSynchronize(d->stream));
+    }
+    return MBPE_OK;
+}
+
+}  // namespace mbpe_host
+
+extern "C" {
+
+int mbpe_decoder_create(int device_id, const uint32_t *merges, uint32_t n_merges, const uint32_t *special_ids,
+                        const uint8_t *special_bytes, const uint64_t *special_off, uint32_t n_special,
+                        mbpe_decoder **out) {
+    if (!out || (!merges && n_merges) || (n_special && (!special_ids || !special_off)))
+        return fail(MBPE_ERR_ARG, "mbpe_decoder_create: NULL argument");
+    *out = nullptr;
+    if (n_merges > MBPE_MAX_VOCAB_WIDE - 256) return fail(MBPE_ERR_ARG, "n_merges beyond MBPE_MAX_VOCAB_WIDE - 256");
+    for (uint32_t k = 0; k < n_special; ++k)
+        if (special_off[k + 1] < special_off[k]) return fail(MBPE_ERR_ARG, "special_off must be ascending");
+    if (n_special && special_off[n_special] > special_off[0] && !special_bytes)
+        return fail(MBPE_ERR_ARG, "mbpe_decoder_create: NULL argument");
+
+    // host side: lengths first (they can double with every merge), then the blob
+    const uint32_t V = 256 + n_merges;
+    std::vector<uint32_t> len(V);
+    std::vector<unsigned long long> off(V);
+    unsigned long long blob_size = 0;
+    for (uint32_t id = 0; id < V; ++id) {
+        unsigned long long l = 1;
+        if (id >= 256) {
+            // a side that names an id not yet defined contributes nothing (Tokenizer::rebuild_vocab)
+            const uint32_t a = merges[2 * (id - 256)], b = merges[2 * (id - 256) + 1];
+            l = (a < id ? len[a] : 0ull) + (b < id ? len[b] : 0ull);
+        }
+        if (l > MBPE_DECODER_MAX_ENTRY) return fail(MBPE_ERR_OOM, "a vocabulary entry exceeds MBPE_DECODER_MAX_ENTRY");
+        len[id] = (uint32_t)l;
+        off[id] = blob_size;
+        blob_size += l;
+        if (blob_size > MBPE_DECODER_MAX_BLOB) return fail(MBPE_ERR_OOM, "the vocabulary's bytes exceed MBPE_DECODER_MAX_BLOB");
+    }
+    // specials: the last one given for an id holds (special_tokens_reverse_lookup[id] = name)
+    std::vector<uint32_t> sp_of(n_special, 0);      // 1: special k is the one that holds for its id
+    uint32_t n_ext = 0;
+    {
+        std::vector<std::pair<uint32_t, uint32_t>> byid(n_special);
+        for (uint32_t k = 0; k < n_special; ++k) byid[k] = {special_ids[k], k};
+        std::sort(byid.begin(), byid.end());
+        for (uint32_t k = 0; k < n_special; ++k)
+            if (k + 1 == n_special || byid[k + 1].first != byid[k].first) sp_of[byid[k].second] = 1;
+    }
+    for (uint32_t k = 0; k < n_special; ++k) {
+        if (!sp_of[k]) continue;
+        const unsigned long long l = special_off[k + 1] - special_off[k];
+        if (l > MBPE_DECODER_MAX_ENTRY) return fail(MBPE_ERR_OOM, "a special token exceeds MBPE_DECODER_MAX_ENTRY");
+        blob_size += l;
+        if (blob_size > MBPE_DECODER_MAX_BLOB) return fail(MBPE_ERR_OOM, "the vocabulary's bytes exceed MBPE_DECODER_MAX_BLOB");
+        if (special_ids[k] >= V) ++n_ext;
+    }
+    std::vector<uint8_t> blob;
+    try {
+        blob.resize(blob_size + kBlobPad);
+        len.reserve((size_t)V + n_ext);
+        off.reserve((size_t)V + n_ext);
+    } catch (const std::bad_alloc &) {
+        return fail(MBPE_ERR_OOM, "mbpe_decoder_create: host allocation failed");
+    }
+    for (uint32_t id = 0; id < 256; ++id) blob[off[id]] = (uint8_t)id;
+    for (uint32_t id = 256; id < V; ++id) {
+        const uint32_t a = merges[2 * (id - 256)], b = merges[2 * (id - 256) + 1];
+        uint8_t *dst = blob.data() + off[id];
+        if (a < id) { memcpy(dst, blob.data() + off[a], len[a]); dst += len[a]; }
+        if (b < id) memcpy(dst, blob.data() + off[b], len[b]);
+    }
+    uint32_t sp_bits = 2;
+    while ((1u << sp_bits) < 2 * n_ext + 2) ++sp_bits;
+    const uint32_t sp_cap = 1u << sp_bits;
+    std::vector<uint32_t> spk(sp_cap, 0), spe(sp_cap, kNone);
+    unsigned long long at = off[V - 1] + len[V - 1];      // the specials' bytes follow the vocabulary's
+    for (uint32_t k = 0; k < n_special; ++k) {
+        if (!sp_of[k]) continue;
+        const uint32_t l = (uint32_t)(special_off[k + 1] - special_off[k]), id = special_ids[k];
+        if (l) memcpy(blob.data() + at, special_bytes + special_off[k], l);
+        if (id < V) {                               // overrides the vocabulary entry: the reverse lookup is asked first
+            len[id] = l;
+            off[id] = at;
+        } else {
+            uint32_t h = dec_hash(id, 32 - sp_bits);
+            while (spe[h] != kNone) h = (h + 1) & (sp_cap - 1);
+            spk[h] = id;
+            spe[h] = (uint32_t)len.size();
+            len.push_back(l);
+            off.push_back(at);
+        }
+        at += l;
+    }
+
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || device_id < 0 || device_id >= n_dev)
+        return fail(MBPE_ERR_NO_DEVICE, "no usable HIP device (the MI355X path has no CPU fallback)");
+    mbpe_decoder *d = new mbpe_decoder;
+    d->device = device_id;
+    auto build = [&]() -> int {
+        DCHK(hipSetDevice(device_id));
+        DCHK(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+        DCHK(hipEventCreate(&d->ev0));
+        DCHK(hipEventCreate(&d->ev1));
+        DCHK(hipMalloc(&d->d_len, len.size() * 4));
+        DCHK(hipMalloc(&d->d_off, off.size() * 8));
+        DCHK(hipMalloc(&d->d_blob, blob.size()));
+        DCHK(hipMalloc(&d->d_spk, (size_t)sp_cap * 4));
+        DCHK(hipMalloc(&d->d_spe, (size_t)sp_cap * 4));
+        DCHK(hipMalloc(&d->d_res, 16));
+        DCHK(hipMemcpyAsync(d->d_len, len.data(), len.size() * 4, hipMemcpyHostToDevice, d->stream));
+        DCHK(hipMemcpyAsync(d->d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, d->stream));
+        DCHK(hipMemcpyAsync(d->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, d->stream));
+        DCHK(hipMemcpyAsync(d->d_spk, spk.data(), (size_t)sp_cap * 4, hipMemcpyHostToDevice, d->stream));
+        DCHK(hipMemcpyAsync(d->d_spe, spe.data(), (size_t)sp_cap * 4, hipMemcpyHostToDevice, d->stream));
+        DCHK(hipStreamSynchronize(d->stream));
+        return MBPE_OK;
+    };
+    const int rc = build();
+    if (rc != MBPE_OK) {
+        const std::string keep = mbpe_host::last_error();
+        mbpe_decoder_destroy(d);
+        mbpe_host::set_last_error(keep);
+        return rc;
+    }
+    d->tab = {d->d_len, d->d_off, d->d_blob, d->d_spk, d->d_spe, V, sp_cap - 1, 32 - sp_bits, n_ext};
+    *out = d;
+    return MBPE_OK;
+}
+
+void mbpe_decoder_destroy(mbpe_decoder *d) {
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    (void)hipFree(d->d_len); (void)hipFree(d->d_off); (void)hipFree(d->d_blob); (void)hipFree(d->d_spk);
+    (void)hipFree(d->d_spe); (void)hipFree(d->d_span); (void)hipFree(d->d_res); (void)hipFree(d->d_tok);
+    (void)hipFree(d->d_out);
+    if (d->ev0) (void)hipEventDestroy(d->ev0);
+    if (d->ev1) (void)hipEventDestroy(d->ev1);
+    if (d->stream) (void)hipStreamDestroy(d->stream);
+    delete d;
+}
+
+int mbpe_decode_tokens(mbpe_decoder *d, const uint32_t *tokens, uint64_t n_tokens, int tokens_on_device,
+                       uint8_t *bytes_out, uint64_t cap, int out_on_device, uint64_t *n_out, uint64_t *n_invalid_out) {
+    if (!d || !n_out || (!tokens && n_tokens)) return fail(MBPE_ERR_ARG, "mbpe_decode_tokens: NULL argument");
+    return dec_run(d, kFmtU32, tokens, n_tokens, tokens_on_device, MBPE_NO_BARRIER, bytes_out, cap, out_on_device, n_out,
+                   n_invalid_out);
+}
+
+int mbpe_decode_slots(mbpe_decoder *d, const void *slots, uint64_t n_slots, uint32_t slot_bits, uint32_t end_bit,
+                      uint32_t barrier, uint8_t *bytes_out, uint64_t cap, int out_on_device, uint64_t *n_out,
+                      uint64_t *n_invalid_out) {
+    if (!d || !n_out || (!slots && n_slots)) return fail(MBPE_ERR_ARG, "mbpe_decode_slots: NULL argument");
+    int fmt = 0;
+    const int rc = slot_format(slot_bits, end_bit, barrier, &fmt);
+    if (rc != MBPE_OK) return rc;
+    return dec_run(d, fmt, slots, n_slots, 1, barrier, bytes_out, cap, out_on_device, n_out, n_invalid_out);
+}
+
+int mbpe_decoder_kernel_ms(const mbpe_decoder *d, float *ms_out) {
+    if (!d || !ms_out) return fail(MBPE_ERR_ARG, "mbpe_decoder_kernel_ms: NULL argument");
+    *ms_out = d->last_ms;
+    return MBPE_OK;
+}
+
+int mbpe_decode_stream(mbpe_ctx *ctx, uint8_t *bytes_out, uint64_t cap, int out_on_device, uint64_t *n_out) {
+    if (!ctx || !n_out) return fail(MBPE_ERR_ARG, "mbpe_decode_stream: NULL argument");
+    *n_out = 0;
+    const void *slots = nullptr;
+    uint64_t n_slots = 0;
+    uint32_t bits = 0, end_bit = 0, barrier = MBPE_NO_BARRIER, n_merges = 0;
+    int rc = mbpe_stream_device(ctx, &slots, &n_slots, &bits, &end_bit, &barrier);
+    if (rc != MBPE_OK) return rc;
+    rc = mbpe_train_result(ctx, nullptr, nullptr, 0, &n_merges);
+    if (rc != MBPE_OK) return rc;
+    std::vector<uint32_t> merges(2 * (size_t)n_merges + 2);
+    rc = mbpe_train_result(ctx, merges.data(), nullptr, n_merges, &n_merges);
+    if (rc != MBPE_OK) return rc;
+    mbpe_decoder *d = nullptr;
+    rc = mbpe_decoder_create(mbpe_host::ctx_device(ctx), merges.data(), n_merges, nullptr, nullptr, nullptr, 0, &d);
+    if (rc != MBPE_OK) return rc;
+    rc = mbpe_decode_slots(d, slots, n_slots, bits, end_bit, barrier, bytes_out, cap, out_on_device, n_out, nullptr);
+    const std::string keep = rc == MBPE_OK ? std::string() : std::string(mbpe_host::last_error());
+    mbpe_decoder_destroy(d);
+    if (rc != MBPE_OK) mbpe_host::set_last_error(keep);
+    return rc;
+}
+
+}  // extern "C"

@@ -250,11 +250,10 @@ bool stoi_value(const uint8_t *s, uint64_t n, long long *out) {
     return true;
 }
 
-}  // namespace
-
-extern "C" int mbpe_encode_chunks(int device_id, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off,
-                                  uint64_t n_chunks, const uint32_t *merges, uint32_t n_merges, uint32_t *tokens_out,
-                                  uint64_t cap, uint64_t *n_out, uint32_t *n_passes_out) {
+// out_on_device: tokens_out is device memory and receives the tokens with their chunk-end flags
+int encode_chunks(int device_id, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off, uint64_t n_chunks,
+                  const uint32_t *merges, uint32_t n_merges, uint32_t *tokens_out, uint64_t cap, uint64_t *n_out,
+                  uint32_t *n_passes_out, bool out_on_device) {
     if (!n_out || (!text && n_bytes) || (!merges && n_merges)) {
         mbpe_host::set_last_error("mbpe_encode_chunks: NULL argument");
         return MBPE_ERR_ARG;
@@ -364,8 +363,13 @@ extern "C" int mbpe_encode_chunks(int device_id, const uint8_t *text, uint64_t n
         if (n_passes_out) *n_passes_out = passes;
         if (tokens_out) {
             if (cap < n) { mbpe_host::set_last_error("tokens_out too small"); rc = MBPE_ERR_ARG; goto done; }
-            if (n) HIPCHK(hipMemcpy(tokens_out, tok[cur], n * 4, hipMemcpyDeviceToHost));
-            for (uint64_t i = 0; i < n; ++i) tokens_out[i] &= kIdMask;      // strip the chunk-end flags
+            if (out_on_device) {
+                if (n) HIPCHK(hipMemcpyAsync(tokens_out, tok[cur], n * 4, hipMemcpyDeviceToDevice, stream));
+                HIPCHK(hipStreamSynchronize(stream));
+            } else {
+                if (n) HIPCHK(hipMemcpy(tokens_out, tok[cur], n * 4, hipMemcpyDeviceToHost));
+                for (uint64_t i = 0; i < n; ++i) tokens_out[i] &= kIdMask;      // strip the chunk-end flags
+            }
         }
     }
 done:
@@ -374,4 +378,21 @@ done:
     (void)hipFree(d_keys); (void)hipFree(d_vals); (void)hipFree(d_singles);
     if (stream) (void)hipStreamDestroy(stream);
     return rc;
+}
+
+}  // namespace
+
+extern "C" int mbpe_encode_chunks(int device_id, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off,
+                                  uint64_t n_chunks, const uint32_t *merges, uint32_t n_merges, uint32_t *tokens_out,
+                                  uint64_t cap, uint64_t *n_out, uint32_t *n_passes_out) {
+    return encode_chunks(device_id, text, n_bytes, chunk_off, n_chunks, merges, n_merges, tokens_out, cap, n_out,
+                         n_passes_out, false);
+}
+
+extern "C" int mbpe_encode_chunks_device(int device_id, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off,
+                                         uint64_t n_chunks, const uint32_t *merges, uint32_t n_merges,
+                                         uint32_t *tokens_dev_out, uint64_t cap, uint64_t *n_out,
+                                         uint32_t *n_passes_out) {
+    return encode_chunks(device_id, text, n_bytes, chunk_off, n_chunks, merges, n_merges, tokens_dev_out, cap, n_out,
+                         n_passes_out, true);
 }

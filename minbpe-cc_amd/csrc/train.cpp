@@ -486,6 +486,10 @@ int do_compact(mbpe_ctx *c) {
 
 }  // namespace
 
+namespace mbpe_host {
+int ctx_device(const mbpe_ctx *c) { return c->device; }
+}  // namespace mbpe_host
+
 extern "C" {
 
 int mbpe_create(int device_id, mbpe_ctx **out) {

@@ -65,7 +65,8 @@ void usage() {
                  "  -c,--conflict-resolution TEXT:{first,lexical}\n"
                  "                              Conflict resolution strategy: 'first' or 'lexical'\n"
                  "  --device INT                HIP device used for training (default 0)\n"
-                 "  --device-encode             When encoding, apply the merges on the HIP device (--device)\n";
+                 "  --device-encode             When encoding, apply the merges on the HIP device (--device)\n"
+                 "  --device-decode             When decoding, expand the tokens on the HIP device (--device)\n";
 }
 
 }  // namespace
@@ -73,7 +74,8 @@ void usage() {
 int main(int argc, char *argv[]) {
     std::string input_path, output_path, special_token_path, encoder = "gpt4", model_path = "./output.model";
     std::string conflict_resolution_str = "first";
-    bool train = false, decode = false, encode = false, write_vocab = false, verbose = false, device_encode = false;
+    bool train = false, decode = false, encode = false, write_vocab = false, verbose = false, device_encode = false,
+         device_decode = false;
     int vocab_size = 512, device = 0;
 
     // option parsing (the reference uses CLI11, :93-133)
@@ -112,6 +114,7 @@ int main(int argc, char *argv[]) {
         else if (arg == "-e" || arg == "--encode") encode = true;
         else if (arg == "-w" || arg == "--write-vocab") write_vocab = true;
         else if (arg == "--device-encode") device_encode = true;
+        else if (arg == "--device-decode") device_decode = true;
         else if (arg == "-v" || arg == "--verbose") verbose = true;
         else { std::cerr << "The following argument was not expected: " << arg << "\n"; return 109; }
     }
@@ -199,12 +202,21 @@ int main(int argc, char *argv[]) {
         std::string err;
         if (load_encoding(input_path, &input, &err)) {
             uint64_t n = 0;
-            mbpe_tok_decode(rt, input.data(), input.size(), 0, nullptr, 0, &n);
+            int drc = device_decode ? mbpe_tok_decode_device(rt, input.data(), input.size(), 0, device, nullptr, 0, &n)
+                                    : mbpe_tok_decode(rt, input.data(), input.size(), 0, nullptr, 0, &n);
             std::string decoded(n, '\0');
-            mbpe_tok_decode(rt, input.data(), input.size(), verbose, reinterpret_cast<uint8_t *>(&decoded[0]), n, &n);
-            std::cout << "Writing " << decoded.size() << " decoded tokens to " << output_path << "\n";
-            std::ofstream file(output_path);
-            if (file) file << decoded;
+            uint8_t *dst = reinterpret_cast<uint8_t *>(&decoded[0]);
+            if (drc == MBPE_OK)
+                drc = device_decode ? mbpe_tok_decode_device(rt, input.data(), input.size(), verbose, device, dst, n, &n)
+                                    : mbpe_tok_decode(rt, input.data(), input.size(), verbose, dst, n, &n);
+            if (drc != MBPE_OK) {
+                std::cerr << "Error: " << mbpe_last_error() << "\n";
+                rc = -1;
+            } else {
+                std::cout << "Writing " << decoded.size() << " decoded tokens to " << output_path << "\n";
+                std::ofstream file(output_path);
+                if (file) file << decoded;
+            }
         } else {
             std::cerr << "Failed with error: " << err << "\n";
         }

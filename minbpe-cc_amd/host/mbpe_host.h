@@ -11,6 +11,9 @@
 #include <string>
 #include <vector>
 
+struct mbpe_ctx;
+struct mbpe_decoder;
+
 namespace mbpe_host {
 
 // last error text of the calling thread (returned by mbpe_last_error())
@@ -22,6 +25,13 @@ struct CodedError : std::runtime_error {
     int code;
     CodedError(int c, const std::string &msg) : std::runtime_error(msg), code(c) {}
 };
+
+// HIP device of a training context (csrc/train.cpp)
+int ctx_device(const mbpe_ctx *c);
+
+// mbpe_decode_tokens (csrc/decode.hip) for host tokens into a string that is sized between the length pass and the
+// copy, so that the tokens are uploaded once; returns an mbpe_status
+int decode_to_string(mbpe_decoder *d, const uint32_t *tokens, uint64_t n, std::string *out, uint64_t *n_invalid);
 
 // Tokenizer.h:59-60; nullptr for an unknown encoder name
 const char *split_pattern_for(const std::string &encoder);

@@ -20,6 +20,14 @@ namespace mbpe_host {
 
 Tokenizer::Tokenizer() {}
 
+Tokenizer::~Tokenizer() { drop_decoder(); }
+
+void Tokenizer::drop_decoder() {
+    if (decoder_) mbpe_decoder_destroy(decoder_);
+    decoder_ = nullptr;
+    decoder_device_ = -1;
+}
+
 Tokenizer::Tokenizer(const std::string &pattern) : pattern_(pattern) {
     std::string err;
     if (splitter_.compile(pattern, &err) != MBPE_OK) throw std::runtime_error(err);   // Tokenizer.h:427-431
@@ -58,6 +66,7 @@ void Tokenizer::rebuild_vocab() {      // :843-861 / :562-564
 }
 
 void Tokenizer::set_merges(const std::vector<TokenPair> &m) {
+    drop_decoder();
     merges_ = m;
     merges_lookup_.clear();
     Token idx = 256;
@@ -66,6 +75,7 @@ void Tokenizer::set_merges(const std::vector<TokenPair> &m) {
 }
 
 void Tokenizer::set_special_tokens_from_file(const std::string &input_string) {   // :476-486
+    drop_decoder();
     special_tokens_.clear();
     special_tokens_reverse_lookup_.clear();
     std::istringstream iss(input_string);
@@ -83,6 +93,7 @@ void Tokenizer::set_special_tokens_from_file(const std::string &input_string) { 
 void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTION conflict_resolution,
                       bool verbose, int device) {
     if (vocab_size < 256) throw std::runtime_error("vocab_size must be >= 256");   // assert, :492
+    drop_decoder();
     merges_.clear();
     merges_lookup_.clear();
     initialize_vocab();
@@ -241,9 +252,37 @@ std::vector<Token> Tokenizer::encode(const std::string &text, bool verbose, int 
 }
 
 // :725-751
-std::string Tokenizer::decode(const std::vector<Token> &tokens, bool verbose) {
+std::string Tokenizer::decode(const std::vector<Token> &tokens, bool verbose, int device) {
     if (verbose) std::cout << "Decoding " << tokens.size() << " tokens\n";
     std::string text;
+    if (device >= 0) {
+        if (!decoder_ || decoder_device_ != device) {
+            drop_decoder();
+            std::vector<uint32_t> flat, ids;
+            std::vector<uint64_t> off{0};
+            std::string bytes;
+            flat.reserve(2 * merges_.size());
+            for (const auto &m : merges_) { flat.push_back(m.first); flat.push_back(m.second); }
+            for (const auto &kv : special_tokens_reverse_lookup_) {
+                ids.push_back(kv.first);
+                bytes += kv.second;
+                off.push_back(bytes.size());
+            }
+            const int rc = mbpe_decoder_create(device, flat.data(), static_cast<uint32_t>(merges_.size()), ids.data(),
+                                               reinterpret_cast<const uint8_t *>(bytes.data()), off.data(),
+                                               static_cast<uint32_t>(ids.size()), &decoder_);
+            if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
+            decoder_device_ = device;
+        }
+        uint64_t n_invalid = 0;
+        const int rc = decode_to_string(decoder_, tokens.data(), tokens.size(), &text, &n_invalid);
+        if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
+        if (n_invalid)                              // rare: the reference's warning for each such id, in order (:734-737)
+            for (Token tkn : tokens)
+                if (tkn >= vocab_.size() && !special_tokens_reverse_lookup_.count(tkn))
+                    std::cerr << "Warning: Attempted to decode invalid token ID: " << tkn << "\n";
+        return text;
+    }
     for (Token tkn : tokens) {
         auto sp = special_tokens_reverse_lookup_.find(tkn);
         if (sp != special_tokens_reverse_lookup_.end()) { text += sp->second; continue; }
@@ -269,6 +308,7 @@ bool Tokenizer::load(const std::string &path, bool verbose) {
         std::cerr << "Unexpected version: " << version << "\n";
         return false;
     }
+    drop_decoder();
     merges_lookup_.clear();
     merges_.clear();
     initialize_vocab();
@@ -447,6 +487,25 @@ int mbpe_tok_encode_device(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, i
         memcpy(tokens_out, enc.data(), enc.size() * sizeof(uint32_t));
         return MBPE_OK;
     } catch (const mbpe_host::CodedError &e) {      // mbpe_encode_chunks failed: its own code (no device, memory, HIP, ids)
+        mbpe_host::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        mbpe_host::set_last_error(e.what());
+        return MBPE_ERR_ARG;
+    }
+}
+
+int mbpe_tok_decode_device(mbpe_tokenizer *t, const uint32_t *tokens, uint64_t n, int verbose, int device_id,
+                           uint8_t *bytes_out, uint64_t cap, uint64_t *n_out) {
+    if (!t || (!tokens && n) || !n_out || device_id < 0) return MBPE_ERR_ARG;
+    try {
+        auto s = t->t->decode(std::vector<mbpe_host::Token>(tokens, tokens + n), verbose != 0, device_id);
+        *n_out = s.size();
+        if (!bytes_out) return MBPE_OK;
+        if (cap < s.size()) { mbpe_host::set_last_error("bytes_out too small"); return MBPE_ERR_ARG; }
+        memcpy(bytes_out, s.data(), s.size());
+        return MBPE_OK;
+    } catch (const mbpe_host::CodedError &e) {      // mbpe_decoder_create / mbpe_decode_tokens failed: its own code
         mbpe_host::set_last_error(e.what());
         return e.code;
     } catch (const std::exception &e) {

@@ -26,6 +26,7 @@ public:
     explicit Tokenizer(const std::string &pattern);   // throws std::runtime_error like :427-431
     Tokenizer(const Tokenizer &) = delete;
     Tokenizer &operator=(const Tokenizer &) = delete;
+    ~Tokenizer();
 
     void set_special_tokens_from_file(const std::string &input_string);   // :476-486
     // :489-598; both CONFLICT_RESOLUTION values run on HIP device `device` (mbpe_train)
@@ -33,7 +34,8 @@ public:
                int device = 0);
     // :653-722; device >= 0 runs internal_encode (:325-377) on that HIP device instead of the host
     std::vector<Token> encode(const std::string &text, bool verbose, int device = -1);
-    std::string decode(const std::vector<Token> &tokens, bool verbose);    // :725-751
+    // :725-751; device >= 0 expands the tokens on that HIP device (mbpe_decode_tokens) instead of the host loop
+    std::string decode(const std::vector<Token> &tokens, bool verbose, int device = -1);
     bool load(const std::string &path, bool verbose);                      // :754-872
     bool save(const std::string &path, bool write_vocab);                  // :875-926
 
@@ -56,6 +58,7 @@ private:
     std::vector<std::string> split_on_special(const std::string &text) const;   // :605-650
     std::vector<Token> internal_internal_encode(std::vector<Token> text) const; // :325-367
     void rebuild_vocab();
+    void drop_decoder();                   // the merges or the specials changed
 
     std::string pattern_;
     Splitter splitter_;
@@ -66,6 +69,8 @@ private:
     std::unordered_map<TokenPair, Token, PairHash> merges_lookup_;
     std::vector<TokenPair> merges_;
     std::vector<std::vector<Token>> vocab_;
+    mbpe_decoder *decoder_ = nullptr;      // device tables of decode(..., device), kept until the model changes
+    int decoder_device_ = -1;
 };
 
 }  // namespace mbpe_host

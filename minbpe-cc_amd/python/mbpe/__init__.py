@@ -27,12 +27,14 @@ EXPORTS = [
     "mbpe_comm_exchange_buffer", "mbpe_comm_exchange_done", "mbpe_presplit",
     "mbpe_split_count", "mbpe_split_offsets", "mbpe_split_has_gaps", "mbpe_split_starts", "mbpe_split_ends",
     "mbpe_split_free", "mbpe_load_corpus_ranges", "mbpe_split_pattern", "mbpe_encode_chunks",
+    "mbpe_encode_chunks_device", "mbpe_decoder_create", "mbpe_decoder_destroy", "mbpe_decode_tokens",
+    "mbpe_decode_slots", "mbpe_decoder_kernel_ms", "mbpe_decode_stream",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
     "mbpe_tok_create", "mbpe_tok_destroy", "mbpe_tok_set_special_tokens", "mbpe_tok_train", "mbpe_tok_set_merges",
     "mbpe_tok_get_merges", "mbpe_tok_save", "mbpe_tok_load", "mbpe_tok_encode", "mbpe_tok_encode_device",
-    "mbpe_tok_decode",
+    "mbpe_tok_decode", "mbpe_tok_decode_device",
 ]
 
 
@@ -120,6 +122,15 @@ def lib():
     L.mbpe_split_pattern.argtypes = [ctypes.c_char_p]
     L.mbpe_split_pattern.restype = ctypes.c_char_p
     L.mbpe_encode_chunks.argtypes = [i32, vp, u64, vp, u64, vp, u32, vp, u64, vp, vp]
+    L.mbpe_encode_chunks_device.argtypes = [i32, vp, u64, vp, u64, vp, u32, vp, u64, vp, vp]
+    L.mbpe_decoder_create.argtypes = [i32, vp, u32, vp, vp, vp, u32, ctypes.POINTER(vp)]
+    L.mbpe_decoder_destroy.argtypes = [vp]
+    L.mbpe_decoder_destroy.restype = None
+    L.mbpe_decode_tokens.argtypes = [vp, vp, u64, i32, vp, u64, i32, vp, vp]
+    L.mbpe_decode_slots.argtypes = [vp, vp, u64, u32, u32, u32, vp, u64, i32, vp, vp]
+    L.mbpe_decoder_kernel_ms.argtypes = [vp, vp]
+    L.mbpe_decode_stream.argtypes = [vp, vp, u64, i32, vp]
+    L.mbpe_tok_decode_device.argtypes = [vp, vp, u64, i32, i32, vp, u64, vp]
     L.mbpe_tok_create.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.mbpe_tok_destroy.argtypes = [vp]
     L.mbpe_tok_destroy.restype = None
@@ -199,6 +210,91 @@ def encode_chunks(data, chunk_off, merges, device=0):
                                     m.ctypes.data if len(m) else None, len(m), out.ctypes.data, len(out),
                                     ctypes.byref(n), ctypes.byref(passes)))
     return out[:n.value].copy(), passes.value
+
+
+def encode_chunks_device(data, chunk_off, merges, out_ptr, cap, device=0):
+    """mbpe_encode_chunks_device: the tokens (bit 31 = chunk end) go to device memory at out_ptr (room for cap
+    tokens; 0 to query) -> (token count, passes)."""
+    text = _u8(data)
+    off = None if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.uint64)
+    m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1, 2)
+    n, passes = ctypes.c_uint64(), ctypes.c_uint32()
+    _check(lib().mbpe_encode_chunks_device(device, text.ctypes.data if len(text) else None, len(text),
+                                           None if off is None else off.ctypes.data, 0 if off is None else len(off) - 1,
+                                           m.ctypes.data if len(m) else None, len(m),
+                                           ctypes.c_void_p(out_ptr) if out_ptr else None, cap,
+                                           ctypes.byref(n), ctypes.byref(passes)))
+    return n.value, passes.value
+
+
+class Decoder:
+    """One mbpe_decoder: Tokenizer::decode (Tokenizer.h:725-751) on a HIP device.  specials: {id: bytes}."""
+
+    def __init__(self, merges, specials=None, device=0):
+        self._h = ctypes.c_void_p()
+        m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1, 2)
+        items = list((specials or {}).items())
+        ids = np.array([k for k, _ in items], dtype=np.uint32)
+        blob = b"".join(bytes(v) for _, v in items)
+        off = np.zeros(len(items) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(v) for _, v in items], dtype=np.uint64) if items else []
+        b = np.frombuffer(blob, dtype=np.uint8)
+        _check(lib().mbpe_decoder_create(device, m.ctypes.data if len(m) else None, len(m),
+                                         ids.ctypes.data if len(ids) else None, b.ctypes.data if len(b) else None,
+                                         off.ctypes.data if len(ids) else None, len(ids), ctypes.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().mbpe_decoder_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def decode(self, tokens, with_invalid=False):
+        """Host tokens -> bytes (mbpe_decode_tokens: a size query, then the decode)."""
+        t = np.ascontiguousarray(tokens, dtype=np.uint32)
+        tp = t.ctypes.data if len(t) else None
+        n, bad = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().mbpe_decode_tokens(self._h, tp, len(t), 0, None, 0, 0, ctypes.byref(n), ctypes.byref(bad)))
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        _check(lib().mbpe_decode_tokens(self._h, tp, len(t), 0, out.ctypes.data, n.value, 0, ctypes.byref(n),
+                                        ctypes.byref(bad)))
+        data = out[:n.value].tobytes()
+        return (data, bad.value) if with_invalid else data
+
+    def decode_device(self, ptr, n_tokens, out_ptr, cap):
+        """n_tokens uint32 ids in device memory at ptr -> bytes in device memory at out_ptr (0: size query; room for
+        cap bytes) -> (decoded length, ids that decoded to nothing)."""
+        n, bad = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().mbpe_decode_tokens(self._h, ctypes.c_void_p(ptr) if ptr else None, n_tokens, 1,
+                                        ctypes.c_void_p(out_ptr) if out_ptr else None, cap, 1,
+                                        ctypes.byref(n), ctypes.byref(bad)))
+        return n.value, bad.value
+
+    def decode_slots_device(self, ptr, n_slots, slot_bits, end_bit, barrier, out_ptr, cap):
+        """The same for device-resident slots in a layout of Trainer.stream_device() (mbpe_decode_slots)."""
+        n, bad = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().mbpe_decode_slots(self._h, ctypes.c_void_p(ptr) if ptr else None, n_slots, slot_bits, end_bit,
+                                       0xFFFFFFFF if barrier is None else barrier,
+                                       ctypes.c_void_p(out_ptr) if out_ptr else None, cap, 1,
+                                       ctypes.byref(n), ctypes.byref(bad)))
+        return n.value, bad.value
+
+    def kernel_ms(self):
+        """Device time of the latest call (mbpe_decoder_kernel_ms)."""
+        ms = ctypes.c_float()
+        _check(lib().mbpe_decoder_kernel_ms(self._h, ctypes.byref(ms)))
+        return ms.value
 
 
 class Trainer:
@@ -343,6 +439,20 @@ class Trainer:
                                         ctypes.byref(bar)))
         return p.value, n.value, bits.value, end.value, (None if bar.value == 0xFFFFFFFF else bar.value)
 
+    def decode_stream(self):
+        """The live stream expanded with the merges made so far (mbpe_decode_stream) -> bytes."""
+        n = ctypes.c_uint64()
+        _check(lib().mbpe_decode_stream(self._h, None, 0, 0, ctypes.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        _check(lib().mbpe_decode_stream(self._h, out.ctypes.data, n.value, 0, ctypes.byref(n)))
+        return out[:n.value].tobytes()
+
+    def decode_stream_device(self, out_ptr, cap):
+        """The same into device memory at out_ptr (0: size query; room for cap bytes) -> decoded length."""
+        n = ctypes.c_uint64()
+        _check(lib().mbpe_decode_stream(self._h, ctypes.c_void_p(out_ptr) if out_ptr else None, cap, 1, ctypes.byref(n)))
+        return n.value
+
     def table_device(self):
         """(device pointer, vshift) of the dense pair table (see mbpe_table_device)."""
         p, v = ctypes.c_void_p(), ctypes.c_uint32()
@@ -435,11 +545,17 @@ class Tokenizer:
                                                 out.ctypes.data, len(out), ctypes.byref(n)))
         return out[:n.value].copy()
 
-    def decode(self, tokens):
+    def decode(self, tokens, device=None):
+        """device None: the host loop; an int: on that HIP device (mbpe_tok_decode_device)."""
         t = np.ascontiguousarray(tokens, dtype=np.uint32)
+        tp = t.ctypes.data if len(t) else None
         n = ctypes.c_uint64()
-        _check(lib().mbpe_tok_decode(self._h, t.ctypes.data if len(t) else None, len(t), 0, None, 0, ctypes.byref(n)))
+        if device is None:
+            _check(lib().mbpe_tok_decode(self._h, tp, len(t), 0, None, 0, ctypes.byref(n)))
+            out = np.zeros(max(n.value, 1), dtype=np.uint8)
+            _check(lib().mbpe_tok_decode(self._h, tp, len(t), 0, out.ctypes.data, len(out), ctypes.byref(n)))
+            return out[:n.value].tobytes()
+        _check(lib().mbpe_tok_decode_device(self._h, tp, len(t), 0, device, None, 0, ctypes.byref(n)))
         out = np.zeros(max(n.value, 1), dtype=np.uint8)
-        _check(lib().mbpe_tok_decode(self._h, t.ctypes.data if len(t) else None, len(t), 0, out.ctypes.data,
-                                     len(out), ctypes.byref(n)))
+        _check(lib().mbpe_tok_decode_device(self._h, tp, len(t), 0, device, out.ctypes.data, len(out), ctypes.byref(n)))
         return out[:n.value].tobytes()
