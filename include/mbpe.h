@@ -321,7 +321,12 @@ MBPE_API int mbpe_set_option(mbpe_ctx *ctx, const char *name, int64_t value);
  *   merges                      2 * n_merges u32, merge k makes token 256 + k; a repeated pair keeps
  *                               the last id (merges_lookup[pair] = idx, Tokenizer.h:579)
  *   tokens_out                  may be NULL to query the count; cap = its capacity in tokens
- *   n_passes_out                optional: stream passes made (the deepest chunk's passes)
+ *   n_out                       required.  Receives the token count whenever the passes ran: with tokens_out NULL, and
+ *                               when cap is smaller -- then the call returns MBPE_ERR_ARG and writes no token.  An argument
+ *                               refused before the passes (NULL text or merges with a count, chunk_off not ascending from
+ *                               0 to n_bytes, a NUL-led chunk's id) leaves 0 there
+ *   n_passes_out                optional: stream passes made (1 + the replacing passes of the deepest chunk; 0 for an
+ *                               empty text), reported together with n_out
  * No CPU fallback: MBPE_ERR_NO_DEVICE without a HIP device.  Token ids must stay below 2^31 - 2. */
 MBPE_API int mbpe_encode_chunks(int device_id, const uint8_t *text, uint64_t n_bytes,
                                 const uint64_t *chunk_off, uint64_t n_chunks,

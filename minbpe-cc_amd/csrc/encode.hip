@@ -254,12 +254,12 @@ bool stoi_value(const uint8_t *s, uint64_t n, long long *out) {
 int encode_chunks(int device_id, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off, uint64_t n_chunks,
                   const uint32_t *merges, uint32_t n_merges, uint32_t *tokens_out, uint64_t cap, uint64_t *n_out,
                   uint32_t *n_passes_out, bool out_on_device) {
+    if (n_out) *n_out = 0;
+    if (n_passes_out) *n_passes_out = 0;
     if (!n_out || (!text && n_bytes) || (!merges && n_merges)) {
         mbpe_host::set_last_error("mbpe_encode_chunks: NULL argument");
         return MBPE_ERR_ARG;
     }
-    *n_out = 0;
-    if (n_passes_out) *n_passes_out = 0;
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || device_id < 0 || device_id >= n_dev) {
         mbpe_host::set_last_error("no usable HIP device (the MI355X path has no CPU fallback)");
@@ -271,6 +271,9 @@ int encode_chunks(int device_id, const uint8_t *text, uint64_t n_bytes, const ui
         mbpe_host::set_last_error("chunk_off must start at 0 and end at n_bytes");
         return MBPE_ERR_ARG;
     }
+    // (every offset is checked before one is used: an offset beyond n_bytes would index the mask and the text below)
+    for (uint64_t c = 0; c < n_chunks; ++c)
+        if (chunk_off[c + 1] < chunk_off[c]) { mbpe_host::set_last_error("chunk_off must be ascending"); return MBPE_ERR_ARG; }
     if (n_bytes == 0) return MBPE_OK;
 
     // host side: chunk-end bits, chunks that are one token, the pair -> id table
@@ -278,7 +281,6 @@ int encode_chunks(int device_id, const uint8_t *text, uint64_t n_bytes, const ui
     std::vector<SingleChunk> singles;
     for (uint64_t c = 0; c < n_chunks; ++c) {
         const uint64_t s = chunk_off[c], e = chunk_off[c + 1];
-        if (e < s) { mbpe_host::set_last_error("chunk_off must be ascending"); return MBPE_ERR_ARG; }
         if (e == s) continue;
         mask[(e - 1) >> 3] |= (uint8_t)(1u << ((e - 1) & 7));
         long long id;

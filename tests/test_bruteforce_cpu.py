@@ -21,6 +21,7 @@ The fixtures' digests were recorded in SURVEY.md 8c by the survey session; this 
 every one of them (ten .model files, three encode vectors) to the algorithm independently of
 oracle/bpe_oracle.c."""
 import hashlib
+import re
 
 import numpy as np
 import pytest
@@ -192,6 +193,41 @@ def parse_model(raw):
         special[name] = int(idx)
     merges = [tuple(int(v) for v in ln.split()) for ln in lines[3 + n_special:] if ln]
     return lines[1], special, merges
+
+
+_STOI = re.compile(rb"[ \t\n\v\f\r]*([+-]?[0-9]+)")
+
+
+def text_to_vector(chunk):
+    """text_to_vector, Tokenizer.h:85-100: the bytes of a chunk as tokens -- unless the chunk starts with NUL and
+    std::stoi takes a number from what follows (:86-93), then that number is the chunk's ONE token (as a uint32_t).
+    std::stoi is strtol in base 10 on the C string (so it ends at a further NUL): blanks, an optional sign, at least
+    one digit; it throws -- and the chunk stays bytes -- when there is no digit there or the value does not fit an int."""
+    chunk = bytes(chunk)
+    if chunk[:1] == b"\0":
+        m = _STOI.match(chunk[1:].split(b"\0")[0])
+        if m and -(1 << 31) <= int(m.group(1)) < (1 << 31):
+            return [int(m.group(1)) & 0xFFFFFFFF]
+    return list(chunk)
+
+
+def brute_force_encode_passes(tokens, lookup):
+    """brute_force_encode_chunk -> (tokens, number of passes that replaced something)."""
+    replacing = 0
+    while True:
+        out, i, merged = [], 0, False
+        while i < len(tokens):
+            if i + 1 < len(tokens) and (tokens[i], tokens[i + 1]) in lookup:
+                out.append(lookup[(tokens[i], tokens[i + 1])])
+                i += 2
+                merged = True
+            else:
+                out.append(tokens[i])
+                i += 1
+        tokens = out
+        if not merged:
+            return tokens, replacing
+        replacing += 1
 
 
 def brute_force_encode_chunk(tokens, lookup):
