@@ -344,6 +344,71 @@ MBPE_API int mbpe_encode_chunks_device(int device_id, const uint8_t *text, uint6
                                        uint32_t *tokens_dev_out, uint64_t cap, uint64_t *n_out,
                                        uint32_t *n_passes_out);
 
+/* An encoder: the same encode as an object that is created once per merges table and called many times.  It keeps,
+ * on HIP device `device_id`, the pair -> id lookup table, its own non-blocking stream and the work buffers (about 13
+ * bytes per text byte of the largest piece encoded so far); a call that needs larger buffers grows them, any other
+ * call allocates nothing.  The two calls above are a temporary encoder plus one mbpe_encoder_encode.
+ * Arguments are checked, and the table is built, before the device is touched.  No CPU fallback: MBPE_ERR_NO_DEVICE
+ * without a HIP device.  Thread-compatible like a context: one call at a time. */
+typedef struct mbpe_encoder mbpe_encoder;
+MBPE_API int  mbpe_encoder_create(int device_id, const uint32_t *merges, uint32_t n_merges, mbpe_encoder **out);
+MBPE_API void mbpe_encoder_destroy(mbpe_encoder *e);
+
+/* Encodes all chunks of a text.
+ *   text               n_bytes bytes; host memory, or -- text_on_device != 0 -- device memory of the encoder's device,
+ *                      which is read in place and never written.  (The chunks of a device text that start with NUL
+ *                      are found by a kernel and copied back for the std::stoi rule; results and error codes are those
+ *                      of a host text.)
+ *   chunk_off, n_chunks  as for mbpe_encode_chunks; always host memory
+ *   tokens_out         cap tokens of token_bits bits each: host memory, or device memory when out_on_device != 0.
+ *                      token_bits 32, host: uint32_t ids.  token_bits 32, device: bit 31 = last token of its chunk,
+ *                      as mbpe_encode_chunks_device leaves them.  token_bits 16: uint16_t ids without flags, host or
+ *                      device; MBPE_ERR_VOCAB, before any pass runs, when 256 + n_merges > 65,536 or a NUL-led chunk
+ *                      names an id >= 65,536.  Any other token_bits is MBPE_ERR_ARG.
+ *                      NULL: query.  n_out receives the count whenever the passes ran; a cap that is too small
+ *                      returns MBPE_ERR_ARG, writes no token (and no chunk offset beyond [0]) and still reports the
+ *                      count.  cap = n_bytes always suffices: encoding never makes more tokens than bytes.
+ *   chunk_tok_off_out  optional, host, n_chunks + 1 entries: the tokens of chunk c are
+ *                      [chunk_tok_off_out[c], chunk_tok_off_out[c + 1]) of the output; [0] == 0, [n_chunks] == *n_out,
+ *                      an empty chunk repeats its predecessor's offset.  Also filled by a query.  NULL: the chunk ends
+ *                      are neither computed nor stored.
+ *   n_passes_out       optional: stream passes made (of the piece that needed most)
+ * Pieces: a text longer than the option "piece_bytes" is cut at chunk boundaries into pieces of at most that many
+ * bytes (greedily: every piece takes as many whole chunks as fit), which go through the same buffers one after the
+ * other; tokens and offsets are appended, the result is that of the unsplit call.  A single chunk longer than a piece
+ * returns MBPE_ERR_OOM with a message that names it; the encoder stays usable.  With "piece_bytes" 0 (the default) a
+ * text that fits the buffers the encoder already holds is one piece; otherwise the limit is
+ * (free + held - (free + held) / 16) / 14 bytes, where free is the device memory hipMemGetInfo reports at the call
+ * and held the size of the encoder's work buffers: a piece costs 13.2 bytes of device memory per text byte.
+ * When the pieces are several and cap < n_bytes, the passes run twice (count first, so that a cap too small writes
+ * nothing). */
+MBPE_API int  mbpe_encoder_encode(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                  const uint64_t *chunk_off, uint64_t n_chunks,
+                                  void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device,
+                                  uint64_t *chunk_tok_off_out, uint64_t *n_out, uint32_t *n_passes_out);
+
+/*   "piece_bytes"   the most text bytes encoded in one go; 0 (default) = chosen at the call, see above.
+ * An unknown name or a negative value is MBPE_ERR_ARG. */
+MBPE_API int  mbpe_encoder_set_option(mbpe_encoder *e, const char *name, int64_t value);
+
+/* Device time of the encoder's latest call in milliseconds: HIP events on its stream around widen, the passes (with
+ * the 8-byte read-back that ends each) and the finishing kernels, summed over the pieces; the copies of text, mask
+ * and output between host and device are outside.  Where the passes ran twice (several pieces and cap < n_bytes)
+ * both runs are in it. */
+MBPE_API int  mbpe_encoder_kernel_ms(const mbpe_encoder *e, float *ms_out);
+
+/* The passes of the latest call: tokens_out[k] = tokens that entered pass k, summed over the pieces ([0] = n_bytes;
+ * of passes that ran twice, one run).
+ * tokens_out NULL: n_out receives how many there are.  For the byte accounting of tools/encode_time.py. */
+MBPE_API int  mbpe_encoder_pass_tokens(const mbpe_encoder *e, uint64_t *tokens_out, uint32_t cap, uint32_t *n_out);
+
+/* Device allocations (hipMalloc calls) the encoder has made since it was created, the lookup table's included.  A
+ * call on a text no longer than an earlier one, with the same arguments, leaves the number as it is.  (Three small
+ * buffers follow other sizes and may still grow then: the list of NUL-led chunks with their number, and a list of
+ * chunk ends of its own when chunks are shorter than two bytes on average -- otherwise the ends borrow the idle
+ * token array.) */
+MBPE_API int  mbpe_encoder_alloc_count(const mbpe_encoder *e, uint64_t *n_out);
+
 /* ---- decode on the device ----------------------------------------------- */
 
 /* Tokenizer::decode (Tokenizer.h:725-751) for whole token streams on HIP device `device_id`: per token a byte

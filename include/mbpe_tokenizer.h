@@ -49,10 +49,21 @@ MBPE_API int mbpe_tok_encode(mbpe_tokenizer *t, const uint8_t *text, uint64_t n,
                              uint32_t *tokens_out, uint64_t cap, uint64_t *n_out);
 
 /* The same with internal_encode (Tokenizer.h:325-377) on HIP device `device_id`
- * (mbpe_encode_chunks); special-token and regex splitting stay on the host.  No CPU
+ * (mbpe_encoder_encode, with an encoder that the tokenizer keeps until its merges change
+ * or another device is named); special-token and regex splitting stay on the host.  No CPU
  * fallback: MBPE_ERR_NO_DEVICE without a device. */
 MBPE_API int mbpe_tok_encode_device(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, int verbose, int device_id,
                                     uint32_t *tokens_out, uint64_t cap, uint64_t *n_out);
+
+/* encode of n_docs documents in one device call.  Document i is text[doc_off[i] .. doc_off[i + 1]) (n_docs + 1
+ * ascending offsets, host memory); every document is split on special tokens and by the pattern on its own, so no
+ * chunk spans two documents, and all chunks go to the device in ONE mbpe_encoder_encode.  tokens_out (NULL: query)
+ * receives the documents' tokens one after the other, doc_tok_off_out (optional, n_docs + 1; also on a query) where each begins:
+ * document i is tokens_out[doc_tok_off_out[i] .. doc_tok_off_out[i + 1]) and equals mbpe_tok_encode of that
+ * document; an empty document has no tokens.  n_out is required; device_id must not be negative. */
+MBPE_API int mbpe_tok_encode_batch_device(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off,
+                                          uint64_t n_docs, int verbose, int device_id, uint32_t *tokens_out,
+                                          uint64_t cap, uint64_t *doc_tok_off_out, uint64_t *n_out);
 
 /* decode, Tokenizer.h:725-751.  bytes_out may be NULL to query the length. */
 MBPE_API int mbpe_tok_decode(mbpe_tokenizer *t, const uint32_t *tokens, uint64_t n, int verbose,

@@ -14,14 +14,23 @@
 // Layout: 32-bit tokens (the reference's Token, Tokenizer.h:37), bit 31 = "last token of its chunk".
 // A span = 1,024 consecutive tokens = the unit one wave walks (16 x 64 lanes, ballots give the
 // candidate masks); spans are linked by two small scans (run parity, output offsets).
+//
+// An mbpe_encoder keeps what does not change between calls: the pair -> id table on the device, a stream, and the
+// work buffers (text, end mask, two token arrays, cand, span arrays), which grow when a call needs more.  A call
+// cuts a text that does not fit into pieces at chunk boundaries and runs each through: widen -> passes -> one
+// finishing kernel that writes the ids in the caller's format (32-bit with or without the flags, 16-bit) and, when
+// the caller wants to know which tokens belong to which chunk, the position after every flagged token (per-span
+// count of flags -> k_enc_scan_sum -> ranked write).  A text that lives on the device is read in place; the chunk
+// starts whose byte is NUL are listed by a small kernel so that the host can parse those chunks.
 #include "mbpe.h"
 #include "../host/mbpe_host.h"
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
+#include <new>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 namespace {
@@ -219,17 +228,95 @@ __global__ __launch_bounds__(kEncThreads) void k_enc_scatter(const uint32_t *__r
     }
 }
 
+// ---- the finishing kernels: what leaves the passes becomes what the caller asked for ----------------------------
+
+// chunk starts whose byte is NUL, for a text that lives on the device (the host runs stoi_value on those chunks):
+// position i starts a chunk when it is the first byte or the byte before it ends one
+__global__ void k_enc_nul_starts(const uint8_t *__restrict__ text, uint64_t n, const uint8_t *__restrict__ endmask,
+                                 unsigned long long *__restrict__ list, unsigned long long cap,
+                                 unsigned long long *__restrict__ count) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) {
+        if (text[i] != 0) continue;
+        if (i != 0 && !((endmask[(i - 1) >> 3] >> ((i - 1) & 7)) & 1u)) continue;
+        const unsigned long long at = atomicAdd(count, 1ull);
+        if (at < cap) list[at] = i;                 // (the host grows the list and asks again when count > cap)
+    }
+}
+
+// per span: how many of its tokens are the last of their chunk
+__global__ __launch_bounds__(kEncThreads) void k_enc_end_count(const uint32_t *__restrict__ tok, uint64_t n,
+                                                               uint32_t *__restrict__ span_ends) {
+    const uint64_t span = (uint64_t)blockIdx.x * (kEncThreads / kWave) + threadIdx.x / kWave;
+    const uint64_t base = span * kSpan;
+    if (base >= n) return;
+    const uint32_t lane = lane_id();
+    uint32_t cnt = 0;
+    for (int it = 0; it < kSpanIters; ++it) {
+        const uint64_t i = base + (uint64_t)it * kWave + lane;
+        const bool end = i < n && (tok[i] & kEnd);
+        cnt += (uint32_t)__popcll(__ballot(end));
+    }
+    if (lane == 0) span_ends[span] = cnt;
+}
+
+enum FinMode {
+    kFinFlags = 0,      // uint32_t, bit 31 = last token of its chunk (as the passes leave them)
+    kFinU32 = 1,        // uint32_t ids
+    kFinU16 = 2,        // uint16_t ids
+    kFinNone = 3        // no tokens: only the chunk ends
+};
+
+// the final stream -> ids in the caller's format; with ENDS also, in order, the position after every token that ends
+// a chunk (span_off = exclusive sums of k_enc_end_count's counts; tok_base = tokens of the pieces before this one)
+template <int MODE, bool ENDS>
+__global__ __launch_bounds__(kEncThreads) void k_enc_finish(const uint32_t *__restrict__ tok, uint64_t n,
+                                                            void *__restrict__ out,
+                                                            const unsigned long long *__restrict__ span_off,
+                                                            unsigned long long tok_base,
+                                                            unsigned long long *__restrict__ ends,
+                                                            unsigned long long ends_cap) {
+    const uint64_t span = (uint64_t)blockIdx.x * (kEncThreads / kWave) + threadIdx.x / kWave;
+    const uint64_t base = span * kSpan;
+    if (base >= n) return;
+    const uint32_t lane = lane_id();
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    unsigned long long o = ENDS ? span_off[span] : 0ull;
+    for (int it = 0; it < kSpanIters; ++it) {
+        const uint64_t i = base + (uint64_t)it * kWave + lane;
+        const uint32_t t = i < n ? tok[i] : 0u;
+        if (i < n) {
+            if (MODE == kFinFlags) static_cast<uint32_t *>(out)[i] = t;
+            if (MODE == kFinU32) static_cast<uint32_t *>(out)[i] = t & kIdMask;
+            if (MODE == kFinU16) static_cast<uint16_t *>(out)[i] = (uint16_t)t;
+        }
+        if (ENDS) {
+            const bool end = i < n && (t & kEnd);
+            const unsigned long long E = __ballot(end);
+            const unsigned long long at = o + (uint32_t)__popcll(E & lt);
+            if (end && at < ends_cap) ends[at] = tok_base + i + 1;
+            o += (uint32_t)__popcll(E);
+        }
+    }
+}
+
 std::string hip_err(const char *what, hipError_t e) { return std::string(what) + ": " + hipGetErrorString(e); }
 
-#define HIPCHK(expr)                                                   \
-    do {                                                               \
-        hipError_t e__ = (expr);                                       \
-        if (e__ != hipSuccess) {                                       \
-            mbpe_host::set_last_error(hip_err(#expr, e__));            \
-            rc = e__ == hipErrorOutOfMemory ? MBPE_ERR_OOM : MBPE_ERR_HIP; \
-            goto done;                                                 \
-        }                                                              \
+#define ECHK(expr)                                                            \
+    do {                                                                      \
+        hipError_t e__ = (expr);                                              \
+        if (e__ != hipSuccess) {                                              \
+            mbpe_host::set_last_error(hip_err(#expr, e__));                   \
+            (void)hipGetLastError();                                          \
+            return e__ == hipErrorOutOfMemory ? MBPE_ERR_OOM : MBPE_ERR_HIP;  \
+        }                                                                     \
     } while (0)
+
+int fail(int code, const std::string &msg) {
+    mbpe_host::set_last_error(msg);
+    return code;
+}
 
 // std::stoi on the remainder of a NUL-led chunk (Tokenizer.h:86-93): value when it parses
 bool stoi_value(const uint8_t *s, uint64_t n, long long *out) {
@@ -250,53 +337,472 @@ bool stoi_value(const uint8_t *s, uint64_t n, long long *out) {
     return true;
 }
 
-// out_on_device: tokens_out is device memory and receives the tokens with their chunk-end flags
+constexpr uint64_t kPieceCost = 14;        // device bytes per text byte of a piece, rounded up (mbpe.h, "piece_bytes")
+constexpr uint64_t kNulListMin = 4096;     // entries the list of NUL-led chunk starts begins with
+constexpr uint64_t kNulCopyEach = 256;     // up to this many NUL-led chunks are copied back one by one
+
+}  // namespace
+
+struct mbpe_encoder {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    float last_ms = 0.f;
+    uint64_t n_allocs = 0;                    // hipMalloc calls so far (mbpe_encoder_alloc_count)
+    uint64_t piece_bytes = 0;                 // option "piece_bytes"; 0 = from the free device memory
+    uint32_t n_merges = 0;
+    // the lookup table
+    unsigned long long *d_keys = nullptr;
+    uint32_t *d_vals = nullptr;
+    EncLut lut = {};
+    // work buffers, grown on demand and kept
+    uint8_t *d_text = nullptr, *d_mask = nullptr;
+    uint32_t *tok[2] = {nullptr, nullptr}, *cand = nullptr, *span_a = nullptr, *span_b = nullptr;
+    unsigned long long *span_off = nullptr;
+    uint64_t cap_text = 0, cap_mask = 0, cap_tok[2] = {0, 0}, cap_cand = 0, cap_span_a = 0, cap_span_b = 0,
+             cap_span_off = 0;
+    unsigned long long *d_res = nullptr;      // [0] total of a sum scan, [1] NUL-led chunk starts found
+    SingleChunk *d_singles = nullptr;
+    uint64_t cap_singles = 0;
+    unsigned long long *d_nul = nullptr;      // starts of NUL-led chunks of a device text
+    uint64_t cap_nul = 0;
+    unsigned long long *d_ends = nullptr;     // chunk ends, only when chunks are shorter than two bytes on average
+    uint64_t cap_ends = 0;
+    // host scratch
+    std::vector<uint8_t> mask, bytes;
+    std::vector<SingleChunk> singles, piece_singles;
+    std::vector<unsigned long long> list;
+    std::vector<uint64_t> pass_tokens;        // latest call: tokens that entered pass k, summed over the pieces
+};
+
+namespace {
+
+template <typename T>
+int enc_grow(mbpe_encoder *e, T **p, uint64_t *cap, uint64_t want_bytes) {
+    if (*p && *cap >= want_bytes) return MBPE_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    ECHK(hipMalloc(reinterpret_cast<void **>(p), want_bytes));
+    ++e->n_allocs;
+    *cap = want_bytes;
+    return MBPE_OK;
+}
+
+uint64_t enc_held(const mbpe_encoder *e) {
+    return e->cap_text + e->cap_mask + e->cap_tok[0] + e->cap_tok[1] + e->cap_cand + e->cap_span_a + e->cap_span_b +
+           e->cap_span_off;
+}
+
+struct Piece { uint64_t c0, c1; };            // chunks [c0, c1)
+
+// chunk-end bits of the chunks [c0, c1), relative to the first one's start
+void build_mask(mbpe_encoder *e, const uint64_t *chunk_off, Piece p) {
+    const uint64_t base = chunk_off[p.c0], pn = chunk_off[p.c1] - base;
+    e->mask.assign((pn + 7) / 8 + 8, 0);
+    for (uint64_t c = p.c0; c < p.c1; ++c) {
+        const uint64_t s = chunk_off[c], t = chunk_off[c + 1];
+        if (t == s) continue;
+        e->mask[(t - 1 - base) >> 3] |= (uint8_t)(1u << ((t - 1 - base) & 7));
+    }
+}
+
+int add_single(mbpe_encoder *e, uint64_t start, uint64_t len, long long id, uint32_t token_bits) {
+    if ((uint32_t)(int)id >= kDrop) return fail(MBPE_ERR_ARG, "token id of a NUL-led chunk does not fit 31 bits");
+    if (token_bits == 16 && (uint32_t)(int)id >= 65536u)
+        return fail(MBPE_ERR_VOCAB, "token id " + std::to_string(id) + " of a NUL-led chunk does not fit 16 bits");
+    e->singles.push_back({start, len, (uint32_t)(int)id, 0});
+    return MBPE_OK;
+}
+
+// the NUL-led chunks of one piece of a device text -> e->singles; leaves the piece's mask on the device
+int device_singles(mbpe_encoder *e, const uint8_t *d_text, const uint64_t *chunk_off, Piece p, uint32_t token_bits) {
+    const uint64_t base = chunk_off[p.c0], pn = chunk_off[p.c1] - base;
+    if (pn == 0) return MBPE_OK;
+    build_mask(e, chunk_off, p);
+    int rc = enc_grow(e, &e->d_mask, &e->cap_mask, e->mask.size());
+    if (rc == MBPE_OK && !e->d_nul) rc = enc_grow(e, &e->d_nul, &e->cap_nul, kNulListMin * 8);
+    if (rc != MBPE_OK) return rc;
+    ECHK(hipMemcpyAsync(e->d_mask, e->mask.data(), e->mask.size(), hipMemcpyHostToDevice, e->stream));
+    unsigned long long found = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        ECHK(hipMemsetAsync(e->d_res + 1, 0, 8, e->stream));
+        const int blocks = (int)std::min<uint64_t>((pn + 255) / 256, 8192);
+        hipLaunchKernelGGL(k_enc_nul_starts, dim3(blocks), dim3(256), 0, e->stream, d_text + base, pn, e->d_mask,
+                           e->d_nul, e->cap_nul / 8, e->d_res + 1);
+        ECHK(hipMemcpyAsync(&found, e->d_res + 1, 8, hipMemcpyDeviceToHost, e->stream));
+        ECHK(hipStreamSynchronize(e->stream));
+        ECHK(hipGetLastError());
+        if (found <= e->cap_nul / 8) break;
+        rc = enc_grow(e, &e->d_nul, &e->cap_nul, found * 8);
+        if (rc != MBPE_OK) return rc;
+    }
+    if (found == 0) return MBPE_OK;
+    e->list.resize(found);
+    ECHK(hipMemcpyAsync(e->list.data(), e->d_nul, found * 8, hipMemcpyDeviceToHost, e->stream));
+    ECHK(hipStreamSynchronize(e->stream));
+    std::sort(e->list.begin(), e->list.end());
+    const bool whole = found > kNulCopyEach;      // many: one copy of the piece instead of one per chunk
+    if (whole) {
+        e->bytes.resize(pn);
+        ECHK(hipMemcpyAsync(e->bytes.data(), d_text + base, pn, hipMemcpyDeviceToHost, e->stream));
+        ECHK(hipStreamSynchronize(e->stream));
+    }
+    for (unsigned long long pos : e->list) {
+        // the chunk that holds byte base + pos; it starts there (k_enc_nul_starts lists chunk starts only)
+        const uint64_t c = (uint64_t)(std::upper_bound(chunk_off + p.c0, chunk_off + p.c1 + 1, base + pos) - chunk_off) - 1;
+        const uint64_t s = chunk_off[c], len = chunk_off[c + 1] - s;
+        if (s != base + pos || len == 0) return fail(MBPE_ERR_HIP, "mbpe_encoder_encode: chunk start list is inconsistent");
+        const uint8_t *b;
+        if (whole) {
+            b = e->bytes.data() + pos;
+        } else {
+            e->bytes.resize(len);
+            ECHK(hipMemcpyAsync(e->bytes.data(), d_text + s, len, hipMemcpyDeviceToHost, e->stream));
+            ECHK(hipStreamSynchronize(e->stream));
+            b = e->bytes.data();
+        }
+        long long id;
+        if (stoi_value(b + 1, len - 1, &id)) {
+            rc = add_single(e, s, len, id, token_bits);
+            if (rc != MBPE_OK) return rc;
+        }
+    }
+    return MBPE_OK;
+}
+
+template <int MODE>
+void launch_finish(mbpe_encoder *e, dim3 grid, const uint32_t *tok, uint64_t n, void *out, bool with_ends,
+                   unsigned long long tok_base, unsigned long long *ends, unsigned long long ends_cap) {
+    if (with_ends)
+        hipLaunchKernelGGL((k_enc_finish<MODE, true>), grid, dim3(kEncThreads), 0, e->stream, tok, n, out, e->span_off,
+                           tok_base, ends, ends_cap);
+    else if constexpr (MODE != kFinNone)            // (no tokens and no ends: nothing to launch)
+        hipLaunchKernelGGL((k_enc_finish<MODE, false>), grid, dim3(kEncThreads), 0, e->stream, tok, n, out, e->span_off,
+                           tok_base, ends, ends_cap);
+}
+
+struct EncCall {
+    const uint8_t *text;
+    int text_on_device;
+    const uint64_t *chunk_off;
+    void *tokens_out;            // NULL: count only (and chunk offsets, when asked for)
+    uint64_t cap;
+    uint32_t token_bits;
+    int out_on_device;
+    uint64_t *chunk_tok_off_out;
+    bool mask_on_device;         // the (single) piece's mask is on the device already
+};
+
+// one piece through the passes and the finishing kernel.  done = tokens of the pieces before it.
+int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_t *n_piece, uint32_t *passes_out,
+              bool *too_small) {
+    const uint64_t base = a.chunk_off[p.c0], pn = a.chunk_off[p.c1] - base;
+    *n_piece = 0;
+    *passes_out = 0;
+    if (pn == 0) {
+        if (a.chunk_tok_off_out)
+            for (uint64_t c = p.c0; c < p.c1; ++c) a.chunk_tok_off_out[c + 1] = done;
+        return MBPE_OK;
+    }
+    const uint64_t n_spans0 = (pn + kSpan - 1) / kSpan;
+    int rc = MBPE_OK;
+    if (!a.text_on_device) rc = enc_grow(e, &e->d_text, &e->cap_text, pn);
+    if (rc == MBPE_OK && !a.mask_on_device) {
+        build_mask(e, a.chunk_off, p);
+        rc = enc_grow(e, &e->d_mask, &e->cap_mask, e->mask.size());
+    }
+    if (rc == MBPE_OK) rc = enc_grow(e, &e->tok[0], &e->cap_tok[0], pn * 4);
+    if (rc == MBPE_OK) rc = enc_grow(e, &e->tok[1], &e->cap_tok[1], pn * 4);
+    if (rc == MBPE_OK) rc = enc_grow(e, &e->cand, &e->cap_cand, pn * 4);
+    if (rc == MBPE_OK) rc = enc_grow(e, &e->span_a, &e->cap_span_a, n_spans0 * 4);
+    if (rc == MBPE_OK) rc = enc_grow(e, &e->span_b, &e->cap_span_b, n_spans0 * 4);
+    if (rc == MBPE_OK) rc = enc_grow(e, &e->span_off, &e->cap_span_off, n_spans0 * 8);
+    if (rc != MBPE_OK) return rc;
+    // the piece's NUL-led chunks (e->singles is sorted by start), relative to the piece
+    e->piece_singles.clear();
+    {
+        auto lo = std::lower_bound(e->singles.begin(), e->singles.end(), base,
+                                   [](const SingleChunk &s, uint64_t v) { return s.start < v; });
+        for (; lo != e->singles.end() && lo->start < base + pn; ++lo)
+            e->piece_singles.push_back({lo->start - base, lo->len, lo->id, 0});
+    }
+    if (!e->piece_singles.empty()) {
+        rc = enc_grow(e, &e->d_singles, &e->cap_singles, e->piece_singles.size() * sizeof(SingleChunk));
+        if (rc != MBPE_OK) return rc;
+    }
+    const uint8_t *d_text = a.text + base;
+    if (!a.text_on_device) {
+        ECHK(hipMemcpyAsync(e->d_text, a.text + base, pn, hipMemcpyHostToDevice, e->stream));
+        d_text = e->d_text;
+    }
+    if (!a.mask_on_device)
+        ECHK(hipMemcpyAsync(e->d_mask, e->mask.data(), e->mask.size(), hipMemcpyHostToDevice, e->stream));
+    if (!e->piece_singles.empty())
+        ECHK(hipMemcpyAsync(e->d_singles, e->piece_singles.data(), e->piece_singles.size() * sizeof(SingleChunk),
+                            hipMemcpyHostToDevice, e->stream));
+
+    ECHK(hipEventRecord(e->ev0, e->stream));
+    const int wblocks = (int)std::min<uint64_t>((pn + 255) / 256, 8192);
+    hipLaunchKernelGGL(k_enc_widen, dim3(wblocks), dim3(256), 0, e->stream, d_text, pn, e->d_mask, e->tok[0]);
+    if (!e->piece_singles.empty())
+        hipLaunchKernelGGL(k_enc_single, dim3((uint32_t)e->piece_singles.size()), dim3(64), 0, e->stream, e->d_singles,
+                           (uint32_t)e->piece_singles.size(), e->tok[0]);
+    uint64_t n = pn;
+    int cur = 0;
+    uint32_t passes = 0;
+    for (;;) {
+        const uint64_t n_spans = (n + kSpan - 1) / kSpan;
+        const dim3 grid((uint32_t)((n_spans + kEncThreads / kWave - 1) / (kEncThreads / kWave))), block(kEncThreads);
+        hipLaunchKernelGGL(k_enc_cand, grid, block, 0, e->stream, e->tok[cur], n, e->lut, e->cand, e->span_a);
+        hipLaunchKernelGGL(k_enc_scan_parity, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans, e->span_b);
+        hipLaunchKernelGGL(k_enc_match, grid, block, 0, e->stream, e->tok[cur], n, e->cand, e->span_b, e->span_a);
+        hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans, e->span_off,
+                           e->d_res);
+        hipLaunchKernelGGL(k_enc_scatter, grid, block, 0, e->stream, e->cand, n, e->span_off, e->tok[1 - cur]);
+        unsigned long long total = 0;
+        ECHK(hipMemcpyAsync(&total, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
+        ECHK(hipStreamSynchronize(e->stream));
+        ECHK(hipGetLastError());
+        if (e->pass_tokens.size() <= passes) e->pass_tokens.resize(passes + 1, 0);
+        e->pass_tokens[passes] += n;
+        ++passes;
+        if (total == n) break;                 // the pass changed nothing: tok[cur] is the result (so is tok[1 - cur])
+        n = total;
+        cur = 1 - cur;
+        if (n == 0) break;
+    }
+    *n_piece = n;
+    *passes_out = passes;
+
+    // the finishing kernel: ids in the caller's format (into cand when they go to the host), chunk ends into tok[1 - cur]
+    *too_small = a.tokens_out && a.cap < done + n;
+    const bool with_ends = a.chunk_tok_off_out && !*too_small;
+    const bool with_tokens = a.tokens_out && !*too_small;
+    const uint64_t tok_bytes = a.token_bits / 8;
+    uint64_t n_ends = 0;
+    unsigned long long *d_ends = nullptr;
+    if (n && (with_ends || with_tokens)) {
+        const uint64_t n_spans = (n + kSpan - 1) / kSpan;
+        const dim3 grid((uint32_t)((n_spans + kEncThreads / kWave - 1) / (kEncThreads / kWave)));
+        if (with_ends) {
+            for (uint64_t c = p.c0; c < p.c1; ++c) n_ends += a.chunk_off[c + 1] > a.chunk_off[c];
+            if (n_ends * 8 <= e->cap_tok[1 - cur]) {
+                d_ends = reinterpret_cast<unsigned long long *>(e->tok[1 - cur]);
+            } else {
+                rc = enc_grow(e, &e->d_ends, &e->cap_ends, n_ends * 8);
+                if (rc != MBPE_OK) return rc;
+                d_ends = e->d_ends;
+            }
+            hipLaunchKernelGGL(k_enc_end_count, grid, dim3(kEncThreads), 0, e->stream, e->tok[cur], n, e->span_a);
+            hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans, e->span_off,
+                               e->d_res);
+        }
+        void *out = !with_tokens ? nullptr
+                    : a.out_on_device ? static_cast<uint8_t *>(a.tokens_out) + done * tok_bytes
+                                      : reinterpret_cast<uint8_t *>(e->cand);
+        const int mode = !with_tokens ? kFinNone : a.token_bits == 16 ? kFinU16 : a.out_on_device ? kFinFlags : kFinU32;
+        switch (mode) {
+            case kFinFlags: launch_finish<kFinFlags>(e, grid, e->tok[cur], n, out, with_ends, done, d_ends, n_ends); break;
+            case kFinU32: launch_finish<kFinU32>(e, grid, e->tok[cur], n, out, with_ends, done, d_ends, n_ends); break;
+            case kFinU16: launch_finish<kFinU16>(e, grid, e->tok[cur], n, out, with_ends, done, d_ends, n_ends); break;
+            default: launch_finish<kFinNone>(e, grid, e->tok[cur], n, out, with_ends, done, d_ends, n_ends); break;
+        }
+    }
+    ECHK(hipEventRecord(e->ev1, e->stream));
+    unsigned long long ends_found = 0;
+    if (with_ends && n) ECHK(hipMemcpyAsync(&ends_found, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
+    ECHK(hipStreamSynchronize(e->stream));
+    ECHK(hipGetLastError());
+    float ms = 0.f;
+    ECHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+    e->last_ms += ms;
+    if (with_tokens && !a.out_on_device && n) {
+        ECHK(hipMemcpyAsync(static_cast<uint8_t *>(a.tokens_out) + done * tok_bytes, e->cand, n * tok_bytes,
+                            hipMemcpyDeviceToHost, e->stream));
+        ECHK(hipStreamSynchronize(e->stream));
+    }
+    if (with_ends) {
+        if (ends_found != n_ends) return fail(MBPE_ERR_HIP, "mbpe_encoder_encode: chunk ends and chunks differ in number");
+        e->list.resize(n_ends);
+        if (n_ends) {
+            ECHK(hipMemcpyAsync(e->list.data(), d_ends, n_ends * 8, hipMemcpyDeviceToHost, e->stream));
+            ECHK(hipStreamSynchronize(e->stream));
+        }
+        uint64_t k = 0, last = done;
+        for (uint64_t c = p.c0; c < p.c1; ++c) {   // an empty chunk repeats its predecessor's offset
+            if (a.chunk_off[c + 1] > a.chunk_off[c]) last = e->list[k++];
+            a.chunk_tok_off_out[c + 1] = last;
+        }
+    }
+    return MBPE_OK;
+}
+
+int enc_run_body(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device, const uint64_t *chunk_off,
+                 uint64_t n_chunks, void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device,
+                 uint64_t *chunk_tok_off_out, uint64_t *n_out, uint32_t *n_passes_out) {
+    const uint64_t one[2] = {0, n_bytes};
+    if (!chunk_off) { chunk_off = one; n_chunks = 1; }
+    if (chunk_off[0] != 0 || chunk_off[n_chunks] != n_bytes)
+        return fail(MBPE_ERR_ARG, "chunk_off must start at 0 and end at n_bytes");
+    // (every offset is checked before one is used: an offset beyond n_bytes would index the mask and the text below)
+    for (uint64_t c = 0; c < n_chunks; ++c)
+        if (chunk_off[c + 1] < chunk_off[c]) return fail(MBPE_ERR_ARG, "chunk_off must be ascending");
+    if (token_bits == 16 && 256ull + e->n_merges > 65536ull)
+        return fail(MBPE_ERR_VOCAB, "token_bits 16 with more than 65,536 token ids");
+    if (chunk_tok_off_out) chunk_tok_off_out[0] = 0;
+    if (n_bytes == 0) {
+        if (chunk_tok_off_out)
+            for (uint64_t c = 0; c < n_chunks; ++c) chunk_tok_off_out[c + 1] = 0;
+        return MBPE_OK;
+    }
+    ECHK(hipSetDevice(e->device));
+    e->last_ms = 0.f;
+    e->pass_tokens.clear();
+
+    // pieces: whole chunks, at most `limit` bytes each
+    uint64_t limit = e->piece_bytes;
+    if (limit == 0) {
+        limit = e->cap_cand / 4;                                  // what the buffers hold already needs no question
+        if (n_bytes > limit) {
+            size_t free_b = 0, total_b = 0;
+            ECHK(hipMemGetInfo(&free_b, &total_b));
+            const uint64_t avail = (uint64_t)free_b + enc_held(e);
+            limit = std::max<uint64_t>((avail - avail / 16) / kPieceCost, limit);
+        }
+    }
+    std::vector<Piece> pieces;
+    if (n_bytes <= limit) {
+        pieces.push_back({0, n_chunks});
+    } else {
+        uint64_t c0 = 0;
+        while (c0 < n_chunks) {
+            uint64_t c1 = c0;
+            while (c1 < n_chunks && chunk_off[c1 + 1] - chunk_off[c0] <= limit) ++c1;
+            if (c1 == c0)
+                return fail(MBPE_ERR_OOM, "chunk " + std::to_string(c0) + " has " +
+                                              std::to_string(chunk_off[c0 + 1] - chunk_off[c0]) +
+                                              " bytes, more than one piece may hold (" + std::to_string(limit) +
+                                              "; option \"piece_bytes\")");
+            pieces.push_back({c0, c1});
+            c0 = c1;
+        }
+    }
+
+    // chunks that are one token, of the whole text, before any pass runs
+    e->singles.clear();
+    bool mask_on_device = false;
+    if (!text_on_device) {
+        for (uint64_t c = 0; c < n_chunks; ++c) {
+            const uint64_t s = chunk_off[c], t = chunk_off[c + 1];
+            long long id;
+            if (t > s && text[s] == 0 && stoi_value(text + s + 1, t - s - 1, &id)) {
+                const int rc = add_single(e, s, t - s, id, token_bits);
+                if (rc != MBPE_OK) return rc;
+            }
+        }
+    } else {
+        for (const Piece &p : pieces) {
+            const int rc = device_singles(e, text, chunk_off, p, token_bits);
+            if (rc != MBPE_OK) return rc;
+        }
+        mask_on_device = pieces.size() == 1;
+    }
+
+    EncCall a = {text, text_on_device, chunk_off, tokens_out, cap, token_bits, out_on_device, chunk_tok_off_out,
+                 mask_on_device};
+    // "a cap too small writes no token": where the pieces before the one that overflows would already have written
+    // theirs, the count comes first (cap >= n_bytes always suffices and never takes this path)
+    if (pieces.size() > 1 && tokens_out && cap < n_bytes) {
+        EncCall q = a;
+        q.tokens_out = nullptr;
+        q.chunk_tok_off_out = nullptr;
+        uint64_t total = 0;
+        uint32_t deepest = 0;
+        for (const Piece &p : pieces) {
+            uint64_t n = 0;
+            uint32_t passes = 0;
+            bool small = false;
+            const int rc = run_piece(e, q, p, total, &n, &passes, &small);
+            if (rc != MBPE_OK) return rc;
+            total += n;
+            deepest = std::max(deepest, passes);
+        }
+        if (cap < total) {
+            *n_out = total;
+            if (n_passes_out) *n_passes_out = deepest;
+            return fail(MBPE_ERR_ARG, "tokens_out too small");
+        }
+        e->pass_tokens.clear();                    // (the kernel time keeps both runs, the pass counts one)
+    }
+    uint64_t total = 0;
+    uint32_t deepest = 0;
+    bool too_small = false;
+    for (const Piece &p : pieces) {
+        uint64_t n = 0;
+        uint32_t passes = 0;
+        bool small = false;
+        const int rc = run_piece(e, a, p, total, &n, &passes, &small);
+        if (rc != MBPE_OK) return rc;
+        total += n;
+        deepest = std::max(deepest, passes);
+        if (small) { too_small = true; a.tokens_out = nullptr; a.chunk_tok_off_out = nullptr; }
+    }
+    *n_out = total;
+    if (n_passes_out) *n_passes_out = deepest;
+    if (too_small) return fail(MBPE_ERR_ARG, "tokens_out too small");
+    return MBPE_OK;
+}
+
+// (the host vectors -- mask, lists, the bytes of NUL-led chunks -- grow with the text: no exception leaves the C-ABI)
+int enc_run(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device, const uint64_t *chunk_off,
+            uint64_t n_chunks, void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device,
+            uint64_t *chunk_tok_off_out, uint64_t *n_out, uint32_t *n_passes_out) {
+    try {
+        return enc_run_body(e, text, n_bytes, text_on_device, chunk_off, n_chunks, tokens_out, cap, token_bits,
+                            out_on_device, chunk_tok_off_out, n_out, n_passes_out);
+    } catch (const std::bad_alloc &) {
+        return fail(MBPE_ERR_OOM, "mbpe_encoder_encode: host allocation failed");
+    }
+}
+
+// the one-shot calls: a temporary encoder and one call
 int encode_chunks(int device_id, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off, uint64_t n_chunks,
                   const uint32_t *merges, uint32_t n_merges, uint32_t *tokens_out, uint64_t cap, uint64_t *n_out,
                   uint32_t *n_passes_out, bool out_on_device) {
     if (n_out) *n_out = 0;
     if (n_passes_out) *n_passes_out = 0;
-    if (!n_out || (!text && n_bytes) || (!merges && n_merges)) {
-        mbpe_host::set_last_error("mbpe_encode_chunks: NULL argument");
-        return MBPE_ERR_ARG;
-    }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || device_id < 0 || device_id >= n_dev) {
-        mbpe_host::set_last_error("no usable HIP device (the MI355X path has no CPU fallback)");
-        return MBPE_ERR_NO_DEVICE;
-    }
-    const uint64_t one[2] = {0, n_bytes};
-    if (!chunk_off) { chunk_off = one; n_chunks = 1; }
-    if (chunk_off[0] != 0 || chunk_off[n_chunks] != n_bytes) {
-        mbpe_host::set_last_error("chunk_off must start at 0 and end at n_bytes");
-        return MBPE_ERR_ARG;
-    }
-    // (every offset is checked before one is used: an offset beyond n_bytes would index the mask and the text below)
-    for (uint64_t c = 0; c < n_chunks; ++c)
-        if (chunk_off[c + 1] < chunk_off[c]) { mbpe_host::set_last_error("chunk_off must be ascending"); return MBPE_ERR_ARG; }
-    if (n_bytes == 0) return MBPE_OK;
+    if (!n_out || (!text && n_bytes) || (!merges && n_merges)) return fail(MBPE_ERR_ARG, "mbpe_encode_chunks: NULL argument");
+    mbpe_encoder *e = nullptr;
+    int rc = mbpe_encoder_create(device_id, merges, n_merges, &e);
+    if (rc != MBPE_OK) return rc;
+    rc = enc_run(e, text, n_bytes, 0, chunk_off, n_chunks, tokens_out, cap, 32, out_on_device ? 1 : 0, nullptr, n_out,
+                 n_passes_out);
+    const std::string keep = rc == MBPE_OK ? std::string() : std::string(mbpe_host::last_error());
+    mbpe_encoder_destroy(e);
+    if (rc != MBPE_OK) mbpe_host::set_last_error(keep);
+    return rc;
+}
 
-    // host side: chunk-end bits, chunks that are one token, the pair -> id table
-    std::vector<uint8_t> mask((n_bytes + 7) / 8 + 8, 0);
-    std::vector<SingleChunk> singles;
-    for (uint64_t c = 0; c < n_chunks; ++c) {
-        const uint64_t s = chunk_off[c], e = chunk_off[c + 1];
-        if (e == s) continue;
-        mask[(e - 1) >> 3] |= (uint8_t)(1u << ((e - 1) & 7));
-        long long id;
-        if (text[s] == 0 && stoi_value(text + s + 1, e - s - 1, &id)) {
-            if ((uint32_t)(int)id >= kDrop) {
-                mbpe_host::set_last_error("token id of a NUL-led chunk does not fit 31 bits");
-                return MBPE_ERR_ARG;
-            }
-            singles.push_back({s, e - s, (uint32_t)(int)id, 0});
-        }
-    }
+}  // namespace
+
+extern "C" {
+
+int mbpe_encoder_create(int device_id, const uint32_t *merges, uint32_t n_merges, mbpe_encoder **out) {
+    if (!out || (!merges && n_merges)) return fail(MBPE_ERR_ARG, "mbpe_encoder_create: NULL argument");
+    *out = nullptr;
+    // host side: the pair -> id table
     uint32_t bits = 4;
     while ((1ull << bits) < 2ull * n_merges + 2) ++bits;
     const uint32_t capacity = 1u << bits;
-    std::vector<unsigned long long> keys(capacity, kEmptyKey);
-    std::vector<uint32_t> vals(capacity, 0);
+    std::vector<unsigned long long> keys;
+    std::vector<uint32_t> vals;
+    try {
+        keys.assign(capacity, kEmptyKey);
+        vals.assign(capacity, 0);
+    } catch (const std::bad_alloc &) {
+        return fail(MBPE_ERR_OOM, "mbpe_encoder_create: host allocation failed");
+    }
     for (uint32_t k = 0; k < n_merges; ++k) {       // merges_lookup[pair] = 256 + k: a repeated pair keeps the last id
         const unsigned long long key = ((unsigned long long)merges[2 * k] << 32) | merges[2 * k + 1];
         uint32_t h = enc_hash(key, 64 - bits);
@@ -304,97 +810,108 @@ int encode_chunks(int device_id, const uint8_t *text, uint64_t n_bytes, const ui
         keys[h] = key;
         vals[h] = 256 + k;
     }
-
-    int rc = MBPE_OK;
-    uint8_t *d_text = nullptr, *d_mask = nullptr;
-    uint32_t *tok[2] = {nullptr, nullptr}, *cand = nullptr, *span_a = nullptr, *span_b = nullptr, *d_vals = nullptr;
-    unsigned long long *span_off = nullptr, *d_total = nullptr, *d_keys = nullptr;
-    SingleChunk *d_singles = nullptr;
-    hipStream_t stream = nullptr;
-    uint64_t n = n_bytes;
-    int cur = 0;
-    uint32_t passes = 0;
-    {
-        const uint64_t n_spans0 = (n + kSpan - 1) / kSpan;
-        HIPCHK(hipSetDevice(device_id));
-        HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        HIPCHK(hipMalloc(&d_text, n_bytes));
-        HIPCHK(hipMalloc(&d_mask, mask.size()));
-        HIPCHK(hipMalloc(&tok[0], n * 4));
-        HIPCHK(hipMalloc(&tok[1], n * 4));
-        HIPCHK(hipMalloc(&cand, n * 4));
-        HIPCHK(hipMalloc(&span_a, n_spans0 * 4));
-        HIPCHK(hipMalloc(&span_b, n_spans0 * 4));
-        HIPCHK(hipMalloc(&span_off, n_spans0 * 8));
-        HIPCHK(hipMalloc(&d_total, 8));
-        HIPCHK(hipMalloc(&d_keys, (size_t)capacity * 8));
-        HIPCHK(hipMalloc(&d_vals, (size_t)capacity * 4));
-        HIPCHK(hipMemcpyAsync(d_text, text, n_bytes, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(d_mask, mask.data(), mask.size(), hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(d_keys, keys.data(), (size_t)capacity * 8, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(d_vals, vals.data(), (size_t)capacity * 4, hipMemcpyHostToDevice, stream));
-        const int wblocks = (int)std::min<uint64_t>((n + 255) / 256, 8192);
-        hipLaunchKernelGGL(k_enc_widen, dim3(wblocks), dim3(256), 0, stream, d_text, n, d_mask, tok[0]);
-        if (!singles.empty()) {
-            HIPCHK(hipMalloc(&d_singles, singles.size() * sizeof(SingleChunk)));
-            HIPCHK(hipMemcpyAsync(d_singles, singles.data(), singles.size() * sizeof(SingleChunk),
-                                  hipMemcpyHostToDevice, stream));
-            hipLaunchKernelGGL(k_enc_single, dim3((uint32_t)singles.size()), dim3(64), 0, stream, d_singles,
-                               (uint32_t)singles.size(), tok[0]);
-        }
-        const EncLut lut = {d_keys, d_vals, 64 - bits, capacity - 1};
-        for (;;) {
-            const uint64_t n_spans = (n + kSpan - 1) / kSpan;
-            const dim3 grid((uint32_t)((n_spans + kEncThreads / kWave - 1) / (kEncThreads / kWave))), block(kEncThreads);
-            hipLaunchKernelGGL(k_enc_cand, grid, block, 0, stream, tok[cur], n, lut, cand, span_a);
-            hipLaunchKernelGGL(k_enc_scan_parity, dim3(1), dim3(kScanThreads), 0, stream, span_a, n_spans, span_b);
-            hipLaunchKernelGGL(k_enc_match, grid, block, 0, stream, tok[cur], n, cand, span_b, span_a);
-            hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, stream, span_a, n_spans, span_off, d_total);
-            hipLaunchKernelGGL(k_enc_scatter, grid, block, 0, stream, cand, n, span_off, tok[1 - cur]);
-            unsigned long long total = 0;
-            HIPCHK(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            HIPCHK(hipGetLastError());
-            ++passes;
-            if (total == n) break;             // the pass changed nothing: tok[cur] is the result (so is tok[1 - cur])
-            n = total;
-            cur = 1 - cur;
-            if (n == 0) break;
-        }
-        *n_out = n;
-        if (n_passes_out) *n_passes_out = passes;
-        if (tokens_out) {
-            if (cap < n) { mbpe_host::set_last_error("tokens_out too small"); rc = MBPE_ERR_ARG; goto done; }
-            if (out_on_device) {
-                if (n) HIPCHK(hipMemcpyAsync(tokens_out, tok[cur], n * 4, hipMemcpyDeviceToDevice, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-            } else {
-                if (n) HIPCHK(hipMemcpy(tokens_out, tok[cur], n * 4, hipMemcpyDeviceToHost));
-                for (uint64_t i = 0; i < n; ++i) tokens_out[i] &= kIdMask;      // strip the chunk-end flags
-            }
-        }
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || device_id < 0 || device_id >= n_dev)
+        return fail(MBPE_ERR_NO_DEVICE, "no usable HIP device (the MI355X path has no CPU fallback)");
+    mbpe_encoder *e = new (std::nothrow) mbpe_encoder;
+    if (!e) return fail(MBPE_ERR_OOM, "mbpe_encoder_create: host allocation failed");
+    e->device = device_id;
+    e->n_merges = n_merges;
+    auto build = [&]() -> int {
+        uint64_t cap_keys = 0, cap_vals = 0, cap_res = 0;
+        ECHK(hipSetDevice(device_id));
+        ECHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+        ECHK(hipEventCreate(&e->ev0));
+        ECHK(hipEventCreate(&e->ev1));
+        int rc = enc_grow(e, &e->d_keys, &cap_keys, (uint64_t)capacity * 8);
+        if (rc == MBPE_OK) rc = enc_grow(e, &e->d_vals, &cap_vals, (uint64_t)capacity * 4);
+        if (rc == MBPE_OK) rc = enc_grow(e, &e->d_res, &cap_res, 16);
+        if (rc != MBPE_OK) return rc;
+        ECHK(hipMemcpyAsync(e->d_keys, keys.data(), (size_t)capacity * 8, hipMemcpyHostToDevice, e->stream));
+        ECHK(hipMemcpyAsync(e->d_vals, vals.data(), (size_t)capacity * 4, hipMemcpyHostToDevice, e->stream));
+        ECHK(hipStreamSynchronize(e->stream));
+        return MBPE_OK;
+    };
+    const int rc = build();
+    if (rc != MBPE_OK) {
+        const std::string keep = mbpe_host::last_error();
+        mbpe_encoder_destroy(e);
+        mbpe_host::set_last_error(keep);
+        return rc;
     }
-done:
-    (void)hipFree(d_text); (void)hipFree(d_mask); (void)hipFree(tok[0]); (void)hipFree(tok[1]); (void)hipFree(cand);
-    (void)hipFree(span_a); (void)hipFree(span_b); (void)hipFree(span_off); (void)hipFree(d_total);
-    (void)hipFree(d_keys); (void)hipFree(d_vals); (void)hipFree(d_singles);
-    if (stream) (void)hipStreamDestroy(stream);
-    return rc;
+    e->lut = {e->d_keys, e->d_vals, 64 - bits, capacity - 1};
+    *out = e;
+    return MBPE_OK;
 }
 
-}  // namespace
+void mbpe_encoder_destroy(mbpe_encoder *e) {
+    if (!e) return;
+    (void)hipSetDevice(e->device);
+    (void)hipFree(e->d_keys); (void)hipFree(e->d_vals); (void)hipFree(e->d_text); (void)hipFree(e->d_mask);
+    (void)hipFree(e->tok[0]); (void)hipFree(e->tok[1]); (void)hipFree(e->cand); (void)hipFree(e->span_a);
+    (void)hipFree(e->span_b); (void)hipFree(e->span_off); (void)hipFree(e->d_res); (void)hipFree(e->d_singles);
+    (void)hipFree(e->d_nul); (void)hipFree(e->d_ends);
+    if (e->ev0) (void)hipEventDestroy(e->ev0);
+    if (e->ev1) (void)hipEventDestroy(e->ev1);
+    if (e->stream) (void)hipStreamDestroy(e->stream);
+    delete e;
+}
 
-extern "C" int mbpe_encode_chunks(int device_id, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off,
-                                  uint64_t n_chunks, const uint32_t *merges, uint32_t n_merges, uint32_t *tokens_out,
-                                  uint64_t cap, uint64_t *n_out, uint32_t *n_passes_out) {
+int mbpe_encoder_set_option(mbpe_encoder *e, const char *name, int64_t value) {
+    if (!e || !name) return fail(MBPE_ERR_ARG, "mbpe_encoder_set_option: NULL argument");
+    if (strcmp(name, "piece_bytes") == 0) {
+        if (value < 0) return fail(MBPE_ERR_ARG, "piece_bytes must not be negative");
+        e->piece_bytes = (uint64_t)value;
+        return MBPE_OK;
+    }
+    return fail(MBPE_ERR_ARG, std::string("mbpe_encoder_set_option: no option \"") + name + "\"");
+}
+
+int mbpe_encoder_encode(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                        const uint64_t *chunk_off, uint64_t n_chunks, void *tokens_out, uint64_t cap,
+                        uint32_t token_bits, int out_on_device, uint64_t *chunk_tok_off_out, uint64_t *n_out,
+                        uint32_t *n_passes_out) {
+    if (n_out) *n_out = 0;
+    if (n_passes_out) *n_passes_out = 0;
+    if (!e || !n_out || (!text && n_bytes)) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode: NULL argument");
+    if (token_bits != 16 && token_bits != 32) return fail(MBPE_ERR_ARG, "token_bits must be 16 or 32");
+    return enc_run(e, text, n_bytes, text_on_device, chunk_off, n_chunks, tokens_out, cap, token_bits, out_on_device,
+                   chunk_tok_off_out, n_out, n_passes_out);
+}
+
+int mbpe_encoder_kernel_ms(const mbpe_encoder *e, float *ms_out) {
+    if (!e || !ms_out) return fail(MBPE_ERR_ARG, "mbpe_encoder_kernel_ms: NULL argument");
+    *ms_out = e->last_ms;
+    return MBPE_OK;
+}
+
+int mbpe_encoder_pass_tokens(const mbpe_encoder *e, uint64_t *tokens_out, uint32_t cap, uint32_t *n_out) {
+    if (!e || !n_out) return fail(MBPE_ERR_ARG, "mbpe_encoder_pass_tokens: NULL argument");
+    *n_out = (uint32_t)e->pass_tokens.size();
+    if (!tokens_out) return MBPE_OK;
+    if (cap < e->pass_tokens.size()) return fail(MBPE_ERR_ARG, "tokens_out too small");
+    for (size_t k = 0; k < e->pass_tokens.size(); ++k) tokens_out[k] = e->pass_tokens[k];
+    return MBPE_OK;
+}
+
+int mbpe_encoder_alloc_count(const mbpe_encoder *e, uint64_t *n_out) {
+    if (!e || !n_out) return fail(MBPE_ERR_ARG, "mbpe_encoder_alloc_count: NULL argument");
+    *n_out = e->n_allocs;
+    return MBPE_OK;
+}
+
+int mbpe_encode_chunks(int device_id, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off,
+                       uint64_t n_chunks, const uint32_t *merges, uint32_t n_merges, uint32_t *tokens_out,
+                       uint64_t cap, uint64_t *n_out, uint32_t *n_passes_out) {
     return encode_chunks(device_id, text, n_bytes, chunk_off, n_chunks, merges, n_merges, tokens_out, cap, n_out,
                          n_passes_out, false);
 }
 
-extern "C" int mbpe_encode_chunks_device(int device_id, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off,
-                                         uint64_t n_chunks, const uint32_t *merges, uint32_t n_merges,
-                                         uint32_t *tokens_dev_out, uint64_t cap, uint64_t *n_out,
-                                         uint32_t *n_passes_out) {
+int mbpe_encode_chunks_device(int device_id, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off,
+                              uint64_t n_chunks, const uint32_t *merges, uint32_t n_merges, uint32_t *tokens_dev_out,
+                              uint64_t cap, uint64_t *n_out, uint32_t *n_passes_out) {
     return encode_chunks(device_id, text, n_bytes, chunk_off, n_chunks, merges, n_merges, tokens_dev_out, cap, n_out,
                          n_passes_out, true);
 }
+
+}  // extern "C"

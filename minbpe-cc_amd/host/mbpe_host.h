@@ -13,6 +13,7 @@
 
 struct mbpe_ctx;
 struct mbpe_decoder;
+struct mbpe_encoder;
 
 namespace mbpe_host {
 

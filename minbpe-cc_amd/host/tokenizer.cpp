@@ -20,7 +20,29 @@ namespace mbpe_host {
 
 Tokenizer::Tokenizer() {}
 
-Tokenizer::~Tokenizer() { drop_decoder(); }
+Tokenizer::~Tokenizer() {
+    drop_decoder();
+    drop_encoder();
+}
+
+void Tokenizer::drop_encoder() {
+    if (encoder_) mbpe_encoder_destroy(encoder_);
+    encoder_ = nullptr;
+    encoder_device_ = -1;
+}
+
+mbpe_encoder *Tokenizer::device_encoder(int device) {
+    if (!encoder_ || encoder_device_ != device) {
+        drop_encoder();
+        std::vector<uint32_t> flat;
+        flat.reserve(2 * merges_.size());
+        for (const auto &m : merges_) { flat.push_back(m.first); flat.push_back(m.second); }
+        const int rc = mbpe_encoder_create(device, flat.data(), static_cast<uint32_t>(merges_.size()), &encoder_);
+        if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
+        encoder_device_ = device;
+    }
+    return encoder_;
+}
 
 void Tokenizer::drop_decoder() {
     if (decoder_) mbpe_decoder_destroy(decoder_);
@@ -67,6 +89,7 @@ void Tokenizer::rebuild_vocab() {      // :843-861 / :562-564
 
 void Tokenizer::set_merges(const std::vector<TokenPair> &m) {
     drop_decoder();
+    drop_encoder();
     merges_ = m;
     merges_lookup_.clear();
     Token idx = 256;
@@ -94,6 +117,7 @@ void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTI
                       bool verbose, int device) {
     if (vocab_size < 256) throw std::runtime_error("vocab_size must be >= 256");   // assert, :492
     drop_decoder();
+    drop_encoder();
     merges_.clear();
     merges_lookup_.clear();
     initialize_vocab();
@@ -198,8 +222,7 @@ std::vector<Token> Tokenizer::internal_internal_encode(std::vector<Token> text) 
     }
 }
 
-// :653-722.  device < 0: internal_encode on the host (below); device >= 0: on that HIP device (mbpe_encode_chunks)
-std::vector<Token> Tokenizer::encode(const std::string &text, bool verbose, int device) {
+void Tokenizer::append_chunks(const std::string &text, bool verbose, std::string *buf, std::vector<uint64_t> *off) const {
     auto split_text = split_on_special(text);
     if (verbose) {
         std::cout << "Splitting input text into " << split_text.size() << " parts\n";
@@ -208,11 +231,6 @@ std::vector<Token> Tokenizer::encode(const std::string &text, bool verbose, int 
             std::cout << "Part: \"" << part << "\" special: " << is_special << "\n";
         }
     }
-    // the chunks, as one byte buffer + offsets: special markers and, with a pattern, the regex matches of every
-    // other part (:664-704); without one, every part is a chunk (:706-709)
-    std::string buf;
-    std::vector<uint64_t> off{0};
-    buf.reserve(text.size() + 16 * split_text.size());
     for (const auto &part : split_text) {
         if (splitter_.has_pattern() && !(part.size() > 0 && part[0] == '\0')) {
             std::vector<uint64_t> starts, ends;
@@ -221,24 +239,31 @@ std::vector<Token> Tokenizer::encode(const std::string &text, bool verbose, int 
                 MBPE_OK)
                 throw std::runtime_error(err);                   // :686-691
             for (size_t i = 0; i < starts.size(); ++i) {
-                buf.append(part, starts[i], ends[i] - starts[i]);
-                off.push_back(buf.size());
+                buf->append(part, starts[i], ends[i] - starts[i]);
+                off->push_back(buf->size());
             }
         } else {
-            buf += part;
-            off.push_back(buf.size());
+            *buf += part;
+            off->push_back(buf->size());
         }
     }
+}
+
+// :653-722.  device < 0: internal_encode on the host (below); device >= 0: on that HIP device (mbpe_encoder_encode,
+// with an encoder that is kept until the merges change)
+std::vector<Token> Tokenizer::encode(const std::string &text, bool verbose, int device) {
+    // the chunks, as one byte buffer + offsets
+    std::string buf;
+    std::vector<uint64_t> off{0};
+    buf.reserve(text.size() + 64);
+    append_chunks(text, verbose, &buf, &off);
     std::vector<Token> out;
     if (device >= 0) {
-        std::vector<uint32_t> flat;
-        flat.reserve(2 * merges_.size());
-        for (const auto &m : merges_) { flat.push_back(m.first); flat.push_back(m.second); }
+        mbpe_encoder *enc = device_encoder(device);
         out.resize(buf.size());
         uint64_t n = 0;
-        const int rc = mbpe_encode_chunks(device, reinterpret_cast<const uint8_t *>(buf.data()), buf.size(), off.data(),
-                                          off.size() - 1, flat.data(), static_cast<uint32_t>(merges_.size()),
-                                          out.data(), out.size(), &n, nullptr);
+        const int rc = mbpe_encoder_encode(enc, reinterpret_cast<const uint8_t *>(buf.data()), buf.size(), 0, off.data(),
+                                           off.size() - 1, out.data(), out.size(), 32, 0, nullptr, &n, nullptr);
         if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());       // (the C-ABI hands the code on unchanged)
         out.resize(n);
     } else {
@@ -248,6 +273,50 @@ std::vector<Token> Tokenizer::encode(const std::string &text, bool verbose, int 
         }
     }
     if (verbose) std::cout << "Encoded input text (length " << text.length() << ") to " << out.size() << " tokens\n";
+    return out;
+}
+
+int Tokenizer::encode_batch_flat(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
+                                 Token *tokens_out, uint64_t cap, uint64_t *n_out, uint64_t *buf_bytes_out,
+                                 std::vector<uint64_t> *doc_tok_off) {
+    // every text is split on its own (a chunk never spans two texts); first_chunk[i] = its first chunk
+    std::string buf;
+    std::vector<uint64_t> off{0}, first_chunk(n_docs + 1, 0);
+    buf.reserve(doc_off[n_docs] - doc_off[0] + 64);
+    for (uint64_t i = 0; i < n_docs; ++i) {
+        first_chunk[i] = off.size() - 1;
+        if (doc_off[i + 1] > doc_off[i])                          // (an empty text has no chunk: an empty result)
+            append_chunks(std::string(text + doc_off[i], doc_off[i + 1] - doc_off[i]), verbose, &buf, &off);
+    }
+    first_chunk[n_docs] = off.size() - 1;
+    if (buf_bytes_out) *buf_bytes_out = buf.size();
+    mbpe_encoder *enc = device_encoder(device);
+    std::vector<uint64_t> chunk_tok_off(off.size(), 0);
+    const int rc = mbpe_encoder_encode(enc, reinterpret_cast<const uint8_t *>(buf.data()), buf.size(), 0, off.data(),
+                                       off.size() - 1, tokens_out, cap, 32, 0, chunk_tok_off.data(), n_out, nullptr);
+    if (rc != MBPE_OK) return rc;
+    doc_tok_off->resize(n_docs + 1);
+    for (uint64_t i = 0; i <= n_docs; ++i) (*doc_tok_off)[i] = chunk_tok_off[first_chunk[i]];
+    if (verbose) std::cout << "Encoded " << n_docs << " texts (length " << buf.size() << ") to " << *n_out << " tokens\n";
+    return MBPE_OK;
+}
+
+std::vector<std::vector<Token>> Tokenizer::encode_batch(const std::vector<std::string> &texts, bool verbose, int device) {
+    std::string all;
+    std::vector<uint64_t> doc_off{0};
+    for (const auto &t : texts) {
+        all += t;
+        doc_off.push_back(all.size());
+    }
+    // (a text never makes more tokens than it has bytes: a special token's name, at least one byte, is one token)
+    std::vector<Token> flat(all.size());
+    std::vector<uint64_t> tok_off;
+    uint64_t n = 0;
+    const int rc = encode_batch_flat(all.data(), doc_off.data(), texts.size(), verbose, device, flat.data(), flat.size(),
+                                     &n, nullptr, &tok_off);
+    if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
+    std::vector<std::vector<Token>> out(texts.size());
+    for (size_t i = 0; i < texts.size(); ++i) out[i].assign(flat.begin() + tok_off[i], flat.begin() + tok_off[i + 1]);
     return out;
 }
 
@@ -309,6 +378,7 @@ bool Tokenizer::load(const std::string &path, bool verbose) {
         return false;
     }
     drop_decoder();
+    drop_encoder();
     merges_lookup_.clear();
     merges_.clear();
     initialize_vocab();
@@ -487,6 +557,33 @@ int mbpe_tok_encode_device(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, i
         memcpy(tokens_out, enc.data(), enc.size() * sizeof(uint32_t));
         return MBPE_OK;
     } catch (const mbpe_host::CodedError &e) {      // mbpe_encode_chunks failed: its own code (no device, memory, HIP, ids)
+        mbpe_host::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        mbpe_host::set_last_error(e.what());
+        return MBPE_ERR_ARG;
+    }
+}
+
+int mbpe_tok_encode_batch_device(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off, uint64_t n_docs,
+                                 int verbose, int device_id, uint32_t *tokens_out, uint64_t cap,
+                                 uint64_t *doc_tok_off_out, uint64_t *n_out) {
+    if (n_out) *n_out = 0;
+    if (!t || !n_out || !doc_off || device_id < 0 || (!text && doc_off[n_docs] > doc_off[0])) {
+        mbpe_host::set_last_error("mbpe_tok_encode_batch_device: NULL argument or negative device");
+        return MBPE_ERR_ARG;
+    }
+    for (uint64_t i = 0; i < n_docs; ++i)
+        if (doc_off[i + 1] < doc_off[i]) { mbpe_host::set_last_error("doc_off must be ascending"); return MBPE_ERR_ARG; }
+    try {
+        // tokens_out, cap and n_out go to the encoder as they are: a query copies no token, a cap too small writes none
+        std::vector<uint64_t> tok_off;
+        const int rc = t->t->encode_batch_flat(reinterpret_cast<const char *>(text), doc_off, n_docs, verbose != 0,
+                                               device_id, tokens_out, cap, n_out, nullptr, &tok_off);
+        if (rc != MBPE_OK) return rc;
+        if (doc_tok_off_out) memcpy(doc_tok_off_out, tok_off.data(), tok_off.size() * sizeof(uint64_t));
+        return MBPE_OK;
+    } catch (const mbpe_host::CodedError &e) {      // mbpe_encoder_create failed: its own code
         mbpe_host::set_last_error(e.what());
         return e.code;
     } catch (const std::exception &e) {

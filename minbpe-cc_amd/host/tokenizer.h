@@ -34,6 +34,14 @@ public:
                int device = 0);
     // :653-722; device >= 0 runs internal_encode (:325-377) on that HIP device instead of the host
     std::vector<Token> encode(const std::string &text, bool verbose, int device = -1);
+    // encode() of every text, [i] == encode(texts[i], false, -1): the chunks of all texts go to HIP device `device`
+    // in one mbpe_encoder_encode, whose per-chunk token offsets are summed per text
+    std::vector<std::vector<Token>> encode_batch(const std::vector<std::string> &texts, bool verbose, int device);
+    // the same over one buffer: n_docs + 1 ascending offsets.  tokens_out / cap / n_out go to mbpe_encoder_encode as
+    // they are (NULL: query), whose code is returned; doc_tok_off receives n_docs + 1 token offsets when it is MBPE_OK
+    int encode_batch_flat(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
+                          Token *tokens_out, uint64_t cap, uint64_t *n_out, uint64_t *buf_bytes_out,
+                          std::vector<uint64_t> *doc_tok_off);
     // :725-751; device >= 0 expands the tokens on that HIP device (mbpe_decode_tokens) instead of the host loop
     std::string decode(const std::vector<Token> &tokens, bool verbose, int device = -1);
     bool load(const std::string &path, bool verbose);                      // :754-872
@@ -59,6 +67,11 @@ private:
     std::vector<Token> internal_internal_encode(std::vector<Token> text) const; // :325-367
     void rebuild_vocab();
     void drop_decoder();                   // the merges or the specials changed
+    void drop_encoder();                   // the merges changed (special tokens do not enter the lookup table)
+    // the chunks of one text appended to buf / off: special markers and, with a pattern, the regex matches of every
+    // other part (:664-704); without one, every part is a chunk (:706-709)
+    void append_chunks(const std::string &text, bool verbose, std::string *buf, std::vector<uint64_t> *off) const;
+    mbpe_encoder *device_encoder(int device);
 
     std::string pattern_;
     Splitter splitter_;
@@ -71,6 +84,8 @@ private:
     std::vector<std::vector<Token>> vocab_;
     mbpe_decoder *decoder_ = nullptr;      // device tables of decode(..., device), kept until the model changes
     int decoder_device_ = -1;
+    mbpe_encoder *encoder_ = nullptr;      // lookup table and buffers of encode(..., device), kept until the merges change
+    int encoder_device_ = -1;
 };
 
 }  // namespace mbpe_host

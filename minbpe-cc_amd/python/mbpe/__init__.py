@@ -28,13 +28,15 @@ EXPORTS = [
     "mbpe_split_count", "mbpe_split_offsets", "mbpe_split_has_gaps", "mbpe_split_starts", "mbpe_split_ends",
     "mbpe_split_free", "mbpe_load_corpus_ranges", "mbpe_split_pattern", "mbpe_encode_chunks",
     "mbpe_encode_chunks_device", "mbpe_decoder_create", "mbpe_decoder_destroy", "mbpe_decode_tokens",
-    "mbpe_decode_slots", "mbpe_decoder_kernel_ms", "mbpe_decode_stream",
+    "mbpe_decode_slots", "mbpe_decoder_kernel_ms", "mbpe_decode_stream", "mbpe_encoder_create",
+    "mbpe_encoder_destroy", "mbpe_encoder_encode", "mbpe_encoder_set_option", "mbpe_encoder_kernel_ms",
+    "mbpe_encoder_alloc_count", "mbpe_encoder_pass_tokens",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
     "mbpe_tok_create", "mbpe_tok_destroy", "mbpe_tok_set_special_tokens", "mbpe_tok_train", "mbpe_tok_set_merges",
     "mbpe_tok_get_merges", "mbpe_tok_save", "mbpe_tok_load", "mbpe_tok_encode", "mbpe_tok_encode_device",
-    "mbpe_tok_decode", "mbpe_tok_decode_device",
+    "mbpe_tok_decode", "mbpe_tok_decode_device", "mbpe_tok_encode_batch_device",
 ]
 
 
@@ -123,6 +125,15 @@ def lib():
     L.mbpe_split_pattern.restype = ctypes.c_char_p
     L.mbpe_encode_chunks.argtypes = [i32, vp, u64, vp, u64, vp, u32, vp, u64, vp, vp]
     L.mbpe_encode_chunks_device.argtypes = [i32, vp, u64, vp, u64, vp, u32, vp, u64, vp, vp]
+    L.mbpe_encoder_create.argtypes = [i32, vp, u32, ctypes.POINTER(vp)]
+    L.mbpe_encoder_destroy.argtypes = [vp]
+    L.mbpe_encoder_destroy.restype = None
+    L.mbpe_encoder_encode.argtypes = [vp, vp, u64, i32, vp, u64, vp, u64, u32, i32, vp, vp, vp]
+    L.mbpe_encoder_set_option.argtypes = [vp, ctypes.c_char_p, i64]
+    L.mbpe_encoder_kernel_ms.argtypes = [vp, vp]
+    L.mbpe_encoder_alloc_count.argtypes = [vp, vp]
+    L.mbpe_encoder_pass_tokens.argtypes = [vp, vp, u32, vp]
+    L.mbpe_tok_encode_batch_device.argtypes = [vp, vp, vp, u64, i32, i32, vp, u64, vp, vp]
     L.mbpe_decoder_create.argtypes = [i32, vp, u32, vp, vp, vp, u32, ctypes.POINTER(vp)]
     L.mbpe_decoder_destroy.argtypes = [vp]
     L.mbpe_decoder_destroy.restype = None
@@ -225,6 +236,94 @@ def encode_chunks_device(data, chunk_off, merges, out_ptr, cap, device=0):
                                            ctypes.c_void_p(out_ptr) if out_ptr else None, cap,
                                            ctypes.byref(n), ctypes.byref(passes)))
     return n.value, passes.value
+
+
+class Encoder:
+    """One mbpe_encoder: internal_encode (Tokenizer.h:325-377) on a HIP device with the lookup table, the stream and
+    the work buffers kept between calls."""
+
+    def __init__(self, merges, device=0):
+        self._h = ctypes.c_void_p()
+        m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1, 2)
+        _check(lib().mbpe_encoder_create(device, m.ctypes.data if len(m) else None, len(m), ctypes.byref(self._h)))
+        self.n_passes = 0
+
+    def close(self):
+        if self._h:
+            lib().mbpe_encoder_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_option(self, name, value):
+        _check(lib().mbpe_encoder_set_option(self._h, name.encode(), int(value)))
+
+    def encode(self, data, chunk_off=None, offsets=False, dtype=np.uint32):
+        """Host text -> host tokens of dtype uint32 or uint16, or (tokens, chunk_tok_off) with offsets=True: the
+        tokens of chunk c are tokens[chunk_tok_off[c]:chunk_tok_off[c + 1]].  The passes made: self.n_passes."""
+        text = _u8(data)
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.uint32), np.dtype(np.uint16)):
+            raise ValueError("dtype must be uint32 or uint16")
+        off = None if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.uint64)
+        n_chunks = 1 if off is None else len(off) - 1
+        out = np.zeros(max(len(text), 1), dtype=dtype)
+        tok_off = np.zeros(n_chunks + 1, dtype=np.uint64) if offsets else None
+        n, passes = ctypes.c_uint64(), ctypes.c_uint32()
+        _check(lib().mbpe_encoder_encode(self._h, text.ctypes.data if len(text) else None, len(text), 0,
+                                         None if off is None else off.ctypes.data, 0 if off is None else n_chunks,
+                                         out.ctypes.data, len(out), dtype.itemsize * 8, 0,
+                                         None if tok_off is None else tok_off.ctypes.data,
+                                         ctypes.byref(n), ctypes.byref(passes)))
+        self.n_passes = passes.value
+        tokens = out[:n.value].copy()
+        return (tokens, tok_off) if offsets else tokens
+
+    def encode_device(self, text_ptr, n_bytes, chunk_off, out_ptr, cap, token_bits=32, offsets=False):
+        """n_bytes of text in device memory at text_ptr (e.g. a torch tensor's data_ptr(); read in place) -> tokens in
+        device memory at out_ptr (0: query; room for cap tokens of token_bits bits; 32: bit 31 = chunk end, 16: plain
+        ids) -> token count, or (count, chunk_tok_off) with offsets=True."""
+        off = None if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.uint64)
+        n_chunks = 1 if off is None else len(off) - 1
+        tok_off = np.zeros(n_chunks + 1, dtype=np.uint64) if offsets else None
+        n, passes = ctypes.c_uint64(), ctypes.c_uint32()
+        _check(lib().mbpe_encoder_encode(self._h, ctypes.c_void_p(text_ptr) if text_ptr else None, n_bytes, 1,
+                                         None if off is None else off.ctypes.data, 0 if off is None else n_chunks,
+                                         ctypes.c_void_p(out_ptr) if out_ptr else None, cap, token_bits, 1,
+                                         None if tok_off is None else tok_off.ctypes.data,
+                                         ctypes.byref(n), ctypes.byref(passes)))
+        self.n_passes = passes.value
+        return (n.value, tok_off) if offsets else n.value
+
+    def kernel_ms(self):
+        """Device time of the latest call (mbpe_encoder_kernel_ms)."""
+        ms = ctypes.c_float()
+        _check(lib().mbpe_encoder_kernel_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def pass_tokens(self):
+        """Tokens that entered every pass of the latest call (mbpe_encoder_pass_tokens) -> list."""
+        n = ctypes.c_uint32()
+        _check(lib().mbpe_encoder_pass_tokens(self._h, None, 0, ctypes.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.uint64)
+        _check(lib().mbpe_encoder_pass_tokens(self._h, out.ctypes.data, n.value, ctypes.byref(n)))
+        return [int(v) for v in out[:n.value]]
+
+    def alloc_count(self):
+        """Device allocations made so far (mbpe_encoder_alloc_count)."""
+        n = ctypes.c_uint64()
+        _check(lib().mbpe_encoder_alloc_count(self._h, ctypes.byref(n)))
+        return n.value
 
 
 class Decoder:
@@ -544,6 +643,21 @@ class Tokenizer:
             _check(lib().mbpe_tok_encode_device(self._h, text.ctypes.data if len(text) else None, len(text), 0, device,
                                                 out.ctypes.data, len(out), ctypes.byref(n)))
         return out[:n.value].copy()
+
+    def encode_batch(self, texts, device=0):
+        """encode() of every text in one device call (mbpe_tok_encode_batch_device) -> list of uint32 arrays."""
+        parts = [bytes(_u8(t)) for t in texts]
+        doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        if parts:
+            doc_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
+        text = np.frombuffer(b"".join(parts), dtype=np.uint8)
+        out = np.zeros(max(len(text), 1), dtype=np.uint32)
+        tok_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        n = ctypes.c_uint64()
+        _check(lib().mbpe_tok_encode_batch_device(self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data,
+                                                  len(parts), 0, device, out.ctypes.data, len(out), tok_off.ctypes.data,
+                                                  ctypes.byref(n)))
+        return [out[int(a):int(b)].copy() for a, b in zip(tok_off[:-1], tok_off[1:])]
 
     def decode(self, tokens, device=None):
         """device None: the host loop; an int: on that HIP device (mbpe_tok_decode_device)."""
