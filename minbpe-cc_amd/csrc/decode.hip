@@ -10,7 +10,7 @@
 // specials with ids >= V follow as entries V .. E-1 and are found through a small open-addressed table that is
 // probed only for ids >= V.
 //
-// A span = 1,024 consecutive tokens = the unit one wave walks, as in encode.hip and wide.hip.
+// A span = 1,024 consecutive tokens = the unit one wave walks (span.h), as in encode.hip and wide.hip.
 //   k_dec_len<F>     token -> length; per span the byte total (u64); ids that decode to nothing are counted
 //   k_dec_scan64     exclusive 64-bit scan of the span totals (one workgroup, 4,096 spans per step)
 //   k_dec_write<F>   per span: prefix sums of the lengths into LDS, then OUTPUT-centric copying: the span's output
@@ -23,10 +23,8 @@
 //
 // Bytes moved per decode: the tokens twice (4 B or 2 B each), the output once; len / off / blob are gathered from
 // cache (a few hundred KB to a few MB for text vocabularies).
-#include "mbpe.h"
-#include "../host/mbpe_host.h"
-
-#include <hip/hip_runtime.h>
+#include "hip_host.h"
+#include "span.h"
 
 #include <algorithm>
 #include <cstring>
@@ -37,20 +35,16 @@
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kSpan = 1024;
-constexpr int kSpanIters = kSpan / kWave;
-constexpr int kDecThreads = 256;           // 4 waves = 4 spans per workgroup
-constexpr int kDecWaves = kDecThreads / kWave;
-constexpr int kScanThreads = 1024;
+using namespace mbpe;
+
 constexpr int kScanPer = 4;                // spans per thread and step of the scan
-constexpr uint32_t kNone = 0xFFFFFFFFu;
+constexpr uint32_t kNone = 0xFFFFFFFFu;   // free slot of the specials' table
 constexpr uint32_t kBlobPad = 16;          // a 16-byte gather may read this far beyond an entry
 
 // how a token is read; the 16-bit layouts are those of mbpe_stream_device (mbpe.h)
 enum DecFmt {
     kFmtU32 = 0,        // plain uint32_t ids
-    kFmtU32End = 1,     // bit 31 = last token of its chunk (encode.hip, wide.hip); all-ones = hole
+    kFmtU32End = 1,     // the layout of span.h: bit 31 = last token of its chunk, all-ones = hole
     kFmtU16 = 2,        // 16-bit slots, all-ones = hole
     kFmtU16End = 3,     // ... bit 15 = last token of its chunk
     kFmtU16Barrier = 4  // ... one slot value is the barrier after a chunk, no token
@@ -70,15 +64,13 @@ struct DecTab {
 
 __host__ __device__ inline uint32_t dec_hash(uint32_t id, uint32_t shift) { return (id * 0x9E3779B1u) >> shift; }
 
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (kWave - 1); }
-
 // slot i -> id; false: the slot holds no token (hole, barrier)
 template <int F>
 __device__ __forceinline__ bool dec_read(const void *__restrict__ tok, uint64_t i, uint32_t barrier, uint32_t *id) {
     if (F == kFmtU32 || F == kFmtU32End) {
         const uint32_t t = static_cast<const uint32_t *>(tok)[i];
-        if (F == kFmtU32End && t == kNone) return false;
-        *id = F == kFmtU32End ? (t & 0x7FFFFFFFu) : t;
+        if (F == kFmtU32End && t == kTokNone) return false;
+        *id = F == kFmtU32End ? (t & kTokIdMask) : t;
         return true;
     }
     const uint32_t s = static_cast<const uint16_t *>(tok)[i];
@@ -102,11 +94,10 @@ __device__ __forceinline__ bool dec_entry(const DecTab &tab, uint32_t id, uint32
 }
 
 template <int F>
-__global__ __launch_bounds__(kDecThreads) void k_dec_len(const void *__restrict__ tok, uint64_t n, uint32_t barrier,
-                                                         DecTab tab, unsigned long long *__restrict__ span_total,
-                                                         unsigned long long *__restrict__ n_invalid) {
-    const uint64_t span = (uint64_t)blockIdx.x * kDecWaves + threadIdx.x / kWave;
-    const uint64_t base = span * kSpan;
+__global__ __launch_bounds__(kSpanThreads) void k_dec_len(const void *__restrict__ tok, uint64_t n, uint32_t barrier,
+                                                          DecTab tab, unsigned long long *__restrict__ span_total,
+                                                          unsigned long long *__restrict__ n_invalid) {
+    const uint64_t span = span_index(), base = span * kSpan;
     if (base >= n) return;
     const uint32_t lane = lane_id();
     unsigned long long sum = 0;
@@ -130,7 +121,7 @@ __global__ __launch_bounds__(kDecThreads) void k_dec_len(const void *__restrict_
 }
 
 // v[s] <- sum of v[0 .. s-1], in place; *total <- the sum of all.  One workgroup walks the spans in steps of
-// kScanThreads * kScanPer with a running carry (encode.hip's scans are 32-bit and one slice per thread).
+// kScanThreads * kScanPer with a running carry (span.h's scans are 32-bit and one slice per thread).
 __global__ __launch_bounds__(kScanThreads) void k_dec_scan64(unsigned long long *__restrict__ v, uint64_t n,
                                                              unsigned long long *__restrict__ total) {
     __shared__ unsigned long long wsum[kScanThreads / kWave];
@@ -177,15 +168,15 @@ __device__ __forceinline__ unsigned __int128 load16(const uint8_t *p) {
 }
 
 template <int F>
-__global__ __launch_bounds__(kDecThreads) void k_dec_write(const void *__restrict__ tok, uint64_t n, uint32_t barrier,
-                                                           DecTab tab, const unsigned long long *__restrict__ span_off,
-                                                           uint8_t *__restrict__ out) {
+__global__ __launch_bounds__(kSpanThreads) void k_dec_write(const void *__restrict__ tok, uint64_t n, uint32_t barrier,
+                                                            DecTab tab, const unsigned long long *__restrict__ span_off,
+                                                            uint8_t *__restrict__ out) {
     // per wave: s_off[j] = bytes of the span before its token j (s_off[kSpan] = the span's total, below 2^32:
     // MBPE_DECODER_MAX_ENTRY), s_src[j] = where token j's bytes start in the blob (below 2^32: MBPE_DECODER_MAX_BLOB)
-    __shared__ uint32_t s_off[kDecWaves][kSpan + 1];
-    __shared__ uint32_t s_src[kDecWaves][kSpan];
+    __shared__ uint32_t s_off[kSpanWaves][kSpan + 1];
+    __shared__ uint32_t s_src[kSpanWaves][kSpan];
     const uint32_t w = threadIdx.x / kWave, lane = lane_id();
-    const uint64_t span = (uint64_t)blockIdx.x * kDecWaves + w;
+    const uint64_t span = span_index();
     const uint64_t base = span * kSpan;
     const bool active = base < n;
     if (active) {
@@ -253,16 +244,7 @@ __global__ __launch_bounds__(kDecThreads) void k_dec_write(const void *__restric
     }
 }
 
-std::string hip_err(const char *what, hipError_t e) { return std::string(what) + ": " + hipGetErrorString(e); }
-
-#define DCHK(expr)                                                            \
-    do {                                                                      \
-        hipError_t e__ = (expr);                                              \
-        if (e__ != hipSuccess) {                                              \
-            mbpe_host::set_last_error(hip_err(#expr, e__));                   \
-            return e__ == hipErrorOutOfMemory ? MBPE_ERR_OOM : MBPE_ERR_HIP;  \
-        }                                                                     \
-    } while (0)
+#define DCHK(expr) MBPE_HIP_CHECK(expr, false)
 
 int fail(int code, const char *msg) {
     mbpe_host::set_last_error(msg);
@@ -293,34 +275,23 @@ struct mbpe_decoder {
 
 namespace {
 
-template <typename T>
-int grow(T **p, uint64_t *cap, uint64_t want_bytes) {
-    if (*cap >= want_bytes && *p) return MBPE_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    DCHK(hipMalloc(reinterpret_cast<void **>(p), want_bytes));
-    *cap = want_bytes;
-    return MBPE_OK;
-}
-
 template <int F>
 void launch_len(mbpe_decoder *d, const void *tok, uint64_t n, uint32_t barrier, uint32_t grid) {
-    hipLaunchKernelGGL(k_dec_len<F>, dim3(grid), dim3(kDecThreads), 0, d->stream, tok, n, barrier, d->tab, d->d_span,
+    hipLaunchKernelGGL(k_dec_len<F>, dim3(grid), dim3(kSpanThreads), 0, d->stream, tok, n, barrier, d->tab, d->d_span,
                        d->d_res + 1);
 }
 template <int F>
 void launch_write(mbpe_decoder *d, const void *tok, uint64_t n, uint32_t barrier, uint32_t grid, uint8_t *out) {
-    hipLaunchKernelGGL(k_dec_write<F>, dim3(grid), dim3(kDecThreads), 0, d->stream, tok, n, barrier, d->tab, d->d_span,
+    hipLaunchKernelGGL(k_dec_write<F>, dim3(grid), dim3(kSpanThreads), 0, d->stream, tok, n, barrier, d->tab, d->d_span,
                        out);
 }
 
 // lengths + scan of n device-resident tokens; ev0 is recorded in front
 int dec_measure(mbpe_decoder *d, int fmt, const void *tok, uint64_t n, uint32_t barrier, uint64_t *total,
                 uint64_t *invalid) {
-    const uint64_t n_spans = (n + kSpan - 1) / kSpan;
-    const uint32_t grid = (uint32_t)((n_spans + kDecWaves - 1) / kDecWaves);
-    int rc = grow(&d->d_span, &d->cap_spans, (n_spans + 1) * 8);
+    const uint64_t n_spans = span_count(n);
+    const uint32_t grid = span_grid(n);
+    int rc = grow(&d->d_span, &d->cap_spans, (n_spans + 1) * 8, false, nullptr);
     if (rc != MBPE_OK) return rc;
     DCHK(hipMemsetAsync(d->d_res, 0, 16, d->stream));
     DCHK(hipEventRecord(d->ev0, d->stream));
@@ -346,8 +317,7 @@ int dec_measure(mbpe_decoder *d, int fmt, const void *tok, uint64_t n, uint32_t 
 // the copy, after dec_measure of the same tokens; records ev1 and waits
 int dec_write(mbpe_decoder *d, int fmt, const void *tok, uint64_t n, uint32_t barrier, uint8_t *out_dev, bool wrote) {
     if (wrote && n) {
-        const uint64_t n_spans = (n + kSpan - 1) / kSpan;
-        const uint32_t grid = (uint32_t)((n_spans + kDecWaves - 1) / kDecWaves);
+        const uint32_t grid = span_grid(n);
         switch (fmt) {
             case kFmtU32: launch_write<kFmtU32>(d, tok, n, barrier, grid, out_dev); break;
             case kFmtU32End: launch_write<kFmtU32End>(d, tok, n, barrier, grid, out_dev); break;
@@ -373,7 +343,7 @@ int dec_run(mbpe_decoder *d, int fmt, const void *tokens, uint64_t n, int tokens
     const uint64_t tok_bytes = n * (fmt <= kFmtU32End ? 4 : 2);
     const void *tok = tokens;
     if (!tokens_on_device && n) {
-        int rc = grow(&d->d_tok, &d->cap_tok, tok_bytes);
+        int rc = grow(&d->d_tok, &d->cap_tok, tok_bytes, false, nullptr);
         if (rc != MBPE_OK) return rc;
         DCHK(hipMemcpyAsync(d->d_tok, tokens, tok_bytes, hipMemcpyHostToDevice, d->stream));
         tok = d->d_tok;
@@ -390,7 +360,7 @@ int dec_run(mbpe_decoder *d, int fmt, const void *tokens, uint64_t n, int tokens
     }
     if (out_on_device) return dec_write(d, fmt, tok, n, barrier, bytes_out, true);
     if (total) {
-        rc = grow(&d->d_out, &d->cap_out, total);
+        rc = grow(&d->d_out, &d->cap_out, total, false, nullptr);
         if (rc != MBPE_OK) return rc;
     }
     rc = dec_write(d, fmt, tok, n, barrier, d->d_out, total != 0);
@@ -403,7 +373,7 @@ int dec_run(mbpe_decoder *d, int fmt, const void *tokens, uint64_t n, int tokens
 }
 
 int slot_format(uint32_t slot_bits, uint32_t end_bit, uint32_t barrier, int *fmt) {
-    if (slot_bits == 32 && barrier == MBPE_NO_BARRIER && (end_bit == 0 || end_bit == 0x80000000u)) {
+    if (slot_bits == 32 && barrier == MBPE_NO_BARRIER && (end_bit == 0 || end_bit == kTokEnd)) {
         *fmt = end_bit ? kFmtU32End : kFmtU32;
         return MBPE_OK;
     }
@@ -428,7 +398,7 @@ int decode_to_string(mbpe_decoder *d, const uint32_t *tokens, uint64_t n, std::s
     if (!d || (!tokens && n)) return fail(MBPE_ERR_ARG, "decode_to_string: NULL argument");
     DCHK(hipSetDevice(d->device));
     if (n) {
-        int rc = grow(&d->d_tok, &d->cap_tok, n * 4);
+        int rc = grow(&d->d_tok, &d->cap_tok, n * 4, false, nullptr);
         if (rc != MBPE_OK) return rc;
         DCHK(hipMemcpyAsync(d->d_tok, tokens, n * 4, hipMemcpyHostToDevice, d->stream));
     }
@@ -436,7 +406,7 @@ int decode_to_string(mbpe_decoder *d, const uint32_t *tokens, uint64_t n, std::s
     int rc = dec_measure(d, kFmtU32, d->d_tok, n, MBPE_NO_BARRIER, &total, n_invalid);
     if (rc != MBPE_OK) return rc;
     if (total) {
-        rc = grow(&d->d_out, &d->cap_out, total);
+        rc = grow(&d->d_out, &d->cap_out, total, false, nullptr);
         if (rc != MBPE_OK) return rc;
     }
     rc = dec_write(d, kFmtU32, d->d_tok, n, MBPE_NO_BARRIER, d->d_out, total != 0);

@@ -12,8 +12,8 @@
 // as it is, so passes over the whole text until nothing changes give every chunk its reference result.
 //
 // Layout: 32-bit tokens (the reference's Token, Tokenizer.h:37), bit 31 = "last token of its chunk".
-// A span = 1,024 consecutive tokens = the unit one wave walks (16 x 64 lanes, ballots give the
-// candidate masks); spans are linked by two small scans (run parity, output offsets).
+// A span = 1,024 consecutive tokens = the unit one wave walks; spans are linked by two small scans (run parity,
+// output offsets).  span.h holds the layout, the run arithmetic, the scans and the compaction.
 //
 // An mbpe_encoder keeps what does not change between calls: the pair -> id table on the device, a stream, and the
 // work buffers (text, end mask, two token arrays, cand, span arrays), which grow when a call needs more.  A call
@@ -22,10 +22,8 @@
 // the caller wants to know which tokens belong to which chunk, the position after every flagged token (per-span
 // count of flags -> k_enc_scan_sum -> ranked write).  A text that lives on the device is read in place; the chunk
 // starts whose byte is NUL are listed by a small kernel so that the host can parse those chunks.
-#include "mbpe.h"
-#include "../host/mbpe_host.h"
-
-#include <hip/hip_runtime.h>
+#include "hip_host.h"
+#include "span.h"
 
 #include <algorithm>
 #include <cstring>
@@ -35,14 +33,9 @@
 
 namespace {
 
-constexpr uint32_t kEnd = 0x80000000u;     // last token of its chunk
-constexpr uint32_t kNone = 0xFFFFFFFFu;    // no candidate / token removed
+using namespace mbpe;
+
 constexpr uint32_t kDrop = 0x7FFFFFFEu;    // byte of a chunk that collapses to one token (Tokenizer.h:86-93)
-constexpr uint32_t kIdMask = 0x7FFFFFFFu;
-constexpr int kWave = 64;
-constexpr int kSpan = 1024;
-constexpr int kSpanIters = kSpan / kWave;
-constexpr int kEncThreads = 256;           // 4 waves = 4 spans per workgroup
 constexpr unsigned long long kEmptyKey = ~0ull;
 
 struct EncLut {
@@ -52,22 +45,16 @@ struct EncLut {
     uint32_t mask;
 };
 
-__host__ __device__ inline uint32_t enc_hash(unsigned long long key, uint32_t shift) {
-    return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> shift);
-}
-
 __device__ __forceinline__ uint32_t enc_lookup(const EncLut &lut, uint32_t a, uint32_t b) {
     const unsigned long long key = ((unsigned long long)a << 32) | b;
-    uint32_t h = enc_hash(key, lut.shift);
+    uint32_t h = pair_hash(key, lut.shift);
     for (;;) {
         const unsigned long long k = lut.keys[h];
         if (k == key) return lut.vals[h];
-        if (k == kEmptyKey) return kNone;
+        if (k == kEmptyKey) return kTokNone;
         h = (h + 1) & lut.mask;
     }
 }
-
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (kWave - 1); }
 
 // text_to_vector, Tokenizer.h:94-99 (char_to_token :80-82) + chunk ends
 __global__ void k_enc_widen(const uint8_t *__restrict__ text, uint64_t n, const uint8_t *__restrict__ endmask,
@@ -76,7 +63,7 @@ __global__ void k_enc_widen(const uint8_t *__restrict__ text, uint64_t n, const 
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) {
         const uint32_t e = (endmask[i >> 3] >> (i & 7)) & 1u;
-        tok[i] = text[i] | (e ? kEnd : 0u);
+        tok[i] = text[i] | (e ? kTokEnd : 0u);
     }
 }
 
@@ -87,145 +74,79 @@ __global__ void k_enc_single(const SingleChunk *__restrict__ sc, uint32_t n_sc, 
     if (c >= n_sc) return;
     const SingleChunk s = sc[c];
     for (unsigned long long i = threadIdx.x; i < s.len; i += blockDim.x)
-        tok[s.start + i] = i == 0 ? (s.id | kEnd) : kDrop;
+        tok[s.start + i] = i == 0 ? (s.id | kTokEnd) : kDrop;
 }
 
-// pass, step 1: cand[i] = id of the token that (t[i], t[i+1]) merges to, or kNone; per span: are all its
+// pass, step 1: cand[i] = id of the token that (t[i], t[i+1]) merges to, or kTokNone; per span: are all its
 // positions candidates, and the parity of its trailing run of candidates
-__global__ __launch_bounds__(kEncThreads) void k_enc_cand(const uint32_t *__restrict__ tok, uint64_t n, EncLut lut,
-                                                          uint32_t *__restrict__ cand,
-                                                          uint32_t *__restrict__ span_sum) {
-    const uint64_t span = (uint64_t)blockIdx.x * (kEncThreads / kWave) + threadIdx.x / kWave;
-    const uint64_t base = span * kSpan;
+__global__ __launch_bounds__(kSpanThreads) void k_enc_cand(const uint32_t *__restrict__ tok, uint64_t n, EncLut lut,
+                                                           uint32_t *__restrict__ cand,
+                                                           uint32_t *__restrict__ span_sum) {
+    const uint64_t span = span_index(), base = span * kSpan;
     if (base >= n) return;
     const uint32_t lane = lane_id();
-    bool all = true;
-    uint32_t par = 0;
+    SpanSum sum = span_empty();
     for (int it = 0; it < kSpanIters; ++it) {
         const uint64_t i = base + (uint64_t)it * kWave + lane;
-        const uint32_t t = i < n ? tok[i] : kDrop;
-        uint32_t nx = __shfl_down(t, 1, kWave);
-        if (lane == kWave - 1) nx = i + 1 < n ? tok[i + 1] : kDrop;
-        uint32_t c = kNone;
-        if (i < n && !(t & kEnd) && t != kDrop && nx != kDrop) c = enc_lookup(lut, t, nx & kIdMask);
+        uint32_t nx;
+        const uint32_t t = load_pair(tok, i, n, lane, kDrop, &nx);
+        uint32_t c = kTokNone;
+        if (i < n && !(t & kTokEnd) && t != kDrop && nx != kDrop) c = enc_lookup(lut, t, nx & kTokIdMask);
         if (i < n) cand[i] = c;
-        const unsigned long long M = __ballot(c != kNone);
-        if (M != ~0ull) {
-            all = false;
-            par = (uint32_t)__builtin_clzll(~M) & 1u;        // candidates at the top of this group
-        }                                                   // (a full group adds 64: parity unchanged)
+        sum = span_add_group(sum, __ballot(c != kTokNone));
     }
-    if (lane == 0) span_sum[span] = (all ? 1u : 0u) | (par << 1);
+    if (lane == 0) span_sum[span] = span_pack(sum);
 }
 
-// One workgroup, two sweeps: out[s] = the fold of elements 0 .. s-1 under an associative operator.
-// Thread t owns a contiguous slice of the spans.
-//   parity scan: element (all, par); L then R = R.all ? (L.all, L.par ^ R.par) : R      [a full span has
-//                                                                                        even length]
-constexpr int kScanThreads = 1024;
+// the two scans that link the spans (span.h): the parity of the run of candidates that reaches each span ...
 __global__ __launch_bounds__(kScanThreads) void k_enc_scan_parity(const uint32_t *__restrict__ span_sum,
                                                                   uint64_t n_spans, uint32_t *__restrict__ in_par) {
     __shared__ uint32_t sh[kScanThreads];
-    const uint64_t per = (n_spans + kScanThreads - 1) / kScanThreads;
-    const uint64_t lo = per * threadIdx.x, hi = lo + per < n_spans ? lo + per : n_spans;
-    uint32_t all = 1, par = 0;
-    for (uint64_t s = lo; s < hi; ++s) {
-        const uint32_t v = span_sum[s];
-        if (v & 1u) par ^= v >> 1; else { all = 0; par = v >> 1; }
-    }
-    sh[threadIdx.x] = all | (par << 1);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t a = 1, p = 0;                 // nothing before the text: an empty (full, even) prefix
-        for (int t = 0; t < kScanThreads; ++t) {
-            const uint32_t v = sh[t];
-            sh[t] = p;                         // parity of the run of candidates right before slice t
-            if (v & 1u) p ^= v >> 1; else { a = 0; p = v >> 1; }
-        }
-        (void)a;
-    }
-    __syncthreads();
-    par = sh[threadIdx.x];
-    for (uint64_t s = lo; s < hi; ++s) {
-        in_par[s] = par;
-        const uint32_t v = span_sum[s];
-        if (v & 1u) par ^= v >> 1; else par = v >> 1;
-    }
+    span_scan_parity(span_sum, n_spans, in_par, sh);
 }
 
-//   sum scan: exclusive prefix sums of the spans' kept-token counts; total to *total
+// ... and the exclusive prefix sums of the spans' kept-token counts; total to *total
 __global__ __launch_bounds__(kScanThreads) void k_enc_scan_sum(const uint32_t *__restrict__ cnt, uint64_t n_spans,
                                                                unsigned long long *__restrict__ off,
                                                                unsigned long long *__restrict__ total) {
     __shared__ unsigned long long sh[kScanThreads];
-    const uint64_t per = (n_spans + kScanThreads - 1) / kScanThreads;
-    const uint64_t lo = per * threadIdx.x, hi = lo + per < n_spans ? lo + per : n_spans;
-    unsigned long long s = 0;
-    for (uint64_t i = lo; i < hi; ++i) s += cnt[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long acc = 0;
-        for (int t = 0; t < kScanThreads; ++t) { const unsigned long long v = sh[t]; sh[t] = acc; acc += v; }
-        *total = acc;
-    }
-    __syncthreads();
-    s = sh[threadIdx.x];
-    for (uint64_t i = lo; i < hi; ++i) { off[i] = s; s += cnt[i]; }
+    const unsigned long long sum = span_scan_sum(cnt, n_spans, off, sh);
+    if (threadIdx.x == 0) *total = sum;
 }
 
 // pass, step 2: with the parity of the candidate run before every position, decide.  cand[i] becomes the
-// value position i contributes to the next stream (kNone: nothing).
-__global__ __launch_bounds__(kEncThreads) void k_enc_match(const uint32_t *__restrict__ tok, uint64_t n,
-                                                           uint32_t *__restrict__ cand,
-                                                           const uint32_t *__restrict__ in_par,
-                                                           uint32_t *__restrict__ span_keep) {
-    const uint64_t span = (uint64_t)blockIdx.x * (kEncThreads / kWave) + threadIdx.x / kWave;
-    const uint64_t base = span * kSpan;
+// value position i contributes to the next stream (kTokNone: nothing).
+__global__ __launch_bounds__(kSpanThreads) void k_enc_match(const uint32_t *__restrict__ tok, uint64_t n,
+                                                            uint32_t *__restrict__ cand,
+                                                            const uint32_t *__restrict__ in_par,
+                                                            uint32_t *__restrict__ span_keep) {
+    const uint64_t span = span_index(), base = span * kSpan;
     if (base >= n) return;
     const uint32_t lane = lane_id();
-    const unsigned long long lt = (1ull << lane) - 1ull;
+    const unsigned long long lt = lanes_below(lane);
     uint32_t carry = in_par[span];             // parity of the run of candidates right before this group
     uint32_t kept = 0;
     for (int it = 0; it < kSpanIters; ++it) {
         const uint64_t i = base + (uint64_t)it * kWave + lane;
-        const uint32_t c = i < n ? cand[i] : kNone;
-        const uint32_t t = i < n ? tok[i] : kDrop;
-        uint32_t nx = __shfl_down(t, 1, kWave);
-        if (lane == kWave - 1) nx = i + 1 < n ? tok[i + 1] : 0u;
-        const unsigned long long M = __ballot(c != kNone);
-        // r = consecutive candidates immediately below this lane (continuing into `carry` if all of them are)
-        const unsigned long long zeros_below = ~M & lt;
-        uint32_t r;
-        if (zeros_below == 0ull) r = lane + carry;
-        else r = lane - 1u - (63u - (uint32_t)__builtin_clzll(zeros_below));
-        const bool odd = r & 1u;
-        uint32_t v = kNone;
-        if (i < n && !odd && t != kDrop) v = c != kNone ? (c | (nx & kEnd)) : t;   // replaced, or kept as it is
+        const uint32_t c = i < n ? cand[i] : kTokNone;
+        uint32_t nx;                           // (only its end flag is used, and only where i + 1 < n)
+        const uint32_t t = load_pair(tok, i, n, lane, kDrop, &nx);
+        const unsigned long long M = __ballot(c != kTokNone);
+        const bool odd = run_below(M, lt, lane, carry) & 1u;
+        uint32_t v = kTokNone;
+        if (i < n && !odd && t != kDrop) v = c != kTokNone ? (c | (nx & kTokEnd)) : t;   // replaced, or kept as it is
         if (i < n) cand[i] = v;
-        kept += (uint32_t)__popcll(__ballot(v != kNone));
-        if (M != ~0ull) carry = (uint32_t)__builtin_clzll(~M) & 1u;
+        kept += wave_count(v != kTokNone);
+        carry = run_carry(M, carry);
     }
     if (lane == 0) span_keep[span] = kept;
 }
 
 // pass, step 3: compact
-__global__ __launch_bounds__(kEncThreads) void k_enc_scatter(const uint32_t *__restrict__ val, uint64_t n,
-                                                             const unsigned long long *__restrict__ span_off,
-                                                             uint32_t *__restrict__ out) {
-    const uint64_t span = (uint64_t)blockIdx.x * (kEncThreads / kWave) + threadIdx.x / kWave;
-    const uint64_t base = span * kSpan;
-    if (base >= n) return;
-    const uint32_t lane = lane_id();
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    unsigned long long o = span_off[span];
-    for (int it = 0; it < kSpanIters; ++it) {
-        const uint64_t i = base + (uint64_t)it * kWave + lane;
-        const uint32_t v = i < n ? val[i] : kNone;
-        const unsigned long long K = __ballot(v != kNone);
-        if (v != kNone) out[o + (uint32_t)__popcll(K & lt)] = v;
-        o += (uint32_t)__popcll(K);
-    }
+__global__ __launch_bounds__(kSpanThreads) void k_enc_scatter(const uint32_t *__restrict__ val, uint64_t n,
+                                                              const unsigned long long *__restrict__ span_off,
+                                                              uint32_t *__restrict__ out) {
+    span_scatter(val, n, span_off, out);
 }
 
 // ---- the finishing kernels: what leaves the passes becomes what the caller asked for ----------------------------
@@ -246,17 +167,15 @@ __global__ void k_enc_nul_starts(const uint8_t *__restrict__ text, uint64_t n, c
 }
 
 // per span: how many of its tokens are the last of their chunk
-__global__ __launch_bounds__(kEncThreads) void k_enc_end_count(const uint32_t *__restrict__ tok, uint64_t n,
-                                                               uint32_t *__restrict__ span_ends) {
-    const uint64_t span = (uint64_t)blockIdx.x * (kEncThreads / kWave) + threadIdx.x / kWave;
-    const uint64_t base = span * kSpan;
+__global__ __launch_bounds__(kSpanThreads) void k_enc_end_count(const uint32_t *__restrict__ tok, uint64_t n,
+                                                                uint32_t *__restrict__ span_ends) {
+    const uint64_t span = span_index(), base = span * kSpan;
     if (base >= n) return;
     const uint32_t lane = lane_id();
     uint32_t cnt = 0;
     for (int it = 0; it < kSpanIters; ++it) {
         const uint64_t i = base + (uint64_t)it * kWave + lane;
-        const bool end = i < n && (tok[i] & kEnd);
-        cnt += (uint32_t)__popcll(__ballot(end));
+        cnt += wave_count(i < n && (tok[i] & kTokEnd));
     }
     if (lane == 0) span_ends[span] = cnt;
 }
@@ -271,70 +190,39 @@ enum FinMode {
 // the final stream -> ids in the caller's format; with ENDS also, in order, the position after every token that ends
 // a chunk (span_off = exclusive sums of k_enc_end_count's counts; tok_base = tokens of the pieces before this one)
 template <int MODE, bool ENDS>
-__global__ __launch_bounds__(kEncThreads) void k_enc_finish(const uint32_t *__restrict__ tok, uint64_t n,
-                                                            void *__restrict__ out,
-                                                            const unsigned long long *__restrict__ span_off,
-                                                            unsigned long long tok_base,
-                                                            unsigned long long *__restrict__ ends,
-                                                            unsigned long long ends_cap) {
-    const uint64_t span = (uint64_t)blockIdx.x * (kEncThreads / kWave) + threadIdx.x / kWave;
-    const uint64_t base = span * kSpan;
+__global__ __launch_bounds__(kSpanThreads) void k_enc_finish(const uint32_t *__restrict__ tok, uint64_t n,
+                                                             void *__restrict__ out,
+                                                             const unsigned long long *__restrict__ span_off,
+                                                             unsigned long long tok_base,
+                                                             unsigned long long *__restrict__ ends,
+                                                             unsigned long long ends_cap) {
+    const uint64_t span = span_index(), base = span * kSpan;
     if (base >= n) return;
     const uint32_t lane = lane_id();
-    const unsigned long long lt = (1ull << lane) - 1ull;
+    const unsigned long long lt = lanes_below(lane);
     unsigned long long o = ENDS ? span_off[span] : 0ull;
     for (int it = 0; it < kSpanIters; ++it) {
         const uint64_t i = base + (uint64_t)it * kWave + lane;
         const uint32_t t = i < n ? tok[i] : 0u;
         if (i < n) {
             if (MODE == kFinFlags) static_cast<uint32_t *>(out)[i] = t;
-            if (MODE == kFinU32) static_cast<uint32_t *>(out)[i] = t & kIdMask;
+            if (MODE == kFinU32) static_cast<uint32_t *>(out)[i] = t & kTokIdMask;
             if (MODE == kFinU16) static_cast<uint16_t *>(out)[i] = (uint16_t)t;
         }
         if (ENDS) {
-            const bool end = i < n && (t & kEnd);
-            const unsigned long long E = __ballot(end);
-            const unsigned long long at = o + (uint32_t)__popcll(E & lt);
-            if (end && at < ends_cap) ends[at] = tok_base + i + 1;
-            o += (uint32_t)__popcll(E);
+            const bool end = i < n && (t & kTokEnd);
+            const WaveKeep e = wave_keep(end, lt);
+            if (end && o + e.rank < ends_cap) ends[o + e.rank] = tok_base + i + 1;
+            o += e.count;
         }
     }
 }
 
-std::string hip_err(const char *what, hipError_t e) { return std::string(what) + ": " + hipGetErrorString(e); }
-
-#define ECHK(expr)                                                            \
-    do {                                                                      \
-        hipError_t e__ = (expr);                                              \
-        if (e__ != hipSuccess) {                                              \
-            mbpe_host::set_last_error(hip_err(#expr, e__));                   \
-            (void)hipGetLastError();                                          \
-            return e__ == hipErrorOutOfMemory ? MBPE_ERR_OOM : MBPE_ERR_HIP;  \
-        }                                                                     \
-    } while (0)
+#define ECHK(expr) MBPE_HIP_CHECK(expr, true)
 
 int fail(int code, const std::string &msg) {
     mbpe_host::set_last_error(msg);
     return code;
-}
-
-// std::stoi on the remainder of a NUL-led chunk (Tokenizer.h:86-93): value when it parses
-bool stoi_value(const uint8_t *s, uint64_t n, long long *out) {
-    uint64_t i = 0;
-    while (i < n && (s[i] == ' ' || (s[i] >= 9 && s[i] <= 13))) i++;
-    bool neg = false;
-    if (i < n && (s[i] == '+' || s[i] == '-')) { neg = s[i] == '-'; i++; }
-    if (i >= n || s[i] < '0' || s[i] > '9') return false;
-    long long v = 0;
-    while (i < n && s[i] >= '0' && s[i] <= '9') {
-        v = v * 10 + (s[i] - '0');
-        if (v > 4294967296LL) return false;
-        i++;
-    }
-    if (neg) v = -v;
-    if (v > 2147483647LL || v < -2147483648LL) return false;
-    *out = v;
-    return true;
 }
 
 constexpr uint64_t kPieceCost = 14;        // device bytes per text byte of a piece, rounded up (mbpe.h, "piece_bytes")
@@ -377,18 +265,6 @@ struct mbpe_encoder {
 
 namespace {
 
-template <typename T>
-int enc_grow(mbpe_encoder *e, T **p, uint64_t *cap, uint64_t want_bytes) {
-    if (*p && *cap >= want_bytes) return MBPE_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    ECHK(hipMalloc(reinterpret_cast<void **>(p), want_bytes));
-    ++e->n_allocs;
-    *cap = want_bytes;
-    return MBPE_OK;
-}
-
 uint64_t enc_held(const mbpe_encoder *e) {
     return e->cap_text + e->cap_mask + e->cap_tok[0] + e->cap_tok[1] + e->cap_cand + e->cap_span_a + e->cap_span_b +
            e->cap_span_off;
@@ -420,8 +296,8 @@ int device_singles(mbpe_encoder *e, const uint8_t *d_text, const uint64_t *chunk
     const uint64_t base = chunk_off[p.c0], pn = chunk_off[p.c1] - base;
     if (pn == 0) return MBPE_OK;
     build_mask(e, chunk_off, p);
-    int rc = enc_grow(e, &e->d_mask, &e->cap_mask, e->mask.size());
-    if (rc == MBPE_OK && !e->d_nul) rc = enc_grow(e, &e->d_nul, &e->cap_nul, kNulListMin * 8);
+    int rc = grow(&e->d_mask, &e->cap_mask, e->mask.size(), true, &e->n_allocs);
+    if (rc == MBPE_OK && !e->d_nul) rc = grow(&e->d_nul, &e->cap_nul, kNulListMin * 8, true, &e->n_allocs);
     if (rc != MBPE_OK) return rc;
     ECHK(hipMemcpyAsync(e->d_mask, e->mask.data(), e->mask.size(), hipMemcpyHostToDevice, e->stream));
     unsigned long long found = 0;
@@ -434,7 +310,7 @@ int device_singles(mbpe_encoder *e, const uint8_t *d_text, const uint64_t *chunk
         ECHK(hipStreamSynchronize(e->stream));
         ECHK(hipGetLastError());
         if (found <= e->cap_nul / 8) break;
-        rc = enc_grow(e, &e->d_nul, &e->cap_nul, found * 8);
+        rc = grow(&e->d_nul, &e->cap_nul, found * 8, true, &e->n_allocs);
         if (rc != MBPE_OK) return rc;
     }
     if (found == 0) return MBPE_OK;
@@ -475,10 +351,10 @@ template <int MODE>
 void launch_finish(mbpe_encoder *e, dim3 grid, const uint32_t *tok, uint64_t n, void *out, bool with_ends,
                    unsigned long long tok_base, unsigned long long *ends, unsigned long long ends_cap) {
     if (with_ends)
-        hipLaunchKernelGGL((k_enc_finish<MODE, true>), grid, dim3(kEncThreads), 0, e->stream, tok, n, out, e->span_off,
+        hipLaunchKernelGGL((k_enc_finish<MODE, true>), grid, dim3(kSpanThreads), 0, e->stream, tok, n, out, e->span_off,
                            tok_base, ends, ends_cap);
     else if constexpr (MODE != kFinNone)            // (no tokens and no ends: nothing to launch)
-        hipLaunchKernelGGL((k_enc_finish<MODE, false>), grid, dim3(kEncThreads), 0, e->stream, tok, n, out, e->span_off,
+        hipLaunchKernelGGL((k_enc_finish<MODE, false>), grid, dim3(kSpanThreads), 0, e->stream, tok, n, out, e->span_off,
                            tok_base, ends, ends_cap);
 }
 
@@ -505,19 +381,19 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
             for (uint64_t c = p.c0; c < p.c1; ++c) a.chunk_tok_off_out[c + 1] = done;
         return MBPE_OK;
     }
-    const uint64_t n_spans0 = (pn + kSpan - 1) / kSpan;
+    const uint64_t n_spans0 = span_count(pn);
     int rc = MBPE_OK;
-    if (!a.text_on_device) rc = enc_grow(e, &e->d_text, &e->cap_text, pn);
+    if (!a.text_on_device) rc = grow(&e->d_text, &e->cap_text, pn, true, &e->n_allocs);
     if (rc == MBPE_OK && !a.mask_on_device) {
         build_mask(e, a.chunk_off, p);
-        rc = enc_grow(e, &e->d_mask, &e->cap_mask, e->mask.size());
+        rc = grow(&e->d_mask, &e->cap_mask, e->mask.size(), true, &e->n_allocs);
     }
-    if (rc == MBPE_OK) rc = enc_grow(e, &e->tok[0], &e->cap_tok[0], pn * 4);
-    if (rc == MBPE_OK) rc = enc_grow(e, &e->tok[1], &e->cap_tok[1], pn * 4);
-    if (rc == MBPE_OK) rc = enc_grow(e, &e->cand, &e->cap_cand, pn * 4);
-    if (rc == MBPE_OK) rc = enc_grow(e, &e->span_a, &e->cap_span_a, n_spans0 * 4);
-    if (rc == MBPE_OK) rc = enc_grow(e, &e->span_b, &e->cap_span_b, n_spans0 * 4);
-    if (rc == MBPE_OK) rc = enc_grow(e, &e->span_off, &e->cap_span_off, n_spans0 * 8);
+    if (rc == MBPE_OK) rc = grow(&e->tok[0], &e->cap_tok[0], pn * 4, true, &e->n_allocs);
+    if (rc == MBPE_OK) rc = grow(&e->tok[1], &e->cap_tok[1], pn * 4, true, &e->n_allocs);
+    if (rc == MBPE_OK) rc = grow(&e->cand, &e->cap_cand, pn * 4, true, &e->n_allocs);
+    if (rc == MBPE_OK) rc = grow(&e->span_a, &e->cap_span_a, n_spans0 * 4, true, &e->n_allocs);
+    if (rc == MBPE_OK) rc = grow(&e->span_b, &e->cap_span_b, n_spans0 * 4, true, &e->n_allocs);
+    if (rc == MBPE_OK) rc = grow(&e->span_off, &e->cap_span_off, n_spans0 * 8, true, &e->n_allocs);
     if (rc != MBPE_OK) return rc;
     // the piece's NUL-led chunks (e->singles is sorted by start), relative to the piece
     e->piece_singles.clear();
@@ -528,7 +404,8 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
             e->piece_singles.push_back({lo->start - base, lo->len, lo->id, 0});
     }
     if (!e->piece_singles.empty()) {
-        rc = enc_grow(e, &e->d_singles, &e->cap_singles, e->piece_singles.size() * sizeof(SingleChunk));
+        rc = grow(&e->d_singles, &e->cap_singles, e->piece_singles.size() * sizeof(SingleChunk), true,
+                  &e->n_allocs);
         if (rc != MBPE_OK) return rc;
     }
     const uint8_t *d_text = a.text + base;
@@ -552,8 +429,8 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
     int cur = 0;
     uint32_t passes = 0;
     for (;;) {
-        const uint64_t n_spans = (n + kSpan - 1) / kSpan;
-        const dim3 grid((uint32_t)((n_spans + kEncThreads / kWave - 1) / (kEncThreads / kWave))), block(kEncThreads);
+        const uint64_t n_spans = span_count(n);
+        const dim3 grid(span_grid(n)), block(kSpanThreads);
         hipLaunchKernelGGL(k_enc_cand, grid, block, 0, e->stream, e->tok[cur], n, e->lut, e->cand, e->span_a);
         hipLaunchKernelGGL(k_enc_scan_parity, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans, e->span_b);
         hipLaunchKernelGGL(k_enc_match, grid, block, 0, e->stream, e->tok[cur], n, e->cand, e->span_b, e->span_a);
@@ -583,18 +460,18 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
     uint64_t n_ends = 0;
     unsigned long long *d_ends = nullptr;
     if (n && (with_ends || with_tokens)) {
-        const uint64_t n_spans = (n + kSpan - 1) / kSpan;
-        const dim3 grid((uint32_t)((n_spans + kEncThreads / kWave - 1) / (kEncThreads / kWave)));
+        const uint64_t n_spans = span_count(n);
+        const dim3 grid(span_grid(n));
         if (with_ends) {
             for (uint64_t c = p.c0; c < p.c1; ++c) n_ends += a.chunk_off[c + 1] > a.chunk_off[c];
             if (n_ends * 8 <= e->cap_tok[1 - cur]) {
                 d_ends = reinterpret_cast<unsigned long long *>(e->tok[1 - cur]);
             } else {
-                rc = enc_grow(e, &e->d_ends, &e->cap_ends, n_ends * 8);
+                rc = grow(&e->d_ends, &e->cap_ends, n_ends * 8, true, &e->n_allocs);
                 if (rc != MBPE_OK) return rc;
                 d_ends = e->d_ends;
             }
-            hipLaunchKernelGGL(k_enc_end_count, grid, dim3(kEncThreads), 0, e->stream, e->tok[cur], n, e->span_a);
+            hipLaunchKernelGGL(k_enc_end_count, grid, dim3(kSpanThreads), 0, e->stream, e->tok[cur], n, e->span_a);
             hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans, e->span_off,
                                e->d_res);
         }
@@ -805,7 +682,7 @@ int mbpe_encoder_create(int device_id, const uint32_t *merges, uint32_t n_merges
     }
     for (uint32_t k = 0; k < n_merges; ++k) {       // merges_lookup[pair] = 256 + k: a repeated pair keeps the last id
         const unsigned long long key = ((unsigned long long)merges[2 * k] << 32) | merges[2 * k + 1];
-        uint32_t h = enc_hash(key, 64 - bits);
+        uint32_t h = pair_hash(key, 64 - bits);
         while (keys[h] != kEmptyKey && keys[h] != key) h = (h + 1) & (capacity - 1);
         keys[h] = key;
         vals[h] = 256 + k;
@@ -823,9 +700,9 @@ int mbpe_encoder_create(int device_id, const uint32_t *merges, uint32_t n_merges
         ECHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
         ECHK(hipEventCreate(&e->ev0));
         ECHK(hipEventCreate(&e->ev1));
-        int rc = enc_grow(e, &e->d_keys, &cap_keys, (uint64_t)capacity * 8);
-        if (rc == MBPE_OK) rc = enc_grow(e, &e->d_vals, &cap_vals, (uint64_t)capacity * 4);
-        if (rc == MBPE_OK) rc = enc_grow(e, &e->d_res, &cap_res, 16);
+        int rc = grow(&e->d_keys, &cap_keys, (uint64_t)capacity * 8, true, &e->n_allocs);
+        if (rc == MBPE_OK) rc = grow(&e->d_vals, &cap_vals, (uint64_t)capacity * 4, true, &e->n_allocs);
+        if (rc == MBPE_OK) rc = grow(&e->d_res, &cap_res, 16, true, &e->n_allocs);
         if (rc != MBPE_OK) return rc;
         ECHK(hipMemcpyAsync(e->d_keys, keys.data(), (size_t)capacity * 8, hipMemcpyHostToDevice, e->stream));
         ECHK(hipMemcpyAsync(e->d_vals, vals.data(), (size_t)capacity * 4, hipMemcpyHostToDevice, e->stream));

@@ -12,7 +12,7 @@
 #include "mbpe.h"
 #include "mbpe_dev.h"
 #include "wide.h"
-#include "../host/mbpe_host.h"
+#include "hip_host.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -31,18 +31,7 @@ using namespace mbpe;
 
 namespace {
 
-std::string hip_err(const char *what, hipError_t e) {
-    return std::string(what) + ": " + hipGetErrorString(e);
-}
-
-#define HIPCHK(expr)                                                   \
-    do {                                                               \
-        hipError_t e__ = (expr);                                       \
-        if (e__ != hipSuccess) {                                       \
-            mbpe_host::set_last_error(hip_err(#expr, e__));            \
-            return e__ == hipErrorOutOfMemory ? MBPE_ERR_OOM : MBPE_ERR_HIP; \
-        }                                                              \
-    } while (0)
+#define HIPCHK(expr) MBPE_HIP_CHECK(expr, false)
 
 uint64_t round_up(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
 
@@ -52,23 +41,8 @@ uint32_t next_pow2(uint64_t v) {
     return (uint32_t)p;
 }
 
-// std::stoi on the remainder of a NUL-led chunk (reference Tokenizer.h:86-93):
-// true when it parses, i.e. the chunk collapses to a single token.
-bool stoi_parses(const uint8_t *s, uint64_t n) {
-    uint64_t i = 0;
-    while (i < n && (s[i] == ' ' || (s[i] >= 9 && s[i] <= 13))) i++;
-    bool neg = false;
-    if (i < n && (s[i] == '+' || s[i] == '-')) { neg = s[i] == '-'; i++; }
-    if (i >= n || s[i] < '0' || s[i] > '9') return false;
-    long long v = 0;
-    while (i < n && s[i] >= '0' && s[i] <= '9') {
-        v = v * 10 + (s[i] - '0');
-        if (v > 4294967296LL) return false;
-        i++;
-    }
-    if (neg) v = -v;
-    return v <= 2147483647LL && v >= -2147483648LL;
-}
+// does a NUL-led chunk collapse to a single token?
+bool stoi_parses(const uint8_t *s, uint64_t n) { long long v; return stoi_value(s, n, &v); }
 
 template <typename T>
 void dfree(T *&p) {
@@ -1966,7 +1940,7 @@ int mbpe_get_stream(mbpe_ctx *c, uint32_t *tokens_out, uint8_t *chunk_end_out, u
         for (uint64_t i = 0; i < n; ++i) {
             // (a one-chunk corpus reports no chunk ends, like the slot stream)
             if (chunk_end_out) chunk_end_out[i] = c->chunked ? (uint8_t)(tokens_out[i] >> 31) : 0;
-            tokens_out[i] &= kWideIdMask;
+            tokens_out[i] &= kTokIdMask;
         }
         return MBPE_OK;
     }
@@ -2002,7 +1976,7 @@ int mbpe_stream_device(mbpe_ctx *c, const void **slots_out, uint64_t *n_slots_ou
         *slots_out = c->wtok[c->wcur];
         *n_slots_out = c->h_wctl.n;
         if (slot_bits_out) *slot_bits_out = 32;
-        if (end_bit_out) *end_bit_out = kWideEnd;
+        if (end_bit_out) *end_bit_out = kTokEnd;
         if (barrier_out) *barrier_out = MBPE_NO_BARRIER;
         return MBPE_OK;
     }

@@ -1,7 +1,7 @@
 // The 32-bit continuation of a training (reference Token = uint32_t, Tokenizer.h:37-38): what runs once the token ids
 // no longer fit the 16-bit slot stream of kernels.hip.  A training whose vocabulary lies beyond the 16-bit format runs
 // its first merges on the slot stream (batch sequences, fused passes) and is then CONVERTED: the stream becomes 32-bit
-// tokens with bit 31 = "last token of its chunk" (the layout of encode.hip), the pair table an open-addressing table
+// tokens with bit 31 = "last token of its chunk" (the layout of span.h), the pair table an open-addressing table
 // with 64-bit keys, and the loop of Tokenizer.h:557-589 continues one merge per pass:
 //
 //   k_wide_argmax_*  get_top_pair_count, PairCount.h:262-269: full scan of the table under CompareLexicalOrder
@@ -32,16 +32,14 @@
 #ifndef MBPE_WIDE_H
 #define MBPE_WIDE_H
 
+#include "span.h"
+
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace mbpe {
 
-constexpr uint32_t kWideEnd = 0x80000000u;      // last token of its chunk
-constexpr uint32_t kWideNone = 0xFFFFFFFFu;     // position contributes nothing to the next stream
-constexpr uint32_t kWideIdMask = 0x7FFFFFFFu;
 constexpr unsigned long long kWideEmpty = ~0ull;
-constexpr int kWideSpan = 1024;                 // tokens one wave walks (16 groups of 64 lanes)
 
 struct WideTable {
     unsigned long long *keys;      // (first << 32) | second, kWideEmpty when free

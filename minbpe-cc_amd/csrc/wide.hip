@@ -8,21 +8,10 @@
 namespace mbpe {
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kSpanIters = kWideSpan / kWave;
-constexpr int kThreads = 256;                   // 4 waves = 4 spans per workgroup
-constexpr int kScanThreads = 1024;
-
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (kWave - 1); }
-
-__host__ __device__ inline uint32_t wide_hash(unsigned long long key, uint32_t shift) {
-    return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> shift);
-}
-
 // create_or_modify_pair, PairCount.h:249-260: find the pair and add `delta`, or insert it with `delta`.  Entries are
 // never removed.  Concurrent inserts of one key meet at the same free slot and the CAS lets exactly one of them in.
 __device__ void wide_add(const WideTable &t, WideCtl *ctl, unsigned long long key, int32_t delta) {
-    uint32_t h = wide_hash(key, t.shift);
+    uint32_t h = pair_hash(key, t.shift);
     for (uint32_t probe = 0; probe <= t.mask; ++probe) {
         unsigned long long k = t.keys[h];
         if (k == kWideEmpty) {
@@ -137,11 +126,11 @@ __global__ __launch_bounds__(kArgBlocks) void k_wide_argmax_final(const unsigned
 }
 
 // ---- `first` tie-break (see wide.h) ----------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t first_bit(unsigned long long key) { return wide_hash(key, 48); }   // 16 bits
+__device__ __forceinline__ uint32_t first_bit(unsigned long long key) { return pair_hash(key, 48); }   // 16 bits
 
 // count of `key`, or -1 when the pair was never inserted
 __device__ __forceinline__ int32_t wide_lookup(const WideTable &t, unsigned long long key) {
-    uint32_t h = wide_hash(key, t.shift);
+    uint32_t h = pair_hash(key, t.shift);
     for (uint32_t probe = 0; probe <= t.mask; ++probe) {
         const unsigned long long k = t.keys[h];
         if (k == key) return t.cnts[h];
@@ -176,23 +165,22 @@ __global__ __launch_bounds__(256) void k_wide_first_gather(WideTable t, const Wi
 }
 
 constexpr int kPosBlocks = 1024;
-__global__ __launch_bounds__(kThreads) void k_wide_first_pos(const uint32_t *__restrict__ tok, WideTable t,
-                                                             const WideCtl *ctl, WideFirst *fs) {
+__global__ __launch_bounds__(kSpanThreads) void k_wide_first_pos(const uint32_t *__restrict__ tok, WideTable t,
+                                                                 const WideCtl *ctl, WideFirst *fs) {
     __shared__ uint32_t bm[kWideFirstBitmapWords];
     if (ctl->k >= ctl->k_limit || !ctl->live) return;
     if (fs->n_tie <= 1) return;                               // a unique maximum: the lexical winner is it
     const uint64_t n = ctl->n;
-    const uint64_t n_spans = (n + kWideSpan - 1) / kWideSpan;
-    const uint64_t waves_per_block = kThreads / kWave;
-    const uint64_t n_waves = (uint64_t)gridDim.x * waves_per_block;
-    const uint64_t first_span = (uint64_t)blockIdx.x * waves_per_block;
+    const uint64_t n_spans = span_count(n);
+    const uint64_t n_waves = (uint64_t)gridDim.x * kSpanWaves;
+    const uint64_t first_span = (uint64_t)blockIdx.x * kSpanWaves;
     if (first_span >= n_spans) return;
     const int32_t M = ctl->count;
-    for (uint32_t i = threadIdx.x; i < kWideFirstBitmapWords; i += kThreads) bm[i] = fs->bitmap[i];
+    for (uint32_t i = threadIdx.x; i < kWideFirstBitmapWords; i += kSpanThreads) bm[i] = fs->bitmap[i];
     __syncthreads();
     const uint32_t lane = lane_id();
     for (uint64_t span = first_span + threadIdx.x / kWave; span < n_spans; span += n_waves) {
-        const uint64_t base = span * kWideSpan;
+        const uint64_t base = span * kSpan;
         // spans are visited in ascending order: nothing at or after this one can win any more
         unsigned long long cur = __hip_atomic_load(&fs->pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         cur = __shfl(cur, 0, kWave);                          // (one decision for the whole wave)
@@ -200,13 +188,11 @@ __global__ __launch_bounds__(kThreads) void k_wide_first_pos(const uint32_t *__r
         bool hit_span = false;
         for (int it = 0; it < kSpanIters; ++it) {
             const uint64_t i = base + (uint64_t)it * kWave + lane;
-            const uint32_t tv = i < n ? tok[i] : kWideEnd;
-            // (no holes: the right neighbour of a span's last token is the next span's first)
-            uint32_t nx = __shfl_down(tv, 1, kWave);
-            if (lane == kWave - 1) nx = i + 1 < n ? tok[i + 1] : kWideEnd;
+            uint32_t nx;
+            const uint32_t tv = load_pair(tok, i, n, lane, kTokEnd, &nx);
             bool hit = false;
-            if (i + 1 < n && !(tv & kWideEnd)) {                  // a pair starts here (Tokenizer.h:135-144)
-                const unsigned long long key = ((unsigned long long)tv << 32) | (nx & kWideIdMask);
+            if (i + 1 < n && !(tv & kTokEnd)) {                  // a pair starts here (Tokenizer.h:135-144)
+                const unsigned long long key = ((unsigned long long)tv << 32) | (nx & kTokIdMask);
                 const uint32_t hb = first_bit(key);
                 if ((bm[hb >> 5] >> (hb & 31u)) & 1u) hit = wide_lookup(t, key) == M;
             }
@@ -229,7 +215,7 @@ __global__ __launch_bounds__(256) void k_wide_first_pick(const uint32_t *__restr
         nt = fs->n_tie;
         const unsigned long long pos = fs->pos;
         if (ctl->k < ctl->k_limit && ctl->live && nt > 1 && pos != ~0ull) {
-            const uint32_t a = tok[pos], b = tok[pos + 1] & kWideIdMask;      // (a: no end flag, a pair starts there)
+            const uint32_t a = tok[pos], b = tok[pos + 1] & kTokIdMask;      // (a: no end flag, a pair starts there)
             ctl->a = a;
             ctl->b = b;
             WideBest wb = {ctl->count, a, b, 0u};
@@ -242,35 +228,11 @@ __global__ __launch_bounds__(256) void k_wide_first_pick(const uint32_t *__restr
     if (nt) for (uint32_t i = threadIdx.x; i < kWideFirstBitmapWords; i += blockDim.x) fs->bitmap[i] = 0;
 }
 
-// ---- scans over the spans (one workgroup, two sweeps; as in encode.hip) ---------------------------------------
+// ---- the scans and the compaction of span.h, under the loop's control block ----------------------------------------
 __global__ __launch_bounds__(kScanThreads) void k_wide_scan_parity(const uint32_t *__restrict__ span_sum,
                                                                    const WideCtl *ctl, uint32_t *__restrict__ in_par) {
     __shared__ uint32_t sh[kScanThreads];
-    const uint64_t n_spans = (ctl->n + kWideSpan - 1) / kWideSpan;
-    const uint64_t per = (n_spans + kScanThreads - 1) / kScanThreads;
-    const uint64_t lo = per * threadIdx.x, hi = lo + per < n_spans ? lo + per : n_spans;
-    uint32_t all = 1, par = 0;
-    for (uint64_t s = lo; s < hi; ++s) {
-        const uint32_t v = span_sum[s];
-        if (v & 1u) par ^= v >> 1; else { all = 0; par = v >> 1; }
-    }
-    sh[threadIdx.x] = all | (par << 1);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t p = 0;
-        for (int t = 0; t < kScanThreads; ++t) {
-            const uint32_t v = sh[t];
-            sh[t] = p;
-            if (v & 1u) p ^= v >> 1; else p = v >> 1;
-        }
-    }
-    __syncthreads();
-    par = sh[threadIdx.x];
-    for (uint64_t s = lo; s < hi; ++s) {
-        in_par[s] = par;
-        const uint32_t v = span_sum[s];
-        if (v & 1u) par ^= v >> 1; else par = v >> 1;
-    }
+    span_scan_parity(span_sum, span_count(ctl->n), in_par, sh);
 }
 
 // exclusive sums of the spans' kept-token counts over the spans of n_in tokens; the total becomes ctl->n (and, when
@@ -279,62 +241,38 @@ __global__ __launch_bounds__(kScanThreads) void k_wide_scan_sum(const uint32_t *
                                                                 unsigned long long *__restrict__ off, WideCtl *ctl,
                                                                 int advance) {
     __shared__ unsigned long long sh[kScanThreads];
+    // Order: every thread reads ctl->k, live and n here, before the first barrier of span_scan_sum; thread 0 writes
+    // n, n_prev, ran and k only after it.  The early return is uniform over the workgroup (the barriers need that).
     if (advance && (ctl->k >= ctl->k_limit || !ctl->live)) return;
     const uint64_t n_in = advance ? ctl->n : n_in_fixed;
-    const uint64_t n_spans = (n_in + kWideSpan - 1) / kWideSpan;
-    const uint64_t per = (n_spans + kScanThreads - 1) / kScanThreads;
-    const uint64_t lo = per * threadIdx.x, hi = lo + per < n_spans ? lo + per : n_spans;
-    unsigned long long s = 0;
-    for (uint64_t i = lo; i < hi; ++i) s += cnt[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
+    const unsigned long long total = span_scan_sum(cnt, span_count(n_in), off, sh);
     if (threadIdx.x == 0) {
-        unsigned long long acc = 0;
-        for (int t = 0; t < kScanThreads; ++t) { const unsigned long long v = sh[t]; sh[t] = acc; acc += v; }
-        sh[0] = 0;
         ctl->n_prev = n_in;                    // (the scatter walks the stream that was read)
-        ctl->n = acc;
+        ctl->n = total;
         ctl->ran = 1;
         if (advance) ctl->k += 1;
     }
-    __syncthreads();
-    s = threadIdx.x == 0 ? 0 : sh[threadIdx.x];
-    for (uint64_t i = lo; i < hi; ++i) { off[i] = s; s += cnt[i]; }
 }
 
-__global__ __launch_bounds__(kThreads) void k_wide_scatter(const uint32_t *__restrict__ val,
-                                                           const unsigned long long *__restrict__ span_off,
-                                                           uint32_t *__restrict__ out, const WideCtl *ctl) {
+__global__ __launch_bounds__(kSpanThreads) void k_wide_scatter(const uint32_t *__restrict__ val,
+                                                               const unsigned long long *__restrict__ span_off,
+                                                               uint32_t *__restrict__ out, const WideCtl *ctl) {
     // (a merge that did not run -- limit reached, empty table -- must not scatter either)
     if (!ctl->ran) return;
-    const uint64_t n_upper = ctl->n_prev;
-    const uint64_t span = (uint64_t)blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave;
-    const uint64_t base = span * kWideSpan;
-    if (base >= n_upper) return;
-    const uint32_t lane = lane_id();
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    unsigned long long o = span_off[span];
-    for (int it = 0; it < kSpanIters; ++it) {
-        const uint64_t i = base + (uint64_t)it * kWave + lane;
-        const uint32_t v = i < n_upper ? val[i] : kWideNone;
-        const unsigned long long K = __ballot(v != kWideNone);
-        if (v != kWideNone) out[o + (uint32_t)__popcll(K & lt)] = v;
-        o += (uint32_t)__popcll(K);
-    }
+    span_scatter(val, ctl->n_prev, span_off, out);
 }
 
 // ---- conversion of the 16-bit slot stream ---------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void k_wide_from_slots(const uint16_t *__restrict__ slots, uint64_t n_live,
-                                                              uint32_t barrier, uint32_t endbit, uint32_t *__restrict__ val,
-                                                              uint32_t *__restrict__ span_keep) {
-    const uint64_t span = (uint64_t)blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave;
-    const uint64_t base = span * kWideSpan;
+__global__ __launch_bounds__(kSpanThreads) void k_wide_from_slots(const uint16_t *__restrict__ slots, uint64_t n_live,
+                                                                  uint32_t barrier, uint32_t endbit, uint32_t *__restrict__ val,
+                                                                  uint32_t *__restrict__ span_keep) {
+    const uint64_t span = span_index(), base = span * kSpan;
     if (base >= n_live) return;
     const uint32_t lane = lane_id();
     uint32_t kept = 0;
     for (int it = 0; it < kSpanIters; ++it) {
         const uint64_t i = base + (uint64_t)it * kWave + lane;
-        uint32_t v = kWideNone;
+        uint32_t v = kTokNone;
         if (i < n_live) {
             const uint32_t s = slots[i];
             if (s != barrier) {
@@ -342,79 +280,63 @@ __global__ __launch_bounds__(kThreads) void k_wide_from_slots(const uint16_t *__
                 const uint32_t nx = last ? barrier : slots[i + 1];
                 // flag bit: the slot says so; barrier layout: a barrier follows; one chunk: only the very last token
                 const bool end = endbit ? (s & endbit) != 0u : barrier == 0xFFFFFFFFu ? last : nx == barrier;
-                v = (s & ~endbit) | (end ? kWideEnd : 0u);
+                v = (s & ~endbit) | (end ? kTokEnd : 0u);
             }
             val[i] = v;
         }
-        kept += (uint32_t)__popcll(__ballot(v != kWideNone));
+        kept += wave_count(v != kTokNone);
     }
     if (lane == 0) span_keep[span] = kept;
 }
 
 // ---- one merge ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool is_cand(uint32_t t, uint32_t nx, uint32_t a, uint32_t b) {
-    return !(t & kWideEnd) && t == a && (nx & kWideIdMask) == b;      // (t carries no end flag here, so t == a compares ids)
+    return !(t & kTokEnd) && t == a && (nx & kTokIdMask) == b;      // (t carries no end flag here, so t == a compares ids)
 }
 
-__global__ __launch_bounds__(kThreads) void k_wide_cand(const uint32_t *__restrict__ tok, uint64_t n_upper,
-                                                        const WideCtl *ctl, uint32_t *__restrict__ span_sum) {
+__global__ __launch_bounds__(kSpanThreads) void k_wide_cand(const uint32_t *__restrict__ tok, const WideCtl *ctl,
+                                                            uint32_t *__restrict__ span_sum) {
     if (ctl->k >= ctl->k_limit || !ctl->live) return;
     const uint64_t n = ctl->n;
-    const uint64_t span = (uint64_t)blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave;
-    const uint64_t base = span * kWideSpan;
+    const uint64_t span = span_index(), base = span * kSpan;
     if (base >= n) return;
     const uint32_t a = ctl->a, b = ctl->b;
     const uint32_t lane = lane_id();
-    bool all = true;
-    uint32_t par = 0;
+    SpanSum sum = span_empty();
     for (int it = 0; it < kSpanIters; ++it) {
         const uint64_t i = base + (uint64_t)it * kWave + lane;
-        const uint32_t t = i < n ? tok[i] : kWideEnd;
-        uint32_t nx = __shfl_down(t, 1, kWave);
-        if (lane == kWave - 1) nx = i + 1 < n ? tok[i + 1] : kWideEnd;
-        const bool c = i < n && i + 1 < n && is_cand(t, nx, a, b);
-        const unsigned long long M = __ballot(c);
-        if (M != ~0ull) {
-            all = false;
-            par = (uint32_t)__builtin_clzll(~M) & 1u;
-        }
+        uint32_t nx;
+        const uint32_t t = load_pair(tok, i, n, lane, kTokEnd, &nx);
+        sum = span_add_group(sum, __ballot(i + 1 < n && is_cand(t, nx, a, b)));
     }
-    (void)n_upper;
-    if (lane == 0) span_sum[span] = (all ? 1u : 0u) | (par << 1);
+    if (lane == 0) span_sum[span] = span_pack(sum);
 }
 
-__global__ __launch_bounds__(kThreads) void k_wide_match(const uint32_t *__restrict__ tok, const uint32_t *__restrict__ in_par,
-                                                         uint32_t *__restrict__ val, uint32_t *__restrict__ span_keep,
-                                                         WideTable tab, WideCtl *ctl, uint32_t new_id_base) {
+__global__ __launch_bounds__(kSpanThreads) void k_wide_match(const uint32_t *__restrict__ tok, const uint32_t *__restrict__ in_par,
+                                                             uint32_t *__restrict__ val, uint32_t *__restrict__ span_keep,
+                                                             WideTable tab, WideCtl *ctl, uint32_t new_id_base) {
     if (ctl->k >= ctl->k_limit || !ctl->live) return;
     const uint64_t n = ctl->n;
-    const uint64_t span = (uint64_t)blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave;
-    const uint64_t base = span * kWideSpan;
+    const uint64_t span = span_index(), base = span * kSpan;
     if (base >= n) return;
     const uint32_t a = ctl->a, b = ctl->b, X = new_id_base + ctl->k;
     const uint32_t lane = lane_id();
-    const unsigned long long lt = (1ull << lane) - 1ull;
+    const unsigned long long lt = lanes_below(lane);
     uint32_t carry = in_par[span];
     uint32_t kept = 0, n_match = 0;
     for (int it = 0; it < kSpanIters; ++it) {
         const uint64_t i = base + (uint64_t)it * kWave + lane;
-        const uint32_t t = i < n ? tok[i] : kWideEnd;
-        uint32_t nx = __shfl_down(t, 1, kWave);
-        if (lane == kWave - 1) nx = i + 1 < n ? tok[i + 1] : kWideEnd;
-        const bool c = i < n && i + 1 < n && is_cand(t, nx, a, b);
+        uint32_t nx;
+        const uint32_t t = load_pair(tok, i, n, lane, kTokEnd, &nx);
+        const bool c = i + 1 < n && is_cand(t, nx, a, b);
         const unsigned long long M = __ballot(c);
-        // r = consecutive candidates immediately below this lane (continuing into `carry` when all of them are)
-        const unsigned long long zeros_below = ~M & lt;
-        uint32_t r;
-        if (zeros_below == 0ull) r = lane + carry;
-        else r = lane - 1u - (63u - (uint32_t)__builtin_clzll(zeros_below));
-        const bool odd = r & 1u;
-        uint32_t v = kWideNone;
+        const bool odd = run_below(M, lt, lane, carry) & 1u;
+        uint32_t v = kTokNone;
         const bool match = c && !odd;
-        if (i < n && !odd) v = match ? (X | (nx & kWideEnd)) : t;
+        if (i < n && !odd) v = match ? (X | (nx & kTokEnd)) : t;
         if (i < n) val[i] = v;
-        kept += (uint32_t)__popcll(__ballot(v != kWideNone));
-        n_match += (uint32_t)__popcll(__ballot(match));
+        kept += wave_count(v != kTokNone);
+        n_match += wave_count(match);
         if (match) {
             // Tokenizer.h:248-260: the left neighbour as it stands AFTER the walk has passed it.  It was swallowed by a
             // match (and is X now) iff a match ends right before i: for a == b that is "(i-1, i) is a candidate too"
@@ -422,23 +344,23 @@ __global__ __launch_bounds__(kThreads) void k_wide_match(const uint32_t *__restr
             // candidates never touch, so every one of them is a match).
             if (i > 0) {
                 const uint32_t p = tok[i - 1];
-                if (!(p & kWideEnd)) {
+                if (!(p & kTokEnd)) {
                     bool swallowed;
                     if (a == b) swallowed = p == a;                   // (no end flag on p: (p, t) is a candidate)
-                    else swallowed = i > 1 && (p & kWideIdMask) == b && tok[i - 2] == a;   // (tok[i-2] == a: no end flag, id a)
+                    else swallowed = i > 1 && (p & kTokIdMask) == b && tok[i - 2] == a;   // (tok[i-2] == a: no end flag, id a)
                     const uint32_t x = swallowed ? X : p;
                     wide_add(tab, ctl, ((unsigned long long)x << 32) | a, -1);
                     wide_add(tab, ctl, ((unsigned long long)x << 32) | X, 1);
                 }
             }
             // :263-279: the right neighbour as it still is
-            if (!(nx & kWideEnd) && i + 2 < n) {
-                const uint32_t y = tok[i + 2] & kWideIdMask;
+            if (!(nx & kTokEnd) && i + 2 < n) {
+                const uint32_t y = tok[i + 2] & kTokIdMask;
                 wide_add(tab, ctl, ((unsigned long long)b << 32) | y, -1);
                 wide_add(tab, ctl, ((unsigned long long)X << 32) | y, 1);
             }
         }
-        if (M != ~0ull) carry = (uint32_t)__builtin_clzll(~M) & 1u;
+        carry = run_carry(M, carry);
     }
     if (lane == 0) {
         span_keep[span] = kept;
@@ -452,14 +374,14 @@ __global__ __launch_bounds__(kThreads) void k_wide_match(const uint32_t *__restr
 }  // namespace
 
 size_t wide_scratch_words(uint64_t n_tokens) {
-    const uint64_t n_spans = (n_tokens + kWideSpan - 1) / kWideSpan + 2;
+    const uint64_t n_spans = span_count(n_tokens) + 2;
     return (size_t)(n_spans * 5 + 8);          // span_sum, in_par, span_keep (u32 each), span_off (u64)
 }
 
 namespace {
 struct Scratch { uint32_t *span_sum, *in_par, *span_keep; unsigned long long *span_off; };
 Scratch carve(uint32_t *scratch, uint64_t n_tokens) {
-    const uint64_t n_spans = (n_tokens + kWideSpan - 1) / kWideSpan + 2;
+    const uint64_t n_spans = span_count(n_tokens) + 2;
     Scratch s;
     s.span_off = reinterpret_cast<unsigned long long *>(scratch);          // (8-byte aligned: first)
     s.span_sum = scratch + 2 * n_spans;
@@ -467,19 +389,15 @@ Scratch carve(uint32_t *scratch, uint64_t n_tokens) {
     s.span_keep = s.in_par + n_spans;
     return s;
 }
-uint32_t span_grid(uint64_t n) {
-    const uint64_t n_spans = (n + kWideSpan - 1) / kWideSpan;
-    return (uint32_t)((n_spans + kThreads / kWave - 1) / (kThreads / kWave));
-}
 }  // namespace
 
 void launch_wide_from_slots(hipStream_t s, const uint16_t *slots, uint64_t n_live, uint32_t barrier, uint32_t endbit,
                             uint32_t *val, uint32_t *span_scratch, uint32_t *tok_out, WideCtl *ctl) {
     if (!n_live) return;
     const Scratch sc = carve(span_scratch, n_live);
-    hipLaunchKernelGGL(k_wide_from_slots, dim3(span_grid(n_live)), dim3(kThreads), 0, s, slots, n_live, barrier, endbit, val, sc.span_keep);
+    hipLaunchKernelGGL(k_wide_from_slots, dim3(span_grid(n_live)), dim3(kSpanThreads), 0, s, slots, n_live, barrier, endbit, val, sc.span_keep);
     hipLaunchKernelGGL(k_wide_scan_sum, dim3(1), dim3(kScanThreads), 0, s, sc.span_keep, n_live, sc.span_off, ctl, 0);
-    hipLaunchKernelGGL(k_wide_scatter, dim3(span_grid(n_live)), dim3(kThreads), 0, s, val, sc.span_off, tok_out, ctl);
+    hipLaunchKernelGGL(k_wide_scatter, dim3(span_grid(n_live)), dim3(kSpanThreads), 0, s, val, sc.span_off, tok_out, ctl);
 }
 
 void launch_wide_table_clear(hipStream_t s, WideTable t) {
@@ -507,7 +425,7 @@ void launch_wide_first(hipStream_t s, const uint32_t *src, uint64_t n_upper, Wid
     hipLaunchKernelGGL(k_wide_first_gather, dim3(kArgBlocks), dim3(256), 0, s, t, ctl, scratch, fs);
     if (n_upper) {
         const uint32_t blocks = std::min<uint32_t>(span_grid(n_upper), kPosBlocks);
-        hipLaunchKernelGGL(k_wide_first_pos, dim3(blocks), dim3(kThreads), 0, s, src, t, ctl, fs);
+        hipLaunchKernelGGL(k_wide_first_pos, dim3(blocks), dim3(kSpanThreads), 0, s, src, t, ctl, fs);
     }
     hipLaunchKernelGGL(k_wide_first_pick, dim3(1), dim3(256), 0, s, src, ctl, best, fs);
 }
@@ -516,8 +434,8 @@ void launch_wide_merge(hipStream_t s, const uint32_t *src, uint32_t *dst, uint64
                        uint32_t *span_scratch, WideTable t, WideCtl *ctl, uint32_t new_id_base) {
     if (!n_upper) return;
     const Scratch sc = carve(span_scratch, n_upper);
-    const dim3 grid(span_grid(n_upper)), block(kThreads);
-    hipLaunchKernelGGL(k_wide_cand, grid, block, 0, s, src, n_upper, ctl, sc.span_sum);
+    const dim3 grid(span_grid(n_upper)), block(kSpanThreads);
+    hipLaunchKernelGGL(k_wide_cand, grid, block, 0, s, src, ctl, sc.span_sum);
     hipLaunchKernelGGL(k_wide_scan_parity, dim3(1), dim3(kScanThreads), 0, s, sc.span_sum, ctl, sc.in_par);
     hipLaunchKernelGGL(k_wide_match, grid, block, 0, s, src, sc.in_par, val, sc.span_keep, t, ctl, new_id_base);
     hipLaunchKernelGGL(k_wide_scan_sum, dim3(1), dim3(kScanThreads), 0, s, sc.span_keep, (uint64_t)0, sc.span_off, ctl, 1);

@@ -16,7 +16,7 @@ import numpy as np
 
 import oracle as O
 
-SPAN = 1024            # tokens one wave walks: kSpan (encode.hip), kWideSpan (wide.h)
+SPAN = 1024            # tokens one wave walks: kSpan (csrc/span.h)
 SLICES = 1024          # threads of a scan = slices the spans are dealt into: kScanThreads
 GROUP = 64             # lanes of a wave: the unit of the ballots inside a span
 
@@ -326,7 +326,7 @@ MAX_SIDE = (1 << 31) - 3                  # "Token ids must stay below 2^31 - 2"
 
 
 def enc_hash(key, shift):
-    # encode.hip, enc_hash:  (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> shift)
+    # csrc/span.h, pair_hash:  (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> shift)
     return ((key * 0x9E3779B97F4A7C15) & M64) >> shift
 
 

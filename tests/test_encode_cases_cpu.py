@@ -119,7 +119,7 @@ def test_oracle_equals_brute_force_on_lookup_cases():
 
 
 def test_lookup_case_has_a_chain_that_wraps_the_table_end():
-    # E.enc_hash mirrors enc_hash() of csrc/encode.hip; E.table_bits and E.build_table mirror the capacity rule
+    # E.enc_hash mirrors pair_hash() of csrc/span.h; E.table_bits and E.build_table mirror the capacity rule
     # (`while ((1ull << bits) < 2ull * n_merges + 2) ++bits;`) and the insertion loop of encode_chunks() there
     case = E.lookup_cases(SCALE)[-1]
     slots, bits = E.build_table(case.merges.tolist())

@@ -152,7 +152,7 @@ def test_lookup_tables(dev):
     assert [len(c.merges) for c in cases] == [1, 7, 8, (1 << 15) - 1, 1 << 15, 100000, 50]
     for c in cases:
         _check(c, dev)
-    # the precondition of the last case, on the Python mirror of enc_hash() and of the capacity rule and insertion loop
+    # the precondition of the last case, on the Python mirror of pair_hash() and of the capacity rule and insertion loop
     # of encode_chunks() in csrc/encode.hip: at least four keys with a home in the last two slots lie behind the wrap
     slots, bits = E.build_table(cases[-1].merges.tolist())
     assert len(E.wrapped_keys(slots, bits)) >= 4 and E.tail_chain(slots, bits)[1] >= 6

@@ -1,6 +1,6 @@
 """The 32-bit merge loop (csrc/wide.hip) on more than 1,024 spans.
 
-Its passes cut the token stream into spans of kWideSpan = 1,024 tokens and link them with two single-workgroup scans
+Its passes cut the token stream into spans of kSpan = 1,024 tokens (csrc/span.h) and link them with two single-workgroup scans
 of 1,024 threads (k_wide_scan_parity, k_wide_scan_sum), thread t owning per = ceil(n_spans / 1,024) consecutive spans.
 tests/test_gpu_wide.py stays below 21 spans (per = 1) and the 5 GiB case of tests/test_gpu_wide_first.py has no span
 whose every position is a candidate.  Here: runs and `ab` / `aab` periods of megabytes (full spans, per = 6),

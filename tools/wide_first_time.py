@@ -18,7 +18,7 @@ import mbpe  # noqa: E402
 import oracle as O  # noqa: E402
 from test_gpu_wide import _word_corpus  # noqa: E402
 
-SPAN = 1024                 # kWideSpan
+SPAN = 1024                 # kSpan (csrc/span.h)
 POS_WAVES = 1024 * 4        # k_wide_first_pos: at most 1,024 workgroups of 4 waves
 
 
