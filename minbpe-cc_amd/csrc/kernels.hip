@@ -4293,6 +4293,14 @@ static inline int slot_mode(uint32_t endbit) { return endbit == kEndBit ? 1 : en
         else if ((endbit) == kBarrier) { constexpr int M = 2; __VA_ARGS__; }               \
         else { constexpr int M = 0; __VA_ARGS__; }                                         \
     } while (0)
+// the four (t,t) member x frequent pair instantiations of a batch pass, as TT / HOT: those that `w` takes (mbpe_dev.h: Inst)
+#define MBPE_BY_INST(w, ...)                                                               \
+    do {                                                                                   \
+        if (inst_takes(w, false, false)) { constexpr bool TT = false, HOT = false; __VA_ARGS__; } \
+        if (inst_takes(w, true, false)) { constexpr bool TT = true, HOT = false; __VA_ARGS__; }   \
+        if (inst_takes(w, false, true)) { constexpr bool TT = false, HOT = true; __VA_ARGS__; }   \
+        if (inst_takes(w, true, true)) { constexpr bool TT = true, HOT = true; __VA_ARGS__; }     \
+    } while (0)
 
 void launch_fill_u32(hipStream_t s, uint32_t *p, uint64_t n, uint32_t v) {
     if (!n) return;
@@ -4339,9 +4347,10 @@ void launch_widen_barrier(hipStream_t s, const uint8_t *text, uint64_t n, const 
                        n_slots);
 }
 
-void launch_summarize(hipStream_t s, const uint16_t *tok, TileSum *sums, uint32_t n_tiles, int n_cus) {
-    if (!n_tiles) return;
-    hipLaunchKernelGGL(k_summarize, dim3(tile_grid(n_tiles, n_cus)), dim3(kMergeThreads), 0, s, tok, sums, n_tiles);
+void launch_summarize(const StreamView &v) {
+    if (!v.n_tiles) return;
+    hipLaunchKernelGGL(k_summarize, dim3(tile_grid(v.n_tiles, v.n_cus)), dim3(kMergeThreads), 0, v.stream, v.tok, v.sums,
+                       v.n_tiles);
 }
 
 void launch_table_init(hipStream_t s, const uint32_t *bp, PairTable t, DevCtl *ctl) {
@@ -4368,132 +4377,123 @@ void launch_first_init(hipStream_t s, void *fs) {
     (void)hipMemsetAsync(fs, 0xFF, 8, s);          // pos_key = ~0
 }
 
-void launch_first_tiebreak(hipStream_t s, PairTable t, const DevCtl *ctl, unsigned long long *best, void *fs_,
-                           const uint16_t *tok, const uint16_t *tok_other, const TileSum *sums, uint32_t n_tiles,
-                           uint32_t endbit, int n_cus, int seq, int phase, const RankEdge *right_edge, uint32_t *xf, int rank,
-                           int n_ranks) {
+void launch_first_tiebreak(const StreamView &v, PairTable t, unsigned long long *best, void *fs_, uint32_t *xf, int seq,
+                           int phase) {
     FirstState *fs = static_cast<FirstState *>(fs_);
+    const hipStream_t s = v.stream;
     if (phase != 2) {
         const uint32_t n_blocks = (t.ecap + kBlockSize - 1) >> kBlockShift;
-        hipLaunchKernelGGL(k_first_gather, dim3(blocks_for(n_blocks, 4, 2048)), dim3(256), 0, s, t, ctl, best, fs, seq);
-        if (n_tiles) {
-            const dim3 grid(tile_grid(n_tiles, n_cus, 8)), block(kMergeThreads);
-            MBPE_BY_MODE(endbit, hipLaunchKernelGGL(k_first_pos<M>, grid, block, 0, s, tok, tok_other, sums, n_tiles, t, best, fs,
-                                                    ctl, seq, right_edge));
+        hipLaunchKernelGGL(k_first_gather, dim3(blocks_for(n_blocks, 4, 2048)), dim3(256), 0, s, t, v.ctl, best, fs, seq);
+        if (v.n_tiles) {
+            const dim3 grid(tile_grid(v.n_tiles, v.n_cus, 8)), block(kMergeThreads);
+            // (the other buffer only inside a batch sequence, where ctl->cur picks)
+            MBPE_BY_MODE(v.endbit, hipLaunchKernelGGL(k_first_pos<M>, grid, block, 0, s, v.tok, seq ? v.tok_other : nullptr, v.sums,
+                                                      v.n_tiles, t, best, fs, v.ctl, seq, v.right_edge));
         }
     }
-    if (phase == 0) hipLaunchKernelGGL(k_first_pick, dim3(1), dim3(256), 0, s, best, fs, ctl, seq);
-    else if (phase == 1) hipLaunchKernelGGL(k_first_publish, dim3(1), dim3(64), 0, s, fs, xf, rank);
-    else hipLaunchKernelGGL(k_first_pick_global, dim3(1), dim3(256), 0, s, best, fs, xf, n_ranks, exchange_header_words(n_ranks));
+    if (phase == 0) hipLaunchKernelGGL(k_first_pick, dim3(1), dim3(256), 0, s, best, fs, v.ctl, seq);
+    else if (phase == 1) hipLaunchKernelGGL(k_first_publish, dim3(1), dim3(64), 0, s, fs, xf, v.rank);
+    else hipLaunchKernelGGL(k_first_pick_global, dim3(1), dim3(256), 0, s, best, fs, xf, v.n_ranks, exchange_header_words(v.n_ranks));
 }
 
 // runs of t before every tile, for the (t,t) pair of a single merge or the (t,t) member(s) of a batch
-void launch_run_lengths(hipStream_t s, const TileSum *sin, uint32_t n_tiles, const unsigned long long *best, const DevCtl *ctl,
-                        int seq, const BatchState *bs, unsigned long long *run_part, const RankEdge *left_edge, uint32_t *run_in) {
-    if (!n_tiles) return;
-    const uint32_t n_chunks = (n_tiles + kRunChunk - 1) / kRunChunk;
-    hipLaunchKernelGGL(k_run_partial, dim3(n_chunks), dim3(kRunThreads), 0, s, sin, n_tiles, best, ctl, seq, bs, run_part);
-    hipLaunchKernelGGL(k_run_final, dim3(n_chunks), dim3(kRunThreads), 0, s, sin, n_tiles, best, ctl, seq, bs, run_part,
-                       left_edge, run_in);
+void launch_run_lengths(const StreamView &v, const BatchState *bs, const unsigned long long *best, int seq) {
+    if (!v.n_tiles) return;
+    const uint32_t n_chunks = (v.n_tiles + kRunChunk - 1) / kRunChunk;
+    hipLaunchKernelGGL(k_run_partial, dim3(n_chunks), dim3(kRunThreads), 0, v.stream, v.sums, v.n_tiles, best, v.ctl, seq, bs,
+                       v.run_part);
+    hipLaunchKernelGGL(k_run_final, dim3(n_chunks), dim3(kRunThreads), 0, v.stream, v.sums, v.n_tiles, best, v.ctl, seq, bs,
+                       v.run_part, v.left_edge, v.run_in);
 }
 
-void launch_merge(hipStream_t s, uint16_t *tok, uint16_t *tok_other, const TileSum *sin, TileSum *sout, uint32_t n_tiles,
-                  uint32_t *chg, const unsigned long long *best, uint32_t new_id, uint32_t endbit, uint32_t *LR,
-                  DevCtl *ctl, uint32_t *m_adj, const RankEdge *left_edge, const RankEdge *right_edge, int n_cus,
-                  int seq, unsigned long long *run_part, uint32_t *run_in, const BatchState *bs, int hot_possible, int only) {
-    if (!n_tiles) return;
+void launch_merge(const StreamView &v, const BatchView &b, const unsigned long long *best, uint32_t new_id,
+                  uint32_t *m_adj, int seq, const Inst &w) {
+    if (!v.n_tiles) return;
+    const BatchState *bs = seq ? b.bs : nullptr;       // (a batch may hold a (t,t) member)
     // runs of t before every tile, for a (t,t) pair (the kernels return at once for any other pair)
-    if (only < 0 || (only & 1)) launch_run_lengths(s, sin, n_tiles, best, ctl, seq, bs, run_part, left_edge, run_in);
+    if (inst_may_tt(w)) launch_run_lengths(v, bs, best, seq);
     static const int occ[3] = {resident_blocks(k_merge<0, false, 0>), resident_blocks(k_merge<1, false, 0>),
                                resident_blocks(k_merge<2, false, 0>)};
-    const dim3 grid(tile_grid(n_tiles, n_cus, occ[slot_mode(endbit)])), block(kMergeThreads);
+    const dim3 grid(tile_grid(v.n_tiles, v.n_cus, occ[slot_mode(v.endbit)])), block(kMergeThreads);
+    const int hot_launched = w.hot;
+#define MBPE_MERGE_ARGS v.tok, v.tok_other, v.sums, v.side, v.n_tiles, v.chg, best, new_id, b.LR, v.ctl, m_adj, v.left_edge, \
+                        v.right_edge, seq, v.run_in, hot_launched
 #ifdef MBPE_DIAG
     static const int diag = getenv("MBPE_MERGE_DIAG") ? atoi(getenv("MBPE_MERGE_DIAG")) : 0;
-    if (diag == 1 && !endbit) {
-        hipLaunchKernelGGL((k_merge<0, false, 1>), grid, block, 0, s, tok, tok_other, sin, sout, n_tiles, chg, best, new_id, LR, ctl,
-                           m_adj, left_edge, right_edge, seq, run_in, hot_possible);
+    if (diag == 1 && !v.endbit) {
+        hipLaunchKernelGGL((k_merge<0, false, 1>), grid, block, 0, v.stream, MBPE_MERGE_ARGS);
         return;
     }
-    if (diag == 2 && !endbit) {
-        hipLaunchKernelGGL((k_merge<0, false, 2>), grid, block, 0, s, tok, tok_other, sin, sout, n_tiles, chg, best, new_id, LR, ctl,
-                           m_adj, left_edge, right_edge, seq, run_in, hot_possible);
+    if (diag == 2 && !v.endbit) {
+        hipLaunchKernelGGL((k_merge<0, false, 2>), grid, block, 0, v.stream, MBPE_MERGE_ARGS);
         return;
     }
 #endif
-    // (both instantiations: each returns at once unless the pair's frequency is its case; only >= 0: exactly the one
-    //  the host knows this merge takes -- bit 1: the frequent-pair instantiation)
-    MBPE_BY_MODE(endbit, {
-        if (only < 0 || !(only & 2))
-            hipLaunchKernelGGL((k_merge<M, false, 0>), grid, block, 0, s, tok, tok_other, sin, sout, n_tiles, chg, best, new_id, LR, ctl,
-                               m_adj, left_edge, right_edge, seq, run_in, hot_possible);
-        if (only < 0 ? hot_possible != 0 : (only & 2) != 0)
-            hipLaunchKernelGGL((k_merge<M, true, 0>), grid, block, 0, s, tok, tok_other, sin, sout, n_tiles, chg, best, new_id, LR,
-                               ctl, m_adj, left_edge, right_edge, seq, run_in, hot_possible);
+    // (both instantiations: each returns at once unless the pair's frequency is its case; w.known: exactly the one
+    //  the host knows this merge takes)
+    MBPE_BY_MODE(v.endbit, {
+        if (inst_takes(w, w.tt, false)) hipLaunchKernelGGL((k_merge<M, false, 0>), grid, block, 0, v.stream, MBPE_MERGE_ARGS);
+        if (inst_takes(w, w.tt, true)) hipLaunchKernelGGL((k_merge<M, true, 0>), grid, block, 0, v.stream, MBPE_MERGE_ARGS);
     });
+#undef MBPE_MERGE_ARGS
 }
 
-void launch_apply(hipStream_t s, PairTable t, DevCtl *ctl, const unsigned long long *best, uint32_t new_id,
-                  uint32_t *LR, const uint32_t *gm_gadj, TileSum *sums, const TileSum *side,
-                  uint32_t *chg, uint32_t n_tiles, int seq) {
-    // new_id: the id of the new token, or (seq != 0) an upper bound of it
-    const uint32_t n_words = (n_tiles + 31u) / 32u;
+void launch_apply(const StreamView &v, const BatchView &b, PairTable t, const unsigned long long *best, uint32_t new_id,
+                  const uint32_t *gm_gadj, int seq) {
+    const uint32_t n_words = (v.n_tiles + 31u) / 32u;
     uint32_t blocks = (new_id + 255) / 256;
     const uint32_t want = (n_words + 255) / 256;
     if (want > blocks) blocks = want < 2048 ? want : 2048;
-    hipLaunchKernelGGL(k_apply, dim3(blocks), dim3(256), 0, s, t, ctl, best, new_id, LR, gm_gadj, sums, side, chg,
-                       n_words, seq);
+    hipLaunchKernelGGL(k_apply, dim3(blocks), dim3(256), 0, v.stream, t, v.ctl, best, new_id, b.LR, gm_gadj, v.sums, v.side,
+                       v.chg, n_words, seq);
 }
 
-void launch_patch_sums(hipStream_t s, const unsigned long long *best, TileSum *sums, const TileSum *side,
-                       uint32_t *chg, uint32_t n_tiles, DevCtl *ctl, int seq) {
-    const uint32_t n_words = (n_tiles + 31u) / 32u;
+void launch_patch_sums(const StreamView &v, const unsigned long long *best, int seq) {
+    const uint32_t n_words = (v.n_tiles + 31u) / 32u;
     uint32_t blocks = (n_words + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(k_patch_sums, dim3(blocks), dim3(256), 0, s, best, sums, side, chg, n_words, ctl, seq, n_tiles);
+    hipLaunchKernelGGL(k_patch_sums, dim3(blocks), dim3(256), 0, v.stream, best, v.sums, v.side, v.chg, n_words, v.ctl, seq,
+                       v.n_tiles);
 }
 
-void launch_select_batch(hipStream_t s, PairTable t, DevCtl *ctl, BatchState *bs, SelList *sel,
-                         unsigned long long *best, uint32_t n_target, uint32_t max_batch, uint32_t fused_min,
-                         int n_cus, int n_ranks, uint32_t endbit, uint32_t sel_cap, bool byte_table, int attempts,
-                         int first_attempt, bool fallback) {
-    const uint32_t fake_id = (endbit == kEndBit ? 0x7FFFu : 0xFFFFu) - 1u;      // see tt_rename
+void launch_select_batch(const StreamView &v, const BatchView &b, PairTable t, unsigned long long *best,
+                         const SelectArgs &a, int attempts, int first_attempt, bool fallback) {
+    const hipStream_t s = v.stream;
+    const uint32_t fake_id = (v.endbit == kEndBit ? 0x7FFFu : 0xFFFFu) - 1u;      // see tt_rename
     // stand-in ids of (t,t) members are the kTTMax ids below the hole / end-bit mask: only while no token has them
-    const uint32_t tt_max = 256u + n_target <= fake_id + 1u - (uint32_t)kTTMax ? (uint32_t)kTTMax : 1u;
-    if (sel_cap < 64u) sel_cap = 64u;
-    if (sel_cap > kSelCap) sel_cap = kSelCap;
-    if (sel) {
-        const int blocks = (n_cus > 0 ? n_cus : 256) * 4;
+    const uint32_t tt_max = 256u + a.n_target <= fake_id + 1u - (uint32_t)kTTMax ? (uint32_t)kTTMax : 1u;
+    const uint32_t sel_cap = a.sel_cap < 64u ? 64u : a.sel_cap > kSelCap ? kSelCap : a.sel_cap;
+    if (a.sel) {
+        const int blocks = (v.n_cus > 0 ? v.n_cus : 256) * 4;
         // (attempts 1 and 2 only work after an overflowing or empty first gather; when they are needed and were not
         //  enqueued the bound-walking kernel below selects -- slower, never wrong)
         for (int attempt = first_attempt < 0 ? 0 : first_attempt; attempt < (attempts < 1 ? 1 : attempts > 3 ? 3 : attempts); ++attempt) {
-            hipLaunchKernelGGL(k_sel_scan, dim3(blocks), dim3(256), 0, s, t, ctl, sel, n_target, sel_cap, attempt);
-            hipLaunchKernelGGL(k_sel_pick, dim3(1), dim3(kPickThreads), 0, s, ctl, bs, sel, best, n_target, max_batch,
-                               fused_min, (uint32_t)n_ranks, attempt, fake_id, sel_cap, tt_max, byte_table ? 1u : 0u);
+            hipLaunchKernelGGL(k_sel_scan, dim3(blocks), dim3(256), 0, s, t, v.ctl, a.sel, a.n_target, sel_cap, attempt);
+            hipLaunchKernelGGL(k_sel_pick, dim3(1), dim3(kPickThreads), 0, s, v.ctl, b.bs, a.sel, best, a.n_target, a.max_batch,
+                               a.fused_min, (uint32_t)v.n_ranks, attempt, fake_id, sel_cap, tt_max, a.byte_table ? 1u : 0u);
         }
     }
     if (fallback)
-        hipLaunchKernelGGL(k_select_batch, dim3(1), dim3(kHierThreads), 0, s, t, ctl, bs, best, n_target, max_batch,
-                           fused_min, (uint32_t)n_ranks);
+        hipLaunchKernelGGL(k_select_batch, dim3(1), dim3(kHierThreads), 0, s, t, v.ctl, b.bs, best, a.n_target, a.max_batch,
+                           a.fused_min, (uint32_t)v.n_ranks);
 }
 
-void launch_fused_batch(hipStream_t s, uint16_t *tok0, uint16_t *tok1, const TileSum *sums, TileSum *side,
-                        uint32_t n_tiles, uint32_t *chg, const BatchState *bs, uint32_t *hdr_adj, uint32_t *LR,
-                        DevCtl *ctl, const RankEdge *left_edge, const RankEdge *right_edge, uint32_t endbit,
-                        int n_cus, uint32_t *hdr_m, const uint32_t *run_in, int hot_possible, int only, uint32_t *T) {
-    if (!n_tiles) return;
+void launch_fused_batch(const StreamView &v, const BatchView &b, const Inst &w) {
+    if (!v.n_tiles) return;
     static const int occ[3] = {resident_blocks(k_fused_batch<0, false, false, 0>, kLutThreads),
                                resident_blocks(k_fused_batch<1, false, false, 0>, kLutThreads),
                                resident_blocks(k_fused_batch<2, false, false, 0>, kLutThreads)};
-    const dim3 grid(tile_grid(n_tiles, n_cus, occ[slot_mode(endbit)], kLutThreads)), block(kLutThreads);
+    const dim3 grid(tile_grid(v.n_tiles, v.n_cus, occ[slot_mode(v.endbit)], kLutThreads)), block(kLutThreads);
+    const int hot_launched = w.hot;
+#define MBPE_FUSED_ARGS v.tok, v.tok_other, v.sums, v.side, v.n_tiles, v.chg, b.bs, b.hdr_adj, b.LR, v.ctl, v.left_edge, \
+                        v.right_edge, b.hdr_m, v.run_in, hot_launched, b.pair_cells
 #ifdef MBPE_DIAG
     const int diag = getenv("MBPE_FUSED_DIAG") ? atoi(getenv("MBPE_FUSED_DIAG")) : 0;   // (re-read: set after warm-up)
 #define MBPE_FUSED_DIAG_CASE(D)                                                                                            \
-    if (diag == D && !endbit) {                                                                                            \
-        hipLaunchKernelGGL((k_fused_batch<0, false, false, D>), grid, block, 0, s, tok0, tok1, sums, side, n_tiles,        \
-                           chg, bs, hdr_adj, LR, ctl, left_edge, right_edge, hdr_m, run_in, hot_possible, T);                               \
-        hipLaunchKernelGGL((k_fused_batch<0, false, true, D>), grid, block, 0, s, tok0, tok1, sums, side, n_tiles,         \
-                           chg, bs, hdr_adj, LR, ctl, left_edge, right_edge, hdr_m, run_in, hot_possible, T);                               \
+    if (diag == D && !v.endbit) {                                                                                          \
+        hipLaunchKernelGGL((k_fused_batch<0, false, false, D>), grid, block, 0, v.stream, MBPE_FUSED_ARGS);                \
+        hipLaunchKernelGGL((k_fused_batch<0, false, true, D>), grid, block, 0, v.stream, MBPE_FUSED_ARGS);                 \
         return;                                                                                                            \
     }
     MBPE_FUSED_DIAG_CASE(2)
@@ -4503,57 +4503,32 @@ void launch_fused_batch(hipStream_t s, uint16_t *tok0, uint16_t *tok1, const Til
     MBPE_FUSED_DIAG_CASE(6)
 #undef MBPE_FUSED_DIAG_CASE
 #endif
-    MBPE_BY_MODE(endbit, {
-        // (only >= 0: exactly the instantiation the host knows this batch takes -- bit 0: (t,t) member, bit 1: frequent pair)
-        if (only < 0 || only == 0)
-            hipLaunchKernelGGL((k_fused_batch<M, false, false>), grid, block, 0, s, tok0, tok1, sums, side, n_tiles, chg, bs, hdr_adj,
-                               LR, ctl, left_edge, right_edge, hdr_m, run_in, hot_possible, T);
-        if (only < 0 || only == 1)
-            hipLaunchKernelGGL((k_fused_batch<M, false, true>), grid, block, 0, s, tok0, tok1, sums, side, n_tiles, chg, bs, hdr_adj,
-                               LR, ctl, left_edge, right_edge, hdr_m, run_in, hot_possible, T);
-        if (only < 0 ? hot_possible != 0 : only == 2)
-            hipLaunchKernelGGL((k_fused_batch<M, true, false>), grid, block, 0, s, tok0, tok1, sums, side, n_tiles, chg, bs, hdr_adj,
-                               LR, ctl, left_edge, right_edge, hdr_m, run_in, hot_possible, T);
-        if (only < 0 ? hot_possible != 0 : only == 3)
-            hipLaunchKernelGGL((k_fused_batch<M, true, true>), grid, block, 0, s, tok0, tok1, sums, side, n_tiles, chg, bs, hdr_adj,
-                               LR, ctl, left_edge, right_edge, hdr_m, run_in, hot_possible, T);
-    });
+    MBPE_BY_MODE(v.endbit, MBPE_BY_INST(w, hipLaunchKernelGGL((k_fused_batch<M, HOT, TT>), grid, block, 0, v.stream, MBPE_FUSED_ARGS)));
+#undef MBPE_FUSED_ARGS
 }
 
-void launch_scan_batch(hipStream_t s, const uint16_t *tok, const uint16_t *tok1, const TileSum *sums, uint32_t n_tiles,
-                       uint32_t *chg, const BatchState *bs, uint32_t *hdr_m, uint32_t *hdr_adj, uint32_t *LR,
-                       const DevCtl *ctl, const RankEdge *left_edge, const RankEdge *right_edge, uint32_t endbit,
-                       int n_cus, const uint32_t *run_in, int hot_possible, int only, uint32_t *T) {
-    if (!n_tiles) return;
+void launch_scan_batch(const StreamView &v, const BatchView &b, const Inst &w) {
+    if (!v.n_tiles) return;
     static const int occ[3] = {resident_blocks(k_scan_batch<0, false, false, 0>, kLutThreads),
                                resident_blocks(k_scan_batch<1, false, false, 0>, kLutThreads),
                                resident_blocks(k_scan_batch<2, false, false, 0>, kLutThreads)};
-    const dim3 grid(tile_grid(n_tiles, n_cus, occ[slot_mode(endbit)], kLutThreads)), block(kLutThreads);
-    MBPE_BY_MODE(endbit, {
-        if (only < 0 || only == 0)
-            hipLaunchKernelGGL((k_scan_batch<M, false, false, 0>), grid, block, 0, s, tok, tok1, sums, n_tiles, chg, bs, hdr_m, hdr_adj,
-                               LR, ctl, left_edge, right_edge, run_in, hot_possible, T);
-        if (only < 0 || only == 1)
-            hipLaunchKernelGGL((k_scan_batch<M, false, true, 0>), grid, block, 0, s, tok, tok1, sums, n_tiles, chg, bs, hdr_m, hdr_adj,
-                               LR, ctl, left_edge, right_edge, run_in, hot_possible, T);
-        if (only < 0 ? hot_possible != 0 : only == 2)
-            hipLaunchKernelGGL((k_scan_batch<M, true, false, 0>), grid, block, 0, s, tok, tok1, sums, n_tiles, chg, bs, hdr_m,
-                               hdr_adj, LR, ctl, left_edge, right_edge, run_in, hot_possible, T);
-        if (only < 0 ? hot_possible != 0 : only == 3)
-            hipLaunchKernelGGL((k_scan_batch<M, true, true, 0>), grid, block, 0, s, tok, tok1, sums, n_tiles, chg, bs, hdr_m,
-                               hdr_adj, LR, ctl, left_edge, right_edge, run_in, hot_possible, T);
-    });
+    const dim3 grid(tile_grid(v.n_tiles, v.n_cus, occ[slot_mode(v.endbit)], kLutThreads)), block(kLutThreads);
+    const int hot_launched = w.hot;
+    MBPE_BY_MODE(v.endbit, MBPE_BY_INST(w, hipLaunchKernelGGL((k_scan_batch<M, HOT, TT, 0>), grid, block, 0, v.stream, v.tok,
+                                                             v.tok_other, v.sums, v.n_tiles, v.chg, b.bs, b.hdr_m, b.hdr_adj, b.LR,
+                                                             v.ctl, v.left_edge, v.right_edge, v.run_in, hot_launched,
+                                                             b.pair_cells)));
 }
 
-void launch_pair_cells_fold(hipStream_t s, uint32_t *T, uint32_t *LR, const DevCtl *ctl, uint32_t n_hint) {
-    if (!T) return;
+void launch_pair_cells_fold(const StreamView &v, const BatchView &b, uint32_t n_hint) {
+    if (!b.pair_cells) return;
     if (n_hint < 64u) n_hint = 64u;
     if (n_hint > 1024u) n_hint = 1024u;
-    hipLaunchKernelGGL(k_pair_cells_fold, dim3(n_hint), dim3(256), 0, s, T, LR, ctl);
+    hipLaunchKernelGGL(k_pair_cells_fold, dim3(n_hint), dim3(256), 0, v.stream, b.pair_cells, b.LR, v.ctl);
 }
 
-void launch_batch_tables(hipStream_t s, PairTable t, DevCtl *ctl, BatchState *bs, uint32_t *hdr_m, uint32_t *hdr_adj,
-                         uint32_t *LR, uint32_t id_upper, uint32_t n_hint) {
+void launch_batch_tables(const StreamView &v, const BatchView &b, PairTable t, uint32_t id_upper, uint32_t n_hint) {
+    const hipStream_t s = v.stream;
     // n_hint: the batch size the grids are sized for (every kernel strides over what the batch really holds)
     if (n_hint < 64u) n_hint = 64u;
     if (n_hint > (uint32_t)kBatchMax) n_hint = kBatchMax;
@@ -4562,42 +4537,40 @@ void launch_batch_tables(hipStream_t s, PairTable t, DevCtl *ctl, BatchState *bs
     uint32_t blocks = (uint32_t)((cells + 255) / 256);
     if (blocks > 2048) blocks = 2048;
     if (blocks < 8) blocks = 8;            // (k_apply_batch: at least kBatchMax threads, for the per-pair part)
-    hipLaunchKernelGGL(k_adj_sums, dim3(n_hint), dim3(kWave), 0, s, hdr_adj, bs, ctl);
+    hipLaunchKernelGGL(k_adj_sums, dim3(n_hint), dim3(kWave), 0, s, b.hdr_adj, b.bs, v.ctl);
     // (work items of k_delta_max: 4096 cells of one LR row each)
-    hipLaunchKernelGGL(k_delta_max, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, s, LR, bs, ctl);
-    hipLaunchKernelGGL(k_adj_max, dim3(n_hint / 4), dim3(256), 0, s, hdr_adj, bs, ctl);
-    hipLaunchKernelGGL(k_validate, dim3(1), dim3(kValThreads), 0, s, t, ctl, bs, hdr_m, hdr_adj, LR);
+    hipLaunchKernelGGL(k_delta_max, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, s, b.LR, b.bs, v.ctl);
+    hipLaunchKernelGGL(k_adj_max, dim3(n_hint / 4), dim3(256), 0, s, b.hdr_adj, b.bs, v.ctl);
+    hipLaunchKernelGGL(k_validate, dim3(1), dim3(kValThreads), 0, s, t, v.ctl, b.bs, b.hdr_m, b.hdr_adj, b.LR);
     if (t.cells) {
         uint32_t j_parts = (n_hint + kApplyTile - 1) / kApplyTile;       // workgroups side by side along the pairs
         if (j_parts > kApplyJParts) j_parts = kApplyJParts;
         uint32_t grid = ((id_upper + kApplyTile - 1) / kApplyTile) * j_parts;
         if (grid < 256u) grid = 256u;               // (the rows of the ADJ block and the per-pair part: a grid stride each)
-        hipLaunchKernelGGL(k_apply_batch_dense, dim3(grid), dim3(256), 0, s, t, ctl, bs, hdr_m, hdr_adj, LR, j_parts);
+        hipLaunchKernelGGL(k_apply_batch_dense, dim3(grid), dim3(256), 0, s, t, v.ctl, b.bs, b.hdr_m, b.hdr_adj, b.LR, j_parts);
     } else {
-        hipLaunchKernelGGL(k_apply_batch, dim3(blocks), dim3(256), 0, s, t, ctl, bs, hdr_m, hdr_adj, LR);
+        hipLaunchKernelGGL(k_apply_batch, dim3(blocks), dim3(256), 0, s, t, v.ctl, b.bs, b.hdr_m, b.hdr_adj, b.LR);
     }
 }
 
-void launch_rewrite_marked(hipStream_t s, uint16_t *tok, uint16_t *tok1, const TileSum *sums, TileSum *side, uint32_t n_tiles,
-                           uint32_t *chg, uint32_t *list, const BatchState *bs, DevCtl *ctl,
-                           const RankEdge *left_edge, const RankEdge *right_edge, uint32_t endbit, int n_cus,
-                           const uint32_t *run_in, int only) {
-    if (!n_tiles) return;
-    const uint32_t n_words = (n_tiles + 31u) / 32u;
-    hipLaunchKernelGGL(k_list_marked, dim3((n_words + 255) / 256), dim3(256), 0, s, chg, n_words, list, ctl, n_tiles);
+void launch_rewrite_marked(const StreamView &v, const BatchView &b, const Inst &w) {
+    if (!v.n_tiles) return;
+    const uint32_t n_words = (v.n_tiles + 31u) / 32u;
+    hipLaunchKernelGGL(k_list_marked, dim3((n_words + 255) / 256), dim3(256), 0, v.stream, v.chg, n_words, v.tile_list, v.ctl,
+                       v.n_tiles);
     static const int occ[3] = {resident_blocks(k_rewrite_marked<0, false>, kLutThreads),
                                resident_blocks(k_rewrite_marked<1, false>, kLutThreads),
                                resident_blocks(k_rewrite_marked<2, false>, kLutThreads)};
-    const dim3 grid(tile_grid(n_tiles, n_cus, occ[slot_mode(endbit)], kLutThreads)), block(kLutThreads);
-    MBPE_BY_MODE(endbit, {
-        // (only >= 0, bit 0: the batch has a (t,t) member.  Validation may keep a prefix that ends before it: then the
+    const dim3 grid(tile_grid(v.n_tiles, v.n_cus, occ[slot_mode(v.endbit)], kLutThreads)), block(kLutThreads);
+#define MBPE_REWRITE_ARGS v.tok, v.tok_other, v.sums, v.side, v.n_tiles, v.chg, v.tile_list, b.bs, v.ctl, v.left_edge, \
+                          v.right_edge, v.run_in
+    MBPE_BY_MODE(v.endbit, {
+        // (a batch the host knows to have a (t,t) member: validation may keep a prefix that ends before it, and then the
         //  other instantiation is the one that works, so both are enqueued for such a batch)
-        hipLaunchKernelGGL((k_rewrite_marked<M, false>), grid, block, 0, s, tok, tok1, sums, side, n_tiles, chg, list, bs, ctl,
-                           left_edge, right_edge, run_in);
-        if (only < 0 || (only & 1))
-            hipLaunchKernelGGL((k_rewrite_marked<M, true>), grid, block, 0, s, tok, tok1, sums, side, n_tiles, chg, list, bs, ctl,
-                               left_edge, right_edge, run_in);
+        hipLaunchKernelGGL((k_rewrite_marked<M, false>), grid, block, 0, v.stream, MBPE_REWRITE_ARGS);
+        if (inst_may_tt(w)) hipLaunchKernelGGL((k_rewrite_marked<M, true>), grid, block, 0, v.stream, MBPE_REWRITE_ARGS);
     });
+#undef MBPE_REWRITE_ARGS
 }
 
 // What the selection of the sequence under way decided, for a host that enqueues only the kernels this sequence needs
@@ -4627,35 +4600,33 @@ __global__ void k_seq_info(const DevCtl *ctl, const BatchState *bs, const unsign
     out[7] = 0;
 }
 
-void launch_seq_info(hipStream_t s, const DevCtl *ctl, const BatchState *bs, const unsigned long long *best, uint32_t *out) {
-    hipLaunchKernelGGL(k_seq_info, dim3(1), dim3(64), 0, s, ctl, bs, best, out);
+void launch_seq_info(const StreamView &v, const BatchView &b, const unsigned long long *best, uint32_t *out) {
+    hipLaunchKernelGGL(k_seq_info, dim3(1), dim3(64), 0, v.stream, v.ctl, b.bs, best, out);
 }
 
-void launch_seq_finish(hipStream_t s, DevCtl *ctl, uint32_t *fused_flag, const BatchState *bs) {
-    hipLaunchKernelGGL(k_seq_finish, dim3(1), dim3(64), 0, s, ctl, fused_flag, bs);
+void launch_seq_finish(const StreamView &v, const BatchView &b, uint32_t *fused_flag) {
+    hipLaunchKernelGGL(k_seq_finish, dim3(1), dim3(64), 0, v.stream, v.ctl, fused_flag, b.bs);
 }
 
-void launch_tile_scan(hipStream_t s, const TileSum *sums, uint32_t n_tiles, unsigned long long *offsets,
-                      DevCtl *ctl) {
+void launch_tile_scan(const StreamView &v, unsigned long long *offsets) {
     // offsets has room for the chunk sums behind its n_tiles entries (tile_scan_scratch_words)
-    if (!n_tiles) return;
-    unsigned long long *part = offsets + n_tiles;
-    const uint32_t n_parts = (n_tiles + kScanChunk - 1) / kScanChunk;
-    hipLaunchKernelGGL(k_tile_scan_partial, dim3(n_parts), dim3(kScanThreads), 0, s, sums, n_tiles, part);
-    hipLaunchKernelGGL(k_tile_scan_top, dim3(1), dim3(1024), 0, s, part, n_parts, ctl);
-    hipLaunchKernelGGL(k_tile_scan_final, dim3(n_parts), dim3(kScanThreads), 0, s, sums, n_tiles, part, offsets);
+    if (!v.n_tiles) return;
+    unsigned long long *part = offsets + v.n_tiles;
+    const uint32_t n_parts = (v.n_tiles + kScanChunk - 1) / kScanChunk;
+    hipLaunchKernelGGL(k_tile_scan_partial, dim3(n_parts), dim3(kScanThreads), 0, v.stream, v.sums, v.n_tiles, part);
+    hipLaunchKernelGGL(k_tile_scan_top, dim3(1), dim3(1024), 0, v.stream, part, n_parts, v.ctl);
+    hipLaunchKernelGGL(k_tile_scan_final, dim3(n_parts), dim3(kScanThreads), 0, v.stream, v.sums, v.n_tiles, part, offsets);
 }
 
-void launch_compact_scatter(hipStream_t s, const uint16_t *src, const TileSum *sums,
-                            const unsigned long long *offsets, uint32_t n_tiles, uint16_t *dst, int n_cus) {
-    if (!n_tiles) return;
-    hipLaunchKernelGGL(k_compact_scatter, dim3(tile_grid(n_tiles, n_cus)), dim3(kMergeThreads), 0, s, src, sums,
-                       offsets, n_tiles, dst);
+void launch_compact_scatter(const StreamView &v, const unsigned long long *offsets) {
+    if (!v.n_tiles) return;
+    hipLaunchKernelGGL(k_compact_scatter, dim3(tile_grid(v.n_tiles, v.n_cus)), dim3(kMergeThreads), 0, v.stream, v.tok, v.sums,
+                       offsets, v.n_tiles, v.tok_other);
 }
 
-void launch_rank_edge(hipStream_t s, const TileSum *sums, uint32_t n_tiles, RankEdge *out, const DevCtl *ctl,
-                      uint32_t *hdr) {
-    hipLaunchKernelGGL(k_rank_edge, dim3(1), dim3(64), 0, s, sums, n_tiles, out, ctl, hdr);
+void launch_rank_edge(const StreamView &v, uint32_t *hdr) {
+    hipLaunchKernelGGL(k_rank_edge, dim3(1), dim3(64), 0, v.stream, v.sums, v.n_tiles, reinterpret_cast<RankEdge *>(hdr + 2) + v.rank,
+                       v.ctl, hdr);
 }
 
 void launch_compose_edges(hipStream_t s, uint32_t *hdr, int rank, int n_ranks, RankEdge *left, RankEdge *right) {

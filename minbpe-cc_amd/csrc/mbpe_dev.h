@@ -237,9 +237,48 @@ __host__ __device__ inline unsigned long long pack_best(int32_t count, uint32_t 
 }
 
 // ---- kernel launchers (implemented in kernels.hip) ------------------------
-struct Launch {
+// What every stream kernel needs is ONE StreamView, the buffers of a batch ONE BatchView (built in one place each:
+// train.cpp, stream_view / batch_view); a launcher takes them plus only what is particular to that launch.
+struct StreamView {
     hipStream_t stream;
+    // seq == 0 (one merge per pass): the live buffer and the other one.  seq != 0 (inside a batch sequence): token
+    // buffers 0 / 1, and ctl->cur picks the live one (a fused pass flips it without the host knowing)
+    uint16_t *tok, *tok_other;
+    TileSum *sums;           // live tile summaries
+    TileSum *side;           // new summaries of the tiles a pass changed (launch_apply / launch_patch_sums fold them in)
+    uint32_t n_tiles;
+    uint32_t *chg;           // bitmap of those tiles
+    uint32_t *tile_list;     // [n_tiles] scratch: the same as a dense list (launch_rewrite_marked)
+    uint32_t *run_in;        // n_tiles entries: run of t before every tile, for (t,t) pairs
+    unsigned long long *run_part;   // tile_scan_scratch(n_tiles) entries (the run kernels' chunk sums)
+    DevCtl *ctl;
+    const RankEdge *left_edge, *right_edge;   // composed neighbours of this rank's shard; NULL on one rank
+    int rank, n_ranks;       // (n_ranks >= 1)
+    uint32_t endbit;         // chunk-end convention: 0 (one chunk), kEndBit (flag in the slot) or kBarrier (barrier slots)
+    int n_cus;
 };
+
+struct BatchView {
+    BatchState *bs;
+    uint32_t *hdr_m, *hdr_adj;   // batch header of the exchange buffer: m_j, ADJ[i][j]
+    uint32_t *LR;                // count deltas: rows L_0, R_0, L_1, R_1, ... (one merge: L[x] = LR[2x], R[y] = LR[2y+1])
+    // (optional) 65,536 u32 cells per pair of the largest batch, all zero between sequences.  A match whose two
+    // neighbours are raw bytes and which no other match touches then costs the scan / fused pass one atomic (cell
+    // [j][x][y]) instead of two (L_j[x], R_j[y]); launch_pair_cells_fold, right behind the pass, adds the blocks' row and
+    // column sums to the LR rows and clears the blocks: everything after it sees the rows it always saw.
+    uint32_t *pair_cells;
+};
+
+// Which instantiations of a stream kernel a launch enqueues: they exist per (t,t) pair / member yes / no and per
+// frequent pair (delta cache) yes / no, and each returns at once unless the pass is its case.  Not known: all of them, the
+// frequent-pair ones only if `hot` (0: they cannot be needed).  Known (launch_seq_info told the host): exactly the one
+// with this `tt` and `hot`.  `hot` is also what the kernels are told was launched (kErrHotSkipped: hot_mismatch).
+struct Inst { bool known, tt, hot; };
+inline Inst inst_any(bool hot_possible) { return Inst{false, false, hot_possible}; }
+inline Inst inst_known(bool tt, bool hot) { return Inst{true, tt, hot}; }
+// is the (tt, hot) instantiation among those `w` enqueues / any that handles a (t,t) pair?
+inline bool inst_takes(const Inst &w, bool tt, bool hot) { return w.known ? w.tt == tt && w.hot == hot : !hot || w.hot; }
+inline bool inst_may_tt(const Inst &w) { return !w.known || w.tt; }
 
 void launch_fill_u32(hipStream_t s, uint32_t *p, uint64_t n, uint32_t v);
 void launch_fill_u16(hipStream_t s, uint16_t *p, uint64_t n, uint16_t v);
@@ -260,8 +299,8 @@ void launch_widen(hipStream_t s, const uint8_t *text, uint64_t n, const uint8_t 
 void launch_widen_barrier(hipStream_t s, const uint8_t *text, uint64_t n, const uint8_t *endmask,
                           uint16_t *tok, uint64_t n_slots);
 
-// recompute every tile summary from the slots
-void launch_summarize(hipStream_t s, const uint16_t *tok, TileSum *sums, uint32_t n_tiles, int n_cus);
+// recompute every tile summary from the slots of v.tok
+void launch_summarize(const StreamView &v);
 
 // dense byte-pair histogram -> pair table
 void launch_table_init(hipStream_t s, const uint32_t *bp, PairTable t, DevCtl *ctl);
@@ -277,102 +316,76 @@ void launch_argmax(hipStream_t s, PairTable t, const DevCtl *ctl, unsigned long 
 // the stream comes first.  fs: first_state_bytes() of device memory, prepared once by launch_first_init.
 size_t first_state_bytes();
 void launch_first_init(hipStream_t s, void *fs);
-// seq != 0: inside a batch sequence: best is the array, the merge index is ctl->k_done, tok / tok_other are token
-// buffers 0 / 1 (ctl->cur picks), and the kernels only work when the selection flagged a tie (ctl->first_tie)
-void launch_first_tiebreak(hipStream_t s, PairTable t, const DevCtl *ctl, unsigned long long *best, void *fs,
-                           const uint16_t *tok, const uint16_t *tok_other, const TileSum *sums, uint32_t n_tiles,
-                           uint32_t endbit, int n_cus, int seq,
-                           int phase = 0 /* 0: one rank -- gather, position, pick.  Sharded stream: 1 = gather, position, publish
-                                            this rank's earliest hit in its slot of xf; [sum xf over the ranks]; 2 = pick the
-                                            hit of the lowest rank that has one */,
-                           const RankEdge *right_edge = nullptr, uint32_t *xf = nullptr /* exchange_header_words(n_ranks) */,
-                           int rank = 0, int n_ranks = 1);
+// seq != 0: inside a batch sequence: best is the array, the merge index is ctl->k_done, and the kernels only work
+// when the selection flagged a tie (ctl->first_tie).
+// phase 0: one rank -- gather, position, pick.  Sharded stream: 1 = gather, position, publish this rank's earliest hit
+// in its slot of xf (exchange_header_words(n_ranks) words); [sum xf over the ranks]; 2 = pick the hit of the lowest
+// rank that has one.
+void launch_first_tiebreak(const StreamView &v, PairTable t, unsigned long long *best, void *fs, uint32_t *xf, int seq,
+                           int phase);
 
-// one merge pass over the stream, in place; new summaries of changed tiles go
-// to `side`, their bits are set in `chg` (launch_apply folds them into sums)
-void launch_merge(hipStream_t s, uint16_t *tok, uint16_t *tok_other, const TileSum *sums, TileSum *side,
-                  uint32_t n_tiles, uint32_t *chg, const unsigned long long *best, uint32_t new_id,
-                  uint32_t endbit, uint32_t *LR, DevCtl *ctl, uint32_t *m_adj /* [m, adj] accumulators */,
-                  const RankEdge *left_edge, const RankEdge *right_edge, int n_cus, int seq,
-                  unsigned long long *run_part /* tile_scan_scratch(n_tiles) entries */,
-                  uint32_t *run_in /* n_tiles entries: run of t before every tile, for (t,t) pairs */,
-                  const BatchState *bs /* seq != 0: a batch may hold a (t,t) member */,
-                  int hot_possible = 1 /* 0: the frequent-pair (delta cache) instantiations cannot be needed: not launched */,
-                  int only = -1 /* >= 0: launch exactly one instantiation -- bit 0: the pair is a (t,t) pair (run kernels),
-                                   bit 1: the frequent-pair one (launch_seq_info told the host) */);
+// one merge pass over the stream, in place; new summaries of changed tiles go to v.side, their bits are set in v.chg
+// (launch_apply folds them into sums).  seq != 0: the kernel runs inside a batch sequence: it reads the merge index
+// from ctl->k_done and returns at once unless the selected batch has one pair (which may be a (t,t) member of b.bs).
+// m_adj: the [m, adj] accumulators.  w.tt: the pair is a (t,t) pair (run kernels).
+void launch_merge(const StreamView &v, const BatchView &b, const unsigned long long *best, uint32_t new_id,
+                  uint32_t *m_adj, int seq, const Inst &w);
 // the run kernels launch_merge starts with, alone (a host that enqueues a batch's pass by itself: train.cpp, lockstep)
-void launch_run_lengths(hipStream_t s, const TileSum *sums, uint32_t n_tiles, const unsigned long long *best, const DevCtl *ctl,
-                        int seq, const BatchState *bs, unsigned long long *run_part, const RankEdge *left_edge, uint32_t *run_in);
-// seq != 0: the kernel runs inside a batch sequence: it reads the merge index
-// from ctl->k_done and returns at once unless the selected batch has one pair;
-// tok / tok_other are then token buffers 0 / 1 and ctl->cur picks the live one
+void launch_run_lengths(const StreamView &v, const BatchState *bs, const unsigned long long *best, int seq);
 
-// fold the merge's count deltas (L, R, m, adj) into the pair table
-// (L[x] = LR[2x], R[y] = LR[2y+1])
-void launch_apply(hipStream_t s, PairTable t, DevCtl *ctl, const unsigned long long *best,
-                  uint32_t new_id, uint32_t *LR, const uint32_t *gm_gadj,
-                  TileSum *sums, const TileSum *side, uint32_t *chg, uint32_t n_tiles, int seq);
+// fold the merge's count deltas (L, R, m, adj) into the pair table; gm_gadj: the [m, adj] summed over the ranks, or NULL;
+// new_id: the id of the new token, or (seq != 0) an upper bound of it
+void launch_apply(const StreamView &v, const BatchView &b, PairTable t, const unsigned long long *best, uint32_t new_id,
+                  const uint32_t *gm_gadj, int seq);
 // only the summary fold of launch_apply (multi-GPU: it must precede the rank edge)
-void launch_patch_sums(hipStream_t s, const unsigned long long *best, TileSum *sums, const TileSum *side,
-                       uint32_t *chg, uint32_t n_tiles, DevCtl *ctl, int seq);
+void launch_patch_sums(const StreamView &v, const unsigned long long *best, int seq);
 
 // ---- batched merges (see kernels.hip "batched merges") ----
+// what a selection is asked for (train.cpp: select_args)
+struct SelectArgs {
+    SelList *sel;            // candidates of the threshold selection; NULL: the bound-walking kernel alone
+    uint32_t n_target, max_batch, fused_min, sel_cap;
+    bool byte_table;
+};
 // k_sel_scan + k_sel_pick (gather everything above a threshold, sort, take the independent
 // prefix), then k_select_batch (walks the argmax bounds one pair at a time) if that could not be used
-void launch_select_batch(hipStream_t s, PairTable t, DevCtl *ctl, BatchState *bs, SelList *sel,
-                         unsigned long long *best, uint32_t n_target, uint32_t max_batch, uint32_t fused_min,
-                         int n_cus, int n_ranks, uint32_t endbit, uint32_t sel_cap, bool byte_table, int attempts = 3,
+void launch_select_batch(const StreamView &v, const BatchView &b, PairTable t, unsigned long long *best,
+                         const SelectArgs &a, int attempts = 3,
                          int first_attempt = 0 /* attempts first_attempt .. attempts - 1 */,
                          bool fallback = true /* the bound-walking kernel behind them */);
 // (up to three gather + pick attempts are enqueued: when the first gather overflows its list -- many equal
 //  counts -- the second lists the block bounds to find a threshold and the third gathers with it.  `attempts` 1: only
 //  the first; the host enqueues the other two while selections have needed them lately)
 // small batch: count the deltas and mark the tiles (the rewrite follows validation)
-void launch_scan_batch(hipStream_t s, const uint16_t *tok0, const uint16_t *tok1, const TileSum *sums,
-                       uint32_t n_tiles, uint32_t *chg, const BatchState *bs, uint32_t *hdr_m, uint32_t *hdr_adj,
-                       uint32_t *LR, const DevCtl *ctl, const RankEdge *left_edge, const RankEdge *right_edge,
-                       uint32_t endbit, int n_cus, const uint32_t *run_in, int hot_possible = 1, int only = -1,
-                       uint32_t *pair_cells = nullptr);
+void launch_scan_batch(const StreamView &v, const BatchView &b, const Inst &w);
 // large batch (ctl->fused): count the deltas and write the merged stream to the other buffer
-void launch_fused_batch(hipStream_t s, uint16_t *tok0, uint16_t *tok1, const TileSum *sums, TileSum *side,
-                        uint32_t n_tiles, uint32_t *chg, const BatchState *bs, uint32_t *hdr_adj, uint32_t *LR,
-                        DevCtl *ctl, const RankEdge *left_edge, const RankEdge *right_edge, uint32_t endbit,
-                        int n_cus, uint32_t *hdr_m, const uint32_t *run_in, int hot_possible = 1, int only = -1,
-                        uint32_t *pair_cells = nullptr);
-// pair_cells (optional, both passes above): 65,536 u32 cells per pair of the largest batch, all zero between sequences.  A
-// match whose two neighbours are raw bytes and which no other match touches then costs the pass one atomic (cell
-// [j][x][y]) instead of two (L_j[x], R_j[y]); launch_pair_cells_fold, right behind the pass, adds the blocks' row and
-// column sums to the LR rows and clears the blocks: everything after it sees the rows it always saw.
-void launch_pair_cells_fold(hipStream_t s, uint32_t *pair_cells, uint32_t *LR, const DevCtl *ctl, uint32_t n_hint);
-// k_delta_max + k_validate + k_apply_batch
-void launch_batch_tables(hipStream_t s, PairTable t, DevCtl *ctl, BatchState *bs, uint32_t *hdr_m, uint32_t *hdr_adj,
-                         uint32_t *LR, uint32_t id_upper, uint32_t n_hint);
-void launch_rewrite_marked(hipStream_t s, uint16_t *tok0, uint16_t *tok1, const TileSum *sums, TileSum *side, uint32_t n_tiles,
-                           uint32_t *chg, uint32_t *list /* [n_tiles] scratch */, const BatchState *bs, DevCtl *ctl,
-                           const RankEdge *left_edge, const RankEdge *right_edge, uint32_t endbit, int n_cus,
-                           const uint32_t *run_in /* as for launch_merge: used when the batch has a (t,t) member */,
-                           int only = -1);
+void launch_fused_batch(const StreamView &v, const BatchView &b, const Inst &w);
+// b.pair_cells -> the LR rows (see BatchView; nothing to do without the blocks)
+void launch_pair_cells_fold(const StreamView &v, const BatchView &b, uint32_t n_hint);
+// k_delta_max + k_validate + k_apply_batch.  n_hint: the batch size the grids are sized for; id_upper: upper bound of
+// the ids that exist
+void launch_batch_tables(const StreamView &v, const BatchView &b, PairTable t, uint32_t id_upper, uint32_t n_hint);
+// w: only whether the batch has a (t,t) member matters (v.run_in is used then, as for launch_merge)
+void launch_rewrite_marked(const StreamView &v, const BatchView &b, const Inst &w);
 // what the selection decided, for a host that enqueues only the kernels a sequence needs: out[0] merges done, [1] pairs
 // in the batch, [2] fused pass, [3] a (t,t) pair among them, [4] frequent-pair instantiation, [5] merge limit,
 // [6] the batch was chosen by a gather + pick attempt (0 after the first attempt alone: enqueue the others and the fallback)
-void launch_seq_info(hipStream_t s, const DevCtl *ctl, const BatchState *bs, const unsigned long long *best, uint32_t *out);
+void launch_seq_info(const StreamView &v, const BatchView &b, const unsigned long long *best, uint32_t *out);
 // fused_flag (optional, 4 words): [0] = 1 when this sequence ran the fused pass, [1..2] = live tokens of the shard after
 // the sequence, [3] = merges it committed
-void launch_seq_finish(hipStream_t s, DevCtl *ctl, uint32_t *fused_flag, const BatchState *bs);
+void launch_seq_finish(const StreamView &v, const BatchView &b, uint32_t *fused_flag);
 
 // compaction: exclusive scan of n_live over tiles, then scatter.  `offsets` needs
 // n_tiles + tile_scan_scratch(n_tiles) entries.
 inline size_t tile_scan_scratch(uint32_t n_tiles) { return (size_t)n_tiles / 4096 + 2; }
-void launch_tile_scan(hipStream_t s, const TileSum *sums, uint32_t n_tiles,
-                      unsigned long long *offsets, DevCtl *ctl);
-void launch_compact_scatter(hipStream_t s, const uint16_t *src, const TileSum *sums,
-                            const unsigned long long *offsets, uint32_t n_tiles, uint16_t *dst, int n_cus);
+void launch_tile_scan(const StreamView &v, unsigned long long *offsets);
+// v.tok -> v.tok_other
+void launch_compact_scatter(const StreamView &v, const unsigned long long *offsets);
 
 // multi-GPU exchange header (u32 words): [0] m, [1] adj, [2 + 8r ..] RankEdge of rank r
 inline uint32_t exchange_header_words(int n_ranks) { return (uint32_t)((2 + 8 * n_ranks + 3) / 4 * 4); }
-// this rank's RankEdge from its tile summaries (+ m, adj into the header when hdr != NULL)
-void launch_rank_edge(hipStream_t s, const TileSum *sums, uint32_t n_tiles, RankEdge *out, const DevCtl *ctl,
-                      uint32_t *hdr);
+// this rank's RankEdge from its tile summaries, into its place in the header (which also receives m, adj)
+void launch_rank_edge(const StreamView &v, uint32_t *hdr);
 // neighbours of this rank's shard from the gathered edges; clears the header
 void launch_compose_edges(hipStream_t s, uint32_t *hdr, int rank, int n_ranks, RankEdge *left, RankEdge *right);
 // the words that follow the header in the begin exchange: the number of pairs counted into the byte-pair table as four

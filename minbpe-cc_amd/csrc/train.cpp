@@ -136,7 +136,6 @@ struct mbpe_ctx {
     // pair table
     PairTable tab = {};
     uint32_t hcap = 0;
-    uint32_t *bp = nullptr;      // unused (the byte-pair table is the front of xb0)
     DevCtl *ctl = nullptr;
     unsigned long long *best = nullptr;   // [n_target + 1]
     // exchange buffer of one merge: [header: m, adj, RankEdge x n_ranks][LR: L[x], R[x] interleaved]
@@ -312,7 +311,7 @@ void free_training(mbpe_ctx *c) {
     tfree(c, c->offsets);
     tfree(c, c->tab.hslot); tfree(c, c->tab.ekey); tfree(c, c->tab.ecnt); tfree(c, c->tab.cells);
     tfree(c, c->tab.bmax); tfree(c, c->tab.smax);
-    tfree(c, c->bp); tfree(c, c->ctl); tfree(c, c->best); tfree(c, c->xb); tfree(c, c->xb0); tfree(c, c->pair_cells);
+    tfree(c, c->ctl); tfree(c, c->best); tfree(c, c->xb); tfree(c, c->xb0); tfree(c, c->pair_cells);
     tfree(c, c->d_left); tfree(c, c->d_right); tfree(c, c->bs); tfree(c, c->sel); tfree(c, c->seq_flags); tfree(c, c->run_in);
     tfree(c, c->first_state);
     tfree(c, c->xf);
@@ -432,20 +431,59 @@ int ensure_pc_scratch(mbpe_ctx *c) {
     return MBPE_OK;
 }
 
+int ensure_events(std::vector<hipEvent_t> &pool, size_t n) {
+    while (pool.size() < n) {
+        hipEvent_t e;
+        HIPCHK(hipEventCreate(&e));
+        pool.push_back(e);
+    }
+    return MBPE_OK;
+}
+
+// the chunk-end convention of the stream, as the launchers take it
+inline uint32_t endbit_of(const mbpe_ctx *c) { return !c->chunked ? 0u : c->barrier ? kBarrier : kEndBit; }
+
+inline bool is_multi(const mbpe_ctx *c) { return c->n_ranks > 1 || c->opt_force_exchange; }
+
+// ---- launch interface (mbpe_dev.h: StreamView, BatchView) ----
+// The builders below are the only places that read the context's stream and batch buffers for a launch.
+// Which token buffer a view names first.  A batch sequence passes buffers 0 and 1 and lets ctl->cur decide (a fused pass
+// flips the live buffer without the host knowing); everything outside the sequences passes the live buffer first.
+enum TokOrder { kBuffers01, kLiveFirst };
+
+StreamView stream_view(const mbpe_ctx *c, TokOrder order) {
+    const int first = order == kLiveFirst ? c->cur : 0;
+    const bool multi = is_multi(c);
+    StreamView v = {};
+    v.stream = c->stream;
+    v.tok = c->tok[first], v.tok_other = c->tok[1 - first];
+    v.sums = c->sums, v.side = c->side, v.n_tiles = c->n_tiles;
+    v.chg = c->chg, v.tile_list = c->tile_list;
+    v.run_in = c->run_in, v.run_part = c->offsets + c->n_tiles;
+    v.ctl = c->ctl;
+    v.left_edge = multi ? c->d_left : nullptr, v.right_edge = multi ? c->d_right : nullptr;
+    v.rank = c->rank, v.n_ranks = std::max(1, c->n_ranks);
+    v.endbit = endbit_of(c), v.n_cus = c->n_cus;
+    return v;
+}
+
+BatchView batch_view(const mbpe_ctx *c) { return BatchView{c->bs, c->hdr_m, c->hdr_adj, c->LR, c->pair_cells}; }
+
 int do_compact(mbpe_ctx *c) {
     // c->h_ctl must be current
     if (!c->n_tiles) return MBPE_OK;
     WallTimer timer(&c->stats.ms_compact);
-    const int src = c->cur, dst = 1 - c->cur;
-    launch_tile_scan(c->stream, c->sums, c->n_tiles, c->offsets, c->ctl);
-    launch_compact_scatter(c->stream, c->tok[src], c->sums, c->offsets, c->n_tiles, c->tok[dst], c->n_cus);
+    const int dst = 1 - c->cur;
+    const StreamView v = stream_view(c, kLiveFirst);       // live buffer -> the other one
+    launch_tile_scan(v, c->offsets);
+    launch_compact_scatter(v, c->offsets);
     const uint64_t live = c->h_ctl.n_live;
     const uint64_t padded = std::max<uint64_t>(round_up(live, kTile), kTile);
     launch_fill_u16(c->stream, c->tok[dst] + live, padded - live, (uint16_t)kHole);
     c->cur = dst;
     c->n_slots = padded;
     c->n_tiles = (uint32_t)(padded / kTile);
-    launch_summarize(c->stream, c->tok[c->cur], c->sums, c->n_tiles, c->n_cus);
+    launch_summarize(stream_view(c, kLiveFirst));
     DevCtl patch = c->h_ctl;
     patch.removed_total = 0;
     HIPCHK(hipMemcpyAsync(&c->ctl->removed_total, &patch.removed_total, sizeof(patch.removed_total),
@@ -713,11 +751,8 @@ int mbpe_pair_count_u8(mbpe_ctx *c, uint32_t *table65536_out) {
     const int reps = table65536_out ? 1 : (int)std::max<int64_t>(1, c->opt_pc_repeat);
     // (every dispatch also carries its own start / stop events -- hipExtLaunchKernelGGL -- so that the kernel's duration
     //  is known without the gap between two launches or the cost of a marker: ms_pair_count_kernel)
-    while (c->kev.size() < 2ull * reps) {
-        hipEvent_t ev;
-        HIPCHK(hipEventCreate(&ev));
-        c->kev.push_back(ev);
-    }
+    rcs = ensure_events(c->kev, 2ull * reps);
+    if (rcs != MBPE_OK) return rcs;
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     if (!c->inert)
         for (int r = 0; r < reps; ++r)
@@ -787,11 +822,6 @@ static inline bool use_hier(const mbpe_ctx *c) {
     return c->h_ctl.n_entries > (1u << 20);
 }
 
-// the chunk-end convention of the stream, as the launchers take it
-static inline uint32_t endbit_of(const mbpe_ctx *c) { return !c->chunked ? 0u : c->barrier ? kBarrier : kEndBit; }
-
-static inline bool is_multi(const mbpe_ctx *c) { return c->n_ranks > 1 || c->opt_force_exchange; }
-
 static int begin_local(mbpe_ctx *c, uint32_t vocab_size) {
     free_training(c);
     c->vocab_size = vocab_size;
@@ -858,7 +888,6 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size) {
         }
     }
     c->k_upper = 0;
-    c->bp = nullptr;   // the byte-pair table lives at the front of xb0
     HIPCHK(tmalloc(c, &c->d_left, sizeof(RankEdge)));
     HIPCHK(tmalloc(c, &c->d_right, sizeof(RankEdge)));
     HIPCHK(tmalloc(c, &c->ctl, sizeof(DevCtl)));
@@ -893,7 +922,7 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size) {
     c->cur = 0;
     if (c->barrier) {
         launch_widen_barrier(c->stream, c->d_text, n, c->d_endmask, c->tok[0], c->n_slots);
-        launch_summarize(c->stream, c->tok[0], c->sums, c->n_tiles, c->n_cus);
+        launch_summarize(stream_view(c, kLiveFirst));
         const double ms_compact = c->stats.ms_compact;
         rc = do_compact(c);                     // tok[0] -> tok[1]; n_slots / n_tiles are the dense ones from here on
         if (rc != MBPE_OK) return rc;
@@ -904,11 +933,11 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size) {
         HIPCHK(tmalloc(c, &c->tok[0], c->cap_slots * 2));
     } else {
         launch_widen(c->stream, c->d_text, n, c->d_endmask, c->tok[0], c->n_slots);
-        launch_summarize(c->stream, c->tok[0], c->sums, c->n_tiles, c->n_cus);
+        launch_summarize(stream_view(c, kLiveFirst));
     }
     if (is_multi(c)) {
         uint32_t *hdr = c->xb0 + 65536;
-        launch_rank_edge(c->stream, c->sums, c->n_tiles, reinterpret_cast<RankEdge *>(hdr + 2) + c->rank, c->ctl, hdr);
+        launch_rank_edge(stream_view(c, kLiveFirst), hdr);
         const uint64_t p = pairs_scanned(c);
         for (uint32_t i = 0; i < kPairCountWords; ++i) c->h_pcount[i] = (uint32_t)(p >> (16 * i)) & 0xFFFFu;
         HIPCHK(hipMemcpyAsync(hdr + c->hdr_words, c->h_pcount, sizeof(c->h_pcount), hipMemcpyHostToDevice, c->stream));
@@ -932,6 +961,12 @@ static void update_hot_possible(mbpe_ctx *c, unsigned long long top_count, uint6
 // finish of a begin / of a step comes in two parts around it
 static inline bool first_sharded(const mbpe_ctx *c) { return c->opt_first && is_multi(c); }
 
+// The `first` tie-break behind an argmax that wrote *best.  seq 0: the one-merge loop (live buffer first); seq 1: inside a
+// batch sequence (best is the array, buffers 0 / 1).  phase: 0 on one rank; 1 before and 2 after the exchange of c->xf.
+static void first_tiebreak(mbpe_ctx *c, unsigned long long *best, int seq, int phase) {
+    launch_first_tiebreak(stream_view(c, seq ? kBuffers01 : kLiveFirst), c->tab, best, c->first_state, c->xf, seq, phase);
+}
+
 static void begin_finish_a(mbpe_ctx *c) {
     const uint32_t endbit = endbit_of(c);
     // (a pair that occurs 2^32 times or more -- on one GPU, or summed over the ranks by the u32 all-reduce -- leaves a
@@ -947,16 +982,11 @@ static void begin_finish_a(mbpe_ctx *c) {
     }
     launch_table_init(c->stream, c->xb0, c->tab, c->ctl);
     launch_argmax(c->stream, c->tab, c->ctl, c->best, use_hier(c));
-    if (c->opt_first)
-        launch_first_tiebreak(c->stream, c->tab, c->ctl, c->best, c->first_state, c->tok[c->cur], nullptr, c->sums, c->n_tiles,
-                              endbit, c->n_cus, 0, first_sharded(c) ? 1 : 0, first_sharded(c) ? c->d_right : nullptr, c->xf,
-                              c->rank, std::max(1, c->n_ranks));
+    if (c->opt_first) first_tiebreak(c, c->best, 0, first_sharded(c) ? 1 : 0);
 }
 
 static int begin_finish_b(mbpe_ctx *c) {
-    if (first_sharded(c))
-        launch_first_tiebreak(c->stream, c->tab, c->ctl, c->best, c->first_state, c->tok[c->cur], nullptr, c->sums, c->n_tiles,
-                              endbit_of(c), c->n_cus, 0, 2, nullptr, c->xf, c->rank, std::max(1, c->n_ranks));
+    if (first_sharded(c)) first_tiebreak(c, c->best, 0, 2);
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     int rc = sync_ctl(c);
     if (rc != MBPE_OK) return rc;
@@ -984,38 +1014,27 @@ static int begin_finish(mbpe_ctx *c) {
 }
 
 static void step_local(mbpe_ctx *c, int ev_slot) {
-    const uint32_t endbit = endbit_of(c);
-    const uint32_t X = 256 + c->k;
+    const StreamView v = stream_view(c, kLiveFirst);
     const bool multi = is_multi(c);
     if (ev_slot >= 0) (void)hipEventRecord(c->kev[2 * ev_slot], c->stream);
-    launch_merge(c->stream, c->tok[c->cur], c->tok[1 - c->cur], c->sums, c->side, c->n_tiles, c->chg, c->best + c->k, X, endbit, c->LR,
-                 c->ctl, &c->ctl->m, multi ? c->d_left : nullptr, multi ? c->d_right : nullptr, c->n_cus, 0,
-                 c->offsets + c->n_tiles, c->run_in, nullptr);
+    launch_merge(v, batch_view(c), c->best + c->k, 256 + c->k, &c->ctl->m, 0, inst_any(true));
     if (ev_slot >= 0) (void)hipEventRecord(c->kev[2 * ev_slot + 1], c->stream);
     if (multi) {
-        launch_patch_sums(c->stream, c->best + c->k, c->sums, c->side, c->chg, c->n_tiles, c->ctl, 0);
-        launch_rank_edge(c->stream, c->sums, c->n_tiles, reinterpret_cast<RankEdge *>(c->xb + 2) + c->rank, c->ctl,
-                         c->xb);
+        launch_patch_sums(v, c->best + c->k, 0);
+        launch_rank_edge(v, c->xb);
     }
 }
 
 static void step_finish_a(mbpe_ctx *c) {
-    const uint32_t X = 256 + c->k;
     const bool multi = is_multi(c);
-    launch_apply(c->stream, c->tab, c->ctl, c->best + c->k, X, c->LR, multi ? c->xb : nullptr, c->sums, c->side,
-                 c->chg, c->n_tiles, 0);
+    launch_apply(stream_view(c, kLiveFirst), batch_view(c), c->tab, c->best + c->k, 256 + c->k, multi ? c->xb : nullptr, 0);
     if (multi) launch_compose_edges(c->stream, c->xb, c->rank, c->n_ranks, c->d_left, c->d_right);
     launch_argmax(c->stream, c->tab, c->ctl, c->best + c->k + 1, use_hier(c));
-    if (c->opt_first)
-        launch_first_tiebreak(c->stream, c->tab, c->ctl, c->best + c->k + 1, c->first_state, c->tok[c->cur], nullptr, c->sums,
-                              c->n_tiles, endbit_of(c), c->n_cus, 0, first_sharded(c) ? 1 : 0,
-                              first_sharded(c) ? c->d_right : nullptr, c->xf, c->rank, std::max(1, c->n_ranks));
+    if (c->opt_first) first_tiebreak(c, c->best + c->k + 1, 0, first_sharded(c) ? 1 : 0);
 }
 
 static void step_finish_b(mbpe_ctx *c) {
-    if (first_sharded(c))
-        launch_first_tiebreak(c->stream, c->tab, c->ctl, c->best + c->k + 1, c->first_state, c->tok[c->cur], nullptr, c->sums,
-                              c->n_tiles, endbit_of(c), c->n_cus, 0, 2, nullptr, c->xf, c->rank, std::max(1, c->n_ranks));
+    if (first_sharded(c)) first_tiebreak(c, c->best + c->k + 1, 0, 2);
     c->k++;
 }
 
@@ -1073,96 +1092,97 @@ static inline bool use_lockstep(const mbpe_ctx *c) {
     return c->n_slots <= kLockstepSlots;
 }
 
+// what every selection of this training is asked for
+static SelectArgs select_args(const mbpe_ctx *c) {
+    SelectArgs a = {};
+    a.sel = c->opt_threshold_select ? c->sel : nullptr;
+    a.n_target = c->n_target, a.max_batch = std::min<uint32_t>((uint32_t)c->opt_max_batch, c->max_batch_eff);
+    a.fused_min = (uint32_t)c->opt_fused_min, a.sel_cap = (uint32_t)c->opt_sel_cap, a.byte_table = c->opt_byte_table;
+    return a;
+}
+
+// (per-sequence record of k_seq_finish, while the kernels are timed)
+static uint32_t *seq_flags_of(const mbpe_ctx *c) { return c->seq_slot >= 0 ? c->seq_flags + 4 * c->seq_slot : nullptr; }
+
+// grids of the per-batch kernels: sized for the cap while batches are large or unknown, for a few dozen pairs on
+// text, where a sequence merges a handful -- they stride over what the batch really holds either way
+static uint32_t batch_hint(const mbpe_ctx *c) {
+    return c->merges_per_seq > 0 && c->merges_per_seq < 128.0 ? 256u : c->max_batch_eff;
+}
+
+// (lockstep excludes several ranks: the view's edges are null and its n_ranks is 1)
 static int seq_lockstep(mbpe_ctx *c, int ev_slot, bool *nothing_left) {
-    const uint32_t endbit = endbit_of(c);
+    const StreamView v = stream_view(c, kBuffers01);
+    const BatchView b = batch_view(c);
+    const SelectArgs sa = select_args(c);
     *nothing_left = false;
     // The first gather + pick attempt alone; only when it did not choose the batch (a list that overflowed or came back
     // empty, an unprimed threshold: a few times per training) the other two and the bound-walking kernel follow, behind one
     // more wait -- five launches fewer for every other sequence.
-    const uint32_t mb = std::min<uint32_t>((uint32_t)c->opt_max_batch, c->max_batch_eff);
-    const bool stepwise = c->opt_threshold_select != 0;
-    launch_select_batch(c->stream, c->tab, c->ctl, c->bs, c->opt_threshold_select ? c->sel : nullptr, c->best, c->n_target, mb,
-                        (uint32_t)c->opt_fused_min, c->n_cus, 1, endbit, (uint32_t)c->opt_sel_cap, c->opt_byte_table,
-                        stepwise ? 1 : c->sel_attempts, 0, !stepwise);
+    const bool stepwise = sa.sel != nullptr;
+    launch_select_batch(v, b, c->tab, c->best, sa, stepwise ? 1 : c->sel_attempts, 0, !stepwise);
     if (!c->d_seq_info) HIPCHK(hipMalloc(&c->d_seq_info, 32));
     for (int round = 0;; ++round) {
-        launch_seq_info(c->stream, c->ctl, c->bs, c->best, c->d_seq_info);
+        launch_seq_info(v, b, c->best, c->d_seq_info);
         HIPCHK(hipMemcpyAsync(c->h_seq + 8, c->d_seq_info, 32, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipEventRecord(c->ev_sel, c->stream));
         HIPCHK(hipEventSynchronize(c->ev_sel));
         if (!stepwise || round > 0 || c->h_seq[14] != 0) break;
-        launch_select_batch(c->stream, c->tab, c->ctl, c->bs, c->sel, c->best, c->n_target, mb, (uint32_t)c->opt_fused_min,
-                            c->n_cus, 1, endbit, (uint32_t)c->opt_sel_cap, c->opt_byte_table, 3, 1, true);
+        launch_select_batch(v, b, c->tab, c->best, sa, 3, 1, true);
     }
-    const uint32_t batch_n = c->h_seq[9], fused = c->h_seq[10], tt = c->h_seq[11], hot = c->h_seq[12];
+    const uint32_t batch_n = c->h_seq[9], fused = c->h_seq[10];
+    const Inst w = inst_known(c->h_seq[11] != 0, c->h_seq[12] != 0);
     if (ev_slot >= 0) { (void)hipEventRecord(c->kev[2 * ev_slot], c->stream); (void)hipEventRecord(c->kev_f[2 * ev_slot], c->stream); }
     if (batch_n == 0) {                        // the merge limit is reached (or the table is empty): nothing to enqueue
         if (ev_slot >= 0) { (void)hipEventRecord(c->kev_f[2 * ev_slot + 1], c->stream); (void)hipEventRecord(c->kev[2 * ev_slot + 1], c->stream); }
         *nothing_left = true;
         return MBPE_OK;
     }
-    const int only = (int)((tt ? 1u : 0u) | (hot ? 2u : 0u));
     if (batch_n == 1) {
-        launch_merge(c->stream, c->tok[0], c->tok[1], c->sums, c->side, c->n_tiles, c->chg, c->best, 0, endbit, c->LR, c->ctl,
-                     &c->ctl->m, nullptr, nullptr, c->n_cus, 1, c->offsets + c->n_tiles, c->run_in, c->bs, (int)hot, only);
+        launch_merge(v, b, c->best, 0, &c->ctl->m, 1, w);
     } else {
         // (a batch with a (t,t) member: the runs of its token before every tile, which launch_merge computes in the
         //  ordinary enqueue-everything flow)
-        if (tt) launch_run_lengths(c->stream, c->sums, c->n_tiles, c->best, c->ctl, 1, c->bs, c->offsets + c->n_tiles, nullptr, c->run_in);
+        if (w.tt) launch_run_lengths(v, b.bs, c->best, 1);
+        if (fused) launch_fused_batch(v, b, w);
+        else launch_scan_batch(v, b, w);
+        launch_pair_cells_fold(v, b, batch_n);
     }
-    if (batch_n == 1) {
-    } else if (fused) {
-        launch_fused_batch(c->stream, c->tok[0], c->tok[1], c->sums, c->side, c->n_tiles, c->chg, c->bs, c->hdr_adj, c->LR,
-                           c->ctl, nullptr, nullptr, endbit, c->n_cus, c->hdr_m, c->run_in, (int)hot, only, c->pair_cells);
-    } else {
-        launch_scan_batch(c->stream, c->tok[0], c->tok[1], c->sums, c->n_tiles, c->chg, c->bs, c->hdr_m, c->hdr_adj, c->LR,
-                          c->ctl, nullptr, nullptr, endbit, c->n_cus, c->run_in, (int)hot, only, c->pair_cells);
-    }
-    if (batch_n >= 2) launch_pair_cells_fold(c->stream, c->pair_cells, c->LR, c->ctl, batch_n);
     if (ev_slot >= 0) { (void)hipEventRecord(c->kev_f[2 * ev_slot + 1], c->stream); (void)hipEventRecord(c->kev[2 * ev_slot + 1], c->stream); }
     c->k_upper = std::min<uint32_t>(c->n_target, c->h_seq[8] + batch_n);
     const uint32_t id_upper = 256 + c->k_upper;
     if (batch_n == 1) {
-        launch_apply(c->stream, c->tab, c->ctl, c->best, id_upper, c->LR, nullptr, c->sums, c->side, c->chg, c->n_tiles, 1);
+        launch_apply(v, b, c->tab, c->best, id_upper, nullptr, 1);
     } else {
-        launch_batch_tables(c->stream, c->tab, c->ctl, c->bs, c->hdr_m, c->hdr_adj, c->LR, id_upper, batch_n);
-        launch_rewrite_marked(c->stream, c->tok[0], c->tok[1], c->sums, c->side, c->n_tiles, c->chg, c->tile_list, c->bs, c->ctl,
-                              nullptr, nullptr, endbit, c->n_cus, c->run_in, (int)(tt ? 1u : 0u));
-        launch_patch_sums(c->stream, c->best, c->sums, c->side, c->chg, c->n_tiles, c->ctl, 1);
+        launch_batch_tables(v, b, c->tab, id_upper, batch_n);
+        launch_rewrite_marked(v, b, w);
+        launch_patch_sums(v, c->best, 1);
     }
-    launch_seq_finish(c->stream, c->ctl, c->seq_slot >= 0 ? c->seq_flags + 4 * c->seq_slot : nullptr, c->bs);
+    launch_seq_finish(v, b, seq_flags_of(c));
     return MBPE_OK;
 }
 
 static int seq_stage_a(mbpe_ctx *c, int ev_slot) {       // up to the delta exchange
-    const uint32_t endbit = endbit_of(c);
-    const bool multi = is_multi(c);
-    const RankEdge *le = multi ? c->d_left : nullptr, *re = multi ? c->d_right : nullptr;
-    launch_select_batch(c->stream, c->tab, c->ctl, c->bs, c->opt_threshold_select ? c->sel : nullptr, c->best,
-                        c->n_target, std::min<uint32_t>((uint32_t)c->opt_max_batch, c->max_batch_eff), (uint32_t)c->opt_fused_min, c->n_cus,
-                        std::max(1, c->n_ranks), endbit, (uint32_t)c->opt_sel_cap, c->opt_byte_table, c->sel_attempts);
-    if (c->opt_first)
-        launch_first_tiebreak(c->stream, c->tab, c->ctl, c->best, c->first_state, c->tok[0], c->tok[1], c->sums, c->n_tiles,
-                              endbit, c->n_cus, 1);
-    if (multi) {
+    const StreamView v = stream_view(c, kBuffers01);
+    const BatchView b = batch_view(c);
+    const Inst w = inst_any(c->hot_possible != 0);
+    launch_select_batch(v, b, c->tab, c->best, select_args(c), c->sel_attempts);
+    if (c->opt_first) first_tiebreak(c, c->best, 1, 0);
+    if (is_multi(c)) {
         // (a failed copy or event would leave the PREVIOUS sequence's sizes in h_seq: this rank would then exchange a
         //  length its peers do not -- fail the call instead)
         const int rc = seq_info_enqueue(c);
         if (rc != MBPE_OK) return rc;
     }
     if (ev_slot >= 0) (void)hipEventRecord(c->kev[2 * ev_slot], c->stream);
-    // (the live token buffer is ctl->cur: a fused pass flips it without the host knowing)
-    launch_merge(c->stream, c->tok[0], c->tok[1], c->sums, c->side, c->n_tiles, c->chg, c->best, 0, endbit, c->LR, c->ctl,
-                 multi ? c->xb : &c->ctl->m, le, re, c->n_cus, 1, c->offsets + c->n_tiles, c->run_in, c->bs, c->hot_possible);
-    launch_scan_batch(c->stream, c->tok[0], c->tok[1], c->sums, c->n_tiles, c->chg, c->bs, c->hdr_m, c->hdr_adj, c->LR,
-                      c->ctl, le, re, endbit, c->n_cus, c->run_in, c->hot_possible, -1, c->pair_cells);
+    // (the [m, adj] of a single pair: with several ranks in the exchange header, which is summed over them)
+    launch_merge(v, b, c->best, 0, is_multi(c) ? c->xb : &c->ctl->m, 1, w);
+    launch_scan_batch(v, b, w);
     if (ev_slot >= 0) (void)hipEventRecord(c->kev_f[2 * ev_slot], c->stream);
-    launch_fused_batch(c->stream, c->tok[0], c->tok[1], c->sums, c->side, c->n_tiles, c->chg, c->bs, c->hdr_adj, c->LR,
-                       c->ctl, le, re, endbit, c->n_cus, c->hdr_m, c->run_in, c->hot_possible, -1, c->pair_cells);
+    launch_fused_batch(v, b, w);
     // (the cell blocks become L / R rows before anything reads the rows: the exchange of several ranks, validation, apply.
     //  Inside the events: the fold is part of what the pass costs)
-    launch_pair_cells_fold(c->stream, c->pair_cells, c->LR, c->ctl,
-                           c->merges_per_seq > 0 && c->merges_per_seq < 128.0 ? 256u : c->max_batch_eff);
+    launch_pair_cells_fold(v, b, batch_hint(c));
     if (ev_slot >= 0) {
         (void)hipEventRecord(c->kev_f[2 * ev_slot + 1], c->stream);
         (void)hipEventRecord(c->kev[2 * ev_slot + 1], c->stream);
@@ -1171,24 +1191,16 @@ static int seq_stage_a(mbpe_ctx *c, int ev_slot) {       // up to the delta exch
 }
 
 static void seq_stage_b(mbpe_ctx *c) {                   // up to the edge exchange
-    const uint32_t endbit = endbit_of(c);
-    const bool multi = is_multi(c);
-    const RankEdge *le = multi ? c->d_left : nullptr, *re = multi ? c->d_right : nullptr;
+    const StreamView v = stream_view(c, kBuffers01);
+    const BatchView b = batch_view(c);
     c->k_upper = std::min<uint32_t>(c->n_target, c->k_upper + std::min<uint32_t>((uint32_t)c->opt_max_batch, c->max_batch_eff));
     const uint32_t id_upper = 256 + c->k_upper;
-    // (grids of the per-batch kernels: sized for the cap while batches are large or unknown, for a few dozen pairs on
-    //  text, where a sequence merges a handful -- they stride over what the batch really holds either way)
-    const uint32_t n_hint = c->merges_per_seq > 0 && c->merges_per_seq < 128.0 ? 256u : c->max_batch_eff;
-    launch_batch_tables(c->stream, c->tab, c->ctl, c->bs, c->hdr_m, c->hdr_adj, c->LR, id_upper, n_hint);
-    launch_apply(c->stream, c->tab, c->ctl, c->best, id_upper, c->LR, multi ? c->xb : nullptr, c->sums, c->side,
-                 c->chg, c->n_tiles, 1);
-    launch_rewrite_marked(c->stream, c->tok[0], c->tok[1], c->sums, c->side, c->n_tiles, c->chg, c->tile_list, c->bs, c->ctl, le, re,
-                          endbit, c->n_cus, c->run_in);
-    launch_patch_sums(c->stream, c->best, c->sums, c->side, c->chg, c->n_tiles, c->ctl, 1);
-    launch_seq_finish(c->stream, c->ctl, c->seq_slot >= 0 ? c->seq_flags + 4 * c->seq_slot : nullptr, c->bs);
-    if (multi)
-        launch_rank_edge(c->stream, c->sums, c->n_tiles, reinterpret_cast<RankEdge *>(c->xb + 2) + c->rank, c->ctl,
-                         c->xb);
+    launch_batch_tables(v, b, c->tab, id_upper, batch_hint(c));
+    launch_apply(v, b, c->tab, c->best, id_upper, is_multi(c) ? c->xb : nullptr, 1);
+    launch_rewrite_marked(v, b, inst_any(c->hot_possible != 0));      // (both instantiations: the host does not know the batch)
+    launch_patch_sums(v, c->best, 1);
+    launch_seq_finish(v, b, seq_flags_of(c));
+    if (is_multi(c)) launch_rank_edge(v, c->xb);
 }
 
 static void seq_stage_c(mbpe_ctx *c) {                   // after the edge exchange
@@ -1283,16 +1295,9 @@ static int train_steps_batched(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_do
             if (rc != MBPE_OK) return rc;
         }
         if (c->opt_time_kernels) {
-            while (c->kev.size() < 2ull * group) {
-                hipEvent_t e;
-                HIPCHK(hipEventCreate(&e));
-                c->kev.push_back(e);
-            }
-            while (c->kev_f.size() < 2ull * group) {
-                hipEvent_t e;
-                HIPCHK(hipEventCreate(&e));
-                c->kev_f.push_back(e);
-            }
+            int rc = ensure_events(c->kev, 2ull * group);
+            if (rc == MBPE_OK) rc = ensure_events(c->kev_f, 2ull * group);
+            if (rc != MBPE_OK) return rc;
         }
         c->k_upper = c->k;
         // (for THIS group: the "batch" / "max_batch" options may have changed since the bound was last computed)
@@ -1407,8 +1412,7 @@ static int train_steps_batched(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_do
                 c->first_legacy = true;
                 HIPCHK(hipMemsetAsync(c->best + c->k, 0, 8, c->stream));
                 launch_argmax(c->stream, c->tab, c->ctl, c->best + c->k, use_hier(c));
-                launch_first_tiebreak(c->stream, c->tab, c->ctl, c->best + c->k, c->first_state, c->tok[c->cur], nullptr,
-                                      c->sums, c->n_tiles, endbit_of(c), c->n_cus, 0);
+                first_tiebreak(c, c->best + c->k, 0, 0);
                 HIPCHK(hipStreamSynchronize(c->stream));
                 break;
             }
@@ -1502,11 +1506,8 @@ static int train_steps16(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_done_out
         int rc = before_batch(c, batch);   // pair-table headroom (h_ctl.n_entries is exact here)
         if (rc != MBPE_OK) return rc;
         if (c->opt_time_kernels) {
-            while (c->kev.size() < 2ull * batch) {
-                hipEvent_t e;
-                HIPCHK(hipEventCreate(&e));
-                c->kev.push_back(e);
-            }
+            rc = ensure_events(c->kev, 2ull * batch);
+            if (rc != MBPE_OK) return rc;
         }
         HIPCHK(hipEventRecord(c->ev0, c->stream));
         for (uint32_t i = 0; i < batch; ++i) {
