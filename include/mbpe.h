@@ -447,6 +447,32 @@ MBPE_API int  mbpe_decode_tokens(mbpe_decoder *d, const uint32_t *tokens, uint64
                                  uint8_t *bytes_out, uint64_t cap, int out_on_device,
                                  uint64_t *n_out, uint64_t *n_invalid_out);
 
+/* The same for a batch of n_docs documents, a document being any run of consecutive tokens (a text of an encoded
+ * batch, a chunk, a line), with the byte offset of every document boundary: ONE device call instead of one per
+ * document.
+ *   tokens            n_tokens ids of token_bits bits, host or device memory (tokens_on_device).  token_bits 32:
+ *                     uint32_t ids, read as mbpe_decode_tokens reads them.  token_bits 16: plain uint16_t ids with no
+ *                     flag and no hole value, as mbpe_encoder_encode writes them with token_bits 16 -- id 65,535 is a
+ *                     token like any other (in the 16-bit layouts of mbpe_decode_slots 0xFFFF stays a hole).  Any
+ *                     other token_bits is MBPE_ERR_ARG.
+ *   doc_tok_off       host, n_docs + 1 ascending offsets with [0] == 0 and [n_docs] == n_tokens: document i is tokens
+ *                     [doc_tok_off[i], doc_tok_off[i + 1]), equal neighbours are an empty document.  The convention of
+ *                     chunk_off (mbpe_load_corpus) and of chunk_tok_off_out (mbpe_encoder_encode), whose arrays can be
+ *                     passed as they are.  Anything else is MBPE_ERR_ARG before the device is touched; n_docs == 0
+ *                     goes with n_tokens == 0 only.
+ *   bytes_out, cap, out_on_device, n_out, n_invalid_out   as for mbpe_decode_tokens: the documents' texts one after
+ *                     the other, the bytes mbpe_decode_tokens gives for the same tokens
+ *   doc_byte_off_out  required; host, n_docs + 1 entries: [b] = the bytes that tokens [0, doc_tok_off[b]) decode to.
+ *                     [0] == 0, [n_docs] == *n_out, document i's text is bytes_out[doc_byte_off_out[i] ..
+ *                     doc_byte_off_out[i + 1]).  Filled whenever the lengths were computed: also by a query and when
+ *                     cap is too small, so that buffers can be sized from them.
+ * The limits are those of mbpe_decode_tokens.  The decoder keeps the device copies of both offset arrays between
+ * calls like its other scratch: a repeat call of no larger size allocates nothing. */
+MBPE_API int  mbpe_decode_batch(mbpe_decoder *d, const void *tokens, uint64_t n_tokens, uint32_t token_bits,
+                                int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs,
+                                uint8_t *bytes_out, uint64_t cap, int out_on_device,
+                                uint64_t *doc_byte_off_out, uint64_t *n_out, uint64_t *n_invalid_out);
+
 /* The same for n_slots device-resident slots in one of the layouts mbpe_stream_device describes (slot_bits 16 or
  * 32, its end_bit and barrier values; an all-ones slot and a barrier slot yield nothing and are not invalid), and
  * for the 32-bit tokens with bit 31 = chunk end that mbpe_encode_chunks_device leaves on the device. */
@@ -455,8 +481,12 @@ MBPE_API int  mbpe_decode_slots(mbpe_decoder *d, const void *slots, uint64_t n_s
                                 int out_on_device, uint64_t *n_out, uint64_t *n_invalid_out);
 
 /* Device time of the decoder's latest call in milliseconds (HIP events on its stream around the length kernel, the
- * scan and the copy kernel; host <-> device copies are outside). */
+ * scan, a batch's boundary-offset kernel and the copy kernel; host <-> device copies are outside). */
 MBPE_API int  mbpe_decoder_kernel_ms(const mbpe_decoder *d, float *ms_out);
+
+/* Device allocations (hipMalloc calls) the decoder has made since it was created, its tables included.  A call of
+ * no larger size than an earlier one (tokens, documents, output) leaves the number as it is. */
+MBPE_API int  mbpe_decoder_alloc_count(const mbpe_decoder *d, uint64_t *n_out);
 
 /* The live stream of a training context, expanded with that training's own merges so far (after
  * mbpe_train_begin; any slot layout, and the 32-bit continuation): decode(stream) == the corpus the context

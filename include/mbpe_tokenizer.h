@@ -75,6 +75,18 @@ MBPE_API int mbpe_tok_decode(mbpe_tokenizer *t, const uint32_t *tokens, uint64_t
 MBPE_API int mbpe_tok_decode_device(mbpe_tokenizer *t, const uint32_t *tokens, uint64_t n, int verbose, int device_id,
                                     uint8_t *bytes_out, uint64_t cap, uint64_t *n_out);
 
+/* decode of n_docs documents in one device call (mbpe_decode_batch, with the same kept decoder).  Document i is
+ * tokens[doc_tok_off[i] .. doc_tok_off[i + 1]): n_docs + 1 ascending offsets from 0, host memory, as
+ * mbpe_tok_encode_batch_device's doc_tok_off_out; the token count is doc_tok_off[n_docs].  bytes_out (NULL: query)
+ * receives the documents' texts one after the other, doc_byte_off_out (required, n_docs + 1; also on a query and
+ * when cap is too small) where each begins: document i is bytes_out[doc_byte_off_out[i] .. doc_byte_off_out[i + 1])
+ * and equals mbpe_tok_decode of that document's tokens.  Every id that decodes to nothing gets the reference's
+ * warning line, in stream order.  The offsets are checked before a decoder is created: a bad array is MBPE_ERR_ARG
+ * also where there is no device.  n_out is required; device_id must not be negative. */
+MBPE_API int mbpe_tok_decode_batch_device(mbpe_tokenizer *t, const uint32_t *tokens, const uint64_t *doc_tok_off,
+                                          uint64_t n_docs, int verbose, int device_id, uint8_t *bytes_out,
+                                          uint64_t cap, uint64_t *doc_byte_off_out, uint64_t *n_out);
+
 #ifdef __cplusplus
 }
 #endif

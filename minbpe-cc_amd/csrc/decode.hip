@@ -19,10 +19,16 @@
 //                    gathers from the blob and stores one dwordx4.  Only the first and the last piece of a span, which
 //                    it shares with its neighbours, are written byte by byte.  A token of any length costs what its
 //                    bytes cost.
+//   k_dec_bounds<F>  batches only (mbpe_decode_batch): the byte offset of every document boundary.  Span-centric like
+//                    the rest: the wave of span s owns the boundaries t with t / 1,024 == s (two binary searches in
+//                    the sorted token offsets find them), builds the span's prefix sums as k_dec_write does and
+//                    stores span_off[s] + prefix[t - base] for each, lanes striding over the boundaries.  A span
+//                    without a boundary reads no token.
 // F is how a token is read (DecFmt): all of them yield "id or nothing".
 //
 // Bytes moved per decode: the tokens twice (4 B or 2 B each), the output once; len / off / blob are gathered from
-// cache (a few hundred KB to a few MB for text vocabularies).
+// cache (a few hundred KB to a few MB for text vocabularies).  A batch adds the tokens of the spans that hold a
+// boundary once more, and 16 B per boundary (its token offset in, its byte offset out).
 #include "hip_host.h"
 #include "span.h"
 
@@ -47,7 +53,8 @@ enum DecFmt {
     kFmtU32End = 1,     // the layout of span.h: bit 31 = last token of its chunk, all-ones = hole
     kFmtU16 = 2,        // 16-bit slots, all-ones = hole
     kFmtU16End = 3,     // ... bit 15 = last token of its chunk
-    kFmtU16Barrier = 4  // ... one slot value is the barrier after a chunk, no token
+    kFmtU16Barrier = 4, // ... one slot value is the barrier after a chunk, no token
+    kFmtU16Plain = 5    // plain uint16_t ids as mbpe_encoder_encode writes them: no flag, no hole, 0xFFFF is an id
 };
 
 struct DecTab {
@@ -74,6 +81,7 @@ __device__ __forceinline__ bool dec_read(const void *__restrict__ tok, uint64_t 
         return true;
     }
     const uint32_t s = static_cast<const uint16_t *>(tok)[i];
+    if (F == kFmtU16Plain) { *id = s; return true; }
     if (s == 0xFFFFu) return false;
     if (F == kFmtU16Barrier && s == barrier) return false;
     *id = F == kFmtU16End ? (s & 0x7FFFu) : s;
@@ -167,38 +175,44 @@ __device__ __forceinline__ unsigned __int128 load16(const uint8_t *p) {
     return v;
 }
 
+// One wave, the span that starts at token `base`: s_off[j] = bytes of the span before its token j (s_off[kSpan] = the
+// span's total, below 2^32: MBPE_DECODER_MAX_ENTRY) and, with kSrc, s_src[j] = where token j's bytes start in the
+// blob (below 2^32: MBPE_DECODER_MAX_BLOB).  Tokens at or beyond n count as nothing.
+template <int F, bool kSrc>
+__device__ __forceinline__ void dec_span_prefix(const void *__restrict__ tok, uint64_t n, uint32_t barrier,
+                                                const DecTab &tab, uint64_t base, uint32_t lane, uint32_t *s_off,
+                                                uint32_t *s_src) {
+    uint32_t run = 0;
+    for (int it = 0; it < kSpanIters; ++it) {
+        const uint64_t i = base + (uint64_t)it * kWave + lane;
+        uint32_t id, ent, l = 0, src = 0;
+        if (i < n && dec_read<F>(tok, i, barrier, &id) && dec_entry(tab, id, &ent)) {
+            l = tab.len[ent];
+            if (kSrc) src = (uint32_t)tab.off[ent];
+        }
+        uint32_t incl = l;
+        for (int d = 1; d < kWave; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d, kWave);
+            if (lane >= (uint32_t)d) incl += up;
+        }
+        s_off[it * kWave + lane] = run + incl - l;
+        if (kSrc) s_src[it * kWave + lane] = src;
+        run += __shfl(incl, kWave - 1, kWave);
+    }
+    if (lane == 0) s_off[kSpan] = run;
+}
+
 template <int F>
 __global__ __launch_bounds__(kSpanThreads) void k_dec_write(const void *__restrict__ tok, uint64_t n, uint32_t barrier,
                                                             DecTab tab, const unsigned long long *__restrict__ span_off,
                                                             uint8_t *__restrict__ out) {
-    // per wave: s_off[j] = bytes of the span before its token j (s_off[kSpan] = the span's total, below 2^32:
-    // MBPE_DECODER_MAX_ENTRY), s_src[j] = where token j's bytes start in the blob (below 2^32: MBPE_DECODER_MAX_BLOB)
     __shared__ uint32_t s_off[kSpanWaves][kSpan + 1];
     __shared__ uint32_t s_src[kSpanWaves][kSpan];
     const uint32_t w = threadIdx.x / kWave, lane = lane_id();
     const uint64_t span = span_index();
     const uint64_t base = span * kSpan;
     const bool active = base < n;
-    if (active) {
-        uint32_t run = 0;
-        for (int it = 0; it < kSpanIters; ++it) {
-            const uint64_t i = base + (uint64_t)it * kWave + lane;
-            uint32_t id, ent, l = 0, src = 0;
-            if (i < n && dec_read<F>(tok, i, barrier, &id) && dec_entry(tab, id, &ent)) {
-                l = tab.len[ent];
-                src = (uint32_t)tab.off[ent];
-            }
-            uint32_t incl = l;
-            for (int d = 1; d < kWave; d <<= 1) {
-                const uint32_t up = __shfl_up(incl, d, kWave);
-                if (lane >= (uint32_t)d) incl += up;
-            }
-            s_off[w][it * kWave + lane] = run + incl - l;
-            s_src[w][it * kWave + lane] = src;
-            run += __shfl(incl, kWave - 1, kWave);
-        }
-        if (lane == 0) s_off[w][kSpan] = run;
-    }
+    if (active) dec_span_prefix<F, true>(tok, n, barrier, tab, base, lane, s_off[w], s_src[w]);
     __syncthreads();
     if (!active) return;
     const uint32_t T = s_off[w][kSpan];
@@ -244,6 +258,44 @@ __global__ __launch_bounds__(kSpanThreads) void k_dec_write(const void *__restri
     }
 }
 
+// the first index b of the ascending v[0 .. n_v) with v[b] >= x (n_v when there is none)
+__device__ __forceinline__ uint64_t dec_lower_bound(const unsigned long long *__restrict__ v, uint64_t n_v, uint64_t x) {
+    uint64_t lo = 0, hi = n_v;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (v[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// doc_byte_off[b] <- the bytes that tokens [0, doc_tok_off[b]) decode to, for the n_b ascending boundaries
+// doc_tok_off[b] <= n.  The wave of span s owns the boundaries in [s * kSpan, (s + 1) * kSpan); the last span's also
+// owns those at n itself, which lie in a span that no wave walks when n is a multiple of kSpan (n - base <= kSpan:
+// they read s_off[kSpan], the span's total).  span_off as for k_dec_write.
+template <int F>
+__global__ __launch_bounds__(kSpanThreads) void k_dec_bounds(const void *__restrict__ tok, uint64_t n, uint32_t barrier,
+                                                             DecTab tab, const unsigned long long *__restrict__ span_off,
+                                                             const unsigned long long *__restrict__ doc_tok_off,
+                                                             uint64_t n_b, unsigned long long *__restrict__ doc_byte_off) {
+    __shared__ uint32_t s_off[kSpanWaves][kSpan + 1];
+    const uint32_t w = threadIdx.x / kWave, lane = lane_id();
+    const uint64_t span = span_index();
+    const uint64_t base = span * kSpan;
+    uint64_t lo = 0, hi = 0;
+    if (base < n) {
+        const uint64_t end = base + kSpan >= n ? n + 1 : base + kSpan;
+        lo = dec_lower_bound(doc_tok_off, n_b, base);
+        hi = lo + dec_lower_bound(doc_tok_off + lo, n_b - lo, end);
+    }
+    const bool active = lo < hi;                     // a span without a boundary reads no token
+    if (active) dec_span_prefix<F, false>(tok, n, barrier, tab, base, lane, s_off[w], nullptr);
+    __syncthreads();
+    if (!active) return;
+    const unsigned long long o = span_off[span];
+    for (uint64_t b = lo + lane; b < hi; b += kWave) doc_byte_off[b] = o + s_off[w][doc_tok_off[b] - base];
+}
+
 #define DCHK(expr) MBPE_HIP_CHECK(expr, false)
 
 int fail(int code, const char *msg) {
@@ -271,6 +323,10 @@ struct mbpe_decoder {
     uint64_t cap_tok = 0;
     uint8_t *d_out = nullptr;                 // staging for output that goes to the host
     uint64_t cap_out = 0;
+    unsigned long long *d_doc_tok = nullptr;  // a batch's document boundaries: token offsets in,
+    unsigned long long *d_doc_byte = nullptr; // byte offsets out
+    uint64_t cap_doc_tok = 0, cap_doc_byte = 0;
+    uint64_t n_allocs = 0;                    // hipMalloc calls so far (mbpe_decoder_alloc_count)
 };
 
 namespace {
@@ -286,13 +342,33 @@ void launch_write(mbpe_decoder *d, const void *tok, uint64_t n, uint32_t barrier
                        out);
 }
 
-// lengths + scan of n device-resident tokens; ev0 is recorded in front
-int dec_measure(mbpe_decoder *d, int fmt, const void *tok, uint64_t n, uint32_t barrier, uint64_t *total,
-                uint64_t *invalid) {
+template <int F>
+void launch_bounds(mbpe_decoder *d, const void *tok, uint64_t n, uint32_t barrier, uint32_t grid, uint64_t n_b) {
+    hipLaunchKernelGGL(k_dec_bounds<F>, dim3(grid), dim3(kSpanThreads), 0, d->stream, tok, n, barrier, d->tab, d->d_span,
+                       d->d_doc_tok, n_b, d->d_doc_byte);
+}
+
+// the documents of a batch: n_b = n_docs + 1 boundaries, checked by mbpe_decode_batch; both arrays are host memory
+struct DecDocs {
+    const uint64_t *tok_off;
+    uint64_t n_b;
+    uint64_t *byte_off_out;
+};
+
+// lengths + scan of n device-resident tokens and, for a batch, its boundaries' byte offsets (left on the device:
+// dec_write fetches them); ev0 is recorded in front
+int dec_measure(mbpe_decoder *d, int fmt, const void *tok, uint64_t n, uint32_t barrier, const DecDocs *docs,
+                uint64_t *total, uint64_t *invalid) {
     const uint64_t n_spans = span_count(n);
     const uint32_t grid = span_grid(n);
-    int rc = grow(&d->d_span, &d->cap_spans, (n_spans + 1) * 8, false, nullptr);
+    int rc = grow(&d->d_span, &d->cap_spans, (n_spans + 1) * 8, false, &d->n_allocs);
     if (rc != MBPE_OK) return rc;
+    if (docs && n) {
+        rc = grow(&d->d_doc_tok, &d->cap_doc_tok, docs->n_b * 8, false, &d->n_allocs);
+        if (rc == MBPE_OK) rc = grow(&d->d_doc_byte, &d->cap_doc_byte, docs->n_b * 8, false, &d->n_allocs);
+        if (rc != MBPE_OK) return rc;
+        DCHK(hipMemcpyAsync(d->d_doc_tok, docs->tok_off, docs->n_b * 8, hipMemcpyHostToDevice, d->stream));
+    }
     DCHK(hipMemsetAsync(d->d_res, 0, 16, d->stream));
     DCHK(hipEventRecord(d->ev0, d->stream));
     if (n) {
@@ -301,9 +377,15 @@ int dec_measure(mbpe_decoder *d, int fmt, const void *tok, uint64_t n, uint32_t 
             case kFmtU32End: launch_len<kFmtU32End>(d, tok, n, barrier, grid); break;
             case kFmtU16: launch_len<kFmtU16>(d, tok, n, barrier, grid); break;
             case kFmtU16End: launch_len<kFmtU16End>(d, tok, n, barrier, grid); break;
-            default: launch_len<kFmtU16Barrier>(d, tok, n, barrier, grid); break;
+            case kFmtU16Barrier: launch_len<kFmtU16Barrier>(d, tok, n, barrier, grid); break;
+            default: launch_len<kFmtU16Plain>(d, tok, n, barrier, grid); break;
         }
         hipLaunchKernelGGL(k_dec_scan64, dim3(1), dim3(kScanThreads), 0, d->stream, d->d_span, n_spans, d->d_res);
+        if (docs) {
+            // (a batch arrives as plain ids only: mbpe_decode_batch)
+            if (fmt == kFmtU32) launch_bounds<kFmtU32>(d, tok, n, barrier, grid, docs->n_b);
+            else launch_bounds<kFmtU16Plain>(d, tok, n, barrier, grid, docs->n_b);
+        }
     }
     unsigned long long res[2] = {0, 0};
     DCHK(hipMemcpyAsync(res, d->d_res, 16, hipMemcpyDeviceToHost, d->stream));
@@ -314,8 +396,9 @@ int dec_measure(mbpe_decoder *d, int fmt, const void *tok, uint64_t n, uint32_t 
     return MBPE_OK;
 }
 
-// the copy, after dec_measure of the same tokens; records ev1 and waits
-int dec_write(mbpe_decoder *d, int fmt, const void *tok, uint64_t n, uint32_t barrier, uint8_t *out_dev, bool wrote) {
+// the copy, after dec_measure of the same tokens; records ev1, fetches a batch's byte offsets and waits
+int dec_write(mbpe_decoder *d, int fmt, const void *tok, uint64_t n, uint32_t barrier, const DecDocs *docs,
+              uint8_t *out_dev, bool wrote) {
     if (wrote && n) {
         const uint32_t grid = span_grid(n);
         switch (fmt) {
@@ -323,19 +406,25 @@ int dec_write(mbpe_decoder *d, int fmt, const void *tok, uint64_t n, uint32_t ba
             case kFmtU32End: launch_write<kFmtU32End>(d, tok, n, barrier, grid, out_dev); break;
             case kFmtU16: launch_write<kFmtU16>(d, tok, n, barrier, grid, out_dev); break;
             case kFmtU16End: launch_write<kFmtU16End>(d, tok, n, barrier, grid, out_dev); break;
-            default: launch_write<kFmtU16Barrier>(d, tok, n, barrier, grid, out_dev); break;
+            case kFmtU16Barrier: launch_write<kFmtU16Barrier>(d, tok, n, barrier, grid, out_dev); break;
+            default: launch_write<kFmtU16Plain>(d, tok, n, barrier, grid, out_dev); break;
         }
     }
     DCHK(hipEventRecord(d->ev1, d->stream));
+    if (docs) {
+        if (n) DCHK(hipMemcpyAsync(docs->byte_off_out, d->d_doc_byte, docs->n_b * 8, hipMemcpyDeviceToHost, d->stream));
+        else memset(docs->byte_off_out, 0, docs->n_b * 8);      // no tokens: no kernel ran, every document is empty
+    }
     DCHK(hipStreamSynchronize(d->stream));
     DCHK(hipGetLastError());
     DCHK(hipEventElapsedTime(&d->last_ms, d->ev0, d->ev1));
     return MBPE_OK;
 }
 
-// tokens / slots in any layout -> bytes; the common body of the three entry points
+// tokens / slots in any layout -> bytes; the common body of the entry points (docs: a batch, or NULL)
 int dec_run(mbpe_decoder *d, int fmt, const void *tokens, uint64_t n, int tokens_on_device, uint32_t barrier,
-            uint8_t *bytes_out, uint64_t cap, int out_on_device, uint64_t *n_out, uint64_t *n_invalid_out) {
+            const DecDocs *docs, uint8_t *bytes_out, uint64_t cap, int out_on_device, uint64_t *n_out,
+            uint64_t *n_invalid_out) {
     *n_out = 0;
     if (n_invalid_out) *n_invalid_out = 0;
     if (n >> 40) return fail(MBPE_ERR_ARG, "more than 2^40 tokens");
@@ -343,27 +432,27 @@ int dec_run(mbpe_decoder *d, int fmt, const void *tokens, uint64_t n, int tokens
     const uint64_t tok_bytes = n * (fmt <= kFmtU32End ? 4 : 2);
     const void *tok = tokens;
     if (!tokens_on_device && n) {
-        int rc = grow(&d->d_tok, &d->cap_tok, tok_bytes, false, nullptr);
+        int rc = grow(&d->d_tok, &d->cap_tok, tok_bytes, false, &d->n_allocs);
         if (rc != MBPE_OK) return rc;
         DCHK(hipMemcpyAsync(d->d_tok, tokens, tok_bytes, hipMemcpyHostToDevice, d->stream));
         tok = d->d_tok;
     }
     uint64_t total = 0, invalid = 0;
-    int rc = dec_measure(d, fmt, tok, n, barrier, &total, &invalid);
+    int rc = dec_measure(d, fmt, tok, n, barrier, docs, &total, &invalid);
     if (rc != MBPE_OK) return rc;
     *n_out = total;
     if (n_invalid_out) *n_invalid_out = invalid;
-    if (!bytes_out) return dec_write(d, fmt, tok, n, barrier, nullptr, false);       // the size query
+    if (!bytes_out) return dec_write(d, fmt, tok, n, barrier, docs, nullptr, false);       // the size query
     if (cap < total) {
-        (void)dec_write(d, fmt, tok, n, barrier, nullptr, false);
-        return fail(MBPE_ERR_ARG, "bytes_out too small");
+        rc = dec_write(d, fmt, tok, n, barrier, docs, nullptr, false);
+        return rc != MBPE_OK ? rc : fail(MBPE_ERR_ARG, "bytes_out too small");
     }
-    if (out_on_device) return dec_write(d, fmt, tok, n, barrier, bytes_out, true);
+    if (out_on_device) return dec_write(d, fmt, tok, n, barrier, docs, bytes_out, true);
     if (total) {
-        rc = grow(&d->d_out, &d->cap_out, total, false, nullptr);
+        rc = grow(&d->d_out, &d->cap_out, total, false, &d->n_allocs);
         if (rc != MBPE_OK) return rc;
     }
-    rc = dec_write(d, fmt, tok, n, barrier, d->d_out, total != 0);
+    rc = dec_write(d, fmt, tok, n, barrier, docs, d->d_out, total != 0);
     if (rc != MBPE_OK) return rc;
     if (total) {
         DCHK(hipMemcpyAsync(bytes_out, d->d_out, total, hipMemcpyDeviceToHost, d->stream));
@@ -392,24 +481,32 @@ int slot_format(uint32_t slot_bits, uint32_t end_bit, uint32_t barrier, int *fmt
 
 namespace mbpe_host {
 
+int check_doc_tok_off(const uint64_t *doc_tok_off, uint64_t n_docs, uint64_t n_tokens) {
+    if (doc_tok_off[0] != 0) return fail(MBPE_ERR_ARG, "doc_tok_off must begin at 0");
+    for (uint64_t i = 0; i < n_docs; ++i)
+        if (doc_tok_off[i + 1] < doc_tok_off[i]) return fail(MBPE_ERR_ARG, "doc_tok_off must be ascending");
+    if (doc_tok_off[n_docs] != n_tokens) return fail(MBPE_ERR_ARG, "doc_tok_off must end at n_tokens");
+    return MBPE_OK;
+}
+
 int decode_to_string(mbpe_decoder *d, const uint32_t *tokens, uint64_t n, std::string *out, uint64_t *n_invalid) {
     out->clear();
     *n_invalid = 0;
     if (!d || (!tokens && n)) return fail(MBPE_ERR_ARG, "decode_to_string: NULL argument");
     DCHK(hipSetDevice(d->device));
     if (n) {
-        int rc = grow(&d->d_tok, &d->cap_tok, n * 4, false, nullptr);
+        int rc = grow(&d->d_tok, &d->cap_tok, n * 4, false, &d->n_allocs);
         if (rc != MBPE_OK) return rc;
         DCHK(hipMemcpyAsync(d->d_tok, tokens, n * 4, hipMemcpyHostToDevice, d->stream));
     }
     uint64_t total = 0;
-    int rc = dec_measure(d, kFmtU32, d->d_tok, n, MBPE_NO_BARRIER, &total, n_invalid);
+    int rc = dec_measure(d, kFmtU32, d->d_tok, n, MBPE_NO_BARRIER, nullptr, &total, n_invalid);
     if (rc != MBPE_OK) return rc;
     if (total) {
-        rc = grow(&d->d_out, &d->cap_out, total, false, nullptr);
+        rc = grow(&d->d_out, &d->cap_out, total, false, &d->n_allocs);
         if (rc != MBPE_OK) return rc;
     }
-    rc = dec_write(d, kFmtU32, d->d_tok, n, MBPE_NO_BARRIER, d->d_out, total != 0);
+    rc = dec_write(d, kFmtU32, d->d_tok, n, MBPE_NO_BARRIER, nullptr, d->d_out, total != 0);
     if (rc != MBPE_OK) return rc;
     if (total) {
         out->resize(total);
@@ -525,6 +622,7 @@ int mbpe_decoder_create(int device_id, const uint32_t *merges, uint32_t n_merges
         DCHK(hipMalloc(&d->d_spk, (size_t)sp_cap * 4));
         DCHK(hipMalloc(&d->d_spe, (size_t)sp_cap * 4));
         DCHK(hipMalloc(&d->d_res, 16));
+        d->n_allocs = 6;
         DCHK(hipMemcpyAsync(d->d_len, len.data(), len.size() * 4, hipMemcpyHostToDevice, d->stream));
         DCHK(hipMemcpyAsync(d->d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, d->stream));
         DCHK(hipMemcpyAsync(d->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, d->stream));
@@ -550,7 +648,7 @@ void mbpe_decoder_destroy(mbpe_decoder *d) {
     (void)hipSetDevice(d->device);
     (void)hipFree(d->d_len); (void)hipFree(d->d_off); (void)hipFree(d->d_blob); (void)hipFree(d->d_spk);
     (void)hipFree(d->d_spe); (void)hipFree(d->d_span); (void)hipFree(d->d_res); (void)hipFree(d->d_tok);
-    (void)hipFree(d->d_out);
+    (void)hipFree(d->d_out); (void)hipFree(d->d_doc_tok); (void)hipFree(d->d_doc_byte);
     if (d->ev0) (void)hipEventDestroy(d->ev0);
     if (d->ev1) (void)hipEventDestroy(d->ev1);
     if (d->stream) (void)hipStreamDestroy(d->stream);
@@ -560,8 +658,22 @@ void mbpe_decoder_destroy(mbpe_decoder *d) {
 int mbpe_decode_tokens(mbpe_decoder *d, const uint32_t *tokens, uint64_t n_tokens, int tokens_on_device,
                        uint8_t *bytes_out, uint64_t cap, int out_on_device, uint64_t *n_out, uint64_t *n_invalid_out) {
     if (!d || !n_out || (!tokens && n_tokens)) return fail(MBPE_ERR_ARG, "mbpe_decode_tokens: NULL argument");
-    return dec_run(d, kFmtU32, tokens, n_tokens, tokens_on_device, MBPE_NO_BARRIER, bytes_out, cap, out_on_device, n_out,
-                   n_invalid_out);
+    return dec_run(d, kFmtU32, tokens, n_tokens, tokens_on_device, MBPE_NO_BARRIER, nullptr, bytes_out, cap,
+                   out_on_device, n_out, n_invalid_out);
+}
+
+int mbpe_decode_batch(mbpe_decoder *d, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
+                      const uint64_t *doc_tok_off, uint64_t n_docs, uint8_t *bytes_out, uint64_t cap, int out_on_device,
+                      uint64_t *doc_byte_off_out, uint64_t *n_out, uint64_t *n_invalid_out) {
+    if (n_out) *n_out = 0;
+    if (!d || !n_out || !doc_tok_off || !doc_byte_off_out || (!tokens && n_tokens))
+        return fail(MBPE_ERR_ARG, "mbpe_decode_batch: NULL argument");
+    if (token_bits != 32 && token_bits != 16) return fail(MBPE_ERR_ARG, "token_bits must be 32 or 16");
+    const int rc = mbpe_host::check_doc_tok_off(doc_tok_off, n_docs, n_tokens);
+    if (rc != MBPE_OK) return rc;
+    const DecDocs docs = {doc_tok_off, n_docs + 1, doc_byte_off_out};
+    return dec_run(d, token_bits == 32 ? kFmtU32 : kFmtU16Plain, tokens, n_tokens, tokens_on_device, MBPE_NO_BARRIER,
+                   &docs, bytes_out, cap, out_on_device, n_out, n_invalid_out);
 }
 
 int mbpe_decode_slots(mbpe_decoder *d, const void *slots, uint64_t n_slots, uint32_t slot_bits, uint32_t end_bit,
@@ -571,12 +683,18 @@ int mbpe_decode_slots(mbpe_decoder *d, const void *slots, uint64_t n_slots, uint
     int fmt = 0;
     const int rc = slot_format(slot_bits, end_bit, barrier, &fmt);
     if (rc != MBPE_OK) return rc;
-    return dec_run(d, fmt, slots, n_slots, 1, barrier, bytes_out, cap, out_on_device, n_out, n_invalid_out);
+    return dec_run(d, fmt, slots, n_slots, 1, barrier, nullptr, bytes_out, cap, out_on_device, n_out, n_invalid_out);
 }
 
 int mbpe_decoder_kernel_ms(const mbpe_decoder *d, float *ms_out) {
     if (!d || !ms_out) return fail(MBPE_ERR_ARG, "mbpe_decoder_kernel_ms: NULL argument");
     *ms_out = d->last_ms;
+    return MBPE_OK;
+}
+
+int mbpe_decoder_alloc_count(const mbpe_decoder *d, uint64_t *n_out) {
+    if (!d || !n_out) return fail(MBPE_ERR_ARG, "mbpe_decoder_alloc_count: NULL argument");
+    *n_out = d->n_allocs;
     return MBPE_OK;
 }
 

@@ -34,6 +34,10 @@ int ctx_device(const mbpe_ctx *c);
 // copy, so that the tokens are uploaded once; returns an mbpe_status
 int decode_to_string(mbpe_decoder *d, const uint32_t *tokens, uint64_t n, std::string *out, uint64_t *n_invalid);
 
+// the doc_tok_off rule of mbpe_decode_batch (csrc/decode.hip): n_docs + 1 ascending offsets from 0 to n_tokens;
+// MBPE_OK, or MBPE_ERR_ARG with the last error set.  Touches no device
+int check_doc_tok_off(const uint64_t *doc_tok_off, uint64_t n_docs, uint64_t n_tokens);
+
 // Tokenizer.h:59-60; nullptr for an unknown encoder name
 const char *split_pattern_for(const std::string &encoder);
 

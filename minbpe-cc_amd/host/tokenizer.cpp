@@ -50,6 +50,34 @@ void Tokenizer::drop_decoder() {
     decoder_device_ = -1;
 }
 
+mbpe_decoder *Tokenizer::device_decoder(int device) {
+    if (!decoder_ || decoder_device_ != device) {
+        drop_decoder();
+        std::vector<uint32_t> flat, ids;
+        std::vector<uint64_t> off{0};
+        std::string bytes;
+        flat.reserve(2 * merges_.size());
+        for (const auto &m : merges_) { flat.push_back(m.first); flat.push_back(m.second); }
+        for (const auto &kv : special_tokens_reverse_lookup_) {
+            ids.push_back(kv.first);
+            bytes += kv.second;
+            off.push_back(bytes.size());
+        }
+        const int rc = mbpe_decoder_create(device, flat.data(), static_cast<uint32_t>(merges_.size()), ids.data(),
+                                           reinterpret_cast<const uint8_t *>(bytes.data()), off.data(),
+                                           static_cast<uint32_t>(ids.size()), &decoder_);
+        if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
+        decoder_device_ = device;
+    }
+    return decoder_;
+}
+
+void Tokenizer::warn_invalid(const Token *tokens, uint64_t n) const {
+    for (uint64_t i = 0; i < n; ++i)
+        if (tokens[i] >= vocab_.size() && !special_tokens_reverse_lookup_.count(tokens[i]))
+            std::cerr << "Warning: Attempted to decode invalid token ID: " << tokens[i] << "\n";
+}
+
 Tokenizer::Tokenizer(const std::string &pattern) : pattern_(pattern) {
     std::string err;
     if (splitter_.compile(pattern, &err) != MBPE_OK) throw std::runtime_error(err);   // Tokenizer.h:427-431
@@ -325,31 +353,10 @@ std::string Tokenizer::decode(const std::vector<Token> &tokens, bool verbose, in
     if (verbose) std::cout << "Decoding " << tokens.size() << " tokens\n";
     std::string text;
     if (device >= 0) {
-        if (!decoder_ || decoder_device_ != device) {
-            drop_decoder();
-            std::vector<uint32_t> flat, ids;
-            std::vector<uint64_t> off{0};
-            std::string bytes;
-            flat.reserve(2 * merges_.size());
-            for (const auto &m : merges_) { flat.push_back(m.first); flat.push_back(m.second); }
-            for (const auto &kv : special_tokens_reverse_lookup_) {
-                ids.push_back(kv.first);
-                bytes += kv.second;
-                off.push_back(bytes.size());
-            }
-            const int rc = mbpe_decoder_create(device, flat.data(), static_cast<uint32_t>(merges_.size()), ids.data(),
-                                               reinterpret_cast<const uint8_t *>(bytes.data()), off.data(),
-                                               static_cast<uint32_t>(ids.size()), &decoder_);
-            if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
-            decoder_device_ = device;
-        }
         uint64_t n_invalid = 0;
-        const int rc = decode_to_string(decoder_, tokens.data(), tokens.size(), &text, &n_invalid);
+        const int rc = decode_to_string(device_decoder(device), tokens.data(), tokens.size(), &text, &n_invalid);
         if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
-        if (n_invalid)                              // rare: the reference's warning for each such id, in order (:734-737)
-            for (Token tkn : tokens)
-                if (tkn >= vocab_.size() && !special_tokens_reverse_lookup_.count(tkn))
-                    std::cerr << "Warning: Attempted to decode invalid token ID: " << tkn << "\n";
+        if (n_invalid) warn_invalid(tokens.data(), tokens.size());      // rare
         return text;
     }
     for (Token tkn : tokens) {
@@ -362,6 +369,40 @@ std::string Tokenizer::decode(const std::vector<Token> &tokens, bool verbose, in
         for (Token c : vocab_[tkn]) text.push_back(static_cast<char>(c));
     }
     return text;
+}
+
+int Tokenizer::decode_batch_flat(const Token *tokens, const uint64_t *doc_tok_off, uint64_t n_docs, bool verbose,
+                                 int device, uint8_t *bytes_out, uint64_t cap, uint64_t *doc_byte_off_out,
+                                 uint64_t *n_out) {
+    const uint64_t n = doc_tok_off[n_docs];
+    if (verbose) std::cout << "Decoding " << n << " tokens of " << n_docs << " texts\n";
+    uint64_t n_invalid = 0;
+    const int rc = mbpe_decode_batch(device_decoder(device), tokens, n, 32, 0, doc_tok_off, n_docs, bytes_out, cap, 0,
+                                     doc_byte_off_out, n_out, &n_invalid);
+    if (n_invalid) warn_invalid(tokens, n);         // (counted whenever the lengths were: also when cap is too small)
+    return rc;
+}
+
+std::vector<std::string> Tokenizer::decode_batch(const std::vector<std::vector<Token>> &docs, bool verbose, int device) {
+    std::vector<Token> flat;
+    std::vector<uint64_t> tok_off{0};
+    for (const auto &d : docs) {
+        flat.insert(flat.end(), d.begin(), d.end());
+        tok_off.push_back(flat.size());
+    }
+    std::vector<uint64_t> byte_off(docs.size() + 1, 0);
+    uint64_t n = 0;
+    int rc = decode_batch_flat(flat.data(), tok_off.data(), docs.size(), verbose, device, nullptr, 0, byte_off.data(), &n);
+    std::string all(n, '\0');
+    if (rc == MBPE_OK && n) {
+        uint64_t n_invalid = 0;                     // (the query has printed the warnings)
+        rc = mbpe_decode_batch(device_decoder(device), flat.data(), flat.size(), 32, 0, tok_off.data(), docs.size(),
+                               reinterpret_cast<uint8_t *>(&all[0]), n, 0, byte_off.data(), &n, &n_invalid);
+    }
+    if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
+    std::vector<std::string> out(docs.size());
+    for (size_t i = 0; i < docs.size(); ++i) out[i] = all.substr(byte_off[i], byte_off[i + 1] - byte_off[i]);
+    return out;
 }
 
 // :754-872
@@ -603,6 +644,28 @@ int mbpe_tok_decode_device(mbpe_tokenizer *t, const uint32_t *tokens, uint64_t n
         memcpy(bytes_out, s.data(), s.size());
         return MBPE_OK;
     } catch (const mbpe_host::CodedError &e) {      // mbpe_decoder_create / mbpe_decode_tokens failed: its own code
+        mbpe_host::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        mbpe_host::set_last_error(e.what());
+        return MBPE_ERR_ARG;
+    }
+}
+
+int mbpe_tok_decode_batch_device(mbpe_tokenizer *t, const uint32_t *tokens, const uint64_t *doc_tok_off,
+                                 uint64_t n_docs, int verbose, int device_id, uint8_t *bytes_out, uint64_t cap,
+                                 uint64_t *doc_byte_off_out, uint64_t *n_out) {
+    if (n_out) *n_out = 0;
+    if (!t || !n_out || !doc_tok_off || !doc_byte_off_out || device_id < 0 || (!tokens && doc_tok_off[n_docs])) {
+        mbpe_host::set_last_error("mbpe_tok_decode_batch_device: NULL argument or negative device");
+        return MBPE_ERR_ARG;
+    }
+    const int rc = mbpe_host::check_doc_tok_off(doc_tok_off, n_docs, doc_tok_off[n_docs]);
+    if (rc != MBPE_OK) return rc;
+    try {
+        return t->t->decode_batch_flat(tokens, doc_tok_off, n_docs, verbose != 0, device_id, bytes_out, cap,
+                                       doc_byte_off_out, n_out);
+    } catch (const mbpe_host::CodedError &e) {      // mbpe_decoder_create failed: its own code
         mbpe_host::set_last_error(e.what());
         return e.code;
     } catch (const std::exception &e) {

@@ -44,6 +44,12 @@ public:
                           std::vector<uint64_t> *doc_tok_off);
     // :725-751; device >= 0 expands the tokens on that HIP device (mbpe_decode_tokens) instead of the host loop
     std::string decode(const std::vector<Token> &tokens, bool verbose, int device = -1);
+    // decode() of every token list, [i] == decode(docs[i], false, -1), in one mbpe_decode_batch on HIP device `device`
+    std::vector<std::string> decode_batch(const std::vector<std::vector<Token>> &docs, bool verbose, int device);
+    // the same over one token array: n_docs + 1 offsets that check_doc_tok_off accepts.  bytes_out / cap /
+    // doc_byte_off_out / n_out go to mbpe_decode_batch as they are (NULL bytes_out: query), whose code is returned
+    int decode_batch_flat(const Token *tokens, const uint64_t *doc_tok_off, uint64_t n_docs, bool verbose, int device,
+                          uint8_t *bytes_out, uint64_t cap, uint64_t *doc_byte_off_out, uint64_t *n_out);
     bool load(const std::string &path, bool verbose);                      // :754-872
     bool save(const std::string &path, bool write_vocab);                  // :875-926
 
@@ -72,6 +78,8 @@ private:
     // other part (:664-704); without one, every part is a chunk (:706-709)
     void append_chunks(const std::string &text, bool verbose, std::string *buf, std::vector<uint64_t> *off) const;
     mbpe_encoder *device_encoder(int device);
+    mbpe_decoder *device_decoder(int device);
+    void warn_invalid(const Token *tokens, uint64_t n) const;   // the warning of :734-737 for each such id, in order
 
     std::string pattern_;
     Splitter splitter_;

@@ -30,13 +30,13 @@ EXPORTS = [
     "mbpe_encode_chunks_device", "mbpe_decoder_create", "mbpe_decoder_destroy", "mbpe_decode_tokens",
     "mbpe_decode_slots", "mbpe_decoder_kernel_ms", "mbpe_decode_stream", "mbpe_encoder_create",
     "mbpe_encoder_destroy", "mbpe_encoder_encode", "mbpe_encoder_set_option", "mbpe_encoder_kernel_ms",
-    "mbpe_encoder_alloc_count", "mbpe_encoder_pass_tokens",
+    "mbpe_encoder_alloc_count", "mbpe_encoder_pass_tokens", "mbpe_decode_batch", "mbpe_decoder_alloc_count",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
     "mbpe_tok_create", "mbpe_tok_destroy", "mbpe_tok_set_special_tokens", "mbpe_tok_train", "mbpe_tok_set_merges",
     "mbpe_tok_get_merges", "mbpe_tok_save", "mbpe_tok_load", "mbpe_tok_encode", "mbpe_tok_encode_device",
-    "mbpe_tok_decode", "mbpe_tok_decode_device", "mbpe_tok_encode_batch_device",
+    "mbpe_tok_decode", "mbpe_tok_decode_device", "mbpe_tok_encode_batch_device", "mbpe_tok_decode_batch_device",
 ]
 
 
@@ -140,6 +140,9 @@ def lib():
     L.mbpe_decode_tokens.argtypes = [vp, vp, u64, i32, vp, u64, i32, vp, vp]
     L.mbpe_decode_slots.argtypes = [vp, vp, u64, u32, u32, u32, vp, u64, i32, vp, vp]
     L.mbpe_decoder_kernel_ms.argtypes = [vp, vp]
+    L.mbpe_decode_batch.argtypes = [vp, vp, u64, u32, i32, vp, u64, vp, u64, i32, vp, vp, vp]
+    L.mbpe_decoder_alloc_count.argtypes = [vp, vp]
+    L.mbpe_tok_decode_batch_device.argtypes = [vp, vp, vp, u64, i32, i32, vp, u64, vp, vp]
     L.mbpe_decode_stream.argtypes = [vp, vp, u64, i32, vp]
     L.mbpe_tok_decode_device.argtypes = [vp, vp, u64, i32, i32, vp, u64, vp]
     L.mbpe_tok_create.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -380,6 +383,42 @@ class Decoder:
                                         ctypes.byref(n), ctypes.byref(bad)))
         return n.value, bad.value
 
+    def decode_batch(self, docs, with_invalid=False, dtype=np.uint32):
+        """A list of token arrays -> the list of their texts, in one device call each for the lengths and the bytes
+        (mbpe_decode_batch).  dtype uint16 sends the ids as plain 16-bit ids."""
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.uint32), np.dtype(np.uint16)):
+            raise ValueError("dtype must be uint32 or uint16")
+        parts = [np.ascontiguousarray(t, dtype=dtype).reshape(-1) for t in docs]
+        tok_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        if parts:
+            tok_off[1:] = np.cumsum([len(t) for t in parts], dtype=np.uint64)
+        t = np.concatenate(parts) if parts else np.zeros(0, dtype=dtype)
+        tp = t.ctypes.data if len(t) else None
+        byte_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        n, bad = ctypes.c_uint64(), ctypes.c_uint64()
+        args = (self._h, tp, len(t), dtype.itemsize * 8, 0, tok_off.ctypes.data, len(parts))
+        _check(lib().mbpe_decode_batch(*args, None, 0, 0, byte_off.ctypes.data, ctypes.byref(n), ctypes.byref(bad)))
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        _check(lib().mbpe_decode_batch(*args, out.ctypes.data, n.value, 0, byte_off.ctypes.data, ctypes.byref(n),
+                                       ctypes.byref(bad)))
+        data = out[:n.value].tobytes()
+        texts = [data[int(a):int(b)] for a, b in zip(byte_off[:-1], byte_off[1:])]
+        return (texts, bad.value) if with_invalid else texts
+
+    def decode_batch_device(self, ptr, n_tokens, doc_tok_off, out_ptr, cap, token_bits=32):
+        """n_tokens ids of token_bits bits in device memory at ptr, document i being tokens doc_tok_off[i] ..
+        doc_tok_off[i + 1] -> bytes in device memory at out_ptr (0: query; room for cap bytes) -> (doc_byte_off,
+        decoded length, ids that decoded to nothing): document i's text is bytes doc_byte_off[i] .. doc_byte_off[i + 1]."""
+        tok_off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+        byte_off = np.zeros(len(tok_off), dtype=np.uint64)
+        n, bad = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().mbpe_decode_batch(self._h, ctypes.c_void_p(ptr) if ptr else None, n_tokens, token_bits, 1,
+                                       tok_off.ctypes.data if len(tok_off) else None, max(len(tok_off), 1) - 1,
+                                       ctypes.c_void_p(out_ptr) if out_ptr else None, cap, 1,
+                                       byte_off.ctypes.data, ctypes.byref(n), ctypes.byref(bad)))
+        return byte_off, n.value, bad.value
+
     def decode_slots_device(self, ptr, n_slots, slot_bits, end_bit, barrier, out_ptr, cap):
         """The same for device-resident slots in a layout of Trainer.stream_device() (mbpe_decode_slots)."""
         n, bad = ctypes.c_uint64(), ctypes.c_uint64()
@@ -394,6 +433,12 @@ class Decoder:
         ms = ctypes.c_float()
         _check(lib().mbpe_decoder_kernel_ms(self._h, ctypes.byref(ms)))
         return ms.value
+
+    def alloc_count(self):
+        """Device allocations made so far (mbpe_decoder_alloc_count)."""
+        n = ctypes.c_uint64()
+        _check(lib().mbpe_decoder_alloc_count(self._h, ctypes.byref(n)))
+        return n.value
 
 
 class Trainer:
@@ -673,3 +718,21 @@ class Tokenizer:
         out = np.zeros(max(n.value, 1), dtype=np.uint8)
         _check(lib().mbpe_tok_decode_device(self._h, tp, len(t), 0, device, out.ctypes.data, len(out), ctypes.byref(n)))
         return out[:n.value].tobytes()
+
+    def decode_batch(self, token_lists, device=0):
+        """decode() of every token list in one device call each for the lengths and the bytes
+        (mbpe_tok_decode_batch_device) -> list of bytes; the mirror of encode_batch."""
+        parts = [np.ascontiguousarray(t, dtype=np.uint32).reshape(-1) for t in token_lists]
+        tok_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        if parts:
+            tok_off[1:] = np.cumsum([len(t) for t in parts], dtype=np.uint64)
+        t = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint32)
+        tp = t.ctypes.data if len(t) else None
+        byte_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        n = ctypes.c_uint64()
+        args = (self._h, tp, tok_off.ctypes.data, len(parts), 0, device)
+        _check(lib().mbpe_tok_decode_batch_device(*args, None, 0, byte_off.ctypes.data, ctypes.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        _check(lib().mbpe_tok_decode_batch_device(*args, out.ctypes.data, len(out), byte_off.ctypes.data, ctypes.byref(n)))
+        data = out[:n.value].tobytes()
+        return [data[int(a):int(b)] for a, b in zip(byte_off[:-1], byte_off[1:])]
