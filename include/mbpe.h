@@ -409,6 +409,90 @@ MBPE_API int  mbpe_encoder_pass_tokens(const mbpe_encoder *e, uint64_t *tokens_o
  * token array.) */
 MBPE_API int  mbpe_encoder_alloc_count(const mbpe_encoder *e, uint64_t *n_out);
 
+/* ---- fixed-length id matrices --------------------------------------------- */
+
+/* A model input is a rectangle: [rows, seq_len] ids plus one length per row.  These calls build it on the device
+ * from a flat token stream with per-document offsets -- what mbpe_encoder_encode leaves there -- and take it back
+ * (csrc/pack.hip).  Let nb / ne be 1 where bos_id / eos_id is set, else 0.
+ *   MBPE_PACK_PADDED  one row per document: [bos] body [eos], where body is the document's first keep = seq_len - nb
+ *                     - ne tokens (its last keep with trunc_left); len = nb + |body| + ne; the row is filled with
+ *                     pad_id up to seq_len on the right, or -- pad_left -- on the left.  An empty document gives a row
+ *                     of len nb + ne.  n_rows = n_docs.
+ *   MBPE_PACK_PACKED  the stream S = the concatenation over the documents of [bos] doc [eos], cut row-major into
+ *                     ceil(|S| / seq_len) rows; the tail of the last row is pad_id; len[r] = elements of S in row r.
+ *                     pad_left and trunc_left must be 0.
+ * Like the encoder and the decoder these calls work on a stream of their own and return when the matrix is complete:
+ * device buffers handed to them must not be in use by work still in flight on another stream. */
+#define MBPE_PACK_PADDED 0u
+#define MBPE_PACK_PACKED 1u
+#define MBPE_NO_TOKEN 0xFFFFFFFFu
+typedef struct {
+    uint32_t layout;      /* MBPE_PACK_PADDED or MBPE_PACK_PACKED */
+    uint32_t seq_len;     /* ids per row, at least 1 */
+    uint32_t out_bits;    /* 16, 32 or 64: uint16_t / uint32_t / uint64_t ids (the last is what an int64 tensor takes) */
+    uint32_t pad_id;
+    uint32_t bos_id;      /* MBPE_NO_TOKEN: none */
+    uint32_t eos_id;      /* MBPE_NO_TOKEN: none */
+    uint32_t pad_left;    /* PADDED: 0 = the padding follows the ids, otherwise it comes first */
+    uint32_t trunc_left;  /* PADDED: 0 = a document too long keeps its first tokens, otherwise its last */
+} mbpe_pack_spec;
+
+/* One call, with its own device scratch for the offsets (and for whatever lives on the host).
+ *   tokens, n_tokens, token_bits, tokens_on_device   the ids: host or device memory.  token_bits 32: uint32_t whose
+ *                     bit 31 is cleared on read, so that host ids and the flagged tokens mbpe_encoder_encode leaves on
+ *                     the device are both accepted.  token_bits 16: plain uint16_t ids, 65,535 included
+ *   doc_tok_off, n_docs   host; the convention of mbpe_decode_batch: n_docs + 1 ascending offsets, [0] == 0,
+ *                     [n_docs] == n_tokens
+ *   ids_out           cap_rows rows of spec->seq_len ids of spec->out_bits bits, row-major without gaps: host memory,
+ *                     or device memory (aligned to one id) when out_on_device != 0.  NULL: query
+ *   len_out           optional: one uint32_t per row, on the same side as ids_out
+ *   n_rows_out        required; written whenever the arguments are valid.  cap_rows smaller than it returns
+ *                     MBPE_ERR_ARG and writes nothing else
+ * MBPE_ERR_ARG: a NULL argument, a bad offset array, seq_len == 0, seq_len < nb + ne (PADDED), an unknown layout or
+ * bit width, pad_left or trunc_left with PACKED.  MBPE_ERR_VOCAB: out_bits 16 with token_bits 32, or with a pad_id,
+ * bos_id or eos_id >= 65,536.  All of it is checked, and a query answered, before the device is touched.  No CPU
+ * fallback: MBPE_ERR_NO_DEVICE without a HIP device. */
+MBPE_API int  mbpe_pack_tokens(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits,
+                               int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs,
+                               const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
+                               uint32_t *len_out, uint64_t *n_rows_out);
+
+/* The inverse of a right-padded PADDED matrix: row r contributes its first len[r] ids.
+ *   ids, n_rows, seq_len, id_bits, ids_on_device   the matrix (id_bits 16, 32 or 64; ids stay below 2^31) and, on the
+ *                     same side, len: one uint32_t per row.  The lengths of a device matrix are copied back first
+ *   tokens_out        cap tokens of token_bits bits (16 only with id_bits 16, else MBPE_ERR_VOCAB; 32), host or device
+ *                     (out_on_device): the rows' ids one after the other.  NULL: query
+ *   doc_tok_off_out   optional, host, n_rows + 1 entries: row r is tokens [doc_tok_off_out[r], doc_tok_off_out[r + 1]).
+ *                     Together with tokens_out on the device this is what mbpe_decode_batch takes, as it is
+ *   n_out             required: the token count, also on a query and when cap is too small (MBPE_ERR_ARG, nothing
+ *                     written to tokens_out)
+ * A len[r] above seq_len is MBPE_ERR_ARG. */
+MBPE_API int  mbpe_unpack_tokens(int device_id, const void *ids, uint64_t n_rows, uint32_t seq_len, uint32_t id_bits,
+                                 int ids_on_device, const uint32_t *len, void *tokens_out, uint64_t cap,
+                                 uint32_t token_bits, int out_on_device, uint64_t *doc_tok_off_out, uint64_t *n_out);
+
+/* Device time in milliseconds of the kernel of the calling thread's latest mbpe_pack_tokens or mbpe_unpack_tokens
+ * (HIP events around it; allocations and copies are outside). */
+MBPE_API int  mbpe_pack_kernel_ms(float *ms_out);
+
+/* Encode and pack in one call: mbpe_encoder_encode into a flat device buffer that the encoder keeps (allocated by
+ * the first such call, grown like the work buffers: a repeat call of no larger size leaves
+ * mbpe_encoder_alloc_count as it is), then the pack kernel on the encoder's own stream.  No token crosses to the
+ * host; only the chunk ends do.
+ *   text .. n_chunks  as for mbpe_encoder_encode (pieces included)
+ *   doc_chunk_off, n_docs   host, n_docs + 1 ascending chunk indices from 0 to n_chunks: document i is the chunks
+ *                     [doc_chunk_off[i], doc_chunk_off[i + 1])
+ *   spec .. n_rows_out   as for mbpe_pack_tokens, for tokens of 16 bits when spec->out_bits is 16 (MBPE_ERR_VOCAB when
+ *                     256 + n_merges > 65,536) and of 32 bits otherwise.  A query (ids_out NULL) runs the passes
+ *   n_tokens_out      optional: tokens encoded, before bos, eos, truncation and padding
+ * mbpe_encoder_kernel_ms then covers both steps, mbpe_encoder_pack_ms the pack kernel alone. */
+MBPE_API int  mbpe_encoder_encode_batch(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                        const uint64_t *chunk_off, uint64_t n_chunks,
+                                        const uint64_t *doc_chunk_off, uint64_t n_docs, const mbpe_pack_spec *spec,
+                                        void *ids_out, uint64_t cap_rows, int out_on_device, uint32_t *len_out,
+                                        uint64_t *n_rows_out, uint64_t *n_tokens_out);
+MBPE_API int  mbpe_encoder_pack_ms(const mbpe_encoder *e, float *ms_out);
+
 /* ---- decode on the device ----------------------------------------------- */
 
 /* Tokenizer::decode (Tokenizer.h:725-751) for whole token streams on HIP device `device_id`: per token a byte

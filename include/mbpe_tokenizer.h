@@ -65,6 +65,17 @@ MBPE_API int mbpe_tok_encode_batch_device(mbpe_tokenizer *t, const uint8_t *text
                                           uint64_t n_docs, int verbose, int device_id, uint32_t *tokens_out,
                                           uint64_t cap, uint64_t *doc_tok_off_out, uint64_t *n_out);
 
+/* The same documents as one id matrix on the device: every document is split as above, all chunks go to the device
+ * in ONE mbpe_encoder_encode_batch (mbpe.h), which encodes them and packs the documents by `spec`.  bos_id and eos_id
+ * may name special-token ids.  spec, ids_out (NULL: query), cap_rows, out_on_device, len_out, n_rows_out (required)
+ * and n_tokens_out (optional) are those of mbpe_encoder_encode_batch.  A PADDED row i is document i: its first (or
+ * last) tokens of mbpe_tok_encode. */
+MBPE_API int mbpe_tok_encode_batch_packed_device(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off,
+                                                 uint64_t n_docs, int verbose, int device_id,
+                                                 const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows,
+                                                 int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                                                 uint64_t *n_tokens_out);
+
 /* decode, Tokenizer.h:725-751.  bytes_out may be NULL to query the length. */
 MBPE_API int mbpe_tok_decode(mbpe_tokenizer *t, const uint32_t *tokens, uint64_t n, int verbose,
                              uint8_t *bytes_out, uint64_t cap, uint64_t *n_out);
@@ -86,6 +97,15 @@ MBPE_API int mbpe_tok_decode_device(mbpe_tokenizer *t, const uint32_t *tokens, u
 MBPE_API int mbpe_tok_decode_batch_device(mbpe_tokenizer *t, const uint32_t *tokens, const uint64_t *doc_tok_off,
                                           uint64_t n_docs, int verbose, int device_id, uint8_t *bytes_out,
                                           uint64_t cap, uint64_t *doc_byte_off_out, uint64_t *n_out);
+
+/* decode of a right-padded id matrix (host memory: n_rows x seq_len uint32_t ids, row r holding len[r] of them, as
+ * MBPE_PACK_PADDED writes it without pad_left): mbpe_unpack_tokens into device memory, then one mbpe_decode_batch
+ * through the kept decoder.  bytes_out, cap, doc_byte_off_out (required, n_rows + 1) and n_out as for
+ * mbpe_tok_decode_batch_device, a row being a document.  A len[r] above seq_len is MBPE_ERR_ARG, also where there is
+ * no device. */
+MBPE_API int mbpe_tok_decode_padded_device(mbpe_tokenizer *t, const uint32_t *ids, uint64_t n_rows, uint32_t seq_len,
+                                           const uint32_t *len, int verbose, int device_id, uint8_t *bytes_out,
+                                           uint64_t cap, uint64_t *doc_byte_off_out, uint64_t *n_out);
 
 #ifdef __cplusplus
 }

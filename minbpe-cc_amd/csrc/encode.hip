@@ -23,6 +23,7 @@
 // count of flags -> k_enc_scan_sum -> ranked write).  A text that lives on the device is read in place; the chunk
 // starts whose byte is NUL are listed by a small kernel so that the host can parse those chunks.
 #include "hip_host.h"
+#include "pack.h"
 #include "span.h"
 
 #include <algorithm>
@@ -256,11 +257,19 @@ struct mbpe_encoder {
     uint64_t cap_nul = 0;
     unsigned long long *d_ends = nullptr;     // chunk ends, only when chunks are shorter than two bytes on average
     uint64_t cap_ends = 0;
+    // mbpe_encoder_encode_batch: the flat tokens of the batch, its document offsets, and a matrix that goes to the host
+    void *d_flat = nullptr;
+    unsigned long long *d_doc_off = nullptr;
+    void *d_ids = nullptr;
+    uint32_t *d_len = nullptr;
+    uint64_t cap_flat = 0, cap_doc_off = 0, cap_ids = 0, cap_len = 0;
+    float pack_ms = 0.f;                      // the pack kernel of the latest such call
     // host scratch
     std::vector<uint8_t> mask, bytes;
     std::vector<SingleChunk> singles, piece_singles;
     std::vector<unsigned long long> list;
     std::vector<uint64_t> pass_tokens;        // latest call: tokens that entered pass k, summed over the pieces
+    std::vector<uint64_t> chunk_tok, doc_tok; // mbpe_encoder_encode_batch: token offsets of the chunks, of the documents
 };
 
 namespace {
@@ -643,6 +652,55 @@ int enc_run(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_
     }
 }
 
+// encode into the kept flat buffer, then pack from it on the encoder's stream (arguments checked by the caller)
+int enc_batch_body(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device, const uint64_t *chunk_off,
+                   uint64_t n_chunks, const uint64_t *doc_chunk_off, uint64_t n_docs, const mbpe_pack_spec &spec,
+                   void *ids_out, uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                   uint64_t *n_tokens_out) {
+    const uint32_t token_bits = spec.out_bits == 16 ? 16 : 32;
+    ECHK(hipSetDevice(e->device));
+    int rc = grow(&e->d_flat, &e->cap_flat, std::max<uint64_t>(n_bytes, 1) * (token_bits / 8), true, &e->n_allocs);
+    if (rc != MBPE_OK) return rc;
+    e->last_ms = 0.f;
+    e->pack_ms = 0.f;
+    e->chunk_tok.assign(n_chunks + 1, 0);
+    uint64_t n_tokens = 0;
+    rc = enc_run_body(e, text, n_bytes, text_on_device, chunk_off, n_chunks, e->d_flat, n_bytes, token_bits, 1,
+                      e->chunk_tok.data(), &n_tokens, nullptr);
+    if (rc != MBPE_OK) return rc;
+    e->doc_tok.resize(n_docs + 1);
+    for (uint64_t i = 0; i <= n_docs; ++i) e->doc_tok[i] = e->chunk_tok[doc_chunk_off[i]];
+    const uint64_t n_rows = pack_rows(spec, n_tokens, n_docs);
+    *n_rows_out = n_rows;
+    if (n_tokens_out) *n_tokens_out = n_tokens;
+    if (!ids_out) return MBPE_OK;                                // the query
+    if (cap_rows < n_rows) return fail(MBPE_ERR_ARG, "ids_out too small");
+    if (n_rows == 0) return MBPE_OK;
+    const uint64_t id_bytes = n_rows * spec.seq_len * (spec.out_bits / 8);
+    rc = grow(&e->d_doc_off, &e->cap_doc_off, (n_docs + 1) * 8, true, &e->n_allocs);
+    if (rc == MBPE_OK && !out_on_device) {
+        rc = grow(&e->d_ids, &e->cap_ids, id_bytes, true, &e->n_allocs);
+        if (rc == MBPE_OK && len_out) rc = grow(&e->d_len, &e->cap_len, n_rows * 4, true, &e->n_allocs);
+    }
+    if (rc != MBPE_OK) return rc;
+    ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
+    const PackSrc src = {e->d_flat, e->d_doc_off, n_docs, n_tokens, token_bits};
+    const PackDst dst = {out_on_device ? ids_out : e->d_ids, out_on_device || !len_out ? len_out : e->d_len, n_rows};
+    ECHK(hipEventRecord(e->ev0, e->stream));
+    pack_launch(e->stream, src, spec, dst);
+    ECHK(hipEventRecord(e->ev1, e->stream));
+    ECHK(hipStreamSynchronize(e->stream));
+    ECHK(hipGetLastError());
+    ECHK(hipEventElapsedTime(&e->pack_ms, e->ev0, e->ev1));
+    e->last_ms += e->pack_ms;
+    if (!out_on_device) {
+        ECHK(hipMemcpyAsync(ids_out, e->d_ids, id_bytes, hipMemcpyDeviceToHost, e->stream));
+        if (len_out) ECHK(hipMemcpyAsync(len_out, e->d_len, n_rows * 4, hipMemcpyDeviceToHost, e->stream));
+        ECHK(hipStreamSynchronize(e->stream));
+    }
+    return MBPE_OK;
+}
+
 // the one-shot calls: a temporary encoder and one call
 int encode_chunks(int device_id, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off, uint64_t n_chunks,
                   const uint32_t *merges, uint32_t n_merges, uint32_t *tokens_out, uint64_t cap, uint64_t *n_out,
@@ -727,7 +785,8 @@ void mbpe_encoder_destroy(mbpe_encoder *e) {
     (void)hipFree(e->d_keys); (void)hipFree(e->d_vals); (void)hipFree(e->d_text); (void)hipFree(e->d_mask);
     (void)hipFree(e->tok[0]); (void)hipFree(e->tok[1]); (void)hipFree(e->cand); (void)hipFree(e->span_a);
     (void)hipFree(e->span_b); (void)hipFree(e->span_off); (void)hipFree(e->d_res); (void)hipFree(e->d_singles);
-    (void)hipFree(e->d_nul); (void)hipFree(e->d_ends);
+    (void)hipFree(e->d_nul); (void)hipFree(e->d_ends); (void)hipFree(e->d_flat); (void)hipFree(e->d_doc_off);
+    (void)hipFree(e->d_ids); (void)hipFree(e->d_len);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -754,6 +813,45 @@ int mbpe_encoder_encode(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, 
     if (token_bits != 16 && token_bits != 32) return fail(MBPE_ERR_ARG, "token_bits must be 16 or 32");
     return enc_run(e, text, n_bytes, text_on_device, chunk_off, n_chunks, tokens_out, cap, token_bits, out_on_device,
                    chunk_tok_off_out, n_out, n_passes_out);
+}
+
+int mbpe_encoder_encode_batch(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                              const uint64_t *chunk_off, uint64_t n_chunks, const uint64_t *doc_chunk_off,
+                              uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows,
+                              int out_on_device, uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!e || !n_rows_out || !doc_chunk_off || !spec || (!text && n_bytes))
+        return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_batch: NULL argument");
+    int rc = pack_check_spec(spec, spec->out_bits == 16 ? 16 : 32);
+    if (rc != MBPE_OK) return rc;
+    const uint64_t one[2] = {0, n_bytes};
+    if (!chunk_off) { chunk_off = one; n_chunks = 1; }
+    if (chunk_off[0] != 0 || chunk_off[n_chunks] != n_bytes)
+        return fail(MBPE_ERR_ARG, "chunk_off must start at 0 and end at n_bytes");
+    for (uint64_t c = 0; c < n_chunks; ++c)
+        if (chunk_off[c + 1] < chunk_off[c]) return fail(MBPE_ERR_ARG, "chunk_off must be ascending");
+    if (doc_chunk_off[0] != 0 || doc_chunk_off[n_docs] != n_chunks)
+        return fail(MBPE_ERR_ARG, "doc_chunk_off must start at 0 and end at n_chunks");
+    for (uint64_t i = 0; i < n_docs; ++i)
+        if (doc_chunk_off[i + 1] < doc_chunk_off[i]) return fail(MBPE_ERR_ARG, "doc_chunk_off must be ascending");
+    if (spec->out_bits == 16 && 256ull + e->n_merges > 65536ull)
+        return fail(MBPE_ERR_VOCAB, "out_bits 16 with more than 65,536 token ids");
+    if (ids_out && out_on_device &&
+        ((uint64_t)(uintptr_t)ids_out % (spec->out_bits / 8) || (uint64_t)(uintptr_t)len_out % 4))
+        return fail(MBPE_ERR_ARG, "ids_out or len_out is not aligned to its elements");
+    try {
+        return enc_batch_body(e, text, n_bytes, text_on_device, chunk_off, n_chunks, doc_chunk_off, n_docs, *spec,
+                              ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out);
+    } catch (const std::bad_alloc &) {
+        return fail(MBPE_ERR_OOM, "mbpe_encoder_encode_batch: host allocation failed");
+    }
+}
+
+int mbpe_encoder_pack_ms(const mbpe_encoder *e, float *ms_out) {
+    if (!e || !ms_out) return fail(MBPE_ERR_ARG, "mbpe_encoder_pack_ms: NULL argument");
+    *ms_out = e->pack_ms;
+    return MBPE_OK;
 }
 
 int mbpe_encoder_kernel_ms(const mbpe_encoder *e, float *ms_out) {

@@ -1,4 +1,4 @@
-// Host helpers of the translation units that drive the device (train.cpp, encode.hip, decode.hip).
+// Host helpers of the translation units that drive the device (train.cpp, encode.hip, decode.hip, pack.hip).
 #ifndef MBPE_HIP_HOST_H
 #define MBPE_HIP_HOST_H
 

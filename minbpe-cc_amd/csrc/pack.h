@@ -1,0 +1,39 @@
+// Packing a ragged token stream into fixed-length id matrices, and back (pack.hip): what the C-ABI entry points and
+// the encoder's batch call (encode.hip) share.  The views name device memory; the checks touch no device.
+#ifndef MBPE_PACK_H
+#define MBPE_PACK_H
+
+#include "mbpe.h"
+
+#include <hip/hip_runtime.h>
+
+namespace mbpe {
+
+// the documents: n_tokens tokens of `bits` bits (16: plain ids; 32: bit 31 is ignored) and n_docs + 1 token offsets
+struct PackSrc {
+    const void *tok;
+    const unsigned long long *doc_off;
+    uint64_t n_docs, n_tokens;
+    uint32_t bits;
+};
+
+// the matrix: n_rows x seq_len ids of the spec's out_bits, and (optional) one length per row
+struct PackDst {
+    void *ids;
+    uint32_t *len;
+    uint64_t n_rows;
+};
+
+// the rules of mbpe_pack_tokens for a spec and the width of the tokens it will read: MBPE_OK, or MBPE_ERR_ARG /
+// MBPE_ERR_VOCAB with the last error set
+int pack_check_spec(const mbpe_pack_spec *spec, uint32_t token_bits);
+
+// rows of the matrix that n_tokens tokens in n_docs documents fill (the spec has passed pack_check_spec)
+uint64_t pack_rows(const mbpe_pack_spec &spec, uint64_t n_tokens, uint64_t n_docs);
+
+// one kernel on `stream`; dst.n_rows == pack_rows(...) > 0.  Nothing is waited for
+void pack_launch(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst);
+
+}  // namespace mbpe
+
+#endif

@@ -1,0 +1,512 @@
+// Ragged token streams <-> fixed-length id matrices on the device: what stands between mbpe_encoder_encode's flat
+// tokens with per-document offsets and a model input of [rows, seq_len] ids plus one length per row.
+//
+//   MBPE_PACK_PADDED   one row per document: [bos] body [eos], pad_id up to seq_len (on the right, or on the left);
+//                      body = the document's first (or last) seq_len - nb - ne tokens
+//   MBPE_PACK_PACKED   the stream S = [bos] doc [eos] over all documents, cut row-major into rows of seq_len; pad_id
+//                      behind its end
+//   unpack             a right-padded PADDED matrix and its lengths -> the flat tokens mbpe_decode_batch reads
+//
+// All three are OUTPUT-centric like decode.hip's copy: the output, whose rows follow each other without a gap, is cut
+// at the 16-byte boundaries of its global address and a lane owns one such piece -- 8, 4 or 2 ids of 16, 32 or 64 bits.
+// It finds where its first id comes from, walks on from there (the next column, row or document), gathers the source
+// tokens with loads of the token's own width (a document starts at any offset) and stores the piece as one dwordx4.
+// A piece may hold the end of one row and the start of the next: a seq_len that is no multiple of the piece costs no
+// narrower store.  Only the first and the last piece of the whole output can be partial (an output address that is
+// not 16-byte aligned, a tail shorter than a piece); those are stored id by id.
+//   k_pack_padded   first id of a piece -> (row, column) by one division; a row's document offsets are read when the
+//                   row is entered.  The lane that writes column 0 of a row also writes its length.
+//   k_pack_stream   PACKED and unpack, which differ in where document d's token k lies (doc_off[d] + k, or
+//                   d * seq_len + k in a matrix) and in what stands around it.  The first id of a piece finds its
+//                   document by a binary search PER LANE over the shifted offsets doc_off[d] + d * (nb + ne), which
+//                   are formed on the fly; the walk then steps over document ends (and empty documents).  The 64 lanes
+//                   of a wave search neighbouring positions, so their probes fall into the same few cache lines.
+// Every output index is 64-bit (row * seq_len passes 2^32).
+//
+// Bytes moved per output id: the id itself written once (2, 4 or 8 B), its token read once (2 or 4 B; pad ids read
+// nothing), per row 16 B of offsets and 4 B of length.
+#include "pack.h"
+
+#include "hip_host.h"
+#include "span.h"
+
+#include <algorithm>
+#include <new>
+#include <string>
+#include <vector>
+
+namespace {
+
+using namespace mbpe;
+
+constexpr int kPackThreads = 256;
+constexpr uint32_t kPackMaxGrid = 0x7FFFFFFFu;
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// what a kernel works on; nb / ne = 1 where bos / eos is set
+struct PackJob {
+    const void *tok;
+    const unsigned long long *doc_off;       // n_docs + 1
+    uint64_t n_docs;
+    uint64_t n_stream;                       // k_pack_stream: ids of the stream (beyond it: pad)
+    void *out;
+    uint32_t *len;                           // or NULL
+    uint64_t n_out;                          // ids of the output
+    uint32_t seq_len, pad, bos, eos, nb, ne, keep, pad_left, trunc_left;
+};
+
+template <int IN>
+__device__ __forceinline__ uint32_t pack_read(const void *__restrict__ tok, uint64_t i) {
+    if (IN == 16) return static_cast<const uint16_t *>(tok)[i];
+    if (IN == 32) return static_cast<const uint32_t *>(tok)[i] & kTokIdMask;
+    return (uint32_t) static_cast<const unsigned long long *>(tok)[i];
+}
+
+template <int OUT> struct PackId;
+template <> struct PackId<16> { typedef uint16_t type; };
+template <> struct PackId<32> { typedef uint32_t type; };
+template <> struct PackId<64> { typedef unsigned long long type; };
+
+// the pieces of an output of n_out ids at address A: piece p is the bytes [B0 + 16 p, B0 + 16 p + 16) that lie in it
+template <int OUT>
+struct PackPieces {
+    uint64_t A, E, B0, n;
+    __device__ __forceinline__ PackPieces(const void *out, uint64_t n_out) {
+        A = (uint64_t)(uintptr_t)out;
+        E = A + n_out * (OUT / 8);
+        B0 = A & ~15ull;
+        n = (E - B0 + 15) >> 4;
+    }
+};
+
+// cnt ids, id e in bits [OUT * e, OUT * e + OUT) of acc, to the bytes [lo, lo + cnt * OUT / 8) of piece B
+template <int OUT>
+__device__ __forceinline__ void pack_store(void *out, uint64_t A, uint64_t B, uint64_t lo, uint32_t cnt,
+                                           unsigned __int128 acc) {
+    uint8_t *base = static_cast<uint8_t *>(out);
+    if (cnt == 128 / OUT) {                          // (then lo == B)
+        u32x4 q;
+        q.x = (uint32_t)acc;
+        q.y = (uint32_t)(acc >> 32);
+        q.z = (uint32_t)(acc >> 64);
+        q.w = (uint32_t)(acc >> 96);
+        *static_cast<u32x4 *>(__builtin_assume_aligned(base + (B - A), 16)) = q;
+    } else {                                         // the first or the last piece of the output
+        typename PackId<OUT>::type *dst = reinterpret_cast<typename PackId<OUT>::type *>(base + (lo - A));
+        for (uint32_t e = 0; e < cnt; ++e) dst[e] = (typename PackId<OUT>::type)(acc >> (OUT * e));
+    }
+}
+
+// a row of the PADDED layout: its ids are pad for columns below lead, then [bos] + body tokens from src0 + [eos]
+struct PadRow {
+    uint64_t src0;
+    uint32_t len, lead;
+};
+
+__device__ __forceinline__ PadRow pad_row(const PackJob &j, uint64_t row) {
+    const uint64_t d0 = j.doc_off[row], dl = j.doc_off[row + 1] - d0;
+    const uint32_t body = dl < j.keep ? (uint32_t)dl : j.keep;
+    PadRow r;
+    r.src0 = d0 + (j.trunc_left ? dl - body : 0ull);
+    r.len = j.nb + body + j.ne;
+    r.lead = j.pad_left ? j.seq_len - r.len : 0u;
+    return r;
+}
+
+template <int IN, int OUT>
+__global__ __launch_bounds__(kPackThreads) void k_pack_padded(PackJob j) {
+    constexpr uint32_t ob = OUT / 8;
+    const PackPieces<OUT> pc(j.out, j.n_out);
+    for (uint64_t p = (uint64_t)blockIdx.x * kPackThreads + threadIdx.x; p < pc.n;
+         p += (uint64_t)gridDim.x * kPackThreads) {
+        const uint64_t B = pc.B0 + (p << 4);
+        const uint64_t lo = B > pc.A ? B : pc.A;
+        const uint64_t hi = B + 16 < pc.E ? B + 16 : pc.E;
+        const uint32_t cnt = (uint32_t)(hi - lo) / ob;           // 1 .. 16 / ob
+        const uint64_t f = (lo - pc.A) / ob;
+        uint64_t row = f / j.seq_len;
+        uint32_t col = (uint32_t)(f - row * j.seq_len);
+        PadRow r = pad_row(j, row);
+        unsigned __int128 acc = 0;
+        for (uint32_t e = 0; e < cnt; ++e) {
+            if (col == 0 && j.len) j.len[row] = r.len;
+            const uint32_t k = col - r.lead;                     // wraps for a pad on the left: >= len
+            uint32_t v = j.pad;
+            if (col >= r.lead && k < r.len) {
+                if (j.nb && k == 0) v = j.bos;
+                else if (j.ne && k == r.len - 1) v = j.eos;
+                else v = pack_read<IN>(j.tok, r.src0 + (k - j.nb));
+            }
+            acc |= (unsigned __int128)v << (OUT * e);
+            if (++col == j.seq_len) {
+                col = 0;
+                ++row;
+                if (e + 1 < cnt) r = pad_row(j, row);            // (another id of the piece: the row exists)
+            }
+        }
+        pack_store<OUT>(j.out, pc.A, B, lo, cnt, acc);
+    }
+}
+
+// where document d begins in the stream, and its ids there (bos and eos included)
+__device__ __forceinline__ uint64_t stream_off(const PackJob &j, uint64_t d) {
+    return j.doc_off[d] + d * (uint64_t)(j.nb + j.ne);
+}
+
+// ROWS: the source is a matrix, document d's token k is tok[d * seq_len + k], the output is the stream itself (unpack;
+// nb == ne == 0, no lengths).  Otherwise PACKED: the source is flat, the output rows of seq_len with pad behind the
+// stream, len[r] = ids of the stream in row r.
+template <int IN, int OUT, bool ROWS>
+__global__ __launch_bounds__(kPackThreads) void k_pack_stream(PackJob j) {
+    constexpr uint32_t ob = OUT / 8;
+    const PackPieces<OUT> pc(j.out, j.n_out);
+    const uint32_t nbe = j.nb + j.ne;
+    for (uint64_t p = (uint64_t)blockIdx.x * kPackThreads + threadIdx.x; p < pc.n;
+         p += (uint64_t)gridDim.x * kPackThreads) {
+        const uint64_t B = pc.B0 + (p << 4);
+        const uint64_t lo = B > pc.A ? B : pc.A;
+        const uint64_t hi = B + 16 < pc.E ? B + 16 : pc.E;
+        const uint32_t cnt = (uint32_t)(hi - lo) / ob;
+        uint64_t f = (lo - pc.A) / ob;
+        uint64_t row = 0;
+        uint32_t col = 0;
+        if (!ROWS) {
+            row = f / j.seq_len;
+            col = (uint32_t)(f - row * j.seq_len);
+        }
+        // the document that holds stream position f: the largest d with stream_off(d) <= f (empty documents without
+        // bos / eos share their successor's offset and are passed over)
+        uint64_t d = 0, k = 0, d0 = 0, dtot = 0;
+        if (f < j.n_stream) {
+            uint64_t hi_d = j.n_docs;                            // stream_off(d) <= f < stream_off(hi_d)
+            while (hi_d - d > 1) {
+                const uint64_t mid = d + (hi_d - d) / 2;
+                if (stream_off(j, mid) <= f) d = mid;
+                else hi_d = mid;
+            }
+            d0 = j.doc_off[d];
+            dtot = j.doc_off[d + 1] - d0 + nbe;
+            k = f - (d0 + d * (uint64_t)nbe);
+        }
+        unsigned __int128 acc = 0;
+        for (uint32_t e = 0; e < cnt; ++e, ++f) {
+            uint32_t v = j.pad;
+            if (f < j.n_stream) {
+                while (k >= dtot) {                              // ends: f < n_stream, a document with ids follows
+                    ++d;
+                    k = 0;
+                    d0 = j.doc_off[d];
+                    dtot = j.doc_off[d + 1] - d0 + nbe;
+                }
+                if (j.nb && k == 0) v = j.bos;
+                else if (j.ne && k == dtot - 1) v = j.eos;
+                else v = pack_read<IN>(j.tok, (ROWS ? d * j.seq_len : d0) + (k - j.nb));
+                ++k;
+            }
+            if (!ROWS) {
+                if (col == 0 && j.len) {
+                    const uint64_t left = f < j.n_stream ? j.n_stream - f : 0ull;
+                    j.len[row] = left < j.seq_len ? (uint32_t)left : j.seq_len;
+                }
+                if (++col == j.seq_len) { col = 0; ++row; }
+            }
+            acc |= (unsigned __int128)v << (OUT * e);
+        }
+        pack_store<OUT>(j.out, pc.A, B, lo, cnt, acc);
+    }
+}
+
+#define PCHK(expr) MBPE_HIP_CHECK(expr, true)
+
+int fail(int code, const std::string &msg) {
+    mbpe_host::set_last_error(msg);
+    return code;
+}
+
+uint32_t pack_grid(const void *out, uint64_t n_out, uint32_t out_bits) {
+    const uint64_t A = (uint64_t)(uintptr_t)out, E = A + n_out * (out_bits / 8);
+    const uint64_t n_pieces = (E - (A & ~15ull) + 15) >> 4;
+    return (uint32_t)std::min<uint64_t>((n_pieces + kPackThreads - 1) / kPackThreads, kPackMaxGrid);
+}
+
+template <int IN, int OUT>
+void launch_pack(hipStream_t stream, bool packed, const PackJob &j) {
+    const dim3 grid(pack_grid(j.out, j.n_out, OUT)), block(kPackThreads);
+    if (packed) hipLaunchKernelGGL((k_pack_stream<IN, OUT, false>), grid, block, 0, stream, j);
+    else hipLaunchKernelGGL((k_pack_padded<IN, OUT>), grid, block, 0, stream, j);
+}
+
+template <int IN, int OUT>
+void launch_unpack(hipStream_t stream, const PackJob &j) {
+    hipLaunchKernelGGL((k_pack_stream<IN, OUT, true>), dim3(pack_grid(j.out, j.n_out, OUT)), dim3(kPackThreads), 0, stream,
+                       j);
+}
+
+// device time of the calling thread's latest one-shot pack or unpack kernel (mbpe_pack_kernel_ms)
+thread_local float g_pack_ms = 0.f;
+
+int find_device(int device_id) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || device_id < 0 || device_id >= n_dev)
+        return fail(MBPE_ERR_NO_DEVICE, "no usable HIP device (the MI355X path has no CPU fallback)");
+    return MBPE_OK;
+}
+
+// the device side of a one-shot call: a stream, two events and the buffers it had to allocate, all released at its end
+struct OneShot {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::vector<void *> bufs;
+    ~OneShot() {
+        for (void *p : bufs) (void)hipFree(p);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+    int open(int device_id) {
+        PCHK(hipSetDevice(device_id));
+        PCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        PCHK(hipEventCreate(&ev0));
+        PCHK(hipEventCreate(&ev1));
+        return MBPE_OK;
+    }
+    // device memory for n bytes (at least one), filled from `host` when that is given
+    int alloc(void **out, uint64_t n, const void *host) {
+        *out = nullptr;
+        PCHK(hipMalloc(out, n ? n : 1));
+        bufs.push_back(*out);
+        if (host && n) PCHK(hipMemcpyAsync(*out, host, n, hipMemcpyHostToDevice, stream));
+        return MBPE_OK;
+    }
+    // what was enqueued between the events has run; its device time
+    int finish(float *ms) {
+        PCHK(hipStreamSynchronize(stream));
+        PCHK(hipGetLastError());
+        PCHK(hipEventElapsedTime(ms, ev0, ev1));
+        return MBPE_OK;
+    }
+};
+
+int pack_run(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
+             const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec &spec, void *ids_out, uint64_t n_rows,
+             int out_on_device, uint32_t *len_out) {
+    int rc = find_device(device_id);
+    if (rc != MBPE_OK) return rc;
+    OneShot dev;
+    rc = dev.open(device_id);
+    if (rc != MBPE_OK) return rc;
+    const uint64_t id_bytes = n_rows * spec.seq_len * (spec.out_bits / 8);
+    void *d_tok = const_cast<void *>(tokens), *d_off = nullptr, *d_ids = ids_out, *d_len = len_out;
+    if (!tokens_on_device) rc = dev.alloc(&d_tok, n_tokens * (token_bits / 8), tokens);
+    if (rc == MBPE_OK) rc = dev.alloc(&d_off, (n_docs + 1) * 8, doc_tok_off);
+    if (rc == MBPE_OK && !out_on_device) {
+        rc = dev.alloc(&d_ids, id_bytes, nullptr);
+        if (rc == MBPE_OK && len_out) rc = dev.alloc(&d_len, n_rows * 4, nullptr);
+    }
+    if (rc != MBPE_OK) return rc;
+    const PackSrc src = {d_tok, static_cast<const unsigned long long *>(d_off), n_docs, n_tokens, token_bits};
+    const PackDst dst = {d_ids, static_cast<uint32_t *>(d_len), n_rows};
+    PCHK(hipEventRecord(dev.ev0, dev.stream));
+    pack_launch(dev.stream, src, spec, dst);
+    PCHK(hipEventRecord(dev.ev1, dev.stream));
+    rc = dev.finish(&g_pack_ms);
+    if (rc != MBPE_OK) return rc;
+    if (!out_on_device) {
+        PCHK(hipMemcpyAsync(ids_out, d_ids, id_bytes, hipMemcpyDeviceToHost, dev.stream));
+        if (len_out) PCHK(hipMemcpyAsync(len_out, d_len, n_rows * 4, hipMemcpyDeviceToHost, dev.stream));
+        PCHK(hipStreamSynchronize(dev.stream));
+    }
+    return MBPE_OK;
+}
+
+int unpack_run(int device_id, const void *ids, uint64_t n_rows, uint32_t seq_len, uint32_t id_bits, int ids_on_device,
+               const uint32_t *len, void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device,
+               uint64_t *doc_tok_off_out, uint64_t *n_out) {
+    // the lengths decide everything else: those of a device matrix come to the host first
+    std::vector<uint32_t> len_host;
+    std::vector<uint64_t> off(n_rows + 1, 0);
+    if (ids_on_device && n_rows) {
+        int rc = find_device(device_id);
+        if (rc != MBPE_OK) return rc;
+        len_host.resize(n_rows);
+        PCHK(hipSetDevice(device_id));
+        PCHK(hipMemcpy(len_host.data(), len, n_rows * 4, hipMemcpyDeviceToHost));
+        len = len_host.data();
+    }
+    for (uint64_t r = 0; r < n_rows; ++r) {
+        if (len[r] > seq_len)
+            return fail(MBPE_ERR_ARG, "len[" + std::to_string(r) + "] = " + std::to_string(len[r]) + " exceeds seq_len");
+        off[r + 1] = off[r] + len[r];
+    }
+    const uint64_t n = off[n_rows];
+    *n_out = n;
+    if (doc_tok_off_out) std::copy(off.begin(), off.end(), doc_tok_off_out);
+    if (!tokens_out) return MBPE_OK;                             // the query
+    if (cap < n) return fail(MBPE_ERR_ARG, "tokens_out too small");
+    if (n == 0) return MBPE_OK;
+    if (out_on_device && (uint64_t)(uintptr_t)tokens_out % (token_bits / 8))
+        return fail(MBPE_ERR_ARG, "tokens_out is not aligned to its tokens");
+    int rc = find_device(device_id);
+    if (rc != MBPE_OK) return rc;
+    OneShot dev;
+    rc = dev.open(device_id);
+    if (rc != MBPE_OK) return rc;
+    void *d_ids = const_cast<void *>(ids), *d_off = nullptr, *d_tok = tokens_out;
+    if (!ids_on_device) rc = dev.alloc(&d_ids, n_rows * seq_len * (id_bits / 8), ids);
+    if (rc == MBPE_OK) rc = dev.alloc(&d_off, (n_rows + 1) * 8, off.data());
+    if (rc == MBPE_OK && !out_on_device) rc = dev.alloc(&d_tok, n * (token_bits / 8), nullptr);
+    if (rc != MBPE_OK) return rc;
+    PackJob j = {};
+    j.tok = d_ids;
+    j.doc_off = static_cast<const unsigned long long *>(d_off);
+    j.n_docs = n_rows;
+    j.n_stream = n;
+    j.out = d_tok;
+    j.n_out = n;
+    j.seq_len = seq_len;
+    PCHK(hipEventRecord(dev.ev0, dev.stream));
+    if (id_bits == 16 && token_bits == 16) launch_unpack<16, 16>(dev.stream, j);
+    else if (id_bits == 16) launch_unpack<16, 32>(dev.stream, j);
+    else if (id_bits == 32) launch_unpack<32, 32>(dev.stream, j);
+    else launch_unpack<64, 32>(dev.stream, j);
+    PCHK(hipEventRecord(dev.ev1, dev.stream));
+    rc = dev.finish(&g_pack_ms);
+    if (rc != MBPE_OK) return rc;
+    if (!out_on_device) {
+        PCHK(hipMemcpyAsync(tokens_out, d_tok, n * (token_bits / 8), hipMemcpyDeviceToHost, dev.stream));
+        PCHK(hipStreamSynchronize(dev.stream));
+    }
+    return MBPE_OK;
+}
+
+}  // namespace
+
+namespace mbpe {
+
+int pack_check_spec(const mbpe_pack_spec *spec, uint32_t token_bits) {
+    if (!spec) return fail(MBPE_ERR_ARG, "NULL pack spec");
+    if (token_bits != 16 && token_bits != 32) return fail(MBPE_ERR_ARG, "token_bits must be 16 or 32");
+    if (spec->layout != MBPE_PACK_PADDED && spec->layout != MBPE_PACK_PACKED)
+        return fail(MBPE_ERR_ARG, "no such pack layout");
+    if (spec->out_bits != 16 && spec->out_bits != 32 && spec->out_bits != 64)
+        return fail(MBPE_ERR_ARG, "out_bits must be 16, 32 or 64");
+    if (spec->seq_len == 0) return fail(MBPE_ERR_ARG, "seq_len must be at least 1");
+    const uint32_t nbe = (spec->bos_id != MBPE_NO_TOKEN) + (spec->eos_id != MBPE_NO_TOKEN);
+    if (spec->layout == MBPE_PACK_PADDED && spec->seq_len < nbe)
+        return fail(MBPE_ERR_ARG, "seq_len has no room for bos and eos");
+    if (spec->layout == MBPE_PACK_PACKED && (spec->pad_left || spec->trunc_left))
+        return fail(MBPE_ERR_ARG, "pad_left and trunc_left go with MBPE_PACK_PADDED only");
+    if (spec->out_bits == 16) {
+        if (token_bits == 32) return fail(MBPE_ERR_VOCAB, "out_bits 16 with 32-bit tokens");
+        if (spec->pad_id >= 65536u || (spec->bos_id != MBPE_NO_TOKEN && spec->bos_id >= 65536u) ||
+            (spec->eos_id != MBPE_NO_TOKEN && spec->eos_id >= 65536u))
+            return fail(MBPE_ERR_VOCAB, "out_bits 16 with a pad, bos or eos id that does not fit 16 bits");
+    }
+    return MBPE_OK;
+}
+
+uint64_t pack_rows(const mbpe_pack_spec &spec, uint64_t n_tokens, uint64_t n_docs) {
+    if (spec.layout == MBPE_PACK_PADDED) return n_docs;
+    const uint64_t nbe = (spec.bos_id != MBPE_NO_TOKEN) + (spec.eos_id != MBPE_NO_TOKEN);
+    return (n_tokens + n_docs * nbe + spec.seq_len - 1) / spec.seq_len;
+}
+
+void pack_launch(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst) {
+    PackJob j = {};
+    j.tok = src.tok;
+    j.doc_off = src.doc_off;
+    j.n_docs = src.n_docs;
+    j.out = dst.ids;
+    j.len = dst.len;
+    j.n_out = dst.n_rows * spec.seq_len;
+    j.seq_len = spec.seq_len;
+    j.pad = spec.pad_id;
+    j.nb = spec.bos_id != MBPE_NO_TOKEN;
+    j.ne = spec.eos_id != MBPE_NO_TOKEN;
+    j.bos = spec.bos_id;
+    j.eos = spec.eos_id;
+    j.n_stream = src.n_tokens + src.n_docs * (uint64_t)(j.nb + j.ne);
+    j.keep = spec.seq_len - j.nb - j.ne;                         // (PADDED: checked; PACKED does not read it)
+    j.pad_left = spec.pad_left != 0;
+    j.trunc_left = spec.trunc_left != 0;
+    const bool packed = spec.layout == MBPE_PACK_PACKED;
+    if (src.bits == 16) {
+        if (spec.out_bits == 16) launch_pack<16, 16>(stream, packed, j);
+        else if (spec.out_bits == 32) launch_pack<16, 32>(stream, packed, j);
+        else launch_pack<16, 64>(stream, packed, j);
+    } else {
+        if (spec.out_bits == 32) launch_pack<32, 32>(stream, packed, j);
+        else launch_pack<32, 64>(stream, packed, j);
+    }
+}
+
+}  // namespace mbpe
+
+namespace mbpe_host {
+
+int device_alloc(int device_id, uint64_t n_bytes, void **out) {
+    *out = nullptr;
+    const int rc = find_device(device_id);
+    if (rc != MBPE_OK) return rc;
+    PCHK(hipSetDevice(device_id));
+    PCHK(hipMalloc(out, n_bytes ? n_bytes : 1));
+    return MBPE_OK;
+}
+
+void device_free(void *p) { (void)hipFree(p); }
+
+}  // namespace mbpe_host
+
+extern "C" {
+
+int mbpe_pack_tokens(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
+                     const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
+                     uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (!n_rows_out || !doc_tok_off || !spec || (!tokens && n_tokens))
+        return fail(MBPE_ERR_ARG, "mbpe_pack_tokens: NULL argument");
+    int rc = pack_check_spec(spec, token_bits);
+    if (rc == MBPE_OK) rc = mbpe_host::check_doc_tok_off(doc_tok_off, n_docs, n_tokens);
+    if (rc != MBPE_OK) return rc;
+    if (n_tokens >> 40 || n_docs >> 40) return fail(MBPE_ERR_ARG, "more than 2^40 tokens or documents");
+    const uint64_t n_rows = pack_rows(*spec, n_tokens, n_docs);
+    *n_rows_out = n_rows;
+    if (!ids_out) return MBPE_OK;                                // the query
+    if (cap_rows < n_rows) return fail(MBPE_ERR_ARG, "ids_out too small");
+    if (n_rows == 0) return MBPE_OK;
+    if (out_on_device && ((uint64_t)(uintptr_t)ids_out % (spec->out_bits / 8) || (uint64_t)(uintptr_t)len_out % 4))
+        return fail(MBPE_ERR_ARG, "ids_out or len_out is not aligned to its elements");
+    try {
+        return pack_run(device_id, tokens, n_tokens, token_bits, tokens_on_device, doc_tok_off, n_docs, *spec, ids_out,
+                        n_rows, out_on_device, len_out);
+    } catch (const std::bad_alloc &) {
+        return fail(MBPE_ERR_OOM, "mbpe_pack_tokens: host allocation failed");
+    }
+}
+
+int mbpe_unpack_tokens(int device_id, const void *ids, uint64_t n_rows, uint32_t seq_len, uint32_t id_bits,
+                       int ids_on_device, const uint32_t *len, void *tokens_out, uint64_t cap, uint32_t token_bits,
+                       int out_on_device, uint64_t *doc_tok_off_out, uint64_t *n_out) {
+    if (n_out) *n_out = 0;
+    if (!n_out || ((!ids || !len) && n_rows)) return fail(MBPE_ERR_ARG, "mbpe_unpack_tokens: NULL argument");
+    if (id_bits != 16 && id_bits != 32 && id_bits != 64) return fail(MBPE_ERR_ARG, "id_bits must be 16, 32 or 64");
+    if (token_bits != 16 && token_bits != 32) return fail(MBPE_ERR_ARG, "token_bits must be 16 or 32");
+    if (seq_len == 0) return fail(MBPE_ERR_ARG, "seq_len must be at least 1");
+    if (n_rows >> 40) return fail(MBPE_ERR_ARG, "more than 2^40 rows");
+    if (token_bits == 16 && id_bits != 16) return fail(MBPE_ERR_VOCAB, "token_bits 16 with wider ids");
+    try {
+        return unpack_run(device_id, ids, n_rows, seq_len, id_bits, ids_on_device, len, tokens_out, cap, token_bits,
+                          out_on_device, doc_tok_off_out, n_out);
+    } catch (const std::bad_alloc &) {
+        return fail(MBPE_ERR_OOM, "mbpe_unpack_tokens: host allocation failed");
+    }
+}
+
+int mbpe_pack_kernel_ms(float *ms_out) {
+    if (!ms_out) return fail(MBPE_ERR_ARG, "mbpe_pack_kernel_ms: NULL argument");
+    *ms_out = g_pack_ms;
+    return MBPE_OK;
+}
+
+}  // extern "C"

@@ -38,6 +38,10 @@ int decode_to_string(mbpe_decoder *d, const uint32_t *tokens, uint64_t n, std::s
 // MBPE_OK, or MBPE_ERR_ARG with the last error set.  Touches no device
 int check_doc_tok_off(const uint64_t *doc_tok_off, uint64_t n_docs, uint64_t n_tokens);
 
+// device memory of HIP device `device` for host code that only hands it on (csrc/pack.hip); an mbpe_status
+int device_alloc(int device, uint64_t n_bytes, void **out);
+void device_free(void *p);
+
 // Tokenizer.h:59-60; nullptr for an unknown encoder name
 const char *split_pattern_for(const std::string &encoder);
 

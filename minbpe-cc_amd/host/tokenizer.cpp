@@ -304,19 +304,26 @@ std::vector<Token> Tokenizer::encode(const std::string &text, bool verbose, int 
     return out;
 }
 
+void Tokenizer::batch_chunks(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, std::string *buf,
+                             std::vector<uint64_t> *off, std::vector<uint64_t> *first_chunk) const {
+    // every text is split on its own (a chunk never spans two texts)
+    off->assign(1, 0);
+    first_chunk->assign(n_docs + 1, 0);
+    buf->reserve(doc_off[n_docs] - doc_off[0] + 64);
+    for (uint64_t i = 0; i < n_docs; ++i) {
+        (*first_chunk)[i] = off->size() - 1;
+        if (doc_off[i + 1] > doc_off[i])                          // (an empty text has no chunk: an empty result)
+            append_chunks(std::string(text + doc_off[i], doc_off[i + 1] - doc_off[i]), verbose, buf, off);
+    }
+    (*first_chunk)[n_docs] = off->size() - 1;
+}
+
 int Tokenizer::encode_batch_flat(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
                                  Token *tokens_out, uint64_t cap, uint64_t *n_out, uint64_t *buf_bytes_out,
                                  std::vector<uint64_t> *doc_tok_off) {
-    // every text is split on its own (a chunk never spans two texts); first_chunk[i] = its first chunk
     std::string buf;
-    std::vector<uint64_t> off{0}, first_chunk(n_docs + 1, 0);
-    buf.reserve(doc_off[n_docs] - doc_off[0] + 64);
-    for (uint64_t i = 0; i < n_docs; ++i) {
-        first_chunk[i] = off.size() - 1;
-        if (doc_off[i + 1] > doc_off[i])                          // (an empty text has no chunk: an empty result)
-            append_chunks(std::string(text + doc_off[i], doc_off[i + 1] - doc_off[i]), verbose, &buf, &off);
-    }
-    first_chunk[n_docs] = off.size() - 1;
+    std::vector<uint64_t> off, first_chunk;
+    batch_chunks(text, doc_off, n_docs, verbose, &buf, &off, &first_chunk);
     if (buf_bytes_out) *buf_bytes_out = buf.size();
     mbpe_encoder *enc = device_encoder(device);
     std::vector<uint64_t> chunk_tok_off(off.size(), 0);
@@ -327,6 +334,24 @@ int Tokenizer::encode_batch_flat(const char *text, const uint64_t *doc_off, uint
     for (uint64_t i = 0; i <= n_docs; ++i) (*doc_tok_off)[i] = chunk_tok_off[first_chunk[i]];
     if (verbose) std::cout << "Encoded " << n_docs << " texts (length " << buf.size() << ") to " << *n_out << " tokens\n";
     return MBPE_OK;
+}
+
+int Tokenizer::encode_batch_packed(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
+                                   const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
+                                   uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out) {
+    std::string buf;
+    std::vector<uint64_t> off, first_chunk;
+    batch_chunks(text, doc_off, n_docs, verbose, &buf, &off, &first_chunk);
+    mbpe_encoder *enc = device_encoder(device);
+    uint64_t n_tokens = 0;
+    const int rc = mbpe_encoder_encode_batch(enc, reinterpret_cast<const uint8_t *>(buf.data()), buf.size(), 0, off.data(),
+                                             off.size() - 1, first_chunk.data(), n_docs, spec, ids_out, cap_rows,
+                                             out_on_device, len_out, n_rows_out, &n_tokens);
+    if (n_tokens_out) *n_tokens_out = n_tokens;
+    if (rc == MBPE_OK && verbose)
+        std::cout << "Encoded " << n_docs << " texts (length " << buf.size() << ") to " << n_tokens << " tokens in "
+                  << *n_rows_out << " rows\n";
+    return rc;
 }
 
 std::vector<std::vector<Token>> Tokenizer::encode_batch(const std::vector<std::string> &texts, bool verbose, int device) {
@@ -380,6 +405,28 @@ int Tokenizer::decode_batch_flat(const Token *tokens, const uint64_t *doc_tok_of
     const int rc = mbpe_decode_batch(device_decoder(device), tokens, n, 32, 0, doc_tok_off, n_docs, bytes_out, cap, 0,
                                      doc_byte_off_out, n_out, &n_invalid);
     if (n_invalid) warn_invalid(tokens, n);         // (counted whenever the lengths were: also when cap is too small)
+    return rc;
+}
+
+int Tokenizer::decode_padded(const Token *ids, uint64_t n_rows, uint32_t seq_len, const uint32_t *len, bool verbose,
+                             int device, uint8_t *bytes_out, uint64_t cap, uint64_t *doc_byte_off_out, uint64_t *n_out) {
+    std::vector<uint64_t> tok_off(n_rows + 1, 0);
+    uint64_t n = 0;
+    int rc = mbpe_unpack_tokens(device, ids, n_rows, seq_len, 32, 0, len, nullptr, 0, 32, 0, tok_off.data(), &n);
+    if (rc != MBPE_OK) return rc;                   // (a length beyond seq_len: before a decoder is created)
+    if (verbose) std::cout << "Decoding " << n << " tokens of " << n_rows << " rows\n";
+    mbpe_decoder *dec = device_decoder(device);
+    void *d_tok = nullptr;
+    rc = device_alloc(device, n * sizeof(Token), &d_tok);
+    if (rc != MBPE_OK) return rc;
+    rc = mbpe_unpack_tokens(device, ids, n_rows, seq_len, 32, 0, len, d_tok, n, 32, 1, nullptr, &n);
+    uint64_t n_invalid = 0;
+    if (rc == MBPE_OK)
+        rc = mbpe_decode_batch(dec, d_tok, n, 32, 1, tok_off.data(), n_rows, bytes_out, cap, 0, doc_byte_off_out, n_out,
+                               &n_invalid);
+    device_free(d_tok);
+    if (n_invalid)
+        for (uint64_t r = 0; r < n_rows; ++r) warn_invalid(ids + r * seq_len, len[r]);
     return rc;
 }
 
@@ -625,6 +672,50 @@ int mbpe_tok_encode_batch_device(mbpe_tokenizer *t, const uint8_t *text, const u
         if (doc_tok_off_out) memcpy(doc_tok_off_out, tok_off.data(), tok_off.size() * sizeof(uint64_t));
         return MBPE_OK;
     } catch (const mbpe_host::CodedError &e) {      // mbpe_encoder_create failed: its own code
+        mbpe_host::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        mbpe_host::set_last_error(e.what());
+        return MBPE_ERR_ARG;
+    }
+}
+
+int mbpe_tok_encode_batch_packed_device(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off, uint64_t n_docs,
+                                        int verbose, int device_id, const mbpe_pack_spec *spec, void *ids_out,
+                                        uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                                        uint64_t *n_tokens_out) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!t || !n_rows_out || !doc_off || !spec || device_id < 0 || (!text && doc_off[n_docs] > doc_off[0])) {
+        mbpe_host::set_last_error("mbpe_tok_encode_batch_packed_device: NULL argument or negative device");
+        return MBPE_ERR_ARG;
+    }
+    for (uint64_t i = 0; i < n_docs; ++i)
+        if (doc_off[i + 1] < doc_off[i]) { mbpe_host::set_last_error("doc_off must be ascending"); return MBPE_ERR_ARG; }
+    try {
+        return t->t->encode_batch_packed(reinterpret_cast<const char *>(text), doc_off, n_docs, verbose != 0, device_id,
+                                         spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out);
+    } catch (const mbpe_host::CodedError &e) {      // mbpe_encoder_create failed: its own code
+        mbpe_host::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        mbpe_host::set_last_error(e.what());
+        return MBPE_ERR_ARG;
+    }
+}
+
+int mbpe_tok_decode_padded_device(mbpe_tokenizer *t, const uint32_t *ids, uint64_t n_rows, uint32_t seq_len,
+                                  const uint32_t *len, int verbose, int device_id, uint8_t *bytes_out, uint64_t cap,
+                                  uint64_t *doc_byte_off_out, uint64_t *n_out) {
+    if (n_out) *n_out = 0;
+    if (!t || !n_out || !doc_byte_off_out || device_id < 0 || ((!ids || !len) && n_rows)) {
+        mbpe_host::set_last_error("mbpe_tok_decode_padded_device: NULL argument or negative device");
+        return MBPE_ERR_ARG;
+    }
+    try {
+        return t->t->decode_padded(ids, n_rows, seq_len, len, verbose != 0, device_id, bytes_out, cap, doc_byte_off_out,
+                                   n_out);
+    } catch (const mbpe_host::CodedError &e) {      // mbpe_decoder_create failed: its own code
         mbpe_host::set_last_error(e.what());
         return e.code;
     } catch (const std::exception &e) {

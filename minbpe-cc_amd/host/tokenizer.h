@@ -11,6 +11,7 @@
 #include <utility>
 #include <vector>
 
+#include "mbpe.h"
 #include "mbpe_host.h"
 
 namespace mbpe_host {
@@ -42,6 +43,11 @@ public:
     int encode_batch_flat(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
                           Token *tokens_out, uint64_t cap, uint64_t *n_out, uint64_t *buf_bytes_out,
                           std::vector<uint64_t> *doc_tok_off);
+    // the same documents as one id matrix (mbpe_encoder_encode_batch): spec, ids_out .. n_tokens_out go to it as they
+    // are, its code is returned
+    int encode_batch_packed(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
+                            const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
+                            uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out);
     // :725-751; device >= 0 expands the tokens on that HIP device (mbpe_decode_tokens) instead of the host loop
     std::string decode(const std::vector<Token> &tokens, bool verbose, int device = -1);
     // decode() of every token list, [i] == decode(docs[i], false, -1), in one mbpe_decode_batch on HIP device `device`
@@ -50,6 +56,10 @@ public:
     // doc_byte_off_out / n_out go to mbpe_decode_batch as they are (NULL bytes_out: query), whose code is returned
     int decode_batch_flat(const Token *tokens, const uint64_t *doc_tok_off, uint64_t n_docs, bool verbose, int device,
                           uint8_t *bytes_out, uint64_t cap, uint64_t *doc_byte_off_out, uint64_t *n_out);
+    // a right-padded matrix of n_rows x seq_len host ids with its lengths: mbpe_unpack_tokens into device memory, then
+    // one mbpe_decode_batch of it as it is; row r's text is bytes_out[doc_byte_off_out[r] .. doc_byte_off_out[r + 1])
+    int decode_padded(const Token *ids, uint64_t n_rows, uint32_t seq_len, const uint32_t *len, bool verbose, int device,
+                      uint8_t *bytes_out, uint64_t cap, uint64_t *doc_byte_off_out, uint64_t *n_out);
     bool load(const std::string &path, bool verbose);                      // :754-872
     bool save(const std::string &path, bool write_vocab);                  // :875-926
 
@@ -74,6 +84,9 @@ private:
     void rebuild_vocab();
     void drop_decoder();                   // the merges or the specials changed
     void drop_encoder();                   // the merges changed (special tokens do not enter the lookup table)
+    // the chunks of n_docs texts (every text split on its own) as one buffer + offsets; first_chunk[i] = text i's first
+    void batch_chunks(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, std::string *buf,
+                      std::vector<uint64_t> *off, std::vector<uint64_t> *first_chunk) const;
     // the chunks of one text appended to buf / off: special markers and, with a pattern, the regex matches of every
     // other part (:664-704); without one, every part is a chunk (:706-709)
     void append_chunks(const std::string &text, bool verbose, std::string *buf, std::vector<uint64_t> *off) const;

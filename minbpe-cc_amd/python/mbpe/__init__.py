@@ -31,12 +31,14 @@ EXPORTS = [
     "mbpe_decode_slots", "mbpe_decoder_kernel_ms", "mbpe_decode_stream", "mbpe_encoder_create",
     "mbpe_encoder_destroy", "mbpe_encoder_encode", "mbpe_encoder_set_option", "mbpe_encoder_kernel_ms",
     "mbpe_encoder_alloc_count", "mbpe_encoder_pass_tokens", "mbpe_decode_batch", "mbpe_decoder_alloc_count",
+    "mbpe_pack_tokens", "mbpe_unpack_tokens", "mbpe_pack_kernel_ms", "mbpe_encoder_encode_batch", "mbpe_encoder_pack_ms",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
     "mbpe_tok_create", "mbpe_tok_destroy", "mbpe_tok_set_special_tokens", "mbpe_tok_train", "mbpe_tok_set_merges",
     "mbpe_tok_get_merges", "mbpe_tok_save", "mbpe_tok_load", "mbpe_tok_encode", "mbpe_tok_encode_device",
     "mbpe_tok_decode", "mbpe_tok_decode_device", "mbpe_tok_encode_batch_device", "mbpe_tok_decode_batch_device",
+    "mbpe_tok_encode_batch_packed_device", "mbpe_tok_decode_padded_device",
 ]
 
 
@@ -63,6 +65,33 @@ class Stats(ctypes.Structure):
         d["size_hist"] = list(self.size_hist)
         return d
 
+
+
+PACK_PADDED, PACK_PACKED = 0, 1
+NO_TOKEN = 0xFFFFFFFF
+
+
+class PackSpec(ctypes.Structure):
+    """mbpe_pack_spec (include/mbpe.h)."""
+    _fields_ = [
+        ("layout", ctypes.c_uint32), ("seq_len", ctypes.c_uint32), ("out_bits", ctypes.c_uint32),
+        ("pad_id", ctypes.c_uint32), ("bos_id", ctypes.c_uint32), ("eos_id", ctypes.c_uint32),
+        ("pad_left", ctypes.c_uint32), ("trunc_left", ctypes.c_uint32),
+    ]
+
+
+_ID_DTYPES = {16: np.uint16, 32: np.uint32, 64: np.uint64}
+
+
+def pack_spec(seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None, pad_left=False,
+              trunc_left=False):
+    """A PackSpec from keywords; layout "padded" / "packed" (or the number), bos_id / eos_id None = none."""
+    if isinstance(layout, str):
+        if layout not in ("padded", "packed"):
+            raise ValueError("layout must be \"padded\" or \"packed\"")
+        layout = PACK_PADDED if layout == "padded" else PACK_PACKED
+    return PackSpec(layout, seq_len, out_bits, pad_id, NO_TOKEN if bos_id is None else bos_id,
+                    NO_TOKEN if eos_id is None else eos_id, int(bool(pad_left)), int(bool(trunc_left)))
 
 
 class MbpeError(RuntimeError):
@@ -133,6 +162,13 @@ def lib():
     L.mbpe_encoder_kernel_ms.argtypes = [vp, vp]
     L.mbpe_encoder_alloc_count.argtypes = [vp, vp]
     L.mbpe_encoder_pass_tokens.argtypes = [vp, vp, u32, vp]
+    L.mbpe_pack_tokens.argtypes = [i32, vp, u64, u32, i32, vp, u64, vp, vp, u64, i32, vp, vp]
+    L.mbpe_unpack_tokens.argtypes = [i32, vp, u64, u32, u32, i32, vp, vp, u64, u32, i32, vp, vp]
+    L.mbpe_pack_kernel_ms.argtypes = [vp]
+    L.mbpe_encoder_encode_batch.argtypes = [vp, vp, u64, i32, vp, u64, vp, u64, vp, vp, u64, i32, vp, vp, vp]
+    L.mbpe_encoder_pack_ms.argtypes = [vp, vp]
+    L.mbpe_tok_encode_batch_packed_device.argtypes = [vp, vp, vp, u64, i32, i32, vp, vp, u64, i32, vp, vp, vp]
+    L.mbpe_tok_decode_padded_device.argtypes = [vp, vp, u64, u32, vp, i32, i32, vp, u64, vp, vp]
     L.mbpe_tok_encode_batch_device.argtypes = [vp, vp, vp, u64, i32, i32, vp, u64, vp, vp]
     L.mbpe_decoder_create.argtypes = [i32, vp, u32, vp, vp, vp, u32, ctypes.POINTER(vp)]
     L.mbpe_decoder_destroy.argtypes = [vp]
@@ -241,6 +277,83 @@ def encode_chunks_device(data, chunk_off, merges, out_ptr, cap, device=0):
     return n.value, passes.value
 
 
+def _ptr(p):
+    return ctypes.c_void_p(p) if p else None
+
+
+def _matrix(n_rows, spec):
+    """Host arrays for n_rows rows of a spec: (ids [n_rows, seq_len], lengths [n_rows])."""
+    return (np.zeros((n_rows, spec.seq_len), dtype=_ID_DTYPES[spec.out_bits]), np.zeros(n_rows, dtype=np.uint32))
+
+
+def pack_tokens(tokens, doc_tok_off, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
+                pad_left=False, trunc_left=False, device=0, tokens_ptr=None, n_tokens=None, token_bits=None,
+                out_ptr=None, len_ptr=None, cap_rows=None):
+    """mbpe_pack_tokens: a flat token array (uint16 or uint32) whose document i is tokens[doc_tok_off[i]:
+    doc_tok_off[i + 1]] -> (ids [n_rows, seq_len] of out_bits bits, lengths [n_rows]) as numpy arrays.
+    Device memory: tokens_ptr= / n_tokens= / token_bits= name the tokens there instead of `tokens`; with out_ptr= (and
+    len_ptr=, room for cap_rows rows) the matrix is written there and the row count is returned."""
+    spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    if tokens_ptr is None:
+        t = np.ascontiguousarray(tokens)
+        if t.dtype not in (np.dtype(np.uint16), np.dtype(np.uint32)):
+            t = t.astype(np.uint32)
+        t = t.reshape(-1)
+        tp, n_tokens, token_bits, on_dev = (t.ctypes.data if len(t) else None), len(t), t.dtype.itemsize * 8, 0
+    else:
+        tp, on_dev = _ptr(tokens_ptr), 1
+    n_rows = ctypes.c_uint64()
+    head = (device, tp, n_tokens, token_bits, on_dev, off.ctypes.data, len(off) - 1, ctypes.byref(spec))
+    if out_ptr is not None:
+        _check(lib().mbpe_pack_tokens(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), ctypes.byref(n_rows)))
+        return n_rows.value
+    _check(lib().mbpe_pack_tokens(*head, None, 0, 0, None, ctypes.byref(n_rows)))
+    ids, lengths = _matrix(n_rows.value, spec)
+    if n_rows.value:
+        _check(lib().mbpe_pack_tokens(*head, ids.ctypes.data, n_rows.value, 0, lengths.ctypes.data,
+                                      ctypes.byref(n_rows)))
+    return ids, lengths
+
+
+def unpack_tokens(ids, lengths, dtype=np.uint32, device=0, ids_ptr=None, len_ptr=None, shape=None, id_bits=None,
+                  out_ptr=None, cap=0):
+    """mbpe_unpack_tokens: a right-padded matrix ids [n_rows, seq_len] (uint16 / uint32 / uint64) and its lengths ->
+    (tokens of dtype uint32 or uint16, doc_tok_off [n_rows + 1]).  Device memory: ids_ptr= / len_ptr= / shape= /
+    id_bits= name the matrix there; with out_ptr= (room for cap tokens) the tokens are written there and (token count,
+    doc_tok_off) is returned -- what Decoder.decode_batch_device takes."""
+    dtype = np.dtype(dtype)
+    if ids_ptr is None:
+        m = np.ascontiguousarray(ids)
+        if m.dtype not in (np.dtype(np.uint16), np.dtype(np.uint32), np.dtype(np.uint64)):
+            m = m.astype(np.uint32)
+        n_rows, seq_len = m.shape
+        ln = np.ascontiguousarray(lengths, dtype=np.uint32)
+        ip, lp, id_bits, on_dev = (m.ctypes.data if m.size else None), (ln.ctypes.data if len(ln) else None), \
+            m.dtype.itemsize * 8, 0
+    else:
+        (n_rows, seq_len), ip, lp, on_dev = shape, _ptr(ids_ptr), _ptr(len_ptr), 1
+    off = np.zeros(n_rows + 1, dtype=np.uint64)
+    n = ctypes.c_uint64()
+    head = (device, ip, n_rows, seq_len, id_bits, on_dev, lp)
+    if out_ptr is not None:
+        _check(lib().mbpe_unpack_tokens(*head, _ptr(out_ptr), cap, dtype.itemsize * 8, 1, off.ctypes.data,
+                                        ctypes.byref(n)))
+        return n.value, off
+    _check(lib().mbpe_unpack_tokens(*head, None, 0, dtype.itemsize * 8, 0, off.ctypes.data, ctypes.byref(n)))
+    out = np.zeros(max(n.value, 1), dtype=dtype)
+    _check(lib().mbpe_unpack_tokens(*head, out.ctypes.data, n.value, dtype.itemsize * 8, 0, off.ctypes.data,
+                                    ctypes.byref(n)))
+    return out[:n.value], off
+
+
+def pack_kernel_ms():
+    """Device time of this thread's latest pack_tokens / unpack_tokens kernel (mbpe_pack_kernel_ms)."""
+    ms = ctypes.c_float()
+    _check(lib().mbpe_pack_kernel_ms(ctypes.byref(ms)))
+    return ms.value
+
+
 class Encoder:
     """One mbpe_encoder: internal_encode (Tokenizer.h:325-377) on a HIP device with the lookup table, the stream and
     the work buffers kept between calls."""
@@ -250,6 +363,7 @@ class Encoder:
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1, 2)
         _check(lib().mbpe_encoder_create(device, m.ctypes.data if len(m) else None, len(m), ctypes.byref(self._h)))
         self.n_passes = 0
+        self.n_tokens = 0
 
     def close(self):
         if self._h:
@@ -307,6 +421,56 @@ class Encoder:
                                          ctypes.byref(n), ctypes.byref(passes)))
         self.n_passes = passes.value
         return (n.value, tok_off) if offsets else n.value
+
+    def encode_batch(self, texts_or_buffer, chunk_off=None, doc_chunk_off=None, *, seq_len, layout="padded",
+                     out_bits=32, pad_id=0, bos_id=None, eos_id=None, pad_left=False, trunc_left=False,
+                     text_ptr=None, n_bytes=None, out_ptr=None, len_ptr=None, cap_rows=None):
+        """Encode and pack in one device call (mbpe_encoder_encode_batch) -> (ids [n_rows, seq_len], lengths [n_rows]) as
+        numpy arrays; the tokens encoded: self.n_tokens.
+        texts_or_buffer: a list of texts, each one document and one chunk; or one buffer with chunk_off (as for
+        encode) and doc_chunk_off, n_docs + 1 chunk indices: document i is the chunks doc_chunk_off[i] ..
+        doc_chunk_off[i + 1] (None: every chunk a document).  text_ptr= / n_bytes= name a buffer in device memory
+        instead.  With out_ptr= and len_ptr= (device memory for cap_rows rows, e.g. a torch tensor's data_ptr()) the
+        matrix is written there and the row count is returned."""
+        spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
+        if text_ptr is None and isinstance(texts_or_buffer, (list, tuple)):
+            parts = [bytes(_u8(t)) for t in texts_or_buffer]
+            chunk_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+            if parts:
+                chunk_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
+            texts_or_buffer, doc_chunk_off = b"".join(parts), None
+        if text_ptr is None:
+            text = _u8(texts_or_buffer)
+            tp, n_bytes, on_dev = (text.ctypes.data if len(text) else None), len(text), 0
+        else:
+            tp, on_dev = _ptr(text_ptr), 1
+        off = np.array([0, n_bytes], dtype=np.uint64) if chunk_off is None else \
+            np.ascontiguousarray(chunk_off, dtype=np.uint64)
+        docs = np.arange(len(off), dtype=np.uint64) if doc_chunk_off is None else \
+            np.ascontiguousarray(doc_chunk_off, dtype=np.uint64)
+        n_rows, n_tok = ctypes.c_uint64(), ctypes.c_uint64()
+        head = (self._h, tp, n_bytes, on_dev, off.ctypes.data, len(off) - 1, docs.ctypes.data, len(docs) - 1,
+                ctypes.byref(spec))
+        tail = (ctypes.byref(n_rows), ctypes.byref(n_tok))
+        if out_ptr is not None:
+            _check(lib().mbpe_encoder_encode_batch(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail))
+            self.n_tokens = n_tok.value
+            return n_rows.value
+        if spec.layout == PACK_PADDED:
+            n_rows.value = len(docs) - 1              # known without a query
+        else:
+            _check(lib().mbpe_encoder_encode_batch(*head, None, 0, 0, None, *tail))
+        ids, lengths = _matrix(n_rows.value, spec)
+        _check(lib().mbpe_encoder_encode_batch(*head, ids.ctypes.data if ids.size else None, len(ids), 0,
+                                               lengths.ctypes.data if len(ids) else None, *tail))
+        self.n_tokens = n_tok.value
+        return ids, lengths
+
+    def pack_ms(self):
+        """Device time of the pack kernel of the latest encode_batch (mbpe_encoder_pack_ms)."""
+        ms = ctypes.c_float()
+        _check(lib().mbpe_encoder_pack_ms(self._h, ctypes.byref(ms)))
+        return ms.value
 
     def kernel_ms(self):
         """Device time of the latest call (mbpe_encoder_kernel_ms)."""
@@ -703,6 +867,51 @@ class Tokenizer:
                                                   len(parts), 0, device, out.ctypes.data, len(out), tok_off.ctypes.data,
                                                   ctypes.byref(n)))
         return [out[int(a):int(b)].copy() for a, b in zip(tok_off[:-1], tok_off[1:])]
+
+    def encode_batch_padded(self, texts, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
+                            pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None):
+        """Every text split like encode(), encoded and packed in one device call
+        (mbpe_tok_encode_batch_packed_device) -> (ids [n_rows, seq_len], lengths [n_rows]) as numpy arrays; with
+        out_ptr= and len_ptr= (device memory for cap_rows rows) the matrix stays on the device and the row count is
+        returned.  bos_id / eos_id may be special-token ids.  layout "packed" gives the MBPE_PACK_PACKED rows."""
+        spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
+        parts = [bytes(_u8(t)) for t in texts]
+        doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        if parts:
+            doc_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
+        text = np.frombuffer(b"".join(parts), dtype=np.uint8)
+        n_rows, n_tok = ctypes.c_uint64(), ctypes.c_uint64()
+        head = (self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data, len(parts), 0, device,
+                ctypes.byref(spec))
+        tail = (ctypes.byref(n_rows), ctypes.byref(n_tok))
+        if out_ptr is not None:
+            _check(lib().mbpe_tok_encode_batch_packed_device(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail))
+            return n_rows.value
+        if spec.layout == PACK_PADDED:
+            n_rows.value = len(parts)
+        else:
+            _check(lib().mbpe_tok_encode_batch_packed_device(*head, None, 0, 0, None, *tail))
+        ids, lengths = _matrix(n_rows.value, spec)
+        _check(lib().mbpe_tok_encode_batch_packed_device(*head, ids.ctypes.data if ids.size else None, len(ids), 0,
+                                                         lengths.ctypes.data if len(ids) else None, *tail))
+        return ids, lengths
+
+    def decode_padded(self, ids, lengths, device=0):
+        """A right-padded id matrix [n_rows, seq_len] and its lengths -> the list of the rows' texts, unpacked and
+        decoded on the device (mbpe_tok_decode_padded_device); the mirror of encode_batch_padded."""
+        m = np.ascontiguousarray(ids, dtype=np.uint32)
+        n_rows, seq_len = m.shape
+        ln = np.ascontiguousarray(lengths, dtype=np.uint32)
+        if len(ln) != n_rows:
+            raise ValueError("one length per row")
+        byte_off = np.zeros(n_rows + 1, dtype=np.uint64)
+        n = ctypes.c_uint64()
+        args = (self._h, m.ctypes.data if m.size else None, n_rows, seq_len, ln.ctypes.data if n_rows else None, 0, device)
+        _check(lib().mbpe_tok_decode_padded_device(*args, None, 0, byte_off.ctypes.data, ctypes.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        _check(lib().mbpe_tok_decode_padded_device(*args, out.ctypes.data, len(out), byte_off.ctypes.data, ctypes.byref(n)))
+        data = out[:n.value].tobytes()
+        return [data[int(a):int(b)] for a, b in zip(byte_off[:-1], byte_off[1:])]
 
     def decode(self, tokens, device=None):
         """device None: the host loop; an int: on that HIP device (mbpe_tok_decode_device)."""
