@@ -95,6 +95,21 @@ Rccl &rccl() {
 }
 }  // namespace
 
+// The exchanges of the sharded protocol, each named for what the ranks sum.  A begin, a one-merge step and a
+// batch sequence are units of local parts with exchanges in between: phase_exchange() says what an exchange carries,
+// continue_after() what follows it.
+enum class Phase {
+    None,
+    BeginCounts,    // begin: the byte-pair tables, the rank edges, the pairs counted
+    BeginFirst,     // begin, `first`: every rank's earliest tied pair
+    StepDeltas,     // one-merge step: one pair's delta rows
+    StepFirst,      // one-merge step, `first`: every rank's earliest tied pair
+    SeqDeltas,      // batch sequence: the delta rows of the batch
+    SeqEdges,       // batch sequence: the rank edges
+};
+
+struct Exchange { uint32_t *buf; size_t words; };
+
 struct mbpe_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -167,7 +182,8 @@ struct mbpe_ctx {
     int rank = 0, n_ranks = 1;
     bool comm_external = false;           // the caller performs the all-reduce
     void *nccl_comm = nullptr;
-    int pending = 0;                      // external mode: 0 none, 1 begin, 2 step
+    Phase pending = Phase::None;          // external mode: the exchange the caller has been asked to make
+    Exchange pending_x = {};              // ... its buffer and size (phase_exchange, asked once when the call suspends)
     uint32_t pending_target = 0;          // external mode: merge count the pending call runs up to
 
     // options
@@ -305,6 +321,23 @@ int sync_ctl(mbpe_ctx *c) {
     return MBPE_OK;
 }
 
+// One group of sequences or steps between two host synchronisations: `enqueue` puts it on the stream, between the
+// events that time it; then the device's state and error flags are read back (h_ctl is current afterwards).
+template <typename Enqueue>
+int timed_group(mbpe_ctx *c, Enqueue enqueue) {
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    int rc = enqueue();
+    if (rc != MBPE_OK) return rc;
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    rc = sync_ctl(c);
+    if (rc != MBPE_OK) return rc;
+    HIPCHK(hipGetLastError());
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->stats.ms_steps += ms;
+    return MBPE_OK;
+}
+
 void free_training(mbpe_ctx *c) {
     tfree(c, c->tok[0]); tfree(c, c->tok[1]);
     tfree(c, c->sums); tfree(c, c->side); tfree(c, c->chg); tfree(c, c->tile_list);
@@ -325,7 +358,7 @@ void free_training(mbpe_ctx *c) {
     c->wn_upper = 0;
     c->h_wbest.clear();
     c->LR = nullptr;
-    c->pending = 0;
+    c->pending = Phase::None;
     c->begun = false;
     c->k = c->n_valid = 0;
     c->exhausted = false;
@@ -568,7 +601,7 @@ int mbpe_set_option(mbpe_ctx *c, const char *name, int64_t value) {
         if (value != 0 && value != 1) { mbpe_host::set_last_error("conflict_resolution: 0 = first, 1 = lexical"); return MBPE_ERR_ARG; }
         // (only while a training is under way: a finished one, or one whose table ran empty, can be followed by
         //  another mbpe_train_begin on the same corpus with the other tie-break)
-        if (c->begun && (c->pending || (c->k < c->n_target && !c->exhausted))) {
+        if (c->begun && (c->pending != Phase::None || (c->k < c->n_target && !c->exhausted))) {
             mbpe_host::set_last_error("conflict_resolution cannot change in the middle of a training");
             return MBPE_ERR_STATE;
         }
@@ -809,11 +842,13 @@ int mbpe_pair_count_u8(mbpe_ctx *c, uint32_t *table65536_out) {
 }
 
 // ---- training phases ---------------------------------------------------------
-// begin  = begin_local  -> [all-reduce xb0] -> begin_finish
-// step   = step_local   -> [all-reduce xb ] -> step_finish
-// With one rank the exchange is skipped.  With RCCL the three parts are
-// enqueued back to back on the context's stream; in external mode the
-// library stops after *_local so that the caller can reduce the buffer.
+// begin    = begin_local -> [BeginCounts] -> begin_finish_a -> [BeginFirst -> the tie-break's pick] -> begin_end
+// step     = step_local  -> [StepDeltas]  -> step_finish_a  -> [StepFirst  -> the tie-break's pick] -> k++
+// sequence = seq_stage_a -> [SeqDeltas]   -> seq_stage_b    -> [SeqEdges]   -> seq_stage_c
+// The *First exchanges exist with the `first` tie-break on a sharded stream only.  continue_after() is the one statement
+// of what follows an exchange.  With one rank the exchanges are skipped, with RCCL they are all-reduces enqueued between
+// the parts on the context's stream (finish_unit); in external mode the library stops at every exchange so that the
+// caller can reduce the buffer (suspend, mbpe_comm_exchange_done).
 
 // large tables: walk the block bounds instead of scanning every entry ("hier_argmax": -1 auto, 0 never, 1 always)
 static inline bool use_hier(const mbpe_ctx *c) {
@@ -821,6 +856,9 @@ static inline bool use_hier(const mbpe_ctx *c) {
     if (c->tab.cells) return c->tab.ecap > (1u << 20);
     return c->h_ctl.n_entries > (1u << 20);
 }
+
+// words of xb0, all of which the begin exchanges: [bp 65,536][header][pairs counted: kPairCountWords limbs]
+static size_t begin_exchange_words(const mbpe_ctx *c) { return 65536 + (size_t)c->hdr_words + kPairCountWords; }
 
 static int begin_local(mbpe_ctx *c, uint32_t vocab_size) {
     free_training(c);
@@ -861,7 +899,7 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size) {
     //  later, larger "max_batch" cannot reach beyond it.  2 x max_batch_eff x lr_pitch(vocab) words: 1.05 GB at the
     //  defaults with vocab 32,000, 262 MB with several ranks or "max_batch" 1024)
     const size_t xb_words = (size_t)c->hdr_words + c->hdrb_words + lr_words(vocab_size, c->max_batch_eff) + 8;
-    const size_t xb0_words = 65536 + (size_t)c->hdr_words + kPairCountWords;
+    const size_t xb0_words = begin_exchange_words(c);
     HIPCHK(tmalloc(c, &c->xb, xb_words * 4));
     HIPCHK(tmalloc(c, &c->xb0, xb0_words * 4));
     HIPCHK(hipMemsetAsync(c->xb, 0, xb_words * 4, c->stream));
@@ -985,8 +1023,7 @@ static void begin_finish_a(mbpe_ctx *c) {
     if (c->opt_first) first_tiebreak(c, c->best, 0, first_sharded(c) ? 1 : 0);
 }
 
-static int begin_finish_b(mbpe_ctx *c) {
-    if (first_sharded(c)) first_tiebreak(c, c->best, 0, 2);
+static int begin_end(mbpe_ctx *c) {
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     int rc = sync_ctl(c);
     if (rc != MBPE_OK) return rc;
@@ -999,18 +1036,6 @@ static int begin_finish_b(mbpe_ctx *c) {
     c->begun = true;
     c->stats.ms_steps = 0;
     return MBPE_OK;
-}
-
-static int comm_allreduce(mbpe_ctx *c, uint32_t *buf, size_t count);   // RCCL (below)
-
-// (one GPU, or several over RCCL; with an external transport the two parts are driven by mbpe_comm_exchange_done)
-static int begin_finish(mbpe_ctx *c) {
-    begin_finish_a(c);
-    if (first_sharded(c)) {
-        const int rc = comm_allreduce(c, c->xf, c->hdr_words);
-        if (rc != MBPE_OK) return rc;
-    }
-    return begin_finish_b(c);
 }
 
 static void step_local(mbpe_ctx *c, int ev_slot) {
@@ -1033,27 +1058,11 @@ static void step_finish_a(mbpe_ctx *c) {
     if (c->opt_first) first_tiebreak(c, c->best + c->k + 1, 0, first_sharded(c) ? 1 : 0);
 }
 
-static void step_finish_b(mbpe_ctx *c) {
-    if (first_sharded(c)) first_tiebreak(c, c->best + c->k + 1, 0, 2);
-    c->k++;
-}
-
-static int step_finish(mbpe_ctx *c) {       // (one GPU, or several over RCCL)
-    step_finish_a(c);
-    if (first_sharded(c)) {
-        const int rc = comm_allreduce(c, c->xf, c->hdr_words);
-        if (rc != MBPE_OK) return rc;
-    }
-    step_finish_b(c);
-    return MBPE_OK;
-}
-
 // words of xb a sequence has to exchange: both headers + the LR rows of its n_pairs members, lr_pitch(ids) cells each
 // (ids = 256 + merges done when the sequence started: the neighbours x that can occur)
 static size_t exchange_words(const mbpe_ctx *c, uint32_t ids, uint32_t n_pairs) {
     return (size_t)c->hdr_words + c->hdrb_words + (size_t)lr_words(ids, n_pairs);
 }
-static size_t step_exchange_words(const mbpe_ctx *c) { return exchange_words(c, 256 + c->k, 1); }
 
 // k_done / batch_n of the sequence whose selection has been enqueued: copied to pinned memory behind it
 static_assert(offsetof(DevCtl, batch_n) == offsetof(DevCtl, k_done) + 8 && offsetof(DevCtl, commit_n) == offsetof(DevCtl, k_done) + 12,
@@ -1207,6 +1216,71 @@ static void seq_stage_c(mbpe_ctx *c) {                   // after the edge excha
     if (is_multi(c)) launch_compose_edges(c->stream, c->xb, c->rank, c->n_ranks, c->d_left, c->d_right);
 }
 
+// ---- the sharded protocol: what an exchange carries, what follows it, and who makes it ----
+
+// What the ranks sum in exchange p.  The only place that forms these sizes, for RCCL and for mbpe_comm_exchange_buffer,
+// asked once per exchange by whoever issues it (finish_unit, suspend); SeqDeltas waits for the selection's result
+// (seq_info_enqueue) and is what stats.exchanges / exchange_words count.
+static int phase_exchange(mbpe_ctx *c, Phase p, Exchange *x) {
+    switch (p) {
+    case Phase::BeginCounts: *x = {c->xb0, begin_exchange_words(c)}; return MBPE_OK;
+    case Phase::StepDeltas: *x = {c->xb, exchange_words(c, 256 + c->k, 1)}; return MBPE_OK;
+    case Phase::SeqDeltas: {
+        uint32_t ids = 0, n_pairs = 0;
+        const int rc = seq_info_wait(c, &ids, &n_pairs);
+        if (rc != MBPE_OK) return rc;
+        *x = {c->xb, exchange_words(c, ids, n_pairs)};
+        c->stats.exchange_words += x->words;
+        c->stats.exchanges++;
+        return MBPE_OK;
+    }
+    case Phase::SeqEdges: *x = {c->xb, c->hdr_words}; return MBPE_OK;
+    case Phase::BeginFirst: case Phase::StepFirst: *x = {c->xf, c->hdr_words}; return MBPE_OK;
+    case Phase::None: break;
+    }
+    *x = {};
+    return MBPE_OK;
+}
+
+// Enqueues the part of a unit that follows exchange p; returns the unit's next exchange, or None when all of it is on the
+// stream (what ends a unit -- begin_end, a step's k++, the host's synchronisation -- is its driver's).
+static Phase continue_after(mbpe_ctx *c, Phase p) {
+    switch (p) {
+    case Phase::BeginCounts: begin_finish_a(c); return first_sharded(c) ? Phase::BeginFirst : Phase::None;
+    case Phase::BeginFirst: first_tiebreak(c, c->best, 0, 2); return Phase::None;
+    case Phase::StepDeltas: step_finish_a(c); return first_sharded(c) ? Phase::StepFirst : Phase::None;
+    case Phase::StepFirst: first_tiebreak(c, c->best + c->k + 1, 0, 2); return Phase::None;
+    case Phase::SeqDeltas: seq_stage_b(c); return Phase::SeqEdges;
+    case Phase::SeqEdges: seq_stage_c(c); return Phase::None;
+    case Phase::None: break;
+    }
+    return Phase::None;
+}
+
+static int comm_allreduce(mbpe_ctx *c, uint32_t *buf, size_t count);   // RCCL (below)
+
+// One rank, or several over RCCL: everything of a unit behind its local part, whose first exchange is p.  With several
+// ranks every exchange is an all-reduce on the context's stream; nothing here synchronises the host with the stream.
+static int finish_unit(mbpe_ctx *c, Phase p) {
+    for (; p != Phase::None; p = continue_after(c, p)) {
+        if (!is_multi(c)) continue;
+        Exchange x = {};
+        int rc = phase_exchange(c, p, &x);
+        if (rc == MBPE_OK) rc = comm_allreduce(c, x.buf, x.words);
+        if (rc != MBPE_OK) return rc;
+    }
+    return MBPE_OK;
+}
+
+// External transport: the caller makes exchange p, and mbpe_comm_exchange_done continues behind it.
+static int suspend(mbpe_ctx *c, Phase p) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int rc = phase_exchange(c, p, &c->pending_x);
+    if (rc != MBPE_OK) return rc;
+    c->pending = p;
+    return MBPE_NEED_EXCHANGE;
+}
+
 // table entries one sequence can add at most
 static uint64_t seq_headroom(const mbpe_ctx *c) {
     return (uint64_t)c->opt_max_batch * (2ull * c->vocab_size + kBatchMax + 1);
@@ -1232,10 +1306,44 @@ static int after_batch(mbpe_ctx *c) {
     return MBPE_OK;
 }
 
-static int before_batch(mbpe_ctx *c, uint32_t batch) {
-    if (!c->tab.cells && (uint64_t)c->h_ctl.n_entries + batch_headroom(c, batch) > c->tab.ecap)
-        return grow_table(c, ((uint64_t)c->h_ctl.n_entries + batch_headroom(c, batch)) * 2);
+// room for `entries` more entries in the pair table (h_ctl.n_entries must be current); the dense table has a cell for
+// every possible pair
+static int reserve_table(mbpe_ctx *c, uint64_t entries) {
+    const uint64_t need = (uint64_t)c->h_ctl.n_entries + entries;
+    if (c->tab.cells || need <= c->tab.ecap) return MBPE_OK;
+    return grow_table(c, need * 2);
+}
+
+// The chosen pair `pair` occurs nowhere.  Merging it changes neither the stream nor the table, so the reference chooses
+// it again and again (its loop only ends on an empty table, Tokenizer.h:586-588; PairCountLexicalOrder never erases):
+// the merges k .. target of this call are that pair, written to best[] from `from` on without their passes.  Batch
+// sequences count their merges on the device (set_k_done); a one-merge step is told its index.
+static int fill_zero_tail(mbpe_ctx *c, unsigned long long pair, uint32_t from, uint32_t target, bool set_k_done) {
+    if (target > c->k) {
+        std::vector<unsigned long long> rest(target - c->k, pair);
+        HIPCHK(hipMemcpy(c->best + from, rest.data(), rest.size() * 8, hipMemcpyHostToDevice));
+    }
+    if (set_k_done) {
+        HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->ctl->k_done), (int)target, 1, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->h_ctl.k_done = target;
+    }
+    c->k = target;
     return MBPE_OK;
+}
+
+// External transport: the local part of the next sequence (or merge) of an mbpe_train_steps call, up to its first exchange.
+static int start_unit_external(mbpe_ctx *c, bool batched) {
+    int rc = reserve_table(c, batched ? seq_headroom(c) : batch_headroom(c, 1));
+    if (rc != MBPE_OK) return rc;
+    if (!batched) {
+        step_local(c, -1);
+        return suspend(c, Phase::StepDeltas);
+    }
+    c->k_upper = c->k;
+    rc = seq_stage_a(c, -1);
+    if (rc != MBPE_OK) return rc;
+    return suspend(c, Phase::SeqDeltas);
 }
 
 int mbpe_train_begin(mbpe_ctx *c, uint32_t vocab_size) {
@@ -1268,16 +1376,10 @@ int mbpe_train_begin(mbpe_ctx *c, uint32_t vocab_size) {
     c->vocab_total = total;
     c->n_target_total = total - 256;
     if (rc != MBPE_OK) return rc;
-    if (is_multi(c)) {
-        if (c->comm_external) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            c->pending = 1;
-            return MBPE_NEED_EXCHANGE;
-        }
-        rc = comm_allreduce(c, c->xb0, 65536 + (size_t)c->hdr_words + kPairCountWords);
-        if (rc != MBPE_OK) return rc;
-    }
-    return begin_finish(c);
+    if (is_multi(c) && c->comm_external) return suspend(c, Phase::BeginCounts);
+    rc = finish_unit(c, Phase::BeginCounts);
+    if (rc != MBPE_OK) return rc;
+    return begin_end(c);
 }
 
 // the batch-sequence loop of mbpe_train_steps (one GPU, or several over RCCL)
@@ -1290,12 +1392,10 @@ static int train_steps_batched(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_do
     uint32_t seqs_left = max_seqs;
     while (c->k < target && !c->exhausted && seqs_left) {
         const uint32_t group = std::min<uint32_t>(seqs_per_sync(c), seqs_left);
-        if (!c->tab.cells && (uint64_t)c->h_ctl.n_entries + seq_headroom(c) * group > c->tab.ecap) {
-            int rc = grow_table(c, ((uint64_t)c->h_ctl.n_entries + seq_headroom(c) * group) * 2);
-            if (rc != MBPE_OK) return rc;
-        }
+        int rc = reserve_table(c, seq_headroom(c) * group);
+        if (rc != MBPE_OK) return rc;
         if (c->opt_time_kernels) {
-            int rc = ensure_events(c->kev, 2ull * group);
+            rc = ensure_events(c->kev, 2ull * group);
             if (rc == MBPE_OK) rc = ensure_events(c->kev_f, 2ull * group);
             if (rc != MBPE_OK) return rc;
         }
@@ -1303,55 +1403,34 @@ static int train_steps_batched(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_do
         // (for THIS group: the "batch" / "max_batch" options may have changed since the bound was last computed)
         update_hot_possible(c, c->last_top, (uint64_t)group * kBatchMax);
         const uint32_t batches_before = c->h_ctl.n_batches, singles_before = c->h_ctl.cut_single;
-        const uint32_t retry_before = c->h_ctl.n_sel_retry + c->h_ctl.n_sel_fallback;
         unsigned long long live_prev = c->h_ctl.n_live;      // (exact: the host synchronised before this group)
-        HIPCHK(hipEventRecord(c->ev0, c->stream));
         uint32_t launched = 0;
-        // (sequences past the target do nothing on the device -- ctl->k_limit -- but cost their launches: enqueue
-        //  as many as the last group's merges per sequence say are needed; before that is known, as many as are
-        //  needed if every one merged max_batch pairs)
-        const bool lockstep = use_lockstep(c);
-        for (uint32_t g = 0; g < group && (lockstep || (c->merges_per_seq > 0 ? c->k + g * c->merges_per_seq < target : c->k_upper < target));
-             ++g, ++launched) {
-            if (lockstep) {
-                bool nothing_left = false;
-                c->seq_slot = c->opt_time_kernels ? (int)g : -1;
-                const int rc = seq_lockstep(c, c->opt_time_kernels ? (int)g : -1, &nothing_left);
-                if (rc != MBPE_OK) return rc;
-                if (nothing_left) { ++launched; break; }
-                continue;
+        rc = timed_group(c, [&]() -> int {
+            // (sequences past the target do nothing on the device -- ctl->k_limit -- but cost their launches: enqueue
+            //  as many as the last group's merges per sequence say are needed; before that is known, as many as are
+            //  needed if every one merged max_batch pairs)
+            const bool lockstep = use_lockstep(c);
+            for (uint32_t g = 0; g < group && (lockstep || (c->merges_per_seq > 0 ? c->k + g * c->merges_per_seq < target : c->k_upper < target));
+                 ++g, ++launched) {
+                const int slot = c->opt_time_kernels ? (int)g : -1;
+                c->seq_slot = slot;
+                if (lockstep) {
+                    bool nothing_left = false;
+                    const int r = seq_lockstep(c, slot, &nothing_left);
+                    if (r != MBPE_OK) return r;
+                    if (nothing_left) { ++launched; break; }
+                    continue;
+                }
+                // (with several ranks the selection's result arrives while the stream pass runs: every rank took the same
+                //  decisions, so the counts agree, and the all-reduce is enqueued long before the pass ends)
+                int r = seq_stage_a(c, slot);
+                if (r == MBPE_OK) r = finish_unit(c, Phase::SeqDeltas);
+                if (r != MBPE_OK) return r;
             }
-            {
-                const int rc = seq_stage_a(c, c->opt_time_kernels ? (int)g : -1);
-                if (rc != MBPE_OK) return rc;
-            }
-            if (is_multi(c)) {
-                // (the selection's result arrives while the stream pass runs: every rank took the same decisions, so
-                //  the counts agree, and the all-reduce is enqueued long before the pass ends)
-                uint32_t ids = 0, n_pairs = 0;
-                int rc = seq_info_wait(c, &ids, &n_pairs);
-                if (rc != MBPE_OK) return rc;
-                c->stats.exchange_words += exchange_words(c, ids, n_pairs);
-                c->stats.exchanges++;
-                rc = comm_allreduce(c, c->xb, exchange_words(c, ids, n_pairs));
-                if (rc != MBPE_OK) return rc;
-            }
-            c->seq_slot = c->opt_time_kernels ? (int)g : -1;
-            seq_stage_b(c);
-            if (is_multi(c)) {
-                int rc = comm_allreduce(c, c->xb, c->hdr_words);
-                if (rc != MBPE_OK) return rc;
-            }
-            seq_stage_c(c);
-        }
-        c->seq_slot = -1;
-        HIPCHK(hipEventRecord(c->ev1, c->stream));
-        int rc = sync_ctl(c);
+            c->seq_slot = -1;
+            return MBPE_OK;
+        });
         if (rc != MBPE_OK) return rc;
-        HIPCHK(hipGetLastError());
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        c->stats.ms_steps += ms;
         if (c->opt_time_kernels) {
             c->h_seq_flags.resize(4 * (size_t)launched);
             if (launched)
@@ -1373,25 +1452,18 @@ static int train_steps_batched(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_do
             }
             c->stats.merge_launches += c->h_ctl.n_batches - batches_before;   // sequences that did work
         }
-        // (Round 4 tried to enqueue the selection's second and third attempts only while the last group had needed one:
-        //  a selection that then needs them falls back to the bound-walking kernel, whose batches are a few pairs -- with a
-        //  host round trip per sequence 138 passes instead of 66 on the benchmark workload.  All three, always.)
-        (void)retry_before;
+        // (All three attempts of the selection, always.  Round 4 tried to enqueue the second and third only while the last
+        //  group had needed one: a selection that then needs them falls back to the bound-walking kernel, whose batches are
+        //  a few pairs -- with a host round trip per sequence 138 passes instead of 66 on the benchmark workload.)
         const uint32_t before = c->k;
         c->k = c->h_ctl.k_done;
         if (c->k) {             // the count of the latest merge bounds every later one
             unsigned long long last = 0;
             HIPCHK(hipMemcpy(&last, c->best + (c->k - 1), 8, hipMemcpyDeviceToHost));
             update_hot_possible(c, last >> 32, (uint64_t)seqs_per_sync(c) * kBatchMax);
-            if ((last >> 32) == 0 && c->k < target && c->k != before) {
-                // The best pair no longer occurs anywhere.  Merging it changes neither the stream nor the table, so the
-                // reference chooses it again and again (its loop only ends on an empty table, Tokenizer.h:586-588;
-                // PairCountLexicalOrder never erases): every remaining merge of this call is that pair.
-                std::vector<unsigned long long> rest(target - c->k, last);
-                HIPCHK(hipMemcpy(c->best + c->k, rest.data(), rest.size() * 8, hipMemcpyHostToDevice));
-                HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->ctl->k_done), (int)target, 1, c->stream));
-                HIPCHK(hipStreamSynchronize(c->stream));
-                c->k = c->h_ctl.k_done = target;
+            if ((last >> 32) == 0 && c->k < target && c->k != before) {      // every remaining merge of this call is that pair
+                rc = fill_zero_tail(c, last, c->k, target, true);
+                if (rc != MBPE_OK) return rc;
             }
         }
         rc = after_batch(c);
@@ -1443,7 +1515,7 @@ int mbpe_train_steps(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_done_out) {
     if (steps_done_out) *steps_done_out = 0;
     if (!c) return MBPE_ERR_ARG;
     if (!c->begun) { mbpe_host::set_last_error("mbpe_train_steps before mbpe_train_begin"); return MBPE_ERR_STATE; }
-    if (c->pending) { mbpe_host::set_last_error("an exchange is pending: call mbpe_comm_exchange_done"); return MBPE_ERR_STATE; }
+    if (c->pending != Phase::None) { mbpe_host::set_last_error("an exchange is pending: call mbpe_comm_exchange_done"); return MBPE_ERR_STATE; }
     HIPCHK(hipSetDevice(c->device));
     if (!c->wide) return train_steps16(c, n_steps, steps_done_out);
     // a training that continues on 32-bit tokens: the slot stream's share first, then the conversion, then the rest
@@ -1470,28 +1542,11 @@ static int train_steps16(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_done_out
         // one sequence (or one merge) per round trip: local part now, the rest in mbpe_comm_exchange_done
         if (n_steps == 0 || c->k >= c->n_target || c->exhausted) return MBPE_OK;
         c->pending_target = std::min<uint32_t>(c->n_target, c->k + n_steps);
-        if (use_batches(c)) {
+        const bool batched = use_batches(c);
+        if (batched)
             HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->ctl->k_limit), (int)c->pending_target, 1,
                                      c->stream));
-            if (!c->tab.cells && (uint64_t)c->h_ctl.n_entries + seq_headroom(c) > c->tab.ecap) {
-                int rc = grow_table(c, ((uint64_t)c->h_ctl.n_entries + seq_headroom(c)) * 2);
-                if (rc != MBPE_OK) return rc;
-            }
-            c->k_upper = c->k;
-            {
-                const int rc = seq_stage_a(c, -1);
-                if (rc != MBPE_OK) return rc;
-            }
-            HIPCHK(hipStreamSynchronize(c->stream));
-            c->pending = 3;
-            return MBPE_NEED_EXCHANGE;
-        }
-        int rc = before_batch(c, 1);
-        if (rc != MBPE_OK) return rc;
-        step_local(c, -1);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        c->pending = 2;
-        return MBPE_NEED_EXCHANGE;
+        return start_unit_external(c, batched);
     }
     uint32_t done = 0;
     if (use_batches(c)) {
@@ -1503,29 +1558,22 @@ static int train_steps16(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_done_out
     }
     while (done < n_steps && c->k < c->n_target && !c->exhausted) {
         uint32_t batch = std::min<uint32_t>({(uint32_t)c->opt_batch, n_steps - done, c->n_target - c->k});
-        int rc = before_batch(c, batch);   // pair-table headroom (h_ctl.n_entries is exact here)
+        int rc = reserve_table(c, batch_headroom(c, batch));   // (h_ctl.n_entries is exact here)
         if (rc != MBPE_OK) return rc;
         if (c->opt_time_kernels) {
             rc = ensure_events(c->kev, 2ull * batch);
             if (rc != MBPE_OK) return rc;
         }
-        HIPCHK(hipEventRecord(c->ev0, c->stream));
-        for (uint32_t i = 0; i < batch; ++i) {
-            step_local(c, c->opt_time_kernels ? (int)i : -1);
-            if (is_multi(c)) {
-                rc = comm_allreduce(c, c->xb, step_exchange_words(c));
-                if (rc != MBPE_OK) return rc;
+        rc = timed_group(c, [&]() -> int {
+            for (uint32_t i = 0; i < batch; ++i) {
+                step_local(c, c->opt_time_kernels ? (int)i : -1);
+                const int r = finish_unit(c, Phase::StepDeltas);
+                if (r != MBPE_OK) return r;
+                c->k++;
             }
-            rc = step_finish(c);
-            if (rc != MBPE_OK) return rc;
-        }
-        HIPCHK(hipEventRecord(c->ev1, c->stream));
-        rc = sync_ctl(c);
+            return MBPE_OK;
+        });
         if (rc != MBPE_OK) return rc;
-        HIPCHK(hipGetLastError());
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        c->stats.ms_steps += ms;
         if (c->opt_time_kernels) {
             for (uint32_t i = 0; i < batch; ++i) {
                 float km = 0;
@@ -1538,8 +1586,7 @@ static int train_steps16(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_done_out
             // Did the table run out of pairs with a count?  best[k - batch .. k] are the pairs of this batch's steps and
             // of the next one.  Merging a pair that occurs nowhere changes neither the stream nor the table, so every
             // later choice is that pair again: `first` ends there like the reference's loop (its rebuilt table is empty,
-            // Tokenizer.h:586-588), `lexical` keeps choosing it (PairCountLexicalOrder never erases) -- the rest of this
-            // call's steps are filled in without their passes, as train_steps_batched does.
+            // Tokenizer.h:586-588), `lexical` keeps choosing it: the rest of this call's steps are filled in (fill_zero_tail).
             std::vector<unsigned long long> hb(batch + 1);
             HIPCHK(hipMemcpy(hb.data(), c->best + (c->k - batch), hb.size() * 8, hipMemcpyDeviceToHost));
             uint32_t z = 0;
@@ -1552,12 +1599,9 @@ static int train_steps16(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_done_out
                     c->n_target = kz;
                 } else {
                     const uint32_t target = std::min<uint64_t>((uint64_t)c->k + (n_steps - done - batch), c->n_target);
-                    if (target > c->k) {
-                        std::vector<unsigned long long> rest(target - c->k, hb[z]);
-                        HIPCHK(hipMemcpy(c->best + c->k + 1, rest.data(), rest.size() * 8, hipMemcpyHostToDevice));
-                    }
                     done += batch + (target - c->k);
-                    c->k = target;
+                    rc = fill_zero_tail(c, hb[z], c->k + 1, target, false);      // (best[k] is that pair already)
+                    if (rc != MBPE_OK) return rc;
                 }
                 rc = after_batch(c);
                 if (rc != MBPE_OK) return rc;
@@ -1722,7 +1766,7 @@ int mbpe_train_sequences(mbpe_ctx *c, uint32_t n_sequences, uint32_t *merges_don
     if (merges_done_out) *merges_done_out = 0;
     if (!c) return MBPE_ERR_ARG;
     if (!c->begun) { mbpe_host::set_last_error("mbpe_train_sequences before mbpe_train_begin"); return MBPE_ERR_STATE; }
-    if (c->pending || (is_multi(c) && c->comm_external)) {
+    if (c->pending != Phase::None || (is_multi(c) && c->comm_external)) {
         mbpe_host::set_last_error("mbpe_train_sequences: not available with an external transport (use mbpe_train_steps)");
         return MBPE_ERR_STATE;
     }
@@ -1735,104 +1779,34 @@ int mbpe_train_sequences(mbpe_ctx *c, uint32_t n_sequences, uint32_t *merges_don
 
 int mbpe_comm_exchange_buffer(mbpe_ctx *c, void **dev_ptr_out, uint64_t *n_u32_out) {
     if (!c || !dev_ptr_out || !n_u32_out) return MBPE_ERR_ARG;
-    switch (c->pending) {
-    case 1: *dev_ptr_out = c->xb0; *n_u32_out = 65536 + (uint64_t)c->hdr_words + kPairCountWords; return MBPE_OK;
-    case 2: *dev_ptr_out = c->xb; *n_u32_out = step_exchange_words(c); return MBPE_OK;
-    case 3:     // deltas of a batch sequence
-        *dev_ptr_out = c->xb;
-        {
-            uint32_t ids = 0, n_pairs = 0;
-            int rc = seq_info_wait(c, &ids, &n_pairs);
-            if (rc != MBPE_OK) return rc;
-            *n_u32_out = exchange_words(c, ids, n_pairs);
-        }
-        return MBPE_OK;
-    case 4: *dev_ptr_out = c->xb; *n_u32_out = c->hdr_words; return MBPE_OK;   // rank edges
-    case 5: case 6: *dev_ptr_out = c->xf; *n_u32_out = c->hdr_words; return MBPE_OK;   // `first`: the ranks' earliest tied pairs
-    default: break;
-    }
-    mbpe_host::set_last_error("no exchange pending");
-    return MBPE_ERR_STATE;
+    if (c->pending == Phase::None) { mbpe_host::set_last_error("no exchange pending"); return MBPE_ERR_STATE; }
+    *dev_ptr_out = c->pending_x.buf;
+    *n_u32_out = c->pending_x.words;
+    return MBPE_OK;
 }
 
+// External transport: the caller has made the pending exchange.  Continues the unit behind it; when the whole unit is on
+// the stream, ends it as the loops of one rank do and starts the next one while the call's target is not reached.
 int mbpe_comm_exchange_done(mbpe_ctx *c) {
     if (!c) return MBPE_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
-    if (c->pending == 1) {
-        c->pending = 0;
-        begin_finish_a(c);
-        if (first_sharded(c)) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            c->pending = 6;
-            return MBPE_NEED_EXCHANGE;
-        }
-        return begin_finish_b(c);
-    }
-    if (c->pending == 6) {
-        c->pending = 0;
-        return begin_finish_b(c);
-    }
-    if (c->pending == 2) {
-        c->pending = 0;
-        step_finish_a(c);
-        if (first_sharded(c)) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            c->pending = 5;
-            return MBPE_NEED_EXCHANGE;
-        }
-        c->pending = 5;            // (falls through to the second part)
-    }
-    if (c->pending == 5) {
-        c->pending = 0;
-        step_finish_b(c);
-        int rc = sync_ctl(c);
-        if (rc != MBPE_OK) return rc;
-        HIPCHK(hipGetLastError());
-        rc = after_batch(c);
-        if (rc != MBPE_OK) return rc;
-        if (c->k < c->pending_target) {
-            rc = before_batch(c, 1);
-            if (rc != MBPE_OK) return rc;
-            step_local(c, -1);
-            HIPCHK(hipStreamSynchronize(c->stream));
-            c->pending = 2;
-            return MBPE_NEED_EXCHANGE;
-        }
-        return MBPE_OK;
-    }
-    if (c->pending == 3) {
-        c->pending = 0;
-        seq_stage_b(c);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        c->pending = 4;
-        return MBPE_NEED_EXCHANGE;
-    }
-    if (c->pending == 4) {
-        c->pending = 0;
-        seq_stage_c(c);
-        int rc = sync_ctl(c);
-        if (rc != MBPE_OK) return rc;
-        HIPCHK(hipGetLastError());
-        const uint32_t before = c->k;
-        c->k = c->h_ctl.k_done;
-        rc = after_batch(c);
-        if (rc != MBPE_OK) return rc;
-        if (c->k < c->pending_target && c->k != before) {
-            if (!c->tab.cells && (uint64_t)c->h_ctl.n_entries + seq_headroom(c) > c->tab.ecap) {
-                rc = grow_table(c, ((uint64_t)c->h_ctl.n_entries + seq_headroom(c)) * 2);
-                if (rc != MBPE_OK) return rc;
-            }
-            c->k_upper = c->k;
-            rc = seq_stage_a(c, -1);
-            if (rc != MBPE_OK) return rc;
-            HIPCHK(hipStreamSynchronize(c->stream));
-            c->pending = 3;
-            return MBPE_NEED_EXCHANGE;
-        }
-        return MBPE_OK;
-    }
-    mbpe_host::set_last_error("no exchange pending");
-    return MBPE_ERR_STATE;
+    const Phase p = c->pending;
+    if (p == Phase::None) { mbpe_host::set_last_error("no exchange pending"); return MBPE_ERR_STATE; }
+    c->pending = Phase::None;
+    const Phase next = continue_after(c, p);
+    if (next != Phase::None) return suspend(c, next);
+    if (p == Phase::BeginCounts || p == Phase::BeginFirst) return begin_end(c);
+    const bool batched = p == Phase::SeqEdges;      // a batch sequence; otherwise a one-merge step
+    if (!batched) c->k++;
+    int rc = sync_ctl(c);
+    if (rc != MBPE_OK) return rc;
+    HIPCHK(hipGetLastError());
+    const uint32_t before = c->k;
+    if (batched) c->k = c->h_ctl.k_done;
+    rc = after_batch(c);
+    if (rc != MBPE_OK) return rc;
+    if (c->k >= c->pending_target || (batched && c->k == before)) return MBPE_OK;      // (a sequence that merged nothing: none left)
+    return start_unit_external(c, batched);
 }
 
 int mbpe_train_result(mbpe_ctx *c, uint32_t *merges_out, int32_t *counts_out, uint32_t cap_merges,
@@ -2119,7 +2093,7 @@ int mbpe_comm_init(mbpe_ctx *c, const uint8_t *id, int rank, int n_ranks) {
         mbpe_host::set_last_error("mbpe_comm_init: bad argument");
         return MBPE_ERR_ARG;
     }
-    if (c->begun || c->pending) { mbpe_host::set_last_error("mbpe_comm_init after mbpe_train_begin"); return MBPE_ERR_STATE; }
+    if (c->begun || c->pending != Phase::None) { mbpe_host::set_last_error("mbpe_comm_init after mbpe_train_begin"); return MBPE_ERR_STATE; }
     HIPCHK(hipSetDevice(c->device));
     Rccl &r = rccl();
     if (!r.ok) { mbpe_host::set_last_error(r.why); return MBPE_ERR_COMM; }
@@ -2143,7 +2117,7 @@ int mbpe_comm_init_external(mbpe_ctx *c, int rank, int n_ranks) {
         mbpe_host::set_last_error("mbpe_comm_init_external: bad argument");
         return MBPE_ERR_ARG;
     }
-    if (c->begun || c->pending) { mbpe_host::set_last_error("mbpe_comm_init_external after mbpe_train_begin"); return MBPE_ERR_STATE; }
+    if (c->begun || c->pending != Phase::None) { mbpe_host::set_last_error("mbpe_comm_init_external after mbpe_train_begin"); return MBPE_ERR_STATE; }
     c->rank = rank;
     c->n_ranks = n_ranks;
     c->comm_external = true;

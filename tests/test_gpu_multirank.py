@@ -5,6 +5,7 @@ C-ABI.  Everything except the ncclAllReduce call itself is the production path.
 Results must equal the single-rank oracle on the whole corpus."""
 import ctypes
 import os
+import re
 
 import numpy as np
 import pytest
@@ -46,6 +47,9 @@ EXCHANGES = []        # (u32 words, merges committed before) of every exchange o
 # batch header of the exchange buffer: m_j (kBatchMax = 4096 words) and the ADJ block, whose row pitch is the largest batch
 # a training selects -- 1,024 pairs with several ranks, so that the block stays 4 MB
 HDRB = (4096 + 1024 * 1024 + 3) // 4 * 4
+# the begin exchange ends with the number of pairs counted, in this many limbs of one u32 word each
+with open(os.path.join(os.path.dirname(__file__), "..", "minbpe-cc_amd", "csrc", "mbpe_dev.h")) as _f:
+    PAIR_COUNT_WORDS = int(re.search(r"constexpr uint32_t kPairCountWords = (\d+);", _f.read()).group(1))
 
 
 def _allreduce(trainers):
@@ -67,6 +71,7 @@ def _train_sharded(data, cuts, vocab, chunk_off=None, decode_check=False):
     bounds = [0] + list(cuts) + [len(data)]
     R = len(bounds) - 1
     trainers = [mbpe.Trainer(0) for _ in range(R)]
+    del EXCHANGES[:]
     try:
         for r, t in enumerate(trainers):
             lo, hi = bounds[r], bounds[r + 1]
@@ -88,7 +93,11 @@ def _train_sharded(data, cuts, vocab, chunk_off=None, decode_check=False):
             _allreduce(trainers)
             codes = [t.exchange_done() for t in trainers]
             n_begin += 1
-        assert all(c == mbpe.OK for c in codes) and n_begin == (2 if EXTRA_OPTS.get("conflict_resolution", 1) == 0 else 1)
+        first = EXTRA_OPTS.get("conflict_resolution", 1) == 0
+        assert all(c == mbpe.OK for c in codes) and n_begin == (2 if first else 1)
+        # the begin: the byte-pair tables with the header and the pairs counted; with `first` then the header-sized xf
+        hdr = (2 + 8 * R + 3) // 4 * 4
+        assert [n for n, _ in EXCHANGES] == [65536 + hdr + PAIR_COUNT_WORDS] + ([hdr] if first else [])
         del EXCHANGES[:]
         codes = [t.train_steps(vocab - 256) for t in trainers]
         while codes[0] == mbpe.NEED_EXCHANGE:
@@ -100,9 +109,21 @@ def _train_sharded(data, cuts, vocab, chunk_off=None, decode_check=False):
         # What crossed the "wire": a sequence exchanges its count deltas -- both headers + exactly the rows L_j, R_j
         # (lr_pitch(ids) cells each) of the pairs of its batch, not the whole 2 x 1024 x ids block -- and then the
         # shard edges (the small header alone).
-        hdr = (2 + 8 * R + 3) // 4 * 4
         n_final = len(results[0][0])
         deltas = [(n, k) for n, k in EXCHANGES if n != hdr]
+        # Their order: every sequence (lexical, batched) is one delta exchange, then one edge exchange of exactly the header;
+        # with `first` every merge is one pair's rows, then the header-sized xf.  Either way the run ends on a small one.
+        assert len(EXCHANGES) % 2 == 0
+        for (n, k), (n2, k2) in zip(EXCHANGES[0::2], EXCHANGES[1::2]):
+            assert n > hdr + HDRB and n2 == hdr and k2 == k, (n, k, n2, k2)
+            if first:
+                assert n == hdr + HDRB + 2 * ((256 + k + 63) & ~63), (n, k)
+        assert len(deltas) == len(EXCHANGES) // 2
+        # the counters: a batch sequence's delta exchange is counted, on every rank (a one-merge step's is not)
+        if not first:
+            for t in trainers:
+                st = t.stats()
+                assert st["exchanges"] == len(deltas) and st["exchange_words"] == sum(n for n, _ in deltas)
         for i, (n, k) in enumerate(deltas):
             pitch = (256 + k + 63) & ~63
             rows, rest = divmod(n - hdr - HDRB, 2 * pitch)
@@ -128,6 +149,43 @@ def _train_sharded(data, cuts, vocab, chunk_off=None, decode_check=False):
                 assert rt["ok"], rt
                 start += n
         return results, streams, tables
+    finally:
+        for t in trainers:
+            t.close()
+
+
+def _raises_state(call):
+    with pytest.raises(mbpe.MbpeError) as e:
+        call()
+    assert e.value.code == mbpe.ERR_STATE
+
+
+def test_external_transport_state_errors():
+    """What the external transport refuses, on two ranks over 4 KiB: the exchange calls with nothing pending,
+    mbpe_train_steps while an exchange is pending, mbpe_train_sequences always.  Asking for the buffer of one
+    exchange twice names the same buffer and counts the exchange once."""
+    data = O.splitmix64_bytes(5, 4096)
+    trainers = [mbpe.Trainer(0) for _ in range(2)]
+    try:
+        for r, t in enumerate(trainers):
+            t.comm_init_external(r, 2)
+            t.set_option("fused_min", FUSED_MIN)
+            t.load_corpus(data[2048 * r:2048 * (r + 1)])
+            _raises_state(t.exchange_buffer)
+            _raises_state(t.exchange_done)
+        assert [t.train_begin(256 + 8) for t in trainers] == [mbpe.NEED_EXCHANGE] * 2
+        _allreduce(trainers)
+        assert [t.exchange_done() for t in trainers] == [mbpe.OK] * 2
+        for t in trainers:
+            _raises_state(t.exchange_buffer)
+            _raises_state(t.exchange_done)
+            _raises_state(lambda: t.train_sequences(1))
+        assert [t.train_steps(8) for t in trainers] == [mbpe.NEED_EXCHANGE] * 2
+        for t in trainers:
+            _raises_state(lambda: t.train_steps(8))
+            _raises_state(lambda: t.train_sequences(1))
+            assert t.exchange_buffer() == t.exchange_buffer()
+            assert t.stats()["exchanges"] == 1 and t.stats()["exchange_words"] == t.exchange_buffer()[1]
     finally:
         for t in trainers:
             t.close()
