@@ -493,6 +493,68 @@ MBPE_API int  mbpe_encoder_encode_batch(mbpe_encoder *e, const uint8_t *text, ui
                                         uint64_t *n_rows_out, uint64_t *n_tokens_out);
 MBPE_API int  mbpe_encoder_pack_ms(const mbpe_encoder *e, float *ms_out);
 
+/* ---- training batches: labels, positions, segments, cu_seqlens ------------ */
+
+/* What a training step needs beside the ids, written by the same kernel from the same walk (k_pack_aux,
+ * csrc/pack.hip).  A document as it appears in the matrix is the element list E_d = [bos] body [eos] with
+ * T_d = |E_d|: for MBPE_PACK_PACKED body is the whole document d, which may span rows; for MBPE_PACK_PADDED it is the
+ * kept (truncated) part, T_d = len[d], in columns [lead, lead + T_d) of row d.  Every cell of the matrix is a pad cell
+ * or holds element k of some E_d:
+ *   labels  [n_rows, seq_len] ids of spec->out_bits bits: E_d[k + 1] if k + 1 < T_d, else ignore_label; ignore_label
+ *           in a pad cell.  A label never crosses a document: with eos set the token before it has label eos and eos
+ *           itself ignore_label.  In PACKED a label does cross a row end inside a document
+ *   pos     [n_rows, seq_len] uint32_t: k (it goes on counting in a document that continues in the next row); 0 in a
+ *           pad cell
+ *   seg     [n_rows, seq_len] uint32_t: d + 1, d the document's number among all n_docs; 0 in a pad cell.  An empty
+ *           document without bos / eos occupies no cell: its number is skipped
+ * ignore_label is written truncated to out_bits: -100 comes out as -100 in an int64 / int32 tensor.  With out_bits 16
+ * it must lie in 0 .. 65,535 (MBPE_ERR_VOCAB), with out_bits 32 in -2^31 .. 2^32 - 1 (MBPE_ERR_ARG).  seg needs
+ * n_docs < 2^32 - 1 and pos, in PACKED, every T_d < 2^32 (MBPE_ERR_ARG). */
+typedef struct {
+    void     *labels;        /* [n_rows, seq_len] ids of spec->out_bits bits, or NULL */
+    uint32_t *pos;           /* [n_rows, seq_len], or NULL */
+    uint32_t *seg;           /* [n_rows, seq_len], or NULL */
+    int64_t   ignore_label;
+} mbpe_pack_aux;             /* on the same side as ids_out */
+
+/* mbpe_pack_tokens with the outputs of `aux` (required: NULL is MBPE_ERR_ARG; all three of its pointers NULL is
+ * valid and gives ids and lengths alone, equal to those of mbpe_pack_tokens).  Every other argument, the query
+ * (ids_out NULL) and the cap rule are those of mbpe_pack_tokens, except that with out_on_device each of ids_out,
+ * labels, pos and seg that is given must be 16-byte aligned (MBPE_ERR_ARG).  Host outputs go through device buffers
+ * of the call's own and come back with the ids.  All arguments are checked before the device is touched; an error
+ * return writes nothing.  mbpe_pack_kernel_ms covers this kernel too. */
+MBPE_API int  mbpe_pack_tokens_aux(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits,
+                                   int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs,
+                                   const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
+                                   uint32_t *len_out, uint64_t *n_rows_out, const mbpe_pack_aux *aux);
+
+/* cu_seqlens and max_seqlen of a MBPE_PACK_PACKED matrix for variable-length attention, on the host alone (no device,
+ * never MBPE_ERR_NO_DEVICE).  With n_stream = doc_tok_off[n_docs] + n_docs * (nb + ne) the list is, ascending and
+ * without duplicates: the row starts r * seq_len < n_stream, the document starts doc_tok_off[d] + d * (nb + ne), and
+ * n_stream -- the boundaries of the maximal runs of cells with equal (row, seg) in the flattened matrix.  Empty
+ * documents vanish, the pad tail behind n_stream is outside, n_stream == 0 gives [0] and n_seqs 0.
+ *   doc_tok_off, n_docs   as for mbpe_pack_tokens (what mbpe_encoder_encode_batch_aux hands back)
+ *   cu_out            cap_seqs + 1 entries, host.  NULL: query
+ *   n_seqs_out, max_seqlen_out   required: the sequences (the list has n_seqs + 1 entries) and the longest of them,
+ *                     at most seq_len; also on a query and when cap_seqs is too small (MBPE_ERR_ARG, nothing written)
+ * MBPE_ERR_ARG also for MBPE_PACK_PADDED (there the sequences are the rows, and mbpe_unpack_tokens gives their
+ * offsets) and for n_stream >= 2^31. */
+MBPE_API int  mbpe_pack_cu_seqlens(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec,
+                                   int32_t *cu_out, uint64_t cap_seqs, uint64_t *n_seqs_out, uint32_t *max_seqlen_out);
+
+/* mbpe_encoder_encode_batch with the outputs of `aux` (rules as for mbpe_pack_tokens_aux; host outputs go through
+ * buffers the encoder keeps, so a repeat call of no larger size leaves mbpe_encoder_alloc_count as it is).
+ *   doc_tok_off_out   optional, host, n_docs + 1 entries: the token offsets of the documents, which the host has
+ *                     after the encode -- what mbpe_pack_cu_seqlens takes.  Written on a query too
+ * The limits on T_d (pos, PACKED) are checked after the encode passes, before the pack kernel.
+ * mbpe_encoder_pack_ms covers this kernel too. */
+MBPE_API int  mbpe_encoder_encode_batch_aux(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                            const uint64_t *chunk_off, uint64_t n_chunks,
+                                            const uint64_t *doc_chunk_off, uint64_t n_docs, const mbpe_pack_spec *spec,
+                                            void *ids_out, uint64_t cap_rows, int out_on_device, uint32_t *len_out,
+                                            uint64_t *n_rows_out, uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
+                                            uint64_t *doc_tok_off_out);
+
 /* ---- decode on the device ----------------------------------------------- */
 
 /* Tokenizer::decode (Tokenizer.h:725-751) for whole token streams on HIP device `device_id`: per token a byte

@@ -76,6 +76,15 @@ MBPE_API int mbpe_tok_encode_batch_packed_device(mbpe_tokenizer *t, const uint8_
                                                  int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
                                                  uint64_t *n_tokens_out);
 
+/* The same with the training-batch outputs of mbpe_encoder_encode_batch_aux (mbpe.h): labels, positions and segments
+ * per `aux` (required), and the documents' token offsets in doc_tok_off_out (optional, host, n_docs + 1), which
+ * mbpe_pack_cu_seqlens takes. */
+MBPE_API int mbpe_tok_encode_batch_aux_device(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off,
+                                              uint64_t n_docs, int verbose, int device_id, const mbpe_pack_spec *spec,
+                                              void *ids_out, uint64_t cap_rows, int out_on_device, uint32_t *len_out,
+                                              uint64_t *n_rows_out, uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
+                                              uint64_t *doc_tok_off_out);
+
 /* decode, Tokenizer.h:725-751.  bytes_out may be NULL to query the length. */
 MBPE_API int mbpe_tok_decode(mbpe_tokenizer *t, const uint32_t *tokens, uint64_t n, int verbose,
                              uint8_t *bytes_out, uint64_t cap, uint64_t *n_out);

@@ -263,6 +263,10 @@ struct mbpe_encoder {
     void *d_ids = nullptr;
     uint32_t *d_len = nullptr;
     uint64_t cap_flat = 0, cap_doc_off = 0, cap_ids = 0, cap_len = 0;
+    // mbpe_encoder_encode_batch_aux: labels, positions and segments that go to the host
+    void *d_labels = nullptr;
+    uint32_t *d_pos = nullptr, *d_seg = nullptr;
+    uint64_t cap_labels = 0, cap_pos = 0, cap_seg = 0;
     float pack_ms = 0.f;                      // the pack kernel of the latest such call
     // host scratch
     std::vector<uint8_t> mask, bytes;
@@ -656,7 +660,7 @@ int enc_run(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_
 int enc_batch_body(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device, const uint64_t *chunk_off,
                    uint64_t n_chunks, const uint64_t *doc_chunk_off, uint64_t n_docs, const mbpe_pack_spec &spec,
                    void *ids_out, uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
-                   uint64_t *n_tokens_out) {
+                   uint64_t *n_tokens_out, const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out) {
     const uint32_t token_bits = spec.out_bits == 16 ? 16 : 32;
     ECHK(hipSetDevice(e->device));
     int rc = grow(&e->d_flat, &e->cap_flat, std::max<uint64_t>(n_bytes, 1) * (token_bits / 8), true, &e->n_allocs);
@@ -670,24 +674,35 @@ int enc_batch_body(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int t
     if (rc != MBPE_OK) return rc;
     e->doc_tok.resize(n_docs + 1);
     for (uint64_t i = 0; i <= n_docs; ++i) e->doc_tok[i] = e->chunk_tok[doc_chunk_off[i]];
+    // (the document lengths exist only now: the limit of pos comes here, still before the pack kernel)
+    if (aux) rc = pack_check_aux(spec, aux, e->doc_tok.data(), n_docs, nullptr, 0);
+    if (rc != MBPE_OK) return rc;
     const uint64_t n_rows = pack_rows(spec, n_tokens, n_docs);
     *n_rows_out = n_rows;
     if (n_tokens_out) *n_tokens_out = n_tokens;
+    if (ids_out && cap_rows < n_rows) return fail(MBPE_ERR_ARG, "ids_out too small");
+    if (doc_tok_off_out) std::copy(e->doc_tok.begin(), e->doc_tok.end(), doc_tok_off_out);
     if (!ids_out) return MBPE_OK;                                // the query
-    if (cap_rows < n_rows) return fail(MBPE_ERR_ARG, "ids_out too small");
     if (n_rows == 0) return MBPE_OK;
-    const uint64_t id_bytes = n_rows * spec.seq_len * (spec.out_bits / 8);
+    const uint64_t id_bytes = n_rows * spec.seq_len * (spec.out_bits / 8), cell_bytes = n_rows * spec.seq_len * 4;
     rc = grow(&e->d_doc_off, &e->cap_doc_off, (n_docs + 1) * 8, true, &e->n_allocs);
     if (rc == MBPE_OK && !out_on_device) {
         rc = grow(&e->d_ids, &e->cap_ids, id_bytes, true, &e->n_allocs);
         if (rc == MBPE_OK && len_out) rc = grow(&e->d_len, &e->cap_len, n_rows * 4, true, &e->n_allocs);
+    }
+    mbpe_pack_aux d_aux = aux ? *aux : mbpe_pack_aux{};
+    if (rc == MBPE_OK && aux && !out_on_device) {
+        if (aux->labels) { rc = grow(&e->d_labels, &e->cap_labels, id_bytes, true, &e->n_allocs); d_aux.labels = e->d_labels; }
+        if (rc == MBPE_OK && aux->pos) { rc = grow(&e->d_pos, &e->cap_pos, cell_bytes, true, &e->n_allocs); d_aux.pos = e->d_pos; }
+        if (rc == MBPE_OK && aux->seg) { rc = grow(&e->d_seg, &e->cap_seg, cell_bytes, true, &e->n_allocs); d_aux.seg = e->d_seg; }
     }
     if (rc != MBPE_OK) return rc;
     ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
     const PackSrc src = {e->d_flat, e->d_doc_off, n_docs, n_tokens, token_bits};
     const PackDst dst = {out_on_device ? ids_out : e->d_ids, out_on_device || !len_out ? len_out : e->d_len, n_rows};
     ECHK(hipEventRecord(e->ev0, e->stream));
-    pack_launch(e->stream, src, spec, dst);
+    if (aux) pack_launch_aux(e->stream, src, spec, dst, d_aux);
+    else pack_launch(e->stream, src, spec, dst);
     ECHK(hipEventRecord(e->ev1, e->stream));
     ECHK(hipStreamSynchronize(e->stream));
     ECHK(hipGetLastError());
@@ -696,6 +711,9 @@ int enc_batch_body(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int t
     if (!out_on_device) {
         ECHK(hipMemcpyAsync(ids_out, e->d_ids, id_bytes, hipMemcpyDeviceToHost, e->stream));
         if (len_out) ECHK(hipMemcpyAsync(len_out, e->d_len, n_rows * 4, hipMemcpyDeviceToHost, e->stream));
+        if (aux && aux->labels) ECHK(hipMemcpyAsync(aux->labels, e->d_labels, id_bytes, hipMemcpyDeviceToHost, e->stream));
+        if (aux && aux->pos) ECHK(hipMemcpyAsync(aux->pos, e->d_pos, cell_bytes, hipMemcpyDeviceToHost, e->stream));
+        if (aux && aux->seg) ECHK(hipMemcpyAsync(aux->seg, e->d_seg, cell_bytes, hipMemcpyDeviceToHost, e->stream));
         ECHK(hipStreamSynchronize(e->stream));
     }
     return MBPE_OK;
@@ -786,7 +804,8 @@ void mbpe_encoder_destroy(mbpe_encoder *e) {
     (void)hipFree(e->tok[0]); (void)hipFree(e->tok[1]); (void)hipFree(e->cand); (void)hipFree(e->span_a);
     (void)hipFree(e->span_b); (void)hipFree(e->span_off); (void)hipFree(e->d_res); (void)hipFree(e->d_singles);
     (void)hipFree(e->d_nul); (void)hipFree(e->d_ends); (void)hipFree(e->d_flat); (void)hipFree(e->d_doc_off);
-    (void)hipFree(e->d_ids); (void)hipFree(e->d_len);
+    (void)hipFree(e->d_ids); (void)hipFree(e->d_len); (void)hipFree(e->d_labels); (void)hipFree(e->d_pos);
+    (void)hipFree(e->d_seg);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -815,10 +834,11 @@ int mbpe_encoder_encode(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, 
                    chunk_tok_off_out, n_out, n_passes_out);
 }
 
-int mbpe_encoder_encode_batch(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
-                              const uint64_t *chunk_off, uint64_t n_chunks, const uint64_t *doc_chunk_off,
-                              uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows,
-                              int out_on_device, uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out) {
+// mbpe_encoder_encode_batch (aux NULL) and mbpe_encoder_encode_batch_aux: the checks that need no device, then the call
+static int enc_batch(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                     const uint64_t *chunk_off, uint64_t n_chunks, const uint64_t *doc_chunk_off, uint64_t n_docs,
+                     const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device, uint32_t *len_out,
+                     uint64_t *n_rows_out, uint64_t *n_tokens_out, const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out) {
     if (n_rows_out) *n_rows_out = 0;
     if (n_tokens_out) *n_tokens_out = 0;
     if (!e || !n_rows_out || !doc_chunk_off || !spec || (!text && n_bytes))
@@ -840,12 +860,37 @@ int mbpe_encoder_encode_batch(mbpe_encoder *e, const uint8_t *text, uint64_t n_b
     if (ids_out && out_on_device &&
         ((uint64_t)(uintptr_t)ids_out % (spec->out_bits / 8) || (uint64_t)(uintptr_t)len_out % 4))
         return fail(MBPE_ERR_ARG, "ids_out or len_out is not aligned to its elements");
+    if (aux) {                                                   // (the document lengths: after the encode)
+        rc = pack_check_aux(*spec, aux, nullptr, n_docs, ids_out, out_on_device);
+        if (rc != MBPE_OK) return rc;
+    }
     try {
         return enc_batch_body(e, text, n_bytes, text_on_device, chunk_off, n_chunks, doc_chunk_off, n_docs, *spec,
-                              ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out);
+                              ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
+                              doc_tok_off_out);
     } catch (const std::bad_alloc &) {
         return fail(MBPE_ERR_OOM, "mbpe_encoder_encode_batch: host allocation failed");
     }
+}
+
+int mbpe_encoder_encode_batch_aux(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                  const uint64_t *chunk_off, uint64_t n_chunks, const uint64_t *doc_chunk_off,
+                                  uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows,
+                                  int out_on_device, uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out,
+                                  const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!aux) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_batch_aux: NULL argument");
+    return enc_batch(e, text, n_bytes, text_on_device, chunk_off, n_chunks, doc_chunk_off, n_docs, spec, ids_out, cap_rows,
+                     out_on_device, len_out, n_rows_out, n_tokens_out, aux, doc_tok_off_out);
+}
+
+int mbpe_encoder_encode_batch(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                              const uint64_t *chunk_off, uint64_t n_chunks, const uint64_t *doc_chunk_off,
+                              uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows,
+                              int out_on_device, uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out) {
+    return enc_batch(e, text, n_bytes, text_on_device, chunk_off, n_chunks, doc_chunk_off, n_docs, spec, ids_out, cap_rows,
+                     out_on_device, len_out, n_rows_out, n_tokens_out, nullptr, nullptr);
 }
 
 int mbpe_encoder_pack_ms(const mbpe_encoder *e, float *ms_out) {

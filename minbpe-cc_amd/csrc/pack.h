@@ -34,6 +34,18 @@ uint64_t pack_rows(const mbpe_pack_spec &spec, uint64_t n_tokens, uint64_t n_doc
 // one kernel on `stream`; dst.n_rows == pack_rows(...) > 0.  Nothing is waited for
 void pack_launch(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst);
 
+// the rules of mbpe_pack_tokens_aux for its aux argument, before any device call: aux itself, the range of
+// ignore_label for the spec's out_bits, the document count when seg is asked for and -- where doc_tok_off is given,
+// PACKED -- the document lengths when pos is; with out_on_device the 16-byte alignment of ids_out and of every aux
+// output.  MBPE_OK, or MBPE_ERR_ARG / MBPE_ERR_VOCAB with the last error set
+int pack_check_aux(const mbpe_pack_spec &spec, const mbpe_pack_aux *aux, const uint64_t *doc_tok_off, uint64_t n_docs,
+                   const void *ids_out, int out_on_device);
+
+// the same matrix from k_pack_aux, which also writes whichever of aux's labels / pos / seg (device memory, 16-byte
+// aligned like dst.ids) are not NULL
+void pack_launch_aux(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst,
+                     const mbpe_pack_aux &aux);
+
 }  // namespace mbpe
 
 #endif

@@ -28,6 +28,7 @@
 #include "pack.h"
 
 #include "hip_host.h"
+#include "pack_host.h"
 #include "span.h"
 
 #include <algorithm>
@@ -217,6 +218,171 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_stream(PackJob j) {
     }
 }
 
+// ---- the training-batch outputs ---------------------------------------------------------------------------------------
+// k_pack_aux writes the ids of either layout and, from the SAME walk, whichever of three more matrices are asked for:
+//   labels  the next element of the cell's document (ignore_label behind its last one and in pad cells)
+//   pos     the element's index k in its document           seg   the document's number d + 1       (0 in pad cells)
+// Unlike the two kernels above it cuts the matrix in CELL-index space: a lane owns the 8 consecutive cells
+// [8 g, 8 g + 8) of the flattened matrix, whatever their width -- one dwordx4 of 16-bit ids, two of 32-bit ids, pos or
+// seg, four of 64-bit ids -- so one (row, column) division or one binary search serves 8 cells of every output.  The
+// outputs are 16-byte aligned (checked by the host), so a full group's stores are aligned and only the last group of
+// the matrix can be partial; it is stored cell by cell.  For the labels the walk runs one element ahead: the element
+// read as a label is kept and becomes the next cell's id, so a group reads 9 tokens at most and none across a
+// document's end.  An output that is NULL is skipped by the whole wave.  Every cell index is 64-bit.
+struct PackAuxJob {
+    PackJob j;
+    void *labels;                            // ids of OUT bits, or NULL
+    uint32_t *pos, *seg;                     // or NULL
+    unsigned long long ignore;               // ignore_label; its low OUT bits are written
+};
+
+constexpr uint32_t kAuxCells = 8;
+
+// the lane's 8 values to cells [c0, c0 + cnt) of a 32-bit matrix
+__device__ __forceinline__ void aux_store32(uint32_t *dst, uint64_t c0, uint32_t cnt, const uint32_t (&v)[kAuxCells]) {
+    if (cnt == kAuxCells) {
+        u32x4 *q = static_cast<u32x4 *>(__builtin_assume_aligned(dst + c0, 16));
+        q[0] = u32x4{v[0], v[1], v[2], v[3]};
+        q[1] = u32x4{v[4], v[5], v[6], v[7]};
+    } else {
+#pragma unroll
+        for (uint32_t e = 0; e < kAuxCells; ++e)
+            if (e < cnt) dst[c0 + e] = v[e];
+    }
+}
+
+// the same for ids of OUT bits; a 64-bit id e has the high word `hi` where bit e of hi_mask is set, else 0
+template <int OUT>
+__device__ __forceinline__ void aux_store_ids(void *dst, uint64_t c0, uint32_t cnt, const uint32_t (&v)[kAuxCells],
+                                              uint32_t hi_mask, uint32_t hi) {
+    if (OUT == 32) {
+        aux_store32(static_cast<uint32_t *>(dst), c0, cnt, v);
+    } else if (OUT == 16) {
+        uint16_t *d16 = static_cast<uint16_t *>(dst);
+        if (cnt == kAuxCells) {
+            *static_cast<u32x4 *>(__builtin_assume_aligned(d16 + c0, 16)) =
+                u32x4{(v[0] & 0xFFFFu) | (v[1] << 16), (v[2] & 0xFFFFu) | (v[3] << 16), (v[4] & 0xFFFFu) | (v[5] << 16),
+                      (v[6] & 0xFFFFu) | (v[7] << 16)};
+        } else {
+#pragma unroll
+            for (uint32_t e = 0; e < kAuxCells; ++e)
+                if (e < cnt) d16[c0 + e] = (uint16_t)v[e];
+        }
+    } else {
+        unsigned long long *d64 = static_cast<unsigned long long *>(dst);
+        uint32_t h[kAuxCells];
+#pragma unroll
+        for (uint32_t e = 0; e < kAuxCells; ++e) h[e] = (hi_mask >> e) & 1u ? hi : 0u;
+        if (cnt == kAuxCells) {
+            u32x4 *q = static_cast<u32x4 *>(__builtin_assume_aligned(d64 + c0, 16));
+            q[0] = u32x4{v[0], h[0], v[1], h[1]};
+            q[1] = u32x4{v[2], h[2], v[3], h[3]};
+            q[2] = u32x4{v[4], h[4], v[5], h[5]};
+            q[3] = u32x4{v[6], h[6], v[7], h[7]};
+        } else {
+#pragma unroll
+            for (uint32_t e = 0; e < kAuxCells; ++e)
+                if (e < cnt) d64[c0 + e] = ((unsigned long long)h[e] << 32) | v[e];
+        }
+    }
+}
+
+template <int IN, int OUT, bool PACKED>
+__global__ __launch_bounds__(kPackThreads) void k_pack_aux(PackAuxJob a) {
+    const PackJob &j = a.j;
+    const bool want_lab = a.labels != nullptr;
+    const uint32_t nbe = j.nb + j.ne;
+    const uint32_t ign_lo = (uint32_t)a.ignore, ign_hi = (uint32_t)(a.ignore >> 32);
+    const uint64_t n_groups = (j.n_out + kAuxCells - 1) / kAuxCells;
+    for (uint64_t g = (uint64_t)blockIdx.x * kPackThreads + threadIdx.x; g < n_groups;
+         g += (uint64_t)gridDim.x * kPackThreads) {
+        const uint64_t c0 = g * kAuxCells;
+        const uint32_t cnt = j.n_out - c0 < kAuxCells ? (uint32_t)(j.n_out - c0) : kAuxCells;
+        uint64_t row = c0 / j.seq_len;
+        uint32_t col = (uint32_t)(c0 - row * j.seq_len);
+        // the document the walk stands in: number d, T elements (bos and eos included), its tokens from src0 on;
+        // k = the element that the next cell inside it holds; lead = pad cells in front (PADDED with pad_left)
+        uint64_t d = 0, k = 0, T = 0, src0 = 0;
+        uint32_t lead = 0;
+        if (PACKED) {
+            if (c0 < j.n_stream) {                               // as in k_pack_stream
+                uint64_t hi_d = j.n_docs;
+                while (hi_d - d > 1) {
+                    const uint64_t mid = d + (hi_d - d) / 2;
+                    if (stream_off(j, mid) <= c0) d = mid;
+                    else hi_d = mid;
+                }
+                src0 = j.doc_off[d];
+                T = j.doc_off[d + 1] - src0 + nbe;
+                k = c0 - (src0 + d * (uint64_t)nbe);
+            }
+        } else {
+            const PadRow r = pad_row(j, row);
+            d = row; T = r.len; src0 = r.src0; lead = r.lead;
+        }
+        auto element = [&](uint64_t i) -> uint32_t {             // element i < T of the document
+            if (j.nb && i == 0) return j.bos;
+            if (j.ne && i == T - 1) return j.eos;
+            return pack_read<IN>(j.tok, src0 + (i - j.nb));
+        };
+        uint32_t id[kAuxCells], lab[kAuxCells], ps[kAuxCells], sg[kAuxCells];
+        uint32_t ign_mask = 0, ahead = 0;                        // ahead: the element read as the cell before's label
+        bool have_ahead = false;
+#pragma unroll
+        for (uint32_t e = 0; e < kAuxCells; ++e) {
+            id[e] = j.pad; lab[e] = ign_lo; ps[e] = 0; sg[e] = 0;
+            ign_mask |= 1u << e;
+            if (e >= cnt) continue;
+            bool in;
+            if (PACKED) {
+                const uint64_t f = c0 + e;
+                in = f < j.n_stream;
+                if (in) {
+                    while (k >= T) {                             // ends: f < n_stream, a document with elements follows
+                        ++d;
+                        k = 0;
+                        src0 = j.doc_off[d];
+                        T = j.doc_off[d + 1] - src0 + nbe;
+                    }
+                }
+                if (col == 0 && j.len) {
+                    const uint64_t left = in ? j.n_stream - f : 0ull;
+                    j.len[row] = left < j.seq_len ? (uint32_t)left : j.seq_len;
+                }
+            } else {
+                if (col == 0 && j.len) j.len[row] = (uint32_t)T;
+                k = col - lead;                                  // wraps for a pad on the left: >= T
+                in = col >= lead && k < T;
+            }
+            if (in) {
+                id[e] = have_ahead ? ahead : element(k);
+                have_ahead = false;
+                if (want_lab && k + 1 < T) {
+                    ahead = element(k + 1);
+                    have_ahead = true;
+                    lab[e] = ahead;
+                    ign_mask &= ~(1u << e);
+                }
+                ps[e] = (uint32_t)k;
+                sg[e] = (uint32_t)d + 1u;
+                if (PACKED) ++k;
+            }
+            if (++col == j.seq_len) {
+                col = 0;
+                ++row;
+                if (!PACKED && e + 1 < cnt) {                    // (another cell of the group: the row exists)
+                    const PadRow r = pad_row(j, row);
+                    d = row; T = r.len; src0 = r.src0; lead = r.lead;
+                }
+            }
+        }
+        aux_store_ids<OUT>(j.out, c0, cnt, id, 0u, 0u);
+        if (want_lab) aux_store_ids<OUT>(a.labels, c0, cnt, lab, ign_mask, ign_hi);
+        if (a.pos) aux_store32(a.pos, c0, cnt, ps);
+        if (a.seg) aux_store32(a.seg, c0, cnt, sg);
+    }
+}
+
 #define PCHK(expr) MBPE_HIP_CHECK(expr, true)
 
 int fail(int code, const std::string &msg) {
@@ -241,6 +407,18 @@ template <int IN, int OUT>
 void launch_unpack(hipStream_t stream, const PackJob &j) {
     hipLaunchKernelGGL((k_pack_stream<IN, OUT, true>), dim3(pack_grid(j.out, j.n_out, OUT)), dim3(kPackThreads), 0, stream,
                        j);
+}
+
+uint32_t aux_grid(uint64_t n_out) {
+    const uint64_t n_groups = (n_out + kAuxCells - 1) / kAuxCells;
+    return (uint32_t)std::min<uint64_t>((n_groups + kPackThreads - 1) / kPackThreads, kPackMaxGrid);
+}
+
+template <int IN, int OUT>
+void launch_pack_aux(hipStream_t stream, bool packed, const PackAuxJob &a) {
+    const dim3 grid(aux_grid(a.j.n_out)), block(kPackThreads);
+    if (packed) hipLaunchKernelGGL((k_pack_aux<IN, OUT, true>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((k_pack_aux<IN, OUT, false>), grid, block, 0, stream, a);
 }
 
 // device time of the calling thread's latest one-shot pack or unpack kernel (mbpe_pack_kernel_ms)
@@ -290,7 +468,7 @@ struct OneShot {
 
 int pack_run(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
              const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec &spec, void *ids_out, uint64_t n_rows,
-             int out_on_device, uint32_t *len_out) {
+             int out_on_device, uint32_t *len_out, const mbpe_pack_aux *aux) {
     int rc = find_device(device_id);
     if (rc != MBPE_OK) return rc;
     OneShot dev;
@@ -304,17 +482,30 @@ int pack_run(int device_id, const void *tokens, uint64_t n_tokens, uint32_t toke
         rc = dev.alloc(&d_ids, id_bytes, nullptr);
         if (rc == MBPE_OK && len_out) rc = dev.alloc(&d_len, n_rows * 4, nullptr);
     }
+    // the aux outputs of a host call go through device buffers of the call's own, like the ids
+    const uint64_t cell_bytes = n_rows * spec.seq_len * 4;
+    mbpe_pack_aux d_aux = aux ? *aux : mbpe_pack_aux{};
+    if (rc == MBPE_OK && aux && !out_on_device) {
+        void *p = nullptr;
+        if (aux->labels) { rc = dev.alloc(&p, id_bytes, nullptr); d_aux.labels = p; }
+        if (rc == MBPE_OK && aux->pos) { rc = dev.alloc(&p, cell_bytes, nullptr); d_aux.pos = static_cast<uint32_t *>(p); }
+        if (rc == MBPE_OK && aux->seg) { rc = dev.alloc(&p, cell_bytes, nullptr); d_aux.seg = static_cast<uint32_t *>(p); }
+    }
     if (rc != MBPE_OK) return rc;
     const PackSrc src = {d_tok, static_cast<const unsigned long long *>(d_off), n_docs, n_tokens, token_bits};
     const PackDst dst = {d_ids, static_cast<uint32_t *>(d_len), n_rows};
     PCHK(hipEventRecord(dev.ev0, dev.stream));
-    pack_launch(dev.stream, src, spec, dst);
+    if (aux) pack_launch_aux(dev.stream, src, spec, dst, d_aux);
+    else pack_launch(dev.stream, src, spec, dst);
     PCHK(hipEventRecord(dev.ev1, dev.stream));
     rc = dev.finish(&g_pack_ms);
     if (rc != MBPE_OK) return rc;
     if (!out_on_device) {
         PCHK(hipMemcpyAsync(ids_out, d_ids, id_bytes, hipMemcpyDeviceToHost, dev.stream));
         if (len_out) PCHK(hipMemcpyAsync(len_out, d_len, n_rows * 4, hipMemcpyDeviceToHost, dev.stream));
+        if (aux && aux->labels) PCHK(hipMemcpyAsync(aux->labels, d_aux.labels, id_bytes, hipMemcpyDeviceToHost, dev.stream));
+        if (aux && aux->pos) PCHK(hipMemcpyAsync(aux->pos, d_aux.pos, cell_bytes, hipMemcpyDeviceToHost, dev.stream));
+        if (aux && aux->seg) PCHK(hipMemcpyAsync(aux->seg, d_aux.seg, cell_bytes, hipMemcpyDeviceToHost, dev.stream));
         PCHK(hipStreamSynchronize(dev.stream));
     }
     return MBPE_OK;
@@ -412,7 +603,7 @@ uint64_t pack_rows(const mbpe_pack_spec &spec, uint64_t n_tokens, uint64_t n_doc
     return (n_tokens + n_docs * nbe + spec.seq_len - 1) / spec.seq_len;
 }
 
-void pack_launch(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst) {
+static PackJob pack_job(const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst) {
     PackJob j = {};
     j.tok = src.tok;
     j.doc_off = src.doc_off;
@@ -430,6 +621,11 @@ void pack_launch(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &s
     j.keep = spec.seq_len - j.nb - j.ne;                         // (PADDED: checked; PACKED does not read it)
     j.pad_left = spec.pad_left != 0;
     j.trunc_left = spec.trunc_left != 0;
+    return j;
+}
+
+void pack_launch(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst) {
+    const PackJob j = pack_job(src, spec, dst);
     const bool packed = spec.layout == MBPE_PACK_PACKED;
     if (src.bits == 16) {
         if (spec.out_bits == 16) launch_pack<16, 16>(stream, packed, j);
@@ -439,6 +635,37 @@ void pack_launch(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &s
         if (spec.out_bits == 32) launch_pack<32, 32>(stream, packed, j);
         else launch_pack<32, 64>(stream, packed, j);
     }
+}
+
+void pack_launch_aux(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst,
+                     const mbpe_pack_aux &aux) {
+    const PackAuxJob a = {pack_job(src, spec, dst), aux.labels, aux.pos, aux.seg, (unsigned long long)aux.ignore_label};
+    const bool packed = spec.layout == MBPE_PACK_PACKED;
+    if (src.bits == 16) {
+        if (spec.out_bits == 16) launch_pack_aux<16, 16>(stream, packed, a);
+        else if (spec.out_bits == 32) launch_pack_aux<16, 32>(stream, packed, a);
+        else launch_pack_aux<16, 64>(stream, packed, a);
+    } else {
+        if (spec.out_bits == 32) launch_pack_aux<32, 32>(stream, packed, a);
+        else launch_pack_aux<32, 64>(stream, packed, a);
+    }
+}
+
+int pack_check_aux(const mbpe_pack_spec &spec, const mbpe_pack_aux *aux, const uint64_t *doc_tok_off, uint64_t n_docs,
+                   const void *ids_out, int out_on_device) {
+    if (!aux) return fail(MBPE_ERR_ARG, "NULL pack aux");
+    const char *msg = "";
+    int rc = pack_check_ignore(spec.out_bits, aux->ignore_label, &msg);
+    if (rc == MBPE_OK && aux->seg) rc = pack_check_seg_docs(n_docs, &msg);
+    if (rc == MBPE_OK && aux->pos && doc_tok_off && spec.layout == MBPE_PACK_PACKED)
+        rc = pack_check_pos_docs(doc_tok_off, n_docs,
+                                 (spec.bos_id != MBPE_NO_TOKEN) + (spec.eos_id != MBPE_NO_TOKEN), &msg);
+    if (rc != MBPE_OK) return fail(rc, msg);
+    if (ids_out && out_on_device)
+        for (const void *p : {ids_out, (const void *)aux->labels, (const void *)aux->pos, (const void *)aux->seg})
+            if ((uint64_t)(uintptr_t)p % 16)
+                return fail(MBPE_ERR_ARG, "ids_out, labels, pos and seg in device memory must be 16-byte aligned");
+    return MBPE_OK;
 }
 
 }  // namespace mbpe
@@ -479,10 +706,59 @@ int mbpe_pack_tokens(int device_id, const void *tokens, uint64_t n_tokens, uint3
         return fail(MBPE_ERR_ARG, "ids_out or len_out is not aligned to its elements");
     try {
         return pack_run(device_id, tokens, n_tokens, token_bits, tokens_on_device, doc_tok_off, n_docs, *spec, ids_out,
-                        n_rows, out_on_device, len_out);
+                        n_rows, out_on_device, len_out, nullptr);
     } catch (const std::bad_alloc &) {
         return fail(MBPE_ERR_OOM, "mbpe_pack_tokens: host allocation failed");
     }
+}
+
+int mbpe_pack_tokens_aux(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
+                         const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
+                         uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                         const mbpe_pack_aux *aux) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (!n_rows_out || !doc_tok_off || !spec || !aux || (!tokens && n_tokens))
+        return fail(MBPE_ERR_ARG, "mbpe_pack_tokens_aux: NULL argument");
+    int rc = pack_check_spec(spec, token_bits);
+    if (rc == MBPE_OK) rc = mbpe_host::check_doc_tok_off(doc_tok_off, n_docs, n_tokens);
+    if (rc != MBPE_OK) return rc;
+    if (n_tokens >> 40 || n_docs >> 40) return fail(MBPE_ERR_ARG, "more than 2^40 tokens or documents");
+    rc = pack_check_aux(*spec, aux, doc_tok_off, n_docs, ids_out, out_on_device);
+    if (rc != MBPE_OK) return rc;
+    const uint64_t n_rows = pack_rows(*spec, n_tokens, n_docs);
+    *n_rows_out = n_rows;
+    if (!ids_out) return MBPE_OK;                                // the query
+    if (cap_rows < n_rows) return fail(MBPE_ERR_ARG, "ids_out too small");
+    if (n_rows == 0) return MBPE_OK;
+    if (out_on_device && (uint64_t)(uintptr_t)len_out % 4) return fail(MBPE_ERR_ARG, "len_out is not aligned to its elements");
+    try {
+        return pack_run(device_id, tokens, n_tokens, token_bits, tokens_on_device, doc_tok_off, n_docs, *spec, ids_out,
+                        n_rows, out_on_device, len_out, aux);
+    } catch (const std::bad_alloc &) {
+        return fail(MBPE_ERR_OOM, "mbpe_pack_tokens_aux: host allocation failed");
+    }
+}
+
+int mbpe_pack_cu_seqlens(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, int32_t *cu_out,
+                         uint64_t cap_seqs, uint64_t *n_seqs_out, uint32_t *max_seqlen_out) {
+    if (n_seqs_out) *n_seqs_out = 0;
+    if (max_seqlen_out) *max_seqlen_out = 0;
+    if (!doc_tok_off || !spec || !n_seqs_out || !max_seqlen_out)
+        return fail(MBPE_ERR_ARG, "mbpe_pack_cu_seqlens: NULL argument");
+    int rc = pack_check_spec(spec, spec->out_bits == 16 ? 16 : 32);
+    if (rc != MBPE_OK) return rc;
+    if (spec->layout != MBPE_PACK_PACKED)
+        return fail(MBPE_ERR_ARG, "cu_seqlens goes with MBPE_PACK_PACKED only (the sequences of PADDED are its rows)");
+    rc = mbpe_host::check_doc_tok_off(doc_tok_off, n_docs, doc_tok_off[n_docs]);
+    if (rc != MBPE_OK) return rc;
+    const char *msg = "";
+    uint64_t n_seqs = 0;
+    uint32_t longest = 0;
+    rc = pack_cu_seqlens(doc_tok_off, n_docs, spec->seq_len, (spec->bos_id != MBPE_NO_TOKEN) + (spec->eos_id != MBPE_NO_TOKEN),
+                         cu_out, cap_seqs, &n_seqs, &longest, &msg);
+    *n_seqs_out = n_seqs;                                        // (also when cap_seqs is too small)
+    *max_seqlen_out = longest;
+    return rc == MBPE_OK ? MBPE_OK : fail(rc, msg);
 }
 
 int mbpe_unpack_tokens(int device_id, const void *ids, uint64_t n_rows, uint32_t seq_len, uint32_t id_bits,

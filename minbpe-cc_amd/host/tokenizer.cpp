@@ -338,15 +338,20 @@ int Tokenizer::encode_batch_flat(const char *text, const uint64_t *doc_off, uint
 
 int Tokenizer::encode_batch_packed(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
                                    const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
-                                   uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out) {
+                                   uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out,
+                                   const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out) {
     std::string buf;
     std::vector<uint64_t> off, first_chunk;
     batch_chunks(text, doc_off, n_docs, verbose, &buf, &off, &first_chunk);
     mbpe_encoder *enc = device_encoder(device);
     uint64_t n_tokens = 0;
-    const int rc = mbpe_encoder_encode_batch(enc, reinterpret_cast<const uint8_t *>(buf.data()), buf.size(), 0, off.data(),
-                                             off.size() - 1, first_chunk.data(), n_docs, spec, ids_out, cap_rows,
-                                             out_on_device, len_out, n_rows_out, &n_tokens);
+    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(buf.data());
+    const int rc = aux ? mbpe_encoder_encode_batch_aux(enc, bytes, buf.size(), 0, off.data(), off.size() - 1,
+                                                       first_chunk.data(), n_docs, spec, ids_out, cap_rows, out_on_device,
+                                                       len_out, n_rows_out, &n_tokens, aux, doc_tok_off_out)
+                       : mbpe_encoder_encode_batch(enc, bytes, buf.size(), 0, off.data(), off.size() - 1,
+                                                   first_chunk.data(), n_docs, spec, ids_out, cap_rows, out_on_device,
+                                                   len_out, n_rows_out, &n_tokens);
     if (n_tokens_out) *n_tokens_out = n_tokens;
     if (rc == MBPE_OK && verbose)
         std::cout << "Encoded " << n_docs << " texts (length " << buf.size() << ") to " << n_tokens << " tokens in "
@@ -695,6 +700,31 @@ int mbpe_tok_encode_batch_packed_device(mbpe_tokenizer *t, const uint8_t *text, 
     try {
         return t->t->encode_batch_packed(reinterpret_cast<const char *>(text), doc_off, n_docs, verbose != 0, device_id,
                                          spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out);
+    } catch (const mbpe_host::CodedError &e) {      // mbpe_encoder_create failed: its own code
+        mbpe_host::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        mbpe_host::set_last_error(e.what());
+        return MBPE_ERR_ARG;
+    }
+}
+
+int mbpe_tok_encode_batch_aux_device(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off, uint64_t n_docs,
+                                     int verbose, int device_id, const mbpe_pack_spec *spec, void *ids_out,
+                                     uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                                     uint64_t *n_tokens_out, const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!t || !n_rows_out || !doc_off || !spec || !aux || device_id < 0 || (!text && doc_off[n_docs] > doc_off[0])) {
+        mbpe_host::set_last_error("mbpe_tok_encode_batch_aux_device: NULL argument or negative device");
+        return MBPE_ERR_ARG;
+    }
+    for (uint64_t i = 0; i < n_docs; ++i)
+        if (doc_off[i + 1] < doc_off[i]) { mbpe_host::set_last_error("doc_off must be ascending"); return MBPE_ERR_ARG; }
+    try {
+        return t->t->encode_batch_packed(reinterpret_cast<const char *>(text), doc_off, n_docs, verbose != 0, device_id,
+                                         spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
+                                         doc_tok_off_out);
     } catch (const mbpe_host::CodedError &e) {      // mbpe_encoder_create failed: its own code
         mbpe_host::set_last_error(e.what());
         return e.code;

@@ -43,11 +43,12 @@ public:
     int encode_batch_flat(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
                           Token *tokens_out, uint64_t cap, uint64_t *n_out, uint64_t *buf_bytes_out,
                           std::vector<uint64_t> *doc_tok_off);
-    // the same documents as one id matrix (mbpe_encoder_encode_batch): spec, ids_out .. n_tokens_out go to it as they
-    // are, its code is returned
+    // the same documents as one id matrix (mbpe_encoder_encode_batch; with aux, mbpe_encoder_encode_batch_aux): spec,
+    // ids_out .. doc_tok_off_out go to it as they are, its code is returned
     int encode_batch_packed(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
                             const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
-                            uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out);
+                            uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out,
+                            const mbpe_pack_aux *aux = nullptr, uint64_t *doc_tok_off_out = nullptr);
     // :725-751; device >= 0 expands the tokens on that HIP device (mbpe_decode_tokens) instead of the host loop
     std::string decode(const std::vector<Token> &tokens, bool verbose, int device = -1);
     // decode() of every token list, [i] == decode(docs[i], false, -1), in one mbpe_decode_batch on HIP device `device`

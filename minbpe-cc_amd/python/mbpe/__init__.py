@@ -32,13 +32,14 @@ EXPORTS = [
     "mbpe_encoder_destroy", "mbpe_encoder_encode", "mbpe_encoder_set_option", "mbpe_encoder_kernel_ms",
     "mbpe_encoder_alloc_count", "mbpe_encoder_pass_tokens", "mbpe_decode_batch", "mbpe_decoder_alloc_count",
     "mbpe_pack_tokens", "mbpe_unpack_tokens", "mbpe_pack_kernel_ms", "mbpe_encoder_encode_batch", "mbpe_encoder_pack_ms",
+    "mbpe_pack_tokens_aux", "mbpe_pack_cu_seqlens", "mbpe_encoder_encode_batch_aux",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
     "mbpe_tok_create", "mbpe_tok_destroy", "mbpe_tok_set_special_tokens", "mbpe_tok_train", "mbpe_tok_set_merges",
     "mbpe_tok_get_merges", "mbpe_tok_save", "mbpe_tok_load", "mbpe_tok_encode", "mbpe_tok_encode_device",
     "mbpe_tok_decode", "mbpe_tok_decode_device", "mbpe_tok_encode_batch_device", "mbpe_tok_decode_batch_device",
-    "mbpe_tok_encode_batch_packed_device", "mbpe_tok_decode_padded_device",
+    "mbpe_tok_encode_batch_packed_device", "mbpe_tok_decode_padded_device", "mbpe_tok_encode_batch_aux_device",
 ]
 
 
@@ -80,7 +81,17 @@ class PackSpec(ctypes.Structure):
     ]
 
 
+class PackAux(ctypes.Structure):
+    """mbpe_pack_aux (include/mbpe.h): where labels, positions and segments go (NULL: not asked for)."""
+    _fields_ = [
+        ("labels", ctypes.c_void_p), ("pos", ctypes.c_void_p), ("seg", ctypes.c_void_p),
+        ("ignore_label", ctypes.c_int64),
+    ]
+
+
 _ID_DTYPES = {16: np.uint16, 32: np.uint32, 64: np.uint64}
+# labels are ids or ignore_label: signed where a negative ignore_label fits
+_LABEL_DTYPES = {16: np.uint16, 32: np.int32, 64: np.int64}
 
 
 def pack_spec(seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None, pad_left=False,
@@ -167,7 +178,11 @@ def lib():
     L.mbpe_pack_kernel_ms.argtypes = [vp]
     L.mbpe_encoder_encode_batch.argtypes = [vp, vp, u64, i32, vp, u64, vp, u64, vp, vp, u64, i32, vp, vp, vp]
     L.mbpe_encoder_pack_ms.argtypes = [vp, vp]
+    L.mbpe_pack_tokens_aux.argtypes = L.mbpe_pack_tokens.argtypes + [vp]
+    L.mbpe_pack_cu_seqlens.argtypes = [vp, u64, vp, vp, u64, vp, vp]
+    L.mbpe_encoder_encode_batch_aux.argtypes = L.mbpe_encoder_encode_batch.argtypes + [vp, vp]
     L.mbpe_tok_encode_batch_packed_device.argtypes = [vp, vp, vp, u64, i32, i32, vp, vp, u64, i32, vp, vp, vp]
+    L.mbpe_tok_encode_batch_aux_device.argtypes = L.mbpe_tok_encode_batch_packed_device.argtypes + [vp, vp]
     L.mbpe_tok_decode_padded_device.argtypes = [vp, vp, u64, u32, vp, i32, i32, vp, u64, vp, vp]
     L.mbpe_tok_encode_batch_device.argtypes = [vp, vp, vp, u64, i32, i32, vp, u64, vp, vp]
     L.mbpe_decoder_create.argtypes = [i32, vp, u32, vp, vp, vp, u32, ctypes.POINTER(vp)]
@@ -316,6 +331,89 @@ def pack_tokens(tokens, doc_tok_off, seq_len, layout="padded", out_bits=32, pad_
     return ids, lengths
 
 
+def pack_cu_seqlens(doc_tok_off, seq_len, bos_id=None, eos_id=None):
+    """mbpe_pack_cu_seqlens: the boundaries of the runs of equal (row, segment) in the flattened MBPE_PACK_PACKED matrix
+    of these documents -> (int32 array of n_seqs + 1 entries, max_seqlen).  Host arithmetic alone: needs no device."""
+    spec = pack_spec(seq_len, "packed", 32, 0, bos_id, eos_id)
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    n_seqs, longest = ctypes.c_uint64(), ctypes.c_uint32()
+    head = (off.ctypes.data, len(off) - 1, ctypes.byref(spec))
+    _check(lib().mbpe_pack_cu_seqlens(*head, None, 0, ctypes.byref(n_seqs), ctypes.byref(longest)))
+    cu = np.zeros(n_seqs.value + 1, dtype=np.int32)
+    _check(lib().mbpe_pack_cu_seqlens(*head, cu.ctypes.data, n_seqs.value, ctypes.byref(n_seqs), ctypes.byref(longest)))
+    return cu, longest.value
+
+
+class _AuxCall:
+    """What the three *_aux calls share: the mbpe_pack_aux of a call and the dict it returns."""
+
+    def __init__(self, spec, labels, positions, segments, cu_seqlens, ignore_label):
+        self.spec, self.want, self.cu = spec, (labels, positions, segments), cu_seqlens
+        self.ignore = int(ignore_label)
+
+    def device(self, labels_ptr, pos_ptr, seg_ptr):
+        return PackAux(labels_ptr or None, pos_ptr or None, seg_ptr or None, self.ignore)
+
+    def host(self, n_rows):
+        """-> (PackAux, its arrays by name) for n_rows rows in host memory."""
+        shape = (n_rows, self.spec.seq_len)
+        dtypes = (("labels", _LABEL_DTYPES[self.spec.out_bits]), ("positions", np.uint32), ("segments", np.uint32))
+        arrays = {name: np.zeros(shape, dtype=dt) for (name, dt), w in zip(dtypes, self.want) if w}
+        ptr = lambda name: arrays[name].ctypes.data if name in arrays and arrays[name].size else None
+        return PackAux(ptr("labels"), ptr("positions"), ptr("segments"), self.ignore), arrays
+
+    def result(self, ids, lengths, arrays, doc_tok_off):
+        out = {"ids": ids, "lengths": lengths}
+        out.update(arrays)
+        if self.cu:
+            out["cu_seqlens"], out["max_seqlen"] = self.cu_seqlens(doc_tok_off)
+        return out
+
+    def cu_seqlens(self, doc_tok_off):
+        none = lambda t: None if t == NO_TOKEN else t
+        return pack_cu_seqlens(doc_tok_off, self.spec.seq_len, none(self.spec.bos_id), none(self.spec.eos_id))
+
+
+def pack_tokens_aux(tokens, doc_tok_off, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
+                    pad_left=False, trunc_left=False, device=0, tokens_ptr=None, n_tokens=None, token_bits=None,
+                    out_ptr=None, len_ptr=None, cap_rows=None, labels=False, positions=False, segments=False,
+                    cu_seqlens=False, ignore_label=-100, labels_ptr=None, pos_ptr=None, seg_ptr=None):
+    """mbpe_pack_tokens_aux: pack_tokens plus what a training step needs, from one kernel -> a dict with "ids",
+    "lengths" and whichever of "labels" (next-token targets that never cross a document; ignore_label elsewhere; int32
+    / int64, uint16 for out_bits 16), "positions" (uint32, restarting at every document), "segments" (uint32, document
+    number + 1, 0 = pad) and "cu_seqlens" with "max_seqlen" (layout "packed" only) were asked for.
+    With out_ptr= the matrices go to device memory at out_ptr / len_ptr / labels_ptr / pos_ptr / seg_ptr (each 16-byte
+    aligned; None = not wanted) and the row count is returned -- (row count, cu_seqlens, max_seqlen) with
+    cu_seqlens=True."""
+    spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
+    call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label)
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    if tokens_ptr is None:
+        t = np.ascontiguousarray(tokens)
+        if t.dtype not in (np.dtype(np.uint16), np.dtype(np.uint32)):
+            t = t.astype(np.uint32)
+        t = t.reshape(-1)
+        tp, n_tokens, token_bits, on_dev = (t.ctypes.data if len(t) else None), len(t), t.dtype.itemsize * 8, 0
+    else:
+        tp, on_dev = _ptr(tokens_ptr), 1
+    n_rows = ctypes.c_uint64()
+    head = (device, tp, n_tokens, token_bits, on_dev, off.ctypes.data, len(off) - 1, ctypes.byref(spec))
+    if out_ptr is not None:
+        aux = call.device(labels_ptr, pos_ptr, seg_ptr)
+        cu = call.cu_seqlens(off) if cu_seqlens else None
+        _check(lib().mbpe_pack_tokens_aux(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), ctypes.byref(n_rows),
+                                          ctypes.byref(aux)))
+        return (n_rows.value,) + cu if cu_seqlens else n_rows.value
+    aux = call.device(None, None, None)
+    _check(lib().mbpe_pack_tokens_aux(*head, None, 0, 0, None, ctypes.byref(n_rows), ctypes.byref(aux)))
+    ids, lengths = _matrix(n_rows.value, spec)
+    aux, arrays = call.host(n_rows.value)
+    if n_rows.value:
+        _check(lib().mbpe_pack_tokens_aux(*head, ids.ctypes.data, n_rows.value, 0, lengths.ctypes.data,
+                                          ctypes.byref(n_rows), ctypes.byref(aux)))
+    return call.result(ids, lengths, arrays, off)
+
+
 def unpack_tokens(ids, lengths, dtype=np.uint32, device=0, ids_ptr=None, len_ptr=None, shape=None, id_bits=None,
                   out_ptr=None, cap=0):
     """mbpe_unpack_tokens: a right-padded matrix ids [n_rows, seq_len] (uint16 / uint32 / uint64) and its lengths ->
@@ -433,24 +531,9 @@ class Encoder:
         instead.  With out_ptr= and len_ptr= (device memory for cap_rows rows, e.g. a torch tensor's data_ptr()) the
         matrix is written there and the row count is returned."""
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
-        if text_ptr is None and isinstance(texts_or_buffer, (list, tuple)):
-            parts = [bytes(_u8(t)) for t in texts_or_buffer]
-            chunk_off = np.zeros(len(parts) + 1, dtype=np.uint64)
-            if parts:
-                chunk_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
-            texts_or_buffer, doc_chunk_off = b"".join(parts), None
-        if text_ptr is None:
-            text = _u8(texts_or_buffer)
-            tp, n_bytes, on_dev = (text.ctypes.data if len(text) else None), len(text), 0
-        else:
-            tp, on_dev = _ptr(text_ptr), 1
-        off = np.array([0, n_bytes], dtype=np.uint64) if chunk_off is None else \
-            np.ascontiguousarray(chunk_off, dtype=np.uint64)
-        docs = np.arange(len(off), dtype=np.uint64) if doc_chunk_off is None else \
-            np.ascontiguousarray(doc_chunk_off, dtype=np.uint64)
+        head, keep = self._batch_head(texts_or_buffer, chunk_off, doc_chunk_off, text_ptr, n_bytes, spec)
+        docs = keep[-1]
         n_rows, n_tok = ctypes.c_uint64(), ctypes.c_uint64()
-        head = (self._h, tp, n_bytes, on_dev, off.ctypes.data, len(off) - 1, docs.ctypes.data, len(docs) - 1,
-                ctypes.byref(spec))
         tail = (ctypes.byref(n_rows), ctypes.byref(n_tok))
         if out_ptr is not None:
             _check(lib().mbpe_encoder_encode_batch(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail))
@@ -465,6 +548,63 @@ class Encoder:
                                                lengths.ctypes.data if len(ids) else None, *tail))
         self.n_tokens = n_tok.value
         return ids, lengths
+
+    def _batch_head(self, texts_or_buffer, chunk_off, doc_chunk_off, text_ptr, n_bytes, spec):
+        """The arguments of mbpe_encoder_encode_batch up to spec -> (tuple, the arrays it points into; the last of them
+        the documents' chunk offsets)."""
+        if text_ptr is None and isinstance(texts_or_buffer, (list, tuple)):
+            parts = [bytes(_u8(t)) for t in texts_or_buffer]
+            chunk_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+            if parts:
+                chunk_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
+            texts_or_buffer, doc_chunk_off = b"".join(parts), None
+        text = None
+        if text_ptr is None:
+            text = _u8(texts_or_buffer)
+            tp, n_bytes, on_dev = (text.ctypes.data if len(text) else None), len(text), 0
+        else:
+            tp, on_dev = _ptr(text_ptr), 1
+        off = np.array([0, n_bytes], dtype=np.uint64) if chunk_off is None else \
+            np.ascontiguousarray(chunk_off, dtype=np.uint64)
+        docs = np.arange(len(off), dtype=np.uint64) if doc_chunk_off is None else \
+            np.ascontiguousarray(doc_chunk_off, dtype=np.uint64)
+        head = (self._h, tp, n_bytes, on_dev, off.ctypes.data, len(off) - 1, docs.ctypes.data, len(docs) - 1,
+                ctypes.byref(spec))
+        return head, (text, off, docs)
+
+    def encode_batch_aux(self, texts_or_buffer, chunk_off=None, doc_chunk_off=None, *, seq_len, layout="padded",
+                         out_bits=32, pad_id=0, bos_id=None, eos_id=None, pad_left=False, trunc_left=False,
+                         text_ptr=None, n_bytes=None, out_ptr=None, len_ptr=None, cap_rows=None, labels=False,
+                         positions=False, segments=False, cu_seqlens=False, ignore_label=-100, labels_ptr=None,
+                         pos_ptr=None, seg_ptr=None):
+        """encode_batch plus labels, positions, segments and cu_seqlens (mbpe_encoder_encode_batch_aux): the arguments
+        of encode_batch and those of pack_tokens_aux, whose dict (or, with out_ptr=, row count) is returned.  The
+        documents' token offsets of the call: self.doc_tok_off."""
+        spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
+        call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label)
+        head, keep = self._batch_head(texts_or_buffer, chunk_off, doc_chunk_off, text_ptr, n_bytes, spec)
+        n_docs = len(keep[-1]) - 1
+        n_rows, n_tok = ctypes.c_uint64(), ctypes.c_uint64()
+        doc_tok_off = np.zeros(n_docs + 1, dtype=np.uint64)
+        tail = (ctypes.byref(n_rows), ctypes.byref(n_tok))
+        if out_ptr is not None:
+            aux = call.device(labels_ptr, pos_ptr, seg_ptr)
+            _check(lib().mbpe_encoder_encode_batch_aux(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail,
+                                                       ctypes.byref(aux), doc_tok_off.ctypes.data))
+            self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
+            return (n_rows.value,) + call.cu_seqlens(doc_tok_off) if cu_seqlens else n_rows.value
+        if spec.layout == PACK_PADDED:
+            n_rows.value = n_docs                     # known without a query
+        else:
+            aux = call.device(None, None, None)
+            _check(lib().mbpe_encoder_encode_batch_aux(*head, None, 0, 0, None, *tail, ctypes.byref(aux), None))
+        ids, lengths = _matrix(n_rows.value, spec)
+        aux, arrays = call.host(n_rows.value)
+        _check(lib().mbpe_encoder_encode_batch_aux(*head, ids.ctypes.data if ids.size else None, len(ids), 0,
+                                                   lengths.ctypes.data if len(ids) else None, *tail, ctypes.byref(aux),
+                                                   doc_tok_off.ctypes.data))
+        self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
+        return call.result(ids, lengths, arrays, doc_tok_off)
 
     def pack_ms(self):
         """Device time of the pack kernel of the latest encode_batch (mbpe_encoder_pack_ms)."""
@@ -895,6 +1035,44 @@ class Tokenizer:
         _check(lib().mbpe_tok_encode_batch_packed_device(*head, ids.ctypes.data if ids.size else None, len(ids), 0,
                                                          lengths.ctypes.data if len(ids) else None, *tail))
         return ids, lengths
+
+    def encode_batch_aux(self, texts, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
+                         pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
+                         labels=False, positions=False, segments=False, cu_seqlens=False, ignore_label=-100,
+                         labels_ptr=None, pos_ptr=None, seg_ptr=None):
+        """encode_batch_padded plus labels, positions, segments and cu_seqlens (mbpe_tok_encode_batch_aux_device): its
+        arguments and those of pack_tokens_aux, whose dict (or, with out_ptr=, row count) is returned.  The documents'
+        token offsets of the call: self.doc_tok_off."""
+        spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
+        call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label)
+        parts = [bytes(_u8(t)) for t in texts]
+        doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        if parts:
+            doc_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
+        text = np.frombuffer(b"".join(parts), dtype=np.uint8)
+        n_rows, n_tok = ctypes.c_uint64(), ctypes.c_uint64()
+        doc_tok_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        head = (self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data, len(parts), 0, device,
+                ctypes.byref(spec))
+        tail = (ctypes.byref(n_rows), ctypes.byref(n_tok))
+        fn = lib().mbpe_tok_encode_batch_aux_device
+        if out_ptr is not None:
+            aux = call.device(labels_ptr, pos_ptr, seg_ptr)
+            _check(fn(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail, ctypes.byref(aux),
+                      doc_tok_off.ctypes.data))
+            self.doc_tok_off = doc_tok_off
+            return (n_rows.value,) + call.cu_seqlens(doc_tok_off) if cu_seqlens else n_rows.value
+        if spec.layout == PACK_PADDED:
+            n_rows.value = len(parts)
+        else:
+            aux = call.device(None, None, None)
+            _check(fn(*head, None, 0, 0, None, *tail, ctypes.byref(aux), None))
+        ids, lengths = _matrix(n_rows.value, spec)
+        aux, arrays = call.host(n_rows.value)
+        _check(fn(*head, ids.ctypes.data if ids.size else None, len(ids), 0, lengths.ctypes.data if len(ids) else None,
+                  *tail, ctypes.byref(aux), doc_tok_off.ctypes.data))
+        self.doc_tok_off = doc_tok_off
+        return call.result(ids, lengths, arrays, doc_tok_off)
 
     def decode_padded(self, ids, lengths, device=0):
         """A right-padded id matrix [n_rows, seq_len] and its lengths -> the list of the rows' texts, unpacked and

@@ -10,6 +10,17 @@ time limit; when one fails, nothing after it is started.
             with numpy, upload -- against one Tokenizer.encode_batch_padded into device memory.
 
     python tools/pack_time.py --json profiles/r09_pack.json
+
+With --aux, the training-batch outputs (k_pack_aux) instead, on the same two shapes -- PADDED seq_len 64 and PACKED
+seq_len 2,048 over shakespeare x --rep, every line a document, 32-bit ids -- from the flat tokens in device memory
+(one shakespeare encoded line by line, its tokens repeated on the device: every copy encodes alike).  Per layout:
+  aux_all   (a) mbpe_pack_tokens_aux with labels, pos and seg, alternating with (c) the route a user has today: the three
+            matrices built by torch ops on the device from the ids, the lengths and the uploaded offsets.  Kernel time
+            of (a), wall clock of both, peak extra device memory of (c), and torch.equal of the results
+  aux_ids   (b) mbpe_pack_tokens_aux with no output but ids and lengths, alternating with mbpe_pack_tokens (k_pack_padded
+            / k_pack_stream): mbpe_pack_kernel_ms of both, and torch.equal of the matrices
+
+    python tools/pack_time.py --aux --json profiles/r10_pack_aux.json
 """
 import argparse
 import json
@@ -178,7 +189,149 @@ def step_route(args):
                       "encode_batch_padded_s_median": statistics.median(b)}))
 
 
-STEPS = {"batch": step_batch, "wide": step_wide, "route": step_route}
+AUX_SHAPES = {"padded": 64, "packed": 2048}
+IGNORE = -100
+
+
+def aux_setup(args):
+    """-> (dev, flat tokens on the device, doc_tok_off, facts): shakespeare x rep, every line a document."""
+    import numpy as np
+    import torch
+    import mbpe
+    import oracle as O
+    dev = torch.device("cuda", 0)
+    lines = open(SHAKESPEARE, "rb").read().splitlines(keepends=True)
+    tok = mbpe.Tokenizer(O.GPT4_SPLIT_PATTERN)
+    tok.set_merges(O.parse_model(open(MODEL, "rb").read())[2])
+    enc = tok.encode_batch(lines, device=0)
+    tok.close()
+    flat = np.concatenate(enc).astype(np.uint32)
+    one_off = np.concatenate([[0], np.cumsum([len(e) for e in enc])]).astype(np.uint64)
+    off = tiled(one_off, len(flat), args.rep)
+    tokens = torch.from_numpy(flat.view(np.int32)).to(dev).repeat(args.rep)
+    torch.cuda.synchronize()
+    facts = {"device": torch.cuda.get_device_name(0), "lib": mbpe.lib().mbpe_version().decode(), "rep": args.rep,
+             "layout": args.layout, "seq_len": AUX_SHAPES[args.layout], "out_bits": 32, "tokens": tokens.numel(),
+             "documents": len(off) - 1, "longest_document": int(np.diff(one_off.astype(np.int64)).max())}
+    return dev, tokens, off, facts
+
+
+def aux_rows(tokens, off, seq_len, layout):
+    """The row count of the matrix: the query of mbpe_pack_tokens (no device work)."""
+    import ctypes
+    import mbpe
+    spec = mbpe.pack_spec(seq_len, layout, 32, PAD)
+    n_rows = ctypes.c_uint64()
+    rc = mbpe.lib().mbpe_pack_tokens(0, ctypes.c_void_p(tokens.data_ptr()), tokens.numel(), 32, 1, off.ctypes.data,
+                                     len(off) - 1, ctypes.byref(spec), None, 0, 1, None, ctypes.byref(n_rows))
+    assert rc == mbpe.OK, rc
+    return n_rows.value
+
+
+def torch_route(torch, ids, lengths, off_host, packed):
+    """What a user builds today from the packed ids, the lengths and the host's offsets -> (labels, pos, seg), int32."""
+    dev = ids.device
+    n_rows, seq_len = ids.shape
+    if not packed:                                                   # right-padded rows: a column mask
+        col = torch.arange(seq_len, dtype=torch.int32, device=dev)
+        mask = col[None, :] < lengths[:, None]
+        pos = torch.where(mask, col[None, :], 0).to(torch.int32)
+        seg = torch.where(mask, torch.arange(1, n_rows + 1, dtype=torch.int32, device=dev)[:, None], 0).to(torch.int32)
+    else:                                                            # the cell's document by a search in the offsets
+        off = torch.from_numpy(off_host.view("int64")).to(dev)
+        f = torch.arange(n_rows * seq_len, dtype=torch.int64, device=dev)
+        d = torch.searchsorted(off[1:], f, right=True)               # (the first document that ends behind f)
+        live = f < off[-1]
+        d.clamp_(max=off.numel() - 2)
+        pos = torch.where(live, f - off[d], 0).to(torch.int32).view(n_rows, seq_len)
+        seg = torch.where(live, d + 1, 0).to(torch.int32).view(n_rows, seq_len)
+    # the usual shift by one column: the last column has no target
+    labels = torch.full_like(ids, IGNORE)
+    same = (seg[:, 1:] == seg[:, :-1]) & (seg[:, 1:] != 0)
+    labels[:, :-1] = torch.where(same, ids[:, 1:], IGNORE)
+    return labels, pos, seg
+
+
+def step_aux_all(args):
+    import torch
+    import mbpe
+    dev, tokens, off, res = aux_setup(args)
+    layout, seq_len = args.layout, AUX_SHAPES[args.layout]
+    kw = dict(tokens_ptr=tokens.data_ptr(), n_tokens=tokens.numel(), token_bits=32)
+    n_rows = aux_rows(tokens, off, seq_len, layout)
+    ids, lab, pos, seg = (torch.empty((n_rows, seq_len), dtype=torch.int32, device=dev) for _ in range(4))
+    lengths = torch.empty(n_rows, dtype=torch.int32, device=dev)
+
+    def ours():
+        got = mbpe.pack_tokens_aux(None, off, seq_len, layout, 32, PAD, out_ptr=ids.data_ptr(), len_ptr=lengths.data_ptr(),
+                                   cap_rows=n_rows, labels_ptr=lab.data_ptr(), pos_ptr=pos.data_ptr(),
+                                   seg_ptr=seg.data_ptr(), ignore_label=IGNORE, **kw)
+        assert got == n_rows
+        return mbpe.pack_kernel_ms()
+
+    ms, wall_a, wall_c, peak = [], [], [], []
+    torch.cuda.synchronize()
+    for i in range(1 + args.reps):
+        t = time.perf_counter(); k = ours(); torch.cuda.synchronize(); ta = time.perf_counter() - t
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        t = time.perf_counter()
+        want = torch_route(torch, ids, lengths, off, layout == "packed")
+        torch.cuda.synchronize()
+        tc = time.perf_counter() - t
+        extra = torch.cuda.max_memory_allocated() - base - sum(w.numel() * 4 for w in want)
+        if i:
+            ms.append(k); wall_a.append(ta); wall_c.append(tc); peak.append(extra)
+        if i < args.reps:
+            del want
+            torch.cuda.empty_cache()
+    cols = slice(None, -1) if layout == "packed" else slice(None)
+    res.update({
+        "rows": n_rows, "cells": n_rows * seq_len,
+        "aux_kernel_ms": ms, "aux_kernel_ms_median": statistics.median(ms),
+        "aux_wall_s": wall_a, "aux_wall_s_median": statistics.median(wall_a),
+        "torch_wall_s": wall_c, "torch_wall_s_median": statistics.median(wall_c),
+        "torch_peak_extra_bytes": max(peak), "result_bytes_three_matrices": 3 * n_rows * seq_len * 4,
+        "pos_equal": bool(torch.equal(want[1], pos)), "seg_equal": bool(torch.equal(want[2], seg)),
+        "labels_equal_compared_columns": "all but the last" if layout == "packed" else "all",
+        "labels_equal": bool(torch.equal(want[0][:, cols], lab[:, cols])),
+        "last_column_labels_that_differ": int((want[0][:, -1] != lab[:, -1]).sum()),
+        "bytes_written": n_rows * seq_len * 16 + n_rows * 4,
+        "bytes_read": int(lengths.sum(dtype=torch.int64)) * 4 + len(off) * 8})
+    res["GBps"] = (res["bytes_read"] + res["bytes_written"]) / res["aux_kernel_ms_median"] / 1e6
+    res["share_of_8TBps"] = res["GBps"] * 1e9 / PEAK_BYTES_PER_S
+    assert res["pos_equal"] and res["seg_equal"] and res["labels_equal"], res
+    print(json.dumps(res))
+
+
+def step_aux_ids(args):
+    import torch
+    import mbpe
+    dev, tokens, off, res = aux_setup(args)
+    layout, seq_len = args.layout, AUX_SHAPES[args.layout]
+    kw = dict(tokens_ptr=tokens.data_ptr(), n_tokens=tokens.numel(), token_bits=32)
+    n_rows = aux_rows(tokens, off, seq_len, layout)
+    old_ids, new_ids = (torch.empty((n_rows, seq_len), dtype=torch.int32, device=dev) for _ in range(2))
+    old_len, new_len = (torch.empty(n_rows, dtype=torch.int32, device=dev) for _ in range(2))
+    old, new = [], []
+    torch.cuda.synchronize()
+    for i in range(1 + args.reps):
+        assert mbpe.pack_tokens(None, off, seq_len, layout, 32, PAD, out_ptr=old_ids.data_ptr(), len_ptr=old_len.data_ptr(),
+                                cap_rows=n_rows, **kw) == n_rows
+        a = mbpe.pack_kernel_ms()
+        assert mbpe.pack_tokens_aux(None, off, seq_len, layout, 32, PAD, out_ptr=new_ids.data_ptr(),
+                                    len_ptr=new_len.data_ptr(), cap_rows=n_rows, **kw) == n_rows
+        b = mbpe.pack_kernel_ms()
+        if i:
+            old.append(a); new.append(b)
+    assert bool(torch.equal(old_ids, new_ids)) and bool(torch.equal(old_len, new_len))
+    res.update({"rows": n_rows, "cells": n_rows * seq_len, "pack_tokens_kernel_ms": old, "aux_ids_only_kernel_ms": new,
+                "pack_tokens_kernel_ms_median": statistics.median(old),
+                "aux_ids_only_kernel_ms_median": statistics.median(new), "ids_and_lengths_equal": True})
+    print(json.dumps(res))
+
+
+STEPS = {"batch": step_batch, "wide": step_wide, "route": step_route, "aux_all": step_aux_all, "aux_ids": step_aux_ids}
 
 
 def child(step, limit, extra):
@@ -198,22 +351,27 @@ def main():
     ap.add_argument("--rep", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--json")
+    ap.add_argument("--aux", action="store_true", help="the k_pack_aux rows instead of the r09 steps")
+    ap.add_argument("--layout", choices=sorted(AUX_SHAPES), default="padded")
     args = ap.parse_args()
     if args.step:
         STEPS[args.step](args)
         return 0
     res = {}
     size = ["--rep", str(args.rep), "--reps", str(args.reps)]
-    plan = [("route", 200, size), ("wide", 200, size), ("batch", 500, size)]
-    for step, limit, extra in plan:
-        res[step] = child(step, limit, extra)
-        if res[step] is None:
+    plan = [("route", "route", 200, size), ("wide", "wide", 200, size), ("batch", "batch", 500, size)]
+    if args.aux:
+        plan = [("%s_%s" % (step, layout), step, 240, size + ["--layout", layout])
+                for layout in ("padded", "packed") for step in ("aux_all", "aux_ids")]
+    for name, step, limit, extra in plan:
+        res[name] = child(step, limit, extra)
+        if res[name] is None:
             break
-        print(json.dumps(res[step]), flush=True)
+        print(json.dumps(res[name]), flush=True)
         if args.json:
             with open(args.json, "w") as f:
                 json.dump(res, f, indent=1)
-    return 0 if all(res.get(k) is not None for k, *_ in plan) else 1
+    return 0 if all(res.get(name) is not None for name, *_ in plan) else 1
 
 
 if __name__ == "__main__":
