@@ -56,7 +56,8 @@ typedef enum {
     MBPE_ERR_STATE     = -5,  /* call order violated (e.g. steps before begin) */
     MBPE_ERR_OOM       = -6,  /* device or host allocation failed */
     MBPE_ERR_REGEX     = -7,  /* PCRE2 unavailable, compile or match error */
-    MBPE_ERR_SPLIT_GAP = -8,  /* (unused since gaps between matches are skipped like the reference does) */
+    MBPE_ERR_SPLIT_GAP = -8,  /* mbpe_splitter_split: PCRE2 left bytes of a host span in no match (invalid UTF-8); use
+                                 mbpe_presplit, which skips such bytes like the reference does */
     MBPE_ERR_COMM      = -9,  /* RCCL unavailable or a collective failed */
     MBPE_ERR_OVERFLOW  = -10, /* pair table or count overflow detected on device */
     MBPE_ERR_IO        = -11  /* file could not be read / written */
@@ -140,6 +141,16 @@ MBPE_API void mbpe_destroy(mbpe_ctx *ctx);
 MBPE_API int mbpe_load_corpus(mbpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes,
                               const uint64_t *chunk_off, uint64_t n_chunks,
                               int text_on_device);
+
+/* The same for a chunked corpus whose chunk ends are already a mask on the device, as mbpe_splitter_split leaves
+ * it: endmask_dev = 2 * ceil(n_bytes / 16) + 16 bytes of device memory, 4-byte aligned, bit i & 7 of byte i >> 3 set
+ * where text byte i is the last of its chunk, nothing set at or beyond n_bytes.  The mask is copied (device to
+ * device) and taken as it is: the chunk count is its population count, taken on the device; no chunk is visited on
+ * the host and a device text is not copied back.  The NUL rule of mbpe_load_corpus is the caller's: a chunk the
+ * reference collapses to one token must come with every one of its bits set.  (The gpt2 / gpt4 patterns never
+ * produce such a chunk: one that starts with NUL holds no ASCII digit, so std::stoi cannot parse its remainder.) */
+MBPE_API int mbpe_load_corpus_endmask(mbpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                      const uint8_t *endmask_dev);
 
 /* The same for chunks given as ranges [starts[c], ends[c]) (ascending, not overlapping) that need
  * not tile the text: bytes outside every chunk are not part of the corpus, as in the reference's
@@ -686,6 +697,65 @@ MBPE_API void            mbpe_split_free(mbpe_split *s);
 
 /* The split patterns of Tokenizer.h:59-60 ("gpt2", "gpt4"; "basic" = ""). */
 MBPE_API const char *mbpe_split_pattern(const char *encoder_name);
+
+/* ---- the gpt2 / gpt4 pre-split on the device ------------------------------ */
+
+/* A splitter: mbpe_presplit for the two built-in patterns as an object on HIP device `device_id` (csrc/split.hip,
+ * DESIGN.md 4g).  The device decides what ASCII bytes decide: a position where a letter or digit is followed by
+ * whitespace is a chunk boundary under either pattern, and a stretch between two such positions that holds only
+ * ASCII and is at most "max_span" bytes long is split by a rule on byte classes (csrc/split_rule.h).  Every other
+ * stretch -- a "host span" -- is matched by PCRE2 on the host exactly as mbpe_presplit would match it, and its chunk
+ * ends are added to the mask on the device.  The result is the split of mbpe_presplit, chunk for chunk.
+ *   pattern   byte-equal to mbpe_split_pattern("gpt2") or ("gpt4"); anything else is MBPE_ERR_ARG
+ * Arguments are checked before the device is touched.  No CPU fallback: MBPE_ERR_NO_DEVICE without a HIP device.
+ * A splitter has its own non-blocking stream and is thread-compatible like a context: one call at a time. */
+#define MBPE_SPLIT_BLOCK    64u    /* text bytes per thread of the walk; the sync pass takes 16 per lane */
+#define MBPE_SPLIT_TILE     16384u /* text bytes per workgroup of the walk (256 threads) */
+#define MBPE_SPLIT_MAX_SPAN 4096u  /* default of the option "max_span" */
+typedef struct mbpe_splitter mbpe_splitter;
+MBPE_API int  mbpe_splitter_create(int device_id, const char *pattern, mbpe_splitter **out);
+MBPE_API void mbpe_splitter_destroy(mbpe_splitter *s);
+
+/* Splits a text.
+ *   text             n_bytes bytes of valid UTF-8; host memory, or -- text_on_device != 0 -- device memory of the
+ *                    splitter's device, 16-byte aligned, read in place and never written.  (When a device text has
+ *                    host spans, its bytes from the first of them to the last come back to the host in one copy.)
+ *   endmask_dev_out  optional: 2 * ceil(n_bytes / 16) + 16 bytes of device memory, 16-byte aligned, which receive the
+ *                    end mask mbpe_load_corpus_endmask takes: bit i & 7 of byte i >> 3 = text byte i is the last of
+ *                    its chunk (the last byte of a non-empty text always is).  With NULL the mask stays in the
+ *                    splitter (mbpe_splitter_endmask) until its next call
+ *   chunk_off_out    optional, host, cap_chunks + 1 entries: the n_chunks + 1 offsets mbpe_presplit gives
+ *   n_chunks_out     required.  The chunk count whenever the split succeeded: cap_chunks smaller than it (with
+ *                    chunk_off_out given) returns MBPE_ERR_ARG and writes nothing else, so that a first call can
+ *                    size the array.  Any other error leaves 0 there
+ * MBPE_ERR_SPLIT_GAP, with neither mask nor offsets written: PCRE2 left bytes of a host span in no match, which only invalid UTF-8
+ * brings about; mbpe_presplit handles such a text the reference's way. */
+MBPE_API int  mbpe_splitter_split(mbpe_splitter *s, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                  uint8_t *endmask_dev_out, uint64_t *chunk_off_out, uint64_t cap_chunks,
+                                  uint64_t *n_chunks_out);
+
+/* The mask of the latest successful call in the splitter's own device memory (valid until its next call), its size,
+ * and -- optional -- where that call's text is on the device: the caller's device text, or the splitter's copy of a
+ * host text, so that a trainer can take it in place (mbpe_load_corpus_endmask with text_on_device) without a second
+ * upload.  MBPE_ERR_STATE before the first successful call. */
+MBPE_API int  mbpe_splitter_endmask(const mbpe_splitter *s, const uint8_t **endmask_dev_out, uint64_t *mask_bytes_out,
+                                    const uint8_t **text_dev_out);
+
+/*   "max_span"   the longest stretch between two sync points that the device walks (default MBPE_SPLIT_MAX_SPAN, at
+ *                least 1); longer ones go to the host.  Same results.
+ * The host spans are matched by up to MBPE_SPLIT_THREADS (environment; default 16) host threads, like mbpe_presplit. */
+MBPE_API int  mbpe_splitter_set_option(mbpe_splitter *s, const char *name, int64_t value);
+
+/* Device time of the latest call in milliseconds (HIP events on the splitter's stream around its kernels; copies
+ * between host and device and the host's PCRE2 work are outside). */
+MBPE_API int  mbpe_splitter_kernel_ms(const mbpe_splitter *s, float *ms_out);
+
+/* Device allocations (hipMalloc calls) since the splitter was created.  A repeat call of no larger size leaves the
+ * number as it is. */
+MBPE_API int  mbpe_splitter_alloc_count(const mbpe_splitter *s, uint64_t *n_out);
+
+/* The host spans of the latest call: how many, and (optional) the text bytes they hold. */
+MBPE_API int  mbpe_splitter_host_spans(const mbpe_splitter *s, uint64_t *n_spans_out, uint64_t *n_bytes_out);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,12 @@ MBPE_API int mbpe_tok_set_special_tokens(mbpe_tokenizer *t, const char *text, ui
 MBPE_API int mbpe_tok_train(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, uint32_t vocab_size,
                             int conflict_resolution, int verbose, int device_id);
 
+/* The same with the gpt2 / gpt4 pre-split on the device as well (mbpe_splitter_split, then
+ * mbpe_load_corpus_endmask on the text the splitter uploaded): same merges.  A tokenizer whose pattern is not one of
+ * the two built-in ones returns MBPE_ERR_ARG; it does not fall back to the host split. */
+MBPE_API int mbpe_tok_train_split_device(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, uint32_t vocab_size,
+                                         int conflict_resolution, int verbose, int device_id);
+
 /* Direct access to the trained / loaded merges (2 u32 per merge). */
 MBPE_API int mbpe_tok_set_merges(mbpe_tokenizer *t, const uint32_t *merges, uint32_t n_merges);
 MBPE_API int mbpe_tok_get_merges(mbpe_tokenizer *t, uint32_t *merges_out, uint32_t cap, uint32_t *n_out);

@@ -1,0 +1,409 @@
+// The gpt2 / gpt4 pre-split on the device: the chunk-end mask of a text, in the trainer's format,
+// without a regex engine or a Unicode table on the device.  split_rule.h holds the rule and the exactness argument;
+// here are the passes around it:
+//   k_split_sync     16 text bytes per lane -> the sync-point bitmap and the non-ASCII bitmap, one bit per byte
+//   k_split_walk     one thread per 64-byte block: every span that starts in it is walked with the step rule (its chunk
+//                    ends are OR-ed into the zeroed mask) or, when it is too long or holds a non-ASCII byte, marked
+//   k_split_compact  the marked spans as a list of (a, b), whose capacity is the walk's own count of its marks
+//   (host)           the listed spans through PCRE2 (presplit.cpp), their chunk ends uploaded
+//   k_split_patch    those chunk ends OR-ed into the mask
+//   k_mask_popcount  the number of chunks
+// All positions are 64-bit.
+#include "hip_host.h"
+#include "split.h"
+#include "split_rule.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace mbpe {
+namespace {
+
+constexpr int kSplitThreads = 256;
+static_assert(kSplitBlock == MBPE_SPLIT_BLOCK, "mbpe.h publishes the walk's block size");
+static_assert(kSplitBlock * kSplitThreads == MBPE_SPLIT_TILE, "... and the bytes of one of its workgroups");
+
+// control words of one call
+enum { kCtlHost = 0, kCtlCursor = 1, kCtlChunks = 2, kCtlWords = 4 };
+
+// bitmaps as 16-bit pieces, one per vector: n_pieces = 4 * n_words of them, those at and beyond the text are 0
+__global__ __launch_bounds__(kSplitThreads) void k_split_sync(const uint8_t *__restrict__ t, uint64_t n,
+                                                              uint64_t n_pieces, uint16_t *__restrict__ sync,
+                                                              uint16_t *__restrict__ hi) {
+    const uint64_t v = (uint64_t)blockIdx.x * kSplitThreads + threadIdx.x;
+    if (v >= n_pieces) return;
+    const uint64_t at = v * kSplitVec;
+    uint32_t w[4] = {0u, 0u, 0u, 0u}, s = 0u, h = 0u;
+    if (at < n) {
+        if (n - at >= (uint64_t)kSplitVec) {
+            const uint4 q = *reinterpret_cast<const uint4 *>(t + at);      // (the text is 16-byte aligned)
+            w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+        } else {
+            for (uint32_t k = 0; k < (uint32_t)(n - at); ++k) w[k >> 2] |= (uint32_t)t[at + k] << (8u * (k & 3u));
+        }
+        split_vec_bits(w, at ? t[at - 1] : (uint32_t)' ', &s, &h);
+    }
+    sync[v] = (uint16_t)s;
+    hi[v] = (uint16_t)h;
+}
+
+// the chunk ends of one thread, gathered per 32-bit word of the mask: a span may reach into the blocks of other
+// threads, so every word goes out with one atomic OR
+struct EndBits {
+    uint32_t *mask;
+    uint64_t word;
+    uint32_t bits;
+    __device__ void operator()(uint64_t p) {
+        const uint64_t w = p >> 5;
+        if (w != word) { flush(); word = w; }
+        bits |= 1u << (p & 31u);
+    }
+    __device__ void flush() {
+        if (bits) atomicOr(mask + word, bits);
+        bits = 0u;
+    }
+};
+
+__global__ __launch_bounds__(kSplitThreads) void k_split_walk(const uint8_t *__restrict__ t, uint64_t n,
+                                                              const unsigned long long *__restrict__ sync,
+                                                              const unsigned long long *__restrict__ hi, uint64_t n_words,
+                                                              uint64_t max_span, int pattern, uint32_t *__restrict__ mask,
+                                                              unsigned long long *__restrict__ hostmark,
+                                                              unsigned long long *__restrict__ ctl) {
+    const uint64_t T = (uint64_t)blockIdx.x * kSplitThreads + threadIdx.x;
+    if (T >= n_words) return;
+    EndBits end = {mask, ~0ull, 0u};
+    const unsigned long long host = split_walk_block(t, n, sync, hi, T, max_span, pattern, end);
+    end.flush();
+    hostmark[T] = host;
+    if (host) atomicAdd(ctl + kCtlHost, (unsigned long long)__popcll(host));
+}
+
+// list[2 j], list[2 j + 1] = a host span and its end, in no particular order; cap = the spans the walk counted
+__global__ __launch_bounds__(kSplitThreads) void k_split_compact(const unsigned long long *__restrict__ sync,
+                                                                 const unsigned long long *__restrict__ hostmark,
+                                                                 uint64_t n, uint64_t n_words,
+                                                                 unsigned long long *__restrict__ list, uint64_t cap,
+                                                                 unsigned long long *__restrict__ ctl) {
+    const uint64_t T = (uint64_t)blockIdx.x * kSplitThreads + threadIdx.x;
+    if (T >= n_words) return;
+    unsigned long long hm = hostmark[T];
+    while (hm) {
+        const uint64_t a = (T << 6) + (uint64_t)__builtin_ctzll(hm);
+        hm &= hm - 1;
+        const uint64_t b = split_next_bit(sync, a + 1, n);
+        const unsigned long long j = atomicAdd(ctl + kCtlCursor, 1ull);
+        if (j < cap) { list[2 * j] = a; list[2 * j + 1] = b; }
+    }
+}
+
+__global__ __launch_bounds__(kSplitThreads) void k_split_patch(const unsigned long long *__restrict__ pos, uint64_t n_pos,
+                                                               uint64_t n, uint32_t *__restrict__ mask) {
+    const uint64_t j = (uint64_t)blockIdx.x * kSplitThreads + threadIdx.x;
+    if (j >= n_pos) return;
+    const uint64_t p = pos[j];
+    if (p < n) atomicOr(mask + (p >> 5), 1u << (p & 31u));
+}
+
+// the set bits of the first n_words32 words of a mask, added to *out
+__global__ __launch_bounds__(kSplitThreads) void k_mask_popcount(const uint32_t *__restrict__ mask, uint64_t n_words32,
+                                                                 unsigned long long *__restrict__ out) {
+    unsigned long long s = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kSplitThreads + threadIdx.x; i < n_words32;
+         i += (uint64_t)gridDim.x * kSplitThreads)
+        s += (unsigned long long)__popc(mask[i]);
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
+    if ((threadIdx.x & 63) == 0 && s) atomicAdd(out, s);
+}
+
+uint32_t grid_for(uint64_t n_items) { return (uint32_t)((n_items + kSplitThreads - 1) / kSplitThreads); }
+
+int fail(int code, const std::string &msg) {
+    mbpe_host::set_last_error(msg);
+    return code;
+}
+
+#define SCHK(expr) MBPE_HIP_CHECK(expr, false)
+
+}  // namespace
+
+void launch_mask_popcount(hipStream_t stream, const uint8_t *mask, uint64_t n_bytes, unsigned long long *count_out) {
+    const uint64_t n_words32 = (n_bytes + 31) / 32;
+    if (!n_words32) return;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(grid_for(n_words32), 2048);
+    hipLaunchKernelGGL(k_mask_popcount, dim3(grid), dim3(kSplitThreads), 0, stream,
+                       reinterpret_cast<const uint32_t *>(mask), n_words32, count_out);
+}
+
+}  // namespace mbpe
+
+using namespace mbpe;
+
+struct mbpe_splitter {
+    int device = 0;
+    int pattern = kSplitGpt2;
+    mbpe_host::Splitter host;                 // the same pattern through PCRE2, for the host spans
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    uint64_t max_span = MBPE_SPLIT_MAX_SPAN;
+    // buffers, grown on demand and kept
+    uint8_t *d_text = nullptr;                // a host text's copy
+    unsigned long long *d_sync = nullptr, *d_hi = nullptr, *d_hostmark = nullptr;
+    uint8_t *d_mask = nullptr;
+    unsigned long long *d_ctl = nullptr;
+    unsigned long long *d_list = nullptr;     // host spans, then their chunk ends
+    uint64_t cap_text = 0, cap_sync = 0, cap_hi = 0, cap_hostmark = 0, cap_mask = 0, cap_list = 0;
+    uint64_t n_allocs = 0;
+    std::vector<uint8_t> h_mask;              // the mask on the host, when offsets are asked for
+    // the latest call
+    float last_ms = 0.f;
+    uint64_t last_n = 0, last_chunks = 0, last_host_spans = 0, last_host_bytes = 0;
+    const uint8_t *last_text = nullptr;       // the text on the device
+    bool have_mask = false;
+};
+
+namespace {
+
+// adds the device time between the two events (both recorded, the stream idle) to the call's total
+int add_ms(mbpe_splitter *s) {
+    float ms = 0.f;
+    SCHK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    s->last_ms += ms;
+    return MBPE_OK;
+}
+
+// the passes; writes nothing the caller sees
+int split_run_passes(mbpe_splitter *s, const uint8_t *text, uint64_t n, int text_on_device, uint64_t *n_chunks) {
+    const uint64_t n_words = (n + kSplitBlock - 1) / kSplitBlock, n_vec = (n + kSplitVec - 1) / kSplitVec;
+    const uint64_t mask_bytes = (n_vec * 2 + 16 + 7) & ~7ull;
+    int rc;
+    if (!text_on_device) {
+        if ((rc = grow(&s->d_text, &s->cap_text, n_vec * 16, false, &s->n_allocs)) != MBPE_OK) return rc;
+        SCHK(hipMemcpyAsync(s->d_text, text, n, hipMemcpyHostToDevice, s->stream));
+    }
+    const uint8_t *d_text = text_on_device ? text : s->d_text;
+    if ((rc = grow(&s->d_sync, &s->cap_sync, n_words * 8, false, &s->n_allocs)) != MBPE_OK) return rc;
+    if ((rc = grow(&s->d_hi, &s->cap_hi, n_words * 8, false, &s->n_allocs)) != MBPE_OK) return rc;
+    if ((rc = grow(&s->d_hostmark, &s->cap_hostmark, n_words * 8, false, &s->n_allocs)) != MBPE_OK) return rc;
+    if ((rc = grow(&s->d_mask, &s->cap_mask, mask_bytes, false, &s->n_allocs)) != MBPE_OK) return rc;
+    s->have_mask = false;
+    s->last_text = d_text;
+
+    SCHK(hipEventRecord(s->ev0, s->stream));
+    SCHK(hipMemsetAsync(s->d_mask, 0, mask_bytes, s->stream));
+    SCHK(hipMemsetAsync(s->d_ctl, 0, kCtlWords * 8, s->stream));
+    hipLaunchKernelGGL(k_split_sync, dim3(grid_for(n_words * 4)), dim3(kSplitThreads), 0, s->stream, d_text, n,
+                       n_words * 4, reinterpret_cast<uint16_t *>(s->d_sync), reinterpret_cast<uint16_t *>(s->d_hi));
+    hipLaunchKernelGGL(k_split_walk, dim3(grid_for(n_words)), dim3(kSplitThreads), 0, s->stream, d_text, n, s->d_sync,
+                       s->d_hi, n_words, s->max_span, s->pattern, reinterpret_cast<uint32_t *>(s->d_mask), s->d_hostmark,
+                       s->d_ctl);
+    SCHK(hipGetLastError());
+    SCHK(hipEventRecord(s->ev1, s->stream));
+    unsigned long long ctl[kCtlWords] = {0, 0, 0, 0};
+    SCHK(hipMemcpyAsync(ctl, s->d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, s->stream));
+    SCHK(hipStreamSynchronize(s->stream));
+    if ((rc = add_ms(s)) != MBPE_OK) return rc;
+
+    const uint64_t n_host = ctl[kCtlHost];
+    uint64_t n_patch = 0;
+    if (n_host) {
+        if ((rc = grow(&s->d_list, &s->cap_list, n_host * 16, false, &s->n_allocs)) != MBPE_OK) return rc;
+        SCHK(hipEventRecord(s->ev0, s->stream));
+        hipLaunchKernelGGL(k_split_compact, dim3(grid_for(n_words)), dim3(kSplitThreads), 0, s->stream, s->d_sync,
+                           s->d_hostmark, n, n_words, s->d_list, n_host, s->d_ctl);
+        SCHK(hipGetLastError());
+        SCHK(hipEventRecord(s->ev1, s->stream));
+        std::vector<uint64_t> spans(2 * n_host);
+        SCHK(hipMemcpyAsync(spans.data(), s->d_list, n_host * 16, hipMemcpyDeviceToHost, s->stream));
+        SCHK(hipStreamSynchronize(s->stream));
+        if ((rc = add_ms(s)) != MBPE_OK) return rc;
+
+        // ascending, and neighbours joined into runs: [a, b) [b, c) is the run [a, c)
+        struct Span { uint64_t a, b; };
+        Span *sp = reinterpret_cast<Span *>(spans.data());
+        std::sort(sp, sp + n_host, [](const Span &x, const Span &y) { return x.a < y.a; });
+        uint64_t n_runs = 0, host_bytes = 0;
+        for (uint64_t i = 0; i < n_host; ++i) {
+            if (sp[i].a >= sp[i].b || sp[i].b > n || (n_runs && sp[i].a < sp[n_runs - 1].b))
+                return fail(MBPE_ERR_HIP, "mbpe_splitter_split: the device listed an impossible host span");
+            host_bytes += sp[i].b - sp[i].a;
+            if (n_runs && sp[n_runs - 1].b == sp[i].a) sp[n_runs - 1].b = sp[i].b;
+            else sp[n_runs++] = sp[i];
+        }
+        s->last_host_spans = n_host;
+        s->last_host_bytes = host_bytes;
+
+        // the bytes PCRE2 reads: [a, min(b + 1, n)) of every run.  A device text comes back once, from the first
+        // run to the last
+        std::vector<uint8_t> back;
+        const uint8_t *sub = text;
+        uint64_t origin = 0;
+        if (text_on_device) {
+            origin = sp[0].a;
+            const uint64_t to = std::min(sp[n_runs - 1].b + 1, n);
+            back.resize(to - origin);
+            SCHK(hipMemcpy(back.data(), text + origin, to - origin, hipMemcpyDeviceToHost));
+            sub = back.data();
+        }
+        std::vector<uint64_t> ends;
+        std::string err;
+        rc = s->host.split_spans(sub, origin, n, spans.data(), n_runs, mbpe_host::split_thread_count(host_bytes), &ends, &err);
+        if (rc != MBPE_OK) return fail(rc, err);
+        n_patch = ends.size();
+        if ((rc = grow(&s->d_list, &s->cap_list, n_patch * 8, false, &s->n_allocs)) != MBPE_OK) return rc;
+        SCHK(hipMemcpyAsync(s->d_list, ends.data(), n_patch * 8, hipMemcpyHostToDevice, s->stream));
+        SCHK(hipStreamSynchronize(s->stream));           // (ends is about to go)
+    }
+
+    SCHK(hipEventRecord(s->ev0, s->stream));
+    if (n_patch)
+        hipLaunchKernelGGL(k_split_patch, dim3(grid_for(n_patch)), dim3(kSplitThreads), 0, s->stream, s->d_list, n_patch,
+                           n, reinterpret_cast<uint32_t *>(s->d_mask));
+    launch_mask_popcount(s->stream, s->d_mask, n, s->d_ctl + kCtlChunks);
+    SCHK(hipGetLastError());
+    SCHK(hipEventRecord(s->ev1, s->stream));
+    SCHK(hipMemcpyAsync(ctl, s->d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, s->stream));
+    SCHK(hipStreamSynchronize(s->stream));
+    if ((rc = add_ms(s)) != MBPE_OK) return rc;
+    *n_chunks = ctl[kCtlChunks];
+    s->have_mask = true;
+    return MBPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mbpe_splitter_create(int device_id, const char *pattern, mbpe_splitter **out) {
+    if (!pattern || !out) return fail(MBPE_ERR_ARG, "mbpe_splitter_create: NULL argument");
+    int which = -1;
+    if (!strcmp(pattern, mbpe_host::split_pattern_for("gpt2"))) which = kSplitGpt2;
+    else if (!strcmp(pattern, mbpe_host::split_pattern_for("gpt4"))) which = kSplitGpt4;
+    if (which < 0)
+        return fail(MBPE_ERR_ARG, "the device split knows the built-in gpt2 and gpt4 patterns only (use mbpe_presplit)");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || device_id < 0 || device_id >= n_dev)
+        return fail(MBPE_ERR_NO_DEVICE, "no usable HIP device (the MI355X path has no CPU fallback)");
+    mbpe_splitter *s = new mbpe_splitter;
+    s->device = device_id;
+    s->pattern = which;
+    auto build = [&]() -> int {
+        std::string err;
+        const int rc = s->host.compile(pattern, &err);
+        if (rc != MBPE_OK) return fail(rc, err);
+        SCHK(hipSetDevice(device_id));
+        SCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+        SCHK(hipEventCreate(&s->ev0));
+        SCHK(hipEventCreate(&s->ev1));
+        SCHK(hipMalloc(&s->d_ctl, kCtlWords * 8));
+        s->n_allocs = 1;
+        return MBPE_OK;
+    };
+    const int rc = build();
+    if (rc != MBPE_OK) {
+        const std::string keep = mbpe_host::last_error();
+        mbpe_splitter_destroy(s);
+        mbpe_host::set_last_error(keep);
+        return rc;
+    }
+    *out = s;
+    return MBPE_OK;
+}
+
+void mbpe_splitter_destroy(mbpe_splitter *s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    (void)hipFree(s->d_text); (void)hipFree(s->d_sync); (void)hipFree(s->d_hi); (void)hipFree(s->d_hostmark);
+    (void)hipFree(s->d_mask); (void)hipFree(s->d_ctl); (void)hipFree(s->d_list);
+    if (s->ev0) (void)hipEventDestroy(s->ev0);
+    if (s->ev1) (void)hipEventDestroy(s->ev1);
+    if (s->stream) (void)hipStreamDestroy(s->stream);
+    delete s;
+}
+
+int mbpe_splitter_set_option(mbpe_splitter *s, const char *name, int64_t value) {
+    if (!s || !name) return fail(MBPE_ERR_ARG, "mbpe_splitter_set_option: NULL argument");
+    if (!strcmp(name, "max_span") && value >= 1) { s->max_span = (uint64_t)value; return MBPE_OK; }
+    return fail(MBPE_ERR_ARG, std::string("mbpe_splitter_set_option: unknown option or bad value: ") + name);
+}
+
+int mbpe_splitter_split(mbpe_splitter *s, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                        uint8_t *endmask_dev_out, uint64_t *chunk_off_out, uint64_t cap_chunks, uint64_t *n_chunks_out) {
+    if (n_chunks_out) *n_chunks_out = 0;
+    if (!s || !n_chunks_out || (!text && n_bytes)) return fail(MBPE_ERR_ARG, "mbpe_splitter_split: NULL argument");
+    if ((text_on_device && ((uintptr_t)text & 15)) || ((uintptr_t)endmask_dev_out & 15))
+        return fail(MBPE_ERR_ARG, "mbpe_splitter_split: device text and device mask must be 16-byte aligned");
+    SCHK(hipSetDevice(s->device));
+    s->last_ms = 0.f;
+    s->last_n = n_bytes;
+    s->last_chunks = s->last_host_spans = s->last_host_bytes = 0;
+    s->last_text = nullptr;
+    s->have_mask = false;
+    const uint64_t mask_bytes = (n_bytes + 15) / 16 * 2 + 16;
+    uint64_t n_chunks = 0;
+    if (n_bytes) {
+        const int rc = split_run_passes(s, text, n_bytes, text_on_device, &n_chunks);
+        if (rc != MBPE_OK) return rc;
+    } else {
+        const int rc = grow(&s->d_mask, &s->cap_mask, 16, false, &s->n_allocs);
+        if (rc != MBPE_OK) return rc;
+        SCHK(hipMemsetAsync(s->d_mask, 0, 16, s->stream));
+        SCHK(hipStreamSynchronize(s->stream));
+        s->have_mask = true;
+    }
+    s->last_chunks = n_chunks;
+    *n_chunks_out = n_chunks;
+    if (chunk_off_out) {
+        if (cap_chunks < n_chunks) return fail(MBPE_ERR_ARG, "mbpe_splitter_split: chunk_off_out is too small");
+        // 1 bit per text byte comes back instead of 8 bytes per chunk; the offsets are read off the mask here
+        s->h_mask.resize((n_bytes + 63) / 64 * 8);
+        if (n_bytes) SCHK(hipMemcpy(s->h_mask.data(), s->d_mask, s->h_mask.size(), hipMemcpyDeviceToHost));
+        uint64_t k = 0;
+        chunk_off_out[k++] = 0;
+        for (uint64_t w = 0; w < s->h_mask.size() / 8 && k <= n_chunks; ++w) {
+            unsigned long long m;
+            memcpy(&m, s->h_mask.data() + 8 * w, 8);
+            for (; m && k <= n_chunks; m &= m - 1) chunk_off_out[k++] = (w << 6) + (uint64_t)__builtin_ctzll(m) + 1;
+        }
+        if (k != n_chunks + 1) return fail(MBPE_ERR_HIP, "mbpe_splitter_split: the mask and its count disagree");
+    }
+    if (endmask_dev_out) {
+        SCHK(hipMemcpyAsync(endmask_dev_out, s->d_mask, mask_bytes, hipMemcpyDeviceToDevice, s->stream));
+        SCHK(hipStreamSynchronize(s->stream));
+    }
+    return MBPE_OK;
+}
+
+int mbpe_splitter_endmask(const mbpe_splitter *s, const uint8_t **endmask_dev_out, uint64_t *mask_bytes_out,
+                          const uint8_t **text_dev_out) {
+    if (!s || !endmask_dev_out) return fail(MBPE_ERR_ARG, "mbpe_splitter_endmask: NULL argument");
+    if (!s->have_mask) return fail(MBPE_ERR_STATE, "mbpe_splitter_endmask: no split has succeeded yet");
+    *endmask_dev_out = s->d_mask;
+    if (mask_bytes_out) *mask_bytes_out = (s->last_n + 15) / 16 * 2 + 16;
+    if (text_dev_out) *text_dev_out = s->last_text;
+    return MBPE_OK;
+}
+
+int mbpe_splitter_kernel_ms(const mbpe_splitter *s, float *ms_out) {
+    if (!s || !ms_out) return fail(MBPE_ERR_ARG, "mbpe_splitter_kernel_ms: NULL argument");
+    *ms_out = s->last_ms;
+    return MBPE_OK;
+}
+
+int mbpe_splitter_alloc_count(const mbpe_splitter *s, uint64_t *n_out) {
+    if (!s || !n_out) return fail(MBPE_ERR_ARG, "mbpe_splitter_alloc_count: NULL argument");
+    *n_out = s->n_allocs;
+    return MBPE_OK;
+}
+
+int mbpe_splitter_host_spans(const mbpe_splitter *s, uint64_t *n_spans_out, uint64_t *n_bytes_out) {
+    if (!s || !n_spans_out) return fail(MBPE_ERR_ARG, "mbpe_splitter_host_spans: NULL argument");
+    *n_spans_out = s->last_host_spans;
+    if (n_bytes_out) *n_bytes_out = s->last_host_bytes;
+    return MBPE_OK;
+}
+
+}  // extern "C"

@@ -12,6 +12,7 @@
 #include "mbpe.h"
 #include "mbpe_dev.h"
 #include "wide.h"
+#include "split.h"
 #include "hip_host.h"
 
 #include <dlfcn.h>
@@ -620,21 +621,53 @@ int mbpe_set_option(mbpe_ctx *c, const char *name, int64_t value) {
     return MBPE_OK;
 }
 
-int mbpe_load_corpus(mbpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off,
-                     uint64_t n_chunks, int text_on_device) {
-    if (!c || (!text && n_bytes)) { mbpe_host::set_last_error("mbpe_load_corpus: NULL argument"); return MBPE_ERR_ARG; }
+// The two ends of a corpus load, shared by mbpe_load_corpus and mbpe_load_corpus_endmask.  load_reset: the old
+// corpus goes, the new one's size and kind are noted.
+static int load_reset(mbpe_ctx *c, uint64_t n_bytes, bool chunked, uint64_t n_chunks) {
     HIPCHK(hipSetDevice(c->device));
     free_training(c);
     free_corpus(c);
     // (the training buffers of a corpus of another size would not be handed out again: give them back before the
     //  new corpus is allocated, not only inside the next mbpe_train_begin)
-    if (n_bytes != c->n_bytes || (chunk_off != nullptr) != c->chunked) pool_trim(c);
+    if (n_bytes != c->n_bytes || chunked != c->chunked) pool_trim(c);
     c->n_bytes = n_bytes;
-    c->chunked = chunk_off != nullptr;
-    c->n_chunks = chunk_off ? n_chunks : 1;
+    c->chunked = chunked;
+    c->n_chunks = chunked ? n_chunks : 1;
     c->n_barriers = 0;
     c->barrier = false;
     c->inert = false;
+    return MBPE_OK;
+}
+
+// load_finish: the text is taken in place or uploaded, the end mask of a chunked corpus (mask_bytes of it, on the
+// side `mask_kind` says) copied into the context's own buffer; c->n_chunks is final by now.
+static int load_finish(mbpe_ctx *c, const uint8_t *text, uint64_t n_bytes, int text_on_device, const uint8_t *mask,
+                       size_t mask_bytes, hipMemcpyKind mask_kind) {
+    const uint64_t n_vec = (n_bytes + 15) / 16;
+    if (text_on_device) {
+        c->d_text = text;
+    } else {
+        HIPCHK(hipMalloc(&c->d_text_owned, std::max<uint64_t>(n_vec * 16, 16)));
+        if (n_bytes) HIPCHK(hipMemcpyAsync(c->d_text_owned, text, n_bytes, hipMemcpyHostToDevice, c->stream));
+        c->d_text = c->d_text_owned;
+    }
+    if (mask) {
+        HIPCHK(hipMalloc(&c->d_endmask, mask_bytes));
+        HIPCHK(hipMemcpyAsync(c->d_endmask, mask, mask_bytes, mask_kind, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->loaded = true;
+    c->stats = {};
+    c->stats.n_bytes = n_bytes;
+    c->stats.n_chunks = c->n_chunks;
+    return MBPE_OK;
+}
+
+int mbpe_load_corpus(mbpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off,
+                     uint64_t n_chunks, int text_on_device) {
+    if (!c || (!text && n_bytes)) { mbpe_host::set_last_error("mbpe_load_corpus: NULL argument"); return MBPE_ERR_ARG; }
+    const int rc0 = load_reset(c, n_bytes, chunk_off != nullptr, n_chunks);
+    if (rc0 != MBPE_OK) return rc0;
     if (chunk_off) {
         if (chunk_off[0] != 0 || chunk_off[n_chunks] != n_bytes) {
             mbpe_host::set_last_error("chunk_off must start at 0 and end at n_bytes");
@@ -699,24 +732,40 @@ int mbpe_load_corpus(mbpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const u
         c->inert = parses;
         if (parses) c->n_chunks = 0;
     }
+    return load_finish(c, text, n_bytes, text_on_device, chunk_off ? mask.data() : nullptr, mask.size(),
+                       hipMemcpyHostToDevice);
+}
 
-    if (text_on_device) {
-        c->d_text = text;
-    } else {
-        HIPCHK(hipMalloc(&c->d_text_owned, std::max<uint64_t>(n_vec * 16, 16)));
-        if (n_bytes) HIPCHK(hipMemcpyAsync(c->d_text_owned, text, n_bytes, hipMemcpyHostToDevice, c->stream));
-        c->d_text = c->d_text_owned;
+int mbpe_load_corpus_endmask(mbpe_ctx *c, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                             const uint8_t *endmask_dev) {
+    if (!c || (!text && n_bytes) || !endmask_dev) {
+        mbpe_host::set_last_error("mbpe_load_corpus_endmask: NULL argument");
+        return MBPE_ERR_ARG;
     }
-    if (chunk_off) {
-        HIPCHK(hipMalloc(&c->d_endmask, mask.size()));
-        HIPCHK(hipMemcpyAsync(c->d_endmask, mask.data(), mask.size(), hipMemcpyHostToDevice, c->stream));
+    if ((text_on_device && ((uintptr_t)text & 15)) || ((uintptr_t)endmask_dev & 3)) {
+        mbpe_host::set_last_error("device text must be 16-byte aligned, the end mask 4-byte aligned");
+        return MBPE_ERR_ARG;
     }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->loaded = true;
-    c->stats = {};
-    c->stats.n_bytes = n_bytes;
-    c->stats.n_chunks = c->n_chunks;
-    return MBPE_OK;
+    const int rc0 = load_reset(c, n_bytes, true, 0);
+    if (rc0 != MBPE_OK) return rc0;
+    // every set bit is a chunk end: the chunks, and the barrier slots of the barrier layout.  (A mask that carries
+    // the NUL rule marks every byte of a collapsed chunk: like mbpe_load_corpus this counts those bytes as barriers;
+    // the masks of mbpe_splitter_split hold no such chunk, see mbpe.h.)
+    unsigned long long *d_count = nullptr, ends = 0;
+    HIPCHK(hipMalloc(&d_count, 8));
+    hipError_t e = hipMemsetAsync(d_count, 0, 8, c->stream);
+    if (e == hipSuccess) {
+        mbpe::launch_mask_popcount(c->stream, endmask_dev, n_bytes, d_count);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&ends, d_count, 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d_count);
+    HIPCHK(e);
+    c->n_chunks = ends;
+    c->n_barriers = ends;
+    return load_finish(c, text, n_bytes, text_on_device, endmask_dev, (n_bytes + 15) / 16 * 2 + 16,
+                       hipMemcpyDeviceToDevice);
 }
 
 int mbpe_load_corpus_ranges(mbpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *starts,

@@ -1,6 +1,6 @@
 // minbpe-cc: the reference's command line (code/examples/minbpe-cc.cpp:92-265)
 // on top of the MI355X training path.  Same flags, defaults, messages and exit
-// codes; `--train -c lexical` runs on the GPU.  The only addition is --device.
+// codes; `--train -c lexical` runs on the GPU.  The only additions are --device and the --device-* switches.
 #include "mbpe.h"
 #include "mbpe_tokenizer.h"
 
@@ -66,7 +66,8 @@ void usage() {
                  "                              Conflict resolution strategy: 'first' or 'lexical'\n"
                  "  --device INT                HIP device used for training (default 0)\n"
                  "  --device-encode             When encoding, apply the merges on the HIP device (--device)\n"
-                 "  --device-decode             When decoding, expand the tokens on the HIP device (--device)\n";
+                 "  --device-decode             When decoding, expand the tokens on the HIP device (--device)\n"
+                 "  --device-split              When training with gpt2 or gpt4, split the text on the HIP device (--device)\n";
 }
 
 }  // namespace
@@ -75,7 +76,7 @@ int main(int argc, char *argv[]) {
     std::string input_path, output_path, special_token_path, encoder = "gpt4", model_path = "./output.model";
     std::string conflict_resolution_str = "first";
     bool train = false, decode = false, encode = false, write_vocab = false, verbose = false, device_encode = false,
-         device_decode = false;
+         device_decode = false, device_split = false;
     int vocab_size = 512, device = 0;
 
     // option parsing (the reference uses CLI11, :93-133)
@@ -115,6 +116,7 @@ int main(int argc, char *argv[]) {
         else if (arg == "-w" || arg == "--write-vocab") write_vocab = true;
         else if (arg == "--device-encode") device_encode = true;
         else if (arg == "--device-decode") device_decode = true;
+        else if (arg == "--device-split") device_split = true;
         else if (arg == "-v" || arg == "--verbose") verbose = true;
         else { std::cerr << "The following argument was not expected: " << arg << "\n"; return 109; }
     }
@@ -158,8 +160,9 @@ int main(int argc, char *argv[]) {
         std::string input, err;
         if (load_file_to_string(input_path, &input, &err)) {
             if (verbose) std::cout << "Starting training...\n";
-            if (mbpe_tok_train(rt, reinterpret_cast<const uint8_t *>(input.data()), input.size(), (uint32_t)vocab_size,
-                               conflict_resolution_str == "lexical" ? 1 : 0, verbose, device) != MBPE_OK) {
+            if ((device_split ? mbpe_tok_train_split_device : mbpe_tok_train)(
+                    rt, reinterpret_cast<const uint8_t *>(input.data()), input.size(), (uint32_t)vocab_size,
+                    conflict_resolution_str == "lexical" ? 1 : 0, verbose, device) != MBPE_OK) {
                 std::cerr << "Error: " << mbpe_last_error() << "\n";
                 rc = -1;
             } else {

@@ -45,6 +45,10 @@ void device_free(void *p);
 // Tokenizer.h:59-60; nullptr for an unknown encoder name
 const char *split_pattern_for(const std::string &encoder);
 
+// host threads for PCRE2 work on n_bytes of text: MBPE_SPLIT_THREADS (environment; default 16), capped by the
+// hardware's threads and by one thread per MiB; at least 1
+unsigned split_thread_count(uint64_t n_bytes);
+
 // Compiled split pattern + match loop (Tokenizer.h:391-451, :506-540).
 class Splitter {
 public:
@@ -58,6 +62,12 @@ public:
     // chunk c = [starts[c], ends[c]); empty pattern -> one chunk = whole text
     int split(const uint8_t *text, uint64_t n, std::vector<uint64_t> *starts,
               std::vector<uint64_t> *ends, std::string *err) const;
+    // The match loop over n_spans stretches [spans[2 k], spans[2 k + 1]) (ascending, disjoint) of a text of n bytes,
+    // each matched from its start on its own subject [a, min(b + 1, n)) by up to n_threads threads; `sub` holds the
+    // text from byte `origin` on.  last_bytes receives, ascending, the last byte of every match.  MBPE_ERR_SPLIT_GAP
+    // when the matches of a stretch do not tile it.  (csrc/split.hip: the host spans of the device split)
+    int split_spans(const uint8_t *sub, uint64_t origin, uint64_t n, const uint64_t *spans, uint64_t n_spans,
+                    unsigned n_threads, std::vector<uint64_t> *last_bytes, std::string *err) const;
     bool has_pattern() const { return code_ != nullptr; }
     const std::string &pattern() const { return pattern_; }
 

@@ -80,6 +80,13 @@ std::string pcre2_message(int code) {
 
 namespace mbpe_host {
 
+unsigned split_thread_count(uint64_t n_bytes) {
+    unsigned hw = std::thread::hardware_concurrency();
+    const char *env = getenv("MBPE_SPLIT_THREADS");
+    unsigned want = env ? (unsigned)atoi(env) : 16u;
+    return std::max(1u, std::min({want, hw ? hw : 1u, (unsigned)std::min<uint64_t>(n_bytes >> 20, 1u << 20)}));
+}
+
 Splitter::~Splitter() { reset(); }
 
 void Splitter::reset() {
@@ -164,12 +171,7 @@ int Splitter::split(const uint8_t *text, uint64_t n, std::vector<uint64_t> *star
     uint32_t lookbehind = 1;
     if (p.pattern_info(code_, kPCRE2_INFO_MAXLOOKBEHIND, &lookbehind) != 0) lookbehind = 1;
     unsigned n_threads = 1;
-    if (lookbehind == 0 && n >= (8u << 20)) {
-        unsigned hw = std::thread::hardware_concurrency();
-        const char *env = getenv("MBPE_SPLIT_THREADS");
-        unsigned want = env ? (unsigned)atoi(env) : 16u;
-        n_threads = std::max(1u, std::min({want, hw ? hw : 1u, (unsigned)(n >> 20)}));
-    }
+    if (lookbehind == 0 && n >= (8u << 20)) n_threads = split_thread_count(n);
     if (n_threads <= 1) {
         size_t offset = 0;
         int rc = match_loop(code_, match_data_, text, n, offset, n, starts, ends, err);
@@ -275,6 +277,71 @@ int Splitter::split(const uint8_t *text, uint64_t n, std::vector<uint64_t> *star
             std::copy(g.e->begin() + g.from, g.e->begin() + g.to, ends->begin() + at[i]);
         });
     for (auto &t : copiers) t.join();
+    return MBPE_OK;
+}
+
+int Splitter::split_spans(const uint8_t *sub, uint64_t origin, uint64_t n, const uint64_t *spans, uint64_t n_spans,
+                          unsigned n_threads, std::vector<uint64_t> *last_bytes, std::string *err) const {
+    last_bytes->clear();
+    if (!n_spans) return MBPE_OK;
+    if (!code_) { *err = "split_spans: no pattern"; return MBPE_ERR_ARG; }
+    Pcre2Api &p = pcre2();
+    // thread k takes the stretches [cut[k], cut[k + 1]): about the same number of bytes each
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n_spans; ++i) total += spans[2 * i + 1] - spans[2 * i];
+    n_threads = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n_threads, n_spans));
+    std::vector<uint64_t> cut(n_threads + 1, n_spans);
+    cut[0] = 0;
+    uint64_t seen = 0;
+    unsigned k = 1;
+    for (uint64_t i = 0; i < n_spans && k < n_threads; ++i) {
+        seen += spans[2 * i + 1] - spans[2 * i];
+        if (seen * n_threads >= total * k) cut[k++] = i + 1;
+    }
+    struct Part { std::vector<uint64_t> last; int rc = MBPE_OK; std::string err; };
+    std::vector<Part> parts(n_threads);
+    auto work = [&](unsigned w) {
+        Part &pt = parts[w];
+        void *md = p.match_data_create_from_pattern(code_, nullptr);
+        if (!md) { pt.rc = MBPE_ERR_REGEX; pt.err = "PCRE2 match data creation failed."; return; }
+        std::vector<uint64_t> starts, ends;
+        for (uint64_t i = cut[w]; i < cut[w + 1] && pt.rc == MBPE_OK; ++i) {
+            const uint64_t a = spans[2 * i], b = spans[2 * i + 1];
+            // No match that starts before b crosses b (t[b - 1] is a letter or digit and t[b] whitespace, or b is
+            // the end of the text), and no decision reads further than t[b]: the subject [a, min(b + 1, n)) is enough
+            const uint64_t len = std::min(b + 1, n) - a;
+            starts.clear();
+            ends.clear();
+            size_t offset = 0;
+            const int rc = match_loop(code_, md, sub + (a - origin), len, offset, b - a, &starts, &ends, &pt.err);
+            if (rc < 0) { pt.rc = rc; break; }
+            uint64_t pos = 0;
+            for (size_t m = 0; m < starts.size(); ++m) {
+                if (starts[m] != pos) break;
+                pos = ends[m];
+                pt.last.push_back(a + pos - 1);
+            }
+            if (pos != b - a || (!ends.empty() && ends.back() != b - a)) {
+                pt.rc = MBPE_ERR_SPLIT_GAP;
+                pt.err = "the split pattern left bytes unmatched between " + std::to_string(a) + " and " +
+                         std::to_string(b) + " (invalid UTF-8?): use the host split";
+            }
+        }
+        p.match_data_free(md);
+    };
+    if (n_threads == 1) work(0);
+    else {
+        std::vector<std::thread> pool;
+        for (unsigned w = 0; w < n_threads; ++w) pool.emplace_back(work, w);
+        for (auto &t : pool) t.join();
+    }
+    size_t count = 0;
+    for (const Part &pt : parts) {
+        if (pt.rc != MBPE_OK) { *err = pt.err; return pt.rc; }
+        count += pt.last.size();
+    }
+    last_bytes->reserve(count);
+    for (const Part &pt : parts) last_bytes->insert(last_bytes->end(), pt.last.begin(), pt.last.end());
     return MBPE_OK;
 }
 

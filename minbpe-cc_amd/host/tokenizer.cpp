@@ -142,7 +142,7 @@ void Tokenizer::set_special_tokens_from_file(const std::string &input_string) { 
 }
 
 void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTION conflict_resolution,
-                      bool verbose, int device) {
+                      bool verbose, int device, bool device_split) {
     if (vocab_size < 256) throw std::runtime_error("vocab_size must be >= 256");   // assert, :492
     drop_decoder();
     drop_encoder();
@@ -150,23 +150,45 @@ void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTI
     merges_lookup_.clear();
     initialize_vocab();
 
-    std::vector<uint64_t> starts, ends;
-    std::string err;
     const uint8_t *bytes = reinterpret_cast<const uint8_t *>(text.data());
-    if (splitter_.split(bytes, text.size(), &starts, &ends, &err) != MBPE_OK) throw std::runtime_error(err);
-    if (verbose) std::cout << "Split input text into " << starts.size() << " chunks\n";   // :546-548
+    std::vector<uint64_t> starts, ends;
+    mbpe_splitter *dev_split = nullptr;
+    const uint8_t *d_text = nullptr, *d_mask = nullptr;
+    if (device_split) {
+        // the split on the device: one upload of the text, which the trainer then takes in place with the mask
+        uint64_t n_chunks = 0;
+        int rc = mbpe_splitter_create(device, pattern_.c_str(), &dev_split);
+        if (rc == MBPE_OK) rc = mbpe_splitter_split(dev_split, bytes, text.size(), 0, nullptr, nullptr, 0, &n_chunks);
+        if (rc == MBPE_OK) rc = mbpe_splitter_endmask(dev_split, &d_mask, nullptr, &d_text);
+        if (rc != MBPE_OK) {
+            const std::string msg = mbpe_last_error();
+            mbpe_splitter_destroy(dev_split);
+            throw CodedError(rc, msg);
+        }
+        if (verbose) std::cout << "Split input text into " << n_chunks << " chunks\n";
+    } else {
+        std::string err;
+        if (splitter_.split(bytes, text.size(), &starts, &ends, &err) != MBPE_OK) throw std::runtime_error(err);
+        if (verbose) std::cout << "Split input text into " << starts.size() << " chunks\n";   // :546-548
+    }
     const bool chunked = splitter_.has_pattern();
 
     mbpe_ctx *ctx = nullptr;
-    if (mbpe_create(device, &ctx) != MBPE_OK) throw std::runtime_error(mbpe_last_error());
+    if (mbpe_create(device, &ctx) != MBPE_OK) {
+        mbpe_splitter_destroy(dev_split);
+        throw std::runtime_error(mbpe_last_error());
+    }
     const uint32_t cap = static_cast<uint32_t>(vocab_size - 256);
     std::vector<uint32_t> flat(2 * static_cast<size_t>(cap) + 2);
     std::vector<int32_t> had(cap + 1);
     uint32_t n_merges = 0;
     mbpe_stats st;
-    // chunks as ranges: bytes between two matches belong to no chunk, as in the reference's loop (:506-540)
-    int rc = chunked ? mbpe_load_corpus_ranges(ctx, bytes, text.size(), starts.data(), ends.data(), starts.size(), 0)
-                     : mbpe_load_corpus(ctx, bytes, text.size(), nullptr, 0, 0);
+    // chunks as ranges: bytes between two matches belong to no chunk, as in the reference's loop (:506-540).  The
+    // device split's mask goes to the trainer as it is: the NUL rule of text_to_vector (:86-93) never fires for the
+    // gpt2 / gpt4 patterns -- a chunk that starts with NUL holds no ASCII digit, so std::stoi cannot parse its remainder
+    int rc = dev_split ? mbpe_load_corpus_endmask(ctx, text.empty() ? bytes : d_text, text.size(), !text.empty(), d_mask)
+             : chunked ? mbpe_load_corpus_ranges(ctx, bytes, text.size(), starts.data(), ends.data(), starts.size(), 0)
+                       : mbpe_load_corpus(ctx, bytes, text.size(), nullptr, 0, 0);
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "conflict_resolution", conflict_resolution == LEXICAL ? 1 : 0);
     // (`first` beyond the 16-bit slot format continues on 32-bit tokens, as the reference's uint32_t Token does)
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "first_wide", 1);
@@ -176,6 +198,7 @@ void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTI
     if (rc == MBPE_OK) rc = mbpe_get_stats(ctx, &st);
     std::string msg = rc == MBPE_OK ? "" : mbpe_last_error();
     mbpe_destroy(ctx);
+    mbpe_splitter_destroy(dev_split);       // (its text and mask were in use until here)
     if (rc != MBPE_OK) throw std::runtime_error(msg);
 
     const int total_merges = vocab_size - 256;
@@ -596,6 +619,23 @@ int mbpe_tok_train(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, uint32_t 
                     device_id);
         return (int)MBPE_OK;
     });
+}
+
+int mbpe_tok_train_split_device(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, uint32_t vocab_size,
+                                int conflict_resolution, int verbose, int device_id) {
+    if (!t || (!text && n)) return MBPE_ERR_ARG;
+    try {
+        t->t->train(std::string(reinterpret_cast<const char *>(text), n), (int)vocab_size,
+                    conflict_resolution ? mbpe_host::Tokenizer::LEXICAL : mbpe_host::Tokenizer::FIRST, verbose != 0,
+                    device_id, true);
+        return MBPE_OK;
+    } catch (const mbpe_host::CodedError &e) {       // the splitter's own code: MBPE_ERR_ARG for a custom pattern
+        mbpe_host::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        mbpe_host::set_last_error(e.what());
+        return MBPE_ERR_ARG;
+    }
 }
 
 int mbpe_tok_set_merges(mbpe_tokenizer *t, const uint32_t *merges, uint32_t n_merges) {

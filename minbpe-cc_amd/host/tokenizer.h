@@ -31,8 +31,11 @@ public:
 
     void set_special_tokens_from_file(const std::string &input_string);   // :476-486
     // :489-598; both CONFLICT_RESOLUTION values run on HIP device `device` (mbpe_train)
+    // device_split: the gpt2 / gpt4 pre-split runs on the device too (mbpe_splitter_split; the text is uploaded once
+    // and the trainer takes text and end mask in place).  Same merges.  A tokenizer with any other pattern throws
+    // CodedError(MBPE_ERR_ARG): there is no silent return to the host split
     void train(const std::string &text, int vocab_size, CONFLICT_RESOLUTION conflict_resolution, bool verbose,
-               int device = 0);
+               int device = 0, bool device_split = false);
     // :653-722; device >= 0 runs internal_encode (:325-377) on that HIP device instead of the host
     std::vector<Token> encode(const std::string &text, bool verbose, int device = -1);
     // encode() of every text, [i] == encode(texts[i], false, -1): the chunks of all texts go to HIP device `device`

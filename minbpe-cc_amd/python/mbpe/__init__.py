@@ -33,6 +33,9 @@ EXPORTS = [
     "mbpe_encoder_alloc_count", "mbpe_encoder_pass_tokens", "mbpe_decode_batch", "mbpe_decoder_alloc_count",
     "mbpe_pack_tokens", "mbpe_unpack_tokens", "mbpe_pack_kernel_ms", "mbpe_encoder_encode_batch", "mbpe_encoder_pack_ms",
     "mbpe_pack_tokens_aux", "mbpe_pack_cu_seqlens", "mbpe_encoder_encode_batch_aux",
+    "mbpe_load_corpus_endmask", "mbpe_splitter_create", "mbpe_splitter_destroy", "mbpe_splitter_split",
+    "mbpe_splitter_endmask", "mbpe_splitter_set_option", "mbpe_splitter_kernel_ms", "mbpe_splitter_alloc_count",
+    "mbpe_splitter_host_spans",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -40,6 +43,7 @@ TOK_EXPORTS = [
     "mbpe_tok_get_merges", "mbpe_tok_save", "mbpe_tok_load", "mbpe_tok_encode", "mbpe_tok_encode_device",
     "mbpe_tok_decode", "mbpe_tok_decode_device", "mbpe_tok_encode_batch_device", "mbpe_tok_decode_batch_device",
     "mbpe_tok_encode_batch_packed_device", "mbpe_tok_decode_padded_device", "mbpe_tok_encode_batch_aux_device",
+    "mbpe_tok_train_split_device",
 ]
 
 
@@ -69,6 +73,7 @@ class Stats(ctypes.Structure):
 
 
 PACK_PADDED, PACK_PACKED = 0, 1
+SPLIT_BLOCK, SPLIT_TILE, SPLIT_MAX_SPAN = 64, 16384, 4096      # MBPE_SPLIT_BLOCK, _TILE, _MAX_SPAN
 NO_TOKEN = 0xFFFFFFFF
 
 
@@ -201,6 +206,17 @@ def lib():
     L.mbpe_tok_destroy.restype = None
     L.mbpe_tok_set_special_tokens.argtypes = [vp, ctypes.c_char_p, u64]
     L.mbpe_tok_train.argtypes = [vp, vp, u64, u32, i32, i32, i32]
+    L.mbpe_tok_train_split_device.argtypes = L.mbpe_tok_train.argtypes
+    L.mbpe_load_corpus_endmask.argtypes = [vp, vp, u64, i32, vp]
+    L.mbpe_splitter_create.argtypes = [i32, ctypes.c_char_p, ctypes.POINTER(vp)]
+    L.mbpe_splitter_destroy.argtypes = [vp]
+    L.mbpe_splitter_destroy.restype = None
+    L.mbpe_splitter_split.argtypes = [vp, vp, u64, i32, vp, vp, u64, vp]
+    L.mbpe_splitter_endmask.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(vp)]
+    L.mbpe_splitter_set_option.argtypes = [vp, ctypes.c_char_p, i64]
+    L.mbpe_splitter_kernel_ms.argtypes = [vp, vp]
+    L.mbpe_splitter_alloc_count.argtypes = [vp, vp]
+    L.mbpe_splitter_host_spans.argtypes = [vp, vp, vp]
     L.mbpe_tok_set_merges.argtypes = [vp, vp, u32]
     L.mbpe_tok_get_merges.argtypes = [vp, vp, u32, vp]
     L.mbpe_tok_save.argtypes = [vp, ctypes.c_char_p, i32]
@@ -745,6 +761,84 @@ class Decoder:
         return n.value
 
 
+class Splitter:
+    """One mbpe_splitter: the gpt2 / gpt4 pre-split on the device (pattern = split_pattern("gpt2") or ("gpt4"))."""
+
+    def __init__(self, pattern, device=0):
+        self._h = ctypes.c_void_p()
+        _check(lib().mbpe_splitter_create(device, pattern.encode("utf-8"), ctypes.byref(self._h)))
+        self._keep = None
+
+    def close(self):
+        if self._h:
+            lib().mbpe_splitter_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_option(self, name, value):
+        _check(lib().mbpe_splitter_set_option(self._h, name.encode(), int(value)))
+
+    def split(self, data=None, offsets=True, mask_ptr=None, text_ptr=None, n_bytes=None, cap_chunks=None):
+        """Splits data (host bytes), or n_bytes of device memory at text_ptr.  Returns the number of chunks, or with
+        offsets the uint64 offsets [n_chunks + 1] that presplit gives.  mask_ptr: device memory for the end mask
+        (mask_bytes(n) of it); otherwise the mask stays in the splitter, see endmask().  cap_chunks: the capacity
+        handed to the library with the offsets array (default: n_bytes, which always suffices)."""
+        if text_ptr is None:
+            text = _u8(data)
+            self._keep = text
+            ptr, n, on_dev = (text.ctypes.data if len(text) else None), len(text), 0
+        else:
+            ptr, n, on_dev = ctypes.c_void_p(text_ptr), n_bytes, 1
+        count = ctypes.c_uint64()
+        mask = None if mask_ptr is None else ctypes.c_void_p(mask_ptr)
+        if not offsets:
+            _check(lib().mbpe_splitter_split(self._h, ptr, n, on_dev, mask, None, 0, ctypes.byref(count)))
+            return count.value
+        if cap_chunks is None:
+            cap_chunks = n          # always enough: no chunk is empty
+        off = np.zeros(cap_chunks + 1, dtype=np.uint64)
+        _check(lib().mbpe_splitter_split(self._h, ptr, n, on_dev, mask, off.ctypes.data, cap_chunks, ctypes.byref(count)))
+        return off[:count.value + 1]
+
+    @staticmethod
+    def mask_bytes(n_bytes):
+        return (n_bytes + 15) // 16 * 2 + 16
+
+    def endmask(self):
+        """(device address of the latest call's end mask, its size in bytes, device address of that call's text);
+        all owned by the splitter (or, the text, by the caller) and valid until its next call."""
+        m, nb, t = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_void_p()
+        _check(lib().mbpe_splitter_endmask(self._h, ctypes.byref(m), ctypes.byref(nb), ctypes.byref(t)))
+        return m.value, nb.value, t.value
+
+    def kernel_ms(self):
+        ms = ctypes.c_float()
+        _check(lib().mbpe_splitter_kernel_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def alloc_count(self):
+        n = ctypes.c_uint64()
+        _check(lib().mbpe_splitter_alloc_count(self._h, ctypes.byref(n)))
+        return n.value
+
+    def host_spans(self):
+        """(host spans, text bytes in them) of the latest call."""
+        n, b = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().mbpe_splitter_host_spans(self._h, ctypes.byref(n), ctypes.byref(b)))
+        return n.value, b.value
+
+
 class Trainer:
     """One mbpe_ctx.  Mirrors the order of Tokenizer::train (Tokenizer.h:489-598)."""
 
@@ -798,6 +892,19 @@ class Trainer:
         _check(lib().mbpe_load_corpus(self._h, ctypes.c_void_p(dev_ptr), n_bytes,
                                       None if off is None else off.ctypes.data,
                                       0 if off is None else len(off) - 1, 1))
+
+    def load_corpus_endmask(self, mask_ptr, data=None, text_ptr=None, n_bytes=None, keep=None):
+        """A chunked corpus whose end mask is in device memory at mask_ptr (Splitter.split / Splitter.endmask); the
+        text is host bytes (data) or n_bytes of device memory at text_ptr, taken in place."""
+        if text_ptr is None:
+            text = _u8(data)
+            self._keep = (text, keep)
+            _check(lib().mbpe_load_corpus_endmask(self._h, text.ctypes.data if len(text) else None, len(text), 0,
+                                                  ctypes.c_void_p(mask_ptr)))
+        else:
+            self._keep = (keep,)
+            _check(lib().mbpe_load_corpus_endmask(self._h, ctypes.c_void_p(text_ptr), n_bytes, 1,
+                                                  ctypes.c_void_p(mask_ptr)))
 
     def pair_count_u8(self, want_table=True):
         table = np.zeros(65536, dtype=np.uint32) if want_table else None
@@ -958,10 +1065,13 @@ class Tokenizer:
         b = text if isinstance(text, bytes) else text.encode("utf-8")
         _check(lib().mbpe_tok_set_special_tokens(self._h, b, len(b)))
 
-    def train(self, data, vocab_size, conflict_resolution=1, verbose=False, device=0):
+    def train(self, data, vocab_size, conflict_resolution=1, verbose=False, device=0, device_split=False):
+        """device_split: the gpt2 / gpt4 pre-split runs on the device too (same merges); a tokenizer with any other
+        pattern raises MbpeError(ERR_ARG)."""
         text = _u8(data)
-        _check(lib().mbpe_tok_train(self._h, text.ctypes.data if len(text) else None, len(text), vocab_size,
-                                    conflict_resolution, int(verbose), device))
+        fn = lib().mbpe_tok_train_split_device if device_split else lib().mbpe_tok_train
+        _check(fn(self._h, text.ctypes.data if len(text) else None, len(text), vocab_size, conflict_resolution,
+                  int(verbose), device))
 
     def set_merges(self, merges):
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1, 2)
