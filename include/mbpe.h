@@ -74,28 +74,37 @@ typedef struct {
     uint64_t n_live;           /* live tokens right now */
     uint32_t n_merges;         /* merges performed so far */
     uint32_t n_compactions;    /* stream compactions performed */
-    uint64_t n_pairs;          /* pairs ever inserted (== PairCount::get_count) */
+    uint64_t n_pairs;          /* members of the device's pair table (what mbpe_get_pairs returns): PairCount::get_count
+                                  less those of the transient zero-count pairs (X,a), which the reference inserts between
+                                  two touching matches, that the device never inserted ("Exactness of the
+                                  parallel merge") */
     float    ms_pair_count;    /* last pair-count scan kernel */
     float    ms_begin;         /* widen + table build + first argmax */
     float    ms_steps;         /* all merge steps so far */
     uint32_t pair_count_launches;
-    uint32_t merge_launches;   /* merge-kernel launches timed ("time_kernels" option) */
+    uint32_t merge_launches;   /* merge-kernel launches timed: grows only while the option "time_kernels" is 1, by one per
+                                  stream pass that merged something, and accumulates over the trainings of a loaded corpus
+                                  (mbpe_load_corpus* resets it, mbpe_train_begin does not); so do ms_merge_kernel and
+                                  the fused_* fields below */
     float    ms_merge_kernel;  /* summed duration of those launches */
     uint32_t n_batches;        /* stream passes that merged something (several merges can share one) */
     uint32_t n_fused;          /* of them: fused passes (large batches, merged stream written to the other buffer) */
     uint32_t n_fused_dropped;  /* fused passes whose output was abandoned because validation kept only a prefix */
     uint32_t cut_conflict;     /* batches ended by a pair that depends on an earlier pair of the batch */
     uint32_t cut_bucket;       /* ... by a full lookup bucket */
-    uint32_t cut_single;       /* ... by a (t,t) or zero-count pair (merged alone) */
+    uint32_t cut_single;       /* ... by a zero-count pair or a (t,t) pair that is merged alone: every (t,t) pair under
+                                  the bound-walking selection ("threshold_select" 0, or as the fallback); under the
+                                  threshold selection only one that finds no stand-in id left in its batch */
     uint32_t cut_full;         /* batches that reached the size limit */
     uint32_t n_validation_drops; /* pairs selected but not merged in that pass (validation) */
     float    ms_grow_table;    /* host wall time spent growing the pair table (allocation + rehash) */
     float    ms_compact;       /* host wall time spent compacting the stream */
     uint32_t n_table_grows;
     uint32_t n_sel_fallback;   /* batches chosen by the bound-walking selection instead of the threshold gather */
-    uint32_t fused_launches;   /* fused passes timed ("time_kernels" option) */
+    uint32_t fused_launches;   /* fused passes timed ("time_kernels" 1 only; accumulates like merge_launches): one per
+                                  sequence that n_fused counts, abandoned ones included */
     float    ms_fused_kernel;  /* their summed duration */
-    uint64_t fused_slots;      /* stream slots those passes read (and wrote) */
+    uint64_t fused_slots;      /* stream slots those passes read (and wrote): n_slots at each pass, summed */
     uint32_t n_sel_retry;      /* batches whose first candidate gather overflowed (threshold found among the block bounds) */
     uint32_t adapt_limit;      /* current batch size limit learnt from validation */
     uint64_t n_sel_blocks;     /* 1024-entry blocks of the pair table read by the candidate gathers */
@@ -106,7 +115,10 @@ typedef struct {
     uint32_t exchanges;        /* ... in this many all-reduces (one per sequence) */
     uint32_t pad_;
     uint64_t fused_live_tokens; /* "time_kernels": live tokens before + live tokens after, summed over the timed fused
-                                   passes (x 2 bytes = SURVEY 8(d)'s 2 B x L read + 2 B x L' written of those passes) */
+                                   passes (x 2 bytes = SURVEY 8(d)'s 2 B x L read + 2 B x L' written of those passes).
+                                   In the barrier layout ("chunk_barrier") both terms include one barrier slot per chunk,
+                                   which the pass reads and writes like a token; n_live above does not.  Accumulates like
+                                   merge_launches */
     float    ms_pair_count_kernel; /* mbpe_pair_count_u8 without a table: mean KERNEL duration of the call's launches
                                    (start/stop events of each dispatch: no gap between launches, no marker overhead) */
     uint32_t pad2_;

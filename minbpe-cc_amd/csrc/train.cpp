@@ -966,6 +966,7 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size) {
     HIPCHK(tmalloc(c, &c->run_in, ((size_t)c->n_tiles + 64) * 4));
     HIPCHK(tmalloc(c, &c->seq_flags, 4096 * 4 * 4));      // 4 words per sequence of a group (k_seq_finish)
     HIPCHK(hipMemsetAsync(c->bs, 0, sizeof(BatchState), c->stream));
+    HIPCHK(hipMemsetAsync(c->seq_flags, 0, 4096 * 4 * 4, c->stream));
     if (c->opt_first) {
         HIPCHK(tmalloc(c, &c->first_state, first_state_bytes()));
         launch_first_init(c->stream, c->first_state);
@@ -1467,7 +1468,12 @@ static int train_steps_batched(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_do
                     bool nothing_left = false;
                     const int r = seq_lockstep(c, slot, &nothing_left);
                     if (r != MBPE_OK) return r;
-                    if (nothing_left) { ++launched; break; }
+                    if (nothing_left) {
+                        // (no k_seq_finish ran for this slot: its record would be an earlier sequence's)
+                        if (slot >= 0) HIPCHK(hipMemsetAsync(c->seq_flags + 4 * slot, 0, 16, c->stream));
+                        ++launched;
+                        break;
+                    }
                     continue;
                 }
                 // (with several ranks the selection's result arrives while the stream pass runs: every rank took the same
