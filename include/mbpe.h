@@ -578,6 +578,49 @@ MBPE_API int  mbpe_encoder_encode_batch_aux(mbpe_encoder *e, const uint8_t *text
                                             uint64_t *n_rows_out, uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
                                             uint64_t *doc_tok_off_out);
 
+/* ---- encode from an end mask that is on the device ----------------------- */
+
+/* mbpe_encoder_encode for a text and an end mask that both are device memory of the encoder's device already -- what
+ * mbpe_splitter_split_docs leaves behind (mbpe_splitter_endmask).  Both are read in place.
+ *   text_dev, n_bytes   the text
+ *   endmask_dev         its end mask in the splitter's and the trainer's layout (bit i & 7 of byte i >> 3 = text byte i
+ *                       is the last of its chunk; 2 * ceil(n_bytes / 16) + 16 bytes, nothing set at or beyond n_bytes),
+ *                       4-byte aligned
+ *   singles, n_singles  host, ascending and disjoint: bytes [start, start + len) are ONE token, `id`.  The text holds
+ *                       the special tokens' names, not "\0<id>" markers, and no chunk is parsed for a number: the
+ *                       caller says which ranges are single tokens.  Checked on the host: order, range, and that every
+ *                       id fits the output (MBPE_ERR_ARG at 2^31 - 2 and above; MBPE_ERR_VOCAB at 65,536 and above with
+ *                       token_bits 16).  NOT checked: that the mask ends a chunk right before and at the end of every
+ *                       single.  That is a precondition; breaking it gives wrong tokens, never a wrong address
+ *   doc_off, n_docs     host, optional (NULL / 0): n_docs + 1 ascending byte offsets up to n_bytes, each of them a chunk
+ *                       boundary (a precondition as well)
+ *   doc_tok_off_out     optional, host, n_docs + 1 entries: [i] = the output tokens that come from the bytes before
+ *                       doc_off[i], computed on the device (the rank of doc_off[i] among the mask's end bits, then the
+ *                       finishing kernel's list of chunk ends).  Also filled by a query; a cap too small writes [0] only
+ *   tokens_out, cap, token_bits, out_on_device, n_out, n_passes_out   as for mbpe_encoder_encode, MBPE_ERR_VOCAB and
+ *                       the query included
+ * One piece only: a text above the piece limit of mbpe_encoder_encode (option "piece_bytes") returns MBPE_ERR_OOM with
+ * a message that names the limit; the encoder stays usable.  A repeat call of no larger size allocates nothing. */
+typedef struct { uint64_t start, len; uint32_t id, pad; } mbpe_single;
+MBPE_API int  mbpe_encoder_encode_endmask(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
+                                          const uint8_t *endmask_dev, const mbpe_single *singles, uint64_t n_singles,
+                                          const uint64_t *doc_off, uint64_t n_docs,
+                                          void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device,
+                                          uint64_t *doc_tok_off_out, uint64_t *n_out, uint32_t *n_passes_out);
+
+/* The same followed by the pack kernel: mbpe_encoder_encode_batch (aux NULL: ids and lengths only) or
+ * mbpe_encoder_encode_batch_aux for the documents doc_off describes, which here must start at 0 and end at n_bytes.
+ * The documents' token offsets go from the encode to the pack kernel on the device; neither a token nor an offset
+ * crosses to the host unless doc_tok_off_out asks for the offsets.  All other arguments and results are those of
+ * mbpe_encoder_encode_batch_aux. */
+MBPE_API int  mbpe_encoder_encode_batch_endmask(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
+                                                const uint8_t *endmask_dev, const mbpe_single *singles,
+                                                uint64_t n_singles, const uint64_t *doc_off, uint64_t n_docs,
+                                                const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows,
+                                                int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                                                uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
+                                                uint64_t *doc_tok_off_out);
+
 /* ---- decode on the device ----------------------------------------------- */
 
 /* Tokenizer::decode (Tokenizer.h:725-751) for whole token streams on HIP device `device_id`: per token a byte
@@ -745,6 +788,46 @@ MBPE_API void mbpe_splitter_destroy(mbpe_splitter *s);
 MBPE_API int  mbpe_splitter_split(mbpe_splitter *s, const uint8_t *text, uint64_t n_bytes, int text_on_device,
                                   uint8_t *endmask_dev_out, uint64_t *chunk_off_out, uint64_t cap_chunks,
                                   uint64_t *n_chunks_out);
+
+/* Splits many texts in one call, around ranges that are not split: for every document on its own, what
+ * Tokenizer::split_on_special followed by the regex split of every part does (Tokenizer.h:605-704), with the result
+ * as an end mask over the original text instead of a rewritten buffer.
+ *   text, n_bytes, text_on_device, endmask_dev_out   as for mbpe_splitter_split
+ *   doc_off, n_docs  host, n_docs + 1 ascending offsets from 0 to n_bytes: document i is bytes [doc_off[i], doc_off[i + 1]).
+ *                    A chunk never crosses a document boundary; an empty document has no chunk; n_docs == 0 or
+ *                    n_bytes == 0 gives an empty result
+ *   names, name_off, n_names   host: name j is names[name_off[j] .. name_off[j + 1]); n_names may be 0.  Every
+ *                    occurrence of a non-empty name that lies inside one document is a candidate; candidates are
+ *                    ordered by (position, name index) and one is TAKEN when it starts at or after the end of the
+ *                    previous one taken in that document.  At most MBPE_SPLIT_MAX_NAMES names with
+ *                    MBPE_SPLIT_MAX_NAME_BYTES bytes in all
+ *   A PART is a maximal stretch of a document between taken occurrences.  A part whose first byte is NUL is not split
+ *   (the reference's rule: such a part counts as special); every other part is split by the pattern as if it were a
+ *   whole text -- so "a  " followed by "b" gives a, two spaces, b, where "a  b" gives a, one space, " b".
+ *   ranges_out       optional, host, cap_ranges entries: ascending, the taken occurrences (name = index) and the
+ *                    NUL-led parts (name = MBPE_SPLIT_RAW).  Each range is exactly one chunk of the mask
+ *   n_ranges_out     optional: how many there are.  cap_ranges smaller than it (with ranges_out given) returns
+ *                    MBPE_ERR_ARG after the count is stored and writes neither ranges nor endmask_dev_out.  With
+ *                    ranges_out NULL they stay readable through mbpe_splitter_ranges
+ *   n_chunks_out     required, as for mbpe_splitter_split
+ * All arguments are checked before the device is touched.  MBPE_ERR_SPLIT_GAP as for mbpe_splitter_split: neither
+ * mask nor ranges are written.  The mask stays readable through mbpe_splitter_endmask. */
+#define MBPE_SPLIT_RAW            0xFFFFFFFFu
+#define MBPE_SPLIT_MAX_NAMES      256u
+#define MBPE_SPLIT_MAX_NAME_BYTES 16384u
+typedef struct { uint64_t start, len; uint32_t name, pad; } mbpe_split_range;
+MBPE_API int  mbpe_splitter_split_docs(mbpe_splitter *s, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                       const uint64_t *doc_off, uint64_t n_docs,
+                                       const uint8_t *names, const uint64_t *name_off, uint32_t n_names,
+                                       uint8_t *endmask_dev_out,
+                                       mbpe_split_range *ranges_out, uint64_t cap_ranges, uint64_t *n_ranges_out,
+                                       uint64_t *n_chunks_out);
+
+/* The ranges of the latest successful mbpe_splitter_split_docs in the splitter's own host memory (valid until its
+ * next call; none after mbpe_splitter_split), and the device time of that call's k_split_find launches (part of
+ * mbpe_splitter_kernel_ms). */
+MBPE_API int  mbpe_splitter_ranges(const mbpe_splitter *s, const mbpe_split_range **ranges_out, uint64_t *n_ranges_out);
+MBPE_API int  mbpe_splitter_find_ms(const mbpe_splitter *s, float *ms_out);
 
 /* The mask of the latest successful call in the splitter's own device memory (valid until its next call), its size,
  * and -- optional -- where that call's text is on the device: the caller's device text, or the splitter's copy of a

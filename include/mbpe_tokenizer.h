@@ -91,6 +91,14 @@ MBPE_API int mbpe_tok_encode_batch_aux_device(mbpe_tokenizer *t, const uint8_t *
                                               uint64_t *n_rows_out, uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
                                               uint64_t *doc_tok_off_out);
 
+/* Where the mbpe_tok_encode*_device calls above split their text: 0 (the default) on the host, as described there;
+ * otherwise on the device too -- the text is uploaded once, cut at the special tokens and split into chunks by
+ * mbpe_splitter_split_docs (a splitter that the tokenizer keeps until another device is named), and the encoder reads
+ * that copy and its end mask in place (mbpe_encoder_encode_endmask, mbpe_encoder_encode_batch_endmask).  Same results.
+ * With it set, a tokenizer whose pattern is not the built-in gpt2 or gpt4 pattern returns MBPE_ERR_ARG from those
+ * calls: there is no silent return to the host split.  Nothing else is affected. */
+MBPE_API int mbpe_tok_set_encode_split(mbpe_tokenizer *t, int on_device);
+
 /* decode, Tokenizer.h:725-751.  bytes_out may be NULL to query the length. */
 MBPE_API int mbpe_tok_decode(mbpe_tokenizer *t, const uint32_t *tokens, uint64_t n, int verbose,
                              uint8_t *bytes_out, uint64_t cap, uint64_t *n_out);

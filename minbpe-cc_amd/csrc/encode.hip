@@ -181,6 +181,47 @@ __global__ __launch_bounds__(kSpanThreads) void k_enc_end_count(const uint32_t *
     if (lane == 0) span_ends[span] = cnt;
 }
 
+// ---- document offsets from an end mask that is on the device (mbpe_encoder_encode_endmask) ----------------------
+// rank(p) = end bits of the mask below text byte p = chunks that end before p.  A mask BLOCK is 64 words of 32 bits
+// (2,048 text bytes): one wave counts a block, k_enc_scan_sum links the blocks, and a position adds the words of its
+// block below its own and the low bits of that one.
+constexpr uint32_t kMaskBlockWords = 64;
+
+__global__ __launch_bounds__(256) void k_enc_mask_count(const uint32_t *__restrict__ mask, uint64_t n_words,
+                                                        uint64_t n_blocks, uint32_t *__restrict__ cnt) {
+    const uint64_t block = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+    if (block >= n_blocks) return;                                   // (whole waves leave together)
+    const uint32_t lane = lane_id();
+    const uint64_t w = block * kMaskBlockWords + lane;
+    uint32_t c = w < n_words ? (uint32_t)__popc(mask[w]) : 0u;
+    for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d, 64);
+    if (lane == 0) cnt[block] = c;
+}
+
+// doc_tok[i] = output tokens that come from the bytes before pos[i] (a chunk boundary): the end of chunk rank - 1 in
+// the list the finishing kernel wrote, or 0 before the first chunk.  mask: 4 * n_words bytes and 4 more are readable
+__global__ __launch_bounds__(256) void k_enc_doc_tok(const unsigned long long *__restrict__ pos, uint64_t n_pos,
+                                                     const uint32_t *__restrict__ mask, uint64_t n_bytes,
+                                                     const unsigned long long *__restrict__ block_off, uint64_t n_blocks,
+                                                     const unsigned long long *__restrict__ total,
+                                                     const unsigned long long *__restrict__ ends, uint64_t n_ends,
+                                                     unsigned long long *__restrict__ doc_tok) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pos) return;
+    const uint64_t p = pos[i] < n_bytes ? pos[i] : n_bytes;
+    const uint64_t w = p >> 5, block = w / kMaskBlockWords;
+    unsigned long long r;
+    if (block >= n_blocks) {
+        r = *total;
+    } else {
+        r = block_off[block];
+        for (uint64_t j = block * kMaskBlockWords; j < w; ++j) r += (unsigned long long)__popc(mask[j]);
+        if (p & 31u) r += (unsigned long long)__popc(mask[w] & ((1u << (p & 31u)) - 1u));
+    }
+    if (r > n_ends) r = n_ends;
+    doc_tok[i] = r ? ends[r - 1] : 0ull;
+}
+
 enum FinMode {
     kFinFlags = 0,      // uint32_t, bit 31 = last token of its chunk (as the passes leave them)
     kFinU32 = 1,        // uint32_t ids
@@ -263,6 +304,8 @@ struct mbpe_encoder {
     void *d_ids = nullptr;
     uint32_t *d_len = nullptr;
     uint64_t cap_flat = 0, cap_doc_off = 0, cap_ids = 0, cap_len = 0;
+    unsigned long long *d_doc_pos = nullptr;  // mbpe_encoder_encode_endmask: the documents' byte offsets
+    uint64_t cap_doc_pos = 0;
     // mbpe_encoder_encode_batch_aux: labels, positions and segments that go to the host
     void *d_labels = nullptr;
     uint32_t *d_pos = nullptr, *d_seg = nullptr;
@@ -381,6 +424,12 @@ struct EncCall {
     int out_on_device;
     uint64_t *chunk_tok_off_out;
     bool mask_on_device;         // the (single) piece's mask is on the device already
+    // mbpe_encoder_encode_endmask: one piece whose mask is the caller's; the token offsets of the documents are left
+    // in e->d_doc_off (and copied to doc_tok_off_out when that is given)
+    const uint8_t *mask_dev = nullptr;
+    const uint64_t *doc_off = nullptr;
+    uint64_t n_docs = 0;
+    uint64_t *doc_tok_off_out = nullptr;
 };
 
 // one piece through the passes and the finishing kernel.  done = tokens of the pieces before it.
@@ -432,9 +481,16 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
         ECHK(hipMemcpyAsync(e->d_singles, e->piece_singles.data(), e->piece_singles.size() * sizeof(SingleChunk),
                             hipMemcpyHostToDevice, e->stream));
 
+    if (a.doc_off) {
+        rc = grow(&e->d_doc_pos, &e->cap_doc_pos, (a.n_docs + 1) * 8, true, &e->n_allocs);
+        if (rc == MBPE_OK) rc = grow(&e->d_doc_off, &e->cap_doc_off, (a.n_docs + 1) * 8, true, &e->n_allocs);
+        if (rc != MBPE_OK) return rc;
+        ECHK(hipMemcpyAsync(e->d_doc_pos, a.doc_off, (a.n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
+    }
     ECHK(hipEventRecord(e->ev0, e->stream));
     const int wblocks = (int)std::min<uint64_t>((pn + 255) / 256, 8192);
-    hipLaunchKernelGGL(k_enc_widen, dim3(wblocks), dim3(256), 0, e->stream, d_text, pn, e->d_mask, e->tok[0]);
+    hipLaunchKernelGGL(k_enc_widen, dim3(wblocks), dim3(256), 0, e->stream, d_text, pn, a.mask_dev ? a.mask_dev : e->d_mask,
+                       e->tok[0]);
     if (!e->piece_singles.empty())
         hipLaunchKernelGGL(k_enc_single, dim3((uint32_t)e->piece_singles.size()), dim3(64), 0, e->stream, e->d_singles,
                            (uint32_t)e->piece_singles.size(), e->tok[0]);
@@ -467,7 +523,8 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
 
     // the finishing kernel: ids in the caller's format (into cand when they go to the host), chunk ends into tok[1 - cur]
     *too_small = a.tokens_out && a.cap < done + n;
-    const bool with_ends = a.chunk_tok_off_out && !*too_small;
+    const bool with_docs = a.doc_off && !*too_small;
+    const bool with_ends = (a.chunk_tok_off_out || a.doc_off) && !*too_small;
     const bool with_tokens = a.tokens_out && !*too_small;
     const uint64_t tok_bytes = a.token_bits / 8;
     uint64_t n_ends = 0;
@@ -476,7 +533,18 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
         const uint64_t n_spans = span_count(n);
         const dim3 grid(span_grid(n));
         if (with_ends) {
-            for (uint64_t c = p.c0; c < p.c1; ++c) n_ends += a.chunk_off[c + 1] > a.chunk_off[c];
+            if (with_docs) {
+                // the chunks are the mask's: their number comes from the device, ahead of the finishing kernel
+                hipLaunchKernelGGL(k_enc_end_count, grid, dim3(kSpanThreads), 0, e->stream, e->tok[cur], n, e->span_a);
+                hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans,
+                                   e->span_off, e->d_res);
+                unsigned long long found = 0;
+                ECHK(hipMemcpyAsync(&found, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
+                ECHK(hipStreamSynchronize(e->stream));
+                n_ends = found;
+            } else {
+                for (uint64_t c = p.c0; c < p.c1; ++c) n_ends += a.chunk_off[c + 1] > a.chunk_off[c];
+            }
             if (n_ends * 8 <= e->cap_tok[1 - cur]) {
                 d_ends = reinterpret_cast<unsigned long long *>(e->tok[1 - cur]);
             } else {
@@ -484,9 +552,11 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
                 if (rc != MBPE_OK) return rc;
                 d_ends = e->d_ends;
             }
-            hipLaunchKernelGGL(k_enc_end_count, grid, dim3(kSpanThreads), 0, e->stream, e->tok[cur], n, e->span_a);
-            hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans, e->span_off,
-                               e->d_res);
+            if (!with_docs) {
+                hipLaunchKernelGGL(k_enc_end_count, grid, dim3(kSpanThreads), 0, e->stream, e->tok[cur], n, e->span_a);
+                hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans,
+                                   e->span_off, e->d_res);
+            }
         }
         void *out = !with_tokens ? nullptr
                     : a.out_on_device ? static_cast<uint8_t *>(a.tokens_out) + done * tok_bytes
@@ -498,10 +568,23 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
             case kFinU16: launch_finish<kFinU16>(e, grid, e->tok[cur], n, out, with_ends, done, d_ends, n_ends); break;
             default: launch_finish<kFinNone>(e, grid, e->tok[cur], n, out, with_ends, done, d_ends, n_ends); break;
         }
+        if (with_docs) {
+            // the rank of every document offset in the mask, then the look-up in the chunk ends (span_a and span_off
+            // are free again: the finishing kernel is ahead on the stream)
+            const uint64_t n_words = (pn + 31) / 32, n_blocks = (n_words + kMaskBlockWords - 1) / kMaskBlockWords;
+            const uint32_t *mask32 = reinterpret_cast<const uint32_t *>(a.mask_dev);
+            hipLaunchKernelGGL(k_enc_mask_count, dim3((uint32_t)((n_blocks * kWave + 255) / 256)), dim3(256), 0, e->stream,
+                               mask32, n_words, n_blocks, e->span_a);
+            hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_blocks, e->span_off,
+                               e->d_res);
+            hipLaunchKernelGGL(k_enc_doc_tok, dim3((uint32_t)((a.n_docs + 1 + 255) / 256)), dim3(256), 0, e->stream,
+                               e->d_doc_pos, a.n_docs + 1, mask32, pn, e->span_off, n_blocks, e->d_res, d_ends, n_ends,
+                               e->d_doc_off);
+        }
     }
     ECHK(hipEventRecord(e->ev1, e->stream));
     unsigned long long ends_found = 0;
-    if (with_ends && n) ECHK(hipMemcpyAsync(&ends_found, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
+    if (with_ends && !with_docs && n) ECHK(hipMemcpyAsync(&ends_found, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
     ECHK(hipStreamSynchronize(e->stream));
     ECHK(hipGetLastError());
     float ms = 0.f;
@@ -512,7 +595,12 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
                             hipMemcpyDeviceToHost, e->stream));
         ECHK(hipStreamSynchronize(e->stream));
     }
-    if (with_ends) {
+    if (with_docs) {
+        if (a.doc_tok_off_out) {
+            ECHK(hipMemcpyAsync(a.doc_tok_off_out, e->d_doc_off, (a.n_docs + 1) * 8, hipMemcpyDeviceToHost, e->stream));
+            ECHK(hipStreamSynchronize(e->stream));
+        }
+    } else if (with_ends) {
         if (ends_found != n_ends) return fail(MBPE_ERR_HIP, "mbpe_encoder_encode: chunk ends and chunks differ in number");
         e->list.resize(n_ends);
         if (n_ends) {
@@ -656,6 +744,55 @@ int enc_run(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_
     }
 }
 
+// the pack step of the batch calls: the flat tokens in e->d_flat, the documents' token offsets in e->doc_tok (host;
+// docs_on_device: in e->d_doc_off already, and on the host only where doc_tok_off_out asks for them)
+int enc_pack_tail(mbpe_encoder *e, uint64_t n_tokens, uint64_t n_docs, uint32_t token_bits, const mbpe_pack_spec &spec,
+                  void *ids_out, uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                  uint64_t *n_tokens_out, const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out, bool docs_on_device) {
+    int rc = MBPE_OK;
+    const uint64_t n_rows = pack_rows(spec, n_tokens, n_docs);
+    *n_rows_out = n_rows;
+    if (n_tokens_out) *n_tokens_out = n_tokens;
+    if (ids_out && cap_rows < n_rows) return fail(MBPE_ERR_ARG, "ids_out too small");
+    if (doc_tok_off_out) std::copy(e->doc_tok.begin(), e->doc_tok.end(), doc_tok_off_out);   // (filled in both cases)
+    if (!ids_out) return MBPE_OK;                                // the query
+    if (n_rows == 0) return MBPE_OK;
+    const uint64_t id_bytes = n_rows * spec.seq_len * (spec.out_bits / 8), cell_bytes = n_rows * spec.seq_len * 4;
+    rc = grow(&e->d_doc_off, &e->cap_doc_off, (n_docs + 1) * 8, true, &e->n_allocs);
+    if (rc == MBPE_OK && !out_on_device) {
+        rc = grow(&e->d_ids, &e->cap_ids, id_bytes, true, &e->n_allocs);
+        if (rc == MBPE_OK && len_out) rc = grow(&e->d_len, &e->cap_len, n_rows * 4, true, &e->n_allocs);
+    }
+    mbpe_pack_aux d_aux = aux ? *aux : mbpe_pack_aux{};
+    if (rc == MBPE_OK && aux && !out_on_device) {
+        if (aux->labels) { rc = grow(&e->d_labels, &e->cap_labels, id_bytes, true, &e->n_allocs); d_aux.labels = e->d_labels; }
+        if (rc == MBPE_OK && aux->pos) { rc = grow(&e->d_pos, &e->cap_pos, cell_bytes, true, &e->n_allocs); d_aux.pos = e->d_pos; }
+        if (rc == MBPE_OK && aux->seg) { rc = grow(&e->d_seg, &e->cap_seg, cell_bytes, true, &e->n_allocs); d_aux.seg = e->d_seg; }
+    }
+    if (rc != MBPE_OK) return rc;
+    if (!docs_on_device)
+        ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
+    const PackSrc src = {e->d_flat, e->d_doc_off, n_docs, n_tokens, token_bits};
+    const PackDst dst = {out_on_device ? ids_out : e->d_ids, out_on_device || !len_out ? len_out : e->d_len, n_rows};
+    ECHK(hipEventRecord(e->ev0, e->stream));
+    if (aux) pack_launch_aux(e->stream, src, spec, dst, d_aux);
+    else pack_launch(e->stream, src, spec, dst);
+    ECHK(hipEventRecord(e->ev1, e->stream));
+    ECHK(hipStreamSynchronize(e->stream));
+    ECHK(hipGetLastError());
+    ECHK(hipEventElapsedTime(&e->pack_ms, e->ev0, e->ev1));
+    e->last_ms += e->pack_ms;
+    if (!out_on_device) {
+        ECHK(hipMemcpyAsync(ids_out, e->d_ids, id_bytes, hipMemcpyDeviceToHost, e->stream));
+        if (len_out) ECHK(hipMemcpyAsync(len_out, e->d_len, n_rows * 4, hipMemcpyDeviceToHost, e->stream));
+        if (aux && aux->labels) ECHK(hipMemcpyAsync(aux->labels, e->d_labels, id_bytes, hipMemcpyDeviceToHost, e->stream));
+        if (aux && aux->pos) ECHK(hipMemcpyAsync(aux->pos, e->d_pos, cell_bytes, hipMemcpyDeviceToHost, e->stream));
+        if (aux && aux->seg) ECHK(hipMemcpyAsync(aux->seg, e->d_seg, cell_bytes, hipMemcpyDeviceToHost, e->stream));
+        ECHK(hipStreamSynchronize(e->stream));
+    }
+    return MBPE_OK;
+}
+
 // encode into the kept flat buffer, then pack from it on the encoder's stream (arguments checked by the caller)
 int enc_batch_body(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device, const uint64_t *chunk_off,
                    uint64_t n_chunks, const uint64_t *doc_chunk_off, uint64_t n_docs, const mbpe_pack_spec &spec,
@@ -677,45 +814,82 @@ int enc_batch_body(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int t
     // (the document lengths exist only now: the limit of pos comes here, still before the pack kernel)
     if (aux) rc = pack_check_aux(spec, aux, e->doc_tok.data(), n_docs, nullptr, 0);
     if (rc != MBPE_OK) return rc;
-    const uint64_t n_rows = pack_rows(spec, n_tokens, n_docs);
-    *n_rows_out = n_rows;
-    if (n_tokens_out) *n_tokens_out = n_tokens;
-    if (ids_out && cap_rows < n_rows) return fail(MBPE_ERR_ARG, "ids_out too small");
-    if (doc_tok_off_out) std::copy(e->doc_tok.begin(), e->doc_tok.end(), doc_tok_off_out);
-    if (!ids_out) return MBPE_OK;                                // the query
-    if (n_rows == 0) return MBPE_OK;
-    const uint64_t id_bytes = n_rows * spec.seq_len * (spec.out_bits / 8), cell_bytes = n_rows * spec.seq_len * 4;
-    rc = grow(&e->d_doc_off, &e->cap_doc_off, (n_docs + 1) * 8, true, &e->n_allocs);
-    if (rc == MBPE_OK && !out_on_device) {
-        rc = grow(&e->d_ids, &e->cap_ids, id_bytes, true, &e->n_allocs);
-        if (rc == MBPE_OK && len_out) rc = grow(&e->d_len, &e->cap_len, n_rows * 4, true, &e->n_allocs);
+    return enc_pack_tail(e, n_tokens, n_docs, token_bits, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out,
+                         n_tokens_out, aux, doc_tok_off_out, false);
+}
+
+// mbpe_encoder_encode_endmask after its checks: one piece, text and mask where they are
+int enc_endmask_body(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes, const uint8_t *mask_dev,
+                     const mbpe_single *singles, uint64_t n_singles, const uint64_t *doc_off, uint64_t n_docs,
+                     void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device, uint64_t *doc_tok_off_out,
+                     uint64_t *n_out, uint32_t *n_passes_out) {
+    if (doc_off && doc_tok_off_out) doc_tok_off_out[0] = 0;
+    ECHK(hipSetDevice(e->device));
+    e->last_ms = 0.f;
+    e->pass_tokens.clear();
+    if (n_bytes == 0) {
+        if (doc_off) {
+            int rc = grow(&e->d_doc_off, &e->cap_doc_off, (n_docs + 1) * 8, true, &e->n_allocs);
+            if (rc != MBPE_OK) return rc;
+            ECHK(hipMemsetAsync(e->d_doc_off, 0, (n_docs + 1) * 8, e->stream));
+            ECHK(hipStreamSynchronize(e->stream));
+            if (doc_tok_off_out) std::fill(doc_tok_off_out, doc_tok_off_out + n_docs + 1, 0);
+        }
+        return MBPE_OK;
     }
-    mbpe_pack_aux d_aux = aux ? *aux : mbpe_pack_aux{};
-    if (rc == MBPE_OK && aux && !out_on_device) {
-        if (aux->labels) { rc = grow(&e->d_labels, &e->cap_labels, id_bytes, true, &e->n_allocs); d_aux.labels = e->d_labels; }
-        if (rc == MBPE_OK && aux->pos) { rc = grow(&e->d_pos, &e->cap_pos, cell_bytes, true, &e->n_allocs); d_aux.pos = e->d_pos; }
-        if (rc == MBPE_OK && aux->seg) { rc = grow(&e->d_seg, &e->cap_seg, cell_bytes, true, &e->n_allocs); d_aux.seg = e->d_seg; }
+    uint64_t limit = e->piece_bytes;                              // the rule of mbpe_encoder_encode
+    if (limit == 0) {
+        limit = e->cap_cand / 4;
+        if (n_bytes > limit) {
+            size_t free_b = 0, total_b = 0;
+            ECHK(hipMemGetInfo(&free_b, &total_b));
+            const uint64_t avail = (uint64_t)free_b + enc_held(e);
+            limit = std::max<uint64_t>((avail - avail / 16) / kPieceCost, limit);
+        }
     }
+    if (n_bytes > limit)
+        return fail(MBPE_ERR_OOM, "mbpe_encoder_encode_endmask: the text has " + std::to_string(n_bytes) +
+                                      " bytes, more than one piece may hold (" + std::to_string(limit) +
+                                      "; option \"piece_bytes\"), and a mask on the device is not cut into pieces");
+    e->singles.clear();
+    for (uint64_t k = 0; k < n_singles; ++k) e->singles.push_back({singles[k].start, singles[k].len, singles[k].id, 0});
+    const uint64_t one[2] = {0, n_bytes};
+    EncCall a = {text_dev, 1, one, tokens_out, cap, token_bits, out_on_device, nullptr, true};
+    a.mask_dev = mask_dev;
+    a.doc_off = doc_off;
+    a.n_docs = n_docs;
+    a.doc_tok_off_out = doc_tok_off_out;
+    uint64_t n = 0;
+    uint32_t passes = 0;
+    bool small = false;
+    const int rc = run_piece(e, a, Piece{0, 1}, 0, &n, &passes, &small);
     if (rc != MBPE_OK) return rc;
-    ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
-    const PackSrc src = {e->d_flat, e->d_doc_off, n_docs, n_tokens, token_bits};
-    const PackDst dst = {out_on_device ? ids_out : e->d_ids, out_on_device || !len_out ? len_out : e->d_len, n_rows};
-    ECHK(hipEventRecord(e->ev0, e->stream));
-    if (aux) pack_launch_aux(e->stream, src, spec, dst, d_aux);
-    else pack_launch(e->stream, src, spec, dst);
-    ECHK(hipEventRecord(e->ev1, e->stream));
-    ECHK(hipStreamSynchronize(e->stream));
-    ECHK(hipGetLastError());
-    ECHK(hipEventElapsedTime(&e->pack_ms, e->ev0, e->ev1));
-    e->last_ms += e->pack_ms;
-    if (!out_on_device) {
-        ECHK(hipMemcpyAsync(ids_out, e->d_ids, id_bytes, hipMemcpyDeviceToHost, e->stream));
-        if (len_out) ECHK(hipMemcpyAsync(len_out, e->d_len, n_rows * 4, hipMemcpyDeviceToHost, e->stream));
-        if (aux && aux->labels) ECHK(hipMemcpyAsync(aux->labels, e->d_labels, id_bytes, hipMemcpyDeviceToHost, e->stream));
-        if (aux && aux->pos) ECHK(hipMemcpyAsync(aux->pos, e->d_pos, cell_bytes, hipMemcpyDeviceToHost, e->stream));
-        if (aux && aux->seg) ECHK(hipMemcpyAsync(aux->seg, e->d_seg, cell_bytes, hipMemcpyDeviceToHost, e->stream));
-        ECHK(hipStreamSynchronize(e->stream));
+    *n_out = n;
+    if (n_passes_out) *n_passes_out = passes;
+    if (small) return fail(MBPE_ERR_ARG, "tokens_out too small");
+    return MBPE_OK;
+}
+
+// the checks of the two endmask calls that need neither encoder nor device
+int enc_endmask_check(const char *who, uint64_t n_bytes, const mbpe_single *singles, uint64_t n_singles,
+                      const uint64_t *doc_off, uint64_t n_docs, uint32_t token_bits) {
+    const std::string w(who);
+    if (token_bits != 16 && token_bits != 32) return fail(MBPE_ERR_ARG, w + ": token_bits must be 16 or 32");
+    if ((!singles && n_singles) || (!doc_off && n_docs)) return fail(MBPE_ERR_ARG, w + ": NULL argument");
+    uint64_t end = 0;
+    for (uint64_t k = 0; k < n_singles; ++k) {
+        const mbpe_single &g = singles[k];
+        if (g.len == 0 || g.start > n_bytes || g.len > n_bytes - g.start)
+            return fail(MBPE_ERR_ARG, w + ": single " + std::to_string(k) + " is empty or out of range");
+        if (g.start < end) return fail(MBPE_ERR_ARG, w + ": singles must be ascending and disjoint");
+        end = g.start + g.len;
+        if (g.id >= kDrop) return fail(MBPE_ERR_ARG, w + ": token id of a single does not fit 31 bits");
+        if (token_bits == 16 && g.id >= 65536u)
+            return fail(MBPE_ERR_VOCAB, w + ": token id " + std::to_string(g.id) + " of a single does not fit 16 bits");
     }
+    for (uint64_t i = 0; i < n_docs; ++i)
+        if (doc_off[i + 1] < doc_off[i]) return fail(MBPE_ERR_ARG, w + ": doc_off must be ascending");
+    if (n_docs && doc_off[n_docs] > n_bytes) return fail(MBPE_ERR_ARG, w + ": doc_off must not exceed n_bytes");
     return MBPE_OK;
 }
 
@@ -805,7 +979,7 @@ void mbpe_encoder_destroy(mbpe_encoder *e) {
     (void)hipFree(e->span_b); (void)hipFree(e->span_off); (void)hipFree(e->d_res); (void)hipFree(e->d_singles);
     (void)hipFree(e->d_nul); (void)hipFree(e->d_ends); (void)hipFree(e->d_flat); (void)hipFree(e->d_doc_off);
     (void)hipFree(e->d_ids); (void)hipFree(e->d_len); (void)hipFree(e->d_labels); (void)hipFree(e->d_pos);
-    (void)hipFree(e->d_seg);
+    (void)hipFree(e->d_seg); (void)hipFree(e->d_doc_pos);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -891,6 +1065,79 @@ int mbpe_encoder_encode_batch(mbpe_encoder *e, const uint8_t *text, uint64_t n_b
                               int out_on_device, uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out) {
     return enc_batch(e, text, n_bytes, text_on_device, chunk_off, n_chunks, doc_chunk_off, n_docs, spec, ids_out, cap_rows,
                      out_on_device, len_out, n_rows_out, n_tokens_out, nullptr, nullptr);
+}
+
+int mbpe_encoder_encode_endmask(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes, const uint8_t *endmask_dev,
+                                const mbpe_single *singles, uint64_t n_singles, const uint64_t *doc_off, uint64_t n_docs,
+                                void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device,
+                                uint64_t *doc_tok_off_out, uint64_t *n_out, uint32_t *n_passes_out) {
+    static_assert(sizeof(mbpe_single) == sizeof(SingleChunk), "mbpe.h and k_enc_single");
+    if (n_out) *n_out = 0;
+    if (n_passes_out) *n_passes_out = 0;
+    int rc = enc_endmask_check("mbpe_encoder_encode_endmask", n_bytes, singles, n_singles, doc_off, n_docs, token_bits);
+    if (rc != MBPE_OK) return rc;
+    if (!e || !n_out || ((!text_dev || !endmask_dev) && n_bytes))
+        return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_endmask: NULL argument");
+    if ((uintptr_t)endmask_dev & 3) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_endmask: the mask must be 4-byte aligned");
+    if (token_bits == 16 && 256ull + e->n_merges > 65536ull)
+        return fail(MBPE_ERR_VOCAB, "token_bits 16 with more than 65,536 token ids");
+    if (n_docs == 0) doc_off = nullptr;
+    try {
+        return enc_endmask_body(e, text_dev, n_bytes, endmask_dev, singles, n_singles, doc_off, n_docs, tokens_out, cap,
+                                token_bits, out_on_device, doc_tok_off_out, n_out, n_passes_out);
+    } catch (const std::bad_alloc &) {
+        return fail(MBPE_ERR_OOM, "mbpe_encoder_encode_endmask: host allocation failed");
+    }
+}
+
+int mbpe_encoder_encode_batch_endmask(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
+                                      const uint8_t *endmask_dev, const mbpe_single *singles, uint64_t n_singles,
+                                      const uint64_t *doc_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
+                                      uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                                      uint64_t *n_tokens_out, const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out) {
+    const char *who = "mbpe_encoder_encode_batch_endmask";
+    if (n_rows_out) *n_rows_out = 0;
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!spec || !doc_off || !n_rows_out) return fail(MBPE_ERR_ARG, std::string(who) + ": NULL argument");
+    int rc = pack_check_spec(spec, spec->out_bits == 16 ? 16 : 32);
+    if (rc != MBPE_OK) return rc;
+    const uint32_t token_bits = spec->out_bits == 16 ? 16 : 32;
+    rc = enc_endmask_check(who, n_bytes, singles, n_singles, doc_off, n_docs, token_bits);
+    if (rc != MBPE_OK) return rc;
+    if (doc_off[0] != 0 || doc_off[n_docs] != n_bytes)
+        return fail(MBPE_ERR_ARG, std::string(who) + ": doc_off must start at 0 and end at n_bytes");
+    if (!e || ((!text_dev || !endmask_dev) && n_bytes)) return fail(MBPE_ERR_ARG, std::string(who) + ": NULL argument");
+    if ((uintptr_t)endmask_dev & 3) return fail(MBPE_ERR_ARG, std::string(who) + ": the mask must be 4-byte aligned");
+    if (spec->out_bits == 16 && 256ull + e->n_merges > 65536ull)
+        return fail(MBPE_ERR_VOCAB, "out_bits 16 with more than 65,536 token ids");
+    if (ids_out && out_on_device &&
+        ((uint64_t)(uintptr_t)ids_out % (spec->out_bits / 8) || (uint64_t)(uintptr_t)len_out % 4))
+        return fail(MBPE_ERR_ARG, "ids_out or len_out is not aligned to its elements");
+    if (aux) {
+        rc = pack_check_aux(*spec, aux, nullptr, n_docs, ids_out, out_on_device);
+        if (rc != MBPE_OK) return rc;
+    }
+    try {
+        ECHK(hipSetDevice(e->device));
+        rc = grow(&e->d_flat, &e->cap_flat, std::max<uint64_t>(n_bytes, 1) * (token_bits / 8), true, &e->n_allocs);
+        if (rc != MBPE_OK) return rc;
+        e->pack_ms = 0.f;
+        // the offsets stay on the device; the host sees them where it asks for them, or where a document could be too
+        // long for pos (only a text of 2^32 bytes or more)
+        const bool to_host = doc_tok_off_out || (aux && n_bytes + 2 >= (1ull << 32));
+        e->doc_tok.assign(n_docs + 1, 0);
+        uint64_t n_tokens = 0;
+        rc = enc_endmask_body(e, text_dev, n_bytes, endmask_dev, singles, n_singles, doc_off, n_docs, e->d_flat, n_bytes,
+                              token_bits, 1, to_host ? e->doc_tok.data() : nullptr, &n_tokens, nullptr);
+        if (rc != MBPE_OK) return rc;
+        if (aux && to_host) rc = pack_check_aux(*spec, aux, e->doc_tok.data(), n_docs, nullptr, 0);
+        if (rc != MBPE_OK) return rc;
+        rc = enc_pack_tail(e, n_tokens, n_docs, token_bits, *spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out,
+                           n_tokens_out, aux, doc_tok_off_out, true);
+        return rc;
+    } catch (const std::bad_alloc &) {
+        return fail(MBPE_ERR_OOM, std::string(who) + ": host allocation failed");
+    }
 }
 
 int mbpe_encoder_pack_ms(const mbpe_encoder *e, float *ms_out) {

@@ -67,7 +67,9 @@ void usage() {
                  "  --device INT                HIP device used for training (default 0)\n"
                  "  --device-encode             When encoding, apply the merges on the HIP device (--device)\n"
                  "  --device-decode             When decoding, expand the tokens on the HIP device (--device)\n"
-                 "  --device-split              When training with gpt2 or gpt4, split the text on the HIP device (--device)\n";
+                 "  --device-split              When training with gpt2 or gpt4, split the text on the HIP device (--device);\n"
+                 "                              when encoding, only together with --device-encode: the text is cut at the\n"
+                 "                              special tokens and split on the device too (without it: no effect)\n";
 }
 
 }  // namespace
@@ -182,6 +184,7 @@ int main(int argc, char *argv[]) {
             std::vector<Token> encoded(input.size() + 1);
             uint64_t n = 0;
             const uint8_t *in = reinterpret_cast<const uint8_t *>(input.data());
+            if (device_encode && device_split) mbpe_tok_set_encode_split(rt, 1);
             const int erc = device_encode
                                 ? mbpe_tok_encode_device(rt, in, input.size(), verbose, device, encoded.data(), encoded.size(), &n)
                                 : mbpe_tok_encode(rt, in, input.size(), verbose, encoded.data(), encoded.size(), &n);

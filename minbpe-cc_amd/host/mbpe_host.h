@@ -65,9 +65,12 @@ public:
     // The match loop over n_spans stretches [spans[2 k], spans[2 k + 1]) (ascending, disjoint) of a text of n bytes,
     // each matched from its start on its own subject [a, min(b + 1, n)) by up to n_threads threads; `sub` holds the
     // text from byte `origin` on.  last_bytes receives, ascending, the last byte of every match.  MBPE_ERR_SPLIT_GAP
-    // when the matches of a stretch do not tile it.  (csrc/split.hip: the host spans of the device split)
+    // when the matches of a stretch do not tile it.  end_is_cut (optional, one flag per stretch): the stretch ends
+    // where another text begins (mbpe_splitter_split_docs) and its subject is [a, b).
+    // (csrc/split.hip: the host spans of the device split)
     int split_spans(const uint8_t *sub, uint64_t origin, uint64_t n, const uint64_t *spans, uint64_t n_spans,
-                    unsigned n_threads, std::vector<uint64_t> *last_bytes, std::string *err) const;
+                    unsigned n_threads, std::vector<uint64_t> *last_bytes, std::string *err,
+                    const uint8_t *end_is_cut = nullptr) const;
     bool has_pattern() const { return code_ != nullptr; }
     const std::string &pattern() const { return pattern_; }
 

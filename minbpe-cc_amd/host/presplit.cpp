@@ -281,7 +281,8 @@ int Splitter::split(const uint8_t *text, uint64_t n, std::vector<uint64_t> *star
 }
 
 int Splitter::split_spans(const uint8_t *sub, uint64_t origin, uint64_t n, const uint64_t *spans, uint64_t n_spans,
-                          unsigned n_threads, std::vector<uint64_t> *last_bytes, std::string *err) const {
+                          unsigned n_threads, std::vector<uint64_t> *last_bytes, std::string *err,
+                          const uint8_t *end_is_cut) const {
     last_bytes->clear();
     if (!n_spans) return MBPE_OK;
     if (!code_) { *err = "split_spans: no pattern"; return MBPE_ERR_ARG; }
@@ -309,7 +310,8 @@ int Splitter::split_spans(const uint8_t *sub, uint64_t origin, uint64_t n, const
             const uint64_t a = spans[2 * i], b = spans[2 * i + 1];
             // No match that starts before b crosses b (t[b - 1] is a letter or digit and t[b] whitespace, or b is
             // the end of the text), and no decision reads further than t[b]: the subject [a, min(b + 1, n)) is enough
-            const uint64_t len = std::min(b + 1, n) - a;
+            // -- unless b is a cut (end_is_cut): there another text begins, and the subject ends at b
+            const uint64_t len = (end_is_cut && end_is_cut[i] ? b : std::min(b + 1, n)) - a;
             starts.clear();
             ends.clear();
             size_t offset = 0;

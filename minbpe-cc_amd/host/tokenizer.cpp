@@ -23,6 +23,23 @@ Tokenizer::Tokenizer() {}
 Tokenizer::~Tokenizer() {
     drop_decoder();
     drop_encoder();
+    drop_splitter();
+}
+
+void Tokenizer::drop_splitter() {
+    if (dev_splitter_) mbpe_splitter_destroy(dev_splitter_);
+    dev_splitter_ = nullptr;
+    dev_splitter_device_ = -1;
+}
+
+mbpe_splitter *Tokenizer::device_splitter(int device) {
+    if (!dev_splitter_ || dev_splitter_device_ != device) {
+        drop_splitter();
+        const int rc = mbpe_splitter_create(device, pattern_.c_str(), &dev_splitter_);
+        if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());   // MBPE_ERR_ARG for a custom pattern
+        dev_splitter_device_ = device;
+    }
+    return dev_splitter_;
 }
 
 void Tokenizer::drop_encoder() {
@@ -300,9 +317,86 @@ void Tokenizer::append_chunks(const std::string &text, bool verbose, std::string
     }
 }
 
+int Tokenizer::split_on_device(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
+                               DeviceSplit *out) {
+    mbpe_splitter *sp = device_splitter(device);
+    const uint64_t base = n_docs ? doc_off[0] : 0;
+    out->doc_off.resize(n_docs + 1);
+    for (uint64_t i = 0; i <= n_docs; ++i) out->doc_off[i] = n_docs ? doc_off[i] - base : 0;
+    out->n_bytes = out->doc_off[n_docs];
+    const char *t = text + base;
+    std::string names;
+    std::vector<uint64_t> name_off{0};
+    for (const auto &kv : special_tokens_) {
+        names += kv.first;
+        name_off.push_back(names.size());
+    }
+    uint64_t n_chunks = 0, n_ranges = 0;
+    int rc = mbpe_splitter_split_docs(sp, reinterpret_cast<const uint8_t *>(t), out->n_bytes, 0, out->doc_off.data(), n_docs,
+                                      reinterpret_cast<const uint8_t *>(names.data()), name_off.data(),
+                                      static_cast<uint32_t>(special_tokens_.size()), nullptr, nullptr, 0, &n_ranges,
+                                      &n_chunks);
+    if (rc != MBPE_OK) return rc;
+    const mbpe_split_range *ranges = nullptr;
+    rc = mbpe_splitter_ranges(sp, &ranges, &n_ranges);
+    if (rc == MBPE_OK) rc = mbpe_splitter_endmask(sp, &out->d_mask, nullptr, &out->d_text);
+    if (rc != MBPE_OK) return rc;
+    // a taken occurrence is its special id; a NUL-led part is one token when std::stoi parses its remainder (:86-93)
+    out->singles.clear();
+    for (uint64_t k = 0; k < n_ranges; ++k) {
+        const mbpe_split_range &r = ranges[k];
+        if (r.name != MBPE_SPLIT_RAW) {
+            out->singles.push_back({r.start, r.len, special_tokens_[r.name].second, 0});
+            continue;
+        }
+        try {
+            const int id = std::stoi(std::string(t + r.start + 1, r.len - 1));
+            out->singles.push_back({r.start, r.len, static_cast<Token>(id), 0});
+        } catch (...) {                                          // stays bytes, as one chunk
+        }
+    }
+    if (verbose) {                                               // the lines of append_chunks, document by document
+        uint64_t k = 0;
+        for (uint64_t d = 0; d < n_docs; ++d) {
+            const uint64_t s = out->doc_off[d], e = out->doc_off[d + 1];
+            if (e == s) continue;
+            std::vector<std::string> parts;
+            uint64_t cursor = s;
+            for (; k < n_ranges && ranges[k].start < e; ++k) {
+                if (ranges[k].name == MBPE_SPLIT_RAW) continue;  // (a part like any other: printed as the text it is)
+                if (ranges[k].start > cursor) parts.push_back(std::string(t + cursor, ranges[k].start - cursor));
+                parts.push_back(std::string(1, '\0') + std::to_string(special_tokens_[ranges[k].name].second));
+                cursor = ranges[k].start + ranges[k].len;
+            }
+            if (cursor < e) parts.push_back(std::string(t + cursor, e - cursor));
+            std::cout << "Splitting input text into " << parts.size() << " parts\n";
+            for (const auto &part : parts) {
+                bool is_special = part.size() > 0 && part[0] == '\0';
+                std::cout << "Part: \"" << part << "\" special: " << is_special << "\n";
+            }
+        }
+    }
+    return MBPE_OK;
+}
+
 // :653-722.  device < 0: internal_encode on the host (below); device >= 0: on that HIP device (mbpe_encoder_encode,
 // with an encoder that is kept until the merges change)
-std::vector<Token> Tokenizer::encode(const std::string &text, bool verbose, int device) {
+std::vector<Token> Tokenizer::encode(const std::string &text, bool verbose, int device, bool device_split) {
+    if (device >= 0 && device_split) {
+        const uint64_t doc_off[2] = {0, text.size()};
+        DeviceSplit ds;
+        int rc = split_on_device(text.data(), doc_off, 1, verbose, device, &ds);
+        if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
+        mbpe_encoder *enc = device_encoder(device);
+        std::vector<Token> out(text.size());
+        uint64_t n = 0;
+        rc = mbpe_encoder_encode_endmask(enc, ds.d_text, text.size(), ds.d_mask, ds.singles.data(), ds.singles.size(),
+                                         nullptr, 0, out.data(), out.size(), 32, 0, nullptr, &n, nullptr);
+        if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
+        out.resize(n);
+        if (verbose) std::cout << "Encoded input text (length " << text.length() << ") to " << out.size() << " tokens\n";
+        return out;
+    }
     // the chunks, as one byte buffer + offsets
     std::string buf;
     std::vector<uint64_t> off{0};
@@ -343,7 +437,21 @@ void Tokenizer::batch_chunks(const char *text, const uint64_t *doc_off, uint64_t
 
 int Tokenizer::encode_batch_flat(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
                                  Token *tokens_out, uint64_t cap, uint64_t *n_out, uint64_t *buf_bytes_out,
-                                 std::vector<uint64_t> *doc_tok_off) {
+                                 std::vector<uint64_t> *doc_tok_off, bool device_split) {
+    if (device_split) {
+        DeviceSplit ds;
+        int rc = split_on_device(text, doc_off, n_docs, verbose, device, &ds);
+        if (rc != MBPE_OK) return rc;
+        if (buf_bytes_out) *buf_bytes_out = ds.n_bytes;
+        mbpe_encoder *enc = device_encoder(device);
+        std::vector<uint64_t> tok_off(n_docs + 1, 0);
+        rc = mbpe_encoder_encode_endmask(enc, ds.d_text, ds.n_bytes, ds.d_mask, ds.singles.data(), ds.singles.size(),
+                                         ds.doc_off.data(), n_docs, tokens_out, cap, 32, 0, tok_off.data(), n_out, nullptr);
+        if (rc != MBPE_OK) return rc;
+        doc_tok_off->swap(tok_off);
+        if (verbose) std::cout << "Encoded " << n_docs << " texts (length " << ds.n_bytes << ") to " << *n_out << " tokens\n";
+        return MBPE_OK;
+    }
     std::string buf;
     std::vector<uint64_t> off, first_chunk;
     batch_chunks(text, doc_off, n_docs, verbose, &buf, &off, &first_chunk);
@@ -362,7 +470,22 @@ int Tokenizer::encode_batch_flat(const char *text, const uint64_t *doc_off, uint
 int Tokenizer::encode_batch_packed(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
                                    const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
                                    uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out,
-                                   const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out) {
+                                   const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out, bool device_split) {
+    if (device_split) {
+        DeviceSplit ds;
+        int rc = split_on_device(text, doc_off, n_docs, verbose, device, &ds);
+        if (rc != MBPE_OK) return rc;
+        mbpe_encoder *enc = device_encoder(device);
+        uint64_t n_tokens = 0;
+        rc = mbpe_encoder_encode_batch_endmask(enc, ds.d_text, ds.n_bytes, ds.d_mask, ds.singles.data(), ds.singles.size(),
+                                               ds.doc_off.data(), n_docs, spec, ids_out, cap_rows, out_on_device, len_out,
+                                               n_rows_out, &n_tokens, aux, doc_tok_off_out);
+        if (n_tokens_out) *n_tokens_out = n_tokens;
+        if (rc == MBPE_OK && verbose)
+            std::cout << "Encoded " << n_docs << " texts (length " << ds.n_bytes << ") to " << n_tokens << " tokens in "
+                      << *n_rows_out << " rows\n";
+        return rc;
+    }
     std::string buf;
     std::vector<uint64_t> off, first_chunk;
     batch_chunks(text, doc_off, n_docs, verbose, &buf, &off, &first_chunk);
@@ -382,7 +505,8 @@ int Tokenizer::encode_batch_packed(const char *text, const uint64_t *doc_off, ui
     return rc;
 }
 
-std::vector<std::vector<Token>> Tokenizer::encode_batch(const std::vector<std::string> &texts, bool verbose, int device) {
+std::vector<std::vector<Token>> Tokenizer::encode_batch(const std::vector<std::string> &texts, bool verbose, int device,
+                                                        bool device_split) {
     std::string all;
     std::vector<uint64_t> doc_off{0};
     for (const auto &t : texts) {
@@ -394,7 +518,7 @@ std::vector<std::vector<Token>> Tokenizer::encode_batch(const std::vector<std::s
     std::vector<uint64_t> tok_off;
     uint64_t n = 0;
     const int rc = encode_batch_flat(all.data(), doc_off.data(), texts.size(), verbose, device, flat.data(), flat.size(),
-                                     &n, nullptr, &tok_off);
+                                     &n, nullptr, &tok_off, device_split);
     if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
     std::vector<std::vector<Token>> out(texts.size());
     for (size_t i = 0; i < texts.size(); ++i) out[i].assign(flat.begin() + tok_off[i], flat.begin() + tok_off[i + 1]);
@@ -495,6 +619,7 @@ bool Tokenizer::load(const std::string &path, bool verbose) {
     }
     drop_decoder();
     drop_encoder();
+    drop_splitter();                                            // (the pattern may change)
     merges_lookup_.clear();
     merges_.clear();
     initialize_vocab();
@@ -638,6 +763,12 @@ int mbpe_tok_train_split_device(mbpe_tokenizer *t, const uint8_t *text, uint64_t
     }
 }
 
+int mbpe_tok_set_encode_split(mbpe_tokenizer *t, int on_device) {
+    if (!t) return MBPE_ERR_ARG;
+    t->t->set_encode_split(on_device != 0);
+    return MBPE_OK;
+}
+
 int mbpe_tok_set_merges(mbpe_tokenizer *t, const uint32_t *merges, uint32_t n_merges) {
     if (!t || (!merges && n_merges)) return MBPE_ERR_ARG;
     std::vector<mbpe_host::TokenPair> m;
@@ -683,7 +814,8 @@ int mbpe_tok_encode_device(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, i
                            uint32_t *tokens_out, uint64_t cap, uint64_t *n_out) {
     if (!t || (!text && n) || !n_out || device_id < 0) return MBPE_ERR_ARG;
     try {
-        auto enc = t->t->encode(std::string(reinterpret_cast<const char *>(text), n), verbose != 0, device_id);
+        auto enc = t->t->encode(std::string(reinterpret_cast<const char *>(text), n), verbose != 0, device_id,
+                                t->t->encode_split());
         *n_out = enc.size();
         if (!tokens_out) return MBPE_OK;
         if (cap < enc.size()) { mbpe_host::set_last_error("tokens_out too small"); return MBPE_ERR_ARG; }
@@ -712,7 +844,8 @@ int mbpe_tok_encode_batch_device(mbpe_tokenizer *t, const uint8_t *text, const u
         // tokens_out, cap and n_out go to the encoder as they are: a query copies no token, a cap too small writes none
         std::vector<uint64_t> tok_off;
         const int rc = t->t->encode_batch_flat(reinterpret_cast<const char *>(text), doc_off, n_docs, verbose != 0,
-                                               device_id, tokens_out, cap, n_out, nullptr, &tok_off);
+                                               device_id, tokens_out, cap, n_out, nullptr, &tok_off,
+                                               t->t->encode_split());
         if (rc != MBPE_OK) return rc;
         if (doc_tok_off_out) memcpy(doc_tok_off_out, tok_off.data(), tok_off.size() * sizeof(uint64_t));
         return MBPE_OK;
@@ -739,7 +872,8 @@ int mbpe_tok_encode_batch_packed_device(mbpe_tokenizer *t, const uint8_t *text, 
         if (doc_off[i + 1] < doc_off[i]) { mbpe_host::set_last_error("doc_off must be ascending"); return MBPE_ERR_ARG; }
     try {
         return t->t->encode_batch_packed(reinterpret_cast<const char *>(text), doc_off, n_docs, verbose != 0, device_id,
-                                         spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out);
+                                         spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out,
+                                         nullptr, nullptr, t->t->encode_split());
     } catch (const mbpe_host::CodedError &e) {      // mbpe_encoder_create failed: its own code
         mbpe_host::set_last_error(e.what());
         return e.code;
@@ -764,7 +898,7 @@ int mbpe_tok_encode_batch_aux_device(mbpe_tokenizer *t, const uint8_t *text, con
     try {
         return t->t->encode_batch_packed(reinterpret_cast<const char *>(text), doc_off, n_docs, verbose != 0, device_id,
                                          spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
-                                         doc_tok_off_out);
+                                         doc_tok_off_out, t->t->encode_split());
     } catch (const mbpe_host::CodedError &e) {      // mbpe_encoder_create failed: its own code
         mbpe_host::set_last_error(e.what());
         return e.code;

@@ -36,22 +36,31 @@ public:
     // CodedError(MBPE_ERR_ARG): there is no silent return to the host split
     void train(const std::string &text, int vocab_size, CONFLICT_RESOLUTION conflict_resolution, bool verbose,
                int device = 0, bool device_split = false);
-    // :653-722; device >= 0 runs internal_encode (:325-377) on that HIP device instead of the host
-    std::vector<Token> encode(const std::string &text, bool verbose, int device = -1);
+    // :653-722; device >= 0 runs internal_encode (:325-377) on that HIP device instead of the host.
+    // device_split (with device >= 0, here and in the batch calls below): the text is also cut at the special tokens
+    // and split into chunks on the device (mbpe_splitter_split_docs with a splitter that is kept), and the encoder
+    // reads the splitter's copy of the text and its end mask in place (mbpe_encoder_encode_endmask): one upload, no
+    // second buffer.  Same tokens.  A tokenizer whose pattern is not gpt2 / gpt4 throws CodedError(MBPE_ERR_ARG)
+    std::vector<Token> encode(const std::string &text, bool verbose, int device = -1, bool device_split = false);
     // encode() of every text, [i] == encode(texts[i], false, -1): the chunks of all texts go to HIP device `device`
     // in one mbpe_encoder_encode, whose per-chunk token offsets are summed per text
-    std::vector<std::vector<Token>> encode_batch(const std::vector<std::string> &texts, bool verbose, int device);
+    std::vector<std::vector<Token>> encode_batch(const std::vector<std::string> &texts, bool verbose, int device,
+                                                 bool device_split = false);
     // the same over one buffer: n_docs + 1 ascending offsets.  tokens_out / cap / n_out go to mbpe_encoder_encode as
     // they are (NULL: query), whose code is returned; doc_tok_off receives n_docs + 1 token offsets when it is MBPE_OK
     int encode_batch_flat(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
                           Token *tokens_out, uint64_t cap, uint64_t *n_out, uint64_t *buf_bytes_out,
-                          std::vector<uint64_t> *doc_tok_off);
+                          std::vector<uint64_t> *doc_tok_off, bool device_split = false);
     // the same documents as one id matrix (mbpe_encoder_encode_batch; with aux, mbpe_encoder_encode_batch_aux): spec,
     // ids_out .. doc_tok_off_out go to it as they are, its code is returned
     int encode_batch_packed(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
                             const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
                             uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out,
-                            const mbpe_pack_aux *aux = nullptr, uint64_t *doc_tok_off_out = nullptr);
+                            const mbpe_pack_aux *aux = nullptr, uint64_t *doc_tok_off_out = nullptr,
+                            bool device_split = false);
+    // what the mbpe_tok_encode*_device calls of the C-ABI pass as device_split (mbpe_tok_set_encode_split)
+    void set_encode_split(bool on) { encode_split_ = on; }
+    bool encode_split() const { return encode_split_; }
     // :725-751; device >= 0 expands the tokens on that HIP device (mbpe_decode_tokens) instead of the host loop
     std::string decode(const std::vector<Token> &tokens, bool verbose, int device = -1);
     // decode() of every token list, [i] == decode(docs[i], false, -1), in one mbpe_decode_batch on HIP device `device`
@@ -95,6 +104,18 @@ private:
     // other part (:664-704); without one, every part is a chunk (:706-709)
     void append_chunks(const std::string &text, bool verbose, std::string *buf, std::vector<uint64_t> *off) const;
     mbpe_encoder *device_encoder(int device);
+    void drop_splitter();
+    mbpe_splitter *device_splitter(int device);       // kept until another device is named or the tokenizer goes
+    // the device split of n_docs texts (doc_off relative to text): the splitter's text and mask on the device, and
+    // the ranges that are single tokens.  Prints the "Part:" lines of append_chunks with verbose
+    struct DeviceSplit {
+        const uint8_t *d_text = nullptr, *d_mask = nullptr;
+        std::vector<mbpe_single> singles;
+        std::vector<uint64_t> doc_off;                // rebased to 0
+        uint64_t n_bytes = 0;
+    };
+    int split_on_device(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
+                        DeviceSplit *out);
     mbpe_decoder *device_decoder(int device);
     void warn_invalid(const Token *tokens, uint64_t n) const;   // the warning of :734-737 for each such id, in order
 
@@ -111,6 +132,9 @@ private:
     int decoder_device_ = -1;
     mbpe_encoder *encoder_ = nullptr;      // lookup table and buffers of encode(..., device), kept until the merges change
     int encoder_device_ = -1;
+    mbpe_splitter *dev_splitter_ = nullptr;  // the device split of encode(..., device, device_split)
+    int dev_splitter_device_ = -1;
+    bool encode_split_ = false;
 };
 
 }  // namespace mbpe_host

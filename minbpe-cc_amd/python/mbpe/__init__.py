@@ -35,7 +35,8 @@ EXPORTS = [
     "mbpe_pack_tokens_aux", "mbpe_pack_cu_seqlens", "mbpe_encoder_encode_batch_aux",
     "mbpe_load_corpus_endmask", "mbpe_splitter_create", "mbpe_splitter_destroy", "mbpe_splitter_split",
     "mbpe_splitter_endmask", "mbpe_splitter_set_option", "mbpe_splitter_kernel_ms", "mbpe_splitter_alloc_count",
-    "mbpe_splitter_host_spans",
+    "mbpe_splitter_host_spans", "mbpe_splitter_split_docs", "mbpe_splitter_ranges", "mbpe_splitter_find_ms",
+    "mbpe_encoder_encode_endmask", "mbpe_encoder_encode_batch_endmask",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -43,7 +44,7 @@ TOK_EXPORTS = [
     "mbpe_tok_get_merges", "mbpe_tok_save", "mbpe_tok_load", "mbpe_tok_encode", "mbpe_tok_encode_device",
     "mbpe_tok_decode", "mbpe_tok_decode_device", "mbpe_tok_encode_batch_device", "mbpe_tok_decode_batch_device",
     "mbpe_tok_encode_batch_packed_device", "mbpe_tok_decode_padded_device", "mbpe_tok_encode_batch_aux_device",
-    "mbpe_tok_train_split_device",
+    "mbpe_tok_train_split_device", "mbpe_tok_set_encode_split",
 ]
 
 
@@ -217,6 +218,13 @@ def lib():
     L.mbpe_splitter_kernel_ms.argtypes = [vp, vp]
     L.mbpe_splitter_alloc_count.argtypes = [vp, vp]
     L.mbpe_splitter_host_spans.argtypes = [vp, vp, vp]
+    L.mbpe_splitter_split_docs.argtypes = [vp, vp, u64, i32, vp, u64, vp, vp, u32, vp, vp, u64, vp, vp]
+    L.mbpe_splitter_ranges.argtypes = [vp, vp, vp]
+    L.mbpe_splitter_find_ms.argtypes = [vp, vp]
+    L.mbpe_encoder_encode_endmask.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, u32, i32, vp, vp, vp]
+    L.mbpe_encoder_encode_batch_endmask.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, u64, i32, vp, vp, vp,
+                                                    vp, vp]
+    L.mbpe_tok_set_encode_split.argtypes = [vp, i32]
     L.mbpe_tok_set_merges.argtypes = [vp, vp, u32]
     L.mbpe_tok_get_merges.argtypes = [vp, vp, u32, vp]
     L.mbpe_tok_save.argtypes = [vp, ctypes.c_char_p, i32]
@@ -468,6 +476,18 @@ def pack_kernel_ms():
     return ms.value
 
 
+SINGLE = np.dtype([("start", np.uint64), ("len", np.uint64), ("id", np.uint32), ("pad", np.uint32)])   # mbpe_single
+SPLIT_RAW = 0xFFFFFFFF      # MBPE_SPLIT_RAW: the name of a range that is a NUL-led part
+
+
+def _singles(rows):
+    """rows (start, len, id) -> an array of mbpe_single."""
+    out = np.zeros(0 if rows is None else len(rows), dtype=SINGLE)
+    for k, (a, n, i) in enumerate([] if rows is None else rows):
+        out[k] = (a, n, i, 0)
+    return out
+
+
 class Encoder:
     """One mbpe_encoder: internal_encode (Tokenizer.h:325-377) on a HIP device with the lookup table, the stream and
     the work buffers kept between calls."""
@@ -621,6 +641,62 @@ class Encoder:
                                                    doc_tok_off.ctypes.data))
         self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
         return call.result(ids, lengths, arrays, doc_tok_off)
+
+    def encode_endmask(self, text_ptr, n_bytes, mask_ptr, singles=None, doc_off=None, dtype=np.uint32, out_ptr=None,
+                       cap=None, query=False):
+        """n_bytes of text in device memory at text_ptr with its end mask in device memory at mask_ptr, both read in
+        place (mbpe_encoder_encode_endmask; what Splitter.split_docs and Splitter.endmask give).  singles: rows
+        (start, len, id) of byte ranges that are one token each; doc_off: n_docs + 1 byte offsets at chunk boundaries.
+        -> (tokens of dtype uint32 or uint16, doc_tok_off or None); with out_ptr= (device memory for cap tokens; 32
+        bits: bit 31 = chunk end) or query=True the token count stands in place of the tokens."""
+        dtype = np.dtype(dtype)
+        sg = _singles(singles)
+        docs = None if doc_off is None else np.ascontiguousarray(doc_off, dtype=np.uint64)
+        n_docs = 0 if docs is None else len(docs) - 1
+        tok_off = None if docs is None else np.zeros(n_docs + 1, dtype=np.uint64)
+        n, passes = ctypes.c_uint64(), ctypes.c_uint32()
+        head = (self._h, _ptr(text_ptr), n_bytes, _ptr(mask_ptr), sg.ctypes.data if len(sg) else None, len(sg),
+                None if docs is None else docs.ctypes.data, n_docs)
+        tail = (dtype.itemsize * 8, 0 if out_ptr is None else 1, None if tok_off is None else tok_off.ctypes.data,
+                ctypes.byref(n), ctypes.byref(passes))
+        if query or out_ptr is not None:
+            _check(lib().mbpe_encoder_encode_endmask(*head, None if query else _ptr(out_ptr), 0 if query else cap, *tail))
+            self.n_passes = passes.value
+            return n.value, tok_off
+        out = np.zeros(max(n_bytes, 1) if cap is None else max(cap, 1), dtype=dtype)
+        _check(lib().mbpe_encoder_encode_endmask(*head, out.ctypes.data, n_bytes if cap is None else cap, *tail))
+        self.n_passes = passes.value
+        return out[:n.value].copy(), tok_off
+
+    def encode_batch_endmask(self, text_ptr, n_bytes, mask_ptr, singles, doc_off, *, seq_len, layout="padded",
+                             out_bits=32, pad_id=0, bos_id=None, eos_id=None, pad_left=False, trunc_left=False,
+                             labels=False, positions=False, segments=False, cu_seqlens=False, ignore_label=-100):
+        """encode_endmask and the pack kernel in one call (mbpe_encoder_encode_batch_endmask): the documents doc_off
+        describes as one id matrix -> (ids, lengths), or with any of labels / positions / segments / cu_seqlens the
+        dict of encode_batch_aux.  The documents' token offsets: self.doc_tok_off."""
+        spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
+        with_aux = labels or positions or segments or cu_seqlens
+        call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label) if with_aux else None
+        sg = _singles(singles)
+        docs = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        n_docs = len(docs) - 1
+        n_rows, n_tok = ctypes.c_uint64(), ctypes.c_uint64()
+        doc_tok_off = np.zeros(n_docs + 1, dtype=np.uint64)
+        head = (self._h, _ptr(text_ptr), n_bytes, _ptr(mask_ptr), sg.ctypes.data if len(sg) else None, len(sg),
+                docs.ctypes.data, n_docs, ctypes.byref(spec))
+        tail = (ctypes.byref(n_rows), ctypes.byref(n_tok))
+        fn = lib().mbpe_encoder_encode_batch_endmask
+        if spec.layout == PACK_PADDED:
+            n_rows.value = n_docs                     # known without a query
+        else:
+            aux = call.device(None, None, None) if call else None
+            _check(fn(*head, None, 0, 0, None, *tail, ctypes.byref(aux) if call else None, None))
+        ids, lengths = _matrix(n_rows.value, spec)
+        aux, arrays = call.host(n_rows.value) if call else (None, None)
+        _check(fn(*head, ids.ctypes.data if ids.size else None, len(ids), 0, lengths.ctypes.data if len(ids) else None,
+                  *tail, ctypes.byref(aux) if call else None, doc_tok_off.ctypes.data))
+        self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
+        return call.result(ids, lengths, arrays, doc_tok_off) if call else (ids, lengths)
 
     def pack_ms(self):
         """Device time of the pack kernel of the latest encode_batch (mbpe_encoder_pack_ms)."""
@@ -810,6 +886,50 @@ class Splitter:
         off = np.zeros(cap_chunks + 1, dtype=np.uint64)
         _check(lib().mbpe_splitter_split(self._h, ptr, n, on_dev, mask, off.ctypes.data, cap_chunks, ctypes.byref(count)))
         return off[:count.value + 1]
+
+    def split_docs(self, data=None, doc_off=None, names=(), mask_ptr=None, text_ptr=None, n_bytes=None, cap_ranges=None):
+        """Splits the documents data[doc_off[i]:doc_off[i + 1]] (host bytes, or n_bytes of device memory at text_ptr)
+        each on its own, around the occurrences of names (a list of bytes) and around NUL-led parts
+        (mbpe_splitter_split_docs) -> (number of chunks, ranges as int64 [n_ranges, 3] rows (start, len, name index or
+        SPLIT_RAW)).  The mask goes to mask_ptr (device memory) or stays in the splitter, see endmask().  cap_ranges:
+        the capacity handed to the library for the ranges (default: they are read from the splitter)."""
+        if text_ptr is None:
+            text = _u8(data)
+            self._keep = text
+            ptr, n, on_dev = (text.ctypes.data if len(text) else None), len(text), 0
+        else:
+            ptr, n, on_dev = ctypes.c_void_p(text_ptr), n_bytes, 1
+        docs = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        names = [bytes(x) for x in names]
+        name_off = np.zeros(len(names) + 1, dtype=np.uint64)
+        if names:
+            name_off[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8)
+        count, n_ranges = ctypes.c_uint64(), ctypes.c_uint64()
+        mask = None if mask_ptr is None else ctypes.c_void_p(mask_ptr)
+        rows = np.zeros(0 if cap_ranges is None else max(cap_ranges, 1), dtype=SINGLE)
+        rc = lib().mbpe_splitter_split_docs(self._h, ptr, n, on_dev, docs.ctypes.data, len(docs) - 1, blob.ctypes.data,
+                                            name_off.ctypes.data, len(names), mask,
+                                            None if cap_ranges is None else rows.ctypes.data, cap_ranges or 0,
+                                            ctypes.byref(n_ranges), ctypes.byref(count))
+        self.n_ranges = n_ranges.value
+        _check(rc)
+        if cap_ranges is None:
+            p, k = ctypes.c_void_p(), ctypes.c_uint64()
+            _check(lib().mbpe_splitter_ranges(self._h, ctypes.byref(p), ctypes.byref(k)))
+            rows = np.zeros(k.value, dtype=SINGLE)
+            if k.value:
+                ctypes.memmove(rows.ctypes.data, p, k.value * SINGLE.itemsize)
+        rows = rows[:n_ranges.value]
+        out = np.stack([rows["start"].astype(np.int64), rows["len"].astype(np.int64), rows["id"].astype(np.int64)],
+                       axis=1) if len(rows) else np.zeros((0, 3), dtype=np.int64)
+        return count.value, out
+
+    def find_ms(self):
+        """Device time of the latest split_docs call's search for the names (mbpe_splitter_find_ms)."""
+        ms = ctypes.c_float()
+        _check(lib().mbpe_splitter_find_ms(self._h, ctypes.byref(ms)))
+        return ms.value
 
     @staticmethod
     def mask_bytes(n_bytes):
@@ -1090,8 +1210,14 @@ class Tokenizer:
     def load(self, path, verbose=False):
         _check(lib().mbpe_tok_load(self._h, os.fsencode(path), int(verbose)))
 
-    def encode(self, data, device=None):
-        """device None: internal_encode on the host; an int: on that HIP device (mbpe_tok_encode_device)."""
+    def _encode_split(self, device_split):
+        _check(lib().mbpe_tok_set_encode_split(self._h, int(bool(device_split))))
+
+    def encode(self, data, device=None, device_split=False):
+        """device None: internal_encode on the host; an int: on that HIP device (mbpe_tok_encode_device).
+        device_split (here and in the batch calls; only with a device): the text is cut at the special tokens and split
+        into chunks on the device too (mbpe_tok_set_encode_split); same tokens, gpt2 / gpt4 patterns only."""
+        self._encode_split(device_split)
         text = _u8(data)
         n = ctypes.c_uint64()
         out = np.zeros(max(len(text), 1), dtype=np.uint32)
@@ -1103,8 +1229,9 @@ class Tokenizer:
                                                 out.ctypes.data, len(out), ctypes.byref(n)))
         return out[:n.value].copy()
 
-    def encode_batch(self, texts, device=0):
+    def encode_batch(self, texts, device=0, device_split=False):
         """encode() of every text in one device call (mbpe_tok_encode_batch_device) -> list of uint32 arrays."""
+        self._encode_split(device_split)
         parts = [bytes(_u8(t)) for t in texts]
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
         if parts:
@@ -1119,11 +1246,13 @@ class Tokenizer:
         return [out[int(a):int(b)].copy() for a, b in zip(tok_off[:-1], tok_off[1:])]
 
     def encode_batch_padded(self, texts, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
-                            pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None):
+                            pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
+                            device_split=False):
         """Every text split like encode(), encoded and packed in one device call
         (mbpe_tok_encode_batch_packed_device) -> (ids [n_rows, seq_len], lengths [n_rows]) as numpy arrays; with
         out_ptr= and len_ptr= (device memory for cap_rows rows) the matrix stays on the device and the row count is
         returned.  bos_id / eos_id may be special-token ids.  layout "packed" gives the MBPE_PACK_PACKED rows."""
+        self._encode_split(device_split)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         parts = [bytes(_u8(t)) for t in texts]
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
@@ -1149,10 +1278,11 @@ class Tokenizer:
     def encode_batch_aux(self, texts, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
                          pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
                          labels=False, positions=False, segments=False, cu_seqlens=False, ignore_label=-100,
-                         labels_ptr=None, pos_ptr=None, seg_ptr=None):
+                         labels_ptr=None, pos_ptr=None, seg_ptr=None, device_split=False):
         """encode_batch_padded plus labels, positions, segments and cu_seqlens (mbpe_tok_encode_batch_aux_device): its
         arguments and those of pack_tokens_aux, whose dict (or, with out_ptr=, row count) is returned.  The documents'
         token offsets of the call: self.doc_tok_off."""
+        self._encode_split(device_split)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label)
         parts = [bytes(_u8(t)) for t in texts]
