@@ -753,6 +753,18 @@ MBPE_API void            mbpe_split_free(mbpe_split *s);
 /* The split patterns of Tokenizer.h:59-60 ("gpt2", "gpt4"; "basic" = ""). */
 MBPE_API const char *mbpe_split_pattern(const char *encoder_name);
 
+/* What PCRE2 (the library and the options mbpe_presplit uses: PCRE2_UTF | PCRE2_UCP) says of every code point
+ * 0 .. 0x10FFFF, asked of it once per process on the first call:
+ *   cls_out       optional, 0x110000 / 16 words: 2 bits per code point, bits 2 * (cp & 15) and up of word cp >> 4:
+ *                 0 = \p{L}, 1 = \p{N}, 2 = \s, 3 = none of them (the surrogates read 3)
+ *   fold_cp_out, fold_to_out, cap_fold   optional: the code points >= 0x80 that match one of the letters
+ *                 s d m t l v e r under PCRE2_CASELESS (the gpt4 contractions), ascending, each with that letter
+ *   n_fold_out    optional: how many there are (MBPE_ERR_ARG when cap_fold is smaller and an array is given)
+ *   build_ms_out  optional: what building the table took, in milliseconds
+ * MBPE_ERR_REGEX when the library is missing or disagrees with the byte rule below 0x80. */
+MBPE_API int mbpe_split_unicode_table(uint32_t *cls_out, uint32_t *fold_cp_out, uint8_t *fold_to_out, uint32_t cap_fold,
+                                      uint32_t *n_fold_out, double *build_ms_out);
+
 /* ---- the gpt2 / gpt4 pre-split on the device ------------------------------ */
 
 /* A splitter: mbpe_presplit for the two built-in patterns as an object on HIP device `device_id` (csrc/split.hip,
@@ -838,6 +850,13 @@ MBPE_API int  mbpe_splitter_endmask(const mbpe_splitter *s, const uint8_t **endm
 
 /*   "max_span"   the longest stretch between two sync points that the device walks (default MBPE_SPLIT_MAX_SPAN, at
  *                least 1); longer ones go to the host.  Same results.
+ *   "unicode"    0 (default) or 1; any other value is MBPE_ERR_ARG.  1: stretches with bytes >= 0x80 are walked on the
+ *                device too, as long as every UTF-8 sequence in them is well-formed (Unicode Table 3-7): the rule then
+ *                reads scalar values, whose classes come from a table that PCRE2 itself fills once per process
+ *                (mbpe_split_unicode_table; 278,528 bytes on the device), and a line break or -- gpt2 -- any whitespace
+ *                but U+0020 in front of a non-whitespace character is a boundary as well.  A stretch with an
+ *                ill-formed sequence, one cut inside a sequence, and one longer than "max_span" bytes stay host spans.
+ *                Same results; mbpe_splitter_host_spans keeps its meaning.  MBPE_ERR_REGEX when PCRE2 cannot be asked.
  * The host spans are matched by up to MBPE_SPLIT_THREADS (environment; default 16) host threads, like mbpe_presplit. */
 MBPE_API int  mbpe_splitter_set_option(mbpe_splitter *s, const char *name, int64_t value);
 

@@ -99,6 +99,11 @@ MBPE_API int mbpe_tok_encode_batch_aux_device(mbpe_tokenizer *t, const uint8_t *
  * calls: there is no silent return to the host split.  Nothing else is affected. */
 MBPE_API int mbpe_tok_set_encode_split(mbpe_tokenizer *t, int on_device);
 
+/* The option "unicode" (mbpe_splitter_set_option) of the device splits this tokenizer makes: 0 (the default) or on.
+ * It applies to mbpe_tok_train_split_device and, while mbpe_tok_set_encode_split is on, to the mbpe_tok_encode*_device
+ * calls, whose kept splitter is re-configured, not re-created.  Same results; otherwise without effect. */
+MBPE_API int mbpe_tok_set_split_unicode(mbpe_tokenizer *t, int on);
+
 /* decode, Tokenizer.h:725-751.  bytes_out may be NULL to query the length. */
 MBPE_API int mbpe_tok_decode(mbpe_tokenizer *t, const uint32_t *tokens, uint64_t n, int verbose,
                              uint8_t *bytes_out, uint64_t cap, uint64_t *n_out);

@@ -11,6 +11,9 @@
 //   (host)           the listed spans through PCRE2 (presplit.cpp), their chunk ends uploaded
 //   k_split_patch    those chunk ends OR-ed into the mask
 //   k_mask_popcount  the number of chunks
+// With the option "unicode" the sync pass and the walk are k_split_sync_u and k_split_walk_u: the rule on scalar values,
+// classes from the table PCRE2 filled (split_rule.h), the second bitmap = the ill-formed bytes.  The default mode's two
+// kernels are untouched by it.
 // All positions are 64-bit.
 #include "hip_host.h"
 #include "split.h"
@@ -50,6 +53,30 @@ __global__ __launch_bounds__(kSplitThreads) void k_split_sync(const uint8_t *__r
             for (uint32_t k = 0; k < (uint32_t)(n - at); ++k) w[k >> 2] |= (uint32_t)t[at + k] << (8u * (k & 3u));
         }
         split_vec_bits(w, at ? t[at - 1] : (uint32_t)' ', &s, &h);
+    }
+    sync[v] = (uint16_t)(cut ? s | cut[v] : s);
+    hi[v] = (uint16_t)h;
+}
+
+// unicode mode: the same lane, the same 16 bytes; a lane that sees a byte >= 0x80 reads its neighbourhood as plain bytes.
+// hi = the ill-formed bitmap
+__global__ __launch_bounds__(kSplitThreads) void k_split_sync_u(const uint8_t *__restrict__ t, uint64_t n,
+                                                                uint64_t n_pieces, const uint16_t *__restrict__ cut,
+                                                                int pattern, const uint32_t *__restrict__ tab,
+                                                                uint16_t *__restrict__ sync,
+                                                                uint16_t *__restrict__ hi) {
+    const uint64_t v = (uint64_t)blockIdx.x * kSplitThreads + threadIdx.x;
+    if (v >= n_pieces) return;
+    const uint64_t at = v * kSplitVec;
+    uint32_t w[4] = {0u, 0u, 0u, 0u}, s = 0u, h = 0u;
+    if (at < n) {
+        if (n - at >= (uint64_t)kSplitVec) {
+            const uint4 q = *reinterpret_cast<const uint4 *>(t + at);
+            w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+        } else {
+            for (uint32_t k = 0; k < (uint32_t)(n - at); ++k) w[k >> 2] |= (uint32_t)t[at + k] << (8u * (k & 3u));
+        }
+        split_vec_bits_u(t, n, at, w, pattern, tab, &s, &h);
     }
     sync[v] = (uint16_t)(cut ? s | cut[v] : s);
     hi[v] = (uint16_t)h;
@@ -156,6 +183,26 @@ __global__ __launch_bounds__(kSplitThreads) void k_split_walk(const uint8_t *__r
     if (host) atomicAdd(ctl + kCtlHost, (unsigned long long)__popcll(host));
 }
 
+__global__ __launch_bounds__(kSplitThreads) void k_split_walk_u(const uint8_t *__restrict__ t, uint64_t n,
+                                                                const unsigned long long *__restrict__ sync,
+                                                                const unsigned long long *__restrict__ bad,
+                                                                const unsigned long long *__restrict__ cut,
+                                                                const unsigned long long *__restrict__ raw, uint64_t n_words,
+                                                                uint64_t max_span, int pattern,
+                                                                const uint32_t *__restrict__ tab, SplitFold fold,
+                                                                uint32_t *__restrict__ mask,
+                                                                unsigned long long *__restrict__ hostmark,
+                                                                unsigned long long *__restrict__ ctl) {
+    const uint64_t T = (uint64_t)blockIdx.x * kSplitThreads + threadIdx.x;
+    if (T >= n_words) return;
+    EndBits end = {mask, ~0ull, 0u};
+    const SplitCharStep step = {pattern, tab, fold};
+    const unsigned long long host = split_walk_block_with(t, n, sync, bad, cut, raw, T, max_span, step, end);
+    end.flush();
+    hostmark[T] = host;
+    if (host) atomicAdd(ctl + kCtlHost, (unsigned long long)__popcll(host));
+}
+
 // list[2 j], list[2 j + 1] = a host span and its end, in no particular order; cap = the spans the walk counted
 __global__ __launch_bounds__(kSplitThreads) void k_split_compact(const unsigned long long *__restrict__ sync,
                                                                  const unsigned long long *__restrict__ hostmark,
@@ -223,6 +270,9 @@ struct mbpe_splitter {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint64_t max_span = MBPE_SPLIT_MAX_SPAN;
+    bool unicode = false;                     // the option; the table is uploaded by the first call that needs it
+    uint32_t *d_tab = nullptr;
+    SplitFold fold = {};
     // buffers, grown on demand and kept
     uint8_t *d_text = nullptr;                // a host text's copy
     unsigned long long *d_sync = nullptr, *d_hi = nullptr, *d_hostmark = nullptr;
@@ -326,6 +376,16 @@ int split_run_passes(mbpe_splitter *s, const uint8_t *text, uint64_t n, int text
     if ((rc = grow(&s->d_hi, &s->cap_hi, n_words * 8, false, &s->n_allocs)) != MBPE_OK) return rc;
     if ((rc = grow(&s->d_hostmark, &s->cap_hostmark, n_words * 8, false, &s->n_allocs)) != MBPE_OK) return rc;
     if ((rc = grow(&s->d_mask, &s->cap_mask, mask_bytes, false, &s->n_allocs)) != MBPE_OK) return rc;
+    if (s->unicode && !s->d_tab) {
+        std::string err;
+        const mbpe_host::SplitUnicodeTable *tb = mbpe_host::split_unicode_table(&err);
+        if (!tb) return fail(MBPE_ERR_REGEX, err);
+        SCHK(hipMalloc(&s->d_tab, kSplitTableWords * 4));
+        ++s->n_allocs;
+        SCHK(hipMemcpy(s->d_tab, tb->cls.data(), kSplitTableWords * 4, hipMemcpyHostToDevice));
+        s->fold.n = tb->n_fold;
+        for (uint32_t k = 0; k < tb->n_fold; ++k) { s->fold.cp[k] = tb->fold_cp[k]; s->fold.to[k] = tb->fold_to[k]; }
+    }
     s->have_mask = false;
     s->last_text = d_text;
 
@@ -380,12 +440,21 @@ int split_run_passes(mbpe_splitter *s, const uint8_t *text, uint64_t n, int text
                            s->d_list + cuts.size(), (uint64_t)ranges->size(), n, s->d_raw);
     }
     const unsigned long long *d_cut = have_cuts ? s->d_cut : nullptr, *d_raw = have_raw ? s->d_raw : nullptr;
-    hipLaunchKernelGGL(k_split_sync, dim3(grid_for(n_words * 4)), dim3(kSplitThreads), 0, s->stream, d_text, n,
-                       n_words * 4, reinterpret_cast<const uint16_t *>(d_cut), reinterpret_cast<uint16_t *>(s->d_sync),
-                       reinterpret_cast<uint16_t *>(s->d_hi));
-    hipLaunchKernelGGL(k_split_walk, dim3(grid_for(n_words)), dim3(kSplitThreads), 0, s->stream, d_text, n, s->d_sync,
-                       s->d_hi, d_cut, d_raw, n_words, s->max_span, s->pattern, reinterpret_cast<uint32_t *>(s->d_mask),
-                       s->d_hostmark, s->d_ctl);
+    if (s->unicode) {
+        hipLaunchKernelGGL(k_split_sync_u, dim3(grid_for(n_words * 4)), dim3(kSplitThreads), 0, s->stream, d_text, n,
+                           n_words * 4, reinterpret_cast<const uint16_t *>(d_cut), s->pattern, s->d_tab,
+                           reinterpret_cast<uint16_t *>(s->d_sync), reinterpret_cast<uint16_t *>(s->d_hi));
+        hipLaunchKernelGGL(k_split_walk_u, dim3(grid_for(n_words)), dim3(kSplitThreads), 0, s->stream, d_text, n,
+                           s->d_sync, s->d_hi, d_cut, d_raw, n_words, s->max_span, s->pattern, s->d_tab, s->fold,
+                           reinterpret_cast<uint32_t *>(s->d_mask), s->d_hostmark, s->d_ctl);
+    } else {
+        hipLaunchKernelGGL(k_split_sync, dim3(grid_for(n_words * 4)), dim3(kSplitThreads), 0, s->stream, d_text, n,
+                           n_words * 4, reinterpret_cast<const uint16_t *>(d_cut), reinterpret_cast<uint16_t *>(s->d_sync),
+                           reinterpret_cast<uint16_t *>(s->d_hi));
+        hipLaunchKernelGGL(k_split_walk, dim3(grid_for(n_words)), dim3(kSplitThreads), 0, s->stream, d_text, n, s->d_sync,
+                           s->d_hi, d_cut, d_raw, n_words, s->max_span, s->pattern,
+                           reinterpret_cast<uint32_t *>(s->d_mask), s->d_hostmark, s->d_ctl);
+    }
     SCHK(hipGetLastError());
     SCHK(hipEventRecord(s->ev1, s->stream));
     unsigned long long ctl[kCtlWords] = {0, 0, 0, 0};
@@ -515,7 +584,7 @@ void mbpe_splitter_destroy(mbpe_splitter *s) {
     (void)hipFree(s->d_text); (void)hipFree(s->d_sync); (void)hipFree(s->d_hi); (void)hipFree(s->d_hostmark);
     (void)hipFree(s->d_mask); (void)hipFree(s->d_ctl); (void)hipFree(s->d_list);
     (void)hipFree(s->d_cut); (void)hipFree(s->d_raw); (void)hipFree(s->d_find); (void)hipFree(s->d_names);
-    (void)hipFree(s->d_first);
+    (void)hipFree(s->d_first); (void)hipFree(s->d_tab);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -525,6 +594,7 @@ void mbpe_splitter_destroy(mbpe_splitter *s) {
 int mbpe_splitter_set_option(mbpe_splitter *s, const char *name, int64_t value) {
     if (!s || !name) return fail(MBPE_ERR_ARG, "mbpe_splitter_set_option: NULL argument");
     if (!strcmp(name, "max_span") && value >= 1) { s->max_span = (uint64_t)value; return MBPE_OK; }
+    if (!strcmp(name, "unicode") && (value == 0 || value == 1)) { s->unicode = value == 1; return MBPE_OK; }
     return fail(MBPE_ERR_ARG, std::string("mbpe_splitter_set_option: unknown option or bad value: ") + name);
 }
 

@@ -69,7 +69,8 @@ void usage() {
                  "  --device-decode             When decoding, expand the tokens on the HIP device (--device)\n"
                  "  --device-split              When training with gpt2 or gpt4, split the text on the HIP device (--device);\n"
                  "                              when encoding, only together with --device-encode: the text is cut at the\n"
-                 "                              special tokens and split on the device too (without it: no effect)\n";
+                 "                              special tokens and split on the device too (without it: no effect)\n"
+                 "  --device-split-unicode      --device-split, with non-ASCII text split on the device as well\n";
 }
 
 }  // namespace
@@ -78,7 +79,7 @@ int main(int argc, char *argv[]) {
     std::string input_path, output_path, special_token_path, encoder = "gpt4", model_path = "./output.model";
     std::string conflict_resolution_str = "first";
     bool train = false, decode = false, encode = false, write_vocab = false, verbose = false, device_encode = false,
-         device_decode = false, device_split = false;
+         device_decode = false, device_split = false, split_unicode = false;
     int vocab_size = 512, device = 0;
 
     // option parsing (the reference uses CLI11, :93-133)
@@ -119,6 +120,7 @@ int main(int argc, char *argv[]) {
         else if (arg == "--device-encode") device_encode = true;
         else if (arg == "--device-decode") device_decode = true;
         else if (arg == "--device-split") device_split = true;
+        else if (arg == "--device-split-unicode") device_split = split_unicode = true;
         else if (arg == "-v" || arg == "--verbose") verbose = true;
         else { std::cerr << "The following argument was not expected: " << arg << "\n"; return 109; }
     }
@@ -162,6 +164,7 @@ int main(int argc, char *argv[]) {
         std::string input, err;
         if (load_file_to_string(input_path, &input, &err)) {
             if (verbose) std::cout << "Starting training...\n";
+            if (split_unicode) mbpe_tok_set_split_unicode(rt, 1);
             if ((device_split ? mbpe_tok_train_split_device : mbpe_tok_train)(
                     rt, reinterpret_cast<const uint8_t *>(input.data()), input.size(), (uint32_t)vocab_size,
                     conflict_resolution_str == "lexical" ? 1 : 0, verbose, device) != MBPE_OK) {
@@ -185,6 +188,7 @@ int main(int argc, char *argv[]) {
             uint64_t n = 0;
             const uint8_t *in = reinterpret_cast<const uint8_t *>(input.data());
             if (device_encode && device_split) mbpe_tok_set_encode_split(rt, 1);
+            if (split_unicode) mbpe_tok_set_split_unicode(rt, 1);
             const int erc = device_encode
                                 ? mbpe_tok_encode_device(rt, in, input.size(), verbose, device, encoded.data(), encoded.size(), &n)
                                 : mbpe_tok_encode(rt, in, input.size(), verbose, encoded.data(), encoded.size(), &n);

@@ -49,6 +49,20 @@ const char *split_pattern_for(const std::string &encoder);
 // hardware's threads and by one thread per MiB; at least 1
 unsigned split_thread_count(uint64_t n_bytes);
 
+// What PCRE2 says of every Unicode scalar value under the options of Splitter::compile, for the device split's
+// "unicode" mode (csrc/split_rule.h): cls = 2 bits per value (bits 2 (cp & 15) .. of word cp >> 4: 0 = \p{L}, 1 = \p{N},
+// 2 = \s, 3 = none of them; the surrogates read 3), fold = the values >= 0x80 that match one of s d m t l v e r under
+// PCRE2_CASELESS, each with that letter.  Asked of the library once per process, on the first call; nullptr with *err
+// set when the library is missing, disagrees with split_class below 0x80, or folds more than 8 values.
+struct SplitUnicodeTable {
+    std::vector<uint32_t> cls;
+    uint32_t n_fold = 0;
+    uint32_t fold_cp[8] = {0};
+    uint8_t fold_to[8] = {0};
+    double build_ms = 0.0;
+};
+const SplitUnicodeTable *split_unicode_table(std::string *err);
+
 // Compiled split pattern + match loop (Tokenizer.h:391-451, :506-540).
 class Splitter {
 public:

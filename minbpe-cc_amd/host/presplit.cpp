@@ -5,9 +5,11 @@
 // entry points used are declared by hand below.
 #include "mbpe.h"
 #include "mbpe_host.h"
+#include "../csrc/split_rule.h"
 
 #include <dlfcn.h>
 #include <algorithm>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -85,6 +87,120 @@ unsigned split_thread_count(uint64_t n_bytes) {
     const char *env = getenv("MBPE_SPLIT_THREADS");
     unsigned want = env ? (unsigned)atoi(env) : 16u;
     return std::max(1u, std::min({want, hw ? hw : 1u, (unsigned)std::min<uint64_t>(n_bytes >> 20, 1u << 20)}));
+}
+
+namespace {
+
+// every scalar value once, ascending, as UTF-8: the one subject all the table's patterns are matched against
+std::vector<uint8_t> all_scalar_values() {
+    std::vector<uint8_t> s;
+    s.reserve(4400000);
+    for (uint32_t cp = 0; cp < 0x110000u; ++cp) {
+        if (cp >= 0xD800u && cp < 0xE000u) continue;
+        if (cp < 0x80u) s.push_back((uint8_t)cp);
+        else if (cp < 0x800u) { s.push_back(0xC0u | (cp >> 6)); s.push_back(0x80u | (cp & 0x3Fu)); }
+        else if (cp < 0x10000u) {
+            s.push_back(0xE0u | (cp >> 12)); s.push_back(0x80u | ((cp >> 6) & 0x3Fu)); s.push_back(0x80u | (cp & 0x3Fu));
+        } else {
+            s.push_back(0xF0u | (cp >> 18)); s.push_back(0x80u | ((cp >> 12) & 0x3Fu));
+            s.push_back(0x80u | ((cp >> 6) & 0x3Fu)); s.push_back(0x80u | (cp & 0x3Fu));
+        }
+    }
+    return s;
+}
+
+// hit(cp) for every scalar value of the subject that `pattern` (one character per match, or runs of them) matches
+template <typename Hit>
+bool find_all(const char *pattern, uint32_t options, const std::vector<uint8_t> &subject, Hit hit, std::string *err) {
+    Pcre2Api &p = pcre2();
+    int errorcode = 0;
+    size_t erroroffset = 0;
+    void *code = p.compile(reinterpret_cast<const uint8_t *>(pattern), strlen(pattern), options, &errorcode,
+                           &erroroffset, nullptr);
+    if (!code) { *err = "PCRE2 pattern compilation failed: " + pcre2_message(errorcode); return false; }
+    p.jit_compile(code, kPCRE2_JIT_COMPLETE);
+    void *md = p.match_data_create_from_pattern(code, nullptr);
+    bool ok = md != nullptr;
+    if (!ok) *err = "PCRE2 match data creation failed.";
+    size_t offset = 0;
+    while (ok && offset < subject.size()) {
+        const int rc = p.match(code, subject.data(), subject.size(), offset, kPCRE2_NO_UTF_CHECK, md, nullptr);
+        if (rc == kPCRE2_ERROR_NOMATCH) break;
+        if (rc < 0) { *err = "PCRE2 match error: " + pcre2_message(rc); ok = false; break; }
+        const size_t *ov = p.get_ovector_pointer(md);
+        if (ov[1] <= ov[0]) { *err = "PCRE2 matched an empty string"; ok = false; break; }
+        for (uint64_t j = ov[0]; j < ov[1];) {
+            const mbpe::SplitChar c = mbpe::split_decode_checked(subject.data(), j, subject.size());
+            if (!c.len) { *err = "PCRE2 matched inside a character"; ok = false; break; }
+            hit(c.cp);
+            j += c.len;
+        }
+        offset = ov[1];
+    }
+    if (md) p.match_data_free(md);
+    p.code_free(code);
+    return ok;
+}
+
+}  // namespace
+
+const SplitUnicodeTable *split_unicode_table(std::string *err) {
+    static SplitUnicodeTable table;
+    static std::string why;
+    static bool ok = false;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        const auto t0 = std::chrono::steady_clock::now();
+        Pcre2Api &p = pcre2();
+        if (!p.ok) { why = p.why; return; }
+        const std::vector<uint8_t> subject = all_scalar_values();
+        std::vector<uint32_t> &cls = table.cls;
+        cls.assign(mbpe::kSplitTableWords, 0xFFFFFFFFu);                  // everything O ...
+        const uint32_t utf = kPCRE2_UTF | kPCRE2_UCP;                      // (Splitter::compile)
+        bool clash = false;
+        auto set = [&](uint32_t cp, uint32_t c) {                          // ... but what one of the three matches
+            const uint32_t sh = 2u * (cp & 15u);
+            if (((cls[cp >> 4] >> sh) & 3u) != mbpe::kClsO) clash = true;
+            cls[cp >> 4] = (cls[cp >> 4] & ~(3u << sh)) | (c << sh);
+        };
+        if (!find_all("\\p{L}+", utf, subject, [&](uint32_t cp) { set(cp, mbpe::kClsL); }, &why)) return;
+        if (!find_all("\\p{N}+", utf, subject, [&](uint32_t cp) { set(cp, mbpe::kClsN); }, &why)) return;
+        if (!find_all("\\s+", utf, subject, [&](uint32_t cp) { set(cp, mbpe::kClsS); }, &why)) return;
+        if (clash) { why = "PCRE2 puts a character into two of \\p{L}, \\p{N}, \\s"; return; }
+        for (uint32_t cp = 0; cp < 0x80u; ++cp)
+            if (((cls[cp >> 4] >> (2u * (cp & 15u))) & 3u) != mbpe::split_class(cp)) {
+                why = "PCRE2 and split_class disagree on the class of byte " + std::to_string(cp);
+                return;
+            }
+        // the fold set: what the contraction letters match caselessly beyond ASCII, then which letter each matches
+        std::vector<uint32_t> folded;
+        const uint32_t caseless = utf | kPCRE2_CASELESS;
+        if (!find_all("[sdmtlver]", caseless, subject, [&](uint32_t cp) { if (cp >= 0x80u) folded.push_back(cp); }, &why))
+            return;
+        if (folded.size() > mbpe::kSplitMaxFold) { why = "PCRE2 folds more characters to s d m t l v e r than the table holds"; return; }
+        for (uint32_t cp : folded) {
+            std::vector<uint8_t> one;
+            for (uint64_t j = 0; j < subject.size();) {                   // (its bytes, from the subject)
+                const mbpe::SplitChar c = mbpe::split_decode_checked(subject.data(), j, subject.size());
+                if (c.cp == cp) { one.assign(subject.begin() + j, subject.begin() + j + c.len); break; }
+                j += c.len;
+            }
+            uint8_t to = 0;
+            for (const char *l = "sdmtlver"; *l; ++l) {
+                const char pat[2] = {*l, 0};
+                bool hit = false;
+                if (!find_all(pat, caseless, one, [&](uint32_t) { hit = true; }, &why)) return;
+                if (hit) to = (uint8_t)*l;
+            }
+            if (!to) { why = "PCRE2 folds a character to none of s d m t l v e r alone"; return; }
+            table.fold_cp[table.n_fold] = cp;
+            table.fold_to[table.n_fold++] = to;
+        }
+        table.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        ok = true;
+    });
+    if (!ok) { if (err) *err = why; return nullptr; }
+    return &table;
 }
 
 Splitter::~Splitter() { reset(); }
@@ -414,6 +530,25 @@ int mbpe_split_has_gaps(const mbpe_split *s) { return s && s->gaps ? 1 : 0; }
 const uint64_t *mbpe_split_starts(const mbpe_split *s) { return s ? s->starts.data() : nullptr; }
 const uint64_t *mbpe_split_ends(const mbpe_split *s) { return s ? s->ends.data() : nullptr; }
 void mbpe_split_free(mbpe_split *s) { delete s; }
+
+int mbpe_split_unicode_table(uint32_t *cls_out, uint32_t *fold_cp_out, uint8_t *fold_to_out, uint32_t cap_fold,
+                             uint32_t *n_fold_out, double *build_ms_out) {
+    std::string err;
+    const mbpe_host::SplitUnicodeTable *tb = mbpe_host::split_unicode_table(&err);
+    if (!tb) { mbpe_host::set_last_error(err); return MBPE_ERR_REGEX; }
+    if (n_fold_out) *n_fold_out = tb->n_fold;
+    if (build_ms_out) *build_ms_out = tb->build_ms;
+    if ((fold_cp_out || fold_to_out) && cap_fold < tb->n_fold) {
+        mbpe_host::set_last_error("mbpe_split_unicode_table: the fold arrays are too small");
+        return MBPE_ERR_ARG;
+    }
+    if (cls_out) memcpy(cls_out, tb->cls.data(), tb->cls.size() * 4);
+    for (uint32_t k = 0; k < tb->n_fold; ++k) {
+        if (fold_cp_out) fold_cp_out[k] = tb->fold_cp[k];
+        if (fold_to_out) fold_to_out[k] = tb->fold_to[k];
+    }
+    return MBPE_OK;
+}
 
 const char *mbpe_split_pattern(const char *encoder_name) {
     if (!encoder_name) return nullptr;

@@ -39,6 +39,8 @@ mbpe_splitter *Tokenizer::device_splitter(int device) {
         if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());   // MBPE_ERR_ARG for a custom pattern
         dev_splitter_device_ = device;
     }
+    const int rc = mbpe_splitter_set_option(dev_splitter_, "unicode", split_unicode_ ? 1 : 0);
+    if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
     return dev_splitter_;
 }
 
@@ -175,6 +177,7 @@ void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTI
         // the split on the device: one upload of the text, which the trainer then takes in place with the mask
         uint64_t n_chunks = 0;
         int rc = mbpe_splitter_create(device, pattern_.c_str(), &dev_split);
+        if (rc == MBPE_OK) rc = mbpe_splitter_set_option(dev_split, "unicode", split_unicode_ ? 1 : 0);
         if (rc == MBPE_OK) rc = mbpe_splitter_split(dev_split, bytes, text.size(), 0, nullptr, nullptr, 0, &n_chunks);
         if (rc == MBPE_OK) rc = mbpe_splitter_endmask(dev_split, &d_mask, nullptr, &d_text);
         if (rc != MBPE_OK) {
@@ -766,6 +769,12 @@ int mbpe_tok_train_split_device(mbpe_tokenizer *t, const uint8_t *text, uint64_t
 int mbpe_tok_set_encode_split(mbpe_tokenizer *t, int on_device) {
     if (!t) return MBPE_ERR_ARG;
     t->t->set_encode_split(on_device != 0);
+    return MBPE_OK;
+}
+
+int mbpe_tok_set_split_unicode(mbpe_tokenizer *t, int on) {
+    if (!t) return MBPE_ERR_ARG;
+    t->t->set_split_unicode(on != 0);
     return MBPE_OK;
 }
 

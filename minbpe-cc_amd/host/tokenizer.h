@@ -61,6 +61,8 @@ public:
     // what the mbpe_tok_encode*_device calls of the C-ABI pass as device_split (mbpe_tok_set_encode_split)
     void set_encode_split(bool on) { encode_split_ = on; }
     bool encode_split() const { return encode_split_; }
+    // the option "unicode" of every device split made from here on (mbpe_tok_set_split_unicode)
+    void set_split_unicode(bool on) { split_unicode_ = on; }
     // :725-751; device >= 0 expands the tokens on that HIP device (mbpe_decode_tokens) instead of the host loop
     std::string decode(const std::vector<Token> &tokens, bool verbose, int device = -1);
     // decode() of every token list, [i] == decode(docs[i], false, -1), in one mbpe_decode_batch on HIP device `device`
@@ -135,6 +137,7 @@ private:
     mbpe_splitter *dev_splitter_ = nullptr;  // the device split of encode(..., device, device_split)
     int dev_splitter_device_ = -1;
     bool encode_split_ = false;
+    bool split_unicode_ = false;
 };
 
 }  // namespace mbpe_host

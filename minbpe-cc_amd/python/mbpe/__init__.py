@@ -36,7 +36,7 @@ EXPORTS = [
     "mbpe_load_corpus_endmask", "mbpe_splitter_create", "mbpe_splitter_destroy", "mbpe_splitter_split",
     "mbpe_splitter_endmask", "mbpe_splitter_set_option", "mbpe_splitter_kernel_ms", "mbpe_splitter_alloc_count",
     "mbpe_splitter_host_spans", "mbpe_splitter_split_docs", "mbpe_splitter_ranges", "mbpe_splitter_find_ms",
-    "mbpe_encoder_encode_endmask", "mbpe_encoder_encode_batch_endmask",
+    "mbpe_encoder_encode_endmask", "mbpe_encoder_encode_batch_endmask", "mbpe_split_unicode_table",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -44,7 +44,7 @@ TOK_EXPORTS = [
     "mbpe_tok_get_merges", "mbpe_tok_save", "mbpe_tok_load", "mbpe_tok_encode", "mbpe_tok_encode_device",
     "mbpe_tok_decode", "mbpe_tok_decode_device", "mbpe_tok_encode_batch_device", "mbpe_tok_decode_batch_device",
     "mbpe_tok_encode_batch_packed_device", "mbpe_tok_decode_padded_device", "mbpe_tok_encode_batch_aux_device",
-    "mbpe_tok_train_split_device", "mbpe_tok_set_encode_split",
+    "mbpe_tok_train_split_device", "mbpe_tok_set_encode_split", "mbpe_tok_set_split_unicode",
 ]
 
 
@@ -225,6 +225,8 @@ def lib():
     L.mbpe_encoder_encode_batch_endmask.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, u64, i32, vp, vp, vp,
                                                     vp, vp]
     L.mbpe_tok_set_encode_split.argtypes = [vp, i32]
+    L.mbpe_tok_set_split_unicode.argtypes = [vp, i32]
+    L.mbpe_split_unicode_table.argtypes = [vp, vp, vp, u32, vp, vp]
     L.mbpe_tok_set_merges.argtypes = [vp, vp, u32]
     L.mbpe_tok_get_merges.argtypes = [vp, vp, u32, vp]
     L.mbpe_tok_save.argtypes = [vp, ctypes.c_char_p, i32]
@@ -253,6 +255,17 @@ def split_pattern(encoder):
     if p is None:
         raise ValueError("Encoder should be one of: basic, gpt2 or gpt4")
     return p.decode("utf-8")
+
+
+def split_unicode_table():
+    """What PCRE2 says of every code point (mbpe_split_unicode_table) -> (classes as uint32[0x110000 / 16], 2 bits per
+    code point: 0 L, 1 N, 2 S, 3 other; {code point >= 0x80: the letter of "sdmtlver" it folds to}; build time in ms)."""
+    cls = np.zeros(0x110000 // 16, dtype=np.uint32)
+    cp, to = np.zeros(8, dtype=np.uint32), np.zeros(8, dtype=np.uint8)
+    n, ms = ctypes.c_uint32(), ctypes.c_double()
+    _check(lib().mbpe_split_unicode_table(cls.ctypes.data, cp.ctypes.data, to.ctypes.data, 8, ctypes.byref(n),
+                                          ctypes.byref(ms)))
+    return cls, {int(cp[k]): chr(to[k]) for k in range(n.value)}, ms.value
 
 
 def presplit_ranges(pattern, data):
@@ -1187,8 +1200,10 @@ class Tokenizer:
 
     def train(self, data, vocab_size, conflict_resolution=1, verbose=False, device=0, device_split=False):
         """device_split: the gpt2 / gpt4 pre-split runs on the device too (same merges); a tokenizer with any other
-        pattern raises MbpeError(ERR_ARG)."""
+        pattern raises MbpeError(ERR_ARG).  "unicode" instead of True: with the splitter's option "unicode", so that
+        well-formed non-ASCII text is split there as well (mbpe_tok_set_split_unicode)."""
         text = _u8(data)
+        _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
         fn = lib().mbpe_tok_train_split_device if device_split else lib().mbpe_tok_train
         _check(fn(self._h, text.ctypes.data if len(text) else None, len(text), vocab_size, conflict_resolution,
                   int(verbose), device))
@@ -1212,11 +1227,13 @@ class Tokenizer:
 
     def _encode_split(self, device_split):
         _check(lib().mbpe_tok_set_encode_split(self._h, int(bool(device_split))))
+        _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
 
     def encode(self, data, device=None, device_split=False):
         """device None: internal_encode on the host; an int: on that HIP device (mbpe_tok_encode_device).
         device_split (here and in the batch calls; only with a device): the text is cut at the special tokens and split
-        into chunks on the device too (mbpe_tok_set_encode_split); same tokens, gpt2 / gpt4 patterns only."""
+        into chunks on the device too (mbpe_tok_set_encode_split); same tokens, gpt2 / gpt4 patterns only.  "unicode"
+        instead of True: with the splitter's option "unicode" for that call (mbpe_tok_set_split_unicode)."""
         self._encode_split(device_split)
         text = _u8(data)
         n = ctypes.c_uint64()
