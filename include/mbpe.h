@@ -411,6 +411,27 @@ MBPE_API int  mbpe_encoder_encode(mbpe_encoder *e, const uint8_t *text, uint64_t
                                   uint64_t *chunk_tok_off_out, uint64_t *n_out, uint32_t *n_passes_out);
 
 /*   "piece_bytes"   the most text bytes encoded in one go; 0 (default) = chosen at the call, see above.
+ *   "rank_order"    the order in which the merges are applied to a chunk.  0 (default): the reference's greedy passes
+ *                   (Tokenizer.h:325-367: a left-to-right pass replaces ANY pair it finds in the lookup, first match
+ *                   wins).  1: rank order.  Per chunk, after text_to_vector: of the adjacent pairs that are in the
+ *                   lookup (a repeated pair keeps the last id) take the smallest id m; stop when there is none;
+ *                   replace every occurrence of that pair with m, left to right and non-overlapping (a a a with (a,a)
+ *                   gives m a); repeat.  For a table in which both sides of merge k are below 256 + k and no pair
+ *                   occurs twice -- every trained model -- that equals applying merges 0 .. n-1 in order: the
+ *                   segmentation the trainer left in its stream (mbpe_get_stream) and what other BPE implementations
+ *                   give for the same merges.  For any other table the loop above is the definition.
+ *                   The option holds for mbpe_encoder_encode, _encode_batch, _encode_batch_aux, _encode_endmask and
+ *                   _encode_batch_endmask, with everything else (pieces, 16-bit output, device text, queries, cap
+ *                   rules, NUL-led chunks, singles) as it is; mbpe_encode_chunks* stay greedy.  Any value but 0 and 1
+ *                   is MBPE_ERR_ARG.
+ *                   Passes: a device pass applies, in every chunk at once, that chunk's smallest candidate id, so
+ *                   n_passes_out is 1 + the most rounds any chunk needs.  That is not capped: a chunk of L tokens
+ *                   needs at most L passes, a text that is ONE chunk one pass per distinct merge that applies (the
+ *                   whole table, for the text a basic model was trained on), where the greedy order needs a
+ *                   handful.  With the gpt2 / gpt4 split at vocab 512: 9-14 passes against 4.  Every pass is a few
+ *                   short kernels and one 8-byte read-back, as in the default order; mbpe_encoder_pass_tokens reports
+ *                   them.  The option adds 20 bytes per 1,024 text bytes to the work buffers, allocated when the
+ *                   first call in rank order needs them.
  * An unknown name or a negative value is MBPE_ERR_ARG. */
 MBPE_API int  mbpe_encoder_set_option(mbpe_encoder *e, const char *name, int64_t value);
 

@@ -99,6 +99,16 @@ MBPE_API int mbpe_tok_encode_batch_aux_device(mbpe_tokenizer *t, const uint8_t *
  * calls: there is no silent return to the host split.  Nothing else is affected. */
 MBPE_API int mbpe_tok_set_encode_split(mbpe_tokenizer *t, int on_device);
 
+/* The order in which mbpe_tok_encode and the mbpe_tok_encode*_device calls apply the merges to a chunk: 0 (the
+ * default) the reference's greedy passes (Tokenizer.h:325-367: a left-to-right pass replaces any pair it finds);
+ * 1 rank order -- of the adjacent pairs that are in the merges, every occurrence of the one with the smallest id is
+ * replaced, left to right and non-overlapping, until no pair is left.  For a trained table (both sides of merge k
+ * below 256 + k, no pair twice) that replays the merges in order: the segmentation the trainer left in its stream,
+ * and what other BPE implementations give for the same merges.  The host loop follows it, and the kept device encoder
+ * is re-configured (mbpe_encoder_set_option "rank_order"), not re-created, with and without the device split.  Splitting
+ * and special tokens are unaffected.  Any other value is MBPE_ERR_ARG. */
+MBPE_API int mbpe_tok_set_encode_order(mbpe_tokenizer *t, int rank_order);
+
 /* The option "unicode" (mbpe_splitter_set_option) of the device splits this tokenizer makes: 0 (the default) or on.
  * It applies to mbpe_tok_train_split_device and, while mbpe_tok_set_encode_split is on, to the mbpe_tok_encode*_device
  * calls, whose kept splitter is re-configured, not re-created.  Same results; otherwise without effect. */

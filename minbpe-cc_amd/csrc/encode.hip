@@ -22,8 +22,14 @@
 // the caller wants to know which tokens belong to which chunk, the position after every flagged token (per-span
 // count of flags -> k_enc_scan_sum -> ranked write).  A text that lives on the device is read in place; the chunk
 // starts whose byte is NUL are listed by a small kernel so that the host can parse those chunks.
+//
+// Option "rank_order": a pass replaces, in every chunk, only the candidates whose id is the smallest candidate id of
+// that chunk -- k_enc_cand, then a segmented minimum of cand over the chunks (rank.h) and a filter, then the same
+// parity scan, match, sum scan and scatter.  Passes repeat until one changes nothing, as above; for a trained table
+// the result is the merges replayed in order, chunk by chunk.
 #include "hip_host.h"
 #include "pack.h"
+#include "rank.h"
 #include "span.h"
 
 #include <algorithm>
@@ -95,6 +101,90 @@ __global__ __launch_bounds__(kSpanThreads) void k_enc_cand(const uint32_t *__res
         if (i < n && !(t & kTokEnd) && t != kDrop && nx != kDrop) c = enc_lookup(lut, t, nx & kTokIdMask);
         if (i < n) cand[i] = c;
         sum = span_add_group(sum, __ballot(c != kTokNone));
+    }
+    if (lane == 0) span_sum[span] = span_pack(sum);
+}
+
+// ---- rank order (option "rank_order"): between k_enc_cand and the parity scan, every candidate above the smallest
+// candidate id of its chunk becomes kTokNone (rank.h).  Two candidates of one chunk with the same id are the same
+// pair, so what is left of a chunk are runs of one pair (a,a) and lone candidates: the run parity decides as before.
+
+// per span: does it hold a chunk end, the minimum of cand up to and including its first end, and after its last one
+__global__ __launch_bounds__(kSpanThreads) void k_enc_rank_sum(const uint32_t *__restrict__ tok, uint64_t n,
+                                                               const uint32_t *__restrict__ cand,
+                                                               RankSum *__restrict__ rank_sum) {
+    const uint64_t span = span_index(), base = span * kSpan;
+    if (base >= n) return;
+    const uint32_t lane = lane_id();
+    uint32_t h = kTokNone, t = kTokNone;
+    bool seen = false;
+    for (int it = 0; it < kSpanIters; ++it) {
+        const uint64_t i = base + (uint64_t)it * kWave + lane;
+        const uint32_t c = i < n ? cand[i] : kTokNone;
+        const unsigned long long E = __ballot(i < n && (tok[i] & kTokEnd));
+        h = rank_head_part(h, seen, E, lane, c);
+        t = rank_tail_part(t, E, lane, c);
+        seen = seen || E != 0ull;
+    }
+    h = wave_min(h);
+    t = wave_min(t);
+    if (lane == 0) rank_sum[span] = {seen ? 1u : 0u, h, t};
+}
+
+// what reaches every span of its chunk from the left and from the right
+__global__ __launch_bounds__(kScanThreads) void k_enc_scan_min(const RankSum *__restrict__ rank_sum, uint64_t n_spans,
+                                                               uint32_t *__restrict__ in_left,
+                                                               uint32_t *__restrict__ in_right) {
+    __shared__ RankSum sh_sum[kScanThreads];
+    __shared__ uint32_t sh_l[kScanThreads], sh_r[kScanThreads];
+    span_scan_min(rank_sum, n_spans, in_left, in_right, sh_sum, sh_l, sh_r);
+}
+
+// the filter: cand keeps the candidates that equal their chunk's minimum; span_sum as k_enc_cand writes it, of those
+__global__ __launch_bounds__(kSpanThreads) void k_enc_rank_filter(const uint32_t *__restrict__ tok, uint64_t n,
+                                                                  uint32_t *__restrict__ cand,
+                                                                  const uint32_t *__restrict__ in_left,
+                                                                  const uint32_t *__restrict__ in_right,
+                                                                  uint32_t *__restrict__ span_sum) {
+    const uint64_t span = span_index(), base = span * kSpan;
+    if (base >= n) return;
+    const uint32_t lane = lane_id();
+    const unsigned long long lt = lanes_below(lane);
+    uint32_t c[kSpanIters], m[kSpanIters], head[kSpanIters], tail[kSpanIters];
+    unsigned long long E[kSpanIters];
+#pragma unroll
+    for (int it = 0; it < kSpanIters; ++it) {
+        const uint64_t i = base + (uint64_t)it * kWave + lane;
+        c[it] = i < n ? cand[i] : kTokNone;
+        E[it] = __ballot(i < n && (tok[i] & kTokEnd));
+        m[it] = group_seg_min(c[it], E[it], lt, lane);
+        // (lane 0's segment is the group's head; lane 63's its tail, unless lane 63 ends a chunk)
+        head[it] = (uint32_t)__shfl((int)m[it], 0, kWave);
+        tail[it] = E[it] >> 63 ? kTokNone : (uint32_t)__shfl((int)m[it], kWave - 1, kWave);
+    }
+    uint32_t left[kSpanIters], right[kSpanIters];
+    uint32_t run = in_left[span];
+#pragma unroll
+    for (int it = 0; it < kSpanIters; ++it) {
+        left[it] = run;
+        run = rank_carry(run, E[it] != 0ull, tail[it]);
+    }
+    run = in_right[span];
+#pragma unroll
+    for (int it = kSpanIters - 1; it >= 0; --it) {
+        right[it] = run;
+        run = rank_carry(run, E[it] != 0ull, head[it]);
+    }
+    SpanSum sum = span_empty();
+#pragma unroll
+    for (int it = 0; it < kSpanIters; ++it) {
+        const uint64_t i = base + (uint64_t)it * kWave + lane;
+        uint32_t v = m[it];
+        if (rank_open_left(E[it], lt)) v = rank_min(v, left[it]);
+        if (rank_open_right(E[it], lt)) v = rank_min(v, right[it]);
+        const uint32_t f = c[it] == v ? c[it] : kTokNone;       // (v == kTokNone: a chunk without candidates)
+        if (i < n) cand[i] = f;
+        sum = span_add_group(sum, __ballot(f != kTokNone));
     }
     if (lane == 0) span_sum[span] = span_pack(sum);
 }
@@ -267,7 +357,8 @@ int fail(int code, const std::string &msg) {
     return code;
 }
 
-constexpr uint64_t kPieceCost = 14;        // device bytes per text byte of a piece, rounded up (mbpe.h, "piece_bytes")
+// device bytes per text byte of a piece, rounded up (mbpe.h, "piece_bytes"): 13.2, and 20 / 1,024 more in rank order
+constexpr uint64_t kPieceCost = 14;
 constexpr uint64_t kNulListMin = 4096;     // entries the list of NUL-led chunk starts begins with
 constexpr uint64_t kNulCopyEach = 256;     // up to this many NUL-led chunks are copied back one by one
 
@@ -280,6 +371,7 @@ struct mbpe_encoder {
     float last_ms = 0.f;
     uint64_t n_allocs = 0;                    // hipMalloc calls so far (mbpe_encoder_alloc_count)
     uint64_t piece_bytes = 0;                 // option "piece_bytes"; 0 = from the free device memory
+    bool rank_order = false;                  // option "rank_order": a pass applies every chunk's lowest merge only
     uint32_t n_merges = 0;
     // the lookup table
     unsigned long long *d_keys = nullptr;
@@ -289,6 +381,9 @@ struct mbpe_encoder {
     uint8_t *d_text = nullptr, *d_mask = nullptr;
     uint32_t *tok[2] = {nullptr, nullptr}, *cand = nullptr, *span_a = nullptr, *span_b = nullptr;
     unsigned long long *span_off = nullptr;
+    RankSum *rank_sum = nullptr;              // rank order only: the spans' summaries, and what reaches every span
+    uint32_t *rank_in = nullptr;              // from the left [0 .. n_spans) and from the right [n_spans .. 2 n_spans)
+    uint64_t cap_rank_sum = 0, cap_rank_in = 0;
     uint64_t cap_text = 0, cap_mask = 0, cap_tok[2] = {0, 0}, cap_cand = 0, cap_span_a = 0, cap_span_b = 0,
              cap_span_off = 0;
     unsigned long long *d_res = nullptr;      // [0] total of a sum scan, [1] NUL-led chunk starts found
@@ -323,7 +418,7 @@ namespace {
 
 uint64_t enc_held(const mbpe_encoder *e) {
     return e->cap_text + e->cap_mask + e->cap_tok[0] + e->cap_tok[1] + e->cap_cand + e->cap_span_a + e->cap_span_b +
-           e->cap_span_off;
+           e->cap_span_off + e->cap_rank_sum + e->cap_rank_in;
 }
 
 struct Piece { uint64_t c0, c1; };            // chunks [c0, c1)
@@ -456,6 +551,10 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
     if (rc == MBPE_OK) rc = grow(&e->span_a, &e->cap_span_a, n_spans0 * 4, true, &e->n_allocs);
     if (rc == MBPE_OK) rc = grow(&e->span_b, &e->cap_span_b, n_spans0 * 4, true, &e->n_allocs);
     if (rc == MBPE_OK) rc = grow(&e->span_off, &e->cap_span_off, n_spans0 * 8, true, &e->n_allocs);
+    if (rc == MBPE_OK && e->rank_order) {
+        rc = grow(&e->rank_sum, &e->cap_rank_sum, n_spans0 * sizeof(RankSum), true, &e->n_allocs);
+        if (rc == MBPE_OK) rc = grow(&e->rank_in, &e->cap_rank_in, n_spans0 * 8, true, &e->n_allocs);
+    }
     if (rc != MBPE_OK) return rc;
     // the piece's NUL-led chunks (e->singles is sorted by start), relative to the piece
     e->piece_singles.clear();
@@ -501,6 +600,14 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
         const uint64_t n_spans = span_count(n);
         const dim3 grid(span_grid(n)), block(kSpanThreads);
         hipLaunchKernelGGL(k_enc_cand, grid, block, 0, e->stream, e->tok[cur], n, e->lut, e->cand, e->span_a);
+        if (e->rank_order) {
+            uint32_t *in_left = e->rank_in, *in_right = e->rank_in + n_spans;
+            hipLaunchKernelGGL(k_enc_rank_sum, grid, block, 0, e->stream, e->tok[cur], n, e->cand, e->rank_sum);
+            hipLaunchKernelGGL(k_enc_scan_min, dim3(1), dim3(kScanThreads), 0, e->stream, e->rank_sum, n_spans, in_left,
+                               in_right);
+            hipLaunchKernelGGL(k_enc_rank_filter, grid, block, 0, e->stream, e->tok[cur], n, e->cand, in_left, in_right,
+                               e->span_a);
+        }
         hipLaunchKernelGGL(k_enc_scan_parity, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans, e->span_b);
         hipLaunchKernelGGL(k_enc_match, grid, block, 0, e->stream, e->tok[cur], n, e->cand, e->span_b, e->span_a);
         hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans, e->span_off,
@@ -980,6 +1087,7 @@ void mbpe_encoder_destroy(mbpe_encoder *e) {
     (void)hipFree(e->d_nul); (void)hipFree(e->d_ends); (void)hipFree(e->d_flat); (void)hipFree(e->d_doc_off);
     (void)hipFree(e->d_ids); (void)hipFree(e->d_len); (void)hipFree(e->d_labels); (void)hipFree(e->d_pos);
     (void)hipFree(e->d_seg); (void)hipFree(e->d_doc_pos);
+    (void)hipFree(e->rank_sum); (void)hipFree(e->rank_in);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -991,6 +1099,11 @@ int mbpe_encoder_set_option(mbpe_encoder *e, const char *name, int64_t value) {
     if (strcmp(name, "piece_bytes") == 0) {
         if (value < 0) return fail(MBPE_ERR_ARG, "piece_bytes must not be negative");
         e->piece_bytes = (uint64_t)value;
+        return MBPE_OK;
+    }
+    if (strcmp(name, "rank_order") == 0) {
+        if (value != 0 && value != 1) return fail(MBPE_ERR_ARG, "rank_order must be 0 or 1");
+        e->rank_order = value == 1;
         return MBPE_OK;
     }
     return fail(MBPE_ERR_ARG, std::string("mbpe_encoder_set_option: no option \"") + name + "\"");

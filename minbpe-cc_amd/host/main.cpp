@@ -1,6 +1,6 @@
 // minbpe-cc: the reference's command line (code/examples/minbpe-cc.cpp:92-265)
 // on top of the MI355X training path.  Same flags, defaults, messages and exit
-// codes; `--train -c lexical` runs on the GPU.  The only additions are --device and the --device-* switches.
+// codes; `--train -c lexical` runs on the GPU.  The only additions are --device, the --device-* switches and --rank-order.
 #include "mbpe.h"
 #include "mbpe_tokenizer.h"
 
@@ -70,7 +70,10 @@ void usage() {
                  "  --device-split              When training with gpt2 or gpt4, split the text on the HIP device (--device);\n"
                  "                              when encoding, only together with --device-encode: the text is cut at the\n"
                  "                              special tokens and split on the device too (without it: no effect)\n"
-                 "  --device-split-unicode      --device-split, with non-ASCII text split on the device as well\n";
+                 "  --device-split-unicode      --device-split, with non-ASCII text split on the device as well\n"
+                 "  --rank-order                When encoding, apply the merges in rank order (a chunk's pair with the lowest\n"
+                 "                              merge id first: the segmentation the model was trained on) instead of the\n"
+                 "                              reference's greedy passes; on the host and with --device-encode\n";
 }
 
 }  // namespace
@@ -79,7 +82,7 @@ int main(int argc, char *argv[]) {
     std::string input_path, output_path, special_token_path, encoder = "gpt4", model_path = "./output.model";
     std::string conflict_resolution_str = "first";
     bool train = false, decode = false, encode = false, write_vocab = false, verbose = false, device_encode = false,
-         device_decode = false, device_split = false, split_unicode = false;
+         device_decode = false, device_split = false, split_unicode = false, rank_order = false;
     int vocab_size = 512, device = 0;
 
     // option parsing (the reference uses CLI11, :93-133)
@@ -121,6 +124,7 @@ int main(int argc, char *argv[]) {
         else if (arg == "--device-decode") device_decode = true;
         else if (arg == "--device-split") device_split = true;
         else if (arg == "--device-split-unicode") device_split = split_unicode = true;
+        else if (arg == "--rank-order") rank_order = true;
         else if (arg == "-v" || arg == "--verbose") verbose = true;
         else { std::cerr << "The following argument was not expected: " << arg << "\n"; return 109; }
     }
@@ -188,6 +192,7 @@ int main(int argc, char *argv[]) {
             uint64_t n = 0;
             const uint8_t *in = reinterpret_cast<const uint8_t *>(input.data());
             if (device_encode && device_split) mbpe_tok_set_encode_split(rt, 1);
+            if (rank_order) mbpe_tok_set_encode_order(rt, 1);
             if (split_unicode) mbpe_tok_set_split_unicode(rt, 1);
             const int erc = device_encode
                                 ? mbpe_tok_encode_device(rt, in, input.size(), verbose, device, encoded.data(), encoded.size(), &n)

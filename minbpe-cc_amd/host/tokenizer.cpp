@@ -13,6 +13,7 @@
 #include <fstream>
 #include <iomanip>
 #include <iostream>
+#include <limits>
 #include <sstream>
 #include <stdexcept>
 
@@ -60,6 +61,8 @@ mbpe_encoder *Tokenizer::device_encoder(int device) {
         if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
         encoder_device_ = device;
     }
+    const int rc = mbpe_encoder_set_option(encoder_, "rank_order", rank_order_ ? 1 : 0);
+    if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
     return encoder_;
 }
 
@@ -293,6 +296,32 @@ std::vector<Token> Tokenizer::internal_internal_encode(std::vector<Token> text) 
     }
 }
 
+std::vector<Token> Tokenizer::encode_rank_ordered(std::vector<Token> text) const {
+    for (;;) {
+        Token best = std::numeric_limits<Token>::max();
+        bool any = false;
+        for (size_t i = 0; i + 1 < text.size(); ++i) {
+            auto it = merges_lookup_.find(TokenPair{text[i], text[i + 1]});
+            if (it != merges_lookup_.end() && (!any || it->second < best)) { best = it->second; any = true; }
+        }
+        if (!any) return text;
+        std::vector<Token> out;
+        out.reserve(text.size());
+        for (size_t i = 0; i < text.size();) {
+            if (i + 1 < text.size()) {
+                auto it = merges_lookup_.find(TokenPair{text[i], text[i + 1]});
+                if (it != merges_lookup_.end() && it->second == best) {
+                    out.push_back(best);
+                    i += 2;
+                    continue;
+                }
+            }
+            out.push_back(text[i++]);
+        }
+        text.swap(out);
+    }
+}
+
 void Tokenizer::append_chunks(const std::string &text, bool verbose, std::string *buf, std::vector<uint64_t> *off) const {
     auto split_text = split_on_special(text);
     if (verbose) {
@@ -416,7 +445,8 @@ std::vector<Token> Tokenizer::encode(const std::string &text, bool verbose, int 
         out.resize(n);
     } else {
         for (size_t c = 0; c + 1 < off.size(); ++c) {           // internal_encode :370-377 + flatten :713-717
-            auto enc = internal_internal_encode(text_to_vector(buf.data() + off[c], off[c + 1] - off[c]));
+            auto vec = text_to_vector(buf.data() + off[c], off[c + 1] - off[c]);
+            auto enc = rank_order_ ? encode_rank_ordered(std::move(vec)) : internal_internal_encode(std::move(vec));
             out.insert(out.end(), enc.begin(), enc.end());
         }
     }
@@ -769,6 +799,16 @@ int mbpe_tok_train_split_device(mbpe_tokenizer *t, const uint8_t *text, uint64_t
 int mbpe_tok_set_encode_split(mbpe_tokenizer *t, int on_device) {
     if (!t) return MBPE_ERR_ARG;
     t->t->set_encode_split(on_device != 0);
+    return MBPE_OK;
+}
+
+int mbpe_tok_set_encode_order(mbpe_tokenizer *t, int rank_order) {
+    if (!t) return MBPE_ERR_ARG;
+    if (rank_order != 0 && rank_order != 1) {
+        mbpe_host::set_last_error("mbpe_tok_set_encode_order: rank_order must be 0 or 1");
+        return MBPE_ERR_ARG;
+    }
+    t->t->set_rank_order(rank_order == 1);
     return MBPE_OK;
 }
 

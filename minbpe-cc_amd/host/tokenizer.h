@@ -61,6 +61,10 @@ public:
     // what the mbpe_tok_encode*_device calls of the C-ABI pass as device_split (mbpe_tok_set_encode_split)
     void set_encode_split(bool on) { encode_split_ = on; }
     bool encode_split() const { return encode_split_; }
+    // the order in which encode and its batch forms apply the merges, on the host and on the device: false (the
+    // default) the reference's greedy passes, true rank order (encode_rank_ordered below; mbpe_tok_set_encode_order)
+    void set_rank_order(bool on) { rank_order_ = on; }
+    bool rank_order() const { return rank_order_; }
     // the option "unicode" of every device split made from here on (mbpe_tok_set_split_unicode)
     void set_split_unicode(bool on) { split_unicode_ = on; }
     // :725-751; device >= 0 expands the tokens on that HIP device (mbpe_decode_tokens) instead of the host loop
@@ -96,6 +100,10 @@ private:
     void initialize_vocab();                                                // :103-111
     std::vector<std::string> split_on_special(const std::string &text) const;   // :605-650
     std::vector<Token> internal_internal_encode(std::vector<Token> text) const; // :325-367
+    // the rank-ordered counterpart: of the adjacent pairs that are in merges_lookup, every occurrence of the one with
+    // the smallest id is replaced, left to right and non-overlapping; repeated until no pair is left.  For a trained
+    // table this replays the merges in order: the trainer's segmentation
+    std::vector<Token> encode_rank_ordered(std::vector<Token> text) const;
     void rebuild_vocab();
     void drop_decoder();                   // the merges or the specials changed
     void drop_encoder();                   // the merges changed (special tokens do not enter the lookup table)
@@ -138,6 +146,7 @@ private:
     int dev_splitter_device_ = -1;
     bool encode_split_ = false;
     bool split_unicode_ = false;
+    bool rank_order_ = false;
 };
 
 }  // namespace mbpe_host

@@ -45,6 +45,7 @@ TOK_EXPORTS = [
     "mbpe_tok_decode", "mbpe_tok_decode_device", "mbpe_tok_encode_batch_device", "mbpe_tok_decode_batch_device",
     "mbpe_tok_encode_batch_packed_device", "mbpe_tok_decode_padded_device", "mbpe_tok_encode_batch_aux_device",
     "mbpe_tok_train_split_device", "mbpe_tok_set_encode_split", "mbpe_tok_set_split_unicode",
+    "mbpe_tok_set_encode_order",
 ]
 
 
@@ -226,6 +227,7 @@ def lib():
                                                     vp, vp]
     L.mbpe_tok_set_encode_split.argtypes = [vp, i32]
     L.mbpe_tok_set_split_unicode.argtypes = [vp, i32]
+    L.mbpe_tok_set_encode_order.argtypes = [vp, i32]
     L.mbpe_split_unicode_table.argtypes = [vp, vp, vp, u32, vp, vp]
     L.mbpe_tok_set_merges.argtypes = [vp, vp, u32]
     L.mbpe_tok_get_merges.argtypes = [vp, vp, u32, vp]
@@ -505,12 +507,15 @@ class Encoder:
     """One mbpe_encoder: internal_encode (Tokenizer.h:325-377) on a HIP device with the lookup table, the stream and
     the work buffers kept between calls."""
 
-    def __init__(self, merges, device=0):
+    def __init__(self, merges, device=0, rank_order=False):
+        """rank_order: the option "rank_order" from the start (set_option changes it between calls)."""
         self._h = ctypes.c_void_p()
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1, 2)
         _check(lib().mbpe_encoder_create(device, m.ctypes.data if len(m) else None, len(m), ctypes.byref(self._h)))
         self.n_passes = 0
         self.n_tokens = 0
+        if rank_order:
+            self.set_option("rank_order", 1)
 
     def close(self):
         if self._h:
@@ -1225,16 +1230,22 @@ class Tokenizer:
     def load(self, path, verbose=False):
         _check(lib().mbpe_tok_load(self._h, os.fsencode(path), int(verbose)))
 
-    def _encode_split(self, device_split):
+    def _encode_split(self, device_split, order="greedy"):
+        if order not in ("greedy", "rank"):
+            raise ValueError('order must be "greedy" or "rank"')
+        _check(lib().mbpe_tok_set_encode_order(self._h, int(order == "rank")))
         _check(lib().mbpe_tok_set_encode_split(self._h, int(bool(device_split))))
         _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
 
-    def encode(self, data, device=None, device_split=False):
+    def encode(self, data, device=None, device_split=False, order="greedy"):
         """device None: internal_encode on the host; an int: on that HIP device (mbpe_tok_encode_device).
         device_split (here and in the batch calls; only with a device): the text is cut at the special tokens and split
         into chunks on the device too (mbpe_tok_set_encode_split); same tokens, gpt2 / gpt4 patterns only.  "unicode"
-        instead of True: with the splitter's option "unicode" for that call (mbpe_tok_set_split_unicode)."""
-        self._encode_split(device_split)
+        instead of True: with the splitter's option "unicode" for that call (mbpe_tok_set_split_unicode).
+        order (here and in the batch calls; host and device): "greedy", the reference's passes that replace any pair
+        they find, or "rank": a chunk's pair with the lowest merge id first, which for a trained model is the
+        segmentation the trainer left in its stream (mbpe_tok_set_encode_order).  Anything else is ValueError."""
+        self._encode_split(device_split, order)
         text = _u8(data)
         n = ctypes.c_uint64()
         out = np.zeros(max(len(text), 1), dtype=np.uint32)
@@ -1246,9 +1257,9 @@ class Tokenizer:
                                                 out.ctypes.data, len(out), ctypes.byref(n)))
         return out[:n.value].copy()
 
-    def encode_batch(self, texts, device=0, device_split=False):
+    def encode_batch(self, texts, device=0, device_split=False, order="greedy"):
         """encode() of every text in one device call (mbpe_tok_encode_batch_device) -> list of uint32 arrays."""
-        self._encode_split(device_split)
+        self._encode_split(device_split, order)
         parts = [bytes(_u8(t)) for t in texts]
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
         if parts:
@@ -1264,12 +1275,12 @@ class Tokenizer:
 
     def encode_batch_padded(self, texts, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
                             pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
-                            device_split=False):
+                            device_split=False, order="greedy"):
         """Every text split like encode(), encoded and packed in one device call
         (mbpe_tok_encode_batch_packed_device) -> (ids [n_rows, seq_len], lengths [n_rows]) as numpy arrays; with
         out_ptr= and len_ptr= (device memory for cap_rows rows) the matrix stays on the device and the row count is
         returned.  bos_id / eos_id may be special-token ids.  layout "packed" gives the MBPE_PACK_PACKED rows."""
-        self._encode_split(device_split)
+        self._encode_split(device_split, order)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         parts = [bytes(_u8(t)) for t in texts]
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
@@ -1295,11 +1306,11 @@ class Tokenizer:
     def encode_batch_aux(self, texts, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
                          pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
                          labels=False, positions=False, segments=False, cu_seqlens=False, ignore_label=-100,
-                         labels_ptr=None, pos_ptr=None, seg_ptr=None, device_split=False):
+                         labels_ptr=None, pos_ptr=None, seg_ptr=None, device_split=False, order="greedy"):
         """encode_batch_padded plus labels, positions, segments and cu_seqlens (mbpe_tok_encode_batch_aux_device): its
         arguments and those of pack_tokens_aux, whose dict (or, with out_ptr=, row count) is returned.  The documents'
         token offsets of the call: self.doc_tok_off."""
-        self._encode_split(device_split)
+        self._encode_split(device_split, order)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label)
         parts = [bytes(_u8(t)) for t in texts]

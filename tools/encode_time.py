@@ -8,7 +8,11 @@ time limit; when one fails, nothing after it is started.
             a pass over n tokens that leaves n' reads the token array three times (k_enc_cand, k_enc_match and the
             look-ahead of both count once each: 3 x 4n), writes cand twice and reads it twice (4 x 4n) and writes the
             output once (4n'); widen reads n bytes and writes 4n, the finishing kernel reads 4n and writes 4n.  The
-            per-pass token counts are the encoder's own (mbpe_encoder_pass_tokens).
+            per-pass token counts are the encoder's own (mbpe_encoder_pass_tokens).  With --rank-order every case
+            is timed in both orders by one process (option "rank_order" 0, then 1, on the same encoder and buffers): a
+            rank pass adds k_enc_rank_sum (reads tokens and cand: 2 x 4n) and k_enc_rank_filter (reads both, writes
+            cand: 3 x 4n) to the bytes above, and the one-chunk case makes one pass per merge that applies -- choose
+            --train-vocab accordingly.
   wall      wall clock, host text in, host tokens out, of a repeated Encoder.encode against the one-shot
             mbpe.encode_chunks of ANOTHER build of the library (--parent-root: a checkout of the parent commit with its
             libmbpe.so built), same inputs, shakespeare x 1, x 16, x 256; the two are run alternately, --rounds
@@ -50,18 +54,20 @@ def tiled(sh_off, n_sh, rep):
     return off
 
 
-def bytes_moved(n_bytes, pass_tokens, n_out, out_bytes_per_token):
+def bytes_moved(n_bytes, pass_tokens, n_out, out_bytes_per_token, rank_order=False):
     passes = 0
     for k, n in enumerate(pass_tokens):
         nxt = pass_tokens[k + 1] if k + 1 < len(pass_tokens) else n_out
-        passes += 28 * n + 4 * nxt
+        passes += (48 if rank_order else 28) * n + 4 * nxt
     widen = n_bytes + n_bytes // 8 + 4 * n_bytes
     finish = 4 * n_out + out_bytes_per_token * n_out
     return passes, widen + finish
 
 
-def kernel_case(name, enc, text_t, off, out_t, reps, torch):
+def kernel_case(name, enc, text_t, off, out_t, reps, torch, rank_order=False):
     n_bytes = text_t.numel()
+    enc.set_option("rank_order", int(rank_order))
+    name += "_rank" if rank_order else ""
 
     def run():
         n = enc.encode_device(text_t.data_ptr(), n_bytes, off, out_t.data_ptr(), out_t.numel(), 32)
@@ -71,8 +77,8 @@ def kernel_case(name, enc, text_t, off, out_t, reps, torch):
     ms = [run()[1] for _ in range(reps)]
     k = statistics.median(ms)
     pt = enc.pass_tokens()
-    in_passes, around = bytes_moved(n_bytes, pt, n_out, 4)
-    return {"case": name, "text_bytes": n_bytes, "chunks": 1 if off is None else len(off) - 1, "tokens": n_out,
+    in_passes, around = bytes_moved(n_bytes, pt, n_out, 4, rank_order)
+    return {"case": name, "order": "rank" if rank_order else "greedy", "kernel_ms_per_pass": k / max(len(pt), 1), "text_bytes": n_bytes, "chunks": 1 if off is None else len(off) - 1, "tokens": n_out,
             "passes": enc.n_passes, "pass_tokens": pt, "reps": reps, "kernel_ms_median": k, "kernel_ms_min": min(ms),
             "kernel_ms_max": max(ms), "text_GBps": n_bytes / k / 1e6, "bytes_moved_passes": in_passes,
             "bytes_moved_widen_finish": around, "bytes_per_pass_mean": in_passes / max(len(pt), 1),
@@ -91,17 +97,21 @@ def step_kernel(args):
     sh_off = mbpe.presplit(O.GPT4_SPLIT_PATTERN, sh)
     res = {"device": torch.cuda.get_device_name(0), "cases": []}
     with mbpe.Encoder(merges) as enc:
-        one = enc.encode(sh, sh_off)
         for rep in (64, 1024):
             text = torch.from_numpy(np.frombuffer(sh, dtype=np.uint8).copy()).to(dev).repeat(rep)
             off = tiled(sh_off, len(sh), rep)
-            out = torch.empty(len(one) * rep + 1, dtype=torch.int32, device=dev)
-            case = kernel_case("shakespeare_x%d_gpt4_512" % rep, enc, text, off, out, args.reps if rep == 64 else max(args.reps // 2, 3), torch)
-            got = out[:len(one) * rep].view(rep, len(one)) & 0x7FFFFFFF
-            assert case["tokens"] == len(one) * rep
-            assert bool((got == torch.from_numpy(one.view(np.int32)).to(dev)).all()), "tiles differ from one copy"
-            res["cases"].append(case)
-            del text, out, got
+            out = torch.empty(len(sh) * rep + 1, dtype=torch.int32, device=dev)
+            for rank_order in ((False, True) if args.rank_order else (False,)):
+                enc.set_option("rank_order", int(rank_order))
+                one = enc.encode(sh, sh_off)
+                case = kernel_case("shakespeare_x%d_gpt4_512" % rep, enc, text, off, out,
+                                   args.reps if rep == 64 else max(args.reps // 2, 3), torch, rank_order)
+                got = out[:len(one) * rep].view(rep, len(one)) & 0x7FFFFFFF
+                assert case["tokens"] == len(one) * rep
+                assert bool((got == torch.from_numpy(one.view(np.int32)).to(dev)).all()), "tiles differ from one copy"
+                res["cases"].append(case)
+                del got
+            del text, out
             torch.cuda.empty_cache()
     print(json.dumps(res))
 
@@ -120,15 +130,20 @@ def step_splitmix(args):
     train_s = time.perf_counter() - t
     text = torch.from_numpy(data).to(dev)
     out = torch.empty(len(data), dtype=torch.int32, device=dev)
+    cases = []
     with mbpe.Encoder(m) as enc, mbpe.Decoder(m) as dec:
-        case = kernel_case("splitmix64_%dMiB_one_chunk_vocab%d" % (args.train_mib, args.train_vocab), enc, text, None, out,
-                           max(args.reps // 2, 3), torch)
         back = torch.empty(len(data), dtype=torch.uint8, device=dev)
-        n_back, bad = dec.decode_slots_device(out.data_ptr(), case["tokens"], 32, 0x80000000, None, back.data_ptr(), len(data))
-        assert (n_back, bad) == (len(data), 0) and bool(torch.equal(back, text)), "decode(encode(text)) != text"
-    case["merges"] = len(m)
-    case["train_s"] = train_s
-    print(json.dumps({"cases": [case]}))
+        for rank_order in ((False, True) if args.rank_order else (False,)):
+            case = kernel_case("splitmix64_%dMiB_one_chunk_vocab%d" % (args.train_mib, args.train_vocab), enc, text, None,
+                               out, max(args.reps // 2, 3), torch, rank_order)
+            back.zero_()
+            n_back, bad = dec.decode_slots_device(out.data_ptr(), case["tokens"], 32, 0x80000000, None, back.data_ptr(),
+                                                  len(data))
+            assert (n_back, bad) == (len(data), 0) and bool(torch.equal(back, text)), "decode(encode(text)) != text"
+            case["merges"] = len(m)
+            case["train_s"] = train_s
+            cases.append(case)
+    print(json.dumps({"cases": cases}))
 
 
 def step_wall(args):
@@ -217,6 +232,8 @@ def main():
     ap.add_argument("--root", default=ROOT)
     ap.add_argument("--api", choices=("encoder", "oneshot"), default="encoder")
     ap.add_argument("--skip", default="", help="comma-separated steps to leave out")
+    ap.add_argument("--rank-order", action="store_true",
+                    help="kernel and splitmix steps: time every case in rank order too (option \"rank_order\")")
     args = ap.parse_args()
     if args.step:
         import torch
@@ -227,6 +244,7 @@ def main():
     skip = set(s for s in args.skip.split(",") if s)
     res, log = {}, []
     common = ["--reps", str(args.reps), "--train-mib", str(args.train_mib), "--train-vocab", str(args.train_vocab)]
+    common += ["--rank-order"] if args.rank_order else []
 
     def done():
         res["log"] = log
