@@ -248,6 +248,52 @@ MBPE_API int mbpe_train(mbpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes,
                         uint32_t *merges_out, int32_t *counts_out,
                         uint32_t *n_merges_out, mbpe_stats *stats_out);
 
+/* ---- continuing from existing merges --------------------------------- */
+
+/* Is `merges` a trained table: both sides of merge k below 256 + k, and no pair twice?  The condition under which the
+ * encoder's "rank_order" equals applying the merges one after the other (see mbpe_encoder_set_option), and the one
+ * mbpe_train_begin_from asks of its prior merges.  Host only, no device.  MBPE_OK, or MBPE_ERR_ARG with a message that
+ * names the first offending index.  An empty table is valid. */
+MBPE_API int mbpe_merges_check(const uint32_t *merges, uint32_t n_merges);
+
+/* mbpe_train_begin for a training that starts from the merges prior_merges[0 .. n_prior) instead of from raw bytes
+ * (a loaded model, an earlier training, a model of another corpus) and adds merges n_prior, n_prior + 1, ... -- tokens
+ * 256 + n_prior, ... -- up to vocab_size.  Same call order as mbpe_train_begin (after a load; "conflict_resolution"
+ * before it); n_prior == 0 IS mbpe_train_begin.
+ *   1. Every chunk of the loaded corpus becomes the token sequence that applying merge 0, 1, ... in order leaves: a
+ *      temporary encoder in rank order reads the context's text and end mask in place (chunks the load dropped or
+ *      made inert stay so) and is freed before the training buffers are allocated.
+ *   2. The pair table is a fresh count of the adjacent pairs of that stream, inside chunks, overlapping positions
+ *      included (calculate_freqs, Tokenizer.h:127-146: a a a gives (a, a) = 2); only pairs that occur are members.
+ *   3. The loop of Tokenizer.h:557-589 runs from there, unchanged: mbpe_train_steps, _sequences, _get_stream,
+ *      _get_pairs, _stream_device, _table_device, _decode_stream, _compact and _get_stats work as after
+ *      mbpe_train_begin.
+ * On the same corpus, training to V at once and training to V0 < V, then continuing to V, give the same merges and
+ * counts for as long as the chosen counts are >= 1: both tie-breaks depend on the current stream and counts alone.
+ * They part in the reference's degenerate tail: its table never erases, so once the maximal count is 0 it goes on
+ * merging zero-count pairs that history inserted; a continuation cannot know those pairs and ends when no pair is
+ * left, like the reference's loop with a table rebuilt at the point of resumption.
+ * mbpe_train_result returns the prior merges followed by the new ones, counts_out[k] = -1 for k < n_prior (no count
+ * was observed; 0 is a count the reference reports); steps_done_out / merges_done_out count new merges only,
+ * mbpe_stats.n_merges all of them, and ms_begin includes the encoder's device time.  n_prior == vocab_size - 256: the
+ * begin succeeds, the training is complete, the result is the prior table.
+ * Decided before the device is touched: MBPE_ERR_ARG for a table mbpe_merges_check refuses, for n_prior > vocab_size -
+ * 256 and for prior_merges NULL; MBPE_ERR_STATE for a context with several ranks (mbpe_comm_init*; "force_exchange");
+ * MBPE_ERR_VOCAB when vocab_size (or 256 + n_prior) lies beyond the 16-bit slot format of this corpus -- the 32-bit
+ * continuation does not start from existing merges -- and when "wide_from" is set.  MBPE_ERR_OOM, with the encoder's
+ * message, for a corpus above the one-piece limit of mbpe_encoder_encode_endmask; the peak of the begin is the replay,
+ * about 18.4 bytes of device memory per corpus byte.  MBPE_ERR_OVERFLOW for a pair that occurs 2^31
+ * times or more, as from mbpe_train_begin. */
+MBPE_API int mbpe_train_begin_from(mbpe_ctx *ctx, uint32_t vocab_size, const uint32_t *prior_merges, uint32_t n_prior);
+
+/* mbpe_train with prior merges: load + mbpe_train_begin_from + all steps + result.  merges_out must hold
+ * 2 * (vocab_size - 256) u32 and receives the prior merges first. */
+MBPE_API int mbpe_train_from(mbpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes,
+                             const uint64_t *chunk_off, uint64_t n_chunks, uint32_t vocab_size,
+                             int conflict_resolution, const uint32_t *prior_merges, uint32_t n_prior,
+                             uint32_t *merges_out, int32_t *counts_out,
+                             uint32_t *n_merges_out, mbpe_stats *stats_out);
+
 MBPE_API int mbpe_get_stats(mbpe_ctx *ctx, mbpe_stats *out);
 
 /* ---- introspection (parity tests) ----------------------------------- */

@@ -40,6 +40,17 @@ MBPE_API int mbpe_tok_train(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, 
 MBPE_API int mbpe_tok_train_split_device(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, uint32_t vocab_size,
                                          int conflict_resolution, int verbose, int device_id);
 
+/* Continues a training: the tokenizer's current merges -- loaded, set or trained -- are the prior table of
+ * mbpe_train_begin_from (mbpe.h), the training adds merges up to vocab_size on `text`, and on success the tokenizer
+ * holds prior + new merges, which mbpe_tok_save writes.  Pattern and special tokens stay.  device_split != 0 takes the
+ * route of mbpe_tok_train_split_device (and honours mbpe_tok_set_split_unicode).  Verbose prints the per-merge line
+ * of the new merges only.  A tokenizer without merges behaves like mbpe_tok_train.  Errors keep the code of the call
+ * that failed: MBPE_ERR_ARG for a vocab_size below the tokens the model has or a table mbpe_merges_check refuses (the
+ * tokenizer is unchanged then), MBPE_ERR_VOCAB beyond the 16-bit slot format, MBPE_ERR_OOM above the encoder's
+ * one-piece limit. */
+MBPE_API int mbpe_tok_train_continue(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, uint32_t vocab_size,
+                                     int conflict_resolution, int verbose, int device_id, int device_split);
+
 /* Direct access to the trained / loaded merges (2 u32 per merge). */
 MBPE_API int mbpe_tok_set_merges(mbpe_tokenizer *t, const uint32_t *merges, uint32_t n_merges);
 MBPE_API int mbpe_tok_get_merges(mbpe_tokenizer *t, uint32_t *merges_out, uint32_t cap, uint32_t *n_out);

@@ -23,6 +23,7 @@
 #include "mbpe_dev.h"
 #include <hip/hip_ext.h>
 
+#include <algorithm>
 #include <cstdlib>
 
 namespace mbpe {
@@ -4253,6 +4254,213 @@ __global__ __launch_bounds__(1024) void k_pair_total(const uint32_t *__restrict_
     if (ctl && total != expect) atomicOr(&ctl->err, kErrCountRange);
 }
 
+// ---- continuing from existing merges: token stream -> slots, pair table ------------------------------------------
+// mbpe_train_begin_from: the rank-ordered encoder leaves the corpus as 32-bit tokens, bit 31 = last token of its
+// chunk (a one-chunk corpus: of the text).  The kernels below build from them what k_widen[_barrier], k_pair_count_u8
+// and k_table_init build from bytes.
+
+// End-bit / one-chunk layout: token i -> slot i (the flag moves to bit 15 when FLAG), holes up to n_slots.
+// 8 slots per thread: two 16-byte loads, one 16-byte store.  2 B written + 4 B read per token.
+template <bool FLAG>
+__global__ void k_slots_from_tokens(const uint32_t *__restrict__ tok, uint64_t n_tok, uint16_t *__restrict__ slots,
+                                    uint64_t n_slots) {
+    uint64_t vec = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t n_vec = n_slots / 8;
+    for (; vec < n_vec; vec += stride) {
+        const uint64_t i0 = vec * 8;
+        uint32_t t[8];
+        if (i0 + 8 <= n_tok) {
+            const uint4 a = reinterpret_cast<const uint4 *>(tok + i0)[0], b = reinterpret_cast<const uint4 *>(tok + i0)[1];
+            t[0] = a.x; t[1] = a.y; t[2] = a.z; t[3] = a.w; t[4] = b.x; t[5] = b.y; t[6] = b.z; t[7] = b.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) t[j] = i0 + j < n_tok ? tok[i0 + j] : 0xFFFFFFFFu;
+        }
+        uint32_t s[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            s[j] = (t[j] & 0xFFFFu) | (FLAG ? (t[j] >> 31) << 15 : 0u);
+            if (i0 + j >= n_tok) s[j] = kHole;
+        }
+        reinterpret_cast<uint4 *>(slots + i0)[0] = pack8(s);
+    }
+}
+
+// Barrier layout, written sparsely like k_widen_barrier: token i -> slot 2i, slot 2i+1 = barrier behind the last
+// token of a chunk, else a hole; the host squeezes the holes out with the ordinary compaction.  4 tokens per thread.
+__global__ void k_slots_from_tokens_barrier(const uint32_t *__restrict__ tok, uint64_t n_tok, uint16_t *__restrict__ slots,
+                                            uint64_t n_slots) {
+    uint64_t vec = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t n_vec = n_slots / 8;
+    for (; vec < n_vec; vec += stride) {
+        const uint64_t i0 = vec * 4;
+        uint32_t s[8];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool in = i0 + j < n_tok;
+            const uint32_t t = in ? tok[i0 + j] : 0u;
+            s[2 * j] = in ? (t & 0xFFFFu) : kHole;
+            s[2 * j + 1] = in && (t >> 31) ? kBarrier : kHole;
+        }
+        reinterpret_cast<uint4 *>(slots + vec * 8)[0] = pack8(s);
+    }
+}
+
+// chunk ends among the tokens (the barrier slots the compaction will keep): one 64-bit atomic per workgroup
+__global__ __launch_bounds__(256) void k_token_ends(const uint32_t *__restrict__ tok, uint64_t n_tok,
+                                                   unsigned long long *n_ends) {
+    uint32_t mine = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_tok; i += (uint64_t)gridDim.x * blockDim.x)
+        mine += tok[i] >> 31;
+    mine = wave_sum(mine);
+    if (lane_id() == 0 && mine) atomicAdd(n_ends, (unsigned long long)mine);
+}
+
+// one (pair, count) into the global bins: the dense table's cell (raw count; k_bins_seal_dense sets the present
+// flags), or an open-addressed key / count table of the begin's own (PairBins) for the hashed layout -- there several
+// workgroups add the same new pair at once, which table_add's insert path does not allow: the bins take that, and
+// k_bins_insert then hands every distinct pair to table_add exactly once
+__device__ __forceinline__ void bins_add(const PairTable &t, const PairBins &bins, ResumeTally *tally, uint32_t key,
+                                         uint32_t n) {
+    if (!bins.key) {
+        atomicAdd(&t.cells[dense_index(t, key)], n);
+        return;
+    }
+    uint32_t h = hash_key(key) & bins.mask;
+    for (uint32_t probe = 0; probe <= bins.mask; ++probe) {
+        uint32_t k = bins.key[h];
+        if (k == kEmptyKey) k = atomicCAS(&bins.key[h], kEmptyKey, key);
+        if (k == kEmptyKey || k == key) { atomicAdd(&bins.cnt[h], n); return; }
+        h = (h + 1) & bins.mask;
+    }
+    atomicOr(&tally->err, kErrTableFull);
+}
+
+// The pair count over tokens (calculate_freqs, Tokenizer.h:127-146, on a merged stream): every position i whose token
+// is not the last of its chunk counts (tok[i], tok[i+1]), overlapping ones too.  Frequent pairs occur millions of
+// times, so a workgroup first counts in an LDS cache -- kPtSlots open-addressed (key, count) entries, up to kPtProbes
+// probes -- and flushes it once at its end: per position one LDS compare-and-swap (skipped when the key is there
+// already) and one LDS add; global atomics only for the cache's entries and for positions that found no entry.
+// A workgroup's share stays far below 2^32 positions (the grid has at least n / 2^20 workgroups), so an LDS count
+// cannot wrap.  ids: the token ids that exist; a token beyond them (never from a checked table) is an error, not an
+// address.  4 B read per token (the neighbour's load hits the same line).
+constexpr int kPtThreads = 256;
+constexpr uint32_t kPtSlots = 2048, kPtProbes = 4;
+__global__ __launch_bounds__(kPtThreads) void k_pair_count_tokens(const uint32_t *__restrict__ tok, uint64_t n_tok,
+                                                                  uint32_t ids, PairTable t, PairBins bins,
+                                                                  ResumeTally *tally) {
+    __shared__ uint32_t ckey[kPtSlots], ccnt[kPtSlots];
+    for (uint32_t i = threadIdx.x; i < kPtSlots; i += kPtThreads) { ckey[i] = kEmptyKey; ccnt[i] = 0; }
+    __syncthreads();
+    // contiguous share per workgroup, so that the cache sees a stretch of text
+    const uint64_t per = (n_tok + gridDim.x - 1) / gridDim.x;
+    const uint64_t lo = (uint64_t)blockIdx.x * per, hi = lo + per < n_tok ? lo + per : n_tok;
+    uint32_t counted = 0;
+    for (uint64_t i = lo + threadIdx.x; i < hi; i += kPtThreads) {
+        const uint32_t a = tok[i];
+        if ((a >> 31) || i + 1 >= n_tok) continue;
+        const uint32_t b = tok[i + 1] & 0x7FFFFFFFu;
+        if (a >= ids || b >= ids) { atomicOr(&tally->err, kErrMissingPair); continue; }
+        const uint32_t key = (a << 16) | b;
+        ++counted;
+        uint32_t h = hash_key(key) & (kPtSlots - 1);
+        bool done = false;
+#pragma unroll
+        for (uint32_t p = 0; p < kPtProbes && !done; ++p) {
+            uint32_t k = ckey[h];
+            if (k == kEmptyKey) k = atomicCAS(&ckey[h], kEmptyKey, key);
+            if (k == kEmptyKey || k == key) { atomicAdd(&ccnt[h], 1u); done = true; }
+            h = (h + 1) & (kPtSlots - 1);
+        }
+        if (!done) bins_add(t, bins, tally, key, 1u);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < kPtSlots; i += kPtThreads)
+        if (ckey[i] != kEmptyKey) bins_add(t, bins, tally, ckey[i], ccnt[i]);
+    counted = wave_sum(counted);
+    if (lane_id() == 0 && counted) atomicAdd(&tally->positions, (unsigned long long)counted);
+}
+
+// Dense layout: raw counts -> kPresent | count, with what k_table_init leaves beside the cells: n_entries and the
+// bounds the argmax walks.  One workgroup per block of 1,024 cells (one bmax entry), over the tile rows of ids that exist.
+__global__ __launch_bounds__(256) void k_bins_seal_dense(PairTable t, uint32_t n_blocks, DevCtl *ctl, ResumeTally *tally) {
+    __shared__ unsigned long long sh_max[256 / kWave];
+    __shared__ uint32_t sh_n[256 / kWave];
+    __shared__ unsigned long long sh_sum[256 / kWave];
+    for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
+        unsigned long long best = 0, sum = 0;
+        uint32_t n = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t e = (blk << kBlockShift) + (uint32_t)j * 256u + threadIdx.x;
+            const uint32_t v = t.cells[e];
+            if (!v) continue;
+            if (v >= kPresent) { atomicOr(&ctl->err, kErrCountRange); continue; }
+            t.cells[e] = kPresent | v;
+            ++n;
+            sum += v;
+            const unsigned long long p = pack_best((int32_t)v, dense_key(t, e));
+            best = p > best ? p : best;
+        }
+        best = wave_max_u64(best);
+        n = wave_sum(n);
+        for (int d = kWave / 2; d > 0; d >>= 1) sum += shfl_xor_u64(sum, d);
+        __syncthreads();
+        if (lane_id() == 0) { sh_max[threadIdx.x / kWave] = best; sh_n[threadIdx.x / kWave] = n; sh_sum[threadIdx.x / kWave] = sum; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < 256 / kWave; ++w) {
+                best = sh_max[w] > best ? sh_max[w] : best;
+                n += sh_n[w];
+                sum += sh_sum[w];
+            }
+            if (n) {
+                t.bmax[blk] = best;        // (this kernel is the block's only writer)
+                atomicMax(&t.smax[blk >> kBlockShift], best);
+                atomicAdd(&ctl->n_entries, n);
+                atomicAdd(&tally->total, sum);
+                atomicAdd(&tally->distinct, n);
+            }
+        }
+    }
+}
+
+// Hashed layout, first the bins' census (the host sizes the pair table by it) ...
+__global__ __launch_bounds__(256) void k_bins_tally(PairBins bins, ResumeTally *tally) {
+    unsigned long long sum = 0;
+    uint32_t n = 0;
+    const uint64_t slots = (uint64_t)bins.mask + 1;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (uint64_t)gridDim.x * blockDim.x) {
+        if (bins.key[i] == kEmptyKey) continue;
+        const uint32_t v = bins.cnt[i];
+        if (v >= kPresent) atomicOr(&tally->err, kErrCountRange);
+        ++n;
+        sum += v;
+    }
+    n = wave_sum(n);
+    for (int d = kWave / 2; d > 0; d >>= 1) sum += shfl_xor_u64(sum, d);
+    if (lane_id() == 0 && n) { atomicAdd(&tally->distinct, n); atomicAdd(&tally->total, sum); }
+}
+
+// ... then every distinct pair into the pair table, by the insert path k_apply takes: one thread per key
+__global__ __launch_bounds__(256) void k_bins_insert(PairBins bins, PairTable t, DevCtl *ctl) {
+    const uint64_t slots = (uint64_t)bins.mask + 1;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t key = bins.key[i], v = bins.cnt[i];
+        if (key == kEmptyKey || !v || v >= kPresent) continue;
+        table_add(t, ctl, key, (int32_t)v, true);
+    }
+}
+
+// the bins must add up to the positions counted (k_pair_total's check for bytes); the count kernel's flags join ctl's
+__global__ void k_resume_check(const ResumeTally *tally, DevCtl *ctl) {
+    uint32_t err = tally->err;
+    if (tally->total != tally->positions) err |= kErrCountRange;
+    if (err) atomicOr(&ctl->err, err);
+}
+
 inline int blocks_for(uint64_t n, int threads, int max_blocks) {
     uint64_t b = (n + threads - 1) / threads;
     if (b < 1) b = 1;
@@ -4640,6 +4848,51 @@ void launch_boundary_pairs(hipStream_t s, uint32_t *bp, const uint32_t *hdr, int
 void launch_pair_total(hipStream_t s, const uint32_t *bp, const uint32_t *pcount, unsigned long long expect,
                        unsigned long long *sum_out, DevCtl *ctl) {
     hipLaunchKernelGGL(k_pair_total, dim3(1), dim3(1024), 0, s, bp, pcount, expect, sum_out, ctl);
+}
+
+void launch_slots_from_tokens(hipStream_t s, const uint32_t *tok, uint64_t n_tok, uint32_t endbit, uint16_t *slots,
+                              uint64_t n_slots) {
+    if (!n_slots) return;
+    const dim3 grid(blocks_for(n_slots / 8, 256, 8192));
+    if (endbit == kBarrier)
+        hipLaunchKernelGGL(k_slots_from_tokens_barrier, grid, dim3(256), 0, s, tok, n_tok, slots, n_slots);
+    else if (endbit == kEndBit)
+        hipLaunchKernelGGL(k_slots_from_tokens<true>, grid, dim3(256), 0, s, tok, n_tok, slots, n_slots);
+    else
+        hipLaunchKernelGGL(k_slots_from_tokens<false>, grid, dim3(256), 0, s, tok, n_tok, slots, n_slots);
+}
+
+void launch_token_ends(hipStream_t s, const uint32_t *tok, uint64_t n_tok, unsigned long long *n_ends) {
+    if (!n_tok) return;
+    hipLaunchKernelGGL(k_token_ends, dim3(blocks_for(n_tok, 256 * 16, 4096)), dim3(256), 0, s, tok, n_tok, n_ends);
+}
+
+void launch_pair_count_tokens(hipStream_t s, const uint32_t *tok, uint64_t n_tok, uint32_t ids, PairTable t, PairBins bins,
+                              ResumeTally *tally, int n_cus) {
+    if (n_tok < 2) return;
+    // 8 workgroups of 16 KB LDS per CU; a workgroup's share is at least 4,096 tokens (so that the flush of its cache
+    // is paid for) and at most 2^20 (LDS counts cannot wrap)
+    uint64_t blocks = (uint64_t)(n_cus > 0 ? n_cus : 256) * 8;
+    blocks = std::min<uint64_t>(blocks, (n_tok + 4095) / 4096);
+    blocks = std::max<uint64_t>(blocks, (n_tok + (1u << 20) - 1) >> 20);
+    hipLaunchKernelGGL(k_pair_count_tokens, dim3((uint32_t)blocks), dim3(kPtThreads), 0, s, tok, n_tok, ids, t, bins, tally);
+}
+
+void launch_bins_seal_dense(hipStream_t s, PairTable t, uint32_t ids, DevCtl *ctl, ResumeTally *tally) {
+    const uint32_t n_blocks = std::min<uint32_t>(((ids + 31u) / 32u) << (t.vshift - 5u), t.ecap >> kBlockShift);
+    hipLaunchKernelGGL(k_bins_seal_dense, dim3(std::min<uint32_t>(n_blocks, 16384u)), dim3(256), 0, s, t, n_blocks, ctl, tally);
+}
+
+void launch_bins_tally(hipStream_t s, PairBins bins, ResumeTally *tally) {
+    hipLaunchKernelGGL(k_bins_tally, dim3(blocks_for((uint64_t)bins.mask + 1, 256 * 4, 4096)), dim3(256), 0, s, bins, tally);
+}
+
+void launch_bins_insert(hipStream_t s, PairBins bins, PairTable t, DevCtl *ctl) {
+    hipLaunchKernelGGL(k_bins_insert, dim3(blocks_for((uint64_t)bins.mask + 1, 256 * 4, 4096)), dim3(256), 0, s, bins, t, ctl);
+}
+
+void launch_resume_check(hipStream_t s, const ResumeTally *tally, DevCtl *ctl) {
+    hipLaunchKernelGGL(k_resume_check, dim3(1), dim3(1), 0, s, tally, ctl);
 }
 
 }  // namespace mbpe

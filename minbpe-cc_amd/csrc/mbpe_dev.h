@@ -399,6 +399,32 @@ void launch_boundary_pairs(hipStream_t s, uint32_t *bp, const uint32_t *hdr, int
 void launch_pair_total(hipStream_t s, const uint32_t *bp, const uint32_t *pcount, unsigned long long expect,
                        unsigned long long *sum_out, DevCtl *ctl);
 
+// ---- continuing from existing merges (mbpe_train_begin_from) ----
+// `tok`: the n_tok 32-bit tokens the rank-ordered encoder leaves on the device, bit 31 = last token of its chunk.
+// The pair counts are gathered in BINS first: the dense pair table's own cells (key == NULL), or -- hashed layout --
+// an open-addressed table of the begin's own (mask + 1 slots, key filled with kEmptyKey, cnt with 0) that takes
+// concurrent adds of a new pair, which the pair table's insert path does not.
+struct PairBins { uint32_t *key, *cnt; uint32_t mask; };
+// positions counted / sum and number of the bins / kErr* flags of the count kernel (zeroed by the host)
+struct ResumeTally { unsigned long long positions, total; uint32_t distinct, err; };
+// tokens -> 16-bit slots.  endbit 0 / kEndBit: slot i = token i, holes up to n_slots (a multiple of kTile).  kBarrier:
+// sparse like launch_widen_barrier -- token i in slot 2i, its barrier or a hole behind it; n_slots = 2 * (n_tok rounded
+// up to kTile / 2) -- for the compaction to squeeze
+void launch_slots_from_tokens(hipStream_t s, const uint32_t *tok, uint64_t n_tok, uint32_t endbit, uint16_t *slots,
+                              uint64_t n_slots);
+// *n_ends += tokens that end a chunk
+void launch_token_ends(hipStream_t s, const uint32_t *tok, uint64_t n_tok, unsigned long long *n_ends);
+// every adjacent pair inside a chunk -> bins (LDS cache per workgroup, flushed once); ids: token ids that exist
+void launch_pair_count_tokens(hipStream_t s, const uint32_t *tok, uint64_t n_tok, uint32_t ids, PairTable t, PairBins bins,
+                              ResumeTally *tally, int n_cus);
+// dense: raw counts in the cells -> present flags, ctl->n_entries, bmax / smax, tally->total / distinct
+void launch_bins_seal_dense(hipStream_t s, PairTable t, uint32_t ids, DevCtl *ctl, ResumeTally *tally);
+// hashed: tally->total / distinct of the bins; then every bin into the pair table (table_add, one thread per pair)
+void launch_bins_tally(hipStream_t s, PairBins bins, ResumeTally *tally);
+void launch_bins_insert(hipStream_t s, PairBins bins, PairTable t, DevCtl *ctl);
+// total != positions -> kErrCountRange; the tally's flags -> ctl->err
+void launch_resume_check(hipStream_t s, const ResumeTally *tally, DevCtl *ctl);
+
 }  // namespace mbpe
 
 #endif

@@ -173,6 +173,10 @@ struct mbpe_ctx {
     uint32_t n_valid = 0;        // merges known to be real (table was not empty)
     bool begun = false;
     bool exhausted = false;
+    uint32_t n_prior = 0;        // merges this training started from (mbpe_train_begin_from): best[0 .. n_prior) holds them
+    std::vector<unsigned long long> h_prior;   // ... as the begin uploads them: count field all ones (no count was observed)
+    ResumeTally *tally = nullptr;              // ... and the tally of its pair count
+    float ms_replay = 0;                       // ... and the device time of the encoder that replayed them
     double merges_per_seq = 0;   // measured over the last group of sequences (0: not known yet)
     uint32_t first_b = 0, first_s = 0;   // `first` mode: sequences / single-pair sequences seen since begin
     bool first_legacy = false;   // `first` mode: most batches were single pairs with a shared count (position tie-breaks):
@@ -349,6 +353,7 @@ void free_training(mbpe_ctx *c) {
     tfree(c, c->d_left); tfree(c, c->d_right); tfree(c, c->bs); tfree(c, c->sel); tfree(c, c->seq_flags); tfree(c, c->run_in);
     tfree(c, c->first_state);
     tfree(c, c->xf);
+    tfree(c, c->tally);
     tfree(c, c->wtok[0]); tfree(c, c->wtok[1]); tfree(c, c->wval); tfree(c, c->wscratch);
     tfree(c, c->wtab.keys); tfree(c, c->wtab.cnts); tfree(c, c->wctl); tfree(c, c->wbest); tfree(c, c->warg);
     tfree(c, c->wfs);
@@ -361,7 +366,7 @@ void free_training(mbpe_ctx *c) {
     c->LR = nullptr;
     c->pending = Phase::None;
     c->begun = false;
-    c->k = c->n_valid = 0;
+    c->k = c->n_valid = c->n_prior = 0;
     c->exhausted = false;
 }
 
@@ -909,19 +914,24 @@ static inline bool use_hier(const mbpe_ctx *c) {
 // words of xb0, all of which the begin exchanges: [bp 65,536][header][pairs counted: kPairCountWords limbs]
 static size_t begin_exchange_words(const mbpe_ctx *c) { return 65536 + (size_t)c->hdr_words + kPairCountWords; }
 
-static int begin_local(mbpe_ctx *c, uint32_t vocab_size) {
+// what a begin that continues from existing merges starts from instead of the bytes: the corpus as the rank-ordered
+// encoder left it (device, bit 31 = last token of its chunk) and the merges that made it
+struct ResumeSrc { const uint32_t *tok; uint64_t n_tok; const uint32_t *prior; uint32_t n_prior; };
+
+static int count_token_pairs(mbpe_ctx *c, const ResumeSrc *rs, uint64_t want);
+
+static int begin_local(mbpe_ctx *c, uint32_t vocab_size, const ResumeSrc *rs = nullptr) {
     free_training(c);
     c->vocab_size = vocab_size;
     c->n_target = vocab_size - 256;
-    c->k = 0;
-    c->n_valid = 0;
+    c->k = c->n_valid = c->n_prior = rs ? rs->n_prior : 0;
     c->exhausted = false;
     c->first_legacy = false;
     c->sel_attempts = 3;             // (the first selection of a training primes its threshold through attempts 1 and 2)
     c->merges_per_seq = 0;
     c->first_b = c->first_s = 0;
 
-    const uint64_t n = c->inert ? 0 : c->n_bytes;
+    const uint64_t n = rs ? rs->n_tok : c->inert ? 0 : c->n_bytes;      // tokens the stream starts with
     // barrier layout: written sparsely (byte i -> slot 2i, its barrier or a hole behind it) into a first buffer of
     // twice the size, squeezed into the second one below, and only then does the first one get its final size
     const uint64_t n_bar = c->barrier ? c->n_barriers : 0;
@@ -975,14 +985,15 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size) {
             HIPCHK(hipMemsetAsync(c->xf, 0, (size_t)c->hdr_words * 4, c->stream));
         }
     }
-    c->k_upper = 0;
+    c->k_upper = c->k;
     HIPCHK(tmalloc(c, &c->d_left, sizeof(RankEdge)));
     HIPCHK(tmalloc(c, &c->d_right, sizeof(RankEdge)));
     HIPCHK(tmalloc(c, &c->ctl, sizeof(DevCtl)));
     HIPCHK(tmalloc(c, &c->best, ((size_t)c->n_target + 2) * 8));
     {
         DevCtl init = {};
-        init.n_live = n + n_bar;         // every corpus byte starts as one live token
+        init.n_live = n + n_bar;         // every corpus byte (every token of a resumed stream) starts as one live token
+        init.k_done = c->k;
         init.n_ranks = (uint32_t)std::max(1, c->n_ranks);
         init.first_mode = c->opt_first ? 1u : 0u;
         init.adj_pitch = c->adj_pitch;
@@ -992,6 +1003,14 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size) {
         HIPCHK(hipMemcpyAsync(c->ctl, &c->h_ctl, sizeof(DevCtl), hipMemcpyHostToDevice, c->stream));
     }
     HIPCHK(hipMemsetAsync(c->best, 0, ((size_t)c->n_target + 2) * 8, c->stream));
+    if (c->k) {
+        // the merges this training continues from, as best[] holds a merge: (count, ~key) with every count bit set --
+        // mbpe_train_result reports that as -1, and as the latest count it rules nothing out (update_hot_possible)
+        c->h_prior.resize(c->k);
+        for (uint32_t i = 0; i < c->k; ++i)
+            c->h_prior[i] = pack_best(-1, (rs->prior[2 * i] << 16) | rs->prior[2 * i + 1]);
+        HIPCHK(hipMemcpyAsync(c->best, c->h_prior.data(), (size_t)c->k * 8, hipMemcpyHostToDevice, c->stream));
+    }
 
     // Sized for 288 GB of HBM: one entry per 8 corpus bytes up front (12 bytes of table per entry
     // plus 16 of hash index), so that even a corpus whose pairs never repeat rarely has to grow
@@ -999,17 +1018,19 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size) {
     uint64_t want = 65536 + 2 * batch_headroom(c, (uint32_t)c->opt_batch);
     want = std::max<uint64_t>(want, n / 8);
     want = std::min<uint64_t>(want, table_cap_limit(c));
-    int rc = use_dense(c) ? alloc_table_dense(c) : alloc_table(c, (uint32_t)want);
+    // (a resumed stream's hashed table is sized once its pairs are counted: count_token_pairs)
+    int rc = use_dense(c) ? alloc_table_dense(c) : rs ? MBPE_OK : alloc_table(c, (uint32_t)want);
     if (rc != MBPE_OK) return rc;
 
     rc = ensure_pc_scratch(c);
     if (rc != MBPE_OK) return rc;
     pool_trim(c);        // what this run did not take over from the previous one goes back to the driver
     HIPCHK(hipEventRecord(c->ev0, c->stream));
-    if (n >= 2) launch_pair_count_u8(c->stream, c->d_text, n, c->d_endmask, c->xb0, c->n_cus, c->pc_scratch);
+    if (!rs && n >= 2) launch_pair_count_u8(c->stream, c->d_text, n, c->d_endmask, c->xb0, c->n_cus, c->pc_scratch);
     c->cur = 0;
+    if (rs) launch_slots_from_tokens(c->stream, rs->tok, n, endbit_of(c), c->tok[0], c->n_slots);
     if (c->barrier) {
-        launch_widen_barrier(c->stream, c->d_text, n, c->d_endmask, c->tok[0], c->n_slots);
+        if (!rs) launch_widen_barrier(c->stream, c->d_text, n, c->d_endmask, c->tok[0], c->n_slots);
         launch_summarize(stream_view(c, kLiveFirst));
         const double ms_compact = c->stats.ms_compact;
         rc = do_compact(c);                     // tok[0] -> tok[1]; n_slots / n_tiles are the dense ones from here on
@@ -1020,9 +1041,10 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size) {
         pool_trim(c);
         HIPCHK(tmalloc(c, &c->tok[0], c->cap_slots * 2));
     } else {
-        launch_widen(c->stream, c->d_text, n, c->d_endmask, c->tok[0], c->n_slots);
+        if (!rs) launch_widen(c->stream, c->d_text, n, c->d_endmask, c->tok[0], c->n_slots);
         launch_summarize(stream_view(c, kLiveFirst));
     }
+    if (rs) return count_token_pairs(c, rs, want);
     if (is_multi(c)) {
         uint32_t *hdr = c->xb0 + 65536;
         launch_rank_edge(stream_view(c, kLiveFirst), hdr);
@@ -1030,6 +1052,55 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size) {
         for (uint32_t i = 0; i < kPairCountWords; ++i) c->h_pcount[i] = (uint32_t)(p >> (16 * i)) & 0xFFFFu;
         HIPCHK(hipMemcpyAsync(hdr + c->hdr_words, c->h_pcount, sizeof(c->h_pcount), hipMemcpyHostToDevice, c->stream));
     }
+    return MBPE_OK;
+}
+
+// The pair table of a resumed stream: a fresh count of its adjacent pairs (the counterpart of launch_pair_count_u8 +
+// launch_pair_total + launch_table_init), then the first argmax.  Dense layout: counted into the cells, sealed in place.
+// Hashed layout: counted into bins of the begin's own, whose census sizes the table (`want`: what a begin from bytes
+// would allocate) before every distinct pair is inserted once; the one host round trip of this path.
+static int count_token_pairs(mbpe_ctx *c, const ResumeSrc *rs, uint64_t want) {
+    const uint32_t ids = 256 + rs->n_prior;
+    HIPCHK(tmalloc(c, &c->tally, sizeof(ResumeTally)));
+    HIPCHK(hipMemsetAsync(c->tally, 0, sizeof(ResumeTally), c->stream));
+    if (c->tab.cells) {
+        launch_pair_count_tokens(c->stream, rs->tok, rs->n_tok, ids, c->tab, PairBins{nullptr, nullptr, 0}, c->tally, c->n_cus);
+        launch_bins_seal_dense(c->stream, c->tab, ids, c->ctl, c->tally);
+    } else {
+        // at most one bin per position and per possible pair; twice that many slots
+        const uint64_t most = std::min<uint64_t>(rs->n_tok, (uint64_t)ids * ids);
+        if (most > (1ull << 30)) {
+            mbpe_host::set_last_error("mbpe_train_begin_from: more than 2^30 pairs to count into the hashed table");
+            return MBPE_ERR_OVERFLOW;
+        }
+        PairBins bins = {nullptr, nullptr, next_pow2(std::max<uint64_t>(2 * most, 1024)) - 1};
+        const size_t slots = (size_t)bins.mask + 1;
+        HIPCHK(tmalloc(c, &bins.key, slots * 4));
+        HIPCHK(tmalloc(c, &bins.cnt, slots * 4));
+        launch_fill_u32(c->stream, bins.key, slots, kEmptyKey);
+        HIPCHK(hipMemsetAsync(bins.cnt, 0, slots * 4, c->stream));
+        launch_pair_count_tokens(c->stream, rs->tok, rs->n_tok, ids, c->tab, bins, c->tally, c->n_cus);
+        launch_bins_tally(c->stream, bins, c->tally);
+        ResumeTally h = {};
+        HIPCHK(hipMemcpyAsync(&h, c->tally, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        int rc = MBPE_OK;
+        if (h.distinct > table_cap_limit(c)) {
+            mbpe_host::set_last_error("mbpe_train_begin_from: the stream holds more distinct pairs than the pair table can");
+            rc = MBPE_ERR_OVERFLOW;
+        }
+        want = std::max<uint64_t>(want, (uint64_t)h.distinct + 2 * batch_headroom(c, (uint32_t)c->opt_batch));
+        want = std::min<uint64_t>(want, table_cap_limit(c));
+        if (rc == MBPE_OK) rc = alloc_table(c, (uint32_t)want);
+        if (rc == MBPE_OK) launch_bins_insert(c->stream, bins, c->tab, c->ctl);
+        tfree(c, bins.key);          // (handed out again, if at all, to work enqueued behind the insert)
+        tfree(c, bins.cnt);
+        if (rc != MBPE_OK) return rc;
+        c->h_ctl.n_entries = h.distinct;      // (use_hier: the table's size, until sync_ctl reads it)
+    }
+    launch_resume_check(c->stream, c->tally, c->ctl);
+    launch_argmax(c->stream, c->tab, c->ctl, c->best + c->k, use_hier(c));
+    if (c->opt_first) launch_first_tiebreak(stream_view(c, kLiveFirst), c->tab, c->best + c->k, c->first_state, c->xf, 0, 0);
     return MBPE_OK;
 }
 
@@ -1080,7 +1151,7 @@ static int begin_end(mbpe_ctx *c) {
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventElapsedTime(&c->stats.ms_begin, c->ev0, c->ev1));
     unsigned long long b0 = 0;
-    HIPCHK(hipMemcpy(&b0, c->best, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&b0, c->best + c->k, 8, hipMemcpyDeviceToHost));      // (k: the merges a resumed training starts from)
     c->exhausted = (b0 == 0);   // empty table: the reference loop breaks at once (Tokenizer.h:586-588)
     update_hot_possible(c, b0 >> 32, (uint64_t)std::max<int64_t>(c->opt_batch, 1) * kBatchMax);
     c->begun = true;
@@ -1430,6 +1501,138 @@ int mbpe_train_begin(mbpe_ctx *c, uint32_t vocab_size) {
     rc = finish_unit(c, Phase::BeginCounts);
     if (rc != MBPE_OK) return rc;
     return begin_end(c);
+}
+
+int mbpe_merges_check(const uint32_t *merges, uint32_t n_merges) {
+    if (!merges && n_merges) { mbpe_host::set_last_error("mbpe_merges_check: merges is NULL"); return MBPE_ERR_ARG; }
+    std::unordered_map<unsigned long long, uint32_t> seen;
+    seen.reserve(n_merges);
+    for (uint32_t k = 0; k < n_merges; ++k) {
+        const uint32_t a = merges[2 * k], b = merges[2 * k + 1];
+        if (a >= 256ull + k || b >= 256ull + k) {
+            mbpe_host::set_last_error("merge " + std::to_string(k) + ": (" + std::to_string(a) + ", " + std::to_string(b) +
+                                      ") names a token that does not exist before it (ids below " +
+                                      std::to_string(256ull + k) + ")");
+            return MBPE_ERR_ARG;
+        }
+        const auto ins = seen.emplace(((unsigned long long)a << 32) | b, k);
+        if (!ins.second) {
+            mbpe_host::set_last_error("merge " + std::to_string(k) + ": the pair (" + std::to_string(a) + ", " +
+                                      std::to_string(b) + ") is merge " + std::to_string(ins.first->second) + " already");
+            return MBPE_ERR_ARG;
+        }
+    }
+    return MBPE_OK;
+}
+
+// The replay of mbpe_train_begin_from: the loaded corpus through a temporary rank-ordered encoder, which reads the
+// context's text and end mask where they are.  *tok_out: n_bytes u32 of device memory of the call's own (the caller
+// frees it), holding *n_tok_out flagged tokens.  The encoder is gone before the training buffers are allocated.
+static int replay_prior(mbpe_ctx *c, const uint32_t *prior, uint32_t n_prior, uint32_t **tok_out, uint64_t *n_tok_out) {
+    *tok_out = nullptr;
+    *n_tok_out = 0;
+    c->ms_replay = 0;
+    const uint64_t n = c->inert ? 0 : c->n_bytes;
+    if (!n) return MBPE_OK;
+    free_training(c);        // (the peak of a resumed begin is the replay: nothing of an earlier training stays beside it)
+    pool_trim(c);
+    uint8_t *own_mask = nullptr;
+    mbpe_encoder *enc = nullptr;
+    auto run = [&]() -> int {
+        const uint8_t *mask = c->d_endmask;
+        if (!mask) {         // one chunk = the whole text: a mask with its last byte marked
+            const size_t mask_bytes = (n + 15) / 16 * 2 + 16;
+            const uint8_t bit = (uint8_t)(1u << ((n - 1) & 7));
+            HIPCHK(hipMalloc(&own_mask, mask_bytes));
+            HIPCHK(hipMemsetAsync(own_mask, 0, mask_bytes, c->stream));
+            HIPCHK(hipMemcpyAsync(own_mask + ((n - 1) >> 3), &bit, 1, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            mask = own_mask;
+        }
+        HIPCHK(hipMalloc(tok_out, n * 4));
+        int rc = mbpe_encoder_create(c->device, prior, n_prior, &enc);
+        if (rc == MBPE_OK) rc = mbpe_encoder_set_option(enc, "rank_order", 1);
+        if (rc == MBPE_OK)
+            rc = mbpe_encoder_encode_endmask(enc, c->d_text, n, mask, nullptr, 0, nullptr, 0, *tok_out, n, 32, 1, nullptr,
+                                             n_tok_out, nullptr);
+        if (rc == MBPE_OK) rc = mbpe_encoder_kernel_ms(enc, &c->ms_replay);
+        return rc;
+    };
+    const int rc = run();
+    const std::string keep = rc == MBPE_OK ? std::string() : std::string(mbpe_last_error());
+    mbpe_encoder_destroy(enc);
+    dfree(own_mask);
+    if (rc != MBPE_OK) {
+        dfree(*tok_out);
+        mbpe_host::set_last_error(keep);
+    }
+    return rc;
+}
+
+int mbpe_train_begin_from(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prior_merges, uint32_t n_prior) {
+    if (!c) return MBPE_ERR_ARG;
+    if (n_prior == 0) return mbpe_train_begin(c, vocab_size);
+    if (!c->loaded) { mbpe_host::set_last_error("mbpe_train_begin_from: no corpus loaded"); return MBPE_ERR_STATE; }
+    if (vocab_size < 256) { mbpe_host::set_last_error("vocab_size must be >= 256"); return MBPE_ERR_ARG; }
+    if (!prior_merges) { mbpe_host::set_last_error("mbpe_train_begin_from: prior_merges is NULL"); return MBPE_ERR_ARG; }
+    if (n_prior > vocab_size - 256) {
+        mbpe_host::set_last_error("mbpe_train_begin_from: " + std::to_string(n_prior) + " prior merges are more than vocab_size " +
+                                  std::to_string(vocab_size) + " holds");
+        return MBPE_ERR_ARG;
+    }
+    int rc = mbpe_merges_check(prior_merges, n_prior);
+    if (rc != MBPE_OK) return rc;
+    if (is_multi(c)) {
+        mbpe_host::set_last_error("mbpe_train_begin_from: continuing from existing merges runs on one rank only");
+        return MBPE_ERR_STATE;
+    }
+    const uint32_t vmax = !c->chunked ? MBPE_MAX_VOCAB_BASIC : c->opt_barrier == 0 ? MBPE_MAX_VOCAB_ENDBIT : MBPE_MAX_VOCAB_CHUNKED;
+    if (vocab_size > vmax || c->opt_wide_from >= 0) {
+        mbpe_host::set_last_error("mbpe_train_begin_from: vocab_size " + std::to_string(vocab_size) + " (with " +
+                                  std::to_string(n_prior) + " prior merges) lies beyond the 16-bit slot format of this corpus (" +
+                                  std::to_string(vmax) + "), or \"wide_from\" is set: the 32-bit continuation does not "
+                                  "start from existing merges");
+        return MBPE_ERR_VOCAB;
+    }
+    c->barrier = c->chunked && (c->opt_barrier == 1 || (c->opt_barrier != 0 && vocab_size > MBPE_MAX_VOCAB_ENDBIT));
+    c->wide = false;
+    HIPCHK(hipSetDevice(c->device));
+    uint32_t *tok = nullptr;
+    uint64_t n_tok = 0;
+    rc = replay_prior(c, prior_merges, n_prior, &tok, &n_tok);
+    if (rc != MBPE_OK) return rc;
+    auto rest = [&]() -> int {
+        if (c->barrier && n_tok) {
+            // the barrier slots the compaction keeps are the tokens' end flags: they must be the mask's end bits, by
+            // which the stream is sized
+            unsigned long long *d_ends = nullptr, ends = 0;
+            HIPCHK(hipMalloc(&d_ends, 8));
+            hipError_t e = hipMemsetAsync(d_ends, 0, 8, c->stream);
+            if (e == hipSuccess) { launch_token_ends(c->stream, tok, n_tok, d_ends); e = hipGetLastError(); }
+            if (e == hipSuccess) e = hipMemcpyAsync(&ends, d_ends, 8, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            (void)hipFree(d_ends);
+            HIPCHK(e);
+            if (ends != c->n_barriers) {
+                mbpe_host::set_last_error("mbpe_train_begin_from: the replay left " + std::to_string(ends) + " chunk ends, the "
+                                          "corpus has " + std::to_string(c->n_barriers));
+                return MBPE_ERR_STATE;
+            }
+        }
+        const ResumeSrc rs = {tok, n_tok, prior_merges, n_prior};
+        int r = begin_local(c, vocab_size, &rs);
+        c->vocab_total = vocab_size;
+        c->n_target_total = vocab_size - 256;
+        if (r != MBPE_OK) return r;
+        r = begin_end(c);
+        c->stats.ms_begin += c->ms_replay;
+        return r;
+    };
+    rc = rest();
+    (void)hipStreamSynchronize(c->stream);      // (the kernels that read the tokens are done)
+    dfree(tok);
+    pool_trim(c);
+    return rc;
 }
 
 // the batch-sequence loop of mbpe_train_steps (one GPU, or several over RCCL)
@@ -1869,7 +2072,7 @@ int mbpe_train_result(mbpe_ctx *c, uint32_t *merges_out, int32_t *counts_out, ui
     if (!c) return MBPE_ERR_ARG;
     if (!c->begun) { mbpe_host::set_last_error("mbpe_train_result before mbpe_train_begin"); return MBPE_ERR_STATE; }
     HIPCHK(hipSetDevice(c->device));
-    uint32_t n = c->exhausted ? 0 : c->n_valid;
+    uint32_t n = c->exhausted ? c->n_prior : c->n_valid;
     std::vector<unsigned long long> h(n);
     if (n) HIPCHK(hipMemcpy(h.data(), c->best, (size_t)n * 8, hipMemcpyDeviceToHost));
     if (c->opt_first) {
@@ -1901,9 +2104,9 @@ int mbpe_get_stats(mbpe_ctx *c, mbpe_stats *out) {
     if (!c || !out) return MBPE_ERR_ARG;
     c->stats.n_slots = c->begun ? c->n_slots : 0;
     c->stats.n_live = c->begun ? c->h_ctl.n_live - (c->barrier ? c->n_barriers : 0) : 0;      // (barriers are no tokens)
-    c->stats.n_merges = c->exhausted ? 0 : c->n_valid;
+    c->stats.n_merges = c->exhausted ? c->n_prior : c->n_valid;
     c->stats.n_pairs = c->begun ? c->h_ctl.n_entries : 0;
-    c->stats.n_batches = c->begun ? (use_batches(c) ? c->h_ctl.n_batches : c->k) : 0;
+    c->stats.n_batches = c->begun ? (use_batches(c) ? c->h_ctl.n_batches : c->k - c->n_prior) : 0;
     c->stats.n_fused = c->begun ? c->h_ctl.n_fused : 0;
     c->stats.n_fused_dropped = c->begun ? c->h_ctl.n_fused_dropped : 0;
     c->stats.cut_conflict = c->begun ? c->h_ctl.cut_conflict : 0;
@@ -1932,6 +2135,13 @@ int mbpe_get_stats(mbpe_ctx *c, mbpe_stats *out) {
 int mbpe_train(mbpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off, uint64_t n_chunks,
                uint32_t vocab_size, int conflict_resolution, uint32_t *merges_out, int32_t *counts_out,
                uint32_t *n_merges_out, mbpe_stats *stats_out) {
+    return mbpe_train_from(c, text, n_bytes, chunk_off, n_chunks, vocab_size, conflict_resolution, nullptr, 0, merges_out,
+                           counts_out, n_merges_out, stats_out);
+}
+
+int mbpe_train_from(mbpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off, uint64_t n_chunks,
+                    uint32_t vocab_size, int conflict_resolution, const uint32_t *prior_merges, uint32_t n_prior,
+                    uint32_t *merges_out, int32_t *counts_out, uint32_t *n_merges_out, mbpe_stats *stats_out) {
     if (!c || !merges_out) { mbpe_host::set_last_error("mbpe_train: NULL argument"); return MBPE_ERR_ARG; }
     if (conflict_resolution != 0 && conflict_resolution != 1) {
         mbpe_host::set_last_error("conflict_resolution: 0 = first, 1 = lexical");
@@ -1941,7 +2151,7 @@ int mbpe_train(mbpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_
     if (rc != MBPE_OK) return rc;
     const int64_t keep = c->opt_first;
     c->opt_first = conflict_resolution == 0;
-    rc = mbpe_train_begin(c, vocab_size);
+    rc = mbpe_train_begin_from(c, vocab_size, prior_merges, n_prior);
     if (rc == MBPE_OK) rc = mbpe_train_steps(c, vocab_size - 256, nullptr);
     if (rc == MBPE_OK) rc = mbpe_train_result(c, merges_out, counts_out, vocab_size - 256, n_merges_out);
     if (rc == MBPE_OK && stats_out) mbpe_get_stats(c, stats_out);

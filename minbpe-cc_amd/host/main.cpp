@@ -73,13 +73,17 @@ void usage() {
                  "  --device-split-unicode      --device-split, with non-ASCII text split on the device as well\n"
                  "  --rank-order                When encoding, apply the merges in rank order (a chunk's pair with the lowest\n"
                  "                              merge id first: the segmentation the model was trained on) instead of the\n"
-                 "                              reference's greedy passes; on the host and with --device-encode\n";
+                 "                              reference's greedy passes; on the host and with --device-encode\n"
+                 "  --continue-from TEXT        With --train: load this model and continue its training on the input up to\n"
+                 "                              --vocab-size, which must not be below the model's size; the result goes to\n"
+                 "                              --model-path.  The loaded model's split pattern is used: --encoder has no\n"
+                 "                              effect then.  One HIP device, vocabularies within the 16-bit slot format\n";
 }
 
 }  // namespace
 
 int main(int argc, char *argv[]) {
-    std::string input_path, output_path, special_token_path, encoder = "gpt4", model_path = "./output.model";
+    std::string input_path, output_path, special_token_path, encoder = "gpt4", model_path = "./output.model", continue_from;
     std::string conflict_resolution_str = "first";
     bool train = false, decode = false, encode = false, write_vocab = false, verbose = false, device_encode = false,
          device_decode = false, device_split = false, split_unicode = false, rank_order = false;
@@ -104,6 +108,7 @@ int main(int argc, char *argv[]) {
         else if (arg == "-s" || arg == "--special-tokens-path") { if (!value(&special_token_path)) return 106; }
         else if (arg == "-m" || arg == "--model-path") { if (!value(&model_path)) return 106; }
         else if (arg == "--encoder") { if (!value(&encoder)) return 106; }
+        else if (arg == "--continue-from") { if (!value(&continue_from)) return 106; }
         else if (arg == "--vocab-size") {
             if (!value(&tmp)) return 106;
             try { vocab_size = std::stoi(tmp); } catch (...) { std::cerr << "--vocab-size: invalid integer " << tmp << "\n"; return 104; }
@@ -159,6 +164,12 @@ int main(int argc, char *argv[]) {
         return -1;
     }
     int rc = 0;
+    if (train && !continue_from.empty() &&
+        (!exists(continue_from) || mbpe_tok_load(rt, continue_from.c_str(), verbose) != MBPE_OK)) {
+        std::cerr << "Model file " << continue_from << " does not exist or could not be loaded\n";
+        mbpe_tok_destroy(rt);
+        return -1;
+    }
     if (train) {                                                // :181-211
         if (have_special) mbpe_tok_set_special_tokens(rt, special_tokens_data.data(), special_tokens_data.size());
         else std::cout << "No special tokens file provided\n";
@@ -169,9 +180,13 @@ int main(int argc, char *argv[]) {
         if (load_file_to_string(input_path, &input, &err)) {
             if (verbose) std::cout << "Starting training...\n";
             if (split_unicode) mbpe_tok_set_split_unicode(rt, 1);
-            if ((device_split ? mbpe_tok_train_split_device : mbpe_tok_train)(
-                    rt, reinterpret_cast<const uint8_t *>(input.data()), input.size(), (uint32_t)vocab_size,
-                    conflict_resolution_str == "lexical" ? 1 : 0, verbose, device) != MBPE_OK) {
+            const uint8_t *in = reinterpret_cast<const uint8_t *>(input.data());
+            const int cr = conflict_resolution_str == "lexical" ? 1 : 0;
+            const int trc = !continue_from.empty()
+                                ? mbpe_tok_train_continue(rt, in, input.size(), (uint32_t)vocab_size, cr, verbose, device, device_split)
+                                : (device_split ? mbpe_tok_train_split_device : mbpe_tok_train)(rt, in, input.size(),
+                                                                                                (uint32_t)vocab_size, cr, verbose, device);
+            if (trc != MBPE_OK) {
                 std::cerr << "Error: " << mbpe_last_error() << "\n";
                 rc = -1;
             } else {

@@ -164,8 +164,19 @@ void Tokenizer::set_special_tokens_from_file(const std::string &input_string) { 
 }
 
 void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTION conflict_resolution,
-                      bool verbose, int device, bool device_split) {
+                      bool verbose, int device, bool device_split, bool resume) {
     if (vocab_size < 256) throw std::runtime_error("vocab_size must be >= 256");   // assert, :492
+    // the table a resumed training continues from: what the tokenizer holds (checked before anything is dropped)
+    std::vector<uint32_t> prior;
+    if (resume) {
+        for (const TokenPair &mp : merges_) { prior.push_back(mp.first); prior.push_back(mp.second); }
+        if (prior.size() / 2 > static_cast<size_t>(vocab_size - 256))
+            throw CodedError(MBPE_ERR_ARG, "vocab_size " + std::to_string(vocab_size) + " is below the " +
+                                               std::to_string(256 + prior.size() / 2) + " tokens the model already has");
+        if (mbpe_merges_check(prior.data(), static_cast<uint32_t>(prior.size() / 2)) != MBPE_OK)
+            throw CodedError(MBPE_ERR_ARG, mbpe_last_error());
+    }
+    const uint32_t n_prior = static_cast<uint32_t>(prior.size() / 2);
     drop_decoder();
     drop_encoder();
     merges_.clear();
@@ -215,13 +226,14 @@ void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTI
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "conflict_resolution", conflict_resolution == LEXICAL ? 1 : 0);
     // (`first` beyond the 16-bit slot format continues on 32-bit tokens, as the reference's uint32_t Token does)
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "first_wide", 1);
-    if (rc == MBPE_OK) rc = mbpe_train_begin(ctx, static_cast<uint32_t>(vocab_size));
+    if (rc == MBPE_OK) rc = mbpe_train_begin_from(ctx, static_cast<uint32_t>(vocab_size), prior.data(), n_prior);
     if (rc == MBPE_OK) rc = mbpe_train_steps(ctx, cap, nullptr);
     if (rc == MBPE_OK) rc = mbpe_train_result(ctx, flat.data(), had.data(), cap, &n_merges);
     if (rc == MBPE_OK) rc = mbpe_get_stats(ctx, &st);
     std::string msg = rc == MBPE_OK ? "" : mbpe_last_error();
     mbpe_destroy(ctx);
     mbpe_splitter_destroy(dev_split);       // (its text and mask were in use until here)
+    if (rc != MBPE_OK && resume) throw CodedError(rc, msg);      // (mbpe_tok_train_continue hands the code on)
     if (rc != MBPE_OK) throw std::runtime_error(msg);
 
     const int total_merges = vocab_size - 256;
@@ -230,7 +242,7 @@ void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTI
         std::vector<Token> appended{vocab_[mp.first]};
         appended.insert(appended.end(), vocab_[mp.second].begin(), vocab_[mp.second].end());
         vocab_.push_back(appended);
-        if (verbose) {                                   // :565-577
+        if (verbose && k >= n_prior) {                   // :565-577 (a resumed training: the new merges)
             std::string s;
             for (auto c : appended) s += (c >= 32 && c < 127) ? static_cast<char>(c) : ' ';
             std::cout << "merge " << k + 1 << "/" << total_merges << ": (" << mp.first << ", " << mp.second
@@ -788,6 +800,23 @@ int mbpe_tok_train_split_device(mbpe_tokenizer *t, const uint8_t *text, uint64_t
                     device_id, true);
         return MBPE_OK;
     } catch (const mbpe_host::CodedError &e) {       // the splitter's own code: MBPE_ERR_ARG for a custom pattern
+        mbpe_host::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        mbpe_host::set_last_error(e.what());
+        return MBPE_ERR_ARG;
+    }
+}
+
+int mbpe_tok_train_continue(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, uint32_t vocab_size,
+                            int conflict_resolution, int verbose, int device_id, int device_split) {
+    if (!t || (!text && n)) return MBPE_ERR_ARG;
+    try {
+        t->t->train(std::string(reinterpret_cast<const char *>(text), n), (int)vocab_size,
+                    conflict_resolution ? mbpe_host::Tokenizer::LEXICAL : mbpe_host::Tokenizer::FIRST, verbose != 0,
+                    device_id, device_split != 0, true);
+        return MBPE_OK;
+    } catch (const mbpe_host::CodedError &e) {
         mbpe_host::set_last_error(e.what());
         return e.code;
     } catch (const std::exception &e) {

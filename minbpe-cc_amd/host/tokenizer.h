@@ -34,8 +34,11 @@ public:
     // device_split: the gpt2 / gpt4 pre-split runs on the device too (mbpe_splitter_split; the text is uploaded once
     // and the trainer takes text and end mask in place).  Same merges.  A tokenizer with any other pattern throws
     // CodedError(MBPE_ERR_ARG): there is no silent return to the host split
+    // resume: the tokenizer's current merges (loaded, set or trained) are the prior table of mbpe_train_begin_from: the
+    // training continues from them up to vocab_size, pattern and special tokens stay, and afterwards the tokenizer holds
+    // prior + new merges.  Verbose prints the per-merge line of the new merges only.  Without merges: an ordinary train
     void train(const std::string &text, int vocab_size, CONFLICT_RESOLUTION conflict_resolution, bool verbose,
-               int device = 0, bool device_split = false);
+               int device = 0, bool device_split = false, bool resume = false);
     // :653-722; device >= 0 runs internal_encode (:325-377) on that HIP device instead of the host.
     // device_split (with device >= 0, here and in the batch calls below): the text is also cut at the special tokens
     // and split into chunks on the device (mbpe_splitter_split_docs with a splitter that is kept), and the encoder

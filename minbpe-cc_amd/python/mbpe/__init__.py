@@ -37,6 +37,7 @@ EXPORTS = [
     "mbpe_splitter_endmask", "mbpe_splitter_set_option", "mbpe_splitter_kernel_ms", "mbpe_splitter_alloc_count",
     "mbpe_splitter_host_spans", "mbpe_splitter_split_docs", "mbpe_splitter_ranges", "mbpe_splitter_find_ms",
     "mbpe_encoder_encode_endmask", "mbpe_encoder_encode_batch_endmask", "mbpe_split_unicode_table",
+    "mbpe_merges_check", "mbpe_train_begin_from", "mbpe_train_from",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -45,7 +46,7 @@ TOK_EXPORTS = [
     "mbpe_tok_decode", "mbpe_tok_decode_device", "mbpe_tok_encode_batch_device", "mbpe_tok_decode_batch_device",
     "mbpe_tok_encode_batch_packed_device", "mbpe_tok_decode_padded_device", "mbpe_tok_encode_batch_aux_device",
     "mbpe_tok_train_split_device", "mbpe_tok_set_encode_split", "mbpe_tok_set_split_unicode",
-    "mbpe_tok_set_encode_order",
+    "mbpe_tok_set_encode_order", "mbpe_tok_train_continue",
 ]
 
 
@@ -142,6 +143,9 @@ def lib():
     L.mbpe_train_result.argtypes = [vp, vp, vp, u32, vp]
     L.mbpe_train_lexical.argtypes = [vp, vp, u64, vp, u64, u32, vp, vp, vp, vp]
     L.mbpe_train.argtypes = [vp, vp, u64, vp, u64, u32, i32, vp, vp, vp, vp]
+    L.mbpe_merges_check.argtypes = [vp, u32]
+    L.mbpe_train_begin_from.argtypes = [vp, u32, vp, u32]
+    L.mbpe_train_from.argtypes = [vp, vp, u64, vp, u64, u32, i32, vp, u32, vp, vp, vp, vp]
     L.mbpe_get_stats.argtypes = [vp, vp]
     L.mbpe_get_stream.argtypes = [vp, vp, vp, u64, vp]
     L.mbpe_stream_device.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(u32), ctypes.POINTER(u32),
@@ -209,6 +213,7 @@ def lib():
     L.mbpe_tok_set_special_tokens.argtypes = [vp, ctypes.c_char_p, u64]
     L.mbpe_tok_train.argtypes = [vp, vp, u64, u32, i32, i32, i32]
     L.mbpe_tok_train_split_device.argtypes = L.mbpe_tok_train.argtypes
+    L.mbpe_tok_train_continue.argtypes = L.mbpe_tok_train.argtypes + [i32]
     L.mbpe_load_corpus_endmask.argtypes = [vp, vp, u64, i32, vp]
     L.mbpe_splitter_create.argtypes = [i32, ctypes.c_char_p, ctypes.POINTER(vp)]
     L.mbpe_splitter_destroy.argtypes = [vp]
@@ -250,6 +255,17 @@ def _u8(data):
     if isinstance(data, np.ndarray):
         return np.ascontiguousarray(data, dtype=np.uint8)
     return np.frombuffer(data, dtype=np.uint8)
+
+
+def _merges(merges):
+    return np.ascontiguousarray([] if merges is None else merges, dtype=np.uint32).reshape(-1, 2)
+
+
+def merges_check(merges):
+    """mbpe_merges_check: raises MbpeError(ERR_ARG), naming the first offending index, unless both sides of merge k are
+    below 256 + k and no pair occurs twice (a trained table).  Host only."""
+    m = _merges(merges)
+    _check(lib().mbpe_merges_check(m.ctypes.data if len(m) else None, len(m)))
 
 
 def split_pattern(encoder):
@@ -1049,10 +1065,16 @@ class Trainer:
         _check(lib().mbpe_pair_count_u8(self._h, None if table is None else table.ctypes.data))
         return table
 
-    def train_begin(self, vocab_size):
-        """Returns NEED_EXCHANGE in external-transport mode, else OK."""
+    def train_begin(self, vocab_size, prior_merges=None):
+        """Returns NEED_EXCHANGE in external-transport mode, else OK.  prior_merges ([n, 2]): continue from these
+        merges instead of from raw bytes (mbpe_train_begin_from)."""
+        if prior_merges is None:
+            rc = _check(lib().mbpe_train_begin(self._h, vocab_size))
+        else:
+            m = _merges(prior_merges)
+            rc = _check(lib().mbpe_train_begin_from(self._h, vocab_size, m.ctypes.data if len(m) else None, len(m)))
         self.vocab_size = vocab_size
-        return _check(lib().mbpe_train_begin(self._h, vocab_size))
+        return rc
 
     def train_steps(self, n_steps):
         """Returns the number of merges made (external-transport mode: NEED_EXCHANGE / OK code)."""
@@ -1093,20 +1115,23 @@ class Trainer:
     def train_lexical(self, data, vocab_size, chunk_off=None):
         return self.train(data, vocab_size, chunk_off, conflict_resolution=1)
 
-    def train(self, data, vocab_size, chunk_off=None, conflict_resolution=1):
-        """conflict_resolution: 1 = lexical, 0 = first (mbpe_train)."""
+    def train(self, data, vocab_size, chunk_off=None, conflict_resolution=1, prior_merges=None):
+        """conflict_resolution: 1 = lexical, 0 = first (mbpe_train).  prior_merges: continue from them (mbpe_train_from);
+        the result then starts with them, with counts of -1."""
         text = _u8(data)
+        prior = _merges(prior_merges)
         off = None if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.uint64)
         cap = max(vocab_size - 256, 1)
         merges = np.zeros((cap, 2), dtype=np.uint32)
         counts = np.zeros(cap, dtype=np.int32)
         n = ctypes.c_uint32()
         st = Stats()
-        _check(lib().mbpe_train(self._h, text.ctypes.data if len(text) else None, len(text),
-                                None if off is None else off.ctypes.data,
-                                0 if off is None else len(off) - 1, vocab_size, conflict_resolution,
-                                merges.ctypes.data, counts.ctypes.data, ctypes.byref(n),
-                                ctypes.byref(st)))
+        _check(lib().mbpe_train_from(self._h, text.ctypes.data if len(text) else None, len(text),
+                                     None if off is None else off.ctypes.data,
+                                     0 if off is None else len(off) - 1, vocab_size, conflict_resolution,
+                                     prior.ctypes.data if len(prior) else None, len(prior),
+                                     merges.ctypes.data, counts.ctypes.data, ctypes.byref(n),
+                                     ctypes.byref(st)))
         self.vocab_size = vocab_size
         return merges[:n.value].copy(), counts[:n.value].copy(), st.as_dict()
 
@@ -1203,12 +1228,19 @@ class Tokenizer:
         b = text if isinstance(text, bytes) else text.encode("utf-8")
         _check(lib().mbpe_tok_set_special_tokens(self._h, b, len(b)))
 
-    def train(self, data, vocab_size, conflict_resolution=1, verbose=False, device=0, device_split=False):
-        """device_split: the gpt2 / gpt4 pre-split runs on the device too (same merges); a tokenizer with any other
+    def train(self, data, vocab_size, conflict_resolution=1, verbose=False, device=0, device_split=False,
+              resume=False):
+        """resume: continue from the merges the tokenizer holds (loaded, set or trained) up to vocab_size instead of
+        starting from raw bytes (mbpe_tok_train_continue); pattern and special tokens stay.
+        device_split: the gpt2 / gpt4 pre-split runs on the device too (same merges); a tokenizer with any other
         pattern raises MbpeError(ERR_ARG).  "unicode" instead of True: with the splitter's option "unicode", so that
         well-formed non-ASCII text is split there as well (mbpe_tok_set_split_unicode)."""
         text = _u8(data)
         _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
+        if resume:
+            _check(lib().mbpe_tok_train_continue(self._h, text.ctypes.data if len(text) else None, len(text), vocab_size,
+                                                 conflict_resolution, int(verbose), device, int(bool(device_split))))
+            return
         fn = lib().mbpe_tok_train_split_device if device_split else lib().mbpe_tok_train
         _check(fn(self._h, text.ctypes.data if len(text) else None, len(text), vocab_size, conflict_resolution,
                   int(verbose), device))
