@@ -113,7 +113,8 @@ typedef struct {
     uint32_t n_skip_cut;       /* ... that had not fallen behind the batch after all (the batch was cut there) */
     uint64_t exchange_words;   /* multi-GPU: u32 words sum-all-reduced for the count deltas of all sequences so far */
     uint32_t exchanges;        /* ... in this many all-reduces (one per sequence) */
-    uint32_t pad_;
+    uint32_t log_spilled;      /* "pair_cells": matches that qualified for the delta log but found it full and were counted
+                                  with atomics instead (this training) */
     uint64_t fused_live_tokens; /* "time_kernels": live tokens before + live tokens after, summed over the timed fused
                                    passes (x 2 bytes = SURVEY 8(d)'s 2 B x L read + 2 B x L' written of those passes).
                                    In the barrier layout ("chunk_barrier") both terms include one barrier slot per chunk,
@@ -121,7 +122,9 @@ typedef struct {
                                    merge_launches */
     float    ms_pair_count_kernel; /* mbpe_pair_count_u8 without a table: mean KERNEL duration of the call's launches
                                    (start/stop events of each dispatch: no gap between launches, no marker overhead) */
-    uint32_t pad2_;
+    uint32_t log_passes;       /* "pair_cells": stream passes whose count deltas went through the delta log (this training) */
+    uint32_t log_refills;      /* "pair_cells": log chunks taken by waves that had filled an earlier one (this training) */
+    uint32_t pad3_;
 } mbpe_stats;
 
 MBPE_API const char *mbpe_last_error(void);
@@ -364,11 +367,18 @@ MBPE_API int mbpe_compact(mbpe_ctx *ctx);
  *                   kernels that sequence needs (one event wait per sequence, ~12 launches instead of ~27), 0 = it
  *                   enqueues whole groups of sequences with every kernel variant and the device decides which work;
  *                   -1 (default): 1 for streams of up to 32 Mi slots on one rank, 0 otherwise.  Same results.
- *   "pair_cells"    a match whose two neighbours are raw bytes costs the stream pass one atomic on a byte x byte cell block
- *                   of its pair (65,536 u32 per pair of the largest batch: 1 GiB at the default "max_batch"), folded into
- *                   the pair's delta rows right behind the pass, instead of two atomics on the rows: 1 / 0, -1 (default) =
- *                   for streams of 64 Mi slots and more, where the passes of thousands of byte pairs are bound by their
- *                   atomics; read by mbpe_train_begin.  Same results.
+ *   "pair_cells"    a match whose two neighbours are raw bytes, with no other match touching it, costs the stream pass
+ *                   one 4-byte record in a log instead of two atomics on its pair's delta rows; three small kernels
+ *                   around the pass sort the records into buckets of 64 pairs and count them in LDS (the name is that
+ *                   of the byte x byte cell blocks the log replaced).  1 / 0, -1 (default) = for streams of 64 Mi slots
+ *                   and more, where the passes of thousands of byte pairs are bound by their atomics; 1 also logs the
+ *                   small batches the default leaves alone.  Read by mbpe_train_begin.  Same results.
+ *   "log_cap"       records the log holds (0, the default: a sixteenth of the slots, between 2^20 and 2^28: 1 GiB on the
+ *                   benchmark, plus a partition buffer of 2 GiB at most).  A wave that finds the log full counts with
+ *                   atomics instead (mbpe_stats.log_spilled); tests reach that with a small value.  Read by
+ *                   mbpe_train_begin.
+ *   "log_chunk"     records a wave of the pass reserves at a time (0, the default: 4,096, less on a small log; rounded
+ *                   to multiples of 256, one tile's most, and at most 65,536); read by mbpe_train_begin
  *   "wide_from"     tests: hand over to the 32-bit continuation after this many merges whatever the vocabulary
  *                   (-1, the default: where the 16-bit slot format ends); read by mbpe_train_begin
  *   "first_wide"    `first` tie-break beyond the 16-bit slot format, one rank: 0 (default) = MBPE_ERR_VOCAB, 1 = the

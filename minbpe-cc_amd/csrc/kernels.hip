@@ -2903,6 +2903,59 @@ __device__ __forceinline__ bool tt_needed(const uint32_t s[8], const uint32_t nx
     return __ballot(need) != 0ull || hneed;
 }
 
+// ---- the delta log: the stream pass's side ------------------------------------------------------
+// A match of batch pair j whose neighbours x, y are raw bytes, with both sides open and no other match touching it, owes
+// the LR block L_j[x] += 1 and R_j[y] += 1.  In the passes of thousands of byte pairs nearly every match is of that kind and
+// the scattered atomics bound the pass, so it writes ONE 4-byte record (j << 16) | (x << 8) | y into a log instead, and
+// three small kernels behind the pass count the records in LDS (k_log_plan, k_log_partition, k_log_count below).
+// A wave holds a chunk [pos, end) of the log and writes records straight from the slot loop, at the wave prefix of the
+// slot's eligible lanes: no LDS, no returning atomic per match.  It takes the next chunk -- one returning atomic on
+// LogState::cursor -- when fewer than kLogChunkMin slots are left, a tile's most, and fills what it leaves unused with
+// kLogNull.  A wave that finds the log full counts its eligible matches with the two atomics from then on.
+struct LogWave {
+    uint32_t pos, end;          // (uniform) the wave's chunk, in records
+    uint32_t cap, chunk;        // (uniform) LogState::cap, ::chunk
+    bool full;                  // (uniform) the log refused a chunk: do not ask again.  Every wave adds its refused
+                                //   chunk to the cursor once: cap (<= 2^29) + waves x chunk (<= 2^16: train.cpp) stays
+                                //   far below 2^32, so the cursor cannot wrap
+    uint32_t spilled;           // (per lane) eligible matches counted with atomics instead
+    LogState *ls;
+    uint32_t *refills;          // DevCtl::log_refills
+};
+__device__ __forceinline__ LogWave log_wave(LogState *ls, bool use_log, const DevCtl *ctl) {
+    return LogWave{0u, 0u, use_log ? rfl(ls->cap) : 0u, use_log ? rfl(ls->chunk) : 0u, false, 0u, ls,
+                   const_cast<uint32_t *>(&ctl->log_refills)};
+}
+__device__ __forceinline__ void log_pad(const LogWave &lw, __amdgpu_buffer_rsrc_t log_rsrc) {
+    for (uint32_t i = lw.pos + lane_id(); i < lw.end; i += kWave)
+        __builtin_amdgcn_raw_buffer_store_b32(kLogNull, log_rsrc, i << 2, 0, 0);
+}
+__device__ __forceinline__ void log_refill(LogWave *lw, __amdgpu_buffer_rsrc_t log_rsrc) {
+    log_pad(*lw, log_rsrc);
+    uint32_t base = 0;
+    if (lane_id() == 0) {
+        if (lw->end) atomicAdd(lw->refills, 1u);         // (the wave has used a chunk up: once per chunk)
+        base = atomicAdd(&lw->ls->cursor, lw->chunk);
+    }
+    base = rfl(base);
+    if (base <= lw->cap - lw->chunk) {          // (cap is a multiple of chunk, at least one)
+        lw->pos = base;
+        lw->end = base + lw->chunk;
+    } else {
+        lw->pos = lw->end = 0u;
+        lw->full = true;
+    }
+}
+// (kernel end) the unused tail of the wave's chunk; what it counted with atomics, for k_seq_finish and the statistics
+__device__ __forceinline__ void log_finish(const LogWave &lw, __amdgpu_buffer_rsrc_t log_rsrc, const DevCtl *ctl) {
+    log_pad(lw, log_rsrc);
+    const uint32_t sp = wave_sum(lw.spilled);
+    if (lane_id() == 0 && sp) {
+        atomicAdd(const_cast<uint32_t *>(&ctl->cell_hits), sp);
+        atomicAdd(const_cast<uint32_t *>(&ctl->log_spilled), sp);
+    }
+}
+
 // (defined with k_fused_batch; WRITE false = count and mark only)
 template <int MODE, int DIAG, bool WRITE, bool TT, class DC>
 __device__ __forceinline__ uint4 fused_tile_pf(const uint4 q_orig, const uint32_t s[8], const Halo h,
@@ -2911,9 +2964,10 @@ __device__ __forceinline__ uint4 fused_tile_pf(const uint4 q_orig, const uint32_
                                                DC &dc, bool dc_on, uint32_t &wave_rm, bool &wrote_sum,
                                                __amdgpu_buffer_rsrc_t lr_rsrc, uint32_t adj_pitch, uint16_t *stage,
                                                uint32_t *chg, bool renamed, TTInfo *ti, bool &need_rename,
-                                               __amdgpu_buffer_rsrc_t t_rsrc = __amdgpu_buffer_rsrc_t(), bool use_t = false);
+                                               __amdgpu_buffer_rsrc_t log_rsrc = __amdgpu_buffer_rsrc_t(), bool use_log = false,
+                                               LogWave *lw = nullptr);
 
-template <int MODE, bool HOT, bool TT, int DIAG = 0>
+template <int MODE, bool HOT, bool TT, int DIAG = 0, bool LOG = false>
 __global__ __launch_bounds__(kLutThreads) void k_scan_batch(const uint16_t *tok0, const uint16_t *tok1,
                                                               const TileSum *__restrict__ sin, uint32_t n_tiles,
                                                               uint32_t *__restrict__ chg, const BatchState *bs,
@@ -2921,7 +2975,7 @@ __global__ __launch_bounds__(kLutThreads) void k_scan_batch(const uint16_t *tok0
                                                               const DevCtl *ctl, const RankEdge *le,
                                                               const RankEdge *re,
                                                               const uint32_t *__restrict__ run_in, int hot_launched,
-                                                              uint32_t *T) {
+                                                              uint32_t *dlog, LogState *ls) {
     constexpr uint32_t idmask = MODE == 1 ? 0x7FFFu : 0xFFFFu;
     __shared__ BatchLutMem lut_mem;
     const uint32_t waves_per_block = kLutThreads / kWave;
@@ -2941,6 +2995,9 @@ __global__ __launch_bounds__(kLutThreads) void k_scan_batch(const uint16_t *tok0
     lut_build(lut, bs, n_keys, idmask - 1u);
     if (TT) tt_build(ti, bs, n_keys, idmask - 1u);
     uint32_t tile = rfl(blockIdx.x * waves_per_block + threadIdx.x / kWave);
+    LogWave lw = log_wave(ls, false, ctl);
+    __amdgpu_buffer_rsrc_t lw_rsrc = __amdgpu_buffer_rsrc_t();
+    bool lw_on = false;
     if (tile < n_tiles) {
 
     const uint32_t last_tile = n_tiles - 1;
@@ -2948,9 +3005,15 @@ __global__ __launch_bounds__(kLutThreads) void k_scan_batch(const uint16_t *tok0
     const __amdgpu_buffer_rsrc_t sums_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<TileSum *>(sin), 0, n_tiles * 16u, 0x00020000);
     const __amdgpu_buffer_rsrc_t lr_rsrc = __builtin_amdgcn_make_buffer_rsrc(LR, 0, 0xFFFFFFFCu, 0x00020000);
-    // (the pairs' byte x byte cell blocks: see k_pair_cells_fold; not with the delta cache of frequent pairs)
-    const bool use_t = T != nullptr && !HOT && ctl->cells_on != 0u && n_keys >= ctl->cells_min;
-    const __amdgpu_buffer_rsrc_t t_rsrc = __builtin_amdgcn_make_buffer_rsrc(T ? T : LR, 0, T ? 0xFFFFFFFCu : 0u, 0x00020000);
+    // (the delta log: k_log_plan decided; never with the delta cache of frequent pairs.  Stores beyond the log's end
+    //  would be dropped by the buffer's bounds check.  LOG: the host launches the instantiations that can log only
+    //  for a training that has a log; the others hold none of its code)
+    const bool use_log = LOG && !HOT && dlog != nullptr && rfl(ls->on) != 0u;
+    const __amdgpu_buffer_rsrc_t log_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(use_log ? dlog : LR, 0, use_log ? rfl(ls->cap) << 2 : 0u, 0x00020000);
+    lw = log_wave(ls, use_log, ctl);
+    lw_rsrc = log_rsrc;
+    lw_on = use_log;
     TileIn t0 = tile_issue(tok, sums_rsrc, tile);
     TileIn t1 = tile_issue(tok, sums_rsrc, clamp_tile((uint64_t)tile + n_waves));
     bool v1 = (uint64_t)tile + n_waves < n_tiles;
@@ -2978,7 +3041,7 @@ __global__ __launch_bounds__(kLutThreads) void k_scan_batch(const uint16_t *tok0
             if (TT) tt_rename<MODE>(s, h, ti, run_in[tile]);      // ((t,t) members: every tile, no tt_needed test first)
             fused_tile_pf<MODE, 0, false, TT>(t0.q, s, h, rlane(t0.smw, 4), rlane(t0.smw, 5), rlane(t0.smw, 6), lut,
                                               256u + ctl_k_done, tile, nullptr, hdr_adj, LR, dc, dc_on, rm_unused, ws_unused,
-                                              lr_rsrc, adj_pitch, nullptr, chg, TT, &ti, no_rename, t_rsrc, use_t);
+                                              lr_rsrc, adj_pitch, nullptr, chg, TT, &ti, no_rename, log_rsrc, use_log, &lw);
         }
         if (!v1) break;
         tile += n_waves;
@@ -2986,6 +3049,7 @@ __global__ __launch_bounds__(kLutThreads) void k_scan_batch(const uint16_t *tok0
         v1 = v2;
     }
     }
+    if (lw_on) log_finish(lw, lw_rsrc, ctl);
     if (dc_on) dc_flush(dc, LR);
     if (TT) {
         tt_flush(ti, hdr_m);
@@ -3018,7 +3082,7 @@ __device__ __forceinline__ uint4 fused_tile_pf(const uint4 q_orig, const uint32_
                                                DC &dc, bool dc_on, uint32_t &wave_rm, bool &wrote_sum,
                                                __amdgpu_buffer_rsrc_t lr_rsrc, uint32_t adj_pitch, uint16_t *stage,
                                                uint32_t *chg, bool renamed, TTInfo *ti, bool &need_rename,
-                                               __amdgpu_buffer_rsrc_t t_rsrc, bool use_t) {
+                                               __amdgpu_buffer_rsrc_t log_rsrc, bool use_log, LogWave *lw) {
     constexpr uint32_t idmask = MODE == 1 ? 0x7FFFu : 0xFFFFu;
     constexpr uint32_t endbit = MODE == 1 ? kEndBit : 0u;
     constexpr uint32_t kNone = 0xFFFFu;          // "this slot starts no match" (batch indices are below kBatchMax)
@@ -3146,11 +3210,21 @@ __device__ __forceinline__ uint4 fused_tile_pf(const uint4 q_orig, const uint32_
         const uint32_t li = live - 1u;
         if (lane == (li >> 3)) n2_patch = li & 7u;
     }
+    // the delta log (see LogWave): room for every match this tile can hold, or none of its matches is logged
+    bool logging = false;                // uniform
+    uint32_t lpos = 0;                   // uniform
+    if (use_log) {
+        if (lw->end - lw->pos < kLogChunkMin && !lw->full) log_refill(lw, log_rsrc);
+        logging = lw->end - lw->pos >= kLogChunkMin;
+        lpos = lw->pos;
+    }
     uint32_t out[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const uint32_t self = s[j];
         uint32_t nv = ((Bm >> j) & 1u) ? kHole : self;
+        bool el = false;
+        uint32_t rec = 0;
         if (__ballot(((Am >> j) & 1u) != 0u) != 0ull) {
             if ((Am >> j) & 1u) {
                 const uint32_t p1 = j == 0 ? prev7 >> 16 : s[j > 0 ? j - 1 : 0];
@@ -3165,12 +3239,14 @@ __device__ __forceinline__ uint4 fused_tile_pf(const uint4 q_orig, const uint32_
                 if (DIAG != 2) {
                     const bool lo = left_open<MODE>(p1), ro = right_open<MODE>(btok, n2);
                     const uint32_t xl = p1 & idmask, yr = n2 & idmask;
-                    if (use_t && lo && ro && ppj == kNone && xl < 256u && yr < 256u) {
-                        // both neighbours are raw bytes and no match touches this one: ONE atomic on the pair's
-                        // byte x byte cell block instead of two on its L and R rows (k_pair_cells_fold adds the
-                        // block's row and column sums to the rows afterwards)
-                        __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(1, t_rsrc, ((ja << 16) | (xl << 8) | yr) << 2, 0, 0);
+                    const bool elig = use_log && lo && ro && ppj == kNone && xl < 256u && yr < 256u;
+                    if (elig && logging) {
+                        // both neighbours are raw bytes and no match touches this one: ONE record in the log instead
+                        // of two atomics on the pair's L and R rows (stored below, outside the divergent part)
+                        el = true;
+                        rec = (ja << 16) | (xl << 8) | yr;
                     } else {
+                        if (elig) lw->spilled += 1u;         // (the log is full)
                         if (lo) {
                             if (ppj != kNone) {      // ... (a', b') (a, b): (b', a) -> (X', X)
                                 atomicAdd(&hdr_adj[ppj * adj_pitch + ja], 1u);
@@ -3183,9 +3259,16 @@ __device__ __forceinline__ uint4 fused_tile_pf(const uint4 q_orig, const uint32_
                     }
                 }
             }
+            if (logging) {               // (uniform) the slot's eligible lanes, in lane order
+                const uint64_t m = __ballot(el);
+                const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                if (el) __builtin_amdgcn_raw_buffer_store_b32(rec, log_rsrc, (lpos + at) << 2, 0, 0);
+                lpos += (uint32_t)__popcll(m);
+            }
         }
         out[j] = nv;
     }
+    if (logging) lw->pos = lpos;
     if (TT && renamed) {                 // (every renamed token was the second token of a match; be safe)
 #pragma unroll
         for (int j = 0; j < 8; ++j)
@@ -3232,7 +3315,7 @@ __device__ __forceinline__ uint4 fused_tile_pf(const uint4 q_orig, const uint32_
 #ifndef MBPE_FUSED_WAVES
 #define MBPE_FUSED_WAVES 4
 #endif
-template <int MODE, bool HOT, bool TT, int DIAG = 0>
+template <int MODE, bool HOT, bool TT, int DIAG = 0, bool LOG = false>
 __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) void k_fused_batch(uint16_t *tok0, uint16_t *tok1,
                                                                const TileSum *__restrict__ sin,
                                                                TileSum *__restrict__ sout, uint32_t n_tiles,
@@ -3240,7 +3323,7 @@ __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) 
                                                                uint32_t *hdr_adj, uint32_t *LR, DevCtl *ctl,
                                                                const RankEdge *le, const RankEdge *re,
                                                                uint32_t *hdr_m, const uint32_t *__restrict__ run_in,
-                                                               int hot_launched, uint32_t *T) {
+                                                               int hot_launched, uint32_t *dlog, LogState *ls) {
     constexpr uint32_t idmask = MODE == 1 ? 0x7FFFu : 0xFFFFu;
     __shared__ BatchLutMem lut_mem;
     const uint32_t lane = lane_id();
@@ -3267,6 +3350,9 @@ __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) 
     if (blockIdx.x == 0 && threadIdx.x == 0) ctl->marks_all = 1;
     uint32_t tile = rfl(blockIdx.x * waves_per_block + threadIdx.x / kWave);
     uint32_t wave_rm = 0;        // uniform
+    LogWave lw = log_wave(ls, false, ctl);
+    __amdgpu_buffer_rsrc_t lw_rsrc = __amdgpu_buffer_rsrc_t();
+    bool lw_on = false;
     if (tile < n_tiles) {
 
     const uint32_t last_tile = n_tiles - 1;
@@ -3274,9 +3360,15 @@ __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) 
     const __amdgpu_buffer_rsrc_t sums_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<TileSum *>(sin), 0, n_tiles * 16u, 0x00020000);
     const __amdgpu_buffer_rsrc_t lr_rsrc = __builtin_amdgcn_make_buffer_rsrc(LR, 0, 0xFFFFFFFCu, 0x00020000);
-    // (the pairs' byte x byte cell blocks: see k_pair_cells_fold; not with the delta cache of frequent pairs)
-    const bool use_t = T != nullptr && !HOT && ctl->cells_on != 0u && n_keys >= ctl->cells_min;
-    const __amdgpu_buffer_rsrc_t t_rsrc = __builtin_amdgcn_make_buffer_rsrc(T ? T : LR, 0, T ? 0xFFFFFFFCu : 0u, 0x00020000);
+    // (the delta log: k_log_plan decided; never with the delta cache of frequent pairs.  Stores beyond the log's end
+    //  would be dropped by the buffer's bounds check.  LOG: the host launches the instantiations that can log only
+    //  for a training that has a log; the others hold none of its code)
+    const bool use_log = LOG && !HOT && dlog != nullptr && rfl(ls->on) != 0u;
+    const __amdgpu_buffer_rsrc_t log_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(use_log ? dlog : LR, 0, use_log ? rfl(ls->cap) << 2 : 0u, 0x00020000);
+    lw = log_wave(ls, use_log, ctl);
+    lw_rsrc = log_rsrc;
+    lw_on = use_log;
     const uint32_t adj_pitch = rfl(ctl->adj_pitch);
     // kDepth tiles are in flight behind the one being worked on (5 registers each)
 #ifndef MBPE_FUSED_DEPTH
@@ -3332,12 +3424,12 @@ __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) 
             }
             outq = fused_tile_pf<MODE, DIAG, true, TT>(t0.q, s, h, old_x, old_y, old_z, lut, X0, tile, sout, hdr_adj, LR, dc,
                                                        dc_on, wave_rm, wrote_sum, lr_rsrc, adj_pitch, stage, chg, renamed, &ti,
-                                                       need_rename, t_rsrc, use_t);
+                                                       need_rename, log_rsrc, use_log, &lw);
             if (TT && need_rename) {             // (uniform, rare)
                 tt_rename<MODE>(s, h, ti, run_in[tile]);
                 outq = fused_tile_pf<MODE, DIAG, true, TT>(t0.q, s, h, old_x, old_y, old_z, lut, X0, tile, sout, hdr_adj, LR,
                                                            dc, dc_on, wave_rm, wrote_sum, lr_rsrc, adj_pitch, stage, chg, true,
-                                                           &ti, need_rename, t_rsrc, use_t);
+                                                           &ti, need_rename, log_rsrc, use_log, &lw);
             }
         }
         // every tile's summary goes to the side array (an unchanged tile's as it was): no tile marks needed
@@ -3354,6 +3446,7 @@ __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) 
         ring[kDepth - 1] = t_new;
     }
     }
+    if (lw_on) log_finish(lw, lw_rsrc, ctl);
     if (dc_on) dc_flush(dc, LR);
     if (lane == 0 && wave_rm) atomicAdd(&ctl->rm, wave_rm);
     if (TT) {                           // matches of the (t,t) member: its count is not simply the pair's count
@@ -3361,41 +3454,165 @@ __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) 
     }
 }
 
-// The pairs' byte x byte cell blocks (round 4).  A match whose two neighbours are raw bytes and which no other match
-// touches costs the stream pass ONE scattered atomic, on cell T[j][x][y] of its pair's 256 x 256 block, instead of two
-// (L_j[x] and R_j[y]): in the passes of thousands of byte pairs, which their atomics bound, most
-// matches are of that kind.  This kernel adds every block's row sums to the pair's L row and its column sums to the R row
-// and clears the block, so that everything behind the pass -- validation, the table update, the exchange of several
-// ranks -- sees the rows it always saw.  One workgroup per pair at a time; 256 KiB read (and what was not zero cleared).
-__global__ __launch_bounds__(256) void k_pair_cells_fold(uint32_t *__restrict__ T, uint32_t *__restrict__ LR, const DevCtl *ctl) {
-    __shared__ uint32_t rows[256];
+// ---- the delta log: behind (and before) the pass ------------------------------------------------
+// k_log_plan       (one wave, before the pass) decides whether the pass logs -- the batch is large enough, not the
+//                  frequent-pair instantiation's, and its records fit the partition buffer -- and lays that buffer out:
+//                  bucket b (pairs 64 b .. 64 b + 63) receives at most the sum of its pairs' counts, one record per
+//                  match at most, and these are known before the pass (BatchState::packed), so the regions are a
+//                  prefix sum and nobody has to count records first.
+// k_log_partition  multisplit: a workgroup takes slices of 8,192 records, histograms them by bucket in LDS, reserves
+//                  room in every bucket's region with one atomic per bucket and slice, sorts the slice by bucket in
+//                  LDS and writes it out in runs.
+// k_log_count      a share of a bucket's records is counted in LDS, 64 x (256 L + 256 R) 32-bit counters, and the
+//                  non-zero counters are added to the LR rows: everything behind it -- validation, the table update,
+//                  the exchange of several ranks -- sees the rows it always saw.  Exact integer arithmetic throughout.
+static_assert(kLogBuckets <= (uint32_t)kWave, "k_log_plan and the scans of k_log_partition: one lane per bucket");
+constexpr uint32_t kLogBucketShift = 22;         // record -> bucket: (j >> 6) of (j << 16 | x << 8 | y)
+
+__global__ __launch_bounds__(kWave) void k_log_plan(DevCtl *ctl, const BatchState *bs, LogState *ls) {
+    const uint32_t b = threadIdx.x;
     const uint32_t n = ctl->batch_n;
-    if (n < ctl->cells_min || !ctl->cells_on) return;          // (the pass did not use the blocks: see k_fused_batch)
-    const uint32_t pitch = lr_pitch(256u + ctl->k_done);
-    uint32_t hits = 0;
-    const uint32_t t = threadIdx.x;
-    for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
-        uint32_t *tj = T + (size_t)j * 65536u;
-        rows[t] = 0;
+    bool on = n >= 2u && ctl->cells_on != 0u && n >= ctl->cells_min;
+    if (on) on = !dc_wanted(bs->packed[0] >> 32, ctl->n_live * ctl->n_ranks);
+    unsigned long long cnt = 0;
+    if (on && b < kLogBuckets) {
+        const uint32_t j1 = n < (b + 1u) * kLogBucketPairs ? n : (b + 1u) * kLogBucketPairs;
+        for (uint32_t j = b * kLogBucketPairs; j < j1; ++j) cnt += bs->packed[j] >> 32;
+    }
+    unsigned long long incl = cnt;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const unsigned long long t = __shfl_up(incl, d, kWave);
+        if (b >= (uint32_t)d) incl += t;
+    }
+    const unsigned long long total = __shfl(incl, kWave - 1, kWave);
+    const bool fits = total <= (unsigned long long)ls->part_cap;        // does not fit: this pass keeps its atomics
+    if (b == 0u) ctl->log_refused = on && !fits ? 1u : 0u;
+    on = on && fits;
+    if (b < kLogBuckets) {
+        ls->base[b + 1u] = on ? (uint32_t)incl : 0u;
+        ls->fill[b] = 0u;
+    }
+    if (b == 0u) {
+        ls->base[0] = 0u;
+        ls->on = on ? 1u : 0u;
+        ls->cursor = 0u;
+        ls->n_buckets = (n + kLogBucketPairs - 1u) / kLogBucketPairs;
+    }
+}
+
+constexpr int kPartThreads = 1024;
+constexpr uint32_t kLogSlice = 8192;             // records per slice: 8 per thread
+static_assert(kLogChunkMin % 8u == 0u, "a thread's 8 records never straddle the end of the log");
+
+__global__ __launch_bounds__(kPartThreads) void k_log_partition(const uint32_t *__restrict__ dlog, uint32_t *__restrict__ part,
+                                                                LogState *ls, DevCtl *ctl) {
+    __shared__ uint32_t hist[kWave];         // records of the slice per bucket, then the running placement rank
+    __shared__ uint32_t off[kWave + 1];      // exclusive prefix of hist: where a bucket starts in `sorted`
+    __shared__ uint32_t gb[kWave];           // where the slice's records of a bucket go in the partition buffer
+    __shared__ uint32_t room[kWave];         // ... and how many of them its region still takes (all, unless kErrLog)
+    __shared__ uint32_t sorted[kLogSlice];
+    if (!ls->on) return;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t cursor = ls->cursor, cap = ls->cap;
+    const uint32_t n_rec = cursor < cap ? cursor : cap;         // (chunks beyond the capacity were refused; both are
+                                                                //  multiples of the chunk size)
+    const uint32_t n_slices = (n_rec + kLogSlice - 1u) / kLogSlice;
+    for (uint32_t sl = blockIdx.x; sl < n_slices; sl += gridDim.x) {
+        if (tid < (uint32_t)kWave) hist[tid] = 0;
         __syncthreads();
-        uint32_t col = 0;
-#pragma unroll 8
-        for (uint32_t x = 0; x < 256u; ++x) {
-            const uint32_t v = tj[x * 256u + t];
-            if (__ballot(v != 0u) == 0ull) continue;          // (this wave's quarter of the row is empty)
-            if (v) tj[x * 256u + t] = 0;
-            col += v;
-            const uint32_t rs = wave_sum(v);
-            if (lane_id() == 0 && rs) atomicAdd(&rows[x], rs);
+        const uint32_t r0 = sl * kLogSlice + tid * 8u;
+        uint32_t rec[8];
+        if (r0 < n_rec) {
+            const uint4 q0 = reinterpret_cast<const uint4 *>(dlog + r0)[0], q1 = reinterpret_cast<const uint4 *>(dlog + r0)[1];
+            rec[0] = q0.x; rec[1] = q0.y; rec[2] = q0.z; rec[3] = q0.w;
+            rec[4] = q1.x; rec[5] = q1.y; rec[6] = q1.z; rec[7] = q1.w;
+        } else {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) rec[u] = kLogNull;
+        }
+        // (a record that names no bucket -- never written by the pass -- is dropped like the chunk tails)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if ((rec[u] >> kLogBucketShift) >= kLogBuckets) rec[u] = kLogNull;
+            if (rec[u] != kLogNull) atomicAdd(&hist[rec[u] >> kLogBucketShift], 1u);
         }
         __syncthreads();
-        if (col) LR[lr_idx(pitch, t, j, 1u)] += col;             // R_j[y = t]
-        if (rows[t]) LR[lr_idx(pitch, t, j, 0u)] += rows[t];     // L_j[x = t]
-        hits += col;
+        if (tid < (uint32_t)kWave) {             // one wave: scan the buckets, reserve their room
+            const uint32_t a = hist[tid];
+            uint32_t incl = a;
+#pragma unroll
+            for (int d = 1; d < kWave; d <<= 1) {
+                const uint32_t t = __shfl_up(incl, d, kWave);
+                if (tid >= (uint32_t)d) incl += t;
+            }
+            off[tid] = incl - a;
+            if (tid == (uint32_t)kWave - 1u) off[kWave] = incl;
+            if (a && tid < kLogBuckets) {
+                const uint32_t at = atomicAdd(&ls->fill[tid], a);
+                const uint32_t size = ls->base[tid + 1u] - ls->base[tid];
+                gb[tid] = ls->base[tid] + at;
+                // (more records than the pair counts allow: never expected; nothing is written out of bounds)
+                room[tid] = at >= size ? 0u : size - at < a ? size - at : a;
+                if (room[tid] < a) atomicOr(&ctl->err, kErrLog);
+            }
+            hist[tid] = 0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if (rec[u] == kLogNull) continue;
+            const uint32_t bk = rec[u] >> kLogBucketShift;
+            const uint32_t r = atomicAdd(&hist[bk], 1u);
+            sorted[off[bk] + r] = rec[u];
+        }
+        __syncthreads();
+        const uint32_t n_sorted = off[kWave];
+        for (uint32_t t = tid; t < n_sorted; t += kPartThreads) {
+            const uint32_t v = sorted[t];
+            const uint32_t bk = v >> kLogBucketShift;
+            if (t - off[bk] < room[bk]) part[gb[bk] + (t - off[bk])] = v;
+        }
         __syncthreads();
     }
-    hits = wave_sum(hits);
-    if (lane_id() == 0 && hits) atomicAdd(const_cast<uint32_t *>(&ctl->cell_hits), hits);
+}
+
+constexpr int kCountThreads = 1024;
+constexpr uint32_t kLogBucketCells = kLogBucketPairs * 512u;     // 128 KiB of counters: [pair][L / R][byte]
+
+__global__ __launch_bounds__(kCountThreads) void k_log_count(const uint32_t *__restrict__ part, uint32_t *LR, const LogState *ls,
+                                                             DevCtl *ctl) {
+    __shared__ uint32_t hist[kLogBucketCells];
+    if (!ls->on) return;
+    const uint32_t P = ls->n_buckets;
+    // workgroups per bucket (few buckets are split; more buckets than workgroups: a workgroup takes several)
+    const uint32_t S = P >= (uint32_t)gridDim.x ? 1u : (uint32_t)gridDim.x / P > 64u ? 64u : (uint32_t)gridDim.x / P;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t pitch = lr_pitch(256u + ctl->k_done);
+    if (blockIdx.x == 0 && tid == 0 && ls->cursor) ctl->log_passes += 1u;
+    for (uint32_t w = blockIdx.x; w < P * S; w += gridDim.x) {
+        const uint32_t b = w / S, share = w - b * S;
+        const uint32_t start = ls->base[b];
+        uint32_t n = ls->fill[b];
+        if (n > ls->base[b + 1u] - start) n = ls->base[b + 1u] - start;        // (kErrLog: see k_log_partition)
+        const uint32_t lo = (uint32_t)((uint64_t)n * share / S), hi = (uint32_t)((uint64_t)n * (share + 1u) / S);
+        if (lo == hi) continue;              // (uniform)
+        for (uint32_t i = tid; i < kLogBucketCells; i += kCountThreads) hist[i] = 0;
+        __syncthreads();
+        for (uint32_t i = lo + tid; i < hi; i += kCountThreads) {
+            const uint32_t v = part[start + i];
+            const uint32_t jl = (v >> 16) & (kLogBucketPairs - 1u);
+            atomicAdd(&hist[jl * 512u + ((v >> 8) & 255u)], 1u);         // L_j[x]
+            atomicAdd(&hist[jl * 512u + 256u + (v & 255u)], 1u);         // R_j[y]
+        }
+        __syncthreads();
+        for (uint32_t i = tid; i < kLogBucketCells; i += kCountThreads) {
+            const uint32_t c = hist[i];
+            if (c) atomicAdd(&LR[lr_idx(pitch, i & 255u, b * kLogBucketPairs + (i >> 9), (i >> 8) & 1u)], c);
+        }
+        if (tid == 0) atomicAdd(&ctl->cell_hits, hi - lo);
+        __syncthreads();
+    }
 }
 
 // Validation (after the all-reduce in a multi-GPU run).  Merge j creates the pairs (x, X_j) with
@@ -3973,9 +4190,10 @@ __global__ void k_seq_finish(DevCtl *ctl, uint32_t *fused_flag, const BatchState
         ctl->skip_penalty /= 2u;
     }
     ctl->skip_failed = 0;
-    // the pairs' cell blocks: once fewer than half of a large batch's matches lay between two raw bytes the stream is
-    // past the stage where that pays (at a third the pass is already 2-8 % slower with the blocks than without) (the share only falls as tokens replace bytes)
-    if (ctl->cells_on && ctl->cells_min >= kCellsMinBatch && ctl->batch_n >= ctl->cells_min &&
+    // the delta log: once fewer than half of a large batch's matches lay between two raw bytes the stream is past the
+    // stage where it pays (the share only falls as tokens replace bytes)
+    // (a pass that k_log_plan kept from logging for want of room counted no such match: it has no say)
+    if (ctl->cells_on && ctl->cells_min >= kCellsMinBatch && ctl->batch_n >= ctl->cells_min && !ctl->log_refused &&
         ctl->cell_hits * 2ull < (unsigned long long)rm_seq)
         ctl->cells_on = 0;
     ctl->cell_hits = 0;
@@ -4695,7 +4913,7 @@ void launch_fused_batch(const StreamView &v, const BatchView &b, const Inst &w) 
     const dim3 grid(tile_grid(v.n_tiles, v.n_cus, occ[slot_mode(v.endbit)], kLutThreads)), block(kLutThreads);
     const int hot_launched = w.hot;
 #define MBPE_FUSED_ARGS v.tok, v.tok_other, v.sums, v.side, v.n_tiles, v.chg, b.bs, b.hdr_adj, b.LR, v.ctl, v.left_edge, \
-                        v.right_edge, b.hdr_m, v.run_in, hot_launched, b.pair_cells
+                        v.right_edge, b.hdr_m, v.run_in, hot_launched, b.dlog, b.ls
 #ifdef MBPE_DIAG
     const int diag = getenv("MBPE_FUSED_DIAG") ? atoi(getenv("MBPE_FUSED_DIAG")) : 0;   // (re-read: set after warm-up)
 #define MBPE_FUSED_DIAG_CASE(D)                                                                                            \
@@ -4711,7 +4929,11 @@ void launch_fused_batch(const StreamView &v, const BatchView &b, const Inst &w) 
     MBPE_FUSED_DIAG_CASE(6)
 #undef MBPE_FUSED_DIAG_CASE
 #endif
-    MBPE_BY_MODE(v.endbit, MBPE_BY_INST(w, hipLaunchKernelGGL((k_fused_batch<M, HOT, TT>), grid, block, 0, v.stream, MBPE_FUSED_ARGS)));
+    // (the plain instantiations exist with and without the delta log's code: see k_fused_batch, LOG)
+    if (b.dlog)
+        MBPE_BY_MODE(v.endbit, MBPE_BY_INST(w, hipLaunchKernelGGL((k_fused_batch<M, HOT, TT, 0, !HOT>), grid, block, 0, v.stream, MBPE_FUSED_ARGS)));
+    else
+        MBPE_BY_MODE(v.endbit, MBPE_BY_INST(w, hipLaunchKernelGGL((k_fused_batch<M, HOT, TT, 0, false>), grid, block, 0, v.stream, MBPE_FUSED_ARGS)));
 #undef MBPE_FUSED_ARGS
 }
 
@@ -4722,17 +4944,25 @@ void launch_scan_batch(const StreamView &v, const BatchView &b, const Inst &w) {
                                resident_blocks(k_scan_batch<2, false, false, 0>, kLutThreads)};
     const dim3 grid(tile_grid(v.n_tiles, v.n_cus, occ[slot_mode(v.endbit)], kLutThreads)), block(kLutThreads);
     const int hot_launched = w.hot;
-    MBPE_BY_MODE(v.endbit, MBPE_BY_INST(w, hipLaunchKernelGGL((k_scan_batch<M, HOT, TT, 0>), grid, block, 0, v.stream, v.tok,
-                                                             v.tok_other, v.sums, v.n_tiles, v.chg, b.bs, b.hdr_m, b.hdr_adj, b.LR,
-                                                             v.ctl, v.left_edge, v.right_edge, v.run_in, hot_launched,
-                                                             b.pair_cells)));
+#define MBPE_SCAN_ARGS v.tok, v.tok_other, v.sums, v.n_tiles, v.chg, b.bs, b.hdr_m, b.hdr_adj, b.LR, v.ctl, v.left_edge, \
+                       v.right_edge, v.run_in, hot_launched, b.dlog, b.ls
+    if (b.dlog)
+        MBPE_BY_MODE(v.endbit, MBPE_BY_INST(w, hipLaunchKernelGGL((k_scan_batch<M, HOT, TT, 0, !HOT>), grid, block, 0, v.stream, MBPE_SCAN_ARGS)));
+    else
+        MBPE_BY_MODE(v.endbit, MBPE_BY_INST(w, hipLaunchKernelGGL((k_scan_batch<M, HOT, TT, 0, false>), grid, block, 0, v.stream, MBPE_SCAN_ARGS)));
+#undef MBPE_SCAN_ARGS
 }
 
-void launch_pair_cells_fold(const StreamView &v, const BatchView &b, uint32_t n_hint) {
-    if (!b.pair_cells) return;
-    if (n_hint < 64u) n_hint = 64u;
-    if (n_hint > 1024u) n_hint = 1024u;
-    hipLaunchKernelGGL(k_pair_cells_fold, dim3(n_hint), dim3(256), 0, v.stream, b.pair_cells, b.LR, v.ctl);
+void launch_log_plan(const StreamView &v, const BatchView &b) {
+    if (!b.dlog) return;
+    hipLaunchKernelGGL(k_log_plan, dim3(1), dim3(kWave), 0, v.stream, v.ctl, b.bs, b.ls);
+}
+
+void launch_log_consume(const StreamView &v, const BatchView &b) {
+    if (!b.dlog) return;
+    const int cus = v.n_cus > 0 ? v.n_cus : 256;
+    hipLaunchKernelGGL(k_log_partition, dim3(cus * 2), dim3(kPartThreads), 0, v.stream, b.dlog, b.part, b.ls, v.ctl);
+    hipLaunchKernelGGL(k_log_count, dim3(cus), dim3(kCountThreads), 0, v.stream, b.part, b.LR, b.ls, v.ctl);
 }
 
 void launch_batch_tables(const StreamView &v, const BatchView &b, PairTable t, uint32_t id_upper, uint32_t n_hint) {

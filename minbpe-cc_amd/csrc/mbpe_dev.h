@@ -135,15 +135,21 @@ struct DevCtl {
     uint32_t first_tie;         // the selection took ONE pair whose count is shared: k_first_* pick the one that comes first
     uint32_t marks_all;         // the fused pass of this sequence wrote EVERY tile's summary to the side array and set no
                                 //   tile marks (its tiles nearly all change): "every tile is marked"
-    uint32_t cells_on;          // (host sets 1 at begin when the pairs' cell blocks exist) matches between two raw bytes are
-                                //   counted in the pair's byte x byte cell block (k_pair_cells_fold); k_seq_finish clears it for
+    uint32_t cells_on;          // (host sets 1 at begin when the delta log exists) matches between two raw bytes are
+                                //   logged as records and counted behind the pass (k_log_count); k_seq_finish clears it for
                                 //   good once fewer than half of a large batch's matches were of that kind
-    uint32_t cell_hits;         // matches counted that way in the sequence under way (k_pair_cells_fold)
-    uint32_t cells_min;         // (host, at begin) batches of at least this many pairs use the blocks (kCellsMinBatch; 2 when the
-                                //   "pair_cells" option forces them on: tests)
+    uint32_t cell_hits;         // matches of that kind in the sequence under way (k_log_count; the pass itself adds those
+                                //   that found the log full)
+    uint32_t cells_min;         // (host, at begin) batches of at least this many pairs log (kCellsMinBatch; 2 when the
+                                //   "pair_cells" option forces the log on: tests)
     uint32_t adj_pitch;         // (host, at begin) row pitch of the ADJ block: the largest batch this training can select
                                 //   ("max_batch" rounded up to 64), so that the block -- and what several GPUs exchange of
                                 //   it -- is as small as the batches allow
+    uint32_t log_spilled;       // eligible matches that found the log full and took the two L / R atomics (statistics)
+    uint32_t log_passes;        // passes whose log held records (statistics)
+    uint32_t log_refills;       // chunks taken by waves that had used one up before (statistics)
+    uint32_t log_refused;       // (k_log_plan) the pass under way would have logged, but its pairs' counts exceed the
+                                //   partition buffer: it says nothing about the share of byte neighbours (k_seq_finish)
 
 };
 
@@ -181,9 +187,28 @@ constexpr uint32_t kTTSlots = 256;
 #define MBPE_SKIP_MAX 32
 #endif
 constexpr int kSkipMax = MBPE_SKIP_MAX;
-// batches of at least this many pairs count matches between raw bytes in the pairs' cell blocks (smaller ones are not bound
-// by their atomics: there the extra tests cost more than the saved atomic -- same box, 976-pair pass: 8.1 -> 8.5 ms)
+// batches of at least this many pairs log their matches between raw bytes (smaller ones are not bound by their atomics:
+// there the extra tests cost more than the saved atomics)
 constexpr uint32_t kCellsMinBatch = 512;
+
+// The delta log (kernels.hip, "the delta log").  A record is (j << 16) | (x << 8) | y: one match of batch pair j between
+// the raw bytes x and y.  Buckets are 64 consecutive pairs: 64 x (256 L + 256 R) counters fill the LDS of k_log_count.
+constexpr uint32_t kLogNull = 0xFFFFFFFFu;          // no record (the unused tail of a chunk)
+constexpr uint32_t kLogBucketPairs = 64;
+constexpr uint32_t kLogBuckets = (uint32_t)MBPE_BATCH_MAX / kLogBucketPairs;
+constexpr uint32_t kLogChunkMin = 256;              // records: a tile's most, so a wave's chunk always holds the next tile
+constexpr uint32_t kLogChunkDefault = 4096;
+static_assert(MBPE_BATCH_MAX % 64 == 0 && MBPE_BATCH_MAX <= 65536, "a record holds the pair index in 16 bits");
+struct LogState {
+    uint32_t cap;               // (host, at begin) records the log holds: a multiple of `chunk`
+    uint32_t chunk;             // (host, at begin) records a wave reserves at a time: a multiple of kLogChunkMin
+    uint32_t part_cap;          // (host, at begin) records the partition buffer holds
+    uint32_t on;                // (k_log_plan) this pass logs
+    uint32_t cursor;            // next free record of the log: waves add `chunk` (may run past cap: refused)
+    uint32_t n_buckets;
+    uint32_t base[kLogBuckets + 1];     // region of every bucket in the partition buffer: prefix sums of the pairs' counts
+    uint32_t fill[kLogBuckets];         // records placed there so far
+};
 constexpr uint32_t kNoTT = 0xFFFFFFFFu;
 struct BatchState {
     uint32_t key[kBatchMax];      // (first << 16) | second
@@ -228,6 +253,7 @@ constexpr uint32_t kErrCountRange  = 8u;   // a pair count does not fit 31 bits 
                                            //   or the byte-pair table does not add up to the pairs counted (k_pair_total)
 constexpr uint32_t kErrHotSkipped  = 16u;  // a pass needed the frequent-pair instantiation of a stream kernel, which the host
                                            //   had ruled out and not launched (kernels.hip: hot_mismatch)
+constexpr uint32_t kErrLog         = 32u;  // the delta log held more records of a bucket than its pairs' counts allow
 
 // packed argmax word: (count << 32) | ~key  -- larger is better:
 // count descending, then key ascending == (first, second) ascending,
@@ -262,11 +288,12 @@ struct BatchView {
     BatchState *bs;
     uint32_t *hdr_m, *hdr_adj;   // batch header of the exchange buffer: m_j, ADJ[i][j]
     uint32_t *LR;                // count deltas: rows L_0, R_0, L_1, R_1, ... (one merge: L[x] = LR[2x], R[y] = LR[2y+1])
-    // (optional) 65,536 u32 cells per pair of the largest batch, all zero between sequences.  A match whose two
-    // neighbours are raw bytes and which no other match touches then costs the scan / fused pass one atomic (cell
-    // [j][x][y]) instead of two (L_j[x], R_j[y]); launch_pair_cells_fold, right behind the pass, adds the blocks' row and
-    // column sums to the LR rows and clears the blocks: everything after it sees the rows it always saw.
-    uint32_t *pair_cells;
+    // (optional) the delta log.  A match whose two neighbours are raw bytes and which no other match touches then costs
+    // the scan / fused pass one 4-byte record in `dlog` instead of two atomics (L_j[x], R_j[y]); launch_log_consume, right
+    // behind the pass, sorts the records by bucket into `part` and adds them to the LR rows: everything after it sees the
+    // rows it always saw.  launch_log_plan, before the pass, lays out `part` and decides whether the pass logs.
+    uint32_t *dlog, *part;
+    LogState *ls;
 };
 
 // Which instantiations of a stream kernel a launch enqueues: they exist per (t,t) pair / member yes / no and per
@@ -360,8 +387,9 @@ void launch_select_batch(const StreamView &v, const BatchView &b, PairTable t, u
 void launch_scan_batch(const StreamView &v, const BatchView &b, const Inst &w);
 // large batch (ctl->fused): count the deltas and write the merged stream to the other buffer
 void launch_fused_batch(const StreamView &v, const BatchView &b, const Inst &w);
-// b.pair_cells -> the LR rows (see BatchView; nothing to do without the blocks)
-void launch_pair_cells_fold(const StreamView &v, const BatchView &b, uint32_t n_hint);
+// the delta log before / behind the pass (see BatchView; nothing to do without the log)
+void launch_log_plan(const StreamView &v, const BatchView &b);
+void launch_log_consume(const StreamView &v, const BatchView &b);
 // k_delta_max + k_validate + k_apply_batch.  n_hint: the batch size the grids are sized for; id_upper: upper bound of
 // the ids that exist
 void launch_batch_tables(const StreamView &v, const BatchView &b, PairTable t, uint32_t id_upper, uint32_t n_hint);

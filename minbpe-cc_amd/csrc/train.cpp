@@ -163,7 +163,9 @@ struct mbpe_ctx {
     BatchState *bs = nullptr;
     uint32_t *xb0 = nullptr;              // begin: [bp 65,536][header][pairs counted: kPairCountWords limbs]
     uint32_t h_pcount[kPairCountWords] = {};   // (host source of this rank's limbs)
-    uint32_t *pair_cells = nullptr;       // byte x byte cell block per pair of a batch (launch_pair_cells_fold), or NULL
+    uint32_t *dlog = nullptr;             // the delta log of a stream pass and its partition buffer (launch_log_consume),
+    uint32_t *dpart = nullptr;            //   or NULL
+    LogState *log_state = nullptr;
     RankEdge *d_left = nullptr, *d_right = nullptr;   // composed neighbours (multi-GPU)
 
     // training
@@ -218,8 +220,12 @@ struct mbpe_ctx {
     // read back while its stream pass runs, so that exactly the cells the batch can touch are exchanged
     uint32_t *h_seq = nullptr;      // pinned, 16 words: [0..3] the multi-GPU copy, [8..15] launch_seq_info's
     uint32_t *d_seq_info = nullptr; // 8 words of device memory for launch_seq_info
-    int64_t opt_pair_cells = -1;    // one atomic per match with byte neighbours (mbpe_dev.h: launch_pair_cells_fold): -1 for
+    int64_t opt_pair_cells = -1;    // one log record per match with byte neighbours (mbpe_dev.h: launch_log_consume): -1 for
                                     //   streams from 64 Mi slots on, 0 never, 1 always
+    int64_t opt_log_cap = 0;        // records the delta log holds (0: from the stream's size) and records a wave reserves
+    int64_t opt_log_chunk = 0;      //   at a time (0: kLogChunkDefault, less on a small log): tests reach the full log and
+                                    //   the chunk refill with them
+    LogState h_log = {};            // what mbpe_train_begin sets the device's LogState to
     int64_t opt_lockstep = -1;      // small corpora: the host waits for every selection and enqueues only the kernels that
                                     //   sequence needs (-1: when the stream is short enough, 0 never, 1 always)
     hipEvent_t ev_sel = nullptr;
@@ -318,7 +324,7 @@ int sync_ctl(mbpe_ctx *c) {
         char buf[320];
         snprintf(buf, sizeof(buf), "device error flags 0x%x (1=pair table full, 2=negative count, 4=missing pair, "
                                    "8=a pair occurs 2^31 times or more, or the byte-pair counts do not add up to the "
-                                   "pairs scanned (a count reached 2^32), 16=a stream pass was skipped)",
+                                   "pairs scanned (a count reached 2^32), 16=a stream pass was skipped, 32=delta log overflow)",
                  c->h_ctl.err);
         mbpe_host::set_last_error(buf);
         return MBPE_ERR_OVERFLOW;
@@ -349,7 +355,8 @@ void free_training(mbpe_ctx *c) {
     tfree(c, c->offsets);
     tfree(c, c->tab.hslot); tfree(c, c->tab.ekey); tfree(c, c->tab.ecnt); tfree(c, c->tab.cells);
     tfree(c, c->tab.bmax); tfree(c, c->tab.smax);
-    tfree(c, c->ctl); tfree(c, c->best); tfree(c, c->xb); tfree(c, c->xb0); tfree(c, c->pair_cells);
+    tfree(c, c->ctl); tfree(c, c->best); tfree(c, c->xb); tfree(c, c->xb0); tfree(c, c->dlog); tfree(c, c->dpart);
+    tfree(c, c->log_state);
     tfree(c, c->d_left); tfree(c, c->d_right); tfree(c, c->bs); tfree(c, c->sel); tfree(c, c->seq_flags); tfree(c, c->run_in);
     tfree(c, c->first_state);
     tfree(c, c->xf);
@@ -506,7 +513,7 @@ StreamView stream_view(const mbpe_ctx *c, TokOrder order) {
     return v;
 }
 
-BatchView batch_view(const mbpe_ctx *c) { return BatchView{c->bs, c->hdr_m, c->hdr_adj, c->LR, c->pair_cells}; }
+BatchView batch_view(const mbpe_ctx *c) { return BatchView{c->bs, c->hdr_m, c->hdr_adj, c->LR, c->dlog, c->dpart, c->log_state}; }
 
 int do_compact(mbpe_ctx *c) {
     // c->h_ctl must be current
@@ -619,6 +626,8 @@ int mbpe_set_option(mbpe_ctx *c, const char *name, int64_t value) {
     else if (n == "byte_table") c->opt_byte_table = value != 0;
     else if (n == "lockstep") c->opt_lockstep = value < 0 ? -1 : value != 0;
     else if (n == "pair_cells") c->opt_pair_cells = value < 0 ? -1 : value != 0;      // (read by the next mbpe_train_begin)
+    else if (n == "log_cap") c->opt_log_cap = value < 0 ? 0 : std::min<int64_t>(value, 1ll << 29);       // (likewise; 0: default)
+    else if (n == "log_chunk") c->opt_log_chunk = value < 0 ? 0 : std::min<int64_t>(value, 1ll << 16);   // (likewise)
     else if (n == "wide_from") c->opt_wide_from = value < 0 ? -1 : value;      // (read by the next mbpe_train_begin)
     else if (n == "first_wide") c->opt_first_wide = value != 0;                // (read by the next mbpe_train_begin)
     else if (n == "pc_repeat") c->opt_pc_repeat = std::min<int64_t>(std::max<int64_t>(1, value), 1000);
@@ -964,9 +973,25 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size, const ResumeSrc *rs = n
     HIPCHK(hipMemsetAsync(c->xb, 0, xb_words * 4, c->stream));
     HIPCHK(hipMemsetAsync(c->xb0, 0, xb0_words * 4, c->stream));
     if (c->opt_pair_cells > 0 || (c->opt_pair_cells < 0 && c->n_slots >= (64ull << 20))) {
-        const size_t cells = (size_t)c->max_batch_eff * 65536u;
-        HIPCHK(tmalloc(c, &c->pair_cells, cells * 4));
-        HIPCHK(hipMemsetAsync(c->pair_cells, 0, cells * 4, c->stream));
+        // The delta log.  A pass writes at most one record per match, and the matches of a batch are at most half the
+        // slots; the partition buffer is laid out by the pairs' counts, which can add up to as much.  Both are capped
+        // where the benchmark's largest pass (4,096 pairs, 2.7e8 matches) still fits: a pass beyond the partition
+        // buffer keeps its atomics, a wave that finds the log full does so for its remaining tiles.
+        LogState &init = c->h_log;
+        init = LogState{};
+        const uint64_t half = c->n_slots / 2 + 1;
+        uint64_t cap = c->opt_log_cap > 0 ? (uint64_t)c->opt_log_cap : std::min<uint64_t>(std::max<uint64_t>(half / 8, 1u << 20), 1u << 28);
+        // (a chunk per wave of the pass: large ones waste their tails on a small log)
+        uint64_t chunk = c->opt_log_chunk > 0 ? (uint64_t)c->opt_log_chunk : std::min<uint64_t>(kLogChunkDefault, cap / 8192);
+        chunk = std::max<uint64_t>(kLogChunkMin, std::min<uint64_t>(chunk, 1u << 16) / kLogChunkMin * kLogChunkMin);
+        cap = std::max<uint64_t>(chunk, std::min<uint64_t>(cap, 1u << 29) / chunk * chunk);
+        init.cap = (uint32_t)cap;
+        init.chunk = (uint32_t)chunk;
+        init.part_cap = (uint32_t)std::min<uint64_t>(half, 1u << 29);
+        HIPCHK(tmalloc(c, &c->dlog, (size_t)init.cap * 4));
+        HIPCHK(tmalloc(c, &c->dpart, (size_t)init.part_cap * 4));
+        HIPCHK(tmalloc(c, &c->log_state, sizeof(LogState)));
+        HIPCHK(hipMemcpyAsync(c->log_state, &init, sizeof(LogState), hipMemcpyHostToDevice, c->stream));
     }
     c->hdr_m = c->xb + c->hdr_words;
     c->hdr_adj = c->hdr_m + kBatchMax;
@@ -997,7 +1022,7 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size, const ResumeSrc *rs = n
         init.n_ranks = (uint32_t)std::max(1, c->n_ranks);
         init.first_mode = c->opt_first ? 1u : 0u;
         init.adj_pitch = c->adj_pitch;
-        init.cells_on = c->pair_cells ? 1u : 0u;
+        init.cells_on = c->dlog ? 1u : 0u;
         init.cells_min = c->opt_pair_cells > 0 ? 2u : kCellsMinBatch;      // (forced on: every batch, and for the whole run)
         c->h_ctl = init;
         HIPCHK(hipMemcpyAsync(c->ctl, &c->h_ctl, sizeof(DevCtl), hipMemcpyHostToDevice, c->stream));
@@ -1274,9 +1299,10 @@ static int seq_lockstep(mbpe_ctx *c, int ev_slot, bool *nothing_left) {
         // (a batch with a (t,t) member: the runs of its token before every tile, which launch_merge computes in the
         //  ordinary enqueue-everything flow)
         if (w.tt) launch_run_lengths(v, b.bs, c->best, 1);
+        launch_log_plan(v, b);
         if (fused) launch_fused_batch(v, b, w);
         else launch_scan_batch(v, b, w);
-        launch_pair_cells_fold(v, b, batch_n);
+        launch_log_consume(v, b);
     }
     if (ev_slot >= 0) { (void)hipEventRecord(c->kev_f[2 * ev_slot + 1], c->stream); (void)hipEventRecord(c->kev[2 * ev_slot + 1], c->stream); }
     c->k_upper = std::min<uint32_t>(c->n_target, c->h_seq[8] + batch_n);
@@ -1307,12 +1333,13 @@ static int seq_stage_a(mbpe_ctx *c, int ev_slot) {       // up to the delta exch
     if (ev_slot >= 0) (void)hipEventRecord(c->kev[2 * ev_slot], c->stream);
     // (the [m, adj] of a single pair: with several ranks in the exchange header, which is summed over them)
     launch_merge(v, b, c->best, 0, is_multi(c) ? c->xb : &c->ctl->m, 1, w);
+    launch_log_plan(v, b);
     launch_scan_batch(v, b, w);
     if (ev_slot >= 0) (void)hipEventRecord(c->kev_f[2 * ev_slot], c->stream);
     launch_fused_batch(v, b, w);
-    // (the cell blocks become L / R rows before anything reads the rows: the exchange of several ranks, validation, apply.
-    //  Inside the events: the fold is part of what the pass costs)
-    launch_pair_cells_fold(v, b, batch_hint(c));
+    // (the logged records become L / R counts before anything reads the rows: the exchange of several ranks, validation,
+    //  apply.  Inside the events: the log's consumers are part of what the pass costs)
+    launch_log_consume(v, b);
     if (ev_slot >= 0) {
         (void)hipEventRecord(c->kev_f[2 * ev_slot + 1], c->stream);
         (void)hipEventRecord(c->kev[2 * ev_slot + 1], c->stream);
@@ -1949,7 +1976,7 @@ static int wide_convert(mbpe_ctx *c) {
     c->wide_active = true;
     // the 16-bit stream and table are done with (their merges stay in best[])
     tfree(c, c->tok[0]); tfree(c, c->tok[1]); tfree(c, c->sums); tfree(c, c->side); tfree(c, c->chg); tfree(c, c->tile_list);
-    tfree(c, c->offsets); tfree(c, c->run_in); tfree(c, c->xb); tfree(c, c->pair_cells);
+    tfree(c, c->offsets); tfree(c, c->run_in); tfree(c, c->xb); tfree(c, c->dlog); tfree(c, c->dpart); tfree(c, c->log_state);
     tfree(c, c->tab.hslot); tfree(c, c->tab.ekey); tfree(c, c->tab.ecnt); tfree(c, c->tab.bmax); tfree(c, c->tab.smax);
     tfree(c, c->first_state);                 // (the slot stream's `first` scratch; the 32-bit loop has its own)
     c->LR = nullptr;
@@ -2115,6 +2142,9 @@ int mbpe_get_stats(mbpe_ctx *c, mbpe_stats *out) {
     c->stats.cut_full = c->begun ? c->h_ctl.cut_full : 0;
     c->stats.n_validation_drops = c->begun ? c->h_ctl.n_validation_drops : 0;
     c->stats.n_sel_fallback = c->begun ? c->h_ctl.n_sel_fallback : 0;
+    c->stats.log_spilled = c->begun ? c->h_ctl.log_spilled : 0;
+    c->stats.log_passes = c->begun ? c->h_ctl.log_passes : 0;
+    c->stats.log_refills = c->begun ? c->h_ctl.log_refills : 0;
     c->stats.n_sel_retry = c->begun ? c->h_ctl.n_sel_retry : 0;
     c->stats.adapt_limit = c->begun ? c->h_ctl.adapt_limit : 0;
     c->stats.n_sel_blocks = c->begun ? c->h_ctl.n_sel_blocks : 0;

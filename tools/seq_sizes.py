@@ -37,4 +37,5 @@ while k < vocab - 256:
     k += got
 print(json.dumps({"columns": ["first_merge", "merges", "live_after", "slots", "ms_stream_kernels", "ms_fused", "ms_wall_seq",
                               "cut_conflict", "cut_full", "skipped", "sel_retry"],
-                  "sequences": len(rows), "rows": rows}))
+                  "sequences": len(rows), "rows": rows,
+                  "log": {k: prev.get(k) for k in ("log_passes", "log_spilled", "log_refills")}}))
