@@ -36,6 +36,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -298,48 +299,38 @@ __global__ __launch_bounds__(kSpanThreads) void k_dec_bounds(const void *__restr
 
 #define DCHK(expr) MBPE_HIP_CHECK(expr, false)
 
-int fail(int code, const char *msg) {
-    mbpe_host::set_last_error(msg);
-    return code;
-}
-
 }  // namespace
 
-struct mbpe_decoder {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct mbpe_decoder : DevQueue {
+    mbpe_decoder() : DevQueue(false) {}
     float last_ms = 0.f;
     // the tables
-    uint32_t *d_len = nullptr, *d_spk = nullptr, *d_spe = nullptr;
-    unsigned long long *d_off = nullptr;
-    uint8_t *d_blob = nullptr;
+    DevBuf<uint32_t> d_len, d_spk, d_spe;
+    DevBuf<unsigned long long> d_off;
+    DevBuf<uint8_t> d_blob;
     DecTab tab = {};
     // scratch, grown on demand and kept
-    unsigned long long *d_span = nullptr;     // span totals, then offsets
-    uint64_t cap_spans = 0;
-    unsigned long long *d_res = nullptr;      // [0] decoded length, [1] ids that decoded to nothing
-    void *d_tok = nullptr;                    // staging for tokens that come from the host
-    uint64_t cap_tok = 0;
-    uint8_t *d_out = nullptr;                 // staging for output that goes to the host
-    uint64_t cap_out = 0;
-    unsigned long long *d_doc_tok = nullptr;  // a batch's document boundaries: token offsets in,
-    unsigned long long *d_doc_byte = nullptr; // byte offsets out
-    uint64_t cap_doc_tok = 0, cap_doc_byte = 0;
-    uint64_t n_allocs = 0;                    // hipMalloc calls so far (mbpe_decoder_alloc_count)
+    DevBuf<unsigned long long> d_span;        // span totals, then offsets
+    DevBuf<unsigned long long> d_res;         // [0] decoded length, [1] ids that decoded to nothing
+    DevBuf<void> d_tok;                       // staging for tokens that come from the host
+    DevBuf<uint8_t> d_out;                    // staging for output that goes to the host
+    DevBuf<unsigned long long> d_doc_tok;     // a batch's document boundaries: token offsets in,
+    DevBuf<unsigned long long> d_doc_byte;    // byte offsets out
 };
 
 namespace {
 
-template <int F>
-void launch_len(mbpe_decoder *d, const void *tok, uint64_t n, uint32_t barrier, uint32_t grid) {
-    hipLaunchKernelGGL(k_dec_len<F>, dim3(grid), dim3(kSpanThreads), 0, d->stream, tok, n, barrier, d->tab, d->d_span,
-                       d->d_res + 1);
-}
-template <int F>
-void launch_write(mbpe_decoder *d, const void *tok, uint64_t n, uint32_t barrier, uint32_t grid, uint8_t *out) {
-    hipLaunchKernelGGL(k_dec_write<F>, dim3(grid), dim3(kSpanThreads), 0, d->stream, tok, n, barrier, d->tab, d->d_span,
-                       out);
+// the runtime format -> the kernels' template argument: f(std::integral_constant<int, F>())
+template <typename Fn>
+void with_format(int fmt, Fn f) {
+    switch (fmt) {
+        case kFmtU32: f(std::integral_constant<int, kFmtU32>()); break;
+        case kFmtU32End: f(std::integral_constant<int, kFmtU32End>()); break;
+        case kFmtU16: f(std::integral_constant<int, kFmtU16>()); break;
+        case kFmtU16End: f(std::integral_constant<int, kFmtU16End>()); break;
+        case kFmtU16Barrier: f(std::integral_constant<int, kFmtU16Barrier>()); break;
+        default: f(std::integral_constant<int, kFmtU16Plain>()); break;
+    }
 }
 
 template <int F>
@@ -361,25 +352,21 @@ int dec_measure(mbpe_decoder *d, int fmt, const void *tok, uint64_t n, uint32_t 
                 uint64_t *total, uint64_t *invalid) {
     const uint64_t n_spans = span_count(n);
     const uint32_t grid = span_grid(n);
-    int rc = grow(&d->d_span, &d->cap_spans, (n_spans + 1) * 8, false, &d->n_allocs);
+    int rc = d->d_span.reserve((n_spans + 1) * 8, d->mem);
     if (rc != MBPE_OK) return rc;
     if (docs && n) {
-        rc = grow(&d->d_doc_tok, &d->cap_doc_tok, docs->n_b * 8, false, &d->n_allocs);
-        if (rc == MBPE_OK) rc = grow(&d->d_doc_byte, &d->cap_doc_byte, docs->n_b * 8, false, &d->n_allocs);
+        rc = d->d_doc_tok.reserve(docs->n_b * 8, d->mem);
+        if (rc == MBPE_OK) rc = d->d_doc_byte.reserve(docs->n_b * 8, d->mem);
         if (rc != MBPE_OK) return rc;
         DCHK(hipMemcpyAsync(d->d_doc_tok, docs->tok_off, docs->n_b * 8, hipMemcpyHostToDevice, d->stream));
     }
     DCHK(hipMemsetAsync(d->d_res, 0, 16, d->stream));
     DCHK(hipEventRecord(d->ev0, d->stream));
     if (n) {
-        switch (fmt) {
-            case kFmtU32: launch_len<kFmtU32>(d, tok, n, barrier, grid); break;
-            case kFmtU32End: launch_len<kFmtU32End>(d, tok, n, barrier, grid); break;
-            case kFmtU16: launch_len<kFmtU16>(d, tok, n, barrier, grid); break;
-            case kFmtU16End: launch_len<kFmtU16End>(d, tok, n, barrier, grid); break;
-            case kFmtU16Barrier: launch_len<kFmtU16Barrier>(d, tok, n, barrier, grid); break;
-            default: launch_len<kFmtU16Plain>(d, tok, n, barrier, grid); break;
-        }
+        with_format(fmt, [&](auto f) {
+            hipLaunchKernelGGL(k_dec_len<f()>, dim3(grid), dim3(kSpanThreads), 0, d->stream, tok, n, barrier, d->tab,
+                               d->d_span, d->d_res + 1);
+        });
         hipLaunchKernelGGL(k_dec_scan64, dim3(1), dim3(kScanThreads), 0, d->stream, d->d_span, n_spans, d->d_res);
         if (docs) {
             // (a batch arrives as plain ids only: mbpe_decode_batch)
@@ -401,24 +388,17 @@ int dec_write(mbpe_decoder *d, int fmt, const void *tok, uint64_t n, uint32_t ba
               uint8_t *out_dev, bool wrote) {
     if (wrote && n) {
         const uint32_t grid = span_grid(n);
-        switch (fmt) {
-            case kFmtU32: launch_write<kFmtU32>(d, tok, n, barrier, grid, out_dev); break;
-            case kFmtU32End: launch_write<kFmtU32End>(d, tok, n, barrier, grid, out_dev); break;
-            case kFmtU16: launch_write<kFmtU16>(d, tok, n, barrier, grid, out_dev); break;
-            case kFmtU16End: launch_write<kFmtU16End>(d, tok, n, barrier, grid, out_dev); break;
-            case kFmtU16Barrier: launch_write<kFmtU16Barrier>(d, tok, n, barrier, grid, out_dev); break;
-            default: launch_write<kFmtU16Plain>(d, tok, n, barrier, grid, out_dev); break;
-        }
+        with_format(fmt, [&](auto f) {
+            hipLaunchKernelGGL(k_dec_write<f()>, dim3(grid), dim3(kSpanThreads), 0, d->stream, tok, n, barrier, d->tab,
+                               d->d_span, out_dev);
+        });
     }
     DCHK(hipEventRecord(d->ev1, d->stream));
     if (docs) {
         if (n) DCHK(hipMemcpyAsync(docs->byte_off_out, d->d_doc_byte, docs->n_b * 8, hipMemcpyDeviceToHost, d->stream));
         else memset(docs->byte_off_out, 0, docs->n_b * 8);      // no tokens: no kernel ran, every document is empty
     }
-    DCHK(hipStreamSynchronize(d->stream));
-    DCHK(hipGetLastError());
-    DCHK(hipEventElapsedTime(&d->last_ms, d->ev0, d->ev1));
-    return MBPE_OK;
+    return d->wait(&d->last_ms);
 }
 
 // tokens / slots in any layout -> bytes; the common body of the entry points (docs: a batch, or NULL)
@@ -432,7 +412,7 @@ int dec_run(mbpe_decoder *d, int fmt, const void *tokens, uint64_t n, int tokens
     const uint64_t tok_bytes = n * (fmt <= kFmtU32End ? 4 : 2);
     const void *tok = tokens;
     if (!tokens_on_device && n) {
-        int rc = grow(&d->d_tok, &d->cap_tok, tok_bytes, false, &d->n_allocs);
+        int rc = d->d_tok.reserve(tok_bytes, d->mem);
         if (rc != MBPE_OK) return rc;
         DCHK(hipMemcpyAsync(d->d_tok, tokens, tok_bytes, hipMemcpyHostToDevice, d->stream));
         tok = d->d_tok;
@@ -449,7 +429,7 @@ int dec_run(mbpe_decoder *d, int fmt, const void *tokens, uint64_t n, int tokens
     }
     if (out_on_device) return dec_write(d, fmt, tok, n, barrier, docs, bytes_out, true);
     if (total) {
-        rc = grow(&d->d_out, &d->cap_out, total, false, &d->n_allocs);
+        rc = d->d_out.reserve(total, d->mem);
         if (rc != MBPE_OK) return rc;
     }
     rc = dec_write(d, fmt, tok, n, barrier, docs, d->d_out, total != 0);
@@ -495,7 +475,7 @@ int decode_to_string(mbpe_decoder *d, const uint32_t *tokens, uint64_t n, std::s
     if (!d || (!tokens && n)) return fail(MBPE_ERR_ARG, "decode_to_string: NULL argument");
     DCHK(hipSetDevice(d->device));
     if (n) {
-        int rc = grow(&d->d_tok, &d->cap_tok, n * 4, false, &d->n_allocs);
+        int rc = d->d_tok.reserve(n * 4, d->mem);
         if (rc != MBPE_OK) return rc;
         DCHK(hipMemcpyAsync(d->d_tok, tokens, n * 4, hipMemcpyHostToDevice, d->stream));
     }
@@ -503,7 +483,7 @@ int decode_to_string(mbpe_decoder *d, const uint32_t *tokens, uint64_t n, std::s
     int rc = dec_measure(d, kFmtU32, d->d_tok, n, MBPE_NO_BARRIER, nullptr, &total, n_invalid);
     if (rc != MBPE_OK) return rc;
     if (total) {
-        rc = grow(&d->d_out, &d->cap_out, total, false, &d->n_allocs);
+        rc = d->d_out.reserve(total, d->mem);
         if (rc != MBPE_OK) return rc;
     }
     rc = dec_write(d, kFmtU32, d->d_tok, n, MBPE_NO_BARRIER, nullptr, d->d_out, total != 0);
@@ -606,23 +586,17 @@ int mbpe_decoder_create(int device_id, const uint32_t *merges, uint32_t n_merges
         at += l;
     }
 
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || device_id < 0 || device_id >= n_dev)
-        return fail(MBPE_ERR_NO_DEVICE, "no usable HIP device (the MI355X path has no CPU fallback)");
+    if (find_device(device_id) != MBPE_OK) return MBPE_ERR_NO_DEVICE;
     mbpe_decoder *d = new mbpe_decoder;
-    d->device = device_id;
     auto build = [&]() -> int {
-        DCHK(hipSetDevice(device_id));
-        DCHK(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-        DCHK(hipEventCreate(&d->ev0));
-        DCHK(hipEventCreate(&d->ev1));
-        DCHK(hipMalloc(&d->d_len, len.size() * 4));
-        DCHK(hipMalloc(&d->d_off, off.size() * 8));
-        DCHK(hipMalloc(&d->d_blob, blob.size()));
-        DCHK(hipMalloc(&d->d_spk, (size_t)sp_cap * 4));
-        DCHK(hipMalloc(&d->d_spe, (size_t)sp_cap * 4));
-        DCHK(hipMalloc(&d->d_res, 16));
-        d->n_allocs = 6;
+        int rc = d->open(device_id);
+        if (rc == MBPE_OK) rc = d->d_len.reserve(len.size() * 4, d->mem);
+        if (rc == MBPE_OK) rc = d->d_off.reserve(off.size() * 8, d->mem);
+        if (rc == MBPE_OK) rc = d->d_blob.reserve(blob.size(), d->mem);
+        if (rc == MBPE_OK) rc = d->d_spk.reserve((size_t)sp_cap * 4, d->mem);
+        if (rc == MBPE_OK) rc = d->d_spe.reserve((size_t)sp_cap * 4, d->mem);
+        if (rc == MBPE_OK) rc = d->d_res.reserve(16, d->mem);
+        if (rc != MBPE_OK) return rc;
         DCHK(hipMemcpyAsync(d->d_len, len.data(), len.size() * 4, hipMemcpyHostToDevice, d->stream));
         DCHK(hipMemcpyAsync(d->d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, d->stream));
         DCHK(hipMemcpyAsync(d->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, d->stream));
@@ -646,13 +620,7 @@ int mbpe_decoder_create(int device_id, const uint32_t *merges, uint32_t n_merges
 void mbpe_decoder_destroy(mbpe_decoder *d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
-    (void)hipFree(d->d_len); (void)hipFree(d->d_off); (void)hipFree(d->d_blob); (void)hipFree(d->d_spk);
-    (void)hipFree(d->d_spe); (void)hipFree(d->d_span); (void)hipFree(d->d_res); (void)hipFree(d->d_tok);
-    (void)hipFree(d->d_out); (void)hipFree(d->d_doc_tok); (void)hipFree(d->d_doc_byte);
-    if (d->ev0) (void)hipEventDestroy(d->ev0);
-    if (d->ev1) (void)hipEventDestroy(d->ev1);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    delete d;
+    delete d;                                 // the buffers, then the events, then the stream
 }
 
 int mbpe_decode_tokens(mbpe_decoder *d, const uint32_t *tokens, uint64_t n_tokens, int tokens_on_device,
@@ -694,7 +662,7 @@ int mbpe_decoder_kernel_ms(const mbpe_decoder *d, float *ms_out) {
 
 int mbpe_decoder_alloc_count(const mbpe_decoder *d, uint64_t *n_out) {
     if (!d || !n_out) return fail(MBPE_ERR_ARG, "mbpe_decoder_alloc_count: NULL argument");
-    *n_out = d->n_allocs;
+    *n_out = d->mem.n_allocs;
     return MBPE_OK;
 }
 

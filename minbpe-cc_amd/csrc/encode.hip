@@ -36,6 +36,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -352,11 +353,6 @@ __global__ __launch_bounds__(kSpanThreads) void k_enc_finish(const uint32_t *__r
 
 #define ECHK(expr) MBPE_HIP_CHECK(expr, true)
 
-int fail(int code, const std::string &msg) {
-    mbpe_host::set_last_error(msg);
-    return code;
-}
-
 // device bytes per text byte of a piece, rounded up (mbpe.h, "piece_bytes"): 13.2, and 20 / 1,024 more in rank order
 constexpr uint64_t kPieceCost = 14;
 constexpr uint64_t kNulListMin = 4096;     // entries the list of NUL-led chunk starts begins with
@@ -364,47 +360,34 @@ constexpr uint64_t kNulCopyEach = 256;     // up to this many NUL-led chunks are
 
 }  // namespace
 
-struct mbpe_encoder {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct mbpe_encoder : DevQueue {
+    mbpe_encoder() : DevQueue(true) {}
     float last_ms = 0.f;
-    uint64_t n_allocs = 0;                    // hipMalloc calls so far (mbpe_encoder_alloc_count)
     uint64_t piece_bytes = 0;                 // option "piece_bytes"; 0 = from the free device memory
     bool rank_order = false;                  // option "rank_order": a pass applies every chunk's lowest merge only
     uint32_t n_merges = 0;
     // the lookup table
-    unsigned long long *d_keys = nullptr;
-    uint32_t *d_vals = nullptr;
+    DevBuf<unsigned long long> d_keys;
+    DevBuf<uint32_t> d_vals;
     EncLut lut = {};
     // work buffers, grown on demand and kept
-    uint8_t *d_text = nullptr, *d_mask = nullptr;
-    uint32_t *tok[2] = {nullptr, nullptr}, *cand = nullptr, *span_a = nullptr, *span_b = nullptr;
-    unsigned long long *span_off = nullptr;
-    RankSum *rank_sum = nullptr;              // rank order only: the spans' summaries, and what reaches every span
-    uint32_t *rank_in = nullptr;              // from the left [0 .. n_spans) and from the right [n_spans .. 2 n_spans)
-    uint64_t cap_rank_sum = 0, cap_rank_in = 0;
-    uint64_t cap_text = 0, cap_mask = 0, cap_tok[2] = {0, 0}, cap_cand = 0, cap_span_a = 0, cap_span_b = 0,
-             cap_span_off = 0;
-    unsigned long long *d_res = nullptr;      // [0] total of a sum scan, [1] NUL-led chunk starts found
-    SingleChunk *d_singles = nullptr;
-    uint64_t cap_singles = 0;
-    unsigned long long *d_nul = nullptr;      // starts of NUL-led chunks of a device text
-    uint64_t cap_nul = 0;
-    unsigned long long *d_ends = nullptr;     // chunk ends, only when chunks are shorter than two bytes on average
-    uint64_t cap_ends = 0;
+    DevBuf<uint8_t> d_text, d_mask;
+    DevBuf<uint32_t> tok[2], cand, span_a, span_b;
+    DevBuf<unsigned long long> span_off;
+    DevBuf<RankSum> rank_sum;                 // rank order only: the spans' summaries, and what reaches every span
+    DevBuf<uint32_t> rank_in;                 // from the left [0 .. n_spans) and from the right [n_spans .. 2 n_spans)
+    DevBuf<unsigned long long> d_res;         // [0] total of a sum scan, [1] NUL-led chunk starts found
+    DevBuf<SingleChunk> d_singles;
+    DevBuf<unsigned long long> d_nul;         // starts of NUL-led chunks of a device text
+    DevBuf<unsigned long long> d_ends;        // chunk ends, only when chunks are shorter than two bytes on average
     // mbpe_encoder_encode_batch: the flat tokens of the batch, its document offsets, and a matrix that goes to the host
-    void *d_flat = nullptr;
-    unsigned long long *d_doc_off = nullptr;
-    void *d_ids = nullptr;
-    uint32_t *d_len = nullptr;
-    uint64_t cap_flat = 0, cap_doc_off = 0, cap_ids = 0, cap_len = 0;
-    unsigned long long *d_doc_pos = nullptr;  // mbpe_encoder_encode_endmask: the documents' byte offsets
-    uint64_t cap_doc_pos = 0;
+    DevBuf<void> d_flat, d_ids;
+    DevBuf<unsigned long long> d_doc_off;
+    DevBuf<uint32_t> d_len;
+    DevBuf<unsigned long long> d_doc_pos;     // mbpe_encoder_encode_endmask: the documents' byte offsets
     // mbpe_encoder_encode_batch_aux: labels, positions and segments that go to the host
-    void *d_labels = nullptr;
-    uint32_t *d_pos = nullptr, *d_seg = nullptr;
-    uint64_t cap_labels = 0, cap_pos = 0, cap_seg = 0;
+    DevBuf<void> d_labels;
+    DevBuf<uint32_t> d_pos, d_seg;
     float pack_ms = 0.f;                      // the pack kernel of the latest such call
     // host scratch
     std::vector<uint8_t> mask, bytes;
@@ -417,8 +400,8 @@ struct mbpe_encoder {
 namespace {
 
 uint64_t enc_held(const mbpe_encoder *e) {
-    return e->cap_text + e->cap_mask + e->cap_tok[0] + e->cap_tok[1] + e->cap_cand + e->cap_span_a + e->cap_span_b +
-           e->cap_span_off + e->cap_rank_sum + e->cap_rank_in;
+    return e->d_text.bytes() + e->d_mask.bytes() + e->tok[0].bytes() + e->tok[1].bytes() + e->cand.bytes() +
+           e->span_a.bytes() + e->span_b.bytes() + e->span_off.bytes() + e->rank_sum.bytes() + e->rank_in.bytes();
 }
 
 struct Piece { uint64_t c0, c1; };            // chunks [c0, c1)
@@ -447,8 +430,8 @@ int device_singles(mbpe_encoder *e, const uint8_t *d_text, const uint64_t *chunk
     const uint64_t base = chunk_off[p.c0], pn = chunk_off[p.c1] - base;
     if (pn == 0) return MBPE_OK;
     build_mask(e, chunk_off, p);
-    int rc = grow(&e->d_mask, &e->cap_mask, e->mask.size(), true, &e->n_allocs);
-    if (rc == MBPE_OK && !e->d_nul) rc = grow(&e->d_nul, &e->cap_nul, kNulListMin * 8, true, &e->n_allocs);
+    int rc = e->d_mask.reserve(e->mask.size(), e->mem);
+    if (rc == MBPE_OK && !e->d_nul) rc = e->d_nul.reserve(kNulListMin * 8, e->mem);
     if (rc != MBPE_OK) return rc;
     ECHK(hipMemcpyAsync(e->d_mask, e->mask.data(), e->mask.size(), hipMemcpyHostToDevice, e->stream));
     unsigned long long found = 0;
@@ -456,12 +439,12 @@ int device_singles(mbpe_encoder *e, const uint8_t *d_text, const uint64_t *chunk
         ECHK(hipMemsetAsync(e->d_res + 1, 0, 8, e->stream));
         const int blocks = (int)std::min<uint64_t>((pn + 255) / 256, 8192);
         hipLaunchKernelGGL(k_enc_nul_starts, dim3(blocks), dim3(256), 0, e->stream, d_text + base, pn, e->d_mask,
-                           e->d_nul, e->cap_nul / 8, e->d_res + 1);
+                           e->d_nul, e->d_nul.bytes() / 8, e->d_res + 1);
         ECHK(hipMemcpyAsync(&found, e->d_res + 1, 8, hipMemcpyDeviceToHost, e->stream));
         ECHK(hipStreamSynchronize(e->stream));
         ECHK(hipGetLastError());
-        if (found <= e->cap_nul / 8) break;
-        rc = grow(&e->d_nul, &e->cap_nul, found * 8, true, &e->n_allocs);
+        if (found <= e->d_nul.bytes() / 8) break;
+        rc = e->d_nul.reserve(found * 8, e->mem);
         if (rc != MBPE_OK) return rc;
     }
     if (found == 0) return MBPE_OK;
@@ -498,62 +481,74 @@ int device_singles(mbpe_encoder *e, const uint8_t *d_text, const uint64_t *chunk
     return MBPE_OK;
 }
 
-template <int MODE>
-void launch_finish(mbpe_encoder *e, dim3 grid, const uint32_t *tok, uint64_t n, void *out, bool with_ends,
-                   unsigned long long tok_base, unsigned long long *ends, unsigned long long ends_cap) {
-    if (with_ends)
-        hipLaunchKernelGGL((k_enc_finish<MODE, true>), grid, dim3(kSpanThreads), 0, e->stream, tok, n, out, e->span_off,
-                           tok_base, ends, ends_cap);
-    else if constexpr (MODE != kFinNone)            // (no tokens and no ends: nothing to launch)
-        hipLaunchKernelGGL((k_enc_finish<MODE, false>), grid, dim3(kSpanThreads), 0, e->stream, tok, n, out, e->span_off,
-                           tok_base, ends, ends_cap);
-}
-
+// one encode request, as the C-ABI states it; an entry point fills it once (what it leaves out is 0 / NULL)
 struct EncCall {
     const uint8_t *text;
+    uint64_t n_bytes;
     int text_on_device;
     const uint64_t *chunk_off;
+    uint64_t n_chunks;
     void *tokens_out;            // NULL: count only (and chunk offsets, when asked for)
     uint64_t cap;
     uint32_t token_bits;
     int out_on_device;
-    uint64_t *chunk_tok_off_out;
+    uint64_t *chunk_tok_off_out, *n_out;
+    uint32_t *n_passes_out;
     bool mask_on_device;         // the (single) piece's mask is on the device already
     // mbpe_encoder_encode_endmask: one piece whose mask is the caller's; the token offsets of the documents are left
     // in e->d_doc_off (and copied to doc_tok_off_out when that is given)
-    const uint8_t *mask_dev = nullptr;
-    const uint64_t *doc_off = nullptr;
-    uint64_t n_docs = 0;
-    uint64_t *doc_tok_off_out = nullptr;
+    const uint8_t *mask_dev;
+    const mbpe_single *singles;
+    uint64_t n_singles;
+    const uint64_t *doc_off;
+    uint64_t n_docs;
+    uint64_t *doc_tok_off_out;
 };
 
-// one piece through the passes and the finishing kernel.  done = tokens of the pieces before it.
-int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_t *n_piece, uint32_t *passes_out,
-              bool *too_small) {
-    const uint64_t base = a.chunk_off[p.c0], pn = a.chunk_off[p.c1] - base;
-    *n_piece = 0;
-    *passes_out = 0;
-    if (pn == 0) {
-        if (a.chunk_tok_off_out)
-            for (uint64_t c = p.c0; c < p.c1; ++c) a.chunk_tok_off_out[c + 1] = done;
-        return MBPE_OK;
-    }
+// what the batch calls add: the documents as chunk ranges (the endmask call has them in EncCall) and the pack step
+struct EncPack {
+    const uint64_t *doc_chunk_off;
+    uint64_t n_docs;
+    const mbpe_pack_spec *spec;
+    void *ids_out;
+    uint64_t cap_rows;
+    int out_on_device;
+    uint32_t *len_out;
+    uint64_t *n_rows_out, *n_tokens_out;
+    const mbpe_pack_aux *aux;
+    uint64_t *doc_tok_off_out;
+    uint32_t token_bits() const { return spec->out_bits == 16 ? 16 : 32; }
+};
+
+// a piece on its way: pn bytes at d_text, then n tokens in tok[cur] after `passes` passes; too_small: the caller's
+// cap does not hold them and nothing was written
+struct PieceRun {
+    uint64_t pn = 0, n = 0;
+    const uint8_t *d_text = nullptr;
+    int cur = 0;
+    uint32_t passes = 0;
+    bool too_small = false;
+};
+
+// buffers for the piece [base, base + pn) and what the host has of it: text, mask, singles, document offsets
+int piece_upload(mbpe_encoder *e, const EncCall &a, Piece p, PieceRun *r) {
+    const uint64_t base = a.chunk_off[p.c0], pn = r->pn;
     const uint64_t n_spans0 = span_count(pn);
     int rc = MBPE_OK;
-    if (!a.text_on_device) rc = grow(&e->d_text, &e->cap_text, pn, true, &e->n_allocs);
+    if (!a.text_on_device) rc = e->d_text.reserve(pn, e->mem);
     if (rc == MBPE_OK && !a.mask_on_device) {
         build_mask(e, a.chunk_off, p);
-        rc = grow(&e->d_mask, &e->cap_mask, e->mask.size(), true, &e->n_allocs);
+        rc = e->d_mask.reserve(e->mask.size(), e->mem);
     }
-    if (rc == MBPE_OK) rc = grow(&e->tok[0], &e->cap_tok[0], pn * 4, true, &e->n_allocs);
-    if (rc == MBPE_OK) rc = grow(&e->tok[1], &e->cap_tok[1], pn * 4, true, &e->n_allocs);
-    if (rc == MBPE_OK) rc = grow(&e->cand, &e->cap_cand, pn * 4, true, &e->n_allocs);
-    if (rc == MBPE_OK) rc = grow(&e->span_a, &e->cap_span_a, n_spans0 * 4, true, &e->n_allocs);
-    if (rc == MBPE_OK) rc = grow(&e->span_b, &e->cap_span_b, n_spans0 * 4, true, &e->n_allocs);
-    if (rc == MBPE_OK) rc = grow(&e->span_off, &e->cap_span_off, n_spans0 * 8, true, &e->n_allocs);
+    if (rc == MBPE_OK) rc = e->tok[0].reserve(pn * 4, e->mem);
+    if (rc == MBPE_OK) rc = e->tok[1].reserve(pn * 4, e->mem);
+    if (rc == MBPE_OK) rc = e->cand.reserve(pn * 4, e->mem);
+    if (rc == MBPE_OK) rc = e->span_a.reserve(n_spans0 * 4, e->mem);
+    if (rc == MBPE_OK) rc = e->span_b.reserve(n_spans0 * 4, e->mem);
+    if (rc == MBPE_OK) rc = e->span_off.reserve(n_spans0 * 8, e->mem);
     if (rc == MBPE_OK && e->rank_order) {
-        rc = grow(&e->rank_sum, &e->cap_rank_sum, n_spans0 * sizeof(RankSum), true, &e->n_allocs);
-        if (rc == MBPE_OK) rc = grow(&e->rank_in, &e->cap_rank_in, n_spans0 * 8, true, &e->n_allocs);
+        rc = e->rank_sum.reserve(n_spans0 * sizeof(RankSum), e->mem);
+        if (rc == MBPE_OK) rc = e->rank_in.reserve(n_spans0 * 8, e->mem);
     }
     if (rc != MBPE_OK) return rc;
     // the piece's NUL-led chunks (e->singles is sorted by start), relative to the piece
@@ -565,14 +560,13 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
             e->piece_singles.push_back({lo->start - base, lo->len, lo->id, 0});
     }
     if (!e->piece_singles.empty()) {
-        rc = grow(&e->d_singles, &e->cap_singles, e->piece_singles.size() * sizeof(SingleChunk), true,
-                  &e->n_allocs);
+        rc = e->d_singles.reserve(e->piece_singles.size() * sizeof(SingleChunk), e->mem);
         if (rc != MBPE_OK) return rc;
     }
-    const uint8_t *d_text = a.text + base;
+    r->d_text = a.text + base;
     if (!a.text_on_device) {
         ECHK(hipMemcpyAsync(e->d_text, a.text + base, pn, hipMemcpyHostToDevice, e->stream));
-        d_text = e->d_text;
+        r->d_text = e->d_text;
     }
     if (!a.mask_on_device)
         ECHK(hipMemcpyAsync(e->d_mask, e->mask.data(), e->mask.size(), hipMemcpyHostToDevice, e->stream));
@@ -581,15 +575,21 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
                             hipMemcpyHostToDevice, e->stream));
 
     if (a.doc_off) {
-        rc = grow(&e->d_doc_pos, &e->cap_doc_pos, (a.n_docs + 1) * 8, true, &e->n_allocs);
-        if (rc == MBPE_OK) rc = grow(&e->d_doc_off, &e->cap_doc_off, (a.n_docs + 1) * 8, true, &e->n_allocs);
+        rc = e->d_doc_pos.reserve((a.n_docs + 1) * 8, e->mem);
+        if (rc == MBPE_OK) rc = e->d_doc_off.reserve((a.n_docs + 1) * 8, e->mem);
         if (rc != MBPE_OK) return rc;
         ECHK(hipMemcpyAsync(e->d_doc_pos, a.doc_off, (a.n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
     }
+    return MBPE_OK;
+}
+
+// ev0, bytes -> tokens, then passes until one changes nothing
+int piece_passes(mbpe_encoder *e, const EncCall &a, PieceRun *r) {
+    const uint64_t pn = r->pn;
     ECHK(hipEventRecord(e->ev0, e->stream));
     const int wblocks = (int)std::min<uint64_t>((pn + 255) / 256, 8192);
-    hipLaunchKernelGGL(k_enc_widen, dim3(wblocks), dim3(256), 0, e->stream, d_text, pn, a.mask_dev ? a.mask_dev : e->d_mask,
-                       e->tok[0]);
+    hipLaunchKernelGGL(k_enc_widen, dim3(wblocks), dim3(256), 0, e->stream, r->d_text, pn,
+                       a.mask_dev ? a.mask_dev : e->d_mask, e->tok[0]);
     if (!e->piece_singles.empty())
         hipLaunchKernelGGL(k_enc_single, dim3((uint32_t)e->piece_singles.size()), dim3(64), 0, e->stream, e->d_singles,
                            (uint32_t)e->piece_singles.size(), e->tok[0]);
@@ -625,15 +625,22 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
         cur = 1 - cur;
         if (n == 0) break;
     }
-    *n_piece = n;
-    *passes_out = passes;
+    r->n = n;
+    r->cur = cur;
+    r->passes = passes;
+    return MBPE_OK;
+}
 
-    // the finishing kernel: ids in the caller's format (into cand when they go to the host), chunk ends into tok[1 - cur]
-    *too_small = a.tokens_out && a.cap < done + n;
-    const bool with_docs = a.doc_off && !*too_small;
-    const bool with_ends = (a.chunk_tok_off_out || a.doc_off) && !*too_small;
-    const bool with_tokens = a.tokens_out && !*too_small;
-    const uint64_t tok_bytes = a.token_bits / 8;
+// the finishing kernel: ids in the caller's format (into cand when they go to the host), chunk ends into tok[1 - cur];
+// ev1 and the kernel time; then what goes to the host: tokens, document offsets or the chunks' token offsets
+int piece_finish(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, PieceRun *r) {
+    const uint64_t n = r->n, pn = r->pn, tok_bytes = a.token_bits / 8;
+    const int cur = r->cur;
+    r->too_small = a.tokens_out && a.cap < done + n;
+    const bool with_docs = a.doc_off && !r->too_small;
+    const bool with_ends = (a.chunk_tok_off_out || a.doc_off) && !r->too_small;
+    const bool with_tokens = a.tokens_out && !r->too_small;
+    int rc = MBPE_OK;
     uint64_t n_ends = 0;
     unsigned long long *d_ends = nullptr;
     if (n && (with_ends || with_tokens)) {
@@ -652,10 +659,10 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
             } else {
                 for (uint64_t c = p.c0; c < p.c1; ++c) n_ends += a.chunk_off[c + 1] > a.chunk_off[c];
             }
-            if (n_ends * 8 <= e->cap_tok[1 - cur]) {
-                d_ends = reinterpret_cast<unsigned long long *>(e->tok[1 - cur]);
+            if (n_ends * 8 <= e->tok[1 - cur].bytes()) {
+                d_ends = reinterpret_cast<unsigned long long *>(e->tok[1 - cur].get());
             } else {
-                rc = grow(&e->d_ends, &e->cap_ends, n_ends * 8, true, &e->n_allocs);
+                rc = e->d_ends.reserve(n_ends * 8, e->mem);
                 if (rc != MBPE_OK) return rc;
                 d_ends = e->d_ends;
             }
@@ -667,13 +674,21 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
         }
         void *out = !with_tokens ? nullptr
                     : a.out_on_device ? static_cast<uint8_t *>(a.tokens_out) + done * tok_bytes
-                                      : reinterpret_cast<uint8_t *>(e->cand);
+                                      : reinterpret_cast<uint8_t *>(e->cand.get());
         const int mode = !with_tokens ? kFinNone : a.token_bits == 16 ? kFinU16 : a.out_on_device ? kFinFlags : kFinU32;
+        auto finish = [&](auto m) {
+            if (with_ends)
+                hipLaunchKernelGGL((k_enc_finish<m(), true>), grid, dim3(kSpanThreads), 0, e->stream, e->tok[cur], n, out,
+                                   e->span_off, done, d_ends, n_ends);
+            else if constexpr (m() != kFinNone)         // (no tokens and no ends: nothing to launch)
+                hipLaunchKernelGGL((k_enc_finish<m(), false>), grid, dim3(kSpanThreads), 0, e->stream, e->tok[cur], n, out,
+                                   e->span_off, done, d_ends, n_ends);
+        };
         switch (mode) {
-            case kFinFlags: launch_finish<kFinFlags>(e, grid, e->tok[cur], n, out, with_ends, done, d_ends, n_ends); break;
-            case kFinU32: launch_finish<kFinU32>(e, grid, e->tok[cur], n, out, with_ends, done, d_ends, n_ends); break;
-            case kFinU16: launch_finish<kFinU16>(e, grid, e->tok[cur], n, out, with_ends, done, d_ends, n_ends); break;
-            default: launch_finish<kFinNone>(e, grid, e->tok[cur], n, out, with_ends, done, d_ends, n_ends); break;
+            case kFinFlags: finish(std::integral_constant<int, kFinFlags>()); break;
+            case kFinU32: finish(std::integral_constant<int, kFinU32>()); break;
+            case kFinU16: finish(std::integral_constant<int, kFinU16>()); break;
+            default: finish(std::integral_constant<int, kFinNone>()); break;
         }
         if (with_docs) {
             // the rank of every document offset in the mask, then the look-up in the chunk ends (span_a and span_off
@@ -692,10 +707,8 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
     ECHK(hipEventRecord(e->ev1, e->stream));
     unsigned long long ends_found = 0;
     if (with_ends && !with_docs && n) ECHK(hipMemcpyAsync(&ends_found, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
-    ECHK(hipStreamSynchronize(e->stream));
-    ECHK(hipGetLastError());
     float ms = 0.f;
-    ECHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+    if ((rc = e->wait(&ms)) != MBPE_OK) return rc;
     e->last_ms += ms;
     if (with_tokens && !a.out_on_device && n) {
         ECHK(hipMemcpyAsync(static_cast<uint8_t *>(a.tokens_out) + done * tok_bytes, e->cand, n * tok_bytes,
@@ -723,22 +736,66 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, uint64_
     return MBPE_OK;
 }
 
-int enc_run_body(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device, const uint64_t *chunk_off,
-                 uint64_t n_chunks, void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device,
-                 uint64_t *chunk_tok_off_out, uint64_t *n_out, uint32_t *n_passes_out) {
-    const uint64_t one[2] = {0, n_bytes};
-    if (!chunk_off) { chunk_off = one; n_chunks = 1; }
+// one piece through the passes and the finishing stage.  done = tokens of the pieces before it.
+int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, PieceRun *r) {
+    *r = PieceRun{};
+    r->pn = a.chunk_off[p.c1] - a.chunk_off[p.c0];
+    if (r->pn == 0) {
+        if (a.chunk_tok_off_out)
+            for (uint64_t c = p.c0; c < p.c1; ++c) a.chunk_tok_off_out[c + 1] = done;
+        return MBPE_OK;
+    }
+    int rc = piece_upload(e, a, p, r);
+    if (rc == MBPE_OK) rc = piece_passes(e, a, r);
+    if (rc == MBPE_OK) rc = piece_finish(e, a, p, done, r);
+    return rc;
+}
+
+// the pieces in order -> sum: n = tokens of all, passes = the deepest.  After a piece that does not fit, the rest
+// is counted only.
+int run_pieces(mbpe_encoder *e, EncCall a, const std::vector<Piece> &pieces, PieceRun *sum) {
+    *sum = PieceRun{};
+    for (const Piece &p : pieces) {
+        PieceRun r;
+        const int rc = run_piece(e, a, p, sum->n, &r);
+        if (rc != MBPE_OK) return rc;
+        sum->n += r.n;
+        sum->passes = std::max(sum->passes, r.passes);
+        if (r.too_small) { sum->too_small = true; a.tokens_out = nullptr; a.chunk_tok_off_out = nullptr; }
+    }
+    return MBPE_OK;
+}
+
+// the bytes one piece may hold: the option, else what the buffers hold already, else from the free device memory
+int piece_limit(mbpe_encoder *e, uint64_t n_bytes, uint64_t *limit) {
+    *limit = e->piece_bytes;
+    if (*limit) return MBPE_OK;
+    *limit = e->cand.bytes() / 4;                                 // what the buffers hold already needs no question
+    if (n_bytes > *limit) {
+        size_t free_b = 0, total_b = 0;
+        ECHK(hipMemGetInfo(&free_b, &total_b));
+        const uint64_t avail = (uint64_t)free_b + enc_held(e);
+        *limit = std::max<uint64_t>((avail - avail / 16) / kPieceCost, *limit);
+    }
+    return MBPE_OK;
+}
+
+int enc_run_body(mbpe_encoder *e, EncCall a) {
+    const uint64_t one[2] = {0, a.n_bytes};
+    if (!a.chunk_off) { a.chunk_off = one; a.n_chunks = 1; }
+    const uint64_t *chunk_off = a.chunk_off;
+    const uint64_t n_bytes = a.n_bytes, n_chunks = a.n_chunks;
     if (chunk_off[0] != 0 || chunk_off[n_chunks] != n_bytes)
         return fail(MBPE_ERR_ARG, "chunk_off must start at 0 and end at n_bytes");
     // (every offset is checked before one is used: an offset beyond n_bytes would index the mask and the text below)
     for (uint64_t c = 0; c < n_chunks; ++c)
         if (chunk_off[c + 1] < chunk_off[c]) return fail(MBPE_ERR_ARG, "chunk_off must be ascending");
-    if (token_bits == 16 && 256ull + e->n_merges > 65536ull)
+    if (a.token_bits == 16 && 256ull + e->n_merges > 65536ull)
         return fail(MBPE_ERR_VOCAB, "token_bits 16 with more than 65,536 token ids");
-    if (chunk_tok_off_out) chunk_tok_off_out[0] = 0;
+    if (a.chunk_tok_off_out) a.chunk_tok_off_out[0] = 0;
     if (n_bytes == 0) {
-        if (chunk_tok_off_out)
-            for (uint64_t c = 0; c < n_chunks; ++c) chunk_tok_off_out[c + 1] = 0;
+        if (a.chunk_tok_off_out)
+            for (uint64_t c = 0; c < n_chunks; ++c) a.chunk_tok_off_out[c + 1] = 0;
         return MBPE_OK;
     }
     ECHK(hipSetDevice(e->device));
@@ -746,16 +803,9 @@ int enc_run_body(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int tex
     e->pass_tokens.clear();
 
     // pieces: whole chunks, at most `limit` bytes each
-    uint64_t limit = e->piece_bytes;
-    if (limit == 0) {
-        limit = e->cap_cand / 4;                                  // what the buffers hold already needs no question
-        if (n_bytes > limit) {
-            size_t free_b = 0, total_b = 0;
-            ECHK(hipMemGetInfo(&free_b, &total_b));
-            const uint64_t avail = (uint64_t)free_b + enc_held(e);
-            limit = std::max<uint64_t>((avail - avail / 16) / kPieceCost, limit);
-        }
-    }
+    uint64_t limit = 0;
+    int rc = piece_limit(e, n_bytes, &limit);
+    if (rc != MBPE_OK) return rc;
     std::vector<Piece> pieces;
     if (n_bytes <= limit) {
         pieces.push_back({0, n_chunks});
@@ -776,122 +826,97 @@ int enc_run_body(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int tex
 
     // chunks that are one token, of the whole text, before any pass runs
     e->singles.clear();
-    bool mask_on_device = false;
-    if (!text_on_device) {
+    if (!a.text_on_device) {
         for (uint64_t c = 0; c < n_chunks; ++c) {
             const uint64_t s = chunk_off[c], t = chunk_off[c + 1];
             long long id;
-            if (t > s && text[s] == 0 && stoi_value(text + s + 1, t - s - 1, &id)) {
-                const int rc = add_single(e, s, t - s, id, token_bits);
+            if (t > s && a.text[s] == 0 && stoi_value(a.text + s + 1, t - s - 1, &id)) {
+                rc = add_single(e, s, t - s, id, a.token_bits);
                 if (rc != MBPE_OK) return rc;
             }
         }
     } else {
         for (const Piece &p : pieces) {
-            const int rc = device_singles(e, text, chunk_off, p, token_bits);
+            rc = device_singles(e, a.text, chunk_off, p, a.token_bits);
             if (rc != MBPE_OK) return rc;
         }
-        mask_on_device = pieces.size() == 1;
+        a.mask_on_device = pieces.size() == 1;
     }
 
-    EncCall a = {text, text_on_device, chunk_off, tokens_out, cap, token_bits, out_on_device, chunk_tok_off_out,
-                 mask_on_device};
+    PieceRun sum;
     // "a cap too small writes no token": where the pieces before the one that overflows would already have written
     // theirs, the count comes first (cap >= n_bytes always suffices and never takes this path)
-    if (pieces.size() > 1 && tokens_out && cap < n_bytes) {
+    if (pieces.size() > 1 && a.tokens_out && a.cap < n_bytes) {
         EncCall q = a;
         q.tokens_out = nullptr;
         q.chunk_tok_off_out = nullptr;
-        uint64_t total = 0;
-        uint32_t deepest = 0;
-        for (const Piece &p : pieces) {
-            uint64_t n = 0;
-            uint32_t passes = 0;
-            bool small = false;
-            const int rc = run_piece(e, q, p, total, &n, &passes, &small);
-            if (rc != MBPE_OK) return rc;
-            total += n;
-            deepest = std::max(deepest, passes);
-        }
-        if (cap < total) {
-            *n_out = total;
-            if (n_passes_out) *n_passes_out = deepest;
+        rc = run_pieces(e, q, pieces, &sum);
+        if (rc != MBPE_OK) return rc;
+        if (a.cap < sum.n) {
+            *a.n_out = sum.n;
+            if (a.n_passes_out) *a.n_passes_out = sum.passes;
             return fail(MBPE_ERR_ARG, "tokens_out too small");
         }
         e->pass_tokens.clear();                    // (the kernel time keeps both runs, the pass counts one)
     }
-    uint64_t total = 0;
-    uint32_t deepest = 0;
-    bool too_small = false;
-    for (const Piece &p : pieces) {
-        uint64_t n = 0;
-        uint32_t passes = 0;
-        bool small = false;
-        const int rc = run_piece(e, a, p, total, &n, &passes, &small);
-        if (rc != MBPE_OK) return rc;
-        total += n;
-        deepest = std::max(deepest, passes);
-        if (small) { too_small = true; a.tokens_out = nullptr; a.chunk_tok_off_out = nullptr; }
-    }
-    *n_out = total;
-    if (n_passes_out) *n_passes_out = deepest;
-    if (too_small) return fail(MBPE_ERR_ARG, "tokens_out too small");
+    rc = run_pieces(e, a, pieces, &sum);
+    if (rc != MBPE_OK) return rc;
+    *a.n_out = sum.n;
+    if (a.n_passes_out) *a.n_passes_out = sum.passes;
+    if (sum.too_small) return fail(MBPE_ERR_ARG, "tokens_out too small");
     return MBPE_OK;
 }
 
 // (the host vectors -- mask, lists, the bytes of NUL-led chunks -- grow with the text: no exception leaves the C-ABI)
-int enc_run(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device, const uint64_t *chunk_off,
-            uint64_t n_chunks, void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device,
-            uint64_t *chunk_tok_off_out, uint64_t *n_out, uint32_t *n_passes_out) {
+template <typename F>
+int enc_guard(const std::string &who, F body) {
     try {
-        return enc_run_body(e, text, n_bytes, text_on_device, chunk_off, n_chunks, tokens_out, cap, token_bits,
-                            out_on_device, chunk_tok_off_out, n_out, n_passes_out);
+        return body();
     } catch (const std::bad_alloc &) {
-        return fail(MBPE_ERR_OOM, "mbpe_encoder_encode: host allocation failed");
+        return fail(MBPE_ERR_OOM, who + ": host allocation failed");
     }
 }
 
 // the pack step of the batch calls: the flat tokens in e->d_flat, the documents' token offsets in e->doc_tok (host;
 // docs_on_device: in e->d_doc_off already, and on the host only where doc_tok_off_out asks for them)
-int enc_pack_tail(mbpe_encoder *e, uint64_t n_tokens, uint64_t n_docs, uint32_t token_bits, const mbpe_pack_spec &spec,
-                  void *ids_out, uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
-                  uint64_t *n_tokens_out, const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out, bool docs_on_device) {
+int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool docs_on_device) {
+    const mbpe_pack_spec &spec = *k.spec;
+    const mbpe_pack_aux *aux = k.aux;
+    const uint64_t n_docs = k.n_docs;
     int rc = MBPE_OK;
     const uint64_t n_rows = pack_rows(spec, n_tokens, n_docs);
-    *n_rows_out = n_rows;
-    if (n_tokens_out) *n_tokens_out = n_tokens;
-    if (ids_out && cap_rows < n_rows) return fail(MBPE_ERR_ARG, "ids_out too small");
-    if (doc_tok_off_out) std::copy(e->doc_tok.begin(), e->doc_tok.end(), doc_tok_off_out);   // (filled in both cases)
-    if (!ids_out) return MBPE_OK;                                // the query
+    *k.n_rows_out = n_rows;
+    if (k.n_tokens_out) *k.n_tokens_out = n_tokens;
+    if (k.ids_out && k.cap_rows < n_rows) return fail(MBPE_ERR_ARG, "ids_out too small");
+    if (k.doc_tok_off_out) std::copy(e->doc_tok.begin(), e->doc_tok.end(), k.doc_tok_off_out);   // (filled in both cases)
+    if (!k.ids_out) return MBPE_OK;                              // the query
     if (n_rows == 0) return MBPE_OK;
     const uint64_t id_bytes = n_rows * spec.seq_len * (spec.out_bits / 8), cell_bytes = n_rows * spec.seq_len * 4;
-    rc = grow(&e->d_doc_off, &e->cap_doc_off, (n_docs + 1) * 8, true, &e->n_allocs);
-    if (rc == MBPE_OK && !out_on_device) {
-        rc = grow(&e->d_ids, &e->cap_ids, id_bytes, true, &e->n_allocs);
-        if (rc == MBPE_OK && len_out) rc = grow(&e->d_len, &e->cap_len, n_rows * 4, true, &e->n_allocs);
+    rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
+    if (rc == MBPE_OK && !k.out_on_device) {
+        rc = e->d_ids.reserve(id_bytes, e->mem);
+        if (rc == MBPE_OK && k.len_out) rc = e->d_len.reserve(n_rows * 4, e->mem);
     }
     mbpe_pack_aux d_aux = aux ? *aux : mbpe_pack_aux{};
-    if (rc == MBPE_OK && aux && !out_on_device) {
-        if (aux->labels) { rc = grow(&e->d_labels, &e->cap_labels, id_bytes, true, &e->n_allocs); d_aux.labels = e->d_labels; }
-        if (rc == MBPE_OK && aux->pos) { rc = grow(&e->d_pos, &e->cap_pos, cell_bytes, true, &e->n_allocs); d_aux.pos = e->d_pos; }
-        if (rc == MBPE_OK && aux->seg) { rc = grow(&e->d_seg, &e->cap_seg, cell_bytes, true, &e->n_allocs); d_aux.seg = e->d_seg; }
+    if (rc == MBPE_OK && aux && !k.out_on_device) {
+        if (aux->labels) { rc = e->d_labels.reserve(id_bytes, e->mem); d_aux.labels = e->d_labels; }
+        if (rc == MBPE_OK && aux->pos) { rc = e->d_pos.reserve(cell_bytes, e->mem); d_aux.pos = e->d_pos; }
+        if (rc == MBPE_OK && aux->seg) { rc = e->d_seg.reserve(cell_bytes, e->mem); d_aux.seg = e->d_seg; }
     }
     if (rc != MBPE_OK) return rc;
     if (!docs_on_device)
         ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
-    const PackSrc src = {e->d_flat, e->d_doc_off, n_docs, n_tokens, token_bits};
-    const PackDst dst = {out_on_device ? ids_out : e->d_ids, out_on_device || !len_out ? len_out : e->d_len, n_rows};
+    const PackSrc src = {e->d_flat, e->d_doc_off, n_docs, n_tokens, k.token_bits()};
+    const PackDst dst = {k.out_on_device ? k.ids_out : e->d_ids.get(),
+                         k.out_on_device || !k.len_out ? k.len_out : e->d_len.get(), n_rows};
     ECHK(hipEventRecord(e->ev0, e->stream));
     if (aux) pack_launch_aux(e->stream, src, spec, dst, d_aux);
     else pack_launch(e->stream, src, spec, dst);
-    ECHK(hipEventRecord(e->ev1, e->stream));
-    ECHK(hipStreamSynchronize(e->stream));
-    ECHK(hipGetLastError());
-    ECHK(hipEventElapsedTime(&e->pack_ms, e->ev0, e->ev1));
+    if ((rc = e->finish(&e->pack_ms)) != MBPE_OK) return rc;
     e->last_ms += e->pack_ms;
-    if (!out_on_device) {
-        ECHK(hipMemcpyAsync(ids_out, e->d_ids, id_bytes, hipMemcpyDeviceToHost, e->stream));
-        if (len_out) ECHK(hipMemcpyAsync(len_out, e->d_len, n_rows * 4, hipMemcpyDeviceToHost, e->stream));
+    if (!k.out_on_device) {
+        ECHK(hipMemcpyAsync(k.ids_out, e->d_ids, id_bytes, hipMemcpyDeviceToHost, e->stream));
+        if (k.len_out) ECHK(hipMemcpyAsync(k.len_out, e->d_len, n_rows * 4, hipMemcpyDeviceToHost, e->stream));
         if (aux && aux->labels) ECHK(hipMemcpyAsync(aux->labels, e->d_labels, id_bytes, hipMemcpyDeviceToHost, e->stream));
         if (aux && aux->pos) ECHK(hipMemcpyAsync(aux->pos, e->d_pos, cell_bytes, hipMemcpyDeviceToHost, e->stream));
         if (aux && aux->seg) ECHK(hipMemcpyAsync(aux->seg, e->d_seg, cell_bytes, hipMemcpyDeviceToHost, e->stream));
@@ -900,80 +925,85 @@ int enc_pack_tail(mbpe_encoder *e, uint64_t n_tokens, uint64_t n_docs, uint32_t 
     return MBPE_OK;
 }
 
-// encode into the kept flat buffer, then pack from it on the encoder's stream (arguments checked by the caller)
-int enc_batch_body(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device, const uint64_t *chunk_off,
-                   uint64_t n_chunks, const uint64_t *doc_chunk_off, uint64_t n_docs, const mbpe_pack_spec &spec,
-                   void *ids_out, uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
-                   uint64_t *n_tokens_out, const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out) {
-    const uint32_t token_bits = spec.out_bits == 16 ? 16 : 32;
+// what the batch calls check alike once their own arguments are in order (the document lengths: after the encode)
+int enc_batch_check(const mbpe_encoder *e, const EncPack &k) {
+    if (k.spec->out_bits == 16 && 256ull + e->n_merges > 65536ull)
+        return fail(MBPE_ERR_VOCAB, "out_bits 16 with more than 65,536 token ids");
+    if (k.ids_out && k.out_on_device &&
+        ((uint64_t)(uintptr_t)k.ids_out % (k.spec->out_bits / 8) || (uint64_t)(uintptr_t)k.len_out % 4))
+        return fail(MBPE_ERR_ARG, "ids_out or len_out is not aligned to its elements");
+    return k.aux ? pack_check_aux(*k.spec, k.aux, nullptr, k.n_docs, k.ids_out, k.out_on_device) : MBPE_OK;
+}
+
+// the flat buffer both batch calls encode into, as the request's output
+int enc_batch_flat(mbpe_encoder *e, EncCall *a, const EncPack &k, uint64_t *n_tokens) {
     ECHK(hipSetDevice(e->device));
-    int rc = grow(&e->d_flat, &e->cap_flat, std::max<uint64_t>(n_bytes, 1) * (token_bits / 8), true, &e->n_allocs);
+    const int rc = e->d_flat.reserve(std::max<uint64_t>(a->n_bytes, 1) * (k.token_bits() / 8), e->mem);
+    if (rc != MBPE_OK) return rc;
+    e->pack_ms = 0.f;
+    a->tokens_out = e->d_flat;
+    a->cap = a->n_bytes;
+    a->token_bits = k.token_bits();
+    a->out_on_device = 1;
+    a->n_out = n_tokens;
+    a->n_passes_out = nullptr;
+    return MBPE_OK;
+}
+
+// encode into the kept flat buffer, then pack from it on the encoder's stream (arguments checked by the caller)
+int enc_batch_body(mbpe_encoder *e, EncCall a, const EncPack &k) {
+    uint64_t n_tokens = 0;
+    int rc = enc_batch_flat(e, &a, k, &n_tokens);
     if (rc != MBPE_OK) return rc;
     e->last_ms = 0.f;
-    e->pack_ms = 0.f;
-    e->chunk_tok.assign(n_chunks + 1, 0);
-    uint64_t n_tokens = 0;
-    rc = enc_run_body(e, text, n_bytes, text_on_device, chunk_off, n_chunks, e->d_flat, n_bytes, token_bits, 1,
-                      e->chunk_tok.data(), &n_tokens, nullptr);
+    e->chunk_tok.assign(a.n_chunks + 1, 0);
+    a.chunk_tok_off_out = e->chunk_tok.data();
+    rc = enc_run_body(e, a);
     if (rc != MBPE_OK) return rc;
-    e->doc_tok.resize(n_docs + 1);
-    for (uint64_t i = 0; i <= n_docs; ++i) e->doc_tok[i] = e->chunk_tok[doc_chunk_off[i]];
+    e->doc_tok.resize(k.n_docs + 1);
+    for (uint64_t i = 0; i <= k.n_docs; ++i) e->doc_tok[i] = e->chunk_tok[k.doc_chunk_off[i]];
     // (the document lengths exist only now: the limit of pos comes here, still before the pack kernel)
-    if (aux) rc = pack_check_aux(spec, aux, e->doc_tok.data(), n_docs, nullptr, 0);
+    if (k.aux) rc = pack_check_aux(*k.spec, k.aux, e->doc_tok.data(), k.n_docs, nullptr, 0);
     if (rc != MBPE_OK) return rc;
-    return enc_pack_tail(e, n_tokens, n_docs, token_bits, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out,
-                         n_tokens_out, aux, doc_tok_off_out, false);
+    return enc_pack_tail(e, k, n_tokens, false);
 }
 
 // mbpe_encoder_encode_endmask after its checks: one piece, text and mask where they are
-int enc_endmask_body(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes, const uint8_t *mask_dev,
-                     const mbpe_single *singles, uint64_t n_singles, const uint64_t *doc_off, uint64_t n_docs,
-                     void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device, uint64_t *doc_tok_off_out,
-                     uint64_t *n_out, uint32_t *n_passes_out) {
-    if (doc_off && doc_tok_off_out) doc_tok_off_out[0] = 0;
+int enc_endmask_body(mbpe_encoder *e, EncCall a) {
+    const uint64_t n_bytes = a.n_bytes, n_docs = a.n_docs;
+    if (a.doc_off && a.doc_tok_off_out) a.doc_tok_off_out[0] = 0;
     ECHK(hipSetDevice(e->device));
     e->last_ms = 0.f;
     e->pass_tokens.clear();
     if (n_bytes == 0) {
-        if (doc_off) {
-            int rc = grow(&e->d_doc_off, &e->cap_doc_off, (n_docs + 1) * 8, true, &e->n_allocs);
+        if (a.doc_off) {
+            int rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
             if (rc != MBPE_OK) return rc;
             ECHK(hipMemsetAsync(e->d_doc_off, 0, (n_docs + 1) * 8, e->stream));
             ECHK(hipStreamSynchronize(e->stream));
-            if (doc_tok_off_out) std::fill(doc_tok_off_out, doc_tok_off_out + n_docs + 1, 0);
+            if (a.doc_tok_off_out) std::fill(a.doc_tok_off_out, a.doc_tok_off_out + n_docs + 1, 0);
         }
         return MBPE_OK;
     }
-    uint64_t limit = e->piece_bytes;                              // the rule of mbpe_encoder_encode
-    if (limit == 0) {
-        limit = e->cap_cand / 4;
-        if (n_bytes > limit) {
-            size_t free_b = 0, total_b = 0;
-            ECHK(hipMemGetInfo(&free_b, &total_b));
-            const uint64_t avail = (uint64_t)free_b + enc_held(e);
-            limit = std::max<uint64_t>((avail - avail / 16) / kPieceCost, limit);
-        }
-    }
+    uint64_t limit = 0;                                           // the rule of mbpe_encoder_encode
+    int rc = piece_limit(e, n_bytes, &limit);
+    if (rc != MBPE_OK) return rc;
     if (n_bytes > limit)
         return fail(MBPE_ERR_OOM, "mbpe_encoder_encode_endmask: the text has " + std::to_string(n_bytes) +
                                       " bytes, more than one piece may hold (" + std::to_string(limit) +
                                       "; option \"piece_bytes\"), and a mask on the device is not cut into pieces");
     e->singles.clear();
-    for (uint64_t k = 0; k < n_singles; ++k) e->singles.push_back({singles[k].start, singles[k].len, singles[k].id, 0});
+    for (uint64_t k = 0; k < a.n_singles; ++k)
+        e->singles.push_back({a.singles[k].start, a.singles[k].len, a.singles[k].id, 0});
     const uint64_t one[2] = {0, n_bytes};
-    EncCall a = {text_dev, 1, one, tokens_out, cap, token_bits, out_on_device, nullptr, true};
-    a.mask_dev = mask_dev;
-    a.doc_off = doc_off;
-    a.n_docs = n_docs;
-    a.doc_tok_off_out = doc_tok_off_out;
-    uint64_t n = 0;
-    uint32_t passes = 0;
-    bool small = false;
-    const int rc = run_piece(e, a, Piece{0, 1}, 0, &n, &passes, &small);
+    a.chunk_off = one;
+    a.n_chunks = 1;
+    PieceRun r;
+    rc = run_piece(e, a, Piece{0, 1}, 0, &r);
     if (rc != MBPE_OK) return rc;
-    *n_out = n;
-    if (n_passes_out) *n_passes_out = passes;
-    if (small) return fail(MBPE_ERR_ARG, "tokens_out too small");
+    *a.n_out = r.n;
+    if (a.n_passes_out) *a.n_passes_out = r.passes;
+    if (r.too_small) return fail(MBPE_ERR_ARG, "tokens_out too small");
     return MBPE_OK;
 }
 
@@ -1010,8 +1040,9 @@ int encode_chunks(int device_id, const uint8_t *text, uint64_t n_bytes, const ui
     mbpe_encoder *e = nullptr;
     int rc = mbpe_encoder_create(device_id, merges, n_merges, &e);
     if (rc != MBPE_OK) return rc;
-    rc = enc_run(e, text, n_bytes, 0, chunk_off, n_chunks, tokens_out, cap, 32, out_on_device ? 1 : 0, nullptr, n_out,
-                 n_passes_out);
+    const EncCall a = {text, n_bytes, 0, chunk_off, n_chunks, tokens_out, cap, 32, out_on_device ? 1 : 0, nullptr, n_out,
+                       n_passes_out};
+    rc = enc_guard("mbpe_encoder_encode", [&] { return enc_run_body(e, a); });
     const std::string keep = rc == MBPE_OK ? std::string() : std::string(mbpe_host::last_error());
     mbpe_encoder_destroy(e);
     if (rc != MBPE_OK) mbpe_host::set_last_error(keep);
@@ -1044,22 +1075,15 @@ int mbpe_encoder_create(int device_id, const uint32_t *merges, uint32_t n_merges
         keys[h] = key;
         vals[h] = 256 + k;
     }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || device_id < 0 || device_id >= n_dev)
-        return fail(MBPE_ERR_NO_DEVICE, "no usable HIP device (the MI355X path has no CPU fallback)");
+    if (find_device(device_id) != MBPE_OK) return MBPE_ERR_NO_DEVICE;
     mbpe_encoder *e = new (std::nothrow) mbpe_encoder;
     if (!e) return fail(MBPE_ERR_OOM, "mbpe_encoder_create: host allocation failed");
-    e->device = device_id;
     e->n_merges = n_merges;
     auto build = [&]() -> int {
-        uint64_t cap_keys = 0, cap_vals = 0, cap_res = 0;
-        ECHK(hipSetDevice(device_id));
-        ECHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-        ECHK(hipEventCreate(&e->ev0));
-        ECHK(hipEventCreate(&e->ev1));
-        int rc = grow(&e->d_keys, &cap_keys, (uint64_t)capacity * 8, true, &e->n_allocs);
-        if (rc == MBPE_OK) rc = grow(&e->d_vals, &cap_vals, (uint64_t)capacity * 4, true, &e->n_allocs);
-        if (rc == MBPE_OK) rc = grow(&e->d_res, &cap_res, 16, true, &e->n_allocs);
+        int rc = e->open(device_id);
+        if (rc == MBPE_OK) rc = e->d_keys.reserve((uint64_t)capacity * 8, e->mem);
+        if (rc == MBPE_OK) rc = e->d_vals.reserve((uint64_t)capacity * 4, e->mem);
+        if (rc == MBPE_OK) rc = e->d_res.reserve(16, e->mem);
         if (rc != MBPE_OK) return rc;
         ECHK(hipMemcpyAsync(e->d_keys, keys.data(), (size_t)capacity * 8, hipMemcpyHostToDevice, e->stream));
         ECHK(hipMemcpyAsync(e->d_vals, vals.data(), (size_t)capacity * 4, hipMemcpyHostToDevice, e->stream));
@@ -1081,17 +1105,7 @@ int mbpe_encoder_create(int device_id, const uint32_t *merges, uint32_t n_merges
 void mbpe_encoder_destroy(mbpe_encoder *e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
-    (void)hipFree(e->d_keys); (void)hipFree(e->d_vals); (void)hipFree(e->d_text); (void)hipFree(e->d_mask);
-    (void)hipFree(e->tok[0]); (void)hipFree(e->tok[1]); (void)hipFree(e->cand); (void)hipFree(e->span_a);
-    (void)hipFree(e->span_b); (void)hipFree(e->span_off); (void)hipFree(e->d_res); (void)hipFree(e->d_singles);
-    (void)hipFree(e->d_nul); (void)hipFree(e->d_ends); (void)hipFree(e->d_flat); (void)hipFree(e->d_doc_off);
-    (void)hipFree(e->d_ids); (void)hipFree(e->d_len); (void)hipFree(e->d_labels); (void)hipFree(e->d_pos);
-    (void)hipFree(e->d_seg); (void)hipFree(e->d_doc_pos);
-    (void)hipFree(e->rank_sum); (void)hipFree(e->rank_in);
-    if (e->ev0) (void)hipEventDestroy(e->ev0);
-    if (e->ev1) (void)hipEventDestroy(e->ev1);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
+    delete e;                                 // the buffers, then the events, then the stream
 }
 
 int mbpe_encoder_set_option(mbpe_encoder *e, const char *name, int64_t value) {
@@ -1117,47 +1131,32 @@ int mbpe_encoder_encode(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, 
     if (n_passes_out) *n_passes_out = 0;
     if (!e || !n_out || (!text && n_bytes)) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode: NULL argument");
     if (token_bits != 16 && token_bits != 32) return fail(MBPE_ERR_ARG, "token_bits must be 16 or 32");
-    return enc_run(e, text, n_bytes, text_on_device, chunk_off, n_chunks, tokens_out, cap, token_bits, out_on_device,
-                   chunk_tok_off_out, n_out, n_passes_out);
+    const EncCall a = {text, n_bytes, text_on_device, chunk_off, n_chunks, tokens_out, cap, token_bits, out_on_device,
+                       chunk_tok_off_out, n_out, n_passes_out};
+    return enc_guard("mbpe_encoder_encode", [&] { return enc_run_body(e, a); });
 }
 
 // mbpe_encoder_encode_batch (aux NULL) and mbpe_encoder_encode_batch_aux: the checks that need no device, then the call
-static int enc_batch(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
-                     const uint64_t *chunk_off, uint64_t n_chunks, const uint64_t *doc_chunk_off, uint64_t n_docs,
-                     const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device, uint32_t *len_out,
-                     uint64_t *n_rows_out, uint64_t *n_tokens_out, const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out) {
-    if (n_rows_out) *n_rows_out = 0;
-    if (n_tokens_out) *n_tokens_out = 0;
-    if (!e || !n_rows_out || !doc_chunk_off || !spec || (!text && n_bytes))
+static int enc_batch(mbpe_encoder *e, EncCall a, const EncPack &k) {
+    if (k.n_rows_out) *k.n_rows_out = 0;
+    if (k.n_tokens_out) *k.n_tokens_out = 0;
+    if (!e || !k.n_rows_out || !k.doc_chunk_off || !k.spec || (!a.text && a.n_bytes))
         return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_batch: NULL argument");
-    int rc = pack_check_spec(spec, spec->out_bits == 16 ? 16 : 32);
+    int rc = pack_check_spec(k.spec, k.token_bits());
     if (rc != MBPE_OK) return rc;
-    const uint64_t one[2] = {0, n_bytes};
-    if (!chunk_off) { chunk_off = one; n_chunks = 1; }
-    if (chunk_off[0] != 0 || chunk_off[n_chunks] != n_bytes)
+    const uint64_t one[2] = {0, a.n_bytes};
+    if (!a.chunk_off) { a.chunk_off = one; a.n_chunks = 1; }
+    if (a.chunk_off[0] != 0 || a.chunk_off[a.n_chunks] != a.n_bytes)
         return fail(MBPE_ERR_ARG, "chunk_off must start at 0 and end at n_bytes");
-    for (uint64_t c = 0; c < n_chunks; ++c)
-        if (chunk_off[c + 1] < chunk_off[c]) return fail(MBPE_ERR_ARG, "chunk_off must be ascending");
-    if (doc_chunk_off[0] != 0 || doc_chunk_off[n_docs] != n_chunks)
+    for (uint64_t c = 0; c < a.n_chunks; ++c)
+        if (a.chunk_off[c + 1] < a.chunk_off[c]) return fail(MBPE_ERR_ARG, "chunk_off must be ascending");
+    if (k.doc_chunk_off[0] != 0 || k.doc_chunk_off[k.n_docs] != a.n_chunks)
         return fail(MBPE_ERR_ARG, "doc_chunk_off must start at 0 and end at n_chunks");
-    for (uint64_t i = 0; i < n_docs; ++i)
-        if (doc_chunk_off[i + 1] < doc_chunk_off[i]) return fail(MBPE_ERR_ARG, "doc_chunk_off must be ascending");
-    if (spec->out_bits == 16 && 256ull + e->n_merges > 65536ull)
-        return fail(MBPE_ERR_VOCAB, "out_bits 16 with more than 65,536 token ids");
-    if (ids_out && out_on_device &&
-        ((uint64_t)(uintptr_t)ids_out % (spec->out_bits / 8) || (uint64_t)(uintptr_t)len_out % 4))
-        return fail(MBPE_ERR_ARG, "ids_out or len_out is not aligned to its elements");
-    if (aux) {                                                   // (the document lengths: after the encode)
-        rc = pack_check_aux(*spec, aux, nullptr, n_docs, ids_out, out_on_device);
-        if (rc != MBPE_OK) return rc;
-    }
-    try {
-        return enc_batch_body(e, text, n_bytes, text_on_device, chunk_off, n_chunks, doc_chunk_off, n_docs, *spec,
-                              ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
-                              doc_tok_off_out);
-    } catch (const std::bad_alloc &) {
-        return fail(MBPE_ERR_OOM, "mbpe_encoder_encode_batch: host allocation failed");
-    }
+    for (uint64_t i = 0; i < k.n_docs; ++i)
+        if (k.doc_chunk_off[i + 1] < k.doc_chunk_off[i]) return fail(MBPE_ERR_ARG, "doc_chunk_off must be ascending");
+    rc = enc_batch_check(e, k);
+    if (rc != MBPE_OK) return rc;
+    return enc_guard("mbpe_encoder_encode_batch", [&] { return enc_batch_body(e, a, k); });
 }
 
 int mbpe_encoder_encode_batch_aux(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
@@ -1168,16 +1167,18 @@ int mbpe_encoder_encode_batch_aux(mbpe_encoder *e, const uint8_t *text, uint64_t
     if (n_rows_out) *n_rows_out = 0;
     if (n_tokens_out) *n_tokens_out = 0;
     if (!aux) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_batch_aux: NULL argument");
-    return enc_batch(e, text, n_bytes, text_on_device, chunk_off, n_chunks, doc_chunk_off, n_docs, spec, ids_out, cap_rows,
-                     out_on_device, len_out, n_rows_out, n_tokens_out, aux, doc_tok_off_out);
+    return enc_batch(e, {text, n_bytes, text_on_device, chunk_off, n_chunks},
+                     {doc_chunk_off, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
+                      doc_tok_off_out});
 }
 
 int mbpe_encoder_encode_batch(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
                               const uint64_t *chunk_off, uint64_t n_chunks, const uint64_t *doc_chunk_off,
                               uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows,
                               int out_on_device, uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out) {
-    return enc_batch(e, text, n_bytes, text_on_device, chunk_off, n_chunks, doc_chunk_off, n_docs, spec, ids_out, cap_rows,
-                     out_on_device, len_out, n_rows_out, n_tokens_out, nullptr, nullptr);
+    return enc_batch(e, {text, n_bytes, text_on_device, chunk_off, n_chunks},
+                     {doc_chunk_off, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out,
+                      nullptr, nullptr});
 }
 
 int mbpe_encoder_encode_endmask(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes, const uint8_t *endmask_dev,
@@ -1194,13 +1195,10 @@ int mbpe_encoder_encode_endmask(mbpe_encoder *e, const uint8_t *text_dev, uint64
     if ((uintptr_t)endmask_dev & 3) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_endmask: the mask must be 4-byte aligned");
     if (token_bits == 16 && 256ull + e->n_merges > 65536ull)
         return fail(MBPE_ERR_VOCAB, "token_bits 16 with more than 65,536 token ids");
-    if (n_docs == 0) doc_off = nullptr;
-    try {
-        return enc_endmask_body(e, text_dev, n_bytes, endmask_dev, singles, n_singles, doc_off, n_docs, tokens_out, cap,
-                                token_bits, out_on_device, doc_tok_off_out, n_out, n_passes_out);
-    } catch (const std::bad_alloc &) {
-        return fail(MBPE_ERR_OOM, "mbpe_encoder_encode_endmask: host allocation failed");
-    }
+    const EncCall a = {text_dev, n_bytes, 1, nullptr, 0, tokens_out, cap, token_bits, out_on_device, nullptr, n_out,
+                       n_passes_out, true, endmask_dev, singles, n_singles, n_docs ? doc_off : nullptr, n_docs,
+                       doc_tok_off_out};
+    return enc_guard("mbpe_encoder_encode_endmask", [&] { return enc_endmask_body(e, a); });
 }
 
 int mbpe_encoder_encode_batch_endmask(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
@@ -1208,49 +1206,44 @@ int mbpe_encoder_encode_batch_endmask(mbpe_encoder *e, const uint8_t *text_dev, 
                                       const uint64_t *doc_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
                                       uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
                                       uint64_t *n_tokens_out, const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out) {
-    const char *who = "mbpe_encoder_encode_batch_endmask";
+    const std::string who = "mbpe_encoder_encode_batch_endmask";
     if (n_rows_out) *n_rows_out = 0;
     if (n_tokens_out) *n_tokens_out = 0;
-    if (!spec || !doc_off || !n_rows_out) return fail(MBPE_ERR_ARG, std::string(who) + ": NULL argument");
-    int rc = pack_check_spec(spec, spec->out_bits == 16 ? 16 : 32);
+    if (!spec || !doc_off || !n_rows_out) return fail(MBPE_ERR_ARG, who + ": NULL argument");
+    const EncPack k = {nullptr, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
+                       doc_tok_off_out};
+    int rc = pack_check_spec(spec, k.token_bits());
     if (rc != MBPE_OK) return rc;
-    const uint32_t token_bits = spec->out_bits == 16 ? 16 : 32;
-    rc = enc_endmask_check(who, n_bytes, singles, n_singles, doc_off, n_docs, token_bits);
+    rc = enc_endmask_check(who.c_str(), n_bytes, singles, n_singles, doc_off, n_docs, k.token_bits());
     if (rc != MBPE_OK) return rc;
     if (doc_off[0] != 0 || doc_off[n_docs] != n_bytes)
-        return fail(MBPE_ERR_ARG, std::string(who) + ": doc_off must start at 0 and end at n_bytes");
-    if (!e || ((!text_dev || !endmask_dev) && n_bytes)) return fail(MBPE_ERR_ARG, std::string(who) + ": NULL argument");
-    if ((uintptr_t)endmask_dev & 3) return fail(MBPE_ERR_ARG, std::string(who) + ": the mask must be 4-byte aligned");
-    if (spec->out_bits == 16 && 256ull + e->n_merges > 65536ull)
-        return fail(MBPE_ERR_VOCAB, "out_bits 16 with more than 65,536 token ids");
-    if (ids_out && out_on_device &&
-        ((uint64_t)(uintptr_t)ids_out % (spec->out_bits / 8) || (uint64_t)(uintptr_t)len_out % 4))
-        return fail(MBPE_ERR_ARG, "ids_out or len_out is not aligned to its elements");
-    if (aux) {
-        rc = pack_check_aux(*spec, aux, nullptr, n_docs, ids_out, out_on_device);
+        return fail(MBPE_ERR_ARG, who + ": doc_off must start at 0 and end at n_bytes");
+    if (!e || ((!text_dev || !endmask_dev) && n_bytes)) return fail(MBPE_ERR_ARG, who + ": NULL argument");
+    if ((uintptr_t)endmask_dev & 3) return fail(MBPE_ERR_ARG, who + ": the mask must be 4-byte aligned");
+    rc = enc_batch_check(e, k);
+    if (rc != MBPE_OK) return rc;
+    return enc_guard(who, [&]() -> int {
+        EncCall a = {text_dev, n_bytes, 1};                      // (enc_batch_flat: where the tokens go)
+        a.mask_on_device = true;
+        a.mask_dev = endmask_dev;
+        a.singles = singles;
+        a.n_singles = n_singles;
+        a.doc_off = doc_off;
+        a.n_docs = n_docs;
+        uint64_t n_tokens = 0;
+        int rc = enc_batch_flat(e, &a, k, &n_tokens);
         if (rc != MBPE_OK) return rc;
-    }
-    try {
-        ECHK(hipSetDevice(e->device));
-        rc = grow(&e->d_flat, &e->cap_flat, std::max<uint64_t>(n_bytes, 1) * (token_bits / 8), true, &e->n_allocs);
-        if (rc != MBPE_OK) return rc;
-        e->pack_ms = 0.f;
         // the offsets stay on the device; the host sees them where it asks for them, or where a document could be too
         // long for pos (only a text of 2^32 bytes or more)
         const bool to_host = doc_tok_off_out || (aux && n_bytes + 2 >= (1ull << 32));
         e->doc_tok.assign(n_docs + 1, 0);
-        uint64_t n_tokens = 0;
-        rc = enc_endmask_body(e, text_dev, n_bytes, endmask_dev, singles, n_singles, doc_off, n_docs, e->d_flat, n_bytes,
-                              token_bits, 1, to_host ? e->doc_tok.data() : nullptr, &n_tokens, nullptr);
+        a.doc_tok_off_out = to_host ? e->doc_tok.data() : nullptr;
+        rc = enc_endmask_body(e, a);
         if (rc != MBPE_OK) return rc;
         if (aux && to_host) rc = pack_check_aux(*spec, aux, e->doc_tok.data(), n_docs, nullptr, 0);
         if (rc != MBPE_OK) return rc;
-        rc = enc_pack_tail(e, n_tokens, n_docs, token_bits, *spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out,
-                           n_tokens_out, aux, doc_tok_off_out, true);
-        return rc;
-    } catch (const std::bad_alloc &) {
-        return fail(MBPE_ERR_OOM, std::string(who) + ": host allocation failed");
-    }
+        return enc_pack_tail(e, k, n_tokens, true);
+    });
 }
 
 int mbpe_encoder_pack_ms(const mbpe_encoder *e, float *ms_out) {
@@ -1276,7 +1269,7 @@ int mbpe_encoder_pass_tokens(const mbpe_encoder *e, uint64_t *tokens_out, uint32
 
 int mbpe_encoder_alloc_count(const mbpe_encoder *e, uint64_t *n_out) {
     if (!e || !n_out) return fail(MBPE_ERR_ARG, "mbpe_encoder_alloc_count: NULL argument");
-    *n_out = e->n_allocs;
+    *n_out = e->mem.n_allocs;
     return MBPE_OK;
 }
 

@@ -385,11 +385,6 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_aux(PackAuxJob a) {
 
 #define PCHK(expr) MBPE_HIP_CHECK(expr, true)
 
-int fail(int code, const std::string &msg) {
-    mbpe_host::set_last_error(msg);
-    return code;
-}
-
 uint32_t pack_grid(const void *out, uint64_t n_out, uint32_t out_bits) {
     const uint64_t A = (uint64_t)(uintptr_t)out, E = A + n_out * (out_bits / 8);
     const uint64_t n_pieces = (E - (A & ~15ull) + 15) >> 4;
@@ -424,44 +419,18 @@ void launch_pack_aux(hipStream_t stream, bool packed, const PackAuxJob &a) {
 // device time of the calling thread's latest one-shot pack or unpack kernel (mbpe_pack_kernel_ms)
 thread_local float g_pack_ms = 0.f;
 
-int find_device(int device_id) {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || device_id < 0 || device_id >= n_dev)
-        return fail(MBPE_ERR_NO_DEVICE, "no usable HIP device (the MI355X path has no CPU fallback)");
-    return MBPE_OK;
-}
-
 // the device side of a one-shot call: a stream, two events and the buffers it had to allocate, all released at its end
-struct OneShot {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::vector<void *> bufs;
-    ~OneShot() {
-        for (void *p : bufs) (void)hipFree(p);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-    int open(int device_id) {
-        PCHK(hipSetDevice(device_id));
-        PCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        PCHK(hipEventCreate(&ev0));
-        PCHK(hipEventCreate(&ev1));
-        return MBPE_OK;
-    }
+struct OneShot : DevQueue {
+    OneShot() : DevQueue(true) {}
+    std::vector<DevBuf<uint8_t>> bufs;
     // device memory for n bytes (at least one), filled from `host` when that is given
     int alloc(void **out, uint64_t n, const void *host) {
         *out = nullptr;
-        PCHK(hipMalloc(out, n ? n : 1));
-        bufs.push_back(*out);
+        bufs.emplace_back();
+        const int rc = bufs.back().reserve(n ? n : 1, mem);
+        if (rc != MBPE_OK) return rc;
+        *out = bufs.back();
         if (host && n) PCHK(hipMemcpyAsync(*out, host, n, hipMemcpyHostToDevice, stream));
-        return MBPE_OK;
-    }
-    // what was enqueued between the events has run; its device time
-    int finish(float *ms) {
-        PCHK(hipStreamSynchronize(stream));
-        PCHK(hipGetLastError());
-        PCHK(hipEventElapsedTime(ms, ev0, ev1));
         return MBPE_OK;
     }
 };
@@ -497,7 +466,6 @@ int pack_run(int device_id, const void *tokens, uint64_t n_tokens, uint32_t toke
     PCHK(hipEventRecord(dev.ev0, dev.stream));
     if (aux) pack_launch_aux(dev.stream, src, spec, dst, d_aux);
     else pack_launch(dev.stream, src, spec, dst);
-    PCHK(hipEventRecord(dev.ev1, dev.stream));
     rc = dev.finish(&g_pack_ms);
     if (rc != MBPE_OK) return rc;
     if (!out_on_device) {
@@ -561,7 +529,6 @@ int unpack_run(int device_id, const void *ids, uint64_t n_rows, uint32_t seq_len
     else if (id_bits == 16) launch_unpack<16, 32>(dev.stream, j);
     else if (id_bits == 32) launch_unpack<32, 32>(dev.stream, j);
     else launch_unpack<64, 32>(dev.stream, j);
-    PCHK(hipEventRecord(dev.ev1, dev.stream));
     rc = dev.finish(&g_pack_ms);
     if (rc != MBPE_OK) return rc;
     if (!out_on_device) {
@@ -677,11 +644,14 @@ int device_alloc(int device_id, uint64_t n_bytes, void **out) {
     const int rc = find_device(device_id);
     if (rc != MBPE_OK) return rc;
     PCHK(hipSetDevice(device_id));
-    PCHK(hipMalloc(out, n_bytes ? n_bytes : 1));
-    return MBPE_OK;
+    DevAlloc mem = {true};
+    DevBuf<void> buf;
+    const int rc_buf = buf.reserve(n_bytes ? n_bytes : 1, mem);
+    *out = buf.release();                                        // the caller's from here on: device_free
+    return rc_buf;
 }
 
-void device_free(void *p) { (void)hipFree(p); }
+void device_free(void *p) { dev_free(p); }
 
 }  // namespace mbpe_host
 

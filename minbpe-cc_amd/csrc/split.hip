@@ -242,11 +242,6 @@ __global__ __launch_bounds__(kSplitThreads) void k_mask_popcount(const uint32_t 
 
 uint32_t grid_for(uint64_t n_items) { return (uint32_t)((n_items + kSplitThreads - 1) / kSplitThreads); }
 
-int fail(int code, const std::string &msg) {
-    mbpe_host::set_last_error(msg);
-    return code;
-}
-
 #define SCHK(expr) MBPE_HIP_CHECK(expr, false)
 
 }  // namespace
@@ -263,31 +258,26 @@ void launch_mask_popcount(hipStream_t stream, const uint8_t *mask, uint64_t n_by
 
 using namespace mbpe;
 
-struct mbpe_splitter {
-    int device = 0;
+struct mbpe_splitter : DevQueue {
+    mbpe_splitter() : DevQueue(false) {}
     int pattern = kSplitGpt2;
     mbpe_host::Splitter host;                 // the same pattern through PCRE2, for the host spans
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint64_t max_span = MBPE_SPLIT_MAX_SPAN;
     bool unicode = false;                     // the option; the table is uploaded by the first call that needs it
-    uint32_t *d_tab = nullptr;
+    DevBuf<uint32_t> d_tab;
     SplitFold fold = {};
     // buffers, grown on demand and kept
-    uint8_t *d_text = nullptr;                // a host text's copy
-    unsigned long long *d_sync = nullptr, *d_hi = nullptr, *d_hostmark = nullptr;
-    uint8_t *d_mask = nullptr;
-    unsigned long long *d_ctl = nullptr;
-    unsigned long long *d_list = nullptr;     // cuts, ranges; host spans, then their chunk ends
-    unsigned long long *d_cut = nullptr, *d_raw = nullptr;    // split_docs: the cut bitmap, the bytes inside ranges
-    unsigned long long *d_find = nullptr;     // ... the occurrences of the names; the positions of the parts
-    uint32_t *d_names = nullptr;              // ... the names as k_split_find takes them
-    uint8_t *d_first = nullptr;               // ... the first byte of every part of a device text
-    uint64_t cap_text = 0, cap_sync = 0, cap_hi = 0, cap_hostmark = 0, cap_mask = 0, cap_list = 0;
-    uint64_t cap_cut = 0, cap_raw = 0, cap_find = 0, cap_names = 0, cap_first = 0;
+    DevBuf<uint8_t> d_text;                   // a host text's copy
+    DevBuf<unsigned long long> d_sync, d_hi, d_hostmark;
+    DevBuf<uint8_t> d_mask;
+    DevBuf<unsigned long long> d_ctl;
+    DevBuf<unsigned long long> d_list;        // cuts, ranges; host spans, then their chunk ends
+    DevBuf<unsigned long long> d_cut, d_raw;  // split_docs: the cut bitmap, the bytes inside ranges
+    DevBuf<unsigned long long> d_find;        // ... the occurrences of the names; the positions of the parts
+    DevBuf<uint32_t> d_names;                 // ... the names as k_split_find takes them
+    DevBuf<uint8_t> d_first;                  // ... the first byte of every part of a device text
     std::vector<SplitRange> ranges;           // the latest split_docs call's
     float find_ms = 0.f;
-    uint64_t n_allocs = 0;
     std::vector<uint8_t> h_mask;              // the mask on the host, when offsets are asked for
     // the latest call
     float last_ms = 0.f;
@@ -328,8 +318,8 @@ int split_find(mbpe_splitter *s, const uint8_t *d_text, uint64_t n, const DocArg
     if (!any) return MBPE_OK;                  // no name, or empty ones only
     memcpy(blob.data() + 8, d.name_off, (d.n_names + 1) * 4);
     if (name_bytes) memcpy(blob.data() + 8 + d.n_names + 1, d.names, name_bytes);
-    int rc = grow(&s->d_names, &s->cap_names, (8 + kSplitMaxNames + 1) * 4 + kSplitMaxNameBytes, false, &s->n_allocs);
-    if (rc == MBPE_OK && !s->d_find) rc = grow(&s->d_find, &s->cap_find, kFindListMin * 8, false, &s->n_allocs);
+    int rc = s->d_names.reserve((8 + kSplitMaxNames + 1) * 4 + kSplitMaxNameBytes, s->mem);
+    if (rc == MBPE_OK && !s->d_find) rc = s->d_find.reserve(kFindListMin * 8, s->mem);
     if (rc != MBPE_OK) return rc;
     SCHK(hipMemcpyAsync(s->d_names, blob.data(), blob.size() * 4, hipMemcpyHostToDevice, s->stream));
     const uint64_t n_vec = (n + kSplitVec - 1) / kSplitVec;
@@ -338,7 +328,7 @@ int split_find(mbpe_splitter *s, const uint8_t *d_text, uint64_t n, const DocArg
         SCHK(hipEventRecord(s->ev0, s->stream));
         SCHK(hipMemsetAsync(s->d_ctl + kCtlFound, 0, 8, s->stream));
         hipLaunchKernelGGL(k_split_find, dim3(grid_for(n_vec)), dim3(kSplitThreads), 0, s->stream, d_text, n, n_vec,
-                           s->d_names, d.n_names, name_bytes, s->d_find, s->cap_find / 8, s->d_ctl + kCtlFound);
+                           s->d_names, d.n_names, name_bytes, s->d_find, s->d_find.bytes() / 8, s->d_ctl + kCtlFound);
         SCHK(hipGetLastError());
         SCHK(hipEventRecord(s->ev1, s->stream));
         SCHK(hipMemcpyAsync(&found, s->d_ctl + kCtlFound, 8, hipMemcpyDeviceToHost, s->stream));
@@ -347,9 +337,9 @@ int split_find(mbpe_splitter *s, const uint8_t *d_text, uint64_t n, const DocArg
         SCHK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
         s->find_ms += ms;
         s->last_ms += ms;
-        if (found <= s->cap_find / 8) break;
+        if (found <= s->d_find.bytes() / 8) break;
         if (attempt == 1) return fail(MBPE_ERR_HIP, "mbpe_splitter_split_docs: the list of occurrences changed size");
-        rc = grow(&s->d_find, &s->cap_find, found * 8, false, &s->n_allocs);
+        rc = s->d_find.reserve(found * 8, s->mem);
         if (rc != MBPE_OK) return rc;
     }
     hits->resize(found);
@@ -368,20 +358,19 @@ int split_run_passes(mbpe_splitter *s, const uint8_t *text, uint64_t n, int text
     const uint64_t mask_bytes = (n_vec * 2 + 16 + 7) & ~7ull;
     int rc;
     if (!text_on_device) {
-        if ((rc = grow(&s->d_text, &s->cap_text, n_vec * 16, false, &s->n_allocs)) != MBPE_OK) return rc;
+        if ((rc = s->d_text.reserve(n_vec * 16, s->mem)) != MBPE_OK) return rc;
         SCHK(hipMemcpyAsync(s->d_text, text, n, hipMemcpyHostToDevice, s->stream));
     }
     const uint8_t *d_text = text_on_device ? text : s->d_text;
-    if ((rc = grow(&s->d_sync, &s->cap_sync, n_words * 8, false, &s->n_allocs)) != MBPE_OK) return rc;
-    if ((rc = grow(&s->d_hi, &s->cap_hi, n_words * 8, false, &s->n_allocs)) != MBPE_OK) return rc;
-    if ((rc = grow(&s->d_hostmark, &s->cap_hostmark, n_words * 8, false, &s->n_allocs)) != MBPE_OK) return rc;
-    if ((rc = grow(&s->d_mask, &s->cap_mask, mask_bytes, false, &s->n_allocs)) != MBPE_OK) return rc;
+    if ((rc = s->d_sync.reserve(n_words * 8, s->mem)) != MBPE_OK) return rc;
+    if ((rc = s->d_hi.reserve(n_words * 8, s->mem)) != MBPE_OK) return rc;
+    if ((rc = s->d_hostmark.reserve(n_words * 8, s->mem)) != MBPE_OK) return rc;
+    if ((rc = s->d_mask.reserve(mask_bytes, s->mem)) != MBPE_OK) return rc;
     if (s->unicode && !s->d_tab) {
         std::string err;
         const mbpe_host::SplitUnicodeTable *tb = mbpe_host::split_unicode_table(&err);
         if (!tb) return fail(MBPE_ERR_REGEX, err);
-        SCHK(hipMalloc(&s->d_tab, kSplitTableWords * 4));
-        ++s->n_allocs;
+        if ((rc = s->d_tab.reserve(kSplitTableWords * 4, s->mem)) != MBPE_OK) return rc;
         SCHK(hipMemcpy(s->d_tab, tb->cls.data(), kSplitTableWords * 4, hipMemcpyHostToDevice));
         s->fold.n = tb->n_fold;
         for (uint32_t k = 0; k < tb->n_fold; ++k) { s->fold.cp[k] = tb->fold_cp[k]; s->fold.to[k] = tb->fold_to[k]; }
@@ -403,8 +392,8 @@ int split_run_passes(mbpe_splitter *s, const uint8_t *text, uint64_t n, int text
         } else if (!parts.empty()) {
             part_pos.resize(parts.size());
             for (size_t k = 0; k < parts.size(); ++k) part_pos[k] = parts[k].start;
-            if ((rc = grow(&s->d_find, &s->cap_find, parts.size() * 8, false, &s->n_allocs)) != MBPE_OK) return rc;
-            if ((rc = grow(&s->d_first, &s->cap_first, parts.size(), false, &s->n_allocs)) != MBPE_OK) return rc;
+            if ((rc = s->d_find.reserve(parts.size() * 8, s->mem)) != MBPE_OK) return rc;
+            if ((rc = s->d_first.reserve(parts.size(), s->mem)) != MBPE_OK) return rc;
             SCHK(hipMemcpyAsync(s->d_find, part_pos.data(), parts.size() * 8, hipMemcpyHostToDevice, s->stream));
             hipLaunchKernelGGL(k_split_gather, dim3(grid_for(parts.size())), dim3(kSplitThreads), 0, s->stream, d_text, n,
                                s->d_find, (uint64_t)parts.size(), s->d_first);
@@ -418,9 +407,9 @@ int split_run_passes(mbpe_splitter *s, const uint8_t *text, uint64_t n, int text
     std::vector<uint64_t> rng(2 * ranges->size());
     if (have_cuts || have_raw) {
         for (size_t k = 0; k < ranges->size(); ++k) { rng[2 * k] = (*ranges)[k].start; rng[2 * k + 1] = (*ranges)[k].len; }
-        if ((rc = grow(&s->d_list, &s->cap_list, (cuts.size() + rng.size()) * 8, false, &s->n_allocs)) != MBPE_OK) return rc;
-        if (have_cuts && (rc = grow(&s->d_cut, &s->cap_cut, n_words * 8, false, &s->n_allocs)) != MBPE_OK) return rc;
-        if (have_raw && (rc = grow(&s->d_raw, &s->cap_raw, n_words * 8, false, &s->n_allocs)) != MBPE_OK) return rc;
+        if ((rc = s->d_list.reserve((cuts.size() + rng.size()) * 8, s->mem)) != MBPE_OK) return rc;
+        if (have_cuts && (rc = s->d_cut.reserve(n_words * 8, s->mem)) != MBPE_OK) return rc;
+        if (have_raw && (rc = s->d_raw.reserve(n_words * 8, s->mem)) != MBPE_OK) return rc;
         if (have_cuts) SCHK(hipMemcpyAsync(s->d_list, cuts.data(), cuts.size() * 8, hipMemcpyHostToDevice, s->stream));
         if (have_raw)
             SCHK(hipMemcpyAsync(s->d_list + cuts.size(), rng.data(), rng.size() * 8, hipMemcpyHostToDevice, s->stream));
@@ -432,7 +421,7 @@ int split_run_passes(mbpe_splitter *s, const uint8_t *text, uint64_t n, int text
     if (have_cuts) {
         SCHK(hipMemsetAsync(s->d_cut, 0, n_words * 8, s->stream));
         hipLaunchKernelGGL(k_split_patch, dim3(grid_for(cuts.size())), dim3(kSplitThreads), 0, s->stream, s->d_list,
-                           (uint64_t)cuts.size(), n, reinterpret_cast<uint32_t *>(s->d_cut));
+                           (uint64_t)cuts.size(), n, reinterpret_cast<uint32_t *>(s->d_cut.get()));
     }
     if (have_raw) {
         SCHK(hipMemsetAsync(s->d_raw, 0, n_words * 8, s->stream));
@@ -443,17 +432,17 @@ int split_run_passes(mbpe_splitter *s, const uint8_t *text, uint64_t n, int text
     if (s->unicode) {
         hipLaunchKernelGGL(k_split_sync_u, dim3(grid_for(n_words * 4)), dim3(kSplitThreads), 0, s->stream, d_text, n,
                            n_words * 4, reinterpret_cast<const uint16_t *>(d_cut), s->pattern, s->d_tab,
-                           reinterpret_cast<uint16_t *>(s->d_sync), reinterpret_cast<uint16_t *>(s->d_hi));
+                           reinterpret_cast<uint16_t *>(s->d_sync.get()), reinterpret_cast<uint16_t *>(s->d_hi.get()));
         hipLaunchKernelGGL(k_split_walk_u, dim3(grid_for(n_words)), dim3(kSplitThreads), 0, s->stream, d_text, n,
                            s->d_sync, s->d_hi, d_cut, d_raw, n_words, s->max_span, s->pattern, s->d_tab, s->fold,
-                           reinterpret_cast<uint32_t *>(s->d_mask), s->d_hostmark, s->d_ctl);
+                           reinterpret_cast<uint32_t *>(s->d_mask.get()), s->d_hostmark, s->d_ctl);
     } else {
         hipLaunchKernelGGL(k_split_sync, dim3(grid_for(n_words * 4)), dim3(kSplitThreads), 0, s->stream, d_text, n,
-                           n_words * 4, reinterpret_cast<const uint16_t *>(d_cut), reinterpret_cast<uint16_t *>(s->d_sync),
-                           reinterpret_cast<uint16_t *>(s->d_hi));
+                           n_words * 4, reinterpret_cast<const uint16_t *>(d_cut), reinterpret_cast<uint16_t *>(s->d_sync.get()),
+                           reinterpret_cast<uint16_t *>(s->d_hi.get()));
         hipLaunchKernelGGL(k_split_walk, dim3(grid_for(n_words)), dim3(kSplitThreads), 0, s->stream, d_text, n, s->d_sync,
                            s->d_hi, d_cut, d_raw, n_words, s->max_span, s->pattern,
-                           reinterpret_cast<uint32_t *>(s->d_mask), s->d_hostmark, s->d_ctl);
+                           reinterpret_cast<uint32_t *>(s->d_mask.get()), s->d_hostmark, s->d_ctl);
     }
     SCHK(hipGetLastError());
     SCHK(hipEventRecord(s->ev1, s->stream));
@@ -466,7 +455,7 @@ int split_run_passes(mbpe_splitter *s, const uint8_t *text, uint64_t n, int text
     uint64_t n_patch = 0;
     std::vector<uint64_t> ends;
     if (n_host) {
-        if ((rc = grow(&s->d_list, &s->cap_list, n_host * 16, false, &s->n_allocs)) != MBPE_OK) return rc;
+        if ((rc = s->d_list.reserve(n_host * 16, s->mem)) != MBPE_OK) return rc;
         SCHK(hipEventRecord(s->ev0, s->stream));
         hipLaunchKernelGGL(k_split_compact, dim3(grid_for(n_words)), dim3(kSplitThreads), 0, s->stream, s->d_sync,
                            s->d_hostmark, n, n_words, s->d_list, n_host, s->d_ctl);
@@ -518,7 +507,7 @@ int split_run_passes(mbpe_splitter *s, const uint8_t *text, uint64_t n, int text
     for (const SplitRange &r : *ranges) ends.push_back(r.start + r.len - 1);      // a range is one chunk
     n_patch = ends.size();
     if (n_patch) {
-        if ((rc = grow(&s->d_list, &s->cap_list, n_patch * 8, false, &s->n_allocs)) != MBPE_OK) return rc;
+        if ((rc = s->d_list.reserve(n_patch * 8, s->mem)) != MBPE_OK) return rc;
         SCHK(hipMemcpyAsync(s->d_list, ends.data(), n_patch * 8, hipMemcpyHostToDevice, s->stream));
         SCHK(hipStreamSynchronize(s->stream));           // (ends is about to go)
     }
@@ -526,7 +515,7 @@ int split_run_passes(mbpe_splitter *s, const uint8_t *text, uint64_t n, int text
     SCHK(hipEventRecord(s->ev0, s->stream));
     if (n_patch)
         hipLaunchKernelGGL(k_split_patch, dim3(grid_for(n_patch)), dim3(kSplitThreads), 0, s->stream, s->d_list, n_patch,
-                           n, reinterpret_cast<uint32_t *>(s->d_mask));
+                           n, reinterpret_cast<uint32_t *>(s->d_mask.get()));
     launch_mask_popcount(s->stream, s->d_mask, n, s->d_ctl + kCtlChunks);
     SCHK(hipGetLastError());
     SCHK(hipEventRecord(s->ev1, s->stream));
@@ -549,23 +538,16 @@ int mbpe_splitter_create(int device_id, const char *pattern, mbpe_splitter **out
     else if (!strcmp(pattern, mbpe_host::split_pattern_for("gpt4"))) which = kSplitGpt4;
     if (which < 0)
         return fail(MBPE_ERR_ARG, "the device split knows the built-in gpt2 and gpt4 patterns only (use mbpe_presplit)");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || device_id < 0 || device_id >= n_dev)
-        return fail(MBPE_ERR_NO_DEVICE, "no usable HIP device (the MI355X path has no CPU fallback)");
+    if (find_device(device_id) != MBPE_OK) return MBPE_ERR_NO_DEVICE;
     mbpe_splitter *s = new mbpe_splitter;
-    s->device = device_id;
+    s->device = device_id;                    // (destroy selects it, also where the pattern fails before open)
     s->pattern = which;
     auto build = [&]() -> int {
         std::string err;
-        const int rc = s->host.compile(pattern, &err);
+        int rc = s->host.compile(pattern, &err);
         if (rc != MBPE_OK) return fail(rc, err);
-        SCHK(hipSetDevice(device_id));
-        SCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-        SCHK(hipEventCreate(&s->ev0));
-        SCHK(hipEventCreate(&s->ev1));
-        SCHK(hipMalloc(&s->d_ctl, kCtlWords * 8));
-        s->n_allocs = 1;
-        return MBPE_OK;
+        if ((rc = s->open(device_id)) != MBPE_OK) return rc;
+        return s->d_ctl.reserve(kCtlWords * 8, s->mem);
     };
     const int rc = build();
     if (rc != MBPE_OK) {
@@ -581,14 +563,7 @@ int mbpe_splitter_create(int device_id, const char *pattern, mbpe_splitter **out
 void mbpe_splitter_destroy(mbpe_splitter *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
-    (void)hipFree(s->d_text); (void)hipFree(s->d_sync); (void)hipFree(s->d_hi); (void)hipFree(s->d_hostmark);
-    (void)hipFree(s->d_mask); (void)hipFree(s->d_ctl); (void)hipFree(s->d_list);
-    (void)hipFree(s->d_cut); (void)hipFree(s->d_raw); (void)hipFree(s->d_find); (void)hipFree(s->d_names);
-    (void)hipFree(s->d_first); (void)hipFree(s->d_tab);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
+    delete s;                                 // the buffers, then the events, then the stream
 }
 
 int mbpe_splitter_set_option(mbpe_splitter *s, const char *name, int64_t value) {
@@ -615,7 +590,7 @@ static int split_call(mbpe_splitter *s, const uint8_t *text, uint64_t n_bytes, i
         if (rc != MBPE_OK) return rc;
         s->ranges.swap(ranges);
     } else {
-        const int rc = grow(&s->d_mask, &s->cap_mask, 16, false, &s->n_allocs);
+        const int rc = s->d_mask.reserve(16, s->mem);
         if (rc != MBPE_OK) return rc;
         SCHK(hipMemsetAsync(s->d_mask, 0, 16, s->stream));
         SCHK(hipStreamSynchronize(s->stream));
@@ -742,7 +717,7 @@ int mbpe_splitter_kernel_ms(const mbpe_splitter *s, float *ms_out) {
 
 int mbpe_splitter_alloc_count(const mbpe_splitter *s, uint64_t *n_out) {
     if (!s || !n_out) return fail(MBPE_ERR_ARG, "mbpe_splitter_alloc_count: NULL argument");
-    *n_out = s->n_allocs;
+    *n_out = s->mem.n_allocs;
     return MBPE_OK;
 }
 
