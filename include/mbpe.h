@@ -282,11 +282,28 @@ MBPE_API int mbpe_merges_check(const uint32_t *merges, uint32_t n_merges);
  * begin succeeds, the training is complete, the result is the prior table.
  * Decided before the device is touched: MBPE_ERR_ARG for a table mbpe_merges_check refuses, for n_prior > vocab_size -
  * 256 and for prior_merges NULL; MBPE_ERR_STATE for a context with several ranks (mbpe_comm_init*; "force_exchange");
- * MBPE_ERR_VOCAB when vocab_size (or 256 + n_prior) lies beyond the 16-bit slot format of this corpus -- the 32-bit
- * continuation does not start from existing merges -- and when "wide_from" is set.  MBPE_ERR_OOM, with the encoder's
- * message, for a corpus above the one-piece limit of mbpe_encoder_encode_endmask; the peak of the begin is the replay,
- * about 18.4 bytes of device memory per corpus byte.  MBPE_ERR_OVERFLOW for a pair that occurs 2^31
- * times or more, as from mbpe_train_begin. */
+ * MBPE_ERR_VOCAB, with the option "resume_wide" 0 (the default), when vocab_size (or 256 + n_prior) lies beyond the
+ * 16-bit slot format of this corpus -- the 32-bit continuation does not start from existing merges -- and when
+ * "wide_from" is set.  MBPE_ERR_OOM, with the encoder's message, for a corpus above the one-piece limit of
+ * mbpe_encoder_encode_endmask; the peak of the begin is the replay, about 18.4 bytes of device memory per corpus byte
+ * (DESIGN.md 4h).  MBPE_ERR_OVERFLOW for a pair that occurs 2^31 times or more, as from mbpe_train_begin.
+ *
+ * With "resume_wide" 1 the training may continue on 32-bit tokens (one rank).  vmax: the slot format's limit for this
+ * corpus and "chunk_barrier", as mbpe_train_begin computes it; h = vmax - 256, or min("wide_from", vmax - 256) when
+ * "wide_from" >= 0: the merge at which the slot stream hands over; T = vocab_size - 256.
+ *   slot case, T <= h            everything above, unchanged
+ *   mixed case, n_prior < h < T  the begin above on the slot stream up to merge h, where the handover of
+ *                                mbpe_train_begin's trainings takes over; chunk ends are kept as mbpe_train_begin
+ *                                would keep them for vocab_size
+ *   direct case, n_prior >= h    no slot stream: the replay's tokens are the 32-bit stream, the 64-bit-key pair table
+ *                                is counted from them (at most 2^30 pairs: MBPE_ERR_OVERFLOW beyond), and the 32-bit
+ *                                loop runs from merge n_prior.  Prior ids may need more than 16 bits.  The calls of
+ *                                point 3 behave as after a handover; a table that holds no pair at all ends the loop
+ *                                (mbpe_train_steps makes fewer steps), in either tie-break
+ * Decided before the device is touched, after the argument checks, in this order: MBPE_ERR_STATE for several ranks;
+ * MBPE_ERR_VOCAB for vocab_size > MBPE_MAX_VOCAB_WIDE; MBPE_ERR_VOCAB for the `first` tie-break without "first_wide" 1
+ * in the mixed or the direct case.  The zero-count divergence above applies unchanged.  A one-chunk corpus replays one
+ * pass per prior merge: tens of thousands of passes for a model near 65,000 merges. */
 MBPE_API int mbpe_train_begin_from(mbpe_ctx *ctx, uint32_t vocab_size, const uint32_t *prior_merges, uint32_t n_prior);
 
 /* mbpe_train with prior merges: load + mbpe_train_begin_from + all steps + result.  merges_out must hold
@@ -385,6 +402,10 @@ MBPE_API int mbpe_compact(mbpe_ctx *ctx);
  *                   first vocab_size limit - 256 merges on the slot stream, the rest on 32-bit tokens with the same
  *                   tie-break (earliest first occurrence among the pairs of maximal count), ending when no pair is
  *                   left; read by mbpe_train_begin.  mbpe_train takes what the context says; Tokenizer::train sets 1
+ *   "resume_wide"   continuing from existing merges beyond the 16-bit slot format, one rank: 0 (default) =
+ *                   MBPE_ERR_VOCAB, 1 = on 32-bit tokens (the mixed and direct cases of mbpe_train_begin_from); any
+ *                   other value is MBPE_ERR_ARG.  Read by mbpe_train_begin_from; mbpe_train_from takes what the
+ *                   context says; Tokenizer::train sets 1
  */
 MBPE_API int mbpe_set_option(mbpe_ctx *ctx, const char *name, int64_t value);
 

@@ -46,8 +46,9 @@ MBPE_API int mbpe_tok_train_split_device(mbpe_tokenizer *t, const uint8_t *text,
  * route of mbpe_tok_train_split_device (and honours mbpe_tok_set_split_unicode).  Verbose prints the per-merge line
  * of the new merges only.  A tokenizer without merges behaves like mbpe_tok_train.  Errors keep the code of the call
  * that failed: MBPE_ERR_ARG for a vocab_size below the tokens the model has or a table mbpe_merges_check refuses (the
- * tokenizer is unchanged then), MBPE_ERR_VOCAB beyond the 16-bit slot format, MBPE_ERR_OOM above the encoder's
- * one-piece limit. */
+ * tokenizer is unchanged then), MBPE_ERR_VOCAB beyond MBPE_MAX_VOCAB_WIDE (beyond the 16-bit slot format the training
+ * continues on 32-bit tokens: the context option "resume_wide" is set), MBPE_ERR_OOM above the encoder's one-piece
+ * limit. */
 MBPE_API int mbpe_tok_train_continue(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, uint32_t vocab_size,
                                      int conflict_resolution, int verbose, int device_id, int device_split);
 

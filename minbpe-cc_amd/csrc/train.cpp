@@ -241,6 +241,10 @@ struct mbpe_ctx {
     uint32_t n_target_total = 0;     // vocab_total - 256
     int64_t opt_wide_from = -1;      // tests: hand over after this many merges whatever the vocabulary (-1: at the format's limit)
     int64_t opt_first_wide = 0;      // 1: a `first` training may continue on 32-bit tokens too (0: MBPE_ERR_VOCAB, as before)
+    int64_t opt_resume_wide = 0;     // 1: mbpe_train_begin_from may continue on 32-bit tokens (0: MBPE_ERR_VOCAB, as before)
+    bool wide_direct = false;        // the training began on 32-bit tokens (wide_begin_from): no slot stream, no best[]
+    std::vector<uint32_t> h_prior_raw;   // ... and its prior merges, (a, b) as given: their ids may need more than 16 bits
+    WideTally *wtally = nullptr;         // ... and the census of its pair count
     bool wfirst = false;             // the 32-bit loop takes the `first` tie-break (fixed at the conversion)
     uint32_t *wtok[2] = {nullptr, nullptr};
     int wcur = 0;
@@ -363,8 +367,10 @@ void free_training(mbpe_ctx *c) {
     tfree(c, c->tally);
     tfree(c, c->wtok[0]); tfree(c, c->wtok[1]); tfree(c, c->wval); tfree(c, c->wscratch);
     tfree(c, c->wtab.keys); tfree(c, c->wtab.cnts); tfree(c, c->wctl); tfree(c, c->wbest); tfree(c, c->warg);
-    tfree(c, c->wfs);
+    tfree(c, c->wfs); tfree(c, c->wtally);
     c->wtab = {};
+    c->wide_direct = false;
+    c->h_prior_raw.clear();
     c->wfirst = false;
     c->wide_active = false;
     c->wk = 0;
@@ -630,6 +636,10 @@ int mbpe_set_option(mbpe_ctx *c, const char *name, int64_t value) {
     else if (n == "log_chunk") c->opt_log_chunk = value < 0 ? 0 : std::min<int64_t>(value, 1ll << 16);   // (likewise)
     else if (n == "wide_from") c->opt_wide_from = value < 0 ? -1 : value;      // (read by the next mbpe_train_begin)
     else if (n == "first_wide") c->opt_first_wide = value != 0;                // (read by the next mbpe_train_begin)
+    else if (n == "resume_wide") {                                             // (read by the next mbpe_train_begin_from)
+        if (value != 0 && value != 1) { mbpe_host::set_last_error("resume_wide: 0 or 1"); return MBPE_ERR_ARG; }
+        c->opt_resume_wide = value;
+    }
     else if (n == "pc_repeat") c->opt_pc_repeat = std::min<int64_t>(std::max<int64_t>(1, value), 1000);
     else { mbpe_host::set_last_error("unknown option " + n); return MBPE_ERR_ARG; }
     return MBPE_OK;
@@ -1596,6 +1606,9 @@ static int replay_prior(mbpe_ctx *c, const uint32_t *prior, uint32_t n_prior, ui
     return rc;
 }
 
+static int wide_begin_from(mbpe_ctx *c, uint32_t vocab_size, uint32_t **tok, uint64_t n_tok, const uint32_t *prior,
+                           uint32_t n_prior);
+
 int mbpe_train_begin_from(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prior_merges, uint32_t n_prior) {
     if (!c) return MBPE_ERR_ARG;
     if (n_prior == 0) return mbpe_train_begin(c, vocab_size);
@@ -1614,7 +1627,24 @@ int mbpe_train_begin_from(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prio
         return MBPE_ERR_STATE;
     }
     const uint32_t vmax = !c->chunked ? MBPE_MAX_VOCAB_BASIC : c->opt_barrier == 0 ? MBPE_MAX_VOCAB_ENDBIT : MBPE_MAX_VOCAB_CHUNKED;
-    if (vocab_size > vmax || c->opt_wide_from >= 0) {
+    // "resume_wide": T merges in all, of which the slot stream can make the first h.  T <= h: the slot case, as ever.
+    // n_prior < h < T: the mixed case -- the begin below with the slot target 256 + h, then the handover of
+    // mbpe_train_begin's trainings (wide_convert).  n_prior >= h: the direct case (wide_begin_from).
+    const uint32_t T = vocab_size - 256;
+    const uint32_t h = c->opt_wide_from >= 0 ? (uint32_t)std::min<int64_t>(c->opt_wide_from, vmax - 256) : vmax - 256;
+    const bool beyond = c->opt_resume_wide && T > h;
+    if (beyond) {
+        if (vocab_size > MBPE_MAX_VOCAB_WIDE) {
+            mbpe_host::set_last_error("vocab_size exceeds " + std::to_string(MBPE_MAX_VOCAB_WIDE));
+            return MBPE_ERR_VOCAB;
+        }
+        if (c->opt_first && !c->opt_first_wide) {
+            mbpe_host::set_last_error("mbpe_train_begin_from: vocab_size exceeds the 16-bit slot format (" + std::to_string(vmax) +
+                                      "): with the `first` tie-break the 32-bit continuation runs only with the option "
+                                      "first_wide = 1");
+            return MBPE_ERR_VOCAB;
+        }
+    } else if (!c->opt_resume_wide && (vocab_size > vmax || c->opt_wide_from >= 0)) {
         mbpe_host::set_last_error("mbpe_train_begin_from: vocab_size " + std::to_string(vocab_size) + " (with " +
                                   std::to_string(n_prior) + " prior merges) lies beyond the 16-bit slot format of this corpus (" +
                                   std::to_string(vmax) + "), or \"wide_from\" is set: the 32-bit continuation does not "
@@ -1628,6 +1658,12 @@ int mbpe_train_begin_from(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prio
     uint64_t n_tok = 0;
     rc = replay_prior(c, prior_merges, n_prior, &tok, &n_tok);
     if (rc != MBPE_OK) return rc;
+    if (beyond && n_prior >= h) {
+        rc = wide_begin_from(c, vocab_size, &tok, n_tok, prior_merges, n_prior);
+        if (rc != MBPE_OK) (void)hipStreamSynchronize(c->stream);
+        dfree(tok);
+        return rc;
+    }
     auto rest = [&]() -> int {
         if (c->barrier && n_tok) {
             // the barrier slots the compaction keeps are the tokens' end flags: they must be the mask's end bits, by
@@ -1647,7 +1683,8 @@ int mbpe_train_begin_from(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prio
             }
         }
         const ResumeSrc rs = {tok, n_tok, prior_merges, n_prior};
-        int r = begin_local(c, vocab_size, &rs);
+        c->wide = beyond;        // (the mixed case: the slot stream's share ends at merge h, where wide_convert takes over)
+        int r = begin_local(c, beyond ? 256 + h : vocab_size, &rs);
         c->vocab_total = vocab_size;
         c->n_target_total = vocab_size - 256;
         if (r != MBPE_OK) return r;
@@ -1924,10 +1961,44 @@ static int wide_sync(mbpe_ctx *c) {
     HIPCHK(hipMemcpyAsync(&c->h_wctl, c->wctl, sizeof(WideCtl), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipGetLastError());
-    if (c->h_wctl.err) {
+    if (c->h_wctl.err & kWideErrFull) {
         mbpe_host::set_last_error("device error: the 32-bit pair table is full");
         return MBPE_ERR_OVERFLOW;
     }
+    if (c->h_wctl.err) {
+        mbpe_host::set_last_error(c->h_wctl.err & kWideErrToken
+                                      ? "device error: the replayed stream holds a token id that no prior merge made"
+                                      : "device error: a pair occurs 2^31 times or more, or the pair counts do not add up "
+                                        "to the pairs scanned");
+        return MBPE_ERR_OVERFLOW;
+    }
+    return MBPE_OK;
+}
+
+// The buffers of the 32-bit loop for a stream of at most n_tok tokens (n_val: positions the value array holds, the
+// slot stream's barriers included at a conversion) and its control block, with n_init tokens in the stream already.
+static int wide_alloc_loop(mbpe_ctx *c, uint64_t n_tok, uint64_t n_val, uint64_t n_init) {
+    const uint32_t n_wide = c->n_target_total - c->n_target;
+    if (!c->wtok[0]) HIPCHK(tmalloc(c, &c->wtok[0], std::max<uint64_t>(n_tok, 1) * 4));      // (wide_begin_from: there already)
+    HIPCHK(tmalloc(c, &c->wtok[1], std::max<uint64_t>(n_tok, 1) * 4));
+    HIPCHK(tmalloc(c, &c->wval, std::max<uint64_t>(n_val, 1) * 4));
+    HIPCHK(tmalloc(c, &c->wscratch, wide_scratch_words(n_val) * 4));
+    HIPCHK(tmalloc(c, &c->wctl, sizeof(WideCtl)));
+    HIPCHK(tmalloc(c, &c->wbest, ((size_t)n_wide + 2) * sizeof(WideBest)));
+    HIPCHK(tmalloc(c, &c->warg, 2 * 1024 * 8));
+    c->wfirst = c->opt_first != 0;
+    c->h_wctl = WideCtl{};
+    c->h_wctl.n = n_init;
+    c->h_wctl.first = c->wfirst ? 1u : 0u;
+    HIPCHK(hipMemcpyAsync(c->wctl, &c->h_wctl, sizeof(WideCtl), hipMemcpyHostToDevice, c->stream));
+    if (c->wfirst) {
+        HIPCHK(tmalloc(c, &c->wfs, sizeof(WideFirst)));
+        HIPCHK(hipMemsetAsync(c->wfs, 0, sizeof(WideFirst), c->stream));
+        HIPCHK(hipMemsetAsync(&c->wfs->pos, 0xFF, sizeof(c->wfs->pos), c->stream));
+    }
+    c->wcur = 0;
+    c->wk = 0;
+    c->h_wbest.clear();
     return MBPE_OK;
 }
 
@@ -1940,22 +2011,8 @@ static int wide_convert(mbpe_ctx *c) {
     if (rc != MBPE_OK) return rc;
     const uint64_t n_live_slots = c->h_ctl.n_live;
     const uint64_t n_tok = n_live_slots - (c->barrier ? c->n_barriers : 0);
-    const uint32_t n_wide = c->n_target_total - c->n_target;
-    HIPCHK(tmalloc(c, &c->wtok[0], std::max<uint64_t>(n_tok, 1) * 4));
-    HIPCHK(tmalloc(c, &c->wtok[1], std::max<uint64_t>(n_tok, 1) * 4));
-    HIPCHK(tmalloc(c, &c->wval, std::max<uint64_t>(n_live_slots, 1) * 4));
-    HIPCHK(tmalloc(c, &c->wscratch, wide_scratch_words(n_live_slots) * 4));
-    HIPCHK(tmalloc(c, &c->wctl, sizeof(WideCtl)));
-    HIPCHK(tmalloc(c, &c->wbest, ((size_t)n_wide + 2) * sizeof(WideBest)));
-    HIPCHK(tmalloc(c, &c->warg, 2 * 1024 * 8));
-    HIPCHK(hipMemsetAsync(c->wctl, 0, sizeof(WideCtl), c->stream));
-    c->wfirst = c->opt_first != 0;
-    if (c->wfirst) {
-        HIPCHK(tmalloc(c, &c->wfs, sizeof(WideFirst)));
-        HIPCHK(hipMemsetAsync(c->wfs, 0, sizeof(WideFirst), c->stream));
-        HIPCHK(hipMemsetAsync(&c->wfs->pos, 0xFF, sizeof(c->wfs->pos), c->stream));
-        HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->wctl->first), 1, 1, c->stream));
-    }
+    rc = wide_alloc_loop(c, n_tok, n_live_slots, 0);
+    if (rc != MBPE_OK) return rc;
     const uint32_t barrier = c->barrier ? kBarrier : 0xFFFFFFFFu;
     const uint32_t endbit = c->chunked && !c->barrier ? kEndBit : 0u;
     launch_wide_from_slots(c->stream, c->tok[c->cur], n_live_slots, barrier, endbit, c->wval, c->wscratch, c->wtok[0], c->wctl);
@@ -1980,6 +2037,70 @@ static int wide_convert(mbpe_ctx *c) {
     tfree(c, c->tab.hslot); tfree(c, c->tab.ekey); tfree(c, c->tab.ecnt); tfree(c, c->tab.bmax); tfree(c, c->tab.smax);
     tfree(c, c->first_state);                 // (the slot stream's `first` scratch; the 32-bit loop has its own)
     c->LR = nullptr;
+    pool_trim(c);
+    return MBPE_OK;
+}
+
+// A training that continues from so many merges that no slot stream can hold their ids: the replay's tokens (*tok,
+// n_tok of them in an array of the caller's, which is freed here once they are copied) ARE the 32-bit stream, the
+// 64-bit-key table is counted from them, and the 32-bit loop runs from merge n_prior.  The table is allocated before
+// the count for the most distinct pairs the stream can hold (wide_add inserts concurrently: no bins, no census) and
+// replaced by one of the right size once the count is known.
+static int wide_begin_from(mbpe_ctx *c, uint32_t vocab_size, uint32_t **tok, uint64_t n_tok, const uint32_t *prior,
+                           uint32_t n_prior) {
+    free_training(c);
+    c->vocab_size = 256 + n_prior;           // (the slot stream's share: the prior merges, all of them made already)
+    c->n_target = c->k = c->n_valid = c->n_prior = c->k_upper = n_prior;
+    c->vocab_total = vocab_size;
+    c->n_target_total = vocab_size - 256;
+    c->exhausted = false;
+    c->barrier = false;                      // (32-bit tokens carry their chunk ends as flags)
+    c->wide = true;
+    c->wide_direct = true;
+    c->h_ctl = DevCtl{};
+    c->h_prior_raw.assign(prior, prior + 2 * (size_t)n_prior);
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    // the stream first, so that the replay's n_bytes x 4 array is gone before anything else is allocated
+    HIPCHK(tmalloc(c, &c->wtok[0], std::max<uint64_t>(n_tok, 1) * 4));
+    if (n_tok) HIPCHK(hipMemcpyAsync(c->wtok[0], *tok, n_tok * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    dfree(*tok);
+    int rc = wide_alloc_loop(c, n_tok, n_tok, n_tok);
+    if (rc != MBPE_OK) return rc;
+    HIPCHK(tmalloc(c, &c->wtally, sizeof(WideTally)));
+    HIPCHK(hipMemsetAsync(c->wtally, 0, sizeof(WideTally), c->stream));
+    const uint64_t ids = 256ull + n_prior;
+    const uint64_t most = std::min<uint64_t>({n_tok ? n_tok - 1 : 0, ids * ids, 1ull << 30});
+    rc = wide_alloc_table(c, &c->wtab, std::max<uint64_t>(most, 1));
+    if (rc != MBPE_OK) return rc;
+    launch_wide_pair_count_tokens(c->stream, c->wtok[0], n_tok, (uint32_t)ids, c->wtab, c->wctl, c->wtally, c->n_cus);
+    WideTally h = {};
+    HIPCHK(hipMemcpyAsync(&h, c->wtally, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    rc = wide_sync(c);
+    if (rc != MBPE_OK) return rc;
+    // the right size: the pairs there are plus what the first group of merges can add, at load factor 1/2
+    const uint64_t need = (uint64_t)c->h_wctl.n_entries + wide_headroom(h.top, 16);
+    uint32_t bits = 12;
+    while ((1ull << bits) < 2 * need && bits < 31) ++bits;
+    if ((uint64_t)c->wtab.mask + 1 != (1ull << bits)) {
+        WideTable old = c->wtab;
+        rc = wide_alloc_table(c, &c->wtab, need);
+        if (rc != MBPE_OK) return rc;
+        HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->wctl->n_entries), 0, 1, c->stream));
+        launch_wide_rehash(c->stream, old, c->wtab, c->wctl);
+        rc = wide_sync(c);
+        trelease(c, old.keys); trelease(c, old.cnts);
+        if (rc != MBPE_OK) return rc;
+    }
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    HIPCHK(hipEventSynchronize(c->ev1));
+    HIPCHK(hipEventElapsedTime(&c->stats.ms_begin, c->ev0, c->ev1));
+    c->stats.ms_begin += c->ms_replay;
+    c->stats.ms_steps = 0;
+    c->wn_upper = n_tok;
+    c->last_top = h.top;
+    c->wide_active = true;
+    c->begun = true;
     pool_trim(c);
     return MBPE_OK;
 }
@@ -2101,8 +2222,8 @@ int mbpe_train_result(mbpe_ctx *c, uint32_t *merges_out, int32_t *counts_out, ui
     HIPCHK(hipSetDevice(c->device));
     uint32_t n = c->exhausted ? c->n_prior : c->n_valid;
     std::vector<unsigned long long> h(n);
-    if (n) HIPCHK(hipMemcpy(h.data(), c->best, (size_t)n * 8, hipMemcpyDeviceToHost));
-    if (c->opt_first) {
+    if (n && !c->wide_direct) HIPCHK(hipMemcpy(h.data(), c->best, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (c->opt_first && !c->wide_direct) {
         // a table rebuilt before every merge holds no zero-count pair: the reference's loop breaks as soon as
         // no pair is left (Tokenizer.h:586-588), the incremental table only shows it as "max count 0"
         uint32_t real = 0;
@@ -2113,7 +2234,12 @@ int mbpe_train_result(mbpe_ctx *c, uint32_t *merges_out, int32_t *counts_out, ui
     if (n_merges_out) *n_merges_out = n + nw;
     if (n + nw > cap_merges && merges_out) { mbpe_host::set_last_error("merges_out too small"); return MBPE_ERR_ARG; }
     if (!(n + nw) || !merges_out) return MBPE_OK;
-    for (uint32_t i = 0; i < n; ++i) {
+    for (uint32_t i = 0; i < n && c->wide_direct; ++i) {      // (all of them prior merges, kept as they were given)
+        merges_out[2 * i] = c->h_prior_raw[2 * i];
+        merges_out[2 * i + 1] = c->h_prior_raw[2 * i + 1];
+        if (counts_out) counts_out[i] = -1;
+    }
+    for (uint32_t i = 0; i < n && !c->wide_direct; ++i) {
         uint32_t key = ~(uint32_t)h[i];
         merges_out[2 * i] = key >> 16;
         merges_out[2 * i + 1] = key & 0xFFFFu;

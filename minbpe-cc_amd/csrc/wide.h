@@ -27,6 +27,13 @@
 //
 // and the loop ends at M = 0 (Tokenizer.h:586-588: a rebuilt table holds no zero-count pair).
 //
+// A training that continues from existing merges (mbpe_train_begin_from, "resume_wide") can also START here, without
+// a slot stream: the rank-ordered replay leaves this very token layout, and
+//
+//   k_wide_pair_count_tokens  counts its adjacent pairs into the table (LDS cache of 64-bit keys per workgroup,
+//                             flushed through the concurrent insert of the merge kernels), followed by a census of
+//                             the table that must add up to the positions counted
+//
 // One GPU, either tie-break.  Slower per merge than the 16-bit path (one merge per pass, ~20 B of traffic per token),
 // but it turns MBPE_ERR_VOCAB into a training for GPT-4-size vocabularies.
 #ifndef MBPE_WIDE_H
@@ -48,10 +55,19 @@ struct WideTable {
     uint32_t shift;                // 64 - log2(capacity)
 };
 
+// WideCtl::err
+constexpr uint32_t kWideErrFull = 1u;       // the table is full
+constexpr uint32_t kWideErrToken = 2u;      // the pair count met a token id that does not exist
+constexpr uint32_t kWideErrCount = 4u;      // the pair count's table does not add up to the positions counted, or a
+                                            //   pair occurs 2^31 times or more
+
+// census of the pair count of a resumed stream (launch_wide_pair_count_tokens)
+struct WideTally { unsigned long long positions, total; uint32_t top, pad; };
+
 struct WideCtl {
     unsigned long long n;          // tokens in the stream
     uint32_t n_entries;            // pairs ever inserted
-    uint32_t err;                  // 1: table full
+    uint32_t err;                  // kWideErr* flags
     uint32_t k;                    // merges done by the wide loop
     uint32_t k_limit;
     uint32_t a, b;                 // the pair chosen for the merge under way
@@ -89,6 +105,12 @@ void launch_wide_table_from16(hipStream_t s, const uint32_t *ekey, const int32_t
                               WideCtl *ctl);
 void launch_wide_table_clear(hipStream_t s, WideTable t);
 void launch_wide_rehash(hipStream_t s, WideTable from, WideTable to, WideCtl *ctl);
+// A stream that starts as 32-bit tokens (a training continued from existing merges, no slot stream): the count of its
+// adjacent pairs into the cleared table t -- k_wide_pair_count_tokens, the 64-bit-key counterpart of
+// k_pair_count_tokens -- then the table's census and its check against the positions counted.  tok: n_tok flagged
+// tokens; ids: the token ids that exist (kWideErrToken for one beyond them).  tally: zeroed by the caller.
+void launch_wide_pair_count_tokens(hipStream_t s, const uint32_t *tok, uint64_t n_tok, uint32_t ids, WideTable t,
+                                   WideCtl *ctl, WideTally *tally, int n_cus);
 // argmax -> ctl->a, b, count, live and best[ctl->k]; clears ctl->ran
 void launch_wide_argmax(hipStream_t s, WideTable t, WideCtl *ctl, WideBest *best, unsigned long long *scratch /* 3 * 1024 */);
 // `first` mode, after launch_wide_argmax (same scratch): among the pairs of the maximal count the one whose first

@@ -55,6 +55,79 @@ __global__ void k_wide_rehash(WideTable from, WideTable to, WideCtl *ctl) {
     }
 }
 
+// ---- the pair count of a stream that starts as 32-bit tokens (a training continued from existing merges) ------------
+// The 64-bit-key counterpart of k_pair_count_tokens (kernels.hip): every position i whose token is not the last of its
+// chunk counts (tok[i], tok[i+1]), overlapping ones too.  A workgroup counts its contiguous share in an LDS cache --
+// kWpSlots open-addressed entries, 64-bit keys beside 32-bit counts, up to kWpProbes probes; the key is claimed with
+// one 8-byte LDS compare-and-swap (skipped when the key is there already) -- and flushes the cache once through
+// wide_add; a position that finds no entry goes to wide_add directly.  A share is at most 2^20 positions (the
+// launcher's grid), so an LDS count cannot wrap.  ids: the token ids that exist; a token beyond them sets
+// kWideErrToken and is never hashed or used as an address.  4 B read per token.
+constexpr int kWpThreads = 256;
+constexpr uint32_t kWpSlots = 1024, kWpProbes = 4;      // 8 KiB of keys + 4 KiB of counts
+__global__ __launch_bounds__(kWpThreads) void k_wide_pair_count_tokens(const uint32_t *__restrict__ tok, uint64_t n_tok,
+                                                                       uint32_t ids, WideTable t, WideCtl *ctl,
+                                                                       WideTally *tally) {
+    __shared__ unsigned long long ckey[kWpSlots];
+    __shared__ uint32_t ccnt[kWpSlots];
+    for (uint32_t i = threadIdx.x; i < kWpSlots; i += kWpThreads) { ckey[i] = kWideEmpty; ccnt[i] = 0; }
+    __syncthreads();
+    const uint64_t per = (n_tok + gridDim.x - 1) / gridDim.x;
+    const uint64_t lo = (uint64_t)blockIdx.x * per, hi = lo + per < n_tok ? lo + per : n_tok;
+    uint32_t counted = 0;
+    for (uint64_t i = lo + threadIdx.x; i < hi; i += kWpThreads) {
+        const uint32_t a = tok[i];
+        if ((a & kTokEnd) || i + 1 >= n_tok) continue;
+        const uint32_t b = tok[i + 1] & kTokIdMask;
+        if (a >= ids || b >= ids) { atomicOr(&ctl->err, kWideErrToken); continue; }
+        const unsigned long long key = ((unsigned long long)a << 32) | b;
+        ++counted;
+        uint32_t h = pair_hash(key, 64 - 10);
+        static_assert(kWpSlots == 1u << 10, "pair_hash's shift above");
+        bool done = false;
+#pragma unroll
+        for (uint32_t p = 0; p < kWpProbes && !done; ++p) {
+            unsigned long long k = ckey[h];
+            if (k == kWideEmpty) k = atomicCAS(&ckey[h], kWideEmpty, key);
+            if (k == kWideEmpty || k == key) { atomicAdd(&ccnt[h], 1u); done = true; }
+            h = (h + 1) & (kWpSlots - 1);
+        }
+        if (!done) wide_add(t, ctl, key, 1);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < kWpSlots; i += kWpThreads)
+        if (ckey[i] != kWideEmpty) wide_add(t, ctl, ckey[i], (int32_t)ccnt[i]);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) counted += __shfl_xor(counted, d, kWave);
+    if (lane_id() == 0 && counted) atomicAdd(&tally->positions, (unsigned long long)counted);
+}
+
+// the census of the table behind that count: the sum of its counts, the largest of them (as unsigned: a count that
+// passed 2^31 shows as one)
+__global__ __launch_bounds__(256) void k_wide_table_tally(WideTable t, WideTally *tally) {
+    unsigned long long sum = 0;
+    uint32_t top = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= t.mask; i += (uint64_t)gridDim.x * blockDim.x) {
+        if (t.keys[i] == kWideEmpty) continue;
+        const uint32_t v = (uint32_t)t.cnts[i];
+        sum += v;
+        top = v > top ? v : top;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        sum += ((unsigned long long)(uint32_t)__shfl_xor((int)(sum >> 32), d, kWave) << 32) | (uint32_t)__shfl_xor((int)sum, d, kWave);
+        const uint32_t o = __shfl_xor(top, d, kWave);
+        top = o > top ? o : top;
+    }
+    if (lane_id() == 0 && top) { atomicAdd(&tally->total, sum); atomicMax(&tally->top, top); }
+}
+
+// the counterpart of k_resume_check: the counts must add up to the positions counted (a count that wrapped past 2^32
+// does not), and none may have reached 2^31
+__global__ void k_wide_resume_check(const WideTally *tally, WideCtl *ctl) {
+    if (tally->total != tally->positions || tally->top >= 0x80000000u) atomicOr(&ctl->err, kWideErrCount);
+}
+
 // ---- argmax: (count desc, first asc, second asc) = the larger of (count, ~key) -------------------------------
 struct Cand128 { long long count; unsigned long long nkey; };      // count = -1: nothing
 __device__ __forceinline__ bool better(const Cand128 &a, const Cand128 &b) {
@@ -413,6 +486,23 @@ void launch_wide_table_from16(hipStream_t s, const uint32_t *ekey, const int32_t
 
 void launch_wide_rehash(hipStream_t s, WideTable from, WideTable to, WideCtl *ctl) {
     hipLaunchKernelGGL(k_wide_rehash, dim3(2048), dim3(256), 0, s, from, to, ctl);
+}
+
+void launch_wide_pair_count_tokens(hipStream_t s, const uint32_t *tok, uint64_t n_tok, uint32_t ids, WideTable t,
+                                   WideCtl *ctl, WideTally *tally, int n_cus) {
+    if (n_tok >= 2) {
+        // 8 workgroups of 12 KiB LDS per CU; a workgroup's share is at least 4,096 tokens (so that the flush of its
+        // cache is paid for) and at most 2^20 (LDS counts cannot wrap)
+        uint64_t blocks = (uint64_t)(n_cus > 0 ? n_cus : 256) * 8;
+        blocks = std::min<uint64_t>(blocks, (n_tok + 4095) / 4096);
+        blocks = std::max<uint64_t>(blocks, (n_tok + (1u << 20) - 1) >> 20);
+        hipLaunchKernelGGL(k_wide_pair_count_tokens, dim3((uint32_t)blocks), dim3(kWpThreads), 0, s, tok, n_tok, ids, t, ctl,
+                           tally);
+    }
+    const uint64_t slots = (uint64_t)t.mask + 1;
+    const uint32_t tb = (uint32_t)std::min<uint64_t>((slots + 1023) / 1024, 4096);
+    hipLaunchKernelGGL(k_wide_table_tally, dim3(tb), dim3(256), 0, s, t, tally);
+    hipLaunchKernelGGL(k_wide_resume_check, dim3(1), dim3(1), 0, s, tally, ctl);
 }
 
 void launch_wide_argmax(hipStream_t s, WideTable t, WideCtl *ctl, WideBest *best, unsigned long long *scratch) {

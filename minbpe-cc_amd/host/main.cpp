@@ -77,7 +77,9 @@ void usage() {
                  "  --continue-from TEXT        With --train: load this model and continue its training on the input up to\n"
                  "                              --vocab-size, which must not be below the model's size; the result goes to\n"
                  "                              --model-path.  The loaded model's split pattern is used: --encoder has no\n"
-                 "                              effect then.  One HIP device, vocabularies within the 16-bit slot format\n";
+                 "                              effect then.  One HIP device; vocabularies up to 16,777,216, beyond the 16-bit\n"
+                 "                              slot format on 32-bit tokens (a model without a split pattern replays one\n"
+                 "                              pass per merge it already has)\n";
 }
 
 }  // namespace

@@ -226,6 +226,8 @@ void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTI
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "conflict_resolution", conflict_resolution == LEXICAL ? 1 : 0);
     // (`first` beyond the 16-bit slot format continues on 32-bit tokens, as the reference's uint32_t Token does)
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "first_wide", 1);
+    // (... and so does a training that continues from existing merges)
+    if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "resume_wide", 1);
     if (rc == MBPE_OK) rc = mbpe_train_begin_from(ctx, static_cast<uint32_t>(vocab_size), prior.data(), n_prior);
     if (rc == MBPE_OK) rc = mbpe_train_steps(ctx, cap, nullptr);
     if (rc == MBPE_OK) rc = mbpe_train_result(ctx, flat.data(), had.data(), cap, &n_merges);

@@ -1068,7 +1068,10 @@ class Trainer:
 
     def train_begin(self, vocab_size, prior_merges=None):
         """Returns NEED_EXCHANGE in external-transport mode, else OK.  prior_merges ([n, 2]): continue from these
-        merges instead of from raw bytes (mbpe_train_begin_from)."""
+        merges instead of from raw bytes (mbpe_train_begin_from).  Beyond the 16-bit slot format that is MbpeError(ERR_VOCAB)
+        unless set_option("resume_wide", 1) was called: then the training continues on 32-bit tokens, from the slot
+        stream's handover or, when the prior merges already reach it, directly (vocabularies up to 2^24, one rank;
+        `first` also needs "first_wide")."""
         if prior_merges is None:
             rc = _check(lib().mbpe_train_begin(self._h, vocab_size))
         else:
@@ -1118,7 +1121,8 @@ class Trainer:
 
     def train(self, data, vocab_size, chunk_off=None, conflict_resolution=1, prior_merges=None):
         """conflict_resolution: 1 = lexical, 0 = first (mbpe_train).  prior_merges: continue from them (mbpe_train_from);
-        the result then starts with them, with counts of -1."""
+        the result then starts with them, with counts of -1.  Options are taken from the context: "resume_wide" 1 lets a
+        continuation pass the 16-bit slot format (see train_begin)."""
         text = _u8(data)
         prior = _merges(prior_merges)
         off = None if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.uint64)
@@ -1232,7 +1236,8 @@ class Tokenizer:
     def train(self, data, vocab_size, conflict_resolution=1, verbose=False, device=0, device_split=False,
               resume=False):
         """resume: continue from the merges the tokenizer holds (loaded, set or trained) up to vocab_size instead of
-        starting from raw bytes (mbpe_tok_train_continue); pattern and special tokens stay.
+        starting from raw bytes (mbpe_tok_train_continue); pattern and special tokens stay.  Vocabularies up to 2^24,
+        either tie-break: beyond the 16-bit slot format the continuation runs on 32-bit tokens ("resume_wide").
         device_split: the gpt2 / gpt4 pre-split runs on the device too (same merges); a tokenizer with any other
         pattern raises MbpeError(ERR_ARG).  "unicode" instead of True: with the splitter's option "unicode", so that
         well-formed non-ASCII text is split there as well (mbpe_tok_set_split_unicode)."""
