@@ -479,7 +479,8 @@ MBPE_API void mbpe_encoder_destroy(mbpe_encoder *e);
  * returns MBPE_ERR_OOM with a message that names it; the encoder stays usable.  With "piece_bytes" 0 (the default) a
  * text that fits the buffers the encoder already holds is one piece; otherwise the limit is
  * (free + held - (free + held) / 16) / 14 bytes, where free is the device memory hipMemGetInfo reports at the call
- * and held the size of the encoder's work buffers: a piece costs 13.2 bytes of device memory per text byte.
+ * and held the size of the encoder's work buffers: a piece costs 13.2 bytes of device memory per text byte
+ * (with token byte offsets for the host: up to 21.2, and the divisor is 22 -- see mbpe_encoder_encode_byteoff).
  * When the pieces are several and cap < n_bytes, the passes run twice (count first, so that a cap too small writes
  * nothing). */
 MBPE_API int  mbpe_encoder_encode(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
@@ -513,9 +514,9 @@ MBPE_API int  mbpe_encoder_encode(mbpe_encoder *e, const uint8_t *text, uint64_t
 MBPE_API int  mbpe_encoder_set_option(mbpe_encoder *e, const char *name, int64_t value);
 
 /* Device time of the encoder's latest call in milliseconds: HIP events on its stream around widen, the passes (with
- * the 8-byte read-back that ends each) and the finishing kernels, summed over the pieces; the copies of text, mask
- * and output between host and device are outside.  Where the passes ran twice (several pieces and cap < n_bytes)
- * both runs are in it. */
+ * the 8-byte read-back that ends each) and the finishing kernels (those of the token byte offsets included), summed
+ * over the pieces; the copies of text, mask and output between host and device are outside.  Where the passes ran
+ * twice (several pieces and cap < n_bytes) both runs are in it. */
 MBPE_API int  mbpe_encoder_kernel_ms(const mbpe_encoder *e, float *ms_out);
 
 /* The passes of the latest call: tokens_out[k] = tokens that entered pass k, summed over the pieces ([0] = n_bytes;
@@ -527,7 +528,8 @@ MBPE_API int  mbpe_encoder_pass_tokens(const mbpe_encoder *e, uint64_t *tokens_o
  * call on a text no longer than an earlier one, with the same arguments, leaves the number as it is.  (Three small
  * buffers follow other sizes and may still grow then: the list of NUL-led chunks with their number, and a list of
  * chunk ends of its own when chunks are shorter than two bytes on average -- otherwise the ends borrow the idle
- * token array.) */
+ * token array.  A call with token byte offsets has three more: len[], once; the singles' token indices; and, for
+ * host output, the staging buffer that follows the TOKEN count of the largest piece.) */
 MBPE_API int  mbpe_encoder_alloc_count(const mbpe_encoder *e, uint64_t *n_out);
 
 /* ---- fixed-length id matrices --------------------------------------------- */
@@ -706,7 +708,46 @@ MBPE_API int  mbpe_encoder_encode_endmask(mbpe_encoder *e, const uint8_t *text_d
                                           void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device,
                                           uint64_t *doc_tok_off_out, uint64_t *n_out, uint32_t *n_passes_out);
 
-/* The same followed by the pack kernel: mbpe_encoder_encode_batch (aux NULL: ids and lengths only) or
+/* ---- token byte offsets ---------------------------------------------------- */
+
+/* mbpe_encoder_encode and mbpe_encoder_encode_endmask that also say which bytes of `text` every token stands for.  All
+ * arguments, results and error codes are those of the counterpart; the one addition:
+ *   tok_byte_off_out   optional; lives where tokens_out lives (host memory, or device memory -- 8-byte aligned -- when
+ *                      out_on_device != 0) and has room for cap + 1 entries.  On success with *n_out == n it holds
+ *                      n + 1 ascending offsets into text: [0] == 0, [n] == n_bytes, and token j stands for
+ *                      text[tok_byte_off[j] .. tok_byte_off[j + 1]).  The chunks tile the text and no token crosses a
+ *                      chunk, so the tokens tile it too (the convention of chunk_off and chunk_tok_off_out).  A chunk
+ *                      that is one token by rule -- NUL-led with a remainder std::stoi parses, or a mbpe_single -- covers
+ *                      its whole chunk whatever its id decodes to; an empty chunk contributes nothing.
+ *                      NULL: the call IS its counterpart.  Ignored (nothing written) by a query (tokens_out NULL).  A
+ *                      cap too small writes no offset.  Pieces: the offsets continue across pieces in 64 bits, the
+ *                      result is that of the unsplit call.  Empty text: [0] = 0.
+ * Precondition, checked on the host before the device is touched: the encoder's table is one mbpe_merges_check accepts
+ * (and no token is longer than 2^32 - 1 bytes).  Only then are the bytes a token covers a function of its id alone:
+ * len[256 + k] = len[a_k] + len[b_k].  Any other table: MBPE_ERR_ARG with a message that says so, from these two calls
+ * only -- the encoder stays usable and the plain calls take such tables as before.
+ * How: after the passes, from the final stream (nothing is carried through the passes; the plain calls run the kernels
+ * they ran before): per span of 1,024 tokens a 64-bit byte count, one scan workgroup, a ranked write with a wave prefix
+ * sum; the one-token chunks get their chunk's length through a list of their token indices (rank of their start among
+ * the mask's end bits -> the finishing kernel's chunk ends).  The new kernels read each token twice and write 8 bytes
+ * per token.  Device memory: 4 bytes per token id (len[], uploaded by the first such call and kept), 8 bytes per 1,024
+ * text bytes, 8 per one-token chunk and -- only when the offsets go to the host -- a staging buffer of 8 bytes per
+ * token of the largest piece.  A piece then costs up to 13.2 + 8 = 21.2 bytes per text byte (every byte its own
+ * token), and the limit that "piece_bytes" 0 derives divides by 22 instead of 14 for such a call; with out_on_device it
+ * stays 14.  A repeat call of no larger size allocates nothing. */
+MBPE_API int  mbpe_encoder_encode_byteoff(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                          const uint64_t *chunk_off, uint64_t n_chunks,
+                                          void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device,
+                                          uint64_t *tok_byte_off_out, uint64_t *chunk_tok_off_out, uint64_t *n_out,
+                                          uint32_t *n_passes_out);
+MBPE_API int  mbpe_encoder_encode_endmask_byteoff(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
+                                                  const uint8_t *endmask_dev, const mbpe_single *singles,
+                                                  uint64_t n_singles, const uint64_t *doc_off, uint64_t n_docs,
+                                                  void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device,
+                                                  uint64_t *tok_byte_off_out, uint64_t *doc_tok_off_out, uint64_t *n_out,
+                                                  uint32_t *n_passes_out);
+
+/* mbpe_encoder_encode_endmask followed by the pack kernel: mbpe_encoder_encode_batch (aux NULL: ids and lengths only) or
  * mbpe_encoder_encode_batch_aux for the documents doc_off describes, which here must start at 0 and end at n_bytes.
  * The documents' token offsets go from the encode to the pack kernel on the device; neither a token nor an offset
  * crosses to the host unless doc_tok_off_out asks for the offsets.  All other arguments and results are those of

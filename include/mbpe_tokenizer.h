@@ -83,6 +83,30 @@ MBPE_API int mbpe_tok_encode_batch_device(mbpe_tokenizer *t, const uint8_t *text
                                           uint64_t n_docs, int verbose, int device_id, uint32_t *tokens_out,
                                           uint64_t cap, uint64_t *doc_tok_off_out, uint64_t *n_out);
 
+/* encode with token byte ranges ("offsets mapping"): the tokens of mbpe_tok_encode / mbpe_tok_encode_device and, for
+ * token j, ranges_out[2j] and ranges_out[2j + 1]: the start and the end of the bytes it stands for in the ORIGINAL text,
+ * relative to its document's first byte.  They are pairs and not a tiling because the encoder does not always read the
+ * original text: with the host split a special token is replaced by a "\0<id>" marker and a custom pattern may leave
+ * bytes between two matches that belong to no token.  The ranges ascend and do not overlap; text[start .. end) is the
+ * token's vocabulary entry, or -- a special token -- the occurrence of its name.
+ *   device_id < 0    (single-text call only) the host loop: text_to_vector, the merge loop in the order
+ *                    mbpe_tok_set_encode_order chose, ranges from the vocabulary's entry lengths within each chunk
+ *   device_id >= 0   mbpe_encoder_encode_byteoff over the host split, whose chunks carry their source ranges (a chunk's
+ *                    first token starts where its source starts, its last one ends where it ends), or -- after
+ *                    mbpe_tok_set_encode_split(1) -- mbpe_encoder_encode_endmask_byteoff over the device split, whose
+ *                    text is the original text.  mbpe_tok_set_split_unicode holds as for the plain calls.  The device
+ *                    routes need merges mbpe_merges_check accepts (MBPE_ERR_ARG otherwise)
+ * The three routes agree token for token and range for range.  tokens_out NULL: query (n_out, and doc_tok_off_out
+ * where given); otherwise ranges_out (2 * cap entries) is required.  A cap too small returns MBPE_ERR_ARG, writes no
+ * token and no range and still reports the count.  The batch call is mbpe_tok_encode_batch_device with ranges_out
+ * added: one device call for all documents, each equal to the single-text call on it. */
+MBPE_API int mbpe_tok_encode_byteoff(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, int verbose, int device_id,
+                                     uint32_t *tokens_out, uint64_t *ranges_out, uint64_t cap, uint64_t *n_out);
+MBPE_API int mbpe_tok_encode_batch_byteoff_device(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off,
+                                                  uint64_t n_docs, int verbose, int device_id, uint32_t *tokens_out,
+                                                  uint64_t *ranges_out, uint64_t cap, uint64_t *doc_tok_off_out,
+                                                  uint64_t *n_out);
+
 /* The same documents as one id matrix on the device: every document is split as above, all chunks go to the device
  * in ONE mbpe_encoder_encode_batch (mbpe.h), which encodes them and packs the documents by `spec`.  bos_id and eos_id
  * may name special-token ids.  spec, ids_out (NULL: query), cap_rows, out_on_device, len_out, n_rows_out (required)

@@ -23,6 +23,10 @@
 // count of flags -> k_enc_scan_sum -> ranked write).  A text that lives on the device is read in place; the chunk
 // starts whose byte is NUL are listed by a small kernel so that the host can parse those chunks.
 //
+// The _byteoff calls also say which text bytes every token stands for: after the passes, from the final stream, a
+// length per id -> a 64-bit byte count per span -> one scan workgroup -> a ranked write with a wave prefix sum; the
+// chunks that are one token by rule are patched with their chunk's length (see "token byte offsets" below).
+//
 // Option "rank_order": a pass replaces, in every chunk, only the candidates whose id is the smallest candidate id of
 // that chunk -- k_enc_cand, then a segmented minimum of cand over the chunks (rank.h) and a filter, then the same
 // parity scan, match, sum scan and scatter.  Passes repeat until one changes nothing, as above; for a trained table
@@ -289,8 +293,20 @@ __global__ __launch_bounds__(256) void k_enc_mask_count(const uint32_t *__restri
     if (lane == 0) cnt[block] = c;
 }
 
+// end bits of the mask below text byte p (<= n_bytes).  mask: 4 * n_words bytes and 4 more are readable
+__device__ __forceinline__ unsigned long long mask_rank(uint64_t p, const uint32_t *__restrict__ mask,
+                                                        const unsigned long long *__restrict__ block_off,
+                                                        uint64_t n_blocks, const unsigned long long *__restrict__ total) {
+    const uint64_t w = p >> 5, block = w / kMaskBlockWords;
+    if (block >= n_blocks) return *total;
+    unsigned long long r = block_off[block];
+    for (uint64_t j = block * kMaskBlockWords; j < w; ++j) r += (unsigned long long)__popc(mask[j]);
+    if (p & 31u) r += (unsigned long long)__popc(mask[w] & ((1u << (p & 31u)) - 1u));
+    return r;
+}
+
 // doc_tok[i] = output tokens that come from the bytes before pos[i] (a chunk boundary): the end of chunk rank - 1 in
-// the list the finishing kernel wrote, or 0 before the first chunk.  mask: 4 * n_words bytes and 4 more are readable
+// the list the finishing kernel wrote, or 0 before the first chunk
 __global__ __launch_bounds__(256) void k_enc_doc_tok(const unsigned long long *__restrict__ pos, uint64_t n_pos,
                                                      const uint32_t *__restrict__ mask, uint64_t n_bytes,
                                                      const unsigned long long *__restrict__ block_off, uint64_t n_blocks,
@@ -300,15 +316,7 @@ __global__ __launch_bounds__(256) void k_enc_doc_tok(const unsigned long long *_
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pos) return;
     const uint64_t p = pos[i] < n_bytes ? pos[i] : n_bytes;
-    const uint64_t w = p >> 5, block = w / kMaskBlockWords;
-    unsigned long long r;
-    if (block >= n_blocks) {
-        r = *total;
-    } else {
-        r = block_off[block];
-        for (uint64_t j = block * kMaskBlockWords; j < w; ++j) r += (unsigned long long)__popc(mask[j]);
-        if (p & 31u) r += (unsigned long long)__popc(mask[w] & ((1u << (p & 31u)) - 1u));
-    }
+    unsigned long long r = mask_rank(p, mask, block_off, n_blocks, total);
     if (r > n_ends) r = n_ends;
     doc_tok[i] = r ? ends[r - 1] : 0ull;
 }
@@ -351,10 +359,95 @@ __global__ __launch_bounds__(kSpanThreads) void k_enc_finish(const uint32_t *__r
     }
 }
 
+// ---- token byte offsets (mbpe_encoder_encode_byteoff, mbpe_encoder_encode_endmask_byteoff) ------------------------
+// After the passes, from the final stream: a token stands for len[id] text bytes (a function of the id alone for a
+// table mbpe_merges_check accepts), a chunk that is one token by rule for its whole chunk.  Per span a 64-bit byte
+// count, one scan workgroup, then a ranked write with a wave prefix sum.  The one-token chunks are PATCHES: the index
+// of single k in the final stream is the number of tokens before its first byte -- the rank of its start among the
+// mask's end bits, looked up in the finishing kernel's list of chunk ends, as k_enc_doc_tok does for documents.
+struct LenTab { const uint32_t *len; uint32_t n; };       // ids at or beyond n (they occur as singles only): 0
+struct LenPatch {                                         // token idx[k] of the piece covers sc[k].len bytes; ascending
+    const unsigned long long *idx;
+    const SingleChunk *sc;
+    uint64_t n;
+};
+
+__global__ __launch_bounds__(256) void k_enc_single_tok(const SingleChunk *__restrict__ sc, uint64_t n_sc,
+                                                        const uint32_t *__restrict__ mask, uint64_t n_bytes,
+                                                        const unsigned long long *__restrict__ block_off,
+                                                        uint64_t n_blocks, const unsigned long long *__restrict__ total,
+                                                        const unsigned long long *__restrict__ ends, uint64_t n_ends,
+                                                        unsigned long long tok_base, unsigned long long *__restrict__ idx) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_sc) return;
+    const uint64_t p = sc[k].start < n_bytes ? sc[k].start : n_bytes;
+    unsigned long long r = mask_rank(p, mask, block_off, n_blocks, total);
+    if (r > n_ends) r = n_ends;
+    idx[k] = r ? ends[r - 1] - tok_base : 0ull;
+}
+
+// the bytes of this lane's token in the group that starts at i0; *k = the first patch at or after i0 (the same in every
+// lane), moved past the group
+__device__ __forceinline__ unsigned long long group_len(uint32_t t, bool live, uint64_t i0, uint32_t lane,
+                                                        const LenTab &tab, const LenPatch &pt, uint64_t *k) {
+    const uint32_t id = t & kTokIdMask;
+    unsigned long long l = live && id < tab.n ? tab.len[id] : 0ull;
+    while (*k < pt.n && pt.idx[*k] < i0 + kWave) {
+        if (pt.idx[*k] == i0 + lane) l = pt.sc[*k].len;
+        ++*k;
+    }
+    return l;
+}
+
+// per span: the text bytes its tokens stand for
+__global__ __launch_bounds__(kSpanThreads) void k_enc_len_sum(const uint32_t *__restrict__ tok, uint64_t n, LenTab tab,
+                                                              LenPatch pt, unsigned long long *__restrict__ span_bytes) {
+    const uint64_t span = span_index(), base = span * kSpan;
+    if (base >= n) return;
+    const uint32_t lane = lane_id();
+    uint64_t k = pt.n ? lower_bound64(pt.idx, pt.n, base) : 0;
+    unsigned long long s = 0;
+    for (int it = 0; it < kSpanIters; ++it) {
+        const uint64_t i0 = base + (uint64_t)it * kWave, i = i0 + lane;
+        s += group_len(i < n ? tok[i] : 0u, i < n, i0, lane, tab, pt, &k);
+    }
+    for (int d = kWave / 2; d > 0; d >>= 1) s += __shfl_down(s, d, kWave);
+    if (lane == 0) span_bytes[span] = s;
+}
+
+// span_bytes -> the bytes before every span
+__global__ __launch_bounds__(kScanThreads) void k_enc_scan_sum64(unsigned long long *__restrict__ span_bytes,
+                                                                 uint64_t n_spans) {
+    __shared__ unsigned long long sh[kScanThreads];
+    (void)span_scan_sum64(span_bytes, n_spans, sh);
+}
+
+// out[i] = byte_base + the bytes before token i, for i in [0, n); out[n] = byte_base + all of them
+__global__ __launch_bounds__(kSpanThreads) void k_enc_len_write(const uint32_t *__restrict__ tok, uint64_t n, LenTab tab,
+                                                                LenPatch pt,
+                                                                const unsigned long long *__restrict__ span_off,
+                                                                unsigned long long byte_base,
+                                                                unsigned long long *__restrict__ out) {
+    const uint64_t span = span_index(), base = span * kSpan;
+    if (base >= n) return;
+    const uint32_t lane = lane_id();
+    uint64_t k = pt.n ? lower_bound64(pt.idx, pt.n, base) : 0;
+    unsigned long long o = byte_base + span_off[span];
+    for (int it = 0; it < kSpanIters; ++it) {
+        const uint64_t i0 = base + (uint64_t)it * kWave, i = i0 + lane;
+        const unsigned long long l = group_len(i < n ? tok[i] : 0u, i < n, i0, lane, tab, pt, &k);
+        const unsigned long long incl = wave_prefix64(l, lane);
+        if (i < n) out[i] = o + incl - l;
+        if (i + 1 == n) out[n] = o + incl;
+        o += __shfl(incl, kWave - 1, kWave);
+    }
+}
+
 #define ECHK(expr) MBPE_HIP_CHECK(expr, true)
 
 // device bytes per text byte of a piece, rounded up (mbpe.h, "piece_bytes"): 13.2, and 20 / 1,024 more in rank order
 constexpr uint64_t kPieceCost = 14;
+constexpr uint64_t kPieceCostByteOff = 8;  // more with byte offsets for the host: one uint64_t per token, at most per byte
 constexpr uint64_t kNulListMin = 4096;     // entries the list of NUL-led chunk starts begins with
 constexpr uint64_t kNulCopyEach = 256;     // up to this many NUL-led chunks are copied back one by one
 
@@ -376,7 +469,7 @@ struct mbpe_encoder : DevQueue {
     DevBuf<unsigned long long> span_off;
     DevBuf<RankSum> rank_sum;                 // rank order only: the spans' summaries, and what reaches every span
     DevBuf<uint32_t> rank_in;                 // from the left [0 .. n_spans) and from the right [n_spans .. 2 n_spans)
-    DevBuf<unsigned long long> d_res;         // [0] total of a sum scan, [1] NUL-led chunk starts found
+    DevBuf<unsigned long long> d_res;         // [0] total of a sum scan, [1] NUL-led chunk starts found, [2] end bits of the mask
     DevBuf<SingleChunk> d_singles;
     DevBuf<unsigned long long> d_nul;         // starts of NUL-led chunks of a device text
     DevBuf<unsigned long long> d_ends;        // chunk ends, only when chunks are shorter than two bytes on average
@@ -389,6 +482,12 @@ struct mbpe_encoder : DevQueue {
     DevBuf<void> d_labels;
     DevBuf<uint32_t> d_pos, d_seg;
     float pack_ms = 0.f;                      // the pack kernel of the latest such call
+    // token byte offsets: len[id] (host; empty with len_error set for a table mbpe_merges_check refuses), on the
+    // device from the first such call on; the spans' byte counts, the singles' token indices, offsets bound for the host
+    std::vector<uint32_t> len;
+    std::string len_error;
+    DevBuf<uint32_t> d_tok_len;
+    DevBuf<unsigned long long> span_bytes, d_single_tok, d_boff;
     // host scratch
     std::vector<uint8_t> mask, bytes;
     std::vector<SingleChunk> singles, piece_singles;
@@ -503,6 +602,8 @@ struct EncCall {
     const uint64_t *doc_off;
     uint64_t n_docs;
     uint64_t *doc_tok_off_out;
+    // the _byteoff calls: cap + 1 byte offsets, where tokens_out lives (NULL: none are computed)
+    uint64_t *tok_byte_off_out;
 };
 
 // what the batch calls add: the documents as chunk ranges (the endmask call has them in EncCall) and the pack step
@@ -561,6 +662,11 @@ int piece_upload(mbpe_encoder *e, const EncCall &a, Piece p, PieceRun *r) {
     }
     if (!e->piece_singles.empty()) {
         rc = e->d_singles.reserve(e->piece_singles.size() * sizeof(SingleChunk), e->mem);
+        if (rc == MBPE_OK && a.tok_byte_off_out) rc = e->d_single_tok.reserve(e->piece_singles.size() * 8, e->mem);
+        if (rc != MBPE_OK) return rc;
+    }
+    if (a.tok_byte_off_out) {
+        rc = e->span_bytes.reserve(n_spans0 * 8, e->mem);
         if (rc != MBPE_OK) return rc;
     }
     r->d_text = a.text + base;
@@ -638,16 +744,21 @@ int piece_finish(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, Piec
     const int cur = r->cur;
     r->too_small = a.tokens_out && a.cap < done + n;
     const bool with_docs = a.doc_off && !r->too_small;
-    const bool with_ends = (a.chunk_tok_off_out || a.doc_off) && !r->too_small;
+    const bool with_boff = a.tok_byte_off_out && a.tokens_out && !r->too_small && n;
+    // (the one-token chunks of the piece: each needs its index in the final stream, which the chunk ends give)
+    const uint64_t n_patch = with_boff ? e->piece_singles.size() : 0;
+    const bool mask_ends = a.mask_dev != nullptr;         // the chunks are the caller's mask's: counted on the device
+    const bool with_ends = (a.chunk_tok_off_out || a.doc_off || n_patch) && !r->too_small;
     const bool with_tokens = a.tokens_out && !r->too_small;
     int rc = MBPE_OK;
+    if (with_boff && !a.out_on_device && (rc = e->d_boff.reserve((n + 1) * 8, e->mem)) != MBPE_OK) return rc;
     uint64_t n_ends = 0;
     unsigned long long *d_ends = nullptr;
     if (n && (with_ends || with_tokens)) {
         const uint64_t n_spans = span_count(n);
         const dim3 grid(span_grid(n));
         if (with_ends) {
-            if (with_docs) {
+            if (mask_ends) {
                 // the chunks are the mask's: their number comes from the device, ahead of the finishing kernel
                 hipLaunchKernelGGL(k_enc_end_count, grid, dim3(kSpanThreads), 0, e->stream, e->tok[cur], n, e->span_a);
                 hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans,
@@ -666,7 +777,7 @@ int piece_finish(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, Piec
                 if (rc != MBPE_OK) return rc;
                 d_ends = e->d_ends;
             }
-            if (!with_docs) {
+            if (!mask_ends) {
                 hipLaunchKernelGGL(k_enc_end_count, grid, dim3(kSpanThreads), 0, e->stream, e->tok[cur], n, e->span_a);
                 hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans,
                                    e->span_off, e->d_res);
@@ -703,10 +814,34 @@ int piece_finish(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, Piec
                                e->d_doc_pos, a.n_docs + 1, mask32, pn, e->span_off, n_blocks, e->d_res, d_ends, n_ends,
                                e->d_doc_off);
         }
+        if (with_boff) {
+            const LenTab tab = {e->d_tok_len, (uint32_t)e->len.size()};
+            const LenPatch pt = {e->d_single_tok, e->d_singles, n_patch};
+            if (n_patch) {
+                // the rank of every single's start in the mask (its total apart from the ends': d_res[2]), then the
+                // look-up in the chunk ends; span_a and span_off are free again, as above
+                const uint64_t n_words = (pn + 31) / 32, n_blocks = (n_words + kMaskBlockWords - 1) / kMaskBlockWords;
+                const uint32_t *mask32 = reinterpret_cast<const uint32_t *>(mask_ends ? a.mask_dev : e->d_mask.get());
+                hipLaunchKernelGGL(k_enc_mask_count, dim3((uint32_t)((n_blocks * kWave + 255) / 256)), dim3(256), 0,
+                                   e->stream, mask32, n_words, n_blocks, e->span_a);
+                hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_blocks,
+                                   e->span_off, e->d_res + 2);
+                hipLaunchKernelGGL(k_enc_single_tok, dim3((uint32_t)((n_patch + 255) / 256)), dim3(256), 0, e->stream,
+                                   e->d_singles, n_patch, mask32, pn, e->span_off, n_blocks, e->d_res + 2, d_ends, n_ends,
+                                   done, e->d_single_tok);
+            }
+            unsigned long long *boff = a.out_on_device ? reinterpret_cast<unsigned long long *>(a.tok_byte_off_out) + done
+                                                       : e->d_boff.get();
+            hipLaunchKernelGGL(k_enc_len_sum, grid, dim3(kSpanThreads), 0, e->stream, e->tok[cur], n, tab, pt,
+                               e->span_bytes);
+            hipLaunchKernelGGL(k_enc_scan_sum64, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_bytes, n_spans);
+            hipLaunchKernelGGL(k_enc_len_write, grid, dim3(kSpanThreads), 0, e->stream, e->tok[cur], n, tab, pt,
+                               e->span_bytes, a.chunk_off[p.c0], boff);
+        }
     }
     ECHK(hipEventRecord(e->ev1, e->stream));
     unsigned long long ends_found = 0;
-    if (with_ends && !with_docs && n) ECHK(hipMemcpyAsync(&ends_found, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
+    if (with_ends && !mask_ends && n) ECHK(hipMemcpyAsync(&ends_found, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
     float ms = 0.f;
     if ((rc = e->wait(&ms)) != MBPE_OK) return rc;
     e->last_ms += ms;
@@ -715,13 +850,18 @@ int piece_finish(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, Piec
                             hipMemcpyDeviceToHost, e->stream));
         ECHK(hipStreamSynchronize(e->stream));
     }
+    if (with_boff && !a.out_on_device) {
+        ECHK(hipMemcpyAsync(a.tok_byte_off_out + done, e->d_boff, (n + 1) * 8, hipMemcpyDeviceToHost, e->stream));
+        ECHK(hipStreamSynchronize(e->stream));
+    }
     if (with_docs) {
         if (a.doc_tok_off_out) {
             ECHK(hipMemcpyAsync(a.doc_tok_off_out, e->d_doc_off, (a.n_docs + 1) * 8, hipMemcpyDeviceToHost, e->stream));
             ECHK(hipStreamSynchronize(e->stream));
         }
-    } else if (with_ends) {
+    } else if (with_ends && !mask_ends) {
         if (ends_found != n_ends) return fail(MBPE_ERR_HIP, "mbpe_encoder_encode: chunk ends and chunks differ in number");
+        if (!a.chunk_tok_off_out) return MBPE_OK;          // (the ends served the byte offsets of one-token chunks only)
         e->list.resize(n_ends);
         if (n_ends) {
             ECHK(hipMemcpyAsync(e->list.data(), d_ends, n_ends * 8, hipMemcpyDeviceToHost, e->stream));
@@ -761,22 +901,53 @@ int run_pieces(mbpe_encoder *e, EncCall a, const std::vector<Piece> &pieces, Pie
         if (rc != MBPE_OK) return rc;
         sum->n += r.n;
         sum->passes = std::max(sum->passes, r.passes);
-        if (r.too_small) { sum->too_small = true; a.tokens_out = nullptr; a.chunk_tok_off_out = nullptr; }
+        if (r.too_small) { sum->too_small = true; a.tokens_out = nullptr; a.chunk_tok_off_out = nullptr; a.tok_byte_off_out = nullptr; }
     }
     return MBPE_OK;
 }
 
 // the bytes one piece may hold: the option, else what the buffers hold already, else from the free device memory
-int piece_limit(mbpe_encoder *e, uint64_t n_bytes, uint64_t *limit) {
+// (boff_host: byte offsets that go to the host are staged on the device, 8 bytes per token)
+int piece_limit(mbpe_encoder *e, uint64_t n_bytes, bool boff_host, uint64_t *limit) {
     *limit = e->piece_bytes;
     if (*limit) return MBPE_OK;
     *limit = e->cand.bytes() / 4;                                 // what the buffers hold already needs no question
     if (n_bytes > *limit) {
         size_t free_b = 0, total_b = 0;
         ECHK(hipMemGetInfo(&free_b, &total_b));
-        const uint64_t avail = (uint64_t)free_b + enc_held(e);
-        *limit = std::max<uint64_t>((avail - avail / 16) / kPieceCost, *limit);
+        const uint64_t avail = (uint64_t)free_b + enc_held(e) + (boff_host ? e->d_boff.bytes() : 0);
+        *limit = std::max<uint64_t>((avail - avail / 16) / (kPieceCost + (boff_host ? kPieceCostByteOff : 0)), *limit);
     }
+    return MBPE_OK;
+}
+
+// what a _byteoff call settles before its pieces run: len[] on the device from the first such call on, and the [0] = 0
+// of an empty text (a query computes no offsets: the entry points have dropped the pointer)
+int boff_begin(mbpe_encoder *e, const EncCall &a) {
+    if (!a.tok_byte_off_out) return MBPE_OK;
+    ECHK(hipSetDevice(e->device));
+    if (!e->d_tok_len) {
+        const int rc = e->d_tok_len.reserve(e->len.size() * 4, e->mem);
+        if (rc != MBPE_OK) return rc;
+        ECHK(hipMemcpyAsync(e->d_tok_len, e->len.data(), e->len.size() * 4, hipMemcpyHostToDevice, e->stream));
+        ECHK(hipStreamSynchronize(e->stream));
+    }
+    if (a.n_bytes == 0) {
+        if (!a.out_on_device) { a.tok_byte_off_out[0] = 0; return MBPE_OK; }
+        ECHK(hipMemsetAsync(a.tok_byte_off_out, 0, 8, e->stream));
+        ECHK(hipStreamSynchronize(e->stream));
+    }
+    return MBPE_OK;
+}
+
+// the checks of a _byteoff call that need no device; drops the pointer of a query
+int boff_check(const mbpe_encoder *e, const std::string &who, EncCall *a) {
+    if (!a->tokens_out) a->tok_byte_off_out = nullptr;
+    if (!a->tok_byte_off_out) return MBPE_OK;
+    if (!e->len_error.empty())
+        return fail(MBPE_ERR_ARG, who + ": token byte offsets need a table mbpe_merges_check accepts (" + e->len_error + ")");
+    if (a->out_on_device && ((uintptr_t)a->tok_byte_off_out & 7))
+        return fail(MBPE_ERR_ARG, who + ": tok_byte_off_out must be 8-byte aligned");
     return MBPE_OK;
 }
 
@@ -796,15 +967,16 @@ int enc_run_body(mbpe_encoder *e, EncCall a) {
     if (n_bytes == 0) {
         if (a.chunk_tok_off_out)
             for (uint64_t c = 0; c < n_chunks; ++c) a.chunk_tok_off_out[c + 1] = 0;
-        return MBPE_OK;
+        return boff_begin(e, a);
     }
     ECHK(hipSetDevice(e->device));
+    if (int rc0 = boff_begin(e, a)) return rc0;
     e->last_ms = 0.f;
     e->pass_tokens.clear();
 
     // pieces: whole chunks, at most `limit` bytes each
     uint64_t limit = 0;
-    int rc = piece_limit(e, n_bytes, &limit);
+    int rc = piece_limit(e, n_bytes, a.tok_byte_off_out && !a.out_on_device, &limit);
     if (rc != MBPE_OK) return rc;
     std::vector<Piece> pieces;
     if (n_bytes <= limit) {
@@ -850,6 +1022,7 @@ int enc_run_body(mbpe_encoder *e, EncCall a) {
         EncCall q = a;
         q.tokens_out = nullptr;
         q.chunk_tok_off_out = nullptr;
+        q.tok_byte_off_out = nullptr;
         rc = run_pieces(e, q, pieces, &sum);
         if (rc != MBPE_OK) return rc;
         if (a.cap < sum.n) {
@@ -975,6 +1148,7 @@ int enc_endmask_body(mbpe_encoder *e, EncCall a) {
     ECHK(hipSetDevice(e->device));
     e->last_ms = 0.f;
     e->pass_tokens.clear();
+    if (int rc0 = boff_begin(e, a)) return rc0;
     if (n_bytes == 0) {
         if (a.doc_off) {
             int rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
@@ -986,7 +1160,7 @@ int enc_endmask_body(mbpe_encoder *e, EncCall a) {
         return MBPE_OK;
     }
     uint64_t limit = 0;                                           // the rule of mbpe_encoder_encode
-    int rc = piece_limit(e, n_bytes, &limit);
+    int rc = piece_limit(e, n_bytes, a.tok_byte_off_out && !a.out_on_device, &limit);
     if (rc != MBPE_OK) return rc;
     if (n_bytes > limit)
         return fail(MBPE_ERR_OOM, "mbpe_encoder_encode_endmask: the text has " + std::to_string(n_bytes) +
@@ -1079,11 +1253,27 @@ int mbpe_encoder_create(int device_id, const uint32_t *merges, uint32_t n_merges
     mbpe_encoder *e = new (std::nothrow) mbpe_encoder;
     if (!e) return fail(MBPE_ERR_OOM, "mbpe_encoder_create: host allocation failed");
     e->n_merges = n_merges;
+    // len[id], for the byte offsets: only a trained table makes the bytes a token covers a function of its id
+    if (mbpe_merges_check(merges, n_merges) != MBPE_OK) {
+        e->len_error = mbpe_host::last_error();
+    } else {
+        try {
+            e->len.assign(256 + (size_t)n_merges, 1u);
+        } catch (const std::bad_alloc &) {
+            delete e;
+            return fail(MBPE_ERR_OOM, "mbpe_encoder_create: host allocation failed");
+        }
+        for (uint32_t k = 0; k < n_merges && e->len_error.empty(); ++k) {
+            const uint64_t l = (uint64_t)e->len[merges[2 * k]] + e->len[merges[2 * k + 1]];
+            if (l > 0xFFFFFFFFull) e->len_error = "token " + std::to_string(256 + k) + " is longer than 2^32 - 1 bytes";
+            e->len[256 + k] = (uint32_t)l;
+        }
+    }
     auto build = [&]() -> int {
         int rc = e->open(device_id);
         if (rc == MBPE_OK) rc = e->d_keys.reserve((uint64_t)capacity * 8, e->mem);
         if (rc == MBPE_OK) rc = e->d_vals.reserve((uint64_t)capacity * 4, e->mem);
-        if (rc == MBPE_OK) rc = e->d_res.reserve(16, e->mem);
+        if (rc == MBPE_OK) rc = e->d_res.reserve(24, e->mem);
         if (rc != MBPE_OK) return rc;
         ECHK(hipMemcpyAsync(e->d_keys, keys.data(), (size_t)capacity * 8, hipMemcpyHostToDevice, e->stream));
         ECHK(hipMemcpyAsync(e->d_vals, vals.data(), (size_t)capacity * 4, hipMemcpyHostToDevice, e->stream));
@@ -1123,17 +1313,28 @@ int mbpe_encoder_set_option(mbpe_encoder *e, const char *name, int64_t value) {
     return fail(MBPE_ERR_ARG, std::string("mbpe_encoder_set_option: no option \"") + name + "\"");
 }
 
-int mbpe_encoder_encode(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
-                        const uint64_t *chunk_off, uint64_t n_chunks, void *tokens_out, uint64_t cap,
-                        uint32_t token_bits, int out_on_device, uint64_t *chunk_tok_off_out, uint64_t *n_out,
-                        uint32_t *n_passes_out) {
+int mbpe_encoder_encode_byteoff(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                const uint64_t *chunk_off, uint64_t n_chunks, void *tokens_out, uint64_t cap,
+                                uint32_t token_bits, int out_on_device, uint64_t *tok_byte_off_out,
+                                uint64_t *chunk_tok_off_out, uint64_t *n_out, uint32_t *n_passes_out) {
     if (n_out) *n_out = 0;
     if (n_passes_out) *n_passes_out = 0;
     if (!e || !n_out || (!text && n_bytes)) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode: NULL argument");
     if (token_bits != 16 && token_bits != 32) return fail(MBPE_ERR_ARG, "token_bits must be 16 or 32");
-    const EncCall a = {text, n_bytes, text_on_device, chunk_off, n_chunks, tokens_out, cap, token_bits, out_on_device,
-                       chunk_tok_off_out, n_out, n_passes_out};
+    EncCall a = {text, n_bytes, text_on_device, chunk_off, n_chunks, tokens_out, cap, token_bits, out_on_device,
+                 chunk_tok_off_out, n_out, n_passes_out};
+    a.tok_byte_off_out = tok_byte_off_out;
+    const int rc = boff_check(e, "mbpe_encoder_encode_byteoff", &a);
+    if (rc != MBPE_OK) return rc;
     return enc_guard("mbpe_encoder_encode", [&] { return enc_run_body(e, a); });
+}
+
+int mbpe_encoder_encode(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                        const uint64_t *chunk_off, uint64_t n_chunks, void *tokens_out, uint64_t cap,
+                        uint32_t token_bits, int out_on_device, uint64_t *chunk_tok_off_out, uint64_t *n_out,
+                        uint32_t *n_passes_out) {
+    return mbpe_encoder_encode_byteoff(e, text, n_bytes, text_on_device, chunk_off, n_chunks, tokens_out, cap, token_bits,
+                                       out_on_device, nullptr, chunk_tok_off_out, n_out, n_passes_out);
 }
 
 // mbpe_encoder_encode_batch (aux NULL) and mbpe_encoder_encode_batch_aux: the checks that need no device, then the call
@@ -1185,6 +1386,16 @@ int mbpe_encoder_encode_endmask(mbpe_encoder *e, const uint8_t *text_dev, uint64
                                 const mbpe_single *singles, uint64_t n_singles, const uint64_t *doc_off, uint64_t n_docs,
                                 void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device,
                                 uint64_t *doc_tok_off_out, uint64_t *n_out, uint32_t *n_passes_out) {
+    return mbpe_encoder_encode_endmask_byteoff(e, text_dev, n_bytes, endmask_dev, singles, n_singles, doc_off, n_docs,
+                                               tokens_out, cap, token_bits, out_on_device, nullptr, doc_tok_off_out, n_out,
+                                               n_passes_out);
+}
+
+int mbpe_encoder_encode_endmask_byteoff(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
+                                        const uint8_t *endmask_dev, const mbpe_single *singles, uint64_t n_singles,
+                                        const uint64_t *doc_off, uint64_t n_docs, void *tokens_out, uint64_t cap,
+                                        uint32_t token_bits, int out_on_device, uint64_t *tok_byte_off_out,
+                                        uint64_t *doc_tok_off_out, uint64_t *n_out, uint32_t *n_passes_out) {
     static_assert(sizeof(mbpe_single) == sizeof(SingleChunk), "mbpe.h and k_enc_single");
     if (n_out) *n_out = 0;
     if (n_passes_out) *n_passes_out = 0;
@@ -1195,9 +1406,11 @@ int mbpe_encoder_encode_endmask(mbpe_encoder *e, const uint8_t *text_dev, uint64
     if ((uintptr_t)endmask_dev & 3) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_endmask: the mask must be 4-byte aligned");
     if (token_bits == 16 && 256ull + e->n_merges > 65536ull)
         return fail(MBPE_ERR_VOCAB, "token_bits 16 with more than 65,536 token ids");
-    const EncCall a = {text_dev, n_bytes, 1, nullptr, 0, tokens_out, cap, token_bits, out_on_device, nullptr, n_out,
-                       n_passes_out, true, endmask_dev, singles, n_singles, n_docs ? doc_off : nullptr, n_docs,
-                       doc_tok_off_out};
+    EncCall a = {text_dev, n_bytes, 1, nullptr, 0, tokens_out, cap, token_bits, out_on_device, nullptr, n_out,
+                 n_passes_out, true, endmask_dev, singles, n_singles, n_docs ? doc_off : nullptr, n_docs,
+                 doc_tok_off_out, tok_byte_off_out};
+    rc = boff_check(e, "mbpe_encoder_encode_endmask_byteoff", &a);
+    if (rc != MBPE_OK) return rc;
     return enc_guard("mbpe_encoder_encode_endmask", [&] { return enc_endmask_body(e, a); });
 }
 

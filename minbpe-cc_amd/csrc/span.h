@@ -78,6 +78,42 @@ MBPE_HD SpanSum span_fold_slice(const uint32_t *span_sum, uint64_t lo, uint64_t 
     return acc;
 }
 
+// ---- 64-bit sums over the spans: pure arithmetic (token byte offsets: a span's bytes, not its tokens) ------------
+// the sum of cnt[lo .. hi)
+MBPE_HD unsigned long long span_sum_slice64(const unsigned long long *cnt, uint64_t lo, uint64_t hi) {
+    unsigned long long s = 0;
+    for (uint64_t i = lo; i < hi; ++i) s += cnt[i];
+    return s;
+}
+
+// off[i] = start + cnt[lo] + .. + cnt[i - 1] for i in [lo, hi); returns start + the slice's sum.  off may be cnt
+MBPE_HD unsigned long long span_offsets_slice64(const unsigned long long *cnt, unsigned long long *off, uint64_t lo,
+                                                uint64_t hi, unsigned long long start) {
+    for (uint64_t i = lo; i < hi; ++i) {
+        const unsigned long long v = cnt[i];
+        off[i] = start;
+        start += v;
+    }
+    return start;
+}
+
+// the slice of spans scan thread t owns: [*lo, *hi)
+MBPE_HD void span_scan_slice(uint64_t n_spans, uint32_t t, uint64_t *lo, uint64_t *hi) {
+    const uint64_t per = (n_spans + kScanThreads - 1) / kScanThreads;
+    *lo = per * t < n_spans ? per * t : n_spans;
+    *hi = *lo + per < n_spans ? *lo + per : n_spans;
+}
+
+// the first index in idx[0 .. n) (ascending) whose value is not below v
+MBPE_HD uint64_t lower_bound64(const unsigned long long *idx, uint64_t n, unsigned long long v) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (idx[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 #ifdef __HIPCC__
 // ---- wave helpers ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (kWave - 1); }
@@ -145,6 +181,31 @@ __device__ __forceinline__ unsigned long long span_scan_sum(const uint32_t *__re
     s = sh[threadIdx.x];
     for (uint64_t i = lo; i < hi; ++i) { off[i] = s; s += cnt[i]; }
     return total;
+}
+
+// the same for 64-bit counts, in place: cnt[s] becomes cnt[0] + .. + cnt[s - 1]; returns the total in thread 0
+__device__ __forceinline__ unsigned long long span_scan_sum64(unsigned long long *cnt, uint64_t n_spans,
+                                                              unsigned long long *sh) {
+    uint64_t lo, hi;
+    span_scan_slice(n_spans, threadIdx.x, &lo, &hi);
+    unsigned long long total = 0;
+    sh[threadIdx.x] = span_sum_slice64(cnt, lo, hi);
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int t = 0; t < kScanThreads; ++t) { const unsigned long long v = sh[t]; sh[t] = total; total += v; }
+    __syncthreads();
+    span_offsets_slice64(cnt, cnt, lo, hi, sh[threadIdx.x]);
+    return total;
+}
+
+// inclusive prefix sum of v over the wave's lanes
+__device__ __forceinline__ unsigned long long wave_prefix64(unsigned long long v, uint32_t lane) {
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const unsigned long long u = __shfl_up(v, d, kWave);
+        if (lane >= (uint32_t)d) v += u;
+    }
+    return v;
 }
 
 // ---- compaction: the values of val[0 .. n) that are not kTokNone, in order, to out; span_off from span_scan_sum --

@@ -74,6 +74,9 @@ void usage() {
                  "  --rank-order                When encoding, apply the merges in rank order (a chunk's pair with the lowest\n"
                  "                              merge id first: the segmentation the model was trained on) instead of the\n"
                  "                              reference's greedy passes; on the host and with --device-encode\n"
+                 "  --byte-ranges-out TEXT      When encoding, also write one line \"start end\" per token to this file: the bytes\n"
+                 "                              of the input the token stands for (a special token: its name's occurrence);\n"
+                 "                              on the host, with --device-encode, --device-split and --rank-order alike\n"
                  "  --continue-from TEXT        With --train: load this model and continue its training on the input up to\n"
                  "                              --vocab-size, which must not be below the model's size; the result goes to\n"
                  "                              --model-path.  The loaded model's split pattern is used: --encoder has no\n"
@@ -85,7 +88,8 @@ void usage() {
 }  // namespace
 
 int main(int argc, char *argv[]) {
-    std::string input_path, output_path, special_token_path, encoder = "gpt4", model_path = "./output.model", continue_from;
+    std::string input_path, output_path, special_token_path, encoder = "gpt4", model_path = "./output.model", continue_from,
+                byte_ranges_path;
     std::string conflict_resolution_str = "first";
     bool train = false, decode = false, encode = false, write_vocab = false, verbose = false, device_encode = false,
          device_decode = false, device_split = false, split_unicode = false, rank_order = false;
@@ -111,6 +115,7 @@ int main(int argc, char *argv[]) {
         else if (arg == "-m" || arg == "--model-path") { if (!value(&model_path)) return 106; }
         else if (arg == "--encoder") { if (!value(&encoder)) return 106; }
         else if (arg == "--continue-from") { if (!value(&continue_from)) return 106; }
+        else if (arg == "--byte-ranges-out") { if (!value(&byte_ranges_path)) return 106; }
         else if (arg == "--vocab-size") {
             if (!value(&tmp)) return 106;
             try { vocab_size = std::stoi(tmp); } catch (...) { std::cerr << "--vocab-size: invalid integer " << tmp << "\n"; return 104; }
@@ -211,7 +216,11 @@ int main(int argc, char *argv[]) {
             if (device_encode && device_split) mbpe_tok_set_encode_split(rt, 1);
             if (rank_order) mbpe_tok_set_encode_order(rt, 1);
             if (split_unicode) mbpe_tok_set_split_unicode(rt, 1);
-            const int erc = device_encode
+            std::vector<uint64_t> ranges(byte_ranges_path.empty() ? 0 : 2 * encoded.size());
+            const int erc = !byte_ranges_path.empty()
+                                ? mbpe_tok_encode_byteoff(rt, in, input.size(), verbose, device_encode ? device : -1,
+                                                          encoded.data(), ranges.data(), encoded.size(), &n)
+                            : device_encode
                                 ? mbpe_tok_encode_device(rt, in, input.size(), verbose, device, encoded.data(), encoded.size(), &n)
                                 : mbpe_tok_encode(rt, in, input.size(), verbose, encoded.data(), encoded.size(), &n);
             if (erc != MBPE_OK) {
@@ -222,6 +231,11 @@ int main(int argc, char *argv[]) {
                 std::cout << "Writing " << encoded.size() << " encoded tokens\n";
                 if (save_encoding(output_path, encoded, &err)) std::cout << "Success\n";
                 else std::cerr << "Failed with error: " << err << "\n";
+                if (!byte_ranges_path.empty()) {
+                    std::ofstream rf(byte_ranges_path);
+                    for (uint64_t j = 0; j < n; ++j) rf << ranges[2 * j] << ' ' << ranges[2 * j + 1] << '\n';
+                    if (!rf) { std::cerr << "Failed to write " << byte_ranges_path << "\n"; rc = -1; }
+                }
             }
         } else {
             std::cerr << "Failed with error: " << err << "\n";

@@ -261,8 +261,10 @@ void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTI
 // :605-650.  Same result as the reference's rescan-from-the-cursor loop, computed in one sweep: every occurrence of
 // every special token is listed once, sorted by (position, token order), and an occurrence is taken when it starts
 // at or after the end of the previous one taken.  A taken token becomes the marker "\0<id>" (:635-637).
-std::vector<std::string> Tokenizer::split_on_special(const std::string &text) const {
+std::vector<std::string> Tokenizer::split_on_special(const std::string &text, std::vector<uint64_t> *origin) const {
     std::vector<std::string> parts;
+    // origin (optional): per part its [start, end) in text -- of a marker, the occurrence of the name it replaces
+    auto from = [&](size_t s, size_t e) { if (origin) { origin->push_back(s); origin->push_back(e); } };
     struct Occ { size_t pos; size_t tok; };
     std::vector<Occ> occ;
     for (size_t k = 0; k < special_tokens_.size(); ++k) {
@@ -274,12 +276,13 @@ std::vector<std::string> Tokenizer::split_on_special(const std::string &text) co
     size_t cursor = 0;
     for (const Occ &o : occ) {
         if (o.pos < cursor) continue;                      // inside a token already taken
-        if (o.pos > cursor) parts.push_back(text.substr(cursor, o.pos - cursor));
+        if (o.pos > cursor) { parts.push_back(text.substr(cursor, o.pos - cursor)); from(cursor, o.pos); }
         parts.push_back(std::string(1, '\0') + std::to_string(special_tokens_[o.tok].second));
         cursor = o.pos + special_tokens_[o.tok].first.size();
+        from(o.pos, cursor);
     }
-    if (cursor < text.size()) parts.push_back(text.substr(cursor));
-    if (parts.empty()) parts.push_back(text);
+    if (cursor < text.size()) { parts.push_back(text.substr(cursor)); from(cursor, text.size()); }
+    if (parts.empty()) { parts.push_back(text); from(0, text.size()); }
     return parts;
 }
 
@@ -336,8 +339,10 @@ std::vector<Token> Tokenizer::encode_rank_ordered(std::vector<Token> text) const
     }
 }
 
-void Tokenizer::append_chunks(const std::string &text, bool verbose, std::string *buf, std::vector<uint64_t> *off) const {
-    auto split_text = split_on_special(text);
+void Tokenizer::append_chunks(const std::string &text, bool verbose, std::string *buf, std::vector<uint64_t> *off,
+                              std::vector<uint64_t> *src) const {
+    std::vector<uint64_t> origin;
+    auto split_text = split_on_special(text, src ? &origin : nullptr);
     if (verbose) {
         std::cout << "Splitting input text into " << split_text.size() << " parts\n";
         for (const auto &part : split_text) {
@@ -345,7 +350,8 @@ void Tokenizer::append_chunks(const std::string &text, bool verbose, std::string
             std::cout << "Part: \"" << part << "\" special: " << is_special << "\n";
         }
     }
-    for (const auto &part : split_text) {
+    for (size_t k = 0; k < split_text.size(); ++k) {
+        const std::string &part = split_text[k];
         if (splitter_.has_pattern() && !(part.size() > 0 && part[0] == '\0')) {
             std::vector<uint64_t> starts, ends;
             std::string err;
@@ -355,10 +361,12 @@ void Tokenizer::append_chunks(const std::string &text, bool verbose, std::string
             for (size_t i = 0; i < starts.size(); ++i) {
                 buf->append(part, starts[i], ends[i] - starts[i]);
                 off->push_back(buf->size());
+                if (src) { src->push_back(origin[2 * k] + starts[i]); src->push_back(origin[2 * k] + ends[i]); }
             }
         } else {
             *buf += part;
             off->push_back(buf->size());
+            if (src) { src->push_back(origin[2 * k]); src->push_back(origin[2 * k + 1]); }
         }
     }
 }
@@ -469,7 +477,8 @@ std::vector<Token> Tokenizer::encode(const std::string &text, bool verbose, int 
 }
 
 void Tokenizer::batch_chunks(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, std::string *buf,
-                             std::vector<uint64_t> *off, std::vector<uint64_t> *first_chunk) const {
+                             std::vector<uint64_t> *off, std::vector<uint64_t> *first_chunk,
+                             std::vector<uint64_t> *src) const {
     // every text is split on its own (a chunk never spans two texts)
     off->assign(1, 0);
     first_chunk->assign(n_docs + 1, 0);
@@ -477,7 +486,7 @@ void Tokenizer::batch_chunks(const char *text, const uint64_t *doc_off, uint64_t
     for (uint64_t i = 0; i < n_docs; ++i) {
         (*first_chunk)[i] = off->size() - 1;
         if (doc_off[i + 1] > doc_off[i])                          // (an empty text has no chunk: an empty result)
-            append_chunks(std::string(text + doc_off[i], doc_off[i + 1] - doc_off[i]), verbose, buf, off);
+            append_chunks(std::string(text + doc_off[i], doc_off[i + 1] - doc_off[i]), verbose, buf, off, src);
     }
     (*first_chunk)[n_docs] = off->size() - 1;
 }
@@ -511,6 +520,80 @@ int Tokenizer::encode_batch_flat(const char *text, const uint64_t *doc_off, uint
     doc_tok_off->resize(n_docs + 1);
     for (uint64_t i = 0; i <= n_docs; ++i) (*doc_tok_off)[i] = chunk_tok_off[first_chunk[i]];
     if (verbose) std::cout << "Encoded " << n_docs << " texts (length " << buf.size() << ") to " << *n_out << " tokens\n";
+    return MBPE_OK;
+}
+
+int Tokenizer::encode_ranges(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
+                             bool device_split, std::vector<Token> *tokens, std::vector<uint64_t> *ranges,
+                             std::vector<uint64_t> *doc_tok_off) {
+    tokens->clear();
+    ranges->clear();
+    doc_tok_off->assign(n_docs + 1, 0);
+    uint64_t n = 0;
+    if (device >= 0 && device_split) {
+        // the splitter's text is the original text: tok_byte_off is in the coordinates of the documents' buffer
+        DeviceSplit ds;
+        int rc = split_on_device(text, doc_off, n_docs, verbose, device, &ds);
+        if (rc != MBPE_OK) return rc;
+        mbpe_encoder *enc = device_encoder(device);
+        tokens->resize(std::max<uint64_t>(ds.n_bytes, 1));
+        std::vector<uint64_t> boff(tokens->size() + 1, 0);
+        rc = mbpe_encoder_encode_endmask_byteoff(enc, ds.d_text, ds.n_bytes, ds.d_mask, ds.singles.data(),
+                                                 ds.singles.size(), ds.doc_off.data(), n_docs, tokens->data(), tokens->size(),
+                                                 32, 0, boff.data(), doc_tok_off->data(), &n, nullptr);
+        if (rc != MBPE_OK) return rc;
+        tokens->resize(n);
+        ranges->resize(2 * n);
+        for (uint64_t d = 0; d < n_docs; ++d)
+            for (uint64_t j = (*doc_tok_off)[d]; j < (*doc_tok_off)[d + 1]; ++j) {
+                (*ranges)[2 * j] = boff[j] - ds.doc_off[d];
+                (*ranges)[2 * j + 1] = boff[j + 1] - ds.doc_off[d];
+            }
+        return MBPE_OK;
+    }
+    // the host split: the encoder reads markers and matches, so every chunk carries its range in its own document
+    std::string buf;
+    std::vector<uint64_t> off, first_chunk, src, boff;
+    batch_chunks(text, doc_off, n_docs, verbose, &buf, &off, &first_chunk, &src);
+    const uint64_t n_chunks = off.size() - 1;
+    std::vector<uint64_t> chunk_tok(n_chunks + 1, 0);
+    if (device >= 0) {
+        mbpe_encoder *enc = device_encoder(device);
+        tokens->resize(std::max<uint64_t>(buf.size(), 1));
+        boff.assign(tokens->size() + 1, 0);
+        const int rc = mbpe_encoder_encode_byteoff(enc, reinterpret_cast<const uint8_t *>(buf.data()), buf.size(), 0,
+                                                   off.data(), n_chunks, tokens->data(), tokens->size(), 32, 0, boff.data(),
+                                                   chunk_tok.data(), &n, nullptr);
+        if (rc != MBPE_OK) return rc;
+        tokens->resize(n);
+    } else {
+        // the reference loop; a token covers as many bytes as its vocabulary entry has
+        for (uint64_t c = 0; c < n_chunks; ++c) {
+            auto vec = text_to_vector(buf.data() + off[c], off[c + 1] - off[c]);
+            auto enc = rank_order_ ? encode_rank_ordered(std::move(vec)) : internal_internal_encode(std::move(vec));
+            uint64_t pos = off[c];
+            for (Token t : enc) {
+                tokens->push_back(t);
+                boff.push_back(pos);
+                pos += t < vocab_.size() ? vocab_[t].size() : 0;
+            }
+            chunk_tok[c + 1] = tokens->size();
+        }
+        boff.push_back(buf.size());
+        n = tokens->size();
+    }
+    // within a chunk the offsets move from the buffer to the chunk's source; its first token starts where the source
+    // starts and its last one ends where it ends (a marker's one token is the whole occurrence of the name)
+    ranges->resize(2 * n);
+    for (uint64_t c = 0; c < n_chunks; ++c) {
+        const uint64_t t0 = chunk_tok[c], t1 = chunk_tok[c + 1];
+        for (uint64_t j = t0; j < t1; ++j) {
+            (*ranges)[2 * j] = j == t0 ? src[2 * c] : src[2 * c] + (boff[j] - off[c]);
+            (*ranges)[2 * j + 1] = j + 1 == t1 ? src[2 * c + 1] : src[2 * c] + (boff[j + 1] - off[c]);
+        }
+    }
+    for (uint64_t i = 0; i <= n_docs; ++i) (*doc_tok_off)[i] = chunk_tok[first_chunk[i]];
+    if (verbose) std::cout << "Encoded " << n_docs << " texts (length " << buf.size() << ") to " << n << " tokens\n";
     return MBPE_OK;
 }
 
@@ -936,6 +1019,61 @@ int mbpe_tok_encode_batch_device(mbpe_tokenizer *t, const uint8_t *text, const u
         mbpe_host::set_last_error(e.what());
         return MBPE_ERR_ARG;
     }
+}
+
+// the two _byteoff calls after their checks: one encode_ranges, then what the caller has room for
+static int tok_encode_ranges(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off, uint64_t n_docs, int verbose,
+                             int device_id, uint32_t *tokens_out, uint64_t *ranges_out, uint64_t cap,
+                             uint64_t *doc_tok_off_out, uint64_t *n_out) {
+    try {
+        std::vector<mbpe_host::Token> tokens;
+        std::vector<uint64_t> ranges, tok_off;
+        const int rc = t->t->encode_ranges(reinterpret_cast<const char *>(text), doc_off, n_docs, verbose != 0, device_id,
+                                           device_id >= 0 && t->t->encode_split(), &tokens, &ranges, &tok_off);
+        if (rc != MBPE_OK) return rc;
+        *n_out = tokens.size();
+        if (doc_tok_off_out) doc_tok_off_out[0] = 0;
+        if (tokens_out && cap < tokens.size()) { mbpe_host::set_last_error("tokens_out too small"); return MBPE_ERR_ARG; }
+        if (doc_tok_off_out) memcpy(doc_tok_off_out, tok_off.data(), tok_off.size() * sizeof(uint64_t));
+        if (!tokens_out) return MBPE_OK;
+        if (!tokens.empty()) {
+            memcpy(tokens_out, tokens.data(), tokens.size() * sizeof(uint32_t));
+            memcpy(ranges_out, ranges.data(), ranges.size() * sizeof(uint64_t));
+        }
+        return MBPE_OK;
+    } catch (const mbpe_host::CodedError &e) {      // the encoder's or the splitter's own code
+        mbpe_host::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        mbpe_host::set_last_error(e.what());
+        return MBPE_ERR_ARG;
+    }
+}
+
+int mbpe_tok_encode_byteoff(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, int verbose, int device_id,
+                            uint32_t *tokens_out, uint64_t *ranges_out, uint64_t cap, uint64_t *n_out) {
+    if (n_out) *n_out = 0;
+    if (!t || !n_out || (!text && n) || (tokens_out && !ranges_out)) {
+        mbpe_host::set_last_error("mbpe_tok_encode_byteoff: NULL argument");
+        return MBPE_ERR_ARG;
+    }
+    const uint64_t doc_off[2] = {0, n};
+    return tok_encode_ranges(t, text, doc_off, 1, verbose, device_id, tokens_out, ranges_out, cap, nullptr, n_out);
+}
+
+int mbpe_tok_encode_batch_byteoff_device(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off, uint64_t n_docs,
+                                         int verbose, int device_id, uint32_t *tokens_out, uint64_t *ranges_out,
+                                         uint64_t cap, uint64_t *doc_tok_off_out, uint64_t *n_out) {
+    if (n_out) *n_out = 0;
+    if (!t || !n_out || !doc_off || device_id < 0 || (!text && doc_off[n_docs] > doc_off[0]) ||
+        (tokens_out && !ranges_out)) {
+        mbpe_host::set_last_error("mbpe_tok_encode_batch_byteoff_device: NULL argument or negative device");
+        return MBPE_ERR_ARG;
+    }
+    for (uint64_t i = 0; i < n_docs; ++i)
+        if (doc_off[i + 1] < doc_off[i]) { mbpe_host::set_last_error("doc_off must be ascending"); return MBPE_ERR_ARG; }
+    return tok_encode_ranges(t, text, doc_off, n_docs, verbose, device_id, tokens_out, ranges_out, cap, doc_tok_off_out,
+                             n_out);
 }
 
 int mbpe_tok_encode_batch_packed_device(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off, uint64_t n_docs,

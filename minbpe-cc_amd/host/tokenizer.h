@@ -54,6 +54,14 @@ public:
     int encode_batch_flat(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
                           Token *tokens_out, uint64_t cap, uint64_t *n_out, uint64_t *buf_bytes_out,
                           std::vector<uint64_t> *doc_tok_off, bool device_split = false);
+    // the same documents with every token's byte range: ranges[2j], ranges[2j + 1] = start and end of token j in its own
+    // document's original text (a special token: the occurrence of its name).  device < 0: the host loop, ranges from
+    // the vocabulary's entry lengths within each chunk; device >= 0: mbpe_encoder_encode_byteoff over the host split,
+    // whose chunks carry their source ranges, or -- device_split -- mbpe_encoder_encode_endmask_byteoff, whose offsets
+    // are in the documents' coordinates already.  The three agree token for token and range for range
+    int encode_ranges(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
+                      bool device_split, std::vector<Token> *tokens, std::vector<uint64_t> *ranges,
+                      std::vector<uint64_t> *doc_tok_off);
     // the same documents as one id matrix (mbpe_encoder_encode_batch; with aux, mbpe_encoder_encode_batch_aux): spec,
     // ids_out .. doc_tok_off_out go to it as they are, its code is returned
     int encode_batch_packed(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
@@ -101,7 +109,8 @@ private:
 
     std::vector<Token> text_to_vector(const char *s, size_t n) const;       // :85-100
     void initialize_vocab();                                                // :103-111
-    std::vector<std::string> split_on_special(const std::string &text) const;   // :605-650
+    // :605-650; origin (optional): per part its [start, end) in text, of a marker the occurrence it replaces
+    std::vector<std::string> split_on_special(const std::string &text, std::vector<uint64_t> *origin = nullptr) const;
     std::vector<Token> internal_internal_encode(std::vector<Token> text) const; // :325-367
     // the rank-ordered counterpart: of the adjacent pairs that are in merges_lookup, every occurrence of the one with
     // the smallest id is replaced, left to right and non-overlapping; repeated until no pair is left.  For a trained
@@ -112,10 +121,13 @@ private:
     void drop_encoder();                   // the merges changed (special tokens do not enter the lookup table)
     // the chunks of n_docs texts (every text split on its own) as one buffer + offsets; first_chunk[i] = text i's first
     void batch_chunks(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, std::string *buf,
-                      std::vector<uint64_t> *off, std::vector<uint64_t> *first_chunk) const;
+                      std::vector<uint64_t> *off, std::vector<uint64_t> *first_chunk,
+                      std::vector<uint64_t> *src = nullptr) const;
     // the chunks of one text appended to buf / off: special markers and, with a pattern, the regex matches of every
     // other part (:664-704); without one, every part is a chunk (:706-709)
-    void append_chunks(const std::string &text, bool verbose, std::string *buf, std::vector<uint64_t> *off) const;
+    // src (optional): per chunk its [start, end) in text -- the part's origin plus the match, or a marker's occurrence
+    void append_chunks(const std::string &text, bool verbose, std::string *buf, std::vector<uint64_t> *off,
+                       std::vector<uint64_t> *src = nullptr) const;
     mbpe_encoder *device_encoder(int device);
     void drop_splitter();
     mbpe_splitter *device_splitter(int device);       // kept until another device is named or the tokenizer goes

@@ -36,7 +36,8 @@ EXPORTS = [
     "mbpe_load_corpus_endmask", "mbpe_splitter_create", "mbpe_splitter_destroy", "mbpe_splitter_split",
     "mbpe_splitter_endmask", "mbpe_splitter_set_option", "mbpe_splitter_kernel_ms", "mbpe_splitter_alloc_count",
     "mbpe_splitter_host_spans", "mbpe_splitter_split_docs", "mbpe_splitter_ranges", "mbpe_splitter_find_ms",
-    "mbpe_encoder_encode_endmask", "mbpe_encoder_encode_batch_endmask", "mbpe_split_unicode_table",
+    "mbpe_encoder_encode_endmask", "mbpe_encoder_encode_batch_endmask", "mbpe_encoder_encode_byteoff",
+    "mbpe_encoder_encode_endmask_byteoff", "mbpe_split_unicode_table",
     "mbpe_merges_check", "mbpe_train_begin_from", "mbpe_train_from",
 ]
 # include/mbpe_tokenizer.h
@@ -46,7 +47,8 @@ TOK_EXPORTS = [
     "mbpe_tok_decode", "mbpe_tok_decode_device", "mbpe_tok_encode_batch_device", "mbpe_tok_decode_batch_device",
     "mbpe_tok_encode_batch_packed_device", "mbpe_tok_decode_padded_device", "mbpe_tok_encode_batch_aux_device",
     "mbpe_tok_train_split_device", "mbpe_tok_set_encode_split", "mbpe_tok_set_split_unicode",
-    "mbpe_tok_set_encode_order", "mbpe_tok_train_continue",
+    "mbpe_tok_set_encode_order", "mbpe_tok_train_continue", "mbpe_tok_encode_byteoff",
+    "mbpe_tok_encode_batch_byteoff_device",
 ]
 
 
@@ -229,6 +231,10 @@ def lib():
     L.mbpe_splitter_ranges.argtypes = [vp, vp, vp]
     L.mbpe_splitter_find_ms.argtypes = [vp, vp]
     L.mbpe_encoder_encode_endmask.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, u32, i32, vp, vp, vp]
+    L.mbpe_encoder_encode_endmask_byteoff.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, u32, i32, vp, vp, vp, vp]
+    L.mbpe_encoder_encode_byteoff.argtypes = [vp, vp, u64, i32, vp, u64, vp, u64, u32, i32, vp, vp, vp, vp]
+    L.mbpe_tok_encode_byteoff.argtypes = [vp, vp, u64, i32, i32, vp, vp, u64, vp]
+    L.mbpe_tok_encode_batch_byteoff_device.argtypes = [vp, vp, vp, u64, i32, i32, vp, vp, u64, vp, vp]
     L.mbpe_encoder_encode_batch_endmask.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, u64, i32, vp, vp, vp,
                                                     vp, vp]
     L.mbpe_tok_set_encode_split.argtypes = [vp, i32]
@@ -554,9 +560,11 @@ class Encoder:
     def set_option(self, name, value):
         _check(lib().mbpe_encoder_set_option(self._h, name.encode(), int(value)))
 
-    def encode(self, data, chunk_off=None, offsets=False, dtype=np.uint32):
+    def encode(self, data, chunk_off=None, offsets=False, dtype=np.uint32, byte_off=False):
         """Host text -> host tokens of dtype uint32 or uint16, or (tokens, chunk_tok_off) with offsets=True: the
-        tokens of chunk c are tokens[chunk_tok_off[c]:chunk_tok_off[c + 1]].  The passes made: self.n_passes."""
+        tokens of chunk c are tokens[chunk_tok_off[c]:chunk_tok_off[c + 1]].  The passes made: self.n_passes.
+        byte_off=True (mbpe_encoder_encode_byteoff) appends tok_byte_off to the result, n + 1 uint64 offsets: token j
+        stands for data[tok_byte_off[j]:tok_byte_off[j + 1]]."""
         text = _u8(data)
         dtype = np.dtype(dtype)
         if dtype not in (np.dtype(np.uint32), np.dtype(np.uint16)):
@@ -566,28 +574,39 @@ class Encoder:
         out = np.zeros(max(len(text), 1), dtype=dtype)
         tok_off = np.zeros(n_chunks + 1, dtype=np.uint64) if offsets else None
         n, passes = ctypes.c_uint64(), ctypes.c_uint32()
-        _check(lib().mbpe_encoder_encode(self._h, text.ctypes.data if len(text) else None, len(text), 0,
-                                         None if off is None else off.ctypes.data, 0 if off is None else n_chunks,
-                                         out.ctypes.data, len(out), dtype.itemsize * 8, 0,
-                                         None if tok_off is None else tok_off.ctypes.data,
-                                         ctypes.byref(n), ctypes.byref(passes)))
+        head = (self._h, text.ctypes.data if len(text) else None, len(text), 0,
+                None if off is None else off.ctypes.data, 0 if off is None else n_chunks,
+                out.ctypes.data, len(out), dtype.itemsize * 8, 0)
+        tail = (None if tok_off is None else tok_off.ctypes.data, ctypes.byref(n), ctypes.byref(passes))
+        if byte_off:
+            boff = np.zeros(len(out) + 1, dtype=np.uint64)
+            _check(lib().mbpe_encoder_encode_byteoff(*head, boff.ctypes.data, *tail))
+        else:
+            _check(lib().mbpe_encoder_encode(*head, *tail))
         self.n_passes = passes.value
         tokens = out[:n.value].copy()
-        return (tokens, tok_off) if offsets else tokens
+        res = (tokens, tok_off) if offsets else (tokens,)
+        if byte_off:
+            res += (boff[:n.value + 1].copy(),)
+        return res if len(res) > 1 else res[0]
 
-    def encode_device(self, text_ptr, n_bytes, chunk_off, out_ptr, cap, token_bits=32, offsets=False):
+    def encode_device(self, text_ptr, n_bytes, chunk_off, out_ptr, cap, token_bits=32, offsets=False, byte_off_ptr=None):
         """n_bytes of text in device memory at text_ptr (e.g. a torch tensor's data_ptr(); read in place) -> tokens in
         device memory at out_ptr (0: query; room for cap tokens of token_bits bits; 32: bit 31 = chunk end, 16: plain
-        ids) -> token count, or (count, chunk_tok_off) with offsets=True."""
+        ids) -> token count, or (count, chunk_tok_off) with offsets=True.  byte_off_ptr: device memory for cap + 1
+        uint64, filled with the count + 1 token byte offsets (mbpe_encoder_encode_byteoff)."""
         off = None if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.uint64)
         n_chunks = 1 if off is None else len(off) - 1
         tok_off = np.zeros(n_chunks + 1, dtype=np.uint64) if offsets else None
         n, passes = ctypes.c_uint64(), ctypes.c_uint32()
-        _check(lib().mbpe_encoder_encode(self._h, ctypes.c_void_p(text_ptr) if text_ptr else None, n_bytes, 1,
-                                         None if off is None else off.ctypes.data, 0 if off is None else n_chunks,
-                                         ctypes.c_void_p(out_ptr) if out_ptr else None, cap, token_bits, 1,
-                                         None if tok_off is None else tok_off.ctypes.data,
-                                         ctypes.byref(n), ctypes.byref(passes)))
+        head = (self._h, ctypes.c_void_p(text_ptr) if text_ptr else None, n_bytes, 1,
+                None if off is None else off.ctypes.data, 0 if off is None else n_chunks,
+                ctypes.c_void_p(out_ptr) if out_ptr else None, cap, token_bits, 1)
+        tail = (None if tok_off is None else tok_off.ctypes.data, ctypes.byref(n), ctypes.byref(passes))
+        if byte_off_ptr:
+            _check(lib().mbpe_encoder_encode_byteoff(*head, ctypes.c_void_p(byte_off_ptr), *tail))
+        else:
+            _check(lib().mbpe_encoder_encode(*head, *tail))
         self.n_passes = passes.value
         return (n.value, tok_off) if offsets else n.value
 
@@ -678,12 +697,14 @@ class Encoder:
         return call.result(ids, lengths, arrays, doc_tok_off)
 
     def encode_endmask(self, text_ptr, n_bytes, mask_ptr, singles=None, doc_off=None, dtype=np.uint32, out_ptr=None,
-                       cap=None, query=False):
+                       cap=None, query=False, byte_off=False, byte_off_ptr=None):
         """n_bytes of text in device memory at text_ptr with its end mask in device memory at mask_ptr, both read in
         place (mbpe_encoder_encode_endmask; what Splitter.split_docs and Splitter.endmask give).  singles: rows
         (start, len, id) of byte ranges that are one token each; doc_off: n_docs + 1 byte offsets at chunk boundaries.
         -> (tokens of dtype uint32 or uint16, doc_tok_off or None); with out_ptr= (device memory for cap tokens; 32
-        bits: bit 31 = chunk end) or query=True the token count stands in place of the tokens."""
+        bits: bit 31 = chunk end) or query=True the token count stands in place of the tokens.
+        byte_off=True (host output; mbpe_encoder_encode_endmask_byteoff) appends the n + 1 token byte offsets to the
+        result; byte_off_ptr (with out_ptr): device memory for cap + 1 uint64 that receives them."""
         dtype = np.dtype(dtype)
         sg = _singles(singles)
         docs = None if doc_off is None else np.ascontiguousarray(doc_off, dtype=np.uint64)
@@ -692,15 +713,20 @@ class Encoder:
         n, passes = ctypes.c_uint64(), ctypes.c_uint32()
         head = (self._h, _ptr(text_ptr), n_bytes, _ptr(mask_ptr), sg.ctypes.data if len(sg) else None, len(sg),
                 None if docs is None else docs.ctypes.data, n_docs)
-        tail = (dtype.itemsize * 8, 0 if out_ptr is None else 1, None if tok_off is None else tok_off.ctypes.data,
-                ctypes.byref(n), ctypes.byref(passes))
+        mid = (dtype.itemsize * 8, 0 if out_ptr is None else 1)
+        tail = (None if tok_off is None else tok_off.ctypes.data, ctypes.byref(n), ctypes.byref(passes))
         if query or out_ptr is not None:
-            _check(lib().mbpe_encoder_encode_endmask(*head, None if query else _ptr(out_ptr), 0 if query else cap, *tail))
+            _check(lib().mbpe_encoder_encode_endmask_byteoff(*head, None if query else _ptr(out_ptr), 0 if query else cap,
+                                                             *mid, None if query else _ptr(byte_off_ptr), *tail))
             self.n_passes = passes.value
             return n.value, tok_off
         out = np.zeros(max(n_bytes, 1) if cap is None else max(cap, 1), dtype=dtype)
-        _check(lib().mbpe_encoder_encode_endmask(*head, out.ctypes.data, n_bytes if cap is None else cap, *tail))
+        boff = np.zeros(len(out) + 1, dtype=np.uint64) if byte_off else None
+        _check(lib().mbpe_encoder_encode_endmask_byteoff(*head, out.ctypes.data, n_bytes if cap is None else cap, *mid,
+                                                         None if boff is None else boff.ctypes.data, *tail))
         self.n_passes = passes.value
+        if byte_off:
+            return out[:n.value].copy(), tok_off, boff[:n.value + 1].copy()
         return out[:n.value].copy(), tok_off
 
     def encode_batch_endmask(self, text_ptr, n_bytes, mask_ptr, singles, doc_off, *, seq_len, layout="padded",
@@ -1275,18 +1301,26 @@ class Tokenizer:
         _check(lib().mbpe_tok_set_encode_split(self._h, int(bool(device_split))))
         _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
 
-    def encode(self, data, device=None, device_split=False, order="greedy"):
+    def encode(self, data, device=None, device_split=False, order="greedy", byte_ranges=False):
         """device None: internal_encode on the host; an int: on that HIP device (mbpe_tok_encode_device).
         device_split (here and in the batch calls; only with a device): the text is cut at the special tokens and split
         into chunks on the device too (mbpe_tok_set_encode_split); same tokens, gpt2 / gpt4 patterns only.  "unicode"
         instead of True: with the splitter's option "unicode" for that call (mbpe_tok_set_split_unicode).
         order (here and in the batch calls; host and device): "greedy", the reference's passes that replace any pair
         they find, or "rank": a chunk's pair with the lowest merge id first, which for a trained model is the
-        segmentation the trainer left in its stream (mbpe_tok_set_encode_order).  Anything else is ValueError."""
+        segmentation the trainer left in its stream (mbpe_tok_set_encode_order).  Anything else is ValueError.
+        byte_ranges=True (mbpe_tok_encode_byteoff): -> (tokens, ranges[n, 2] uint64), token j stands for
+        data[ranges[j, 0]:ranges[j, 1]] (a special token: the occurrence of its name)."""
         self._encode_split(device_split, order)
         text = _u8(data)
         n = ctypes.c_uint64()
         out = np.zeros(max(len(text), 1), dtype=np.uint32)
+        if byte_ranges:
+            ranges = np.zeros((len(out), 2), dtype=np.uint64)
+            _check(lib().mbpe_tok_encode_byteoff(self._h, text.ctypes.data if len(text) else None, len(text), 0,
+                                                 -1 if device is None else device, out.ctypes.data, ranges.ctypes.data,
+                                                 len(out), ctypes.byref(n)))
+            return out[:n.value].copy(), ranges[:n.value].copy()
         if device is None:
             _check(lib().mbpe_tok_encode(self._h, text.ctypes.data if len(text) else None, len(text), 0,
                                          out.ctypes.data, len(out), ctypes.byref(n)))
@@ -1295,8 +1329,10 @@ class Tokenizer:
                                                 out.ctypes.data, len(out), ctypes.byref(n)))
         return out[:n.value].copy()
 
-    def encode_batch(self, texts, device=0, device_split=False, order="greedy"):
-        """encode() of every text in one device call (mbpe_tok_encode_batch_device) -> list of uint32 arrays."""
+    def encode_batch(self, texts, device=0, device_split=False, order="greedy", byte_ranges=False):
+        """encode() of every text in one device call (mbpe_tok_encode_batch_device) -> list of uint32 arrays; with
+        byte_ranges=True (mbpe_tok_encode_batch_byteoff_device) a list of (tokens, ranges[n, 2] uint64) pairs, the
+        ranges relative to each text's first byte."""
         self._encode_split(device_split, order)
         parts = [bytes(_u8(t)) for t in texts]
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
@@ -1306,6 +1342,13 @@ class Tokenizer:
         out = np.zeros(max(len(text), 1), dtype=np.uint32)
         tok_off = np.zeros(len(parts) + 1, dtype=np.uint64)
         n = ctypes.c_uint64()
+        if byte_ranges:
+            ranges = np.zeros((len(out), 2), dtype=np.uint64)
+            _check(lib().mbpe_tok_encode_batch_byteoff_device(self._h, text.ctypes.data if len(text) else None,
+                                                              doc_off.ctypes.data, len(parts), 0, device, out.ctypes.data,
+                                                              ranges.ctypes.data, len(out), tok_off.ctypes.data,
+                                                              ctypes.byref(n)))
+            return [(out[int(a):int(b)].copy(), ranges[int(a):int(b)].copy()) for a, b in zip(tok_off[:-1], tok_off[1:])]
         _check(lib().mbpe_tok_encode_batch_device(self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data,
                                                   len(parts), 0, device, out.ctypes.data, len(out), tok_off.ctypes.data,
                                                   ctypes.byref(n)))
