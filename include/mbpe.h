@@ -481,6 +481,9 @@ MBPE_API void mbpe_encoder_destroy(mbpe_encoder *e);
  * (free + held - (free + held) / 16) / 14 bytes, where free is the device memory hipMemGetInfo reports at the call
  * and held the size of the encoder's work buffers: a piece costs 13.2 bytes of device memory per text byte
  * (with token byte offsets for the host: up to 21.2, and the divisor is 22 -- see mbpe_encoder_encode_byteoff).
+ * While dropout is on (mbpe_encoder_set_dropout) a piece costs 8 bytes per text byte more, the two arrays of byte
+ * starts: the divisor is 22 instead of 14, with byte offsets for the host 30 instead of 22, and a piece holds at most
+ * 2^32 bytes whatever "piece_bytes" says, because a byte start is 32 bits.
  * When the pieces are several and cap < n_bytes, the passes run twice (count first, so that a cap too small writes
  * nothing). */
 MBPE_API int  mbpe_encoder_encode(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
@@ -512,6 +515,36 @@ MBPE_API int  mbpe_encoder_encode(mbpe_encoder *e, const uint8_t *text, uint64_t
  *                   first call in rank order needs them.
  * An unknown name or a negative value is MBPE_ERR_ARG. */
 MBPE_API int  mbpe_encoder_set_option(mbpe_encoder *e, const char *name, int64_t value);
+
+/* BPE-dropout (Provilkov et al., 2020; the `dropout` of other tokenizers' BPE models) in rank order: a merge that
+ * applies is skipped with probability p, so the same text gets another segmentation with every seed.
+ * Definition.  Rank order only.  Per chunk, after text_to_vector, repeat: of the adjacent pairs (t[i], t[i + 1]) that
+ * are in the lookup AND whose instance is not dropped take the smallest merged id m; stop when there is none; replace
+ * the surviving instances of m, left to right and non-overlapping.  An INSTANCE is (pos, id): pos = the offset of the
+ * first byte of t[i] in the buffer the encoder read -- 64 bits, over the whole call, not over a piece or a chunk --
+ * and id = the merged token.  It is dropped iff drop_hash(seed, pos, id) < threshold, threshold in [0, 2^32]:
+ *     x  = seed + pos * 0x9E3779B97F4A7C15 + (uint64_t)id * 0xD1B54A32D192ED03           (mod 2^64)
+ *     x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31
+ *     drop_hash = x >> 32
+ * A pure function of (seed, pos, id): an instance that is dropped stays dropped in every later round, and the result
+ * does not depend on pieces, spans or the other chunks; a CPU loop reproduces it bit for bit.  threshold 2^32 (p = 1)
+ * leaves the bytes, threshold 0 is plain rank order.  In a run a a a with (a,a) whose instance at 0 is dropped, the
+ * instance at 1 is replaced: the left-to-right rule runs over the surviving candidates.  Chunks that are one token by
+ * rule (NUL-led with a number, mbpe_single) have no candidates and are never touched.
+ *   mbpe_dropout_threshold    floor(p * 2^32), exact for p = 0 and p = 1; NaN or a p outside [0, 1]: MBPE_ERR_ARG
+ *   mbpe_encoder_set_dropout  holds from the next call on for mbpe_encoder_encode, _encode_batch, _encode_batch_aux,
+ *                             _encode_endmask, _encode_batch_endmask and the _byteoff calls (whose offsets come from
+ *                             the final stream, as without dropout).  A threshold above 2^32 is MBPE_ERR_ARG.
+ * An encode call with threshold > 0 while "rank_order" is 0 returns MBPE_ERR_ARG with a message, before the device is
+ * touched; the encoder stays usable and the order is never switched silently.  mbpe_encode_chunks* and the replay
+ * inside mbpe_train_begin_from never drop.
+ * How: every token carries the byte start of its first byte through the passes (32 bits, relative to the piece, beside
+ * the two token arrays; a merged token keeps its left token's), the candidate kernel reads it where the lookup hit and
+ * clears a dropped candidate before the rank kernels see it; every kernel after that is the plain one.  With threshold
+ * 0 the launches, the buffers and mbpe_encoder_alloc_count are exactly those of an encoder that never heard of
+ * dropout; the 8 bytes per text byte are reserved by the first call that needs them (see "Pieces" above). */
+MBPE_API int  mbpe_dropout_threshold(double p, uint64_t *threshold_out);
+MBPE_API int  mbpe_encoder_set_dropout(mbpe_encoder *e, uint64_t threshold, uint64_t seed);
 
 /* Device time of the encoder's latest call in milliseconds: HIP events on its stream around widen, the passes (with
  * the 8-byte read-back that ends each) and the finishing kernels (those of the token byte offsets included), summed
@@ -734,7 +767,8 @@ MBPE_API int  mbpe_encoder_encode_endmask(mbpe_encoder *e, const uint8_t *text_d
  * text bytes, 8 per one-token chunk and -- only when the offsets go to the host -- a staging buffer of 8 bytes per
  * token of the largest piece.  A piece then costs up to 13.2 + 8 = 21.2 bytes per text byte (every byte its own
  * token), and the limit that "piece_bytes" 0 derives divides by 22 instead of 14 for such a call; with out_on_device it
- * stays 14.  A repeat call of no larger size allocates nothing. */
+ * stays 14 (while dropout is on: 30 instead of 22, mbpe_encoder_set_dropout).  A repeat call of no larger size
+ * allocates nothing. */
 MBPE_API int  mbpe_encoder_encode_byteoff(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
                                           const uint64_t *chunk_off, uint64_t n_chunks,
                                           void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device,

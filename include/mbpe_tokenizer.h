@@ -145,6 +145,20 @@ MBPE_API int mbpe_tok_set_encode_split(mbpe_tokenizer *t, int on_device);
  * and special tokens are unaffected.  Any other value is MBPE_ERR_ARG. */
 MBPE_API int mbpe_tok_set_encode_order(mbpe_tokenizer *t, int rank_order);
 
+/* BPE-dropout for mbpe_tok_encode, mbpe_tok_encode_byteoff and the mbpe_tok_encode*_device calls: threshold and seed
+ * as for mbpe_encoder_set_dropout (mbpe.h, which holds the definition; mbpe_dropout_threshold converts a probability).
+ * The host loop applies the same instance rule -- encode_rank_ordered carries every token's byte start, with the
+ * chunk's offset in its buffer as base -- and the kept device encoder is re-configured, not re-created.  A threshold
+ * above 2^32 is MBPE_ERR_ARG; so is every encode call while the threshold is above 0 and the order is greedy
+ * (mbpe_tok_set_encode_order): dropout is defined on the rank order alone and the order is never switched silently.
+ * Positions: an instance's pos is in the coordinates of the buffer the route hands the encoder.  With the device split
+ * that is the original text -- in a batch call the documents laid end to end.  With the host split, on the host loop
+ * and on the device alike, it is the chunk buffer: the pattern's matches one after the other, a special token as its
+ * "\0<id>" marker.  So the host loop and the device over the host split always agree, and both agree with the device
+ * split whenever that buffer IS the text: no special token and no NUL-led part occurs and the pattern is basic, gpt2
+ * or gpt4 (whose matches tile the text).  Otherwise the device split gives another, equally valid, draw. */
+MBPE_API int mbpe_tok_set_encode_dropout(mbpe_tokenizer *t, uint64_t threshold, uint64_t seed);
+
 /* The option "unicode" (mbpe_splitter_set_option) of the device splits this tokenizer makes: 0 (the default) or on.
  * It applies to mbpe_tok_train_split_device and, while mbpe_tok_set_encode_split is on, to the mbpe_tok_encode*_device
  * calls, whose kept splitter is re-configured, not re-created.  Same results; otherwise without effect. */

@@ -31,6 +31,14 @@
 // that chunk -- k_enc_cand, then a segmented minimum of cand over the chunks (rank.h) and a filter, then the same
 // parity scan, match, sum scan and scatter.  Passes repeat until one changes nothing, as above; for a trained table
 // the result is the merges replayed in order, chunk by chunk.
+//
+// BPE-dropout (mbpe_encoder_set_dropout, rank order only; dropout.h): a candidate whose instance (byte start of its
+// left token, merged id) is dropped becomes kTokNone in k_enc_cand, before span_sum is formed and before the rank
+// kernels see it; everything after k_enc_cand is unchanged.  Tokens move when a pass compacts, so every token's byte
+// start travels with it: org[i] (32 bits, relative to the piece), written by the widen kernel, carried by the scatter
+// kernel beside the tokens and ping-ponged like them; a merged token keeps its left token's org.  With threshold 0
+// none of this exists: the plain kernels are launched and no org buffer is reserved.
+#include "dropout.h"
 #include "hip_host.h"
 #include "pack.h"
 #include "rank.h"
@@ -68,14 +76,17 @@ __device__ __forceinline__ uint32_t enc_lookup(const EncLut &lut, uint32_t a, ui
     }
 }
 
-// text_to_vector, Tokenizer.h:94-99 (char_to_token :80-82) + chunk ends
+// text_to_vector, Tokenizer.h:94-99 (char_to_token :80-82) + chunk ends; ORG: also every token's byte start in the
+// piece (n <= 2^32 then: piece_limit)
+template <bool ORG>
 __global__ void k_enc_widen(const uint8_t *__restrict__ text, uint64_t n, const uint8_t *__restrict__ endmask,
-                            uint32_t *__restrict__ tok) {
+                            uint32_t *__restrict__ tok, uint32_t *__restrict__ org) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) {
         const uint32_t e = (endmask[i >> 3] >> (i & 7)) & 1u;
         tok[i] = text[i] | (e ? kTokEnd : 0u);
+        if (ORG) org[i] = (uint32_t)i;
     }
 }
 
@@ -90,10 +101,14 @@ __global__ void k_enc_single(const SingleChunk *__restrict__ sc, uint32_t n_sc, 
 }
 
 // pass, step 1: cand[i] = id of the token that (t[i], t[i+1]) merges to, or kTokNone; per span: are all its
-// positions candidates, and the parity of its trailing run of candidates
+// positions candidates, and the parity of its trailing run of candidates.  DROP: a candidate whose instance
+// (piece_base + org[i], id) is dropped is none (org is read where the lookup hit only)
+struct EncDrop { const uint32_t *org; unsigned long long piece_base, seed, threshold; };
+
+template <bool DROP>
 __global__ __launch_bounds__(kSpanThreads) void k_enc_cand(const uint32_t *__restrict__ tok, uint64_t n, EncLut lut,
                                                            uint32_t *__restrict__ cand,
-                                                           uint32_t *__restrict__ span_sum) {
+                                                           uint32_t *__restrict__ span_sum, EncDrop drop) {
     const uint64_t span = span_index(), base = span * kSpan;
     if (base >= n) return;
     const uint32_t lane = lane_id();
@@ -104,6 +119,8 @@ __global__ __launch_bounds__(kSpanThreads) void k_enc_cand(const uint32_t *__res
         const uint32_t t = load_pair(tok, i, n, lane, kDrop, &nx);
         uint32_t c = kTokNone;
         if (i < n && !(t & kTokEnd) && t != kDrop && nx != kDrop) c = enc_lookup(lut, t, nx & kTokIdMask);
+        if (DROP && c != kTokNone && dropout_dropped(drop.seed, drop.piece_base + drop.org[i], c, drop.threshold))
+            c = kTokNone;
         if (i < n) cand[i] = c;
         sum = span_add_group(sum, __ballot(c != kTokNone));
     }
@@ -243,6 +260,16 @@ __global__ __launch_bounds__(kSpanThreads) void k_enc_scatter(const uint32_t *__
                                                               const unsigned long long *__restrict__ span_off,
                                                               uint32_t *__restrict__ out) {
     span_scatter(val, n, span_off, out);
+}
+
+// the same with the byte starts: org_out gets org[i] wherever out gets val[i] (a replaced pair contributes at its left
+// position: the merged token keeps the left token's start)
+__global__ __launch_bounds__(kSpanThreads) void k_enc_scatter_org(const uint32_t *__restrict__ val, uint64_t n,
+                                                                  const unsigned long long *__restrict__ span_off,
+                                                                  uint32_t *__restrict__ out,
+                                                                  const uint32_t *__restrict__ org,
+                                                                  uint32_t *__restrict__ org_out) {
+    span_scatter_carry<true>(val, n, span_off, out, org, org_out);
 }
 
 // ---- the finishing kernels: what leaves the passes becomes what the caller asked for ----------------------------
@@ -447,6 +474,8 @@ __global__ __launch_bounds__(kSpanThreads) void k_enc_len_write(const uint32_t *
 
 // device bytes per text byte of a piece, rounded up (mbpe.h, "piece_bytes"): 13.2, and 20 / 1,024 more in rank order
 constexpr uint64_t kPieceCost = 14;
+constexpr uint64_t kPieceCostDropout = 8;  // more while dropout is on: the two org arrays, one uint32_t per token each
+constexpr uint64_t kPieceMaxDropout = 1ull << 32;   // ... and the most bytes of a piece then: org is 32 bits
 constexpr uint64_t kPieceCostByteOff = 8;  // more with byte offsets for the host: one uint64_t per token, at most per byte
 constexpr uint64_t kNulListMin = 4096;     // entries the list of NUL-led chunk starts begins with
 constexpr uint64_t kNulCopyEach = 256;     // up to this many NUL-led chunks are copied back one by one
@@ -458,6 +487,8 @@ struct mbpe_encoder : DevQueue {
     float last_ms = 0.f;
     uint64_t piece_bytes = 0;                 // option "piece_bytes"; 0 = from the free device memory
     bool rank_order = false;                  // option "rank_order": a pass applies every chunk's lowest merge only
+    unsigned long long drop_threshold = 0;    // mbpe_encoder_set_dropout: 0 = off, 2^32 = every instance is dropped
+    unsigned long long drop_seed = 0;
     uint32_t n_merges = 0;
     // the lookup table
     DevBuf<unsigned long long> d_keys;
@@ -469,6 +500,7 @@ struct mbpe_encoder : DevQueue {
     DevBuf<unsigned long long> span_off;
     DevBuf<RankSum> rank_sum;                 // rank order only: the spans' summaries, and what reaches every span
     DevBuf<uint32_t> rank_in;                 // from the left [0 .. n_spans) and from the right [n_spans .. 2 n_spans)
+    DevBuf<uint32_t> org[2];                  // dropout only: the tokens' byte starts in the piece, beside tok[0 / 1]
     DevBuf<unsigned long long> d_res;         // [0] total of a sum scan, [1] NUL-led chunk starts found, [2] end bits of the mask
     DevBuf<SingleChunk> d_singles;
     DevBuf<unsigned long long> d_nul;         // starts of NUL-led chunks of a device text
@@ -500,7 +532,8 @@ namespace {
 
 uint64_t enc_held(const mbpe_encoder *e) {
     return e->d_text.bytes() + e->d_mask.bytes() + e->tok[0].bytes() + e->tok[1].bytes() + e->cand.bytes() +
-           e->span_a.bytes() + e->span_b.bytes() + e->span_off.bytes() + e->rank_sum.bytes() + e->rank_in.bytes();
+           e->span_a.bytes() + e->span_b.bytes() + e->span_off.bytes() + e->rank_sum.bytes() + e->rank_in.bytes() +
+           e->org[0].bytes() + e->org[1].bytes();
 }
 
 struct Piece { uint64_t c0, c1; };            // chunks [c0, c1)
@@ -651,6 +684,10 @@ int piece_upload(mbpe_encoder *e, const EncCall &a, Piece p, PieceRun *r) {
         rc = e->rank_sum.reserve(n_spans0 * sizeof(RankSum), e->mem);
         if (rc == MBPE_OK) rc = e->rank_in.reserve(n_spans0 * 8, e->mem);
     }
+    if (rc == MBPE_OK && e->drop_threshold) {
+        rc = e->org[0].reserve(pn * 4, e->mem);
+        if (rc == MBPE_OK) rc = e->org[1].reserve(pn * 4, e->mem);
+    }
     if (rc != MBPE_OK) return rc;
     // the piece's NUL-led chunks (e->singles is sorted by start), relative to the piece
     e->piece_singles.clear();
@@ -689,13 +726,18 @@ int piece_upload(mbpe_encoder *e, const EncCall &a, Piece p, PieceRun *r) {
     return MBPE_OK;
 }
 
-// ev0, bytes -> tokens, then passes until one changes nothing
-int piece_passes(mbpe_encoder *e, const EncCall &a, PieceRun *r) {
+// ev0, bytes -> tokens, then passes until one changes nothing.  piece_base = the piece's first byte in the call's text
+int piece_passes(mbpe_encoder *e, const EncCall &a, uint64_t piece_base, PieceRun *r) {
     const uint64_t pn = r->pn;
+    const bool drop = e->drop_threshold != 0;
     ECHK(hipEventRecord(e->ev0, e->stream));
     const int wblocks = (int)std::min<uint64_t>((pn + 255) / 256, 8192);
-    hipLaunchKernelGGL(k_enc_widen, dim3(wblocks), dim3(256), 0, e->stream, r->d_text, pn,
-                       a.mask_dev ? a.mask_dev : e->d_mask, e->tok[0]);
+    if (drop)
+        hipLaunchKernelGGL(k_enc_widen<true>, dim3(wblocks), dim3(256), 0, e->stream, r->d_text, pn,
+                           a.mask_dev ? a.mask_dev : e->d_mask, e->tok[0], e->org[0]);
+    else
+        hipLaunchKernelGGL(k_enc_widen<false>, dim3(wblocks), dim3(256), 0, e->stream, r->d_text, pn,
+                           a.mask_dev ? a.mask_dev : e->d_mask, e->tok[0], nullptr);
     if (!e->piece_singles.empty())
         hipLaunchKernelGGL(k_enc_single, dim3((uint32_t)e->piece_singles.size()), dim3(64), 0, e->stream, e->d_singles,
                            (uint32_t)e->piece_singles.size(), e->tok[0]);
@@ -705,7 +747,12 @@ int piece_passes(mbpe_encoder *e, const EncCall &a, PieceRun *r) {
     for (;;) {
         const uint64_t n_spans = span_count(n);
         const dim3 grid(span_grid(n)), block(kSpanThreads);
-        hipLaunchKernelGGL(k_enc_cand, grid, block, 0, e->stream, e->tok[cur], n, e->lut, e->cand, e->span_a);
+        if (drop)
+            hipLaunchKernelGGL(k_enc_cand<true>, grid, block, 0, e->stream, e->tok[cur], n, e->lut, e->cand, e->span_a,
+                               EncDrop{e->org[cur], piece_base, e->drop_seed, e->drop_threshold});
+        else
+            hipLaunchKernelGGL(k_enc_cand<false>, grid, block, 0, e->stream, e->tok[cur], n, e->lut, e->cand, e->span_a,
+                               EncDrop{});
         if (e->rank_order) {
             uint32_t *in_left = e->rank_in, *in_right = e->rank_in + n_spans;
             hipLaunchKernelGGL(k_enc_rank_sum, grid, block, 0, e->stream, e->tok[cur], n, e->cand, e->rank_sum);
@@ -718,7 +765,11 @@ int piece_passes(mbpe_encoder *e, const EncCall &a, PieceRun *r) {
         hipLaunchKernelGGL(k_enc_match, grid, block, 0, e->stream, e->tok[cur], n, e->cand, e->span_b, e->span_a);
         hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans, e->span_off,
                            e->d_res);
-        hipLaunchKernelGGL(k_enc_scatter, grid, block, 0, e->stream, e->cand, n, e->span_off, e->tok[1 - cur]);
+        if (drop)
+            hipLaunchKernelGGL(k_enc_scatter_org, grid, block, 0, e->stream, e->cand, n, e->span_off, e->tok[1 - cur],
+                               e->org[cur], e->org[1 - cur]);
+        else
+            hipLaunchKernelGGL(k_enc_scatter, grid, block, 0, e->stream, e->cand, n, e->span_off, e->tok[1 - cur]);
         unsigned long long total = 0;
         ECHK(hipMemcpyAsync(&total, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
         ECHK(hipStreamSynchronize(e->stream));
@@ -886,7 +937,7 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, PieceRu
         return MBPE_OK;
     }
     int rc = piece_upload(e, a, p, r);
-    if (rc == MBPE_OK) rc = piece_passes(e, a, r);
+    if (rc == MBPE_OK) rc = piece_passes(e, a, a.chunk_off[p.c0], r);
     if (rc == MBPE_OK) rc = piece_finish(e, a, p, done, r);
     return rc;
 }
@@ -909,15 +960,20 @@ int run_pieces(mbpe_encoder *e, EncCall a, const std::vector<Piece> &pieces, Pie
 // the bytes one piece may hold: the option, else what the buffers hold already, else from the free device memory
 // (boff_host: byte offsets that go to the host are staged on the device, 8 bytes per token)
 int piece_limit(mbpe_encoder *e, uint64_t n_bytes, bool boff_host, uint64_t *limit) {
+    const bool drop = e->drop_threshold != 0;
     *limit = e->piece_bytes;
-    if (*limit) return MBPE_OK;
-    *limit = e->cand.bytes() / 4;                                 // what the buffers hold already needs no question
-    if (n_bytes > *limit) {
-        size_t free_b = 0, total_b = 0;
-        ECHK(hipMemGetInfo(&free_b, &total_b));
-        const uint64_t avail = (uint64_t)free_b + enc_held(e) + (boff_host ? e->d_boff.bytes() : 0);
-        *limit = std::max<uint64_t>((avail - avail / 16) / (kPieceCost + (boff_host ? kPieceCostByteOff : 0)), *limit);
+    if (*limit == 0) {
+        // what the buffers hold already needs no question (with dropout: the org arrays are among them)
+        *limit = drop ? std::min(e->cand.bytes(), e->org[1].bytes()) / 4 : e->cand.bytes() / 4;
+        if (n_bytes > *limit) {
+            size_t free_b = 0, total_b = 0;
+            ECHK(hipMemGetInfo(&free_b, &total_b));
+            const uint64_t avail = (uint64_t)free_b + enc_held(e) + (boff_host ? e->d_boff.bytes() : 0);
+            const uint64_t cost = kPieceCost + (drop ? kPieceCostDropout : 0) + (boff_host ? kPieceCostByteOff : 0);
+            *limit = std::max<uint64_t>((avail - avail / 16) / cost, *limit);
+        }
     }
+    if (drop) *limit = std::min(*limit, kPieceMaxDropout);
     return MBPE_OK;
 }
 
@@ -937,6 +993,14 @@ int boff_begin(mbpe_encoder *e, const EncCall &a) {
         ECHK(hipMemsetAsync(a.tok_byte_off_out, 0, 8, e->stream));
         ECHK(hipStreamSynchronize(e->stream));
     }
+    return MBPE_OK;
+}
+
+// dropout is defined on the rank order alone: an encode call of an encoder with a threshold above 0 and the greedy
+// order is refused before the device is touched (there is no silent switch of the order)
+int drop_check(const mbpe_encoder *e, const std::string &who) {
+    if (e->drop_threshold && !e->rank_order)
+        return fail(MBPE_ERR_ARG, who + ": dropout needs the option \"rank_order\" (mbpe_encoder_set_dropout)");
     return MBPE_OK;
 }
 
@@ -1313,6 +1377,22 @@ int mbpe_encoder_set_option(mbpe_encoder *e, const char *name, int64_t value) {
     return fail(MBPE_ERR_ARG, std::string("mbpe_encoder_set_option: no option \"") + name + "\"");
 }
 
+int mbpe_dropout_threshold(double p, uint64_t *threshold_out) {
+    if (!threshold_out) return fail(MBPE_ERR_ARG, "mbpe_dropout_threshold: NULL argument");
+    unsigned long long t = 0;
+    if (!dropout_threshold(p, &t)) return fail(MBPE_ERR_ARG, "mbpe_dropout_threshold: p must lie in [0, 1]");
+    *threshold_out = t;
+    return MBPE_OK;
+}
+
+int mbpe_encoder_set_dropout(mbpe_encoder *e, uint64_t threshold, uint64_t seed) {
+    if (!e) return fail(MBPE_ERR_ARG, "mbpe_encoder_set_dropout: NULL argument");
+    if (threshold > kDropoutOne) return fail(MBPE_ERR_ARG, "mbpe_encoder_set_dropout: threshold must not exceed 2^32");
+    e->drop_threshold = threshold;
+    e->drop_seed = seed;
+    return MBPE_OK;
+}
+
 int mbpe_encoder_encode_byteoff(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
                                 const uint64_t *chunk_off, uint64_t n_chunks, void *tokens_out, uint64_t cap,
                                 uint32_t token_bits, int out_on_device, uint64_t *tok_byte_off_out,
@@ -1324,7 +1404,8 @@ int mbpe_encoder_encode_byteoff(mbpe_encoder *e, const uint8_t *text, uint64_t n
     EncCall a = {text, n_bytes, text_on_device, chunk_off, n_chunks, tokens_out, cap, token_bits, out_on_device,
                  chunk_tok_off_out, n_out, n_passes_out};
     a.tok_byte_off_out = tok_byte_off_out;
-    const int rc = boff_check(e, "mbpe_encoder_encode_byteoff", &a);
+    int rc = drop_check(e, "mbpe_encoder_encode");
+    if (rc == MBPE_OK) rc = boff_check(e, "mbpe_encoder_encode_byteoff", &a);
     if (rc != MBPE_OK) return rc;
     return enc_guard("mbpe_encoder_encode", [&] { return enc_run_body(e, a); });
 }
@@ -1343,7 +1424,8 @@ static int enc_batch(mbpe_encoder *e, EncCall a, const EncPack &k) {
     if (k.n_tokens_out) *k.n_tokens_out = 0;
     if (!e || !k.n_rows_out || !k.doc_chunk_off || !k.spec || (!a.text && a.n_bytes))
         return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_batch: NULL argument");
-    int rc = pack_check_spec(k.spec, k.token_bits());
+    int rc = drop_check(e, "mbpe_encoder_encode_batch");
+    if (rc == MBPE_OK) rc = pack_check_spec(k.spec, k.token_bits());
     if (rc != MBPE_OK) return rc;
     const uint64_t one[2] = {0, a.n_bytes};
     if (!a.chunk_off) { a.chunk_off = one; a.n_chunks = 1; }
@@ -1403,6 +1485,7 @@ int mbpe_encoder_encode_endmask_byteoff(mbpe_encoder *e, const uint8_t *text_dev
     if (rc != MBPE_OK) return rc;
     if (!e || !n_out || ((!text_dev || !endmask_dev) && n_bytes))
         return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_endmask: NULL argument");
+    if ((rc = drop_check(e, "mbpe_encoder_encode_endmask")) != MBPE_OK) return rc;
     if ((uintptr_t)endmask_dev & 3) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_endmask: the mask must be 4-byte aligned");
     if (token_bits == 16 && 256ull + e->n_merges > 65536ull)
         return fail(MBPE_ERR_VOCAB, "token_bits 16 with more than 65,536 token ids");
@@ -1432,6 +1515,7 @@ int mbpe_encoder_encode_batch_endmask(mbpe_encoder *e, const uint8_t *text_dev, 
     if (doc_off[0] != 0 || doc_off[n_docs] != n_bytes)
         return fail(MBPE_ERR_ARG, who + ": doc_off must start at 0 and end at n_bytes");
     if (!e || ((!text_dev || !endmask_dev) && n_bytes)) return fail(MBPE_ERR_ARG, who + ": NULL argument");
+    if ((rc = drop_check(e, who)) != MBPE_OK) return rc;
     if ((uintptr_t)endmask_dev & 3) return fail(MBPE_ERR_ARG, who + ": the mask must be 4-byte aligned");
     rc = enc_batch_check(e, k);
     if (rc != MBPE_OK) return rc;

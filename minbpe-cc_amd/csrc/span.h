@@ -209,9 +209,12 @@ __device__ __forceinline__ unsigned long long wave_prefix64(unsigned long long v
 }
 
 // ---- compaction: the values of val[0 .. n) that are not kTokNone, in order, to out; span_off from span_scan_sum --
-__device__ __forceinline__ void span_scatter(const uint32_t *__restrict__ val, uint64_t n,
-                                             const unsigned long long *__restrict__ span_off,
-                                             uint32_t *__restrict__ out) {
+// CARRY: a second array travels with them, carry_out gets carry[i] wherever out gets val[i]
+template <bool CARRY>
+__device__ __forceinline__ void span_scatter_carry(const uint32_t *__restrict__ val, uint64_t n,
+                                                   const unsigned long long *__restrict__ span_off,
+                                                   uint32_t *__restrict__ out, const uint32_t *__restrict__ carry,
+                                                   uint32_t *__restrict__ carry_out) {
     const uint64_t span = span_index(), base = span * kSpan;
     if (base >= n) return;
     const uint32_t lane = lane_id();
@@ -221,9 +224,18 @@ __device__ __forceinline__ void span_scatter(const uint32_t *__restrict__ val, u
         const uint64_t i = base + (uint64_t)it * kWave + lane;
         const uint32_t v = i < n ? val[i] : kTokNone;
         const WaveKeep k = wave_keep(v != kTokNone, lt);
-        if (v != kTokNone) out[o + k.rank] = v;
+        if (v != kTokNone) {
+            out[o + k.rank] = v;
+            if (CARRY) carry_out[o + k.rank] = carry[i];
+        }
         o += k.count;
     }
+}
+
+__device__ __forceinline__ void span_scatter(const uint32_t *__restrict__ val, uint64_t n,
+                                             const unsigned long long *__restrict__ span_off,
+                                             uint32_t *__restrict__ out) {
+    span_scatter_carry<false>(val, n, span_off, out, nullptr, nullptr);
 }
 #endif  // __HIPCC__
 

@@ -1,6 +1,7 @@
 // minbpe-cc: the reference's command line (code/examples/minbpe-cc.cpp:92-265)
 // on top of the MI355X training path.  Same flags, defaults, messages and exit
-// codes; `--train -c lexical` runs on the GPU.  The only additions are --device, the --device-* switches and --rank-order.
+// codes; `--train -c lexical` runs on the GPU.  The only additions are --device, the --device-* switches, --rank-order,
+// --dropout / --seed, --byte-ranges-out and --continue-from.
 #include "mbpe.h"
 #include "mbpe_tokenizer.h"
 
@@ -74,6 +75,11 @@ void usage() {
                  "  --rank-order                When encoding, apply the merges in rank order (a chunk's pair with the lowest\n"
                  "                              merge id first: the segmentation the model was trained on) instead of the\n"
                  "                              reference's greedy passes; on the host and with --device-encode\n"
+                 "  --dropout FLOAT             When encoding with --rank-order: BPE-dropout, a merge that applies is skipped with\n"
+                 "                              this probability (0 .. 1), so the text gets another segmentation per --seed;\n"
+                 "                              on the host, with --device-encode and with --device-split.  Without\n"
+                 "                              --rank-order it is a usage error\n"
+                 "  --seed UINT                 The seed of --dropout (default 0); the same seed gives the same tokens\n"
                  "  --byte-ranges-out TEXT      When encoding, also write one line \"start end\" per token to this file: the bytes\n"
                  "                              of the input the token stands for (a special token: its name's occurrence);\n"
                  "                              on the host, with --device-encode, --device-split and --rank-order alike\n"
@@ -94,6 +100,9 @@ int main(int argc, char *argv[]) {
     bool train = false, decode = false, encode = false, write_vocab = false, verbose = false, device_encode = false,
          device_decode = false, device_split = false, split_unicode = false, rank_order = false;
     int vocab_size = 512, device = 0;
+    double dropout = 0.0;
+    bool have_dropout = false;
+    unsigned long long seed = 0;
 
     // option parsing (the reference uses CLI11, :93-133)
     for (int i = 1; i < argc; ++i) {
@@ -122,6 +131,17 @@ int main(int argc, char *argv[]) {
         } else if (arg == "--device") {
             if (!value(&tmp)) return 106;
             try { device = std::stoi(tmp); } catch (...) { std::cerr << "--device: invalid integer " << tmp << "\n"; return 104; }
+        } else if (arg == "--dropout") {
+            if (!value(&tmp)) return 106;
+            size_t used = 0;
+            try { dropout = std::stod(tmp, &used); } catch (...) { used = 0; }
+            if (used == 0 || used != tmp.size()) { std::cerr << "--dropout: invalid number " << tmp << "\n"; return 104; }
+            have_dropout = true;
+        } else if (arg == "--seed") {
+            if (!value(&tmp)) return 106;
+            size_t used = 0;
+            try { seed = std::stoull(tmp, &used); } catch (...) { used = 0; }
+            if (used == 0 || used != tmp.size() || tmp[0] == '-') { std::cerr << "--seed: invalid integer " << tmp << "\n"; return 104; }
         } else if (arg == "-c" || arg == "--conflict-resolution") {
             if (!value(&conflict_resolution_str)) return 106;
             if (conflict_resolution_str != "first" && conflict_resolution_str != "lexical") {   // CLI::IsMember, :129-131
@@ -139,6 +159,15 @@ int main(int argc, char *argv[]) {
         else if (arg == "--rank-order") rank_order = true;
         else if (arg == "-v" || arg == "--verbose") verbose = true;
         else { std::cerr << "The following argument was not expected: " << arg << "\n"; return 109; }
+    }
+
+    uint64_t drop_threshold = 0;
+    if (have_dropout) {
+        if (mbpe_dropout_threshold(dropout, &drop_threshold) != MBPE_OK) {
+            std::cerr << "--dropout: " << dropout << " not in [0, 1]\n";
+            return 105;
+        }
+        if (!rank_order) { std::cerr << "--dropout requires --rank-order\n"; return 107; }
     }
 
     if (!input_path.empty()) {                                  // :135-144
@@ -215,6 +244,7 @@ int main(int argc, char *argv[]) {
             const uint8_t *in = reinterpret_cast<const uint8_t *>(input.data());
             if (device_encode && device_split) mbpe_tok_set_encode_split(rt, 1);
             if (rank_order) mbpe_tok_set_encode_order(rt, 1);
+            if (have_dropout) mbpe_tok_set_encode_dropout(rt, drop_threshold, seed);
             if (split_unicode) mbpe_tok_set_split_unicode(rt, 1);
             std::vector<uint64_t> ranges(byte_ranges_path.empty() ? 0 : 2 * encoded.size());
             const int erc = !byte_ranges_path.empty()

@@ -4,6 +4,7 @@
 // GPU through mbpe_train_lexical.
 #include "tokenizer.h"
 
+#include "dropout.h"
 #include "mbpe.h"
 #include "mbpe_tokenizer.h"
 
@@ -61,7 +62,8 @@ mbpe_encoder *Tokenizer::device_encoder(int device) {
         if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
         encoder_device_ = device;
     }
-    const int rc = mbpe_encoder_set_option(encoder_, "rank_order", rank_order_ ? 1 : 0);
+    int rc = mbpe_encoder_set_option(encoder_, "rank_order", rank_order_ ? 1 : 0);
+    if (rc == MBPE_OK) rc = mbpe_encoder_set_dropout(encoder_, drop_threshold_, drop_seed_);
     if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
     return encoder_;
 }
@@ -313,29 +315,41 @@ std::vector<Token> Tokenizer::internal_internal_encode(std::vector<Token> text) 
     }
 }
 
-std::vector<Token> Tokenizer::encode_rank_ordered(std::vector<Token> text) const {
+void Tokenizer::check_dropout_order() const {
+    if (drop_threshold_ && !rank_order_)
+        throw CodedError(MBPE_ERR_ARG, "encode: dropout needs the rank order (mbpe_tok_set_encode_order)");
+}
+
+std::vector<Token> Tokenizer::encode_rank_ordered(std::vector<Token> text, uint64_t base) const {
+    const bool drop = drop_threshold_ != 0;
+    std::vector<uint64_t> pos, pos_out;            // dropout only: the byte start of every token
+    if (drop) {
+        pos.resize(text.size());
+        for (size_t i = 0; i < text.size(); ++i) pos[i] = base + i;      // (text_to_vector: one token per byte, or one)
+    }
+    // the id (t[i], t[i + 1]) merges to when the pair is in the lookup and its instance survives, else "none"
+    const Token none = std::numeric_limits<Token>::max();
+    auto candidate = [&](size_t i) -> Token {
+        auto it = merges_lookup_.find(TokenPair{text[i], text[i + 1]});
+        if (it == merges_lookup_.end()) return none;
+        if (drop && mbpe::dropout_dropped(drop_seed_, pos[i], it->second, drop_threshold_)) return none;
+        return it->second;
+    };
     for (;;) {
-        Token best = std::numeric_limits<Token>::max();
-        bool any = false;
-        for (size_t i = 0; i + 1 < text.size(); ++i) {
-            auto it = merges_lookup_.find(TokenPair{text[i], text[i + 1]});
-            if (it != merges_lookup_.end() && (!any || it->second < best)) { best = it->second; any = true; }
-        }
-        if (!any) return text;
+        Token best = none;
+        for (size_t i = 0; i + 1 < text.size(); ++i) best = std::min(best, candidate(i));
+        if (best == none) return text;
         std::vector<Token> out;
         out.reserve(text.size());
+        pos_out.clear();
         for (size_t i = 0; i < text.size();) {
-            if (i + 1 < text.size()) {
-                auto it = merges_lookup_.find(TokenPair{text[i], text[i + 1]});
-                if (it != merges_lookup_.end() && it->second == best) {
-                    out.push_back(best);
-                    i += 2;
-                    continue;
-                }
-            }
-            out.push_back(text[i++]);
+            const bool hit = i + 1 < text.size() && candidate(i) == best;
+            out.push_back(hit ? best : text[i]);
+            if (drop) pos_out.push_back(pos[i]);
+            i += hit ? 2 : 1;
         }
         text.swap(out);
+        pos.swap(pos_out);
     }
 }
 
@@ -436,6 +450,7 @@ int Tokenizer::split_on_device(const char *text, const uint64_t *doc_off, uint64
 // :653-722.  device < 0: internal_encode on the host (below); device >= 0: on that HIP device (mbpe_encoder_encode,
 // with an encoder that is kept until the merges change)
 std::vector<Token> Tokenizer::encode(const std::string &text, bool verbose, int device, bool device_split) {
+    check_dropout_order();
     if (device >= 0 && device_split) {
         const uint64_t doc_off[2] = {0, text.size()};
         DeviceSplit ds;
@@ -468,7 +483,7 @@ std::vector<Token> Tokenizer::encode(const std::string &text, bool verbose, int 
     } else {
         for (size_t c = 0; c + 1 < off.size(); ++c) {           // internal_encode :370-377 + flatten :713-717
             auto vec = text_to_vector(buf.data() + off[c], off[c + 1] - off[c]);
-            auto enc = rank_order_ ? encode_rank_ordered(std::move(vec)) : internal_internal_encode(std::move(vec));
+            auto enc = rank_order_ ? encode_rank_ordered(std::move(vec), off[c]) : internal_internal_encode(std::move(vec));
             out.insert(out.end(), enc.begin(), enc.end());
         }
     }
@@ -529,6 +544,10 @@ int Tokenizer::encode_ranges(const char *text, const uint64_t *doc_off, uint64_t
     tokens->clear();
     ranges->clear();
     doc_tok_off->assign(n_docs + 1, 0);
+    if (drop_threshold_ && !rank_order_) {
+        set_last_error("encode: dropout needs the rank order (mbpe_tok_set_encode_order)");
+        return MBPE_ERR_ARG;
+    }
     uint64_t n = 0;
     if (device >= 0 && device_split) {
         // the splitter's text is the original text: tok_byte_off is in the coordinates of the documents' buffer
@@ -570,7 +589,7 @@ int Tokenizer::encode_ranges(const char *text, const uint64_t *doc_off, uint64_t
         // the reference loop; a token covers as many bytes as its vocabulary entry has
         for (uint64_t c = 0; c < n_chunks; ++c) {
             auto vec = text_to_vector(buf.data() + off[c], off[c + 1] - off[c]);
-            auto enc = rank_order_ ? encode_rank_ordered(std::move(vec)) : internal_internal_encode(std::move(vec));
+            auto enc = rank_order_ ? encode_rank_ordered(std::move(vec), off[c]) : internal_internal_encode(std::move(vec));
             uint64_t pos = off[c];
             for (Token t : enc) {
                 tokens->push_back(t);
@@ -923,6 +942,16 @@ int mbpe_tok_set_encode_order(mbpe_tokenizer *t, int rank_order) {
         return MBPE_ERR_ARG;
     }
     t->t->set_rank_order(rank_order == 1);
+    return MBPE_OK;
+}
+
+int mbpe_tok_set_encode_dropout(mbpe_tokenizer *t, uint64_t threshold, uint64_t seed) {
+    if (!t) return MBPE_ERR_ARG;
+    if (threshold > mbpe::kDropoutOne) {
+        mbpe_host::set_last_error("mbpe_tok_set_encode_dropout: threshold must not exceed 2^32");
+        return MBPE_ERR_ARG;
+    }
+    t->t->set_dropout(threshold, seed);
     return MBPE_OK;
 }
 

@@ -76,6 +76,12 @@ public:
     // default) the reference's greedy passes, true rank order (encode_rank_ordered below; mbpe_tok_set_encode_order)
     void set_rank_order(bool on) { rank_order_ = on; }
     bool rank_order() const { return rank_order_; }
+    // BPE-dropout of encode and its batch forms (mbpe_tok_set_encode_dropout; dropout.h): threshold in [0, 2^32], 0 =
+    // off.  With a threshold above 0 the order has to be the rank order: every encode route throws / returns
+    // MBPE_ERR_ARG otherwise.  An instance's position is in the buffer the route hands the encoder: the original text
+    // with the device split, the chunk buffer of append_chunks / batch_chunks with the host split (host loop and
+    // device alike) -- the same whenever that buffer is the text
+    void set_dropout(uint64_t threshold, uint64_t seed) { drop_threshold_ = threshold; drop_seed_ = seed; }
     // the option "unicode" of every device split made from here on (mbpe_tok_set_split_unicode)
     void set_split_unicode(bool on) { split_unicode_ = on; }
     // :725-751; device >= 0 expands the tokens on that HIP device (mbpe_decode_tokens) instead of the host loop
@@ -114,8 +120,11 @@ private:
     std::vector<Token> internal_internal_encode(std::vector<Token> text) const; // :325-367
     // the rank-ordered counterpart: of the adjacent pairs that are in merges_lookup, every occurrence of the one with
     // the smallest id is replaced, left to right and non-overlapping; repeated until no pair is left.  For a trained
-    // table this replays the merges in order: the trainer's segmentation
-    std::vector<Token> encode_rank_ordered(std::vector<Token> text) const;
+    // table this replays the merges in order: the trainer's segmentation.
+    // With dropout a pair whose instance (byte start of its left token, merged id) is dropped is no candidate: every
+    // token carries its byte start, base = the chunk's offset in the buffer the encoder reads (off[c])
+    std::vector<Token> encode_rank_ordered(std::vector<Token> text, uint64_t base) const;
+    void check_dropout_order() const;      // throws CodedError(MBPE_ERR_ARG): dropout with the greedy order
     void rebuild_vocab();
     void drop_decoder();                   // the merges or the specials changed
     void drop_encoder();                   // the merges changed (special tokens do not enter the lookup table)
@@ -162,6 +171,7 @@ private:
     bool encode_split_ = false;
     bool split_unicode_ = false;
     bool rank_order_ = false;
+    uint64_t drop_threshold_ = 0, drop_seed_ = 0;
 };
 
 }  // namespace mbpe_host

@@ -39,6 +39,7 @@ EXPORTS = [
     "mbpe_encoder_encode_endmask", "mbpe_encoder_encode_batch_endmask", "mbpe_encoder_encode_byteoff",
     "mbpe_encoder_encode_endmask_byteoff", "mbpe_split_unicode_table",
     "mbpe_merges_check", "mbpe_train_begin_from", "mbpe_train_from",
+    "mbpe_dropout_threshold", "mbpe_encoder_set_dropout",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -48,7 +49,7 @@ TOK_EXPORTS = [
     "mbpe_tok_encode_batch_packed_device", "mbpe_tok_decode_padded_device", "mbpe_tok_encode_batch_aux_device",
     "mbpe_tok_train_split_device", "mbpe_tok_set_encode_split", "mbpe_tok_set_split_unicode",
     "mbpe_tok_set_encode_order", "mbpe_tok_train_continue", "mbpe_tok_encode_byteoff",
-    "mbpe_tok_encode_batch_byteoff_device",
+    "mbpe_tok_encode_batch_byteoff_device", "mbpe_tok_set_encode_dropout",
 ]
 
 
@@ -240,6 +241,9 @@ def lib():
     L.mbpe_tok_set_encode_split.argtypes = [vp, i32]
     L.mbpe_tok_set_split_unicode.argtypes = [vp, i32]
     L.mbpe_tok_set_encode_order.argtypes = [vp, i32]
+    L.mbpe_dropout_threshold.argtypes = [ctypes.c_double, vp]
+    L.mbpe_encoder_set_dropout.argtypes = [vp, u64, u64]
+    L.mbpe_tok_set_encode_dropout.argtypes = [vp, u64, u64]
     L.mbpe_split_unicode_table.argtypes = [vp, vp, vp, u32, vp, vp]
     L.mbpe_tok_set_merges.argtypes = [vp, vp, u32]
     L.mbpe_tok_get_merges.argtypes = [vp, vp, u32, vp]
@@ -518,6 +522,14 @@ SINGLE = np.dtype([("start", np.uint64), ("len", np.uint64), ("id", np.uint32), 
 SPLIT_RAW = 0xFFFFFFFF      # MBPE_SPLIT_RAW: the name of a range that is a NUL-led part
 
 
+def dropout_threshold(p):
+    """A dropout probability in [0, 1] -> the threshold floor(p * 2^32) of mbpe_encoder_set_dropout
+    (mbpe_dropout_threshold; NaN or a value outside [0, 1] raises the library's error)."""
+    t = ctypes.c_uint64()
+    _check(lib().mbpe_dropout_threshold(float(p), ctypes.byref(t)))
+    return t.value
+
+
 def _singles(rows):
     """rows (start, len, id) -> an array of mbpe_single."""
     out = np.zeros(0 if rows is None else len(rows), dtype=SINGLE)
@@ -530,8 +542,9 @@ class Encoder:
     """One mbpe_encoder: internal_encode (Tokenizer.h:325-377) on a HIP device with the lookup table, the stream and
     the work buffers kept between calls."""
 
-    def __init__(self, merges, device=0, rank_order=False):
-        """rank_order: the option "rank_order" from the start (set_option changes it between calls)."""
+    def __init__(self, merges, device=0, rank_order=False, dropout=0.0, seed=0):
+        """rank_order: the option "rank_order" from the start (set_option changes it between calls).
+        dropout, seed: BPE-dropout from the start (set_dropout changes it between calls); needs rank_order."""
         self._h = ctypes.c_void_p()
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1, 2)
         _check(lib().mbpe_encoder_create(device, m.ctypes.data if len(m) else None, len(m), ctypes.byref(self._h)))
@@ -539,6 +552,8 @@ class Encoder:
         self.n_tokens = 0
         if rank_order:
             self.set_option("rank_order", 1)
+        if dropout or seed:
+            self.set_dropout(dropout, seed)
 
     def close(self):
         if self._h:
@@ -559,6 +574,13 @@ class Encoder:
 
     def set_option(self, name, value):
         _check(lib().mbpe_encoder_set_option(self._h, name.encode(), int(value)))
+
+    def set_dropout(self, p, seed=0):
+        """BPE-dropout for the calls that follow (mbpe_encoder_set_dropout): a merge instance -- (byte start of the
+        pair's left token in the call's text, merged id) -- is skipped with probability p, decided by a hash of
+        (seed, position, id).  Rank order only: an encode call with p > 0 and the greedy order raises MbpeError(ERR_ARG).
+        p = 0 is plain rank order, p = 1 leaves the bytes."""
+        _check(lib().mbpe_encoder_set_dropout(self._h, dropout_threshold(p), int(seed) & 0xFFFFFFFFFFFFFFFF))
 
     def encode(self, data, chunk_off=None, offsets=False, dtype=np.uint32, byte_off=False):
         """Host text -> host tokens of dtype uint32 or uint16, or (tokens, chunk_tok_off) with offsets=True: the
@@ -1294,14 +1316,15 @@ class Tokenizer:
     def load(self, path, verbose=False):
         _check(lib().mbpe_tok_load(self._h, os.fsencode(path), int(verbose)))
 
-    def _encode_split(self, device_split, order="greedy"):
+    def _encode_split(self, device_split, order="greedy", dropout=0.0, seed=0):
         if order not in ("greedy", "rank"):
             raise ValueError('order must be "greedy" or "rank"')
         _check(lib().mbpe_tok_set_encode_order(self._h, int(order == "rank")))
+        _check(lib().mbpe_tok_set_encode_dropout(self._h, dropout_threshold(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF))
         _check(lib().mbpe_tok_set_encode_split(self._h, int(bool(device_split))))
         _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
 
-    def encode(self, data, device=None, device_split=False, order="greedy", byte_ranges=False):
+    def encode(self, data, device=None, device_split=False, order="greedy", byte_ranges=False, dropout=0.0, seed=0):
         """device None: internal_encode on the host; an int: on that HIP device (mbpe_tok_encode_device).
         device_split (here and in the batch calls; only with a device): the text is cut at the special tokens and split
         into chunks on the device too (mbpe_tok_set_encode_split); same tokens, gpt2 / gpt4 patterns only.  "unicode"
@@ -1309,9 +1332,14 @@ class Tokenizer:
         order (here and in the batch calls; host and device): "greedy", the reference's passes that replace any pair
         they find, or "rank": a chunk's pair with the lowest merge id first, which for a trained model is the
         segmentation the trainer left in its stream (mbpe_tok_set_encode_order).  Anything else is ValueError.
+        dropout, seed (here and in the batch calls; host and device; mbpe_tok_set_encode_dropout): BPE-dropout, a merge
+        instance is skipped with probability dropout, decided by a hash of (seed, byte position, merged id); only with
+        order="rank" -- with "greedy" and dropout > 0 the library's error is raised.  Positions are those of the
+        buffer the route hands the encoder, so the host loop and the device over the host split always agree, and
+        they agree with device_split when the text has no special token and the pattern is basic, gpt2 or gpt4.
         byte_ranges=True (mbpe_tok_encode_byteoff): -> (tokens, ranges[n, 2] uint64), token j stands for
         data[ranges[j, 0]:ranges[j, 1]] (a special token: the occurrence of its name)."""
-        self._encode_split(device_split, order)
+        self._encode_split(device_split, order, dropout, seed)
         text = _u8(data)
         n = ctypes.c_uint64()
         out = np.zeros(max(len(text), 1), dtype=np.uint32)
@@ -1329,11 +1357,12 @@ class Tokenizer:
                                                 out.ctypes.data, len(out), ctypes.byref(n)))
         return out[:n.value].copy()
 
-    def encode_batch(self, texts, device=0, device_split=False, order="greedy", byte_ranges=False):
+    def encode_batch(self, texts, device=0, device_split=False, order="greedy", byte_ranges=False, dropout=0.0,
+                     seed=0):
         """encode() of every text in one device call (mbpe_tok_encode_batch_device) -> list of uint32 arrays; with
         byte_ranges=True (mbpe_tok_encode_batch_byteoff_device) a list of (tokens, ranges[n, 2] uint64) pairs, the
-        ranges relative to each text's first byte."""
-        self._encode_split(device_split, order)
+        ranges relative to each text's first byte.  With dropout, positions run over the texts laid end to end."""
+        self._encode_split(device_split, order, dropout, seed)
         parts = [bytes(_u8(t)) for t in texts]
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
         if parts:
@@ -1356,12 +1385,12 @@ class Tokenizer:
 
     def encode_batch_padded(self, texts, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
                             pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
-                            device_split=False, order="greedy"):
+                            device_split=False, order="greedy", dropout=0.0, seed=0):
         """Every text split like encode(), encoded and packed in one device call
         (mbpe_tok_encode_batch_packed_device) -> (ids [n_rows, seq_len], lengths [n_rows]) as numpy arrays; with
         out_ptr= and len_ptr= (device memory for cap_rows rows) the matrix stays on the device and the row count is
         returned.  bos_id / eos_id may be special-token ids.  layout "packed" gives the MBPE_PACK_PACKED rows."""
-        self._encode_split(device_split, order)
+        self._encode_split(device_split, order, dropout, seed)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         parts = [bytes(_u8(t)) for t in texts]
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
@@ -1387,11 +1416,12 @@ class Tokenizer:
     def encode_batch_aux(self, texts, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
                          pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
                          labels=False, positions=False, segments=False, cu_seqlens=False, ignore_label=-100,
-                         labels_ptr=None, pos_ptr=None, seg_ptr=None, device_split=False, order="greedy"):
+                         labels_ptr=None, pos_ptr=None, seg_ptr=None, device_split=False, order="greedy", dropout=0.0,
+                         seed=0):
         """encode_batch_padded plus labels, positions, segments and cu_seqlens (mbpe_tok_encode_batch_aux_device): its
         arguments and those of pack_tokens_aux, whose dict (or, with out_ptr=, row count) is returned.  The documents'
         token offsets of the call: self.doc_tok_off."""
-        self._encode_split(device_split, order)
+        self._encode_split(device_split, order, dropout, seed)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label)
         parts = [bytes(_u8(t)) for t in texts]
