@@ -167,6 +167,36 @@ MBPE_API int mbpe_load_corpus(mbpe_ctx *ctx, const uint8_t *text, uint64_t n_byt
 MBPE_API int mbpe_load_corpus_endmask(mbpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int text_on_device,
                                       const uint8_t *endmask_dev);
 
+/* A corpus of chunks with weights: chunk c stands for weights[c] occurrences of its bytes, and every pair count is the
+ * weight-sum over the chunks -- the counts of the corpus in which each chunk is written out weights[c] times.  This is
+ * how a corpus is trained on its distinct chunks (mbpe_dedup_*, or a word-count table of the caller's).  The result
+ * equals the training on the expanded corpus for both tie-breaks, provided that, for `first`, the chunks stand in the
+ * order of their first occurrence there.
+ *   mbpe_load_corpus_weighted          as mbpe_load_corpus with chunk_off required (NUL rule included); weights: n_chunks
+ *                                      u32 of host memory
+ *   mbpe_load_corpus_endmask_weighted  as mbpe_load_corpus_endmask (the NUL rule is the caller's); weights: n_weights
+ *                                      u32, host memory or, with weights_on_device, device memory (4-byte aligned, copied):
+ *                                      what mbpe_dedup_result returns goes in without a host round trip.  n_weights
+ *                                      must equal the mask's population count (MBPE_ERR_ARG)
+ * A weight of 0, or of 2^31 or more, is MBPE_ERR_ARG (host weights are checked on the host, device weights by a kernel).
+ * After such a load
+ *   - mbpe_train_begin and mbpe_train_begin_from run on 32-bit tokens (csrc/wide.h) from merge n_prior on, 0 included,
+ *     whatever the vocabulary (up to MBPE_MAX_VOCAB_WIDE) and with either tie-break; the options "wide_from",
+ *     "first_wide", "resume_wide" and "chunk_barrier" have no effect.  One merge per pass: on a stream of unique chunks
+ *     a pass is short, but a large stream trains slowly this way.  Several ranks: MBPE_ERR_STATE.
+ *   - a pair whose weighted count reaches 2^31 (or wraps 2^32) is MBPE_ERR_OVERFLOW from the begin; 2^31 - 1 trains
+ *   - mbpe_pair_count_u8 returns MBPE_ERR_STATE
+ *   - mbpe_train_steps, _train_sequences, _train_result, _get_stream, _get_pairs, _decode_stream and _get_stats behave as
+ *     after the handover to 32-bit tokens: stream and decode are those of the chunks that were loaded (the unique
+ *     text), counts in _train_result and _get_pairs are the weighted ones.  The zero-count tail (lexical) and the early
+ *     end (`first`) are those of the 32-bit loop.
+ * Device memory beside that loop's: 4 B per weight, and two u32 arrays of one entry per token. */
+MBPE_API int mbpe_load_corpus_weighted(mbpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off,
+                                       uint64_t n_chunks, int text_on_device, const uint32_t *weights);
+MBPE_API int mbpe_load_corpus_endmask_weighted(mbpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                               const uint8_t *endmask_dev, const uint32_t *weights, uint64_t n_weights,
+                                               int weights_on_device);
+
 /* The same for chunks given as ranges [starts[c], ends[c]) (ascending, not overlapping) that need
  * not tile the text: bytes outside every chunk are not part of the corpus, as in the reference's
  * match loop (Tokenizer.h:506-540).  When there are such bytes the library trains on a packed copy
@@ -1043,6 +1073,52 @@ MBPE_API int  mbpe_splitter_alloc_count(const mbpe_splitter *s, uint64_t *n_out)
 
 /* The host spans of the latest call: how many, and (optional) the text bytes they hold. */
 MBPE_API int  mbpe_splitter_host_spans(const mbpe_splitter *s, uint64_t *n_spans_out, uint64_t *n_bytes_out);
+
+/* ---- chunk deduplication on the device (csrc/dedup.hip, dedup.h) ------------------------------------------------------
+ * The distinct chunks of a chunked text in the order of their first occurrence, packed into one text with an end mask
+ * in the layout mbpe_load_corpus_endmask reads, and for unique chunk j
+ *   weights[j]      (u32) how often it occurs in the input; the weights add up to the input's chunk count
+ *   first_chunk[j]  (u64) the index of its first occurrence among the input's chunks
+ * Equality is decided by the bytes; the hash only places a chunk in a table, so the result is deterministic and
+ * depends neither on the hash function nor on a collision.  Together with mbpe_load_corpus_endmask_weighted a training
+ * runs on the unique chunks and still counts what the whole corpus holds.
+ *
+ * A deduper has its own non-blocking stream and owns its device buffers; a repeat call of no larger size allocates
+ * nothing (mbpe_dedup_alloc_count).  Device memory: 16 B per chunk (end offset, table position) plus a table of
+ * 12 B x the power of two at or above 2 x n_chunks (24 .. 48 B per chunk), 16 B per 256 chunks and 8 B per 16 KiB of
+ * text for the scans; the result takes 1 1/8 B per unique byte and 12 B per unique chunk.  mbpe_dedup_chunks adds the
+ * uploaded text (host text only), 1/8 B per byte for its mask and, with empty chunks, 8 B per chunk.
+ *
+ *   mbpe_dedup_chunks_endmask  text_dev (16-byte aligned) and endmask_dev (4-byte aligned, the layout of
+ *                              mbpe_splitter_split) are read in place.  Bytes behind the last end bit belong to no
+ *                              chunk.  2^32 - 1 chunks or more: MBPE_ERR_ARG, here once the device has counted them.
+ *   mbpe_dedup_chunks          chunk_off as for mbpe_load_corpus (host, required); the mask is built on the host the same
+ *                              way, except that the NUL rule is not applied: deduplication is about bytes.  Empty
+ *                              chunks vanish; first_chunk still counts them.  n_chunks >= 2^32 - 1 is MBPE_ERR_ARG.
+ *   n_unique_out (required), n_unique_bytes_out (optional)   the result's sizes
+ *   mbpe_dedup_result          device views of the latest result, valid until the deduper's next call (any may be NULL)
+ *   mbpe_dedup_get             host copies: text_out (cap_bytes), chunk_off_out (cap_chunks + 1 offsets), weights_out and
+ *                              first_chunk_out (cap_chunks each); any may be NULL.  A cap below the size the dedup
+ *                              call reported is MBPE_ERR_ARG and nothing is written.
+ *   options   "max_chunk_bytes"  default 256: a longer chunk is never hashed and passes through as a unique chunk of
+ *                                weight 1 at its place (a duplicate of it appears twice: still exact)
+ *             "hash_bits"        default 64; 0 .. 64: the hash is cut to that many bits (tests: collisions)
+ * Arguments are checked before the device is touched.  No CPU fallback: MBPE_ERR_NO_DEVICE without a HIP device. */
+typedef struct mbpe_dedup mbpe_dedup;
+MBPE_API int  mbpe_dedup_create(int device_id, mbpe_dedup **out);
+MBPE_API void mbpe_dedup_destroy(mbpe_dedup *d);
+MBPE_API int  mbpe_dedup_chunks_endmask(mbpe_dedup *d, const uint8_t *text_dev, uint64_t n_bytes, const uint8_t *endmask_dev,
+                                        uint64_t *n_unique_out, uint64_t *n_unique_bytes_out);
+MBPE_API int  mbpe_dedup_chunks(mbpe_dedup *d, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                const uint64_t *chunk_off, uint64_t n_chunks, uint64_t *n_unique_out,
+                                uint64_t *n_unique_bytes_out);
+MBPE_API int  mbpe_dedup_result(const mbpe_dedup *d, const uint8_t **text_dev_out, const uint8_t **endmask_dev_out,
+                                const uint32_t **weights_dev_out, const uint64_t **first_chunk_dev_out);
+MBPE_API int  mbpe_dedup_get(mbpe_dedup *d, uint8_t *text_out, uint64_t *chunk_off_out, uint32_t *weights_out,
+                             uint64_t *first_chunk_out, uint64_t cap_bytes, uint64_t cap_chunks);
+MBPE_API int  mbpe_dedup_set_option(mbpe_dedup *d, const char *name, int64_t value);
+MBPE_API int  mbpe_dedup_kernel_ms(const mbpe_dedup *d, float *ms_out);
+MBPE_API int  mbpe_dedup_alloc_count(const mbpe_dedup *d, uint64_t *n_out);
 
 #ifdef __cplusplus
 }

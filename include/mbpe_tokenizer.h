@@ -164,6 +164,21 @@ MBPE_API int mbpe_tok_set_encode_dropout(mbpe_tokenizer *t, uint64_t threshold, 
  * calls, whose kept splitter is re-configured, not re-created.  Same results; otherwise without effect. */
 MBPE_API int mbpe_tok_set_split_unicode(mbpe_tokenizer *t, int on);
 
+/* Training on the distinct chunks with their counts: 0 (the default) or 1; anything else is MBPE_ERR_ARG.  While it is
+ * on, mbpe_tok_train, mbpe_tok_train_split_device and mbpe_tok_train_continue split as they do (host, device,
+ * mbpe_tok_set_split_unicode), then deduplicate the chunks on the device (mbpe_dedup_*, mbpe.h), load the unique
+ * chunks with their counts as weights (mbpe_load_corpus_*_weighted) and train on those: the same merges, the same
+ * counts, the same verbose lines, .model and .vocab, for both tie-breaks.  After the device split neither text nor mask
+ * returns to the host; after the host split the packed chunks that mbpe_load_corpus_ranges would train on are
+ * deduplicated, and the unique ones come back once so that the NUL rule is applied as ever.
+ * The training then runs on the 32-bit loop, one merge per pass over the unique chunks.  That wins where the default
+ * route takes a pass over the whole corpus per merge as well: the `first` tie-break, vocabularies beyond the 16-bit
+ * slot format, a continued training.  It loses against the lexical tie-break within the slot format, which merges
+ * thousands of pairs per pass.  A tokenizer without a pattern has one chunk, the whole text: it passes through the
+ * deduper unhashed and trains on the 32-bit loop -- correct and slow; the route is not switched silently.
+ * One rank.  A chunk above 256 bytes is never merged with its duplicates (it appears as often as it occurs). */
+MBPE_API int mbpe_tok_set_train_dedup(mbpe_tokenizer *t, int on);
+
 /* decode, Tokenizer.h:725-751.  bytes_out may be NULL to query the length. */
 MBPE_API int mbpe_tok_decode(mbpe_tokenizer *t, const uint32_t *tokens, uint64_t n, int verbose,
                              uint8_t *bytes_out, uint64_t cap, uint64_t *n_out);

@@ -128,6 +128,9 @@ struct mbpe_ctx {
     bool barrier = false;        // this training keeps the chunk ends as barrier slots (mbpe_dev.h: kBarrier)
     bool loaded = false;
     bool inert = false;          // whole corpus collapses to one token (NUL quirk, basic)
+    bool weighted = false;       // chunks come with weights (mbpe_load_corpus_weighted): the training runs on 32-bit tokens
+    uint32_t *d_weights = nullptr;   // ... one per end bit of the mask, in order
+    uint64_t n_weights = 0;
 
     uint32_t *pc_scratch = nullptr;   // pair-count scan: per-workgroup histogram snapshots (kept for the context's life)
     uint32_t *pc_bp = nullptr;        // mbpe_pair_count_u8: the 65,536-entry result table, then the 64-bit sum of its bins
@@ -249,6 +252,7 @@ struct mbpe_ctx {
     uint32_t *wtok[2] = {nullptr, nullptr};
     int wcur = 0;
     uint32_t *wval = nullptr, *wscratch = nullptr;
+    uint32_t *wwt[2] = {nullptr, nullptr};   // weighted corpus: the weight of every token's chunk, beside wtok[]
     WideTable wtab = {};
     WideCtl *wctl = nullptr;
     WideBest *wbest = nullptr;
@@ -366,6 +370,7 @@ void free_training(mbpe_ctx *c) {
     tfree(c, c->xf);
     tfree(c, c->tally);
     tfree(c, c->wtok[0]); tfree(c, c->wtok[1]); tfree(c, c->wval); tfree(c, c->wscratch);
+    tfree(c, c->wwt[0]); tfree(c, c->wwt[1]);
     tfree(c, c->wtab.keys); tfree(c, c->wtab.cnts); tfree(c, c->wctl); tfree(c, c->wbest); tfree(c, c->warg);
     tfree(c, c->wfs); tfree(c, c->wtally);
     c->wtab = {};
@@ -386,6 +391,9 @@ void free_training(mbpe_ctx *c) {
 void free_corpus(mbpe_ctx *c) {
     dfree(c->d_text_owned);
     dfree(c->d_endmask);
+    dfree(c->d_weights);
+    c->n_weights = 0;
+    c->weighted = false;
     c->d_text = nullptr;
     c->loaded = false;
 }
@@ -792,6 +800,102 @@ int mbpe_load_corpus_endmask(mbpe_ctx *c, const uint8_t *text, uint64_t n_bytes,
                        hipMemcpyDeviceToDevice);
 }
 
+// The weights of a loaded chunked corpus, one per end bit of its mask: from here on the context trains weighted.
+static int attach_weights(mbpe_ctx *c, const uint32_t *weights, uint64_t n_weights, hipMemcpyKind kind) {
+    HIPCHK(hipMalloc(&c->d_weights, std::max<uint64_t>(n_weights, 1) * 4));
+    if (n_weights) HIPCHK(hipMemcpyAsync(c->d_weights, weights, n_weights * 4, kind, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->n_weights = n_weights;
+    c->weighted = true;
+    return MBPE_OK;
+}
+
+static bool weight_ok(uint32_t w) { return w != 0u && w < 0x80000000u; }
+
+int mbpe_load_corpus_weighted(mbpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off,
+                              uint64_t n_chunks, int text_on_device, const uint32_t *weights) {
+    if (!c || (!text && n_bytes) || !chunk_off || (!weights && n_chunks)) {
+        mbpe_host::set_last_error("mbpe_load_corpus_weighted: NULL argument");
+        return MBPE_ERR_ARG;
+    }
+    for (uint64_t i = 0; i < n_chunks; ++i)
+        if (!weight_ok(weights[i])) {
+            mbpe_host::set_last_error("mbpe_load_corpus_weighted: weight " + std::to_string(i) + " is 0, or 2^31 or more");
+            return MBPE_ERR_ARG;
+        }
+    int rc = mbpe_load_corpus(c, text, n_bytes, chunk_off, n_chunks, text_on_device);
+    if (rc != MBPE_OK) return rc;
+    // One weight per end bit of the mask the load built: an empty chunk has none, a chunk the NUL rule made inert has
+    // one per byte (every byte of it is a chunk end; no pair starts there, so the value never counts).
+    std::vector<uint8_t> tmp;
+    const uint8_t *h_text = text;
+    if (text_on_device && n_bytes) {
+        tmp.resize(n_bytes);
+        HIPCHK(hipMemcpy(tmp.data(), text, n_bytes, hipMemcpyDeviceToHost));
+        h_text = tmp.data();
+    }
+    std::vector<uint32_t> per_end;
+    per_end.reserve(n_chunks);
+    for (uint64_t ci = 0; ci < n_chunks; ++ci) {
+        const uint64_t s = chunk_off[ci], e = chunk_off[ci + 1];
+        if (e == s) continue;
+        const bool inert = h_text[s] == 0 && stoi_parses(h_text + s + 1, e - s - 1);
+        per_end.insert(per_end.end(), inert ? e - s : 1, weights[ci]);
+    }
+    if (per_end.size() != c->n_barriers) {
+        mbpe_host::set_last_error("mbpe_load_corpus_weighted: the weights and the mask's chunk ends disagree");
+        c->loaded = false;
+        return MBPE_ERR_STATE;
+    }
+    rc = attach_weights(c, per_end.data(), per_end.size(), hipMemcpyHostToDevice);
+    if (rc != MBPE_OK) c->loaded = false;
+    return rc;
+}
+
+int mbpe_load_corpus_endmask_weighted(mbpe_ctx *c, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                      const uint8_t *endmask_dev, const uint32_t *weights, uint64_t n_weights,
+                                      int weights_on_device) {
+    if (!c || (!weights && n_weights)) {
+        mbpe_host::set_last_error("mbpe_load_corpus_endmask_weighted: NULL argument");
+        return MBPE_ERR_ARG;
+    }
+    if (weights_on_device && ((uintptr_t)weights & 3)) {
+        mbpe_host::set_last_error("mbpe_load_corpus_endmask_weighted: device weights must be 4-byte aligned");
+        return MBPE_ERR_ARG;
+    }
+    if (!weights_on_device)
+        for (uint64_t i = 0; i < n_weights; ++i)
+            if (!weight_ok(weights[i])) {
+                mbpe_host::set_last_error("mbpe_load_corpus_endmask_weighted: weight " + std::to_string(i) +
+                                          " is 0, or 2^31 or more");
+                return MBPE_ERR_ARG;
+            }
+    int rc = mbpe_load_corpus_endmask(c, text, n_bytes, text_on_device, endmask_dev);
+    if (rc != MBPE_OK) return rc;
+    auto refuse = [&](const std::string &msg) {
+        free_corpus(c);
+        mbpe_host::set_last_error(msg);
+        return MBPE_ERR_ARG;
+    };
+    if (n_weights != c->n_barriers)
+        return refuse("mbpe_load_corpus_endmask_weighted: " + std::to_string(n_weights) + " weights for a mask of " +
+                      std::to_string(c->n_barriers) + " chunk ends");
+    if (weights_on_device && n_weights) {
+        uint32_t *d_flag = nullptr, flag = 0;
+        HIPCHK(hipMalloc(&d_flag, 4));
+        hipError_t e = hipMemsetAsync(d_flag, 0, 4, c->stream);
+        if (e == hipSuccess) { launch_wide_check_weights(c->stream, weights, n_weights, d_flag); e = hipGetLastError(); }
+        if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        (void)hipFree(d_flag);
+        HIPCHK(e);
+        if (flag) return refuse("mbpe_load_corpus_endmask_weighted: a weight is 0, or 2^31 or more");
+    }
+    rc = attach_weights(c, weights, n_weights, weights_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
+    if (rc != MBPE_OK) c->loaded = false;
+    return rc;
+}
+
 int mbpe_load_corpus_ranges(mbpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *starts,
                             const uint64_t *ends, uint64_t n_chunks, int text_on_device) {
     if (!c || (!text && n_bytes) || ((!starts || !ends) && n_chunks)) {
@@ -846,6 +950,7 @@ static uint64_t pairs_scanned(const mbpe_ctx *c) {
 int mbpe_pair_count_u8(mbpe_ctx *c, uint32_t *table65536_out) {
     if (!c) return MBPE_ERR_ARG;
     if (!c->loaded) { mbpe_host::set_last_error("mbpe_pair_count_u8: no corpus loaded"); return MBPE_ERR_STATE; }
+    if (c->weighted) { mbpe_host::set_last_error("mbpe_pair_count_u8: the corpus has chunk weights"); return MBPE_ERR_STATE; }
     HIPCHK(hipSetDevice(c->device));
     int rcs = ensure_pc_scratch(c);
     if (rcs != MBPE_OK) return rcs;
@@ -1504,10 +1609,13 @@ static int start_unit_external(mbpe_ctx *c, bool batched) {
     return suspend(c, Phase::SeqDeltas);
 }
 
+static int weighted_begin(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prior, uint32_t n_prior);
+
 int mbpe_train_begin(mbpe_ctx *c, uint32_t vocab_size) {
     if (!c) return MBPE_ERR_ARG;
     if (!c->loaded) { mbpe_host::set_last_error("mbpe_train_begin: no corpus loaded"); return MBPE_ERR_STATE; }
     if (vocab_size < 256) { mbpe_host::set_last_error("vocab_size must be >= 256"); return MBPE_ERR_ARG; }
+    if (c->weighted) return weighted_begin(c, vocab_size, nullptr, 0);
     const uint32_t vmax = !c->chunked ? MBPE_MAX_VOCAB_BASIC : c->opt_barrier == 0 ? MBPE_MAX_VOCAB_ENDBIT : MBPE_MAX_VOCAB_CHUNKED;
     c->barrier = c->chunked && (c->opt_barrier == 1 || (c->opt_barrier != 0 && vocab_size > MBPE_MAX_VOCAB_ENDBIT));
     // Beyond the 16-bit slot format (Token is a uint32_t in the reference, Tokenizer.h:37-38) the training runs its first
@@ -1622,6 +1730,7 @@ int mbpe_train_begin_from(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prio
     }
     int rc = mbpe_merges_check(prior_merges, n_prior);
     if (rc != MBPE_OK) return rc;
+    if (c->weighted) return weighted_begin(c, vocab_size, prior_merges, n_prior);
     if (is_multi(c)) {
         mbpe_host::set_last_error("mbpe_train_begin_from: continuing from existing merges runs on one rank only");
         return MBPE_ERR_STATE;
@@ -1696,6 +1805,29 @@ int mbpe_train_begin_from(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prio
     (void)hipStreamSynchronize(c->stream);      // (the kernels that read the tokens are done)
     dfree(tok);
     pool_trim(c);
+    return rc;
+}
+
+// A corpus with chunk weights trains on 32-bit tokens from merge n_prior on (0 included), whatever the vocabulary and
+// either tie-break: the text widened by the replay (an empty prior table leaves the bytes as tokens), then the route
+// of the direct continuation.  "wide_from", "first_wide", "resume_wide" and "chunk_barrier" play no part.
+static int weighted_begin(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prior, uint32_t n_prior) {
+    if (is_multi(c)) {
+        mbpe_host::set_last_error("a corpus with chunk weights trains on one rank only");
+        return MBPE_ERR_STATE;
+    }
+    if (vocab_size > MBPE_MAX_VOCAB_WIDE) {
+        mbpe_host::set_last_error("vocab_size exceeds " + std::to_string(MBPE_MAX_VOCAB_WIDE));
+        return MBPE_ERR_VOCAB;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    uint32_t *tok = nullptr;
+    uint64_t n_tok = 0;
+    int rc = replay_prior(c, prior, n_prior, &tok, &n_tok);
+    if (rc != MBPE_OK) return rc;
+    rc = wide_begin_from(c, vocab_size, &tok, n_tok, prior, n_prior);
+    if (rc != MBPE_OK) (void)hipStreamSynchronize(c->stream);
+    dfree(tok);
     return rc;
 }
 
@@ -1955,7 +2087,11 @@ static int wide_alloc_table(mbpe_ctx *c, WideTable *t, uint64_t want_entries) {
 
 // entries `merges` merges can add at most when no count exceeds `top`: per match one (x,X) and one (X,y), per merge
 // possibly the transient (X,a) of touching matches; a merge has at most `top` matches
-static uint64_t wide_headroom(unsigned long long top, uint32_t merges) { return (uint64_t)merges * (2ull * top + 2); }
+// -- and at most one per position of the stream, which bounds it where counts are weighted (a count of 10^9 on a stream
+// of ten tokens)
+static uint64_t wide_headroom(unsigned long long top, uint64_t positions, uint32_t merges) {
+    return (uint64_t)merges * (2ull * std::min<unsigned long long>(top, positions) + 2);
+}
 
 static int wide_sync(mbpe_ctx *c) {
     HIPCHK(hipMemcpyAsync(&c->h_wctl, c->wctl, sizeof(WideCtl), hipMemcpyDeviceToHost, c->stream));
@@ -1964,6 +2100,10 @@ static int wide_sync(mbpe_ctx *c) {
     if (c->h_wctl.err & kWideErrFull) {
         mbpe_host::set_last_error("device error: the 32-bit pair table is full");
         return MBPE_ERR_OVERFLOW;
+    }
+    if (c->h_wctl.err & kWideErrWeight) {
+        mbpe_host::set_last_error("device error: a chunk weight is 0, or 2^31 or more, or the stream has more chunks than weights");
+        return MBPE_ERR_ARG;
     }
     if (c->h_wctl.err) {
         mbpe_host::set_last_error(c->h_wctl.err & kWideErrToken
@@ -2018,7 +2158,7 @@ static int wide_convert(mbpe_ctx *c) {
     launch_wide_from_slots(c->stream, c->tok[c->cur], n_live_slots, barrier, endbit, c->wval, c->wscratch, c->wtok[0], c->wctl);
     c->wcur = 0;
     unsigned long long top = c->last_top == ~0ull ? n_tok : c->last_top;
-    rc = wide_alloc_table(c, &c->wtab, (uint64_t)c->h_ctl.n_entries + wide_headroom(top, 16));
+    rc = wide_alloc_table(c, &c->wtab, (uint64_t)c->h_ctl.n_entries + wide_headroom(top, n_tok, 16));
     if (rc != MBPE_OK) return rc;
     launch_wide_table_from16(c->stream, c->tab.ekey, c->tab.ecnt, c->h_ctl.n_entries, c->wtab, c->wctl);
     rc = wide_sync(c);
@@ -2069,17 +2209,22 @@ static int wide_begin_from(mbpe_ctx *c, uint32_t vocab_size, uint32_t **tok, uin
     if (rc != MBPE_OK) return rc;
     HIPCHK(tmalloc(c, &c->wtally, sizeof(WideTally)));
     HIPCHK(hipMemsetAsync(c->wtally, 0, sizeof(WideTally), c->stream));
+    if (c->weighted) {
+        HIPCHK(tmalloc(c, &c->wwt[0], std::max<uint64_t>(n_tok, 1) * 4));
+        HIPCHK(tmalloc(c, &c->wwt[1], std::max<uint64_t>(n_tok, 1) * 4));
+        launch_wide_token_weights(c->stream, c->wtok[0], n_tok, c->d_weights, c->n_weights, c->wwt[0], c->wscratch, c->wctl);
+    }
     const uint64_t ids = 256ull + n_prior;
     const uint64_t most = std::min<uint64_t>({n_tok ? n_tok - 1 : 0, ids * ids, 1ull << 30});
     rc = wide_alloc_table(c, &c->wtab, std::max<uint64_t>(most, 1));
     if (rc != MBPE_OK) return rc;
-    launch_wide_pair_count_tokens(c->stream, c->wtok[0], n_tok, (uint32_t)ids, c->wtab, c->wctl, c->wtally, c->n_cus);
+    launch_wide_pair_count_tokens(c->stream, c->wtok[0], c->wwt[0], n_tok, (uint32_t)ids, c->wtab, c->wctl, c->wtally, c->n_cus);
     WideTally h = {};
     HIPCHK(hipMemcpyAsync(&h, c->wtally, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     rc = wide_sync(c);
     if (rc != MBPE_OK) return rc;
     // the right size: the pairs there are plus what the first group of merges can add, at load factor 1/2
-    const uint64_t need = (uint64_t)c->h_wctl.n_entries + wide_headroom(h.top, 16);
+    const uint64_t need = (uint64_t)c->h_wctl.n_entries + wide_headroom(h.top, n_tok, 16);
     uint32_t bits = 12;
     while ((1ull << bits) < 2 * need && bits < 31) ++bits;
     if ((uint64_t)c->wtab.mask + 1 != (1ull << bits)) {
@@ -2114,9 +2259,9 @@ static int wide_steps(mbpe_ctx *c, uint32_t n_steps, uint32_t *done_out) {
     while (done < n_steps && c->wk < n_wide) {
         const uint32_t group = std::min<uint32_t>({16u, n_steps - done, n_wide - c->wk});
         // room for what this group can insert (load factor 1/2 at most)
-        if (2 * ((uint64_t)c->h_wctl.n_entries + wide_headroom(top, group)) > (uint64_t)c->wtab.mask + 1) {
+        if (2 * ((uint64_t)c->h_wctl.n_entries + wide_headroom(top, c->wn_upper, group)) > (uint64_t)c->wtab.mask + 1) {
             WideTable old = c->wtab;
-            int rc = wide_alloc_table(c, &c->wtab, 2 * ((uint64_t)c->h_wctl.n_entries + wide_headroom(top, group)));
+            int rc = wide_alloc_table(c, &c->wtab, 2 * ((uint64_t)c->h_wctl.n_entries + wide_headroom(top, c->wn_upper, group)));
             if (rc != MBPE_OK) return rc;
             HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->wctl->n_entries), 0, 1, c->stream));
             launch_wide_rehash(c->stream, old, c->wtab, c->wctl);
@@ -2132,7 +2277,8 @@ static int wide_steps(mbpe_ctx *c, uint32_t n_steps, uint32_t *done_out) {
                 launch_wide_first(c->stream, c->wtok[c->wcur ^ (g & 1)], c->wn_upper, c->wtab, c->wctl, c->wbest, c->warg,
                                   c->wfs);
             launch_wide_merge(c->stream, c->wtok[c->wcur ^ (g & 1)], c->wtok[c->wcur ^ (g & 1) ^ 1], c->wn_upper, c->wval,
-                              c->wscratch, c->wtab, c->wctl, 256 + c->n_target);
+                              c->wscratch, c->wtab, c->wctl, 256 + c->n_target, c->wwt[c->wcur ^ (g & 1)],
+                              c->wwt[c->wcur ^ (g & 1) ^ 1]);
         }
         HIPCHK(hipEventRecord(c->ev1, c->stream));
         int rc = wide_sync(c);

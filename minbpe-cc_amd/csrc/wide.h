@@ -34,6 +34,21 @@
 //                             flushed through the concurrent insert of the merge kernels), followed by a census of
 //                             the table that must add up to the positions counted
 //
+// CHUNK WEIGHTS (mbpe_load_corpus_weighted, mbpe_load_corpus_endmask_weighted).  A chunk's token sequence after any
+// number of merges is a function of its bytes alone, so a corpus may be given as its distinct chunks with the number of
+// occurrences of each (dedup.h): every pair count of the full corpus is the weight-sum over the unique chunks.  Such a
+// training runs here from its first merge.  A u32 array beside the tokens holds every token's chunk weight -- filled
+// at the begin from the token's rank among the end flags, carried through the compaction, a merged token keeping its
+// left half's entry -- and the pair count adds w where it added 1, k_wide_match +-w on the neighbours and the sum of
+// the matched weights on (a, b).  The kernels are templates on "weighted": the unweighted instantiations are the code
+// they were.  ctl->matches and ctl->n stay position counts; table headroom is therefore bounded by the stream's
+// positions, not by a count (a count can be 10^9 on a stream of ten tokens).
+// The `first` position search needs no change: it compares table counts with the maximum M, both weighted alike, and
+// looks for the earliest position in the stream it is given.  With the unique chunks in order of first occurrence that
+// position decides as the full corpus would: the earliest occurrence of any pair in the full corpus lies in the first
+// occurrence of its chunk (an earlier copy of the chunk would hold the pair too), so the tied pairs' first positions
+// keep their order.
+//
 // One GPU, either tie-break.  Slower per merge than the 16-bit path (one merge per pass, ~20 B of traffic per token),
 // but it turns MBPE_ERR_VOCAB into a training for GPT-4-size vocabularies.
 #ifndef MBPE_WIDE_H
@@ -60,6 +75,7 @@ constexpr uint32_t kWideErrFull = 1u;       // the table is full
 constexpr uint32_t kWideErrToken = 2u;      // the pair count met a token id that does not exist
 constexpr uint32_t kWideErrCount = 4u;      // the pair count's table does not add up to the positions counted, or a
                                             //   pair occurs 2^31 times or more
+constexpr uint32_t kWideErrWeight = 8u;     // a chunk weight of 0, or of 2^31 or more, or fewer weights than chunks
 
 // census of the pair count of a resumed stream (launch_wide_pair_count_tokens)
 struct WideTally { unsigned long long positions, total; uint32_t top, pad; };
@@ -109,8 +125,16 @@ void launch_wide_rehash(hipStream_t s, WideTable from, WideTable to, WideCtl *ct
 // adjacent pairs into the cleared table t -- k_wide_pair_count_tokens, the 64-bit-key counterpart of
 // k_pair_count_tokens -- then the table's census and its check against the positions counted.  tok: n_tok flagged
 // tokens; ids: the token ids that exist (kWideErrToken for one beyond them).  tally: zeroed by the caller.
-void launch_wide_pair_count_tokens(hipStream_t s, const uint32_t *tok, uint64_t n_tok, uint32_t ids, WideTable t,
-                                   WideCtl *ctl, WideTally *tally, int n_cus);
+// wt: NULL, or the tokens' weights (launch_wide_token_weights): a position counts that often, and the census compares
+// the table with the 64-bit sum of the weights counted.
+void launch_wide_pair_count_tokens(hipStream_t s, const uint32_t *tok, const uint32_t *wt, uint64_t n_tok, uint32_t ids,
+                                   WideTable t, WideCtl *ctl, WideTally *tally, int n_cus);
+// wt[i] = weights[number of end flags before token i], for the n_tok flagged tokens of tok; weights: n_weights u32 on
+// the device.  kWideErrWeight for a chunk without a weight and for a weight outside 1 .. 2^31 - 1.
+void launch_wide_token_weights(hipStream_t s, const uint32_t *tok, uint64_t n_tok, const uint32_t *weights,
+                               uint64_t n_weights, uint32_t *wt, uint32_t *span_scratch, WideCtl *ctl);
+// flag[0] |= 1 when one of the n device weights lies outside 1 .. 2^31 - 1
+void launch_wide_check_weights(hipStream_t s, const uint32_t *weights, uint64_t n, uint32_t *flag);
 // argmax -> ctl->a, b, count, live and best[ctl->k]; clears ctl->ran
 void launch_wide_argmax(hipStream_t s, WideTable t, WideCtl *ctl, WideBest *best, unsigned long long *scratch /* 3 * 1024 */);
 // `first` mode, after launch_wide_argmax (same scratch): among the pairs of the maximal count the one whose first
@@ -119,8 +143,10 @@ void launch_wide_first(hipStream_t s, const uint32_t *src, uint64_t n_upper, Wid
                        const unsigned long long *scratch, WideFirst *fs);
 // one merge (ctl->a, ctl->b) -> new_id_base + ctl->k over the stream src (ctl->n tokens, at most n_upper) into dst;
 // advances ctl->k, sets ctl->n.  Does nothing when ctl->k >= ctl->k_limit or the table is empty.
+// wsrc / wdst: NULL, or the weights of the tokens of src and the array that receives those of dst.
 void launch_wide_merge(hipStream_t s, const uint32_t *src, uint32_t *dst, uint64_t n_upper, uint32_t *val,
-                       uint32_t *span_scratch, WideTable t, WideCtl *ctl, uint32_t new_id_base);
+                       uint32_t *span_scratch, WideTable t, WideCtl *ctl, uint32_t new_id_base, const uint32_t *wsrc = nullptr,
+                       uint32_t *wdst = nullptr);
 
 }  // namespace mbpe
 

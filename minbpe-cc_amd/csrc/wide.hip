@@ -65,7 +65,12 @@ __global__ void k_wide_rehash(WideTable from, WideTable to, WideCtl *ctl) {
 // kWideErrToken and is never hashed or used as an address.  4 B read per token.
 constexpr int kWpThreads = 256;
 constexpr uint32_t kWpSlots = 1024, kWpProbes = 4;      // 8 KiB of keys + 4 KiB of counts
-__global__ __launch_bounds__(kWpThreads) void k_wide_pair_count_tokens(const uint32_t *__restrict__ tok, uint64_t n_tok,
+// W: a position counts wt[i] times, its chunk's weight (a corpus of unique chunks, wide.h), and the tally's
+// "positions" is the 64-bit sum of the weights counted.  An LDS count may then wrap 2^32 like the table's own count
+// it is added to; the census catches either, since the true sum no longer equals the sum of the table's counts.
+template <bool W>
+__global__ __launch_bounds__(kWpThreads) void k_wide_pair_count_tokens(const uint32_t *__restrict__ tok,
+                                                                       const uint32_t *__restrict__ wt, uint64_t n_tok,
                                                                        uint32_t ids, WideTable t, WideCtl *ctl,
                                                                        WideTally *tally) {
     __shared__ unsigned long long ckey[kWpSlots];
@@ -75,13 +80,15 @@ __global__ __launch_bounds__(kWpThreads) void k_wide_pair_count_tokens(const uin
     const uint64_t per = (n_tok + gridDim.x - 1) / gridDim.x;
     const uint64_t lo = (uint64_t)blockIdx.x * per, hi = lo + per < n_tok ? lo + per : n_tok;
     uint32_t counted = 0;
+    unsigned long long wsum = 0;
     for (uint64_t i = lo + threadIdx.x; i < hi; i += kWpThreads) {
         const uint32_t a = tok[i];
         if ((a & kTokEnd) || i + 1 >= n_tok) continue;
         const uint32_t b = tok[i + 1] & kTokIdMask;
         if (a >= ids || b >= ids) { atomicOr(&ctl->err, kWideErrToken); continue; }
         const unsigned long long key = ((unsigned long long)a << 32) | b;
-        ++counted;
+        const uint32_t w = W ? wt[i] : 1u;
+        if (W) wsum += w; else ++counted;
         uint32_t h = pair_hash(key, 64 - 10);
         static_assert(kWpSlots == 1u << 10, "pair_hash's shift above");
         bool done = false;
@@ -89,17 +96,79 @@ __global__ __launch_bounds__(kWpThreads) void k_wide_pair_count_tokens(const uin
         for (uint32_t p = 0; p < kWpProbes && !done; ++p) {
             unsigned long long k = ckey[h];
             if (k == kWideEmpty) k = atomicCAS(&ckey[h], kWideEmpty, key);
-            if (k == kWideEmpty || k == key) { atomicAdd(&ccnt[h], 1u); done = true; }
+            if (k == kWideEmpty || k == key) { atomicAdd(&ccnt[h], w); done = true; }
             h = (h + 1) & (kWpSlots - 1);
         }
-        if (!done) wide_add(t, ctl, key, 1);
+        if (!done) wide_add(t, ctl, key, (int32_t)w);
     }
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < kWpSlots; i += kWpThreads)
         if (ckey[i] != kWideEmpty) wide_add(t, ctl, ckey[i], (int32_t)ccnt[i]);
+    if (W) {
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) counted += __shfl_xor(counted, d, kWave);
-    if (lane_id() == 0 && counted) atomicAdd(&tally->positions, (unsigned long long)counted);
+        for (int d = 32; d >= 1; d >>= 1)
+            wsum += ((unsigned long long)(uint32_t)__shfl_xor((int)(wsum >> 32), d, kWave) << 32) |
+                    (uint32_t)__shfl_xor((int)wsum, d, kWave);
+        if (lane_id() == 0 && wsum) atomicAdd(&tally->positions, wsum);
+    } else {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) counted += __shfl_xor(counted, d, kWave);
+        if (lane_id() == 0 && counted) atomicAdd(&tally->positions, (unsigned long long)counted);
+    }
+}
+
+// ---- chunk weights (wide.h): every token gets the weight of its chunk ------------------------------------------------
+// the chunk of token i is the number of end flags before it: per span the flags it holds, a scan, a ranked fill
+__global__ __launch_bounds__(kSpanThreads) void k_wide_end_count(const uint32_t *__restrict__ tok, uint64_t n,
+                                                                 uint32_t *__restrict__ span_ends) {
+    const uint64_t span = span_index(), base = span * kSpan;
+    if (base >= n) return;
+    const uint32_t lane = lane_id();
+    uint32_t ends = 0;
+    for (int it = 0; it < kSpanIters; ++it) {
+        const uint64_t i = base + (uint64_t)it * kWave + lane;
+        ends += wave_count(i < n && (tok[i] & kTokEnd));
+    }
+    if (lane == 0) span_ends[span] = ends;
+}
+
+__global__ __launch_bounds__(kScanThreads) void k_wide_scan_ends(const uint32_t *__restrict__ cnt, uint64_t n,
+                                                                 unsigned long long *__restrict__ off) {
+    __shared__ unsigned long long sh[kScanThreads];
+    span_scan_sum(cnt, span_count(n), off, sh);
+}
+
+// wt[i] = weights[chunk of i]; a chunk beyond n_weights, a weight of 0 or one of 2^31 or more sets kWideErrWeight
+__global__ __launch_bounds__(kSpanThreads) void k_wide_fill_weights(const uint32_t *__restrict__ tok, uint64_t n,
+                                                                    const unsigned long long *__restrict__ span_off,
+                                                                    const uint32_t *__restrict__ weights, uint64_t n_weights,
+                                                                    uint32_t *__restrict__ wt, WideCtl *ctl) {
+    const uint64_t span = span_index(), base = span * kSpan;
+    if (base >= n) return;
+    const uint32_t lane = lane_id();
+    const unsigned long long lt = lanes_below(lane);
+    unsigned long long chunk = span_off[span];
+    for (int it = 0; it < kSpanIters; ++it) {
+        const uint64_t i = base + (uint64_t)it * kWave + lane;
+        const WaveKeep k = wave_keep(i < n && (tok[i] & kTokEnd), lt);
+        if (i < n) {
+            const unsigned long long c = chunk + k.rank;
+            uint32_t w = 1u;
+            if (c < n_weights) w = weights[c];
+            if (c >= n_weights || w == 0u || w >= 0x80000000u) { atomicOr(&ctl->err, kWideErrWeight); w = 1u; }
+            wt[i] = w;
+        }
+        chunk += k.count;
+    }
+}
+
+// flag[0] = 1 when one of the n weights is 0, or 2^31 or more
+__global__ __launch_bounds__(256) void k_wide_check_weights(const uint32_t *__restrict__ weights, uint64_t n, uint32_t *flag) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    bool bad = false;
+    for (; i < n; i += stride) { const uint32_t w = weights[i]; bad |= w == 0u || w >= 0x80000000u; }
+    if (bad) atomicOr(flag, 1u);
 }
 
 // the census of the table behind that count: the sum of its counts, the largest of them (as unsigned: a count that
@@ -327,12 +396,15 @@ __global__ __launch_bounds__(kScanThreads) void k_wide_scan_sum(const uint32_t *
     }
 }
 
+// W: the tokens' weights travel with them (a merged token stands where its left half stood and keeps that entry)
+template <bool W>
 __global__ __launch_bounds__(kSpanThreads) void k_wide_scatter(const uint32_t *__restrict__ val,
                                                                const unsigned long long *__restrict__ span_off,
-                                                               uint32_t *__restrict__ out, const WideCtl *ctl) {
+                                                               uint32_t *__restrict__ out, const WideCtl *ctl,
+                                                               const uint32_t *__restrict__ wt, uint32_t *__restrict__ wt_out) {
     // (a merge that did not run -- limit reached, empty table -- must not scatter either)
     if (!ctl->ran) return;
-    span_scatter(val, ctl->n_prev, span_off, out);
+    span_scatter_carry<W>(val, ctl->n_prev, span_off, out, wt, wt_out);
 }
 
 // ---- conversion of the 16-bit slot stream ---------------------------------------------------------------------
@@ -385,7 +457,11 @@ __global__ __launch_bounds__(kSpanThreads) void k_wide_cand(const uint32_t *__re
     if (lane == 0) span_sum[span] = span_pack(sum);
 }
 
-__global__ __launch_bounds__(kSpanThreads) void k_wide_match(const uint32_t *__restrict__ tok, const uint32_t *__restrict__ in_par,
+// W: every update is worth the weight of the match's chunk (its neighbours lie in the same chunk), and (a, b) loses
+// the sum of the weights matched, which is at most its count and so below 2^31; ctl->matches stays a position count.
+template <bool W>
+__global__ __launch_bounds__(kSpanThreads) void k_wide_match(const uint32_t *__restrict__ tok, const uint32_t *__restrict__ wt,
+                                                             const uint32_t *__restrict__ in_par,
                                                              uint32_t *__restrict__ val, uint32_t *__restrict__ span_keep,
                                                              WideTable tab, WideCtl *ctl, uint32_t new_id_base) {
     if (ctl->k >= ctl->k_limit || !ctl->live) return;
@@ -396,7 +472,7 @@ __global__ __launch_bounds__(kSpanThreads) void k_wide_match(const uint32_t *__r
     const uint32_t lane = lane_id();
     const unsigned long long lt = lanes_below(lane);
     uint32_t carry = in_par[span];
-    uint32_t kept = 0, n_match = 0;
+    uint32_t kept = 0, n_match = 0, w_match = 0;
     for (int it = 0; it < kSpanIters; ++it) {
         const uint64_t i = base + (uint64_t)it * kWave + lane;
         uint32_t nx;
@@ -411,6 +487,8 @@ __global__ __launch_bounds__(kSpanThreads) void k_wide_match(const uint32_t *__r
         kept += wave_count(v != kTokNone);
         n_match += wave_count(match);
         if (match) {
+            const int32_t w = W ? (int32_t)wt[i] : 1;
+            if (W) w_match += (uint32_t)w;
             // Tokenizer.h:248-260: the left neighbour as it stands AFTER the walk has passed it.  It was swallowed by a
             // match (and is X now) iff a match ends right before i: for a == b that is "(i-1, i) is a candidate too"
             // (then the run before i-1 is odd, r being even here), for a != b "(i-2, i-1) is a candidate" (such
@@ -422,23 +500,27 @@ __global__ __launch_bounds__(kSpanThreads) void k_wide_match(const uint32_t *__r
                     if (a == b) swallowed = p == a;                   // (no end flag on p: (p, t) is a candidate)
                     else swallowed = i > 1 && (p & kTokIdMask) == b && tok[i - 2] == a;   // (tok[i-2] == a: no end flag, id a)
                     const uint32_t x = swallowed ? X : p;
-                    wide_add(tab, ctl, ((unsigned long long)x << 32) | a, -1);
-                    wide_add(tab, ctl, ((unsigned long long)x << 32) | X, 1);
+                    wide_add(tab, ctl, ((unsigned long long)x << 32) | a, -w);
+                    wide_add(tab, ctl, ((unsigned long long)x << 32) | X, w);
                 }
             }
             // :263-279: the right neighbour as it still is
             if (!(nx & kTokEnd) && i + 2 < n) {
                 const uint32_t y = tok[i + 2] & kTokIdMask;
-                wide_add(tab, ctl, ((unsigned long long)b << 32) | y, -1);
-                wide_add(tab, ctl, ((unsigned long long)X << 32) | y, 1);
+                wide_add(tab, ctl, ((unsigned long long)b << 32) | y, -w);
+                wide_add(tab, ctl, ((unsigned long long)X << 32) | y, w);
             }
         }
         carry = run_carry(M, carry);
     }
+    if (W) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) w_match += __shfl_xor(w_match, d, kWave);
+    }
     if (lane == 0) {
         span_keep[span] = kept;
         if (n_match) {
-            wide_add(tab, ctl, ((unsigned long long)a << 32) | b, -(int32_t)n_match);      // :240-246
+            wide_add(tab, ctl, ((unsigned long long)a << 32) | b, -(int32_t)(W ? w_match : n_match));      // :240-246
             atomicAdd(&ctl->matches, n_match);
         }
     }
@@ -470,7 +552,8 @@ void launch_wide_from_slots(hipStream_t s, const uint16_t *slots, uint64_t n_liv
     const Scratch sc = carve(span_scratch, n_live);
     hipLaunchKernelGGL(k_wide_from_slots, dim3(span_grid(n_live)), dim3(kSpanThreads), 0, s, slots, n_live, barrier, endbit, val, sc.span_keep);
     hipLaunchKernelGGL(k_wide_scan_sum, dim3(1), dim3(kScanThreads), 0, s, sc.span_keep, n_live, sc.span_off, ctl, 0);
-    hipLaunchKernelGGL(k_wide_scatter, dim3(span_grid(n_live)), dim3(kSpanThreads), 0, s, val, sc.span_off, tok_out, ctl);
+    hipLaunchKernelGGL(k_wide_scatter<false>, dim3(span_grid(n_live)), dim3(kSpanThreads), 0, s, val, sc.span_off, tok_out, ctl,
+                       (const uint32_t *)nullptr, (uint32_t *)nullptr);
 }
 
 void launch_wide_table_clear(hipStream_t s, WideTable t) {
@@ -488,16 +571,36 @@ void launch_wide_rehash(hipStream_t s, WideTable from, WideTable to, WideCtl *ct
     hipLaunchKernelGGL(k_wide_rehash, dim3(2048), dim3(256), 0, s, from, to, ctl);
 }
 
-void launch_wide_pair_count_tokens(hipStream_t s, const uint32_t *tok, uint64_t n_tok, uint32_t ids, WideTable t,
-                                   WideCtl *ctl, WideTally *tally, int n_cus) {
+void launch_wide_token_weights(hipStream_t s, const uint32_t *tok, uint64_t n_tok, const uint32_t *weights,
+                               uint64_t n_weights, uint32_t *wt, uint32_t *span_scratch, WideCtl *ctl) {
+    if (!n_tok) return;
+    const Scratch sc = carve(span_scratch, n_tok);
+    const dim3 grid(span_grid(n_tok)), block(kSpanThreads);
+    hipLaunchKernelGGL(k_wide_end_count, grid, block, 0, s, tok, n_tok, sc.span_keep);
+    hipLaunchKernelGGL(k_wide_scan_ends, dim3(1), dim3(kScanThreads), 0, s, sc.span_keep, n_tok, sc.span_off);
+    hipLaunchKernelGGL(k_wide_fill_weights, grid, block, 0, s, tok, n_tok, sc.span_off, weights, n_weights, wt, ctl);
+}
+
+void launch_wide_check_weights(hipStream_t s, const uint32_t *weights, uint64_t n, uint32_t *flag) {
+    if (!n) return;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_wide_check_weights, dim3(blocks), dim3(256), 0, s, weights, n, flag);
+}
+
+void launch_wide_pair_count_tokens(hipStream_t s, const uint32_t *tok, const uint32_t *wt, uint64_t n_tok, uint32_t ids,
+                                   WideTable t, WideCtl *ctl, WideTally *tally, int n_cus) {
     if (n_tok >= 2) {
         // 8 workgroups of 12 KiB LDS per CU; a workgroup's share is at least 4,096 tokens (so that the flush of its
         // cache is paid for) and at most 2^20 (LDS counts cannot wrap)
         uint64_t blocks = (uint64_t)(n_cus > 0 ? n_cus : 256) * 8;
         blocks = std::min<uint64_t>(blocks, (n_tok + 4095) / 4096);
         blocks = std::max<uint64_t>(blocks, (n_tok + (1u << 20) - 1) >> 20);
-        hipLaunchKernelGGL(k_wide_pair_count_tokens, dim3((uint32_t)blocks), dim3(kWpThreads), 0, s, tok, n_tok, ids, t, ctl,
-                           tally);
+        if (wt)
+            hipLaunchKernelGGL(k_wide_pair_count_tokens<true>, dim3((uint32_t)blocks), dim3(kWpThreads), 0, s, tok, wt, n_tok,
+                               ids, t, ctl, tally);
+        else
+            hipLaunchKernelGGL(k_wide_pair_count_tokens<false>, dim3((uint32_t)blocks), dim3(kWpThreads), 0, s, tok, wt, n_tok,
+                               ids, t, ctl, tally);
     }
     const uint64_t slots = (uint64_t)t.mask + 1;
     const uint32_t tb = (uint32_t)std::min<uint64_t>((slots + 1023) / 1024, 4096);
@@ -521,15 +624,22 @@ void launch_wide_first(hipStream_t s, const uint32_t *src, uint64_t n_upper, Wid
 }
 
 void launch_wide_merge(hipStream_t s, const uint32_t *src, uint32_t *dst, uint64_t n_upper, uint32_t *val,
-                       uint32_t *span_scratch, WideTable t, WideCtl *ctl, uint32_t new_id_base) {
+                       uint32_t *span_scratch, WideTable t, WideCtl *ctl, uint32_t new_id_base, const uint32_t *wsrc,
+                       uint32_t *wdst) {
     if (!n_upper) return;
     const Scratch sc = carve(span_scratch, n_upper);
     const dim3 grid(span_grid(n_upper)), block(kSpanThreads);
     hipLaunchKernelGGL(k_wide_cand, grid, block, 0, s, src, ctl, sc.span_sum);
     hipLaunchKernelGGL(k_wide_scan_parity, dim3(1), dim3(kScanThreads), 0, s, sc.span_sum, ctl, sc.in_par);
-    hipLaunchKernelGGL(k_wide_match, grid, block, 0, s, src, sc.in_par, val, sc.span_keep, t, ctl, new_id_base);
+    if (wsrc)
+        hipLaunchKernelGGL(k_wide_match<true>, grid, block, 0, s, src, wsrc, sc.in_par, val, sc.span_keep, t, ctl, new_id_base);
+    else
+        hipLaunchKernelGGL(k_wide_match<false>, grid, block, 0, s, src, wsrc, sc.in_par, val, sc.span_keep, t, ctl, new_id_base);
     hipLaunchKernelGGL(k_wide_scan_sum, dim3(1), dim3(kScanThreads), 0, s, sc.span_keep, (uint64_t)0, sc.span_off, ctl, 1);
-    hipLaunchKernelGGL(k_wide_scatter, grid, block, 0, s, val, sc.span_off, dst, ctl);
+    if (wsrc)
+        hipLaunchKernelGGL(k_wide_scatter<true>, grid, block, 0, s, val, sc.span_off, dst, ctl, wsrc, wdst);
+    else
+        hipLaunchKernelGGL(k_wide_scatter<false>, grid, block, 0, s, val, sc.span_off, dst, ctl, wsrc, wdst);
 }
 
 }  // namespace mbpe

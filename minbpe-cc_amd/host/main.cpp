@@ -83,6 +83,12 @@ void usage() {
                  "  --byte-ranges-out TEXT      When encoding, also write one line \"start end\" per token to this file: the bytes\n"
                  "                              of the input the token stands for (a special token: its name's occurrence);\n"
                  "                              on the host, with --device-encode, --device-split and --rank-order alike\n"
+                 "  --dedup                     With --train: split as asked, then train on the distinct chunks with their counts\n"
+                 "                              (deduplicated on the HIP device): the same model.  One pass over the unique\n"
+                 "                              chunks per merge: meant for -c first, for vocabularies beyond 65,536 and for\n"
+                 "                              --continue-from; -c lexical below that is faster without it, and --encoder\n"
+                 "                              basic has one chunk, so nothing is saved.  Combines with --device-split,\n"
+                 "                              --device-split-unicode, --continue-from and --conflict-resolution\n"
                  "  --continue-from TEXT        With --train: load this model and continue its training on the input up to\n"
                  "                              --vocab-size, which must not be below the model's size; the result goes to\n"
                  "                              --model-path.  The loaded model's split pattern is used: --encoder has no\n"
@@ -98,7 +104,7 @@ int main(int argc, char *argv[]) {
                 byte_ranges_path;
     std::string conflict_resolution_str = "first";
     bool train = false, decode = false, encode = false, write_vocab = false, verbose = false, device_encode = false,
-         device_decode = false, device_split = false, split_unicode = false, rank_order = false;
+         device_decode = false, device_split = false, split_unicode = false, rank_order = false, dedup = false;
     int vocab_size = 512, device = 0;
     double dropout = 0.0;
     bool have_dropout = false;
@@ -157,6 +163,7 @@ int main(int argc, char *argv[]) {
         else if (arg == "--device-split") device_split = true;
         else if (arg == "--device-split-unicode") device_split = split_unicode = true;
         else if (arg == "--rank-order") rank_order = true;
+        else if (arg == "--dedup") dedup = true;
         else if (arg == "-v" || arg == "--verbose") verbose = true;
         else { std::cerr << "The following argument was not expected: " << arg << "\n"; return 109; }
     }
@@ -216,6 +223,7 @@ int main(int argc, char *argv[]) {
         if (load_file_to_string(input_path, &input, &err)) {
             if (verbose) std::cout << "Starting training...\n";
             if (split_unicode) mbpe_tok_set_split_unicode(rt, 1);
+            if (dedup) mbpe_tok_set_train_dedup(rt, 1);
             const uint8_t *in = reinterpret_cast<const uint8_t *>(input.data());
             const int cr = conflict_resolution_str == "lexical" ? 1 : 0;
             const int trc = !continue_from.empty()

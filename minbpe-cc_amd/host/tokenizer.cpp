@@ -214,6 +214,55 @@ void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTI
         mbpe_splitter_destroy(dev_split);
         throw std::runtime_error(mbpe_last_error());
     }
+    // Dedup (mbpe_tok_set_train_dedup): the distinct chunks in order of first occurrence and their counts, and the
+    // training on those with the counts as weights -- the same merges and counts, on the 32-bit loop.  After the device
+    // split neither text nor mask returns to the host: the deduper reads them where the splitter left them and the
+    // trainer takes the deduper's result in place.  After the host split the chunks go up packed, as
+    // mbpe_load_corpus_ranges would train on them, and the unique ones come back for mbpe_load_corpus_weighted, which
+    // applies the NUL rule (a custom pattern can produce such a chunk).  Without a pattern the text is one chunk:
+    // nothing to deduplicate, it passes through.
+    mbpe_dedup *dd = nullptr;
+    std::vector<uint32_t> dd_weights;             // host copy of the weights (host split; verbose)
+    int dd_rc = MBPE_OK;
+    if (train_dedup_) {
+        uint64_t n_unique = 0, n_unique_bytes = 0;
+        dd_rc = mbpe_dedup_create(device, &dd);
+        if (dd_rc == MBPE_OK && dev_split) {
+            const uint8_t *u_text = nullptr, *u_mask = nullptr;
+            const uint32_t *u_weights = nullptr;
+            dd_rc = mbpe_dedup_chunks_endmask(dd, text.empty() ? nullptr : d_text, text.size(), text.empty() ? nullptr : d_mask,
+                                              &n_unique, &n_unique_bytes);
+            if (dd_rc == MBPE_OK) dd_rc = mbpe_dedup_result(dd, &u_text, &u_mask, &u_weights, nullptr);
+            if (dd_rc == MBPE_OK)
+                dd_rc = mbpe_load_corpus_endmask_weighted(ctx, u_text, n_unique_bytes, 1, u_mask, u_weights, n_unique, 1);
+            if (dd_rc == MBPE_OK && verbose) {
+                dd_weights.resize(n_unique);
+                dd_rc = mbpe_dedup_get(dd, nullptr, nullptr, dd_weights.data(), nullptr, 0, n_unique);
+            }
+        } else if (dd_rc == MBPE_OK) {
+            std::string packed;
+            std::vector<uint64_t> off(1, 0);
+            if (chunked) {
+                for (size_t i = 0; i < starts.size(); ++i) {
+                    packed.append(text, starts[i], ends[i] - starts[i]);
+                    off.push_back(packed.size());
+                }
+            } else {
+                off.push_back(text.size());
+            }
+            const std::string &src = chunked ? packed : text;
+            dd_rc = mbpe_dedup_chunks(dd, reinterpret_cast<const uint8_t *>(src.data()), src.size(), 0, off.data(),
+                                      off.size() - 1, &n_unique, &n_unique_bytes);
+            std::vector<uint8_t> u_text(n_unique_bytes + 1);
+            std::vector<uint64_t> u_off(n_unique + 1, 0);
+            dd_weights.resize(n_unique);
+            if (dd_rc == MBPE_OK)
+                dd_rc = mbpe_dedup_get(dd, u_text.data(), u_off.data(), dd_weights.data(), nullptr, n_unique_bytes, n_unique);
+            if (dd_rc == MBPE_OK)
+                dd_rc = mbpe_load_corpus_weighted(ctx, u_text.data(), n_unique_bytes, u_off.data(), n_unique, 0,
+                                                  dd_weights.data());
+        }
+    }
     const uint32_t cap = static_cast<uint32_t>(vocab_size - 256);
     std::vector<uint32_t> flat(2 * static_cast<size_t>(cap) + 2);
     std::vector<int32_t> had(cap + 1);
@@ -222,9 +271,10 @@ void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTI
     // chunks as ranges: bytes between two matches belong to no chunk, as in the reference's loop (:506-540).  The
     // device split's mask goes to the trainer as it is: the NUL rule of text_to_vector (:86-93) never fires for the
     // gpt2 / gpt4 patterns -- a chunk that starts with NUL holds no ASCII digit, so std::stoi cannot parse its remainder
-    int rc = dev_split ? mbpe_load_corpus_endmask(ctx, text.empty() ? bytes : d_text, text.size(), !text.empty(), d_mask)
-             : chunked ? mbpe_load_corpus_ranges(ctx, bytes, text.size(), starts.data(), ends.data(), starts.size(), 0)
-                       : mbpe_load_corpus(ctx, bytes, text.size(), nullptr, 0, 0);
+    int rc = train_dedup_ ? dd_rc
+             : dev_split  ? mbpe_load_corpus_endmask(ctx, text.empty() ? bytes : d_text, text.size(), !text.empty(), d_mask)
+             : chunked    ? mbpe_load_corpus_ranges(ctx, bytes, text.size(), starts.data(), ends.data(), starts.size(), 0)
+                          : mbpe_load_corpus(ctx, bytes, text.size(), nullptr, 0, 0);
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "conflict_resolution", conflict_resolution == LEXICAL ? 1 : 0);
     // (`first` beyond the 16-bit slot format continues on 32-bit tokens, as the reference's uint32_t Token does)
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "first_wide", 1);
@@ -234,8 +284,23 @@ void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTI
     if (rc == MBPE_OK) rc = mbpe_train_steps(ctx, cap, nullptr);
     if (rc == MBPE_OK) rc = mbpe_train_result(ctx, flat.data(), had.data(), cap, &n_merges);
     if (rc == MBPE_OK) rc = mbpe_get_stats(ctx, &st);
+    if (rc == MBPE_OK && train_dedup_ && verbose) {
+        // the length the verbose line reports is the full corpus's: every unique chunk's tokens, weights[c] times
+        uint64_t n_stream = 0;
+        rc = mbpe_get_stream(ctx, nullptr, nullptr, 0, &n_stream);
+        std::vector<uint32_t> toks(n_stream + 1);
+        std::vector<uint8_t> is_end(n_stream + 1);
+        if (rc == MBPE_OK) rc = mbpe_get_stream(ctx, toks.data(), is_end.data(), n_stream, &n_stream);
+        uint64_t total = 0, chunk = 0;
+        for (uint64_t i = 0; i < n_stream && rc == MBPE_OK; ++i) {
+            total += chunk < dd_weights.size() ? dd_weights[chunk] : 1;
+            if (is_end[i]) ++chunk;
+        }
+        st.n_live = total;
+    }
     std::string msg = rc == MBPE_OK ? "" : mbpe_last_error();
     mbpe_destroy(ctx);
+    mbpe_dedup_destroy(dd);                 // (the trainer has its own copies of mask and weights; the text until here)
     mbpe_splitter_destroy(dev_split);       // (its text and mask were in use until here)
     if (rc != MBPE_OK && resume) throw CodedError(rc, msg);      // (mbpe_tok_train_continue hands the code on)
     if (rc != MBPE_OK) throw std::runtime_error(msg);
@@ -952,6 +1017,16 @@ int mbpe_tok_set_encode_dropout(mbpe_tokenizer *t, uint64_t threshold, uint64_t 
         return MBPE_ERR_ARG;
     }
     t->t->set_dropout(threshold, seed);
+    return MBPE_OK;
+}
+
+int mbpe_tok_set_train_dedup(mbpe_tokenizer *t, int on) {
+    if (!t) return MBPE_ERR_ARG;
+    if (on != 0 && on != 1) {
+        mbpe_host::set_last_error("mbpe_tok_set_train_dedup: on must be 0 or 1");
+        return MBPE_ERR_ARG;
+    }
+    t->t->set_train_dedup(on == 1);
     return MBPE_OK;
 }
 

@@ -40,6 +40,9 @@ EXPORTS = [
     "mbpe_encoder_encode_endmask_byteoff", "mbpe_split_unicode_table",
     "mbpe_merges_check", "mbpe_train_begin_from", "mbpe_train_from",
     "mbpe_dropout_threshold", "mbpe_encoder_set_dropout",
+    "mbpe_dedup_create", "mbpe_dedup_destroy", "mbpe_dedup_chunks_endmask", "mbpe_dedup_chunks", "mbpe_dedup_result",
+    "mbpe_dedup_get", "mbpe_dedup_set_option", "mbpe_dedup_kernel_ms", "mbpe_dedup_alloc_count",
+    "mbpe_load_corpus_weighted", "mbpe_load_corpus_endmask_weighted",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -49,7 +52,7 @@ TOK_EXPORTS = [
     "mbpe_tok_encode_batch_packed_device", "mbpe_tok_decode_padded_device", "mbpe_tok_encode_batch_aux_device",
     "mbpe_tok_train_split_device", "mbpe_tok_set_encode_split", "mbpe_tok_set_split_unicode",
     "mbpe_tok_set_encode_order", "mbpe_tok_train_continue", "mbpe_tok_encode_byteoff",
-    "mbpe_tok_encode_batch_byteoff_device", "mbpe_tok_set_encode_dropout",
+    "mbpe_tok_encode_batch_byteoff_device", "mbpe_tok_set_encode_dropout", "mbpe_tok_set_train_dedup",
 ]
 
 
@@ -240,6 +243,19 @@ def lib():
                                                     vp, vp]
     L.mbpe_tok_set_encode_split.argtypes = [vp, i32]
     L.mbpe_tok_set_split_unicode.argtypes = [vp, i32]
+    L.mbpe_tok_set_train_dedup.argtypes = [vp, i32]
+    L.mbpe_dedup_create.argtypes = [i32, ctypes.POINTER(vp)]
+    L.mbpe_dedup_destroy.argtypes = [vp]
+    L.mbpe_dedup_destroy.restype = None
+    L.mbpe_dedup_chunks_endmask.argtypes = [vp, vp, u64, vp, vp, vp]
+    L.mbpe_dedup_chunks.argtypes = [vp, vp, u64, i32, vp, u64, vp, vp]
+    L.mbpe_dedup_result.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    L.mbpe_dedup_get.argtypes = [vp, vp, vp, vp, vp, u64, u64]
+    L.mbpe_dedup_set_option.argtypes = [vp, ctypes.c_char_p, i64]
+    L.mbpe_dedup_kernel_ms.argtypes = [vp, vp]
+    L.mbpe_dedup_alloc_count.argtypes = [vp, vp]
+    L.mbpe_load_corpus_weighted.argtypes = [vp, vp, u64, vp, u64, i32, vp]
+    L.mbpe_load_corpus_endmask_weighted.argtypes = [vp, vp, u64, i32, vp, vp, u64, i32]
     L.mbpe_tok_set_encode_order.argtypes = [vp, i32]
     L.mbpe_dropout_threshold.argtypes = [ctypes.c_double, vp]
     L.mbpe_encoder_set_dropout.argtypes = [vp, u64, u64]
@@ -1042,6 +1058,93 @@ class Splitter:
         return n.value, b.value
 
 
+class Deduper:
+    """One mbpe_dedup: the distinct chunks of a chunked text in order of first occurrence, with their counts."""
+
+    def __init__(self, device=0):
+        self._h = ctypes.c_void_p()
+        _check(lib().mbpe_dedup_create(device, ctypes.byref(self._h)))
+        self._keep = None
+        self.n_unique = self.n_unique_bytes = 0
+
+    def close(self):
+        if self._h:
+            lib().mbpe_dedup_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_option(self, name, value):
+        _check(lib().mbpe_dedup_set_option(self._h, name.encode(), int(value)))
+
+    def _done(self, rc, nu, nb):
+        self.n_unique, self.n_unique_bytes = nu.value, nb.value
+        _check(rc)
+        return nu.value, nb.value
+
+    def chunks(self, data, chunk_off, text_ptr=None, n_bytes=None):
+        """The chunks data[chunk_off[c]:chunk_off[c + 1]] (host bytes, or n_bytes of device memory at text_ptr) ->
+        (n_unique, n_unique_bytes).  Empty chunks vanish."""
+        off = np.ascontiguousarray(chunk_off, dtype=np.uint64)
+        if text_ptr is None:
+            text = _u8(data)
+            ptr, n, on_dev = (text.ctypes.data if len(text) else None), len(text), 0
+        else:
+            text, ptr, n, on_dev = None, ctypes.c_void_p(text_ptr), n_bytes, 1
+        self._keep = (text, off)
+        nu, nb = ctypes.c_uint64(), ctypes.c_uint64()
+        return self._done(lib().mbpe_dedup_chunks(self._h, ptr, n, on_dev, off.ctypes.data, len(off) - 1, ctypes.byref(nu),
+                                                  ctypes.byref(nb)), nu, nb)
+
+    def chunks_endmask(self, text_ptr, n_bytes, mask_ptr):
+        """n_bytes of device text at text_ptr with the end mask at mask_ptr (Splitter.endmask), both read in place ->
+        (n_unique, n_unique_bytes)."""
+        nu, nb = ctypes.c_uint64(), ctypes.c_uint64()
+        return self._done(lib().mbpe_dedup_chunks_endmask(self._h, ctypes.c_void_p(text_ptr) if text_ptr else None, n_bytes,
+                                                          ctypes.c_void_p(mask_ptr) if mask_ptr else None,
+                                                          ctypes.byref(nu), ctypes.byref(nb)), nu, nb)
+
+    def result(self):
+        """Device addresses (text, end mask, weights u32, first_chunk u64) of the latest result, owned by the deduper
+        and valid until its next call."""
+        t, m, w, f = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        _check(lib().mbpe_dedup_result(self._h, ctypes.byref(t), ctypes.byref(m), ctypes.byref(w), ctypes.byref(f)))
+        return t.value, m.value, w.value, f.value
+
+    def get(self, cap_bytes=None, cap_chunks=None):
+        """Host copies of the latest result -> (text bytes, chunk_off uint64 [n_unique + 1], weights uint32,
+        first_chunk uint64).  cap_bytes / cap_chunks: the capacities handed to the library (default: the result's
+        sizes)."""
+        nb = self.n_unique_bytes if cap_bytes is None else cap_bytes
+        nu = self.n_unique if cap_chunks is None else cap_chunks
+        text = np.zeros(max(nb, 1), dtype=np.uint8)
+        off = np.zeros(nu + 1, dtype=np.uint64)
+        w = np.zeros(max(nu, 1), dtype=np.uint32)
+        f = np.zeros(max(nu, 1), dtype=np.uint64)
+        _check(lib().mbpe_dedup_get(self._h, text.ctypes.data, off.ctypes.data, w.ctypes.data, f.ctypes.data, nb, nu))
+        return (text[:self.n_unique_bytes].tobytes(), off[:self.n_unique + 1], w[:self.n_unique], f[:self.n_unique])
+
+    def kernel_ms(self):
+        ms = ctypes.c_float()
+        _check(lib().mbpe_dedup_kernel_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def alloc_count(self):
+        n = ctypes.c_uint64()
+        _check(lib().mbpe_dedup_alloc_count(self._h, ctypes.byref(n)))
+        return n.value
+
+
 class Trainer:
     """One mbpe_ctx.  Mirrors the order of Tokenizer::train (Tokenizer.h:489-598)."""
 
@@ -1109,6 +1212,35 @@ class Trainer:
             _check(lib().mbpe_load_corpus_endmask(self._h, ctypes.c_void_p(text_ptr), n_bytes, 1,
                                                   ctypes.c_void_p(mask_ptr)))
 
+    def load_corpus_weighted(self, data, chunk_off, weights):
+        """Chunk c stands for weights[c] occurrences (mbpe_load_corpus_weighted): the training then runs on 32-bit
+        tokens and counts what the expanded corpus holds."""
+        text = _u8(data)
+        off = np.ascontiguousarray(chunk_off, dtype=np.uint64)
+        w = np.ascontiguousarray(weights, dtype=np.uint32)
+        if len(w) != len(off) - 1:
+            raise ValueError("one weight per chunk")
+        self._keep = (text, off, w)
+        _check(lib().mbpe_load_corpus_weighted(self._h, text.ctypes.data if len(text) else None, len(text),
+                                               off.ctypes.data, len(off) - 1, 0, w.ctypes.data if len(w) else None))
+
+    def load_corpus_endmask_weighted(self, mask_ptr, weights=None, data=None, text_ptr=None, n_bytes=None,
+                                     weights_ptr=None, n_weights=None, keep=None):
+        """load_corpus_endmask with one weight per end bit of the mask: weights (host array) or n_weights u32 of device
+        memory at weights_ptr -- Deduper.result() goes in as it is."""
+        if weights_ptr is None:
+            w = np.ascontiguousarray(weights, dtype=np.uint32)
+            wp, nw, w_dev = (w.ctypes.data if len(w) else None), len(w), 0
+        else:
+            w, wp, nw, w_dev = None, ctypes.c_void_p(weights_ptr), n_weights, 1
+        if text_ptr is None:
+            text = _u8(data)
+            tp, n, t_dev = (text.ctypes.data if len(text) else None), len(text), 0
+        else:
+            text, tp, n, t_dev = None, ctypes.c_void_p(text_ptr), n_bytes, 1
+        self._keep = (text, w, keep)
+        _check(lib().mbpe_load_corpus_endmask_weighted(self._h, tp, n, t_dev, ctypes.c_void_p(mask_ptr), wp, nw, w_dev))
+
     def pair_count_u8(self, want_table=True):
         table = np.zeros(65536, dtype=np.uint32) if want_table else None
         _check(lib().mbpe_pair_count_u8(self._h, None if table is None else table.ctypes.data))
@@ -1167,10 +1299,18 @@ class Trainer:
     def train_lexical(self, data, vocab_size, chunk_off=None):
         return self.train(data, vocab_size, chunk_off, conflict_resolution=1)
 
-    def train(self, data, vocab_size, chunk_off=None, conflict_resolution=1, prior_merges=None):
+    def train(self, data, vocab_size, chunk_off=None, conflict_resolution=1, prior_merges=None, weights=None):
         """conflict_resolution: 1 = lexical, 0 = first (mbpe_train).  prior_merges: continue from them (mbpe_train_from);
         the result then starts with them, with counts of -1.  Options are taken from the context: "resume_wide" 1 lets a
-        continuation pass the 16-bit slot format (see train_begin)."""
+        continuation pass the 16-bit slot format (see train_begin).  weights: one per chunk (load_corpus_weighted); the
+        training then runs on 32-bit tokens, and the context's "conflict_resolution" is left as this call set it."""
+        if weights is not None:
+            self.load_corpus_weighted(data, chunk_off, weights)
+            self.set_option("conflict_resolution", conflict_resolution)
+            self.train_begin(vocab_size, prior_merges if prior_merges is not None and len(prior_merges) else None)
+            self.train_steps(vocab_size - 256)
+            merges, counts = self.train_result()
+            return merges, counts, self.stats()
         text = _u8(data)
         prior = _merges(prior_merges)
         off = None if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.uint64)
@@ -1282,8 +1422,12 @@ class Tokenizer:
         _check(lib().mbpe_tok_set_special_tokens(self._h, b, len(b)))
 
     def train(self, data, vocab_size, conflict_resolution=1, verbose=False, device=0, device_split=False,
-              resume=False):
-        """resume: continue from the merges the tokenizer holds (loaded, set or trained) up to vocab_size instead of
+              resume=False, dedup=False):
+        """dedup: split as asked, deduplicate the chunks on the device and train on the distinct ones with their
+        counts (mbpe_tok_set_train_dedup): same merges, counts, .model and .vocab.  Meant for the `first` tie-break,
+        for vocabularies beyond the 16-bit slot format and with resume; the lexical tie-break within the slot format
+        is faster without it.  A tokenizer without a pattern has one chunk and trains slowly this way.
+        resume: continue from the merges the tokenizer holds (loaded, set or trained) up to vocab_size instead of
         starting from raw bytes (mbpe_tok_train_continue); pattern and special tokens stay.  Vocabularies up to 2^24,
         either tie-break: beyond the 16-bit slot format the continuation runs on 32-bit tokens ("resume_wide").
         device_split: the gpt2 / gpt4 pre-split runs on the device too (same merges); a tokenizer with any other
@@ -1291,6 +1435,7 @@ class Tokenizer:
         well-formed non-ASCII text is split there as well (mbpe_tok_set_split_unicode)."""
         text = _u8(data)
         _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
+        _check(lib().mbpe_tok_set_train_dedup(self._h, int(bool(dedup))))
         if resume:
             _check(lib().mbpe_tok_train_continue(self._h, text.ctypes.data if len(text) else None, len(text), vocab_size,
                                                  conflict_resolution, int(verbose), device, int(bool(device_split))))
