@@ -595,6 +595,52 @@ MBPE_API int  mbpe_encoder_pass_tokens(const mbpe_encoder *e, uint64_t *tokens_o
  * host output, the staging buffer that follows the TOKEN count of the largest piece.) */
 MBPE_API int  mbpe_encoder_alloc_count(const mbpe_encoder *e, uint64_t *n_out);
 
+/* ---- encode through the unique chunks (csrc/expand.hip, expand.h) --------------------------------------------------
+ * mbpe_encoder_set_option(e, "dedup", 0 | 1), default 0; any other value is MBPE_ERR_ARG.  With 0 the encoder launches
+ * and allocates exactly what it does without the option: no deduper exists and mbpe_encoder_alloc_count is unchanged.
+ * With 1, mbpe_encoder_encode, _encode_batch, _encode_batch_aux, _encode_endmask and _encode_batch_endmask give the same
+ * tokens, offsets, matrices and error codes on another route.  Without dropout a chunk's tokens depend on its bytes
+ * alone, in both orders, so:
+ *   1. the encoder's own deduper (mbpe_dedup_*, created by the first such call, option "map" on) finds the unique chunks
+ *      of the call's text and mask (the endmask calls) or text and chunk_off (host or device text; a device text that
+ *      is not 16-byte aligned is copied once);
+ *   2. the existing passes, greedy or rank order, run over the unique text and its end mask as ONE piece, without any
+ *      single and without the NUL rule: a NUL-led chunk's bytes there are ordinary bytes that nothing points at;
+ *   3. the finishing kernel writes them into a kept table in the caller's format (32 bits with bit 31 on a chunk's last
+ *      token, plain 32 bits, 16 bits) with every run's end; the chunks that are one token by rule (NUL-led with a number,
+ *      mbpe_single) become runs of their own behind them;
+ *   4. the expansion copies every chunk's run to its place: a 64-bit token count per span of 1,024 chunks, one scan,
+ *      the total read back BEFORE anything is written (a cap that is too small writes nothing and still reports the
+ *      count), then one wave per span that walks the span's output in pieces of 16 aligned bytes.  The chunks' token
+ *      offsets (chunk_tok_off_out, the batch calls' documents) and the endmask calls' document offsets come from the
+ *      same sums; the latter stay on the device for the pack kernel.
+ * Pieces: the call's text is one piece for the deduper, and the unique text is one piece under the limit of
+ * mbpe_encoder_encode (option "piece_bytes"); a unique text above it returns MBPE_ERR_OOM with a message that names both
+ * numbers, and the encoder stays usable.  Device memory: the deduper's (see mbpe_dedup_*: 1 1/8 B per text byte of a host
+ * text, 44 .. 68 B per chunk with the map, 8 B more per chunk where chunk_off has empty chunks), the pieces' 14 B per
+ * UNIQUE byte, the table (4 or 2 B per unique token, 8 B per unique chunk and per one-token chunk), 8 B per 1,024 chunks,
+ * 8 B per chunk where the chunks' token offsets are asked for (the batch calls), the output's size once more when it
+ * goes to the host, and for the endmask calls with singles or documents 12 B per 2,048 text bytes.
+ * Refused, before the device is touched, with MBPE_ERR_ARG: any of these calls while mbpe_encoder_set_dropout has a
+ * threshold above 0 (a dropped instance depends on its position, so equal chunks do not share their tokens), and the
+ * _byteoff calls with a tok_byte_off_out that is not NULL (with NULL they are their counterparts, as ever); a device
+ * tokens_out that is not aligned to its elements.  The route is never switched silently.
+ *   "dedup_max_chunk_bytes"  forwards to the deduper's "max_chunk_bytes" (default 256; 0 .. 2^31 - 1): a longer chunk
+ *                            passes through as a unique chunk every time it occurs, which is as exact
+ * mbpe_encode_chunks* and the replay inside mbpe_train_begin_from never take this route.
+ * mbpe_encoder_pass_tokens then reports the passes over the unique text ([0] = its byte count), mbpe_encoder_kernel_ms
+ * the deduper's kernels, the passes, the finishing kernel and the expansion.  A repeat call of no larger size allocates
+ * nothing.
+ *   mbpe_encoder_dedup_stats  the latest call: the chunks the deduper kept, the unique chunks, their bytes, the tokens they
+ *                             became (the table without the one-token chunks) and the device time of the expansion
+ *                             (chunk look-ups, count, scan, copy); any pointer may be NULL.  MBPE_ERR_STATE when the
+ *                             latest call did not take this route.
+ * Use it for large texts in natural language (few distinct chunks), above all in rank order, whose many passes then
+ * run over a few hundred kilobytes; do not use it where most chunks are distinct or the text is one chunk: the dedup
+ * and the copy come on top of the same passes (README, "Encoding through the unique chunks"). */
+MBPE_API int  mbpe_encoder_dedup_stats(const mbpe_encoder *e, uint64_t *n_chunks_out, uint64_t *n_unique_out,
+                                       uint64_t *n_unique_bytes_out, uint64_t *n_unique_tokens_out, float *expand_ms_out);
+
 /* ---- fixed-length id matrices --------------------------------------------- */
 
 /* A model input is a rectangle: [rows, seq_len] ids plus one length per row.  These calls build it on the device
@@ -1119,6 +1165,18 @@ MBPE_API int  mbpe_dedup_get(mbpe_dedup *d, uint8_t *text_out, uint64_t *chunk_o
 MBPE_API int  mbpe_dedup_set_option(mbpe_dedup *d, const char *name, int64_t value);
 MBPE_API int  mbpe_dedup_kernel_ms(const mbpe_dedup *d, float *ms_out);
 MBPE_API int  mbpe_dedup_alloc_count(const mbpe_dedup *d, uint64_t *n_out);
+
+/* The inverse map: unique_of[c] (u32) = the index j of the unique chunk that has chunk c's bytes, for every chunk the
+ * deduper kept (the empty chunks of mbpe_dedup_chunks stay out, as everywhere; a chunk that passed through unhashed is
+ * its own unique chunk).  Computed only while the option "map" is 1 (default 0: the deduper launches and allocates
+ * exactly what it does without it); it costs one more short kernel and 4 B per chunk.  Any other value is MBPE_ERR_ARG.
+ *   mbpe_dedup_map      device view of the latest result and the number of chunks it speaks of, valid until the
+ *                       deduper's next call (either may be NULL)
+ *   mbpe_dedup_get_map  host copy; unique_of_out NULL: n_chunks_out receives the count only.  A cap below it is
+ *                       MBPE_ERR_ARG and nothing is written
+ * MBPE_ERR_STATE when the latest dedup did not succeed or ran without the option. */
+MBPE_API int  mbpe_dedup_map(const mbpe_dedup *d, const uint32_t **unique_of_dev_out, uint64_t *n_chunks_out);
+MBPE_API int  mbpe_dedup_get_map(mbpe_dedup *d, uint32_t *unique_of_out, uint64_t cap_chunks, uint64_t *n_chunks_out);
 
 #ifdef __cplusplus
 }

@@ -179,6 +179,17 @@ MBPE_API int mbpe_tok_set_split_unicode(mbpe_tokenizer *t, int on);
  * One rank.  A chunk above 256 bytes is never merged with its duplicates (it appears as often as it occurs). */
 MBPE_API int mbpe_tok_set_train_dedup(mbpe_tokenizer *t, int on);
 
+/* Encoding through the distinct chunks: 0 (the default) or 1; anything else is MBPE_ERR_ARG.  While it is on,
+ * mbpe_tok_encode_device and the three batch calls (mbpe_tok_encode_batch_device, _batch_packed_device,
+ * _batch_aux_device) run the kept device encoder with its option "dedup" (mbpe.h: the chunks are deduplicated on the
+ * device, the distinct ones go through the merge passes once, and a copy kernel writes every chunk's tokens to its
+ * place), with the host split and with the device split, in both orders: the same tokens, offsets and matrices.  The
+ * encoder is re-configured, not re-created.  The host loop (mbpe_tok_encode) is unaffected.  The byte-range calls on
+ * a device (mbpe_tok_encode_byteoff with a device, mbpe_tok_encode_batch_byteoff_device) and every device call while
+ * a dropout threshold above 0 is set return MBPE_ERR_ARG while it is on: a dropped instance depends on its position,
+ * so equal chunks do not share tokens, and the route is never switched silently. */
+MBPE_API int mbpe_tok_set_encode_dedup(mbpe_tokenizer *t, int on);
+
 /* decode, Tokenizer.h:725-751.  bytes_out may be NULL to query the length. */
 MBPE_API int mbpe_tok_decode(mbpe_tokenizer *t, const uint32_t *tokens, uint64_t n, int verbose,
                              uint8_t *bytes_out, uint64_t cap, uint64_t *n_out);

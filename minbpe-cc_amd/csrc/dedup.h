@@ -66,12 +66,13 @@ MBPE_HD bool dedup_equal(const uint8_t *a, const uint8_t *b, uint64_t len) {
 #ifndef __HIP_DEVICE_COMPILE__
 // The whole operation on the host, through the same table.  Chunk c is text[c ? ends[c - 1] : 0 .. ends[c]), none
 // empty.  Result: the unique chunks' bytes packed in order of first occurrence, their ends in that text, their
-// weights and the input index of each one's first occurrence.
+// weights and the input index of each one's first occurrence; unique_of[c] = the unique chunk that has chunk c's bytes.
 struct DedupHost {
     std::vector<uint8_t> text;
     std::vector<uint64_t> ends;
     std::vector<uint32_t> weights;
     std::vector<uint64_t> first_chunk;
+    std::vector<uint32_t> unique_of;
 };
 inline DedupHost dedup_host(const uint8_t *text, const uint64_t *ends, uint64_t n_chunks, uint32_t max_chunk_bytes,
                             uint32_t hash_bits) {
@@ -79,7 +80,7 @@ inline DedupHost dedup_host(const uint8_t *text, const uint64_t *ends, uint64_t 
     const uint32_t bits = dedup_table_bits(n_chunks);
     const uint64_t mask = (1ull << bits) - 1;
     std::vector<unsigned long long> slots(mask + 1, kDedupEmpty);
-    std::vector<uint64_t> unique_of(mask + 1, 0);      // slot -> index among the unique chunks
+    std::vector<uint64_t> slot_unique(mask + 1, 0);    // slot -> index among the unique chunks
     for (uint64_t c = 0; c < n_chunks; ++c) {
         const uint64_t start = c ? ends[c - 1] : 0, len = ends[c] - start;
         bool is_new = true;
@@ -91,18 +92,20 @@ inline DedupHost dedup_host(const uint8_t *text, const uint64_t *ends, uint64_t 
                 const unsigned long long v = slots[pos];
                 if (v == kDedupEmpty) {
                     slots[pos] = dedup_slot(tag, c);
-                    unique_of[pos] = r.weights.size();
+                    slot_unique[pos] = r.weights.size();
                     break;
                 }
                 const uint64_t rep = v & 0xFFFFFFFFull, rs = rep ? ends[rep - 1] : 0;
                 if (dedup_tag(v) == tag && ends[rep] - rs == len && dedup_equal(text + start, text + rs, len)) {
-                    r.weights[unique_of[pos]] += 1;
+                    r.weights[slot_unique[pos]] += 1;
+                    r.unique_of.push_back((uint32_t)slot_unique[pos]);
                     is_new = false;
                     break;
                 }
             }
         }
         if (is_new) {
+            r.unique_of.push_back((uint32_t)r.weights.size());
             r.text.insert(r.text.end(), text + start, text + start + len);
             r.ends.push_back(r.text.size());
             r.weights.push_back(1);

@@ -10,6 +10,8 @@
 //   k_dd_first_count  per 256 chunks: first occurrences and their bytes      -> two scans -> n_unique, n_unique_bytes
 //   k_dd_emit         the first occurrences' bytes (16-byte pieces where source and target are aligned alike), end
 //                     mask, weights and first_chunk
+//   k_dd_map          option "map" only: unique_of[c] of every chunk that is not a first occurrence, read from its
+//                     representative's (k_dd_emit has written those)
 //
 // Bytes at and beyond n never count: mask bits there are cleared as the words are read.  Bytes behind the last end bit
 // belong to no chunk and vanish.
@@ -207,7 +209,8 @@ __global__ __launch_bounds__(kDdThreads) void k_dd_emit(const uint8_t *__restric
                                                         const unsigned long long *__restrict__ remap, uint64_t n_unique,
                                                         uint64_t n_unique_bytes, uint8_t *__restrict__ out_text,
                                                         uint32_t *__restrict__ out_mask, uint32_t *__restrict__ weights,
-                                                        unsigned long long *__restrict__ first_chunk) {
+                                                        unsigned long long *__restrict__ first_chunk,
+                                                        uint32_t *__restrict__ unique_of) {
     __shared__ unsigned long long sh[kDdWaves];
     const uint64_t c = (uint64_t)blockIdx.x * kDdThreads + threadIdx.x;
     uint64_t start = 0, len = 0;
@@ -223,6 +226,7 @@ __global__ __launch_bounds__(kDdThreads) void k_dd_emit(const uint8_t *__restric
     const unsigned long long p = home[c];
     weights[j] = p == kDedupNoHome ? 1u : t.cnts[p];
     first_chunk[j] = remap ? remap[c] : c;
+    if (unique_of) unique_of[c] = (uint32_t)j;
     const uint8_t *src = text + start;
     uint8_t *dst = out_text + o;
     uint64_t i = 0;
@@ -233,6 +237,18 @@ __global__ __launch_bounds__(kDdThreads) void k_dd_emit(const uint8_t *__restric
     for (; i < len; ++i) dst[i] = src[i];
     const uint64_t e = o + len - 1;
     atomicOr(&out_mask[e >> 5], 1u << (e & 31));
+}
+
+// option "map": the chunks that are not a first occurrence take their representative's index among the unique chunks
+// (k_dd_emit wrote it; a representative's entry is not written here, so reads and writes never meet)
+__global__ __launch_bounds__(kDdThreads) void k_dd_map(const unsigned long long *__restrict__ home, DdTable t,
+                                                       uint64_t n_chunks, uint32_t *__restrict__ unique_of) {
+    const uint64_t c = (uint64_t)blockIdx.x * kDdThreads + threadIdx.x;
+    if (c >= n_chunks) return;
+    const unsigned long long p = home[c];
+    if (p == kDedupNoHome) return;                 // passes through: its own representative
+    const uint64_t rep = t.slots[p] & 0xFFFFFFFFull;
+    if (rep != c && rep < n_chunks) unique_of[c] = unique_of[rep];
 }
 
 uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kDdThreads - 1) / kDdThreads); }
@@ -253,6 +269,8 @@ struct mbpe_dedup : DevQueue {
     DevBuf<uint8_t> d_out_text, d_out_mask;
     DevBuf<uint32_t> d_weights;
     DevBuf<unsigned long long> d_first;
+    DevBuf<uint32_t> d_unique_of;                         // option "map": the unique chunk of every kept chunk
+    bool want_map = false, have_map = false;
     uint64_t n_chunks = 0, n_unique = 0, n_unique_bytes = 0;
     bool have = false;
     float last_ms = 0.f;
@@ -270,7 +288,7 @@ int dd_add_ms(mbpe_dedup *d) {
 // text and mask on the device; remap: NULL, or n_chunks input indices on the device
 int dd_run(mbpe_dedup *d, const uint8_t *text, uint64_t n_bytes, const uint8_t *mask, const unsigned long long *remap) {
     int rc;
-    d->have = false;
+    d->have = d->have_map = false;
     d->last_ms = 0.f;
     d->n_chunks = d->n_unique = d->n_unique_bytes = 0;
     const uint32_t *m32 = reinterpret_cast<const uint32_t *>(mask);
@@ -333,12 +351,16 @@ int dd_run(mbpe_dedup *d, const uint8_t *text, uint64_t n_bytes, const uint8_t *
         if ((rc = d->d_out_mask.reserve(out_mask_bytes, d->mem)) != MBPE_OK) return rc;
         if ((rc = d->d_weights.reserve(ctl.n_unique * 4, d->mem)) != MBPE_OK) return rc;
         if ((rc = d->d_first.reserve(ctl.n_unique * 8, d->mem)) != MBPE_OK) return rc;
+        if (d->want_map && (rc = d->d_unique_of.reserve(n_chunks * 4, d->mem)) != MBPE_OK) return rc;
+        uint32_t *unique_of = d->want_map ? d->d_unique_of.get() : nullptr;
         DCHK(hipEventRecord(d->ev0, d->stream));
         DCHK(hipMemsetAsync(d->d_out_mask, 0, out_mask_bytes, d->stream));
         hipLaunchKernelGGL(k_dd_emit, dim3(n_blk), dim3(kDdThreads), 0, d->stream, text, d->d_cend.get(), d->d_home.get(), t,
                            n_chunks, blk_cnt, blk_bytes, remap, (uint64_t)ctl.n_unique, (uint64_t)ctl.n_unique_bytes,
                            d->d_out_text.get(), reinterpret_cast<uint32_t *>(d->d_out_mask.get()), d->d_weights.get(),
-                           d->d_first.get());
+                           d->d_first.get(), unique_of);
+        if (unique_of)
+            hipLaunchKernelGGL(k_dd_map, dim3(n_blk), dim3(kDdThreads), 0, d->stream, d->d_home.get(), t, n_chunks, unique_of);
         DCHK(hipGetLastError());
         DCHK(hipEventRecord(d->ev1, d->stream));
         DCHK(hipStreamSynchronize(d->stream));
@@ -351,10 +373,12 @@ int dd_run(mbpe_dedup *d, const uint8_t *text, uint64_t n_bytes, const uint8_t *
         if ((rc = d->d_out_mask.reserve(16, d->mem)) != MBPE_OK) return rc;
         if ((rc = d->d_weights.reserve(16, d->mem)) != MBPE_OK) return rc;
         if ((rc = d->d_first.reserve(16, d->mem)) != MBPE_OK) return rc;
+        if (d->want_map && (rc = d->d_unique_of.reserve(16, d->mem)) != MBPE_OK) return rc;
         DCHK(hipMemsetAsync(d->d_out_mask, 0, 16, d->stream));
         DCHK(hipStreamSynchronize(d->stream));
     }
     d->have = true;
+    d->have_map = d->want_map;
     return MBPE_OK;
 }
 
@@ -389,6 +413,7 @@ int mbpe_dedup_set_option(mbpe_dedup *d, const char *name, int64_t value) {
     if (!d || !name) return fail(MBPE_ERR_ARG, "mbpe_dedup_set_option: NULL argument");
     if (!strcmp(name, "max_chunk_bytes") && value >= 0 && value <= 0x7FFFFFFF) { d->max_chunk = (uint32_t)value; return MBPE_OK; }
     if (!strcmp(name, "hash_bits") && value >= 0 && value <= 64) { d->hash_bits = (uint32_t)value; return MBPE_OK; }
+    if (!strcmp(name, "map") && (value == 0 || value == 1)) { d->want_map = value == 1; return MBPE_OK; }
     return fail(MBPE_ERR_ARG, std::string("mbpe_dedup_set_option: unknown option or bad value: ") + name);
 }
 
@@ -507,6 +532,28 @@ int mbpe_dedup_get(mbpe_dedup *d, uint8_t *text_out, uint64_t *chunk_off_out, ui
             return fail(MBPE_ERR_OOM, "mbpe_dedup_get: host allocation failed");
         }
     }
+    return MBPE_OK;
+}
+
+int mbpe_dedup_map(const mbpe_dedup *d, const uint32_t **unique_of_dev_out, uint64_t *n_chunks_out) {
+    if (!d) return fail(MBPE_ERR_ARG, "mbpe_dedup_map: NULL argument");
+    if (!d->have) return fail(MBPE_ERR_STATE, "mbpe_dedup_map: no dedup has succeeded yet");
+    if (!d->have_map) return fail(MBPE_ERR_STATE, "mbpe_dedup_map: the latest dedup ran without the option \"map\"");
+    if (unique_of_dev_out) *unique_of_dev_out = d->d_unique_of;
+    if (n_chunks_out) *n_chunks_out = d->n_chunks;
+    return MBPE_OK;
+}
+
+int mbpe_dedup_get_map(mbpe_dedup *d, uint32_t *unique_of_out, uint64_t cap_chunks, uint64_t *n_chunks_out) {
+    const uint32_t *src = nullptr;
+    uint64_t n = 0;
+    const int rc = mbpe_dedup_map(d, &src, &n);
+    if (rc != MBPE_OK) return rc;
+    if (n_chunks_out) *n_chunks_out = n;
+    if (!unique_of_out) return MBPE_OK;
+    if (cap_chunks < n) return fail(MBPE_ERR_ARG, "mbpe_dedup_get_map: unique_of_out is too small");
+    DCHK(hipSetDevice(d->device));
+    if (n) DCHK(hipMemcpy(unique_of_out, src, n * 4, hipMemcpyDeviceToHost));
     return MBPE_OK;
 }
 

@@ -38,7 +38,14 @@
 // start travels with it: org[i] (32 bits, relative to the piece), written by the widen kernel, carried by the scatter
 // kernel beside the tokens and ping-ponged like them; a merged token keeps its left token's org.  With threshold 0
 // none of this exists: the plain kernels are launched and no org buffer is reserved.
+//
+// Option "dedup" (no dropout, no byte offsets): a chunk's tokens depend on its bytes alone, so the call's chunks go
+// through the encoder's own deduper (dedup.h, with the inverse map), the passes above run over the unique text as one
+// piece, the finishing kernel writes a table of token runs in the caller's format, and the expansion (expand.h) copies
+// every chunk's run to its place -- see enc_dedup_body.  With the option off none of this exists either.
+#include "dedup.h"
 #include "dropout.h"
+#include "expand.h"
 #include "hip_host.h"
 #include "pack.h"
 #include "rank.h"
@@ -348,6 +355,19 @@ __global__ __launch_bounds__(256) void k_enc_doc_tok(const unsigned long long *_
     doc_tok[i] = r ? ends[r - 1] : 0ull;
 }
 
+// rank[i] = the end bits of the mask below text byte pos[i]: the index of the chunk that starts there (option "dedup":
+// the chunks of the singles and of the document boundaries)
+__global__ __launch_bounds__(256) void k_enc_pos_rank(const unsigned long long *__restrict__ pos, uint64_t n_pos,
+                                                      const uint32_t *__restrict__ mask, uint64_t n_bytes,
+                                                      const unsigned long long *__restrict__ block_off, uint64_t n_blocks,
+                                                      const unsigned long long *__restrict__ total,
+                                                      unsigned long long *__restrict__ rank) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pos) return;
+    const uint64_t p = pos[i] < n_bytes ? pos[i] : n_bytes;
+    rank[i] = mask_rank(p, mask, block_off, n_blocks, total);
+}
+
 enum FinMode {
     kFinFlags = 0,      // uint32_t, bit 31 = last token of its chunk (as the passes leave them)
     kFinU32 = 1,        // uint32_t ids
@@ -526,6 +546,21 @@ struct mbpe_encoder : DevQueue {
     std::vector<unsigned long long> list;
     std::vector<uint64_t> pass_tokens;        // latest call: tokens that entered pass k, summed over the pieces
     std::vector<uint64_t> chunk_tok, doc_tok; // mbpe_encoder_encode_batch: token offsets of the chunks, of the documents
+    // option "dedup" (nothing of this exists while it is 0): the deduper; the unique chunks' tokens in the caller's
+    // format and their ends, the one-token chunks behind them; the expansion's span offsets and chunk ends; the
+    // positions whose chunk is asked for and those chunks; the mask's block counts; host output on its way
+    bool dedup = false;
+    int64_t dedup_max_chunk = -1;             // option "dedup_max_chunk_bytes"; -1: the deduper's default
+    mbpe_dedup *dd = nullptr;
+    DevBuf<uint8_t> d_utab, d_stage;
+    DevBuf<unsigned long long> d_uends, d_exp_off, d_exp_ends, d_q_pos, d_q_chunk, d_mblk_off;
+    DevBuf<uint32_t> d_sg_tok, d_mblk_cnt;
+    std::vector<uint32_t> sg_tok;
+    std::vector<unsigned long long> q_pos;
+    std::vector<SingleChunk> dd_singles;
+    bool dd_ran = false;                      // the latest call went through the deduper (mbpe_encoder_dedup_stats)
+    uint64_t dd_chunks = 0, dd_unique = 0, dd_unique_bytes = 0, dd_unique_tokens = 0;
+    float dd_expand_ms = 0.f;
 };
 
 namespace {
@@ -1015,6 +1050,247 @@ int boff_check(const mbpe_encoder *e, const std::string &who, EncCall *a) {
     return MBPE_OK;
 }
 
+// ---- option "dedup": dedup -> the passes over the unique chunks -> expansion (expand.h) ---------------------------
+// Without dropout a chunk's tokens depend on its bytes alone, in both orders: the deduper (dedup.h, with "map") names
+// the unique chunk of every chunk, the passes run over the unique text as one piece without any single -- a NUL-led
+// chunk's bytes there are ordinary bytes that nothing points at --, the finishing kernel writes the table in the
+// caller's format with the runs' ends, the chunks that are one token by rule become runs of their own, and the
+// expansion writes every chunk's run to its place.
+
+// what dropout and byte offsets get on this route, before the device is touched
+int dedup_check(const mbpe_encoder *e, const std::string &who, const uint64_t *tok_byte_off_out) {
+    if (!e->dedup) return MBPE_OK;
+    if (e->drop_threshold)
+        return fail(MBPE_ERR_ARG, who + ": dropout and the option \"dedup\" exclude each other (a dropped instance depends "
+                                        "on its position, so equal chunks do not share their tokens)");
+    if (tok_byte_off_out)
+        return fail(MBPE_ERR_ARG, who + ": token byte offsets are not computed while the option \"dedup\" is on");
+    return MBPE_OK;
+}
+
+// a call that met nothing to dedup (an empty text) still went this way
+void dedup_nothing(mbpe_encoder *e) {
+    e->dd_ran = true;
+    e->dd_chunks = e->dd_unique = e->dd_unique_bytes = e->dd_unique_tokens = 0;
+    e->dd_expand_ms = 0.f;
+}
+
+// a.mask_dev: the endmask calls (text, mask, singles, doc_off as they state them); else chunk_off, checked, n_bytes > 0
+int enc_dedup_body(mbpe_encoder *e, const EncCall &a) {
+    const bool endmask = a.mask_dev != nullptr;
+    const uint64_t n_bytes = a.n_bytes, esz = a.token_bits / 8;
+    const std::string who = endmask ? "mbpe_encoder_encode_endmask" : "mbpe_encoder_encode";
+    int rc = MBPE_OK;
+    if (a.tokens_out && a.out_on_device && ((uintptr_t)a.tokens_out & (esz - 1)))
+        return fail(MBPE_ERR_ARG, who + ": tokens_out must be aligned to its elements (option \"dedup\")");
+    ECHK(hipSetDevice(e->device));
+    e->dd_ran = false;
+    // the chunks that are one token, before anything else (a host text: before the device is touched)
+    e->singles.clear();
+    if (endmask) {
+        for (uint64_t k = 0; k < a.n_singles; ++k)
+            e->singles.push_back({a.singles[k].start, a.singles[k].len, a.singles[k].id, 0});
+    } else if (!a.text_on_device) {
+        for (uint64_t c = 0; c < a.n_chunks; ++c) {
+            const uint64_t s = a.chunk_off[c], t = a.chunk_off[c + 1];
+            long long id;
+            if (t > s && a.text[s] == 0 && stoi_value(a.text + s + 1, t - s - 1, &id))
+                if ((rc = add_single(e, s, t - s, id, a.token_bits)) != MBPE_OK) return rc;
+        }
+    } else {
+        if ((rc = device_singles(e, a.text, a.chunk_off, Piece{0, a.n_chunks}, a.token_bits)) != MBPE_OK) return rc;
+    }
+    e->dd_singles.swap(e->singles);               // (the unique text is encoded without any: piece_upload reads e->singles)
+    e->singles.clear();
+    const uint64_t n_sg = e->dd_singles.size();
+
+    // the deduper: created by the first call that needs it; its stream starts where the encoder's has finished
+    if (!e->dd) {
+        if ((rc = mbpe_dedup_create(e->device, &e->dd)) != MBPE_OK) return rc;
+        if ((rc = mbpe_dedup_set_option(e->dd, "map", 1)) != MBPE_OK) return rc;
+    }
+    if ((rc = mbpe_dedup_set_option(e->dd, "max_chunk_bytes",
+                                    e->dedup_max_chunk >= 0 ? e->dedup_max_chunk : (int64_t)kDedupMaxChunkBytes)) != MBPE_OK)
+        return rc;
+    const uint8_t *text = a.text;
+    if (a.text_on_device && ((uintptr_t)a.text & 15)) {        // the deduper reads 16 aligned bytes at a time
+        if ((rc = e->d_text.reserve(n_bytes, e->mem)) != MBPE_OK) return rc;
+        ECHK(hipMemcpyAsync(e->d_text, a.text, n_bytes, hipMemcpyDeviceToDevice, e->stream));
+        text = e->d_text;
+    }
+    ECHK(hipStreamSynchronize(e->stream));
+    uint64_t nu = 0, nub = 0, n_kept = 0;
+    rc = endmask ? mbpe_dedup_chunks_endmask(e->dd, text, n_bytes, a.mask_dev, &nu, &nub)
+                 : mbpe_dedup_chunks(e->dd, text, n_bytes, a.text_on_device, a.chunk_off, a.n_chunks, &nu, &nub);
+    if (rc != MBPE_OK) return rc;
+    const uint8_t *u_text = nullptr, *u_mask = nullptr;
+    const uint32_t *uof_view = nullptr;
+    float dd_ms = 0.f;
+    if ((rc = mbpe_dedup_result(e->dd, &u_text, &u_mask, nullptr, nullptr)) != MBPE_OK) return rc;
+    if ((rc = mbpe_dedup_map(e->dd, &uof_view, &n_kept)) != MBPE_OK) return rc;
+    if ((rc = mbpe_dedup_kernel_ms(e->dd, &dd_ms)) != MBPE_OK) return rc;
+    uint32_t *uof = const_cast<uint32_t *>(uof_view);           // (the singles' chunks are patched in place)
+    e->last_ms += dd_ms;
+    const uint64_t n_entries = nu + n_sg + 1;                   // the unique chunks, the singles, the empty run
+    if (n_entries >= 0xFFFFFFFFull) return fail(MBPE_ERR_ARG, who + ": 2^32 - 1 table runs or more (option \"dedup\")");
+
+    // the unique text through the passes, as one piece
+    PieceRun r;
+    r.pn = nub;
+    uint64_t limit = 0;
+    if ((rc = piece_limit(e, nub, false, &limit)) != MBPE_OK) return rc;
+    if (nub > limit)
+        return fail(MBPE_ERR_OOM, who + ": the unique chunks hold " + std::to_string(nub) +
+                                      " bytes, more than one piece may hold (" + std::to_string(limit) +
+                                      "; option \"piece_bytes\"), and the \"dedup\" route runs them as one piece");
+    const uint64_t one[2] = {0, nub};
+    EncCall u = {};
+    u.text = u_text;
+    u.n_bytes = nub;
+    u.text_on_device = 1;
+    u.chunk_off = one;
+    u.n_chunks = 1;
+    u.token_bits = a.token_bits;
+    u.mask_on_device = true;
+    u.mask_dev = u_mask;
+    const int mode = a.token_bits == 16 ? kFinU16 : a.out_on_device ? kFinFlags : kFinU32;
+    if (nub) {
+        if ((rc = piece_upload(e, u, Piece{0, 1}, &r)) != MBPE_OK) return rc;
+        if ((rc = piece_passes(e, u, 0, &r)) != MBPE_OK) return rc;
+    }
+    const uint64_t n = r.n;
+    if ((rc = e->d_utab.reserve((n + n_sg + 8) * esz, e->mem)) != MBPE_OK) return rc;
+    if ((rc = e->d_uends.reserve(n_entries * 8, e->mem)) != MBPE_OK) return rc;
+    if (n) {
+        const uint64_t n_spans = span_count(n);
+        const dim3 grid(span_grid(n));
+        hipLaunchKernelGGL(k_enc_end_count, grid, dim3(kSpanThreads), 0, e->stream, e->tok[r.cur], n, e->span_a);
+        hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans, e->span_off,
+                           e->d_res);
+        auto finish = [&](auto m) {
+            hipLaunchKernelGGL((k_enc_finish<m(), true>), grid, dim3(kSpanThreads), 0, e->stream, e->tok[r.cur], n,
+                               static_cast<void *>(e->d_utab.get()), e->span_off, 0ull, e->d_uends.get(), nu);
+        };
+        switch (mode) {
+            case kFinFlags: finish(std::integral_constant<int, kFinFlags>()); break;
+            case kFinU32: finish(std::integral_constant<int, kFinU32>()); break;
+            default: finish(std::integral_constant<int, kFinU16>()); break;
+        }
+        ECHK(hipEventRecord(e->ev1, e->stream));
+        unsigned long long found = 0;
+        ECHK(hipMemcpyAsync(&found, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
+        float ms = 0.f;
+        if ((rc = e->wait(&ms)) != MBPE_OK) return rc;
+        e->last_ms += ms;
+        if (found != nu) return fail(MBPE_ERR_HIP, who + ": the unique chunks and their token runs differ in number");
+    } else if (nu) {
+        return fail(MBPE_ERR_HIP, who + ": the unique chunks left no token");
+    }
+
+    // whose chunk is asked for: the singles' first and last bytes' (2 n_sg) and, from the endmask calls, the documents'
+    const uint64_t n_docq = endmask && a.doc_off ? a.n_docs + 1 : 0, n_q = 2 * n_sg + n_docq;
+    e->sg_tok.resize(n_sg);
+    e->q_pos.assign(n_q, 0);
+    for (uint64_t k = 0; k < n_sg; ++k) e->sg_tok[k] = e->dd_singles[k].id | (mode == kFinFlags ? kTokEnd : 0u);
+    if (endmask) {
+        for (uint64_t k = 0; k < n_sg; ++k) {
+            e->q_pos[k] = e->dd_singles[k].start;
+            e->q_pos[n_sg + k] = e->dd_singles[k].start + e->dd_singles[k].len;
+        }
+        for (uint64_t i = 0; i < n_docq; ++i) e->q_pos[2 * n_sg + i] = a.doc_off[i];
+    } else {
+        // chunk_off says it: a single is one chunk, and its index counts the chunks that are not empty
+        uint64_t kept = 0, k = 0;
+        for (uint64_t c = 0; c < a.n_chunks && k < n_sg; ++c) {
+            if (a.chunk_off[c + 1] == a.chunk_off[c]) continue;
+            if (a.chunk_off[c] == e->dd_singles[k].start) { e->q_pos[k] = kept; e->q_pos[n_sg + k] = kept + 1; ++k; }
+            ++kept;
+        }
+        if (k != n_sg) return fail(MBPE_ERR_HIP, who + ": a one-token chunk is not among the chunks");
+    }
+    const uint64_t n_spans_x = expand_span_count(n_kept);
+    if ((rc = e->d_exp_off.reserve((n_spans_x + 1) * 8, e->mem)) != MBPE_OK) return rc;
+    if (n_q) {
+        if ((rc = e->d_q_pos.reserve(n_q * 8, e->mem)) != MBPE_OK) return rc;
+        if ((rc = e->d_q_chunk.reserve(n_q * 8, e->mem)) != MBPE_OK) return rc;
+        if (n_sg && (rc = e->d_sg_tok.reserve(n_sg * 4, e->mem)) != MBPE_OK) return rc;
+    }
+    if (n_docq && (rc = e->d_doc_off.reserve(n_docq * 8, e->mem)) != MBPE_OK) return rc;
+    const uint64_t n_words = (n_bytes + 31) / 32, n_blocks = (n_words + kMaskBlockWords - 1) / kMaskBlockWords;
+    if (endmask && n_q) {
+        if ((rc = e->d_mblk_cnt.reserve(n_blocks * 4, e->mem)) != MBPE_OK) return rc;
+        if ((rc = e->d_mblk_off.reserve(n_blocks * 8, e->mem)) != MBPE_OK) return rc;
+    }
+    ECHK(hipEventRecord(e->ev0, e->stream));
+    unsigned long long *q_chunk = endmask ? e->d_q_chunk.get() : e->d_q_pos.get();
+    if (n_q) {
+        ECHK(hipMemcpyAsync(e->d_q_pos, e->q_pos.data(), n_q * 8, hipMemcpyHostToDevice, e->stream));
+        if (n_sg) ECHK(hipMemcpyAsync(e->d_sg_tok, e->sg_tok.data(), n_sg * 4, hipMemcpyHostToDevice, e->stream));
+        if (endmask) {
+            const uint32_t *mask32 = reinterpret_cast<const uint32_t *>(a.mask_dev);
+            hipLaunchKernelGGL(k_enc_mask_count, dim3((uint32_t)((n_blocks * kWave + 255) / 256)), dim3(256), 0, e->stream,
+                               mask32, n_words, n_blocks, e->d_mblk_cnt.get());
+            hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->d_mblk_cnt.get(), n_blocks,
+                               e->d_mblk_off.get(), e->d_res + 2);
+            hipLaunchKernelGGL(k_enc_pos_rank, dim3((uint32_t)((n_q + 255) / 256)), dim3(256), 0, e->stream, e->d_q_pos.get(),
+                               n_q, mask32, n_bytes, e->d_mblk_off.get(), n_blocks, e->d_res + 2, e->d_q_chunk.get());
+        }
+    }
+    expand_patch_launch(e->stream, e->d_utab.get(), n, a.token_bits, e->d_uends, nu, uof, n_kept,
+                        ExpandSingles{e->d_sg_tok, q_chunk, q_chunk + n_sg, n_sg});
+    const ExpandSrc src = {e->d_utab.get(), n + n_sg, e->d_uends, n_entries, uof, n_kept, a.token_bits};
+    expand_count_launch(e->stream, src, e->d_exp_off, e->d_res);
+    ECHK(hipEventRecord(e->ev1, e->stream));
+    unsigned long long total = 0;
+    ECHK(hipMemcpyAsync(&total, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
+    float ms_count = 0.f, ms_write = 0.f;
+    if ((rc = e->wait(&ms_count)) != MBPE_OK) return rc;
+
+    e->dd_ran = true;
+    e->dd_chunks = n_kept;
+    e->dd_unique = nu;
+    e->dd_unique_bytes = nub;
+    e->dd_unique_tokens = n;
+    e->dd_expand_ms = ms_count;
+    e->last_ms += ms_count;
+    *a.n_out = total;
+    if (a.n_passes_out) *a.n_passes_out = r.passes;
+    // nothing has been written yet: an output that is too small stays as it was
+    if (a.tokens_out && a.cap < total) return fail(MBPE_ERR_ARG, "tokens_out too small");
+
+    const bool want_ends = a.chunk_tok_off_out != nullptr;
+    const bool to_host = a.tokens_out && !a.out_on_device;
+    if (to_host && (rc = e->d_stage.reserve(std::max<uint64_t>(total, 1) * esz, e->mem)) != MBPE_OK) return rc;
+    if (want_ends && (rc = e->d_exp_ends.reserve(std::max<uint64_t>(n_kept, 1) * 8, e->mem)) != MBPE_OK) return rc;
+    void *out = !a.tokens_out ? nullptr : to_host ? static_cast<void *>(e->d_stage.get()) : a.tokens_out;
+    ECHK(hipEventRecord(e->ev0, e->stream));
+    if ((out && total) || want_ends)
+        expand_write_launch(e->stream, src, e->d_exp_off, out, want_ends ? e->d_exp_ends.get() : nullptr, 0);
+    if (n_docq)
+        expand_before_launch(e->stream, src, e->d_exp_off, q_chunk + 2 * n_sg, n_docq, e->d_doc_off);
+    if ((rc = e->finish(&ms_write)) != MBPE_OK) return rc;
+    e->dd_expand_ms += ms_write;
+    e->last_ms += ms_write;
+
+    if (to_host && total) ECHK(hipMemcpyAsync(a.tokens_out, e->d_stage, total * esz, hipMemcpyDeviceToHost, e->stream));
+    if (n_docq && a.doc_tok_off_out)
+        ECHK(hipMemcpyAsync(a.doc_tok_off_out, e->d_doc_off, n_docq * 8, hipMemcpyDeviceToHost, e->stream));
+    if (want_ends) {
+        e->list.resize(n_kept);
+        if (n_kept) ECHK(hipMemcpyAsync(e->list.data(), e->d_exp_ends, n_kept * 8, hipMemcpyDeviceToHost, e->stream));
+    }
+    ECHK(hipStreamSynchronize(e->stream));
+    if (want_ends) {
+        uint64_t k = 0, last = 0;
+        a.chunk_tok_off_out[0] = 0;
+        for (uint64_t c = 0; c < a.n_chunks; ++c) {    // an empty chunk repeats its predecessor's offset
+            if (a.chunk_off[c + 1] > a.chunk_off[c] && k < n_kept) last = e->list[k++];
+            a.chunk_tok_off_out[c + 1] = last;
+        }
+    }
+    return MBPE_OK;
+}
+
 int enc_run_body(mbpe_encoder *e, EncCall a) {
     const uint64_t one[2] = {0, a.n_bytes};
     if (!a.chunk_off) { a.chunk_off = one; a.n_chunks = 1; }
@@ -1028,15 +1304,18 @@ int enc_run_body(mbpe_encoder *e, EncCall a) {
     if (a.token_bits == 16 && 256ull + e->n_merges > 65536ull)
         return fail(MBPE_ERR_VOCAB, "token_bits 16 with more than 65,536 token ids");
     if (a.chunk_tok_off_out) a.chunk_tok_off_out[0] = 0;
+    e->dd_ran = false;
     if (n_bytes == 0) {
         if (a.chunk_tok_off_out)
             for (uint64_t c = 0; c < n_chunks; ++c) a.chunk_tok_off_out[c + 1] = 0;
+        if (e->dedup) dedup_nothing(e);
         return boff_begin(e, a);
     }
     ECHK(hipSetDevice(e->device));
     if (int rc0 = boff_begin(e, a)) return rc0;
     e->last_ms = 0.f;
     e->pass_tokens.clear();
+    if (e->dedup) return enc_dedup_body(e, a);
 
     // pieces: whole chunks, at most `limit` bytes each
     uint64_t limit = 0;
@@ -1212,8 +1491,10 @@ int enc_endmask_body(mbpe_encoder *e, EncCall a) {
     ECHK(hipSetDevice(e->device));
     e->last_ms = 0.f;
     e->pass_tokens.clear();
+    e->dd_ran = false;
     if (int rc0 = boff_begin(e, a)) return rc0;
     if (n_bytes == 0) {
+        if (e->dedup) dedup_nothing(e);
         if (a.doc_off) {
             int rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
             if (rc != MBPE_OK) return rc;
@@ -1223,6 +1504,7 @@ int enc_endmask_body(mbpe_encoder *e, EncCall a) {
         }
         return MBPE_OK;
     }
+    if (e->dedup) return enc_dedup_body(e, a);
     uint64_t limit = 0;                                           // the rule of mbpe_encoder_encode
     int rc = piece_limit(e, n_bytes, a.tok_byte_off_out && !a.out_on_device, &limit);
     if (rc != MBPE_OK) return rc;
@@ -1359,6 +1641,7 @@ int mbpe_encoder_create(int device_id, const uint32_t *merges, uint32_t n_merges
 void mbpe_encoder_destroy(mbpe_encoder *e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
+    if (e->dd) mbpe_dedup_destroy(e->dd);
     delete e;                                 // the buffers, then the events, then the stream
 }
 
@@ -1372,6 +1655,16 @@ int mbpe_encoder_set_option(mbpe_encoder *e, const char *name, int64_t value) {
     if (strcmp(name, "rank_order") == 0) {
         if (value != 0 && value != 1) return fail(MBPE_ERR_ARG, "rank_order must be 0 or 1");
         e->rank_order = value == 1;
+        return MBPE_OK;
+    }
+    if (strcmp(name, "dedup") == 0) {
+        if (value != 0 && value != 1) return fail(MBPE_ERR_ARG, "dedup must be 0 or 1");
+        e->dedup = value == 1;
+        return MBPE_OK;
+    }
+    if (strcmp(name, "dedup_max_chunk_bytes") == 0) {
+        if (value < 0 || value > 0x7FFFFFFF) return fail(MBPE_ERR_ARG, "dedup_max_chunk_bytes must lie in [0, 2^31)");
+        e->dedup_max_chunk = value;
         return MBPE_OK;
     }
     return fail(MBPE_ERR_ARG, std::string("mbpe_encoder_set_option: no option \"") + name + "\"");
@@ -1405,6 +1698,7 @@ int mbpe_encoder_encode_byteoff(mbpe_encoder *e, const uint8_t *text, uint64_t n
                  chunk_tok_off_out, n_out, n_passes_out};
     a.tok_byte_off_out = tok_byte_off_out;
     int rc = drop_check(e, "mbpe_encoder_encode");
+    if (rc == MBPE_OK) rc = dedup_check(e, "mbpe_encoder_encode", tok_byte_off_out);
     if (rc == MBPE_OK) rc = boff_check(e, "mbpe_encoder_encode_byteoff", &a);
     if (rc != MBPE_OK) return rc;
     return enc_guard("mbpe_encoder_encode", [&] { return enc_run_body(e, a); });
@@ -1425,6 +1719,7 @@ static int enc_batch(mbpe_encoder *e, EncCall a, const EncPack &k) {
     if (!e || !k.n_rows_out || !k.doc_chunk_off || !k.spec || (!a.text && a.n_bytes))
         return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_batch: NULL argument");
     int rc = drop_check(e, "mbpe_encoder_encode_batch");
+    if (rc == MBPE_OK) rc = dedup_check(e, "mbpe_encoder_encode_batch", nullptr);
     if (rc == MBPE_OK) rc = pack_check_spec(k.spec, k.token_bits());
     if (rc != MBPE_OK) return rc;
     const uint64_t one[2] = {0, a.n_bytes};
@@ -1486,6 +1781,7 @@ int mbpe_encoder_encode_endmask_byteoff(mbpe_encoder *e, const uint8_t *text_dev
     if (!e || !n_out || ((!text_dev || !endmask_dev) && n_bytes))
         return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_endmask: NULL argument");
     if ((rc = drop_check(e, "mbpe_encoder_encode_endmask")) != MBPE_OK) return rc;
+    if ((rc = dedup_check(e, "mbpe_encoder_encode_endmask", tok_byte_off_out)) != MBPE_OK) return rc;
     if ((uintptr_t)endmask_dev & 3) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_endmask: the mask must be 4-byte aligned");
     if (token_bits == 16 && 256ull + e->n_merges > 65536ull)
         return fail(MBPE_ERR_VOCAB, "token_bits 16 with more than 65,536 token ids");
@@ -1516,6 +1812,7 @@ int mbpe_encoder_encode_batch_endmask(mbpe_encoder *e, const uint8_t *text_dev, 
         return fail(MBPE_ERR_ARG, who + ": doc_off must start at 0 and end at n_bytes");
     if (!e || ((!text_dev || !endmask_dev) && n_bytes)) return fail(MBPE_ERR_ARG, who + ": NULL argument");
     if ((rc = drop_check(e, who)) != MBPE_OK) return rc;
+    if ((rc = dedup_check(e, who, nullptr)) != MBPE_OK) return rc;
     if ((uintptr_t)endmask_dev & 3) return fail(MBPE_ERR_ARG, who + ": the mask must be 4-byte aligned");
     rc = enc_batch_check(e, k);
     if (rc != MBPE_OK) return rc;
@@ -1561,6 +1858,18 @@ int mbpe_encoder_pass_tokens(const mbpe_encoder *e, uint64_t *tokens_out, uint32
     if (!tokens_out) return MBPE_OK;
     if (cap < e->pass_tokens.size()) return fail(MBPE_ERR_ARG, "tokens_out too small");
     for (size_t k = 0; k < e->pass_tokens.size(); ++k) tokens_out[k] = e->pass_tokens[k];
+    return MBPE_OK;
+}
+
+int mbpe_encoder_dedup_stats(const mbpe_encoder *e, uint64_t *n_chunks_out, uint64_t *n_unique_out,
+                             uint64_t *n_unique_bytes_out, uint64_t *n_unique_tokens_out, float *expand_ms_out) {
+    if (!e) return fail(MBPE_ERR_ARG, "mbpe_encoder_dedup_stats: NULL argument");
+    if (!e->dd_ran) return fail(MBPE_ERR_STATE, "mbpe_encoder_dedup_stats: the latest call did not dedup");
+    if (n_chunks_out) *n_chunks_out = e->dd_chunks;
+    if (n_unique_out) *n_unique_out = e->dd_unique;
+    if (n_unique_bytes_out) *n_unique_bytes_out = e->dd_unique_bytes;
+    if (n_unique_tokens_out) *n_unique_tokens_out = e->dd_unique_tokens;
+    if (expand_ms_out) *expand_ms_out = e->dd_expand_ms;
     return MBPE_OK;
 }
 

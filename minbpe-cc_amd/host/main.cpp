@@ -88,7 +88,12 @@ void usage() {
                  "                              chunks per merge: meant for -c first, for vocabularies beyond 65,536 and for\n"
                  "                              --continue-from; -c lexical below that is faster without it, and --encoder\n"
                  "                              basic has one chunk, so nothing is saved.  Combines with --device-split,\n"
-                 "                              --device-split-unicode, --continue-from and --conflict-resolution\n"
+                 "                              --device-split-unicode, --continue-from and --conflict-resolution.\n"
+                 "                              With --encode --device-encode: deduplicate the chunks on the device, encode\n"
+                 "                              the distinct ones and copy their tokens to every occurrence: the same output,\n"
+                 "                              with or without --device-split, --device-split-unicode and --rank-order;\n"
+                 "                              meant for large texts of natural language in rank order.  With --dropout or\n"
+                 "                              --byte-ranges-out it is an error; without --device-encode it has no effect\n"
                  "  --continue-from TEXT        With --train: load this model and continue its training on the input up to\n"
                  "                              --vocab-size, which must not be below the model's size; the result goes to\n"
                  "                              --model-path.  The loaded model's split pattern is used: --encoder has no\n"
@@ -254,6 +259,7 @@ int main(int argc, char *argv[]) {
             if (rank_order) mbpe_tok_set_encode_order(rt, 1);
             if (have_dropout) mbpe_tok_set_encode_dropout(rt, drop_threshold, seed);
             if (split_unicode) mbpe_tok_set_split_unicode(rt, 1);
+            if (dedup && device_encode) mbpe_tok_set_encode_dedup(rt, 1);
             std::vector<uint64_t> ranges(byte_ranges_path.empty() ? 0 : 2 * encoded.size());
             const int erc = !byte_ranges_path.empty()
                                 ? mbpe_tok_encode_byteoff(rt, in, input.size(), verbose, device_encode ? device : -1,

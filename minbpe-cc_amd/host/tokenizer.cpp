@@ -63,6 +63,7 @@ mbpe_encoder *Tokenizer::device_encoder(int device) {
         encoder_device_ = device;
     }
     int rc = mbpe_encoder_set_option(encoder_, "rank_order", rank_order_ ? 1 : 0);
+    if (rc == MBPE_OK) rc = mbpe_encoder_set_option(encoder_, "dedup", encode_dedup_ ? 1 : 0);
     if (rc == MBPE_OK) rc = mbpe_encoder_set_dropout(encoder_, drop_threshold_, drop_seed_);
     if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
     return encoder_;
@@ -1027,6 +1028,16 @@ int mbpe_tok_set_train_dedup(mbpe_tokenizer *t, int on) {
         return MBPE_ERR_ARG;
     }
     t->t->set_train_dedup(on == 1);
+    return MBPE_OK;
+}
+
+int mbpe_tok_set_encode_dedup(mbpe_tokenizer *t, int on) {
+    if (!t) return MBPE_ERR_ARG;
+    if (on != 0 && on != 1) {
+        mbpe_host::set_last_error("mbpe_tok_set_encode_dedup: on must be 0 or 1");
+        return MBPE_ERR_ARG;
+    }
+    t->t->set_encode_dedup(on == 1);
     return MBPE_OK;
 }
 

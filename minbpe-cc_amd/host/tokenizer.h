@@ -86,6 +86,8 @@ public:
     void set_split_unicode(bool on) { split_unicode_ = on; }
     // train() from here on runs on the distinct chunks with their counts (mbpe_tok_set_train_dedup)
     void set_train_dedup(bool on) { train_dedup_ = on; }
+    // the device encode calls from here on go through the encoder's "dedup" route (mbpe_tok_set_encode_dedup)
+    void set_encode_dedup(bool on) { encode_dedup_ = on; }
     // :725-751; device >= 0 expands the tokens on that HIP device (mbpe_decode_tokens) instead of the host loop
     std::string decode(const std::vector<Token> &tokens, bool verbose, int device = -1);
     // decode() of every token list, [i] == decode(docs[i], false, -1), in one mbpe_decode_batch on HIP device `device`
@@ -173,6 +175,7 @@ private:
     bool encode_split_ = false;
     bool split_unicode_ = false;
     bool train_dedup_ = false;
+    bool encode_dedup_ = false;
     bool rank_order_ = false;
     uint64_t drop_threshold_ = 0, drop_seed_ = 0;
 };

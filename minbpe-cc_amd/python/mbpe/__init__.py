@@ -43,6 +43,7 @@ EXPORTS = [
     "mbpe_dedup_create", "mbpe_dedup_destroy", "mbpe_dedup_chunks_endmask", "mbpe_dedup_chunks", "mbpe_dedup_result",
     "mbpe_dedup_get", "mbpe_dedup_set_option", "mbpe_dedup_kernel_ms", "mbpe_dedup_alloc_count",
     "mbpe_load_corpus_weighted", "mbpe_load_corpus_endmask_weighted",
+    "mbpe_dedup_map", "mbpe_dedup_get_map", "mbpe_encoder_dedup_stats",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -53,6 +54,7 @@ TOK_EXPORTS = [
     "mbpe_tok_train_split_device", "mbpe_tok_set_encode_split", "mbpe_tok_set_split_unicode",
     "mbpe_tok_set_encode_order", "mbpe_tok_train_continue", "mbpe_tok_encode_byteoff",
     "mbpe_tok_encode_batch_byteoff_device", "mbpe_tok_set_encode_dropout", "mbpe_tok_set_train_dedup",
+    "mbpe_tok_set_encode_dedup",
 ]
 
 
@@ -254,6 +256,10 @@ def lib():
     L.mbpe_dedup_set_option.argtypes = [vp, ctypes.c_char_p, i64]
     L.mbpe_dedup_kernel_ms.argtypes = [vp, vp]
     L.mbpe_dedup_alloc_count.argtypes = [vp, vp]
+    L.mbpe_dedup_map.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u64)]
+    L.mbpe_dedup_get_map.argtypes = [vp, vp, u64, vp]
+    L.mbpe_encoder_dedup_stats.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.mbpe_tok_set_encode_dedup.argtypes = [vp, i32]
     L.mbpe_load_corpus_weighted.argtypes = [vp, vp, u64, vp, u64, i32, vp]
     L.mbpe_load_corpus_endmask_weighted.argtypes = [vp, vp, u64, i32, vp, vp, u64, i32]
     L.mbpe_tok_set_encode_order.argtypes = [vp, i32]
@@ -558,9 +564,11 @@ class Encoder:
     """One mbpe_encoder: internal_encode (Tokenizer.h:325-377) on a HIP device with the lookup table, the stream and
     the work buffers kept between calls."""
 
-    def __init__(self, merges, device=0, rank_order=False, dropout=0.0, seed=0):
+    def __init__(self, merges, device=0, rank_order=False, dropout=0.0, seed=0, dedup=False):
         """rank_order: the option "rank_order" from the start (set_option changes it between calls).
-        dropout, seed: BPE-dropout from the start (set_dropout changes it between calls); needs rank_order."""
+        dropout, seed: BPE-dropout from the start (set_dropout changes it between calls); needs rank_order.
+        dedup: the option "dedup" from the start: every call dedups its chunks on the device, encodes the distinct
+        ones and expands (the same results; dropout and byte offsets raise MbpeError(ERR_ARG) while it is on)."""
         self._h = ctypes.c_void_p()
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1, 2)
         _check(lib().mbpe_encoder_create(device, m.ctypes.data if len(m) else None, len(m), ctypes.byref(self._h)))
@@ -570,6 +578,8 @@ class Encoder:
             self.set_option("rank_order", 1)
         if dropout or seed:
             self.set_dropout(dropout, seed)
+        if dedup:
+            self.set_option("dedup", 1)
 
     def close(self):
         if self._h:
@@ -822,6 +832,15 @@ class Encoder:
         n = ctypes.c_uint64()
         _check(lib().mbpe_encoder_alloc_count(self._h, ctypes.byref(n)))
         return n.value
+
+    def dedup_stats(self):
+        """The latest call on the "dedup" route (mbpe_encoder_dedup_stats) -> dict: n_chunks (those the deduper kept),
+        n_unique, n_unique_bytes, n_unique_tokens, expand_ms.  MbpeError(ERR_STATE) when that call did not dedup."""
+        v = [ctypes.c_uint64() for _ in range(4)]
+        ms = ctypes.c_float()
+        _check(lib().mbpe_encoder_dedup_stats(self._h, *[ctypes.byref(x) for x in v], ctypes.byref(ms)))
+        names = ("n_chunks", "n_unique", "n_unique_bytes", "n_unique_tokens")
+        return dict(zip(names, (x.value for x in v)), expand_ms=ms.value)
 
 
 class Decoder:
@@ -1133,6 +1152,21 @@ class Deduper:
         f = np.zeros(max(nu, 1), dtype=np.uint64)
         _check(lib().mbpe_dedup_get(self._h, text.ctypes.data, off.ctypes.data, w.ctypes.data, f.ctypes.data, nb, nu))
         return (text[:self.n_unique_bytes].tobytes(), off[:self.n_unique + 1], w[:self.n_unique], f[:self.n_unique])
+
+    def unique_of(self):
+        """Host copy of the inverse map of the latest result (option "map"; mbpe_dedup_get_map) -> uint32 array with one
+        entry per chunk the deduper kept: the index of the unique chunk that has its bytes."""
+        n = ctypes.c_uint64()
+        _check(lib().mbpe_dedup_get_map(self._h, None, 0, ctypes.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.uint32)
+        _check(lib().mbpe_dedup_get_map(self._h, out.ctypes.data, n.value, ctypes.byref(n)))
+        return out[:n.value]
+
+    def map_device(self):
+        """Device address of unique_of (u32) and the number of chunks kept (mbpe_dedup_map), valid until the next call."""
+        p, n = ctypes.c_void_p(), ctypes.c_uint64()
+        _check(lib().mbpe_dedup_map(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
 
     def kernel_ms(self):
         ms = ctypes.c_float()
@@ -1461,15 +1495,17 @@ class Tokenizer:
     def load(self, path, verbose=False):
         _check(lib().mbpe_tok_load(self._h, os.fsencode(path), int(verbose)))
 
-    def _encode_split(self, device_split, order="greedy", dropout=0.0, seed=0):
+    def _encode_split(self, device_split, order="greedy", dropout=0.0, seed=0, dedup=False):
         if order not in ("greedy", "rank"):
             raise ValueError('order must be "greedy" or "rank"')
+        _check(lib().mbpe_tok_set_encode_dedup(self._h, int(bool(dedup))))
         _check(lib().mbpe_tok_set_encode_order(self._h, int(order == "rank")))
         _check(lib().mbpe_tok_set_encode_dropout(self._h, dropout_threshold(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF))
         _check(lib().mbpe_tok_set_encode_split(self._h, int(bool(device_split))))
         _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
 
-    def encode(self, data, device=None, device_split=False, order="greedy", byte_ranges=False, dropout=0.0, seed=0):
+    def encode(self, data, device=None, device_split=False, order="greedy", byte_ranges=False, dropout=0.0, seed=0,
+               dedup=False):
         """device None: internal_encode on the host; an int: on that HIP device (mbpe_tok_encode_device).
         device_split (here and in the batch calls; only with a device): the text is cut at the special tokens and split
         into chunks on the device too (mbpe_tok_set_encode_split); same tokens, gpt2 / gpt4 patterns only.  "unicode"
@@ -1483,8 +1519,11 @@ class Tokenizer:
         buffer the route hands the encoder, so the host loop and the device over the host split always agree, and
         they agree with device_split when the text has no special token and the pattern is basic, gpt2 or gpt4.
         byte_ranges=True (mbpe_tok_encode_byteoff): -> (tokens, ranges[n, 2] uint64), token j stands for
-        data[ranges[j, 0]:ranges[j, 1]] (a special token: the occurrence of its name)."""
-        self._encode_split(device_split, order, dropout, seed)
+        data[ranges[j, 0]:ranges[j, 1]] (a special token: the occurrence of its name).
+        dedup=True (here and in the batch calls; only with a device; mbpe_tok_set_encode_dedup): the chunks are
+        deduplicated on the device, the distinct ones encoded once and their tokens copied to every occurrence; same
+        tokens.  With byte_ranges or dropout > 0 the library's error is raised."""
+        self._encode_split(device_split, order, dropout, seed, dedup)
         text = _u8(data)
         n = ctypes.c_uint64()
         out = np.zeros(max(len(text), 1), dtype=np.uint32)
@@ -1503,11 +1542,11 @@ class Tokenizer:
         return out[:n.value].copy()
 
     def encode_batch(self, texts, device=0, device_split=False, order="greedy", byte_ranges=False, dropout=0.0,
-                     seed=0):
+                     seed=0, dedup=False):
         """encode() of every text in one device call (mbpe_tok_encode_batch_device) -> list of uint32 arrays; with
         byte_ranges=True (mbpe_tok_encode_batch_byteoff_device) a list of (tokens, ranges[n, 2] uint64) pairs, the
         ranges relative to each text's first byte.  With dropout, positions run over the texts laid end to end."""
-        self._encode_split(device_split, order, dropout, seed)
+        self._encode_split(device_split, order, dropout, seed, dedup)
         parts = [bytes(_u8(t)) for t in texts]
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
         if parts:
@@ -1530,12 +1569,12 @@ class Tokenizer:
 
     def encode_batch_padded(self, texts, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
                             pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
-                            device_split=False, order="greedy", dropout=0.0, seed=0):
+                            device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False):
         """Every text split like encode(), encoded and packed in one device call
         (mbpe_tok_encode_batch_packed_device) -> (ids [n_rows, seq_len], lengths [n_rows]) as numpy arrays; with
         out_ptr= and len_ptr= (device memory for cap_rows rows) the matrix stays on the device and the row count is
         returned.  bos_id / eos_id may be special-token ids.  layout "packed" gives the MBPE_PACK_PACKED rows."""
-        self._encode_split(device_split, order, dropout, seed)
+        self._encode_split(device_split, order, dropout, seed, dedup)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         parts = [bytes(_u8(t)) for t in texts]
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
@@ -1562,11 +1601,11 @@ class Tokenizer:
                          pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
                          labels=False, positions=False, segments=False, cu_seqlens=False, ignore_label=-100,
                          labels_ptr=None, pos_ptr=None, seg_ptr=None, device_split=False, order="greedy", dropout=0.0,
-                         seed=0):
+                         seed=0, dedup=False):
         """encode_batch_padded plus labels, positions, segments and cu_seqlens (mbpe_tok_encode_batch_aux_device): its
         arguments and those of pack_tokens_aux, whose dict (or, with out_ptr=, row count) is returned.  The documents'
         token offsets of the call: self.doc_tok_off."""
-        self._encode_split(device_split, order, dropout, seed)
+        self._encode_split(device_split, order, dropout, seed, dedup)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label)
         parts = [bytes(_u8(t)) for t in texts]
