@@ -327,45 +327,35 @@ __global__ __launch_bounds__(256) void k_enc_mask_count(const uint32_t *__restri
     if (lane == 0) cnt[block] = c;
 }
 
-// end bits of the mask below text byte p (<= n_bytes).  mask: 4 * n_words bytes and 4 more are readable
-__device__ __forceinline__ unsigned long long mask_rank(uint64_t p, const uint32_t *__restrict__ mask,
-                                                        const unsigned long long *__restrict__ block_off,
-                                                        uint64_t n_blocks, const unsigned long long *__restrict__ total) {
+// a mask with its blocks counted (mask_count_launch): block_off = the end bits before every block, *total = all of them
+struct MaskView {                          // (words: 4 * ceil(n_bytes / 32) bytes and 4 more are readable)
+    const uint32_t *words; uint64_t n_bytes, n_blocks; const unsigned long long *block_off, *total;
+};
+
+// end bits of the mask below text byte p (<= n_bytes)
+__device__ __forceinline__ unsigned long long mask_rank(uint64_t p, const MaskView &m) {
     const uint64_t w = p >> 5, block = w / kMaskBlockWords;
-    if (block >= n_blocks) return *total;
-    unsigned long long r = block_off[block];
-    for (uint64_t j = block * kMaskBlockWords; j < w; ++j) r += (unsigned long long)__popc(mask[j]);
-    if (p & 31u) r += (unsigned long long)__popc(mask[w] & ((1u << (p & 31u)) - 1u));
+    if (block >= m.n_blocks) return *m.total;
+    unsigned long long r = m.block_off[block];
+    for (uint64_t j = block * kMaskBlockWords; j < w; ++j) r += (unsigned long long)__popc(m.words[j]);
+    if (p & 31u) r += (unsigned long long)__popc(m.words[w] & ((1u << (p & 31u)) - 1u));
     return r;
 }
 
-// doc_tok[i] = output tokens that come from the bytes before pos[i] (a chunk boundary): the end of chunk rank - 1 in
-// the list the finishing kernel wrote, or 0 before the first chunk
-__global__ __launch_bounds__(256) void k_enc_doc_tok(const unsigned long long *__restrict__ pos, uint64_t n_pos,
-                                                     const uint32_t *__restrict__ mask, uint64_t n_bytes,
-                                                     const unsigned long long *__restrict__ block_off, uint64_t n_blocks,
-                                                     const unsigned long long *__restrict__ total,
-                                                     const unsigned long long *__restrict__ ends, uint64_t n_ends,
-                                                     unsigned long long *__restrict__ doc_tok) {
+// position i = pos[i * stride] (stride in 8-byte words: 1 for a list, 3 for the starts of SingleChunks), r = its rank =
+// the index of the chunk that starts there.  ends NULL: out[i] = r.  Else out[i] = the piece's tokens that come from the
+// bytes before the position: the end of chunk r - 1 in the finishing kernel's list, less tok_base; 0 before the first
+__global__ __launch_bounds__(256) void k_enc_mask_query(const unsigned long long *__restrict__ pos, uint32_t stride,
+                                                        uint64_t n_pos, MaskView m,
+                                                        const unsigned long long *__restrict__ ends, uint64_t n_ends,
+                                                        unsigned long long tok_base, unsigned long long *__restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pos) return;
-    const uint64_t p = pos[i] < n_bytes ? pos[i] : n_bytes;
-    unsigned long long r = mask_rank(p, mask, block_off, n_blocks, total);
+    const unsigned long long at = pos[i * stride];
+    unsigned long long r = mask_rank(at < m.n_bytes ? at : m.n_bytes, m);
+    if (!ends) { out[i] = r; return; }
     if (r > n_ends) r = n_ends;
-    doc_tok[i] = r ? ends[r - 1] : 0ull;
-}
-
-// rank[i] = the end bits of the mask below text byte pos[i]: the index of the chunk that starts there (option "dedup":
-// the chunks of the singles and of the document boundaries)
-__global__ __launch_bounds__(256) void k_enc_pos_rank(const unsigned long long *__restrict__ pos, uint64_t n_pos,
-                                                      const uint32_t *__restrict__ mask, uint64_t n_bytes,
-                                                      const unsigned long long *__restrict__ block_off, uint64_t n_blocks,
-                                                      const unsigned long long *__restrict__ total,
-                                                      unsigned long long *__restrict__ rank) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_pos) return;
-    const uint64_t p = pos[i] < n_bytes ? pos[i] : n_bytes;
-    rank[i] = mask_rank(p, mask, block_off, n_blocks, total);
+    out[i] = r ? ends[r - 1] - tok_base : 0ull;
 }
 
 enum FinMode {
@@ -411,27 +401,13 @@ __global__ __launch_bounds__(kSpanThreads) void k_enc_finish(const uint32_t *__r
 // table mbpe_merges_check accepts), a chunk that is one token by rule for its whole chunk.  Per span a 64-bit byte
 // count, one scan workgroup, then a ranked write with a wave prefix sum.  The one-token chunks are PATCHES: the index
 // of single k in the final stream is the number of tokens before its first byte -- the rank of its start among the
-// mask's end bits, looked up in the finishing kernel's list of chunk ends, as k_enc_doc_tok does for documents.
+// mask's end bits, looked up in the finishing kernel's list of chunk ends, as for the documents (k_enc_mask_query).
 struct LenTab { const uint32_t *len; uint32_t n; };       // ids at or beyond n (they occur as singles only): 0
 struct LenPatch {                                         // token idx[k] of the piece covers sc[k].len bytes; ascending
     const unsigned long long *idx;
     const SingleChunk *sc;
     uint64_t n;
 };
-
-__global__ __launch_bounds__(256) void k_enc_single_tok(const SingleChunk *__restrict__ sc, uint64_t n_sc,
-                                                        const uint32_t *__restrict__ mask, uint64_t n_bytes,
-                                                        const unsigned long long *__restrict__ block_off,
-                                                        uint64_t n_blocks, const unsigned long long *__restrict__ total,
-                                                        const unsigned long long *__restrict__ ends, uint64_t n_ends,
-                                                        unsigned long long tok_base, unsigned long long *__restrict__ idx) {
-    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n_sc) return;
-    const uint64_t p = sc[k].start < n_bytes ? sc[k].start : n_bytes;
-    unsigned long long r = mask_rank(p, mask, block_off, n_blocks, total);
-    if (r > n_ends) r = n_ends;
-    idx[k] = r ? ends[r - 1] - tok_base : 0ull;
-}
 
 // the bytes of this lane's token in the group that starts at i0; *k = the first patch at or after i0 (the same in every
 // lane), moved past the group
@@ -648,7 +624,7 @@ int device_singles(mbpe_encoder *e, const uint8_t *d_text, const uint64_t *chunk
     return MBPE_OK;
 }
 
-// one encode request, as the C-ABI states it; an entry point fills it once (what it leaves out is 0 / NULL)
+// one encode request, as the C-ABI states it: text and chunks in braces, the other fields by name (left out: 0 / NULL)
 struct EncCall {
     const uint8_t *text;
     uint64_t n_bytes;
@@ -661,10 +637,11 @@ struct EncCall {
     int out_on_device;
     uint64_t *chunk_tok_off_out, *n_out;
     uint32_t *n_passes_out;
-    bool mask_on_device;         // the (single) piece's mask is on the device already
-    // mbpe_encoder_encode_endmask: one piece whose mask is the caller's; the token offsets of the documents are left
-    // in e->d_doc_off (and copied to doc_tok_off_out when that is given)
+    // the only piece's mask where it is on the device already (the caller's, or e->d_mask: gather_singles); NULL: every
+    // piece's is built from chunk_off and uploaded.  endmask (mbpe_encoder_encode_endmask): the chunks are that mask's,
+    // not chunk_off's; the documents' token offsets are left in e->d_doc_off (and copied to doc_tok_off_out when given)
     const uint8_t *mask_dev;
+    bool endmask;
     const mbpe_single *singles;
     uint64_t n_singles;
     const uint64_t *doc_off;
@@ -673,6 +650,17 @@ struct EncCall {
     // the _byteoff calls: cap + 1 byte offsets, where tokens_out lives (NULL: none are computed)
     uint64_t *tok_byte_off_out;
 };
+
+// where a call's ids go and in what width, and where it reports how many they are
+void enc_out(EncCall *a, void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device, uint64_t *n_out,
+             uint32_t *n_passes_out) {
+    a->tokens_out = tokens_out;
+    a->cap = cap;
+    a->token_bits = token_bits;
+    a->out_on_device = out_on_device;
+    a->n_out = n_out;
+    a->n_passes_out = n_passes_out;
+}
 
 // what the batch calls add: the documents as chunk ranges (the endmask call has them in EncCall) and the pack step
 struct EncPack {
@@ -689,15 +677,22 @@ struct EncPack {
     uint32_t token_bits() const { return spec->out_bits == 16 ? 16 : 32; }
 };
 
-// a piece on its way: pn bytes at d_text, then n tokens in tok[cur] after `passes` passes; too_small: the caller's
-// cap does not hold them and nothing was written
+// a piece on its way: pn bytes at d_text with their end mask at d_mask, then n tokens in tok[cur] after `passes` passes;
+// too_small: the caller's cap does not hold them and nothing was written
 struct PieceRun {
     uint64_t pn = 0, n = 0;
-    const uint8_t *d_text = nullptr;
+    const uint8_t *d_text = nullptr, *d_mask = nullptr;
     int cur = 0;
     uint32_t passes = 0;
     bool too_small = false;
 };
+
+// the count and the passes of a call that has run, and what a cap that did not hold the tokens gets
+int enc_report(const EncCall &a, const PieceRun &sum, bool too_small) {
+    *a.n_out = sum.n;
+    if (a.n_passes_out) *a.n_passes_out = sum.passes;
+    return too_small ? fail(MBPE_ERR_ARG, "tokens_out too small") : MBPE_OK;
+}
 
 // buffers for the piece [base, base + pn) and what the host has of it: text, mask, singles, document offsets
 int piece_upload(mbpe_encoder *e, const EncCall &a, Piece p, PieceRun *r) {
@@ -705,7 +700,7 @@ int piece_upload(mbpe_encoder *e, const EncCall &a, Piece p, PieceRun *r) {
     const uint64_t n_spans0 = span_count(pn);
     int rc = MBPE_OK;
     if (!a.text_on_device) rc = e->d_text.reserve(pn, e->mem);
-    if (rc == MBPE_OK && !a.mask_on_device) {
+    if (rc == MBPE_OK && !a.mask_dev) {
         build_mask(e, a.chunk_off, p);
         rc = e->d_mask.reserve(e->mask.size(), e->mem);
     }
@@ -746,7 +741,8 @@ int piece_upload(mbpe_encoder *e, const EncCall &a, Piece p, PieceRun *r) {
         ECHK(hipMemcpyAsync(e->d_text, a.text + base, pn, hipMemcpyHostToDevice, e->stream));
         r->d_text = e->d_text;
     }
-    if (!a.mask_on_device)
+    r->d_mask = a.mask_dev ? a.mask_dev : e->d_mask.get();
+    if (!a.mask_dev)
         ECHK(hipMemcpyAsync(e->d_mask, e->mask.data(), e->mask.size(), hipMemcpyHostToDevice, e->stream));
     if (!e->piece_singles.empty())
         ECHK(hipMemcpyAsync(e->d_singles, e->piece_singles.data(), e->piece_singles.size() * sizeof(SingleChunk),
@@ -762,17 +758,17 @@ int piece_upload(mbpe_encoder *e, const EncCall &a, Piece p, PieceRun *r) {
 }
 
 // ev0, bytes -> tokens, then passes until one changes nothing.  piece_base = the piece's first byte in the call's text
-int piece_passes(mbpe_encoder *e, const EncCall &a, uint64_t piece_base, PieceRun *r) {
+int piece_passes(mbpe_encoder *e, uint64_t piece_base, PieceRun *r) {
     const uint64_t pn = r->pn;
     const bool drop = e->drop_threshold != 0;
     ECHK(hipEventRecord(e->ev0, e->stream));
     const int wblocks = (int)std::min<uint64_t>((pn + 255) / 256, 8192);
     if (drop)
         hipLaunchKernelGGL(k_enc_widen<true>, dim3(wblocks), dim3(256), 0, e->stream, r->d_text, pn,
-                           a.mask_dev ? a.mask_dev : e->d_mask, e->tok[0], e->org[0]);
+                           r->d_mask, e->tok[0], e->org[0]);
     else
         hipLaunchKernelGGL(k_enc_widen<false>, dim3(wblocks), dim3(256), 0, e->stream, r->d_text, pn,
-                           a.mask_dev ? a.mask_dev : e->d_mask, e->tok[0], nullptr);
+                           r->d_mask, e->tok[0], nullptr);
     if (!e->piece_singles.empty())
         hipLaunchKernelGGL(k_enc_single, dim3((uint32_t)e->piece_singles.size()), dim3(64), 0, e->stream, e->d_singles,
                            (uint32_t)e->piece_singles.size(), e->tok[0]);
@@ -823,111 +819,127 @@ int piece_passes(mbpe_encoder *e, const EncCall &a, uint64_t piece_base, PieceRu
     return MBPE_OK;
 }
 
-// the finishing kernel: ids in the caller's format (into cand when they go to the host), chunk ends into tok[1 - cur];
-// ev1 and the kernel time; then what goes to the host: tokens, document offsets or the chunks' token offsets
+// ---- the launch sequences that the plain pieces and the "dedup" route share ---------------------------------------
+// the chunk ends of tok[0 .. n): the spans' counts in span_a, the ends before every span in span_off, all in d_res[0]
+void end_count_launch(mbpe_encoder *e, const uint32_t *tok, uint64_t n) {
+    hipLaunchKernelGGL(k_enc_end_count, dim3(span_grid(n)), dim3(kSpanThreads), 0, e->stream, tok, n, e->span_a);
+    hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, span_count(n), e->span_off,
+                       e->d_res);
+}
+
+// the finishing kernel in the form asked for (no tokens and no ends: nothing to launch).  with_ends: end_count_launch
+// has run on the same tokens; ends[0 .. ends_cap) gets tok_base + the position after every token that ends a chunk
+void finish_launch(mbpe_encoder *e, int mode, bool with_ends, const uint32_t *tok, uint64_t n, void *out,
+                   unsigned long long tok_base, unsigned long long *ends, uint64_t ends_cap) {
+    const dim3 grid(span_grid(n));
+    auto finish = [&](auto m) {
+        if (with_ends)
+            hipLaunchKernelGGL((k_enc_finish<m(), true>), grid, dim3(kSpanThreads), 0, e->stream, tok, n, out, e->span_off,
+                               tok_base, ends, ends_cap);
+        else if constexpr (m() != kFinNone)
+            hipLaunchKernelGGL((k_enc_finish<m(), false>), grid, dim3(kSpanThreads), 0, e->stream, tok, n, out, e->span_off,
+                               tok_base, ends, ends_cap);
+    };
+    switch (mode) {
+        case kFinFlags: finish(std::integral_constant<int, kFinFlags>()); break;
+        case kFinU32: finish(std::integral_constant<int, kFinU32>()); break;
+        case kFinU16: finish(std::integral_constant<int, kFinU16>()); break;
+        default: finish(std::integral_constant<int, kFinNone>()); break;
+    }
+}
+
+// the blocks of the mask of n_bytes text bytes, counted into cnt and linked into off (an entry per block each), for the
+// queries of mask_query_launch; the total goes to d_res[2]: d_res[0] may hold a count of chunk ends that is read later
+MaskView mask_count_launch(mbpe_encoder *e, const uint8_t *mask, uint64_t n_bytes, uint32_t *cnt,
+                           unsigned long long *off) {
+    const uint64_t n_words = (n_bytes + 31) / 32, n_blocks = (n_words + kMaskBlockWords - 1) / kMaskBlockWords;
+    const uint32_t *words = reinterpret_cast<const uint32_t *>(mask);
+    hipLaunchKernelGGL(k_enc_mask_count, dim3((uint32_t)((n_blocks * kWave + 255) / 256)), dim3(256), 0, e->stream, words,
+                       n_words, n_blocks, cnt);
+    hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, cnt, n_blocks, off, e->d_res + 2);
+    return {words, n_bytes, n_blocks, off, e->d_res + 2};
+}
+
+void mask_query_launch(mbpe_encoder *e, const MaskView &m, const unsigned long long *pos, uint32_t stride, uint64_t n_pos,
+                       const unsigned long long *ends, uint64_t n_ends, uint64_t tok_base, unsigned long long *out) {
+    hipLaunchKernelGGL(k_enc_mask_query, dim3((uint32_t)((n_pos + 255) / 256)), dim3(256), 0, e->stream, pos, stride, n_pos,
+                       m, ends, n_ends, tok_base, out);
+}
+
+// chunk_tok_off_out[c + 1] for the chunks [p.c0, p.c1): a chunk that is not empty takes the next of ends[0 .. n_ends),
+// an empty one repeats its predecessor's offset (`before`: the offset the first chunk starts at)
+void fill_chunk_tok_off(const EncCall &a, Piece p, uint64_t before, const unsigned long long *ends, uint64_t n_ends) {
+    uint64_t k = 0, last = before;
+    for (uint64_t c = p.c0; c < p.c1; ++c) {
+        if (a.chunk_off[c + 1] > a.chunk_off[c] && k < n_ends) last = ends[k++];
+        a.chunk_tok_off_out[c + 1] = last;
+    }
+}
+
+// the finishing stage: chunk ends (their list in tok[1 - cur] when it fits), ids in the caller's format (into cand when
+// they go to the host), document and byte offsets; ev1 and the kernel time; then what goes to the host
 int piece_finish(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, PieceRun *r) {
     const uint64_t n = r->n, pn = r->pn, tok_bytes = a.token_bits / 8;
-    const int cur = r->cur;
+    const uint32_t *tok = e->tok[r->cur];
+    DevBuf<uint32_t> &idle = e->tok[1 - r->cur];          // the other token array: room for the list of chunk ends
     r->too_small = a.tokens_out && a.cap < done + n;
     const bool with_docs = a.doc_off && !r->too_small;
     const bool with_boff = a.tok_byte_off_out && a.tokens_out && !r->too_small && n;
     // (the one-token chunks of the piece: each needs its index in the final stream, which the chunk ends give)
     const uint64_t n_patch = with_boff ? e->piece_singles.size() : 0;
-    const bool mask_ends = a.mask_dev != nullptr;         // the chunks are the caller's mask's: counted on the device
     const bool with_ends = (a.chunk_tok_off_out || a.doc_off || n_patch) && !r->too_small;
     const bool with_tokens = a.tokens_out && !r->too_small;
     int rc = MBPE_OK;
     if (with_boff && !a.out_on_device && (rc = e->d_boff.reserve((n + 1) * 8, e->mem)) != MBPE_OK) return rc;
     uint64_t n_ends = 0;
     unsigned long long *d_ends = nullptr;
-    if (n && (with_ends || with_tokens)) {
-        const uint64_t n_spans = span_count(n);
-        const dim3 grid(span_grid(n));
-        if (with_ends) {
-            if (mask_ends) {
-                // the chunks are the mask's: their number comes from the device, ahead of the finishing kernel
-                hipLaunchKernelGGL(k_enc_end_count, grid, dim3(kSpanThreads), 0, e->stream, e->tok[cur], n, e->span_a);
-                hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans,
-                                   e->span_off, e->d_res);
-                unsigned long long found = 0;
-                ECHK(hipMemcpyAsync(&found, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
-                ECHK(hipStreamSynchronize(e->stream));
-                n_ends = found;
-            } else {
-                for (uint64_t c = p.c0; c < p.c1; ++c) n_ends += a.chunk_off[c + 1] > a.chunk_off[c];
-            }
-            if (n_ends * 8 <= e->tok[1 - cur].bytes()) {
-                d_ends = reinterpret_cast<unsigned long long *>(e->tok[1 - cur].get());
-            } else {
-                rc = e->d_ends.reserve(n_ends * 8, e->mem);
-                if (rc != MBPE_OK) return rc;
-                d_ends = e->d_ends;
-            }
-            if (!mask_ends) {
-                hipLaunchKernelGGL(k_enc_end_count, grid, dim3(kSpanThreads), 0, e->stream, e->tok[cur], n, e->span_a);
-                hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans,
-                                   e->span_off, e->d_res);
-            }
+    if (n && with_ends) {
+        end_count_launch(e, tok, n);
+        if (a.endmask) {                                  // the chunks are the mask's: their number comes from the device
+            unsigned long long found = 0;
+            ECHK(hipMemcpyAsync(&found, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
+            ECHK(hipStreamSynchronize(e->stream));
+            n_ends = found;
+        } else {
+            for (uint64_t c = p.c0; c < p.c1; ++c) n_ends += a.chunk_off[c + 1] > a.chunk_off[c];
         }
+        d_ends = reinterpret_cast<unsigned long long *>(idle.get());
+        if (n_ends * 8 > idle.bytes()) {                  // (chunks shorter than two bytes on average)
+            if ((rc = e->d_ends.reserve(n_ends * 8, e->mem)) != MBPE_OK) return rc;
+            d_ends = e->d_ends;
+        }
+    }
+    if (n && (with_ends || with_tokens)) {
         void *out = !with_tokens ? nullptr
                     : a.out_on_device ? static_cast<uint8_t *>(a.tokens_out) + done * tok_bytes
                                       : reinterpret_cast<uint8_t *>(e->cand.get());
         const int mode = !with_tokens ? kFinNone : a.token_bits == 16 ? kFinU16 : a.out_on_device ? kFinFlags : kFinU32;
-        auto finish = [&](auto m) {
-            if (with_ends)
-                hipLaunchKernelGGL((k_enc_finish<m(), true>), grid, dim3(kSpanThreads), 0, e->stream, e->tok[cur], n, out,
-                                   e->span_off, done, d_ends, n_ends);
-            else if constexpr (m() != kFinNone)         // (no tokens and no ends: nothing to launch)
-                hipLaunchKernelGGL((k_enc_finish<m(), false>), grid, dim3(kSpanThreads), 0, e->stream, e->tok[cur], n, out,
-                                   e->span_off, done, d_ends, n_ends);
-        };
-        switch (mode) {
-            case kFinFlags: finish(std::integral_constant<int, kFinFlags>()); break;
-            case kFinU32: finish(std::integral_constant<int, kFinU32>()); break;
-            case kFinU16: finish(std::integral_constant<int, kFinU16>()); break;
-            default: finish(std::integral_constant<int, kFinNone>()); break;
-        }
-        if (with_docs) {
-            // the rank of every document offset in the mask, then the look-up in the chunk ends (span_a and span_off
-            // are free again: the finishing kernel is ahead on the stream)
-            const uint64_t n_words = (pn + 31) / 32, n_blocks = (n_words + kMaskBlockWords - 1) / kMaskBlockWords;
-            const uint32_t *mask32 = reinterpret_cast<const uint32_t *>(a.mask_dev);
-            hipLaunchKernelGGL(k_enc_mask_count, dim3((uint32_t)((n_blocks * kWave + 255) / 256)), dim3(256), 0, e->stream,
-                               mask32, n_words, n_blocks, e->span_a);
-            hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_blocks, e->span_off,
-                               e->d_res);
-            hipLaunchKernelGGL(k_enc_doc_tok, dim3((uint32_t)((a.n_docs + 1 + 255) / 256)), dim3(256), 0, e->stream,
-                               e->d_doc_pos, a.n_docs + 1, mask32, pn, e->span_off, n_blocks, e->d_res, d_ends, n_ends,
-                               e->d_doc_off);
-        }
-        if (with_boff) {
-            const LenTab tab = {e->d_tok_len, (uint32_t)e->len.size()};
-            const LenPatch pt = {e->d_single_tok, e->d_singles, n_patch};
-            if (n_patch) {
-                // the rank of every single's start in the mask (its total apart from the ends': d_res[2]), then the
-                // look-up in the chunk ends; span_a and span_off are free again, as above
-                const uint64_t n_words = (pn + 31) / 32, n_blocks = (n_words + kMaskBlockWords - 1) / kMaskBlockWords;
-                const uint32_t *mask32 = reinterpret_cast<const uint32_t *>(mask_ends ? a.mask_dev : e->d_mask.get());
-                hipLaunchKernelGGL(k_enc_mask_count, dim3((uint32_t)((n_blocks * kWave + 255) / 256)), dim3(256), 0,
-                                   e->stream, mask32, n_words, n_blocks, e->span_a);
-                hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_blocks,
-                                   e->span_off, e->d_res + 2);
-                hipLaunchKernelGGL(k_enc_single_tok, dim3((uint32_t)((n_patch + 255) / 256)), dim3(256), 0, e->stream,
-                                   e->d_singles, n_patch, mask32, pn, e->span_off, n_blocks, e->d_res + 2, d_ends, n_ends,
-                                   done, e->d_single_tok);
-            }
-            unsigned long long *boff = a.out_on_device ? reinterpret_cast<unsigned long long *>(a.tok_byte_off_out) + done
-                                                       : e->d_boff.get();
-            hipLaunchKernelGGL(k_enc_len_sum, grid, dim3(kSpanThreads), 0, e->stream, e->tok[cur], n, tab, pt,
-                               e->span_bytes);
-            hipLaunchKernelGGL(k_enc_scan_sum64, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_bytes, n_spans);
-            hipLaunchKernelGGL(k_enc_len_write, grid, dim3(kSpanThreads), 0, e->stream, e->tok[cur], n, tab, pt,
-                               e->span_bytes, a.chunk_off[p.c0], boff);
-        }
+        finish_launch(e, mode, with_ends, tok, n, out, done, d_ends, n_ends);
+    }
+    if (n && (with_docs || n_patch)) {
+        // the rank of every document offset and of every single's start in the mask, then the look-up in the chunk
+        // ends (span_a and span_off are free again: the finishing kernel is ahead on the stream)
+        const MaskView m = mask_count_launch(e, r->d_mask, pn, e->span_a, e->span_off);
+        if (with_docs)
+            mask_query_launch(e, m, e->d_doc_pos, 1, a.n_docs + 1, d_ends, n_ends, done, e->d_doc_off);
+        if (n_patch)                                      // (a SingleChunk begins with its start)
+            mask_query_launch(e, m, &e->d_singles.get()->start, sizeof(SingleChunk) / 8, n_patch, d_ends, n_ends, done,
+                              e->d_single_tok);
+    }
+    if (with_boff) {
+        const LenTab tab = {e->d_tok_len, (uint32_t)e->len.size()};
+        const LenPatch pt = {e->d_single_tok, e->d_singles, n_patch};
+        unsigned long long *boff = a.out_on_device ? reinterpret_cast<unsigned long long *>(a.tok_byte_off_out) + done
+                                                   : e->d_boff.get();
+        const dim3 grid(span_grid(n));
+        hipLaunchKernelGGL(k_enc_len_sum, grid, dim3(kSpanThreads), 0, e->stream, tok, n, tab, pt, e->span_bytes);
+        hipLaunchKernelGGL(k_enc_scan_sum64, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_bytes, span_count(n));
+        hipLaunchKernelGGL(k_enc_len_write, grid, dim3(kSpanThreads), 0, e->stream, tok, n, tab, pt, e->span_bytes,
+                           a.chunk_off[p.c0], boff);
     }
     ECHK(hipEventRecord(e->ev1, e->stream));
     unsigned long long ends_found = 0;
-    if (with_ends && !mask_ends && n) ECHK(hipMemcpyAsync(&ends_found, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
+    if (with_ends && !a.endmask && n) ECHK(hipMemcpyAsync(&ends_found, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
     float ms = 0.f;
     if ((rc = e->wait(&ms)) != MBPE_OK) return rc;
     e->last_ms += ms;
@@ -945,7 +957,7 @@ int piece_finish(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, Piec
             ECHK(hipMemcpyAsync(a.doc_tok_off_out, e->d_doc_off, (a.n_docs + 1) * 8, hipMemcpyDeviceToHost, e->stream));
             ECHK(hipStreamSynchronize(e->stream));
         }
-    } else if (with_ends && !mask_ends) {
+    } else if (with_ends && !a.endmask) {
         if (ends_found != n_ends) return fail(MBPE_ERR_HIP, "mbpe_encoder_encode: chunk ends and chunks differ in number");
         if (!a.chunk_tok_off_out) return MBPE_OK;          // (the ends served the byte offsets of one-token chunks only)
         e->list.resize(n_ends);
@@ -953,11 +965,7 @@ int piece_finish(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, Piec
             ECHK(hipMemcpyAsync(e->list.data(), d_ends, n_ends * 8, hipMemcpyDeviceToHost, e->stream));
             ECHK(hipStreamSynchronize(e->stream));
         }
-        uint64_t k = 0, last = done;
-        for (uint64_t c = p.c0; c < p.c1; ++c) {   // an empty chunk repeats its predecessor's offset
-            if (a.chunk_off[c + 1] > a.chunk_off[c]) last = e->list[k++];
-            a.chunk_tok_off_out[c + 1] = last;
-        }
+        fill_chunk_tok_off(a, p, done, e->list.data(), n_ends);
     }
     return MBPE_OK;
 }
@@ -967,12 +975,11 @@ int run_piece(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, PieceRu
     *r = PieceRun{};
     r->pn = a.chunk_off[p.c1] - a.chunk_off[p.c0];
     if (r->pn == 0) {
-        if (a.chunk_tok_off_out)
-            for (uint64_t c = p.c0; c < p.c1; ++c) a.chunk_tok_off_out[c + 1] = done;
+        if (a.chunk_tok_off_out) fill_chunk_tok_off(a, p, done, nullptr, 0);
         return MBPE_OK;
     }
     int rc = piece_upload(e, a, p, r);
-    if (rc == MBPE_OK) rc = piece_passes(e, a, a.chunk_off[p.c0], r);
+    if (rc == MBPE_OK) rc = piece_passes(e, a.chunk_off[p.c0], r);
     if (rc == MBPE_OK) rc = piece_finish(e, a, p, done, r);
     return rc;
 }
@@ -1075,36 +1082,62 @@ void dedup_nothing(mbpe_encoder *e) {
     e->dd_expand_ms = 0.f;
 }
 
-// a.mask_dev: the endmask calls (text, mask, singles, doc_off as they state them); else chunk_off, checked, n_bytes > 0
-int enc_dedup_body(mbpe_encoder *e, const EncCall &a) {
-    const bool endmask = a.mask_dev != nullptr;
-    const uint64_t n_bytes = a.n_bytes, esz = a.token_bits / 8;
-    const std::string who = endmask ? "mbpe_encoder_encode_endmask" : "mbpe_encoder_encode";
+// checks of more than one entry point: chunk_off (absent: one chunk, in `one`, which lives as long as the request) ...
+int chunk_off_check(EncCall *a, uint64_t one[2]) {
+    if (!a->chunk_off) { one[0] = 0; one[1] = a->n_bytes; a->chunk_off = one; a->n_chunks = 1; }
+    if (a->chunk_off[0] != 0 || a->chunk_off[a->n_chunks] != a->n_bytes)
+        return fail(MBPE_ERR_ARG, "chunk_off must start at 0 and end at n_bytes");
+    // (every offset is checked before one is used: one beyond n_bytes would index the mask and the text)
+    for (uint64_t c = 0; c < a->n_chunks; ++c)
+        if (a->chunk_off[c + 1] < a->chunk_off[c]) return fail(MBPE_ERR_ARG, "chunk_off must be ascending");
+    return MBPE_OK;
+}
+
+// ... and 16-bit ids for a table that has more (word: what the call names the width, "token_bits" or "out_bits")
+int vocab16_check(const mbpe_encoder *e, uint32_t bits, const char *word) {
+    if (bits != 16 || 256ull + e->n_merges <= 65536ull) return MBPE_OK;
+    return fail(MBPE_ERR_VOCAB, std::string(word) + " 16 with more than 65,536 token ids");
+}
+
+// the one-token chunks of the whole text, before any pass runs -> e->singles, sorted by start: the caller's list, a
+// host text's NUL-led chunks, or a device text's piece by piece (one piece: its mask is then on the device, a->mask_dev)
+int gather_singles(mbpe_encoder *e, EncCall *a, const Piece *pieces, size_t n_pieces) {
     int rc = MBPE_OK;
-    if (a.tokens_out && a.out_on_device && ((uintptr_t)a.tokens_out & (esz - 1)))
-        return fail(MBPE_ERR_ARG, who + ": tokens_out must be aligned to its elements (option \"dedup\")");
-    ECHK(hipSetDevice(e->device));
-    e->dd_ran = false;
-    // the chunks that are one token, before anything else (a host text: before the device is touched)
     e->singles.clear();
-    if (endmask) {
-        for (uint64_t k = 0; k < a.n_singles; ++k)
-            e->singles.push_back({a.singles[k].start, a.singles[k].len, a.singles[k].id, 0});
-    } else if (!a.text_on_device) {
-        for (uint64_t c = 0; c < a.n_chunks; ++c) {
-            const uint64_t s = a.chunk_off[c], t = a.chunk_off[c + 1];
+    if (a->endmask) {
+        for (uint64_t k = 0; k < a->n_singles; ++k)
+            e->singles.push_back({a->singles[k].start, a->singles[k].len, a->singles[k].id, 0});
+    } else if (!a->text_on_device) {
+        for (uint64_t c = 0; c < a->n_chunks; ++c) {
+            const uint64_t s = a->chunk_off[c], t = a->chunk_off[c + 1];
             long long id;
-            if (t > s && a.text[s] == 0 && stoi_value(a.text + s + 1, t - s - 1, &id))
-                if ((rc = add_single(e, s, t - s, id, a.token_bits)) != MBPE_OK) return rc;
+            if (t > s && a->text[s] == 0 && stoi_value(a->text + s + 1, t - s - 1, &id))
+                if ((rc = add_single(e, s, t - s, id, a->token_bits)) != MBPE_OK) return rc;
         }
     } else {
-        if ((rc = device_singles(e, a.text, a.chunk_off, Piece{0, a.n_chunks}, a.token_bits)) != MBPE_OK) return rc;
+        for (size_t i = 0; i < n_pieces; ++i)
+            if ((rc = device_singles(e, a->text, a->chunk_off, pieces[i], a->token_bits)) != MBPE_OK) return rc;
+        if (n_pieces == 1) a->mask_dev = e->d_mask;
     }
-    e->dd_singles.swap(e->singles);               // (the unique text is encoded without any: piece_upload reads e->singles)
-    e->singles.clear();
-    const uint64_t n_sg = e->dd_singles.size();
+    return MBPE_OK;
+}
 
-    // the deduper: created by the first call that needs it; its stream starts where the encoder's has finished
+// the "dedup" route on its way: nu unique chunks of nub bytes, n_kept chunks (uof: the unique chunk of each), n_sg
+// singles, the unique text's piece, and on the device the chunks of the positions asked for (q_chunk: dedup_queries)
+struct DedupRun {
+    std::string who;
+    uint64_t nu = 0, nub = 0, n_kept = 0, n_sg = 0, n_docq = 0;
+    const uint8_t *u_text = nullptr, *u_mask = nullptr;
+    uint32_t *uof = nullptr;
+    int mode = kFinU32;                           // the table's format: the caller's
+    PieceRun r;
+    unsigned long long *q_chunk = nullptr;
+    uint64_t n_entries() const { return nu + n_sg + 1; }      // the unique chunks, the singles, the empty run
+};
+
+// stage 1, the deduper: created by the first call that needs it; its stream starts where the encoder's has finished
+int dedup_unique(mbpe_encoder *e, const EncCall &a, DedupRun *d) {
+    int rc = MBPE_OK;
     if (!e->dd) {
         if ((rc = mbpe_dedup_create(e->device, &e->dd)) != MBPE_OK) return rc;
         if ((rc = mbpe_dedup_set_option(e->dd, "map", 1)) != MBPE_OK) return rc;
@@ -1113,132 +1146,122 @@ int enc_dedup_body(mbpe_encoder *e, const EncCall &a) {
                                     e->dedup_max_chunk >= 0 ? e->dedup_max_chunk : (int64_t)kDedupMaxChunkBytes)) != MBPE_OK)
         return rc;
     const uint8_t *text = a.text;
+    const uint64_t n_bytes = a.n_bytes;
     if (a.text_on_device && ((uintptr_t)a.text & 15)) {        // the deduper reads 16 aligned bytes at a time
         if ((rc = e->d_text.reserve(n_bytes, e->mem)) != MBPE_OK) return rc;
         ECHK(hipMemcpyAsync(e->d_text, a.text, n_bytes, hipMemcpyDeviceToDevice, e->stream));
         text = e->d_text;
     }
     ECHK(hipStreamSynchronize(e->stream));
-    uint64_t nu = 0, nub = 0, n_kept = 0;
-    rc = endmask ? mbpe_dedup_chunks_endmask(e->dd, text, n_bytes, a.mask_dev, &nu, &nub)
-                 : mbpe_dedup_chunks(e->dd, text, n_bytes, a.text_on_device, a.chunk_off, a.n_chunks, &nu, &nub);
+    rc = a.endmask ? mbpe_dedup_chunks_endmask(e->dd, text, n_bytes, a.mask_dev, &d->nu, &d->nub)
+                   : mbpe_dedup_chunks(e->dd, text, n_bytes, a.text_on_device, a.chunk_off, a.n_chunks, &d->nu, &d->nub);
     if (rc != MBPE_OK) return rc;
-    const uint8_t *u_text = nullptr, *u_mask = nullptr;
     const uint32_t *uof_view = nullptr;
     float dd_ms = 0.f;
-    if ((rc = mbpe_dedup_result(e->dd, &u_text, &u_mask, nullptr, nullptr)) != MBPE_OK) return rc;
-    if ((rc = mbpe_dedup_map(e->dd, &uof_view, &n_kept)) != MBPE_OK) return rc;
+    if ((rc = mbpe_dedup_result(e->dd, &d->u_text, &d->u_mask, nullptr, nullptr)) != MBPE_OK) return rc;
+    if ((rc = mbpe_dedup_map(e->dd, &uof_view, &d->n_kept)) != MBPE_OK) return rc;
     if ((rc = mbpe_dedup_kernel_ms(e->dd, &dd_ms)) != MBPE_OK) return rc;
-    uint32_t *uof = const_cast<uint32_t *>(uof_view);           // (the singles' chunks are patched in place)
+    d->uof = const_cast<uint32_t *>(uof_view);                  // (the singles' chunks are patched in place)
     e->last_ms += dd_ms;
-    const uint64_t n_entries = nu + n_sg + 1;                   // the unique chunks, the singles, the empty run
-    if (n_entries >= 0xFFFFFFFFull) return fail(MBPE_ERR_ARG, who + ": 2^32 - 1 table runs or more (option \"dedup\")");
+    if (d->n_entries() >= 0xFFFFFFFFull)
+        return fail(MBPE_ERR_ARG, d->who + ": 2^32 - 1 table runs or more (option \"dedup\")");
+    return MBPE_OK;
+}
 
-    // the unique text through the passes, as one piece
-    PieceRun r;
-    r.pn = nub;
+// stage 2: the unique text through the passes as one piece without any single (e->singles is empty), then the finishing
+// kernel writes the table, d_utab, in the caller's format and the runs' ends, d_uends
+int dedup_table(mbpe_encoder *e, const EncCall &a, DedupRun *d) {
+    const uint64_t nub = d->nub, esz = a.token_bits / 8;
+    int rc = MBPE_OK;
+    d->r.pn = nub;
     uint64_t limit = 0;
     if ((rc = piece_limit(e, nub, false, &limit)) != MBPE_OK) return rc;
     if (nub > limit)
-        return fail(MBPE_ERR_OOM, who + ": the unique chunks hold " + std::to_string(nub) +
+        return fail(MBPE_ERR_OOM, d->who + ": the unique chunks hold " + std::to_string(nub) +
                                       " bytes, more than one piece may hold (" + std::to_string(limit) +
                                       "; option \"piece_bytes\"), and the \"dedup\" route runs them as one piece");
     const uint64_t one[2] = {0, nub};
-    EncCall u = {};
-    u.text = u_text;
-    u.n_bytes = nub;
-    u.text_on_device = 1;
-    u.chunk_off = one;
-    u.n_chunks = 1;
+    EncCall u = {d->u_text, nub, 1, one, 1};
     u.token_bits = a.token_bits;
-    u.mask_on_device = true;
-    u.mask_dev = u_mask;
-    const int mode = a.token_bits == 16 ? kFinU16 : a.out_on_device ? kFinFlags : kFinU32;
+    u.mask_dev = d->u_mask;
     if (nub) {
-        if ((rc = piece_upload(e, u, Piece{0, 1}, &r)) != MBPE_OK) return rc;
-        if ((rc = piece_passes(e, u, 0, &r)) != MBPE_OK) return rc;
+        if ((rc = piece_upload(e, u, Piece{0, 1}, &d->r)) != MBPE_OK) return rc;
+        if ((rc = piece_passes(e, 0, &d->r)) != MBPE_OK) return rc;
     }
-    const uint64_t n = r.n;
-    if ((rc = e->d_utab.reserve((n + n_sg + 8) * esz, e->mem)) != MBPE_OK) return rc;
-    if ((rc = e->d_uends.reserve(n_entries * 8, e->mem)) != MBPE_OK) return rc;
-    if (n) {
-        const uint64_t n_spans = span_count(n);
-        const dim3 grid(span_grid(n));
-        hipLaunchKernelGGL(k_enc_end_count, grid, dim3(kSpanThreads), 0, e->stream, e->tok[r.cur], n, e->span_a);
-        hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->span_a, n_spans, e->span_off,
-                           e->d_res);
-        auto finish = [&](auto m) {
-            hipLaunchKernelGGL((k_enc_finish<m(), true>), grid, dim3(kSpanThreads), 0, e->stream, e->tok[r.cur], n,
-                               static_cast<void *>(e->d_utab.get()), e->span_off, 0ull, e->d_uends.get(), nu);
-        };
-        switch (mode) {
-            case kFinFlags: finish(std::integral_constant<int, kFinFlags>()); break;
-            case kFinU32: finish(std::integral_constant<int, kFinU32>()); break;
-            default: finish(std::integral_constant<int, kFinU16>()); break;
-        }
-        ECHK(hipEventRecord(e->ev1, e->stream));
-        unsigned long long found = 0;
-        ECHK(hipMemcpyAsync(&found, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
-        float ms = 0.f;
-        if ((rc = e->wait(&ms)) != MBPE_OK) return rc;
-        e->last_ms += ms;
-        if (found != nu) return fail(MBPE_ERR_HIP, who + ": the unique chunks and their token runs differ in number");
-    } else if (nu) {
-        return fail(MBPE_ERR_HIP, who + ": the unique chunks left no token");
-    }
+    const uint64_t n = d->r.n;
+    if ((rc = e->d_utab.reserve((n + d->n_sg + 8) * esz, e->mem)) != MBPE_OK) return rc;
+    if ((rc = e->d_uends.reserve(d->n_entries() * 8, e->mem)) != MBPE_OK) return rc;
+    if (n == 0) return d->nu ? fail(MBPE_ERR_HIP, d->who + ": the unique chunks left no token") : MBPE_OK;
+    end_count_launch(e, e->tok[d->r.cur], n);
+    finish_launch(e, d->mode, true, e->tok[d->r.cur], n, e->d_utab.get(), 0, e->d_uends, d->nu);
+    ECHK(hipEventRecord(e->ev1, e->stream));
+    unsigned long long found = 0;
+    ECHK(hipMemcpyAsync(&found, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
+    float ms = 0.f;
+    if ((rc = e->wait(&ms)) != MBPE_OK) return rc;
+    e->last_ms += ms;
+    if (found != d->nu) return fail(MBPE_ERR_HIP, d->who + ": the unique chunks and their token runs differ in number");
+    return MBPE_OK;
+}
 
-    // whose chunk is asked for: the singles' first and last bytes' (2 n_sg) and, from the endmask calls, the documents'
-    const uint64_t n_docq = endmask && a.doc_off ? a.n_docs + 1 : 0, n_q = 2 * n_sg + n_docq;
+// stage 3, whose chunk is asked for: the singles' first and last bytes' (2 n_sg) and, from the endmask calls, the
+// documents'.  chunk_off says it on the host; a mask is asked on the device.  Records ev0: the expansion follows
+int dedup_queries(mbpe_encoder *e, const EncCall &a, DedupRun *d) {
+    d->n_docq = a.endmask && a.doc_off ? a.n_docs + 1 : 0;
+    const uint64_t n_sg = d->n_sg, n_docq = d->n_docq, n_q = 2 * n_sg + n_docq;
+    int rc = MBPE_OK;
     e->sg_tok.resize(n_sg);
     e->q_pos.assign(n_q, 0);
-    for (uint64_t k = 0; k < n_sg; ++k) e->sg_tok[k] = e->dd_singles[k].id | (mode == kFinFlags ? kTokEnd : 0u);
-    if (endmask) {
+    for (uint64_t k = 0; k < n_sg; ++k) e->sg_tok[k] = e->dd_singles[k].id | (d->mode == kFinFlags ? kTokEnd : 0u);
+    if (a.endmask) {
         for (uint64_t k = 0; k < n_sg; ++k) {
             e->q_pos[k] = e->dd_singles[k].start;
             e->q_pos[n_sg + k] = e->dd_singles[k].start + e->dd_singles[k].len;
         }
         for (uint64_t i = 0; i < n_docq; ++i) e->q_pos[2 * n_sg + i] = a.doc_off[i];
     } else {
-        // chunk_off says it: a single is one chunk, and its index counts the chunks that are not empty
+        // a single is one chunk, and its index counts the chunks that are not empty
         uint64_t kept = 0, k = 0;
         for (uint64_t c = 0; c < a.n_chunks && k < n_sg; ++c) {
             if (a.chunk_off[c + 1] == a.chunk_off[c]) continue;
             if (a.chunk_off[c] == e->dd_singles[k].start) { e->q_pos[k] = kept; e->q_pos[n_sg + k] = kept + 1; ++k; }
             ++kept;
         }
-        if (k != n_sg) return fail(MBPE_ERR_HIP, who + ": a one-token chunk is not among the chunks");
+        if (k != n_sg) return fail(MBPE_ERR_HIP, d->who + ": a one-token chunk is not among the chunks");
     }
-    const uint64_t n_spans_x = expand_span_count(n_kept);
-    if ((rc = e->d_exp_off.reserve((n_spans_x + 1) * 8, e->mem)) != MBPE_OK) return rc;
+    if ((rc = e->d_exp_off.reserve((expand_span_count(d->n_kept) + 1) * 8, e->mem)) != MBPE_OK) return rc;
     if (n_q) {
         if ((rc = e->d_q_pos.reserve(n_q * 8, e->mem)) != MBPE_OK) return rc;
         if ((rc = e->d_q_chunk.reserve(n_q * 8, e->mem)) != MBPE_OK) return rc;
         if (n_sg && (rc = e->d_sg_tok.reserve(n_sg * 4, e->mem)) != MBPE_OK) return rc;
     }
     if (n_docq && (rc = e->d_doc_off.reserve(n_docq * 8, e->mem)) != MBPE_OK) return rc;
-    const uint64_t n_words = (n_bytes + 31) / 32, n_blocks = (n_words + kMaskBlockWords - 1) / kMaskBlockWords;
-    if (endmask && n_q) {
+    // (the mask spans the whole text while span_a and span_off are sized for the unique text: buffers of its own)
+    const uint64_t n_blocks = ((a.n_bytes + 31) / 32 + kMaskBlockWords - 1) / kMaskBlockWords;
+    if (a.endmask && n_q) {
         if ((rc = e->d_mblk_cnt.reserve(n_blocks * 4, e->mem)) != MBPE_OK) return rc;
         if ((rc = e->d_mblk_off.reserve(n_blocks * 8, e->mem)) != MBPE_OK) return rc;
     }
     ECHK(hipEventRecord(e->ev0, e->stream));
-    unsigned long long *q_chunk = endmask ? e->d_q_chunk.get() : e->d_q_pos.get();
-    if (n_q) {
-        ECHK(hipMemcpyAsync(e->d_q_pos, e->q_pos.data(), n_q * 8, hipMemcpyHostToDevice, e->stream));
-        if (n_sg) ECHK(hipMemcpyAsync(e->d_sg_tok, e->sg_tok.data(), n_sg * 4, hipMemcpyHostToDevice, e->stream));
-        if (endmask) {
-            const uint32_t *mask32 = reinterpret_cast<const uint32_t *>(a.mask_dev);
-            hipLaunchKernelGGL(k_enc_mask_count, dim3((uint32_t)((n_blocks * kWave + 255) / 256)), dim3(256), 0, e->stream,
-                               mask32, n_words, n_blocks, e->d_mblk_cnt.get());
-            hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->d_mblk_cnt.get(), n_blocks,
-                               e->d_mblk_off.get(), e->d_res + 2);
-            hipLaunchKernelGGL(k_enc_pos_rank, dim3((uint32_t)((n_q + 255) / 256)), dim3(256), 0, e->stream, e->d_q_pos.get(),
-                               n_q, mask32, n_bytes, e->d_mblk_off.get(), n_blocks, e->d_res + 2, e->d_q_chunk.get());
-        }
+    d->q_chunk = a.endmask ? e->d_q_chunk.get() : e->d_q_pos.get();
+    if (n_q == 0) return MBPE_OK;
+    ECHK(hipMemcpyAsync(e->d_q_pos, e->q_pos.data(), n_q * 8, hipMemcpyHostToDevice, e->stream));
+    if (n_sg) ECHK(hipMemcpyAsync(e->d_sg_tok, e->sg_tok.data(), n_sg * 4, hipMemcpyHostToDevice, e->stream));
+    if (a.endmask) {
+        const MaskView m = mask_count_launch(e, a.mask_dev, a.n_bytes, e->d_mblk_cnt, e->d_mblk_off);
+        mask_query_launch(e, m, e->d_q_pos, 1, n_q, nullptr, 0, 0, e->d_q_chunk);
     }
-    expand_patch_launch(e->stream, e->d_utab.get(), n, a.token_bits, e->d_uends, nu, uof, n_kept,
-                        ExpandSingles{e->d_sg_tok, q_chunk, q_chunk + n_sg, n_sg});
-    const ExpandSrc src = {e->d_utab.get(), n + n_sg, e->d_uends, n_entries, uof, n_kept, a.token_bits};
+    return MBPE_OK;
+}
+
+// stage 4: the singles become runs of the table, the expansion is counted (nothing is written before the cap is known
+// to hold it), written, and what the host asked for is copied to it
+int dedup_expand(mbpe_encoder *e, const EncCall &a, const DedupRun &d) {
+    const uint64_t n = d.r.n, n_sg = d.n_sg, n_kept = d.n_kept, n_docq = d.n_docq, esz = a.token_bits / 8;
+    int rc = MBPE_OK;
+    expand_patch_launch(e->stream, e->d_utab.get(), n, a.token_bits, e->d_uends, d.nu, d.uof, n_kept,
+                        ExpandSingles{e->d_sg_tok, d.q_chunk, d.q_chunk + n_sg, n_sg});
+    const ExpandSrc src = {e->d_utab.get(), n + n_sg, e->d_uends, d.n_entries(), d.uof, n_kept, a.token_bits};
     expand_count_launch(e->stream, src, e->d_exp_off, e->d_res);
     ECHK(hipEventRecord(e->ev1, e->stream));
     unsigned long long total = 0;
@@ -1248,13 +1271,13 @@ int enc_dedup_body(mbpe_encoder *e, const EncCall &a) {
 
     e->dd_ran = true;
     e->dd_chunks = n_kept;
-    e->dd_unique = nu;
-    e->dd_unique_bytes = nub;
+    e->dd_unique = d.nu;
+    e->dd_unique_bytes = d.nub;
     e->dd_unique_tokens = n;
     e->dd_expand_ms = ms_count;
     e->last_ms += ms_count;
     *a.n_out = total;
-    if (a.n_passes_out) *a.n_passes_out = r.passes;
+    if (a.n_passes_out) *a.n_passes_out = d.r.passes;
     // nothing has been written yet: an output that is too small stays as it was
     if (a.tokens_out && a.cap < total) return fail(MBPE_ERR_ARG, "tokens_out too small");
 
@@ -1267,7 +1290,7 @@ int enc_dedup_body(mbpe_encoder *e, const EncCall &a) {
     if ((out && total) || want_ends)
         expand_write_launch(e->stream, src, e->d_exp_off, out, want_ends ? e->d_exp_ends.get() : nullptr, 0);
     if (n_docq)
-        expand_before_launch(e->stream, src, e->d_exp_off, q_chunk + 2 * n_sg, n_docq, e->d_doc_off);
+        expand_before_launch(e->stream, src, e->d_exp_off, d.q_chunk + 2 * n_sg, n_docq, e->d_doc_off);
     if ((rc = e->finish(&ms_write)) != MBPE_OK) return rc;
     e->dd_expand_ms += ms_write;
     e->last_ms += ms_write;
@@ -1280,34 +1303,43 @@ int enc_dedup_body(mbpe_encoder *e, const EncCall &a) {
         if (n_kept) ECHK(hipMemcpyAsync(e->list.data(), e->d_exp_ends, n_kept * 8, hipMemcpyDeviceToHost, e->stream));
     }
     ECHK(hipStreamSynchronize(e->stream));
-    if (want_ends) {
-        uint64_t k = 0, last = 0;
-        a.chunk_tok_off_out[0] = 0;
-        for (uint64_t c = 0; c < a.n_chunks; ++c) {    // an empty chunk repeats its predecessor's offset
-            if (a.chunk_off[c + 1] > a.chunk_off[c] && k < n_kept) last = e->list[k++];
-            a.chunk_tok_off_out[c + 1] = last;
-        }
-    }
+    if (want_ends) fill_chunk_tok_off(a, Piece{0, a.n_chunks}, 0, e->list.data(), n_kept);
     return MBPE_OK;
 }
 
+// a.endmask: the endmask calls (text, mask, singles, doc_off as they state them); else chunk_off, checked, n_bytes > 0
+int enc_dedup_body(mbpe_encoder *e, EncCall a) {
+    DedupRun d;
+    d.who = a.endmask ? "mbpe_encoder_encode_endmask" : "mbpe_encoder_encode";
+    d.mode = a.token_bits == 16 ? kFinU16 : a.out_on_device ? kFinFlags : kFinU32;
+    if (a.tokens_out && a.out_on_device && ((uintptr_t)a.tokens_out & (a.token_bits / 8 - 1)))
+        return fail(MBPE_ERR_ARG, d.who + ": tokens_out must be aligned to its elements (option \"dedup\")");
+    ECHK(hipSetDevice(e->device));
+    e->dd_ran = false;
+    // the chunks that are one token, before anything else (a host text: before the device is touched)
+    const Piece all = {0, a.n_chunks};
+    int rc = gather_singles(e, &a, &all, 1);
+    if (rc != MBPE_OK) return rc;
+    e->dd_singles.swap(e->singles);               // (the unique text is encoded without any: piece_upload reads e->singles)
+    e->singles.clear();
+    d.n_sg = e->dd_singles.size();
+    if ((rc = dedup_unique(e, a, &d)) != MBPE_OK) return rc;
+    if ((rc = dedup_table(e, a, &d)) != MBPE_OK) return rc;
+    if ((rc = dedup_queries(e, a, &d)) != MBPE_OK) return rc;
+    return dedup_expand(e, a, d);
+}
+
 int enc_run_body(mbpe_encoder *e, EncCall a) {
-    const uint64_t one[2] = {0, a.n_bytes};
-    if (!a.chunk_off) { a.chunk_off = one; a.n_chunks = 1; }
+    uint64_t one[2];
+    int rc = chunk_off_check(&a, one);
+    if (rc == MBPE_OK) rc = vocab16_check(e, a.token_bits, "token_bits");
+    if (rc != MBPE_OK) return rc;
     const uint64_t *chunk_off = a.chunk_off;
     const uint64_t n_bytes = a.n_bytes, n_chunks = a.n_chunks;
-    if (chunk_off[0] != 0 || chunk_off[n_chunks] != n_bytes)
-        return fail(MBPE_ERR_ARG, "chunk_off must start at 0 and end at n_bytes");
-    // (every offset is checked before one is used: an offset beyond n_bytes would index the mask and the text below)
-    for (uint64_t c = 0; c < n_chunks; ++c)
-        if (chunk_off[c + 1] < chunk_off[c]) return fail(MBPE_ERR_ARG, "chunk_off must be ascending");
-    if (a.token_bits == 16 && 256ull + e->n_merges > 65536ull)
-        return fail(MBPE_ERR_VOCAB, "token_bits 16 with more than 65,536 token ids");
     if (a.chunk_tok_off_out) a.chunk_tok_off_out[0] = 0;
     e->dd_ran = false;
     if (n_bytes == 0) {
-        if (a.chunk_tok_off_out)
-            for (uint64_t c = 0; c < n_chunks; ++c) a.chunk_tok_off_out[c + 1] = 0;
+        if (a.chunk_tok_off_out) fill_chunk_tok_off(a, Piece{0, n_chunks}, 0, nullptr, 0);
         if (e->dedup) dedup_nothing(e);
         return boff_begin(e, a);
     }
@@ -1319,7 +1351,7 @@ int enc_run_body(mbpe_encoder *e, EncCall a) {
 
     // pieces: whole chunks, at most `limit` bytes each
     uint64_t limit = 0;
-    int rc = piece_limit(e, n_bytes, a.tok_byte_off_out && !a.out_on_device, &limit);
+    rc = piece_limit(e, n_bytes, a.tok_byte_off_out && !a.out_on_device, &limit);
     if (rc != MBPE_OK) return rc;
     std::vector<Piece> pieces;
     if (n_bytes <= limit) {
@@ -1338,25 +1370,7 @@ int enc_run_body(mbpe_encoder *e, EncCall a) {
             c0 = c1;
         }
     }
-
-    // chunks that are one token, of the whole text, before any pass runs
-    e->singles.clear();
-    if (!a.text_on_device) {
-        for (uint64_t c = 0; c < n_chunks; ++c) {
-            const uint64_t s = chunk_off[c], t = chunk_off[c + 1];
-            long long id;
-            if (t > s && a.text[s] == 0 && stoi_value(a.text + s + 1, t - s - 1, &id)) {
-                rc = add_single(e, s, t - s, id, a.token_bits);
-                if (rc != MBPE_OK) return rc;
-            }
-        }
-    } else {
-        for (const Piece &p : pieces) {
-            rc = device_singles(e, a.text, chunk_off, p, a.token_bits);
-            if (rc != MBPE_OK) return rc;
-        }
-        a.mask_on_device = pieces.size() == 1;
-    }
+    if ((rc = gather_singles(e, &a, pieces.data(), pieces.size())) != MBPE_OK) return rc;
 
     PieceRun sum;
     // "a cap too small writes no token": where the pieces before the one that overflows would already have written
@@ -1368,19 +1382,11 @@ int enc_run_body(mbpe_encoder *e, EncCall a) {
         q.tok_byte_off_out = nullptr;
         rc = run_pieces(e, q, pieces, &sum);
         if (rc != MBPE_OK) return rc;
-        if (a.cap < sum.n) {
-            *a.n_out = sum.n;
-            if (a.n_passes_out) *a.n_passes_out = sum.passes;
-            return fail(MBPE_ERR_ARG, "tokens_out too small");
-        }
+        if (a.cap < sum.n) return enc_report(a, sum, true);
         e->pass_tokens.clear();                    // (the kernel time keeps both runs, the pass counts one)
     }
     rc = run_pieces(e, a, pieces, &sum);
-    if (rc != MBPE_OK) return rc;
-    *a.n_out = sum.n;
-    if (a.n_passes_out) *a.n_passes_out = sum.passes;
-    if (sum.too_small) return fail(MBPE_ERR_ARG, "tokens_out too small");
-    return MBPE_OK;
+    return rc != MBPE_OK ? rc : enc_report(a, sum, sum.too_small);
 }
 
 // (the host vectors -- mask, lists, the bytes of NUL-led chunks -- grow with the text: no exception leaves the C-ABI)
@@ -1443,8 +1449,7 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool doc
 
 // what the batch calls check alike once their own arguments are in order (the document lengths: after the encode)
 int enc_batch_check(const mbpe_encoder *e, const EncPack &k) {
-    if (k.spec->out_bits == 16 && 256ull + e->n_merges > 65536ull)
-        return fail(MBPE_ERR_VOCAB, "out_bits 16 with more than 65,536 token ids");
+    if (const int rc = vocab16_check(e, k.spec->out_bits, "out_bits")) return rc;
     if (k.ids_out && k.out_on_device &&
         ((uint64_t)(uintptr_t)k.ids_out % (k.spec->out_bits / 8) || (uint64_t)(uintptr_t)k.len_out % 4))
         return fail(MBPE_ERR_ARG, "ids_out or len_out is not aligned to its elements");
@@ -1457,12 +1462,7 @@ int enc_batch_flat(mbpe_encoder *e, EncCall *a, const EncPack &k, uint64_t *n_to
     const int rc = e->d_flat.reserve(std::max<uint64_t>(a->n_bytes, 1) * (k.token_bits() / 8), e->mem);
     if (rc != MBPE_OK) return rc;
     e->pack_ms = 0.f;
-    a->tokens_out = e->d_flat;
-    a->cap = a->n_bytes;
-    a->token_bits = k.token_bits();
-    a->out_on_device = 1;
-    a->n_out = n_tokens;
-    a->n_passes_out = nullptr;
+    enc_out(a, e->d_flat, a->n_bytes, k.token_bits(), 1, n_tokens, nullptr);
     return MBPE_OK;
 }
 
@@ -1512,19 +1512,14 @@ int enc_endmask_body(mbpe_encoder *e, EncCall a) {
         return fail(MBPE_ERR_OOM, "mbpe_encoder_encode_endmask: the text has " + std::to_string(n_bytes) +
                                       " bytes, more than one piece may hold (" + std::to_string(limit) +
                                       "; option \"piece_bytes\"), and a mask on the device is not cut into pieces");
-    e->singles.clear();
-    for (uint64_t k = 0; k < a.n_singles; ++k)
-        e->singles.push_back({a.singles[k].start, a.singles[k].len, a.singles[k].id, 0});
     const uint64_t one[2] = {0, n_bytes};
+    const Piece all = {0, 1};
     a.chunk_off = one;
     a.n_chunks = 1;
+    if ((rc = gather_singles(e, &a, &all, 1)) != MBPE_OK) return rc;
     PieceRun r;
-    rc = run_piece(e, a, Piece{0, 1}, 0, &r);
-    if (rc != MBPE_OK) return rc;
-    *a.n_out = r.n;
-    if (a.n_passes_out) *a.n_passes_out = r.passes;
-    if (r.too_small) return fail(MBPE_ERR_ARG, "tokens_out too small");
-    return MBPE_OK;
+    rc = run_piece(e, a, all, 0, &r);
+    return rc != MBPE_OK ? rc : enc_report(a, r, r.too_small);
 }
 
 // the checks of the two endmask calls that need neither encoder nor device
@@ -1550,6 +1545,19 @@ int enc_endmask_check(const char *who, uint64_t n_bytes, const mbpe_single *sing
     return MBPE_OK;
 }
 
+// what the endmask calls say of their input: a device text whose chunks are its mask's
+EncCall endmask_call(const uint8_t *text_dev, uint64_t n_bytes, const uint8_t *endmask_dev, const mbpe_single *singles,
+                     uint64_t n_singles, const uint64_t *doc_off, uint64_t n_docs) {
+    EncCall a = {text_dev, n_bytes, 1, nullptr, 0};
+    a.mask_dev = endmask_dev;
+    a.endmask = true;
+    a.singles = singles;
+    a.n_singles = n_singles;
+    a.doc_off = doc_off;
+    a.n_docs = n_docs;
+    return a;
+}
+
 // the one-shot calls: a temporary encoder and one call
 int encode_chunks(int device_id, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off, uint64_t n_chunks,
                   const uint32_t *merges, uint32_t n_merges, uint32_t *tokens_out, uint64_t cap, uint64_t *n_out,
@@ -1560,8 +1568,8 @@ int encode_chunks(int device_id, const uint8_t *text, uint64_t n_bytes, const ui
     mbpe_encoder *e = nullptr;
     int rc = mbpe_encoder_create(device_id, merges, n_merges, &e);
     if (rc != MBPE_OK) return rc;
-    const EncCall a = {text, n_bytes, 0, chunk_off, n_chunks, tokens_out, cap, 32, out_on_device ? 1 : 0, nullptr, n_out,
-                       n_passes_out};
+    EncCall a = {text, n_bytes, 0, chunk_off, n_chunks};
+    enc_out(&a, tokens_out, cap, 32, out_on_device ? 1 : 0, n_out, n_passes_out);
     rc = enc_guard("mbpe_encoder_encode", [&] { return enc_run_body(e, a); });
     const std::string keep = rc == MBPE_OK ? std::string() : std::string(mbpe_host::last_error());
     mbpe_encoder_destroy(e);
@@ -1694,8 +1702,9 @@ int mbpe_encoder_encode_byteoff(mbpe_encoder *e, const uint8_t *text, uint64_t n
     if (n_passes_out) *n_passes_out = 0;
     if (!e || !n_out || (!text && n_bytes)) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode: NULL argument");
     if (token_bits != 16 && token_bits != 32) return fail(MBPE_ERR_ARG, "token_bits must be 16 or 32");
-    EncCall a = {text, n_bytes, text_on_device, chunk_off, n_chunks, tokens_out, cap, token_bits, out_on_device,
-                 chunk_tok_off_out, n_out, n_passes_out};
+    EncCall a = {text, n_bytes, text_on_device, chunk_off, n_chunks};
+    enc_out(&a, tokens_out, cap, token_bits, out_on_device, n_out, n_passes_out);
+    a.chunk_tok_off_out = chunk_tok_off_out;
     a.tok_byte_off_out = tok_byte_off_out;
     int rc = drop_check(e, "mbpe_encoder_encode");
     if (rc == MBPE_OK) rc = dedup_check(e, "mbpe_encoder_encode", tok_byte_off_out);
@@ -1722,12 +1731,8 @@ static int enc_batch(mbpe_encoder *e, EncCall a, const EncPack &k) {
     if (rc == MBPE_OK) rc = dedup_check(e, "mbpe_encoder_encode_batch", nullptr);
     if (rc == MBPE_OK) rc = pack_check_spec(k.spec, k.token_bits());
     if (rc != MBPE_OK) return rc;
-    const uint64_t one[2] = {0, a.n_bytes};
-    if (!a.chunk_off) { a.chunk_off = one; a.n_chunks = 1; }
-    if (a.chunk_off[0] != 0 || a.chunk_off[a.n_chunks] != a.n_bytes)
-        return fail(MBPE_ERR_ARG, "chunk_off must start at 0 and end at n_bytes");
-    for (uint64_t c = 0; c < a.n_chunks; ++c)
-        if (a.chunk_off[c + 1] < a.chunk_off[c]) return fail(MBPE_ERR_ARG, "chunk_off must be ascending");
+    uint64_t one[2];
+    if ((rc = chunk_off_check(&a, one)) != MBPE_OK) return rc;
     if (k.doc_chunk_off[0] != 0 || k.doc_chunk_off[k.n_docs] != a.n_chunks)
         return fail(MBPE_ERR_ARG, "doc_chunk_off must start at 0 and end at n_chunks");
     for (uint64_t i = 0; i < k.n_docs; ++i)
@@ -1783,13 +1788,12 @@ int mbpe_encoder_encode_endmask_byteoff(mbpe_encoder *e, const uint8_t *text_dev
     if ((rc = drop_check(e, "mbpe_encoder_encode_endmask")) != MBPE_OK) return rc;
     if ((rc = dedup_check(e, "mbpe_encoder_encode_endmask", tok_byte_off_out)) != MBPE_OK) return rc;
     if ((uintptr_t)endmask_dev & 3) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_endmask: the mask must be 4-byte aligned");
-    if (token_bits == 16 && 256ull + e->n_merges > 65536ull)
-        return fail(MBPE_ERR_VOCAB, "token_bits 16 with more than 65,536 token ids");
-    EncCall a = {text_dev, n_bytes, 1, nullptr, 0, tokens_out, cap, token_bits, out_on_device, nullptr, n_out,
-                 n_passes_out, true, endmask_dev, singles, n_singles, n_docs ? doc_off : nullptr, n_docs,
-                 doc_tok_off_out, tok_byte_off_out};
-    rc = boff_check(e, "mbpe_encoder_encode_endmask_byteoff", &a);
-    if (rc != MBPE_OK) return rc;
+    if ((rc = vocab16_check(e, token_bits, "token_bits")) != MBPE_OK) return rc;
+    EncCall a = endmask_call(text_dev, n_bytes, endmask_dev, singles, n_singles, n_docs ? doc_off : nullptr, n_docs);
+    enc_out(&a, tokens_out, cap, token_bits, out_on_device, n_out, n_passes_out);
+    a.doc_tok_off_out = doc_tok_off_out;
+    a.tok_byte_off_out = tok_byte_off_out;
+    if ((rc = boff_check(e, "mbpe_encoder_encode_endmask_byteoff", &a)) != MBPE_OK) return rc;
     return enc_guard("mbpe_encoder_encode_endmask", [&] { return enc_endmask_body(e, a); });
 }
 
@@ -1817,13 +1821,8 @@ int mbpe_encoder_encode_batch_endmask(mbpe_encoder *e, const uint8_t *text_dev, 
     rc = enc_batch_check(e, k);
     if (rc != MBPE_OK) return rc;
     return enc_guard(who, [&]() -> int {
-        EncCall a = {text_dev, n_bytes, 1};                      // (enc_batch_flat: where the tokens go)
-        a.mask_on_device = true;
-        a.mask_dev = endmask_dev;
-        a.singles = singles;
-        a.n_singles = n_singles;
-        a.doc_off = doc_off;
-        a.n_docs = n_docs;
+        EncCall a = endmask_call(text_dev, n_bytes, endmask_dev, singles, n_singles, doc_off, n_docs);
+        // (enc_batch_flat: where the tokens go)
         uint64_t n_tokens = 0;
         int rc = enc_batch_flat(e, &a, k, &n_tokens);
         if (rc != MBPE_OK) return rc;

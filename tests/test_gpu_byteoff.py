@@ -196,7 +196,7 @@ def test_singles_from_the_device_split(dev, rank):
         for s, l, i in c.singles:                                 # the single's range is its name's occurrence
             j = tokens.tolist().index(i)
             assert (boff[j], boff[j + 1]) == (s, s + l)
-        docs = [0, c.singles[0][0], len(c.data)]                  # with document offsets: the mask is ranked twice
+        docs = [0, c.singles[0][0], len(c.data)]                  # with document offsets: two queries of one count
         tokens, doc_tok, boff = enc.encode_endmask(*c.ptrs(), singles=c.singles, doc_off=docs, byte_off=True)
         check((tokens, boff), want, "split_docs + documents")
         assert boff[doc_tok.astype(np.int64)].tolist() == docs

@@ -21,6 +21,7 @@ from conftest import read_data, read_golden
 from test_bruteforce_cpu import text_to_vector
 from test_gpu_encode_spans import oracle_encode
 from test_gpu_encode_split import Case as DeviceCase
+from test_gpu_encoder import one_byte_chunks
 from test_gpu_pack import ref_pack
 from test_gpu_pack_aux import ref_aux
 
@@ -157,6 +158,20 @@ def test_shapes(dev, name, table, order):
                 cnt_box.append(dd.encode_device(text.data_ptr(), len(data), off, out.data_ptr(), n - 1))
             assert e.value.code == mbpe.ERR_ARG and (out.cpu().numpy().view(np.uint32) == SENTINEL).all()
             assert dd.dedup_stats()["n_chunks"] == len(chunks)
+
+
+def test_one_byte_chunks():
+    """3,077 chunks of one byte, b"a" and b"b" in turn (one_byte_chunks of tests/test_gpu_encoder.py): two unique
+    chunks, every chunk kept, and the chunks' token offsets are the byte offsets."""
+    c = one_byte_chunks()
+    want, lens = oracle_encode(c)
+    want_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    assert np.array_equal(want, c.data) and np.array_equal(want_off, c.chunk_off)      # (what the oracle says of it)
+    with mbpe.Encoder(c.merges, dedup=True) as enc:
+        got, off = enc.encode(c.data, c.chunk_off, offsets=True)
+        assert np.array_equal(got, want) and np.array_equal(off, want_off)
+        st = enc.dedup_stats()
+        assert (st["n_chunks"], st["n_unique"], st["n_unique_bytes"]) == (len(c.data), 2, 2)
 
 
 def test_too_small_reports_the_count(dev):

@@ -128,6 +128,33 @@ def test_chunk_offsets():
         assert rc == mbpe.OK and n == len(want) and np.array_equal(off_q, want_off)
 
 
+def one_byte_chunks():
+    """Every byte a chunk of its own, three spans and five bytes of them: nothing merges, and the list of chunk ends
+    (8 bytes per chunk) is twice the size of a token array (4 bytes per byte), so a fresh encoder, whose buffers hold
+    exactly what the call asks for, cannot keep the list in the idle token array and gives it a buffer of its own."""
+    n = 3 * E.SPAN + 5
+    data = np.ascontiguousarray(np.tile(np.frombuffer(b"ab", dtype=np.uint8), n // 2 + 1)[:n])
+    merges = np.array([[97, 98], [256, 256]], dtype=np.uint32)
+    return E.Case(data, np.arange(n + 1, dtype=np.uint64), merges, "one-byte chunks")
+
+
+def test_chunk_offsets_of_one_byte_chunks():
+    c = one_byte_chunks()
+    want, want_off = _expect(c)
+    assert np.array_equal(want, O.encode_chunks(c.data, c.chunk_off, c.merges))
+    assert np.array_equal(want, c.data) and np.array_equal(want_off, c.chunk_off)     # (what the oracle says of it)
+    h = _handmade()
+    with mbpe.Encoder(c.merges) as enc:
+        got, off = enc.encode(c.data, c.chunk_off, offsets=True)
+        _same(got, want, enc.n_passes, c.name)
+        assert off.dtype == np.uint64 and np.array_equal(off, want_off)
+        got16, off16 = enc.encode(c.data, c.chunk_off, offsets=True, dtype=np.uint16)
+        assert got16.dtype == np.uint16 and np.array_equal(got16, want.astype(np.uint16))
+        assert np.array_equal(off16, want_off)
+        # the same encoder afterwards on the ordinary path: the spill leaves it intact
+        _check_case(enc, E.Case(h.data, h.chunk_off, c.merges, h.name + " (after one-byte chunks)"))
+
+
 # ---- the C function as it is --------------------------------------------------------------------------------------
 
 def _raw(enc, data, off=None, cap=None, out=True, bits=32, offsets=False):

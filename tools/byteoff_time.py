@@ -1,7 +1,8 @@
 """Token byte offsets timed (profiles/r18_byteoff.md): mbpe_encoder_kernel_ms of an Encoder call, text and output on
 the device, on shakespeare x 1024 with the gpt4 split and the golden gpt4 model, in both orders -- the plain call on
 ANOTHER build of the library (--parent-root: a checkout of the parent commit with its libmbpe.so built) and on this
-tree's, alternately, every run a fresh process under its own time limit; and the byte-offset call on this tree's.
+tree's, alternately, every run a fresh process under its own time limit; and the byte-offset call on this tree's, or,
+with --parent-byteoff (a parent that has the call: profiles/r22_encode_host.md), on both builds in every run.
 Nothing is started after a run that fails.  Every run: 2 warm-up calls, then 15 timed ones.
 
     python tools/byteoff_time.py --parent-root <checkout of the parent commit> --json byteoff_time.json
@@ -63,10 +64,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-root", required=True)
     ap.add_argument("--json", default="byteoff_time.json")
+    ap.add_argument("--parent-byteoff", action="store_true", help="the parent has the byte-offset call: time it there too")
     args = ap.parse_args()
     runs = []
     parent = os.path.abspath(args.parent_root)
-    for root, boff in ((parent, 0), (ROOT, 0), (parent, 0), (ROOT, 1), (parent, 0), (ROOT, 0)):
+    order = ((parent, 0), (ROOT, 0), (parent, 0), (ROOT, 1), (parent, 0), (ROOT, 0))
+    if args.parent_byteoff:
+        order = ((parent, 1), (ROOT, 1), (parent, 1), (ROOT, 1))
+    for root, boff in order:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "child", root, str(boff)], capture_output=True,
                            text=True, timeout=240)
         if r.returncode != 0:

@@ -14,6 +14,8 @@ merges of the committed 512-entry model of that text):
             dedup off and on, this build
   default   dedup off, both orders, on the first text: the parent build and this build alternately (twice each) in one
             call; the bar for "did not move" is the parent's own spread between its two runs
+  --parent-endmask  (a parent that has the "dedup" route: profiles/r22_encode_host.md) the endmask job alternates the
+            builds in the same way
   bench     bench.py --gpus 1 --steps 3 --warmup 1 of both builds alternately (twice each)
 
 Every (build, job) is one child process; the builds alternate.  A run needs a GPU and torch (the output buffers):
@@ -172,6 +174,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--pkg-root", help="(worker) the checkout whose binding and library are timed")
     ap.add_argument("--parent-root", help="checkout of the parent commit with minbpe-cc_amd/libmbpe.so built")
+    ap.add_argument("--parent-endmask", action="store_true", help="run the endmask job on the parent build too, alternately")
     ap.add_argument("--json")
     args = ap.parse_args()
     if args.worker:
@@ -192,7 +195,8 @@ def main():
 
     for text in texts:
         if "endmask" in jobs:
-            run("this", "endmask", text)
+            for build in ("parent", "this", "parent", "this") if args.parent_endmask else ("this",):
+                run(build, "endmask", text)
         if "tokenizer" in jobs:
             run("parent", "tokenizer", text)
             run("this", "tokenizer", text)
