@@ -1178,6 +1178,58 @@ MBPE_API int  mbpe_dedup_alloc_count(const mbpe_dedup *d, uint64_t *n_out);
 MBPE_API int  mbpe_dedup_map(const mbpe_dedup *d, const uint32_t **unique_of_dev_out, uint64_t *n_chunks_out);
 MBPE_API int  mbpe_dedup_get_map(mbpe_dedup *d, uint32_t *unique_of_out, uint64_t cap_chunks, uint64_t *n_chunks_out);
 
+/* ---- word counts across calls (csrc/wordcount.hip, wordcount.h) --------------------------------------------------------
+ * A corpus that arrives in pieces: every add call dedups its piece on the device (an owned mbpe_dedup) and folds the
+ * result into a table the object keeps there.  With piece p's chunk list L_p (empty chunks dropped), the table after
+ * L_0, L_1, ... holds the unique chunks, weights and first occurrences of ONE dedup of the concatenated list
+ * L_0 + L_1 + ...: first-occurrence order over the concatenation, first_chunk the index in it, and a chunk above
+ * "max_chunk_bytes" once per occurrence with weight 1.  Training on it (mbpe_load_corpus_*_weighted) therefore equals
+ * training on the concatenated list, for both tie-breaks.  Pieces are split independently: a piece boundary is a chunk
+ * boundary.  Device memory while counting: the deduper's for the largest piece (see mbpe_dedup_*) plus, per unique
+ * chunk, its bytes, 24 B and 16 .. 32 B of table; host memory: one piece.
+ *
+ *   mbpe_wordcount_add_endmask  a piece as device text with an end mask; mbpe_wordcount_add: as text with chunk_off.
+ *                               Argument conventions, layouts and alignment are those of mbpe_dedup_chunks_endmask and
+ *                               mbpe_dedup_chunks (first_chunk counts the empty chunks of chunk_off).  repeat >= 1 counts
+ *                               the piece that many times, written out back to back: the weights are multiplied, order
+ *                               and first_chunk are those of one copy, and the chunks after it move on by repeat x the
+ *                               piece's; 0 is MBPE_ERR_ARG.  n_unique_total_out (required) and
+ *                               n_unique_bytes_total_out (optional): the table's sizes after the call.  2^32 - 1 unique
+ *                               chunks or more: MBPE_ERR_ARG.  A later call that brings no new chunk and is no larger
+ *                               than an earlier piece allocates nothing (mbpe_wordcount_alloc_count).
+ *   mbpe_wordcount_result       device views: the packed text, its end mask in the layout mbpe_load_corpus_endmask reads,
+ *                               the weights as u32 and first_chunk (u64); any may be NULL.  Valid until the next add or
+ *                               reset; they go into mbpe_load_corpus_endmask_weighted(..., weights_on_device = 1) as they
+ *                               are.
+ *   mbpe_wordcount_get          host copies, as mbpe_dedup_get
+ *   A weight that reaches 2^31 (the limit of the weighted load; the u64 sums saturate) makes _result and _get return
+ *   MBPE_ERR_OVERFLOW until mbpe_wordcount_reset.
+ *   mbpe_wordcount_stats        pieces added, chunks counted (repeats included), unique chunks and their bytes
+ *   mbpe_wordcount_reset        empty again, buffers kept
+ *   mbpe_wordcount_set_option   "max_chunk_bytes", "hash_bits": handed to the owned deduper, same defaults and ranges;
+ *                               MBPE_ERR_STATE once a piece has been added (until the next reset)
+ *   mbpe_wordcount_kernel_ms    device time of the latest add call: the deduper's kernels and the fold's
+ * Arguments are checked before the device is touched.  No CPU fallback: MBPE_ERR_NO_DEVICE without a HIP device. */
+typedef struct mbpe_wordcount mbpe_wordcount;
+MBPE_API int  mbpe_wordcount_create(int device_id, mbpe_wordcount **out);
+MBPE_API void mbpe_wordcount_destroy(mbpe_wordcount *w);
+MBPE_API int  mbpe_wordcount_add_endmask(mbpe_wordcount *w, const uint8_t *text_dev, uint64_t n_bytes,
+                                         const uint8_t *endmask_dev, uint32_t repeat, uint64_t *n_unique_total_out,
+                                         uint64_t *n_unique_bytes_total_out);
+MBPE_API int  mbpe_wordcount_add(mbpe_wordcount *w, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                 const uint64_t *chunk_off, uint64_t n_chunks, uint32_t repeat,
+                                 uint64_t *n_unique_total_out, uint64_t *n_unique_bytes_total_out);
+MBPE_API int  mbpe_wordcount_result(mbpe_wordcount *w, const uint8_t **text_dev_out, const uint8_t **endmask_dev_out,
+                                    const uint32_t **weights_dev_out, const uint64_t **first_chunk_dev_out);
+MBPE_API int  mbpe_wordcount_get(mbpe_wordcount *w, uint8_t *text_out, uint64_t *chunk_off_out, uint32_t *weights_out,
+                                 uint64_t *first_chunk_out, uint64_t cap_bytes, uint64_t cap_chunks);
+MBPE_API int  mbpe_wordcount_stats(const mbpe_wordcount *w, uint64_t *n_pieces_out, uint64_t *n_chunks_total_out,
+                                   uint64_t *n_unique_out, uint64_t *n_unique_bytes_out);
+MBPE_API int  mbpe_wordcount_reset(mbpe_wordcount *w);
+MBPE_API int  mbpe_wordcount_set_option(mbpe_wordcount *w, const char *name, int64_t value);
+MBPE_API int  mbpe_wordcount_kernel_ms(const mbpe_wordcount *w, float *ms_out);
+MBPE_API int  mbpe_wordcount_alloc_count(const mbpe_wordcount *w, uint64_t *n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,34 @@ MBPE_API int mbpe_tok_train_split_device(mbpe_tokenizer *t, const uint8_t *text,
 MBPE_API int mbpe_tok_train_continue(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, uint32_t vocab_size,
                                      int conflict_resolution, int verbose, int device_id, int device_split);
 
+/* Training on a corpus that arrives in pieces -- many files, more than one host buffer or more than device memory holds.
+ * The pieces' chunks are counted on the device as they pass (mbpe_wordcount_*, mbpe.h) and the training runs on the
+ * table: the merges, counts, verbose lines, .model and .vocab of a training on the pieces' chunk lists laid end to end,
+ * for both tie-breaks.  Every piece is split on its own, so a piece boundary is a chunk boundary ("a  " + "b" is not
+ * "a  b"); cut where a letter or digit is followed by whitespace -- a chunk boundary under gpt2 and gpt4 -- and the
+ * pieces give the whole text's result.  Host memory: one piece; device memory while counting: the largest piece's
+ * split and dedup plus the unique chunks.  The training is that of mbpe_tok_set_train_dedup: one rank, the 32-bit
+ * loop, and a chunk above 256 bytes is never merged with its duplicates.
+ *   _begin   opens the session on device_id; device_split != 0: the pieces are split on the device too.
+ *            MBPE_ERR_STATE while a session is open.
+ *   _add     one piece, counted `repeat` (>= 1, else MBPE_ERR_ARG) times, as if written out back to back: how a data mix
+ *            up-weights a source.  With the device split (one splitter for the session, mbpe_tok_set_split_unicode
+ *            honoured by every add) neither text nor mask returns to the host; a pattern that is not gpt2 / gpt4 is
+ *            MBPE_ERR_ARG there, as for mbpe_tok_train_split_device.  MBPE_ERR_STATE without a session.  A failed add
+ *            leaves the session open; the tokenizer's merges are untouched.
+ *   _finish  loads the table into a fresh context -- in place after the device split; after the host split the unique
+ *            chunks come back once and go through mbpe_load_corpus_weighted, so the NUL rule is applied as ever -- and
+ *            trains as mbpe_tok_train does.  resume != 0 continues from the merges the tokenizer holds, with the checks
+ *            and error codes of mbpe_tok_train_continue.  Verbose prints "Split input text into N chunks" once, with
+ *            the session's total, and the length in the closing line is the whole corpus's.  The tokenizer's merges
+ *            change only when it succeeds; the session is closed either way.
+ *   _abort   closes the session, if any.  After _finish or _abort the session's device objects are gone. */
+MBPE_API int mbpe_tok_train_pieces_begin(mbpe_tokenizer *t, int device_id, int device_split);
+MBPE_API int mbpe_tok_train_pieces_add(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, uint32_t repeat);
+MBPE_API int mbpe_tok_train_pieces_finish(mbpe_tokenizer *t, uint32_t vocab_size, int conflict_resolution, int verbose,
+                                          int resume);
+MBPE_API int mbpe_tok_train_pieces_abort(mbpe_tokenizer *t);
+
 /* Direct access to the trained / loaded merges (2 u32 per merge). */
 MBPE_API int mbpe_tok_set_merges(mbpe_tokenizer *t, const uint32_t *merges, uint32_t n_merges);
 MBPE_API int mbpe_tok_get_merges(mbpe_tokenizer *t, uint32_t *merges_out, uint32_t cap, uint32_t *n_out);

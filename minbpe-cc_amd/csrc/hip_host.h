@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <utility>
 
 namespace mbpe {
 
@@ -74,6 +75,21 @@ public:
     operator T *() const { return p_; }
     uint64_t bytes() const { return cap_; }
     T *release() { T *p = p_; p_ = nullptr; cap_ = 0; return p; }
+    void swap(DevBuf &o) noexcept { std::swap(p_, o.p_); std::swap(cap_, o.cap_); }
+    // reserve that keeps the first used_bytes: at least want_bytes, grown geometrically into a new buffer with a
+    // device-to-device copy on `stream`, which is waited for before the old buffer goes
+    int grow(uint64_t used_bytes, uint64_t want_bytes, DevAlloc &a, hipStream_t stream) {
+        if (p_ && cap_ >= want_bytes) return MBPE_OK;
+        DevBuf bigger;
+        const int rc = bigger.reserve(want_bytes > 2 * cap_ ? want_bytes : 2 * cap_, a);
+        if (rc != MBPE_OK) return rc;
+        if (p_ && used_bytes) {
+            MBPE_HIP_CHECK(hipMemcpyAsync(bigger.p_, p_, used_bytes, hipMemcpyDeviceToDevice, stream), a.clear_last);
+            MBPE_HIP_CHECK(hipStreamSynchronize(stream), a.clear_last);
+        }
+        swap(bigger);
+        return MBPE_OK;
+    }
 
 private:
     T *p_ = nullptr;

@@ -1,7 +1,7 @@
 // minbpe-cc: the reference's command line (code/examples/minbpe-cc.cpp:92-265)
 // on top of the MI355X training path.  Same flags, defaults, messages and exit
 // codes; `--train -c lexical` runs on the GPU.  The only additions are --device, the --device-* switches, --rank-order,
-// --dropout / --seed, --byte-ranges-out and --continue-from.
+// --dropout / --seed, --byte-ranges-out, --continue-from and --input-list.
 #include "mbpe.h"
 #include "mbpe_tokenizer.h"
 
@@ -99,14 +99,22 @@ void usage() {
                  "                              --model-path.  The loaded model's split pattern is used: --encoder has no\n"
                  "                              effect then.  One HIP device; vocabularies up to 16,777,216, beyond the 16-bit\n"
                  "                              slot format on 32-bit tokens (a model without a split pattern replays one\n"
-                 "                              pass per merge it already has)\n";
+                 "                              pass per merge it already has)\n"
+                 "  --input-list TEXT           With --train, instead of --input: a file with one path per line, each file one\n"
+                 "                              piece of the corpus, optionally followed by a tab and a repeat count (the piece\n"
+                 "                              is counted that many times); blank lines are skipped.  The pieces are read one\n"
+                 "                              at a time, their chunks counted on the HIP device, and the training runs on the\n"
+                 "                              counts as with --dedup: the model of the pieces' chunks laid end to end.  Every\n"
+                 "                              piece is split on its own, so cut files where a letter or digit is followed by\n"
+                 "                              whitespace.  Combines with --device-split, --device-split-unicode,\n"
+                 "                              --continue-from, -c and -w; with --input or without --train it is an error\n";
 }
 
 }  // namespace
 
 int main(int argc, char *argv[]) {
-    std::string input_path, output_path, special_token_path, encoder = "gpt4", model_path = "./output.model", continue_from,
-                byte_ranges_path;
+    std::string input_path, input_list_path, output_path, special_token_path, encoder = "gpt4", model_path = "./output.model",
+                continue_from, byte_ranges_path;
     std::string conflict_resolution_str = "first";
     bool train = false, decode = false, encode = false, write_vocab = false, verbose = false, device_encode = false,
          device_decode = false, device_split = false, split_unicode = false, rank_order = false, dedup = false;
@@ -130,6 +138,7 @@ int main(int argc, char *argv[]) {
         std::string tmp;
         if (arg == "-h" || arg == "--help") { usage(); return 0; }
         else if (arg == "-i" || arg == "--input") { if (!value(&input_path)) return 106; }
+        else if (arg == "--input-list") { if (!value(&input_list_path)) return 106; }
         else if (arg == "-o" || arg == "--output") { if (!value(&output_path)) return 106; }
         else if (arg == "-s" || arg == "--special-tokens-path") { if (!value(&special_token_path)) return 106; }
         else if (arg == "-m" || arg == "--model-path") { if (!value(&model_path)) return 106; }
@@ -182,7 +191,33 @@ int main(int argc, char *argv[]) {
         if (!rank_order) { std::cerr << "--dropout requires --rank-order\n"; return 107; }
     }
 
-    if (!input_path.empty()) {                                  // :135-144
+    struct Piece { std::string path; uint32_t repeat; };
+    std::vector<Piece> pieces;
+    if (!input_list_path.empty()) {
+        if (!input_path.empty()) { std::cerr << "--input-list excludes --input\n"; return 107; }
+        if (!train) { std::cerr << "--input-list requires --train\n"; return 107; }
+        if (!exists(input_list_path)) { std::cerr << "Input file " << input_list_path << " does not exist\n"; return -1; }
+        std::ifstream list(input_list_path);
+        for (std::string line; std::getline(list, line);) {
+            if (!line.empty() && line.back() == '\r') line.pop_back();
+            if (line.empty()) continue;
+            Piece p{line, 1};
+            const size_t tab = line.find('\t');
+            if (tab != std::string::npos) {
+                const std::string count = line.substr(tab + 1);
+                size_t used = 0;
+                unsigned long long v = 0;
+                try { v = std::stoull(count, &used); } catch (...) { used = 0; }
+                if (used == 0 || used != count.size() || count[0] == '-' || v == 0 || v > 0xFFFFFFFFull) {
+                    std::cerr << "--input-list: invalid repeat count " << count << " for " << line.substr(0, tab) << "\n";
+                    return 104;
+                }
+                p = Piece{line.substr(0, tab), static_cast<uint32_t>(v)};
+            }
+            if (!exists(p.path)) { std::cerr << "Input file " << p.path << " does not exist\n"; return -1; }
+            pieces.push_back(p);
+        }
+    } else if (!input_path.empty()) {                           // :135-144
         if (!exists(input_path)) { std::cerr << "Input file " << input_path << " does not exist\n"; return -1; }
     } else {
         std::cerr << "Input file not specified\n";
@@ -221,28 +256,58 @@ int main(int argc, char *argv[]) {
     if (train) {                                                // :181-211
         if (have_special) mbpe_tok_set_special_tokens(rt, special_tokens_data.data(), special_tokens_data.size());
         else std::cout << "No special tokens file provided\n";
-        std::cout << "Training using file \"" << input_path << "\" encoder " << encoder << " vocab size " << vocab_size
-                  << " model path " << model_path << "\n";
-        if (verbose) std::cout << "Loading file " << input_path << "\n";
+        std::cout << "Training using file \"" << (input_list_path.empty() ? input_path : input_list_path) << "\" encoder "
+                  << encoder << " vocab size " << vocab_size << " model path " << model_path << "\n";
+        const int cr = conflict_resolution_str == "lexical" ? 1 : 0;
         std::string input, err;
-        if (load_file_to_string(input_path, &input, &err)) {
-            if (verbose) std::cout << "Starting training...\n";
+        if (!input_list_path.empty()) {
+            // the corpus in pieces: one file in memory at a time, its chunks counted on the device
             if (split_unicode) mbpe_tok_set_split_unicode(rt, 1);
-            if (dedup) mbpe_tok_set_train_dedup(rt, 1);
-            const uint8_t *in = reinterpret_cast<const uint8_t *>(input.data());
-            const int cr = conflict_resolution_str == "lexical" ? 1 : 0;
-            const int trc = !continue_from.empty()
-                                ? mbpe_tok_train_continue(rt, in, input.size(), (uint32_t)vocab_size, cr, verbose, device, device_split)
-                                : (device_split ? mbpe_tok_train_split_device : mbpe_tok_train)(rt, in, input.size(),
-                                                                                                (uint32_t)vocab_size, cr, verbose, device);
-            if (trc != MBPE_OK) {
-                std::cerr << "Error: " << mbpe_last_error() << "\n";
-                rc = -1;
+            int trc = mbpe_tok_train_pieces_begin(rt, device, device_split);
+            bool read_ok = true;
+            for (size_t k = 0; k < pieces.size() && trc == MBPE_OK && read_ok; ++k) {
+                if (verbose) std::cout << "Loading file " << pieces[k].path << "\n";
+                read_ok = load_file_to_string(pieces[k].path, &input, &err);
+                if (read_ok)
+                    trc = mbpe_tok_train_pieces_add(rt, reinterpret_cast<const uint8_t *>(input.data()), input.size(),
+                                                    pieces[k].repeat);
+            }
+            if (!read_ok) {
+                std::cerr << "Failed to load training input file: " << err << "\n";
+                mbpe_tok_train_pieces_abort(rt);
             } else {
-                mbpe_tok_save(rt, model_path.c_str(), write_vocab);
+                if (verbose && trc == MBPE_OK) std::cout << "Starting training...\n";
+                if (trc == MBPE_OK)
+                    trc = mbpe_tok_train_pieces_finish(rt, (uint32_t)vocab_size, cr, verbose, !continue_from.empty());
+                if (trc != MBPE_OK) {
+                    std::cerr << "Error: " << mbpe_last_error() << "\n";
+                    mbpe_tok_train_pieces_abort(rt);
+                    rc = -1;
+                } else {
+                    mbpe_tok_save(rt, model_path.c_str(), write_vocab);
+                }
             }
         } else {
-            std::cerr << "Failed to load training input file: " << err << "\n";
+            if (verbose) std::cout << "Loading file " << input_path << "\n";
+            if (load_file_to_string(input_path, &input, &err)) {
+                if (verbose) std::cout << "Starting training...\n";
+                if (split_unicode) mbpe_tok_set_split_unicode(rt, 1);
+                if (dedup) mbpe_tok_set_train_dedup(rt, 1);
+                const uint8_t *in = reinterpret_cast<const uint8_t *>(input.data());
+                const int trc =
+                    !continue_from.empty()
+                        ? mbpe_tok_train_continue(rt, in, input.size(), (uint32_t)vocab_size, cr, verbose, device, device_split)
+                        : (device_split ? mbpe_tok_train_split_device : mbpe_tok_train)(rt, in, input.size(),
+                                                                                        (uint32_t)vocab_size, cr, verbose, device);
+                if (trc != MBPE_OK) {
+                    std::cerr << "Error: " << mbpe_last_error() << "\n";
+                    rc = -1;
+                } else {
+                    mbpe_tok_save(rt, model_path.c_str(), write_vocab);
+                }
+            } else {
+                std::cerr << "Failed to load training input file: " << err << "\n";
+            }
         }
     } else if (encode) {                                        // :212-242
         if (output_path.empty()) { std::cerr << "Output file not specified\n"; mbpe_tok_destroy(rt); return -1; }

@@ -26,6 +26,7 @@ Tokenizer::~Tokenizer() {
     drop_decoder();
     drop_encoder();
     drop_splitter();
+    train_pieces_abort();
 }
 
 void Tokenizer::drop_splitter() {
@@ -168,23 +169,8 @@ void Tokenizer::set_special_tokens_from_file(const std::string &input_string) { 
 
 void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTION conflict_resolution,
                       bool verbose, int device, bool device_split, bool resume) {
-    if (vocab_size < 256) throw std::runtime_error("vocab_size must be >= 256");   // assert, :492
-    // the table a resumed training continues from: what the tokenizer holds (checked before anything is dropped)
-    std::vector<uint32_t> prior;
-    if (resume) {
-        for (const TokenPair &mp : merges_) { prior.push_back(mp.first); prior.push_back(mp.second); }
-        if (prior.size() / 2 > static_cast<size_t>(vocab_size - 256))
-            throw CodedError(MBPE_ERR_ARG, "vocab_size " + std::to_string(vocab_size) + " is below the " +
-                                               std::to_string(256 + prior.size() / 2) + " tokens the model already has");
-        if (mbpe_merges_check(prior.data(), static_cast<uint32_t>(prior.size() / 2)) != MBPE_OK)
-            throw CodedError(MBPE_ERR_ARG, mbpe_last_error());
-    }
-    const uint32_t n_prior = static_cast<uint32_t>(prior.size() / 2);
-    drop_decoder();
-    drop_encoder();
-    merges_.clear();
-    merges_lookup_.clear();
-    initialize_vocab();
+    const std::vector<uint32_t> prior = training_prior(vocab_size, resume);      // (checked before anything is dropped)
+    clear_model();
 
     const uint8_t *bytes = reinterpret_cast<const uint8_t *>(text.data());
     std::vector<uint64_t> starts, ends;
@@ -264,11 +250,6 @@ void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTI
                                                   dd_weights.data());
         }
     }
-    const uint32_t cap = static_cast<uint32_t>(vocab_size - 256);
-    std::vector<uint32_t> flat(2 * static_cast<size_t>(cap) + 2);
-    std::vector<int32_t> had(cap + 1);
-    uint32_t n_merges = 0;
-    mbpe_stats st;
     // chunks as ranges: bytes between two matches belong to no chunk, as in the reference's loop (:506-540).  The
     // device split's mask goes to the trainer as it is: the NUL rule of text_to_vector (:86-93) never fires for the
     // gpt2 / gpt4 patterns -- a chunk that starts with NUL holds no ASCII digit, so std::stoi cannot parse its remainder
@@ -276,16 +257,57 @@ void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTI
              : dev_split  ? mbpe_load_corpus_endmask(ctx, text.empty() ? bytes : d_text, text.size(), !text.empty(), d_mask)
              : chunked    ? mbpe_load_corpus_ranges(ctx, bytes, text.size(), starts.data(), ends.data(), starts.size(), 0)
                           : mbpe_load_corpus(ctx, bytes, text.size(), nullptr, 0, 0);
+    Trained tr;
+    rc = run_training(ctx, rc, vocab_size, conflict_resolution, prior, train_dedup_ && verbose ? &dd_weights : nullptr, &tr);
+    std::string msg = rc == MBPE_OK ? "" : mbpe_last_error();
+    mbpe_destroy(ctx);
+    mbpe_dedup_destroy(dd);                 // (the trainer has its own copies of mask and weights; the text until here)
+    mbpe_splitter_destroy(dev_split);       // (its text and mask were in use until here)
+    if (rc != MBPE_OK && resume) throw CodedError(rc, msg);      // (mbpe_tok_train_continue hands the code on)
+    if (rc != MBPE_OK) throw std::runtime_error(msg);
+    adopt_training(tr, vocab_size, n_prior_of(prior), verbose, text.length());
+}
+
+std::vector<uint32_t> Tokenizer::training_prior(int vocab_size, bool resume) const {
+    if (vocab_size < 256) throw std::runtime_error("vocab_size must be >= 256");   // assert, :492
+    // the table a resumed training continues from: what the tokenizer holds
+    std::vector<uint32_t> prior;
+    if (resume) {
+        for (const TokenPair &mp : merges_) { prior.push_back(mp.first); prior.push_back(mp.second); }
+        if (prior.size() / 2 > static_cast<size_t>(vocab_size - 256))
+            throw CodedError(MBPE_ERR_ARG, "vocab_size " + std::to_string(vocab_size) + " is below the " +
+                                               std::to_string(256 + prior.size() / 2) + " tokens the model already has");
+        if (mbpe_merges_check(prior.data(), static_cast<uint32_t>(prior.size() / 2)) != MBPE_OK)
+            throw CodedError(MBPE_ERR_ARG, mbpe_last_error());
+    }
+    return prior;
+}
+
+void Tokenizer::clear_model() {
+    drop_decoder();
+    drop_encoder();
+    merges_.clear();
+    merges_lookup_.clear();
+    initialize_vocab();
+}
+
+int Tokenizer::run_training(mbpe_ctx *ctx, int rc, int vocab_size, CONFLICT_RESOLUTION conflict_resolution,
+                            const std::vector<uint32_t> &prior, const std::vector<uint32_t> *weights, Trained *out) {
+    const uint32_t cap = static_cast<uint32_t>(vocab_size - 256);
+    out->flat.assign(2 * static_cast<size_t>(cap) + 2, 0);
+    out->had.assign(cap + 1, 0);
+    out->n_merges = 0;
+    mbpe_stats &st = out->st;
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "conflict_resolution", conflict_resolution == LEXICAL ? 1 : 0);
     // (`first` beyond the 16-bit slot format continues on 32-bit tokens, as the reference's uint32_t Token does)
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "first_wide", 1);
     // (... and so does a training that continues from existing merges)
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "resume_wide", 1);
-    if (rc == MBPE_OK) rc = mbpe_train_begin_from(ctx, static_cast<uint32_t>(vocab_size), prior.data(), n_prior);
+    if (rc == MBPE_OK) rc = mbpe_train_begin_from(ctx, static_cast<uint32_t>(vocab_size), prior.data(), n_prior_of(prior));
     if (rc == MBPE_OK) rc = mbpe_train_steps(ctx, cap, nullptr);
-    if (rc == MBPE_OK) rc = mbpe_train_result(ctx, flat.data(), had.data(), cap, &n_merges);
+    if (rc == MBPE_OK) rc = mbpe_train_result(ctx, out->flat.data(), out->had.data(), cap, &out->n_merges);
     if (rc == MBPE_OK) rc = mbpe_get_stats(ctx, &st);
-    if (rc == MBPE_OK && train_dedup_ && verbose) {
+    if (rc == MBPE_OK && weights) {
         // the length the verbose line reports is the full corpus's: every unique chunk's tokens, weights[c] times
         uint64_t n_stream = 0;
         rc = mbpe_get_stream(ctx, nullptr, nullptr, 0, &n_stream);
@@ -294,21 +316,18 @@ void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTI
         if (rc == MBPE_OK) rc = mbpe_get_stream(ctx, toks.data(), is_end.data(), n_stream, &n_stream);
         uint64_t total = 0, chunk = 0;
         for (uint64_t i = 0; i < n_stream && rc == MBPE_OK; ++i) {
-            total += chunk < dd_weights.size() ? dd_weights[chunk] : 1;
+            total += chunk < weights->size() ? (*weights)[chunk] : 1;
             if (is_end[i]) ++chunk;
         }
         st.n_live = total;
     }
-    std::string msg = rc == MBPE_OK ? "" : mbpe_last_error();
-    mbpe_destroy(ctx);
-    mbpe_dedup_destroy(dd);                 // (the trainer has its own copies of mask and weights; the text until here)
-    mbpe_splitter_destroy(dev_split);       // (its text and mask were in use until here)
-    if (rc != MBPE_OK && resume) throw CodedError(rc, msg);      // (mbpe_tok_train_continue hands the code on)
-    if (rc != MBPE_OK) throw std::runtime_error(msg);
+    return rc;
+}
 
+void Tokenizer::adopt_training(const Trained &tr, int vocab_size, uint32_t n_prior, bool verbose, uint64_t text_length) {
     const int total_merges = vocab_size - 256;
-    for (uint32_t k = 0; k < n_merges; ++k) {            // the bookkeeping of :562-579
-        const TokenPair mp{flat[2 * k], flat[2 * k + 1]};
+    for (uint32_t k = 0; k < tr.n_merges; ++k) {         // the bookkeeping of :562-579
+        const TokenPair mp{tr.flat[2 * k], tr.flat[2 * k + 1]};
         std::vector<Token> appended{vocab_[mp.first]};
         appended.insert(appended.end(), vocab_[mp.second].begin(), vocab_[mp.second].end());
         vocab_.push_back(appended);
@@ -316,13 +335,116 @@ void Tokenizer::train(const std::string &text, int vocab_size, CONFLICT_RESOLUTI
             std::string s;
             for (auto c : appended) s += (c >= 32 && c < 127) ? static_cast<char>(c) : ' ';
             std::cout << "merge " << k + 1 << "/" << total_merges << ": (" << mp.first << ", " << mp.second
-                      << ") -> " << 256 + k << " (b'" << s << "') had " << had[k] << " occurrences\n";
+                      << ") -> " << 256 + k << " (b'" << s << "') had " << tr.had[k] << " occurrences\n";
         }
         merges_.push_back(mp);
         merges_lookup_[mp] = 256 + k;
     }
     if (verbose)                                         // :591-597
-        std::cout << "Length of training text " << text.length() << ". After merges " << st.n_live << ".\n";
+        std::cout << "Length of training text " << text_length << ". After merges " << tr.st.n_live << ".\n";
+}
+
+// ---- training on a corpus that arrives in pieces (mbpe_tok_train_pieces_*) ---------------------------------------------
+void Tokenizer::train_pieces_abort() {
+    if (pieces_.wc) mbpe_wordcount_destroy(pieces_.wc);
+    if (pieces_.splitter) mbpe_splitter_destroy(pieces_.splitter);
+    pieces_ = PieceSession();
+}
+
+void Tokenizer::train_pieces_begin(int device, bool device_split) {
+    if (pieces_.open) throw CodedError(MBPE_ERR_STATE, "train_pieces_begin: a session is open already");
+    PieceSession s;
+    s.device = device;
+    s.device_split = device_split;
+    const int rc = mbpe_wordcount_create(device, &s.wc);
+    if (rc != MBPE_OK) throw CodedError(rc, mbpe_last_error());
+    s.open = true;
+    pieces_ = s;
+}
+
+void Tokenizer::train_pieces_add(const char *text, uint64_t n, uint32_t repeat) {
+    if (!pieces_.open) throw CodedError(MBPE_ERR_STATE, "train_pieces_add: no session is open (train_pieces_begin)");
+    if (repeat == 0) throw CodedError(MBPE_ERR_ARG, "train_pieces_add: repeat must be at least 1");
+    static const char nothing = 0;
+    if (!text) text = &nothing;                   // (an empty piece)
+    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(text);
+    uint64_t n_chunks = 0, n_unique = 0;
+    int rc;
+    if (pieces_.device_split) {
+        // split and counted on the device: neither the text nor its mask returns to the host
+        // (one splitter for the session; a custom pattern is refused: MBPE_ERR_ARG, no return to the host split)
+        const uint8_t *d_text = nullptr, *d_mask = nullptr;
+        rc = pieces_.splitter ? MBPE_OK : mbpe_splitter_create(pieces_.device, pattern_.c_str(), &pieces_.splitter);
+        if (rc == MBPE_OK) rc = mbpe_splitter_set_option(pieces_.splitter, "unicode", split_unicode_ ? 1 : 0);
+        if (rc == MBPE_OK) rc = mbpe_splitter_split(pieces_.splitter, bytes, n, 0, nullptr, nullptr, 0, &n_chunks);
+        if (rc == MBPE_OK) rc = mbpe_splitter_endmask(pieces_.splitter, &d_mask, nullptr, &d_text);
+        if (rc == MBPE_OK)
+            rc = mbpe_wordcount_add_endmask(pieces_.wc, n ? d_text : nullptr, n, n ? d_mask : nullptr, repeat, &n_unique,
+                                            nullptr);
+    } else {
+        // the chunks packed, as Tokenizer::train hands them to the deduper; without a pattern the piece is one chunk
+        std::vector<uint64_t> off(1, 0);
+        std::string packed;
+        const bool chunked = splitter_.has_pattern();
+        if (chunked) {
+            std::vector<uint64_t> starts, ends;
+            std::string err;
+            if (splitter_.split(bytes, n, &starts, &ends, &err) != MBPE_OK) throw std::runtime_error(err);
+            for (size_t i = 0; i < starts.size(); ++i) {
+                packed.append(text + starts[i], ends[i] - starts[i]);
+                off.push_back(packed.size());
+            }
+        } else {
+            off.push_back(n);
+        }
+        n_chunks = off.size() - 1;
+        rc = mbpe_wordcount_add(pieces_.wc, chunked ? reinterpret_cast<const uint8_t *>(packed.data()) : bytes,
+                                chunked ? packed.size() : n, 0, off.data(), n_chunks, repeat, &n_unique, nullptr);
+    }
+    if (rc != MBPE_OK) throw CodedError(rc, mbpe_last_error());
+    pieces_.n_chunks += n_chunks * repeat;
+    pieces_.n_bytes += n * repeat;
+}
+
+void Tokenizer::train_pieces_finish(int vocab_size, CONFLICT_RESOLUTION conflict_resolution, bool verbose, bool resume) {
+    if (!pieces_.open) throw CodedError(MBPE_ERR_STATE, "train_pieces_finish: no session is open (train_pieces_begin)");
+    // the session ends here, however this goes; the merges stay as they are until the training has succeeded
+    struct Close {
+        Tokenizer *t;
+        ~Close() { t->train_pieces_abort(); }
+    } close{this};
+    const std::vector<uint32_t> prior = training_prior(vocab_size, resume);
+    if (verbose) std::cout << "Split input text into " << pieces_.n_chunks << " chunks\n";
+    uint64_t n_unique = 0, n_unique_bytes = 0;
+    int rc = mbpe_wordcount_stats(pieces_.wc, nullptr, nullptr, &n_unique, &n_unique_bytes);
+    mbpe_ctx *ctx = nullptr;
+    if (rc == MBPE_OK) rc = mbpe_create(pieces_.device, &ctx);
+    std::vector<uint32_t> weights(n_unique);
+    if (rc == MBPE_OK && pieces_.device_split) {
+        // the table is loaded where it lies
+        const uint8_t *u_text = nullptr, *u_mask = nullptr;
+        const uint32_t *u_weights = nullptr;
+        rc = mbpe_wordcount_result(pieces_.wc, &u_text, &u_mask, &u_weights, nullptr);
+        if (rc == MBPE_OK)
+            rc = mbpe_load_corpus_endmask_weighted(ctx, u_text, n_unique_bytes, 1, u_mask, u_weights, n_unique, 1);
+        if (rc == MBPE_OK && verbose)
+            rc = mbpe_wordcount_get(pieces_.wc, nullptr, nullptr, weights.data(), nullptr, 0, n_unique);
+    } else if (rc == MBPE_OK) {
+        // the unique chunks come back once, so that the NUL rule is applied as ever
+        std::vector<uint8_t> u_text(n_unique_bytes + 1);
+        std::vector<uint64_t> u_off(n_unique + 1, 0);
+        rc = mbpe_wordcount_get(pieces_.wc, u_text.data(), u_off.data(), weights.data(), nullptr, n_unique_bytes, n_unique);
+        if (rc == MBPE_OK)
+            rc = mbpe_load_corpus_weighted(ctx, u_text.data(), n_unique_bytes, u_off.data(), n_unique, 0, weights.data());
+    }
+    Trained tr;
+    rc = run_training(ctx, rc, vocab_size, conflict_resolution, prior, verbose ? &weights : nullptr, &tr);
+    const std::string msg = rc == MBPE_OK ? "" : mbpe_last_error();
+    if (ctx) mbpe_destroy(ctx);             // (the table's text was in use until here)
+    if (rc != MBPE_OK) throw CodedError(rc, msg);
+    const uint64_t n_bytes = pieces_.n_bytes;
+    clear_model();
+    adopt_training(tr, vocab_size, n_prior_of(prior), verbose, n_bytes);
 }
 
 // :605-650
@@ -924,6 +1046,23 @@ int guarded(F f) {
         return MBPE_ERR_ARG;
     }
 }
+template <typename F>
+int coded(F f) {                                     // a CodedError's own code, MBPE_ERR_ARG for anything else
+    try {
+        f();
+        return MBPE_OK;
+    } catch (const mbpe_host::CodedError &e) {
+        mbpe_host::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        mbpe_host::set_last_error(e.what());
+        return MBPE_ERR_ARG;
+    }
+}
+int null_argument(const char *who) {
+    mbpe_host::set_last_error(std::string(who) + ": NULL argument");
+    return MBPE_ERR_ARG;
+}
 }  // namespace
 
 extern "C" {
@@ -993,6 +1132,31 @@ int mbpe_tok_train_continue(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, 
         mbpe_host::set_last_error(e.what());
         return MBPE_ERR_ARG;
     }
+}
+
+int mbpe_tok_train_pieces_begin(mbpe_tokenizer *t, int device_id, int device_split) {
+    if (!t) return null_argument("mbpe_tok_train_pieces_begin");
+    return coded([&] { t->t->train_pieces_begin(device_id, device_split != 0); });
+}
+
+int mbpe_tok_train_pieces_add(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, uint32_t repeat) {
+    if (!t || (!text && n)) return null_argument("mbpe_tok_train_pieces_add");
+    return coded([&] { t->t->train_pieces_add(reinterpret_cast<const char *>(text), n, repeat); });
+}
+
+int mbpe_tok_train_pieces_finish(mbpe_tokenizer *t, uint32_t vocab_size, int conflict_resolution, int verbose, int resume) {
+    if (!t) return null_argument("mbpe_tok_train_pieces_finish");
+    return coded([&] {
+        t->t->train_pieces_finish((int)vocab_size,
+                                  conflict_resolution ? mbpe_host::Tokenizer::LEXICAL : mbpe_host::Tokenizer::FIRST,
+                                  verbose != 0, resume != 0);
+    });
+}
+
+int mbpe_tok_train_pieces_abort(mbpe_tokenizer *t) {
+    if (!t) return null_argument("mbpe_tok_train_pieces_abort");
+    t->t->train_pieces_abort();
+    return MBPE_OK;
 }
 
 int mbpe_tok_set_encode_split(mbpe_tokenizer *t, int on_device) {

@@ -39,6 +39,17 @@ public:
     // prior + new merges.  Verbose prints the per-merge line of the new merges only.  Without merges: an ordinary train
     void train(const std::string &text, int vocab_size, CONFLICT_RESOLUTION conflict_resolution, bool verbose,
                int device = 0, bool device_split = false, bool resume = false);
+    // The same training on a corpus that arrives in pieces (mbpe_tok_train_pieces_*): begin opens a session on `device`
+    // with a device word count (mbpe_wordcount_*); add splits a piece as train()
+    // does -- on the host into packed chunks, or on the device, where neither text nor mask returns -- and counts its
+    // chunks `repeat` times; finish loads the table into a fresh context (in place after the device split, through
+    // mbpe_load_corpus_weighted and its NUL rule after the host split) and runs the tail of train().  The merges are
+    // untouched until finish has succeeded; after finish or abort the session's device objects are gone.  Errors are
+    // CodedError: MBPE_ERR_STATE for a call out of order, otherwise the code of the call that failed
+    void train_pieces_begin(int device, bool device_split);
+    void train_pieces_add(const char *text, uint64_t n, uint32_t repeat);
+    void train_pieces_finish(int vocab_size, CONFLICT_RESOLUTION conflict_resolution, bool verbose, bool resume);
+    void train_pieces_abort();
     // :653-722; device >= 0 runs internal_encode (:325-377) on that HIP device instead of the host.
     // device_split (with device >= 0, here and in the batch calls below): the text is also cut at the special tokens
     // and split into chunks on the device (mbpe_splitter_split_docs with a splitter that is kept), and the encoder
@@ -130,6 +141,23 @@ private:
     std::vector<Token> encode_rank_ordered(std::vector<Token> text, uint64_t base) const;
     void check_dropout_order() const;      // throws CodedError(MBPE_ERR_ARG): dropout with the greedy order
     void rebuild_vocab();
+    // the tail every training route shares.  training_prior: the checks of a training up to vocab_size and, with
+    // resume, the merges it continues from (nothing is changed); clear_model: back to the 256 bytes; run_training: with
+    // the corpus loaded into ctx (rc: the load's code, handed through when it failed) the options, the begin, the steps
+    // and the result -- weights (optional): the loaded chunks' weights, with which the stream's length becomes the whole
+    // corpus's; adopt_training: the vocab bookkeeping and the verbose lines
+    struct Trained {
+        std::vector<uint32_t> flat;
+        std::vector<int32_t> had;
+        uint32_t n_merges = 0;
+        mbpe_stats st;
+    };
+    static uint32_t n_prior_of(const std::vector<uint32_t> &prior) { return static_cast<uint32_t>(prior.size() / 2); }
+    std::vector<uint32_t> training_prior(int vocab_size, bool resume) const;
+    void clear_model();
+    int run_training(mbpe_ctx *ctx, int rc, int vocab_size, CONFLICT_RESOLUTION conflict_resolution,
+                     const std::vector<uint32_t> &prior, const std::vector<uint32_t> *weights, Trained *out);
+    void adopt_training(const Trained &tr, int vocab_size, uint32_t n_prior, bool verbose, uint64_t text_length);
     void drop_decoder();                   // the merges or the specials changed
     void drop_encoder();                   // the merges changed (special tokens do not enter the lookup table)
     // the chunks of n_docs texts (every text split on its own) as one buffer + offsets; first_chunk[i] = text i's first
@@ -172,6 +200,13 @@ private:
     int encoder_device_ = -1;
     mbpe_splitter *dev_splitter_ = nullptr;  // the device split of encode(..., device, device_split)
     int dev_splitter_device_ = -1;
+    struct PieceSession {                    // train_pieces_*
+        bool open = false, device_split = false;
+        int device = 0;
+        mbpe_wordcount *wc = nullptr;
+        mbpe_splitter *splitter = nullptr;
+        uint64_t n_chunks = 0, n_bytes = 0;  // what the verbose lines report: chunks and bytes, repeats included
+    } pieces_;
     bool encode_split_ = false;
     bool split_unicode_ = false;
     bool train_dedup_ = false;

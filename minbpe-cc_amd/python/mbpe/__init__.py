@@ -44,6 +44,9 @@ EXPORTS = [
     "mbpe_dedup_get", "mbpe_dedup_set_option", "mbpe_dedup_kernel_ms", "mbpe_dedup_alloc_count",
     "mbpe_load_corpus_weighted", "mbpe_load_corpus_endmask_weighted",
     "mbpe_dedup_map", "mbpe_dedup_get_map", "mbpe_encoder_dedup_stats",
+    "mbpe_wordcount_create", "mbpe_wordcount_destroy", "mbpe_wordcount_add_endmask", "mbpe_wordcount_add",
+    "mbpe_wordcount_result", "mbpe_wordcount_get", "mbpe_wordcount_stats", "mbpe_wordcount_reset",
+    "mbpe_wordcount_set_option", "mbpe_wordcount_kernel_ms", "mbpe_wordcount_alloc_count",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -54,7 +57,8 @@ TOK_EXPORTS = [
     "mbpe_tok_train_split_device", "mbpe_tok_set_encode_split", "mbpe_tok_set_split_unicode",
     "mbpe_tok_set_encode_order", "mbpe_tok_train_continue", "mbpe_tok_encode_byteoff",
     "mbpe_tok_encode_batch_byteoff_device", "mbpe_tok_set_encode_dropout", "mbpe_tok_set_train_dedup",
-    "mbpe_tok_set_encode_dedup",
+    "mbpe_tok_set_encode_dedup", "mbpe_tok_train_pieces_begin", "mbpe_tok_train_pieces_add",
+    "mbpe_tok_train_pieces_finish", "mbpe_tok_train_pieces_abort",
 ]
 
 
@@ -260,6 +264,22 @@ def lib():
     L.mbpe_dedup_get_map.argtypes = [vp, vp, u64, vp]
     L.mbpe_encoder_dedup_stats.argtypes = [vp, vp, vp, vp, vp, vp]
     L.mbpe_tok_set_encode_dedup.argtypes = [vp, i32]
+    L.mbpe_wordcount_create.argtypes = [i32, ctypes.POINTER(vp)]
+    L.mbpe_wordcount_destroy.argtypes = [vp]
+    L.mbpe_wordcount_destroy.restype = None
+    L.mbpe_wordcount_add_endmask.argtypes = [vp, vp, u64, vp, u32, vp, vp]
+    L.mbpe_wordcount_add.argtypes = [vp, vp, u64, i32, vp, u64, u32, vp, vp]
+    L.mbpe_wordcount_result.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    L.mbpe_wordcount_get.argtypes = [vp, vp, vp, vp, vp, u64, u64]
+    L.mbpe_wordcount_stats.argtypes = [vp, vp, vp, vp, vp]
+    L.mbpe_wordcount_reset.argtypes = [vp]
+    L.mbpe_wordcount_set_option.argtypes = [vp, ctypes.c_char_p, i64]
+    L.mbpe_wordcount_kernel_ms.argtypes = [vp, vp]
+    L.mbpe_wordcount_alloc_count.argtypes = [vp, vp]
+    L.mbpe_tok_train_pieces_begin.argtypes = [vp, i32, i32]
+    L.mbpe_tok_train_pieces_add.argtypes = [vp, vp, u64, u32]
+    L.mbpe_tok_train_pieces_finish.argtypes = [vp, u32, i32, i32, i32]
+    L.mbpe_tok_train_pieces_abort.argtypes = [vp]
     L.mbpe_load_corpus_weighted.argtypes = [vp, vp, u64, vp, u64, i32, vp]
     L.mbpe_load_corpus_endmask_weighted.argtypes = [vp, vp, u64, i32, vp, vp, u64, i32]
     L.mbpe_tok_set_encode_order.argtypes = [vp, i32]
@@ -1179,6 +1199,104 @@ class Deduper:
         return n.value
 
 
+class WordCount:
+    """One mbpe_wordcount: the distinct chunks of a corpus that is added piece by piece, in order of first occurrence
+    over all pieces, with their counts -- one dedup of the pieces' chunk lists laid end to end."""
+
+    def __init__(self, device=0):
+        self._h = ctypes.c_void_p()
+        _check(lib().mbpe_wordcount_create(device, ctypes.byref(self._h)))
+        self._keep = None
+        self.n_unique = self.n_unique_bytes = 0
+
+    def close(self):
+        if self._h:
+            lib().mbpe_wordcount_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_option(self, name, value):
+        """"max_chunk_bytes", "hash_bits": the owned deduper's; MbpeError(ERR_STATE) once a piece has been added."""
+        _check(lib().mbpe_wordcount_set_option(self._h, name.encode(), int(value)))
+
+    def _done(self, rc, nu, nb):
+        _check(rc)
+        self.n_unique, self.n_unique_bytes = nu.value, nb.value
+        return nu.value, nb.value
+
+    def add(self, data, chunk_off, repeat=1, text_ptr=None, n_bytes=None):
+        """One piece: the chunks data[chunk_off[c]:chunk_off[c + 1]] (host bytes, or n_bytes of device memory at
+        text_ptr), counted `repeat` times -> the table's (n_unique, n_unique_bytes) after it."""
+        off = np.ascontiguousarray(chunk_off, dtype=np.uint64)
+        if text_ptr is None:
+            text = _u8(data)
+            ptr, n, on_dev = (text.ctypes.data if len(text) else None), len(text), 0
+        else:
+            text, ptr, n, on_dev = None, ctypes.c_void_p(text_ptr), n_bytes, 1
+        self._keep = (text, off)
+        nu, nb = ctypes.c_uint64(), ctypes.c_uint64()
+        return self._done(lib().mbpe_wordcount_add(self._h, ptr, n, on_dev, off.ctypes.data, len(off) - 1, repeat,
+                                                   ctypes.byref(nu), ctypes.byref(nb)), nu, nb)
+
+    def add_endmask(self, text_ptr, n_bytes, mask_ptr, repeat=1):
+        """One piece: n_bytes of device text at text_ptr with the end mask at mask_ptr (Splitter.endmask), both read in
+        place, counted `repeat` times -> the table's (n_unique, n_unique_bytes) after it."""
+        nu, nb = ctypes.c_uint64(), ctypes.c_uint64()
+        return self._done(lib().mbpe_wordcount_add_endmask(self._h, ctypes.c_void_p(text_ptr) if text_ptr else None, n_bytes,
+                                                           ctypes.c_void_p(mask_ptr) if mask_ptr else None, repeat,
+                                                           ctypes.byref(nu), ctypes.byref(nb)), nu, nb)
+
+    def result(self):
+        """Device addresses (text, end mask, weights u32, first_chunk u64) of the table, owned by the object and valid
+        until its next add or reset: Trainer.load_corpus_endmask_weighted takes them as they are."""
+        t, m, w, f = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        _check(lib().mbpe_wordcount_result(self._h, ctypes.byref(t), ctypes.byref(m), ctypes.byref(w), ctypes.byref(f)))
+        return t.value, m.value, w.value, f.value
+
+    def get(self):
+        """Host copies of the table -> (text bytes, chunk_off uint64 [n_unique + 1], weights uint32, first_chunk uint64)."""
+        nb, nu = self.n_unique_bytes, self.n_unique
+        text = np.zeros(max(nb, 1), dtype=np.uint8)
+        off = np.zeros(nu + 1, dtype=np.uint64)
+        w = np.zeros(max(nu, 1), dtype=np.uint32)
+        f = np.zeros(max(nu, 1), dtype=np.uint64)
+        _check(lib().mbpe_wordcount_get(self._h, text.ctypes.data, off.ctypes.data, w.ctypes.data, f.ctypes.data, nb, nu))
+        return text[:nb].tobytes(), off, w[:nu], f[:nu]
+
+    def stats(self):
+        """-> dict: n_pieces, n_chunks_total (repeats included), n_unique, n_unique_bytes."""
+        v = [ctypes.c_uint64() for _ in range(4)]
+        _check(lib().mbpe_wordcount_stats(self._h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("n_pieces", "n_chunks_total", "n_unique", "n_unique_bytes"), (x.value for x in v)))
+
+    def reset(self):
+        """Empty again; the device buffers are kept."""
+        _check(lib().mbpe_wordcount_reset(self._h))
+        self.n_unique = self.n_unique_bytes = 0
+
+    def kernel_ms(self):
+        """Device time of the latest add: the deduper's kernels and the fold's."""
+        ms = ctypes.c_float()
+        _check(lib().mbpe_wordcount_kernel_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def alloc_count(self):
+        n = ctypes.c_uint64()
+        _check(lib().mbpe_wordcount_alloc_count(self._h, ctypes.byref(n)))
+        return n.value
+
+
 class Trainer:
     """One mbpe_ctx.  Mirrors the order of Tokenizer::train (Tokenizer.h:489-598)."""
 
@@ -1477,6 +1595,37 @@ class Tokenizer:
         fn = lib().mbpe_tok_train_split_device if device_split else lib().mbpe_tok_train
         _check(fn(self._h, text.ctypes.data if len(text) else None, len(text), vocab_size, conflict_resolution,
                   int(verbose), device))
+
+    def train_from_iterator(self, texts, vocab_size, conflict_resolution=1, verbose=False, device=0, device_split=False,
+                            resume=False, repeats=None):
+        """Train on a corpus that arrives in pieces (mbpe_tok_train_pieces_*): every text is split on its own and its
+        chunks are counted on the device (mbpe_wordcount_*), then the training runs on the table -- the merges of a
+        training on the pieces' chunk lists laid end to end, for both tie-breaks, with one piece in host memory at a
+        time.  A piece boundary is a chunk boundary: to get a whole file's result, cut it where a letter or digit is
+        followed by whitespace.  repeats: one count per text (default 1), the text counted that many times.
+        device_split, resume: as for train().  The tokenizer's merges stay as they are until the training has
+        succeeded; the session is aborted when the iterator or a call raises."""
+        _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
+        _check(lib().mbpe_tok_train_pieces_begin(self._h, device, int(bool(device_split))))
+        try:
+            reps = None if repeats is None else iter(repeats)
+            for data in texts:
+                text = _u8(data)
+                rep = 1 if reps is None else int(next(reps))
+                _check(lib().mbpe_tok_train_pieces_add(self._h, text.ctypes.data if len(text) else None, len(text), rep))
+            _check(lib().mbpe_tok_train_pieces_finish(self._h, vocab_size, conflict_resolution, int(verbose),
+                                                      int(bool(resume))))
+        except BaseException:
+            lib().mbpe_tok_train_pieces_abort(self._h)
+            raise
+
+    def train_files(self, paths, vocab_size, **kw):
+        """train_from_iterator over the files' contents, read one at a time."""
+        def read():
+            for p in paths:
+                with open(p, "rb") as f:
+                    yield f.read()
+        self.train_from_iterator(read(), vocab_size, **kw)
 
     def set_merges(self, merges):
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1, 2)
