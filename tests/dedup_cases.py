@@ -47,15 +47,18 @@ def end_mask(off, n_bytes):
     return mask
 
 
-def weighted_bpe(chunks, weights, vocab_size, first_mode):
+def weighted_bpe(chunks, weights, vocab_size, first_mode, start=None, with_seqs=False):
     """BPE on chunks with weights -> (merges, counts).
     Lexical: one table, counted once and then updated by every merge as the reference's walk does -- (a, b) - w,
     (x, a) - w, (x, X) + w with x the left neighbour as already rewritten, (b, y) - w, (X, y) + w with y the right
     neighbour as it still is; a pair stays in the table at count 0.  The choice is the largest weighted count, then the
     smallest (first, second), until the vocabulary is full.
     first: the table is recounted before every merge; among the pairs of maximal weighted count the one whose first
-    occurrence in the stream of chunks is earliest wins; the loop ends when no pair is left."""
-    seqs = [list(c) for c in chunks]
+    occurrence in the stream of chunks is earliest wins; the loop ends when no pair is left.
+    start: token sequences that already hold ids 256 .. 255 + n in place of `chunks` as bytes, as (sequences, n) -- the
+    training continues from merge n, and the merges and counts returned are the new ones only.
+    with_seqs: -> (merges, counts, final token sequences)."""
+    seqs, k0 = ([list(c) for c in chunks], 0) if start is None else ([list(s) for s in start[0]], int(start[1]))
 
     def recount():
         cnt, pos = {}, {}
@@ -70,7 +73,7 @@ def weighted_bpe(chunks, weights, vocab_size, first_mode):
 
     tab, _ = recount()
     merges, counts = [], []
-    for k in range(vocab_size - 256):
+    for k in range(k0, vocab_size - 256):
         if first_mode:
             tab, pos = recount()
             if not tab:
@@ -106,7 +109,7 @@ def weighted_bpe(chunks, weights, vocab_size, first_mode):
                     out.append(s[i])
                     i += 1
             seqs[n] = out
-    return merges, counts
+    return (merges, counts, seqs) if with_seqs else (merges, counts)
 
 
 # ---- generators ------------------------------------------------------------------------------------------------------
