@@ -436,6 +436,32 @@ MBPE_API int mbpe_compact(mbpe_ctx *ctx);
  *                   MBPE_ERR_VOCAB, 1 = on 32-bit tokens (the mixed and direct cases of mbpe_train_begin_from); any
  *                   other value is MBPE_ERR_ARG.  Read by mbpe_train_begin_from; mbpe_train_from takes what the
  *                   context says; Tokenizer::train sets 1
+ *   "min_frequency", "max_token_length"
+ *                   the stopping rules of a training; both 0 (the default) = none, and every call does exactly what it
+ *                   does without them.  Read by mbpe_train_begin and mbpe_train_begin_from; mbpe_train, _train_lexical
+ *                   and _train_from take what the context says.
+ *                     "max_token_length" L: 0, or 2 .. 2^31 - 1 bytes.  A token's length is 1 for a byte and the sum of
+ *                       its halves' for a merge; the prior merges of a continued training count, whatever their length.
+ *                       A pair (a, b) is eligible iff len[a] + len[b] <= L.  Ineligible pairs stay in the stream and
+ *                       the table and are counted as ever; they are never chosen, never win a tie and do not make a
+ *                       unique eligible maximum a tie.
+ *                     "min_frequency" f: 0 .. 2^31 - 1, compared with the (weighted) pair count.
+ *                   Any other value is MBPE_ERR_ARG.  One step: M is the largest count among the eligible pairs; the
+ *                   training ends when no pair is eligible, when M < f, or (`first`, as ever) when M is 0; otherwise the
+ *                   tie-break chooses among the eligible pairs of count M.  The limits apply to the new merges only.  A
+ *                   training that ended reports fewer merges than vocab_size - 256 (mbpe_train_result), and
+ *                   mbpe_train_steps makes fewer steps, then 0.  With lexical and f = 0 an eligible pair of count 0 is
+ *                   chosen again and again, as without limits.
+ *                   With either option non-zero the training runs on 32-bit tokens (csrc/wide.h) from merge n_prior
+ *                   on, 0 included, like one on a corpus with chunk weights: weighted or not, either tie-break, any
+ *                   vocabulary up to MBPE_MAX_VOCAB_WIDE (beyond: MBPE_ERR_VOCAB); "wide_from", "first_wide",
+ *                   "resume_wide" and "chunk_barrier" play no part.  Several ranks, "force_exchange" included:
+ *                   MBPE_ERR_STATE.  The text is widened by the rank-ordered replay of mbpe_train_begin_from, so a
+ *                   corpus above the encoder's one-piece limit is MBPE_ERR_OOM.  The rules live in that loop's argmax,
+ *                   on the device; the 16-bit slot stream's batched selection does not know them.  So a limited training
+ *                   makes one pass over the loaded corpus per merge: load the distinct chunks with their counts
+ *                   (mbpe_dedup_*, mbpe_load_corpus_*_weighted), or it is correct and slow.  The route is never
+ *                   switched beyond this.  Device memory beside the loop's: 4 B per token id for the lengths.
  */
 MBPE_API int mbpe_set_option(mbpe_ctx *ctx, const char *name, int64_t value);
 

@@ -207,6 +207,20 @@ MBPE_API int mbpe_tok_set_split_unicode(mbpe_tokenizer *t, int on);
  * One rank.  A chunk above 256 bytes is never merged with its duplicates (it appears as often as it occurs). */
 MBPE_API int mbpe_tok_set_train_dedup(mbpe_tokenizer *t, int on);
 
+/* The stopping rules of the trainings from here on (mbpe_tok_train, _train_split_device, _train_continue,
+ * _train_pieces_finish, with and without mbpe_tok_set_train_dedup): the context options "min_frequency" and
+ * "max_token_length" of mbpe.h, 0 = off (the default).  min_frequency: 0 .. 2^31 - 1, the training ends when the best
+ * pair left occurs less often; max_token_length: 0, or 2 .. 2^31 - 1 bytes, no NEW token is longer -- the merges a
+ * continued training starts from stay, whatever their length.  Anything else is MBPE_ERR_ARG.  A training that ends
+ * early leaves fewer than vocab_size - 256 merges, as the `first` tie-break may.  The .model and .vocab formats are
+ * unchanged.
+ * With either set the training runs on the 32-bit loop from its first new merge, one merge per pass over the corpus
+ * it is given: combine it with mbpe_tok_set_train_dedup (or the piece-wise calls, which count words anyway), so that
+ * a pass runs over the distinct chunks only.  Without dedup the result is the same and every merge is a pass over the
+ * whole corpus; the route is not switched silently.  One rank; a corpus above the encoder's one-piece limit returns
+ * MBPE_ERR_OOM, as for mbpe_tok_train_continue. */
+MBPE_API int mbpe_tok_set_train_limits(mbpe_tokenizer *t, int64_t min_frequency, int64_t max_token_length);
+
 /* Encoding through the distinct chunks: 0 (the default) or 1; anything else is MBPE_ERR_ARG.  While it is on,
  * mbpe_tok_encode_device and the three batch calls (mbpe_tok_encode_batch_device, _batch_packed_device,
  * _batch_aux_device) run the kept device encoder with its option "dedup" (mbpe.h: the chunks are deduplicated on the

@@ -245,6 +245,9 @@ struct mbpe_ctx {
     int64_t opt_wide_from = -1;      // tests: hand over after this many merges whatever the vocabulary (-1: at the format's limit)
     int64_t opt_first_wide = 0;      // 1: a `first` training may continue on 32-bit tokens too (0: MBPE_ERR_VOCAB, as before)
     int64_t opt_resume_wide = 0;     // 1: mbpe_train_begin_from may continue on 32-bit tokens (0: MBPE_ERR_VOCAB, as before)
+    int64_t opt_min_frequency = 0;   // stopping rules (wide.h), read by the next begin: either non-zero and the training runs
+    int64_t opt_max_token_length = 0;   // on 32-bit tokens from its first new merge, like one on a weighted corpus
+    WideLimits wlim = {};            // ... what the training under way was begun with (wlim.len: vocab_total u32 of the pool)
     bool wide_direct = false;        // the training began on 32-bit tokens (wide_begin_from): no slot stream, no best[]
     std::vector<uint32_t> h_prior_raw;   // ... and its prior merges, (a, b) as given: their ids may need more than 16 bits
     WideTally *wtally = nullptr;         // ... and the census of its pair count
@@ -373,6 +376,8 @@ void free_training(mbpe_ctx *c) {
     tfree(c, c->wwt[0]); tfree(c, c->wwt[1]);
     tfree(c, c->wtab.keys); tfree(c, c->wtab.cnts); tfree(c, c->wctl); tfree(c, c->wbest); tfree(c, c->warg);
     tfree(c, c->wfs); tfree(c, c->wtally);
+    tfree(c, c->wlim.len);
+    c->wlim = {};
     c->wtab = {};
     c->wide_direct = false;
     c->h_prior_raw.clear();
@@ -504,6 +509,7 @@ int ensure_events(std::vector<hipEvent_t> &pool, size_t n) {
 inline uint32_t endbit_of(const mbpe_ctx *c) { return !c->chunked ? 0u : c->barrier ? kBarrier : kEndBit; }
 
 inline bool is_multi(const mbpe_ctx *c) { return c->n_ranks > 1 || c->opt_force_exchange; }
+inline bool is_limited(const mbpe_ctx *c) { return c->opt_min_frequency != 0 || c->opt_max_token_length != 0; }
 
 // ---- launch interface (mbpe_dev.h: StreamView, BatchView) ----
 // The builders below are the only places that read the context's stream and batch buffers for a launch.
@@ -647,6 +653,17 @@ int mbpe_set_option(mbpe_ctx *c, const char *name, int64_t value) {
     else if (n == "resume_wide") {                                             // (read by the next mbpe_train_begin_from)
         if (value != 0 && value != 1) { mbpe_host::set_last_error("resume_wide: 0 or 1"); return MBPE_ERR_ARG; }
         c->opt_resume_wide = value;
+    }
+    else if (n == "min_frequency") {                                           // (read by the next begin)
+        if (value < 0 || value > 0x7FFFFFFFll) { mbpe_host::set_last_error("min_frequency: 0 (off) .. 2^31 - 1"); return MBPE_ERR_ARG; }
+        c->opt_min_frequency = value;
+    }
+    else if (n == "max_token_length") {                                        // (likewise)
+        if (value != 0 && (value < 2 || value > 0x7FFFFFFFll)) {
+            mbpe_host::set_last_error("max_token_length: 0 (off), or 2 .. 2^31 - 1 bytes");
+            return MBPE_ERR_ARG;
+        }
+        c->opt_max_token_length = value;
     }
     else if (n == "pc_repeat") c->opt_pc_repeat = std::min<int64_t>(std::max<int64_t>(1, value), 1000);
     else { mbpe_host::set_last_error("unknown option " + n); return MBPE_ERR_ARG; }
@@ -1615,7 +1632,7 @@ int mbpe_train_begin(mbpe_ctx *c, uint32_t vocab_size) {
     if (!c) return MBPE_ERR_ARG;
     if (!c->loaded) { mbpe_host::set_last_error("mbpe_train_begin: no corpus loaded"); return MBPE_ERR_STATE; }
     if (vocab_size < 256) { mbpe_host::set_last_error("vocab_size must be >= 256"); return MBPE_ERR_ARG; }
-    if (c->weighted) return weighted_begin(c, vocab_size, nullptr, 0);
+    if (c->weighted || is_limited(c)) return weighted_begin(c, vocab_size, nullptr, 0);
     const uint32_t vmax = !c->chunked ? MBPE_MAX_VOCAB_BASIC : c->opt_barrier == 0 ? MBPE_MAX_VOCAB_ENDBIT : MBPE_MAX_VOCAB_CHUNKED;
     c->barrier = c->chunked && (c->opt_barrier == 1 || (c->opt_barrier != 0 && vocab_size > MBPE_MAX_VOCAB_ENDBIT));
     // Beyond the 16-bit slot format (Token is a uint32_t in the reference, Tokenizer.h:37-38) the training runs its first
@@ -1730,7 +1747,7 @@ int mbpe_train_begin_from(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prio
     }
     int rc = mbpe_merges_check(prior_merges, n_prior);
     if (rc != MBPE_OK) return rc;
-    if (c->weighted) return weighted_begin(c, vocab_size, prior_merges, n_prior);
+    if (c->weighted || is_limited(c)) return weighted_begin(c, vocab_size, prior_merges, n_prior);
     if (is_multi(c)) {
         mbpe_host::set_last_error("mbpe_train_begin_from: continuing from existing merges runs on one rank only");
         return MBPE_ERR_STATE;
@@ -1811,9 +1828,11 @@ int mbpe_train_begin_from(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prio
 // A corpus with chunk weights trains on 32-bit tokens from merge n_prior on (0 included), whatever the vocabulary and
 // either tie-break: the text widened by the replay (an empty prior table leaves the bytes as tokens), then the route
 // of the direct continuation.  "wide_from", "first_wide", "resume_wide" and "chunk_barrier" play no part.
+// So does any corpus under a stopping rule ("min_frequency", "max_token_length"): the rules live in that loop's argmax.
 static int weighted_begin(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prior, uint32_t n_prior) {
     if (is_multi(c)) {
-        mbpe_host::set_last_error("a corpus with chunk weights trains on one rank only");
+        mbpe_host::set_last_error(c->weighted ? "a corpus with chunk weights trains on one rank only"
+                                              : "a training with min_frequency or max_token_length runs on one rank only");
         return MBPE_ERR_STATE;
     }
     if (vocab_size > MBPE_MAX_VOCAB_WIDE) {
@@ -2181,6 +2200,25 @@ static int wide_convert(mbpe_ctx *c) {
     return MBPE_OK;
 }
 
+// The stopping rules of the training that begins (wide.h): the options as they stand, and for a length limit the
+// lengths of the bytes and of the prior merges -- which count, whatever their length; the limits apply to the new
+// merges only.  The entries of the new tokens are written by the loop.
+static int wide_begin_limits(mbpe_ctx *c, const uint32_t *prior, uint32_t n_prior) {
+    c->wlim = WideLimits{};
+    c->wlim.min_count = (int32_t)c->opt_min_frequency;
+    c->wlim.new_id_base = 256 + n_prior;
+    if (!c->opt_max_token_length) return MBPE_OK;
+    std::vector<uint32_t> len((size_t)c->vocab_total, 0u);
+    for (uint32_t i = 0; i < 256 && i < c->vocab_total; ++i) len[i] = 1;
+    for (uint32_t k = 0; k < n_prior; ++k)      // (mbpe_merges_check: both halves exist before merge k)
+        len[256 + k] = (uint32_t)std::min<uint64_t>((uint64_t)len[prior[2 * k]] + len[prior[2 * k + 1]], kWideLenMax);
+    HIPCHK(tmalloc(c, &c->wlim.len, len.size() * 4));
+    HIPCHK(hipMemcpyAsync(c->wlim.len, len.data(), len.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->wlim.max_len = (uint32_t)c->opt_max_token_length;
+    return MBPE_OK;
+}
+
 // A training that continues from so many merges that no slot stream can hold their ids: the replay's tokens (*tok,
 // n_tok of them in an array of the caller's, which is freed here once they are copied) ARE the 32-bit stream, the
 // 64-bit-key table is counted from them, and the 32-bit loop runs from merge n_prior.  The table is allocated before
@@ -2213,6 +2251,10 @@ static int wide_begin_from(mbpe_ctx *c, uint32_t vocab_size, uint32_t **tok, uin
         HIPCHK(tmalloc(c, &c->wwt[0], std::max<uint64_t>(n_tok, 1) * 4));
         HIPCHK(tmalloc(c, &c->wwt[1], std::max<uint64_t>(n_tok, 1) * 4));
         launch_wide_token_weights(c->stream, c->wtok[0], n_tok, c->d_weights, c->n_weights, c->wwt[0], c->wscratch, c->wctl);
+    }
+    if (is_limited(c)) {
+        rc = wide_begin_limits(c, prior, n_prior);
+        if (rc != MBPE_OK) return rc;
     }
     const uint64_t ids = 256ull + n_prior;
     const uint64_t most = std::min<uint64_t>({n_tok ? n_tok - 1 : 0, ids * ids, 1ull << 30});
@@ -2272,10 +2314,10 @@ static int wide_steps(mbpe_ctx *c, uint32_t n_steps, uint32_t *done_out) {
         HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->wctl->k_limit), (int)(c->wk + group), 1, c->stream));
         HIPCHK(hipEventRecord(c->ev0, c->stream));
         for (uint32_t g = 0; g < group; ++g) {
-            launch_wide_argmax(c->stream, c->wtab, c->wctl, c->wbest, c->warg);
+            launch_wide_argmax(c->stream, c->wtab, c->wctl, c->wbest, c->warg, c->wlim);
             if (c->wfirst)
                 launch_wide_first(c->stream, c->wtok[c->wcur ^ (g & 1)], c->wn_upper, c->wtab, c->wctl, c->wbest, c->warg,
-                                  c->wfs);
+                                  c->wfs, c->wlim);
             launch_wide_merge(c->stream, c->wtok[c->wcur ^ (g & 1)], c->wtok[c->wcur ^ (g & 1) ^ 1], c->wn_upper, c->wval,
                               c->wscratch, c->wtab, c->wctl, 256 + c->n_target, c->wwt[c->wcur ^ (g & 1)],
                               c->wwt[c->wcur ^ (g & 1) ^ 1]);

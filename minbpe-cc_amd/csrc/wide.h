@@ -49,6 +49,22 @@
 // occurrence of its chunk (an earlier copy of the chunk would hold the pair too), so the tied pairs' first positions
 // keep their order.
 //
+// STOPPING RULES (the options "min_frequency" and "max_token_length" of mbpe.h).  A training that began here may carry
+// a WideLimits: the pairs the argmax may choose are the ELIGIBLE ones, len[a] + len[b] <= max_len with len[] the tokens'
+// lengths in bytes, and the loop ends (ctl->live = 0, as on an empty table) when no pair is eligible or the largest
+// eligible count lies below min_count.  Ineligible pairs stay in the stream and the table and are counted as ever.
+//   len[]  one u32 per token id below the training's vocab_size, SATURATING at kWideLenMax = 2^31 - 1 (a prior merge
+//          may be longer than any text; max_len is below 2^31, so a saturated token is in no eligible pair, and the
+//          sum of two entries never wraps).  The host fills bytes and prior merges; the entry of id 256 + k is written
+//          on the device where ctl->a, b of merge k are final: k_wide_argmax_final (lexical), k_wide_first_pick (`first`)
+//   where  eligibility is decided in the scans, not at insert time.  It is a property of the key alone, but the table
+//          has no room for it (64-bit keys that every probe compares, 32-bit counts whose every bit counts), and the
+//          four inserts of a match would each pay two gathers.  The argmax tests a pair only once it beats the
+//          thread's best so far, the gather and the position search only pairs whose count is M: a handful of 4-byte
+//          gathers per thread from an array of 4 B per token id, which stays in L2 beside the 12 B per entry streamed
+//   kernels are templates on "limited": the unlimited instantiations are the code they were, and a training without
+//          limits launches exactly those
+//
 // One GPU, either tie-break.  Slower per merge than the 16-bit path (one merge per pass, ~20 B of traffic per token),
 // but it turns MBPE_ERR_VOCAB into a training for GPT-4-size vocabularies.
 #ifndef MBPE_WIDE_H
@@ -105,6 +121,15 @@ struct WideFirst {
     uint32_t bitmap[kWideFirstBitmapWords];
 };
 
+// stopping rules of a training (see above); all zero: none
+constexpr uint32_t kWideLenMax = 0x7FFFFFFFu;
+struct WideLimits {
+    uint32_t *len;                 // NULL: no length limit; else the byte length of every token id, saturating
+    uint32_t max_len;              // a pair is eligible iff len[a] + len[b] <= max_len
+    int32_t min_count;             // the loop ends when the largest eligible count is below this
+    uint32_t new_id_base;          // len[new_id_base + ctl->k] receives the length of the merge under way
+};
+
 // best[k] of the wide loop: count, first, second
 struct WideBest { int32_t count; uint32_t first, second, pad; };
 
@@ -135,12 +160,14 @@ void launch_wide_token_weights(hipStream_t s, const uint32_t *tok, uint64_t n_to
                                uint64_t n_weights, uint32_t *wt, uint32_t *span_scratch, WideCtl *ctl);
 // flag[0] |= 1 when one of the n device weights lies outside 1 .. 2^31 - 1
 void launch_wide_check_weights(hipStream_t s, const uint32_t *weights, uint64_t n, uint32_t *flag);
-// argmax -> ctl->a, b, count, live and best[ctl->k]; clears ctl->ran
-void launch_wide_argmax(hipStream_t s, WideTable t, WideCtl *ctl, WideBest *best, unsigned long long *scratch /* 3 * 1024 */);
+// argmax -> ctl->a, b, count, live and best[ctl->k]; clears ctl->ran.  lim: the stopping rules (all zero: none)
+void launch_wide_argmax(hipStream_t s, WideTable t, WideCtl *ctl, WideBest *best, unsigned long long *scratch /* 3 * 1024 */,
+                        WideLimits lim = WideLimits{});
 // `first` mode, after launch_wide_argmax (same scratch): among the pairs of the maximal count the one whose first
-// occurrence in the stream src (ctl->n tokens, at most n_upper) comes first replaces ctl->a, b and best[ctl->k]
+// occurrence in the stream src (ctl->n tokens, at most n_upper) comes first replaces ctl->a, b and best[ctl->k].
+// lim: what launch_wide_argmax was given
 void launch_wide_first(hipStream_t s, const uint32_t *src, uint64_t n_upper, WideTable t, WideCtl *ctl, WideBest *best,
-                       const unsigned long long *scratch, WideFirst *fs);
+                       const unsigned long long *scratch, WideFirst *fs, WideLimits lim = WideLimits{});
 // one merge (ctl->a, ctl->b) -> new_id_base + ctl->k over the stream src (ctl->n tokens, at most n_upper) into dst;
 // advances ctl->k, sets ctl->n.  Does nothing when ctl->k >= ctl->k_limit or the table is empty.
 // wsrc / wdst: NULL, or the weights of the tokens of src and the array that receives those of dst.

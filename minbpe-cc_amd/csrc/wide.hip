@@ -224,9 +224,26 @@ __device__ Cand128 block_best(Cand128 v, Cand128 *sh) {
     return r;
 }
 
+// ---- stopping rules (wide.h): which pairs the argmax may choose ------------------------------------------------------
+// len[a] + len[b] <= max_len; the entries saturate at kWideLenMax, so the sum does not wrap.  Every id of a key in the
+// table or of a token in the stream lies below the training's vocab_size, which is how many entries len[] has.
+__device__ __forceinline__ bool wide_eligible(const uint32_t *__restrict__ len, uint32_t max_len, unsigned long long key) {
+    return len[(uint32_t)(key >> 32)] + len[(uint32_t)key] <= max_len;
+}
+// the length of the token that the merge under way makes, once ctl->a, b are final
+__device__ __forceinline__ void wide_new_len(const WideLimits &lim, const WideCtl *ctl) {
+    const uint32_t l = lim.len[ctl->a] + lim.len[ctl->b];
+    lim.len[lim.new_id_base + ctl->k] = l < kWideLenMax ? l : kWideLenMax;
+}
+
 constexpr int kArgBlocks = 1024;
+// LIM: only eligible pairs.  A pair is tested once it beats the thread's best so far, so the two gathers of the test
+// are paid a few times per thread, not per entry (unless ineligible pairs lead the table, where every leader is
+// tested once).
+template <bool LIM>
 __global__ __launch_bounds__(256) void k_wide_argmax_partial(WideTable t, const WideCtl *ctl,
-                                                             unsigned long long *__restrict__ part) {
+                                                             unsigned long long *__restrict__ part,
+                                                             const uint32_t *__restrict__ len, uint32_t max_len) {
     __shared__ Cand128 sh[4];
     Cand128 v = {-1, 0};
     if (ctl->k < ctl->k_limit) {
@@ -236,15 +253,18 @@ __global__ __launch_bounds__(256) void k_wide_argmax_partial(WideTable t, const 
             const unsigned long long k = t.keys[i];
             if (k == kWideEmpty) continue;
             Cand128 c = {(long long)t.cnts[i], ~k};
-            if (better(c, v)) v = c;
+            if (better(c, v) && (!LIM || wide_eligible(len, max_len, k))) v = c;
         }
     }
     v = block_best(v, sh);
     if (threadIdx.x == 0) { part[2 * blockIdx.x] = (unsigned long long)v.count; part[2 * blockIdx.x + 1] = v.nkey; }
 }
 
+// LIM: the loop also ends when the best eligible count lies below lim.min_count (no eligible pair: the partials hold
+// count -1, as for an empty table), and in lexical mode the new token's length is noted (`first`: k_wide_first_pick)
+template <bool LIM>
 __global__ __launch_bounds__(kArgBlocks) void k_wide_argmax_final(const unsigned long long *__restrict__ part,
-                                                                  WideCtl *ctl, WideBest *best) {
+                                                                  WideCtl *ctl, WideBest *best, WideLimits lim) {
     __shared__ Cand128 sh[kArgBlocks / kWave];
     if (threadIdx.x == 0) ctl->ran = 0;        // (whatever follows: no scatter without a merge of its own)
     if (ctl->k >= ctl->k_limit) return;
@@ -253,7 +273,8 @@ __global__ __launch_bounds__(kArgBlocks) void k_wide_argmax_final(const unsigned
     if (threadIdx.x == 0) {
         // (a count can never be negative: every decrement undoes an increment.  `first`: a rebuilt table holds no
         //  zero-count pair, so M = 0 ends the loop, Tokenizer.h:586-588)
-        const bool any = ctl->first ? v.count > 0 : v.count >= 0;
+        bool any = ctl->first ? v.count > 0 : v.count >= 0;
+        if (LIM) any = any && v.count >= (long long)lim.min_count;
         const unsigned long long key = ~v.nkey;
         ctl->live = any ? 1u : 0u;
         ctl->a = (uint32_t)(key >> 32);
@@ -263,6 +284,7 @@ __global__ __launch_bounds__(kArgBlocks) void k_wide_argmax_final(const unsigned
         if (any) {
             WideBest wb = {(int32_t)v.count, (uint32_t)(key >> 32), (uint32_t)key, 0u};
             best[ctl->k] = wb;
+            if (LIM && lim.len && !ctl->first) wide_new_len(lim, ctl);
         }
     }
 }
@@ -282,9 +304,12 @@ __device__ __forceinline__ int32_t wide_lookup(const WideTable &t, unsigned long
     return -1;
 }
 
-// the grid and stride of k_wide_argmax_partial: block b walks the slice whose maximum is part[2 b]
+// the grid and stride of k_wide_argmax_partial: block b walks the slice whose maximum is part[2 b].
+// LIM: n_tie and the bitmap hold eligible pairs only (part[] is the eligible maximum already)
+template <bool LIM>
 __global__ __launch_bounds__(256) void k_wide_first_gather(WideTable t, const WideCtl *ctl,
-                                                           const unsigned long long *__restrict__ part, WideFirst *fs) {
+                                                           const unsigned long long *__restrict__ part, WideFirst *fs,
+                                                           const uint32_t *__restrict__ len, uint32_t max_len) {
     if (ctl->k >= ctl->k_limit || !ctl->live) return;
     const int32_t M = ctl->count;
     if ((long long)part[2 * blockIdx.x] < (long long)M) return;
@@ -295,6 +320,7 @@ __global__ __launch_bounds__(256) void k_wide_first_gather(WideTable t, const Wi
         if (t.cnts[i] != M) continue;
         const unsigned long long k = t.keys[i];
         if (k == kWideEmpty) continue;
+        if (LIM && !wide_eligible(len, max_len, k)) continue;
         const uint32_t hb = first_bit(k), bit = 1u << (hb & 31u);
         // (thousands of tied pairs share 2,048 words: most bits are set already, skip their atomics)
         if (!(__hip_atomic_load(&fs->bitmap[hb >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit))
@@ -307,8 +333,12 @@ __global__ __launch_bounds__(256) void k_wide_first_gather(WideTable t, const Wi
 }
 
 constexpr int kPosBlocks = 1024;
+// LIM: a hit needs count == M and eligibility -- an ineligible pair of count M may share a bitmap bit with a tied one,
+// or be one whose bit an eligible pair of the same hash set
+template <bool LIM>
 __global__ __launch_bounds__(kSpanThreads) void k_wide_first_pos(const uint32_t *__restrict__ tok, WideTable t,
-                                                                 const WideCtl *ctl, WideFirst *fs) {
+                                                                 const WideCtl *ctl, WideFirst *fs,
+                                                                 const uint32_t *__restrict__ len, uint32_t max_len) {
     __shared__ uint32_t bm[kWideFirstBitmapWords];
     if (ctl->k >= ctl->k_limit || !ctl->live) return;
     if (fs->n_tie <= 1) return;                               // a unique maximum: the lexical winner is it
@@ -336,7 +366,8 @@ __global__ __launch_bounds__(kSpanThreads) void k_wide_first_pos(const uint32_t 
             if (i + 1 < n && !(tv & kTokEnd)) {                  // a pair starts here (Tokenizer.h:135-144)
                 const unsigned long long key = ((unsigned long long)tv << 32) | (nx & kTokIdMask);
                 const uint32_t hb = first_bit(key);
-                if ((bm[hb >> 5] >> (hb & 31u)) & 1u) hit = wide_lookup(t, key) == M;
+                if ((bm[hb >> 5] >> (hb & 31u)) & 1u)
+                    hit = wide_lookup(t, key) == M && (!LIM || wide_eligible(len, max_len, key));
             }
             const unsigned long long H = __ballot(hit);
             if (H) {
@@ -350,8 +381,10 @@ __global__ __launch_bounds__(kSpanThreads) void k_wide_first_pos(const uint32_t 
     }
 }
 
+// LIM: ctl->a, b are final here, whichever kernel chose them: the new token's length is noted
+template <bool LIM>
 __global__ __launch_bounds__(256) void k_wide_first_pick(const uint32_t *__restrict__ tok, WideCtl *ctl, WideBest *best,
-                                                         WideFirst *fs) {
+                                                         WideFirst *fs, WideLimits lim) {
     __shared__ uint32_t nt;
     if (threadIdx.x == 0) {
         nt = fs->n_tie;
@@ -363,6 +396,7 @@ __global__ __launch_bounds__(256) void k_wide_first_pick(const uint32_t *__restr
             WideBest wb = {ctl->count, a, b, 0u};
             best[ctl->k] = wb;
         }
+        if (LIM && ctl->k < ctl->k_limit && ctl->live) wide_new_len(lim, ctl);
         fs->pos = ~0ull;
         fs->n_tie = 0;
     }
@@ -608,19 +642,37 @@ void launch_wide_pair_count_tokens(hipStream_t s, const uint32_t *tok, const uin
     hipLaunchKernelGGL(k_wide_resume_check, dim3(1), dim3(1), 0, s, tally, ctl);
 }
 
-void launch_wide_argmax(hipStream_t s, WideTable t, WideCtl *ctl, WideBest *best, unsigned long long *scratch) {
-    hipLaunchKernelGGL(k_wide_argmax_partial, dim3(kArgBlocks), dim3(256), 0, s, t, ctl, scratch);
-    hipLaunchKernelGGL(k_wide_argmax_final, dim3(1), dim3(kArgBlocks), 0, s, scratch, ctl, best);
+// (the scans are limited by a length array, the final stage also by a minimal count alone)
+void launch_wide_argmax(hipStream_t s, WideTable t, WideCtl *ctl, WideBest *best, unsigned long long *scratch, WideLimits lim) {
+    const uint32_t *len = lim.len;
+    if (len)
+        hipLaunchKernelGGL(k_wide_argmax_partial<true>, dim3(kArgBlocks), dim3(256), 0, s, t, ctl, scratch, len, lim.max_len);
+    else
+        hipLaunchKernelGGL(k_wide_argmax_partial<false>, dim3(kArgBlocks), dim3(256), 0, s, t, ctl, scratch, len, 0u);
+    if (len || lim.min_count)
+        hipLaunchKernelGGL(k_wide_argmax_final<true>, dim3(1), dim3(kArgBlocks), 0, s, scratch, ctl, best, lim);
+    else
+        hipLaunchKernelGGL(k_wide_argmax_final<false>, dim3(1), dim3(kArgBlocks), 0, s, scratch, ctl, best, lim);
 }
 
 void launch_wide_first(hipStream_t s, const uint32_t *src, uint64_t n_upper, WideTable t, WideCtl *ctl, WideBest *best,
-                       const unsigned long long *scratch, WideFirst *fs) {
-    hipLaunchKernelGGL(k_wide_first_gather, dim3(kArgBlocks), dim3(256), 0, s, t, ctl, scratch, fs);
+                       const unsigned long long *scratch, WideFirst *fs, WideLimits lim) {
+    const uint32_t *len = lim.len;
+    if (len)
+        hipLaunchKernelGGL(k_wide_first_gather<true>, dim3(kArgBlocks), dim3(256), 0, s, t, ctl, scratch, fs, len, lim.max_len);
+    else
+        hipLaunchKernelGGL(k_wide_first_gather<false>, dim3(kArgBlocks), dim3(256), 0, s, t, ctl, scratch, fs, len, 0u);
     if (n_upper) {
         const uint32_t blocks = std::min<uint32_t>(span_grid(n_upper), kPosBlocks);
-        hipLaunchKernelGGL(k_wide_first_pos, dim3(blocks), dim3(kSpanThreads), 0, s, src, t, ctl, fs);
+        if (len)
+            hipLaunchKernelGGL(k_wide_first_pos<true>, dim3(blocks), dim3(kSpanThreads), 0, s, src, t, ctl, fs, len, lim.max_len);
+        else
+            hipLaunchKernelGGL(k_wide_first_pos<false>, dim3(blocks), dim3(kSpanThreads), 0, s, src, t, ctl, fs, len, 0u);
     }
-    hipLaunchKernelGGL(k_wide_first_pick, dim3(1), dim3(256), 0, s, src, ctl, best, fs);
+    if (len)
+        hipLaunchKernelGGL(k_wide_first_pick<true>, dim3(1), dim3(256), 0, s, src, ctl, best, fs, lim);
+    else
+        hipLaunchKernelGGL(k_wide_first_pick<false>, dim3(1), dim3(256), 0, s, src, ctl, best, fs, lim);
 }
 
 void launch_wide_merge(hipStream_t s, const uint32_t *src, uint32_t *dst, uint64_t n_upper, uint32_t *val,

@@ -107,7 +107,15 @@ void usage() {
                  "                              counts as with --dedup: the model of the pieces' chunks laid end to end.  Every\n"
                  "                              piece is split on its own, so cut files where a letter or digit is followed by\n"
                  "                              whitespace.  Combines with --device-split, --device-split-unicode,\n"
-                 "                              --continue-from, -c and -w; with --input or without --train it is an error\n";
+                 "                              --continue-from, -c and -w; with --input or without --train it is an error\n"
+                 "  --min-frequency INT         With --train: the training ends when the best pair left occurs less often than\n"
+                 "                              this (0, the default: no such rule), with fewer merges than --vocab-size asks for\n"
+                 "  --max-token-length INT      With --train: no new token is longer than this many bytes (0, the default: no\n"
+                 "                              limit; else at least 2); pairs that would make one are never chosen, and the\n"
+                 "                              training ends when no other pair is left.  The tokens of a --continue-from\n"
+                 "                              model stay.  Either option trains one merge per pass over the corpus: combine\n"
+                 "                              with --dedup (or --input-list), so that a pass runs over the distinct chunks.\n"
+                 "                              Both combine with every other --train option; without --train they are an error\n";
 }
 
 }  // namespace
@@ -119,6 +127,8 @@ int main(int argc, char *argv[]) {
     bool train = false, decode = false, encode = false, write_vocab = false, verbose = false, device_encode = false,
          device_decode = false, device_split = false, split_unicode = false, rank_order = false, dedup = false;
     int vocab_size = 512, device = 0;
+    long long min_frequency = 0, max_token_length = 0;
+    bool have_limits = false;
     double dropout = 0.0;
     bool have_dropout = false;
     unsigned long long seed = 0;
@@ -151,6 +161,15 @@ int main(int argc, char *argv[]) {
         } else if (arg == "--device") {
             if (!value(&tmp)) return 106;
             try { device = std::stoi(tmp); } catch (...) { std::cerr << "--device: invalid integer " << tmp << "\n"; return 104; }
+        } else if (arg == "--min-frequency" || arg == "--max-token-length") {
+            const std::string name = arg;
+            if (!value(&tmp)) return 106;
+            size_t used = 0;
+            long long v = 0;
+            try { v = std::stoll(tmp, &used); } catch (...) { used = 0; }
+            if (used == 0 || used != tmp.size()) { std::cerr << name << ": invalid integer " << tmp << "\n"; return 104; }
+            (name == "--min-frequency" ? min_frequency : max_token_length) = v;
+            have_limits = true;
         } else if (arg == "--dropout") {
             if (!value(&tmp)) return 106;
             size_t used = 0;
@@ -190,6 +209,8 @@ int main(int argc, char *argv[]) {
         }
         if (!rank_order) { std::cerr << "--dropout requires --rank-order\n"; return 107; }
     }
+
+    if (have_limits && !train) { std::cerr << "--min-frequency and --max-token-length require --train\n"; return 107; }
 
     struct Piece { std::string path; uint32_t repeat; };
     std::vector<Piece> pieces;
@@ -252,6 +273,11 @@ int main(int argc, char *argv[]) {
         std::cerr << "Model file " << continue_from << " does not exist or could not be loaded\n";
         mbpe_tok_destroy(rt);
         return -1;
+    }
+    if (train && have_limits && mbpe_tok_set_train_limits(rt, min_frequency, max_token_length) != MBPE_OK) {
+        std::cerr << "Error: " << mbpe_last_error() << "\n";
+        mbpe_tok_destroy(rt);
+        return 105;
     }
     if (train) {                                                // :181-211
         if (have_special) mbpe_tok_set_special_tokens(rt, special_tokens_data.data(), special_tokens_data.size());

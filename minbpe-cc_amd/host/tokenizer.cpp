@@ -303,6 +303,9 @@ int Tokenizer::run_training(mbpe_ctx *ctx, int rc, int vocab_size, CONFLICT_RESO
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "first_wide", 1);
     // (... and so does a training that continues from existing merges)
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "resume_wide", 1);
+    // (the stopping rules, mbpe_tok_set_train_limits: either non-zero and the training runs on 32-bit tokens throughout)
+    if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "min_frequency", train_min_frequency_);
+    if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "max_token_length", train_max_token_length_);
     if (rc == MBPE_OK) rc = mbpe_train_begin_from(ctx, static_cast<uint32_t>(vocab_size), prior.data(), n_prior_of(prior));
     if (rc == MBPE_OK) rc = mbpe_train_steps(ctx, cap, nullptr);
     if (rc == MBPE_OK) rc = mbpe_train_result(ctx, out->flat.data(), out->had.data(), cap, &out->n_merges);
@@ -1192,6 +1195,20 @@ int mbpe_tok_set_train_dedup(mbpe_tokenizer *t, int on) {
         return MBPE_ERR_ARG;
     }
     t->t->set_train_dedup(on == 1);
+    return MBPE_OK;
+}
+
+int mbpe_tok_set_train_limits(mbpe_tokenizer *t, int64_t min_frequency, int64_t max_token_length) {
+    if (!t) return MBPE_ERR_ARG;
+    if (min_frequency < 0 || min_frequency > 0x7FFFFFFFll) {
+        mbpe_host::set_last_error("mbpe_tok_set_train_limits: min_frequency is 0 (off) .. 2^31 - 1");
+        return MBPE_ERR_ARG;
+    }
+    if (max_token_length != 0 && (max_token_length < 2 || max_token_length > 0x7FFFFFFFll)) {
+        mbpe_host::set_last_error("mbpe_tok_set_train_limits: max_token_length is 0 (off), or 2 .. 2^31 - 1 bytes");
+        return MBPE_ERR_ARG;
+    }
+    t->t->set_train_limits(min_frequency, max_token_length);
     return MBPE_OK;
 }
 

@@ -97,6 +97,12 @@ public:
     void set_split_unicode(bool on) { split_unicode_ = on; }
     // train() from here on runs on the distinct chunks with their counts (mbpe_tok_set_train_dedup)
     void set_train_dedup(bool on) { train_dedup_ = on; }
+    // the stopping rules of every training from here on (mbpe_tok_set_train_limits): the context options
+    // "min_frequency" and "max_token_length", 0 = off
+    void set_train_limits(int64_t min_frequency, int64_t max_token_length) {
+        train_min_frequency_ = min_frequency;
+        train_max_token_length_ = max_token_length;
+    }
     // the device encode calls from here on go through the encoder's "dedup" route (mbpe_tok_set_encode_dedup)
     void set_encode_dedup(bool on) { encode_dedup_ = on; }
     // :725-751; device >= 0 expands the tokens on that HIP device (mbpe_decode_tokens) instead of the host loop
@@ -210,6 +216,7 @@ private:
     bool encode_split_ = false;
     bool split_unicode_ = false;
     bool train_dedup_ = false;
+    int64_t train_min_frequency_ = 0, train_max_token_length_ = 0;
     bool encode_dedup_ = false;
     bool rank_order_ = false;
     uint64_t drop_threshold_ = 0, drop_seed_ = 0;

@@ -58,7 +58,7 @@ TOK_EXPORTS = [
     "mbpe_tok_set_encode_order", "mbpe_tok_train_continue", "mbpe_tok_encode_byteoff",
     "mbpe_tok_encode_batch_byteoff_device", "mbpe_tok_set_encode_dropout", "mbpe_tok_set_train_dedup",
     "mbpe_tok_set_encode_dedup", "mbpe_tok_train_pieces_begin", "mbpe_tok_train_pieces_add",
-    "mbpe_tok_train_pieces_finish", "mbpe_tok_train_pieces_abort",
+    "mbpe_tok_train_pieces_finish", "mbpe_tok_train_pieces_abort", "mbpe_tok_set_train_limits",
 ]
 
 
@@ -250,6 +250,7 @@ def lib():
     L.mbpe_tok_set_encode_split.argtypes = [vp, i32]
     L.mbpe_tok_set_split_unicode.argtypes = [vp, i32]
     L.mbpe_tok_set_train_dedup.argtypes = [vp, i32]
+    L.mbpe_tok_set_train_limits.argtypes = [vp, ctypes.c_int64, ctypes.c_int64]
     L.mbpe_dedup_create.argtypes = [i32, ctypes.POINTER(vp)]
     L.mbpe_dedup_destroy.argtypes = [vp]
     L.mbpe_dedup_destroy.restype = None
@@ -1574,8 +1575,14 @@ class Tokenizer:
         _check(lib().mbpe_tok_set_special_tokens(self._h, b, len(b)))
 
     def train(self, data, vocab_size, conflict_resolution=1, verbose=False, device=0, device_split=False,
-              resume=False, dedup=False):
-        """dedup: split as asked, deduplicate the chunks on the device and train on the distinct ones with their
+              resume=False, dedup=False, min_frequency=0, max_token_length=0):
+        """min_frequency, max_token_length (here, in train_from_iterator and train_files; mbpe_tok_set_train_limits):
+        the stopping rules.  The training ends when the best pair left occurs fewer than min_frequency times, and no
+        new token is longer than max_token_length bytes (at least 2; the merges a resumed training starts from stay):
+        pairs that would make one are never chosen, and the training ends when no other pair is left.  0: off.  The
+        tokenizer then holds fewer merges than vocab_size asks for.  With either the training makes one pass per
+        merge over the corpus it is given: combine with dedup=True, so that a pass runs over the distinct chunks.
+        dedup: split as asked, deduplicate the chunks on the device and train on the distinct ones with their
         counts (mbpe_tok_set_train_dedup): same merges, counts, .model and .vocab.  Meant for the `first` tie-break,
         for vocabularies beyond the 16-bit slot format and with resume; the lexical tie-break within the slot format
         is faster without it.  A tokenizer without a pattern has one chunk and trains slowly this way.
@@ -1588,6 +1595,7 @@ class Tokenizer:
         text = _u8(data)
         _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
         _check(lib().mbpe_tok_set_train_dedup(self._h, int(bool(dedup))))
+        _check(lib().mbpe_tok_set_train_limits(self._h, int(min_frequency), int(max_token_length)))
         if resume:
             _check(lib().mbpe_tok_train_continue(self._h, text.ctypes.data if len(text) else None, len(text), vocab_size,
                                                  conflict_resolution, int(verbose), device, int(bool(device_split))))
@@ -1597,15 +1605,16 @@ class Tokenizer:
                   int(verbose), device))
 
     def train_from_iterator(self, texts, vocab_size, conflict_resolution=1, verbose=False, device=0, device_split=False,
-                            resume=False, repeats=None):
+                            resume=False, repeats=None, min_frequency=0, max_token_length=0):
         """Train on a corpus that arrives in pieces (mbpe_tok_train_pieces_*): every text is split on its own and its
         chunks are counted on the device (mbpe_wordcount_*), then the training runs on the table -- the merges of a
         training on the pieces' chunk lists laid end to end, for both tie-breaks, with one piece in host memory at a
         time.  A piece boundary is a chunk boundary: to get a whole file's result, cut it where a letter or digit is
         followed by whitespace.  repeats: one count per text (default 1), the text counted that many times.
-        device_split, resume: as for train().  The tokenizer's merges stay as they are until the training has
+        device_split, resume, min_frequency, max_token_length: as for train().  The tokenizer's merges stay as they are until the training has
         succeeded; the session is aborted when the iterator or a call raises."""
         _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
+        _check(lib().mbpe_tok_set_train_limits(self._h, int(min_frequency), int(max_token_length)))
         _check(lib().mbpe_tok_train_pieces_begin(self._h, device, int(bool(device_split))))
         try:
             reps = None if repeats is None else iter(repeats)
