@@ -1234,8 +1234,43 @@ MBPE_API int  mbpe_dedup_get_map(mbpe_dedup *d, uint32_t *unique_of_out, uint64_
  *   mbpe_wordcount_reset        empty again, buffers kept
  *   mbpe_wordcount_set_option   "max_chunk_bytes", "hash_bits": handed to the owned deduper, same defaults and ranges;
  *                               MBPE_ERR_STATE once a piece has been added (until the next reset)
- *   mbpe_wordcount_kernel_ms    device time of the latest add call: the deduper's kernels and the fold's
- * Arguments are checked before the device is touched.  No CPU fallback: MBPE_ERR_NO_DEVICE without a HIP device. */
+ *   mbpe_wordcount_kernel_ms    device time of the latest add or merge call: the deduper's kernels (add) and the fold's,
+ *                               for mbpe_wordcount_merge_blob with the check of the incoming chunks
+ * Arguments are checked before the device is touched.  No CPU fallback: MBPE_ERR_NO_DEVICE without a HIP device.
+ *
+ * Tables merge, so the counting can be spread over devices, processes and days, and be checkpointed.  Let A be the count
+ * of pieces P_0 .. P_{i-1} and B, a fresh object with the same "max_chunk_bytes", the count of P_i .. P_{k-1}.  After
+ * merging B into A, A is, bit for bit, the table of counting P_0 .. P_{k-1} into one object: text, ends, u64 weights,
+ * first_chunk, the chunks above "max_chunk_bytes" once per occurrence, and the totals.  Per entry of B: found in A -> its
+ * weight is added; not found -> appended in B's order with first_chunk = A's chunks so far + B's first_chunk; above
+ * "max_chunk_bytes" -> appended without a look; then A's chunks so far, chunks counted and pieces grow by B's.  Merging
+ * in piece order is therefore associative: a chain ((A + B) + C) and a tree (A + (B + C)) give the same table, and a
+ * training on it is the training on all pieces.  Merging out of order is allowed and gives the table of the pieces in
+ * that order: the weights are the same, the order of the entries and first_chunk -- what the `first` tie-break sees --
+ * are those of that order.  A weight that reaches 2^31 sets the sticky overflow as an add does.  Moving a blob between
+ * processes or machines is the caller's business (files, torch.distributed.all_gather_object, MPI).
+ *   mbpe_wordcount_export_size, mbpe_wordcount_export
+ *       the table as a host blob; the object is unchanged and goes on counting, so an export is also a checkpoint.
+ *       Little-endian: a 64-byte header (u32 magic "MBWC", u32 version 1, then u64 max_chunk_bytes, n_unique, n_bytes,
+ *       n_pieces, n_chunks_total, chunk_base -- the chunks of the concatenated list, empty ones included -- and a u64
+ *       that is 0), then ends, weights and first_chunk (n_unique u64 each), then the text padded with zeros to 16
+ *       bytes.  "hash_bits" is not in it: it places slots and decides nothing.  A cap below the size is MBPE_ERR_ARG;
+ *       an overflowed table MBPE_ERR_OVERFLOW, as for mbpe_wordcount_get.  n_bytes_out of _export may be NULL.
+ *   mbpe_wordcount_merge_blob
+ *       checks, uploads and folds a blob; into an empty object it is an import (exporting again gives the same
+ *       bytes).  The outputs (either may be NULL) are the table's sizes after the call.  A blob is not trusted: it is
+ *       refused with MBPE_ERR_ARG and a message naming the rule when the magic or the version is wrong; when the sizes do
+ *       not give the blob's length; when the ends are not strictly ascending or do not end at n_bytes; when a weight
+ *       is 0; when first_chunk is not strictly ascending or not below chunk_base; when the weights' sum is not
+ *       n_chunks_total; when it was counted with another "max_chunk_bytes"; and when two of its chunks at or below
+ *       "max_chunk_bytes" have the same bytes (checked on the device in a scratch table).  All of this comes before any
+ *       weight of the object is touched: a refused merge leaves the table, its statistics and its views as they were.
+ *   mbpe_wordcount_merge
+ *       the same fold straight from the device buffers of `other`, which stays unchanged; no check is needed.
+ *       MBPE_ERR_ARG when the objects are on different devices (use the blob there), when w == other, and when their
+ *       options differ; MBPE_ERR_OVERFLOW when `other` has overflowed.
+ *   A merge that fails later, in an allocation or on the device, leaves the object as a failed add does: weights of
+ *   entries that were found may have grown; reset it. */
 typedef struct mbpe_wordcount mbpe_wordcount;
 MBPE_API int  mbpe_wordcount_create(int device_id, mbpe_wordcount **out);
 MBPE_API void mbpe_wordcount_destroy(mbpe_wordcount *w);
@@ -1255,6 +1290,11 @@ MBPE_API int  mbpe_wordcount_reset(mbpe_wordcount *w);
 MBPE_API int  mbpe_wordcount_set_option(mbpe_wordcount *w, const char *name, int64_t value);
 MBPE_API int  mbpe_wordcount_kernel_ms(const mbpe_wordcount *w, float *ms_out);
 MBPE_API int  mbpe_wordcount_alloc_count(const mbpe_wordcount *w, uint64_t *n_out);
+MBPE_API int  mbpe_wordcount_export_size(const mbpe_wordcount *w, uint64_t *n_bytes_out);
+MBPE_API int  mbpe_wordcount_export(mbpe_wordcount *w, uint8_t *blob_out, uint64_t cap_bytes, uint64_t *n_bytes_out);
+MBPE_API int  mbpe_wordcount_merge_blob(mbpe_wordcount *w, const uint8_t *blob, uint64_t n_bytes,
+                                        uint64_t *n_unique_total_out, uint64_t *n_unique_bytes_total_out);
+MBPE_API int  mbpe_wordcount_merge(mbpe_wordcount *w, const mbpe_wordcount *other);
 
 #ifdef __cplusplus
 }

@@ -58,8 +58,9 @@ MBPE_API int mbpe_tok_train_continue(mbpe_tokenizer *t, const uint8_t *text, uin
  * for both tie-breaks.  Every piece is split on its own, so a piece boundary is a chunk boundary ("a  " + "b" is not
  * "a  b"); cut where a letter or digit is followed by whitespace -- a chunk boundary under gpt2 and gpt4 -- and the
  * pieces give the whole text's result.  Host memory: one piece; device memory while counting: the largest piece's
- * split and dedup plus the unique chunks.  The training is that of mbpe_tok_set_train_dedup: one rank, the 32-bit
- * loop, and a chunk above 256 bytes is never merged with its duplicates.
+ * split and dedup plus the unique chunks.  The training is that of mbpe_tok_set_train_dedup: one rank (the counting
+ * can be spread over devices, processes and runs: _export and _merge below), the 32-bit loop, and a chunk above 256
+ * bytes is never merged with its duplicates.
  *   _begin   opens the session on device_id; device_split != 0: the pieces are split on the device too.
  *            MBPE_ERR_STATE while a session is open.
  *   _add     one piece, counted `repeat` (>= 1, else MBPE_ERR_ARG) times, as if written out back to back: how a data mix
@@ -73,12 +74,28 @@ MBPE_API int mbpe_tok_train_continue(mbpe_tokenizer *t, const uint8_t *text, uin
  *            and error codes of mbpe_tok_train_continue.  Verbose prints "Split input text into N chunks" once, with
  *            the session's total, and the length in the closing line is the whole corpus's.  The tokenizer's merges
  *            change only when it succeeds; the session is closed either way.
- *   _abort   closes the session, if any.  After _finish or _abort the session's device objects are gone. */
+ *   _abort   closes the session, if any.  After _finish or _abort the session's device objects are gone.
+ * The counting can be spread over devices, processes and runs; the training stage stays one rank.
+ *   _export_size, _export   the open session's counts as a host blob: 32 bytes (u32 magic "MBTC", u32 version 1, u64
+ *            length of the split pattern, u64 chunks and u64 bytes the session has seen), the pattern padded with zeros
+ *            to 8 bytes, then the blob of mbpe_wordcount_export (mbpe.h).  The session stays open and goes on counting:
+ *            an export is also a checkpoint.  A cap below the size is MBPE_ERR_ARG; n_bytes_out of _export may be NULL.
+ *   _merge   merges a blob into the open session as mbpe_wordcount_merge_blob does -- the session becomes the count of
+ *            its own pieces followed by the blob's, with the checks listed there -- and adds the blob's chunks and bytes
+ *            to the totals that the verbose lines of _finish report, so a session that merged the blobs of all pieces
+ *            trains and prints like one that was given all pieces.  Host split and either device split give the same
+ *            chunks: sessions counted on different routes merge freely.  A blob counted under another split pattern,
+ *            or one that is truncated or not a counts blob, is MBPE_ERR_ARG; the session is unchanged then.  Merged out
+ *            of piece order, the `first` tie-break sees the first occurrences of that order.
+ *   All three return MBPE_ERR_STATE without a session.  How a blob travels is the caller's business. */
 MBPE_API int mbpe_tok_train_pieces_begin(mbpe_tokenizer *t, int device_id, int device_split);
 MBPE_API int mbpe_tok_train_pieces_add(mbpe_tokenizer *t, const uint8_t *text, uint64_t n, uint32_t repeat);
 MBPE_API int mbpe_tok_train_pieces_finish(mbpe_tokenizer *t, uint32_t vocab_size, int conflict_resolution, int verbose,
                                           int resume);
 MBPE_API int mbpe_tok_train_pieces_abort(mbpe_tokenizer *t);
+MBPE_API int mbpe_tok_train_pieces_export_size(mbpe_tokenizer *t, uint64_t *n_bytes_out);
+MBPE_API int mbpe_tok_train_pieces_export(mbpe_tokenizer *t, uint8_t *blob_out, uint64_t cap_bytes, uint64_t *n_bytes_out);
+MBPE_API int mbpe_tok_train_pieces_merge(mbpe_tokenizer *t, const uint8_t *blob, uint64_t n_bytes);
 
 /* Direct access to the trained / loaded merges (2 u32 per merge). */
 MBPE_API int mbpe_tok_set_merges(mbpe_tokenizer *t, const uint32_t *merges, uint32_t n_merges);

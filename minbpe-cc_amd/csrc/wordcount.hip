@@ -12,6 +12,11 @@
 //                   first_chunk, and one compare-and-swap each for a free slot
 //
 // The order between them is the order of the kernels on the stream; nothing else is needed.
+//
+// A merge folds another table instead of a piece: the same steps from k_wc_rehash on, with the table's own u64 ends and
+// weights (k_wc_lookup and k_wc_append are templates over the weight type).  A table that arrives as a blob is checked
+// first -- wordcount_blob_check on the host, then k_wc_distinct on the device: the incoming hashed chunks claim slots of
+// a scratch table, and a chunk that meets its own bytes there raises a flag -- and only then does a weight change.
 #include "wordcount.h"
 #include "dedup_dev.h"
 #include "hip_host.h"
@@ -30,7 +35,7 @@ namespace {
 #define WCHK(expr) MBPE_HIP_CHECK(expr, false)
 
 // what the host reads back after the lookup
-struct WcCtl { unsigned long long n_ends, n_new, n_new_bytes, piece_chunks, overflow, pad; };
+struct WcCtl { unsigned long long n_ends, n_new, n_new_bytes, piece_chunks, overflow, dup; };
 
 struct WcTable {
     unsigned long long *slots;     // dedup_slot(tag, entry), kDedupEmpty when free
@@ -64,9 +69,11 @@ __global__ __launch_bounds__(kDdThreads) void k_wc_rehash(WcAcc a, WcTable t, ui
 // The piece's unique chunks that were hashed are pairwise distinct -- the owned deduper runs with this object's
 // "max_chunk_bytes", so every chunk at or below it occurs once in the piece's result -- hence no two lanes find the same
 // entry and the weight is updated with a plain load and store.
+// (W: uint32_t for a piece out of the deduper, unsigned long long for a table that is merged)
+template <typename W>
 __global__ __launch_bounds__(kDdThreads) void k_wc_lookup(const uint8_t *__restrict__ ptext,
                                                           const unsigned long long *__restrict__ pend,
-                                                          const uint32_t *__restrict__ pweights, uint64_t nu, uint32_t repeat,
+                                                          const W *__restrict__ pweights, uint64_t nu, uint32_t repeat,
                                                           WcAcc a, WcTable t, uint32_t max_chunk, uint32_t hash_bits,
                                                           unsigned long long *__restrict__ hash_out,
                                                           uint8_t *__restrict__ new_out,
@@ -118,9 +125,10 @@ __global__ __launch_bounds__(kDdThreads) void k_wc_lookup(const uint8_t *__restr
     if (over) ctl->overflow = 1;
 }
 
+template <typename W>
 __global__ __launch_bounds__(kDdThreads) void k_wc_append(const uint8_t *__restrict__ ptext,
                                                           const unsigned long long *__restrict__ pend,
-                                                          const uint32_t *__restrict__ pweights,
+                                                          const W *__restrict__ pweights,
                                                           const unsigned long long *__restrict__ pfirst, uint64_t nu,
                                                           uint32_t repeat, uint64_t chunk_base, WcAcc a, WcTable t,
                                                           uint32_t max_chunk, const unsigned long long *__restrict__ hash,
@@ -146,6 +154,41 @@ __global__ __launch_bounds__(kDdThreads) void k_wc_append(const uint8_t *__restr
     a.weights[e] = wordcount_sat_mul(pweights[j], repeat);
     a.first[e] = chunk_base + pfirst[j];
     if (len <= max_chunk) wc_claim(t, hash[j], e);
+}
+
+// The check of a table nobody vouches for: are its hashed chunks pairwise distinct?  Every one claims a slot of the empty
+// scratch table t with the insert of dedup.hip -- a free slot by compare-and-swap, whose answer is looked at when it
+// fails -- and one that meets a slot with its own bytes sets *dup.  Chunks with the same bytes walk the same probe
+// sequence and slots never become free, so the later of two always meets the earlier.  Nothing else is written.
+__global__ __launch_bounds__(kDdThreads) void k_wc_distinct(const uint8_t *__restrict__ ptext,
+                                                            const unsigned long long *__restrict__ pend, uint64_t nu,
+                                                            WcTable t, uint32_t max_chunk, uint32_t hash_bits,
+                                                            unsigned long long *dup) {
+    const uint64_t j = (uint64_t)blockIdx.x * kDdThreads + threadIdx.x;
+    if (j >= nu) return;
+    uint64_t start, len;
+    chunk_range(pend, j, &start, &len);
+    if (len > max_chunk) return;
+    const unsigned long long h = dedup_hash(ptext + start, len, hash_bits);
+    const uint32_t tag = dedup_tag(h);
+    const unsigned long long mine = dedup_slot(tag, j);
+    uint64_t pos = dedup_home(h, t.bits);
+    for (uint64_t probe = 0; probe <= t.mask; ++probe, pos = (pos + 1) & t.mask) {
+        unsigned long long v = t.slots[pos];
+        if (v == kDedupEmpty) {
+            v = atomicCAS(&t.slots[pos], kDedupEmpty, mine);
+            if (v == kDedupEmpty) return;
+        }
+        if (dedup_tag(v) != tag) continue;
+        const uint64_t r = v & 0xFFFFFFFFull;
+        if (r >= nu) continue;                    // (never: the scratch table speaks of these chunks only)
+        uint64_t rs, rl;
+        chunk_range(pend, r, &rs, &rl);
+        if (rl == len && dedup_equal(ptext + start, ptext + rs, len)) {
+            *dup = 1;
+            return;
+        }
+    }
 }
 
 // the views of mbpe_wordcount_result: the end mask of the packed text and the weights as u32
@@ -180,6 +223,10 @@ struct mbpe_wordcount : DevQueue {
     // one piece
     DevBuf<unsigned long long> d_tile, d_pend, d_hash, d_blk, d_ctl;
     DevBuf<uint8_t> d_new;
+    // one table out of a blob: ends, weights, first_chunk and text as uploaded, the scratch table of its check
+    DevBuf<unsigned long long> d_in, d_scratch;
+    DevBuf<uint8_t> d_in_text;
+    bool last_was_add = true;                              // does the deduper's time belong to the latest call?
     // mbpe_wordcount_result
     DevBuf<uint8_t> d_mask;
     DevBuf<uint32_t> d_w32;
@@ -199,6 +246,100 @@ int wc_add_ms(mbpe_wordcount *w) {
     return MBPE_OK;
 }
 
+// What steps 1 - 4 fold into the accumulated table: nu chunks that are pairwise distinct wherever they are hashed, in a
+// packed text of nb bytes (in a 16-byte aligned buffer), with weights and first_chunk on the device.  The deduper's
+// result is one (u32 weights; its ends come out of the end mask m32), another table the other (u64 weights, ends given,
+// m32 NULL).
+template <typename W>
+struct WcSource {
+    const uint8_t *text;
+    const uint32_t *m32;
+    const unsigned long long *ends;
+    const W *weights;
+    const unsigned long long *first;
+    uint64_t nu, nb;
+};
+
+// steps 1 - 4 for a source with nu > 0; *kept_out: the sum of its weights.  first_chunk moves on by w->chunk_base
+template <typename W>
+int wc_fold_source(mbpe_wordcount *w, const WcSource<W> &s, uint32_t repeat, uint64_t *kept_out) {
+    int rc;
+    const uint64_t nu = s.nu, nb = s.nb;
+    if (w->n_unique + nu >= 0xFFFFFFFFull) return fail(MBPE_ERR_ARG, "wordcount: 2^32 - 1 unique chunks or more");
+    const uint64_t n_words = (nb + 63) / 64, n_tiles = blocks_for(n_words);
+    const uint32_t n_blk = blocks_for(nu);
+    if ((rc = w->d_ctl.reserve(sizeof(WcCtl), w->mem)) != MBPE_OK) return rc;
+    if (s.m32) {
+        if ((rc = w->d_tile.reserve(n_tiles * 8, w->mem)) != MBPE_OK) return rc;
+        if ((rc = w->d_pend.reserve(nu * 8, w->mem)) != MBPE_OK) return rc;
+    }
+    if ((rc = w->d_hash.reserve(nu * 8, w->mem)) != MBPE_OK) return rc;
+    if ((rc = w->d_new.reserve(nu, w->mem)) != MBPE_OK) return rc;
+    if ((rc = w->d_blk.reserve((uint64_t)n_blk * 16, w->mem)) != MBPE_OK) return rc;
+    // 1. capacity, before anything else: the lookup and the append below can never fill the table
+    const bool rebuild = wordcount_needs_rebuild(w->n_unique + nu, w->table_bits ? 1ull << w->table_bits : 0);
+    if (rebuild) {
+        const uint32_t bits = dedup_table_bits(w->n_unique + nu);
+        if ((rc = w->d_slots.reserve((1ull << bits) * 8, w->mem)) != MBPE_OK) { w->table_bits = 0; return rc; }
+        w->table_bits = bits;
+    }
+    WcCtl *dctl = reinterpret_cast<WcCtl *>(w->d_ctl.get());
+    unsigned long long *blk_cnt = w->d_blk, *blk_bytes = w->d_blk.get() + n_blk;
+    const unsigned long long *pend = s.m32 ? w->d_pend.get() : s.ends;
+    const WcTable t = w->table();
+    WCHK(hipEventRecord(w->ev0, w->stream));
+    WCHK(hipMemsetAsync(w->d_ctl, 0, sizeof(WcCtl), w->stream));
+    if (s.m32) {
+        hipLaunchKernelGGL(k_dd_tile_count, dim3((uint32_t)n_tiles), dim3(kDdThreads), 0, w->stream, s.m32, nb, n_words,
+                           w->d_tile.get());
+        hipLaunchKernelGGL(k_dd_scan, dim3(1), dim3(kScanThreads), 0, w->stream, w->d_tile.get(), n_tiles, &dctl->n_ends);
+        hipLaunchKernelGGL(k_dd_chunk_ends, dim3((uint32_t)n_tiles), dim3(kDdThreads), 0, w->stream, s.m32, nb, n_words,
+                           w->d_tile.get(), nu, w->d_pend.get());
+    }
+    if (rebuild) {
+        WCHK(hipMemsetAsync(t.slots, 0xFF, (t.mask + 1) * 8, w->stream));
+        if (w->n_unique)
+            hipLaunchKernelGGL(k_wc_rehash, dim3(blocks_for(w->n_unique)), dim3(kDdThreads), 0, w->stream, w->acc(), t,
+                               w->max_chunk, w->hash_bits);
+    }
+    // 2. lookup, 3. scan
+    hipLaunchKernelGGL(k_wc_lookup<W>, dim3(n_blk), dim3(kDdThreads), 0, w->stream, s.text, pend, s.weights, nu, repeat,
+                       w->acc(), t, w->max_chunk, w->hash_bits, w->d_hash.get(), w->d_new.get(), blk_cnt, blk_bytes, dctl);
+    hipLaunchKernelGGL(k_dd_scan, dim3(1), dim3(kScanThreads), 0, w->stream, blk_cnt, (uint64_t)n_blk, &dctl->n_new);
+    hipLaunchKernelGGL(k_dd_scan, dim3(1), dim3(kScanThreads), 0, w->stream, blk_bytes, (uint64_t)n_blk,
+                       &dctl->n_new_bytes);
+    WCHK(hipGetLastError());
+    WCHK(hipEventRecord(w->ev1, w->stream));
+    WcCtl ctl = {};
+    WCHK(hipMemcpyAsync(&ctl, w->d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, w->stream));
+    WCHK(hipStreamSynchronize(w->stream));
+    if ((rc = wc_add_ms(w)) != MBPE_OK) return rc;
+    // (weights of entries that were found have grown already: from here on the source counts)
+    w->overflow = w->overflow || ctl.overflow != 0;
+    if ((s.m32 && ctl.n_ends != nu) || ctl.n_new > nu || ctl.n_new_bytes > nb || ctl.n_new_bytes < ctl.n_new)
+        return fail(MBPE_ERR_HIP, "wordcount: the device counted impossible new chunks");
+    // 4. append
+    if (ctl.n_new) {
+        const uint64_t n_after = w->n_unique + ctl.n_new, b_after = w->n_bytes + ctl.n_new_bytes;
+        if ((rc = w->d_text.grow(w->n_bytes, (b_after + 15) / 16 * 16, w->mem, w->stream)) != MBPE_OK) return rc;
+        if ((rc = w->d_ends.grow(w->n_unique * 8, n_after * 8, w->mem, w->stream)) != MBPE_OK) return rc;
+        if ((rc = w->d_weights.grow(w->n_unique * 8, n_after * 8, w->mem, w->stream)) != MBPE_OK) return rc;
+        if ((rc = w->d_first.grow(w->n_unique * 8, n_after * 8, w->mem, w->stream)) != MBPE_OK) return rc;
+        WCHK(hipEventRecord(w->ev0, w->stream));
+        hipLaunchKernelGGL(k_wc_append<W>, dim3(n_blk), dim3(kDdThreads), 0, w->stream, s.text, pend, s.weights, s.first, nu,
+                           repeat, w->chunk_base, w->acc(), t, w->max_chunk, w->d_hash.get(), w->d_new.get(), blk_cnt,
+                           blk_bytes, (uint64_t)ctl.n_new, (uint64_t)ctl.n_new_bytes);
+        WCHK(hipGetLastError());
+        WCHK(hipEventRecord(w->ev1, w->stream));
+        WCHK(hipStreamSynchronize(w->stream));
+        if ((rc = wc_add_ms(w)) != MBPE_OK) return rc;
+        w->n_unique = n_after;
+        w->n_bytes = b_after;
+    }
+    *kept_out = ctl.piece_chunks;
+    return MBPE_OK;
+}
+
 // the piece the deduper holds -> the accumulated table.  piece_input_chunks: what first_chunk of the piece counts in
 // (mbpe_wordcount_add: its chunk_off entries, the empty chunks included); kWcKeptChunks: the chunks of the piece's mask,
 // which are its weights' sum, taken by the lookup
@@ -212,80 +353,55 @@ int wc_fold(mbpe_wordcount *w, uint64_t nu, uint64_t nb, uint64_t piece_input_ch
     if ((rc = mbpe_dedup_result(w->dd, &ptext, &pmask, &pweights, &pfirst)) != MBPE_OK) return rc;
     uint64_t kept = 0;
     if (nu) {
-        if (w->n_unique + nu >= 0xFFFFFFFFull) return fail(MBPE_ERR_ARG, "wordcount: 2^32 - 1 unique chunks or more");
-        const uint32_t *m32 = reinterpret_cast<const uint32_t *>(pmask);
-        const uint64_t n_words = (nb + 63) / 64, n_tiles = blocks_for(n_words);
-        const uint32_t n_blk = blocks_for(nu);
-        if ((rc = w->d_ctl.reserve(sizeof(WcCtl), w->mem)) != MBPE_OK) return rc;
-        if ((rc = w->d_tile.reserve(n_tiles * 8, w->mem)) != MBPE_OK) return rc;
-        if ((rc = w->d_pend.reserve(nu * 8, w->mem)) != MBPE_OK) return rc;
-        if ((rc = w->d_hash.reserve(nu * 8, w->mem)) != MBPE_OK) return rc;
-        if ((rc = w->d_new.reserve(nu, w->mem)) != MBPE_OK) return rc;
-        if ((rc = w->d_blk.reserve((uint64_t)n_blk * 16, w->mem)) != MBPE_OK) return rc;
-        // 1. capacity, before anything else: the lookup and the append below can never fill the table
-        const bool rebuild = wordcount_needs_rebuild(w->n_unique + nu, w->table_bits ? 1ull << w->table_bits : 0);
-        if (rebuild) {
-            const uint32_t bits = dedup_table_bits(w->n_unique + nu);
-            if ((rc = w->d_slots.reserve((1ull << bits) * 8, w->mem)) != MBPE_OK) { w->table_bits = 0; return rc; }
-            w->table_bits = bits;
-        }
-        WcCtl *dctl = reinterpret_cast<WcCtl *>(w->d_ctl.get());
-        unsigned long long *blk_cnt = w->d_blk, *blk_bytes = w->d_blk.get() + n_blk;
-        const WcTable t = w->table();
-        WCHK(hipEventRecord(w->ev0, w->stream));
-        WCHK(hipMemsetAsync(w->d_ctl, 0, sizeof(WcCtl), w->stream));
-        hipLaunchKernelGGL(k_dd_tile_count, dim3((uint32_t)n_tiles), dim3(kDdThreads), 0, w->stream, m32, nb, n_words,
-                           w->d_tile.get());
-        hipLaunchKernelGGL(k_dd_scan, dim3(1), dim3(kScanThreads), 0, w->stream, w->d_tile.get(), n_tiles, &dctl->n_ends);
-        hipLaunchKernelGGL(k_dd_chunk_ends, dim3((uint32_t)n_tiles), dim3(kDdThreads), 0, w->stream, m32, nb, n_words,
-                           w->d_tile.get(), nu, w->d_pend.get());
-        if (rebuild) {
-            WCHK(hipMemsetAsync(t.slots, 0xFF, (t.mask + 1) * 8, w->stream));
-            if (w->n_unique)
-                hipLaunchKernelGGL(k_wc_rehash, dim3(blocks_for(w->n_unique)), dim3(kDdThreads), 0, w->stream, w->acc(), t,
-                                   w->max_chunk, w->hash_bits);
-        }
-        // 2. lookup, 3. scan
-        hipLaunchKernelGGL(k_wc_lookup, dim3(n_blk), dim3(kDdThreads), 0, w->stream, ptext, w->d_pend.get(), pweights, nu,
-                           repeat, w->acc(), t, w->max_chunk, w->hash_bits, w->d_hash.get(), w->d_new.get(), blk_cnt,
-                           blk_bytes, dctl);
-        hipLaunchKernelGGL(k_dd_scan, dim3(1), dim3(kScanThreads), 0, w->stream, blk_cnt, (uint64_t)n_blk, &dctl->n_new);
-        hipLaunchKernelGGL(k_dd_scan, dim3(1), dim3(kScanThreads), 0, w->stream, blk_bytes, (uint64_t)n_blk,
-                           &dctl->n_new_bytes);
-        WCHK(hipGetLastError());
-        WCHK(hipEventRecord(w->ev1, w->stream));
-        WcCtl ctl = {};
-        WCHK(hipMemcpyAsync(&ctl, w->d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, w->stream));
-        WCHK(hipStreamSynchronize(w->stream));
-        if ((rc = wc_add_ms(w)) != MBPE_OK) return rc;
-        // (weights of entries that were found have grown already: from here on the piece counts)
-        w->overflow = w->overflow || ctl.overflow != 0;
-        if (ctl.n_ends != nu || ctl.n_new > nu || ctl.n_new_bytes > nb || ctl.n_new_bytes < ctl.n_new)
-            return fail(MBPE_ERR_HIP, "wordcount: the device counted impossible new chunks");
-        // 4. append
-        if (ctl.n_new) {
-            const uint64_t n_after = w->n_unique + ctl.n_new, b_after = w->n_bytes + ctl.n_new_bytes;
-            if ((rc = w->d_text.grow(w->n_bytes, (b_after + 15) / 16 * 16, w->mem, w->stream)) != MBPE_OK) return rc;
-            if ((rc = w->d_ends.grow(w->n_unique * 8, n_after * 8, w->mem, w->stream)) != MBPE_OK) return rc;
-            if ((rc = w->d_weights.grow(w->n_unique * 8, n_after * 8, w->mem, w->stream)) != MBPE_OK) return rc;
-            if ((rc = w->d_first.grow(w->n_unique * 8, n_after * 8, w->mem, w->stream)) != MBPE_OK) return rc;
-            WCHK(hipEventRecord(w->ev0, w->stream));
-            hipLaunchKernelGGL(k_wc_append, dim3(n_blk), dim3(kDdThreads), 0, w->stream, ptext, w->d_pend.get(), pweights,
-                               reinterpret_cast<const unsigned long long *>(pfirst), nu, repeat, w->chunk_base, w->acc(), t,
-                               w->max_chunk, w->d_hash.get(), w->d_new.get(), blk_cnt, blk_bytes, (uint64_t)ctl.n_new,
-                               (uint64_t)ctl.n_new_bytes);
-            WCHK(hipGetLastError());
-            WCHK(hipEventRecord(w->ev1, w->stream));
-            WCHK(hipStreamSynchronize(w->stream));
-            if ((rc = wc_add_ms(w)) != MBPE_OK) return rc;
-            w->n_unique = n_after;
-            w->n_bytes = b_after;
-        }
-        kept = ctl.piece_chunks;
+        const WcSource<uint32_t> s = {ptext, reinterpret_cast<const uint32_t *>(pmask), nullptr, pweights,
+                                      reinterpret_cast<const unsigned long long *>(pfirst), nu, nb};
+        if ((rc = wc_fold_source(w, s, repeat, &kept)) != MBPE_OK) return rc;
     }
     w->n_chunks_total += kept * repeat;
     w->chunk_base += (piece_input_chunks == kWcKeptChunks ? kept : piece_input_chunks) * repeat;
     w->n_pieces += 1;
+    return MBPE_OK;
+}
+
+// Another table -> the accumulated table: its entries on this object's device, vouched for (another object's, or a blob's
+// after wordcount_blob_check and wc_distinct), and its totals
+struct WcIncoming {
+    WcSource<unsigned long long> s;
+    uint64_t n_pieces, n_chunks_total, chunk_base;
+};
+int wc_fold_table(mbpe_wordcount *w, const WcIncoming &in) {
+    w->views_valid = false;
+    uint64_t sum = 0;
+    if (in.s.nu) {
+        const int rc = wc_fold_source(w, in.s, 1, &sum);
+        if (rc != MBPE_OK) return rc;
+    }
+    w->n_chunks_total += in.n_chunks_total;
+    w->chunk_base += in.chunk_base;
+    w->n_pieces += in.n_pieces;
+    return MBPE_OK;
+}
+
+// are the hashed chunks of s pairwise distinct?  Touches the scratch table only
+int wc_distinct(mbpe_wordcount *w, const WcSource<unsigned long long> &s, bool *distinct_out) {
+    int rc;
+    const uint32_t bits = dedup_table_bits(s.nu);
+    if ((rc = w->d_ctl.reserve(sizeof(WcCtl), w->mem)) != MBPE_OK) return rc;
+    if ((rc = w->d_scratch.reserve((1ull << bits) * 8, w->mem)) != MBPE_OK) return rc;
+    const WcTable t = {w->d_scratch.get(), (1ull << bits) - 1, bits};
+    WcCtl *dctl = reinterpret_cast<WcCtl *>(w->d_ctl.get());
+    WCHK(hipEventRecord(w->ev0, w->stream));
+    WCHK(hipMemsetAsync(w->d_ctl, 0, sizeof(WcCtl), w->stream));
+    WCHK(hipMemsetAsync(t.slots, 0xFF, (t.mask + 1) * 8, w->stream));
+    hipLaunchKernelGGL(k_wc_distinct, dim3(blocks_for(s.nu)), dim3(kDdThreads), 0, w->stream, s.text, s.ends, s.nu, t,
+                       w->max_chunk, w->hash_bits, &dctl->dup);
+    WCHK(hipGetLastError());
+    WCHK(hipEventRecord(w->ev1, w->stream));
+    WcCtl ctl = {};
+    WCHK(hipMemcpyAsync(&ctl, w->d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, w->stream));
+    WCHK(hipStreamSynchronize(w->stream));
+    if ((rc = wc_add_ms(w)) != MBPE_OK) return rc;
+    *distinct_out = ctl.dup == 0;
     return MBPE_OK;
 }
 
@@ -333,7 +449,8 @@ int mbpe_wordcount_set_option(mbpe_wordcount *w, const char *name, int64_t value
     if (!(is_max && value >= 0 && value <= 0x7FFFFFFF) && !(is_bits && value >= 0 && value <= 64))
         return fail(MBPE_ERR_ARG, std::string("mbpe_wordcount_set_option: unknown option or bad value: ") + name);
     if (!w) return fail(MBPE_ERR_ARG, "mbpe_wordcount_set_option: NULL argument");
-    if (w->n_pieces) return fail(MBPE_ERR_STATE, "mbpe_wordcount_set_option: a piece has been added already");
+    if (w->n_pieces || w->n_unique || w->chunk_base)
+        return fail(MBPE_ERR_STATE, "mbpe_wordcount_set_option: a piece has been added already");
     const int rc = mbpe_dedup_set_option(w->dd, name, value);
     if (rc != MBPE_OK) return rc;
     (is_max ? w->max_chunk : w->hash_bits) = (uint32_t)value;
@@ -348,6 +465,7 @@ int mbpe_wordcount_add_endmask(mbpe_wordcount *w, const uint8_t *text_dev, uint6
     wc_report(w, n_unique_total_out, n_unique_bytes_total_out);
     uint64_t nu = 0, nb = 0;
     w->last_ms = 0.f;
+    w->last_was_add = true;
     int rc = mbpe_dedup_chunks_endmask(w->dd, text_dev, n_bytes, endmask_dev, &nu, &nb);      // (checks the alignment)
     if (rc != MBPE_OK) return rc;
     WCHK(hipSetDevice(w->device));
@@ -365,6 +483,7 @@ int mbpe_wordcount_add(mbpe_wordcount *w, const uint8_t *text, uint64_t n_bytes,
     wc_report(w, n_unique_total_out, n_unique_bytes_total_out);
     uint64_t nu = 0, nb = 0;
     w->last_ms = 0.f;
+    w->last_was_add = true;
     int rc = mbpe_dedup_chunks(w->dd, text, n_bytes, text_on_device, chunk_off, n_chunks, &nu, &nb);   // (checks the rest)
     if (rc != MBPE_OK) return rc;
     WCHK(hipSetDevice(w->device));
@@ -429,6 +548,91 @@ int mbpe_wordcount_get(mbpe_wordcount *w, uint8_t *text_out, uint64_t *chunk_off
     return MBPE_OK;
 }
 
+int mbpe_wordcount_export_size(const mbpe_wordcount *w, uint64_t *n_bytes_out) {
+    if (!w || !n_bytes_out) return fail(MBPE_ERR_ARG, "mbpe_wordcount_export_size: NULL argument");
+    const int rc = wc_usable(w, "mbpe_wordcount_export_size");
+    if (rc != MBPE_OK) return rc;
+    *n_bytes_out = wordcount_blob_size(w->n_unique, w->n_bytes);
+    return MBPE_OK;
+}
+
+int mbpe_wordcount_export(mbpe_wordcount *w, uint8_t *blob_out, uint64_t cap_bytes, uint64_t *n_bytes_out) {
+    if (!w || !blob_out) return fail(MBPE_ERR_ARG, "mbpe_wordcount_export: NULL argument");
+    const int rc = wc_usable(w, "mbpe_wordcount_export");
+    if (rc != MBPE_OK) return rc;
+    const uint64_t nu = w->n_unique, nb = w->n_bytes, size = wordcount_blob_size(nu, nb);
+    if (cap_bytes < size) return fail(MBPE_ERR_ARG, "mbpe_wordcount_export: blob_out is too small");
+    WCHK(hipSetDevice(w->device));
+    const uint32_t head[2] = {kWordcountBlobMagic, kWordcountBlobVersion};
+    const uint64_t fields[7] = {w->max_chunk, nu, nb, w->n_pieces, w->n_chunks_total, w->chunk_base, 0};
+    memcpy(blob_out, head, 8);
+    memcpy(blob_out + 8, fields, 56);
+    uint8_t *at = blob_out + kWordcountBlobHeader;
+    for (const unsigned long long *src : {w->d_ends.get(), w->d_weights.get(), w->d_first.get()}) {
+        if (nu) WCHK(hipMemcpy(at, src, nu * 8, hipMemcpyDeviceToHost));
+        at += nu * 8;
+    }
+    if (nb) WCHK(hipMemcpy(at, w->d_text, nb, hipMemcpyDeviceToHost));
+    memset(at + nb, 0, size - (uint64_t)(at - blob_out) - nb);
+    if (n_bytes_out) *n_bytes_out = size;
+    return MBPE_OK;
+}
+
+int mbpe_wordcount_merge_blob(mbpe_wordcount *w, const uint8_t *blob, uint64_t n_bytes, uint64_t *n_unique_total_out,
+                              uint64_t *n_unique_bytes_total_out) {
+    if (!w || !blob) return fail(MBPE_ERR_ARG, "mbpe_wordcount_merge_blob: NULL argument");
+    wc_report(w, n_unique_total_out, n_unique_bytes_total_out);
+    WordcountBlob b;
+    const char *why = wordcount_blob_check(blob, n_bytes, &b);
+    if (why) return fail(MBPE_ERR_ARG, std::string("mbpe_wordcount_merge_blob: ") + why);
+    if (b.max_chunk_bytes != w->max_chunk)
+        return fail(MBPE_ERR_ARG, "mbpe_wordcount_merge_blob: counted with another max_chunk_bytes");
+    WCHK(hipSetDevice(w->device));
+    w->last_ms = 0.f;
+    w->last_was_add = false;
+    int rc;
+    WcIncoming in = {{nullptr, nullptr, nullptr, nullptr, nullptr, b.n_unique, b.n_bytes},
+                     b.n_pieces, b.n_chunks_total, b.chunk_base};
+    if (b.n_unique) {
+        // ends, weights and first_chunk lie back to back in the blob: one upload, and one for the text
+        const uint64_t nu = b.n_unique;
+        if ((rc = w->d_in.reserve(nu * 24, w->mem)) != MBPE_OK) return rc;
+        if ((rc = w->d_in_text.reserve((b.n_bytes + 15) / 16 * 16, w->mem)) != MBPE_OK) return rc;
+        WCHK(hipMemcpyAsync(w->d_in, b.ends, nu * 24, hipMemcpyHostToDevice, w->stream));
+        WCHK(hipMemcpyAsync(w->d_in_text, b.text, b.n_bytes, hipMemcpyHostToDevice, w->stream));
+        in.s.text = w->d_in_text;
+        in.s.ends = w->d_in;
+        in.s.weights = w->d_in.get() + nu;
+        in.s.first = w->d_in.get() + 2 * nu;
+        // nothing of the table changes before the incoming chunks are known to be distinct
+        bool distinct = false;
+        if ((rc = wc_distinct(w, in.s, &distinct)) != MBPE_OK) return rc;
+        if (!distinct) return fail(MBPE_ERR_ARG, "mbpe_wordcount_merge_blob: a hashed chunk is present twice");
+    }
+    if ((rc = wc_fold_table(w, in)) != MBPE_OK) return rc;
+    wc_report(w, n_unique_total_out, n_unique_bytes_total_out);
+    return MBPE_OK;
+}
+
+int mbpe_wordcount_merge(mbpe_wordcount *w, const mbpe_wordcount *other) {
+    if (!w || !other) return fail(MBPE_ERR_ARG, "mbpe_wordcount_merge: NULL argument");
+    if (w == other) return fail(MBPE_ERR_ARG, "mbpe_wordcount_merge: an object cannot be merged into itself");
+    if (w->device != other->device)
+        return fail(MBPE_ERR_ARG, "mbpe_wordcount_merge: the objects are on different devices (mbpe_wordcount_merge_blob)");
+    if (w->max_chunk != other->max_chunk || w->hash_bits != other->hash_bits)
+        return fail(MBPE_ERR_ARG, "mbpe_wordcount_merge: the objects' options differ");
+    const int rc = wc_usable(other, "mbpe_wordcount_merge");
+    if (rc != MBPE_OK) return rc;
+    WCHK(hipSetDevice(w->device));
+    w->last_ms = 0.f;
+    w->last_was_add = false;
+    // (every call of `other` ended synchronised: its buffers are at rest, and its own entries are distinct as they are)
+    const WcIncoming in = {{other->d_text.get(), nullptr, other->d_ends.get(), other->d_weights.get(), other->d_first.get(),
+                            other->n_unique, other->n_bytes},
+                           other->n_pieces, other->n_chunks_total, other->chunk_base};
+    return wc_fold_table(w, in);
+}
+
 int mbpe_wordcount_stats(const mbpe_wordcount *w, uint64_t *n_pieces_out, uint64_t *n_chunks_total_out,
                          uint64_t *n_unique_out, uint64_t *n_unique_bytes_out) {
     if (!w) return fail(MBPE_ERR_ARG, "mbpe_wordcount_stats: NULL argument");
@@ -455,7 +659,7 @@ int mbpe_wordcount_kernel_ms(const mbpe_wordcount *w, float *ms_out) {
     float dd_ms = 0.f;
     const int rc = mbpe_dedup_kernel_ms(w->dd, &dd_ms);
     if (rc != MBPE_OK) return rc;
-    *ms_out = dd_ms + w->last_ms;
+    *ms_out = (w->last_was_add ? dd_ms : 0.f) + w->last_ms;      // (a merge does not run the deduper)
     return MBPE_OK;
 }
 

@@ -1,7 +1,7 @@
 // minbpe-cc: the reference's command line (code/examples/minbpe-cc.cpp:92-265)
 // on top of the MI355X training path.  Same flags, defaults, messages and exit
 // codes; `--train -c lexical` runs on the GPU.  The only additions are --device, the --device-* switches, --rank-order,
-// --dropout / --seed, --byte-ranges-out, --continue-from and --input-list.
+// --dropout / --seed, --byte-ranges-out, --continue-from, --input-list, and --count / --counts / --counts-out.
 #include "mbpe.h"
 #include "mbpe_tokenizer.h"
 
@@ -108,6 +108,21 @@ void usage() {
                  "                              piece is split on its own, so cut files where a letter or digit is followed by\n"
                  "                              whitespace.  Combines with --device-split, --device-split-unicode,\n"
                  "                              --continue-from, -c and -w; with --input or without --train it is an error\n"
+                 "  --count                     Count only: split the pieces of --input-list, count their chunks on the HIP device\n"
+                 "                              and write the counts to --counts-out.  Nothing is trained and no model is\n"
+                 "                              written.  Many runs, on many devices or machines, can each count a share of a\n"
+                 "                              corpus; --train --counts trains on all of them.  Combines with --encoder,\n"
+                 "                              --device, --device-split, --device-split-unicode and --counts; with --train,\n"
+                 "                              --encode, --decode or --input it is an error\n"
+                 "  --counts-out TEXT           With --count (required there): the file the counts are written to\n"
+                 "  --counts TEXT               With --train or --count, repeatable: counts written by --count, merged in the\n"
+                 "                              order given before any --input-list pieces.  --train --counts a --counts b is\n"
+                 "                              the model of --train --input-list over all the pieces behind a and b, in that\n"
+                 "                              order (given out of order: the same counts, but -c first sees the first\n"
+                 "                              occurrences of that order); --count --counts ckpt --input-list rest continues\n"
+                 "                              a counting run.  The counts must come from the same --encoder; a missing or\n"
+                 "                              malformed file is an error.  Excludes --input.  The training itself runs on one\n"
+                 "                              HIP device\n"
                  "  --min-frequency INT         With --train: the training ends when the best pair left occurs less often than\n"
                  "                              this (0, the default: no such rule), with fewer merges than --vocab-size asks for\n"
                  "  --max-token-length INT      With --train: no new token is longer than this many bytes (0, the default: no\n"
@@ -122,10 +137,12 @@ void usage() {
 
 int main(int argc, char *argv[]) {
     std::string input_path, input_list_path, output_path, special_token_path, encoder = "gpt4", model_path = "./output.model",
-                continue_from, byte_ranges_path;
+                continue_from, byte_ranges_path, counts_out_path;
+    std::vector<std::string> counts_paths;
     std::string conflict_resolution_str = "first";
     bool train = false, decode = false, encode = false, write_vocab = false, verbose = false, device_encode = false,
-         device_decode = false, device_split = false, split_unicode = false, rank_order = false, dedup = false;
+         device_decode = false, device_split = false, split_unicode = false, rank_order = false, dedup = false,
+         count = false;
     int vocab_size = 512, device = 0;
     long long min_frequency = 0, max_token_length = 0;
     bool have_limits = false;
@@ -155,6 +172,8 @@ int main(int argc, char *argv[]) {
         else if (arg == "--encoder") { if (!value(&encoder)) return 106; }
         else if (arg == "--continue-from") { if (!value(&continue_from)) return 106; }
         else if (arg == "--byte-ranges-out") { if (!value(&byte_ranges_path)) return 106; }
+        else if (arg == "--counts-out") { if (!value(&counts_out_path)) return 106; }
+        else if (arg == "--counts") { if (!value(&tmp)) return 106; counts_paths.push_back(tmp); }
         else if (arg == "--vocab-size") {
             if (!value(&tmp)) return 106;
             try { vocab_size = std::stoi(tmp); } catch (...) { std::cerr << "--vocab-size: invalid integer " << tmp << "\n"; return 104; }
@@ -197,6 +216,7 @@ int main(int argc, char *argv[]) {
         else if (arg == "--device-split-unicode") device_split = split_unicode = true;
         else if (arg == "--rank-order") rank_order = true;
         else if (arg == "--dedup") dedup = true;
+        else if (arg == "--count") count = true;
         else if (arg == "-v" || arg == "--verbose") verbose = true;
         else { std::cerr << "The following argument was not expected: " << arg << "\n"; return 109; }
     }
@@ -212,11 +232,20 @@ int main(int argc, char *argv[]) {
 
     if (have_limits && !train) { std::cerr << "--min-frequency and --max-token-length require --train\n"; return 107; }
 
+    if (count && (train || encode || decode)) { std::cerr << "--count excludes --train, --encode and --decode\n"; return 107; }
+    if (count && counts_out_path.empty()) { std::cerr << "--count requires --counts-out\n"; return 107; }
+    if (!counts_out_path.empty() && !count) { std::cerr << "--counts-out requires --count\n"; return 107; }
+    if (!counts_paths.empty() && !train && !count) { std::cerr << "--counts requires --train or --count\n"; return 107; }
+    if (!counts_paths.empty() && !input_path.empty()) { std::cerr << "--counts excludes --input\n"; return 107; }
+    if (count && !input_path.empty()) { std::cerr << "--count takes --input-list, not --input\n"; return 107; }
+    for (const std::string &c : counts_paths)
+        if (!exists(c)) { std::cerr << "Counts file " << c << " does not exist\n"; return -1; }
+
     struct Piece { std::string path; uint32_t repeat; };
     std::vector<Piece> pieces;
     if (!input_list_path.empty()) {
         if (!input_path.empty()) { std::cerr << "--input-list excludes --input\n"; return 107; }
-        if (!train) { std::cerr << "--input-list requires --train\n"; return 107; }
+        if (!train && !count) { std::cerr << "--input-list requires --train or --count\n"; return 107; }
         if (!exists(input_list_path)) { std::cerr << "Input file " << input_list_path << " does not exist\n"; return -1; }
         std::ifstream list(input_list_path);
         for (std::string line; std::getline(list, line);) {
@@ -240,7 +269,7 @@ int main(int argc, char *argv[]) {
         }
     } else if (!input_path.empty()) {                           // :135-144
         if (!exists(input_path)) { std::cerr << "Input file " << input_path << " does not exist\n"; return -1; }
-    } else {
+    } else if (counts_paths.empty()) {
         std::cerr << "Input file not specified\n";
         return -1;
     }
@@ -279,28 +308,51 @@ int main(int argc, char *argv[]) {
         mbpe_tok_destroy(rt);
         return 105;
     }
+    // --counts and --input-list: opens the pieces session, merges the counts files in the order given, then reads the
+    // pieces one at a time.  false: a file could not be used (said on stderr; counts_failed for a counts file);
+    // *trc: the code of the library call that failed, if one did
+    bool counts_failed = false;
+    auto feed_session = [&](int *trc) -> bool {
+        std::string data, err;
+        if (split_unicode) mbpe_tok_set_split_unicode(rt, 1);
+        *trc = mbpe_tok_train_pieces_begin(rt, device, device_split);
+        for (size_t k = 0; k < counts_paths.size() && *trc == MBPE_OK; ++k) {
+            if (verbose) std::cout << "Loading counts " << counts_paths[k] << "\n";
+            if (!load_file_to_string(counts_paths[k], &data, &err)) {
+                std::cerr << "Failed to load counts file " << counts_paths[k] << ": " << err << "\n";
+                return !(counts_failed = true);
+            }
+            if (mbpe_tok_train_pieces_merge(rt, reinterpret_cast<const uint8_t *>(data.data()), data.size()) != MBPE_OK) {
+                std::cerr << "Counts file " << counts_paths[k] << " was refused: " << mbpe_last_error() << "\n";
+                return !(counts_failed = true);
+            }
+        }
+        for (size_t k = 0; k < pieces.size() && *trc == MBPE_OK; ++k) {
+            if (verbose) std::cout << "Loading file " << pieces[k].path << "\n";
+            if (!load_file_to_string(pieces[k].path, &data, &err)) {
+                std::cerr << "Failed to load training input file: " << err << "\n";
+                return false;
+            }
+            *trc = mbpe_tok_train_pieces_add(rt, reinterpret_cast<const uint8_t *>(data.data()), data.size(), pieces[k].repeat);
+        }
+        return true;
+    };
     if (train) {                                                // :181-211
         if (have_special) mbpe_tok_set_special_tokens(rt, special_tokens_data.data(), special_tokens_data.size());
         else std::cout << "No special tokens file provided\n";
-        std::cout << "Training using file \"" << (input_list_path.empty() ? input_path : input_list_path) << "\" encoder "
-                  << encoder << " vocab size " << vocab_size << " model path " << model_path << "\n";
+        const std::string &named = !input_list_path.empty() ? input_list_path : !input_path.empty() ? input_path : counts_paths[0];
+        std::cout << "Training using file \"" << named << "\" encoder " << encoder << " vocab size " << vocab_size
+                  << " model path " << model_path << "\n";
         const int cr = conflict_resolution_str == "lexical" ? 1 : 0;
         std::string input, err;
-        if (!input_list_path.empty()) {
-            // the corpus in pieces: one file in memory at a time, its chunks counted on the device
-            if (split_unicode) mbpe_tok_set_split_unicode(rt, 1);
-            int trc = mbpe_tok_train_pieces_begin(rt, device, device_split);
-            bool read_ok = true;
-            for (size_t k = 0; k < pieces.size() && trc == MBPE_OK && read_ok; ++k) {
-                if (verbose) std::cout << "Loading file " << pieces[k].path << "\n";
-                read_ok = load_file_to_string(pieces[k].path, &input, &err);
-                if (read_ok)
-                    trc = mbpe_tok_train_pieces_add(rt, reinterpret_cast<const uint8_t *>(input.data()), input.size(),
-                                                    pieces[k].repeat);
-            }
+        if (!input_list_path.empty() || !counts_paths.empty()) {
+            // the corpus in pieces: counts made earlier first, then one file in memory at a time, its chunks counted on
+            // the device
+            int trc = MBPE_OK;
+            const bool read_ok = feed_session(&trc);
             if (!read_ok) {
-                std::cerr << "Failed to load training input file: " << err << "\n";
                 mbpe_tok_train_pieces_abort(rt);
+                if (counts_failed) rc = -1;
             } else {
                 if (verbose && trc == MBPE_OK) std::cout << "Starting training...\n";
                 if (trc == MBPE_OK)
@@ -335,6 +387,41 @@ int main(int argc, char *argv[]) {
                 std::cerr << "Failed to load training input file: " << err << "\n";
             }
         }
+    } else if (count) {
+        // the counting stage alone: nothing is trained and no model is written
+        std::cout << "Counting chunks, encoder " << encoder << ", counts to " << counts_out_path << "\n";
+        int trc = MBPE_OK;
+        bool ok = feed_session(&trc);
+        if (ok && trc != MBPE_OK) {
+            std::cerr << "Error: " << mbpe_last_error() << "\n";
+            ok = false;
+        }
+        uint64_t n = 0;
+        std::vector<uint8_t> blob;
+        if (ok) {
+            trc = mbpe_tok_train_pieces_export_size(rt, &n);
+            if (trc == MBPE_OK) {
+                blob.resize(n);
+                trc = mbpe_tok_train_pieces_export(rt, blob.data(), blob.size(), &n);
+            }
+            if (trc != MBPE_OK) {
+                std::cerr << "Error: " << mbpe_last_error() << "\n";
+                ok = false;
+            }
+        }
+        mbpe_tok_train_pieces_abort(rt);
+        if (ok) {
+            std::ofstream file(counts_out_path, std::ios::binary);
+            file.write(reinterpret_cast<const char *>(blob.data()), (std::streamsize)n);
+            file.close();
+            if (!file) {
+                std::cerr << "Failed to write " << counts_out_path << "\n";
+                ok = false;
+            } else {
+                std::cout << "Wrote " << n << " bytes of counts\n";
+            }
+        }
+        if (!ok) rc = -1;
     } else if (encode) {                                        // :212-242
         if (output_path.empty()) { std::cerr << "Output file not specified\n"; mbpe_tok_destroy(rt); return -1; }
         if (!exists(model_path)) { std::cerr << "Model file " << model_path << " does not exist\n"; mbpe_tok_destroy(rt); return -1; }

@@ -409,6 +409,57 @@ void Tokenizer::train_pieces_add(const char *text, uint64_t n, uint32_t repeat) 
     pieces_.n_bytes += n * repeat;
 }
 
+// The session's counts as a blob: 32 bytes -- u32 magic "MBTC", u32 version, u64 length of the split pattern, u64 chunks
+// and u64 bytes the session has seen (what the verbose lines of finish report) -- then the pattern padded with zeros to
+// 8 bytes, then the blob of mbpe_wordcount_export.  Little-endian, as the hosts this runs on.
+namespace {
+constexpr uint32_t kCountsMagic = 0x4354424Du, kCountsVersion = 1;        // "MBTC"
+constexpr uint64_t kCountsHeader = 32;
+uint64_t counts_prefix(uint64_t pattern_len) { return kCountsHeader + (pattern_len + 7) / 8 * 8; }
+}  // namespace
+
+uint64_t Tokenizer::train_pieces_export_size() {
+    if (!pieces_.open) throw CodedError(MBPE_ERR_STATE, "train_pieces_export: no session is open (train_pieces_begin)");
+    uint64_t n = 0;
+    const int rc = mbpe_wordcount_export_size(pieces_.wc, &n);
+    if (rc != MBPE_OK) throw CodedError(rc, mbpe_last_error());
+    return counts_prefix(pattern_.size()) + n;
+}
+
+uint64_t Tokenizer::train_pieces_export(uint8_t *blob_out, uint64_t cap) {
+    const uint64_t size = train_pieces_export_size(), prefix = counts_prefix(pattern_.size());
+    if (cap < size) throw CodedError(MBPE_ERR_ARG, "train_pieces_export: blob_out is too small");
+    const uint32_t head[2] = {kCountsMagic, kCountsVersion};
+    const uint64_t fields[3] = {pattern_.size(), pieces_.n_chunks, pieces_.n_bytes};
+    memset(blob_out, 0, prefix);
+    memcpy(blob_out, head, 8);
+    memcpy(blob_out + 8, fields, 24);
+    memcpy(blob_out + kCountsHeader, pattern_.data(), pattern_.size());
+    const int rc = mbpe_wordcount_export(pieces_.wc, blob_out + prefix, cap - prefix, nullptr);
+    if (rc != MBPE_OK) throw CodedError(rc, mbpe_last_error());
+    return size;
+}
+
+void Tokenizer::train_pieces_merge(const uint8_t *blob, uint64_t n) {
+    if (!pieces_.open) throw CodedError(MBPE_ERR_STATE, "train_pieces_merge: no session is open (train_pieces_begin)");
+    uint32_t head[2] = {0, 0};
+    uint64_t fields[3] = {0, 0, 0};
+    if (n >= kCountsHeader) {
+        memcpy(head, blob, 8);
+        memcpy(fields, blob + 8, 24);
+    }
+    if (n < kCountsHeader || head[0] != kCountsMagic || head[1] != kCountsVersion || fields[0] > n - kCountsHeader ||
+        counts_prefix(fields[0]) > n)
+        throw CodedError(MBPE_ERR_ARG, "train_pieces_merge: not a counts blob (truncated, bad magic or unknown version)");
+    if (fields[0] != pattern_.size() || memcmp(blob + kCountsHeader, pattern_.data(), pattern_.size()) != 0)
+        throw CodedError(MBPE_ERR_ARG, "train_pieces_merge: the blob was counted under another split pattern");
+    const uint64_t prefix = counts_prefix(fields[0]);
+    const int rc = mbpe_wordcount_merge_blob(pieces_.wc, blob + prefix, n - prefix, nullptr, nullptr);
+    if (rc != MBPE_OK) throw CodedError(rc, mbpe_last_error());
+    pieces_.n_chunks += fields[1];
+    pieces_.n_bytes += fields[2];
+}
+
 void Tokenizer::train_pieces_finish(int vocab_size, CONFLICT_RESOLUTION conflict_resolution, bool verbose, bool resume) {
     if (!pieces_.open) throw CodedError(MBPE_ERR_STATE, "train_pieces_finish: no session is open (train_pieces_begin)");
     // the session ends here, however this goes; the merges stay as they are until the training has succeeded
@@ -1154,6 +1205,24 @@ int mbpe_tok_train_pieces_finish(mbpe_tokenizer *t, uint32_t vocab_size, int con
                                   conflict_resolution ? mbpe_host::Tokenizer::LEXICAL : mbpe_host::Tokenizer::FIRST,
                                   verbose != 0, resume != 0);
     });
+}
+
+int mbpe_tok_train_pieces_export_size(mbpe_tokenizer *t, uint64_t *n_bytes_out) {
+    if (!t || !n_bytes_out) return null_argument("mbpe_tok_train_pieces_export_size");
+    return coded([&] { *n_bytes_out = t->t->train_pieces_export_size(); });
+}
+
+int mbpe_tok_train_pieces_export(mbpe_tokenizer *t, uint8_t *blob_out, uint64_t cap_bytes, uint64_t *n_bytes_out) {
+    if (!t || !blob_out) return null_argument("mbpe_tok_train_pieces_export");
+    return coded([&] {
+        const uint64_t n = t->t->train_pieces_export(blob_out, cap_bytes);
+        if (n_bytes_out) *n_bytes_out = n;
+    });
+}
+
+int mbpe_tok_train_pieces_merge(mbpe_tokenizer *t, const uint8_t *blob, uint64_t n_bytes) {
+    if (!t || !blob) return null_argument("mbpe_tok_train_pieces_merge");
+    return coded([&] { t->t->train_pieces_merge(blob, n_bytes); });
 }
 
 int mbpe_tok_train_pieces_abort(mbpe_tokenizer *t) {

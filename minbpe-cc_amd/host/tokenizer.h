@@ -50,6 +50,13 @@ public:
     void train_pieces_add(const char *text, uint64_t n, uint32_t repeat);
     void train_pieces_finish(int vocab_size, CONFLICT_RESOLUTION conflict_resolution, bool verbose, bool resume);
     void train_pieces_abort();
+    // The open session's counts as a blob, and a blob merged into the open session (mbpe_tok_train_pieces_export /
+    // _merge): the blob of mbpe_wordcount_export behind the split pattern and the chunks and bytes the session has seen,
+    // so that a session which merged the blobs of all pieces finishes like one that was given all pieces.  A blob counted
+    // under another pattern is CodedError(MBPE_ERR_ARG); without a session MBPE_ERR_STATE.  The session goes on
+    uint64_t train_pieces_export_size();
+    uint64_t train_pieces_export(uint8_t *blob_out, uint64_t cap);
+    void train_pieces_merge(const uint8_t *blob, uint64_t n);
     // :653-722; device >= 0 runs internal_encode (:325-377) on that HIP device instead of the host.
     // device_split (with device >= 0, here and in the batch calls below): the text is also cut at the special tokens
     // and split into chunks on the device (mbpe_splitter_split_docs with a splitter that is kept), and the encoder

@@ -47,6 +47,7 @@ EXPORTS = [
     "mbpe_wordcount_create", "mbpe_wordcount_destroy", "mbpe_wordcount_add_endmask", "mbpe_wordcount_add",
     "mbpe_wordcount_result", "mbpe_wordcount_get", "mbpe_wordcount_stats", "mbpe_wordcount_reset",
     "mbpe_wordcount_set_option", "mbpe_wordcount_kernel_ms", "mbpe_wordcount_alloc_count",
+    "mbpe_wordcount_export_size", "mbpe_wordcount_export", "mbpe_wordcount_merge_blob", "mbpe_wordcount_merge",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -59,6 +60,7 @@ TOK_EXPORTS = [
     "mbpe_tok_encode_batch_byteoff_device", "mbpe_tok_set_encode_dropout", "mbpe_tok_set_train_dedup",
     "mbpe_tok_set_encode_dedup", "mbpe_tok_train_pieces_begin", "mbpe_tok_train_pieces_add",
     "mbpe_tok_train_pieces_finish", "mbpe_tok_train_pieces_abort", "mbpe_tok_set_train_limits",
+    "mbpe_tok_train_pieces_export_size", "mbpe_tok_train_pieces_export", "mbpe_tok_train_pieces_merge",
 ]
 
 
@@ -277,6 +279,13 @@ def lib():
     L.mbpe_wordcount_set_option.argtypes = [vp, ctypes.c_char_p, i64]
     L.mbpe_wordcount_kernel_ms.argtypes = [vp, vp]
     L.mbpe_wordcount_alloc_count.argtypes = [vp, vp]
+    L.mbpe_wordcount_export_size.argtypes = [vp, vp]
+    L.mbpe_wordcount_export.argtypes = [vp, vp, u64, vp]
+    L.mbpe_wordcount_merge_blob.argtypes = [vp, vp, u64, vp, vp]
+    L.mbpe_wordcount_merge.argtypes = [vp, vp]
+    L.mbpe_tok_train_pieces_export_size.argtypes = [vp, vp]
+    L.mbpe_tok_train_pieces_export.argtypes = [vp, vp, u64, vp]
+    L.mbpe_tok_train_pieces_merge.argtypes = [vp, vp, u64]
     L.mbpe_tok_train_pieces_begin.argtypes = [vp, i32, i32]
     L.mbpe_tok_train_pieces_add.argtypes = [vp, vp, u64, u32]
     L.mbpe_tok_train_pieces_finish.argtypes = [vp, u32, i32, i32, i32]
@@ -1286,8 +1295,34 @@ class WordCount:
         _check(lib().mbpe_wordcount_reset(self._h))
         self.n_unique = self.n_unique_bytes = 0
 
+    def export(self):
+        """The table as bytes (mbpe_wordcount_export): header, ends, weights, first_chunk, text.  The object is
+        unchanged and goes on counting, so this is also a checkpoint.  MbpeError(ERR_OVERFLOW) once a count has
+        reached 2^31."""
+        n = ctypes.c_uint64()
+        _check(lib().mbpe_wordcount_export_size(self._h, ctypes.byref(n)))
+        blob = np.zeros(n.value, dtype=np.uint8)
+        _check(lib().mbpe_wordcount_export(self._h, blob.ctypes.data, n.value, ctypes.byref(n)))
+        return blob[:n.value].tobytes()
+
+    def merge(self, other):
+        """Another table -- the bytes of export(), from any process or device, or a WordCount on the same device, which
+        stays unchanged -- folded into this one: afterwards this is the count of its own pieces followed by the
+        other's, bit for bit what adding all of them here gives.  Merge in piece order for the `first` tie-break's
+        order; any order gives the same weights.  A blob is checked before anything changes: MbpeError(ERR_ARG) naming
+        the rule, the table as it was.  -> the table's (n_unique, n_unique_bytes) after it."""
+        if isinstance(other, WordCount):
+            _check(lib().mbpe_wordcount_merge(self._h, other._h))
+            st = self.stats()
+            self.n_unique, self.n_unique_bytes = st["n_unique"], st["n_unique_bytes"]
+            return self.n_unique, self.n_unique_bytes
+        blob = _u8(other)
+        nu, nb = ctypes.c_uint64(), ctypes.c_uint64()
+        return self._done(lib().mbpe_wordcount_merge_blob(self._h, blob.ctypes.data, len(blob), ctypes.byref(nu),
+                                                          ctypes.byref(nb)), nu, nb)
+
     def kernel_ms(self):
-        """Device time of the latest add: the deduper's kernels and the fold's."""
+        """Device time of the latest add or merge: the deduper's kernels (add) and the fold's, with the check of a blob."""
         ms = ctypes.c_float()
         _check(lib().mbpe_wordcount_kernel_ms(self._h, ctypes.byref(ms)))
         return ms.value
@@ -1635,6 +1670,70 @@ class Tokenizer:
                 with open(p, "rb") as f:
                     yield f.read()
         self.train_from_iterator(read(), vocab_size, **kw)
+
+    def _add_pieces(self, texts, repeats):
+        reps = None if repeats is None else iter(repeats)
+        for data in texts:
+            text = _u8(data)
+            rep = 1 if reps is None else int(next(reps))
+            _check(lib().mbpe_tok_train_pieces_add(self._h, text.ctypes.data if len(text) else None, len(text), rep))
+
+    def _export_pieces(self):
+        n = ctypes.c_uint64()
+        _check(lib().mbpe_tok_train_pieces_export_size(self._h, ctypes.byref(n)))
+        blob = np.zeros(n.value, dtype=np.uint8)
+        _check(lib().mbpe_tok_train_pieces_export(self._h, blob.ctypes.data, n.value, ctypes.byref(n)))
+        return blob[:n.value].tobytes()
+
+    def count_from_iterator(self, texts, repeats=None, device=0, device_split=False, counts=()):
+        """The counting stage of train_from_iterator on its own: the texts are split and their chunks counted on the
+        device, and the counts come back as bytes (mbpe_tok_train_pieces_export) -- the word-count table with the
+        split pattern and the totals of the verbose lines.  Nothing is trained and the merges are untouched.  Many
+        processes, devices or runs can each count a share of the corpus; train_from_counts trains on all of them.
+        counts: blobs merged first, in the order given -- how a counting run continues from a checkpoint.  Moving the
+        bytes is the caller's business (files, torch.distributed.all_gather_object, MPI)."""
+        _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
+        _check(lib().mbpe_tok_train_pieces_begin(self._h, device, int(bool(device_split))))
+        try:
+            for blob in counts:
+                b = _u8(blob)
+                _check(lib().mbpe_tok_train_pieces_merge(self._h, b.ctypes.data, len(b)))
+            self._add_pieces(texts, repeats)
+            return self._export_pieces()
+        finally:
+            lib().mbpe_tok_train_pieces_abort(self._h)
+
+    def count_files(self, paths, **kw):
+        """count_from_iterator over the files' contents, read one at a time."""
+        def read():
+            for p in paths:
+                with open(p, "rb") as f:
+                    yield f.read()
+        return self.count_from_iterator(read(), **kw)
+
+    def train_from_counts(self, blobs, vocab_size, conflict_resolution=1, verbose=False, device=0, resume=False,
+                          min_frequency=0, max_token_length=0, texts=None, device_split=False):
+        """The training stage on counts made elsewhere: the blobs of count_from_iterator are merged in the order given,
+        then any `texts` are added as train_from_iterator adds them (device_split: how these are split), then the
+        training runs -- merges, counts, .model, .vocab and verbose lines of train_from_iterator on all the pieces in
+        that order, for both tie-breaks.  Blobs given out of piece order train on the pieces in that order: the same
+        counts, but the `first` tie-break sees another order of first occurrences.  One rank.  A blob counted under
+        another split pattern or one that fails its checks raises MbpeError(ERR_ARG); the merges stay as they are until
+        the training has succeeded."""
+        _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
+        _check(lib().mbpe_tok_set_train_limits(self._h, int(min_frequency), int(max_token_length)))
+        _check(lib().mbpe_tok_train_pieces_begin(self._h, device, int(bool(device_split))))
+        try:
+            for blob in blobs:
+                b = _u8(blob)
+                _check(lib().mbpe_tok_train_pieces_merge(self._h, b.ctypes.data, len(b)))
+            if texts is not None:
+                self._add_pieces(texts, None)
+            _check(lib().mbpe_tok_train_pieces_finish(self._h, vocab_size, conflict_resolution, int(verbose),
+                                                      int(bool(resume))))
+        except BaseException:
+            lib().mbpe_tok_train_pieces_abort(self._h)
+            raise
 
     def set_merges(self, merges):
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1, 2)
