@@ -1,4 +1,5 @@
-// Host helpers of the translation units that drive the device (train.cpp, encode.hip, decode.hip, pack.hip, split.hip).
+// Host helpers of the translation units that drive the device (train.cpp, wide_run.cpp, encode.hip, decode.hip,
+// pack.hip, split.hip).
 #ifndef MBPE_HIP_HOST_H
 #define MBPE_HIP_HOST_H
 
@@ -39,6 +40,21 @@ inline int find_device(int device_id) {
             return e__ == hipErrorOutOfMemory ? MBPE_ERR_OOM : MBPE_ERR_HIP;  \
         }                                                                     \
     } while (0)
+
+// A kernel that leaves one scalar: a zeroed T on the device, enqueue(T *) puts the work on `stream`, the value comes
+// back in *out once the stream has run.  The scalar is freed on every path.
+template <typename T, typename Enqueue>
+hipError_t read_scalar(hipStream_t stream, T *out, Enqueue enqueue) {
+    T *d = nullptr;
+    hipError_t e = hipMalloc(&d, sizeof(T));
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(d, 0, sizeof(T), stream);
+    if (e == hipSuccess) { enqueue(d); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d, sizeof(T), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    (void)hipFree(d);
+    return e;
+}
 
 // What a handle decides once for all its device memory: clear_last as in MBPE_HIP_CHECK; n_allocs counts the
 // hipMalloc calls that succeeded (mbpe_*_alloc_count)

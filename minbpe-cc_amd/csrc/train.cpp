@@ -11,7 +11,9 @@
 // compaction of holes, growth of the pair table.
 #include "mbpe.h"
 #include "mbpe_dev.h"
-#include "wide.h"
+#include "dev_pool.h"
+#include "wide_run.h"
+#include "train_plan.h"
 #include "split.h"
 #include "hip_host.h"
 
@@ -23,7 +25,6 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -51,13 +52,6 @@ void dfree(T *&p) {
 }
 
 }  // namespace
-
-struct mbpe_ctx;
-namespace {
-template <typename T> hipError_t tmalloc(mbpe_ctx *c, T **p, size_t bytes);
-template <typename T> void tfree(mbpe_ctx *c, T *&p);
-void pool_trim(mbpe_ctx *c);
-}
 
 // ---- RCCL, bound at run time: the library loads and runs on one GPU without it ----
 namespace {
@@ -237,9 +231,9 @@ struct mbpe_ctx {
     uint32_t *seq_flags = nullptr;  // per sequence of a group: 1 = a fused pass ran (opt_time_kernels)
     std::vector<uint32_t> h_seq_flags;
 
-    // 32-bit continuation of a training whose vocabulary lies beyond the 16-bit slot format (wide.h)
+    // 32-bit continuation of a training whose vocabulary lies beyond the 16-bit slot format (wide.h, wide_run.h)
     bool wide = false;               // this training hands over to the 32-bit loop after n_target merges
-    bool wide_active = false;        // ... and has done so
+    WideRun wr;                      // ... that loop's buffers and state (wr.active: it has done so)
     uint32_t vocab_total = 0;        // the caller's vocab_size (vocab_size is the 16-bit part's)
     uint32_t n_target_total = 0;     // vocab_total - 256
     int64_t opt_wide_from = -1;      // tests: hand over after this many merges whatever the vocabulary (-1: at the format's limit)
@@ -247,82 +241,17 @@ struct mbpe_ctx {
     int64_t opt_resume_wide = 0;     // 1: mbpe_train_begin_from may continue on 32-bit tokens (0: MBPE_ERR_VOCAB, as before)
     int64_t opt_min_frequency = 0;   // stopping rules (wide.h), read by the next begin: either non-zero and the training runs
     int64_t opt_max_token_length = 0;   // on 32-bit tokens from its first new merge, like one on a weighted corpus
-    WideLimits wlim = {};            // ... what the training under way was begun with (wlim.len: vocab_total u32 of the pool)
-    bool wide_direct = false;        // the training began on 32-bit tokens (wide_begin_from): no slot stream, no best[]
+    bool wide_direct = false;        // the training began on 32-bit tokens (begin_wide_direct): no slot stream, no best[]
     std::vector<uint32_t> h_prior_raw;   // ... and its prior merges, (a, b) as given: their ids may need more than 16 bits
-    WideTally *wtally = nullptr;         // ... and the census of its pair count
-    bool wfirst = false;             // the 32-bit loop takes the `first` tie-break (fixed at the conversion)
-    uint32_t *wtok[2] = {nullptr, nullptr};
-    int wcur = 0;
-    uint32_t *wval = nullptr, *wscratch = nullptr;
-    uint32_t *wwt[2] = {nullptr, nullptr};   // weighted corpus: the weight of every token's chunk, beside wtok[]
-    WideTable wtab = {};
-    WideCtl *wctl = nullptr;
-    WideBest *wbest = nullptr;
-    unsigned long long *warg = nullptr;
-    WideFirst *wfs = nullptr;        // `first` tie-break scratch of the 32-bit loop
-    uint64_t wn_upper = 0;           // host-side upper bound of the stream length
-    uint32_t wk = 0;                 // merges of the wide loop known to the host
-    WideCtl h_wctl = {};
-    std::vector<WideBest> h_wbest;   // ... and what they were
 
     mbpe_stats stats = {};
-
-    // Device buffers of a training run are kept when the run ends and handed out again to the next one that asks
-    // for the same sizes (mbpe_train_begin twice on one corpus: no 25 GB of hipFree / hipMalloc in between).
-    std::unordered_map<void *, size_t> pool_live;
-    std::multimap<size_t, void *> pool_idle;
+    DevPool pool;                    // the device buffers of the trainings (dev_pool.h)
 };
 
 namespace {
 
-template <typename T>
-hipError_t tmalloc(mbpe_ctx *c, T **p, size_t bytes) {
-    if (bytes == 0) bytes = 4;
-    auto it = c->pool_idle.find(bytes);
-    if (it != c->pool_idle.end()) {
-        *p = static_cast<T *>(it->second);
-        c->pool_live[it->second] = bytes;
-        c->pool_idle.erase(it);
-        return hipSuccess;
-    }
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e == hipErrorOutOfMemory && !c->pool_idle.empty()) {       // give the idle buffers back and retry
-        pool_trim(c);
-        e = hipMalloc(&q, bytes);
-    }
-    if (e != hipSuccess) return e;
-    c->pool_live[q] = bytes;
-    *p = static_cast<T *>(q);
-    return hipSuccess;
-}
-
-template <typename T>
-void tfree(mbpe_ctx *c, T *&p) {
-    if (!p) return;
-    auto it = c->pool_live.find((void *)p);
-    if (it != c->pool_live.end()) {
-        c->pool_idle.emplace(it->second, it->first);
-        c->pool_live.erase(it);
-    } else {
-        (void)hipFree((void *)p);
-    }
-    p = nullptr;
-}
-
-// a buffer that leaves the pool for good (freed right away)
-template <typename T>
-void trelease(mbpe_ctx *c, T *p) {
-    if (!p) return;
-    c->pool_live.erase((void *)p);
-    (void)hipFree((void *)p);
-}
-
-void pool_trim(mbpe_ctx *c) {
-    for (auto &kv : c->pool_idle) (void)hipFree(kv.second);
-    c->pool_idle.clear();
-}
+// what the 32-bit loop's calls get of the context
+WideDev wide_dev(mbpe_ctx *c) { return WideDev{c->stream, c->ev0, c->ev1, c->pool, c->n_cus, c->stats}; }
 
 int sync_ctl(mbpe_ctx *c) {
     HIPCHK(hipMemcpyAsync(&c->h_ctl, c->ctl, sizeof(DevCtl), hipMemcpyDeviceToHost, c->stream));
@@ -360,33 +289,31 @@ int timed_group(mbpe_ctx *c, Enqueue enqueue) {
     return MBPE_OK;
 }
 
+// The slot stream's buffers and the hashed pair table: what the conversion to the 32-bit loop is done with, and what a
+// training that ends gives back first.  (best[] holds the slot stream's merges and stays.)
+void free_slot_stream(mbpe_ctx *c) {
+    c->pool.free(c->tok[0]); c->pool.free(c->tok[1]);
+    c->pool.free(c->sums); c->pool.free(c->side); c->pool.free(c->chg); c->pool.free(c->tile_list);
+    c->pool.free(c->offsets);
+    c->pool.free(c->tab.hslot); c->pool.free(c->tab.ekey); c->pool.free(c->tab.ecnt);
+    c->pool.free(c->tab.bmax); c->pool.free(c->tab.smax);
+    c->pool.free(c->xb); c->pool.free(c->dlog); c->pool.free(c->dpart);
+    c->pool.free(c->log_state);
+    c->pool.free(c->run_in);
+    c->pool.free(c->first_state);             // (the slot stream's `first` scratch; the 32-bit loop has its own)
+    c->LR = nullptr;
+}
+
 void free_training(mbpe_ctx *c) {
-    tfree(c, c->tok[0]); tfree(c, c->tok[1]);
-    tfree(c, c->sums); tfree(c, c->side); tfree(c, c->chg); tfree(c, c->tile_list);
-    tfree(c, c->offsets);
-    tfree(c, c->tab.hslot); tfree(c, c->tab.ekey); tfree(c, c->tab.ecnt); tfree(c, c->tab.cells);
-    tfree(c, c->tab.bmax); tfree(c, c->tab.smax);
-    tfree(c, c->ctl); tfree(c, c->best); tfree(c, c->xb); tfree(c, c->xb0); tfree(c, c->dlog); tfree(c, c->dpart);
-    tfree(c, c->log_state);
-    tfree(c, c->d_left); tfree(c, c->d_right); tfree(c, c->bs); tfree(c, c->sel); tfree(c, c->seq_flags); tfree(c, c->run_in);
-    tfree(c, c->first_state);
-    tfree(c, c->xf);
-    tfree(c, c->tally);
-    tfree(c, c->wtok[0]); tfree(c, c->wtok[1]); tfree(c, c->wval); tfree(c, c->wscratch);
-    tfree(c, c->wwt[0]); tfree(c, c->wwt[1]);
-    tfree(c, c->wtab.keys); tfree(c, c->wtab.cnts); tfree(c, c->wctl); tfree(c, c->wbest); tfree(c, c->warg);
-    tfree(c, c->wfs); tfree(c, c->wtally);
-    tfree(c, c->wlim.len);
-    c->wlim = {};
-    c->wtab = {};
+    free_slot_stream(c);
+    c->pool.free(c->tab.cells);
+    c->pool.free(c->ctl); c->pool.free(c->best); c->pool.free(c->xb0);
+    c->pool.free(c->d_left); c->pool.free(c->d_right); c->pool.free(c->bs); c->pool.free(c->sel); c->pool.free(c->seq_flags);
+    c->pool.free(c->xf);
+    c->pool.free(c->tally);
+    c->wr.release(c->pool);
     c->wide_direct = false;
     c->h_prior_raw.clear();
-    c->wfirst = false;
-    c->wide_active = false;
-    c->wk = 0;
-    c->wn_upper = 0;
-    c->h_wbest.clear();
-    c->LR = nullptr;
     c->pending = Phase::None;
     c->begun = false;
     c->k = c->n_valid = c->n_prior = 0;
@@ -418,11 +345,11 @@ int alloc_table_dense(mbpe_ctx *c) {
     c->tab.vshift = vshift;
     c->tab.ecap = 1u << (2 * vshift);                 // <= 2^30 cells
     const size_t cells = (size_t)1 << (2 * vshift);
-    HIPCHK(tmalloc(c, &c->tab.cells, cells * 4));
+    HIPCHK(c->pool.alloc(&c->tab.cells, cells * 4));
     HIPCHK(hipMemsetAsync(c->tab.cells, 0, cells * 4, c->stream));
     const size_t nb = (cells >> kBlockShift) + 2, ns = (cells >> (2 * kBlockShift)) + 2;
-    HIPCHK(tmalloc(c, &c->tab.bmax, nb * 8));
-    HIPCHK(tmalloc(c, &c->tab.smax, ns * 8));
+    HIPCHK(c->pool.alloc(&c->tab.bmax, nb * 8));
+    HIPCHK(c->pool.alloc(&c->tab.smax, ns * 8));
     HIPCHK(hipMemsetAsync(c->tab.bmax, 0, nb * 8, c->stream));
     HIPCHK(hipMemsetAsync(c->tab.smax, 0, ns * 8, c->stream));
     return MBPE_OK;
@@ -432,12 +359,12 @@ int alloc_table(mbpe_ctx *c, uint32_t ecap) {
     c->tab.ecap = ecap;
     c->hcap = next_pow2((uint64_t)ecap * 2);
     c->tab.hmask = c->hcap - 1;
-    HIPCHK(tmalloc(c, &c->tab.hslot, (size_t)c->hcap * 8));
-    HIPCHK(tmalloc(c, &c->tab.ekey, (size_t)ecap * 4));
-    HIPCHK(tmalloc(c, &c->tab.ecnt, (size_t)ecap * 4));
+    HIPCHK(c->pool.alloc(&c->tab.hslot, (size_t)c->hcap * 8));
+    HIPCHK(c->pool.alloc(&c->tab.ekey, (size_t)ecap * 4));
+    HIPCHK(c->pool.alloc(&c->tab.ecnt, (size_t)ecap * 4));
     const size_t nb = ((size_t)ecap >> kBlockShift) + 2, ns = ((size_t)ecap >> (2 * kBlockShift)) + 2;
-    HIPCHK(tmalloc(c, &c->tab.bmax, nb * 8));
-    HIPCHK(tmalloc(c, &c->tab.smax, ns * 8));
+    HIPCHK(c->pool.alloc(&c->tab.bmax, nb * 8));
+    HIPCHK(c->pool.alloc(&c->tab.smax, ns * 8));
     HIPCHK(hipMemsetAsync(c->tab.bmax, 0, nb * 8, c->stream));
     HIPCHK(hipMemsetAsync(c->tab.smax, 0, ns * 8, c->stream));
     launch_fill_u32(c->stream, reinterpret_cast<uint32_t *>(c->tab.hslot), (uint64_t)c->hcap * 2, 0xFFFFFFFFu);
@@ -486,8 +413,8 @@ int grow_table(mbpe_ctx *c, uint64_t want) {
                           hipMemcpyDeviceToDevice, c->stream));
     launch_table_rehash(c->stream, c->tab, c->ctl);
     HIPCHK(hipStreamSynchronize(c->stream));
-    trelease(c, old.hslot); trelease(c, old.ekey); trelease(c, old.ecnt);
-    trelease(c, old.bmax); trelease(c, old.smax);
+    c->pool.release(old.hslot); c->pool.release(old.ekey); c->pool.release(old.ecnt);
+    c->pool.release(old.bmax); c->pool.release(old.smax);
     return MBPE_OK;
 }
 
@@ -601,7 +528,7 @@ void mbpe_destroy(mbpe_ctx *c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_training(c);
-    pool_trim(c);
+    c->pool.trim();
     free_corpus(c);
     dfree(c->pc_scratch);
     dfree(c->pc_bp);
@@ -678,7 +605,7 @@ static int load_reset(mbpe_ctx *c, uint64_t n_bytes, bool chunked, uint64_t n_ch
     free_corpus(c);
     // (the training buffers of a corpus of another size would not be handed out again: give them back before the
     //  new corpus is allocated, not only inside the next mbpe_train_begin)
-    if (n_bytes != c->n_bytes || chunked != c->chunked) pool_trim(c);
+    if (n_bytes != c->n_bytes || chunked != c->chunked) c->pool.trim();
     c->n_bytes = n_bytes;
     c->chunked = chunked;
     c->n_chunks = chunked ? n_chunks : 1;
@@ -800,17 +727,8 @@ int mbpe_load_corpus_endmask(mbpe_ctx *c, const uint8_t *text, uint64_t n_bytes,
     // every set bit is a chunk end: the chunks, and the barrier slots of the barrier layout.  (A mask that carries
     // the NUL rule marks every byte of a collapsed chunk: like mbpe_load_corpus this counts those bytes as barriers;
     // the masks of mbpe_splitter_split hold no such chunk, see mbpe.h.)
-    unsigned long long *d_count = nullptr, ends = 0;
-    HIPCHK(hipMalloc(&d_count, 8));
-    hipError_t e = hipMemsetAsync(d_count, 0, 8, c->stream);
-    if (e == hipSuccess) {
-        mbpe::launch_mask_popcount(c->stream, endmask_dev, n_bytes, d_count);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&ends, d_count, 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_count);
-    HIPCHK(e);
+    unsigned long long ends = 0;
+    HIPCHK(read_scalar(c->stream, &ends, [&](unsigned long long *d) { launch_mask_popcount(c->stream, endmask_dev, n_bytes, d); }));
     c->n_chunks = ends;
     c->n_barriers = ends;
     return load_finish(c, text, n_bytes, text_on_device, endmask_dev, (n_bytes + 15) / 16 * 2 + 16,
@@ -898,14 +816,8 @@ int mbpe_load_corpus_endmask_weighted(mbpe_ctx *c, const uint8_t *text, uint64_t
         return refuse("mbpe_load_corpus_endmask_weighted: " + std::to_string(n_weights) + " weights for a mask of " +
                       std::to_string(c->n_barriers) + " chunk ends");
     if (weights_on_device && n_weights) {
-        uint32_t *d_flag = nullptr, flag = 0;
-        HIPCHK(hipMalloc(&d_flag, 4));
-        hipError_t e = hipMemsetAsync(d_flag, 0, 4, c->stream);
-        if (e == hipSuccess) { launch_wide_check_weights(c->stream, weights, n_weights, d_flag); e = hipGetLastError(); }
-        if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_flag);
-        HIPCHK(e);
+        uint32_t flag = 0;
+        HIPCHK(read_scalar(c->stream, &flag, [&](uint32_t *d) { launch_wide_check_weights(c->stream, weights, n_weights, d); }));
         if (flag) return refuse("mbpe_load_corpus_endmask_weighted: a weight is 0, or 2^31 or more");
     }
     rc = attach_weights(c, weights, n_weights, weights_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
@@ -1087,21 +999,21 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size, const ResumeSrc *rs = n
     c->max_batch_eff = (uint32_t)std::min<int64_t>(c->opt_max_batch, is_multi(c) ? 1024 : kBatchMax);
     c->adj_pitch = (uint32_t)round_up(std::max<uint32_t>(c->max_batch_eff, 64u), 64);
     c->hdrb_words = (batch_header_words(c->adj_pitch) + 3) / 4 * 4;
-    HIPCHK(tmalloc(c, &c->tok[0], c->n_slots * 2));
-    HIPCHK(tmalloc(c, &c->tok[1], c->cap_slots * 2));
-    HIPCHK(tmalloc(c, &c->sums, (size_t)c->n_tiles * sizeof(TileSum)));
-    HIPCHK(tmalloc(c, &c->side, (size_t)c->n_tiles * sizeof(TileSum)));
-    HIPCHK(tmalloc(c, &c->chg, ((size_t)c->n_tiles / 32 + 2) * 4));
-    HIPCHK(tmalloc(c, &c->tile_list, ((size_t)c->n_tiles + 64) * 4));
+    HIPCHK(c->pool.alloc(&c->tok[0], c->n_slots * 2));
+    HIPCHK(c->pool.alloc(&c->tok[1], c->cap_slots * 2));
+    HIPCHK(c->pool.alloc(&c->sums, (size_t)c->n_tiles * sizeof(TileSum)));
+    HIPCHK(c->pool.alloc(&c->side, (size_t)c->n_tiles * sizeof(TileSum)));
+    HIPCHK(c->pool.alloc(&c->chg, ((size_t)c->n_tiles / 32 + 2) * 4));
+    HIPCHK(c->pool.alloc(&c->tile_list, ((size_t)c->n_tiles + 64) * 4));
     HIPCHK(hipMemsetAsync(c->chg, 0, ((size_t)c->n_tiles / 32 + 2) * 4, c->stream));
-    HIPCHK(tmalloc(c, &c->offsets, ((size_t)c->n_tiles + tile_scan_scratch(c->n_tiles)) * 8));
+    HIPCHK(c->pool.alloc(&c->offsets, ((size_t)c->n_tiles + tile_scan_scratch(c->n_tiles)) * 8));
     // (the LR rows of the largest batch THIS training can select: seq_stage_a clamps every batch to max_batch_eff, so a
     //  later, larger "max_batch" cannot reach beyond it.  2 x max_batch_eff x lr_pitch(vocab) words: 1.05 GB at the
     //  defaults with vocab 32,000, 262 MB with several ranks or "max_batch" 1024)
     const size_t xb_words = (size_t)c->hdr_words + c->hdrb_words + lr_words(vocab_size, c->max_batch_eff) + 8;
     const size_t xb0_words = begin_exchange_words(c);
-    HIPCHK(tmalloc(c, &c->xb, xb_words * 4));
-    HIPCHK(tmalloc(c, &c->xb0, xb0_words * 4));
+    HIPCHK(c->pool.alloc(&c->xb, xb_words * 4));
+    HIPCHK(c->pool.alloc(&c->xb0, xb0_words * 4));
     HIPCHK(hipMemsetAsync(c->xb, 0, xb_words * 4, c->stream));
     HIPCHK(hipMemsetAsync(c->xb0, 0, xb0_words * 4, c->stream));
     if (c->opt_pair_cells > 0 || (c->opt_pair_cells < 0 && c->n_slots >= (64ull << 20))) {
@@ -1120,33 +1032,33 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size, const ResumeSrc *rs = n
         init.cap = (uint32_t)cap;
         init.chunk = (uint32_t)chunk;
         init.part_cap = (uint32_t)std::min<uint64_t>(half, 1u << 29);
-        HIPCHK(tmalloc(c, &c->dlog, (size_t)init.cap * 4));
-        HIPCHK(tmalloc(c, &c->dpart, (size_t)init.part_cap * 4));
-        HIPCHK(tmalloc(c, &c->log_state, sizeof(LogState)));
+        HIPCHK(c->pool.alloc(&c->dlog, (size_t)init.cap * 4));
+        HIPCHK(c->pool.alloc(&c->dpart, (size_t)init.part_cap * 4));
+        HIPCHK(c->pool.alloc(&c->log_state, sizeof(LogState)));
         HIPCHK(hipMemcpyAsync(c->log_state, &init, sizeof(LogState), hipMemcpyHostToDevice, c->stream));
     }
     c->hdr_m = c->xb + c->hdr_words;
     c->hdr_adj = c->hdr_m + kBatchMax;
     c->LR = c->xb + c->hdr_words + c->hdrb_words;
-    HIPCHK(tmalloc(c, &c->bs, sizeof(BatchState)));
-    HIPCHK(tmalloc(c, &c->sel, sizeof(SelList)));
-    HIPCHK(tmalloc(c, &c->run_in, ((size_t)c->n_tiles + 64) * 4));
-    HIPCHK(tmalloc(c, &c->seq_flags, 4096 * 4 * 4));      // 4 words per sequence of a group (k_seq_finish)
+    HIPCHK(c->pool.alloc(&c->bs, sizeof(BatchState)));
+    HIPCHK(c->pool.alloc(&c->sel, sizeof(SelList)));
+    HIPCHK(c->pool.alloc(&c->run_in, ((size_t)c->n_tiles + 64) * 4));
+    HIPCHK(c->pool.alloc(&c->seq_flags, 4096 * 4 * 4));      // 4 words per sequence of a group (k_seq_finish)
     HIPCHK(hipMemsetAsync(c->bs, 0, sizeof(BatchState), c->stream));
     HIPCHK(hipMemsetAsync(c->seq_flags, 0, 4096 * 4 * 4, c->stream));
     if (c->opt_first) {
-        HIPCHK(tmalloc(c, &c->first_state, first_state_bytes()));
+        HIPCHK(c->pool.alloc(&c->first_state, first_state_bytes()));
         launch_first_init(c->stream, c->first_state);
         if (is_multi(c)) {
-            HIPCHK(tmalloc(c, &c->xf, (size_t)c->hdr_words * 4));
+            HIPCHK(c->pool.alloc(&c->xf, (size_t)c->hdr_words * 4));
             HIPCHK(hipMemsetAsync(c->xf, 0, (size_t)c->hdr_words * 4, c->stream));
         }
     }
     c->k_upper = c->k;
-    HIPCHK(tmalloc(c, &c->d_left, sizeof(RankEdge)));
-    HIPCHK(tmalloc(c, &c->d_right, sizeof(RankEdge)));
-    HIPCHK(tmalloc(c, &c->ctl, sizeof(DevCtl)));
-    HIPCHK(tmalloc(c, &c->best, ((size_t)c->n_target + 2) * 8));
+    HIPCHK(c->pool.alloc(&c->d_left, sizeof(RankEdge)));
+    HIPCHK(c->pool.alloc(&c->d_right, sizeof(RankEdge)));
+    HIPCHK(c->pool.alloc(&c->ctl, sizeof(DevCtl)));
+    HIPCHK(c->pool.alloc(&c->best, ((size_t)c->n_target + 2) * 8));
     {
         DevCtl init = {};
         init.n_live = n + n_bar;         // every corpus byte (every token of a resumed stream) starts as one live token
@@ -1181,7 +1093,7 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size, const ResumeSrc *rs = n
 
     rc = ensure_pc_scratch(c);
     if (rc != MBPE_OK) return rc;
-    pool_trim(c);        // what this run did not take over from the previous one goes back to the driver
+    c->pool.trim();        // what this run did not take over from the previous one goes back to the driver
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     if (!rs && n >= 2) launch_pair_count_u8(c->stream, c->d_text, n, c->d_endmask, c->xb0, c->n_cus, c->pc_scratch);
     c->cur = 0;
@@ -1194,9 +1106,9 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size, const ResumeSrc *rs = n
         if (rc != MBPE_OK) return rc;
         c->stats.n_compactions--;               // (part of the set-up, not one of the run's compactions)
         c->stats.ms_compact = ms_compact;
-        tfree(c, c->tok[0]);
-        pool_trim(c);
-        HIPCHK(tmalloc(c, &c->tok[0], c->cap_slots * 2));
+        c->pool.free(c->tok[0]);
+        c->pool.trim();
+        HIPCHK(c->pool.alloc(&c->tok[0], c->cap_slots * 2));
     } else {
         if (!rs) launch_widen(c->stream, c->d_text, n, c->d_endmask, c->tok[0], c->n_slots);
         launch_summarize(stream_view(c, kLiveFirst));
@@ -1218,7 +1130,7 @@ static int begin_local(mbpe_ctx *c, uint32_t vocab_size, const ResumeSrc *rs = n
 // would allocate) before every distinct pair is inserted once; the one host round trip of this path.
 static int count_token_pairs(mbpe_ctx *c, const ResumeSrc *rs, uint64_t want) {
     const uint32_t ids = 256 + rs->n_prior;
-    HIPCHK(tmalloc(c, &c->tally, sizeof(ResumeTally)));
+    HIPCHK(c->pool.alloc(&c->tally, sizeof(ResumeTally)));
     HIPCHK(hipMemsetAsync(c->tally, 0, sizeof(ResumeTally), c->stream));
     if (c->tab.cells) {
         launch_pair_count_tokens(c->stream, rs->tok, rs->n_tok, ids, c->tab, PairBins{nullptr, nullptr, 0}, c->tally, c->n_cus);
@@ -1232,8 +1144,8 @@ static int count_token_pairs(mbpe_ctx *c, const ResumeSrc *rs, uint64_t want) {
         }
         PairBins bins = {nullptr, nullptr, next_pow2(std::max<uint64_t>(2 * most, 1024)) - 1};
         const size_t slots = (size_t)bins.mask + 1;
-        HIPCHK(tmalloc(c, &bins.key, slots * 4));
-        HIPCHK(tmalloc(c, &bins.cnt, slots * 4));
+        HIPCHK(c->pool.alloc(&bins.key, slots * 4));
+        HIPCHK(c->pool.alloc(&bins.cnt, slots * 4));
         launch_fill_u32(c->stream, bins.key, slots, kEmptyKey);
         HIPCHK(hipMemsetAsync(bins.cnt, 0, slots * 4, c->stream));
         launch_pair_count_tokens(c->stream, rs->tok, rs->n_tok, ids, c->tab, bins, c->tally, c->n_cus);
@@ -1250,8 +1162,8 @@ static int count_token_pairs(mbpe_ctx *c, const ResumeSrc *rs, uint64_t want) {
         want = std::min<uint64_t>(want, table_cap_limit(c));
         if (rc == MBPE_OK) rc = alloc_table(c, (uint32_t)want);
         if (rc == MBPE_OK) launch_bins_insert(c->stream, bins, c->tab, c->ctl);
-        tfree(c, bins.key);          // (handed out again, if at all, to work enqueued behind the insert)
-        tfree(c, bins.cnt);
+        c->pool.free(bins.key);          // (handed out again, if at all, to work enqueued behind the insert)
+        c->pool.free(bins.cnt);
         if (rc != MBPE_OK) return rc;
         c->h_ctl.n_entries = h.distinct;      // (use_hier: the table's size, until sync_ctl reads it)
     }
@@ -1626,45 +1538,6 @@ static int start_unit_external(mbpe_ctx *c, bool batched) {
     return suspend(c, Phase::SeqDeltas);
 }
 
-static int weighted_begin(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prior, uint32_t n_prior);
-
-int mbpe_train_begin(mbpe_ctx *c, uint32_t vocab_size) {
-    if (!c) return MBPE_ERR_ARG;
-    if (!c->loaded) { mbpe_host::set_last_error("mbpe_train_begin: no corpus loaded"); return MBPE_ERR_STATE; }
-    if (vocab_size < 256) { mbpe_host::set_last_error("vocab_size must be >= 256"); return MBPE_ERR_ARG; }
-    if (c->weighted || is_limited(c)) return weighted_begin(c, vocab_size, nullptr, 0);
-    const uint32_t vmax = !c->chunked ? MBPE_MAX_VOCAB_BASIC : c->opt_barrier == 0 ? MBPE_MAX_VOCAB_ENDBIT : MBPE_MAX_VOCAB_CHUNKED;
-    c->barrier = c->chunked && (c->opt_barrier == 1 || (c->opt_barrier != 0 && vocab_size > MBPE_MAX_VOCAB_ENDBIT));
-    // Beyond the 16-bit slot format (Token is a uint32_t in the reference, Tokenizer.h:37-38) the training runs its first
-    // vmax - 256 merges on the slot stream and continues on 32-bit tokens (wide.h): one GPU; the `first` tie-break only
-    // when the caller asks for it ("first_wide").
-    const uint32_t total = vocab_size;
-    c->wide = false;
-    if (vocab_size > vmax || (c->opt_wide_from >= 0 && (int64_t)vocab_size - 256 > c->opt_wide_from)) {
-        if (vocab_size > MBPE_MAX_VOCAB_WIDE) {
-            mbpe_host::set_last_error("vocab_size exceeds " + std::to_string(MBPE_MAX_VOCAB_WIDE));
-            return MBPE_ERR_VOCAB;
-        }
-        if ((c->opt_first && !c->opt_first_wide) || is_multi(c)) {
-            mbpe_host::set_last_error("vocab_size exceeds the 16-bit slot format (" + std::to_string(vmax) +
-                                      "): the 32-bit continuation runs on one GPU only, and with the `first` tie-break "
-                                      "only with the option first_wide = 1");
-            return MBPE_ERR_VOCAB;
-        }
-        c->wide = true;
-        vocab_size = c->opt_wide_from >= 0 ? (uint32_t)std::min<int64_t>(256 + c->opt_wide_from, vmax) : vmax;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    int rc = begin_local(c, vocab_size);
-    c->vocab_total = total;
-    c->n_target_total = total - 256;
-    if (rc != MBPE_OK) return rc;
-    if (is_multi(c) && c->comm_external) return suspend(c, Phase::BeginCounts);
-    rc = finish_unit(c, Phase::BeginCounts);
-    if (rc != MBPE_OK) return rc;
-    return begin_end(c);
-}
-
 int mbpe_merges_check(const uint32_t *merges, uint32_t n_merges) {
     if (!merges && n_merges) { mbpe_host::set_last_error("mbpe_merges_check: merges is NULL"); return MBPE_ERR_ARG; }
     std::unordered_map<unsigned long long, uint32_t> seen;
@@ -1697,7 +1570,7 @@ static int replay_prior(mbpe_ctx *c, const uint32_t *prior, uint32_t n_prior, ui
     const uint64_t n = c->inert ? 0 : c->n_bytes;
     if (!n) return MBPE_OK;
     free_training(c);        // (the peak of a resumed begin is the replay: nothing of an earlier training stays beside it)
-    pool_trim(c);
+    c->pool.trim();
     uint8_t *own_mask = nullptr;
     mbpe_encoder *enc = nullptr;
     auto run = [&]() -> int {
@@ -1731,8 +1604,97 @@ static int replay_prior(mbpe_ctx *c, const uint32_t *prior, uint32_t n_prior, ui
     return rc;
 }
 
-static int wide_begin_from(mbpe_ctx *c, uint32_t vocab_size, uint32_t **tok, uint64_t n_tok, const uint32_t *prior,
-                           uint32_t n_prior);
+// A training that begins on 32-bit tokens (Route::WideDirect): one on a corpus with chunk weights or under a stopping
+// rule, from merge n_prior on (0 included: an empty prior table leaves the bytes as tokens), and one continued from so
+// many merges that no slot stream can hold their ids.  The replay's tokens are the 32-bit stream (WideRun::begin_from):
+// no slot stream, no best[].
+static int begin_wide_direct(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prior, uint32_t n_prior) {
+    uint32_t *tok = nullptr;
+    uint64_t n_tok = 0;
+    int rc = replay_prior(c, prior, n_prior, &tok, &n_tok);
+    if (rc != MBPE_OK) return rc;
+    free_training(c);
+    c->vocab_size = 256 + n_prior;           // (the slot stream's share: the prior merges, all of them made already)
+    c->n_target = c->k = c->n_valid = c->n_prior = c->k_upper = n_prior;
+    c->vocab_total = vocab_size;
+    c->n_target_total = vocab_size - 256;
+    c->exhausted = false;
+    c->barrier = false;                      // (32-bit tokens carry their chunk ends as flags)
+    c->wide = true;
+    c->wide_direct = true;
+    c->h_ctl = DevCtl{};
+    c->h_prior_raw.assign(prior, prior + 2 * (size_t)n_prior);
+    const WideTokens src = {&tok, n_tok, c->ms_replay, prior, n_prior, vocab_size, c->weighted ? c->d_weights : nullptr,
+                            c->n_weights, c->opt_min_frequency, c->opt_max_token_length};
+    rc = c->wr.begin_from(wide_dev(c), src, WideGoal{vocab_size - 256 - n_prior, 256 + n_prior, c->opt_first != 0});
+    if (rc == MBPE_OK) {
+        c->last_top = c->wr.top0;
+        c->begun = true;
+        c->pool.trim();
+    } else {
+        (void)hipStreamSynchronize(c->stream);
+    }
+    dfree(tok);
+    return rc;
+}
+
+// Every begin, behind its entry point's argument checks: the route (train_plan.h), then the begin it names.
+static int begin_routed(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prior, uint32_t n_prior) {
+    const BeginPlan plan = plan_begin(BeginIn{c->chunked, c->opt_barrier, c->opt_first, c->opt_first_wide, c->opt_resume_wide,
+                                              c->opt_wide_from, c->weighted, is_limited(c), is_multi(c), vocab_size, n_prior});
+    if (plan.rc != MBPE_OK) return fail(plan.rc, plan.message);
+    HIPCHK(hipSetDevice(c->device));
+    if (plan.route == Route::WideDirect) return begin_wide_direct(c, vocab_size, prior, n_prior);
+    c->barrier = plan.barrier;
+    c->wide = plan.route == Route::SlotThenWide;      // (the slot stream's share ends at slot_vocab, where wide_convert takes over)
+    if (!n_prior) {
+        int rc = begin_local(c, plan.slot_vocab);
+        c->vocab_total = vocab_size;
+        c->n_target_total = vocab_size - 256;
+        if (rc != MBPE_OK) return rc;
+        if (is_multi(c) && c->comm_external) return suspend(c, Phase::BeginCounts);
+        rc = finish_unit(c, Phase::BeginCounts);
+        if (rc != MBPE_OK) return rc;
+        return begin_end(c);
+    }
+    uint32_t *tok = nullptr;
+    uint64_t n_tok = 0;
+    int rc = replay_prior(c, prior, n_prior, &tok, &n_tok);
+    if (rc != MBPE_OK) return rc;
+    auto rest = [&]() -> int {
+        if (c->barrier && n_tok) {
+            // the barrier slots the compaction keeps are the tokens' end flags: they must be the mask's end bits, by
+            // which the stream is sized
+            unsigned long long ends = 0;
+            HIPCHK(read_scalar(c->stream, &ends, [&](unsigned long long *d) { launch_token_ends(c->stream, tok, n_tok, d); }));
+            if (ends != c->n_barriers) {
+                mbpe_host::set_last_error("mbpe_train_begin_from: the replay left " + std::to_string(ends) + " chunk ends, the "
+                                          "corpus has " + std::to_string(c->n_barriers));
+                return MBPE_ERR_STATE;
+            }
+        }
+        const ResumeSrc rs = {tok, n_tok, prior, n_prior};
+        int r = begin_local(c, plan.slot_vocab, &rs);
+        c->vocab_total = vocab_size;
+        c->n_target_total = vocab_size - 256;
+        if (r != MBPE_OK) return r;
+        r = begin_end(c);
+        c->stats.ms_begin += c->ms_replay;
+        return r;
+    };
+    rc = rest();
+    (void)hipStreamSynchronize(c->stream);      // (the kernels that read the tokens are done)
+    dfree(tok);
+    c->pool.trim();
+    return rc;
+}
+
+int mbpe_train_begin(mbpe_ctx *c, uint32_t vocab_size) {
+    if (!c) return MBPE_ERR_ARG;
+    if (!c->loaded) { mbpe_host::set_last_error("mbpe_train_begin: no corpus loaded"); return MBPE_ERR_STATE; }
+    if (vocab_size < 256) { mbpe_host::set_last_error("vocab_size must be >= 256"); return MBPE_ERR_ARG; }
+    return begin_routed(c, vocab_size, nullptr, 0);
+}
 
 int mbpe_train_begin_from(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prior_merges, uint32_t n_prior) {
     if (!c) return MBPE_ERR_ARG;
@@ -1745,109 +1707,8 @@ int mbpe_train_begin_from(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prio
                                   std::to_string(vocab_size) + " holds");
         return MBPE_ERR_ARG;
     }
-    int rc = mbpe_merges_check(prior_merges, n_prior);
-    if (rc != MBPE_OK) return rc;
-    if (c->weighted || is_limited(c)) return weighted_begin(c, vocab_size, prior_merges, n_prior);
-    if (is_multi(c)) {
-        mbpe_host::set_last_error("mbpe_train_begin_from: continuing from existing merges runs on one rank only");
-        return MBPE_ERR_STATE;
-    }
-    const uint32_t vmax = !c->chunked ? MBPE_MAX_VOCAB_BASIC : c->opt_barrier == 0 ? MBPE_MAX_VOCAB_ENDBIT : MBPE_MAX_VOCAB_CHUNKED;
-    // "resume_wide": T merges in all, of which the slot stream can make the first h.  T <= h: the slot case, as ever.
-    // n_prior < h < T: the mixed case -- the begin below with the slot target 256 + h, then the handover of
-    // mbpe_train_begin's trainings (wide_convert).  n_prior >= h: the direct case (wide_begin_from).
-    const uint32_t T = vocab_size - 256;
-    const uint32_t h = c->opt_wide_from >= 0 ? (uint32_t)std::min<int64_t>(c->opt_wide_from, vmax - 256) : vmax - 256;
-    const bool beyond = c->opt_resume_wide && T > h;
-    if (beyond) {
-        if (vocab_size > MBPE_MAX_VOCAB_WIDE) {
-            mbpe_host::set_last_error("vocab_size exceeds " + std::to_string(MBPE_MAX_VOCAB_WIDE));
-            return MBPE_ERR_VOCAB;
-        }
-        if (c->opt_first && !c->opt_first_wide) {
-            mbpe_host::set_last_error("mbpe_train_begin_from: vocab_size exceeds the 16-bit slot format (" + std::to_string(vmax) +
-                                      "): with the `first` tie-break the 32-bit continuation runs only with the option "
-                                      "first_wide = 1");
-            return MBPE_ERR_VOCAB;
-        }
-    } else if (!c->opt_resume_wide && (vocab_size > vmax || c->opt_wide_from >= 0)) {
-        mbpe_host::set_last_error("mbpe_train_begin_from: vocab_size " + std::to_string(vocab_size) + " (with " +
-                                  std::to_string(n_prior) + " prior merges) lies beyond the 16-bit slot format of this corpus (" +
-                                  std::to_string(vmax) + "), or \"wide_from\" is set: the 32-bit continuation does not "
-                                  "start from existing merges");
-        return MBPE_ERR_VOCAB;
-    }
-    c->barrier = c->chunked && (c->opt_barrier == 1 || (c->opt_barrier != 0 && vocab_size > MBPE_MAX_VOCAB_ENDBIT));
-    c->wide = false;
-    HIPCHK(hipSetDevice(c->device));
-    uint32_t *tok = nullptr;
-    uint64_t n_tok = 0;
-    rc = replay_prior(c, prior_merges, n_prior, &tok, &n_tok);
-    if (rc != MBPE_OK) return rc;
-    if (beyond && n_prior >= h) {
-        rc = wide_begin_from(c, vocab_size, &tok, n_tok, prior_merges, n_prior);
-        if (rc != MBPE_OK) (void)hipStreamSynchronize(c->stream);
-        dfree(tok);
-        return rc;
-    }
-    auto rest = [&]() -> int {
-        if (c->barrier && n_tok) {
-            // the barrier slots the compaction keeps are the tokens' end flags: they must be the mask's end bits, by
-            // which the stream is sized
-            unsigned long long *d_ends = nullptr, ends = 0;
-            HIPCHK(hipMalloc(&d_ends, 8));
-            hipError_t e = hipMemsetAsync(d_ends, 0, 8, c->stream);
-            if (e == hipSuccess) { launch_token_ends(c->stream, tok, n_tok, d_ends); e = hipGetLastError(); }
-            if (e == hipSuccess) e = hipMemcpyAsync(&ends, d_ends, 8, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            (void)hipFree(d_ends);
-            HIPCHK(e);
-            if (ends != c->n_barriers) {
-                mbpe_host::set_last_error("mbpe_train_begin_from: the replay left " + std::to_string(ends) + " chunk ends, the "
-                                          "corpus has " + std::to_string(c->n_barriers));
-                return MBPE_ERR_STATE;
-            }
-        }
-        const ResumeSrc rs = {tok, n_tok, prior_merges, n_prior};
-        c->wide = beyond;        // (the mixed case: the slot stream's share ends at merge h, where wide_convert takes over)
-        int r = begin_local(c, beyond ? 256 + h : vocab_size, &rs);
-        c->vocab_total = vocab_size;
-        c->n_target_total = vocab_size - 256;
-        if (r != MBPE_OK) return r;
-        r = begin_end(c);
-        c->stats.ms_begin += c->ms_replay;
-        return r;
-    };
-    rc = rest();
-    (void)hipStreamSynchronize(c->stream);      // (the kernels that read the tokens are done)
-    dfree(tok);
-    pool_trim(c);
-    return rc;
-}
-
-// A corpus with chunk weights trains on 32-bit tokens from merge n_prior on (0 included), whatever the vocabulary and
-// either tie-break: the text widened by the replay (an empty prior table leaves the bytes as tokens), then the route
-// of the direct continuation.  "wide_from", "first_wide", "resume_wide" and "chunk_barrier" play no part.
-// So does any corpus under a stopping rule ("min_frequency", "max_token_length"): the rules live in that loop's argmax.
-static int weighted_begin(mbpe_ctx *c, uint32_t vocab_size, const uint32_t *prior, uint32_t n_prior) {
-    if (is_multi(c)) {
-        mbpe_host::set_last_error(c->weighted ? "a corpus with chunk weights trains on one rank only"
-                                              : "a training with min_frequency or max_token_length runs on one rank only");
-        return MBPE_ERR_STATE;
-    }
-    if (vocab_size > MBPE_MAX_VOCAB_WIDE) {
-        mbpe_host::set_last_error("vocab_size exceeds " + std::to_string(MBPE_MAX_VOCAB_WIDE));
-        return MBPE_ERR_VOCAB;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    uint32_t *tok = nullptr;
-    uint64_t n_tok = 0;
-    int rc = replay_prior(c, prior, n_prior, &tok, &n_tok);
-    if (rc != MBPE_OK) return rc;
-    rc = wide_begin_from(c, vocab_size, &tok, n_tok, prior, n_prior);
-    if (rc != MBPE_OK) (void)hipStreamSynchronize(c->stream);
-    dfree(tok);
-    return rc;
+    const int rc = mbpe_merges_check(prior_merges, n_prior);
+    return rc != MBPE_OK ? rc : begin_routed(c, vocab_size, prior_merges, n_prior);
 }
 
 // the batch-sequence loop of mbpe_train_steps (one GPU, or several over RCCL)
@@ -1967,48 +1828,6 @@ static int train_steps_batched(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_do
     return MBPE_OK;
 }
 
-static int train_steps16(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_done_out);
-static int wide_convert(mbpe_ctx *c);
-static int wide_steps(mbpe_ctx *c, uint32_t n_steps, uint32_t *done_out);
-
-// `first` mode: did the slot stream's share already end where the reference's loop breaks (no pair left,
-// Tokenizer.h:586-588)?  Then there is nothing to continue: the result is the merges so far, as at a smaller vocabulary.
-static int first_ran_out(mbpe_ctx *c, bool *out) {
-    *out = false;
-    if (!c->opt_first) return MBPE_OK;
-    if (c->n_target < c->vocab_size - 256) { *out = true; return MBPE_OK; }     // (the one-merge loop cut n_target there)
-    if (c->k == 0) return MBPE_OK;
-    unsigned long long last = 0;
-    HIPCHK(hipMemcpy(&last, c->best + (c->k - 1), 8, hipMemcpyDeviceToHost));
-    *out = (last >> 32) == 0;
-    return MBPE_OK;
-}
-
-int mbpe_train_steps(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_done_out) {
-    if (steps_done_out) *steps_done_out = 0;
-    if (!c) return MBPE_ERR_ARG;
-    if (!c->begun) { mbpe_host::set_last_error("mbpe_train_steps before mbpe_train_begin"); return MBPE_ERR_STATE; }
-    if (c->pending != Phase::None) { mbpe_host::set_last_error("an exchange is pending: call mbpe_comm_exchange_done"); return MBPE_ERR_STATE; }
-    HIPCHK(hipSetDevice(c->device));
-    if (!c->wide) return train_steps16(c, n_steps, steps_done_out);
-    // a training that continues on 32-bit tokens: the slot stream's share first, then the conversion, then the rest
-    uint32_t done = 0;
-    if (!c->wide_active) {
-        int rc = train_steps16(c, n_steps, &done);
-        if (steps_done_out) *steps_done_out = done;
-        if (rc != MBPE_OK || done >= n_steps || c->exhausted || c->k < c->n_target) return rc;
-        bool out = false;
-        rc = first_ran_out(c, &out);
-        if (rc != MBPE_OK || out) return rc;
-        rc = wide_convert(c);
-        if (rc != MBPE_OK) return rc;
-    }
-    uint32_t more = 0;
-    int rc = wide_steps(c, n_steps - done, &more);
-    if (steps_done_out) *steps_done_out = done + more;
-    return rc;
-}
-
 static int train_steps16(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_done_out) {
     if (steps_done_out) *steps_done_out = 0;
     if (is_multi(c) && c->comm_external) {
@@ -2089,271 +1908,59 @@ static int train_steps16(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_done_out
     return MBPE_OK;
 }
 
-// ---- the 32-bit continuation (wide.h) ----------------------------------------------------------------------------
-
-static int wide_alloc_table(mbpe_ctx *c, WideTable *t, uint64_t want_entries) {
-    uint32_t bits = 12;
-    while ((1ull << bits) < 2 * want_entries && bits < 31) ++bits;
-    if ((1ull << bits) < 2 * want_entries) { mbpe_host::set_last_error("pair table beyond 2^30 entries"); return MBPE_ERR_OVERFLOW; }
-    *t = {};
-    t->mask = (uint32_t)((1ull << bits) - 1);
-    t->shift = 64 - bits;
-    HIPCHK(tmalloc(c, &t->keys, (size_t)8 << bits));
-    HIPCHK(tmalloc(c, &t->cnts, (size_t)4 << bits));
-    launch_wide_table_clear(c->stream, *t);
-    return MBPE_OK;
-}
-
-// entries `merges` merges can add at most when no count exceeds `top`: per match one (x,X) and one (X,y), per merge
-// possibly the transient (X,a) of touching matches; a merge has at most `top` matches
-// -- and at most one per position of the stream, which bounds it where counts are weighted (a count of 10^9 on a stream
-// of ten tokens)
-static uint64_t wide_headroom(unsigned long long top, uint64_t positions, uint32_t merges) {
-    return (uint64_t)merges * (2ull * std::min<unsigned long long>(top, positions) + 2);
-}
-
-static int wide_sync(mbpe_ctx *c) {
-    HIPCHK(hipMemcpyAsync(&c->h_wctl, c->wctl, sizeof(WideCtl), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipGetLastError());
-    if (c->h_wctl.err & kWideErrFull) {
-        mbpe_host::set_last_error("device error: the 32-bit pair table is full");
-        return MBPE_ERR_OVERFLOW;
-    }
-    if (c->h_wctl.err & kWideErrWeight) {
-        mbpe_host::set_last_error("device error: a chunk weight is 0, or 2^31 or more, or the stream has more chunks than weights");
-        return MBPE_ERR_ARG;
-    }
-    if (c->h_wctl.err) {
-        mbpe_host::set_last_error(c->h_wctl.err & kWideErrToken
-                                      ? "device error: the replayed stream holds a token id that no prior merge made"
-                                      : "device error: a pair occurs 2^31 times or more, or the pair counts do not add up "
-                                        "to the pairs scanned");
-        return MBPE_ERR_OVERFLOW;
-    }
-    return MBPE_OK;
-}
-
-// The buffers of the 32-bit loop for a stream of at most n_tok tokens (n_val: positions the value array holds, the
-// slot stream's barriers included at a conversion) and its control block, with n_init tokens in the stream already.
-static int wide_alloc_loop(mbpe_ctx *c, uint64_t n_tok, uint64_t n_val, uint64_t n_init) {
-    const uint32_t n_wide = c->n_target_total - c->n_target;
-    if (!c->wtok[0]) HIPCHK(tmalloc(c, &c->wtok[0], std::max<uint64_t>(n_tok, 1) * 4));      // (wide_begin_from: there already)
-    HIPCHK(tmalloc(c, &c->wtok[1], std::max<uint64_t>(n_tok, 1) * 4));
-    HIPCHK(tmalloc(c, &c->wval, std::max<uint64_t>(n_val, 1) * 4));
-    HIPCHK(tmalloc(c, &c->wscratch, wide_scratch_words(n_val) * 4));
-    HIPCHK(tmalloc(c, &c->wctl, sizeof(WideCtl)));
-    HIPCHK(tmalloc(c, &c->wbest, ((size_t)n_wide + 2) * sizeof(WideBest)));
-    HIPCHK(tmalloc(c, &c->warg, 2 * 1024 * 8));
-    c->wfirst = c->opt_first != 0;
-    c->h_wctl = WideCtl{};
-    c->h_wctl.n = n_init;
-    c->h_wctl.first = c->wfirst ? 1u : 0u;
-    HIPCHK(hipMemcpyAsync(c->wctl, &c->h_wctl, sizeof(WideCtl), hipMemcpyHostToDevice, c->stream));
-    if (c->wfirst) {
-        HIPCHK(tmalloc(c, &c->wfs, sizeof(WideFirst)));
-        HIPCHK(hipMemsetAsync(c->wfs, 0, sizeof(WideFirst), c->stream));
-        HIPCHK(hipMemsetAsync(&c->wfs->pos, 0xFF, sizeof(c->wfs->pos), c->stream));
-    }
-    c->wcur = 0;
-    c->wk = 0;
-    c->h_wbest.clear();
-    return MBPE_OK;
-}
-
-// slot stream + hashed pair table of the 16-bit part -> 32-bit tokens + 64-bit-key table.  From here on the training's
-// stream, table and merge counter live in the w* members; the 16-bit buffers go back to the pool.
+// slot stream + hashed pair table of the 16-bit part -> the 32-bit loop (WideRun::convert).  From here on the training's
+// stream, table and merge counter live in c->wr; the 16-bit buffers go back to the pool (their merges stay in best[]).
 static int wide_convert(mbpe_ctx *c) {
     int rc = sync_ctl(c);
     if (rc != MBPE_OK) return rc;
     rc = do_compact(c);                       // no holes left: the first n_live slots are the stream (barriers included)
     if (rc != MBPE_OK) return rc;
-    const uint64_t n_live_slots = c->h_ctl.n_live;
-    const uint64_t n_tok = n_live_slots - (c->barrier ? c->n_barriers : 0);
-    rc = wide_alloc_loop(c, n_tok, n_live_slots, 0);
+    const WideSlots src = {c->tok[c->cur], c->h_ctl.n_live, c->barrier ? c->n_barriers : 0,
+                           c->barrier ? kBarrier : 0xFFFFFFFFu, c->chunked && !c->barrier ? kEndBit : 0u,
+                           c->tab.ekey, c->tab.ecnt, c->h_ctl.n_entries, c->last_top};
+    rc = c->wr.convert(wide_dev(c), src, WideGoal{c->n_target_total - c->n_target, 256 + c->n_target, c->opt_first != 0});
     if (rc != MBPE_OK) return rc;
-    const uint32_t barrier = c->barrier ? kBarrier : 0xFFFFFFFFu;
-    const uint32_t endbit = c->chunked && !c->barrier ? kEndBit : 0u;
-    launch_wide_from_slots(c->stream, c->tok[c->cur], n_live_slots, barrier, endbit, c->wval, c->wscratch, c->wtok[0], c->wctl);
-    c->wcur = 0;
-    unsigned long long top = c->last_top == ~0ull ? n_tok : c->last_top;
-    rc = wide_alloc_table(c, &c->wtab, (uint64_t)c->h_ctl.n_entries + wide_headroom(top, n_tok, 16));
-    if (rc != MBPE_OK) return rc;
-    launch_wide_table_from16(c->stream, c->tab.ekey, c->tab.ecnt, c->h_ctl.n_entries, c->wtab, c->wctl);
-    rc = wide_sync(c);
-    if (rc != MBPE_OK) return rc;
-    if (c->h_wctl.n != n_tok || c->h_wctl.n_entries != c->h_ctl.n_entries) {
-        mbpe_host::set_last_error("conversion to 32-bit tokens lost tokens or pairs");
-        return MBPE_ERR_OVERFLOW;
-    }
-    c->wn_upper = n_tok;
-    c->wk = 0;
-    c->h_wbest.clear();
-    c->wide_active = true;
-    // the 16-bit stream and table are done with (their merges stay in best[])
-    tfree(c, c->tok[0]); tfree(c, c->tok[1]); tfree(c, c->sums); tfree(c, c->side); tfree(c, c->chg); tfree(c, c->tile_list);
-    tfree(c, c->offsets); tfree(c, c->run_in); tfree(c, c->xb); tfree(c, c->dlog); tfree(c, c->dpart); tfree(c, c->log_state);
-    tfree(c, c->tab.hslot); tfree(c, c->tab.ekey); tfree(c, c->tab.ecnt); tfree(c, c->tab.bmax); tfree(c, c->tab.smax);
-    tfree(c, c->first_state);                 // (the slot stream's `first` scratch; the 32-bit loop has its own)
-    c->LR = nullptr;
-    pool_trim(c);
+    free_slot_stream(c);
+    c->pool.trim();
     return MBPE_OK;
 }
 
-// The stopping rules of the training that begins (wide.h): the options as they stand, and for a length limit the
-// lengths of the bytes and of the prior merges -- which count, whatever their length; the limits apply to the new
-// merges only.  The entries of the new tokens are written by the loop.
-static int wide_begin_limits(mbpe_ctx *c, const uint32_t *prior, uint32_t n_prior) {
-    c->wlim = WideLimits{};
-    c->wlim.min_count = (int32_t)c->opt_min_frequency;
-    c->wlim.new_id_base = 256 + n_prior;
-    if (!c->opt_max_token_length) return MBPE_OK;
-    std::vector<uint32_t> len((size_t)c->vocab_total, 0u);
-    for (uint32_t i = 0; i < 256 && i < c->vocab_total; ++i) len[i] = 1;
-    for (uint32_t k = 0; k < n_prior; ++k)      // (mbpe_merges_check: both halves exist before merge k)
-        len[256 + k] = (uint32_t)std::min<uint64_t>((uint64_t)len[prior[2 * k]] + len[prior[2 * k + 1]], kWideLenMax);
-    HIPCHK(tmalloc(c, &c->wlim.len, len.size() * 4));
-    HIPCHK(hipMemcpyAsync(c->wlim.len, len.data(), len.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->wlim.max_len = (uint32_t)c->opt_max_token_length;
+// `first` mode: did the slot stream's share already end where the reference's loop breaks (no pair left,
+// Tokenizer.h:586-588)?  Then there is nothing to continue: the result is the merges so far, as at a smaller vocabulary.
+static int first_ran_out(mbpe_ctx *c, bool *out) {
+    *out = false;
+    if (!c->opt_first) return MBPE_OK;
+    if (c->n_target < c->vocab_size - 256) { *out = true; return MBPE_OK; }     // (the one-merge loop cut n_target there)
+    if (c->k == 0) return MBPE_OK;
+    unsigned long long last = 0;
+    HIPCHK(hipMemcpy(&last, c->best + (c->k - 1), 8, hipMemcpyDeviceToHost));
+    *out = (last >> 32) == 0;
     return MBPE_OK;
 }
 
-// A training that continues from so many merges that no slot stream can hold their ids: the replay's tokens (*tok,
-// n_tok of them in an array of the caller's, which is freed here once they are copied) ARE the 32-bit stream, the
-// 64-bit-key table is counted from them, and the 32-bit loop runs from merge n_prior.  The table is allocated before
-// the count for the most distinct pairs the stream can hold (wide_add inserts concurrently: no bins, no census) and
-// replaced by one of the right size once the count is known.
-static int wide_begin_from(mbpe_ctx *c, uint32_t vocab_size, uint32_t **tok, uint64_t n_tok, const uint32_t *prior,
-                           uint32_t n_prior) {
-    free_training(c);
-    c->vocab_size = 256 + n_prior;           // (the slot stream's share: the prior merges, all of them made already)
-    c->n_target = c->k = c->n_valid = c->n_prior = c->k_upper = n_prior;
-    c->vocab_total = vocab_size;
-    c->n_target_total = vocab_size - 256;
-    c->exhausted = false;
-    c->barrier = false;                      // (32-bit tokens carry their chunk ends as flags)
-    c->wide = true;
-    c->wide_direct = true;
-    c->h_ctl = DevCtl{};
-    c->h_prior_raw.assign(prior, prior + 2 * (size_t)n_prior);
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
-    // the stream first, so that the replay's n_bytes x 4 array is gone before anything else is allocated
-    HIPCHK(tmalloc(c, &c->wtok[0], std::max<uint64_t>(n_tok, 1) * 4));
-    if (n_tok) HIPCHK(hipMemcpyAsync(c->wtok[0], *tok, n_tok * 4, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    dfree(*tok);
-    int rc = wide_alloc_loop(c, n_tok, n_tok, n_tok);
-    if (rc != MBPE_OK) return rc;
-    HIPCHK(tmalloc(c, &c->wtally, sizeof(WideTally)));
-    HIPCHK(hipMemsetAsync(c->wtally, 0, sizeof(WideTally), c->stream));
-    if (c->weighted) {
-        HIPCHK(tmalloc(c, &c->wwt[0], std::max<uint64_t>(n_tok, 1) * 4));
-        HIPCHK(tmalloc(c, &c->wwt[1], std::max<uint64_t>(n_tok, 1) * 4));
-        launch_wide_token_weights(c->stream, c->wtok[0], n_tok, c->d_weights, c->n_weights, c->wwt[0], c->wscratch, c->wctl);
-    }
-    if (is_limited(c)) {
-        rc = wide_begin_limits(c, prior, n_prior);
-        if (rc != MBPE_OK) return rc;
-    }
-    const uint64_t ids = 256ull + n_prior;
-    const uint64_t most = std::min<uint64_t>({n_tok ? n_tok - 1 : 0, ids * ids, 1ull << 30});
-    rc = wide_alloc_table(c, &c->wtab, std::max<uint64_t>(most, 1));
-    if (rc != MBPE_OK) return rc;
-    launch_wide_pair_count_tokens(c->stream, c->wtok[0], c->wwt[0], n_tok, (uint32_t)ids, c->wtab, c->wctl, c->wtally, c->n_cus);
-    WideTally h = {};
-    HIPCHK(hipMemcpyAsync(&h, c->wtally, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    rc = wide_sync(c);
-    if (rc != MBPE_OK) return rc;
-    // the right size: the pairs there are plus what the first group of merges can add, at load factor 1/2
-    const uint64_t need = (uint64_t)c->h_wctl.n_entries + wide_headroom(h.top, n_tok, 16);
-    uint32_t bits = 12;
-    while ((1ull << bits) < 2 * need && bits < 31) ++bits;
-    if ((uint64_t)c->wtab.mask + 1 != (1ull << bits)) {
-        WideTable old = c->wtab;
-        rc = wide_alloc_table(c, &c->wtab, need);
-        if (rc != MBPE_OK) return rc;
-        HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->wctl->n_entries), 0, 1, c->stream));
-        launch_wide_rehash(c->stream, old, c->wtab, c->wctl);
-        rc = wide_sync(c);
-        trelease(c, old.keys); trelease(c, old.cnts);
-        if (rc != MBPE_OK) return rc;
-    }
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipEventSynchronize(c->ev1));
-    HIPCHK(hipEventElapsedTime(&c->stats.ms_begin, c->ev0, c->ev1));
-    c->stats.ms_begin += c->ms_replay;
-    c->stats.ms_steps = 0;
-    c->wn_upper = n_tok;
-    c->last_top = h.top;
-    c->wide_active = true;
-    c->begun = true;
-    pool_trim(c);
-    return MBPE_OK;
-}
-
-static int wide_steps(mbpe_ctx *c, uint32_t n_steps, uint32_t *done_out) {
-    *done_out = 0;
-    const uint32_t n_wide = c->n_target_total - c->n_target;
+int mbpe_train_steps(mbpe_ctx *c, uint32_t n_steps, uint32_t *steps_done_out) {
+    if (steps_done_out) *steps_done_out = 0;
+    if (!c) return MBPE_ERR_ARG;
+    if (!c->begun) { mbpe_host::set_last_error("mbpe_train_steps before mbpe_train_begin"); return MBPE_ERR_STATE; }
+    if (c->pending != Phase::None) { mbpe_host::set_last_error("an exchange is pending: call mbpe_comm_exchange_done"); return MBPE_ERR_STATE; }
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->wide) return train_steps16(c, n_steps, steps_done_out);
+    // a training that continues on 32-bit tokens: the slot stream's share first, then the conversion, then the rest
     uint32_t done = 0;
-    unsigned long long top = c->h_wbest.empty() ? (c->last_top == ~0ull ? c->wn_upper : c->last_top)
-                                                : (unsigned long long)c->h_wbest.back().count;
-    while (done < n_steps && c->wk < n_wide) {
-        const uint32_t group = std::min<uint32_t>({16u, n_steps - done, n_wide - c->wk});
-        // room for what this group can insert (load factor 1/2 at most)
-        if (2 * ((uint64_t)c->h_wctl.n_entries + wide_headroom(top, c->wn_upper, group)) > (uint64_t)c->wtab.mask + 1) {
-            WideTable old = c->wtab;
-            int rc = wide_alloc_table(c, &c->wtab, 2 * ((uint64_t)c->h_wctl.n_entries + wide_headroom(top, c->wn_upper, group)));
-            if (rc != MBPE_OK) return rc;
-            HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->wctl->n_entries), 0, 1, c->stream));
-            launch_wide_rehash(c->stream, old, c->wtab, c->wctl);
-            HIPCHK(hipStreamSynchronize(c->stream));
-            trelease(c, old.keys); trelease(c, old.cnts);
-            c->stats.n_table_grows++;
-        }
-        HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->wctl->k_limit), (int)(c->wk + group), 1, c->stream));
-        HIPCHK(hipEventRecord(c->ev0, c->stream));
-        for (uint32_t g = 0; g < group; ++g) {
-            launch_wide_argmax(c->stream, c->wtab, c->wctl, c->wbest, c->warg, c->wlim);
-            if (c->wfirst)
-                launch_wide_first(c->stream, c->wtok[c->wcur ^ (g & 1)], c->wn_upper, c->wtab, c->wctl, c->wbest, c->warg,
-                                  c->wfs, c->wlim);
-            launch_wide_merge(c->stream, c->wtok[c->wcur ^ (g & 1)], c->wtok[c->wcur ^ (g & 1) ^ 1], c->wn_upper, c->wval,
-                              c->wscratch, c->wtab, c->wctl, 256 + c->n_target, c->wwt[c->wcur ^ (g & 1)],
-                              c->wwt[c->wcur ^ (g & 1) ^ 1]);
-        }
-        HIPCHK(hipEventRecord(c->ev1, c->stream));
-        int rc = wide_sync(c);
+    if (!c->wr.active) {
+        int rc = train_steps16(c, n_steps, &done);
+        if (steps_done_out) *steps_done_out = done;
+        if (rc != MBPE_OK || done >= n_steps || c->exhausted || c->k < c->n_target) return rc;
+        bool out = false;
+        rc = first_ran_out(c, &out);
+        if (rc != MBPE_OK || out) return rc;
+        rc = wide_convert(c);
         if (rc != MBPE_OK) return rc;
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        c->stats.ms_steps += ms;
-        const uint32_t ran = c->h_wctl.k - c->wk;
-        // empty table (Tokenizer.h:586-588): cannot happen after a 16-bit part that merged -- except in `first` mode, where
-        // it means no pair is left: the loop ends there, with fewer merges than the vocabulary asks for
-        if (ran == 0) break;
-        c->h_wbest.resize((size_t)c->wk + ran);
-        HIPCHK(hipMemcpy(c->h_wbest.data() + c->wk, c->wbest + c->wk, (size_t)ran * sizeof(WideBest), hipMemcpyDeviceToHost));
-        c->wcur ^= (int)(ran & 1u);
-        c->wn_upper = c->h_wctl.n;
-        c->wk += ran;
-        done += ran;
-        top = (unsigned long long)std::max(0, c->h_wbest.back().count);
-        if (!c->wfirst && c->h_wbest.back().count == 0 && done < n_steps && c->wk < n_wide) {
-            // The best pair no longer occurs anywhere: merging it changes nothing, the reference chooses it again and
-            // again (never-erased table, PairCount.h:249-260; the loop only ends on an empty table, Tokenizer.h:586-588)
-            const uint32_t fill = std::min<uint32_t>(n_steps - done, n_wide - c->wk);
-            c->h_wbest.resize((size_t)c->wk + fill, c->h_wbest.back());
-            c->wk += fill;
-            done += fill;
-            HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->wctl->k), (int)c->wk, 1, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            c->h_wctl.k = c->wk;
-        }
-        if (ran < group) break;
     }
-    *done_out = done;
-    return MBPE_OK;
+    uint32_t more = 0;
+    int rc = c->wr.steps(wide_dev(c), n_steps - done, &more);
+    if (steps_done_out) *steps_done_out = done + more;
+    return rc;
 }
 
 int mbpe_train_sequences(mbpe_ctx *c, uint32_t n_sequences, uint32_t *merges_done_out) {
@@ -2364,7 +1971,7 @@ int mbpe_train_sequences(mbpe_ctx *c, uint32_t n_sequences, uint32_t *merges_don
         mbpe_host::set_last_error("mbpe_train_sequences: not available with an external transport (use mbpe_train_steps)");
         return MBPE_ERR_STATE;
     }
-    if (c->wide_active || (c->wide && c->k >= c->n_target))
+    if (c->wr.active || (c->wide && c->k >= c->n_target))
         return mbpe_train_steps(c, n_sequences, merges_done_out);                    // (32-bit loop: one merge per pass)
     if (!use_batches(c)) return mbpe_train_steps(c, n_sequences, merges_done_out);   // one merge per pass
     HIPCHK(hipSetDevice(c->device));
@@ -2418,7 +2025,7 @@ int mbpe_train_result(mbpe_ctx *c, uint32_t *merges_out, int32_t *counts_out, ui
         while (real < n && (h[real] >> 32) != 0) ++real;
         n = real;
     }
-    const uint32_t nw = c->wide_active ? (uint32_t)c->h_wbest.size() : 0u;      // merges of the 32-bit continuation
+    const uint32_t nw = c->wr.n_merges();      // merges of the 32-bit continuation
     if (n_merges_out) *n_merges_out = n + nw;
     if (n + nw > cap_merges && merges_out) { mbpe_host::set_last_error("merges_out too small"); return MBPE_ERR_ARG; }
     if (!(n + nw) || !merges_out) return MBPE_OK;
@@ -2433,11 +2040,7 @@ int mbpe_train_result(mbpe_ctx *c, uint32_t *merges_out, int32_t *counts_out, ui
         merges_out[2 * i + 1] = key & 0xFFFFu;
         if (counts_out) counts_out[i] = (int32_t)(h[i] >> 32);
     }
-    for (uint32_t i = 0; i < nw; ++i) {
-        merges_out[2 * (n + i)] = c->h_wbest[i].first;
-        merges_out[2 * (n + i) + 1] = c->h_wbest[i].second;
-        if (counts_out) counts_out[n + i] = c->h_wbest[i].count;
-    }
+    c->wr.merges(merges_out + 2 * (size_t)n, counts_out ? counts_out + n : nullptr);
     return MBPE_OK;
 }
 
@@ -2465,13 +2068,7 @@ int mbpe_get_stats(mbpe_ctx *c, mbpe_stats *out) {
     for (int i = 0; i < 8; ++i) c->stats.size_hist[i] = c->begun ? c->h_ctl.size_hist[i] : 0;
     c->stats.n_skipped = c->begun ? c->h_ctl.n_skipped : 0;
     c->stats.n_skip_cut = c->begun ? c->h_ctl.n_skip_cut : 0;
-    if (c->begun && c->wide_active) {          // the stream and the table are the 32-bit ones now
-        c->stats.n_slots = c->h_wctl.n;
-        c->stats.n_live = c->h_wctl.n;
-        c->stats.n_merges += (uint32_t)c->h_wbest.size();
-        c->stats.n_pairs = c->h_wctl.n_entries;
-        c->stats.n_batches += c->wk;            // (one stream pass per merge)
-    }
+    if (c->begun && c->wr.active) c->wr.add_stats(&c->stats);
     *out = c->stats;
     return MBPE_OK;
 }
@@ -2515,19 +2112,7 @@ int mbpe_get_stream(mbpe_ctx *c, uint32_t *tokens_out, uint8_t *chunk_end_out, u
     if (!c->begun) { mbpe_host::set_last_error("mbpe_get_stream before mbpe_train_begin"); return MBPE_ERR_STATE; }
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->wide_active) {
-        const uint64_t n = c->h_wctl.n;
-        *n_out = n;
-        if (!tokens_out) return MBPE_OK;
-        if (cap < n) { mbpe_host::set_last_error("tokens_out too small"); return MBPE_ERR_ARG; }
-        if (n) HIPCHK(hipMemcpy(tokens_out, c->wtok[c->wcur], n * 4, hipMemcpyDeviceToHost));
-        for (uint64_t i = 0; i < n; ++i) {
-            // (a one-chunk corpus reports no chunk ends, like the slot stream)
-            if (chunk_end_out) chunk_end_out[i] = c->chunked ? (uint8_t)(tokens_out[i] >> 31) : 0;
-            tokens_out[i] &= kTokIdMask;
-        }
-        return MBPE_OK;
-    }
+    if (c->wr.active) return c->wr.get_stream(c->chunked, tokens_out, chunk_end_out, cap, n_out);
     std::vector<uint16_t> h(c->n_slots);
     HIPCHK(hipMemcpy(h.data(), c->tok[c->cur], c->n_slots * 2, hipMemcpyDeviceToHost));
     const bool endflag = c->chunked && !c->barrier;
@@ -2555,15 +2140,7 @@ int mbpe_stream_device(mbpe_ctx *c, const void **slots_out, uint64_t *n_slots_ou
     if (!c || !slots_out || !n_slots_out) return MBPE_ERR_ARG;
     if (!c->begun) { mbpe_host::set_last_error("mbpe_stream_device before mbpe_train_begin"); return MBPE_ERR_STATE; }
     HIPCHK(hipSetDevice(c->device));
-    if (c->wide_active) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        *slots_out = c->wtok[c->wcur];
-        *n_slots_out = c->h_wctl.n;
-        if (slot_bits_out) *slot_bits_out = 32;
-        if (end_bit_out) *end_bit_out = kTokEnd;
-        if (barrier_out) *barrier_out = MBPE_NO_BARRIER;
-        return MBPE_OK;
-    }
+    if (c->wr.active) return c->wr.stream_device(wide_dev(c), slots_out, n_slots_out, slot_bits_out, end_bit_out, barrier_out);
     int rc = sync_ctl(c);          // also refreshes which of the two buffers is live
     if (rc != MBPE_OK) return rc;
     *slots_out = c->tok[c->cur];
@@ -2578,7 +2155,7 @@ int mbpe_table_device(mbpe_ctx *c, const void **cells_out, uint32_t *vshift_out)
     if (!c || !cells_out || !vshift_out) return MBPE_ERR_ARG;
     if (!c->begun) { mbpe_host::set_last_error("mbpe_table_device before mbpe_train_begin"); return MBPE_ERR_STATE; }
     HIPCHK(hipSetDevice(c->device));
-    if (c->wide_active) { mbpe_host::set_last_error("the pair table is hashed (no dense view)"); return MBPE_ERR_STATE; }
+    if (c->wr.active) { mbpe_host::set_last_error("the pair table is hashed (no dense view)"); return MBPE_ERR_STATE; }
     int rc = sync_ctl(c);
     if (rc != MBPE_OK) return rc;
     if (!c->tab.cells) { mbpe_host::set_last_error("the pair table is hashed (no dense view)"); return MBPE_ERR_STATE; }
@@ -2592,28 +2169,7 @@ int mbpe_get_pairs(mbpe_ctx *c, uint32_t *first_out, uint32_t *second_out, int32
     if (!c || !n_out) return MBPE_ERR_ARG;
     if (!c->begun) { mbpe_host::set_last_error("mbpe_get_pairs before mbpe_train_begin"); return MBPE_ERR_STATE; }
     HIPCHK(hipSetDevice(c->device));
-    if (c->wide_active) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        const uint64_t n = c->h_wctl.n_entries, slots = (uint64_t)c->wtab.mask + 1;
-        *n_out = n;
-        if (!first_out) return MBPE_OK;
-        if (cap < n) { mbpe_host::set_last_error("pair arrays too small"); return MBPE_ERR_ARG; }
-        std::vector<unsigned long long> keys(slots);
-        std::vector<int32_t> cnts(slots);
-        HIPCHK(hipMemcpy(keys.data(), c->wtab.keys, slots * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(cnts.data(), c->wtab.cnts, slots * 4, hipMemcpyDeviceToHost));
-        uint64_t o = 0;
-        for (uint64_t i = 0; i < slots; ++i) {
-            if (keys[i] == kWideEmpty) continue;
-            if (o >= n) { mbpe_host::set_last_error("pair table holds more pairs than counted"); return MBPE_ERR_OVERFLOW; }
-            first_out[o] = (uint32_t)(keys[i] >> 32);
-            second_out[o] = (uint32_t)keys[i];
-            if (count_out) count_out[o] = cnts[i];
-            ++o;
-        }
-        if (o != n) { mbpe_host::set_last_error("pair table holds fewer pairs than counted"); return MBPE_ERR_OVERFLOW; }
-        return MBPE_OK;
-    }
+    if (c->wr.active) return c->wr.get_pairs(wide_dev(c), first_out, second_out, count_out, cap, n_out);
     int rc = sync_ctl(c);
     if (rc != MBPE_OK) return rc;
     const uint64_t n = c->h_ctl.n_entries;
@@ -2666,7 +2222,7 @@ int mbpe_compact(mbpe_ctx *c) {
     if (!c) return MBPE_ERR_ARG;
     if (!c->begun) { mbpe_host::set_last_error("mbpe_compact before mbpe_train_begin"); return MBPE_ERR_STATE; }
     HIPCHK(hipSetDevice(c->device));
-    if (c->wide_active) return MBPE_OK;        // (the 32-bit stream has no holes)
+    if (c->wr.active) return MBPE_OK;        // (the 32-bit stream has no holes)
     int rc = sync_ctl(c);
     if (rc != MBPE_OK) return rc;
     return do_compact(c);

@@ -66,7 +66,7 @@
 //          limits launches exactly those
 //
 // One GPU, either tie-break.  Slower per merge than the 16-bit path (one merge per pass, ~20 B of traffic per token),
-// but it turns MBPE_ERR_VOCAB into a training for GPT-4-size vocabularies.
+// but it turns MBPE_ERR_VOCAB into a training for GPT-4-size vocabularies.  The host side of the loop is wide_run.h.
 #ifndef MBPE_WIDE_H
 #define MBPE_WIDE_H
 

@@ -1,4 +1,4 @@
-"""The weighted 32-bit training loop (csrc/wide.hip under weighted_begin, csrc/train.cpp) at its limits, on the cases of
+"""The weighted 32-bit training loop (csrc/wide.hip under WideRun::begin_from, csrc/wide_run.cpp) at its limits, on the cases of
 tests/weighted_limit_cases.py: a corpus whose weighted positions add up to far more than 2^32 trains, step for step, to
 what the reference in Python integers gives -- pair and count at every step, then the stream, the chunk ends, the
 non-zero table and the decoded text -- and a pair whose true count is 2^31 or more, up to beyond 2^33 and wherever its
