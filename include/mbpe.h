@@ -896,6 +896,72 @@ MBPE_API int  mbpe_encoder_encode_batch_endmask(mbpe_encoder *e, const uint8_t *
                                                 uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
                                                 uint64_t *doc_tok_off_out);
 
+/* ---- long documents as overlapping windows --------------------------------- */
+
+/* The third way into [rows, seq_len]: one document per row like MBPE_PACK_PADDED, but a document that does not fit
+ * becomes several rows of its own, and consecutive rows share `stride` tokens of context (elsewhere: stride,
+ * return_overflowing_tokens, overflow_to_sample_mapping).  With keep = seq_len - nb - ne and step = keep - stride, a
+ * document d of L tokens tok[0 .. L) has W_d = 1 windows if L <= keep (an empty one too), else
+ * 1 + ceil((L - keep) / step).  Window i holds tok[a .. b), a = i * step, b = min(a + keep, L), and is the last one iff
+ * i == W_d - 1; the last window always brings a token no earlier one held.  row_start being the exclusive 64-bit prefix
+ * sum of W_d, row row_start[d] + i is [bos] tok[a .. b) [eos] -- bos in every window, eos in the last one only -- then
+ * pad_id up to seq_len; len[row] = nb + (b - a) + (ne and last); n_rows = the sum of W_d.  From the same walk
+ * (k_pack_windows, csrc/pack.hip):
+ *   labels  the bos cell gets tok[a], the cell of tok[t] gets tok[t + 1] -- also across the row end, in a window that
+ *           is not the last: the cell of tok[b - 1] gets tok[b] -- and the cell of tok[L - 1] gets eos if it is set,
+ *           else ignore_label (the bos cell of an empty document likewise); the eos cell and every pad cell get
+ *           ignore_label.  With score_once the bos cell and the first `stride` body cells of every window i >= 1 get
+ *           ignore_label too: those targets were labels in window i - 1.  Then, over the rows of one document in
+ *           order, the labels that are not ignore_label read tok[0 .. L) with bos (tok[1 .. L) without) and then eos
+ *           if it is set: each target exactly once, which is what a sliding-window perplexity sums over
+ *   pos     the element's index in its row, 0 .. len - 1; 0 in a pad cell        seg   d + 1; 0 in a pad cell
+ *   row_doc [n_rows] the row's document d        row_tok0 [n_rows] a, the index in the document of the row's first
+ *           body token; with the token byte offsets of the _byteoff calls, the bytes a row covers
+ * When every document has at most keep tokens, ids, len, labels, pos and seg are those of mbpe_pack_tokens_aux with
+ * MBPE_PACK_PADDED, bit for bit. */
+typedef struct {
+    uint32_t  stride;      /* body tokens two consecutive windows of a document share: 0 .. keep - 1 */
+    uint32_t  score_once;  /* 0 or 1, see above */
+    uint32_t *row_doc;     /* [n_rows] or NULL; on the same side as ids_out */
+    uint64_t *row_tok0;    /* [n_rows] or NULL; 8-byte aligned on the device */
+} mbpe_pack_window;
+
+/* mbpe_pack_tokens_aux for the window layout.  All arguments up to aux are those of mbpe_pack_tokens_aux; spec->layout
+ * must be MBPE_PACK_PADDED with pad_left and trunc_left 0; aux is required, all of its pointers may be NULL.
+ * MBPE_ERR_ARG: win NULL, seq_len < nb + ne + 1, stride >= keep, score_once > 1, row_doc with n_docs >= 2^32 - 1, more
+ * than 2^40 rows, and the NULL and alignment rules of mbpe_pack_tokens_aux (row_doc 4, row_tok0 8 bytes on the
+ * device); MBPE_ERR_VOCAB as for mbpe_pack_tokens.  All of it is checked, and a query (ids_out NULL) answered, on the
+ * host before the device is touched; a cap_rows too small is MBPE_ERR_ARG, writes nothing and still reports the count.
+ * On the device k_win_rows computes W_d, one scan workgroup and k_win_offsets make row_start of them, then
+ * k_pack_windows writes the matrices; mbpe_pack_kernel_ms covers the four.  Device scratch: 8 bytes per document. */
+MBPE_API int  mbpe_pack_windows(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits,
+                                int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs,
+                                const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
+                                uint32_t *len_out, uint64_t *n_rows_out, const mbpe_pack_aux *aux,
+                                const mbpe_pack_window *win);
+
+/* mbpe_encoder_encode_batch_aux and mbpe_encoder_encode_batch_endmask (aux required here too) for the window layout:
+ * their arguments, then win.  No token crosses to the host.  The row count depends on the tokens, so it comes back
+ * from the device's scan like the token count, and a query (ids_out NULL) runs the passes; a cap_rows too small is
+ * found after them, writes nothing and reports the count.  Host outputs, row_doc and row_tok0 included, go through
+ * buffers the encoder keeps: a repeat call of no larger size leaves mbpe_encoder_alloc_count as it is.  Windowing
+ * happens after the tokens exist, so "rank_order", dropout and "dedup" hold as for the other batch calls.
+ * mbpe_encoder_pack_ms covers k_win_rows, the scan, k_win_offsets and k_pack_windows. */
+MBPE_API int  mbpe_encoder_encode_batch_windows(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes,
+                                                int text_on_device, const uint64_t *chunk_off, uint64_t n_chunks,
+                                                const uint64_t *doc_chunk_off, uint64_t n_docs,
+                                                const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows,
+                                                int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                                                uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
+                                                uint64_t *doc_tok_off_out, const mbpe_pack_window *win);
+MBPE_API int  mbpe_encoder_encode_batch_endmask_windows(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
+                                                        const uint8_t *endmask_dev, const mbpe_single *singles,
+                                                        uint64_t n_singles, const uint64_t *doc_off, uint64_t n_docs,
+                                                        const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows,
+                                                        int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                                                        uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
+                                                        uint64_t *doc_tok_off_out, const mbpe_pack_window *win);
+
 /* ---- decode on the device ----------------------------------------------- */
 
 /* Tokenizer::decode (Tokenizer.h:725-751) for whole token streams on HIP device `device_id`: per token a byte

@@ -509,6 +509,9 @@ struct mbpe_encoder : DevQueue {
     // mbpe_encoder_encode_batch_aux: labels, positions and segments that go to the host
     DevBuf<void> d_labels;
     DevBuf<uint32_t> d_pos, d_seg;
+    // the _windows calls: the rows' prefix sum over the documents; row_doc and row_tok0 that go to the host
+    DevBuf<unsigned long long> d_row_start, d_row_tok0;
+    DevBuf<uint32_t> d_row_doc;
     float pack_ms = 0.f;                      // the pack kernel of the latest such call
     // token byte offsets: len[id] (host; empty with len_error set for a table mbpe_merges_check refuses), on the
     // device from the first such call on; the spans' byte counts, the singles' token indices, offsets bound for the host
@@ -674,6 +677,7 @@ struct EncPack {
     uint64_t *n_rows_out, *n_tokens_out;
     const mbpe_pack_aux *aux;
     uint64_t *doc_tok_off_out;
+    const mbpe_pack_window *win;    // the _windows calls; NULL: the spec's own layout
     uint32_t token_bits() const { return spec->out_bits == 16 ? 16 : 32; }
 };
 
@@ -1405,8 +1409,28 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool doc
     const mbpe_pack_spec &spec = *k.spec;
     const mbpe_pack_aux *aux = k.aux;
     const uint64_t n_docs = k.n_docs;
+    const mbpe_pack_window *win = k.win;
     int rc = MBPE_OK;
-    const uint64_t n_rows = pack_rows(spec, n_tokens, n_docs);
+    uint64_t n_rows = win ? 0 : pack_rows(spec, n_tokens, n_docs);
+    float rows_ms = 0.f;
+    if (win && n_docs) {
+        // the row count depends on the tokens: k_win_rows, the scan and k_win_offsets over the device's offsets, then the total
+        rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
+        if (rc == MBPE_OK) rc = e->d_row_start.reserve(pack_win_scratch_bytes(n_docs), e->mem);
+        if (rc != MBPE_OK) return rc;
+        if (!docs_on_device)
+            ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
+        ECHK(hipEventRecord(e->ev0, e->stream));
+        pack_launch_win_rows(e->stream, e->d_doc_off, n_docs, spec, *win, e->d_row_start);
+        if ((rc = e->finish(&rows_ms)) != MBPE_OK) return rc;
+        unsigned long long total = 0;
+        ECHK(hipMemcpyAsync(&total, e->d_row_start + n_docs, 8, hipMemcpyDeviceToHost, e->stream));
+        ECHK(hipStreamSynchronize(e->stream));
+        if (total > (1ull << 40)) return fail(MBPE_ERR_ARG, "more than 2^40 rows");
+        n_rows = total;
+        e->pack_ms = rows_ms;
+        e->last_ms += rows_ms;
+    }
     *k.n_rows_out = n_rows;
     if (k.n_tokens_out) *k.n_tokens_out = n_tokens;
     if (k.ids_out && k.cap_rows < n_rows) return fail(MBPE_ERR_ARG, "ids_out too small");
@@ -1425,23 +1449,35 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool doc
         if (rc == MBPE_OK && aux->pos) { rc = e->d_pos.reserve(cell_bytes, e->mem); d_aux.pos = e->d_pos; }
         if (rc == MBPE_OK && aux->seg) { rc = e->d_seg.reserve(cell_bytes, e->mem); d_aux.seg = e->d_seg; }
     }
+    mbpe_pack_window d_win = win ? *win : mbpe_pack_window{};
+    if (rc == MBPE_OK && win && !k.out_on_device) {
+        if (win->row_doc) { rc = e->d_row_doc.reserve(n_rows * 4, e->mem); d_win.row_doc = e->d_row_doc; }
+        if (rc == MBPE_OK && win->row_tok0) {
+            rc = e->d_row_tok0.reserve(n_rows * 8, e->mem);
+            d_win.row_tok0 = reinterpret_cast<uint64_t *>(e->d_row_tok0.get());
+        }
+    }
     if (rc != MBPE_OK) return rc;
-    if (!docs_on_device)
+    if (!docs_on_device && !win)
         ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
     const PackSrc src = {e->d_flat, e->d_doc_off, n_docs, n_tokens, k.token_bits()};
     const PackDst dst = {k.out_on_device ? k.ids_out : e->d_ids.get(),
                          k.out_on_device || !k.len_out ? k.len_out : e->d_len.get(), n_rows};
     ECHK(hipEventRecord(e->ev0, e->stream));
-    if (aux) pack_launch_aux(e->stream, src, spec, dst, d_aux);
+    if (win) pack_launch_windows(e->stream, src, spec, dst, d_aux, d_win, e->d_row_start);
+    else if (aux) pack_launch_aux(e->stream, src, spec, dst, d_aux);
     else pack_launch(e->stream, src, spec, dst);
     if ((rc = e->finish(&e->pack_ms)) != MBPE_OK) return rc;
     e->last_ms += e->pack_ms;
+    e->pack_ms += rows_ms;
     if (!k.out_on_device) {
         ECHK(hipMemcpyAsync(k.ids_out, e->d_ids, id_bytes, hipMemcpyDeviceToHost, e->stream));
         if (k.len_out) ECHK(hipMemcpyAsync(k.len_out, e->d_len, n_rows * 4, hipMemcpyDeviceToHost, e->stream));
         if (aux && aux->labels) ECHK(hipMemcpyAsync(aux->labels, e->d_labels, id_bytes, hipMemcpyDeviceToHost, e->stream));
         if (aux && aux->pos) ECHK(hipMemcpyAsync(aux->pos, e->d_pos, cell_bytes, hipMemcpyDeviceToHost, e->stream));
         if (aux && aux->seg) ECHK(hipMemcpyAsync(aux->seg, e->d_seg, cell_bytes, hipMemcpyDeviceToHost, e->stream));
+        if (win && win->row_doc) ECHK(hipMemcpyAsync(win->row_doc, e->d_row_doc, n_rows * 4, hipMemcpyDeviceToHost, e->stream));
+        if (win && win->row_tok0) ECHK(hipMemcpyAsync(win->row_tok0, e->d_row_tok0, n_rows * 8, hipMemcpyDeviceToHost, e->stream));
         ECHK(hipStreamSynchronize(e->stream));
     }
     return MBPE_OK;
@@ -1453,6 +1489,7 @@ int enc_batch_check(const mbpe_encoder *e, const EncPack &k) {
     if (k.ids_out && k.out_on_device &&
         ((uint64_t)(uintptr_t)k.ids_out % (k.spec->out_bits / 8) || (uint64_t)(uintptr_t)k.len_out % 4))
         return fail(MBPE_ERR_ARG, "ids_out or len_out is not aligned to its elements");
+    if (k.win) return pack_check_windows(k.spec, k.token_bits(), k.aux, k.win, k.n_docs, k.ids_out, k.out_on_device);
     return k.aux ? pack_check_aux(*k.spec, k.aux, nullptr, k.n_docs, k.ids_out, k.out_on_device) : MBPE_OK;
 }
 
@@ -1742,6 +1779,19 @@ static int enc_batch(mbpe_encoder *e, EncCall a, const EncPack &k) {
     return enc_guard("mbpe_encoder_encode_batch", [&] { return enc_batch_body(e, a, k); });
 }
 
+int mbpe_encoder_encode_batch_windows(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                      const uint64_t *chunk_off, uint64_t n_chunks, const uint64_t *doc_chunk_off,
+                                      uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows,
+                                      int out_on_device, uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out,
+                                      const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out, const mbpe_pack_window *win) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!aux || !win) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_batch_windows: NULL argument");
+    return enc_batch(e, {text, n_bytes, text_on_device, chunk_off, n_chunks},
+                     {doc_chunk_off, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
+                      doc_tok_off_out, win});
+}
+
 int mbpe_encoder_encode_batch_aux(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
                                   const uint64_t *chunk_off, uint64_t n_chunks, const uint64_t *doc_chunk_off,
                                   uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows,
@@ -1797,17 +1847,18 @@ int mbpe_encoder_encode_endmask_byteoff(mbpe_encoder *e, const uint8_t *text_dev
     return enc_guard("mbpe_encoder_encode_endmask", [&] { return enc_endmask_body(e, a); });
 }
 
-int mbpe_encoder_encode_batch_endmask(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
-                                      const uint8_t *endmask_dev, const mbpe_single *singles, uint64_t n_singles,
-                                      const uint64_t *doc_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
-                                      uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
-                                      uint64_t *n_tokens_out, const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out) {
-    const std::string who = "mbpe_encoder_encode_batch_endmask";
+// mbpe_encoder_encode_batch_endmask (win NULL) and mbpe_encoder_encode_batch_endmask_windows
+static int enc_batch_endmask(const std::string &who, mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
+                             const uint8_t *endmask_dev, const mbpe_single *singles, uint64_t n_singles,
+                             const uint64_t *doc_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
+                             uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                             uint64_t *n_tokens_out, const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out,
+                             const mbpe_pack_window *win) {
     if (n_rows_out) *n_rows_out = 0;
     if (n_tokens_out) *n_tokens_out = 0;
     if (!spec || !doc_off || !n_rows_out) return fail(MBPE_ERR_ARG, who + ": NULL argument");
     const EncPack k = {nullptr, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
-                       doc_tok_off_out};
+                       doc_tok_off_out, win};
     int rc = pack_check_spec(spec, k.token_bits());
     if (rc != MBPE_OK) return rc;
     rc = enc_endmask_check(who.c_str(), n_bytes, singles, n_singles, doc_off, n_docs, k.token_bits());
@@ -1837,6 +1888,30 @@ int mbpe_encoder_encode_batch_endmask(mbpe_encoder *e, const uint8_t *text_dev, 
         if (rc != MBPE_OK) return rc;
         return enc_pack_tail(e, k, n_tokens, true);
     });
+}
+
+int mbpe_encoder_encode_batch_endmask(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
+                                      const uint8_t *endmask_dev, const mbpe_single *singles, uint64_t n_singles,
+                                      const uint64_t *doc_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
+                                      uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                                      uint64_t *n_tokens_out, const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out) {
+    return enc_batch_endmask("mbpe_encoder_encode_batch_endmask", e, text_dev, n_bytes, endmask_dev, singles, n_singles,
+                             doc_off, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
+                             doc_tok_off_out, nullptr);
+}
+
+int mbpe_encoder_encode_batch_endmask_windows(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
+                                              const uint8_t *endmask_dev, const mbpe_single *singles, uint64_t n_singles,
+                                              const uint64_t *doc_off, uint64_t n_docs, const mbpe_pack_spec *spec,
+                                              void *ids_out, uint64_t cap_rows, int out_on_device, uint32_t *len_out,
+                                              uint64_t *n_rows_out, uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
+                                              uint64_t *doc_tok_off_out, const mbpe_pack_window *win) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!aux || !win) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_batch_endmask_windows: NULL argument");
+    return enc_batch_endmask("mbpe_encoder_encode_batch_endmask_windows", e, text_dev, n_bytes, endmask_dev, singles,
+                             n_singles, doc_off, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out,
+                             n_tokens_out, aux, doc_tok_off_out, win);
 }
 
 int mbpe_encoder_pack_ms(const mbpe_encoder *e, float *ms_out) {

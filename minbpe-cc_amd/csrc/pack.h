@@ -46,6 +46,30 @@ int pack_check_aux(const mbpe_pack_spec &spec, const mbpe_pack_aux *aux, const u
 void pack_launch_aux(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst,
                      const mbpe_pack_aux &aux);
 
+// ---- overlapping windows (mbpe_pack_windows; the arithmetic is in pack_host.h) -----------------------------------------
+
+// the rules of the window calls that need neither offsets nor a device: pack_check_spec, the window's own rules
+// (pack_win_check), pack_check_aux, and with out_on_device the alignment of row_doc (4) and row_tok0 (8).  MBPE_OK, or
+// MBPE_ERR_ARG / MBPE_ERR_VOCAB with the last error set
+int pack_check_windows(const mbpe_pack_spec *spec, uint32_t token_bits, const mbpe_pack_aux *aux,
+                       const mbpe_pack_window *win, uint64_t n_docs, const void *ids_out, int out_on_device);
+
+// n_rows of the host's document offsets: MBPE_OK, or MBPE_ERR_ARG (more than 2^40 rows) with the last error set
+int pack_window_rows(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec &spec, const mbpe_pack_window &win,
+                     uint64_t *n_rows_out);
+
+// k_win_rows, the scan and k_win_offsets on `stream`: row_start (device, pack_win_scratch_bytes(n_docs): n_docs + 1
+// entries and, behind them, one per span of 1,024 documents) becomes the exclusive prefix sum of W_d over the device's
+// document offsets, row_start[n_docs] the row count.  n_docs > 0.  Nothing is waited for
+uint64_t pack_win_scratch_bytes(uint64_t n_docs);
+void pack_launch_win_rows(hipStream_t stream, const unsigned long long *doc_off, uint64_t n_docs,
+                          const mbpe_pack_spec &spec, const mbpe_pack_window &win, unsigned long long *row_start);
+
+// k_pack_windows on `stream`: dst.n_rows == row_start[n_docs] > 0; aux's and win's pointers name device memory (ids,
+// labels, pos and seg 16-byte aligned) or are NULL
+void pack_launch_windows(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst,
+                         const mbpe_pack_aux &aux, const mbpe_pack_window &win, const unsigned long long *row_start);
+
 }  // namespace mbpe
 
 #endif

@@ -6,6 +6,8 @@
 //   MBPE_PACK_PACKED   the stream S = [bos] doc [eos] over all documents, cut row-major into rows of seq_len; pad_id
 //                      behind its end
 //   unpack             a right-padded PADDED matrix and its lengths -> the flat tokens mbpe_decode_batch reads
+//   windows            PADDED rows, but a document that does not fit becomes several rows of its own that share `stride`
+//                      tokens (mbpe_pack_windows; k_win_rows .. k_pack_windows below, after k_pack_aux)
 //
 // All three are OUTPUT-centric like decode.hip's copy: the output, whose rows follow each other without a gap, is cut
 // at the 16-byte boundaries of its global address and a lane owns one such piece -- 8, 4 or 2 ids of 16, 32 or 64 bits.
@@ -383,6 +385,161 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_aux(PackAuxJob a) {
     }
 }
 
+// ---- overlapping windows ------------------------------------------------------------------------------------------------
+// A document that does not fit a row becomes several rows of its own, consecutive ones sharing `stride` body tokens
+// (mbpe.h, mbpe_pack_window; the arithmetic is pack_host.h's).  Three kernels:
+//   k_win_rows      one thread per document: W_d into row_start[d]; one wave per span of 1,024 documents, which also
+//                   leaves the span's sum
+//   k_win_scan      one workgroup: span.h's 64-bit scan over the spans' sums (per document it would walk 8 B at a
+//                   stride of a slice, uncoalesced: measured at 2.8 us per 1,000 documents); the total -- the row
+//                   count -- goes to row_start[n_docs]
+//   k_win_offsets   the spans again: a wave prefix sum turns the counts into the exclusive prefix sum, in place
+//   k_pack_windows  the matrices.  It cuts cell-index space like k_pack_aux (8 cells per lane, the same stores).  The
+//                   first cell of a lane finds its row by one division and the row's document by one binary search
+//                   PER LANE over row_start; the walk then steps to the next window and, behind a document's last
+//                   one, to the next document.  Labels use the one-element look-ahead of k_pack_aux; the label that
+//                   crosses a row end (tok[b] in the cell of tok[b - 1]) is one more read per row.
+// Bytes moved per cell: what k_pack_aux moves (the id and each output written once, a token read once, twice where
+// rows overlap), per row 16 B of offsets, 4 B of length and -- when asked for -- 4 B of row_doc and 8 B of row_tok0, per
+// lane at most log2(n_docs) probes of 8 B that neighbouring lanes share (none where every document is one row), per
+// document 16 B of offsets read and 8 B of row_start written twice and read once.
+struct PackWinJob {
+    PackAuxJob a;
+    const unsigned long long *row_start;     // n_docs + 1
+    uint32_t *row_doc;                       // or NULL
+    unsigned long long *row_tok0;            // or NULL
+    uint32_t stride, step, score_once;
+};
+
+__global__ __launch_bounds__(kSpanThreads) void k_win_rows(const unsigned long long *__restrict__ doc_off, uint64_t n_docs,
+                                                            uint32_t keep, uint32_t step,
+                                                            unsigned long long *__restrict__ row_start,
+                                                            unsigned long long *__restrict__ span_cnt) {
+    const uint64_t span = span_index(), base = span * kSpan;
+    if (base >= n_docs) return;
+    const uint32_t lane = lane_id();
+    unsigned long long s = 0;
+    for (int it = 0; it < kSpanIters; ++it) {
+        const uint64_t d = base + (uint64_t)it * kWave + lane;
+        if (d < n_docs) {
+            const unsigned long long w = pack_win_count(doc_off[d + 1] - doc_off[d], keep, step);
+            row_start[d] = w;
+            s += w;
+        }
+    }
+    for (int k = kWave / 2; k > 0; k >>= 1) s += __shfl_down(s, k, kWave);
+    if (lane == 0) span_cnt[span] = s;
+}
+
+__global__ __launch_bounds__(kScanThreads) void k_win_scan(unsigned long long *__restrict__ span_cnt, uint64_t n_spans,
+                                                            unsigned long long *__restrict__ total) {
+    __shared__ unsigned long long sh[kScanThreads];
+    const unsigned long long sum = span_scan_sum64(span_cnt, n_spans, sh);
+    if (threadIdx.x == 0) *total = sum;
+}
+
+__global__ __launch_bounds__(kSpanThreads) void k_win_offsets(unsigned long long *__restrict__ row_start, uint64_t n_docs,
+                                                               const unsigned long long *__restrict__ span_off) {
+    const uint64_t span = span_index(), base = span * kSpan;
+    if (base >= n_docs) return;
+    const uint32_t lane = lane_id();
+    unsigned long long o = span_off[span];
+    for (int it = 0; it < kSpanIters; ++it) {
+        const uint64_t d = base + (uint64_t)it * kWave + lane;
+        const unsigned long long w = d < n_docs ? row_start[d] : 0ull;
+        const unsigned long long incl = wave_prefix64(w, lane);
+        if (d < n_docs) row_start[d] = o + incl - w;
+        o += __shfl(incl, kWave - 1, kWave);
+    }
+}
+
+// the row the walk stands in: window i of document d, whose L tokens begin at d0; r = its body and whether it is the
+// last; T = its elements (bos and eos included)
+struct WinAt {
+    uint64_t d, i, d0, L;
+    PackWinRow r;
+    uint32_t T;
+};
+
+__device__ __forceinline__ void win_enter(const PackJob &j, uint32_t step, WinAt *w) {
+    w->d0 = j.doc_off[w->d];
+    w->L = j.doc_off[w->d + 1] - w->d0;
+    w->r = pack_win_row(w->L, w->i, j.keep, step);
+    w->T = j.nb + w->r.body + (j.ne & w->r.last);
+}
+
+template <int IN, int OUT>
+__global__ __launch_bounds__(kPackThreads) void k_pack_windows(PackWinJob wj) {
+    const PackJob &j = wj.a.j;
+    const bool want_lab = wj.a.labels != nullptr;
+    const uint32_t ign_lo = (uint32_t)wj.a.ignore, ign_hi = (uint32_t)(wj.a.ignore >> 32);
+    const uint64_t n_groups = (j.n_out + kAuxCells - 1) / kAuxCells;
+    for (uint64_t g = (uint64_t)blockIdx.x * kPackThreads + threadIdx.x; g < n_groups;
+         g += (uint64_t)gridDim.x * kPackThreads) {
+        const uint64_t c0 = g * kAuxCells;
+        const uint32_t cnt = j.n_out - c0 < kAuxCells ? (uint32_t)(j.n_out - c0) : kAuxCells;
+        uint64_t row = c0 / j.seq_len;
+        uint32_t col = (uint32_t)(c0 - row * j.seq_len);
+        WinAt w;
+        w.d = pack_win_doc(wj.row_start, j.n_docs, j.n_out / j.seq_len, row);
+        w.i = row - wj.row_start[w.d];
+        win_enter(j, wj.step, &w);
+        uint32_t id[kAuxCells], lab[kAuxCells], ps[kAuxCells], sg[kAuxCells];
+        uint32_t ign_mask = 0, ahead = 0;                        // ahead: the token read as the cell before's label
+        bool have_ahead = false;
+#pragma unroll
+        for (uint32_t e = 0; e < kAuxCells; ++e) {
+            id[e] = j.pad; lab[e] = ign_lo; ps[e] = 0; sg[e] = 0;
+            ign_mask |= 1u << e;
+            if (e >= cnt) continue;
+            if (col == 0) {
+                if (j.len) j.len[row] = w.T;
+                if (wj.row_doc) wj.row_doc[row] = (uint32_t)w.d;
+                if (wj.row_tok0) wj.row_tok0[row] = w.r.a;
+            }
+            const uint32_t k = col, body_end = j.nb + w.r.body;  // elements [nb, body_end) are tokens
+            if (k < w.T) {
+                if (k >= body_end) id[e] = j.eos;
+                else if (k < j.nb) id[e] = j.bos;
+                else id[e] = have_ahead ? ahead : pack_read<IN>(j.tok, w.d0 + w.r.a + (k - j.nb));
+                have_ahead = false;
+                if (want_lab && k < body_end) {
+                    // the target: the document's token behind this element (index nx), eos behind the last one
+                    const uint64_t nx = w.r.a + (k + 1 - j.nb);
+                    bool is = true;
+                    uint32_t v = j.eos;
+                    if (nx < w.L) {
+                        v = pack_read<IN>(j.tok, w.d0 + nx);
+                        if (k + 1 < body_end) { ahead = v; have_ahead = true; }
+                    } else {
+                        is = j.ne != 0;
+                    }
+                    if (wj.score_once && w.i && k < j.nb + wj.stride) is = false;
+                    if (is) {
+                        lab[e] = v;
+                        ign_mask &= ~(1u << e);
+                    }
+                }
+                ps[e] = k;
+                sg[e] = (uint32_t)w.d + 1u;
+            }
+            if (++col == j.seq_len) {
+                col = 0;
+                ++row;
+                if (e + 1 < cnt) {                               // (another cell of the group: the row exists)
+                    if (w.r.last) { ++w.d; w.i = 0; }
+                    else ++w.i;
+                    win_enter(j, wj.step, &w);
+                }
+            }
+        }
+        aux_store_ids<OUT>(j.out, c0, cnt, id, 0u, 0u);
+        if (want_lab) aux_store_ids<OUT>(wj.a.labels, c0, cnt, lab, ign_mask, ign_hi);
+        if (wj.a.pos) aux_store32(wj.a.pos, c0, cnt, ps);
+        if (wj.a.seg) aux_store32(wj.a.seg, c0, cnt, sg);
+    }
+}
+
 #define PCHK(expr) MBPE_HIP_CHECK(expr, true)
 
 uint32_t pack_grid(const void *out, uint64_t n_out, uint32_t out_bits) {
@@ -416,6 +573,11 @@ void launch_pack_aux(hipStream_t stream, bool packed, const PackAuxJob &a) {
     else hipLaunchKernelGGL((k_pack_aux<IN, OUT, false>), grid, block, 0, stream, a);
 }
 
+template <int IN, int OUT>
+void launch_pack_windows(hipStream_t stream, const PackWinJob &wj) {
+    hipLaunchKernelGGL((k_pack_windows<IN, OUT>), dim3(aux_grid(wj.a.j.n_out)), dim3(kPackThreads), 0, stream, wj);
+}
+
 // device time of the calling thread's latest one-shot pack or unpack kernel (mbpe_pack_kernel_ms)
 thread_local float g_pack_ms = 0.f;
 
@@ -437,7 +599,7 @@ struct OneShot : DevQueue {
 
 int pack_run(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
              const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec &spec, void *ids_out, uint64_t n_rows,
-             int out_on_device, uint32_t *len_out, const mbpe_pack_aux *aux) {
+             int out_on_device, uint32_t *len_out, const mbpe_pack_aux *aux, const mbpe_pack_window *win = nullptr) {
     int rc = find_device(device_id);
     if (rc != MBPE_OK) return rc;
     OneShot dev;
@@ -460,11 +622,24 @@ int pack_run(int device_id, const void *tokens, uint64_t n_tokens, uint32_t toke
         if (rc == MBPE_OK && aux->pos) { rc = dev.alloc(&p, cell_bytes, nullptr); d_aux.pos = static_cast<uint32_t *>(p); }
         if (rc == MBPE_OK && aux->seg) { rc = dev.alloc(&p, cell_bytes, nullptr); d_aux.seg = static_cast<uint32_t *>(p); }
     }
+    // the windows: row_start, and row_doc / row_tok0 of a host call like the aux outputs
+    mbpe_pack_window d_win = win ? *win : mbpe_pack_window{};
+    void *d_row_start = nullptr;
+    if (rc == MBPE_OK && win) {
+        void *p = nullptr;
+        rc = dev.alloc(&d_row_start, pack_win_scratch_bytes(n_docs), nullptr);
+        if (rc == MBPE_OK && win->row_doc && !out_on_device) { rc = dev.alloc(&p, n_rows * 4, nullptr); d_win.row_doc = static_cast<uint32_t *>(p); }
+        if (rc == MBPE_OK && win->row_tok0 && !out_on_device) { rc = dev.alloc(&p, n_rows * 8, nullptr); d_win.row_tok0 = static_cast<uint64_t *>(p); }
+    }
     if (rc != MBPE_OK) return rc;
     const PackSrc src = {d_tok, static_cast<const unsigned long long *>(d_off), n_docs, n_tokens, token_bits};
     const PackDst dst = {d_ids, static_cast<uint32_t *>(d_len), n_rows};
     PCHK(hipEventRecord(dev.ev0, dev.stream));
-    if (aux) pack_launch_aux(dev.stream, src, spec, dst, d_aux);
+    if (win) {
+        unsigned long long *row_start = static_cast<unsigned long long *>(d_row_start);
+        pack_launch_win_rows(dev.stream, src.doc_off, n_docs, spec, d_win, row_start);
+        pack_launch_windows(dev.stream, src, spec, dst, d_aux, d_win, row_start);
+    } else if (aux) pack_launch_aux(dev.stream, src, spec, dst, d_aux);
     else pack_launch(dev.stream, src, spec, dst);
     rc = dev.finish(&g_pack_ms);
     if (rc != MBPE_OK) return rc;
@@ -474,6 +649,8 @@ int pack_run(int device_id, const void *tokens, uint64_t n_tokens, uint32_t toke
         if (aux && aux->labels) PCHK(hipMemcpyAsync(aux->labels, d_aux.labels, id_bytes, hipMemcpyDeviceToHost, dev.stream));
         if (aux && aux->pos) PCHK(hipMemcpyAsync(aux->pos, d_aux.pos, cell_bytes, hipMemcpyDeviceToHost, dev.stream));
         if (aux && aux->seg) PCHK(hipMemcpyAsync(aux->seg, d_aux.seg, cell_bytes, hipMemcpyDeviceToHost, dev.stream));
+        if (win && win->row_doc) PCHK(hipMemcpyAsync(win->row_doc, d_win.row_doc, n_rows * 4, hipMemcpyDeviceToHost, dev.stream));
+        if (win && win->row_tok0) PCHK(hipMemcpyAsync(win->row_tok0, d_win.row_tok0, n_rows * 8, hipMemcpyDeviceToHost, dev.stream));
         PCHK(hipStreamSynchronize(dev.stream));
     }
     return MBPE_OK;
@@ -618,6 +795,64 @@ void pack_launch_aux(hipStream_t stream, const PackSrc &src, const mbpe_pack_spe
     }
 }
 
+static PackWinJob pack_win_job(const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst, const mbpe_pack_aux &aux,
+                               const mbpe_pack_window &win, const unsigned long long *row_start) {
+    PackWinJob wj = {};
+    wj.a = {pack_job(src, spec, dst), aux.labels, aux.pos, aux.seg, (unsigned long long)aux.ignore_label};
+    wj.row_start = row_start;
+    wj.row_doc = win.row_doc;
+    wj.row_tok0 = reinterpret_cast<unsigned long long *>(win.row_tok0);
+    wj.stride = win.stride;
+    wj.step = wj.a.j.keep - win.stride;
+    wj.score_once = win.score_once;
+    return wj;
+}
+
+void pack_launch_win_rows(hipStream_t stream, const unsigned long long *doc_off, uint64_t n_docs,
+                          const mbpe_pack_spec &spec, const mbpe_pack_window &win, unsigned long long *row_start) {
+    const uint32_t keep = spec.seq_len - (spec.bos_id != MBPE_NO_TOKEN) - (spec.eos_id != MBPE_NO_TOKEN);
+    unsigned long long *span_cnt = row_start + n_docs + 1;       // (pack_win_scratch_bytes)
+    const dim3 grid(span_grid(n_docs)), block(kSpanThreads);
+    hipLaunchKernelGGL(k_win_rows, grid, block, 0, stream, doc_off, n_docs, keep, keep - win.stride, row_start, span_cnt);
+    hipLaunchKernelGGL(k_win_scan, dim3(1), dim3(kScanThreads), 0, stream, span_cnt, span_count(n_docs), row_start + n_docs);
+    hipLaunchKernelGGL(k_win_offsets, grid, block, 0, stream, row_start, n_docs, span_cnt);
+}
+
+uint64_t pack_win_scratch_bytes(uint64_t n_docs) { return (n_docs + 1 + span_count(n_docs)) * 8; }
+
+void pack_launch_windows(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst,
+                         const mbpe_pack_aux &aux, const mbpe_pack_window &win, const unsigned long long *row_start) {
+    const PackWinJob wj = pack_win_job(src, spec, dst, aux, win, row_start);
+    if (src.bits == 16) {
+        if (spec.out_bits == 16) launch_pack_windows<16, 16>(stream, wj);
+        else if (spec.out_bits == 32) launch_pack_windows<16, 32>(stream, wj);
+        else launch_pack_windows<16, 64>(stream, wj);
+    } else {
+        if (spec.out_bits == 32) launch_pack_windows<32, 32>(stream, wj);
+        else launch_pack_windows<32, 64>(stream, wj);
+    }
+}
+
+int pack_check_windows(const mbpe_pack_spec *spec, uint32_t token_bits, const mbpe_pack_aux *aux,
+                       const mbpe_pack_window *win, uint64_t n_docs, const void *ids_out, int out_on_device) {
+    int rc = pack_check_spec(spec, token_bits);
+    if (rc != MBPE_OK) return rc;
+    const char *msg = "";
+    if ((rc = pack_win_check(*spec, win, n_docs, &msg)) != MBPE_OK) return fail(rc, msg);
+    if ((rc = pack_check_aux(*spec, aux, nullptr, n_docs, ids_out, out_on_device)) != MBPE_OK) return rc;
+    if (ids_out && out_on_device && ((uint64_t)(uintptr_t)win->row_doc % 4 || (uint64_t)(uintptr_t)win->row_tok0 % 8))
+        return fail(MBPE_ERR_ARG, "row_doc or row_tok0 in device memory is not aligned to its elements");
+    return MBPE_OK;
+}
+
+int pack_window_rows(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec &spec, const mbpe_pack_window &win,
+                     uint64_t *n_rows_out) {
+    const char *msg = "";
+    const uint32_t keep = spec.seq_len - (spec.bos_id != MBPE_NO_TOKEN) - (spec.eos_id != MBPE_NO_TOKEN);
+    const int rc = pack_win_rows(doc_tok_off, n_docs, keep, win.stride, n_rows_out, &msg);
+    return rc == MBPE_OK ? MBPE_OK : fail(rc, msg);
+}
+
 int pack_check_aux(const mbpe_pack_spec &spec, const mbpe_pack_aux *aux, const uint64_t *doc_tok_off, uint64_t n_docs,
                    const void *ids_out, int out_on_device) {
     if (!aux) return fail(MBPE_ERR_ARG, "NULL pack aux");
@@ -706,6 +941,32 @@ int mbpe_pack_tokens_aux(int device_id, const void *tokens, uint64_t n_tokens, u
                         n_rows, out_on_device, len_out, aux);
     } catch (const std::bad_alloc &) {
         return fail(MBPE_ERR_OOM, "mbpe_pack_tokens_aux: host allocation failed");
+    }
+}
+
+int mbpe_pack_windows(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
+                      const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
+                      uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                      const mbpe_pack_aux *aux, const mbpe_pack_window *win) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (!n_rows_out || !doc_tok_off || !spec || !aux || !win || (!tokens && n_tokens))
+        return fail(MBPE_ERR_ARG, "mbpe_pack_windows: NULL argument");
+    int rc = pack_check_windows(spec, token_bits, aux, win, n_docs, ids_out, out_on_device);
+    if (rc == MBPE_OK) rc = mbpe_host::check_doc_tok_off(doc_tok_off, n_docs, n_tokens);
+    if (rc != MBPE_OK) return rc;
+    if (n_tokens >> 40 || n_docs >> 40) return fail(MBPE_ERR_ARG, "more than 2^40 tokens or documents");
+    uint64_t n_rows = 0;
+    if ((rc = pack_window_rows(doc_tok_off, n_docs, *spec, *win, &n_rows)) != MBPE_OK) return rc;
+    *n_rows_out = n_rows;
+    if (!ids_out) return MBPE_OK;                                // the query
+    if (cap_rows < n_rows) return fail(MBPE_ERR_ARG, "ids_out too small");
+    if (n_rows == 0) return MBPE_OK;
+    if (out_on_device && (uint64_t)(uintptr_t)len_out % 4) return fail(MBPE_ERR_ARG, "len_out is not aligned to its elements");
+    try {
+        return pack_run(device_id, tokens, n_tokens, token_bits, tokens_on_device, doc_tok_off, n_docs, *spec, ids_out,
+                        n_rows, out_on_device, len_out, aux, win);
+    } catch (const std::bad_alloc &) {
+        return fail(MBPE_ERR_OOM, "mbpe_pack_windows: host allocation failed");
     }
 }
 

@@ -1,11 +1,14 @@
 // The host arithmetic of the training-batch outputs of pack.hip (labels, positions, segments, cu_seqlens): the range
 // of ignore_label, the limits of the 32-bit outputs, and the cu_seqlens merge over the host's document offsets.
 // Plain C++ without a HIP include, so that a host compiler builds it alone (tests/pack_check.cpp).  Every function
-// returns an mbpe_status and, on an error, a static text in *msg; nothing here touches a device.
+// returns an mbpe_status and, on an error, a static text in *msg; nothing here touches a device.  The arithmetic of
+// the overlapping windows (mbpe_pack_windows) is here too: what the kernels of pack.hip and the host share is marked
+// MBPE_HD (span.h), and tests/pack_window_check.cpp runs it.
 #ifndef MBPE_PACK_HOST_H
 #define MBPE_PACK_HOST_H
 
 #include "mbpe.h"
+#include "span.h"
 
 #include <cstdint>
 
@@ -83,6 +86,94 @@ inline int pack_cu_seqlens(const uint64_t *doc_tok_off, uint64_t n_docs, uint32_
         }
     }
     return MBPE_OK;
+}
+
+// ---- overlapping windows (mbpe_pack_windows) -------------------------------------------------------------------------
+// A document of L tokens that does not fit keep = seq_len - nb - ne body tokens becomes W rows of its own; window i
+// holds tok[a .. b) with a = i * step, b = min(a + keep, L), step = keep - stride, and is the last one iff a + keep >= L
+// (which for L > keep is i == ceil((L - keep) / step): the last window always brings a token no earlier one held).
+MBPE_HD uint64_t pack_win_count(uint64_t L, uint32_t keep, uint32_t step) {
+    return L <= keep ? 1ull : 1ull + (L - keep + step - 1) / step;
+}
+
+// window i of a document of L tokens: its body tok[a .. a + body), and whether it is the document's last
+struct PackWinRow {
+    uint64_t a;
+    uint32_t body, last;
+};
+MBPE_HD PackWinRow pack_win_row(uint64_t L, uint64_t i, uint32_t keep, uint32_t step) {
+    PackWinRow r;
+    r.a = i * step;
+    r.last = r.a + keep >= L;
+    r.body = r.last ? (uint32_t)(L - r.a) : keep;
+    return r;
+}
+
+constexpr uint64_t kPackWinMaxRows = 1ull << 40;
+
+// the argument rules of the window calls that need no offsets: the spec is PADDED without pad_left / trunc_left and
+// has room for one body token, stride < keep, score_once is 0 or 1, row_doc holds d in 32 bits
+inline int pack_win_check(const mbpe_pack_spec &spec, const mbpe_pack_window *win, uint64_t n_docs, const char **msg) {
+    if (!win) {
+        *msg = "NULL pack window";
+        return MBPE_ERR_ARG;
+    }
+    if (spec.layout != MBPE_PACK_PADDED || spec.pad_left || spec.trunc_left) {
+        *msg = "windows go with MBPE_PACK_PADDED, pad_left 0 and trunc_left 0 only";
+        return MBPE_ERR_ARG;
+    }
+    const uint32_t nbe = (spec.bos_id != MBPE_NO_TOKEN) + (spec.eos_id != MBPE_NO_TOKEN);
+    if (spec.seq_len < nbe + 1) {
+        *msg = "seq_len has no room for bos, eos and one token";
+        return MBPE_ERR_ARG;
+    }
+    if (win->stride >= spec.seq_len - nbe) {
+        *msg = "stride must be below seq_len - nb - ne";
+        return MBPE_ERR_ARG;
+    }
+    if (win->score_once > 1) {
+        *msg = "score_once must be 0 or 1";
+        return MBPE_ERR_ARG;
+    }
+    if (win->row_doc && n_docs >= 0xFFFFFFFFull) {
+        *msg = "row_doc with 2^32 - 1 documents or more";
+        return MBPE_ERR_ARG;
+    }
+    return MBPE_OK;
+}
+
+// n_rows = the sum of W_d over the host's document offsets (the spec and the window have passed pack_win_check); more
+// than 2^40 rows is MBPE_ERR_ARG with *n_rows_out left alone
+inline int pack_win_rows(const uint64_t *doc_tok_off, uint64_t n_docs, uint32_t keep, uint32_t stride, uint64_t *n_rows_out,
+                         const char **msg) {
+    uint64_t n = 0;
+    for (uint64_t d = 0; d < n_docs; ++d) {
+        const uint64_t w = pack_win_count(doc_tok_off[d + 1] - doc_tok_off[d], keep, keep - stride);
+        n = w > kPackWinMaxRows ? w : n + w;                     // (no wrap: n <= 2^40 here)
+        if (n > kPackWinMaxRows) {
+            *msg = "more than 2^40 rows";
+            return MBPE_ERR_ARG;
+        }
+    }
+    *n_rows_out = n;
+    return MBPE_OK;
+}
+
+// the document and the window of a row < n_rows: the largest d with row_start[d] <= row (every document has a window,
+// so row_start -- the exclusive prefix sum of W_d, n_docs + 1 entries, the last one n_rows -- ascends strictly), then
+// i = row - row_start[d].  Every document has at least one row, before the row and behind it: d <= row, and
+// n_docs - 1 - d <= n_rows - 1 - row.  The search starts from these bounds, so where every document is one row it
+// probes nothing, and otherwise never more than log2 of the rows beyond one per document
+MBPE_HD uint64_t pack_win_doc(const unsigned long long *row_start, uint64_t n_docs, uint64_t n_rows, uint64_t row) {
+    const uint64_t behind = n_rows - row;                        // rows from this one on: at least as many documents
+    uint64_t d = n_docs > behind ? n_docs - behind : 0;          // row_start[d] <= row < row_start[hi]
+    uint64_t hi = row + 1 < n_docs ? row + 1 : n_docs;
+    while (hi - d > 1) {
+        const uint64_t mid = d + (hi - d) / 2;
+        if (row_start[mid] <= row) d = mid;
+        else hi = mid;
+    }
+    return d;
 }
 
 }  // namespace mbpe

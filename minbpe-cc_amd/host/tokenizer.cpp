@@ -861,16 +861,21 @@ int Tokenizer::encode_ranges(const char *text, const uint64_t *doc_off, uint64_t
 int Tokenizer::encode_batch_packed(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
                                    const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
                                    uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out,
-                                   const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out, bool device_split) {
+                                   const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out, bool device_split,
+                                   const mbpe_pack_window *win) {
     if (device_split) {
         DeviceSplit ds;
         int rc = split_on_device(text, doc_off, n_docs, verbose, device, &ds);
         if (rc != MBPE_OK) return rc;
         mbpe_encoder *enc = device_encoder(device);
         uint64_t n_tokens = 0;
-        rc = mbpe_encoder_encode_batch_endmask(enc, ds.d_text, ds.n_bytes, ds.d_mask, ds.singles.data(), ds.singles.size(),
-                                               ds.doc_off.data(), n_docs, spec, ids_out, cap_rows, out_on_device, len_out,
-                                               n_rows_out, &n_tokens, aux, doc_tok_off_out);
+        rc = win ? mbpe_encoder_encode_batch_endmask_windows(enc, ds.d_text, ds.n_bytes, ds.d_mask, ds.singles.data(),
+                                                             ds.singles.size(), ds.doc_off.data(), n_docs, spec, ids_out,
+                                                             cap_rows, out_on_device, len_out, n_rows_out, &n_tokens, aux,
+                                                             doc_tok_off_out, win)
+                 : mbpe_encoder_encode_batch_endmask(enc, ds.d_text, ds.n_bytes, ds.d_mask, ds.singles.data(),
+                                                     ds.singles.size(), ds.doc_off.data(), n_docs, spec, ids_out, cap_rows,
+                                                     out_on_device, len_out, n_rows_out, &n_tokens, aux, doc_tok_off_out);
         if (n_tokens_out) *n_tokens_out = n_tokens;
         if (rc == MBPE_OK && verbose)
             std::cout << "Encoded " << n_docs << " texts (length " << ds.n_bytes << ") to " << n_tokens << " tokens in "
@@ -883,7 +888,11 @@ int Tokenizer::encode_batch_packed(const char *text, const uint64_t *doc_off, ui
     mbpe_encoder *enc = device_encoder(device);
     uint64_t n_tokens = 0;
     const uint8_t *bytes = reinterpret_cast<const uint8_t *>(buf.data());
-    const int rc = aux ? mbpe_encoder_encode_batch_aux(enc, bytes, buf.size(), 0, off.data(), off.size() - 1,
+    const int rc = win ? mbpe_encoder_encode_batch_windows(enc, bytes, buf.size(), 0, off.data(), off.size() - 1,
+                                                           first_chunk.data(), n_docs, spec, ids_out, cap_rows,
+                                                           out_on_device, len_out, n_rows_out, &n_tokens, aux,
+                                                           doc_tok_off_out, win)
+                   : aux ? mbpe_encoder_encode_batch_aux(enc, bytes, buf.size(), 0, off.data(), off.size() - 1,
                                                        first_chunk.data(), n_docs, spec, ids_out, cap_rows, out_on_device,
                                                        len_out, n_rows_out, &n_tokens, aux, doc_tok_off_out)
                        : mbpe_encoder_encode_batch(enc, bytes, buf.size(), 0, off.data(), off.size() - 1,
@@ -1482,6 +1491,33 @@ int mbpe_tok_encode_batch_aux_device(mbpe_tokenizer *t, const uint8_t *text, con
         return t->t->encode_batch_packed(reinterpret_cast<const char *>(text), doc_off, n_docs, verbose != 0, device_id,
                                          spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
                                          doc_tok_off_out, t->t->encode_split());
+    } catch (const mbpe_host::CodedError &e) {      // mbpe_encoder_create failed: its own code
+        mbpe_host::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        mbpe_host::set_last_error(e.what());
+        return MBPE_ERR_ARG;
+    }
+}
+
+int mbpe_tok_encode_batch_windows_device(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off, uint64_t n_docs,
+                                         int verbose, int device_id, const mbpe_pack_spec *spec, void *ids_out,
+                                         uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                                         uint64_t *n_tokens_out, const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out,
+                                         const mbpe_pack_window *win) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!t || !n_rows_out || !doc_off || !spec || !aux || !win || device_id < 0 ||
+        (!text && doc_off[n_docs] > doc_off[0])) {
+        mbpe_host::set_last_error("mbpe_tok_encode_batch_windows_device: NULL argument or negative device");
+        return MBPE_ERR_ARG;
+    }
+    for (uint64_t i = 0; i < n_docs; ++i)
+        if (doc_off[i + 1] < doc_off[i]) { mbpe_host::set_last_error("doc_off must be ascending"); return MBPE_ERR_ARG; }
+    try {
+        return t->t->encode_batch_packed(reinterpret_cast<const char *>(text), doc_off, n_docs, verbose != 0, device_id,
+                                         spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
+                                         doc_tok_off_out, t->t->encode_split(), win);
     } catch (const mbpe_host::CodedError &e) {      // mbpe_encoder_create failed: its own code
         mbpe_host::set_last_error(e.what());
         return e.code;

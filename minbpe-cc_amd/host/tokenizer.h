@@ -80,13 +80,13 @@ public:
     int encode_ranges(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
                       bool device_split, std::vector<Token> *tokens, std::vector<uint64_t> *ranges,
                       std::vector<uint64_t> *doc_tok_off);
-    // the same documents as one id matrix (mbpe_encoder_encode_batch; with aux, mbpe_encoder_encode_batch_aux): spec,
-    // ids_out .. doc_tok_off_out go to it as they are, its code is returned
+    // the same documents as one id matrix (mbpe_encoder_encode_batch; with aux, mbpe_encoder_encode_batch_aux; with
+    // win, mbpe_encoder_encode_batch_windows): spec, ids_out .. doc_tok_off_out go to it as they are, its code is returned
     int encode_batch_packed(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
                             const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
                             uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out,
                             const mbpe_pack_aux *aux = nullptr, uint64_t *doc_tok_off_out = nullptr,
-                            bool device_split = false);
+                            bool device_split = false, const mbpe_pack_window *win = nullptr);
     // what the mbpe_tok_encode*_device calls of the C-ABI pass as device_split (mbpe_tok_set_encode_split)
     void set_encode_split(bool on) { encode_split_ = on; }
     bool encode_split() const { return encode_split_; }

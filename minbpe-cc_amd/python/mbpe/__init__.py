@@ -48,6 +48,7 @@ EXPORTS = [
     "mbpe_wordcount_result", "mbpe_wordcount_get", "mbpe_wordcount_stats", "mbpe_wordcount_reset",
     "mbpe_wordcount_set_option", "mbpe_wordcount_kernel_ms", "mbpe_wordcount_alloc_count",
     "mbpe_wordcount_export_size", "mbpe_wordcount_export", "mbpe_wordcount_merge_blob", "mbpe_wordcount_merge",
+    "mbpe_pack_windows", "mbpe_encoder_encode_batch_windows", "mbpe_encoder_encode_batch_endmask_windows",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -61,6 +62,7 @@ TOK_EXPORTS = [
     "mbpe_tok_set_encode_dedup", "mbpe_tok_train_pieces_begin", "mbpe_tok_train_pieces_add",
     "mbpe_tok_train_pieces_finish", "mbpe_tok_train_pieces_abort", "mbpe_tok_set_train_limits",
     "mbpe_tok_train_pieces_export_size", "mbpe_tok_train_pieces_export", "mbpe_tok_train_pieces_merge",
+    "mbpe_tok_encode_batch_windows_device",
 ]
 
 
@@ -109,6 +111,15 @@ class PackAux(ctypes.Structure):
     _fields_ = [
         ("labels", ctypes.c_void_p), ("pos", ctypes.c_void_p), ("seg", ctypes.c_void_p),
         ("ignore_label", ctypes.c_int64),
+    ]
+
+
+class PackWindow(ctypes.Structure):
+    """mbpe_pack_window (include/mbpe.h): how the windows of a long document overlap, and where the rows' document
+    numbers and first-token indices go (NULL: not asked for)."""
+    _fields_ = [
+        ("stride", ctypes.c_uint32), ("score_once", ctypes.c_uint32), ("row_doc", ctypes.c_void_p),
+        ("row_tok0", ctypes.c_void_p),
     ]
 
 
@@ -209,6 +220,9 @@ def lib():
     L.mbpe_encoder_encode_batch_aux.argtypes = L.mbpe_encoder_encode_batch.argtypes + [vp, vp]
     L.mbpe_tok_encode_batch_packed_device.argtypes = [vp, vp, vp, u64, i32, i32, vp, vp, u64, i32, vp, vp, vp]
     L.mbpe_tok_encode_batch_aux_device.argtypes = L.mbpe_tok_encode_batch_packed_device.argtypes + [vp, vp]
+    L.mbpe_pack_windows.argtypes = L.mbpe_pack_tokens_aux.argtypes + [vp]
+    L.mbpe_encoder_encode_batch_windows.argtypes = L.mbpe_encoder_encode_batch_aux.argtypes + [vp]
+    L.mbpe_tok_encode_batch_windows_device.argtypes = L.mbpe_tok_encode_batch_aux_device.argtypes + [vp]
     L.mbpe_tok_decode_padded_device.argtypes = [vp, vp, u64, u32, vp, i32, i32, vp, u64, vp, vp]
     L.mbpe_tok_encode_batch_device.argtypes = [vp, vp, vp, u64, i32, i32, vp, u64, vp, vp]
     L.mbpe_decoder_create.argtypes = [i32, vp, u32, vp, vp, vp, u32, ctypes.POINTER(vp)]
@@ -249,6 +263,7 @@ def lib():
     L.mbpe_tok_encode_batch_byteoff_device.argtypes = [vp, vp, vp, u64, i32, i32, vp, vp, u64, vp, vp]
     L.mbpe_encoder_encode_batch_endmask.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, u64, i32, vp, vp, vp,
                                                     vp, vp]
+    L.mbpe_encoder_encode_batch_endmask_windows.argtypes = L.mbpe_encoder_encode_batch_endmask.argtypes + [vp]
     L.mbpe_tok_set_encode_split.argtypes = [vp, i32]
     L.mbpe_tok_set_split_unicode.argtypes = [vp, i32]
     L.mbpe_tok_set_train_dedup.argtypes = [vp, i32]
@@ -532,6 +547,70 @@ def pack_tokens_aux(tokens, doc_tok_off, seq_len, layout="padded", out_bits=32, 
     return call.result(ids, lengths, arrays, off)
 
 
+class _WinCall(_AuxCall):
+    """What the *_windows calls share: the mbpe_pack_aux and the mbpe_pack_window of a call, the query for the row
+    count, and the dict it returns."""
+
+    def __init__(self, spec, stride, score_once, labels, positions, segments, ignore_label, row_doc, row_tok0):
+        super().__init__(spec, labels, positions, segments, False, ignore_label)
+        self.stride, self.once, self.want_rows = int(stride), int(bool(score_once)), (row_doc, row_tok0)
+
+    def window(self, row_doc_ptr=None, row_tok0_ptr=None):
+        return PackWindow(self.stride, self.once, row_doc_ptr or None, row_tok0_ptr or None)
+
+    def run(self, fn, head, tail, out_ptr, len_ptr, cap_rows, ptrs):
+        """fn(*head, ids, cap_rows, on_device, len, *tail(n_rows), aux, ..., win): with out_ptr= into device memory ->
+        the row count; else a query, host arrays of that size and the call -> the dict."""
+        n_rows = ctypes.c_uint64()
+        if out_ptr is not None:
+            aux, win = self.device(*ptrs[:3]), self.window(*ptrs[3:])
+            _check(fn(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail(n_rows, aux, win)))
+            return n_rows.value
+        aux, win = self.device(None, None, None), self.window()
+        _check(fn(*head, None, 0, 0, None, *tail(n_rows, aux, win)))
+        n = n_rows.value
+        ids, lengths = _matrix(n, self.spec)
+        aux, arrays = self.host(n)
+        if self.want_rows[0]:
+            arrays["row_doc"] = np.zeros(n, dtype=np.uint32)
+        if self.want_rows[1]:
+            arrays["row_tok0"] = np.zeros(n, dtype=np.uint64)
+        ptr = lambda name: arrays[name].ctypes.data if name in arrays and n else None
+        win = self.window(ptr("row_doc"), ptr("row_tok0"))
+        if n:
+            _check(fn(*head, ids.ctypes.data, n, 0, lengths.ctypes.data, *tail(n_rows, aux, win)))
+        return self.result(ids, lengths, arrays, None)
+
+
+def pack_windows(tokens, doc_tok_off, seq_len, stride, score_once=False, out_bits=32, pad_id=0, bos_id=None, eos_id=None,
+                 device=0, tokens_ptr=None, n_tokens=None, token_bits=None, out_ptr=None, len_ptr=None, cap_rows=None,
+                 labels=False, positions=False, segments=False, ignore_label=-100, labels_ptr=None, pos_ptr=None,
+                 seg_ptr=None, row_doc=False, row_tok0=False, row_doc_ptr=None, row_tok0_ptr=None):
+    """mbpe_pack_windows: one document per row like pack_tokens_aux(layout="padded"), but a document longer than
+    keep = seq_len - (bos) - (eos) tokens becomes several rows of its own, consecutive ones sharing `stride` tokens
+    (window i holds tokens [i * (keep - stride), i * (keep - stride) + keep); bos in every row, eos in the last).
+    Labels also cross the row end inside a document; score_once=True sets the labels of the shared cells of every
+    later window to ignore_label, so that each target is scored once.  -> the dict of pack_tokens_aux plus "row_doc"
+    (uint32: the row's document) and "row_tok0" (uint64: the index in the document of the row's first token) when
+    asked for.  With out_ptr= the outputs go to device memory (row_doc_ptr= / row_tok0_ptr= beside the pointers of
+    pack_tokens_aux) and the row count is returned."""
+    spec = pack_spec(seq_len, "padded", out_bits, pad_id, bos_id, eos_id)
+    call = _WinCall(spec, stride, score_once, labels, positions, segments, ignore_label, row_doc, row_tok0)
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    if tokens_ptr is None:
+        t = np.ascontiguousarray(tokens)
+        if t.dtype not in (np.dtype(np.uint16), np.dtype(np.uint32)):
+            t = t.astype(np.uint32)
+        t = t.reshape(-1)
+        tp, n_tokens, token_bits, on_dev = (t.ctypes.data if len(t) else None), len(t), t.dtype.itemsize * 8, 0
+    else:
+        tp, on_dev = _ptr(tokens_ptr), 1
+    head = (device, tp, n_tokens, token_bits, on_dev, off.ctypes.data, len(off) - 1, ctypes.byref(spec))
+    tail = lambda n_rows, aux, win: (ctypes.byref(n_rows), ctypes.byref(aux), ctypes.byref(win))
+    return call.run(lib().mbpe_pack_windows, head, tail, out_ptr, len_ptr, cap_rows,
+                    (labels_ptr, pos_ptr, seg_ptr, row_doc_ptr, row_tok0_ptr))
+
+
 def unpack_tokens(ids, lengths, dtype=np.uint32, device=0, ids_ptr=None, len_ptr=None, shape=None, id_bits=None,
                   out_ptr=None, cap=0):
     """mbpe_unpack_tokens: a right-padded matrix ids [n_rows, seq_len] (uint16 / uint32 / uint64) and its lengths ->
@@ -773,6 +852,49 @@ class Encoder:
                                                    doc_tok_off.ctypes.data))
         self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
         return call.result(ids, lengths, arrays, doc_tok_off)
+
+    def encode_batch_windows(self, texts_or_buffer, chunk_off=None, doc_chunk_off=None, *, seq_len, stride,
+                             score_once=False, out_bits=32, pad_id=0, bos_id=None, eos_id=None, text_ptr=None,
+                             n_bytes=None, out_ptr=None, len_ptr=None, cap_rows=None, labels=False, positions=False,
+                             segments=False, ignore_label=-100, labels_ptr=None, pos_ptr=None, seg_ptr=None,
+                             row_doc=False, row_tok0=False, row_doc_ptr=None, row_tok0_ptr=None):
+        """encode_batch_aux for the window layout (mbpe_encoder_encode_batch_windows): the documents of encode_batch,
+        the keywords and the result of pack_windows.  The row count depends on the tokens: the host form asks for it
+        first, which runs the passes.  The documents' token offsets of the call: self.doc_tok_off."""
+        spec = pack_spec(seq_len, "padded", out_bits, pad_id, bos_id, eos_id)
+        call = _WinCall(spec, stride, score_once, labels, positions, segments, ignore_label, row_doc, row_tok0)
+        head, keep = self._batch_head(texts_or_buffer, chunk_off, doc_chunk_off, text_ptr, n_bytes, spec)
+        n_tok = ctypes.c_uint64()
+        doc_tok_off = np.zeros(len(keep[-1]), dtype=np.uint64)
+        tail = lambda n_rows, aux, win: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
+                                         doc_tok_off.ctypes.data, ctypes.byref(win))
+        out = call.run(lib().mbpe_encoder_encode_batch_windows, head, tail, out_ptr, len_ptr, cap_rows,
+                       (labels_ptr, pos_ptr, seg_ptr, row_doc_ptr, row_tok0_ptr))
+        self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
+        return out
+
+    def encode_batch_endmask_windows(self, text_ptr, n_bytes, mask_ptr, singles, doc_off, *, seq_len, stride,
+                                     score_once=False, out_bits=32, pad_id=0, bos_id=None, eos_id=None, out_ptr=None,
+                                     len_ptr=None, cap_rows=None, labels=False, positions=False, segments=False,
+                                     ignore_label=-100, labels_ptr=None, pos_ptr=None, seg_ptr=None, row_doc=False,
+                                     row_tok0=False, row_doc_ptr=None, row_tok0_ptr=None):
+        """encode_batch_endmask for the window layout (mbpe_encoder_encode_batch_endmask_windows): its text, mask,
+        singles and documents, the keywords and the result of pack_windows.  The documents' token offsets:
+        self.doc_tok_off."""
+        spec = pack_spec(seq_len, "padded", out_bits, pad_id, bos_id, eos_id)
+        call = _WinCall(spec, stride, score_once, labels, positions, segments, ignore_label, row_doc, row_tok0)
+        sg = _singles(singles)
+        docs = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        n_tok = ctypes.c_uint64()
+        doc_tok_off = np.zeros(len(docs), dtype=np.uint64)
+        head = (self._h, _ptr(text_ptr), n_bytes, _ptr(mask_ptr), sg.ctypes.data if len(sg) else None, len(sg),
+                docs.ctypes.data, len(docs) - 1, ctypes.byref(spec))
+        tail = lambda n_rows, aux, win: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
+                                         doc_tok_off.ctypes.data, ctypes.byref(win))
+        out = call.run(lib().mbpe_encoder_encode_batch_endmask_windows, head, tail, out_ptr, len_ptr, cap_rows,
+                       (labels_ptr, pos_ptr, seg_ptr, row_doc_ptr, row_tok0_ptr))
+        self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
+        return out
 
     def encode_endmask(self, text_ptr, n_bytes, mask_ptr, singles=None, doc_off=None, dtype=np.uint32, out_ptr=None,
                        cap=None, query=False, byte_off=False, byte_off_ptr=None):
@@ -1893,6 +2015,34 @@ class Tokenizer:
                   *tail, ctypes.byref(aux), doc_tok_off.ctypes.data))
         self.doc_tok_off = doc_tok_off
         return call.result(ids, lengths, arrays, doc_tok_off)
+
+    def encode_batch_windows(self, texts, seq_len, stride, score_once=False, out_bits=32, pad_id=0, bos_id=None,
+                             eos_id=None, device=0, out_ptr=None, len_ptr=None, cap_rows=None, labels=False,
+                             positions=False, segments=False, ignore_label=-100, labels_ptr=None, pos_ptr=None,
+                             seg_ptr=None, row_doc=False, row_tok0=False, row_doc_ptr=None, row_tok0_ptr=None,
+                             device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False):
+        """encode_batch_aux for the window layout (mbpe_tok_encode_batch_windows_device): every text split like
+        encode(), encoded, and cut into rows of seq_len that share `stride` tokens where a text does not fit one --
+        the keywords and the result of pack_windows ("row_doc" maps a row back to its text).  The texts' token
+        offsets of the call: self.doc_tok_off."""
+        self._encode_split(device_split, order, dropout, seed, dedup)
+        spec = pack_spec(seq_len, "padded", out_bits, pad_id, bos_id, eos_id)
+        call = _WinCall(spec, stride, score_once, labels, positions, segments, ignore_label, row_doc, row_tok0)
+        parts = [bytes(_u8(t)) for t in texts]
+        doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        if parts:
+            doc_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
+        text = np.frombuffer(b"".join(parts), dtype=np.uint8)
+        n_tok = ctypes.c_uint64()
+        doc_tok_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        head = (self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data, len(parts), 0, device,
+                ctypes.byref(spec))
+        tail = lambda n_rows, aux, win: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
+                                         doc_tok_off.ctypes.data, ctypes.byref(win))
+        out = call.run(lib().mbpe_tok_encode_batch_windows_device, head, tail, out_ptr, len_ptr, cap_rows,
+                       (labels_ptr, pos_ptr, seg_ptr, row_doc_ptr, row_tok0_ptr))
+        self.doc_tok_off = doc_tok_off
+        return out
 
     def decode_padded(self, ids, lengths, device=0):
         """A right-padded id matrix [n_rows, seq_len] and its lengths -> the list of the rows' texts, unpacked and
