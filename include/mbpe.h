@@ -1362,6 +1362,62 @@ MBPE_API int  mbpe_wordcount_merge_blob(mbpe_wordcount *w, const uint8_t *blob, 
                                         uint64_t *n_unique_total_out, uint64_t *n_unique_bytes_total_out);
 MBPE_API int  mbpe_wordcount_merge(mbpe_wordcount *w, const mbpe_wordcount *other);
 
+/* ---- token frequency tables (csrc/hist.hip, hist.h) -----------------------------------------------------------------
+ * How often every token id is used, counted on the device in 64 bits, exact: no floating point and no 32-bit
+ * intermediate that can wrap (a workgroup's private 32-bit counters are flushed before 2^32 adds; hist.h).  With T the
+ * tokens the corresponding encode call would return for the same arguments and encoder state (order, dropout and
+ * seed, "dedup", pieces, NUL-led chunks, singles):
+ *     counts[id] += repeat * |{ j : T[j] == id }|   for id < n_ids
+ *     n_other    += repeat * |{ j : T[j] >= n_ids }|
+ *     n_tokens   += repeat * |T|
+ * so sum(counts) + n_other == n_tokens always.  A call that returns an error leaves the table exactly as it was.
+ *
+ * mbpe_token_counts: tokens that exist already.  The conventions of mbpe_pack_tokens: token_bits 32 (bit 31 is cleared
+ * on read) or 16 (plain ids, 65,535 is one), host or device (tokens_on_device; a device pointer aligned to its
+ * elements).  WRITES counts_out[0 .. n_ids) (host, or device with out_on_device: 8-byte aligned) and *n_other_out
+ * (required, host).  n_ids must lie in 1 .. MBPE_MAX_COUNT_IDS; that, an unknown token_bits, more than 2^40 tokens
+ * and a misaligned device pointer are MBPE_ERR_ARG before the device is touched.  n_tokens == 0 gives zeros.
+ * mbpe_token_counts_kernel_ms: the device time of the calling thread's latest such call (the histogram kernel alone).
+ *
+ * mbpe_encoder_count, mbpe_encoder_count_endmask: mbpe_encoder_encode and mbpe_encoder_encode_endmask called as a
+ * query (tokens_out NULL), plus the count; no token leaves the device.  Argument checks, error codes, pieces (the
+ * passes run once), the NUL rule, singles, "rank_order" and dropout hold as they do there.  With "dedup" 1 they take
+ * that route WITHOUT the expansion: the count of the whole text is the count of the table of token runs, every run
+ * weighted by how many chunks copy it, and those weights are the histogram of the patched unique_of map (which
+ * handles one-token chunks and the empty run by construction).  Dropout > 0 with "dedup" stays MBPE_ERR_ARG.
+ *   repeat            at least 1 (0: MBPE_ERR_ARG): the text counts that many times, as for mbpe_wordcount_add
+ *   n_tokens_out      required: |T|, without repeat
+ * Overflow is decided on the host before the device is touched: with S the weighted token total the table has
+ * reached, S + n_bytes * repeat >= 2^64 is MBPE_ERR_OVERFLOW.  Encoding never makes more tokens than bytes and every
+ * bin is at most the total, so no bin can wrap.
+ * The table has n_ids = max(256 + n_merges, option "count_ids") entries; ids at or beyond it (one-token chunks only)
+ * are counted in n_other.  "count_ids" is 0 (the default) .. MBPE_MAX_COUNT_IDS (else MBPE_ERR_ARG) and MBPE_ERR_STATE
+ * once something has been counted and not reset; 256 + n_merges above MBPE_MAX_COUNT_IDS is MBPE_ERR_VOCAB from the
+ * first count call.  Every call counts into a scratch table of the call's own and folds it into the kept one
+ * (kept[i] += repeat * call[i]) after everything that can fail has succeeded.  The table and its scratch (16 bytes
+ * per id; on the "dedup" route 8 bytes per table run in addition) are allocated by the first count call: an encoder
+ * that is never asked to count launches and allocates exactly what it did before, and mbpe_encoder_alloc_count of
+ * the other calls is unchanged.  A repeat count call of no larger size allocates nothing.  mbpe_encoder_kernel_ms
+ * includes the histogram and the fold.
+ *   mbpe_encoder_counts        copies the table: counts_out (cap_ids entries, host or device; fewer than n_ids is
+ *                              MBPE_ERR_ARG; NULL: query), and n_ids, n_other and the weighted token total (each
+ *                              pointer may be NULL)
+ *   mbpe_encoder_counts_reset  zeroes the table and the totals; "count_ids" may change again */
+#define MBPE_MAX_COUNT_IDS 33554432u   /* 2^25 */
+MBPE_API int  mbpe_token_counts(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits,
+                                int tokens_on_device, uint64_t *counts_out, uint64_t n_ids, int out_on_device,
+                                uint64_t *n_other_out);
+MBPE_API int  mbpe_token_counts_kernel_ms(float *ms_out);
+MBPE_API int  mbpe_encoder_count(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                 const uint64_t *chunk_off, uint64_t n_chunks, uint64_t repeat, uint64_t *n_tokens_out,
+                                 uint32_t *n_passes_out);
+MBPE_API int  mbpe_encoder_count_endmask(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
+                                         const uint8_t *endmask_dev, const mbpe_single *singles, uint64_t n_singles,
+                                         uint64_t repeat, uint64_t *n_tokens_out, uint32_t *n_passes_out);
+MBPE_API int  mbpe_encoder_counts(mbpe_encoder *e, uint64_t *counts_out, uint64_t cap_ids, int out_on_device,
+                                  uint64_t *n_ids_out, uint64_t *n_other_out, uint64_t *n_tokens_out);
+MBPE_API int  mbpe_encoder_counts_reset(mbpe_encoder *e);
+
 #ifdef __cplusplus
 }
 #endif

@@ -260,6 +260,29 @@ MBPE_API int mbpe_tok_set_train_limits(mbpe_tokenizer *t, int64_t min_frequency,
  * so equal chunks do not share tokens, and the route is never switched silently. */
 MBPE_API int mbpe_tok_set_encode_dedup(mbpe_tokenizer *t, int on);
 
+/* Token frequency tables: how often every token id is used on a corpus, without a token leaving the device.
+ * mbpe_tok_count_tokens splits the documents as mbpe_tok_encode_batch_device does (special tokens first, each document on
+ * its own) and adds what mbpe_tok_encode would return for each, `repeat` times (at least 1: 0 is MBPE_ERR_ARG), to a
+ * table the tokenizer keeps on the host.
+ *   device_id < 0    the host loop: mbpe_tok_encode of every document, counted
+ *   device_id >= 0   the kept encoder through mbpe_encoder_count over the host split or -- after
+ *                    mbpe_tok_set_encode_split(1) -- the kept splitter and mbpe_encoder_count_endmask.
+ *                    mbpe_tok_set_encode_order, _dropout, _dedup and _split_unicode hold as for the batch encode calls
+ *   n_tokens_out     required: the tokens of this call's documents, without repeat
+ * After each device call the encoder's table is read back, added to the host's and zeroed, so an encoder that is
+ * re-created (another device) loses nothing.  The table has n_ids = max(256 + n_merges, largest special id + 1)
+ * entries; a special id (or 256 + n_merges) at or above MBPE_MAX_COUNT_IDS is MBPE_ERR_VOCAB before any work, and
+ * MBPE_ERR_OVERFLOW comes before the weighted total could reach 2^64.  A call that fails adds nothing.  Changing the
+ * merges (train, load, set_merges) or the special tokens empties the table.
+ *   mbpe_tok_token_counts        counts_out (cap_ids entries; fewer than n_ids is MBPE_ERR_ARG; NULL: query), n_ids and
+ *                                the weighted token total (each pointer may be NULL)
+ *   mbpe_tok_token_counts_reset  empties the table */
+MBPE_API int mbpe_tok_count_tokens(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off, uint64_t n_docs,
+                                   int verbose, int device_id, uint64_t repeat, uint64_t *n_tokens_out);
+MBPE_API int mbpe_tok_token_counts(mbpe_tokenizer *t, uint64_t *counts_out, uint64_t cap_ids, uint64_t *n_ids_out,
+                                   uint64_t *n_tokens_out);
+MBPE_API int mbpe_tok_token_counts_reset(mbpe_tokenizer *t);
+
 /* decode, Tokenizer.h:725-751.  bytes_out may be NULL to query the length. */
 MBPE_API int mbpe_tok_decode(mbpe_tokenizer *t, const uint32_t *tokens, uint64_t n, int verbose,
                              uint8_t *bytes_out, uint64_t cap, uint64_t *n_out);

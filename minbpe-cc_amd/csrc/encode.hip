@@ -43,10 +43,17 @@
 // through the encoder's own deduper (dedup.h, with the inverse map), the passes above run over the unique text as one
 // piece, the finishing kernel writes a table of token runs in the caller's format, and the expansion (expand.h) copies
 // every chunk's run to its place -- see enc_dedup_body.  With the option off none of this exists either.
+//
+// The count calls (mbpe_encoder_count, _count_endmask; hist.h): the encode calls as a query, plus a histogram of every
+// piece's final stream into a scratch table of the call's own, which is folded into the kept table once nothing can
+// fail any more.  On the "dedup" route the expansion is left out: the runs' weights are the histogram of the patched
+// unique_of map, and the table of token runs is counted with them -- see dedup_count.  An encoder that is never asked
+// to count has none of these buffers.
 #include "dedup.h"
 #include "dropout.h"
 #include "expand.h"
 #include "hip_host.h"
+#include "hist.h"
 #include "pack.h"
 #include "rank.h"
 #include "span.h"
@@ -540,6 +547,13 @@ struct mbpe_encoder : DevQueue {
     bool dd_ran = false;                      // the latest call went through the deduper (mbpe_encoder_dedup_stats)
     uint64_t dd_chunks = 0, dd_unique = 0, dd_unique_bytes = 0, dd_unique_tokens = 0;
     float dd_expand_ms = 0.f;
+    // the count calls (nothing of this exists before the first one): the kept table, cnt_ids bins and `other` behind
+    // them; the call's scratch table, with the call's token total behind `other` ("dedup" route); the runs' weights
+    uint64_t count_ids = 0;                   // option "count_ids"
+    uint64_t cnt_ids = 0;                     // bins of the table as it is allocated; 0: not yet
+    uint64_t cnt_tokens = 0;                  // the weighted token total the table has reached
+    bool cnt_used = false;                    // something has been counted and not reset
+    DevBuf<unsigned long long> d_cnt, d_cnt_call, d_cnt_w;
 };
 
 namespace {
@@ -652,6 +666,8 @@ struct EncCall {
     uint64_t *doc_tok_off_out;
     // the _byteoff calls: cap + 1 byte offsets, where tokens_out lives (NULL: none are computed)
     uint64_t *tok_byte_off_out;
+    // the count calls: every piece's final stream is counted into e->d_cnt_call (tokens_out is NULL)
+    bool count;
 };
 
 // where a call's ids go and in what width, and where it reports how many they are
@@ -941,6 +957,8 @@ int piece_finish(mbpe_encoder *e, const EncCall &a, Piece p, uint64_t done, Piec
         hipLaunchKernelGGL(k_enc_len_write, grid, dim3(kSpanThreads), 0, e->stream, tok, n, tab, pt, e->span_bytes,
                            a.chunk_off[p.c0], boff);
     }
+    if (a.count && n)
+        hist_tokens_launch(e->stream, tok, n, 32, e->d_cnt_call, e->cnt_ids, e->d_cnt_call + e->cnt_ids);
     ECHK(hipEventRecord(e->ev1, e->stream));
     unsigned long long ends_found = 0;
     if (with_ends && !a.endmask && n) ECHK(hipMemcpyAsync(&ends_found, e->d_res, 8, hipMemcpyDeviceToHost, e->stream));
@@ -1233,7 +1251,7 @@ int dedup_queries(mbpe_encoder *e, const EncCall &a, DedupRun *d) {
         }
         if (k != n_sg) return fail(MBPE_ERR_HIP, d->who + ": a one-token chunk is not among the chunks");
     }
-    if ((rc = e->d_exp_off.reserve((expand_span_count(d->n_kept) + 1) * 8, e->mem)) != MBPE_OK) return rc;
+    if (!a.count && (rc = e->d_exp_off.reserve((expand_span_count(d->n_kept) + 1) * 8, e->mem)) != MBPE_OK) return rc;
     if (n_q) {
         if ((rc = e->d_q_pos.reserve(n_q * 8, e->mem)) != MBPE_OK) return rc;
         if ((rc = e->d_q_chunk.reserve(n_q * 8, e->mem)) != MBPE_OK) return rc;
@@ -1311,6 +1329,38 @@ int dedup_expand(mbpe_encoder *e, const EncCall &a, const DedupRun &d) {
     return MBPE_OK;
 }
 
+// stage 4 of a count call, in place of the expansion: the singles become runs of the table as there, the runs' weights
+// are the histogram of the patched map (w[j] = the chunks that copy run j; the one-token chunks and the empty run
+// included, by construction), and the table is counted with them into the call's scratch
+int dedup_count(mbpe_encoder *e, const EncCall &a, const DedupRun &d) {
+    const uint64_t n = d.r.n, n_sg = d.n_sg, n_ent = d.n_entries(), n_ids = e->cnt_ids;
+    int rc = MBPE_OK;
+    if (n_ent >> 31) return fail(MBPE_ERR_ARG, d.who + ": 2^31 table runs or more (option \"dedup\")");
+    if ((rc = e->d_cnt_w.reserve((n_ent + 1) * 8, e->mem)) != MBPE_OK) return rc;
+    ECHK(hipMemsetAsync(e->d_cnt_w, 0, (n_ent + 1) * 8, e->stream));
+    expand_patch_launch(e->stream, e->d_utab.get(), n, a.token_bits, e->d_uends, d.nu, d.uof, d.n_kept,
+                        ExpandSingles{e->d_sg_tok, d.q_chunk, d.q_chunk + n_sg, n_sg});
+    hist_tokens_launch(e->stream, d.uof, d.n_kept, 32, e->d_cnt_w, n_ent, e->d_cnt_w + n_ent);
+    unsigned long long *call = e->d_cnt_call;
+    hist_runs_launch(e->stream, e->d_utab.get(), n + n_sg, a.token_bits, e->d_uends, n_ent, e->d_cnt_w, call, n_ids,
+                     call + n_ids, call + n_ids + 1);
+    ECHK(hipEventRecord(e->ev1, e->stream));
+    unsigned long long total = 0;
+    ECHK(hipMemcpyAsync(&total, call + n_ids + 1, 8, hipMemcpyDeviceToHost, e->stream));
+    float ms = 0.f;
+    if ((rc = e->wait(&ms)) != MBPE_OK) return rc;
+    e->dd_ran = true;
+    e->dd_chunks = d.n_kept;
+    e->dd_unique = d.nu;
+    e->dd_unique_bytes = d.nub;
+    e->dd_unique_tokens = n;
+    e->dd_expand_ms = 0.f;
+    e->last_ms += ms;
+    *a.n_out = total;
+    if (a.n_passes_out) *a.n_passes_out = d.r.passes;
+    return MBPE_OK;
+}
+
 // a.endmask: the endmask calls (text, mask, singles, doc_off as they state them); else chunk_off, checked, n_bytes > 0
 int enc_dedup_body(mbpe_encoder *e, EncCall a) {
     DedupRun d;
@@ -1330,7 +1380,24 @@ int enc_dedup_body(mbpe_encoder *e, EncCall a) {
     if ((rc = dedup_unique(e, a, &d)) != MBPE_OK) return rc;
     if ((rc = dedup_table(e, a, &d)) != MBPE_OK) return rc;
     if ((rc = dedup_queries(e, a, &d)) != MBPE_OK) return rc;
-    return dedup_expand(e, a, d);
+    return a.count ? dedup_count(e, a, d) : dedup_expand(e, a, d);
+}
+
+// what a count call settles before its pieces run: the kept table (allocated and zeroed by the first count call, and
+// again when "count_ids" has changed, which only an empty table allows) and the call's zeroed scratch
+int count_begin(mbpe_encoder *e, const EncCall &a) {
+    if (!a.count) return MBPE_OK;
+    const uint64_t want = std::max<uint64_t>(256ull + e->n_merges, e->count_ids);
+    if (want != e->cnt_ids) {
+        e->cnt_ids = 0;
+        int rc = e->d_cnt.reserve((want + 1) * 8, e->mem);
+        if (rc == MBPE_OK) rc = e->d_cnt_call.reserve((want + 2) * 8, e->mem);
+        if (rc != MBPE_OK) return rc;
+        ECHK(hipMemsetAsync(e->d_cnt, 0, (want + 1) * 8, e->stream));
+        e->cnt_ids = want;
+    }
+    ECHK(hipMemsetAsync(e->d_cnt_call, 0, (e->cnt_ids + 2) * 8, e->stream));
+    return MBPE_OK;
 }
 
 int enc_run_body(mbpe_encoder *e, EncCall a) {
@@ -1349,6 +1416,7 @@ int enc_run_body(mbpe_encoder *e, EncCall a) {
     }
     ECHK(hipSetDevice(e->device));
     if (int rc0 = boff_begin(e, a)) return rc0;
+    if (int rc0 = count_begin(e, a)) return rc0;
     e->last_ms = 0.f;
     e->pass_tokens.clear();
     if (e->dedup) return enc_dedup_body(e, a);
@@ -1541,6 +1609,7 @@ int enc_endmask_body(mbpe_encoder *e, EncCall a) {
         }
         return MBPE_OK;
     }
+    if (int rc0 = count_begin(e, a)) return rc0;
     if (e->dedup) return enc_dedup_body(e, a);
     uint64_t limit = 0;                                           // the rule of mbpe_encoder_encode
     int rc = piece_limit(e, n_bytes, a.tok_byte_off_out && !a.out_on_device, &limit);
@@ -1710,6 +1779,14 @@ int mbpe_encoder_set_option(mbpe_encoder *e, const char *name, int64_t value) {
     if (strcmp(name, "dedup_max_chunk_bytes") == 0) {
         if (value < 0 || value > 0x7FFFFFFF) return fail(MBPE_ERR_ARG, "dedup_max_chunk_bytes must lie in [0, 2^31)");
         e->dedup_max_chunk = value;
+        return MBPE_OK;
+    }
+    if (strcmp(name, "count_ids") == 0) {
+        if (value < 0 || value > (int64_t)MBPE_MAX_COUNT_IDS)
+            return fail(MBPE_ERR_ARG, "count_ids must lie in 0 .. MBPE_MAX_COUNT_IDS");
+        if (e->cnt_used)
+            return fail(MBPE_ERR_STATE, "count_ids: tokens have been counted (mbpe_encoder_counts_reset comes first)");
+        e->count_ids = (uint64_t)value;
         return MBPE_OK;
     }
     return fail(MBPE_ERR_ARG, std::string("mbpe_encoder_set_option: no option \"") + name + "\"");
@@ -1912,6 +1989,117 @@ int mbpe_encoder_encode_batch_endmask_windows(mbpe_encoder *e, const uint8_t *te
     return enc_batch_endmask("mbpe_encoder_encode_batch_endmask_windows", e, text_dev, n_bytes, endmask_dev, singles,
                              n_singles, doc_off, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out,
                              n_tokens_out, aux, doc_tok_off_out, win);
+}
+
+// ---- the count calls (hist.h) -----------------------------------------------------------------------------------------
+// what they check on the host beyond their encode counterparts: repeat, the table's size, and the total, without wrapping
+static int count_check(const mbpe_encoder *e, const std::string &who, uint64_t n_bytes, uint64_t repeat) {
+    if (repeat == 0) return fail(MBPE_ERR_ARG, who + ": repeat must be at least 1");
+    if (256ull + e->n_merges > MBPE_MAX_COUNT_IDS)
+        return fail(MBPE_ERR_VOCAB, who + ": more than MBPE_MAX_COUNT_IDS token ids");
+    // S + n_bytes * repeat < 2^64  <=>  n_bytes <= (2^64 - 1 - S) / repeat
+    if (n_bytes > (~0ull - e->cnt_tokens) / repeat)
+        return fail(MBPE_ERR_OVERFLOW, who + ": the weighted token total could reach 2^64");
+    return MBPE_OK;
+}
+
+// the call's scratch into the kept table, `other` included; nothing can fail before it that has not failed already
+static int count_fold(mbpe_encoder *e, uint64_t repeat, uint64_t n_tokens) {
+    ECHK(hipEventRecord(e->ev0, e->stream));
+    hist_fold_launch(e->stream, e->d_cnt, e->d_cnt_call, e->cnt_ids + 1, repeat);
+    float ms = 0.f;
+    const int rc = e->finish(&ms);
+    if (rc != MBPE_OK) return rc;
+    e->last_ms += ms;
+    e->cnt_tokens += repeat * n_tokens;
+    e->cnt_used = true;
+    return MBPE_OK;
+}
+
+int mbpe_encoder_count(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                       const uint64_t *chunk_off, uint64_t n_chunks, uint64_t repeat, uint64_t *n_tokens_out,
+                       uint32_t *n_passes_out) {
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (n_passes_out) *n_passes_out = 0;
+    if (!e || !n_tokens_out || (!text && n_bytes)) return fail(MBPE_ERR_ARG, "mbpe_encoder_count: NULL argument");
+    EncCall a = {text, n_bytes, text_on_device, chunk_off, n_chunks};
+    enc_out(&a, nullptr, 0, 32, 0, n_tokens_out, n_passes_out);
+    a.count = true;
+    int rc = drop_check(e, "mbpe_encoder_count");
+    if (rc == MBPE_OK) rc = dedup_check(e, "mbpe_encoder_count", nullptr);
+    if (rc == MBPE_OK) rc = count_check(e, "mbpe_encoder_count", n_bytes, repeat);
+    if (rc != MBPE_OK) return rc;
+    return enc_guard("mbpe_encoder_count", [&] {
+        const int rc = enc_run_body(e, a);
+        return rc != MBPE_OK || n_bytes == 0 ? rc : count_fold(e, repeat, *n_tokens_out);
+    });
+}
+
+int mbpe_encoder_count_endmask(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes, const uint8_t *endmask_dev,
+                               const mbpe_single *singles, uint64_t n_singles, uint64_t repeat, uint64_t *n_tokens_out,
+                               uint32_t *n_passes_out) {
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (n_passes_out) *n_passes_out = 0;
+    int rc = enc_endmask_check("mbpe_encoder_count_endmask", n_bytes, singles, n_singles, nullptr, 0, 32);
+    if (rc != MBPE_OK) return rc;
+    if (!e || !n_tokens_out || ((!text_dev || !endmask_dev) && n_bytes))
+        return fail(MBPE_ERR_ARG, "mbpe_encoder_count_endmask: NULL argument");
+    if ((rc = drop_check(e, "mbpe_encoder_count_endmask")) != MBPE_OK) return rc;
+    if ((rc = dedup_check(e, "mbpe_encoder_count_endmask", nullptr)) != MBPE_OK) return rc;
+    if ((uintptr_t)endmask_dev & 3) return fail(MBPE_ERR_ARG, "mbpe_encoder_count_endmask: the mask must be 4-byte aligned");
+    if ((rc = count_check(e, "mbpe_encoder_count_endmask", n_bytes, repeat)) != MBPE_OK) return rc;
+    EncCall a = endmask_call(text_dev, n_bytes, endmask_dev, singles, n_singles, nullptr, 0);
+    enc_out(&a, nullptr, 0, 32, 0, n_tokens_out, n_passes_out);
+    a.count = true;
+    return enc_guard("mbpe_encoder_count_endmask", [&] {
+        const int rc = enc_endmask_body(e, a);
+        return rc != MBPE_OK || n_bytes == 0 ? rc : count_fold(e, repeat, *n_tokens_out);
+    });
+}
+
+int mbpe_encoder_counts(mbpe_encoder *e, uint64_t *counts_out, uint64_t cap_ids, int out_on_device, uint64_t *n_ids_out,
+                        uint64_t *n_other_out, uint64_t *n_tokens_out) {
+    if (!e) return fail(MBPE_ERR_ARG, "mbpe_encoder_counts: NULL argument");
+    // (before the first count call, and after "count_ids" has changed, the table is what the next count call will
+    // allocate: all zeros)
+    const uint64_t n_ids = std::max<uint64_t>(256ull + e->n_merges, e->count_ids);
+    const bool live = e->cnt_ids == n_ids;
+    if (n_ids_out) *n_ids_out = n_ids;
+    if (n_tokens_out) *n_tokens_out = e->cnt_tokens;
+    if (n_other_out) *n_other_out = 0;
+    if (counts_out && cap_ids < n_ids) return fail(MBPE_ERR_ARG, "counts_out too small");
+    if (counts_out && out_on_device && ((uintptr_t)counts_out & 7))
+        return fail(MBPE_ERR_ARG, "mbpe_encoder_counts: counts_out in device memory must be 8-byte aligned");
+    if (!live && !(counts_out && out_on_device)) {
+        if (counts_out) std::fill(counts_out, counts_out + n_ids, 0);
+        return MBPE_OK;
+    }
+    ECHK(hipSetDevice(e->device));
+    if (!live) {
+        ECHK(hipMemsetAsync(counts_out, 0, n_ids * 8, e->stream));
+        ECHK(hipStreamSynchronize(e->stream));
+        return MBPE_OK;
+    }
+    unsigned long long other = 0;
+    if (counts_out)
+        ECHK(hipMemcpyAsync(counts_out, e->d_cnt, n_ids * 8, out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                            e->stream));
+    if (n_other_out) ECHK(hipMemcpyAsync(&other, e->d_cnt + n_ids, 8, hipMemcpyDeviceToHost, e->stream));
+    ECHK(hipStreamSynchronize(e->stream));
+    if (n_other_out) *n_other_out = other;
+    return MBPE_OK;
+}
+
+int mbpe_encoder_counts_reset(mbpe_encoder *e) {
+    if (!e) return fail(MBPE_ERR_ARG, "mbpe_encoder_counts_reset: NULL argument");
+    if (e->cnt_ids) {
+        ECHK(hipSetDevice(e->device));
+        ECHK(hipMemsetAsync(e->d_cnt, 0, (e->cnt_ids + 1) * 8, e->stream));
+        ECHK(hipStreamSynchronize(e->stream));
+    }
+    e->cnt_tokens = 0;
+    e->cnt_used = false;
+    return MBPE_OK;
 }
 
 int mbpe_encoder_pack_ms(const mbpe_encoder *e, float *ms_out) {

@@ -1,7 +1,8 @@
 // minbpe-cc: the reference's command line (code/examples/minbpe-cc.cpp:92-265)
 // on top of the MI355X training path.  Same flags, defaults, messages and exit
 // codes; `--train -c lexical` runs on the GPU.  The only additions are --device, the --device-* switches, --rank-order,
-// --dropout / --seed, --byte-ranges-out, --continue-from, --input-list, and --count / --counts / --counts-out.
+// --dropout / --seed, --byte-ranges-out, --continue-from, --input-list, --count / --counts / --counts-out, and
+// --token-counts-out.
 #include "mbpe.h"
 #include "mbpe_tokenizer.h"
 
@@ -123,6 +124,14 @@ void usage() {
                  "                              a counting run.  The counts must come from the same --encoder; a missing or\n"
                  "                              malformed file is an error.  Excludes --input.  The training itself runs on one\n"
                  "                              HIP device\n"
+                 "  --token-counts-out TEXT     With --encode, instead of --output: count how often every token id is used and\n"
+                 "                              write one line \"id count\" per id, ascending from 0, zero counts included; no\n"
+                 "                              token file is written, and with --device-encode no token leaves the device.\n"
+                 "                              Takes --input, or --input-list (one path per line, optionally a tab and a\n"
+                 "                              repeat count: the file is counted that many times).  --device-encode,\n"
+                 "                              --device-split, --device-split-unicode, --rank-order, --dedup, --dropout and\n"
+                 "                              --seed mean what they mean for --encode; without --device-encode the host loop\n"
+                 "                              counts.  With --output, or without --encode, it is an error\n"
                  "  --min-frequency INT         With --train: the training ends when the best pair left occurs less often than\n"
                  "                              this (0, the default: no such rule), with fewer merges than --vocab-size asks for\n"
                  "  --max-token-length INT      With --train: no new token is longer than this many bytes (0, the default: no\n"
@@ -137,7 +146,7 @@ void usage() {
 
 int main(int argc, char *argv[]) {
     std::string input_path, input_list_path, output_path, special_token_path, encoder = "gpt4", model_path = "./output.model",
-                continue_from, byte_ranges_path, counts_out_path;
+                continue_from, byte_ranges_path, counts_out_path, token_counts_path;
     std::vector<std::string> counts_paths;
     std::string conflict_resolution_str = "first";
     bool train = false, decode = false, encode = false, write_vocab = false, verbose = false, device_encode = false,
@@ -173,6 +182,7 @@ int main(int argc, char *argv[]) {
         else if (arg == "--continue-from") { if (!value(&continue_from)) return 106; }
         else if (arg == "--byte-ranges-out") { if (!value(&byte_ranges_path)) return 106; }
         else if (arg == "--counts-out") { if (!value(&counts_out_path)) return 106; }
+        else if (arg == "--token-counts-out") { if (!value(&token_counts_path)) return 106; }
         else if (arg == "--counts") { if (!value(&tmp)) return 106; counts_paths.push_back(tmp); }
         else if (arg == "--vocab-size") {
             if (!value(&tmp)) return 106;
@@ -232,6 +242,9 @@ int main(int argc, char *argv[]) {
 
     if (have_limits && !train) { std::cerr << "--min-frequency and --max-token-length require --train\n"; return 107; }
 
+    if (!token_counts_path.empty() && (!encode || train || decode)) { std::cerr << "--token-counts-out requires --encode\n"; return 107; }
+    if (!token_counts_path.empty() && !output_path.empty()) { std::cerr << "--token-counts-out excludes --output\n"; return 107; }
+    if (!token_counts_path.empty() && !byte_ranges_path.empty()) { std::cerr << "--token-counts-out excludes --byte-ranges-out\n"; return 107; }
     if (count && (train || encode || decode)) { std::cerr << "--count excludes --train, --encode and --decode\n"; return 107; }
     if (count && counts_out_path.empty()) { std::cerr << "--count requires --counts-out\n"; return 107; }
     if (!counts_out_path.empty() && !count) { std::cerr << "--counts-out requires --count\n"; return 107; }
@@ -245,7 +258,10 @@ int main(int argc, char *argv[]) {
     std::vector<Piece> pieces;
     if (!input_list_path.empty()) {
         if (!input_path.empty()) { std::cerr << "--input-list excludes --input\n"; return 107; }
-        if (!train && !count) { std::cerr << "--input-list requires --train or --count\n"; return 107; }
+        if (!train && !count && token_counts_path.empty()) {
+            std::cerr << "--input-list requires --train, --count or --token-counts-out\n";
+            return 107;
+        }
         if (!exists(input_list_path)) { std::cerr << "Input file " << input_list_path << " does not exist\n"; return -1; }
         std::ifstream list(input_list_path);
         for (std::string line; std::getline(list, line);) {
@@ -422,6 +438,51 @@ int main(int argc, char *argv[]) {
             }
         }
         if (!ok) rc = -1;
+    } else if (encode && !token_counts_path.empty()) {
+        // the token frequency table of the input, or of the pieces of --input-list with their repeat counts
+        if (!exists(model_path)) { std::cerr << "Model file " << model_path << " does not exist\n"; mbpe_tok_destroy(rt); return -1; }
+        std::cout << "Counting tokens, encoder " << encoder << " model path " << model_path << " counts to "
+                  << token_counts_path << "\n";
+        mbpe_tok_load(rt, model_path.c_str(), verbose);
+        if (device_encode && device_split) mbpe_tok_set_encode_split(rt, 1);
+        if (rank_order) mbpe_tok_set_encode_order(rt, 1);
+        if (have_dropout) mbpe_tok_set_encode_dropout(rt, drop_threshold, seed);
+        if (split_unicode) mbpe_tok_set_split_unicode(rt, 1);
+        if (dedup && device_encode) mbpe_tok_set_encode_dedup(rt, 1);
+        if (pieces.empty()) pieces.push_back(Piece{input_path, 1});
+        uint64_t total = 0;
+        for (size_t k = 0; k < pieces.size() && rc == 0; ++k) {
+            std::string input, err;
+            if (verbose) std::cout << "Loading file " << pieces[k].path << "\n";
+            if (!load_file_to_string(pieces[k].path, &input, &err)) {
+                std::cerr << "Failed with error: " << err << "\n";
+                rc = -1;
+                break;
+            }
+            const uint64_t doc_off[2] = {0, input.size()};
+            uint64_t n = 0;
+            if (mbpe_tok_count_tokens(rt, reinterpret_cast<const uint8_t *>(input.data()), doc_off, 1, verbose,
+                                      device_encode ? device : -1, pieces[k].repeat, &n) != MBPE_OK) {
+                std::cerr << "Error: " << mbpe_last_error() << "\n";
+                rc = -1;
+            }
+            total += n * pieces[k].repeat;
+        }
+        if (rc == 0) {
+            uint64_t n_ids = 0;
+            mbpe_tok_token_counts(rt, nullptr, 0, &n_ids, nullptr);
+            std::vector<uint64_t> table(n_ids);
+            if (mbpe_tok_token_counts(rt, table.data(), n_ids, &n_ids, nullptr) != MBPE_OK) {
+                std::cerr << "Error: " << mbpe_last_error() << "\n";
+                rc = -1;
+            } else {
+                std::ofstream file(token_counts_path);
+                for (uint64_t i = 0; i < n_ids; ++i) file << i << ' ' << table[i] << '\n';
+                file.close();
+                if (!file) { std::cerr << "Failed to write " << token_counts_path << "\n"; rc = -1; }
+                else std::cout << "Counted " << total << " tokens, wrote " << n_ids << " ids\n";
+            }
+        }
     } else if (encode) {                                        // :212-242
         if (output_path.empty()) { std::cerr << "Output file not specified\n"; mbpe_tok_destroy(rt); return -1; }
         if (!exists(model_path)) { std::cerr << "Model file " << model_path << " does not exist\n"; mbpe_tok_destroy(rt); return -1; }

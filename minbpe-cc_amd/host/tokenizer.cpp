@@ -144,6 +144,7 @@ void Tokenizer::rebuild_vocab() {      // :843-861 / :562-564
 void Tokenizer::set_merges(const std::vector<TokenPair> &m) {
     drop_decoder();
     drop_encoder();
+    drop_counts();
     merges_ = m;
     merges_lookup_.clear();
     Token idx = 256;
@@ -153,6 +154,7 @@ void Tokenizer::set_merges(const std::vector<TokenPair> &m) {
 
 void Tokenizer::set_special_tokens_from_file(const std::string &input_string) {   // :476-486
     drop_decoder();
+    drop_counts();
     special_tokens_.clear();
     special_tokens_reverse_lookup_.clear();
     std::istringstream iss(input_string);
@@ -286,6 +288,7 @@ std::vector<uint32_t> Tokenizer::training_prior(int vocab_size, bool resume) con
 void Tokenizer::clear_model() {
     drop_decoder();
     drop_encoder();
+    drop_counts();
     merges_.clear();
     merges_lookup_.clear();
     initialize_vocab();
@@ -780,6 +783,71 @@ int Tokenizer::encode_batch_flat(const char *text, const uint64_t *doc_off, uint
     return MBPE_OK;
 }
 
+void Tokenizer::drop_counts() {
+    counts_.clear();
+    counts_total_ = 0;
+}
+
+uint64_t Tokenizer::count_ids() const {
+    uint64_t n = 256 + static_cast<uint64_t>(merges_.size());
+    for (const auto &kv : special_tokens_) n = std::max<uint64_t>(n, static_cast<uint64_t>(kv.second) + 1);
+    return n;
+}
+
+int Tokenizer::count_tokens(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
+                            uint64_t repeat, uint64_t *n_tokens_out, bool device_split) {
+    *n_tokens_out = 0;
+    auto fail = [](int code, const std::string &msg) { mbpe_host::set_last_error(msg); return code; };
+    if (repeat == 0) return fail(MBPE_ERR_ARG, "count_tokens: repeat must be at least 1");
+    const uint64_t n_ids = count_ids();
+    if (n_ids > MBPE_MAX_COUNT_IDS) return fail(MBPE_ERR_VOCAB, "count_tokens: a token id at or above MBPE_MAX_COUNT_IDS");
+    if (drop_threshold_ && !rank_order_) return fail(MBPE_ERR_ARG, "count_tokens: dropout needs the rank order");
+    const uint64_t n_bytes = doc_off[n_docs] - doc_off[0];
+    // (special tokens are shorter than their names only as NUL-led markers of the chunk buffer: twice the bytes bounds both)
+    if (n_bytes > (~0ull - counts_total_) / repeat / 2)
+        return fail(MBPE_ERR_OVERFLOW, "count_tokens: the weighted token total could reach 2^64");
+    if (counts_.size() != n_ids) { counts_.assign(n_ids, 0); counts_total_ = 0; }
+    std::vector<uint64_t> call(n_ids, 0);
+    uint64_t n = 0;
+    if (device < 0) {
+        for (uint64_t i = 0; i < n_docs; ++i) {
+            const std::vector<Token> toks = encode(std::string(text + doc_off[i], doc_off[i + 1] - doc_off[i]), verbose, -1);
+            for (Token t : toks)
+                if (t < n_ids) call[t] += repeat;      // (an id beyond the table: a NUL-led number in the text itself)
+            n += toks.size();
+        }
+    } else {
+        mbpe_encoder *enc = device_encoder(device);
+        int rc = mbpe_encoder_counts_reset(enc);
+        if (rc == MBPE_OK) rc = mbpe_encoder_set_option(enc, "count_ids", static_cast<int64_t>(n_ids));
+        if (rc != MBPE_OK) return rc;
+        if (device_split) {
+            DeviceSplit ds;
+            if ((rc = split_on_device(text, doc_off, n_docs, verbose, device, &ds)) != MBPE_OK) return rc;
+            rc = mbpe_encoder_count_endmask(enc, ds.d_text, ds.n_bytes, ds.d_mask, ds.singles.data(), ds.singles.size(),
+                                            repeat, &n, nullptr);
+        } else {
+            std::string buf;
+            std::vector<uint64_t> off, first_chunk;
+            batch_chunks(text, doc_off, n_docs, verbose, &buf, &off, &first_chunk);
+            rc = mbpe_encoder_count(enc, reinterpret_cast<const uint8_t *>(buf.data()), buf.size(), 0, off.data(),
+                                    off.size() - 1, repeat, &n, nullptr);
+        }
+        // the encoder's small table comes back, is added below and is zeroed: a re-created encoder loses nothing
+        uint64_t got_ids = 0;
+        if (rc == MBPE_OK) rc = mbpe_encoder_counts(enc, call.data(), call.size(), 0, &got_ids, nullptr, nullptr);
+        if (rc == MBPE_OK && got_ids != n_ids) rc = fail(MBPE_ERR_STATE, "count_tokens: the encoder's table has another size");
+        const int rc_reset = mbpe_encoder_counts_reset(enc);
+        if (rc != MBPE_OK) return rc;
+        if (rc_reset != MBPE_OK) return rc_reset;
+    }
+    for (uint64_t i = 0; i < n_ids; ++i) counts_[i] += call[i];
+    counts_total_ += repeat * n;
+    *n_tokens_out = n;
+    if (verbose) std::cout << "Counted " << n_docs << " texts (length " << n_bytes << "): " << n << " tokens\n";
+    return MBPE_OK;
+}
+
 int Tokenizer::encode_ranges(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
                              bool device_split, std::vector<Token> *tokens, std::vector<uint64_t> *ranges,
                              std::vector<uint64_t> *doc_tok_off) {
@@ -1019,6 +1087,7 @@ bool Tokenizer::load(const std::string &path, bool verbose) {
     }
     drop_decoder();
     drop_encoder();
+    drop_counts();
     drop_splitter();                                            // (the pattern may change)
     merges_lookup_.clear();
     merges_.clear();
@@ -1393,6 +1462,44 @@ int mbpe_tok_encode_batch_device(mbpe_tokenizer *t, const uint8_t *text, const u
         mbpe_host::set_last_error(e.what());
         return MBPE_ERR_ARG;
     }
+}
+
+int mbpe_tok_count_tokens(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off, uint64_t n_docs, int verbose,
+                          int device_id, uint64_t repeat, uint64_t *n_tokens_out) {
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!t || !n_tokens_out || !doc_off || (!text && doc_off[n_docs] > doc_off[0])) return null_argument("mbpe_tok_count_tokens");
+    for (uint64_t i = 0; i < n_docs; ++i)
+        if (doc_off[i + 1] < doc_off[i]) { mbpe_host::set_last_error("doc_off must be ascending"); return MBPE_ERR_ARG; }
+    try {
+        return t->t->count_tokens(reinterpret_cast<const char *>(text), doc_off, n_docs, verbose != 0, device_id, repeat,
+                                  n_tokens_out, t->t->encode_split());
+    } catch (const mbpe_host::CodedError &e) {
+        mbpe_host::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        mbpe_host::set_last_error(e.what());
+        return MBPE_ERR_ARG;
+    }
+}
+
+int mbpe_tok_token_counts(mbpe_tokenizer *t, uint64_t *counts_out, uint64_t cap_ids, uint64_t *n_ids_out,
+                          uint64_t *n_tokens_out) {
+    if (!t) return null_argument("mbpe_tok_token_counts");
+    const std::vector<uint64_t> &c = t->t->token_counts();
+    const uint64_t n_ids = c.empty() ? t->t->count_ids() : c.size();
+    if (n_ids_out) *n_ids_out = n_ids;
+    if (n_tokens_out) *n_tokens_out = t->t->token_counts_total();
+    if (!counts_out) return MBPE_OK;
+    if (cap_ids < n_ids) { mbpe_host::set_last_error("counts_out too small"); return MBPE_ERR_ARG; }
+    if (c.empty()) memset(counts_out, 0, n_ids * sizeof(uint64_t));
+    else memcpy(counts_out, c.data(), n_ids * sizeof(uint64_t));
+    return MBPE_OK;
+}
+
+int mbpe_tok_token_counts_reset(mbpe_tokenizer *t) {
+    if (!t) return null_argument("mbpe_tok_token_counts_reset");
+    t->t->drop_counts();
+    return MBPE_OK;
 }
 
 // the two _byteoff calls after their checks: one encode_ranges, then what the caller has room for

@@ -87,6 +87,21 @@ public:
                             uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out,
                             const mbpe_pack_aux *aux = nullptr, uint64_t *doc_tok_off_out = nullptr,
                             bool device_split = false, const mbpe_pack_window *win = nullptr);
+    // How often every token id is used (mbpe_tok_count_tokens): the documents are split as in encode_batch_flat and what
+    // encode would return for each is counted `repeat` times into a table the tokenizer keeps on the host, of
+    // count_ids() = max(256 + merges, largest special id + 1) entries.  device < 0: the host loop over encode();
+    // otherwise mbpe_encoder_count over the host split or, device_split, mbpe_encoder_count_endmask over the device
+    // split -- no token leaves the device; the encoder's table is read back, added and zeroed after every call.
+    // Order, dropout, dedup and the unicode split hold as for the batch encode calls.  MBPE_ERR_ARG for repeat 0,
+    // MBPE_ERR_VOCAB for an id at or above MBPE_MAX_COUNT_IDS, MBPE_ERR_OVERFLOW before the total could reach 2^64;
+    // a call that fails adds nothing.  Changing the merges or the special tokens empties the table.  (An id beyond
+    // the table can only come from a NUL-led number in the text itself; it is counted in n_tokens_out alone.)
+    int count_tokens(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device, uint64_t repeat,
+                     uint64_t *n_tokens_out, bool device_split = false);
+    uint64_t count_ids() const;
+    const std::vector<uint64_t> &token_counts() const { return counts_; }   // empty before the first count: all zeros
+    uint64_t token_counts_total() const { return counts_total_; }
+    void drop_counts();
     // what the mbpe_tok_encode*_device calls of the C-ABI pass as device_split (mbpe_tok_set_encode_split)
     void set_encode_split(bool on) { encode_split_ = on; }
     bool encode_split() const { return encode_split_; }
@@ -227,6 +242,8 @@ private:
     bool encode_dedup_ = false;
     bool rank_order_ = false;
     uint64_t drop_threshold_ = 0, drop_seed_ = 0;
+    std::vector<uint64_t> counts_;           // count_tokens: the table, and the weighted token total it has reached
+    uint64_t counts_total_ = 0;
 };
 
 }  // namespace mbpe_host

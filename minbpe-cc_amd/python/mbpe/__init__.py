@@ -49,6 +49,8 @@ EXPORTS = [
     "mbpe_wordcount_set_option", "mbpe_wordcount_kernel_ms", "mbpe_wordcount_alloc_count",
     "mbpe_wordcount_export_size", "mbpe_wordcount_export", "mbpe_wordcount_merge_blob", "mbpe_wordcount_merge",
     "mbpe_pack_windows", "mbpe_encoder_encode_batch_windows", "mbpe_encoder_encode_batch_endmask_windows",
+    "mbpe_token_counts", "mbpe_token_counts_kernel_ms", "mbpe_encoder_count", "mbpe_encoder_count_endmask",
+    "mbpe_encoder_counts", "mbpe_encoder_counts_reset",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -62,7 +64,8 @@ TOK_EXPORTS = [
     "mbpe_tok_set_encode_dedup", "mbpe_tok_train_pieces_begin", "mbpe_tok_train_pieces_add",
     "mbpe_tok_train_pieces_finish", "mbpe_tok_train_pieces_abort", "mbpe_tok_set_train_limits",
     "mbpe_tok_train_pieces_export_size", "mbpe_tok_train_pieces_export", "mbpe_tok_train_pieces_merge",
-    "mbpe_tok_encode_batch_windows_device",
+    "mbpe_tok_encode_batch_windows_device", "mbpe_tok_count_tokens", "mbpe_tok_token_counts",
+    "mbpe_tok_token_counts_reset",
 ]
 
 
@@ -319,6 +322,15 @@ def lib():
     L.mbpe_tok_encode.argtypes = [vp, vp, u64, i32, vp, u64, vp]
     L.mbpe_tok_encode_device.argtypes = [vp, vp, u64, i32, i32, vp, u64, vp]
     L.mbpe_tok_decode.argtypes = [vp, vp, u64, i32, vp, u64, vp]
+    L.mbpe_token_counts.argtypes = [i32, vp, u64, u32, i32, vp, u64, i32, vp]
+    L.mbpe_token_counts_kernel_ms.argtypes = [vp]
+    L.mbpe_encoder_count.argtypes = [vp, vp, u64, i32, vp, u64, u64, vp, vp]
+    L.mbpe_encoder_count_endmask.argtypes = [vp, vp, u64, vp, vp, u64, u64, vp, vp]
+    L.mbpe_encoder_counts.argtypes = [vp, vp, u64, i32, vp, vp, vp]
+    L.mbpe_encoder_counts_reset.argtypes = [vp]
+    L.mbpe_tok_count_tokens.argtypes = [vp, vp, vp, u64, i32, i32, u64, vp]
+    L.mbpe_tok_token_counts.argtypes = [vp, vp, u64, vp, vp]
+    L.mbpe_tok_token_counts_reset.argtypes = [vp]
     _lib = L
     return L
 
@@ -462,6 +474,36 @@ def pack_tokens(tokens, doc_tok_off, seq_len, layout="padded", out_bits=32, pad_
         _check(lib().mbpe_pack_tokens(*head, ids.ctypes.data, n_rows.value, 0, lengths.ctypes.data,
                                       ctypes.byref(n_rows)))
     return ids, lengths
+
+
+def token_counts(tokens, n_ids, device=0, tokens_ptr=None, n_tokens=None, token_bits=None, out_ptr=None):
+    """mbpe_token_counts: how often every id below n_ids occurs in a token array (uint16, or uint32 whose bit 31 is
+    ignored) -> (counts uint64[n_ids], n_other), n_other counting the ids at or beyond n_ids.  Device memory:
+    tokens_ptr= / n_tokens= / token_bits= name the tokens there instead of `tokens`; with out_ptr= (room for n_ids
+    uint64) the table is written there and only n_other is returned."""
+    if tokens_ptr is None:
+        t = np.ascontiguousarray(tokens)
+        if t.dtype not in (np.dtype(np.uint16), np.dtype(np.uint32)):
+            t = t.astype(np.uint32)
+        t = t.reshape(-1)
+        tp, n_tokens, token_bits, on_dev = (t.ctypes.data if len(t) else None), len(t), t.dtype.itemsize * 8, 0
+    else:
+        tp, on_dev = _ptr(tokens_ptr), 1
+    other = ctypes.c_uint64()
+    if out_ptr is not None:
+        _check(lib().mbpe_token_counts(device, tp, n_tokens, token_bits, on_dev, _ptr(out_ptr), n_ids, 1, ctypes.byref(other)))
+        return other.value
+    # (the library checks n_ids before it writes: the array only has to exist for a valid one)
+    out = np.zeros(n_ids if 0 < n_ids <= (1 << 25) else 1, dtype=np.uint64)
+    _check(lib().mbpe_token_counts(device, tp, n_tokens, token_bits, on_dev, out.ctypes.data, n_ids, 0, ctypes.byref(other)))
+    return out, other.value
+
+
+def token_counts_kernel_ms():
+    """Device time of the histogram kernel of this thread's latest token_counts (mbpe_token_counts_kernel_ms)."""
+    ms = ctypes.c_float()
+    _check(lib().mbpe_token_counts_kernel_ms(ctypes.byref(ms)))
+    return ms.value
 
 
 def pack_cu_seqlens(doc_tok_off, seq_len, bos_id=None, eos_id=None):
@@ -673,8 +715,9 @@ class Encoder:
     """One mbpe_encoder: internal_encode (Tokenizer.h:325-377) on a HIP device with the lookup table, the stream and
     the work buffers kept between calls."""
 
-    def __init__(self, merges, device=0, rank_order=False, dropout=0.0, seed=0, dedup=False):
-        """rank_order: the option "rank_order" from the start (set_option changes it between calls).
+    def __init__(self, merges, device=0, rank_order=False, dropout=0.0, seed=0, dedup=False, count_ids=None):
+        """count_ids: the option "count_ids" from the start: the table of count() has max(256 + n_merges, count_ids) bins.
+        rank_order: the option "rank_order" from the start (set_option changes it between calls).
         dropout, seed: BPE-dropout from the start (set_dropout changes it between calls); needs rank_order.
         dedup: the option "dedup" from the start: every call dedups its chunks on the device, encodes the distinct
         ones and expands (the same results; dropout and byte offsets raise MbpeError(ERR_ARG) while it is on)."""
@@ -689,6 +732,8 @@ class Encoder:
             self.set_dropout(dropout, seed)
         if dedup:
             self.set_option("dedup", 1)
+        if count_ids is not None:
+            self.set_option("count_ids", count_ids)
 
     def close(self):
         if self._h:
@@ -958,6 +1003,54 @@ class Encoder:
                   *tail, ctypes.byref(aux) if call else None, doc_tok_off.ctypes.data))
         self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
         return call.result(ids, lengths, arrays, doc_tok_off) if call else (ids, lengths)
+
+    def _count(self, fn, head, repeat):
+        n, passes = ctypes.c_uint64(), ctypes.c_uint32()
+        _check(fn(*head, int(repeat), ctypes.byref(n), ctypes.byref(passes)))
+        self.n_passes = passes.value
+        return n.value
+
+    def count(self, data, chunk_off=None, repeat=1):
+        """Encode a host text and count its tokens into the table the encoder keeps (mbpe_encoder_count): what encode
+        would return for the same arguments, `repeat` times; no token leaves the device -> the token count (without
+        repeat).  counts() reads the table, reset_counts() zeroes it."""
+        text = _u8(data)
+        off = None if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.uint64)
+        head = (self._h, text.ctypes.data if len(text) else None, len(text), 0,
+                None if off is None else off.ctypes.data, 0 if off is None else len(off) - 1)
+        return self._count(lib().mbpe_encoder_count, head, repeat)
+
+    def count_device(self, text_ptr, n_bytes, chunk_off, repeat=1):
+        """count for n_bytes of text in device memory at text_ptr (read in place)."""
+        off = None if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.uint64)
+        head = (self._h, _ptr(text_ptr), n_bytes, 1, None if off is None else off.ctypes.data,
+                0 if off is None else len(off) - 1)
+        return self._count(lib().mbpe_encoder_count, head, repeat)
+
+    def count_endmask(self, text_ptr, n_bytes, mask_ptr, singles=None, repeat=1):
+        """count for a device text with its end mask in device memory (mbpe_encoder_count_endmask; the arguments of
+        encode_endmask)."""
+        sg = _singles(singles)
+        head = (self._h, _ptr(text_ptr), n_bytes, _ptr(mask_ptr), sg.ctypes.data if len(sg) else None, len(sg))
+        return self._count(lib().mbpe_encoder_count_endmask, head, repeat)
+
+    def counts(self, out_ptr=None):
+        """The table (mbpe_encoder_counts) -> (counts uint64[n_ids], n_other, n_tokens): n_other counts the ids at or
+        beyond n_ids, n_tokens is the weighted total, and sum(counts) + n_other == n_tokens.  With out_ptr= (device
+        memory for n_ids uint64) the table is written there and n_ids stands in place of the array."""
+        n_ids, other, total = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        tail = (ctypes.byref(n_ids), ctypes.byref(other), ctypes.byref(total))
+        _check(lib().mbpe_encoder_counts(self._h, None, 0, 0, *tail))
+        if out_ptr is not None:
+            _check(lib().mbpe_encoder_counts(self._h, _ptr(out_ptr), n_ids.value, 1, *tail))
+            return n_ids.value, other.value, total.value
+        out = np.zeros(n_ids.value, dtype=np.uint64)
+        _check(lib().mbpe_encoder_counts(self._h, out.ctypes.data, len(out), 0, *tail))
+        return out, other.value, total.value
+
+    def reset_counts(self):
+        """Zero the table (mbpe_encoder_counts_reset)."""
+        _check(lib().mbpe_encoder_counts_reset(self._h))
 
     def pack_ms(self):
         """Device time of the pack kernel of the latest encode_batch (mbpe_encoder_pack_ms)."""
@@ -1945,6 +2038,43 @@ class Tokenizer:
                                                   len(parts), 0, device, out.ctypes.data, len(out), tok_off.ctypes.data,
                                                   ctypes.byref(n)))
         return [out[int(a):int(b)].copy() for a, b in zip(tok_off[:-1], tok_off[1:])]
+
+    def token_counts(self, texts, device=0, device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False,
+                     repeats=None, batch_bytes=1 << 28):
+        """How often every token id is used on `texts` (any iterable of texts) -> uint64[n_ids], n_ids = max(256 +
+        merges, largest special id + 1): the bincount of encode() of every text, text i counted repeats[i] times
+        (mbpe_tok_count_tokens).  With a device no token leaves it: the texts go there in batches of whole texts of at
+        most batch_bytes (a longer text is a batch of its own), and only the table comes back.  device=None is the host
+        loop.  device_split, order, dropout, seed and dedup as for encode_batch.  The table is reset first."""
+        self._encode_split(device_split, order, dropout, seed, dedup)
+        _check(lib().mbpe_tok_token_counts_reset(self._h))
+        dev = -1 if device is None else device
+
+        def flush(parts, rep):
+            doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+            doc_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
+            text = np.frombuffer(b"".join(parts), dtype=np.uint8)
+            n = ctypes.c_uint64()
+            _check(lib().mbpe_tok_count_tokens(self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data,
+                                               len(parts), 0, dev, rep, ctypes.byref(n)))
+
+        reps = None if repeats is None else iter(repeats)
+        parts, held, cur = [], 0, 1
+        for data in texts:
+            part = bytes(_u8(data))
+            rep = 1 if reps is None else int(next(reps))
+            if parts and (rep != cur or held + len(part) > batch_bytes):
+                flush(parts, cur)
+                parts, held = [], 0
+            parts.append(part)
+            held, cur = held + len(part), rep
+        if parts:
+            flush(parts, cur)
+        n_ids = ctypes.c_uint64()
+        _check(lib().mbpe_tok_token_counts(self._h, None, 0, ctypes.byref(n_ids), None))
+        out = np.zeros(n_ids.value, dtype=np.uint64)
+        _check(lib().mbpe_tok_token_counts(self._h, out.ctypes.data, len(out), ctypes.byref(n_ids), None))
+        return out
 
     def encode_batch_padded(self, texts, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
                             pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
