@@ -962,6 +962,93 @@ MBPE_API int  mbpe_encoder_encode_batch_endmask_windows(mbpe_encoder *e, const u
                                                         uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
                                                         uint64_t *doc_tok_off_out, const mbpe_pack_window *win);
 
+/* ---- whole documents packed into rows by best fit -------------------------- */
+
+/* The fourth way into [rows, seq_len]: many whole documents per row, none cut unless it is longer than a row, as little
+ * padding as the best-fit-decreasing rule leaves (Ding et al. 2024, "Fewer Truncations Improve Language Modeling").
+ * Let S = seq_len.  Document d is the element list E_d = [bos] doc_d [eos] of MBPE_PACK_PACKED, T_d = L_d + nb + ne,
+ * never truncated.
+ *   Pieces     d has q_d = T_d / S full pieces, piece i holding elements [i * S, (i + 1) * S), and, where
+ *              r_d = T_d % S > 0, one tail piece: elements [q_d * S, T_d).  T_d == 0 gives no piece.
+ *   Placement  all pieces are taken by size descending, then d ascending, then i ascending.  A piece of size s goes to
+ *              the row, among those opened so far with free >= s, that has the smallest free (ties: the lowest row
+ *              index), into columns [S - free, S - free + s).  If no row has room a new one is opened -- its index is
+ *              the number of rows opened so far -- and the piece starts at column 0.  n_rows = the rows opened.
+ * So rows 0 .. F - 1, F = the sum of q_d, are the full pieces in document order; piece sizes do not increase from left
+ * to right in a row; padding lies only at the right end of a row and len[row] is the number of cells used; a document
+ * with T_d <= S lies in one row, contiguously; at most one row has 2 * len <= S.
+ *   Cells      cell (row, col0 + t) of a piece that starts at element k0 of E_d holds element k = k0 + t:
+ *              ids E_d[k]; labels E_d[k + 1] if k + 1 < T_d, else ignore_label -- as in PACKED a label crosses a piece
+ *              end inside a document and never crosses into another document; pos k, which goes on counting through
+ *              the pieces of a long document; seg d + 1.  Pad cells get pad_id, ignore_label, 0 and 0.
+ *   doc_row, doc_col   [n_docs]: the cell that holds the first element of the document's last piece (the tail piece if
+ *              r_d > 0, else the last full piece); UINT64_MAX and 0 for T_d == 0.  The full pieces of d are the rows
+ *              [sum of q_e over e < d, ... + q_d).
+ * When every T_d is a multiple of S the matrices are those of mbpe_pack_tokens_aux with MBPE_PACK_PACKED, and when
+ * every T_d is one value in (S / 2, S] those with MBPE_PACK_PADDED, bit for bit.
+ * Use it only where attention is masked by seg or by cu_seqlens: a row holds unrelated documents. */
+struct mbpe_pack_fit {    /* a tag, not a typedef: the call below has the name.  Write `struct mbpe_pack_fit` */
+    uint64_t *doc_row;     /* [n_docs] or NULL; on the same side as ids_out, 8-byte aligned on the device */
+    uint32_t *doc_col;     /* [n_docs] or NULL; 4-byte aligned on the device */
+};
+
+/* The plan alone, on the host (no device, never MBPE_ERR_NO_DEVICE): the row count, the cells used per row and where
+ * every document lies.  About O((pieces + rows) * log S) time.
+ *   doc_tok_off, n_docs, spec   as for mbpe_pack_fit; out_bits and pad_id play no part
+ *   len_out           cap_rows entries, or NULL: count only.  A cap_rows too small is MBPE_ERR_ARG, writes nothing
+ *                     and still reports the count
+ *   n_rows_out        required
+ *   doc_row_out, doc_col_out   optional, n_docs entries each */
+MBPE_API int  mbpe_pack_fit_plan(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec,
+                                 uint32_t *len_out, uint64_t cap_rows, uint64_t *n_rows_out, uint64_t *doc_row_out,
+                                 uint32_t *doc_col_out);
+
+/* cu_seqlens and max_seqlen of a fit matrix for variable-length attention, on the host alone, with the conventions of
+ * mbpe_pack_cu_seqlens (query, cap rule, required outputs).  The list holds the boundaries of the maximal runs of equal
+ * (row, seg) in the flattened matrix.  Unlike PACKED, pad runs lie inside the matrix: each counts as a sequence of its
+ * own, whose labels are all ignore_label.  The list therefore starts at 0 and ends at n_rows * seq_len (n_rows == 0:
+ * [0] and n_seqs 0); max_seqlen is the longest run, pad runs included.  n_rows * seq_len >= 2^31 is MBPE_ERR_ARG. */
+MBPE_API int  mbpe_pack_fit_cu_seqlens(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec,
+                                       int32_t *cu_out, uint64_t cap_seqs, uint64_t *n_seqs_out,
+                                       uint32_t *max_seqlen_out);
+
+/* mbpe_pack_tokens_aux for the fit layout.  All arguments up to aux are those of mbpe_pack_tokens_aux; spec->layout must
+ * be MBPE_PACK_PACKED (so pad_left and trunc_left 0); aux and fit are required, all of their pointers may be NULL.
+ * MBPE_ERR_ARG: fit NULL, another layout, more than 2^40 rows, seg with n_docs >= 2^32 - 1, pos with a T_d >= 2^32, and
+ * the NULL and alignment rules of mbpe_pack_tokens_aux (doc_row 8, doc_col 4 bytes on the device); MBPE_ERR_VOCAB as for
+ * mbpe_pack_tokens.  All of it is checked, the plan made and a query (ids_out NULL: the row count alone) answered on
+ * the host before the device is touched; a cap_rows too small is MBPE_ERR_ARG, writes nothing and still reports the
+ * count; an error return writes nothing.  The plan is uploaded once per call, 24 bytes per piece and 8 bytes per row
+ * of device scratch, and k_pack_fit (csrc/pack.hip) writes the matrices; mbpe_pack_kernel_ms covers it.  doc_row and
+ * doc_col are the plan's and are copied to where fit names them. */
+MBPE_API int  mbpe_pack_fit(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits,
+                            int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs,
+                            const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
+                            uint32_t *len_out, uint64_t *n_rows_out, const mbpe_pack_aux *aux,
+                            const struct mbpe_pack_fit *fit);
+
+/* mbpe_encoder_encode_batch_aux and mbpe_encoder_encode_batch_endmask (aux required here too) for the fit layout: their
+ * arguments, then fit.  No token crosses to the host.  The documents' token offsets do, after the passes, 8 bytes per
+ * document -- the one thing that crosses, also in the endmask call -- because the plan is made on the host; a query
+ * (ids_out NULL) therefore runs the passes, and a cap_rows too small is found after them, writes nothing and reports
+ * the count.  The plan, its device copy (24 bytes per piece, 8 per row) and the staging of host outputs live in buffers
+ * the encoder keeps: a repeat call of no larger size leaves mbpe_encoder_alloc_count as it is.  Packing happens after
+ * the tokens exist, so "rank_order", dropout and "dedup" hold as for the other batch calls.  mbpe_encoder_pack_ms
+ * covers k_pack_fit. */
+MBPE_API int  mbpe_encoder_encode_batch_fit(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                            const uint64_t *chunk_off, uint64_t n_chunks,
+                                            const uint64_t *doc_chunk_off, uint64_t n_docs, const mbpe_pack_spec *spec,
+                                            void *ids_out, uint64_t cap_rows, int out_on_device, uint32_t *len_out,
+                                            uint64_t *n_rows_out, uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
+                                            uint64_t *doc_tok_off_out, const struct mbpe_pack_fit *fit);
+MBPE_API int  mbpe_encoder_encode_batch_endmask_fit(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
+                                                    const uint8_t *endmask_dev, const mbpe_single *singles,
+                                                    uint64_t n_singles, const uint64_t *doc_off, uint64_t n_docs,
+                                                    const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows,
+                                                    int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                                                    uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
+                                                    uint64_t *doc_tok_off_out, const struct mbpe_pack_fit *fit);
+
 /* ---- decode on the device ----------------------------------------------- */
 
 /* Tokenizer::decode (Tokenizer.h:725-751) for whole token streams on HIP device `device_id`: per token a byte

@@ -183,6 +183,17 @@ MBPE_API int mbpe_tok_encode_batch_windows_device(mbpe_tokenizer *t, const uint8
                                                   uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
                                                   uint64_t *doc_tok_off_out, const mbpe_pack_window *win);
 
+/* The same for the fit layout of mbpe_pack_fit (mbpe.h): whole texts, many per row, placed by best fit; a text is cut
+ * only where it is longer than a row.  The arguments of mbpe_tok_encode_batch_aux_device, then fit (required; spec->layout
+ * MBPE_PACK_PACKED); the call goes to mbpe_encoder_encode_batch_fit or -- mbpe_tok_set_encode_split --
+ * mbpe_encoder_encode_batch_endmask_fit, and mbpe_tok_set_encode_order, _dropout, _dedup and _split_unicode hold as for
+ * the other batch calls. */
+MBPE_API int mbpe_tok_encode_batch_fit_device(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off,
+                                              uint64_t n_docs, int verbose, int device_id, const mbpe_pack_spec *spec,
+                                              void *ids_out, uint64_t cap_rows, int out_on_device, uint32_t *len_out,
+                                              uint64_t *n_rows_out, uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
+                                              uint64_t *doc_tok_off_out, const struct mbpe_pack_fit *fit);
+
 /* Where the mbpe_tok_encode*_device calls above split their text: 0 (the default) on the host, as described there;
  * otherwise on the device too -- the text is uploaded once, cut at the special tokens and split into chunks by
  * mbpe_splitter_split_docs (a splitter that the tokenizer keeps until another device is named), and the encoder reads

@@ -55,6 +55,7 @@
 #include "hip_host.h"
 #include "hist.h"
 #include "pack.h"
+#include "pack_fit.h"
 #include "rank.h"
 #include "span.h"
 
@@ -519,6 +520,10 @@ struct mbpe_encoder : DevQueue {
     // the _windows calls: the rows' prefix sum over the documents; row_doc and row_tok0 that go to the host
     DevBuf<unsigned long long> d_row_start, d_row_tok0;
     DevBuf<uint32_t> d_row_doc;
+    // the _fit calls: the plan (host, made from the documents' token offsets) and its copy for k_pack_fit
+    PackFitPlan fit_plan;
+    DevBuf<uint8_t> d_fit_pieces;
+    DevBuf<unsigned long long> d_fit_rows;
     float pack_ms = 0.f;                      // the pack kernel of the latest such call
     // token byte offsets: len[id] (host; empty with len_error set for a table mbpe_merges_check refuses), on the
     // device from the first such call on; the spans' byte counts, the singles' token indices, offsets bound for the host
@@ -694,6 +699,7 @@ struct EncPack {
     const mbpe_pack_aux *aux;
     uint64_t *doc_tok_off_out;
     const mbpe_pack_window *win;    // the _windows calls; NULL: the spec's own layout
+    const struct mbpe_pack_fit *fit;   // the _fit calls (win NULL); NULL: the spec's own layout
     uint32_t token_bits() const { return spec->out_bits == 16 ? 16 : 32; }
 };
 
@@ -1478,9 +1484,15 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool doc
     const mbpe_pack_aux *aux = k.aux;
     const uint64_t n_docs = k.n_docs;
     const mbpe_pack_window *win = k.win;
+    const struct mbpe_pack_fit *fit = k.fit;
     int rc = MBPE_OK;
     uint64_t n_rows = win ? 0 : pack_rows(spec, n_tokens, n_docs);
     float rows_ms = 0.f;
+    if (fit) {
+        // the rows depend on the plan, and the plan is host work: from e->doc_tok, which both callers have filled
+        if ((rc = pack_fit_make(e->doc_tok.data(), n_docs, spec, &e->fit_plan)) != MBPE_OK) return rc;
+        n_rows = e->fit_plan.n_rows;
+    }
     if (win && n_docs) {
         // the row count depends on the tokens: k_win_rows, the scan and k_win_offsets over the device's offsets, then the total
         rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
@@ -1504,9 +1516,13 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool doc
     if (k.ids_out && k.cap_rows < n_rows) return fail(MBPE_ERR_ARG, "ids_out too small");
     if (k.doc_tok_off_out) std::copy(e->doc_tok.begin(), e->doc_tok.end(), k.doc_tok_off_out);   // (filled in both cases)
     if (!k.ids_out) return MBPE_OK;                              // the query
-    if (n_rows == 0) return MBPE_OK;
+    if (n_rows == 0) return fit ? pack_fit_doc_out(e->stream, *fit, e->fit_plan, k.out_on_device) : MBPE_OK;
     const uint64_t id_bytes = n_rows * spec.seq_len * (spec.out_bits / 8), cell_bytes = n_rows * spec.seq_len * 4;
     rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
+    if (rc == MBPE_OK && fit) {
+        rc = e->d_fit_pieces.reserve(pack_fit_piece_bytes(e->fit_plan), e->mem);
+        if (rc == MBPE_OK) rc = e->d_fit_rows.reserve((n_rows + 1) * 8, e->mem);
+    }
     if (rc == MBPE_OK && !k.out_on_device) {
         rc = e->d_ids.reserve(id_bytes, e->mem);
         if (rc == MBPE_OK && k.len_out) rc = e->d_len.reserve(n_rows * 4, e->mem);
@@ -1531,8 +1547,14 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool doc
     const PackSrc src = {e->d_flat, e->d_doc_off, n_docs, n_tokens, k.token_bits()};
     const PackDst dst = {k.out_on_device ? k.ids_out : e->d_ids.get(),
                          k.out_on_device || !k.len_out ? k.len_out : e->d_len.get(), n_rows};
+    if (fit) {
+        ECHK(hipMemcpyAsync(e->d_fit_pieces, e->fit_plan.pieces.data(), pack_fit_piece_bytes(e->fit_plan),
+                            hipMemcpyHostToDevice, e->stream));
+        ECHK(hipMemcpyAsync(e->d_fit_rows, e->fit_plan.row_first.data(), (n_rows + 1) * 8, hipMemcpyHostToDevice, e->stream));
+    }
     ECHK(hipEventRecord(e->ev0, e->stream));
-    if (win) pack_launch_windows(e->stream, src, spec, dst, d_aux, d_win, e->d_row_start);
+    if (fit) pack_launch_fit(e->stream, src, spec, dst, d_aux, e->d_fit_pieces, e->d_fit_rows);
+    else if (win) pack_launch_windows(e->stream, src, spec, dst, d_aux, d_win, e->d_row_start);
     else if (aux) pack_launch_aux(e->stream, src, spec, dst, d_aux);
     else pack_launch(e->stream, src, spec, dst);
     if ((rc = e->finish(&e->pack_ms)) != MBPE_OK) return rc;
@@ -1548,7 +1570,7 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool doc
         if (win && win->row_tok0) ECHK(hipMemcpyAsync(win->row_tok0, e->d_row_tok0, n_rows * 8, hipMemcpyDeviceToHost, e->stream));
         ECHK(hipStreamSynchronize(e->stream));
     }
-    return MBPE_OK;
+    return fit ? pack_fit_doc_out(e->stream, *fit, e->fit_plan, k.out_on_device) : MBPE_OK;
 }
 
 // what the batch calls check alike once their own arguments are in order (the document lengths: after the encode)
@@ -1558,6 +1580,7 @@ int enc_batch_check(const mbpe_encoder *e, const EncPack &k) {
         ((uint64_t)(uintptr_t)k.ids_out % (k.spec->out_bits / 8) || (uint64_t)(uintptr_t)k.len_out % 4))
         return fail(MBPE_ERR_ARG, "ids_out or len_out is not aligned to its elements");
     if (k.win) return pack_check_windows(k.spec, k.token_bits(), k.aux, k.win, k.n_docs, k.ids_out, k.out_on_device);
+    if (k.fit) return pack_check_fit(k.spec, k.token_bits(), k.aux, k.fit, k.n_docs, k.ids_out, k.out_on_device);
     return k.aux ? pack_check_aux(*k.spec, k.aux, nullptr, k.n_docs, k.ids_out, k.out_on_device) : MBPE_OK;
 }
 
@@ -1869,6 +1892,19 @@ int mbpe_encoder_encode_batch_windows(mbpe_encoder *e, const uint8_t *text, uint
                       doc_tok_off_out, win});
 }
 
+int mbpe_encoder_encode_batch_fit(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                  const uint64_t *chunk_off, uint64_t n_chunks, const uint64_t *doc_chunk_off,
+                                  uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows,
+                                  int out_on_device, uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out,
+                                  const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out, const struct mbpe_pack_fit *fit) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!aux || !fit) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_batch_fit: NULL argument");
+    return enc_batch(e, {text, n_bytes, text_on_device, chunk_off, n_chunks},
+                     {doc_chunk_off, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
+                      doc_tok_off_out, nullptr, fit});
+}
+
 int mbpe_encoder_encode_batch_aux(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
                                   const uint64_t *chunk_off, uint64_t n_chunks, const uint64_t *doc_chunk_off,
                                   uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows,
@@ -1924,18 +1960,18 @@ int mbpe_encoder_encode_endmask_byteoff(mbpe_encoder *e, const uint8_t *text_dev
     return enc_guard("mbpe_encoder_encode_endmask", [&] { return enc_endmask_body(e, a); });
 }
 
-// mbpe_encoder_encode_batch_endmask (win NULL) and mbpe_encoder_encode_batch_endmask_windows
+// mbpe_encoder_encode_batch_endmask (win and fit NULL), mbpe_encoder_encode_batch_endmask_windows and _fit
 static int enc_batch_endmask(const std::string &who, mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
                              const uint8_t *endmask_dev, const mbpe_single *singles, uint64_t n_singles,
                              const uint64_t *doc_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
                              uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
                              uint64_t *n_tokens_out, const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out,
-                             const mbpe_pack_window *win) {
+                             const mbpe_pack_window *win, const struct mbpe_pack_fit *fit = nullptr) {
     if (n_rows_out) *n_rows_out = 0;
     if (n_tokens_out) *n_tokens_out = 0;
     if (!spec || !doc_off || !n_rows_out) return fail(MBPE_ERR_ARG, who + ": NULL argument");
     const EncPack k = {nullptr, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
-                       doc_tok_off_out, win};
+                       doc_tok_off_out, win, fit};
     int rc = pack_check_spec(spec, k.token_bits());
     if (rc != MBPE_OK) return rc;
     rc = enc_endmask_check(who.c_str(), n_bytes, singles, n_singles, doc_off, n_docs, k.token_bits());
@@ -1955,8 +1991,8 @@ static int enc_batch_endmask(const std::string &who, mbpe_encoder *e, const uint
         int rc = enc_batch_flat(e, &a, k, &n_tokens);
         if (rc != MBPE_OK) return rc;
         // the offsets stay on the device; the host sees them where it asks for them, or where a document could be too
-        // long for pos (only a text of 2^32 bytes or more)
-        const bool to_host = doc_tok_off_out || (aux && n_bytes + 2 >= (1ull << 32));
+        // long for pos (only a text of 2^32 bytes or more), or where the fit plan is made of them
+        const bool to_host = doc_tok_off_out || fit || (aux && n_bytes + 2 >= (1ull << 32));
         e->doc_tok.assign(n_docs + 1, 0);
         a.doc_tok_off_out = to_host ? e->doc_tok.data() : nullptr;
         rc = enc_endmask_body(e, a);
@@ -1989,6 +2025,20 @@ int mbpe_encoder_encode_batch_endmask_windows(mbpe_encoder *e, const uint8_t *te
     return enc_batch_endmask("mbpe_encoder_encode_batch_endmask_windows", e, text_dev, n_bytes, endmask_dev, singles,
                              n_singles, doc_off, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out,
                              n_tokens_out, aux, doc_tok_off_out, win);
+}
+
+int mbpe_encoder_encode_batch_endmask_fit(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
+                                          const uint8_t *endmask_dev, const mbpe_single *singles, uint64_t n_singles,
+                                          const uint64_t *doc_off, uint64_t n_docs, const mbpe_pack_spec *spec,
+                                          void *ids_out, uint64_t cap_rows, int out_on_device, uint32_t *len_out,
+                                          uint64_t *n_rows_out, uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
+                                          uint64_t *doc_tok_off_out, const struct mbpe_pack_fit *fit) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!aux || !fit) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_batch_endmask_fit: NULL argument");
+    return enc_batch_endmask("mbpe_encoder_encode_batch_endmask_fit", e, text_dev, n_bytes, endmask_dev, singles, n_singles,
+                             doc_off, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out,
+                             aux, doc_tok_off_out, nullptr, fit);
 }
 
 // ---- the count calls (hist.h) -----------------------------------------------------------------------------------------

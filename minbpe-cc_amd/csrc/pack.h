@@ -70,6 +70,31 @@ void pack_launch_win_rows(hipStream_t stream, const unsigned long long *doc_off,
 void pack_launch_windows(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst,
                          const mbpe_pack_aux &aux, const mbpe_pack_window &win, const unsigned long long *row_start);
 
+// ---- best-fit packing (mbpe_pack_fit; the planner is in pack_fit.h) -------------------------------------------------------
+
+struct PackFitPlan;
+
+// the rules of the fit calls that need neither offsets nor a device: pack_check_spec, the layout (MBPE_PACK_PACKED),
+// fit itself, pack_check_aux, and with out_on_device the alignment of doc_row (8) and doc_col (4).  MBPE_OK, or
+// MBPE_ERR_ARG / MBPE_ERR_VOCAB with the last error set
+int pack_check_fit(const mbpe_pack_spec *spec, uint32_t token_bits, const mbpe_pack_aux *aux, const struct mbpe_pack_fit *fit,
+                   uint64_t n_docs, const void *ids_out, int out_on_device);
+
+// the plan of the host's document offsets: MBPE_OK, or MBPE_ERR_ARG (more than 2^40 rows) with the last error set
+int pack_fit_make(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec &spec, PackFitPlan *plan);
+
+// what a plan puts on the device beside row_first ((n_rows + 1) * 8 bytes): its piece table
+uint64_t pack_fit_piece_bytes(const PackFitPlan &plan);
+
+// k_pack_fit on `stream`: dst.n_rows == plan.n_rows > 0; pieces and row_first are the plan's, in device memory; aux's
+// pointers name device memory (ids, labels, pos and seg 16-byte aligned) or are NULL.  Nothing is waited for
+void pack_launch_fit(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst,
+                     const mbpe_pack_aux &aux, const void *pieces, const unsigned long long *row_first);
+
+// the plan's doc_row / doc_col to where fit asks for them: host memory, or device memory through `stream`, which is
+// waited for
+int pack_fit_doc_out(hipStream_t stream, const struct mbpe_pack_fit &fit, const PackFitPlan &plan, int out_on_device);
+
 }  // namespace mbpe
 
 #endif

@@ -8,6 +8,8 @@
 //   unpack             a right-padded PADDED matrix and its lengths -> the flat tokens mbpe_decode_batch reads
 //   windows            PADDED rows, but a document that does not fit becomes several rows of its own that share `stride`
 //                      tokens (mbpe_pack_windows; k_win_rows .. k_pack_windows below, after k_pack_aux)
+//   fit                whole documents, many per row, placed by best fit on the host (mbpe_pack_fit; k_pack_fit below,
+//                      after k_pack_windows)
 //
 // All three are OUTPUT-centric like decode.hip's copy: the output, whose rows follow each other without a gap, is cut
 // at the 16-byte boundaries of its global address and a lane owns one such piece -- 8, 4 or 2 ids of 16, 32 or 64 bits.
@@ -30,6 +32,7 @@
 #include "pack.h"
 
 #include "hip_host.h"
+#include "pack_fit.h"
 #include "pack_host.h"
 #include "span.h"
 
@@ -540,6 +543,116 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_windows(PackWinJob wj) {
     }
 }
 
+// ---- best-fit packing ----------------------------------------------------------------------------------------------------
+// Whole documents, many per row (mbpe.h, mbpe_pack_fit).  Where the pieces go is decided on the host (pack_fit.h); the
+// kernel gets the plan: the piece table sorted by (row, column), 24 B per piece, and row_first, 8 B per row.
+//   k_pack_fit      the matrices.  It cuts cell-index space like k_pack_aux (8 cells per lane, the same stores).  The
+//                   first cell of a lane finds its row by one division and its piece by one binary search PER LANE
+//                   over the row's slice of the table (the largest col0 <= column; the first piece of a row starts at
+//                   column 0 and the pieces of a row touch, so whatever lies behind the last one is pad).  The walk
+//                   then steps to the next piece, which is the next table entry also across a row end: every row has a
+//                   piece.  Labels use the one-element look-ahead of k_pack_aux; it is dropped at a piece end, behind
+//                   which another document begins, and the label there is read from the document itself (element
+//                   k + 1 lies in the document's next piece, in another row).
+// Bytes moved per cell: what k_pack_aux moves (the id and each output written once, a token read once, twice at the end
+// of a piece that is not its document's last), per piece 24 B of the table and 16 B of offsets, per row 16 B of
+// row_first, 24 B of its last piece and 4 B of length, per lane at most log2(pieces of its row) probes of 4 B in 24-byte
+// entries that neighbouring lanes share.
+struct PackFitJob {
+    PackAuxJob a;
+    const PackFitPiece *pieces;
+    const unsigned long long *row_first;     // n_rows + 1
+};
+
+// the piece the walk stands in: table entry p, which ends before column `end`; its document has T elements, tokens from
+// src0 on
+struct FitAt {
+    uint64_t p, d, k0, src0, T;
+    uint32_t col0, end;
+};
+
+__device__ __forceinline__ void fit_enter(const PackJob &j, const PackFitPiece *__restrict__ pieces, FitAt *f) {
+    const PackFitPiece pc = pieces[f->p];
+    f->d = pc.d;
+    f->k0 = pc.k0;
+    f->col0 = pc.col0;
+    f->end = pc.col0 + pc.size;                                  // (<= seq_len)
+    f->src0 = j.doc_off[pc.d];
+    f->T = j.doc_off[pc.d + 1] - f->src0 + j.nb + j.ne;
+}
+
+template <int IN, int OUT>
+__global__ __launch_bounds__(kPackThreads) void k_pack_fit(PackFitJob fj) {
+    const PackJob &j = fj.a.j;
+    const bool want_lab = fj.a.labels != nullptr;
+    const uint32_t ign_lo = (uint32_t)fj.a.ignore, ign_hi = (uint32_t)(fj.a.ignore >> 32);
+    const uint64_t n_groups = (j.n_out + kAuxCells - 1) / kAuxCells;
+    for (uint64_t g = (uint64_t)blockIdx.x * kPackThreads + threadIdx.x; g < n_groups;
+         g += (uint64_t)gridDim.x * kPackThreads) {
+        const uint64_t c0 = g * kAuxCells;
+        const uint32_t cnt = j.n_out - c0 < kAuxCells ? (uint32_t)(j.n_out - c0) : kAuxCells;
+        uint64_t row = c0 / j.seq_len;
+        uint32_t col = (uint32_t)(c0 - row * j.seq_len);
+        uint64_t row_end = fj.row_first[row + 1];                // the row's pieces are [.., row_end)
+        FitAt f;
+        f.p = fj.row_first[row];                                 // pieces[p].col0 <= col < pieces[hi].col0
+        for (uint64_t hi = row_end; hi - f.p > 1;) {
+            const uint64_t mid = f.p + (hi - f.p) / 2;
+            if (fj.pieces[mid].col0 <= col) f.p = mid;
+            else hi = mid;
+        }
+        fit_enter(j, fj.pieces, &f);
+        auto element = [&](uint64_t i) -> uint32_t {             // element i < T of the document
+            if (j.nb && i == 0) return j.bos;
+            if (j.ne && i == f.T - 1) return j.eos;
+            return pack_read<IN>(j.tok, f.src0 + (i - j.nb));
+        };
+        uint32_t id[kAuxCells], lab[kAuxCells], ps[kAuxCells], sg[kAuxCells];
+        uint32_t ign_mask = 0, ahead = 0;                        // ahead: the element read as the cell before's label
+        bool have_ahead = false;
+#pragma unroll
+        for (uint32_t e = 0; e < kAuxCells; ++e) {
+            id[e] = j.pad; lab[e] = ign_lo; ps[e] = 0; sg[e] = 0;
+            ign_mask |= 1u << e;
+            if (e >= cnt) continue;
+            if (col == 0 && j.len) {
+                const PackFitPiece last = fj.pieces[row_end - 1];
+                j.len[row] = last.col0 + last.size;
+            }
+            if (col < f.end) {                                   // (col >= col0: the walk entered the piece there)
+                const uint64_t k = f.k0 + (col - f.col0);
+                id[e] = have_ahead ? ahead : element(k);
+                have_ahead = false;
+                if (want_lab && k + 1 < f.T) {
+                    ahead = element(k + 1);
+                    have_ahead = col + 1 < f.end;
+                    lab[e] = ahead;
+                    ign_mask &= ~(1u << e);
+                }
+                ps[e] = (uint32_t)k;
+                sg[e] = (uint32_t)f.d + 1u;
+            }
+            ++col;
+            if (col == j.seq_len) {
+                col = 0;
+                ++row;
+                if (e + 1 < cnt) {                               // (another cell of the group: the row exists)
+                    f.p = row_end;
+                    row_end = fj.row_first[row + 1];
+                    fit_enter(j, fj.pieces, &f);
+                }
+            } else if (col == f.end && f.p + 1 < row_end) {
+                ++f.p;
+                fit_enter(j, fj.pieces, &f);
+            }
+        }
+        aux_store_ids<OUT>(j.out, c0, cnt, id, 0u, 0u);
+        if (want_lab) aux_store_ids<OUT>(fj.a.labels, c0, cnt, lab, ign_mask, ign_hi);
+        if (fj.a.pos) aux_store32(fj.a.pos, c0, cnt, ps);
+        if (fj.a.seg) aux_store32(fj.a.seg, c0, cnt, sg);
+    }
+}
+
 #define PCHK(expr) MBPE_HIP_CHECK(expr, true)
 
 uint32_t pack_grid(const void *out, uint64_t n_out, uint32_t out_bits) {
@@ -578,6 +691,11 @@ void launch_pack_windows(hipStream_t stream, const PackWinJob &wj) {
     hipLaunchKernelGGL((k_pack_windows<IN, OUT>), dim3(aux_grid(wj.a.j.n_out)), dim3(kPackThreads), 0, stream, wj);
 }
 
+template <int IN, int OUT>
+void launch_pack_fit(hipStream_t stream, const PackFitJob &fj) {
+    hipLaunchKernelGGL((k_pack_fit<IN, OUT>), dim3(aux_grid(fj.a.j.n_out)), dim3(kPackThreads), 0, stream, fj);
+}
+
 // device time of the calling thread's latest one-shot pack or unpack kernel (mbpe_pack_kernel_ms)
 thread_local float g_pack_ms = 0.f;
 
@@ -599,7 +717,8 @@ struct OneShot : DevQueue {
 
 int pack_run(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
              const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec &spec, void *ids_out, uint64_t n_rows,
-             int out_on_device, uint32_t *len_out, const mbpe_pack_aux *aux, const mbpe_pack_window *win = nullptr) {
+             int out_on_device, uint32_t *len_out, const mbpe_pack_aux *aux, const mbpe_pack_window *win = nullptr,
+             const struct mbpe_pack_fit *fit = nullptr, const PackFitPlan *plan = nullptr) {
     int rc = find_device(device_id);
     if (rc != MBPE_OK) return rc;
     OneShot dev;
@@ -631,11 +750,19 @@ int pack_run(int device_id, const void *tokens, uint64_t n_tokens, uint32_t toke
         if (rc == MBPE_OK && win->row_doc && !out_on_device) { rc = dev.alloc(&p, n_rows * 4, nullptr); d_win.row_doc = static_cast<uint32_t *>(p); }
         if (rc == MBPE_OK && win->row_tok0 && !out_on_device) { rc = dev.alloc(&p, n_rows * 8, nullptr); d_win.row_tok0 = static_cast<uint64_t *>(p); }
     }
+    // the plan of a fit call: the piece table and row_first
+    void *d_pieces = nullptr, *d_row_first = nullptr;
+    if (rc == MBPE_OK && fit) {
+        rc = dev.alloc(&d_pieces, pack_fit_piece_bytes(*plan), plan->pieces.data());
+        if (rc == MBPE_OK) rc = dev.alloc(&d_row_first, (n_rows + 1) * 8, plan->row_first.data());
+    }
     if (rc != MBPE_OK) return rc;
     const PackSrc src = {d_tok, static_cast<const unsigned long long *>(d_off), n_docs, n_tokens, token_bits};
     const PackDst dst = {d_ids, static_cast<uint32_t *>(d_len), n_rows};
     PCHK(hipEventRecord(dev.ev0, dev.stream));
-    if (win) {
+    if (fit) {
+        pack_launch_fit(dev.stream, src, spec, dst, d_aux, d_pieces, static_cast<const unsigned long long *>(d_row_first));
+    } else if (win) {
         unsigned long long *row_start = static_cast<unsigned long long *>(d_row_start);
         pack_launch_win_rows(dev.stream, src.doc_off, n_docs, spec, d_win, row_start);
         pack_launch_windows(dev.stream, src, spec, dst, d_aux, d_win, row_start);
@@ -653,7 +780,7 @@ int pack_run(int device_id, const void *tokens, uint64_t n_tokens, uint32_t toke
         if (win && win->row_tok0) PCHK(hipMemcpyAsync(win->row_tok0, d_win.row_tok0, n_rows * 8, hipMemcpyDeviceToHost, dev.stream));
         PCHK(hipStreamSynchronize(dev.stream));
     }
-    return MBPE_OK;
+    return fit ? pack_fit_doc_out(dev.stream, *fit, *plan, out_on_device) : MBPE_OK;
 }
 
 int unpack_run(int device_id, const void *ids, uint64_t n_rows, uint32_t seq_len, uint32_t id_bits, int ids_on_device,
@@ -853,6 +980,58 @@ int pack_window_rows(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pa
     return rc == MBPE_OK ? MBPE_OK : fail(rc, msg);
 }
 
+uint64_t pack_fit_piece_bytes(const PackFitPlan &plan) { return plan.pieces.size() * sizeof(PackFitPiece); }
+
+void pack_launch_fit(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst,
+                     const mbpe_pack_aux &aux, const void *pieces, const unsigned long long *row_first) {
+    PackFitJob fj = {};
+    fj.a = {pack_job(src, spec, dst), aux.labels, aux.pos, aux.seg, (unsigned long long)aux.ignore_label};
+    fj.pieces = static_cast<const PackFitPiece *>(pieces);
+    fj.row_first = row_first;
+    if (src.bits == 16) {
+        if (spec.out_bits == 16) launch_pack_fit<16, 16>(stream, fj);
+        else if (spec.out_bits == 32) launch_pack_fit<16, 32>(stream, fj);
+        else launch_pack_fit<16, 64>(stream, fj);
+    } else {
+        if (spec.out_bits == 32) launch_pack_fit<32, 32>(stream, fj);
+        else launch_pack_fit<32, 64>(stream, fj);
+    }
+}
+
+int pack_check_fit(const mbpe_pack_spec *spec, uint32_t token_bits, const mbpe_pack_aux *aux, const struct mbpe_pack_fit *fit,
+                   uint64_t n_docs, const void *ids_out, int out_on_device) {
+    int rc = pack_check_spec(spec, token_bits);
+    if (rc != MBPE_OK) return rc;
+    if (!fit) return fail(MBPE_ERR_ARG, "NULL pack fit");
+    if (spec->layout != MBPE_PACK_PACKED)
+        return fail(MBPE_ERR_ARG, "fit goes with MBPE_PACK_PACKED, pad_left 0 and trunc_left 0 only");
+    if ((rc = pack_check_aux(*spec, aux, nullptr, n_docs, ids_out, out_on_device)) != MBPE_OK) return rc;
+    if (ids_out && out_on_device && ((uint64_t)(uintptr_t)fit->doc_row % 8 || (uint64_t)(uintptr_t)fit->doc_col % 4))
+        return fail(MBPE_ERR_ARG, "doc_row or doc_col in device memory is not aligned to its elements");
+    return MBPE_OK;
+}
+
+int pack_fit_make(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec &spec, PackFitPlan *plan) {
+    const char *msg = "";
+    const int rc = pack_fit_plan(doc_tok_off, n_docs, spec.seq_len,
+                                 (spec.bos_id != MBPE_NO_TOKEN) + (spec.eos_id != MBPE_NO_TOKEN), plan, &msg);
+    return rc == MBPE_OK ? MBPE_OK : fail(rc, msg);
+}
+
+int pack_fit_doc_out(hipStream_t stream, const struct mbpe_pack_fit &fit, const PackFitPlan &plan, int out_on_device) {
+    const uint64_t n_docs = plan.doc_row.size();
+    if (!n_docs) return MBPE_OK;
+    if (!out_on_device) {
+        if (fit.doc_row) std::copy(plan.doc_row.begin(), plan.doc_row.end(), fit.doc_row);
+        if (fit.doc_col) std::copy(plan.doc_col.begin(), plan.doc_col.end(), fit.doc_col);
+        return MBPE_OK;
+    }
+    if (fit.doc_row) PCHK(hipMemcpyAsync(fit.doc_row, plan.doc_row.data(), n_docs * 8, hipMemcpyHostToDevice, stream));
+    if (fit.doc_col) PCHK(hipMemcpyAsync(fit.doc_col, plan.doc_col.data(), n_docs * 4, hipMemcpyHostToDevice, stream));
+    if (fit.doc_row || fit.doc_col) PCHK(hipStreamSynchronize(stream));
+    return MBPE_OK;
+}
+
 int pack_check_aux(const mbpe_pack_spec &spec, const mbpe_pack_aux *aux, const uint64_t *doc_tok_off, uint64_t n_docs,
                    const void *ids_out, int out_on_device) {
     if (!aux) return fail(MBPE_ERR_ARG, "NULL pack aux");
@@ -990,6 +1169,97 @@ int mbpe_pack_cu_seqlens(const uint64_t *doc_tok_off, uint64_t n_docs, const mbp
     *n_seqs_out = n_seqs;                                        // (also when cap_seqs is too small)
     *max_seqlen_out = longest;
     return rc == MBPE_OK ? MBPE_OK : fail(rc, msg);
+}
+
+// what the two host-only fit calls check alike: the spec (for tokens as wide as its ids allow), the layout, the offsets
+static int fit_host_check(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec) {
+    int rc = pack_check_spec(spec, spec->out_bits == 16 ? 16 : 32);
+    if (rc != MBPE_OK) return rc;
+    if (spec->layout != MBPE_PACK_PACKED)
+        return fail(MBPE_ERR_ARG, "fit goes with MBPE_PACK_PACKED, pad_left 0 and trunc_left 0 only");
+    if (n_docs >> 40) return fail(MBPE_ERR_ARG, "more than 2^40 tokens or documents");
+    rc = mbpe_host::check_doc_tok_off(doc_tok_off, n_docs, doc_tok_off[n_docs]);
+    if (rc == MBPE_OK && doc_tok_off[n_docs] >> 40) rc = fail(MBPE_ERR_ARG, "more than 2^40 tokens or documents");
+    return rc;
+}
+
+int mbpe_pack_fit_plan(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, uint32_t *len_out,
+                       uint64_t cap_rows, uint64_t *n_rows_out, uint64_t *doc_row_out, uint32_t *doc_col_out) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (!doc_tok_off || !spec || !n_rows_out) return fail(MBPE_ERR_ARG, "mbpe_pack_fit_plan: NULL argument");
+    int rc = fit_host_check(doc_tok_off, n_docs, spec);
+    if (rc != MBPE_OK) return rc;
+    try {
+        PackFitPlan plan;
+        if ((rc = pack_fit_make(doc_tok_off, n_docs, *spec, &plan)) != MBPE_OK) return rc;
+        *n_rows_out = plan.n_rows;
+        if (len_out && cap_rows < plan.n_rows) return fail(MBPE_ERR_ARG, "len_out too small");
+        if (len_out) std::copy(plan.len.begin(), plan.len.end(), len_out);
+        if (doc_row_out) std::copy(plan.doc_row.begin(), plan.doc_row.end(), doc_row_out);
+        if (doc_col_out) std::copy(plan.doc_col.begin(), plan.doc_col.end(), doc_col_out);
+        return MBPE_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(MBPE_ERR_OOM, "mbpe_pack_fit_plan: host allocation failed");
+    }
+}
+
+int mbpe_pack_fit_cu_seqlens(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, int32_t *cu_out,
+                             uint64_t cap_seqs, uint64_t *n_seqs_out, uint32_t *max_seqlen_out) {
+    if (n_seqs_out) *n_seqs_out = 0;
+    if (max_seqlen_out) *max_seqlen_out = 0;
+    if (!doc_tok_off || !spec || !n_seqs_out || !max_seqlen_out)
+        return fail(MBPE_ERR_ARG, "mbpe_pack_fit_cu_seqlens: NULL argument");
+    int rc = fit_host_check(doc_tok_off, n_docs, spec);
+    if (rc != MBPE_OK) return rc;
+    try {
+        PackFitPlan plan;
+        if ((rc = pack_fit_make(doc_tok_off, n_docs, *spec, &plan)) != MBPE_OK) return rc;
+        const char *msg = "";
+        uint64_t n_seqs = 0;
+        uint32_t longest = 0;
+        rc = pack_fit_cu_seqlens(plan, spec->seq_len, cu_out, cap_seqs, &n_seqs, &longest, &msg);
+        *n_seqs_out = n_seqs;                                    // (also when cap_seqs is too small)
+        *max_seqlen_out = longest;
+        return rc == MBPE_OK ? MBPE_OK : fail(rc, msg);
+    } catch (const std::bad_alloc &) {
+        return fail(MBPE_ERR_OOM, "mbpe_pack_fit_cu_seqlens: host allocation failed");
+    }
+}
+
+int mbpe_pack_fit(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
+                  const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
+                  uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out, const mbpe_pack_aux *aux,
+                  const struct mbpe_pack_fit *fit) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (!n_rows_out || !doc_tok_off || !spec || !aux || !fit || (!tokens && n_tokens))
+        return fail(MBPE_ERR_ARG, "mbpe_pack_fit: NULL argument");
+    int rc = pack_check_fit(spec, token_bits, aux, fit, n_docs, ids_out, out_on_device);
+    if (rc == MBPE_OK) rc = mbpe_host::check_doc_tok_off(doc_tok_off, n_docs, n_tokens);
+    if (rc != MBPE_OK) return rc;
+    if (n_tokens >> 40 || n_docs >> 40) return fail(MBPE_ERR_ARG, "more than 2^40 tokens or documents");
+    if ((rc = pack_check_aux(*spec, aux, doc_tok_off, n_docs, nullptr, 0)) != MBPE_OK) return rc;   // (pos: every T_d)
+    try {
+        PackFitPlan plan;
+        if ((rc = pack_fit_make(doc_tok_off, n_docs, *spec, &plan)) != MBPE_OK) return rc;
+        const uint64_t n_rows = plan.n_rows;
+        *n_rows_out = n_rows;
+        if (!ids_out) return MBPE_OK;                            // the query
+        if (cap_rows < n_rows) return fail(MBPE_ERR_ARG, "ids_out too small");
+        if (out_on_device && (uint64_t)(uintptr_t)len_out % 4)
+            return fail(MBPE_ERR_ARG, "len_out is not aligned to its elements");
+        if (n_rows == 0) {                                       // no document has an element: doc_row says so
+            if (!out_on_device || !n_docs || (!fit->doc_row && !fit->doc_col))
+                return pack_fit_doc_out(nullptr, *fit, plan, 0);
+            if ((rc = find_device(device_id)) != MBPE_OK) return rc;
+            OneShot dev;
+            if ((rc = dev.open(device_id)) != MBPE_OK) return rc;
+            return pack_fit_doc_out(dev.stream, *fit, plan, 1);
+        }
+        return pack_run(device_id, tokens, n_tokens, token_bits, tokens_on_device, doc_tok_off, n_docs, *spec, ids_out,
+                        n_rows, out_on_device, len_out, aux, nullptr, fit, &plan);
+    } catch (const std::bad_alloc &) {
+        return fail(MBPE_ERR_OOM, "mbpe_pack_fit: host allocation failed");
+    }
 }
 
 int mbpe_unpack_tokens(int device_id, const void *ids, uint64_t n_rows, uint32_t seq_len, uint32_t id_bits,

@@ -930,14 +930,18 @@ int Tokenizer::encode_batch_packed(const char *text, const uint64_t *doc_off, ui
                                    const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
                                    uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out,
                                    const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out, bool device_split,
-                                   const mbpe_pack_window *win) {
+                                   const mbpe_pack_window *win, const struct mbpe_pack_fit *fit) {
     if (device_split) {
         DeviceSplit ds;
         int rc = split_on_device(text, doc_off, n_docs, verbose, device, &ds);
         if (rc != MBPE_OK) return rc;
         mbpe_encoder *enc = device_encoder(device);
         uint64_t n_tokens = 0;
-        rc = win ? mbpe_encoder_encode_batch_endmask_windows(enc, ds.d_text, ds.n_bytes, ds.d_mask, ds.singles.data(),
+        rc = fit ? mbpe_encoder_encode_batch_endmask_fit(enc, ds.d_text, ds.n_bytes, ds.d_mask, ds.singles.data(),
+                                                         ds.singles.size(), ds.doc_off.data(), n_docs, spec, ids_out,
+                                                         cap_rows, out_on_device, len_out, n_rows_out, &n_tokens, aux,
+                                                         doc_tok_off_out, fit)
+           : win ? mbpe_encoder_encode_batch_endmask_windows(enc, ds.d_text, ds.n_bytes, ds.d_mask, ds.singles.data(),
                                                              ds.singles.size(), ds.doc_off.data(), n_docs, spec, ids_out,
                                                              cap_rows, out_on_device, len_out, n_rows_out, &n_tokens, aux,
                                                              doc_tok_off_out, win)
@@ -956,7 +960,10 @@ int Tokenizer::encode_batch_packed(const char *text, const uint64_t *doc_off, ui
     mbpe_encoder *enc = device_encoder(device);
     uint64_t n_tokens = 0;
     const uint8_t *bytes = reinterpret_cast<const uint8_t *>(buf.data());
-    const int rc = win ? mbpe_encoder_encode_batch_windows(enc, bytes, buf.size(), 0, off.data(), off.size() - 1,
+    const int rc = fit ? mbpe_encoder_encode_batch_fit(enc, bytes, buf.size(), 0, off.data(), off.size() - 1,
+                                                       first_chunk.data(), n_docs, spec, ids_out, cap_rows, out_on_device,
+                                                       len_out, n_rows_out, &n_tokens, aux, doc_tok_off_out, fit)
+                   : win ? mbpe_encoder_encode_batch_windows(enc, bytes, buf.size(), 0, off.data(), off.size() - 1,
                                                            first_chunk.data(), n_docs, spec, ids_out, cap_rows,
                                                            out_on_device, len_out, n_rows_out, &n_tokens, aux,
                                                            doc_tok_off_out, win)
@@ -1625,6 +1632,33 @@ int mbpe_tok_encode_batch_windows_device(mbpe_tokenizer *t, const uint8_t *text,
         return t->t->encode_batch_packed(reinterpret_cast<const char *>(text), doc_off, n_docs, verbose != 0, device_id,
                                          spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
                                          doc_tok_off_out, t->t->encode_split(), win);
+    } catch (const mbpe_host::CodedError &e) {      // mbpe_encoder_create failed: its own code
+        mbpe_host::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        mbpe_host::set_last_error(e.what());
+        return MBPE_ERR_ARG;
+    }
+}
+
+int mbpe_tok_encode_batch_fit_device(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off, uint64_t n_docs,
+                                     int verbose, int device_id, const mbpe_pack_spec *spec, void *ids_out,
+                                     uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                                     uint64_t *n_tokens_out, const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out,
+                                     const struct mbpe_pack_fit *fit) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!t || !n_rows_out || !doc_off || !spec || !aux || !fit || device_id < 0 ||
+        (!text && doc_off[n_docs] > doc_off[0])) {
+        mbpe_host::set_last_error("mbpe_tok_encode_batch_fit_device: NULL argument or negative device");
+        return MBPE_ERR_ARG;
+    }
+    for (uint64_t i = 0; i < n_docs; ++i)
+        if (doc_off[i + 1] < doc_off[i]) { mbpe_host::set_last_error("doc_off must be ascending"); return MBPE_ERR_ARG; }
+    try {
+        return t->t->encode_batch_packed(reinterpret_cast<const char *>(text), doc_off, n_docs, verbose != 0, device_id,
+                                         spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
+                                         doc_tok_off_out, t->t->encode_split(), nullptr, fit);
     } catch (const mbpe_host::CodedError &e) {      // mbpe_encoder_create failed: its own code
         mbpe_host::set_last_error(e.what());
         return e.code;

@@ -81,12 +81,14 @@ public:
                       bool device_split, std::vector<Token> *tokens, std::vector<uint64_t> *ranges,
                       std::vector<uint64_t> *doc_tok_off);
     // the same documents as one id matrix (mbpe_encoder_encode_batch; with aux, mbpe_encoder_encode_batch_aux; with
-    // win, mbpe_encoder_encode_batch_windows): spec, ids_out .. doc_tok_off_out go to it as they are, its code is returned
+    // win, mbpe_encoder_encode_batch_windows; with fit, mbpe_encoder_encode_batch_fit): spec, ids_out .. doc_tok_off_out
+    // go to it as they are, its code is returned
     int encode_batch_packed(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
                             const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
                             uint32_t *len_out, uint64_t *n_rows_out, uint64_t *n_tokens_out,
                             const mbpe_pack_aux *aux = nullptr, uint64_t *doc_tok_off_out = nullptr,
-                            bool device_split = false, const mbpe_pack_window *win = nullptr);
+                            bool device_split = false, const mbpe_pack_window *win = nullptr,
+                            const struct mbpe_pack_fit *fit = nullptr);
     // How often every token id is used (mbpe_tok_count_tokens): the documents are split as in encode_batch_flat and what
     // encode would return for each is counted `repeat` times into a table the tokenizer keeps on the host, of
     // count_ids() = max(256 + merges, largest special id + 1) entries.  device < 0: the host loop over encode();

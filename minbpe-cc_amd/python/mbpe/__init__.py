@@ -51,6 +51,8 @@ EXPORTS = [
     "mbpe_pack_windows", "mbpe_encoder_encode_batch_windows", "mbpe_encoder_encode_batch_endmask_windows",
     "mbpe_token_counts", "mbpe_token_counts_kernel_ms", "mbpe_encoder_count", "mbpe_encoder_count_endmask",
     "mbpe_encoder_counts", "mbpe_encoder_counts_reset",
+    "mbpe_pack_fit", "mbpe_pack_fit_plan", "mbpe_pack_fit_cu_seqlens", "mbpe_encoder_encode_batch_fit",
+    "mbpe_encoder_encode_batch_endmask_fit",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -65,7 +67,7 @@ TOK_EXPORTS = [
     "mbpe_tok_train_pieces_finish", "mbpe_tok_train_pieces_abort", "mbpe_tok_set_train_limits",
     "mbpe_tok_train_pieces_export_size", "mbpe_tok_train_pieces_export", "mbpe_tok_train_pieces_merge",
     "mbpe_tok_encode_batch_windows_device", "mbpe_tok_count_tokens", "mbpe_tok_token_counts",
-    "mbpe_tok_token_counts_reset",
+    "mbpe_tok_token_counts_reset", "mbpe_tok_encode_batch_fit_device",
 ]
 
 
@@ -124,6 +126,12 @@ class PackWindow(ctypes.Structure):
         ("stride", ctypes.c_uint32), ("score_once", ctypes.c_uint32), ("row_doc", ctypes.c_void_p),
         ("row_tok0", ctypes.c_void_p),
     ]
+
+
+class PackFit(ctypes.Structure):
+    """struct mbpe_pack_fit (include/mbpe.h): where the cell of every document's last piece goes (NULL: not asked
+    for)."""
+    _fields_ = [("doc_row", ctypes.c_void_p), ("doc_col", ctypes.c_void_p)]
 
 
 _ID_DTYPES = {16: np.uint16, 32: np.uint32, 64: np.uint64}
@@ -226,6 +234,11 @@ def lib():
     L.mbpe_pack_windows.argtypes = L.mbpe_pack_tokens_aux.argtypes + [vp]
     L.mbpe_encoder_encode_batch_windows.argtypes = L.mbpe_encoder_encode_batch_aux.argtypes + [vp]
     L.mbpe_tok_encode_batch_windows_device.argtypes = L.mbpe_tok_encode_batch_aux_device.argtypes + [vp]
+    L.mbpe_pack_fit.argtypes = L.mbpe_pack_tokens_aux.argtypes + [vp]
+    L.mbpe_pack_fit_plan.argtypes = [vp, u64, vp, vp, u64, vp, vp, vp]
+    L.mbpe_pack_fit_cu_seqlens.argtypes = L.mbpe_pack_cu_seqlens.argtypes
+    L.mbpe_encoder_encode_batch_fit.argtypes = L.mbpe_encoder_encode_batch_aux.argtypes + [vp]
+    L.mbpe_tok_encode_batch_fit_device.argtypes = L.mbpe_tok_encode_batch_aux_device.argtypes + [vp]
     L.mbpe_tok_decode_padded_device.argtypes = [vp, vp, u64, u32, vp, i32, i32, vp, u64, vp, vp]
     L.mbpe_tok_encode_batch_device.argtypes = [vp, vp, vp, u64, i32, i32, vp, u64, vp, vp]
     L.mbpe_decoder_create.argtypes = [i32, vp, u32, vp, vp, vp, u32, ctypes.POINTER(vp)]
@@ -267,6 +280,7 @@ def lib():
     L.mbpe_encoder_encode_batch_endmask.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, u64, i32, vp, vp, vp,
                                                     vp, vp]
     L.mbpe_encoder_encode_batch_endmask_windows.argtypes = L.mbpe_encoder_encode_batch_endmask.argtypes + [vp]
+    L.mbpe_encoder_encode_batch_endmask_fit.argtypes = L.mbpe_encoder_encode_batch_endmask.argtypes + [vp]
     L.mbpe_tok_set_encode_split.argtypes = [vp, i32]
     L.mbpe_tok_set_split_unicode.argtypes = [vp, i32]
     L.mbpe_tok_set_train_dedup.argtypes = [vp, i32]
@@ -653,6 +667,116 @@ def pack_windows(tokens, doc_tok_off, seq_len, stride, score_once=False, out_bit
                     (labels_ptr, pos_ptr, seg_ptr, row_doc_ptr, row_tok0_ptr))
 
 
+def _fit_spec(seq_len, out_bits=32, pad_id=0, bos_id=None, eos_id=None):
+    return pack_spec(seq_len, "packed", out_bits, pad_id, bos_id, eos_id)
+
+
+def pack_fit_plan(doc_tok_off, seq_len, bos_id=None, eos_id=None):
+    """mbpe_pack_fit_plan: where best-fit packing puts documents of these token offsets into rows of seq_len -> a
+    dict with "n_rows", "lengths" (uint32, the cells used per row), "doc_row" (uint64) and "doc_col" (uint32): the cell
+    of the first element of every document's last piece (2^64 - 1 and 0 for a document without elements).  Host
+    arithmetic alone: needs no device."""
+    spec = _fit_spec(seq_len, bos_id=bos_id, eos_id=eos_id)
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    n_docs = len(off) - 1
+    n_rows = ctypes.c_uint64()
+    head = (off.ctypes.data, n_docs, ctypes.byref(spec))
+    # one plan, not a query and a plan: there are no more rows than pieces.  (A count beyond reason -- offsets that
+    # descend wrap to one -- goes to the query, which refuses what the library refuses)
+    T = np.diff(off) + np.uint64((bos_id is not None) + (eos_id is not None))
+    cap = int((T // np.uint64(max(seq_len, 1))).sum() + np.count_nonzero(T)) if n_docs > 0 else 0
+    if cap >> 32:
+        _check(lib().mbpe_pack_fit_plan(*head, None, 0, ctypes.byref(n_rows), None, None))
+        cap = n_rows.value
+    lengths = np.zeros(cap, dtype=np.uint32)
+    doc_row, doc_col = np.zeros(n_docs, dtype=np.uint64), np.zeros(n_docs, dtype=np.uint32)
+    ptr = lambda a: a.ctypes.data if len(a) else None
+    _check(lib().mbpe_pack_fit_plan(*head, ptr(lengths), len(lengths), ctypes.byref(n_rows), ptr(doc_row), ptr(doc_col)))
+    return {"n_rows": n_rows.value, "lengths": lengths[:n_rows.value], "doc_row": doc_row, "doc_col": doc_col}
+
+
+def pack_fit_cu_seqlens(doc_tok_off, seq_len, bos_id=None, eos_id=None):
+    """mbpe_pack_fit_cu_seqlens: the boundaries of the runs of equal (row, segment) in the flattened matrix of pack_fit,
+    pad runs included, from 0 to n_rows * seq_len -> (int32 array of n_seqs + 1 entries, max_seqlen).  Host arithmetic
+    alone: needs no device."""
+    spec = _fit_spec(seq_len, bos_id=bos_id, eos_id=eos_id)
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    n_seqs, longest = ctypes.c_uint64(), ctypes.c_uint32()
+    head = (off.ctypes.data, len(off) - 1, ctypes.byref(spec))
+    _check(lib().mbpe_pack_fit_cu_seqlens(*head, None, 0, ctypes.byref(n_seqs), ctypes.byref(longest)))
+    cu = np.zeros(n_seqs.value + 1, dtype=np.int32)
+    _check(lib().mbpe_pack_fit_cu_seqlens(*head, cu.ctypes.data, n_seqs.value, ctypes.byref(n_seqs), ctypes.byref(longest)))
+    return cu, longest.value
+
+
+class _FitCall(_AuxCall):
+    """What the *_fit calls share: the mbpe_pack_aux and the mbpe_pack_fit of a call, the query for the row count, and
+    the dict it returns."""
+
+    def __init__(self, spec, labels, positions, segments, cu_seqlens, ignore_label, doc_row, doc_col):
+        super().__init__(spec, labels, positions, segments, cu_seqlens, ignore_label)
+        self.want_docs = (doc_row, doc_col)
+
+    def cu_seqlens(self, doc_tok_off):
+        none = lambda t: None if t == NO_TOKEN else t
+        return pack_fit_cu_seqlens(doc_tok_off, self.spec.seq_len, none(self.spec.bos_id), none(self.spec.eos_id))
+
+    def run(self, fn, head, tail, n_docs, doc_tok_off, out_ptr, len_ptr, cap_rows, ptrs):
+        """fn(*head, ids, cap_rows, on_device, len, *tail(n_rows, aux, fit)): with out_ptr= into device memory -> the
+        row count (with cu_seqlens: and the list and max_seqlen); else a query, host arrays of that size and the call
+        -> the dict.  doc_tok_off(): the documents' token offsets once fn has run."""
+        n_rows = ctypes.c_uint64()
+        if out_ptr is not None:
+            aux, fit = self.device(*ptrs[:3]), PackFit(ptrs[3] or None, ptrs[4] or None)
+            _check(fn(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail(n_rows, aux, fit)))
+            return (n_rows.value,) + self.cu_seqlens(doc_tok_off()) if self.cu else n_rows.value
+        aux, fit = self.device(None, None, None), PackFit(None, None)
+        _check(fn(*head, None, 0, 0, None, *tail(n_rows, aux, fit)))
+        n = n_rows.value
+        ids, lengths = _matrix(n, self.spec)
+        aux, arrays = self.host(n)
+        if self.want_docs[0]:
+            arrays["doc_row"] = np.zeros(n_docs, dtype=np.uint64)
+        if self.want_docs[1]:
+            arrays["doc_col"] = np.zeros(n_docs, dtype=np.uint32)
+        ptr = lambda name: arrays[name].ctypes.data if name in arrays and n_docs else None
+        fit = PackFit(ptr("doc_row"), ptr("doc_col"))
+        if n or n_docs:
+            # (no row, yet documents: doc_row says that they are empty; ids_out must not be NULL, which is the query)
+            where = ids if n else np.zeros(1, dtype=ids.dtype)
+            _check(fn(*head, where.ctypes.data, n, 0, lengths.ctypes.data if n else None, *tail(n_rows, aux, fit)))
+        return self.result(ids, lengths, arrays, doc_tok_off())
+
+
+def pack_fit(tokens, doc_tok_off, seq_len, out_bits=32, pad_id=0, bos_id=None, eos_id=None, device=0, tokens_ptr=None,
+             n_tokens=None, token_bits=None, out_ptr=None, len_ptr=None, cap_rows=None, labels=False, positions=False,
+             segments=False, cu_seqlens=False, ignore_label=-100, labels_ptr=None, pos_ptr=None, seg_ptr=None,
+             doc_row=False, doc_col=False, doc_row_ptr=None, doc_col_ptr=None):
+    """mbpe_pack_fit: best-fit packing.  Every document [bos] doc [eos] stays whole and shares its row with others;
+    only a document longer than seq_len is cut, into full rows of its own and one tail.  The pieces are placed by size
+    descending into the row with the least room that still holds them, so padding stays small and lies at the right
+    end of a row.  Labels, positions and segments as for layout "packed" of pack_tokens_aux: use them, or cu_seqlens
+    (pad runs are sequences of their own there), to keep attention inside a document.  -> the dict of pack_tokens_aux
+    plus "doc_row" (uint64) and "doc_col" (uint32) when asked for: the cell of the first element of each document's
+    last piece.  With out_ptr= the outputs go to device memory (doc_row_ptr= / doc_col_ptr= beside the pointers of
+    pack_tokens_aux) and the row count is returned -- (row count, cu_seqlens, max_seqlen) with cu_seqlens=True."""
+    spec = _fit_spec(seq_len, out_bits, pad_id, bos_id, eos_id)
+    call = _FitCall(spec, labels, positions, segments, cu_seqlens, ignore_label, doc_row, doc_col)
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    if tokens_ptr is None:
+        t = np.ascontiguousarray(tokens)
+        if t.dtype not in (np.dtype(np.uint16), np.dtype(np.uint32)):
+            t = t.astype(np.uint32)
+        t = t.reshape(-1)
+        tp, n_tokens, token_bits, on_dev = (t.ctypes.data if len(t) else None), len(t), t.dtype.itemsize * 8, 0
+    else:
+        tp, on_dev = _ptr(tokens_ptr), 1
+    head = (device, tp, n_tokens, token_bits, on_dev, off.ctypes.data, len(off) - 1, ctypes.byref(spec))
+    tail = lambda n_rows, aux, fit: (ctypes.byref(n_rows), ctypes.byref(aux), ctypes.byref(fit))
+    return call.run(lib().mbpe_pack_fit, head, tail, len(off) - 1, lambda: off, out_ptr, len_ptr, cap_rows,
+                    (labels_ptr, pos_ptr, seg_ptr, doc_row_ptr, doc_col_ptr))
+
+
 def unpack_tokens(ids, lengths, dtype=np.uint32, device=0, ids_ptr=None, len_ptr=None, shape=None, id_bits=None,
                   out_ptr=None, cap=0):
     """mbpe_unpack_tokens: a right-padded matrix ids [n_rows, seq_len] (uint16 / uint32 / uint64) and its lengths ->
@@ -938,6 +1062,49 @@ class Encoder:
                                          doc_tok_off.ctypes.data, ctypes.byref(win))
         out = call.run(lib().mbpe_encoder_encode_batch_endmask_windows, head, tail, out_ptr, len_ptr, cap_rows,
                        (labels_ptr, pos_ptr, seg_ptr, row_doc_ptr, row_tok0_ptr))
+        self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
+        return out
+
+    def encode_batch_fit(self, texts_or_buffer, chunk_off=None, doc_chunk_off=None, *, seq_len, out_bits=32, pad_id=0,
+                         bos_id=None, eos_id=None, text_ptr=None, n_bytes=None, out_ptr=None, len_ptr=None,
+                         cap_rows=None, labels=False, positions=False, segments=False, cu_seqlens=False,
+                         ignore_label=-100, labels_ptr=None, pos_ptr=None, seg_ptr=None, doc_row=False, doc_col=False,
+                         doc_row_ptr=None, doc_col_ptr=None):
+        """encode_batch_aux for the fit layout (mbpe_encoder_encode_batch_fit): the documents of encode_batch, the
+        keywords and the result of pack_fit.  The plan is made on the host from the documents' token offsets, which
+        cross after the passes; the host form asks for the row count first, which runs the passes.  The offsets of
+        the call: self.doc_tok_off."""
+        spec = _fit_spec(seq_len, out_bits, pad_id, bos_id, eos_id)
+        call = _FitCall(spec, labels, positions, segments, cu_seqlens, ignore_label, doc_row, doc_col)
+        head, keep = self._batch_head(texts_or_buffer, chunk_off, doc_chunk_off, text_ptr, n_bytes, spec)
+        n_tok = ctypes.c_uint64()
+        doc_tok_off = np.zeros(len(keep[-1]), dtype=np.uint64)
+        tail = lambda n_rows, aux, fit: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
+                                         doc_tok_off.ctypes.data, ctypes.byref(fit))
+        out = call.run(lib().mbpe_encoder_encode_batch_fit, head, tail, len(doc_tok_off) - 1, lambda: doc_tok_off,
+                       out_ptr, len_ptr, cap_rows, (labels_ptr, pos_ptr, seg_ptr, doc_row_ptr, doc_col_ptr))
+        self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
+        return out
+
+    def encode_batch_endmask_fit(self, text_ptr, n_bytes, mask_ptr, singles, doc_off, *, seq_len, out_bits=32, pad_id=0,
+                                 bos_id=None, eos_id=None, out_ptr=None, len_ptr=None, cap_rows=None, labels=False,
+                                 positions=False, segments=False, cu_seqlens=False, ignore_label=-100, labels_ptr=None,
+                                 pos_ptr=None, seg_ptr=None, doc_row=False, doc_col=False, doc_row_ptr=None,
+                                 doc_col_ptr=None):
+        """encode_batch_endmask for the fit layout (mbpe_encoder_encode_batch_endmask_fit): its text, mask, singles
+        and documents, the keywords and the result of pack_fit.  The documents' token offsets: self.doc_tok_off."""
+        spec = _fit_spec(seq_len, out_bits, pad_id, bos_id, eos_id)
+        call = _FitCall(spec, labels, positions, segments, cu_seqlens, ignore_label, doc_row, doc_col)
+        sg = _singles(singles)
+        docs = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        n_tok = ctypes.c_uint64()
+        doc_tok_off = np.zeros(len(docs), dtype=np.uint64)
+        head = (self._h, _ptr(text_ptr), n_bytes, _ptr(mask_ptr), sg.ctypes.data if len(sg) else None, len(sg),
+                docs.ctypes.data, len(docs) - 1, ctypes.byref(spec))
+        tail = lambda n_rows, aux, fit: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
+                                         doc_tok_off.ctypes.data, ctypes.byref(fit))
+        out = call.run(lib().mbpe_encoder_encode_batch_endmask_fit, head, tail, len(docs) - 1, lambda: doc_tok_off,
+                       out_ptr, len_ptr, cap_rows, (labels_ptr, pos_ptr, seg_ptr, doc_row_ptr, doc_col_ptr))
         self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
         return out
 
@@ -2171,6 +2338,34 @@ class Tokenizer:
                                          doc_tok_off.ctypes.data, ctypes.byref(win))
         out = call.run(lib().mbpe_tok_encode_batch_windows_device, head, tail, out_ptr, len_ptr, cap_rows,
                        (labels_ptr, pos_ptr, seg_ptr, row_doc_ptr, row_tok0_ptr))
+        self.doc_tok_off = doc_tok_off
+        return out
+
+    def encode_batch_fit(self, texts, seq_len, out_bits=32, pad_id=0, bos_id=None, eos_id=None, device=0, out_ptr=None,
+                         len_ptr=None, cap_rows=None, labels=False, positions=False, segments=False, cu_seqlens=False,
+                         ignore_label=-100, labels_ptr=None, pos_ptr=None, seg_ptr=None, doc_row=False, doc_col=False,
+                         doc_row_ptr=None, doc_col_ptr=None, device_split=False, order="greedy", dropout=0.0, seed=0,
+                         dedup=False):
+        """encode_batch_aux for the fit layout (mbpe_tok_encode_batch_fit_device): every text split like encode(),
+        encoded, and packed whole into rows of seq_len by best fit; only a text longer than a row is cut -- the
+        keywords and the result of pack_fit ("doc_row" / "doc_col" say where a text's last piece begins, "segments"
+        holds the text's number + 1 in every cell).  The texts' token offsets of the call: self.doc_tok_off."""
+        self._encode_split(device_split, order, dropout, seed, dedup)
+        spec = _fit_spec(seq_len, out_bits, pad_id, bos_id, eos_id)
+        call = _FitCall(spec, labels, positions, segments, cu_seqlens, ignore_label, doc_row, doc_col)
+        parts = [bytes(_u8(t)) for t in texts]
+        doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        if parts:
+            doc_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
+        text = np.frombuffer(b"".join(parts), dtype=np.uint8)
+        n_tok = ctypes.c_uint64()
+        doc_tok_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        head = (self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data, len(parts), 0, device,
+                ctypes.byref(spec))
+        tail = lambda n_rows, aux, fit: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
+                                         doc_tok_off.ctypes.data, ctypes.byref(fit))
+        out = call.run(lib().mbpe_tok_encode_batch_fit_device, head, tail, len(parts), lambda: doc_tok_off, out_ptr,
+                       len_ptr, cap_rows, (labels_ptr, pos_ptr, seg_ptr, doc_row_ptr, doc_col_ptr))
         self.doc_tok_off = doc_tok_off
         return out
 
