@@ -1049,6 +1049,79 @@ MBPE_API int  mbpe_encoder_encode_batch_endmask_fit(mbpe_encoder *e, const uint8
                                                     uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
                                                     uint64_t *doc_tok_off_out, const struct mbpe_pack_fit *fit);
 
+/* ---- fill-in-the-middle ---------------------------------------------------- */
+
+/* The fill-in-the-middle transform of token documents (Bavarian et al., 2022: the "FIM rate" and "SPM rate" of code
+ * models), between encode and pack: it changes every transformed document's length and therefore every row.  A
+ * document is cut at two random points into prefix P, middle M and suffix S and rewritten with three sentinel ids:
+ *   PSM   pre P suf S mid M            SPM   pre suf S mid P M
+ * For document d of a call let t[0 .. L) be its tokens, g = doc_base + d (mod 2^64) and u_i = h(seed, g, i) for
+ * i = 0 .. 3, h the hash of BPE-dropout above (the document number stands where the byte offset stood, the draw's
+ * index where the merged id stood).
+ *   transformed   iff u_0 < rate, L >= max(min_tokens, 1) and (max_tokens == 0 or L <= max_tokens)
+ *   cuts          c1 = (u_1 * (L + 1)) >> 32, c2 = (u_2 * (L + 1)) >> 32 as 64-bit products; a = min(c1, c2),
+ *                 b = max(c1, c2), both in [0, L]: P = t[0:a], M = t[a:b], S = t[b:L]; empty parts are allowed
+ *   mode          SPM iff u_3 < spm, else PSM; either way the document has L + 3 ids afterwards
+ * An untransformed document is copied as it is; an empty one stays empty.  The result is a pure function of (spec, d,
+ * L, tokens): the same call gives the same batch, another seed another epoch, and a corpus fed in batches gets the
+ * result of one big call by passing in doc_base the number of each batch's first document.  bos and eos stay the
+ * packer's business: with eos_id set the end token follows the middle.  Thresholds come from mbpe_dropout_threshold.
+ * Tokens are read as the packers read them (16-bit plain ids, or 32-bit with bit 31 ignored) and written as plain
+ * ids of the same width.
+ * Errors, all before the device is touched: MBPE_ERR_ARG for a threshold above 2^32, max_tokens != 0 with min_tokens >
+ * max_tokens, a sentinel id >= 2^31 - 2, a NULL spec where one is required and bad offsets; MBPE_ERR_VOCAB for a
+ * sentinel id >= 65,536 with 16-bit tokens; MBPE_ERR_ARG, naming the document, for a document of 2^32 - 1 tokens or
+ * more while rate > 0 (where only the device holds the offsets, the plan kernel flags it and the host reads the flag
+ * with the new token count). */
+typedef struct {
+    uint64_t rate;        /* threshold in [0, 2^32]: a document is transformed iff its draw is below it */
+    uint64_t spm;         /* threshold in [0, 2^32]: a transformed document is SPM iff its draw is below it, else PSM */
+    uint64_t seed;
+    uint64_t doc_base;    /* number of the call's first document in the caller's corpus */
+    uint32_t pre_id, suf_id, mid_id;
+    uint32_t min_tokens;  /* documents shorter than max(min_tokens, 1) stay as they are */
+    uint32_t max_tokens;  /* 0: no limit; otherwise documents longer than this stay as they are */
+} mbpe_fim_spec;
+
+/* The plan alone, on the host (never MBPE_ERR_NO_DEVICE): doc_tok_off_out (n_docs + 1, required) = the token offsets
+ * after the transform; mode_out (n_docs bytes, or NULL) = 0 untransformed / 1 PSM / 2 SPM; cut_out (2 per document,
+ * or NULL) = a, b (0, 0 for an untransformed document).  The sentinel ids are checked as for 32-bit tokens. */
+MBPE_API int  mbpe_fim_plan(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_fim_spec *spec,
+                            uint64_t *doc_tok_off_out, uint8_t *mode_out, uint64_t *cut_out);
+
+/* The transform of a flat token stream on HIP device `device_id`, with the conventions of mbpe_pack_tokens: tokens
+ * and tokens_out in host or device memory (tokens_on_device / out_on_device; tokens_out on the device aligned to its
+ * tokens), doc_tok_off (n_docs + 1) and doc_tok_off_out (n_docs + 1, or NULL) on the host.  *n_out = the new token
+ * count.  tokens_out NULL is a query, answered from the host's offsets without a device (doc_tok_off_out is filled);
+ * a cap too small is MBPE_ERR_ARG: nothing is written and n_out is still reported.  tokens_out and doc_tok_off_out are
+ * what mbpe_pack_* and mbpe_decode_batch take as they are.  Kernels (csrc/fim.hip): k_fim_plan, one lane per document,
+ * leaves the plan and the new lengths, a 64-bit scan over spans of 1,024 documents the new offsets; k_fim_gather
+ * writes the new stream, a lane per 16-byte piece of it, every token read and written once.  mbpe_fim_kernel_ms: the
+ * device time of the calling thread's latest such call. */
+MBPE_API int  mbpe_fim_tokens(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits,
+                              int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs,
+                              const mbpe_fim_spec *spec, void *tokens_out, uint64_t cap, int out_on_device,
+                              uint64_t *doc_tok_off_out, uint64_t *n_out);
+MBPE_API int  mbpe_fim_kernel_ms(float *ms_out);
+
+/* The transform as a stage of the encoder's batch calls; spec NULL turns it off.  It holds from the next call on for
+ * every call that packs: mbpe_encoder_encode_batch, _aux, _windows, _fit and the four _endmask batch calls.  The stage
+ * runs between the encode and the pack kernel, into a second flat buffer and offset array the encoder keeps (a repeat
+ * call of no larger size leaves mbpe_encoder_alloc_count as it is); everything downstream -- the rows, the window and
+ * fit plans, labels, pos and seg -- sees the transformed documents.  doc_tok_off_out gives the offsets AFTER the
+ * transform: what the matrices were built from and what the cu_seqlens calls take.  n_tokens_out stays "tokens
+ * encoded", so doc_tok_off_out[n_docs] == n_tokens_out + 3 * (documents transformed).  The sentinel ids are checked
+ * against the width of the tokens a call packs from (16 bits with out_bits 16) when the call is made.  The flat encode
+ * calls, the count calls and mbpe_encode_chunks* are unaffected.  Dropout and "dedup" combine freely: they act before
+ * the stage.  With no spec, and with rate 0, every call launches and allocates exactly what it does without.
+ * mbpe_encoder_kernel_ms and mbpe_encoder_pack_ms include the stage.
+ * mbpe_encoder_fim_info: the plan of the latest batch call, on the host: *n_docs_out = its documents; mode_out
+ * (bytes) and cut_out (2 per document), each NULL or with room for cap_docs documents (fewer than n_docs:
+ * MBPE_ERR_ARG, the count is still reported).  All zero where the stage was off. */
+MBPE_API int  mbpe_encoder_set_fim(mbpe_encoder *e, const mbpe_fim_spec *spec);
+MBPE_API int  mbpe_encoder_fim_info(mbpe_encoder *e, uint8_t *mode_out, uint64_t *cut_out, uint64_t cap_docs,
+                                    uint64_t *n_docs_out);
+
 /* ---- decode on the device ----------------------------------------------- */
 
 /* Tokenizer::decode (Tokenizer.h:725-751) for whole token streams on HIP device `device_id`: per token a byte

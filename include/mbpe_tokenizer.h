@@ -226,6 +226,18 @@ MBPE_API int mbpe_tok_set_encode_order(mbpe_tokenizer *t, int rank_order);
  * or gpt4 (whose matches tile the text).  Otherwise the device split gives another, equally valid, draw. */
 MBPE_API int mbpe_tok_set_encode_dropout(mbpe_tokenizer *t, uint64_t threshold, uint64_t seed);
 
+/* Fill-in-the-middle for the device batch calls that pack (mbpe_tok_encode_batch_packed_device, _aux_device,
+ * _windows_device and _fit_device): spec as for mbpe_encoder_set_fim (mbpe.h, which holds the rule), NULL turns it off.
+ * It holds with the host split and with the device split alike; the kept device encoder is re-configured, not
+ * re-created, and every other call is unaffected.  The sentinel ids may be special-token ids: the stage writes ids and
+ * never looks them up.  Errors as for mbpe_encoder_set_fim; a sentinel id that does not fit a 16-bit matrix is
+ * MBPE_ERR_VOCAB from the batch call.
+ * mbpe_tok_encode_fim_info: mbpe_encoder_fim_info of the kept encoder -- the plan of the latest batch call; no
+ * documents before the first device call. */
+MBPE_API int mbpe_tok_set_encode_fim(mbpe_tokenizer *t, const mbpe_fim_spec *spec);
+MBPE_API int mbpe_tok_encode_fim_info(mbpe_tokenizer *t, uint8_t *mode_out, uint64_t *cut_out, uint64_t cap_docs,
+                                      uint64_t *n_docs_out);
+
 /* The option "unicode" (mbpe_splitter_set_option) of the device splits this tokenizer makes: 0 (the default) or on.
  * It applies to mbpe_tok_train_split_device and, while mbpe_tok_set_encode_split is on, to the mbpe_tok_encode*_device
  * calls, whose kept splitter is re-configured, not re-created.  Same results; otherwise without effect. */

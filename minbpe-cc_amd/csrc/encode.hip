@@ -52,6 +52,7 @@
 #include "dedup.h"
 #include "dropout.h"
 #include "expand.h"
+#include "fim.h"
 #include "hip_host.h"
 #include "hist.h"
 #include "pack.h"
@@ -525,6 +526,15 @@ struct mbpe_encoder : DevQueue {
     DevBuf<uint8_t> d_fit_pieces;
     DevBuf<unsigned long long> d_fit_rows;
     float pack_ms = 0.f;                      // the pack kernel of the latest such call
+    // mbpe_encoder_set_fim (nothing of this exists while it is off or its rate 0): the spec; the second flat buffer and
+    // offset array the stage writes, the plan beside them; the latest batch call's documents and whether the stage ran
+    bool fim_on = false;
+    mbpe_fim_spec fim = {};
+    DevBuf<void> d_fim_flat;
+    DevBuf<unsigned long long> d_fim_off, d_fim_cut;
+    DevBuf<uint8_t> d_fim_mode;
+    uint64_t fim_docs = 0;
+    bool fim_ran = false;
     // token byte offsets: len[id] (host; empty with len_error set for a table mbpe_merges_check refuses), on the
     // device from the first such call on; the spans' byte counts, the singles' token indices, offsets bound for the host
     std::vector<uint32_t> len;
@@ -1477,17 +1487,62 @@ int enc_guard(const std::string &who, F body) {
     }
 }
 
+// the fill-in-the-middle stage of a batch call (mbpe_encoder_set_fim with rate > 0; n_tokens > 0): e->d_flat and the
+// documents' offsets -> e->d_fim_flat and e->d_fim_off, which the pack step then reads.  One wait; the new token count
+// and the flag come back with it, and, to_host, the new offsets into e->doc_tok
+int enc_fim_stage(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool docs_on_device, bool to_host, uint64_t *n_new,
+                  float *ms) {
+    const uint64_t n_docs = k.n_docs, cap = n_tokens + 3 * n_docs;   // (every document transformed: no more ids than these)
+    int rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
+    if (rc == MBPE_OK) rc = e->d_fim_flat.reserve(cap * (k.token_bits() / 8), e->mem);
+    if (rc == MBPE_OK) rc = e->d_fim_off.reserve(fim_off_bytes(n_docs), e->mem);
+    if (rc == MBPE_OK) rc = e->d_fim_cut.reserve(n_docs * 16, e->mem);
+    if (rc == MBPE_OK) rc = e->d_fim_mode.reserve(n_docs, e->mem);
+    if (rc != MBPE_OK) return rc;
+    if (!docs_on_device)
+        ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
+    const FimDst dst = {e->d_fim_flat, cap, e->d_fim_off, e->d_fim_cut, e->d_fim_mode};
+    ECHK(hipEventRecord(e->ev0, e->stream));
+    fim_launch(e->stream, e->d_flat, n_tokens, k.token_bits(), e->d_doc_off, n_docs, e->fim, dst);
+    if ((rc = e->finish(ms)) != MBPE_OK) return rc;
+    e->last_ms += *ms;
+    unsigned long long res[2] = {0, 0};                          // the new token count, the first document too long
+    ECHK(hipMemcpyAsync(res, e->d_fim_off + n_docs, 16, hipMemcpyDeviceToHost, e->stream));
+    if (to_host) {
+        e->doc_tok.resize(n_docs + 1);
+        ECHK(hipMemcpyAsync(e->doc_tok.data(), e->d_fim_off, (n_docs + 1) * 8, hipMemcpyDeviceToHost, e->stream));
+    }
+    ECHK(hipStreamSynchronize(e->stream));
+    if (res[1] != ~0ull)
+        return fail(MBPE_ERR_ARG, "fim: document " + std::to_string(res[1]) + " has 2^32 - 1 tokens or more");
+    if (res[0] >> 40) return fail(MBPE_ERR_ARG, "fim: more than 2^40 tokens");
+    *n_new = res[0];
+    e->fim_ran = true;
+    return MBPE_OK;
+}
+
 // the pack step of the batch calls: the flat tokens in e->d_flat, the documents' token offsets in e->doc_tok (host;
-// docs_on_device: in e->d_doc_off already, and on the host only where doc_tok_off_out asks for them)
-int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool docs_on_device) {
+// docs_on_device: in e->d_doc_off already, and on the host only where doc_tok_off_out asks for them).  With
+// fill-in-the-middle on, the stage comes first and everything below reads what it wrote
+int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_on_device) {
     const mbpe_pack_spec &spec = *k.spec;
     const mbpe_pack_aux *aux = k.aux;
     const uint64_t n_docs = k.n_docs;
     const mbpe_pack_window *win = k.win;
     const struct mbpe_pack_fit *fit = k.fit;
     int rc = MBPE_OK;
+    uint64_t n_tokens = n_enc;                                   // tokens the packers read
+    float rows_ms = 0.f;                                         // the kernels before the pack kernel
+    e->fim_docs = n_docs;
+    e->fim_ran = false;
+    const bool fim = e->fim_on && e->fim.rate && n_enc;
+    if (fim) {
+        const bool to_host = k.doc_tok_off_out || fit || (aux && n_enc + 3 * n_docs + 2 >= (1ull << 32));
+        if ((rc = enc_fim_stage(e, k, n_enc, docs_on_device, to_host, &n_tokens, &rows_ms)) != MBPE_OK) return rc;
+        e->pack_ms = rows_ms;
+        if (aux && to_host && (rc = pack_check_aux(spec, aux, e->doc_tok.data(), n_docs, nullptr, 0)) != MBPE_OK) return rc;
+    }
     uint64_t n_rows = win ? 0 : pack_rows(spec, n_tokens, n_docs);
-    float rows_ms = 0.f;
     if (fit) {
         // the rows depend on the plan, and the plan is host work: from e->doc_tok, which both callers have filled
         if ((rc = pack_fit_make(e->doc_tok.data(), n_docs, spec, &e->fit_plan)) != MBPE_OK) return rc;
@@ -1498,21 +1553,23 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool doc
         rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
         if (rc == MBPE_OK) rc = e->d_row_start.reserve(pack_win_scratch_bytes(n_docs), e->mem);
         if (rc != MBPE_OK) return rc;
-        if (!docs_on_device)
+        if (!docs_on_device && !fim)
             ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
+        float win_ms = 0.f;
         ECHK(hipEventRecord(e->ev0, e->stream));
-        pack_launch_win_rows(e->stream, e->d_doc_off, n_docs, spec, *win, e->d_row_start);
-        if ((rc = e->finish(&rows_ms)) != MBPE_OK) return rc;
+        pack_launch_win_rows(e->stream, fim ? e->d_fim_off : e->d_doc_off, n_docs, spec, *win, e->d_row_start);
+        if ((rc = e->finish(&win_ms)) != MBPE_OK) return rc;
         unsigned long long total = 0;
         ECHK(hipMemcpyAsync(&total, e->d_row_start + n_docs, 8, hipMemcpyDeviceToHost, e->stream));
         ECHK(hipStreamSynchronize(e->stream));
         if (total > (1ull << 40)) return fail(MBPE_ERR_ARG, "more than 2^40 rows");
         n_rows = total;
+        rows_ms += win_ms;
         e->pack_ms = rows_ms;
-        e->last_ms += rows_ms;
+        e->last_ms += win_ms;
     }
     *k.n_rows_out = n_rows;
-    if (k.n_tokens_out) *k.n_tokens_out = n_tokens;
+    if (k.n_tokens_out) *k.n_tokens_out = n_enc;
     if (k.ids_out && k.cap_rows < n_rows) return fail(MBPE_ERR_ARG, "ids_out too small");
     if (k.doc_tok_off_out) std::copy(e->doc_tok.begin(), e->doc_tok.end(), k.doc_tok_off_out);   // (filled in both cases)
     if (!k.ids_out) return MBPE_OK;                              // the query
@@ -1542,9 +1599,10 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool doc
         }
     }
     if (rc != MBPE_OK) return rc;
-    if (!docs_on_device && !win)
+    if (!docs_on_device && !win && !fim)
         ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
-    const PackSrc src = {e->d_flat, e->d_doc_off, n_docs, n_tokens, k.token_bits()};
+    const PackSrc src = {fim ? e->d_fim_flat.get() : e->d_flat.get(), fim ? e->d_fim_off : e->d_doc_off, n_docs, n_tokens,
+                         k.token_bits()};
     const PackDst dst = {k.out_on_device ? k.ids_out : e->d_ids.get(),
                          k.out_on_device || !k.len_out ? k.len_out : e->d_len.get(), n_rows};
     if (fit) {
@@ -1579,6 +1637,10 @@ int enc_batch_check(const mbpe_encoder *e, const EncPack &k) {
     if (k.ids_out && k.out_on_device &&
         ((uint64_t)(uintptr_t)k.ids_out % (k.spec->out_bits / 8) || (uint64_t)(uintptr_t)k.len_out % 4))
         return fail(MBPE_ERR_ARG, "ids_out or len_out is not aligned to its elements");
+    if (e->fim_on) {
+        const char *msg = "";
+        if (const int rc = fim_check_spec(&e->fim, k.token_bits(), &msg)) return fail(rc, msg);
+    }
     if (k.win) return pack_check_windows(k.spec, k.token_bits(), k.aux, k.win, k.n_docs, k.ids_out, k.out_on_device);
     if (k.fit) return pack_check_fit(k.spec, k.token_bits(), k.aux, k.fit, k.n_docs, k.ids_out, k.out_on_device);
     return k.aux ? pack_check_aux(*k.spec, k.aux, nullptr, k.n_docs, k.ids_out, k.out_on_device) : MBPE_OK;
@@ -1828,6 +1890,36 @@ int mbpe_encoder_set_dropout(mbpe_encoder *e, uint64_t threshold, uint64_t seed)
     if (threshold > kDropoutOne) return fail(MBPE_ERR_ARG, "mbpe_encoder_set_dropout: threshold must not exceed 2^32");
     e->drop_threshold = threshold;
     e->drop_seed = seed;
+    return MBPE_OK;
+}
+
+int mbpe_encoder_set_fim(mbpe_encoder *e, const mbpe_fim_spec *spec) {
+    if (!e) return fail(MBPE_ERR_ARG, "mbpe_encoder_set_fim: NULL argument");
+    if (spec) {
+        const char *msg = "";
+        if (const int rc = fim_check_spec(spec, 32, &msg)) return fail(rc, std::string("mbpe_encoder_set_fim: ") + msg);
+        e->fim = *spec;
+    }
+    e->fim_on = spec != nullptr;
+    return MBPE_OK;
+}
+
+int mbpe_encoder_fim_info(mbpe_encoder *e, uint8_t *mode_out, uint64_t *cut_out, uint64_t cap_docs, uint64_t *n_docs_out) {
+    if (!e || !n_docs_out) return fail(MBPE_ERR_ARG, "mbpe_encoder_fim_info: NULL argument");
+    const uint64_t n = e->fim_docs;
+    *n_docs_out = n;
+    if (!mode_out && !cut_out) return MBPE_OK;
+    if (cap_docs < n) return fail(MBPE_ERR_ARG, "mbpe_encoder_fim_info: room for fewer documents than the call had");
+    if (n == 0) return MBPE_OK;
+    if (!e->fim_ran) {                                           // the stage was off: every document is as it was
+        if (mode_out) std::fill(mode_out, mode_out + n, 0);
+        if (cut_out) std::fill(cut_out, cut_out + 2 * n, 0);
+        return MBPE_OK;
+    }
+    ECHK(hipSetDevice(e->device));
+    if (mode_out) ECHK(hipMemcpyAsync(mode_out, e->d_fim_mode, n, hipMemcpyDeviceToHost, e->stream));
+    if (cut_out) ECHK(hipMemcpyAsync(cut_out, e->d_fim_cut, n * 16, hipMemcpyDeviceToHost, e->stream));
+    ECHK(hipStreamSynchronize(e->stream));
     return MBPE_OK;
 }
 

@@ -10,6 +10,7 @@
 
 #include <string>
 #include <utility>
+#include <vector>
 
 namespace mbpe {
 
@@ -143,6 +144,22 @@ struct DevQueue {
     int finish(float *ms) {                       // ev1 goes here, with nothing after it
         MBPE_HIP_CHECK(hipEventRecord(ev1, stream), mem.clear_last);
         return wait(ms);
+    }
+};
+
+// The device side of a one-shot call: a stream, two events and the buffers it had to allocate, all released at its end
+struct OneShot : DevQueue {
+    OneShot() : DevQueue(true) {}
+    std::vector<DevBuf<uint8_t>> bufs;
+    // device memory for n bytes (at least one), filled from `host` when that is given
+    int alloc(void **out, uint64_t n, const void *host) {
+        *out = nullptr;
+        bufs.emplace_back();
+        const int rc = bufs.back().reserve(n ? n : 1, mem);
+        if (rc != MBPE_OK) return rc;
+        *out = bufs.back();
+        if (host && n) MBPE_HIP_CHECK(hipMemcpyAsync(*out, host, n, hipMemcpyHostToDevice, stream), true);
+        return MBPE_OK;
     }
 };
 

@@ -699,22 +699,6 @@ void launch_pack_fit(hipStream_t stream, const PackFitJob &fj) {
 // device time of the calling thread's latest one-shot pack or unpack kernel (mbpe_pack_kernel_ms)
 thread_local float g_pack_ms = 0.f;
 
-// the device side of a one-shot call: a stream, two events and the buffers it had to allocate, all released at its end
-struct OneShot : DevQueue {
-    OneShot() : DevQueue(true) {}
-    std::vector<DevBuf<uint8_t>> bufs;
-    // device memory for n bytes (at least one), filled from `host` when that is given
-    int alloc(void **out, uint64_t n, const void *host) {
-        *out = nullptr;
-        bufs.emplace_back();
-        const int rc = bufs.back().reserve(n ? n : 1, mem);
-        if (rc != MBPE_OK) return rc;
-        *out = bufs.back();
-        if (host && n) PCHK(hipMemcpyAsync(*out, host, n, hipMemcpyHostToDevice, stream));
-        return MBPE_OK;
-    }
-};
-
 int pack_run(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
              const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec &spec, void *ids_out, uint64_t n_rows,
              int out_on_device, uint32_t *len_out, const mbpe_pack_aux *aux, const mbpe_pack_window *win = nullptr,

@@ -5,6 +5,7 @@
 #include "tokenizer.h"
 
 #include "dropout.h"
+#include "fim.h"
 #include "mbpe.h"
 #include "mbpe_tokenizer.h"
 
@@ -66,6 +67,7 @@ mbpe_encoder *Tokenizer::device_encoder(int device) {
     int rc = mbpe_encoder_set_option(encoder_, "rank_order", rank_order_ ? 1 : 0);
     if (rc == MBPE_OK) rc = mbpe_encoder_set_option(encoder_, "dedup", encode_dedup_ ? 1 : 0);
     if (rc == MBPE_OK) rc = mbpe_encoder_set_dropout(encoder_, drop_threshold_, drop_seed_);
+    if (rc == MBPE_OK) rc = mbpe_encoder_set_fim(encoder_, fim_on_ ? &fim_ : nullptr);
     if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
     return encoder_;
 }
@@ -1340,6 +1342,31 @@ int mbpe_tok_set_encode_dropout(mbpe_tokenizer *t, uint64_t threshold, uint64_t 
     }
     t->t->set_dropout(threshold, seed);
     return MBPE_OK;
+}
+
+int mbpe_tok_set_encode_fim(mbpe_tokenizer *t, const mbpe_fim_spec *spec) {
+    if (!t) return MBPE_ERR_ARG;
+    if (spec) {
+        const char *msg = "";
+        const int rc = mbpe::fim_check_spec(spec, 32, &msg);
+        if (rc != MBPE_OK) {
+            mbpe_host::set_last_error(std::string("mbpe_tok_set_encode_fim: ") + msg);
+            return rc;
+        }
+    }
+    t->t->set_fim(spec);
+    return MBPE_OK;
+}
+
+int mbpe_tok_encode_fim_info(mbpe_tokenizer *t, uint8_t *mode_out, uint64_t *cut_out, uint64_t cap_docs,
+                             uint64_t *n_docs_out) {
+    if (!t || !n_docs_out) {
+        mbpe_host::set_last_error("mbpe_tok_encode_fim_info: NULL argument");
+        return MBPE_ERR_ARG;
+    }
+    *n_docs_out = 0;
+    mbpe_encoder *enc = t->t->kept_encoder();
+    return enc ? mbpe_encoder_fim_info(enc, mode_out, cut_out, cap_docs, n_docs_out) : MBPE_OK;
 }
 
 int mbpe_tok_set_train_dedup(mbpe_tokenizer *t, int on) {

@@ -117,6 +117,11 @@ public:
     // with the device split, the chunk buffer of append_chunks / batch_chunks with the host split (host loop and
     // device alike) -- the same whenever that buffer is the text
     void set_dropout(uint64_t threshold, uint64_t seed) { drop_threshold_ = threshold; drop_seed_ = seed; }
+    // fill-in-the-middle of the device batch calls that pack (mbpe_tok_set_encode_fim; mbpe.h holds the rule): NULL =
+    // off.  The kept device encoder is re-configured, not re-created; the plan of its latest batch call is its own
+    // (mbpe_encoder_fim_info on kept_encoder(), NULL before the first device call)
+    void set_fim(const mbpe_fim_spec *spec) { fim_on_ = spec != nullptr; if (spec) fim_ = *spec; }
+    mbpe_encoder *kept_encoder() const { return encoder_; }
     // the option "unicode" of every device split made from here on (mbpe_tok_set_split_unicode)
     void set_split_unicode(bool on) { split_unicode_ = on; }
     // train() from here on runs on the distinct chunks with their counts (mbpe_tok_set_train_dedup)
@@ -244,6 +249,8 @@ private:
     bool encode_dedup_ = false;
     bool rank_order_ = false;
     uint64_t drop_threshold_ = 0, drop_seed_ = 0;
+    bool fim_on_ = false;
+    mbpe_fim_spec fim_ = {};
     std::vector<uint64_t> counts_;           // count_tokens: the table, and the weighted token total it has reached
     uint64_t counts_total_ = 0;
 };

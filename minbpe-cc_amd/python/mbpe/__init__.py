@@ -53,6 +53,7 @@ EXPORTS = [
     "mbpe_encoder_counts", "mbpe_encoder_counts_reset",
     "mbpe_pack_fit", "mbpe_pack_fit_plan", "mbpe_pack_fit_cu_seqlens", "mbpe_encoder_encode_batch_fit",
     "mbpe_encoder_encode_batch_endmask_fit",
+    "mbpe_fim_plan", "mbpe_fim_tokens", "mbpe_fim_kernel_ms", "mbpe_encoder_set_fim", "mbpe_encoder_fim_info",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -67,7 +68,8 @@ TOK_EXPORTS = [
     "mbpe_tok_train_pieces_finish", "mbpe_tok_train_pieces_abort", "mbpe_tok_set_train_limits",
     "mbpe_tok_train_pieces_export_size", "mbpe_tok_train_pieces_export", "mbpe_tok_train_pieces_merge",
     "mbpe_tok_encode_batch_windows_device", "mbpe_tok_count_tokens", "mbpe_tok_token_counts",
-    "mbpe_tok_token_counts_reset", "mbpe_tok_encode_batch_fit_device",
+    "mbpe_tok_token_counts_reset", "mbpe_tok_encode_batch_fit_device", "mbpe_tok_set_encode_fim",
+    "mbpe_tok_encode_fim_info",
 ]
 
 
@@ -133,6 +135,17 @@ class PackFit(ctypes.Structure):
     for)."""
     _fields_ = [("doc_row", ctypes.c_void_p), ("doc_col", ctypes.c_void_p)]
 
+
+class FimSpec(ctypes.Structure):
+    """mbpe_fim_spec (include/mbpe.h): the fill-in-the-middle transform; fim_spec() makes one from rates."""
+    _fields_ = [
+        ("rate", ctypes.c_uint64), ("spm", ctypes.c_uint64), ("seed", ctypes.c_uint64), ("doc_base", ctypes.c_uint64),
+        ("pre_id", ctypes.c_uint32), ("suf_id", ctypes.c_uint32), ("mid_id", ctypes.c_uint32),
+        ("min_tokens", ctypes.c_uint32), ("max_tokens", ctypes.c_uint32),
+    ]
+
+
+FIM_NONE, FIM_PSM, FIM_SPM = 0, 1, 2      # the modes of fim_plan / fim_info
 
 _ID_DTYPES = {16: np.uint16, 32: np.uint32, 64: np.uint64}
 # labels are ids or ignore_label: signed where a negative ignore_label fits
@@ -345,6 +358,13 @@ def lib():
     L.mbpe_tok_count_tokens.argtypes = [vp, vp, vp, u64, i32, i32, u64, vp]
     L.mbpe_tok_token_counts.argtypes = [vp, vp, u64, vp, vp]
     L.mbpe_tok_token_counts_reset.argtypes = [vp]
+    L.mbpe_fim_plan.argtypes = [vp, u64, vp, vp, vp, vp]
+    L.mbpe_fim_tokens.argtypes = [i32, vp, u64, u32, i32, vp, u64, vp, vp, u64, i32, vp, vp]
+    L.mbpe_fim_kernel_ms.argtypes = [vp]
+    L.mbpe_encoder_set_fim.argtypes = [vp, vp]
+    L.mbpe_encoder_fim_info.argtypes = [vp, vp, vp, u64, vp]
+    L.mbpe_tok_set_encode_fim.argtypes = [vp, vp]
+    L.mbpe_tok_encode_fim_info.argtypes = [vp, vp, vp, u64, vp]
     _lib = L
     return L
 
@@ -488,6 +508,72 @@ def pack_tokens(tokens, doc_tok_off, seq_len, layout="padded", out_bits=32, pad_
         _check(lib().mbpe_pack_tokens(*head, ids.ctypes.data, n_rows.value, 0, lengths.ctypes.data,
                                       ctypes.byref(n_rows)))
     return ids, lengths
+
+
+def fim_spec(rate, spm_rate, pre_id, suf_id, mid_id, seed=0, doc_base=0, min_tokens=0, max_tokens=0):
+    """A FimSpec from probabilities: a document is transformed with probability `rate`, a transformed one is SPM with
+    probability spm_rate (else PSM); pre_id / suf_id / mid_id are the sentinel ids; seed picks the epoch's draw,
+    doc_base is the number of the call's first document in the corpus; documents shorter than max(min_tokens, 1) or
+    -- max_tokens > 0 -- longer than max_tokens stay as they are.  The rule: include/mbpe.h, mbpe_fim_spec."""
+    return FimSpec(dropout_threshold(rate), dropout_threshold(spm_rate), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                   int(doc_base) & 0xFFFFFFFFFFFFFFFF, pre_id, suf_id, mid_id, min_tokens, max_tokens)
+
+
+def fim_plan(doc_tok_off, spec):
+    """mbpe_fim_plan (host only): what the transform does to documents of these token offsets -> (doc_tok_off after it
+    [n_docs + 1], mode uint8[n_docs] (FIM_NONE / FIM_PSM / FIM_SPM), cuts uint64[n_docs, 2] = (a, b))."""
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    n_docs = len(off) - 1
+    new_off = np.zeros(n_docs + 1, dtype=np.uint64)
+    mode = np.zeros(max(n_docs, 1), dtype=np.uint8)
+    cuts = np.zeros((max(n_docs, 1), 2), dtype=np.uint64)
+    _check(lib().mbpe_fim_plan(off.ctypes.data, n_docs, ctypes.byref(spec), new_off.ctypes.data, mode.ctypes.data,
+                               cuts.ctypes.data))
+    return new_off, mode[:n_docs], cuts[:n_docs]
+
+
+def fim_tokens(tokens, doc_tok_off, spec, device=0, tokens_ptr=None, n_tokens=None, token_bits=None, out_ptr=None,
+               cap=0):
+    """mbpe_fim_tokens: the fill-in-the-middle transform of a flat token array (uint16 or uint32) whose document i is
+    tokens[doc_tok_off[i]:doc_tok_off[i + 1]] -> (tokens of the same dtype, doc_tok_off after it): what pack_* and
+    Decoder.decode_batch take.  Device memory: tokens_ptr= / n_tokens= / token_bits= name the tokens there instead of
+    `tokens`; with out_ptr= (room for cap tokens) the tokens are written there and (token count, doc_tok_off) is
+    returned."""
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    if tokens_ptr is None:
+        t = np.ascontiguousarray(tokens)
+        if t.dtype not in (np.dtype(np.uint16), np.dtype(np.uint32)):
+            t = t.astype(np.uint32)
+        t = t.reshape(-1)
+        tp, n_tokens, token_bits, on_dev = (t.ctypes.data if len(t) else None), len(t), t.dtype.itemsize * 8, 0
+    else:
+        tp, on_dev = _ptr(tokens_ptr), 1
+    new_off = np.zeros(len(off), dtype=np.uint64)
+    n = ctypes.c_uint64()
+    head = (device, tp, n_tokens, token_bits, on_dev, off.ctypes.data, len(off) - 1, ctypes.byref(spec))
+    if out_ptr is not None:
+        _check(lib().mbpe_fim_tokens(*head, _ptr(out_ptr), cap, 1, new_off.ctypes.data, ctypes.byref(n)))
+        return n.value, new_off
+    _check(lib().mbpe_fim_tokens(*head, None, 0, 0, new_off.ctypes.data, ctypes.byref(n)))
+    out = np.zeros(max(n.value, 1), dtype=_ID_DTYPES[token_bits])
+    _check(lib().mbpe_fim_tokens(*head, out.ctypes.data, n.value, 0, new_off.ctypes.data, ctypes.byref(n)))
+    return out[:n.value], new_off
+
+
+def fim_kernel_ms():
+    """Device time of the kernels of this thread's latest fim_tokens (mbpe_fim_kernel_ms)."""
+    ms = ctypes.c_float()
+    _check(lib().mbpe_fim_kernel_ms(ctypes.byref(ms)))
+    return ms.value
+
+
+def _fim_info(fn, handle):
+    n = ctypes.c_uint64()
+    _check(fn(handle, None, None, 0, ctypes.byref(n)))
+    mode = np.zeros(max(n.value, 1), dtype=np.uint8)
+    cuts = np.zeros((max(n.value, 1), 2), dtype=np.uint64)
+    _check(fn(handle, mode.ctypes.data, cuts.ctypes.data, n.value, ctypes.byref(n)))
+    return mode[:n.value], cuts[:n.value]
 
 
 def token_counts(tokens, n_ids, device=0, tokens_ptr=None, n_tokens=None, token_bits=None, out_ptr=None):
@@ -885,6 +971,18 @@ class Encoder:
         (seed, position, id).  Rank order only: an encode call with p > 0 and the greedy order raises MbpeError(ERR_ARG).
         p = 0 is plain rank order, p = 1 leaves the bytes."""
         _check(lib().mbpe_encoder_set_dropout(self._h, dropout_threshold(p), int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def set_fim(self, spec):
+        """Fill-in-the-middle for the batch calls that follow (mbpe_encoder_set_fim): a FimSpec (fim_spec()), or None
+        to turn it off.  The stage runs between the encode and the pack kernel of encode_batch, _aux, _windows, _fit and
+        their endmask forms; the flat calls and count() are unaffected.  doc_tok_off of those calls is the one after
+        the transform."""
+        _check(lib().mbpe_encoder_set_fim(self._h, None if spec is None else ctypes.byref(spec)))
+
+    def fim_info(self):
+        """The plan of the latest batch call (mbpe_encoder_fim_info) -> (mode uint8[n_docs], cuts uint64[n_docs, 2]);
+        all zero where the stage was off."""
+        return _fim_info(lib().mbpe_encoder_fim_info, self._h)
 
     def encode(self, data, chunk_off=None, offsets=False, dtype=np.uint32, byte_off=False):
         """Host text -> host tokens of dtype uint32 or uint16, or (tokens, chunk_tok_off) with offsets=True: the
@@ -2134,7 +2232,7 @@ class Tokenizer:
     def load(self, path, verbose=False):
         _check(lib().mbpe_tok_load(self._h, os.fsencode(path), int(verbose)))
 
-    def _encode_split(self, device_split, order="greedy", dropout=0.0, seed=0, dedup=False):
+    def _encode_split(self, device_split, order="greedy", dropout=0.0, seed=0, dedup=False, fim=None):
         if order not in ("greedy", "rank"):
             raise ValueError('order must be "greedy" or "rank"')
         _check(lib().mbpe_tok_set_encode_dedup(self._h, int(bool(dedup))))
@@ -2142,6 +2240,12 @@ class Tokenizer:
         _check(lib().mbpe_tok_set_encode_dropout(self._h, dropout_threshold(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF))
         _check(lib().mbpe_tok_set_encode_split(self._h, int(bool(device_split))))
         _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
+        _check(lib().mbpe_tok_set_encode_fim(self._h, None if fim is None else ctypes.byref(fim)))
+
+    def fim_info(self):
+        """The fill-in-the-middle plan of the latest batch call with a device (mbpe_tok_encode_fim_info) -> (mode
+        uint8[n_texts], cuts uint64[n_texts, 2]): FIM_NONE / FIM_PSM / FIM_SPM and the cuts (a, b) of every text."""
+        return _fim_info(lib().mbpe_tok_encode_fim_info, self._h)
 
     def encode(self, data, device=None, device_split=False, order="greedy", byte_ranges=False, dropout=0.0, seed=0,
                dedup=False):
@@ -2245,12 +2349,16 @@ class Tokenizer:
 
     def encode_batch_padded(self, texts, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
                             pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
-                            device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False):
+                            device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False, fim=None):
         """Every text split like encode(), encoded and packed in one device call
         (mbpe_tok_encode_batch_packed_device) -> (ids [n_rows, seq_len], lengths [n_rows]) as numpy arrays; with
         out_ptr= and len_ptr= (device memory for cap_rows rows) the matrix stays on the device and the row count is
-        returned.  bos_id / eos_id may be special-token ids.  layout "packed" gives the MBPE_PACK_PACKED rows."""
-        self._encode_split(device_split, order, dropout, seed, dedup)
+        returned.  bos_id / eos_id may be special-token ids.  layout "packed" gives the MBPE_PACK_PACKED rows.
+        fim (here and in _aux, _windows and _fit; mbpe_tok_set_encode_fim): a FimSpec (fim_spec()) -- every text's
+        tokens go through the fill-in-the-middle transform on the device before they are packed; its sentinel ids may
+        be special-token ids; fim_info() tells what was done to each text.  With "padded" rows and truncation a
+        transformed text that does not fit loses its middle: use max_tokens, windows, "packed" or fit there."""
+        self._encode_split(device_split, order, dropout, seed, dedup, fim)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         parts = [bytes(_u8(t)) for t in texts]
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
@@ -2277,11 +2385,11 @@ class Tokenizer:
                          pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
                          labels=False, positions=False, segments=False, cu_seqlens=False, ignore_label=-100,
                          labels_ptr=None, pos_ptr=None, seg_ptr=None, device_split=False, order="greedy", dropout=0.0,
-                         seed=0, dedup=False):
+                         seed=0, dedup=False, fim=None):
         """encode_batch_padded plus labels, positions, segments and cu_seqlens (mbpe_tok_encode_batch_aux_device): its
         arguments and those of pack_tokens_aux, whose dict (or, with out_ptr=, row count) is returned.  The documents'
-        token offsets of the call: self.doc_tok_off."""
-        self._encode_split(device_split, order, dropout, seed, dedup)
+        token offsets of the call (with fim: after the transform): self.doc_tok_off."""
+        self._encode_split(device_split, order, dropout, seed, dedup, fim)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label)
         parts = [bytes(_u8(t)) for t in texts]
@@ -2317,12 +2425,12 @@ class Tokenizer:
                              eos_id=None, device=0, out_ptr=None, len_ptr=None, cap_rows=None, labels=False,
                              positions=False, segments=False, ignore_label=-100, labels_ptr=None, pos_ptr=None,
                              seg_ptr=None, row_doc=False, row_tok0=False, row_doc_ptr=None, row_tok0_ptr=None,
-                             device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False):
+                             device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False, fim=None):
         """encode_batch_aux for the window layout (mbpe_tok_encode_batch_windows_device): every text split like
         encode(), encoded, and cut into rows of seq_len that share `stride` tokens where a text does not fit one --
         the keywords and the result of pack_windows ("row_doc" maps a row back to its text).  The texts' token
         offsets of the call: self.doc_tok_off."""
-        self._encode_split(device_split, order, dropout, seed, dedup)
+        self._encode_split(device_split, order, dropout, seed, dedup, fim)
         spec = pack_spec(seq_len, "padded", out_bits, pad_id, bos_id, eos_id)
         call = _WinCall(spec, stride, score_once, labels, positions, segments, ignore_label, row_doc, row_tok0)
         parts = [bytes(_u8(t)) for t in texts]
@@ -2345,12 +2453,12 @@ class Tokenizer:
                          len_ptr=None, cap_rows=None, labels=False, positions=False, segments=False, cu_seqlens=False,
                          ignore_label=-100, labels_ptr=None, pos_ptr=None, seg_ptr=None, doc_row=False, doc_col=False,
                          doc_row_ptr=None, doc_col_ptr=None, device_split=False, order="greedy", dropout=0.0, seed=0,
-                         dedup=False):
+                         dedup=False, fim=None):
         """encode_batch_aux for the fit layout (mbpe_tok_encode_batch_fit_device): every text split like encode(),
         encoded, and packed whole into rows of seq_len by best fit; only a text longer than a row is cut -- the
         keywords and the result of pack_fit ("doc_row" / "doc_col" say where a text's last piece begins, "segments"
         holds the text's number + 1 in every cell).  The texts' token offsets of the call: self.doc_tok_off."""
-        self._encode_split(device_split, order, dropout, seed, dedup)
+        self._encode_split(device_split, order, dropout, seed, dedup, fim)
         spec = _fit_spec(seq_len, out_bits, pad_id, bos_id, eos_id)
         call = _FitCall(spec, labels, positions, segments, cu_seqlens, ignore_label, doc_row, doc_col)
         parts = [bytes(_u8(t)) for t in texts]
