@@ -1122,6 +1122,101 @@ MBPE_API int  mbpe_encoder_set_fim(mbpe_encoder *e, const mbpe_fim_spec *spec);
 MBPE_API int  mbpe_encoder_fim_info(mbpe_encoder *e, uint8_t *mode_out, uint64_t *cut_out, uint64_t cap_docs,
                                     uint64_t *n_docs_out);
 
+/* ---- masked-LM batches ----------------------------------------------------- */
+
+/* Masked-LM corruption of token documents (Devlin et al., 2019: select 15 % of the tokens, replace 80 % of those by a
+ * mask id, 10 % by a random id, leave 10 % as they are), between encode and pack, token by token or -- whole_word -- word
+ * by word, a word being a chunk of the encoder's split: in a 32-bit device stream bit 31 of a token says "last token of
+ * its word", and a document's last token ends a word whether flagged or not.  For document d of a call let t[0 .. L) be
+ * its tokens, g = doc_base + d (mod 2^64), h the hash of BPE-dropout above and
+ *   s_g = (h(seed, g, 0x4D4C4D00) << 32) | h(seed, g, 0x4D4C4D01).
+ * Token k belongs to the word whose first token has index w(k): w(k) = k if k == 0, or whole_word == 0, or token k - 1
+ * is flagged; otherwise w(k) = w(k - 1).
+ *   selected      iff h(s_g, w(k), 0) < select and the token's id is not among protect[0 .. n_protect)
+ *   replacement   for a selected token r = h(s_g, k, 1): r < mask gives mask_id; else r < mask + random gives
+ *                 (h(s_g, k, 2) * vocab_n) >> 32 as a 64-bit product, an id in [0, vocab_n); else the id stays
+ *   target        target[k] = the old id if the token is selected, else MBPE_NO_TOKEN
+ * The new stream has the length of the old one, so doc_tok_off holds for both; it is written as plain ids of the
+ * input's width.  The target stream is uint32 whatever the width.  The result is a pure function of (spec, d, tokens
+ * of d): the same call gives the same batch, another seed another epoch, a corpus fed in batches gets the result of one
+ * big call by passing in doc_base the number of each batch's first document, and a document is masked alike in every
+ * layout it is packed into.  Thresholds come from mbpe_dropout_threshold.  A protected token inside a selected word
+ * stays and is no target; the rest of the word is masked.  Random ids are drawn from all of [0, vocab_n): special ids
+ * below vocab_n included.
+ * Errors, all before the device is touched: MBPE_ERR_ARG for a threshold above 2^32, mask + random > 2^32, random > 0
+ * with vocab_n == 0, n_protect > 8, whole_word > 1, mask_id or vocab_n >= 2^31 - 2, whole_word with 16-bit tokens (they
+ * carry no flag), bad offsets and a NULL spec where one is required; MBPE_ERR_VOCAB for mask_id >= 65,536 or
+ * vocab_n > 65,536 with 16-bit tokens. */
+typedef struct {
+    uint64_t select;      /* threshold in [0, 2^32]: a word (a token without whole_word) is selected iff its draw is below it */
+    uint64_t mask;        /* threshold in [0, 2^32]: a selected token becomes mask_id iff its draw is below it */
+    uint64_t random;      /* threshold in [0, 2^32 - mask]: the share next to it becomes a random id */
+    uint64_t seed;
+    uint64_t doc_base;    /* number of the call's first document in the caller's corpus */
+    uint32_t mask_id;
+    uint32_t vocab_n;     /* random ids are drawn from [0, vocab_n) */
+    uint32_t whole_word;  /* 0 or 1 */
+    uint32_t n_protect;   /* ids of protect[] in use: 0 .. 8 */
+    uint32_t protect[8];  /* ids that are never selected (bos, eos, separators) */
+} mbpe_mlm_spec;
+
+/* The rule on the host alone (never MBPE_ERR_NO_DEVICE): tokens (n_tokens of token_bits bits, host memory; 32-bit
+ * tokens with bit 31 = word end) and doc_tok_off (n_docs + 1) -> tokens_out (n_tokens plain ids of token_bits bits, or
+ * NULL) and targets_out (n_tokens uint32, or NULL). */
+MBPE_API int  mbpe_mlm_plan(const void *tokens, uint64_t n_tokens, uint32_t token_bits, const uint64_t *doc_tok_off,
+                            uint64_t n_docs, const mbpe_mlm_spec *spec, void *tokens_out, uint32_t *targets_out);
+
+/* The same of a flat token stream on HIP device `device_id`, with the conventions of mbpe_fim_tokens: tokens in host
+ * or device memory (tokens_on_device), tokens_out (required, n_tokens ids) and targets_out (n_tokens uint32, or NULL)
+ * both in host or both in device memory (out_on_device; on the device aligned to their elements), doc_tok_off on the
+ * host.  There is no query form: the length does not change.  n_tokens == 0 is no device call.  The outputs are what
+ * mbpe_pack_tokens_aux_labels, mbpe_pack_windows_labels and mbpe_pack_fit_labels take as tokens and label_tokens.
+ * Kernels (csrc/mlm.hip): k_mlm_apply, a lane per 16 bytes of tokens, reads every token once and writes the new id and
+ * the target once, all in 16-byte pieces where the three addresses are 16-byte aligned (id by id otherwise); a lane
+ * finds its document by one search per span of 1,024 tokens.  With whole_word k_mlm_starts first leaves the latest
+ * word start of every span and k_mlm_scan the running maximum over the spans, which k_mlm_apply carries on.
+ * mbpe_mlm_kernel_ms: the device time of the calling thread's latest such call. */
+MBPE_API int  mbpe_mlm_tokens(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits,
+                              int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs,
+                              const mbpe_mlm_spec *spec, void *tokens_out, uint32_t *targets_out, int out_on_device);
+MBPE_API int  mbpe_mlm_kernel_ms(float *ms_out);
+
+/* mbpe_pack_tokens_aux, mbpe_pack_windows and mbpe_pack_fit with the labels taken from a target stream instead of the
+ * next token: each is the call it is named after plus label_tokens, n_tokens uint32 on the same side as tokens
+ * (required: NULL is MBPE_ERR_ARG; 4-byte aligned on the device).  A cell that holds body token j of the stream gets
+ * label_tokens[j], or ignore_label where that is MBPE_NO_TOKEN; bos, eos and pad cells get ignore_label.  In windows
+ * with score_once the cells a window shares with the one before it get ignore_label as they do without, so a token is
+ * a target at most once.  ids, len, pos, seg and every other output are untouched.  With out_bits 16 a label is the
+ * low 16 bits of its entry. */
+MBPE_API int  mbpe_pack_tokens_aux_labels(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits,
+                                          int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs,
+                                          const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows,
+                                          int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                                          const mbpe_pack_aux *aux, const uint32_t *label_tokens);
+MBPE_API int  mbpe_pack_windows_labels(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits,
+                                       int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs,
+                                       const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
+                                       uint32_t *len_out, uint64_t *n_rows_out, const mbpe_pack_aux *aux,
+                                       const mbpe_pack_window *win, const uint32_t *label_tokens);
+MBPE_API int  mbpe_pack_fit_labels(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits,
+                                   int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs,
+                                   const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
+                                   uint32_t *len_out, uint64_t *n_rows_out, const mbpe_pack_aux *aux,
+                                   const struct mbpe_pack_fit *fit, const uint32_t *label_tokens);
+
+/* The corruption as a stage of the encoder's batch calls; spec NULL turns it off.  It holds from the next call on for
+ * every call that packs (those of mbpe_encoder_set_fim).  The stage runs after the encode -- so after dropout and
+ * "dedup" -- and before the pack kernel, into a second flat buffer and a target buffer the encoder keeps (a repeat call
+ * of no larger size leaves mbpe_encoder_alloc_count as it is); the matrices hold the new ids, and labels -- where aux
+ * asks for them -- the targets as in the _labels calls above.  The plain batch calls without aux get the new ids alone.
+ * Both stages on is MBPE_ERR_ARG from the batch call, never a silent choice.  whole_word reads the flagged 32-bit
+ * stream the passes leave, which every route keeps up to the stage (host split, endmask, both orders, dropout, "dedup",
+ * texts cut into pieces, one-token chunks); with out_bits 16 the flat stream is 16 bits wide and whole_word is
+ * MBPE_ERR_ARG from the batch call, as are a mask_id or vocab_n that do not fit (MBPE_ERR_VOCAB).  With no spec, and
+ * with select 0, every call launches and allocates exactly what it does without.  mbpe_encoder_kernel_ms and
+ * mbpe_encoder_pack_ms include the stage. */
+MBPE_API int  mbpe_encoder_set_mlm(mbpe_encoder *e, const mbpe_mlm_spec *spec);
+
 /* ---- decode on the device ----------------------------------------------- */
 
 /* Tokenizer::decode (Tokenizer.h:725-751) for whole token streams on HIP device `device_id`: per token a byte

@@ -238,6 +238,17 @@ MBPE_API int mbpe_tok_set_encode_fim(mbpe_tokenizer *t, const mbpe_fim_spec *spe
 MBPE_API int mbpe_tok_encode_fim_info(mbpe_tokenizer *t, uint8_t *mode_out, uint64_t *cut_out, uint64_t cap_docs,
                                       uint64_t *n_docs_out);
 
+/* Masked-LM corruption for the device batch calls that pack (those of mbpe_tok_set_encode_fim): spec as for
+ * mbpe_encoder_set_mlm (mbpe.h, which holds the rule), NULL turns it off.  It holds with the host split and with the
+ * device split alike; the kept device encoder is re-configured, not re-created, and every other call is unaffected.
+ * The ids of the matrices are the corrupted ones and the labels of _aux_device, _windows_device and _fit_device the
+ * targets (ignore_label in every cell that is none).  whole_word masks the chunks of this tokenizer's split pattern; a
+ * special token is a word of its own.  mask_id and the protected ids may be special-token ids: the stage writes and
+ * compares ids and never looks them up.  Errors as for mbpe_encoder_set_mlm; from the batch call MBPE_ERR_ARG while
+ * fill-in-the-middle is on too and for whole_word with a 16-bit matrix, MBPE_ERR_VOCAB for a mask_id or vocab_n that
+ * does not fit one. */
+MBPE_API int mbpe_tok_set_encode_mlm(mbpe_tokenizer *t, const mbpe_mlm_spec *spec);
+
 /* The option "unicode" (mbpe_splitter_set_option) of the device splits this tokenizer makes: 0 (the default) or on.
  * It applies to mbpe_tok_train_split_device and, while mbpe_tok_set_encode_split is on, to the mbpe_tok_encode*_device
  * calls, whose kept splitter is re-configured, not re-created.  Same results; otherwise without effect. */

@@ -53,6 +53,7 @@
 #include "dropout.h"
 #include "expand.h"
 #include "fim.h"
+#include "mlm.h"
 #include "hip_host.h"
 #include "hist.h"
 #include "pack.h"
@@ -535,6 +536,13 @@ struct mbpe_encoder : DevQueue {
     DevBuf<uint8_t> d_fim_mode;
     uint64_t fim_docs = 0;
     bool fim_ran = false;
+    // mbpe_encoder_set_mlm (nothing of this exists while it is off or its select 0): the spec; the second flat buffer,
+    // the target stream and, for whole_word, the spans' word starts
+    bool mlm_on = false;
+    mbpe_mlm_spec mlm = {};
+    DevBuf<void> d_mlm_flat;
+    DevBuf<uint32_t> d_mlm_tgt;
+    DevBuf<unsigned long long> d_mlm_scr;
     // token byte offsets: len[id] (host; empty with len_error set for a table mbpe_merges_check refuses), on the
     // device from the first such call on; the spans' byte counts, the singles' token indices, offsets bound for the host
     std::vector<uint32_t> len;
@@ -1521,6 +1529,26 @@ int enc_fim_stage(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool doc
     return MBPE_OK;
 }
 
+// the masked-LM stage of a batch call (mbpe_encoder_set_mlm with select > 0; n_tokens > 0): e->d_flat, which holds the
+// passes' 32-bit tokens with their word-end flags (or plain 16-bit ids), and the documents' offsets in e->d_doc_off ->
+// e->d_mlm_flat and e->d_mlm_tgt, which the pack step then reads as tokens and label tokens.  One wait, for the time
+int enc_mlm_stage(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool docs_on_device, float *ms) {
+    const uint64_t n_docs = k.n_docs;
+    int rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
+    if (rc == MBPE_OK) rc = e->d_mlm_flat.reserve(n_tokens * (k.token_bits() / 8), e->mem);
+    if (rc == MBPE_OK) rc = e->d_mlm_tgt.reserve(n_tokens * 4, e->mem);
+    if (rc == MBPE_OK && e->mlm.whole_word) rc = e->d_mlm_scr.reserve(mlm_scratch_bytes(n_tokens), e->mem);
+    if (rc != MBPE_OK) return rc;
+    if (!docs_on_device)
+        ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
+    const MlmDst dst = {e->d_mlm_flat, e->d_mlm_tgt, e->d_mlm_scr};
+    ECHK(hipEventRecord(e->ev0, e->stream));
+    mlm_launch(e->stream, e->d_flat, n_tokens, k.token_bits(), e->d_doc_off, n_docs, e->mlm, dst);
+    if ((rc = e->finish(ms)) != MBPE_OK) return rc;
+    e->last_ms += *ms;
+    return MBPE_OK;
+}
+
 // the pack step of the batch calls: the flat tokens in e->d_flat, the documents' token offsets in e->doc_tok (host;
 // docs_on_device: in e->d_doc_off already, and on the host only where doc_tok_off_out asks for them).  With
 // fill-in-the-middle on, the stage comes first and everything below reads what it wrote
@@ -1542,6 +1570,11 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
         e->pack_ms = rows_ms;
         if (aux && to_host && (rc = pack_check_aux(spec, aux, e->doc_tok.data(), n_docs, nullptr, 0)) != MBPE_OK) return rc;
     }
+    const bool mlm = e->mlm_on && e->mlm.select && n_enc;        // (never with fim: enc_batch_check)
+    if (mlm) {
+        if ((rc = enc_mlm_stage(e, k, n_enc, docs_on_device, &rows_ms)) != MBPE_OK) return rc;
+        e->pack_ms = rows_ms;
+    }
     uint64_t n_rows = win ? 0 : pack_rows(spec, n_tokens, n_docs);
     if (fit) {
         // the rows depend on the plan, and the plan is host work: from e->doc_tok, which both callers have filled
@@ -1553,7 +1586,7 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
         rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
         if (rc == MBPE_OK) rc = e->d_row_start.reserve(pack_win_scratch_bytes(n_docs), e->mem);
         if (rc != MBPE_OK) return rc;
-        if (!docs_on_device && !fim)
+        if (!docs_on_device && !fim && !mlm)
             ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
         float win_ms = 0.f;
         ECHK(hipEventRecord(e->ev0, e->stream));
@@ -1599,10 +1632,11 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
         }
     }
     if (rc != MBPE_OK) return rc;
-    if (!docs_on_device && !win && !fim)
+    if (!docs_on_device && !win && !fim && !mlm)
         ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
-    const PackSrc src = {fim ? e->d_fim_flat.get() : e->d_flat.get(), fim ? e->d_fim_off : e->d_doc_off, n_docs, n_tokens,
-                         k.token_bits()};
+    const PackSrc src = {fim ? e->d_fim_flat.get() : mlm ? e->d_mlm_flat.get() : e->d_flat.get(),
+                         fim ? e->d_fim_off : e->d_doc_off, n_docs, n_tokens, k.token_bits(),
+                         mlm ? e->d_mlm_tgt.get() : nullptr};
     const PackDst dst = {k.out_on_device ? k.ids_out : e->d_ids.get(),
                          k.out_on_device || !k.len_out ? k.len_out : e->d_len.get(), n_rows};
     if (fit) {
@@ -1640,6 +1674,11 @@ int enc_batch_check(const mbpe_encoder *e, const EncPack &k) {
     if (e->fim_on) {
         const char *msg = "";
         if (const int rc = fim_check_spec(&e->fim, k.token_bits(), &msg)) return fail(rc, msg);
+    }
+    if (e->mlm_on) {
+        const char *msg = "";
+        if (e->fim_on) return fail(MBPE_ERR_ARG, "fill-in-the-middle and masked-LM are both on: turn one of them off");
+        if (const int rc = mlm_check_spec(&e->mlm, k.token_bits(), &msg)) return fail(rc, msg);
     }
     if (k.win) return pack_check_windows(k.spec, k.token_bits(), k.aux, k.win, k.n_docs, k.ids_out, k.out_on_device);
     if (k.fit) return pack_check_fit(k.spec, k.token_bits(), k.aux, k.fit, k.n_docs, k.ids_out, k.out_on_device);
@@ -1901,6 +1940,17 @@ int mbpe_encoder_set_fim(mbpe_encoder *e, const mbpe_fim_spec *spec) {
         e->fim = *spec;
     }
     e->fim_on = spec != nullptr;
+    return MBPE_OK;
+}
+
+int mbpe_encoder_set_mlm(mbpe_encoder *e, const mbpe_mlm_spec *spec) {
+    if (!e) return fail(MBPE_ERR_ARG, "mbpe_encoder_set_mlm: NULL argument");
+    if (spec) {
+        const char *msg = "";
+        if (const int rc = mlm_check_spec(spec, 32, &msg)) return fail(rc, std::string("mbpe_encoder_set_mlm: ") + msg);
+        e->mlm = *spec;
+    }
+    e->mlm_on = spec != nullptr;
     return MBPE_OK;
 }
 

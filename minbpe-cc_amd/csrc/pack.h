@@ -9,12 +9,15 @@
 
 namespace mbpe {
 
-// the documents: n_tokens tokens of `bits` bits (16: plain ids; 32: bit 31 is ignored) and n_docs + 1 token offsets
+// the documents: n_tokens tokens of `bits` bits (16: plain ids; 32: bit 31 is ignored) and n_docs + 1 token offsets.
+// label_tok: NULL for next-token labels, else n_tokens targets (mlm.h) that k_pack_aux, k_pack_windows and k_pack_fit
+// write as labels: a body cell gets its token's entry, ignore_label where that is MBPE_NO_TOKEN and in every other cell
 struct PackSrc {
     const void *tok;
     const unsigned long long *doc_off;
     uint64_t n_docs, n_tokens;
     uint32_t bits;
+    const uint32_t *label_tok = nullptr;
 };
 
 // the matrix: n_rows x seq_len ids of the spec's out_bits, and (optional) one length per row

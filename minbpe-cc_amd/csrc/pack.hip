@@ -234,11 +234,16 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_stream(PackJob j) {
 // the matrix can be partial; it is stored cell by cell.  For the labels the walk runs one element ahead: the element
 // read as a label is kept and becomes the next cell's id, so a group reads 9 tokens at most and none across a
 // document's end.  An output that is NULL is skipped by the whole wave.  Every cell index is 64-bit.
+// With label_tok (the _labels calls; masked-LM targets; LT, an instantiation of its own so that the next-token kernels
+// stay the code they were) nothing is read ahead: the cell of body token t gets label_tok[t], read with the id, and
+// bos, eos and pad cells keep ignore_label.  k_pack_windows and k_pack_fit alike.
 struct PackAuxJob {
     PackJob j;
     void *labels;                            // ids of OUT bits, or NULL
     uint32_t *pos, *seg;                     // or NULL
     unsigned long long ignore;               // ignore_label; its low OUT bits are written
+    const uint32_t *label_tok;               // NULL: the labels are next elements.  Else a target per token of the flat
+                                             // stream: a body cell's label is its token's entry (MBPE_NO_TOKEN: ignore)
 };
 
 constexpr uint32_t kAuxCells = 8;
@@ -292,7 +297,7 @@ __device__ __forceinline__ void aux_store_ids(void *dst, uint64_t c0, uint32_t c
     }
 }
 
-template <int IN, int OUT, bool PACKED>
+template <int IN, int OUT, bool PACKED, bool LT>
 __global__ __launch_bounds__(kPackThreads) void k_pack_aux(PackAuxJob a) {
     const PackJob &j = a.j;
     const bool want_lab = a.labels != nullptr;
@@ -362,7 +367,12 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_aux(PackAuxJob a) {
             if (in) {
                 id[e] = have_ahead ? ahead : element(k);
                 have_ahead = false;
-                if (want_lab && k + 1 < T) {
+                if (LT) {
+                    if (want_lab && k >= j.nb && !(j.ne && k == T - 1)) {
+                        const uint32_t v = a.label_tok[src0 + (k - j.nb)];
+                        if (v != MBPE_NO_TOKEN) { lab[e] = v; ign_mask &= ~(1u << e); }
+                    }
+                } else if (want_lab && k + 1 < T) {
                     ahead = element(k + 1);
                     have_ahead = true;
                     lab[e] = ahead;
@@ -471,7 +481,7 @@ __device__ __forceinline__ void win_enter(const PackJob &j, uint32_t step, WinAt
     w->T = j.nb + w->r.body + (j.ne & w->r.last);
 }
 
-template <int IN, int OUT>
+template <int IN, int OUT, bool LT>
 __global__ __launch_bounds__(kPackThreads) void k_pack_windows(PackWinJob wj) {
     const PackJob &j = wj.a.j;
     const bool want_lab = wj.a.labels != nullptr;
@@ -506,7 +516,12 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_windows(PackWinJob wj) {
                 else if (k < j.nb) id[e] = j.bos;
                 else id[e] = have_ahead ? ahead : pack_read<IN>(j.tok, w.d0 + w.r.a + (k - j.nb));
                 have_ahead = false;
-                if (want_lab && k < body_end) {
+                if (LT) {
+                    if (want_lab && k >= j.nb && k < body_end && !(wj.score_once && w.i && k < j.nb + wj.stride)) {
+                        const uint32_t v = wj.a.label_tok[w.d0 + w.r.a + (k - j.nb)];
+                        if (v != MBPE_NO_TOKEN) { lab[e] = v; ign_mask &= ~(1u << e); }
+                    }
+                } else if (want_lab && k < body_end) {
                     // the target: the document's token behind this element (index nx), eos behind the last one
                     const uint64_t nx = w.r.a + (k + 1 - j.nb);
                     bool is = true;
@@ -581,7 +596,7 @@ __device__ __forceinline__ void fit_enter(const PackJob &j, const PackFitPiece *
     f->T = j.doc_off[pc.d + 1] - f->src0 + j.nb + j.ne;
 }
 
-template <int IN, int OUT>
+template <int IN, int OUT, bool LT>
 __global__ __launch_bounds__(kPackThreads) void k_pack_fit(PackFitJob fj) {
     const PackJob &j = fj.a.j;
     const bool want_lab = fj.a.labels != nullptr;
@@ -623,7 +638,12 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_fit(PackFitJob fj) {
                 const uint64_t k = f.k0 + (col - f.col0);
                 id[e] = have_ahead ? ahead : element(k);
                 have_ahead = false;
-                if (want_lab && k + 1 < f.T) {
+                if (LT) {
+                    if (want_lab && k >= j.nb && !(j.ne && k == f.T - 1)) {
+                        const uint32_t v = fj.a.label_tok[f.src0 + (k - j.nb)];
+                        if (v != MBPE_NO_TOKEN) { lab[e] = v; ign_mask &= ~(1u << e); }
+                    }
+                } else if (want_lab && k + 1 < f.T) {
                     ahead = element(k + 1);
                     have_ahead = col + 1 < f.end;
                     lab[e] = ahead;
@@ -682,18 +702,25 @@ uint32_t aux_grid(uint64_t n_out) {
 template <int IN, int OUT>
 void launch_pack_aux(hipStream_t stream, bool packed, const PackAuxJob &a) {
     const dim3 grid(aux_grid(a.j.n_out)), block(kPackThreads);
-    if (packed) hipLaunchKernelGGL((k_pack_aux<IN, OUT, true>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((k_pack_aux<IN, OUT, false>), grid, block, 0, stream, a);
+    if (a.label_tok) {                                           // (kernels of their own: the others stay what they were)
+        if (packed) hipLaunchKernelGGL((k_pack_aux<IN, OUT, true, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((k_pack_aux<IN, OUT, false, true>), grid, block, 0, stream, a);
+    } else if (packed) hipLaunchKernelGGL((k_pack_aux<IN, OUT, true, false>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((k_pack_aux<IN, OUT, false, false>), grid, block, 0, stream, a);
 }
 
 template <int IN, int OUT>
 void launch_pack_windows(hipStream_t stream, const PackWinJob &wj) {
-    hipLaunchKernelGGL((k_pack_windows<IN, OUT>), dim3(aux_grid(wj.a.j.n_out)), dim3(kPackThreads), 0, stream, wj);
+    const dim3 grid(aux_grid(wj.a.j.n_out)), block(kPackThreads);
+    if (wj.a.label_tok) hipLaunchKernelGGL((k_pack_windows<IN, OUT, true>), grid, block, 0, stream, wj);
+    else hipLaunchKernelGGL((k_pack_windows<IN, OUT, false>), grid, block, 0, stream, wj);
 }
 
 template <int IN, int OUT>
 void launch_pack_fit(hipStream_t stream, const PackFitJob &fj) {
-    hipLaunchKernelGGL((k_pack_fit<IN, OUT>), dim3(aux_grid(fj.a.j.n_out)), dim3(kPackThreads), 0, stream, fj);
+    const dim3 grid(aux_grid(fj.a.j.n_out)), block(kPackThreads);
+    if (fj.a.label_tok) hipLaunchKernelGGL((k_pack_fit<IN, OUT, true>), grid, block, 0, stream, fj);
+    else hipLaunchKernelGGL((k_pack_fit<IN, OUT, false>), grid, block, 0, stream, fj);
 }
 
 // device time of the calling thread's latest one-shot pack or unpack kernel (mbpe_pack_kernel_ms)
@@ -702,7 +729,8 @@ thread_local float g_pack_ms = 0.f;
 int pack_run(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
              const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec &spec, void *ids_out, uint64_t n_rows,
              int out_on_device, uint32_t *len_out, const mbpe_pack_aux *aux, const mbpe_pack_window *win = nullptr,
-             const struct mbpe_pack_fit *fit = nullptr, const PackFitPlan *plan = nullptr) {
+             const struct mbpe_pack_fit *fit = nullptr, const PackFitPlan *plan = nullptr,
+             const uint32_t *label_tokens = nullptr) {
     int rc = find_device(device_id);
     if (rc != MBPE_OK) return rc;
     OneShot dev;
@@ -711,6 +739,8 @@ int pack_run(int device_id, const void *tokens, uint64_t n_tokens, uint32_t toke
     const uint64_t id_bytes = n_rows * spec.seq_len * (spec.out_bits / 8);
     void *d_tok = const_cast<void *>(tokens), *d_off = nullptr, *d_ids = ids_out, *d_len = len_out;
     if (!tokens_on_device) rc = dev.alloc(&d_tok, n_tokens * (token_bits / 8), tokens);
+    void *d_lab_tok = const_cast<uint32_t *>(label_tokens);      // on the same side as the tokens
+    if (rc == MBPE_OK && label_tokens && !tokens_on_device) rc = dev.alloc(&d_lab_tok, n_tokens * 4, label_tokens);
     if (rc == MBPE_OK) rc = dev.alloc(&d_off, (n_docs + 1) * 8, doc_tok_off);
     if (rc == MBPE_OK && !out_on_device) {
         rc = dev.alloc(&d_ids, id_bytes, nullptr);
@@ -741,7 +771,8 @@ int pack_run(int device_id, const void *tokens, uint64_t n_tokens, uint32_t toke
         if (rc == MBPE_OK) rc = dev.alloc(&d_row_first, (n_rows + 1) * 8, plan->row_first.data());
     }
     if (rc != MBPE_OK) return rc;
-    const PackSrc src = {d_tok, static_cast<const unsigned long long *>(d_off), n_docs, n_tokens, token_bits};
+    const PackSrc src = {d_tok, static_cast<const unsigned long long *>(d_off), n_docs, n_tokens, token_bits,
+                         static_cast<const uint32_t *>(d_lab_tok)};
     const PackDst dst = {d_ids, static_cast<uint32_t *>(d_len), n_rows};
     PCHK(hipEventRecord(dev.ev0, dev.stream));
     if (fit) {
@@ -894,7 +925,8 @@ void pack_launch(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &s
 
 void pack_launch_aux(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst,
                      const mbpe_pack_aux &aux) {
-    const PackAuxJob a = {pack_job(src, spec, dst), aux.labels, aux.pos, aux.seg, (unsigned long long)aux.ignore_label};
+    const PackAuxJob a = {pack_job(src, spec, dst), aux.labels, aux.pos, aux.seg, (unsigned long long)aux.ignore_label,
+                          src.label_tok};
     const bool packed = spec.layout == MBPE_PACK_PACKED;
     if (src.bits == 16) {
         if (spec.out_bits == 16) launch_pack_aux<16, 16>(stream, packed, a);
@@ -909,7 +941,7 @@ void pack_launch_aux(hipStream_t stream, const PackSrc &src, const mbpe_pack_spe
 static PackWinJob pack_win_job(const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst, const mbpe_pack_aux &aux,
                                const mbpe_pack_window &win, const unsigned long long *row_start) {
     PackWinJob wj = {};
-    wj.a = {pack_job(src, spec, dst), aux.labels, aux.pos, aux.seg, (unsigned long long)aux.ignore_label};
+    wj.a = {pack_job(src, spec, dst), aux.labels, aux.pos, aux.seg, (unsigned long long)aux.ignore_label, src.label_tok};
     wj.row_start = row_start;
     wj.row_doc = win.row_doc;
     wj.row_tok0 = reinterpret_cast<unsigned long long *>(win.row_tok0);
@@ -969,7 +1001,7 @@ uint64_t pack_fit_piece_bytes(const PackFitPlan &plan) { return plan.pieces.size
 void pack_launch_fit(hipStream_t stream, const PackSrc &src, const mbpe_pack_spec &spec, const PackDst &dst,
                      const mbpe_pack_aux &aux, const void *pieces, const unsigned long long *row_first) {
     PackFitJob fj = {};
-    fj.a = {pack_job(src, spec, dst), aux.labels, aux.pos, aux.seg, (unsigned long long)aux.ignore_label};
+    fj.a = {pack_job(src, spec, dst), aux.labels, aux.pos, aux.seg, (unsigned long long)aux.ignore_label, src.label_tok};
     fj.pieces = static_cast<const PackFitPiece *>(pieces);
     fj.row_first = row_first;
     if (src.bits == 16) {
@@ -1080,13 +1112,25 @@ int mbpe_pack_tokens(int device_id, const void *tokens, uint64_t n_tokens, uint3
     }
 }
 
-int mbpe_pack_tokens_aux(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
-                         const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
-                         uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
-                         const mbpe_pack_aux *aux) {
+// The three aux calls and their _labels forms share one implementation each.  with_labels: label_tokens is required
+// (n_tokens entries on the side of the tokens, 4-byte aligned there); otherwise it is NULL
+static int label_tokens_check(const std::string &who, bool with_labels, const uint32_t *label_tokens, uint64_t n_tokens,
+                              int tokens_on_device) {
+    if (!with_labels) return MBPE_OK;
+    if (!label_tokens && n_tokens) return fail(MBPE_ERR_ARG, who + ": NULL argument");
+    if (tokens_on_device && (uint64_t)(uintptr_t)label_tokens % 4)
+        return fail(MBPE_ERR_ARG, who + ": label_tokens is not aligned to its elements");
+    return MBPE_OK;
+}
+
+static int pack_aux_entry(const std::string &who, bool with_labels, int device_id, const void *tokens, uint64_t n_tokens,
+                          uint32_t token_bits, int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs,
+                          const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
+                          uint32_t *len_out, uint64_t *n_rows_out, const mbpe_pack_aux *aux, const uint32_t *label_tokens) {
     if (n_rows_out) *n_rows_out = 0;
     if (!n_rows_out || !doc_tok_off || !spec || !aux || (!tokens && n_tokens))
-        return fail(MBPE_ERR_ARG, "mbpe_pack_tokens_aux: NULL argument");
+        return fail(MBPE_ERR_ARG, who + ": NULL argument");
+    if (const int rc0 = label_tokens_check(who, with_labels, label_tokens, n_tokens, tokens_on_device)) return rc0;
     int rc = pack_check_spec(spec, token_bits);
     if (rc == MBPE_OK) rc = mbpe_host::check_doc_tok_off(doc_tok_off, n_docs, n_tokens);
     if (rc != MBPE_OK) return rc;
@@ -1101,19 +1145,39 @@ int mbpe_pack_tokens_aux(int device_id, const void *tokens, uint64_t n_tokens, u
     if (out_on_device && (uint64_t)(uintptr_t)len_out % 4) return fail(MBPE_ERR_ARG, "len_out is not aligned to its elements");
     try {
         return pack_run(device_id, tokens, n_tokens, token_bits, tokens_on_device, doc_tok_off, n_docs, *spec, ids_out,
-                        n_rows, out_on_device, len_out, aux);
+                        n_rows, out_on_device, len_out, aux, nullptr, nullptr, nullptr, label_tokens);
     } catch (const std::bad_alloc &) {
-        return fail(MBPE_ERR_OOM, "mbpe_pack_tokens_aux: host allocation failed");
+        return fail(MBPE_ERR_OOM, who + ": host allocation failed");
     }
 }
 
-int mbpe_pack_windows(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
-                      const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
-                      uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
-                      const mbpe_pack_aux *aux, const mbpe_pack_window *win) {
+int mbpe_pack_tokens_aux(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
+                         const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
+                         uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                         const mbpe_pack_aux *aux) {
+    return pack_aux_entry("mbpe_pack_tokens_aux", false, device_id, tokens, n_tokens, token_bits, tokens_on_device,
+                          doc_tok_off, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, aux, nullptr);
+}
+
+int mbpe_pack_tokens_aux_labels(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits,
+                                int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs,
+                                const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
+                                uint32_t *len_out, uint64_t *n_rows_out, const mbpe_pack_aux *aux,
+                                const uint32_t *label_tokens) {
+    return pack_aux_entry("mbpe_pack_tokens_aux_labels", true, device_id, tokens, n_tokens, token_bits, tokens_on_device,
+                          doc_tok_off, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, aux,
+                          label_tokens);
+}
+
+static int pack_windows_entry(const std::string &who, bool with_labels, int device_id, const void *tokens, uint64_t n_tokens,
+                              uint32_t token_bits, int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs,
+                              const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
+                              uint32_t *len_out, uint64_t *n_rows_out, const mbpe_pack_aux *aux,
+                              const mbpe_pack_window *win, const uint32_t *label_tokens) {
     if (n_rows_out) *n_rows_out = 0;
     if (!n_rows_out || !doc_tok_off || !spec || !aux || !win || (!tokens && n_tokens))
-        return fail(MBPE_ERR_ARG, "mbpe_pack_windows: NULL argument");
+        return fail(MBPE_ERR_ARG, who + ": NULL argument");
+    if (const int rc0 = label_tokens_check(who, with_labels, label_tokens, n_tokens, tokens_on_device)) return rc0;
     int rc = pack_check_windows(spec, token_bits, aux, win, n_docs, ids_out, out_on_device);
     if (rc == MBPE_OK) rc = mbpe_host::check_doc_tok_off(doc_tok_off, n_docs, n_tokens);
     if (rc != MBPE_OK) return rc;
@@ -1127,10 +1191,28 @@ int mbpe_pack_windows(int device_id, const void *tokens, uint64_t n_tokens, uint
     if (out_on_device && (uint64_t)(uintptr_t)len_out % 4) return fail(MBPE_ERR_ARG, "len_out is not aligned to its elements");
     try {
         return pack_run(device_id, tokens, n_tokens, token_bits, tokens_on_device, doc_tok_off, n_docs, *spec, ids_out,
-                        n_rows, out_on_device, len_out, aux, win);
+                        n_rows, out_on_device, len_out, aux, win, nullptr, nullptr, label_tokens);
     } catch (const std::bad_alloc &) {
-        return fail(MBPE_ERR_OOM, "mbpe_pack_windows: host allocation failed");
+        return fail(MBPE_ERR_OOM, who + ": host allocation failed");
     }
+}
+
+int mbpe_pack_windows(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
+                      const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
+                      uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                      const mbpe_pack_aux *aux, const mbpe_pack_window *win) {
+    return pack_windows_entry("mbpe_pack_windows", false, device_id, tokens, n_tokens, token_bits, tokens_on_device,
+                              doc_tok_off, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, aux, win,
+                              nullptr);
+}
+
+int mbpe_pack_windows_labels(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
+                             const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
+                             uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                             const mbpe_pack_aux *aux, const mbpe_pack_window *win, const uint32_t *label_tokens) {
+    return pack_windows_entry("mbpe_pack_windows_labels", true, device_id, tokens, n_tokens, token_bits, tokens_on_device,
+                              doc_tok_off, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, aux, win,
+                              label_tokens);
 }
 
 int mbpe_pack_cu_seqlens(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, int32_t *cu_out,
@@ -1210,13 +1292,15 @@ int mbpe_pack_fit_cu_seqlens(const uint64_t *doc_tok_off, uint64_t n_docs, const
     }
 }
 
-int mbpe_pack_fit(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
-                  const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
-                  uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out, const mbpe_pack_aux *aux,
-                  const struct mbpe_pack_fit *fit) {
+static int pack_fit_entry(const std::string &who, bool with_labels, int device_id, const void *tokens, uint64_t n_tokens,
+                          uint32_t token_bits, int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs,
+                          const mbpe_pack_spec *spec, void *ids_out, uint64_t cap_rows, int out_on_device,
+                          uint32_t *len_out, uint64_t *n_rows_out, const mbpe_pack_aux *aux,
+                          const struct mbpe_pack_fit *fit, const uint32_t *label_tokens) {
     if (n_rows_out) *n_rows_out = 0;
     if (!n_rows_out || !doc_tok_off || !spec || !aux || !fit || (!tokens && n_tokens))
-        return fail(MBPE_ERR_ARG, "mbpe_pack_fit: NULL argument");
+        return fail(MBPE_ERR_ARG, who + ": NULL argument");
+    if (const int rc0 = label_tokens_check(who, with_labels, label_tokens, n_tokens, tokens_on_device)) return rc0;
     int rc = pack_check_fit(spec, token_bits, aux, fit, n_docs, ids_out, out_on_device);
     if (rc == MBPE_OK) rc = mbpe_host::check_doc_tok_off(doc_tok_off, n_docs, n_tokens);
     if (rc != MBPE_OK) return rc;
@@ -1240,10 +1324,27 @@ int mbpe_pack_fit(int device_id, const void *tokens, uint64_t n_tokens, uint32_t
             return pack_fit_doc_out(dev.stream, *fit, plan, 1);
         }
         return pack_run(device_id, tokens, n_tokens, token_bits, tokens_on_device, doc_tok_off, n_docs, *spec, ids_out,
-                        n_rows, out_on_device, len_out, aux, nullptr, fit, &plan);
+                        n_rows, out_on_device, len_out, aux, nullptr, fit, &plan, label_tokens);
     } catch (const std::bad_alloc &) {
-        return fail(MBPE_ERR_OOM, "mbpe_pack_fit: host allocation failed");
+        return fail(MBPE_ERR_OOM, who + ": host allocation failed");
     }
+}
+
+int mbpe_pack_fit(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
+                  const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
+                  uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out, const mbpe_pack_aux *aux,
+                  const struct mbpe_pack_fit *fit) {
+    return pack_fit_entry("mbpe_pack_fit", false, device_id, tokens, n_tokens, token_bits, tokens_on_device, doc_tok_off,
+                          n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, aux, fit, nullptr);
+}
+
+int mbpe_pack_fit_labels(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits, int tokens_on_device,
+                         const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
+                         uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
+                         const mbpe_pack_aux *aux, const struct mbpe_pack_fit *fit, const uint32_t *label_tokens) {
+    return pack_fit_entry("mbpe_pack_fit_labels", true, device_id, tokens, n_tokens, token_bits, tokens_on_device,
+                          doc_tok_off, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, aux, fit,
+                          label_tokens);
 }
 
 int mbpe_unpack_tokens(int device_id, const void *ids, uint64_t n_rows, uint32_t seq_len, uint32_t id_bits,

@@ -6,6 +6,7 @@
 
 #include "dropout.h"
 #include "fim.h"
+#include "mlm.h"
 #include "mbpe.h"
 #include "mbpe_tokenizer.h"
 
@@ -68,6 +69,7 @@ mbpe_encoder *Tokenizer::device_encoder(int device) {
     if (rc == MBPE_OK) rc = mbpe_encoder_set_option(encoder_, "dedup", encode_dedup_ ? 1 : 0);
     if (rc == MBPE_OK) rc = mbpe_encoder_set_dropout(encoder_, drop_threshold_, drop_seed_);
     if (rc == MBPE_OK) rc = mbpe_encoder_set_fim(encoder_, fim_on_ ? &fim_ : nullptr);
+    if (rc == MBPE_OK) rc = mbpe_encoder_set_mlm(encoder_, mlm_on_ ? &mlm_ : nullptr);
     if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
     return encoder_;
 }
@@ -1355,6 +1357,20 @@ int mbpe_tok_set_encode_fim(mbpe_tokenizer *t, const mbpe_fim_spec *spec) {
         }
     }
     t->t->set_fim(spec);
+    return MBPE_OK;
+}
+
+int mbpe_tok_set_encode_mlm(mbpe_tokenizer *t, const mbpe_mlm_spec *spec) {
+    if (!t) return MBPE_ERR_ARG;
+    if (spec) {
+        const char *msg = "";
+        const int rc = mbpe::mlm_check_spec(spec, 32, &msg);
+        if (rc != MBPE_OK) {
+            mbpe_host::set_last_error(std::string("mbpe_tok_set_encode_mlm: ") + msg);
+            return rc;
+        }
+    }
+    t->t->set_mlm(spec);
     return MBPE_OK;
 }
 

@@ -121,6 +121,8 @@ public:
     // off.  The kept device encoder is re-configured, not re-created; the plan of its latest batch call is its own
     // (mbpe_encoder_fim_info on kept_encoder(), NULL before the first device call)
     void set_fim(const mbpe_fim_spec *spec) { fim_on_ = spec != nullptr; if (spec) fim_ = *spec; }
+    // masked-LM corruption of the same calls (mbpe_tok_set_encode_mlm; mbpe.h holds the rule): NULL = off
+    void set_mlm(const mbpe_mlm_spec *spec) { mlm_on_ = spec != nullptr; if (spec) mlm_ = *spec; }
     mbpe_encoder *kept_encoder() const { return encoder_; }
     // the option "unicode" of every device split made from here on (mbpe_tok_set_split_unicode)
     void set_split_unicode(bool on) { split_unicode_ = on; }
@@ -251,6 +253,8 @@ private:
     uint64_t drop_threshold_ = 0, drop_seed_ = 0;
     bool fim_on_ = false;
     mbpe_fim_spec fim_ = {};
+    bool mlm_on_ = false;
+    mbpe_mlm_spec mlm_ = {};
     std::vector<uint64_t> counts_;           // count_tokens: the table, and the weighted token total it has reached
     uint64_t counts_total_ = 0;
 };

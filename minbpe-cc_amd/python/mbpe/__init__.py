@@ -54,6 +54,8 @@ EXPORTS = [
     "mbpe_pack_fit", "mbpe_pack_fit_plan", "mbpe_pack_fit_cu_seqlens", "mbpe_encoder_encode_batch_fit",
     "mbpe_encoder_encode_batch_endmask_fit",
     "mbpe_fim_plan", "mbpe_fim_tokens", "mbpe_fim_kernel_ms", "mbpe_encoder_set_fim", "mbpe_encoder_fim_info",
+    "mbpe_mlm_plan", "mbpe_mlm_tokens", "mbpe_mlm_kernel_ms", "mbpe_pack_tokens_aux_labels", "mbpe_pack_windows_labels",
+    "mbpe_pack_fit_labels", "mbpe_encoder_set_mlm",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -69,7 +71,7 @@ TOK_EXPORTS = [
     "mbpe_tok_train_pieces_export_size", "mbpe_tok_train_pieces_export", "mbpe_tok_train_pieces_merge",
     "mbpe_tok_encode_batch_windows_device", "mbpe_tok_count_tokens", "mbpe_tok_token_counts",
     "mbpe_tok_token_counts_reset", "mbpe_tok_encode_batch_fit_device", "mbpe_tok_set_encode_fim",
-    "mbpe_tok_encode_fim_info",
+    "mbpe_tok_encode_fim_info", "mbpe_tok_set_encode_mlm",
 ]
 
 
@@ -146,6 +148,16 @@ class FimSpec(ctypes.Structure):
 
 
 FIM_NONE, FIM_PSM, FIM_SPM = 0, 1, 2      # the modes of fim_plan / fim_info
+
+
+class MlmSpec(ctypes.Structure):
+    """mbpe_mlm_spec (include/mbpe.h): masked-LM corruption; mlm_spec() makes one from rates."""
+    _fields_ = [
+        ("select", ctypes.c_uint64), ("mask", ctypes.c_uint64), ("random", ctypes.c_uint64), ("seed", ctypes.c_uint64),
+        ("doc_base", ctypes.c_uint64), ("mask_id", ctypes.c_uint32), ("vocab_n", ctypes.c_uint32),
+        ("whole_word", ctypes.c_uint32), ("n_protect", ctypes.c_uint32), ("protect", ctypes.c_uint32 * 8),
+    ]
+
 
 _ID_DTYPES = {16: np.uint16, 32: np.uint32, 64: np.uint64}
 # labels are ids or ignore_label: signed where a negative ignore_label fits
@@ -365,6 +377,14 @@ def lib():
     L.mbpe_encoder_fim_info.argtypes = [vp, vp, vp, u64, vp]
     L.mbpe_tok_set_encode_fim.argtypes = [vp, vp]
     L.mbpe_tok_encode_fim_info.argtypes = [vp, vp, vp, u64, vp]
+    L.mbpe_mlm_plan.argtypes = [vp, u64, u32, vp, u64, vp, vp, vp]
+    L.mbpe_mlm_tokens.argtypes = [i32, vp, u64, u32, i32, vp, u64, vp, vp, vp, i32]
+    L.mbpe_mlm_kernel_ms.argtypes = [vp]
+    L.mbpe_pack_tokens_aux_labels.argtypes = L.mbpe_pack_tokens_aux.argtypes + [vp]
+    L.mbpe_pack_windows_labels.argtypes = L.mbpe_pack_windows.argtypes + [vp]
+    L.mbpe_pack_fit_labels.argtypes = L.mbpe_pack_fit.argtypes + [vp]
+    L.mbpe_encoder_set_mlm.argtypes = [vp, vp]
+    L.mbpe_tok_set_encode_mlm.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -567,6 +587,78 @@ def fim_kernel_ms():
     return ms.value
 
 
+def mlm_spec(rate, mask_id, vocab_n, mask_share=0.8, random_share=0.1, seed=0, doc_base=0, whole_word=False, protect=()):
+    """An MlmSpec from probabilities: a token (with whole_word: a word) is selected with probability `rate`; a selected
+    token becomes mask_id with probability mask_share, a random id below vocab_n with probability random_share, and
+    stays otherwise -- a target either way.  seed picks the epoch's draw, doc_base is the number of the call's first
+    document in the corpus; protect: up to 8 ids that are never selected (bos, eos, separators).  Random ids may be
+    special ids unless vocab_n excludes them.  The rule: include/mbpe.h, mbpe_mlm_spec."""
+    protect = [int(p) for p in protect]
+    if len(protect) > 8:
+        raise MbpeError(ERR_ARG, "mlm_spec: more than 8 protected ids")
+    # (shares that sum to more than 1 give thresholds that sum to more than 2^32, which the library refuses)
+    return MlmSpec(dropout_threshold(rate), dropout_threshold(mask_share), dropout_threshold(random_share),
+                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(doc_base) & 0xFFFFFFFFFFFFFFFF, mask_id, vocab_n,
+                   int(bool(whole_word)), len(protect), (ctypes.c_uint32 * 8)(*protect))
+
+
+def _mlm_host_tokens(tokens, word_ends):
+    t = np.ascontiguousarray(tokens)
+    if t.dtype not in (np.dtype(np.uint16), np.dtype(np.uint32)):
+        t = t.astype(np.uint32)
+    t = t.reshape(-1)
+    if word_ends is not None:
+        if t.dtype != np.dtype(np.uint32):
+            raise MbpeError(ERR_ARG, "word_ends go into bit 31 of 32-bit tokens: 16-bit tokens have no room for them")
+        w = np.ascontiguousarray(word_ends, dtype=bool).reshape(-1)
+        if len(w) != len(t):
+            raise ValueError("word_ends must have one entry per token")
+        t = t | (w.astype(np.uint32) << np.uint32(31))
+    return t
+
+
+def mlm_plan(tokens, doc_tok_off, spec, word_ends=None):
+    """mbpe_mlm_plan (host only): the rule over a flat token array (uint16 or uint32; bit 31 of a uint32 token, or
+    word_ends, marks the last token of a word) -> (tokens after it, same dtype; targets uint32, NO_TOKEN = none)."""
+    t = _mlm_host_tokens(tokens, word_ends)
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    out, tgt = np.zeros(max(len(t), 1), dtype=t.dtype), np.zeros(max(len(t), 1), dtype=np.uint32)
+    _check(lib().mbpe_mlm_plan(t.ctypes.data if len(t) else None, len(t), t.dtype.itemsize * 8, off.ctypes.data,
+                               len(off) - 1, ctypes.byref(spec), out.ctypes.data, tgt.ctypes.data))
+    return out[:len(t)], tgt[:len(t)]
+
+
+def mlm_tokens(tokens, doc_tok_off, spec, word_ends=None, device=0, tokens_ptr=None, n_tokens=None, token_bits=None,
+               out_ptr=None, targets_ptr=None):
+    """mbpe_mlm_tokens: masked-LM corruption of a flat token array (uint16 or uint32) whose document i is
+    tokens[doc_tok_off[i]:doc_tok_off[i + 1]] -> (tokens of the same dtype, targets uint32 with NO_TOKEN where a token
+    is no target): what pack_tokens_aux, pack_windows and pack_fit take as tokens and label_tokens=.  whole_word needs
+    the word ends: bit 31 of uint32 tokens, or word_ends= (a bool per token), which is ORed into it.  Device memory:
+    tokens_ptr= / n_tokens= / token_bits= name the tokens there instead of `tokens`; with out_ptr= (and targets_ptr=,
+    or None) the results are written there and None is returned."""
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    if tokens_ptr is None:
+        t = _mlm_host_tokens(tokens, word_ends)
+        tp, n_tokens, token_bits, on_dev = (t.ctypes.data if len(t) else None), len(t), t.dtype.itemsize * 8, 0
+    else:
+        tp, on_dev = _ptr(tokens_ptr), 1
+    head = (device, tp, n_tokens, token_bits, on_dev, off.ctypes.data, len(off) - 1, ctypes.byref(spec))
+    if out_ptr is not None:
+        _check(lib().mbpe_mlm_tokens(*head, _ptr(out_ptr), _ptr(targets_ptr), 1))
+        return None
+    out = np.zeros(max(n_tokens, 1), dtype=_ID_DTYPES[token_bits])
+    tgt = np.zeros(max(n_tokens, 1), dtype=np.uint32)
+    _check(lib().mbpe_mlm_tokens(*head, out.ctypes.data, tgt.ctypes.data, 0))
+    return out[:n_tokens], tgt[:n_tokens]
+
+
+def mlm_kernel_ms():
+    """Device time of the kernels of this thread's latest mlm_tokens (mbpe_mlm_kernel_ms)."""
+    ms = ctypes.c_float()
+    _check(lib().mbpe_mlm_kernel_ms(ctypes.byref(ms)))
+    return ms.value
+
+
 def _fim_info(fn, handle):
     n = ctypes.c_uint64()
     _check(fn(handle, None, None, 0, ctypes.byref(n)))
@@ -619,6 +711,18 @@ def pack_cu_seqlens(doc_tok_off, seq_len, bos_id=None, eos_id=None):
     return cu, longest.value
 
 
+def _label_call(fn, fn_labels, label_tokens, on_dev, n_tokens):
+    """label_tokens= of the pack calls -> (the entry point, its trailing arguments, what keeps them alive)"""
+    if label_tokens is None:
+        return fn, (), None
+    if on_dev:
+        return fn_labels, (_ptr(int(label_tokens)),), None
+    a = np.ascontiguousarray(label_tokens, dtype=np.uint32).reshape(-1)
+    if len(a) != n_tokens:
+        raise ValueError("label_tokens must have one entry per token")
+    return fn_labels, (a.ctypes.data if len(a) else None,), a
+
+
 class _AuxCall:
     """What the three *_aux calls share: the mbpe_pack_aux of a call and the dict it returns."""
 
@@ -652,14 +756,18 @@ class _AuxCall:
 def pack_tokens_aux(tokens, doc_tok_off, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
                     pad_left=False, trunc_left=False, device=0, tokens_ptr=None, n_tokens=None, token_bits=None,
                     out_ptr=None, len_ptr=None, cap_rows=None, labels=False, positions=False, segments=False,
-                    cu_seqlens=False, ignore_label=-100, labels_ptr=None, pos_ptr=None, seg_ptr=None):
+                    cu_seqlens=False, ignore_label=-100, labels_ptr=None, pos_ptr=None, seg_ptr=None, label_tokens=None):
     """mbpe_pack_tokens_aux: pack_tokens plus what a training step needs, from one kernel -> a dict with "ids",
     "lengths" and whichever of "labels" (next-token targets that never cross a document; ignore_label elsewhere; int32
     / int64, uint16 for out_bits 16), "positions" (uint32, restarting at every document), "segments" (uint32, document
     number + 1, 0 = pad) and "cu_seqlens" with "max_seqlen" (layout "packed" only) were asked for.
     With out_ptr= the matrices go to device memory at out_ptr / len_ptr / labels_ptr / pos_ptr / seg_ptr (each 16-byte
     aligned; None = not wanted) and the row count is returned -- (row count, cu_seqlens, max_seqlen) with
-    cu_seqlens=True."""
+    cu_seqlens=True.
+    label_tokens= (here, in pack_windows and in pack_fit; mbpe_pack_tokens_aux_labels and its kin): a uint32 target per
+    token, on the side of the tokens (an array, or a device address with tokens_ptr=) -- the targets of mlm_tokens.  The
+    labels are then these targets in the cells of their tokens and ignore_label wherever the target is NO_TOKEN and in
+    bos, eos and pad cells; everything else is as without."""
     spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
     call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label)
     off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
@@ -673,19 +781,20 @@ def pack_tokens_aux(tokens, doc_tok_off, seq_len, layout="padded", out_bits=32, 
         tp, on_dev = _ptr(tokens_ptr), 1
     n_rows = ctypes.c_uint64()
     head = (device, tp, n_tokens, token_bits, on_dev, off.ctypes.data, len(off) - 1, ctypes.byref(spec))
+    fn, extra, _keep = _label_call(lib().mbpe_pack_tokens_aux, lib().mbpe_pack_tokens_aux_labels, label_tokens, on_dev,
+                                   n_tokens)
     if out_ptr is not None:
         aux = call.device(labels_ptr, pos_ptr, seg_ptr)
         cu = call.cu_seqlens(off) if cu_seqlens else None
-        _check(lib().mbpe_pack_tokens_aux(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), ctypes.byref(n_rows),
-                                          ctypes.byref(aux)))
+        _check(fn(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), ctypes.byref(n_rows), ctypes.byref(aux), *extra))
         return (n_rows.value,) + cu if cu_seqlens else n_rows.value
     aux = call.device(None, None, None)
-    _check(lib().mbpe_pack_tokens_aux(*head, None, 0, 0, None, ctypes.byref(n_rows), ctypes.byref(aux)))
+    _check(fn(*head, None, 0, 0, None, ctypes.byref(n_rows), ctypes.byref(aux), *extra))
     ids, lengths = _matrix(n_rows.value, spec)
     aux, arrays = call.host(n_rows.value)
     if n_rows.value:
-        _check(lib().mbpe_pack_tokens_aux(*head, ids.ctypes.data, n_rows.value, 0, lengths.ctypes.data,
-                                          ctypes.byref(n_rows), ctypes.byref(aux)))
+        _check(fn(*head, ids.ctypes.data, n_rows.value, 0, lengths.ctypes.data, ctypes.byref(n_rows), ctypes.byref(aux),
+                  *extra))
     return call.result(ids, lengths, arrays, off)
 
 
@@ -727,7 +836,7 @@ class _WinCall(_AuxCall):
 def pack_windows(tokens, doc_tok_off, seq_len, stride, score_once=False, out_bits=32, pad_id=0, bos_id=None, eos_id=None,
                  device=0, tokens_ptr=None, n_tokens=None, token_bits=None, out_ptr=None, len_ptr=None, cap_rows=None,
                  labels=False, positions=False, segments=False, ignore_label=-100, labels_ptr=None, pos_ptr=None,
-                 seg_ptr=None, row_doc=False, row_tok0=False, row_doc_ptr=None, row_tok0_ptr=None):
+                 seg_ptr=None, row_doc=False, row_tok0=False, row_doc_ptr=None, row_tok0_ptr=None, label_tokens=None):
     """mbpe_pack_windows: one document per row like pack_tokens_aux(layout="padded"), but a document longer than
     keep = seq_len - (bos) - (eos) tokens becomes several rows of its own, consecutive ones sharing `stride` tokens
     (window i holds tokens [i * (keep - stride), i * (keep - stride) + keep); bos in every row, eos in the last).
@@ -748,8 +857,9 @@ def pack_windows(tokens, doc_tok_off, seq_len, stride, score_once=False, out_bit
     else:
         tp, on_dev = _ptr(tokens_ptr), 1
     head = (device, tp, n_tokens, token_bits, on_dev, off.ctypes.data, len(off) - 1, ctypes.byref(spec))
-    tail = lambda n_rows, aux, win: (ctypes.byref(n_rows), ctypes.byref(aux), ctypes.byref(win))
-    return call.run(lib().mbpe_pack_windows, head, tail, out_ptr, len_ptr, cap_rows,
+    fn, extra, _keep = _label_call(lib().mbpe_pack_windows, lib().mbpe_pack_windows_labels, label_tokens, on_dev, n_tokens)
+    tail = lambda n_rows, aux, win: (ctypes.byref(n_rows), ctypes.byref(aux), ctypes.byref(win)) + extra
+    return call.run(fn, head, tail, out_ptr, len_ptr, cap_rows,
                     (labels_ptr, pos_ptr, seg_ptr, row_doc_ptr, row_tok0_ptr))
 
 
@@ -837,7 +947,7 @@ class _FitCall(_AuxCall):
 def pack_fit(tokens, doc_tok_off, seq_len, out_bits=32, pad_id=0, bos_id=None, eos_id=None, device=0, tokens_ptr=None,
              n_tokens=None, token_bits=None, out_ptr=None, len_ptr=None, cap_rows=None, labels=False, positions=False,
              segments=False, cu_seqlens=False, ignore_label=-100, labels_ptr=None, pos_ptr=None, seg_ptr=None,
-             doc_row=False, doc_col=False, doc_row_ptr=None, doc_col_ptr=None):
+             doc_row=False, doc_col=False, doc_row_ptr=None, doc_col_ptr=None, label_tokens=None):
     """mbpe_pack_fit: best-fit packing.  Every document [bos] doc [eos] stays whole and shares its row with others;
     only a document longer than seq_len is cut, into full rows of its own and one tail.  The pieces are placed by size
     descending into the row with the least room that still holds them, so padding stays small and lies at the right
@@ -858,8 +968,9 @@ def pack_fit(tokens, doc_tok_off, seq_len, out_bits=32, pad_id=0, bos_id=None, e
     else:
         tp, on_dev = _ptr(tokens_ptr), 1
     head = (device, tp, n_tokens, token_bits, on_dev, off.ctypes.data, len(off) - 1, ctypes.byref(spec))
-    tail = lambda n_rows, aux, fit: (ctypes.byref(n_rows), ctypes.byref(aux), ctypes.byref(fit))
-    return call.run(lib().mbpe_pack_fit, head, tail, len(off) - 1, lambda: off, out_ptr, len_ptr, cap_rows,
+    fn, extra, _keep = _label_call(lib().mbpe_pack_fit, lib().mbpe_pack_fit_labels, label_tokens, on_dev, n_tokens)
+    tail = lambda n_rows, aux, fit: (ctypes.byref(n_rows), ctypes.byref(aux), ctypes.byref(fit)) + extra
+    return call.run(fn, head, tail, len(off) - 1, lambda: off, out_ptr, len_ptr, cap_rows,
                     (labels_ptr, pos_ptr, seg_ptr, doc_row_ptr, doc_col_ptr))
 
 
@@ -978,6 +1089,11 @@ class Encoder:
         their endmask forms; the flat calls and count() are unaffected.  doc_tok_off of those calls is the one after
         the transform."""
         _check(lib().mbpe_encoder_set_fim(self._h, None if spec is None else ctypes.byref(spec)))
+
+    def set_mlm(self, spec):
+        """Masked-LM corruption for the batch calls that follow (mbpe_encoder_set_mlm): an MlmSpec (mlm_spec()), or None
+        to turn it off.  The matrices hold the corrupted ids and "labels" the targets."""
+        _check(lib().mbpe_encoder_set_mlm(self._h, None if spec is None else ctypes.byref(spec)))
 
     def fim_info(self):
         """The plan of the latest batch call (mbpe_encoder_fim_info) -> (mode uint8[n_docs], cuts uint64[n_docs, 2]);
@@ -2232,7 +2348,7 @@ class Tokenizer:
     def load(self, path, verbose=False):
         _check(lib().mbpe_tok_load(self._h, os.fsencode(path), int(verbose)))
 
-    def _encode_split(self, device_split, order="greedy", dropout=0.0, seed=0, dedup=False, fim=None):
+    def _encode_split(self, device_split, order="greedy", dropout=0.0, seed=0, dedup=False, fim=None, mlm=None):
         if order not in ("greedy", "rank"):
             raise ValueError('order must be "greedy" or "rank"')
         _check(lib().mbpe_tok_set_encode_dedup(self._h, int(bool(dedup))))
@@ -2241,6 +2357,7 @@ class Tokenizer:
         _check(lib().mbpe_tok_set_encode_split(self._h, int(bool(device_split))))
         _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
         _check(lib().mbpe_tok_set_encode_fim(self._h, None if fim is None else ctypes.byref(fim)))
+        _check(lib().mbpe_tok_set_encode_mlm(self._h, None if mlm is None else ctypes.byref(mlm)))
 
     def fim_info(self):
         """The fill-in-the-middle plan of the latest batch call with a device (mbpe_tok_encode_fim_info) -> (mode
@@ -2385,11 +2502,15 @@ class Tokenizer:
                          pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
                          labels=False, positions=False, segments=False, cu_seqlens=False, ignore_label=-100,
                          labels_ptr=None, pos_ptr=None, seg_ptr=None, device_split=False, order="greedy", dropout=0.0,
-                         seed=0, dedup=False, fim=None):
+                         seed=0, dedup=False, fim=None, mlm=None):
         """encode_batch_padded plus labels, positions, segments and cu_seqlens (mbpe_tok_encode_batch_aux_device): its
         arguments and those of pack_tokens_aux, whose dict (or, with out_ptr=, row count) is returned.  The documents'
-        token offsets of the call (with fim: after the transform): self.doc_tok_off."""
-        self._encode_split(device_split, order, dropout, seed, dedup, fim)
+        token offsets of the call (with fim: after the transform): self.doc_tok_off.
+        mlm (here and in _windows and _fit; mbpe_tok_set_encode_mlm): an MlmSpec (mlm_spec()) -- every text's tokens go
+        through masked-LM corruption on the device before they are packed: "ids" are the corrupted ids, "labels" the
+        targets (ignore_label in every other cell).  whole_word masks the chunks of the split pattern as wholes and
+        needs out_bits 32 or 64.  Not together with fim."""
+        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label)
         parts = [bytes(_u8(t)) for t in texts]
@@ -2425,12 +2546,13 @@ class Tokenizer:
                              eos_id=None, device=0, out_ptr=None, len_ptr=None, cap_rows=None, labels=False,
                              positions=False, segments=False, ignore_label=-100, labels_ptr=None, pos_ptr=None,
                              seg_ptr=None, row_doc=False, row_tok0=False, row_doc_ptr=None, row_tok0_ptr=None,
-                             device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False, fim=None):
+                             device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False, fim=None,
+                             mlm=None):
         """encode_batch_aux for the window layout (mbpe_tok_encode_batch_windows_device): every text split like
         encode(), encoded, and cut into rows of seq_len that share `stride` tokens where a text does not fit one --
         the keywords and the result of pack_windows ("row_doc" maps a row back to its text).  The texts' token
         offsets of the call: self.doc_tok_off."""
-        self._encode_split(device_split, order, dropout, seed, dedup, fim)
+        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm)
         spec = pack_spec(seq_len, "padded", out_bits, pad_id, bos_id, eos_id)
         call = _WinCall(spec, stride, score_once, labels, positions, segments, ignore_label, row_doc, row_tok0)
         parts = [bytes(_u8(t)) for t in texts]
@@ -2453,12 +2575,12 @@ class Tokenizer:
                          len_ptr=None, cap_rows=None, labels=False, positions=False, segments=False, cu_seqlens=False,
                          ignore_label=-100, labels_ptr=None, pos_ptr=None, seg_ptr=None, doc_row=False, doc_col=False,
                          doc_row_ptr=None, doc_col_ptr=None, device_split=False, order="greedy", dropout=0.0, seed=0,
-                         dedup=False, fim=None):
+                         dedup=False, fim=None, mlm=None):
         """encode_batch_aux for the fit layout (mbpe_tok_encode_batch_fit_device): every text split like encode(),
         encoded, and packed whole into rows of seq_len by best fit; only a text longer than a row is cut -- the
         keywords and the result of pack_fit ("doc_row" / "doc_col" say where a text's last piece begins, "segments"
         holds the text's number + 1 in every cell).  The texts' token offsets of the call: self.doc_tok_off."""
-        self._encode_split(device_split, order, dropout, seed, dedup, fim)
+        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm)
         spec = _fit_spec(seq_len, out_bits, pad_id, bos_id, eos_id)
         call = _FitCall(spec, labels, positions, segments, cu_seqlens, ignore_label, doc_row, doc_col)
         parts = [bytes(_u8(t)) for t in texts]
