@@ -815,7 +815,9 @@ class _WinCall(_AuxCall):
         n_rows = ctypes.c_uint64()
         if out_ptr is not None:
             aux, win = self.device(*ptrs[:3]), self.window(*ptrs[3:])
-            _check(fn(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail(n_rows, aux, win)))
+            rc = fn(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail(n_rows, aux, win))
+            self.n_rows = n_rows.value               # (reported also where a cap_rows too small is refused)
+            _check(rc)
             return n_rows.value
         aux, win = self.device(None, None, None), self.window()
         _check(fn(*head, None, 0, 0, None, *tail(n_rows, aux, win)))
@@ -924,7 +926,9 @@ class _FitCall(_AuxCall):
         n_rows = ctypes.c_uint64()
         if out_ptr is not None:
             aux, fit = self.device(*ptrs[:3]), PackFit(ptrs[3] or None, ptrs[4] or None)
-            _check(fn(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail(n_rows, aux, fit)))
+            rc = fn(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail(n_rows, aux, fit))
+            self.n_rows = n_rows.value               # (reported also where a cap_rows too small is refused)
+            _check(rc)
             return (n_rows.value,) + self.cu_seqlens(doc_tok_off()) if self.cu else n_rows.value
         aux, fit = self.device(None, None, None), PackFit(None, None)
         _check(fn(*head, None, 0, 0, None, *tail(n_rows, aux, fit)))
@@ -1100,29 +1104,39 @@ class Encoder:
         all zero where the stage was off."""
         return _fim_info(lib().mbpe_encoder_fim_info, self._h)
 
-    def encode(self, data, chunk_off=None, offsets=False, dtype=np.uint32, byte_off=False):
+    def encode(self, data, chunk_off=None, offsets=False, dtype=np.uint32, byte_off=False, text_ptr=None, n_bytes=None,
+               cap=None):
         """Host text -> host tokens of dtype uint32 or uint16, or (tokens, chunk_tok_off) with offsets=True: the
         tokens of chunk c are tokens[chunk_tok_off[c]:chunk_tok_off[c + 1]].  The passes made: self.n_passes.
         byte_off=True (mbpe_encoder_encode_byteoff) appends tok_byte_off to the result, n + 1 uint64 offsets: token j
-        stands for data[tok_byte_off[j]:tok_byte_off[j + 1]]."""
-        text = _u8(data)
+        stands for data[tok_byte_off[j]:tok_byte_off[j + 1]].
+        text_ptr= / n_bytes= name a text in device memory instead of `data`.  cap= the room of the host array in tokens
+        (default: n_bytes, which always suffices).  The count the library reported, also when it refused a cap that is
+        too small: self.n_out."""
         dtype = np.dtype(dtype)
         if dtype not in (np.dtype(np.uint32), np.dtype(np.uint16)):
             raise ValueError("dtype must be uint32 or uint16")
+        if text_ptr is None:
+            text = _u8(data)
+            tp, n_bytes, on_dev = (text.ctypes.data if len(text) else None), len(text), 0
+        else:
+            tp, on_dev = _ptr(text_ptr), 1
         off = None if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.uint64)
         n_chunks = 1 if off is None else len(off) - 1
-        out = np.zeros(max(len(text), 1), dtype=dtype)
+        room = n_bytes if cap is None else cap
+        out = np.zeros(max(room, 1), dtype=dtype)
         tok_off = np.zeros(n_chunks + 1, dtype=np.uint64) if offsets else None
         n, passes = ctypes.c_uint64(), ctypes.c_uint32()
-        head = (self._h, text.ctypes.data if len(text) else None, len(text), 0,
-                None if off is None else off.ctypes.data, 0 if off is None else n_chunks,
-                out.ctypes.data, len(out), dtype.itemsize * 8, 0)
+        head = (self._h, tp, n_bytes, on_dev, None if off is None else off.ctypes.data, 0 if off is None else n_chunks,
+                out.ctypes.data, room if cap is not None else len(out), dtype.itemsize * 8, 0)
         tail = (None if tok_off is None else tok_off.ctypes.data, ctypes.byref(n), ctypes.byref(passes))
         if byte_off:
             boff = np.zeros(len(out) + 1, dtype=np.uint64)
-            _check(lib().mbpe_encoder_encode_byteoff(*head, boff.ctypes.data, *tail))
+            rc = lib().mbpe_encoder_encode_byteoff(*head, boff.ctypes.data, *tail)
         else:
-            _check(lib().mbpe_encoder_encode(*head, *tail))
+            rc = lib().mbpe_encoder_encode(*head, *tail)
+        self.n_out = n.value
+        _check(rc)
         self.n_passes = passes.value
         tokens = out[:n.value].copy()
         res = (tokens, tok_off) if offsets else (tokens,)
@@ -1130,23 +1144,27 @@ class Encoder:
             res += (boff[:n.value + 1].copy(),)
         return res if len(res) > 1 else res[0]
 
-    def encode_device(self, text_ptr, n_bytes, chunk_off, out_ptr, cap, token_bits=32, offsets=False, byte_off_ptr=None):
+    def encode_device(self, text_ptr, n_bytes, chunk_off, out_ptr, cap, token_bits=32, offsets=False, byte_off_ptr=None,
+                      text_on_device=True):
         """n_bytes of text in device memory at text_ptr (e.g. a torch tensor's data_ptr(); read in place) -> tokens in
         device memory at out_ptr (0: query; room for cap tokens of token_bits bits; 32: bit 31 = chunk end, 16: plain
         ids) -> token count, or (count, chunk_tok_off) with offsets=True.  byte_off_ptr: device memory for cap + 1
-        uint64, filled with the count + 1 token byte offsets (mbpe_encoder_encode_byteoff)."""
+        uint64, filled with the count + 1 token byte offsets (mbpe_encoder_encode_byteoff).  text_on_device=False:
+        text_ptr is an address in host memory.  The count the library reported, also when it refused: self.n_out."""
         off = None if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.uint64)
         n_chunks = 1 if off is None else len(off) - 1
         tok_off = np.zeros(n_chunks + 1, dtype=np.uint64) if offsets else None
         n, passes = ctypes.c_uint64(), ctypes.c_uint32()
-        head = (self._h, ctypes.c_void_p(text_ptr) if text_ptr else None, n_bytes, 1,
+        head = (self._h, ctypes.c_void_p(text_ptr) if text_ptr else None, n_bytes, int(bool(text_on_device)),
                 None if off is None else off.ctypes.data, 0 if off is None else n_chunks,
                 ctypes.c_void_p(out_ptr) if out_ptr else None, cap, token_bits, 1)
         tail = (None if tok_off is None else tok_off.ctypes.data, ctypes.byref(n), ctypes.byref(passes))
         if byte_off_ptr:
-            _check(lib().mbpe_encoder_encode_byteoff(*head, ctypes.c_void_p(byte_off_ptr), *tail))
+            rc = lib().mbpe_encoder_encode_byteoff(*head, ctypes.c_void_p(byte_off_ptr), *tail)
         else:
-            _check(lib().mbpe_encoder_encode(*head, *tail))
+            rc = lib().mbpe_encoder_encode(*head, *tail)
+        self.n_out = n.value
+        _check(rc)
         self.n_passes = passes.value
         return (n.value, tok_off) if offsets else n.value
 
@@ -1166,8 +1184,9 @@ class Encoder:
         n_rows, n_tok = ctypes.c_uint64(), ctypes.c_uint64()
         tail = (ctypes.byref(n_rows), ctypes.byref(n_tok))
         if out_ptr is not None:
-            _check(lib().mbpe_encoder_encode_batch(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail))
-            self.n_tokens = n_tok.value
+            rc = lib().mbpe_encoder_encode_batch(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail)
+            self.n_rows, self.n_tokens = n_rows.value, n_tok.value     # (also where a cap_rows too small is refused)
+            _check(rc)
             return n_rows.value
         if spec.layout == PACK_PADDED:
             n_rows.value = len(docs) - 1              # known without a query
@@ -1219,9 +1238,10 @@ class Encoder:
         tail = (ctypes.byref(n_rows), ctypes.byref(n_tok))
         if out_ptr is not None:
             aux = call.device(labels_ptr, pos_ptr, seg_ptr)
-            _check(lib().mbpe_encoder_encode_batch_aux(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail,
-                                                       ctypes.byref(aux), doc_tok_off.ctypes.data))
-            self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
+            rc = lib().mbpe_encoder_encode_batch_aux(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail,
+                                                     ctypes.byref(aux), doc_tok_off.ctypes.data)
+            self.n_rows, self.n_tokens, self.doc_tok_off = n_rows.value, n_tok.value, doc_tok_off
+            _check(rc)
             return (n_rows.value,) + call.cu_seqlens(doc_tok_off) if cu_seqlens else n_rows.value
         if spec.layout == PACK_PADDED:
             n_rows.value = n_docs                     # known without a query
@@ -1251,9 +1271,11 @@ class Encoder:
         doc_tok_off = np.zeros(len(keep[-1]), dtype=np.uint64)
         tail = lambda n_rows, aux, win: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
                                          doc_tok_off.ctypes.data, ctypes.byref(win))
-        out = call.run(lib().mbpe_encoder_encode_batch_windows, head, tail, out_ptr, len_ptr, cap_rows,
-                       (labels_ptr, pos_ptr, seg_ptr, row_doc_ptr, row_tok0_ptr))
-        self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
+        try:
+            out = call.run(lib().mbpe_encoder_encode_batch_windows, head, tail, out_ptr, len_ptr, cap_rows,
+                           (labels_ptr, pos_ptr, seg_ptr, row_doc_ptr, row_tok0_ptr))
+        finally:
+            self.n_rows, self.n_tokens, self.doc_tok_off = getattr(call, "n_rows", None), n_tok.value, doc_tok_off
         return out
 
     def encode_batch_endmask_windows(self, text_ptr, n_bytes, mask_ptr, singles, doc_off, *, seq_len, stride,
@@ -1274,9 +1296,11 @@ class Encoder:
                 docs.ctypes.data, len(docs) - 1, ctypes.byref(spec))
         tail = lambda n_rows, aux, win: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
                                          doc_tok_off.ctypes.data, ctypes.byref(win))
-        out = call.run(lib().mbpe_encoder_encode_batch_endmask_windows, head, tail, out_ptr, len_ptr, cap_rows,
-                       (labels_ptr, pos_ptr, seg_ptr, row_doc_ptr, row_tok0_ptr))
-        self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
+        try:
+            out = call.run(lib().mbpe_encoder_encode_batch_endmask_windows, head, tail, out_ptr, len_ptr, cap_rows,
+                           (labels_ptr, pos_ptr, seg_ptr, row_doc_ptr, row_tok0_ptr))
+        finally:
+            self.n_rows, self.n_tokens, self.doc_tok_off = getattr(call, "n_rows", None), n_tok.value, doc_tok_off
         return out
 
     def encode_batch_fit(self, texts_or_buffer, chunk_off=None, doc_chunk_off=None, *, seq_len, out_bits=32, pad_id=0,
@@ -1295,9 +1319,11 @@ class Encoder:
         doc_tok_off = np.zeros(len(keep[-1]), dtype=np.uint64)
         tail = lambda n_rows, aux, fit: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
                                          doc_tok_off.ctypes.data, ctypes.byref(fit))
-        out = call.run(lib().mbpe_encoder_encode_batch_fit, head, tail, len(doc_tok_off) - 1, lambda: doc_tok_off,
-                       out_ptr, len_ptr, cap_rows, (labels_ptr, pos_ptr, seg_ptr, doc_row_ptr, doc_col_ptr))
-        self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
+        try:
+            out = call.run(lib().mbpe_encoder_encode_batch_fit, head, tail, len(doc_tok_off) - 1, lambda: doc_tok_off,
+                           out_ptr, len_ptr, cap_rows, (labels_ptr, pos_ptr, seg_ptr, doc_row_ptr, doc_col_ptr))
+        finally:
+            self.n_rows, self.n_tokens, self.doc_tok_off = getattr(call, "n_rows", None), n_tok.value, doc_tok_off
         return out
 
     def encode_batch_endmask_fit(self, text_ptr, n_bytes, mask_ptr, singles, doc_off, *, seq_len, out_bits=32, pad_id=0,
@@ -1317,9 +1343,11 @@ class Encoder:
                 docs.ctypes.data, len(docs) - 1, ctypes.byref(spec))
         tail = lambda n_rows, aux, fit: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
                                          doc_tok_off.ctypes.data, ctypes.byref(fit))
-        out = call.run(lib().mbpe_encoder_encode_batch_endmask_fit, head, tail, len(docs) - 1, lambda: doc_tok_off,
-                       out_ptr, len_ptr, cap_rows, (labels_ptr, pos_ptr, seg_ptr, doc_row_ptr, doc_col_ptr))
-        self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
+        try:
+            out = call.run(lib().mbpe_encoder_encode_batch_endmask_fit, head, tail, len(docs) - 1, lambda: doc_tok_off,
+                           out_ptr, len_ptr, cap_rows, (labels_ptr, pos_ptr, seg_ptr, doc_row_ptr, doc_col_ptr))
+        finally:
+            self.n_rows, self.n_tokens, self.doc_tok_off = getattr(call, "n_rows", None), n_tok.value, doc_tok_off
         return out
 
     def encode_endmask(self, text_ptr, n_bytes, mask_ptr, singles=None, doc_off=None, dtype=np.uint32, out_ptr=None,
@@ -1342,14 +1370,18 @@ class Encoder:
         mid = (dtype.itemsize * 8, 0 if out_ptr is None else 1)
         tail = (None if tok_off is None else tok_off.ctypes.data, ctypes.byref(n), ctypes.byref(passes))
         if query or out_ptr is not None:
-            _check(lib().mbpe_encoder_encode_endmask_byteoff(*head, None if query else _ptr(out_ptr), 0 if query else cap,
-                                                             *mid, None if query else _ptr(byte_off_ptr), *tail))
+            rc = lib().mbpe_encoder_encode_endmask_byteoff(*head, None if query else _ptr(out_ptr), 0 if query else cap,
+                                                           *mid, None if query else _ptr(byte_off_ptr), *tail)
+            self.n_out = n.value                     # (reported also where a cap too small is refused)
+            _check(rc)
             self.n_passes = passes.value
             return n.value, tok_off
         out = np.zeros(max(n_bytes, 1) if cap is None else max(cap, 1), dtype=dtype)
         boff = np.zeros(len(out) + 1, dtype=np.uint64) if byte_off else None
-        _check(lib().mbpe_encoder_encode_endmask_byteoff(*head, out.ctypes.data, n_bytes if cap is None else cap, *mid,
-                                                         None if boff is None else boff.ctypes.data, *tail))
+        rc = lib().mbpe_encoder_encode_endmask_byteoff(*head, out.ctypes.data, n_bytes if cap is None else cap, *mid,
+                                                       None if boff is None else boff.ctypes.data, *tail)
+        self.n_out = n.value
+        _check(rc)
         self.n_passes = passes.value
         if byte_off:
             return out[:n.value].copy(), tok_off, boff[:n.value + 1].copy()
@@ -1357,10 +1389,13 @@ class Encoder:
 
     def encode_batch_endmask(self, text_ptr, n_bytes, mask_ptr, singles, doc_off, *, seq_len, layout="padded",
                              out_bits=32, pad_id=0, bos_id=None, eos_id=None, pad_left=False, trunc_left=False,
-                             labels=False, positions=False, segments=False, cu_seqlens=False, ignore_label=-100):
+                             labels=False, positions=False, segments=False, cu_seqlens=False, ignore_label=-100,
+                             out_ptr=None, len_ptr=None, cap_rows=None, labels_ptr=None, pos_ptr=None, seg_ptr=None):
         """encode_endmask and the pack kernel in one call (mbpe_encoder_encode_batch_endmask): the documents doc_off
         describes as one id matrix -> (ids, lengths), or with any of labels / positions / segments / cu_seqlens the
-        dict of encode_batch_aux.  The documents' token offsets: self.doc_tok_off."""
+        dict of encode_batch_aux.  The documents' token offsets: self.doc_tok_off.  With out_ptr= (and len_ptr=,
+        labels_ptr=, pos_ptr=, seg_ptr=: device memory for cap_rows rows; 0 = a query) the matrices go there and the row
+        count is returned; self.n_rows holds it also where a cap_rows too small is refused."""
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         with_aux = labels or positions or segments or cu_seqlens
         call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label) if with_aux else None
@@ -1373,6 +1408,14 @@ class Encoder:
                 docs.ctypes.data, n_docs, ctypes.byref(spec))
         tail = (ctypes.byref(n_rows), ctypes.byref(n_tok))
         fn = lib().mbpe_encoder_encode_batch_endmask
+        if out_ptr is not None:
+            with_aux = labels_ptr or pos_ptr or seg_ptr
+            aux = PackAux(labels_ptr or None, pos_ptr or None, seg_ptr or None, int(ignore_label))
+            rc = fn(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail, ctypes.byref(aux) if with_aux else None,
+                    doc_tok_off.ctypes.data)
+            self.n_rows, self.n_tokens, self.doc_tok_off = n_rows.value, n_tok.value, doc_tok_off
+            _check(rc)
+            return n_rows.value
         if spec.layout == PACK_PADDED:
             n_rows.value = n_docs                     # known without a query
         else:
