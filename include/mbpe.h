@@ -1217,6 +1217,127 @@ MBPE_API int  mbpe_pack_fit_labels(int device_id, const void *tokens, uint64_t n
  * mbpe_encoder_pack_ms include the stage. */
 MBPE_API int  mbpe_encoder_set_mlm(mbpe_encoder *e, const mbpe_mlm_spec *spec);
 
+/* ---- span-corruption (denoise) batches for encoder-decoder models ------------ */
+
+/* T5 / UL2-style span corruption (Raffel et al., 2020) between encode and pack: runs of tokens are replaced by sentinel
+ * ids in the INPUTS, and the dropped runs follow their sentinels in the TARGETS.  One stream becomes two, and a long
+ * document becomes several units first (T5's split_tokens), so the stage also changes the number of rows.  ("Span"
+ * already means 1,024 scan elements in this code base, hence the name.)  All of it is integer arithmetic; h is the hash
+ * of BPE-dropout above.
+ *   units       document d of the call has L_d tokens and g = doc_base + d (mod 2^64).  It has U_d = 1 units if
+ *               segment_tokens == 0, else max(1, ceil(L_d / segment_tokens)); an empty document keeps one empty unit.
+ *               Unit u holds the tokens [u * seg, min((u + 1) * seg, L_d)); units are numbered through the call in
+ *               document order
+ *   seeds       s_g = (h(seed, g, 0x44454E00) << 32) | h(seed, g, 0x44454E01);  s_u = (h(s_g, u, 2) << 32) | h(s_g, u, 3)
+ *   counts      a unit of L tokens stays as it is (inputs = its tokens, no targets) if density == 0 or
+ *               L < max(min_tokens, 2).  Otherwise N = clamp((L * density + 2^31) >> 32, 1, L - 1) tokens are noise, in
+ *               S = clamp((N * 256 + mean_span_q8 / 2) / mean_span_q8, 1, min(N, L - N, n_sentinels)) parts
+ *   boundaries  to cut a total T into S parts >= 1 with draw c: E = T - S, q(j) = floor(j * E / S), c_0 = 0, c_S = E,
+ *               c_j = q(j - 1) + ((h(s_u, j, c) * (q(j) - q(j - 1) + 1)) >> 32) for 0 < j < S, and B_j = j + c_j.
+ *               Every cut lies in its own stratum, so B ascends strictly and any B_j costs one hash.
+ *               Bn = boundaries(N, S, 0) are the noise parts, Bm = boundaries(L - N, S, 1) the kept parts
+ *   layout      kept part 0, noise part 0, kept part 1, .. noise part S - 1, with s_j the sentinel of part j
+ *               (sentinel_id - j with sentinel_down, T5's <extra_id_j>; else sentinel_id + j):
+ *                 inputs  = kept_0 s_0 kept_1 s_1 .. kept_{S-1} s_{S-1}        L - N + S ids
+ *                 targets = s_0 noise_0 s_1 noise_1 .. s_{S-1} noise_{S-1}     N + S ids
+ * The result is a pure function of (spec, d, tokens of d): the same call gives the same batch, another seed another
+ * epoch, and a corpus fed in batches gets the result of one big call by passing in doc_base the number of each batch's
+ * first document.  Thresholds come from mbpe_dropout_threshold.  Tokens are read as the packers read them (16-bit plain
+ * ids, or 32-bit with bit 31 ignored) and written as plain ids of the same width.  eos and the decoder start id stay
+ * the packer's business.
+ * Errors, all before the device is touched: MBPE_ERR_ARG for a NULL spec where one is required, density > 2^32,
+ * mean_span_q8 < 256, n_sentinels == 0, sentinel_down > 1, a sentinel range that leaves [0, 2^31 - 2), bad offsets,
+ * more than 2^40 units or ids, and -- naming the document -- a unit of 2^32 - 1 tokens or more while density > 0 (where
+ * only the device holds the offsets, a flag word is read back with the totals); MBPE_ERR_VOCAB for a sentinel
+ * >= 65,536 with 16-bit tokens. */
+typedef struct {
+    uint64_t density;        /* threshold in [0, 2^32]: share of a unit's tokens that become noise (T5: 0.15) */
+    uint64_t seed;
+    uint64_t doc_base;       /* number of the call's first document in the caller's corpus */
+    uint32_t mean_span_q8;   /* mean noise-part length in 1/256 tokens, >= 256 (T5: 3.0 = 768) */
+    uint32_t segment_tokens; /* 0: a document is one unit; else it is cut into units of this many tokens, the last shorter */
+    uint32_t min_tokens;     /* units shorter than max(min_tokens, 2) stay as they are */
+    uint32_t sentinel_id;    /* id of part 0's sentinel */
+    uint32_t sentinel_down;  /* 1: part j gets sentinel_id - j (T5's <extra_id_j>), 0: sentinel_id + j */
+    uint32_t n_sentinels;    /* >= 1: no unit gets more parts than this */
+} mbpe_denoise_spec;         /* 48 bytes; sentinel_id at offset 36 */
+
+/* The plan alone, on the host (never MBPE_ERR_NO_DEVICE): *n_units_out (required) = the units of the call;
+ * unit_in_off and unit_tg_off (n_units + 1 each) = the units' offsets into the inputs and into the targets;
+ * unit_doc (n_units) = each unit's document.  Each of the three is NULL or has room for cap_units units; a cap too
+ * small is MBPE_ERR_ARG, writes nothing and still reports the count.  The sentinels are checked as for 32-bit tokens. */
+MBPE_API int  mbpe_denoise_plan(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_denoise_spec *spec,
+                                uint64_t *n_units_out, uint64_t *unit_in_off, uint64_t *unit_tg_off, uint64_t *unit_doc,
+                                uint64_t cap_units);
+
+/* The two streams of a flat token stream on HIP device `device_id`, with the conventions of mbpe_fim_tokens: tokens in
+ * host or device memory (tokens_on_device), doc_tok_off (n_docs + 1) on the host; inputs_out (cap_in ids) and
+ * targets_out (cap_tg ids) both in host or both in device memory (out_on_device; on the device aligned to their ids);
+ * the three unit arrays of mbpe_denoise_plan on the host, each NULL or with room for cap_units.  n_units_out, n_in_out
+ * and n_tg_out are required.  inputs_out NULL is a query, answered from the host's plan without a device (the unit
+ * arrays are filled); a cap too small -- cap_in, cap_tg or, with a unit array given, cap_units -- is MBPE_ERR_ARG: nothing
+ * is written and the counts are still reported.  (inputs_out, unit_in_off) and (targets_out, unit_tg_off) are what
+ * mbpe_pack_tokens* and mbpe_decode_batch take as they are, one row per unit.
+ * Kernels (csrc/denoise.hip): k_dn_units, one lane per document, and a 64-bit scan over spans of 1,024 documents leave
+ * the unit offsets; k_dn_lengths, one lane per unit, finds its document by binary search and leaves both lengths, two
+ * scans the two offset arrays; k_dn_gather runs once per side, a lane per 16-byte piece of the output: it finds its
+ * unit and its part by binary search (one hash per probe) and walks, every token read once and written once.  No table
+ * of part boundaries is ever stored.  With ids asked for, the unit arrays handed back are the device's own.
+ * mbpe_denoise_kernel_ms: the device time of the calling thread's latest such call. */
+MBPE_API int  mbpe_denoise_tokens(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits,
+                                  int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs,
+                                  const mbpe_denoise_spec *spec, void *inputs_out, uint64_t cap_in, void *targets_out,
+                                  uint64_t cap_tg, int out_on_device, uint64_t *unit_in_off, uint64_t *unit_tg_off,
+                                  uint64_t *unit_doc, uint64_t cap_units, uint64_t *n_units_out, uint64_t *n_in_out,
+                                  uint64_t *n_tg_out);
+MBPE_API int  mbpe_denoise_kernel_ms(float *ms_out);
+
+/* What the two batch calls below write, one row per unit; on the same side as each other (out_on_device), on the device
+ * dec_ids and dec_labels 16-byte aligned, the others aligned to their elements.
+ *   enc_ids     [rows, enc_spec->seq_len] ids: the inputs packed with enc_spec.  NULL: query
+ *   enc_len     [rows] or NULL
+ *   dec_ids     [rows, dec_spec->seq_len] ids: the targets packed with dec_spec through the aux packer.  Required with
+ *               enc_ids.  With dec_spec->bos_id = the decoder start id and eos_id set, dec_ids / dec_labels are T5's
+ *               decoder_input_ids / labels
+ *   dec_len     [rows] or NULL
+ *   dec_labels  [rows, dec_spec->seq_len] ids or NULL: next-token labels of dec_ids, ignore_label elsewhere
+ *   row_doc     [rows] or NULL: the row's document */
+typedef struct {
+    void     *enc_ids;
+    uint32_t *enc_len;
+    void     *dec_ids;
+    uint32_t *dec_len;
+    void     *dec_labels;
+    uint32_t *row_doc;
+    int64_t   ignore_label;
+} mbpe_denoise_batch;
+
+/* Encode, the stage, then two PADDED packs with the pack kernels on the encoder's stream: mbpe_encoder_encode_batch_aux
+ * and mbpe_encoder_encode_batch_endmask for encoder-decoder batches.  Arguments up to n_docs as for those calls; dn the
+ * rule's spec; enc_spec and dec_spec the two matrices' specs, both MBPE_PACK_PADDED with equal out_bits (anything else
+ * is MBPE_ERR_ARG); out as above with room for cap_rows rows.  No token crosses to the host.  *n_rows_out = the units
+ * of the call: it comes back from the device, so a query (out->enc_ids NULL) runs the passes and the unit and length
+ * kernels, and a cap_rows too small is found after them, writes nothing and reports the count.  n_tokens_out stays
+ * "tokens encoded".  Buffers are kept by the encoder: a repeat call of no larger size leaves mbpe_encoder_alloc_count
+ * as it is.  mbpe_encoder_kernel_ms and mbpe_encoder_pack_ms include the stage.  "rank_order", dropout and "dedup" act
+ * before the stage and combine freely.  mbpe_encoder_set_fim and mbpe_encoder_set_mlm do not apply here: a call while
+ * either is on is MBPE_ERR_ARG, never a silent choice.  The sentinels are checked against the width of the tokens the
+ * call packs from (16 bits with out_bits 16: MBPE_ERR_VOCAB).  row_doc needs n_docs < 2^32 - 1. */
+MBPE_API int  mbpe_encoder_encode_batch_denoise(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                                const uint64_t *chunk_off, uint64_t n_chunks,
+                                                const uint64_t *doc_chunk_off, uint64_t n_docs,
+                                                const mbpe_denoise_spec *dn, const mbpe_pack_spec *enc_spec,
+                                                const mbpe_pack_spec *dec_spec, const mbpe_denoise_batch *out,
+                                                uint64_t cap_rows, int out_on_device, uint64_t *n_rows_out,
+                                                uint64_t *n_tokens_out);
+MBPE_API int  mbpe_encoder_encode_batch_endmask_denoise(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
+                                                        const uint8_t *endmask_dev, const mbpe_single *singles,
+                                                        uint64_t n_singles, const uint64_t *doc_off, uint64_t n_docs,
+                                                        const mbpe_denoise_spec *dn, const mbpe_pack_spec *enc_spec,
+                                                        const mbpe_pack_spec *dec_spec, const mbpe_denoise_batch *out,
+                                                        uint64_t cap_rows, int out_on_device, uint64_t *n_rows_out,
+                                                        uint64_t *n_tokens_out);
+
 /* ---- decode on the device ----------------------------------------------- */
 
 /* Tokenizer::decode (Tokenizer.h:725-751) for whole token streams on HIP device `device_id`: per token a byte

@@ -172,6 +172,20 @@ MBPE_API int mbpe_tok_encode_batch_aux_device(mbpe_tokenizer *t, const uint8_t *
                                               uint64_t *n_rows_out, uint64_t *n_tokens_out, const mbpe_pack_aux *aux,
                                               uint64_t *doc_tok_off_out);
 
+/* The same documents as an encoder-decoder batch by span corruption (mbpe.h, which holds the rule): the arguments of
+ * mbpe_tok_encode_batch_aux_device up to device_id, then dn, the two specs and the output struct of
+ * mbpe_encoder_encode_batch_denoise in place of spec / aux.  One row per unit: with dn->segment_tokens a long text
+ * becomes several rows, out->row_doc says whose.  The call goes to mbpe_encoder_encode_batch_denoise or --
+ * mbpe_tok_set_encode_split -- mbpe_encoder_encode_batch_endmask_denoise, and mbpe_tok_set_encode_order, _dropout,
+ * _dedup and _split_unicode hold as for the other batch calls.  The sentinels may be special-token ids: the stage
+ * writes ids and never looks them up.  While mbpe_tok_set_encode_fim or _mlm is on the call is MBPE_ERR_ARG. */
+MBPE_API int mbpe_tok_encode_batch_denoise_device(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off,
+                                                  uint64_t n_docs, int verbose, int device_id,
+                                                  const mbpe_denoise_spec *dn, const mbpe_pack_spec *enc_spec,
+                                                  const mbpe_pack_spec *dec_spec, const mbpe_denoise_batch *out,
+                                                  uint64_t cap_rows, int out_on_device, uint64_t *n_rows_out,
+                                                  uint64_t *n_tokens_out);
+
 /* The same for the window layout of mbpe_pack_windows (mbpe.h): a text that does not fit a row becomes several rows
  * that share win->stride tokens.  The arguments of mbpe_tok_encode_batch_aux_device, then win (required); the call goes
  * to mbpe_encoder_encode_batch_windows or -- mbpe_tok_set_encode_split -- mbpe_encoder_encode_batch_endmask_windows, and

@@ -50,6 +50,7 @@
 // unique_of map, and the table of token runs is counted with them -- see dedup_count.  An encoder that is never asked
 // to count has none of these buffers.
 #include "dedup.h"
+#include "denoise.h"
 #include "dropout.h"
 #include "expand.h"
 #include "fim.h"
@@ -543,6 +544,11 @@ struct mbpe_encoder : DevQueue {
     DevBuf<void> d_mlm_flat;
     DevBuf<uint32_t> d_mlm_tgt;
     DevBuf<unsigned long long> d_mlm_scr;
+    // the _denoise calls (nothing of this exists before the first one): the two flat streams the stage writes; its index
+    // arrays in one buffer (dn_index); the rows' documents; the decoder side's matrix and lengths that go to the host
+    DevBuf<void> d_dn_in, d_dn_tg, d_dn_dec_ids;
+    DevBuf<unsigned long long> d_dn_idx;
+    DevBuf<uint32_t> d_dn_row_doc, d_dn_dec_len;
     // token byte offsets: len[id] (host; empty with len_error set for a table mbpe_merges_check refuses), on the
     // device from the first such call on; the spans' byte counts, the singles' token indices, offsets bound for the host
     std::vector<uint32_t> len;
@@ -704,6 +710,13 @@ void enc_out(EncCall *a, void *tokens_out, uint64_t cap, uint32_t token_bits, in
     a->n_passes_out = n_passes_out;
 }
 
+// what the _denoise calls add to a batch call: the rule, the decoder side's spec, and where both matrices go
+struct EncDenoise {
+    const mbpe_denoise_spec *spec;
+    const mbpe_pack_spec *dec_spec;
+    const mbpe_denoise_batch *out;
+};
+
 // what the batch calls add: the documents as chunk ranges (the endmask call has them in EncCall) and the pack step
 struct EncPack {
     const uint64_t *doc_chunk_off;
@@ -718,6 +731,7 @@ struct EncPack {
     uint64_t *doc_tok_off_out;
     const mbpe_pack_window *win;    // the _windows calls; NULL: the spec's own layout
     const struct mbpe_pack_fit *fit;   // the _fit calls (win NULL); NULL: the spec's own layout
+    const struct EncDenoise *dn;    // the _denoise calls (aux, win and fit NULL): spec, ids_out and len_out are the encoder side's
     uint32_t token_bits() const { return spec->out_bits == 16 ? 16 : 32; }
 };
 
@@ -1549,6 +1563,118 @@ int enc_mlm_stage(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool doc
     return MBPE_OK;
 }
 
+// where the index arrays of the denoise stage lie in e->d_dn_idx, for n_docs documents and room for cap units
+struct DnIndex {
+    uint64_t uoff, unit_doc, in_off, tg_off, res, scratch, words;
+    DnIndex(uint64_t n_docs, uint64_t cap) {
+        uoff = 0;
+        unit_doc = uoff + n_docs + 1;
+        in_off = unit_doc + cap;
+        tg_off = in_off + cap + 1;
+        res = tg_off + cap + 1;
+        scratch = res + 4;
+        words = scratch + dn_scratch_bytes(n_docs, cap) / 8;
+    }
+};
+
+// what a _denoise call checks beyond the batch calls' own arguments, before the device is touched
+int enc_denoise_check(const mbpe_encoder *e, const EncPack &k) {
+    const EncDenoise &dn = *k.dn;
+    const mbpe_denoise_batch &o = *dn.out;
+    const char *msg = "";
+    if (const int rc = denoise_check_spec(dn.spec, k.token_bits(), &msg)) return fail(rc, msg);
+    if (e->fim_on || e->mlm_on)
+        return fail(MBPE_ERR_ARG, "fill-in-the-middle or masked-LM is on: they do not apply to the denoise calls, turn them off");
+    if (const int rc = pack_check_spec(dn.dec_spec, k.token_bits())) return rc;
+    if (k.spec->layout != MBPE_PACK_PADDED || dn.dec_spec->layout != MBPE_PACK_PADDED)
+        return fail(MBPE_ERR_ARG, "the denoise calls take MBPE_PACK_PADDED specs");
+    if (k.spec->out_bits != dn.dec_spec->out_bits)
+        return fail(MBPE_ERR_ARG, "the denoise calls take two specs of equal out_bits");
+    if (o.enc_ids && !o.dec_ids) return fail(MBPE_ERR_ARG, "enc_ids without dec_ids");
+    if (o.row_doc && k.n_docs >= 0xFFFFFFFFull) return fail(MBPE_ERR_ARG, "row_doc needs fewer than 2^32 - 1 documents");
+    if (o.enc_ids && k.out_on_device && ((uint64_t)(uintptr_t)o.dec_len % 4 || (uint64_t)(uintptr_t)o.row_doc % 4))
+        return fail(MBPE_ERR_ARG, "dec_len or row_doc is not aligned to its elements");
+    const mbpe_pack_aux aux = {o.dec_labels, nullptr, nullptr, o.ignore_label};
+    return pack_check_aux(*dn.dec_spec, &aux, nullptr, 0, o.dec_ids, o.enc_ids ? k.out_on_device : 0);
+}
+
+// the tail of the _denoise calls: the flat tokens in e->d_flat and the documents' token offsets (as for enc_pack_tail)
+// -> the stage's two streams, one unit per row -> k_pack_stream's matrix of the inputs and k_pack_aux's of the targets.
+// One wait for the stage -- the unit count, both totals and the flag come back with it -- and one for the two packs
+int enc_denoise_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_on_device) {
+    const EncDenoise &dn = *k.dn;
+    const mbpe_denoise_batch &o = *dn.out;
+    const mbpe_pack_spec &es = *k.spec, &ds = *dn.dec_spec;
+    const uint64_t n_docs = k.n_docs, tb = k.token_bits() / 8;
+    const bool query = !o.enc_ids;
+    *k.n_rows_out = 0;
+    if (k.n_tokens_out) *k.n_tokens_out = n_enc;
+    if (n_docs == 0) return MBPE_OK;
+    // (a document of L tokens has at most 1 + L / segment_tokens units, and neither stream more ids than the tokens)
+    const uint64_t cap_units = n_docs + (dn.spec->segment_tokens ? n_enc / dn.spec->segment_tokens : 0);
+    const DnIndex ix(n_docs, cap_units);
+    int rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
+    if (rc == MBPE_OK) rc = e->d_dn_idx.reserve(ix.words * 8, e->mem);
+    if (rc == MBPE_OK && o.row_doc) rc = e->d_dn_row_doc.reserve(cap_units * 4, e->mem);
+    if (rc == MBPE_OK && !query) rc = e->d_dn_in.reserve(std::max<uint64_t>(n_enc, 1) * tb, e->mem);
+    if (rc == MBPE_OK && !query) rc = e->d_dn_tg.reserve(std::max<uint64_t>(n_enc, 1) * tb, e->mem);
+    if (rc != MBPE_OK) return rc;
+    if (!docs_on_device)
+        ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
+    unsigned long long *idx = e->d_dn_idx;
+    const DnDst dst = {query ? nullptr : e->d_dn_in.get(), query ? nullptr : e->d_dn_tg.get(), query ? 0 : n_enc,
+                       query ? 0 : n_enc, idx + ix.uoff, idx + ix.unit_doc, idx + ix.in_off, idx + ix.tg_off, idx + ix.res,
+                       idx + ix.scratch, o.row_doc ? e->d_dn_row_doc.get() : nullptr, cap_units};
+    float stage_ms = 0.f;
+    ECHK(hipEventRecord(e->ev0, e->stream));
+    dn_launch(e->stream, e->d_flat, k.token_bits(), e->d_doc_off, n_docs, *dn.spec, dst);
+    if ((rc = e->finish(&stage_ms)) != MBPE_OK) return rc;
+    e->last_ms += stage_ms;
+    e->pack_ms = stage_ms;
+    unsigned long long res[4] = {0, 0, 0, 0};                    // units, input ids, target ids, the first document too long
+    ECHK(hipMemcpyAsync(res, idx + ix.res, 32, hipMemcpyDeviceToHost, e->stream));
+    ECHK(hipStreamSynchronize(e->stream));
+    if (res[3] != ~0ull)
+        return fail(MBPE_ERR_ARG, "denoise: document " + std::to_string(res[3]) + " has a unit of 2^32 - 1 tokens or more");
+    if (res[0] >> 40) return fail(MBPE_ERR_ARG, "denoise: more than 2^40 units");
+    const uint64_t n_rows = res[0];
+    *k.n_rows_out = n_rows;
+    if (query) return MBPE_OK;
+    if (k.cap_rows < n_rows) return fail(MBPE_ERR_ARG, "ids_out too small");
+    const uint64_t eb = es.out_bits / 8, enc_bytes = n_rows * es.seq_len * eb, dec_bytes = n_rows * ds.seq_len * eb;
+    mbpe_denoise_batch d = o;                                    // where the kernels write
+    if (!k.out_on_device) {
+        rc = e->d_ids.reserve(enc_bytes, e->mem);
+        d.enc_ids = e->d_ids;
+        if (rc == MBPE_OK && o.enc_len) { rc = e->d_len.reserve(n_rows * 4, e->mem); d.enc_len = e->d_len; }
+        if (rc == MBPE_OK) { rc = e->d_dn_dec_ids.reserve(dec_bytes, e->mem); d.dec_ids = e->d_dn_dec_ids; }
+        if (rc == MBPE_OK && o.dec_len) { rc = e->d_dn_dec_len.reserve(n_rows * 4, e->mem); d.dec_len = e->d_dn_dec_len; }
+        if (rc == MBPE_OK && o.dec_labels) { rc = e->d_labels.reserve(dec_bytes, e->mem); d.dec_labels = e->d_labels; }
+        if (rc != MBPE_OK) return rc;
+    }
+    const PackSrc src_in = {e->d_dn_in.get(), idx + ix.in_off, n_rows, res[1], k.token_bits()};
+    const PackSrc src_tg = {e->d_dn_tg.get(), idx + ix.tg_off, n_rows, res[2], k.token_bits()};
+    const mbpe_pack_aux aux = {d.dec_labels, nullptr, nullptr, o.ignore_label};
+    float packs_ms = 0.f;
+    ECHK(hipEventRecord(e->ev0, e->stream));
+    pack_launch(e->stream, src_in, es, {d.enc_ids, d.enc_len, n_rows});
+    pack_launch_aux(e->stream, src_tg, ds, {d.dec_ids, d.dec_len, n_rows}, aux);
+    if ((rc = e->finish(&packs_ms)) != MBPE_OK) return rc;
+    e->last_ms += packs_ms;
+    e->pack_ms += packs_ms;
+    const hipMemcpyKind kind = k.out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (o.row_doc) ECHK(hipMemcpyAsync(o.row_doc, e->d_dn_row_doc, n_rows * 4, kind, e->stream));
+    if (!k.out_on_device) {
+        ECHK(hipMemcpyAsync(o.enc_ids, d.enc_ids, enc_bytes, kind, e->stream));
+        if (o.enc_len) ECHK(hipMemcpyAsync(o.enc_len, d.enc_len, n_rows * 4, kind, e->stream));
+        ECHK(hipMemcpyAsync(o.dec_ids, d.dec_ids, dec_bytes, kind, e->stream));
+        if (o.dec_len) ECHK(hipMemcpyAsync(o.dec_len, d.dec_len, n_rows * 4, kind, e->stream));
+        if (o.dec_labels) ECHK(hipMemcpyAsync(o.dec_labels, d.dec_labels, dec_bytes, kind, e->stream));
+    }
+    ECHK(hipStreamSynchronize(e->stream));
+    return MBPE_OK;
+}
+
 // the pack step of the batch calls: the flat tokens in e->d_flat, the documents' token offsets in e->doc_tok (host;
 // docs_on_device: in e->d_doc_off already, and on the host only where doc_tok_off_out asks for them).  With
 // fill-in-the-middle on, the stage comes first and everything below reads what it wrote
@@ -1563,6 +1689,7 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
     float rows_ms = 0.f;                                         // the kernels before the pack kernel
     e->fim_docs = n_docs;
     e->fim_ran = false;
+    if (k.dn) return enc_denoise_tail(e, k, n_enc, docs_on_device);
     const bool fim = e->fim_on && e->fim.rate && n_enc;
     if (fim) {
         const bool to_host = k.doc_tok_off_out || fit || (aux && n_enc + 3 * n_docs + 2 >= (1ull << 32));
@@ -1671,6 +1798,7 @@ int enc_batch_check(const mbpe_encoder *e, const EncPack &k) {
     if (k.ids_out && k.out_on_device &&
         ((uint64_t)(uintptr_t)k.ids_out % (k.spec->out_bits / 8) || (uint64_t)(uintptr_t)k.len_out % 4))
         return fail(MBPE_ERR_ARG, "ids_out or len_out is not aligned to its elements");
+    if (k.dn) return enc_denoise_check(e, k);
     if (e->fim_on) {
         const char *msg = "";
         if (const int rc = fim_check_spec(&e->fim, k.token_bits(), &msg)) return fail(rc, msg);
@@ -2069,6 +2197,20 @@ int mbpe_encoder_encode_batch(mbpe_encoder *e, const uint8_t *text, uint64_t n_b
                       nullptr, nullptr});
 }
 
+int mbpe_encoder_encode_batch_denoise(mbpe_encoder *e, const uint8_t *text, uint64_t n_bytes, int text_on_device,
+                                      const uint64_t *chunk_off, uint64_t n_chunks, const uint64_t *doc_chunk_off,
+                                      uint64_t n_docs, const mbpe_denoise_spec *dn, const mbpe_pack_spec *enc_spec,
+                                      const mbpe_pack_spec *dec_spec, const mbpe_denoise_batch *out, uint64_t cap_rows,
+                                      int out_on_device, uint64_t *n_rows_out, uint64_t *n_tokens_out) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!dn || !dec_spec || !out) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_batch_denoise: NULL argument");
+    const EncDenoise d = {dn, dec_spec, out};
+    return enc_batch(e, {text, n_bytes, text_on_device, chunk_off, n_chunks},
+                     {doc_chunk_off, n_docs, enc_spec, out->enc_ids, cap_rows, out_on_device, out->enc_len, n_rows_out,
+                      n_tokens_out, nullptr, nullptr, nullptr, nullptr, &d});
+}
+
 int mbpe_encoder_encode_endmask(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes, const uint8_t *endmask_dev,
                                 const mbpe_single *singles, uint64_t n_singles, const uint64_t *doc_off, uint64_t n_docs,
                                 void *tokens_out, uint64_t cap, uint32_t token_bits, int out_on_device,
@@ -2108,12 +2250,13 @@ static int enc_batch_endmask(const std::string &who, mbpe_encoder *e, const uint
                              const uint64_t *doc_off, uint64_t n_docs, const mbpe_pack_spec *spec, void *ids_out,
                              uint64_t cap_rows, int out_on_device, uint32_t *len_out, uint64_t *n_rows_out,
                              uint64_t *n_tokens_out, const mbpe_pack_aux *aux, uint64_t *doc_tok_off_out,
-                             const mbpe_pack_window *win, const struct mbpe_pack_fit *fit = nullptr) {
+                             const mbpe_pack_window *win, const struct mbpe_pack_fit *fit = nullptr,
+                             const EncDenoise *dn = nullptr) {
     if (n_rows_out) *n_rows_out = 0;
     if (n_tokens_out) *n_tokens_out = 0;
     if (!spec || !doc_off || !n_rows_out) return fail(MBPE_ERR_ARG, who + ": NULL argument");
     const EncPack k = {nullptr, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
-                       doc_tok_off_out, win, fit};
+                       doc_tok_off_out, win, fit, dn};
     int rc = pack_check_spec(spec, k.token_bits());
     if (rc != MBPE_OK) return rc;
     rc = enc_endmask_check(who.c_str(), n_bytes, singles, n_singles, doc_off, n_docs, k.token_bits());
@@ -2153,6 +2296,21 @@ int mbpe_encoder_encode_batch_endmask(mbpe_encoder *e, const uint8_t *text_dev, 
     return enc_batch_endmask("mbpe_encoder_encode_batch_endmask", e, text_dev, n_bytes, endmask_dev, singles, n_singles,
                              doc_off, n_docs, spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
                              doc_tok_off_out, nullptr);
+}
+
+int mbpe_encoder_encode_batch_endmask_denoise(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,
+                                              const uint8_t *endmask_dev, const mbpe_single *singles, uint64_t n_singles,
+                                              const uint64_t *doc_off, uint64_t n_docs, const mbpe_denoise_spec *dn,
+                                              const mbpe_pack_spec *enc_spec, const mbpe_pack_spec *dec_spec,
+                                              const mbpe_denoise_batch *out, uint64_t cap_rows, int out_on_device,
+                                              uint64_t *n_rows_out, uint64_t *n_tokens_out) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!dn || !dec_spec || !out) return fail(MBPE_ERR_ARG, "mbpe_encoder_encode_batch_endmask_denoise: NULL argument");
+    const EncDenoise d = {dn, dec_spec, out};
+    return enc_batch_endmask("mbpe_encoder_encode_batch_endmask_denoise", e, text_dev, n_bytes, endmask_dev, singles,
+                             n_singles, doc_off, n_docs, enc_spec, out->enc_ids, cap_rows, out_on_device, out->enc_len,
+                             n_rows_out, n_tokens_out, nullptr, nullptr, nullptr, nullptr, &d);
 }
 
 int mbpe_encoder_encode_batch_endmask_windows(mbpe_encoder *e, const uint8_t *text_dev, uint64_t n_bytes,

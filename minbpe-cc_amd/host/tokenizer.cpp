@@ -984,6 +984,37 @@ int Tokenizer::encode_batch_packed(const char *text, const uint64_t *doc_off, ui
     return rc;
 }
 
+int Tokenizer::encode_batch_denoise(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
+                                    const mbpe_denoise_spec *dn, const mbpe_pack_spec *enc_spec,
+                                    const mbpe_pack_spec *dec_spec, const mbpe_denoise_batch *out, uint64_t cap_rows,
+                                    int out_on_device, uint64_t *n_rows_out, uint64_t *n_tokens_out, bool device_split) {
+    uint64_t n_tokens = 0, n_bytes = 0;
+    int rc = MBPE_OK;
+    if (device_split) {
+        DeviceSplit ds;
+        rc = split_on_device(text, doc_off, n_docs, verbose, device, &ds);
+        if (rc != MBPE_OK) return rc;
+        n_bytes = ds.n_bytes;
+        rc = mbpe_encoder_encode_batch_endmask_denoise(device_encoder(device), ds.d_text, ds.n_bytes, ds.d_mask,
+                                                       ds.singles.data(), ds.singles.size(), ds.doc_off.data(), n_docs, dn,
+                                                       enc_spec, dec_spec, out, cap_rows, out_on_device, n_rows_out,
+                                                       &n_tokens);
+    } else {
+        std::string buf;
+        std::vector<uint64_t> off, first_chunk;
+        batch_chunks(text, doc_off, n_docs, verbose, &buf, &off, &first_chunk);
+        n_bytes = buf.size();
+        rc = mbpe_encoder_encode_batch_denoise(device_encoder(device), reinterpret_cast<const uint8_t *>(buf.data()),
+                                               buf.size(), 0, off.data(), off.size() - 1, first_chunk.data(), n_docs, dn,
+                                               enc_spec, dec_spec, out, cap_rows, out_on_device, n_rows_out, &n_tokens);
+    }
+    if (n_tokens_out) *n_tokens_out = n_tokens;
+    if (rc == MBPE_OK && verbose)
+        std::cout << "Encoded " << n_docs << " texts (length " << n_bytes << ") to " << n_tokens << " tokens in "
+                  << *n_rows_out << " rows of inputs and targets\n";
+    return rc;
+}
+
 std::vector<std::vector<Token>> Tokenizer::encode_batch(const std::vector<std::string> &texts, bool verbose, int device,
                                                         bool device_split) {
     std::string all;
@@ -1648,6 +1679,33 @@ int mbpe_tok_encode_batch_aux_device(mbpe_tokenizer *t, const uint8_t *text, con
         return t->t->encode_batch_packed(reinterpret_cast<const char *>(text), doc_off, n_docs, verbose != 0, device_id,
                                          spec, ids_out, cap_rows, out_on_device, len_out, n_rows_out, n_tokens_out, aux,
                                          doc_tok_off_out, t->t->encode_split());
+    } catch (const mbpe_host::CodedError &e) {      // mbpe_encoder_create failed: its own code
+        mbpe_host::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        mbpe_host::set_last_error(e.what());
+        return MBPE_ERR_ARG;
+    }
+}
+
+int mbpe_tok_encode_batch_denoise_device(mbpe_tokenizer *t, const uint8_t *text, const uint64_t *doc_off, uint64_t n_docs,
+                                         int verbose, int device_id, const mbpe_denoise_spec *dn,
+                                         const mbpe_pack_spec *enc_spec, const mbpe_pack_spec *dec_spec,
+                                         const mbpe_denoise_batch *out, uint64_t cap_rows, int out_on_device,
+                                         uint64_t *n_rows_out, uint64_t *n_tokens_out) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!t || !n_rows_out || !doc_off || !dn || !enc_spec || !dec_spec || !out || device_id < 0 ||
+        (!text && doc_off[n_docs] > doc_off[0])) {
+        mbpe_host::set_last_error("mbpe_tok_encode_batch_denoise_device: NULL argument or negative device");
+        return MBPE_ERR_ARG;
+    }
+    for (uint64_t i = 0; i < n_docs; ++i)
+        if (doc_off[i + 1] < doc_off[i]) { mbpe_host::set_last_error("doc_off must be ascending"); return MBPE_ERR_ARG; }
+    try {
+        return t->t->encode_batch_denoise(reinterpret_cast<const char *>(text), doc_off, n_docs, verbose != 0, device_id, dn,
+                                          enc_spec, dec_spec, out, cap_rows, out_on_device, n_rows_out, n_tokens_out,
+                                          t->t->encode_split());
     } catch (const mbpe_host::CodedError &e) {      // mbpe_encoder_create failed: its own code
         mbpe_host::set_last_error(e.what());
         return e.code;

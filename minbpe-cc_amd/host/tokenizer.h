@@ -89,6 +89,12 @@ public:
                             const mbpe_pack_aux *aux = nullptr, uint64_t *doc_tok_off_out = nullptr,
                             bool device_split = false, const mbpe_pack_window *win = nullptr,
                             const struct mbpe_pack_fit *fit = nullptr);
+    // the same documents as the two matrices of an encoder-decoder batch (mbpe_encoder_encode_batch_denoise, or --
+    // device_split -- mbpe_encoder_encode_batch_endmask_denoise): the arguments go to it as they are, its code is returned
+    int encode_batch_denoise(const char *text, const uint64_t *doc_off, uint64_t n_docs, bool verbose, int device,
+                             const mbpe_denoise_spec *dn, const mbpe_pack_spec *enc_spec, const mbpe_pack_spec *dec_spec,
+                             const mbpe_denoise_batch *out, uint64_t cap_rows, int out_on_device, uint64_t *n_rows_out,
+                             uint64_t *n_tokens_out, bool device_split);
     // How often every token id is used (mbpe_tok_count_tokens): the documents are split as in encode_batch_flat and what
     // encode would return for each is counted `repeat` times into a table the tokenizer keeps on the host, of
     // count_ids() = max(256 + merges, largest special id + 1) entries.  device < 0: the host loop over encode();

@@ -56,6 +56,8 @@ EXPORTS = [
     "mbpe_fim_plan", "mbpe_fim_tokens", "mbpe_fim_kernel_ms", "mbpe_encoder_set_fim", "mbpe_encoder_fim_info",
     "mbpe_mlm_plan", "mbpe_mlm_tokens", "mbpe_mlm_kernel_ms", "mbpe_pack_tokens_aux_labels", "mbpe_pack_windows_labels",
     "mbpe_pack_fit_labels", "mbpe_encoder_set_mlm",
+    "mbpe_denoise_plan", "mbpe_denoise_tokens", "mbpe_denoise_kernel_ms", "mbpe_encoder_encode_batch_denoise",
+    "mbpe_encoder_encode_batch_endmask_denoise",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -71,7 +73,7 @@ TOK_EXPORTS = [
     "mbpe_tok_train_pieces_export_size", "mbpe_tok_train_pieces_export", "mbpe_tok_train_pieces_merge",
     "mbpe_tok_encode_batch_windows_device", "mbpe_tok_count_tokens", "mbpe_tok_token_counts",
     "mbpe_tok_token_counts_reset", "mbpe_tok_encode_batch_fit_device", "mbpe_tok_set_encode_fim",
-    "mbpe_tok_encode_fim_info", "mbpe_tok_set_encode_mlm",
+    "mbpe_tok_encode_fim_info", "mbpe_tok_set_encode_mlm", "mbpe_tok_encode_batch_denoise_device",
 ]
 
 
@@ -156,6 +158,24 @@ class MlmSpec(ctypes.Structure):
         ("select", ctypes.c_uint64), ("mask", ctypes.c_uint64), ("random", ctypes.c_uint64), ("seed", ctypes.c_uint64),
         ("doc_base", ctypes.c_uint64), ("mask_id", ctypes.c_uint32), ("vocab_n", ctypes.c_uint32),
         ("whole_word", ctypes.c_uint32), ("n_protect", ctypes.c_uint32), ("protect", ctypes.c_uint32 * 8),
+    ]
+
+
+class DenoiseSpec(ctypes.Structure):
+    """mbpe_denoise_spec (include/mbpe.h): span corruption for encoder-decoder models; denoise_spec() makes one."""
+    _fields_ = [
+        ("density", ctypes.c_uint64), ("seed", ctypes.c_uint64), ("doc_base", ctypes.c_uint64),
+        ("mean_span_q8", ctypes.c_uint32), ("segment_tokens", ctypes.c_uint32), ("min_tokens", ctypes.c_uint32),
+        ("sentinel_id", ctypes.c_uint32), ("sentinel_down", ctypes.c_uint32), ("n_sentinels", ctypes.c_uint32),
+    ]
+
+
+class DenoiseBatch(ctypes.Structure):
+    """mbpe_denoise_batch (include/mbpe.h): where the two matrices of a denoise batch call go (NULL: not asked for)."""
+    _fields_ = [
+        ("enc_ids", ctypes.c_void_p), ("enc_len", ctypes.c_void_p), ("dec_ids", ctypes.c_void_p),
+        ("dec_len", ctypes.c_void_p), ("dec_labels", ctypes.c_void_p), ("row_doc", ctypes.c_void_p),
+        ("ignore_label", ctypes.c_int64),
     ]
 
 
@@ -370,6 +390,14 @@ def lib():
     L.mbpe_tok_count_tokens.argtypes = [vp, vp, vp, u64, i32, i32, u64, vp]
     L.mbpe_tok_token_counts.argtypes = [vp, vp, u64, vp, vp]
     L.mbpe_tok_token_counts_reset.argtypes = [vp]
+    L.mbpe_denoise_plan.argtypes = [vp, u64, vp, vp, vp, vp, vp, u64]
+    L.mbpe_denoise_tokens.argtypes = [i32, vp, u64, u32, i32, vp, u64, vp, vp, u64, vp, u64, i32, vp, vp, vp, u64, vp, vp,
+                                      vp]
+    L.mbpe_denoise_kernel_ms.argtypes = [vp]
+    L.mbpe_encoder_encode_batch_denoise.argtypes = [vp, vp, u64, i32, vp, u64, vp, u64, vp, vp, vp, vp, u64, i32, vp, vp]
+    L.mbpe_encoder_encode_batch_endmask_denoise.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, vp, vp, u64, i32,
+                                                            vp, vp]
+    L.mbpe_tok_encode_batch_denoise_device.argtypes = [vp, vp, vp, u64, i32, i32, vp, vp, vp, vp, u64, i32, vp, vp]
     L.mbpe_fim_plan.argtypes = [vp, u64, vp, vp, vp, vp]
     L.mbpe_fim_tokens.argtypes = [i32, vp, u64, u32, i32, vp, u64, vp, vp, u64, i32, vp, vp]
     L.mbpe_fim_kernel_ms.argtypes = [vp]
@@ -585,6 +613,147 @@ def fim_kernel_ms():
     ms = ctypes.c_float()
     _check(lib().mbpe_fim_kernel_ms(ctypes.byref(ms)))
     return ms.value
+
+
+def denoise_spec(density=0.15, mean_span=3.0, sentinel_id=None, n_sentinels=100, sentinel_down=True, segment_tokens=0,
+                 min_tokens=0, seed=0, doc_base=0):
+    """A DenoiseSpec from T5's terms: `density` of every unit's tokens become noise, in runs of mean_span tokens on
+    average; run j is replaced by the sentinel sentinel_id - j (sentinel_down, T5's <extra_id_j>) or sentinel_id + j,
+    and no unit gets more than n_sentinels runs.  segment_tokens > 0 cuts every document into units of that many tokens
+    first (denoise_segment_for() finds the number that fills two sequence lengths); units shorter than
+    max(min_tokens, 2) stay as they are.  seed picks the epoch's draw, doc_base is the number of the call's first
+    document in the corpus.  The rule: include/mbpe.h, mbpe_denoise_spec."""
+    if sentinel_id is None:
+        raise ValueError("sentinel_id is required: the id of the first sentinel")
+    q8 = int(round(float(mean_span) * 256))
+    return DenoiseSpec(dropout_threshold(density), int(seed) & 0xFFFFFFFFFFFFFFFF, int(doc_base) & 0xFFFFFFFFFFFFFFFF,
+                       q8, segment_tokens, min_tokens, sentinel_id, int(bool(sentinel_down)), n_sentinels)
+
+
+def _denoise_counts(L, density, mean_q8, n_sentinels, min_tokens=0):
+    """(N, S) of a unit of L tokens -- the closed forms of include/mbpe.h -- for a density threshold."""
+    if density == 0 or L < max(min_tokens, 2):
+        return 0, 0
+    N = min(max((L * density + (1 << 31)) >> 32, 1), L - 1)
+    S = (N * 256 + mean_q8 // 2) // mean_q8
+    return N, max(1, min(S, N, L - N, n_sentinels))
+
+
+def denoise_segment_for(enc_len, dec_len, density=0.15, mean_span=3.0, eos=True, n_sentinels=100):
+    """The largest segment_tokens whose units all fit: the inputs of every unit of up to that many tokens (and eos)
+    fit enc_len, and its targets (and eos) fit dec_len, by search over the closed-form counts.  T5's 512 / 114 at the
+    defaults give 568.  0 if not even a unit of one token fits."""
+    thr, q8, e = dropout_threshold(density), int(round(float(mean_span) * 256)), int(bool(eos))
+    best = 0
+    while True:
+        L = best + 1
+        N, S = _denoise_counts(L, thr, q8, n_sentinels)
+        if L - N + S + e > enc_len or (N + S + e if S else 0) > dec_len or L >= 0xFFFFFFFF:
+            return best
+        best = L
+
+
+def _flat_tokens(tokens, tokens_ptr, n_tokens, token_bits):
+    """tokens (or a device pointer) as the C-ABI takes them -> (array kept alive, pointer, count, bits, on_device)."""
+    if tokens_ptr is not None:
+        return None, _ptr(tokens_ptr), n_tokens, token_bits, 1
+    t = np.ascontiguousarray(tokens)
+    if t.dtype not in (np.dtype(np.uint16), np.dtype(np.uint32)):
+        t = t.astype(np.uint32)
+    t = t.reshape(-1)
+    return t, (t.ctypes.data if len(t) else None), len(t), t.dtype.itemsize * 8, 0
+
+
+def denoise_plan(doc_tok_off, spec):
+    """mbpe_denoise_plan (host only): what span corruption makes of documents of these token offsets -> (unit_in_off
+    [n_units + 1], unit_tg_off [n_units + 1], unit_doc [n_units]): the units' offsets into the inputs and into the
+    targets, and every unit's document."""
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    n = ctypes.c_uint64()
+    _check(lib().mbpe_denoise_plan(off.ctypes.data, len(off) - 1, ctypes.byref(spec), ctypes.byref(n), None, None, None, 0))
+    in_off, tg_off = np.zeros(n.value + 1, dtype=np.uint64), np.zeros(n.value + 1, dtype=np.uint64)
+    unit_doc = np.zeros(max(n.value, 1), dtype=np.uint64)
+    _check(lib().mbpe_denoise_plan(off.ctypes.data, len(off) - 1, ctypes.byref(spec), ctypes.byref(n), in_off.ctypes.data,
+                                   tg_off.ctypes.data, unit_doc.ctypes.data, n.value))
+    return in_off, tg_off, unit_doc[:n.value]
+
+
+def denoise_tokens(tokens, doc_tok_off, spec, device=0, tokens_ptr=None, n_tokens=None, token_bits=None, in_ptr=None,
+                   cap_in=0, tg_ptr=None, cap_tg=0):
+    """mbpe_denoise_tokens: span corruption of a flat token array (uint16 or uint32) whose document i is
+    tokens[doc_tok_off[i]:doc_tok_off[i + 1]] -> (inputs, targets, unit_in_off, unit_tg_off, unit_doc): two flat arrays
+    of the same dtype, one document ("unit") per row-to-be in each, which pack_* and Decoder.decode_batch take with
+    their offsets.  Device memory: tokens_ptr= / n_tokens= / token_bits= name the tokens there instead of `tokens`; with
+    in_ptr= and tg_ptr= (room for cap_in / cap_tg ids) the streams are written there and (n_in, n_tg, unit_in_off,
+    unit_tg_off, unit_doc) is returned."""
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    keep, tp, n_tokens, token_bits, on_dev = _flat_tokens(tokens, tokens_ptr, n_tokens, token_bits)
+    nu, ni, nt = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    head = (device, tp, n_tokens, token_bits, on_dev, off.ctypes.data, len(off) - 1, ctypes.byref(spec))
+    tail = (ctypes.byref(nu), ctypes.byref(ni), ctypes.byref(nt))
+    fn = lib().mbpe_denoise_tokens
+    _check(fn(*head, None, 0, None, 0, 0, None, None, None, 0, *tail))
+    in_off, tg_off = np.zeros(nu.value + 1, dtype=np.uint64), np.zeros(nu.value + 1, dtype=np.uint64)
+    unit_doc = np.zeros(max(nu.value, 1), dtype=np.uint64)
+    units = (in_off.ctypes.data, tg_off.ctypes.data, unit_doc.ctypes.data, nu.value)
+    if in_ptr is not None:
+        rc = fn(*head, _ptr(in_ptr), cap_in, _ptr(tg_ptr), cap_tg, 1, *units, *tail)
+        _check(rc)
+        return ni.value, nt.value, in_off, tg_off, unit_doc[:nu.value]
+    inp = np.zeros(max(ni.value, 1), dtype=_ID_DTYPES[token_bits])
+    tgt = np.zeros(max(nt.value, 1), dtype=_ID_DTYPES[token_bits])
+    _check(fn(*head, inp.ctypes.data, ni.value, tgt.ctypes.data, nt.value, 0, *units, *tail))
+    return inp[:ni.value], tgt[:nt.value], in_off, tg_off, unit_doc[:nu.value]
+
+
+def denoise_kernel_ms():
+    """Device time of the kernels of this thread's latest denoise_tokens (mbpe_denoise_kernel_ms)."""
+    ms = ctypes.c_float()
+    _check(lib().mbpe_denoise_kernel_ms(ctypes.byref(ms)))
+    return ms.value
+
+
+_DENOISE_PTRS = ("enc_ids", "enc_len", "dec_ids", "dec_len", "dec_labels", "row_doc")
+
+
+def _denoise_specs(enc_len, dec_len, out_bits, pad_id, eos_id, decoder_start_id):
+    """The two PADDED specs of a denoise batch: the encoder side ends in eos, the decoder side begins with the decoder
+    start id and ends in eos (either None: none)."""
+    return (pack_spec(enc_len, "padded", out_bits, pad_id, None, eos_id),
+            pack_spec(dec_len, "padded", out_bits, pad_id, decoder_start_id, eos_id))
+
+
+def _denoise_batch(call, n_docs, dn, enc_spec, dec_spec, ignore_label, ptrs, cap_rows, labels, row_doc):
+    """One denoise batch call.  call(batch_ref, cap_rows, on_device) -> (rc, n_rows, n_tokens).  ptrs: a dict of device
+    pointers by the names of mbpe_denoise_batch -> (n_rows, n_tokens); None -> (dict of numpy arrays, n_tokens)."""
+    if ptrs is not None:
+        unknown = set(ptrs) - set(_DENOISE_PTRS)
+        if unknown:
+            raise ValueError("unknown outputs: %s" % sorted(unknown))
+        b = DenoiseBatch(*[ptrs.get(k) or None for k in _DENOISE_PTRS], int(ignore_label))
+        rc, n_rows, n_tok = call(ctypes.byref(b), cap_rows or 0, 1)
+        return rc, n_rows, n_tok
+    if dn.segment_tokens == 0:
+        n_rows = n_docs                               # known without a query
+    else:
+        rc, n_rows, n_tok = call(ctypes.byref(DenoiseBatch(None, None, None, None, None, None, int(ignore_label))), 0, 0)
+        _check(rc)
+    enc_ids, enc_n = _matrix(n_rows, enc_spec)
+    dec_ids, dec_n = _matrix(n_rows, dec_spec)
+    lab = np.zeros((n_rows, dec_spec.seq_len), dtype=_LABEL_DTYPES[dec_spec.out_bits]) if labels else None
+    rd = np.zeros(n_rows, dtype=np.uint32) if row_doc else None
+    out = {"enc_ids": enc_ids, "enc_len": enc_n, "dec_ids": dec_ids, "dec_len": dec_n}
+    if labels:
+        out["dec_labels"] = lab
+    if row_doc:
+        out["row_doc"] = rd
+    n_tok = 0
+    if n_rows:
+        b = DenoiseBatch(enc_ids.ctypes.data, enc_n.ctypes.data, dec_ids.ctypes.data, dec_n.ctypes.data,
+                         lab.ctypes.data if labels else None, rd.ctypes.data if row_doc else None, int(ignore_label))
+        rc, _, n_tok = call(ctypes.byref(b), n_rows, 0)
+        _check(rc)
+    return 0, out, n_tok
 
 
 def mlm_spec(rate, mask_id, vocab_n, mask_share=0.8, random_share=0.1, seed=0, doc_base=0, whole_word=False, protect=()):
@@ -1427,6 +1596,56 @@ class Encoder:
                   *tail, ctypes.byref(aux) if call else None, doc_tok_off.ctypes.data))
         self.n_tokens, self.doc_tok_off = n_tok.value, doc_tok_off
         return call.result(ids, lengths, arrays, doc_tok_off) if call else (ids, lengths)
+
+    def encode_batch_denoise(self, texts_or_buffer, chunk_off=None, doc_chunk_off=None, *, enc_len, dec_len, denoise,
+                             out_bits=32, pad_id=0, eos_id=None, decoder_start_id=None, ignore_label=-100, labels=True,
+                             row_doc=True, text_ptr=None, n_bytes=None, ptrs=None, cap_rows=None):
+        """Encode, span-corrupt and pack twice in one device call (mbpe_encoder_encode_batch_denoise): texts as for
+        encode_batch, denoise a DenoiseSpec (denoise_spec()) -> a dict of numpy arrays, one row per unit: "enc_ids"
+        [rows, enc_len] and "enc_len" -- the inputs, ending in eos_id --, "dec_ids" [rows, dec_len] and "dec_len" -- the
+        targets behind decoder_start_id, ending in eos_id --, "dec_labels" (next-token labels of dec_ids, ignore_label
+        elsewhere) and "row_doc" (the row's document).  With ptrs= (a dict of device pointers by those names, e.g.
+        torch tensors' data_ptr(), with room for cap_rows rows; an empty dict is a query) the matrices are written
+        there and the row count is returned; self.n_rows holds it also where a cap_rows too small is refused.  The
+        tokens encoded: self.n_tokens.  Not while set_fim or set_mlm is on."""
+        es, ds = _denoise_specs(enc_len, dec_len, out_bits, pad_id, eos_id, decoder_start_id)
+        head, keep = self._batch_head(texts_or_buffer, chunk_off, doc_chunk_off, text_ptr, n_bytes, es)
+        fn = lib().mbpe_encoder_encode_batch_denoise
+
+        def call(batch, cap, on_dev):
+            n_rows, n_tok = ctypes.c_uint64(), ctypes.c_uint64()
+            rc = fn(*head[:-1], ctypes.byref(denoise), ctypes.byref(es), ctypes.byref(ds), batch, cap, on_dev,
+                    ctypes.byref(n_rows), ctypes.byref(n_tok))
+            return rc, n_rows.value, n_tok.value
+        return self._denoise_done(_denoise_batch(call, len(keep[-1]) - 1, denoise, es, ds, ignore_label, ptrs, cap_rows,
+                                                 labels, row_doc))
+
+    def encode_batch_endmask_denoise(self, text_ptr, n_bytes, mask_ptr, singles, doc_off, *, enc_len, dec_len, denoise,
+                                     out_bits=32, pad_id=0, eos_id=None, decoder_start_id=None, ignore_label=-100,
+                                     labels=True, row_doc=True, ptrs=None, cap_rows=None):
+        """encode_batch_denoise for a text and an end mask on the device (mbpe_encoder_encode_batch_endmask_denoise):
+        the first five arguments as for encode_batch_endmask, the rest and the result as for encode_batch_denoise."""
+        es, ds = _denoise_specs(enc_len, dec_len, out_bits, pad_id, eos_id, decoder_start_id)
+        sg = _singles(singles)
+        docs = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        fn = lib().mbpe_encoder_encode_batch_endmask_denoise
+
+        def call(batch, cap, on_dev):
+            n_rows, n_tok = ctypes.c_uint64(), ctypes.c_uint64()
+            rc = fn(self._h, _ptr(text_ptr), n_bytes, _ptr(mask_ptr), sg.ctypes.data if len(sg) else None, len(sg),
+                    docs.ctypes.data, len(docs) - 1, ctypes.byref(denoise), ctypes.byref(es), ctypes.byref(ds), batch, cap,
+                    on_dev, ctypes.byref(n_rows), ctypes.byref(n_tok))
+            return rc, n_rows.value, n_tok.value
+        return self._denoise_done(_denoise_batch(call, len(docs) - 1, denoise, es, ds, ignore_label, ptrs, cap_rows, labels,
+                                                 row_doc))
+
+    def _denoise_done(self, res):
+        rc, out, n_tok = res
+        self.n_tokens = n_tok
+        if isinstance(out, int):
+            self.n_rows = out
+        _check(rc)
+        return out
 
     def _count(self, fn, head, repeat):
         n, passes = ctypes.c_uint64(), ctypes.c_uint32()
@@ -2540,6 +2759,38 @@ class Tokenizer:
         _check(lib().mbpe_tok_encode_batch_packed_device(*head, ids.ctypes.data if ids.size else None, len(ids), 0,
                                                          lengths.ctypes.data if len(ids) else None, *tail))
         return ids, lengths
+
+    def encode_batch_denoise(self, texts, enc_len, dec_len, denoise, device=0, out_bits=32, pad_id=0, eos_id=None,
+                             decoder_start_id=None, ignore_label=-100, labels=True, row_doc=True, ptrs=None,
+                             cap_rows=None, device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False):
+        """Every text split like encode(), encoded, span-corrupted (T5 / UL2; denoise: a DenoiseSpec from
+        denoise_spec()) and packed into the two matrices of an encoder-decoder batch in one device call
+        (mbpe_tok_encode_batch_denoise_device) -> the dict of Encoder.encode_batch_denoise, as numpy arrays or -- ptrs=,
+        cap_rows= -- written into device memory such as torch tensors, the row count returned (self.n_rows holds it
+        also where cap_rows is too small).  One row per unit: with denoise.segment_tokens a long text becomes several
+        rows and "row_doc" says whose.  eos_id, decoder_start_id and the sentinels may be special-token ids.  The
+        tokens encoded: self.n_tokens."""
+        self._encode_split(device_split, order, dropout, seed, dedup)
+        es, ds = _denoise_specs(enc_len, dec_len, out_bits, pad_id, eos_id, decoder_start_id)
+        parts = [bytes(_u8(t)) for t in texts]
+        doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        if parts:
+            doc_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
+        text = np.frombuffer(b"".join(parts), dtype=np.uint8)
+        fn = lib().mbpe_tok_encode_batch_denoise_device
+
+        def call(batch, cap, on_dev):
+            n_rows, n_tok = ctypes.c_uint64(), ctypes.c_uint64()
+            rc = fn(self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data, len(parts), 0, device,
+                    ctypes.byref(denoise), ctypes.byref(es), ctypes.byref(ds), batch, cap, on_dev, ctypes.byref(n_rows),
+                    ctypes.byref(n_tok))
+            return rc, n_rows.value, n_tok.value
+        rc, out, self.n_tokens = _denoise_batch(call, len(parts), denoise, es, ds, ignore_label, ptrs, cap_rows, labels,
+                                                row_doc)
+        if isinstance(out, int):
+            self.n_rows = out
+        _check(rc)
+        return out
 
     def encode_batch_aux(self, texts, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
                          pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
