@@ -569,6 +569,9 @@ MBPE_API int  mbpe_encoder_encode(mbpe_encoder *e, const uint8_t *text, uint64_t
  *                   short kernels and one 8-byte read-back, as in the default order; mbpe_encoder_pass_tokens reports
  *                   them.  The option adds 20 bytes per 1,024 text bytes to the work buffers, allocated when the
  *                   first call in rank order needs them.
+ *   "resident"      0 (default) | 1: the rounds of every chunk of at most 256 bytes run in one kernel, on the chip; the
+ *                   result is the same, n_passes_out and mbpe_encoder_pass_tokens count the stage as one pass -- see
+ *                   mbpe_encoder_resident_stats.
  * An unknown name or a negative value is MBPE_ERR_ARG. */
 MBPE_API int  mbpe_encoder_set_option(mbpe_encoder *e, const char *name, int64_t value);
 
@@ -666,6 +669,36 @@ MBPE_API int  mbpe_encoder_alloc_count(const mbpe_encoder *e, uint64_t *n_out);
  * and the copy come on top of the same passes (README, "Encoding through the unique chunks"). */
 MBPE_API int  mbpe_encoder_dedup_stats(const mbpe_encoder *e, uint64_t *n_chunks_out, uint64_t *n_unique_out,
                                        uint64_t *n_unique_bytes_out, uint64_t *n_unique_tokens_out, float *expand_ms_out);
+
+/* ---- the short chunks' rounds in one kernel (csrc/resident.h, k_enc_resident in csrc/encode.hip) ----------------------
+ * mbpe_encoder_set_option(e, "resident", 0 | 1), default 0; any other value is MBPE_ERR_ARG.  With 0 the encoder launches
+ * and allocates exactly what it does without the option.  With 1 every encode and count call gives the same tokens,
+ * offsets, matrices and error codes, in both orders and with dropout, and only the pass stage differs: the upload, the
+ * widen kernel and the one-token chunks before it and the finishing stage after it are as they are.
+ *   1. The piece is cut into TILES of whole chunks near every multiple of 768 bytes: a boundary is the position after
+ *      the first chunk end among the 256 bytes from byte 768 t - 1 on (the search bound).  A tile holds at most 1,023
+ *      bytes.  Where no chunk ends there -- a chunk longer than the search bound -- the boundary is 768 t and the two
+ *      tiles beside it are RAW.
+ *   2. One wave per tile runs every merge round of its chunks on a private 6 KB of LDS until a round replaces nothing,
+ *      with no pass over the stream, no scan and no read-back in between; a raw tile is left as it is and counted.
+ *   3. One scan over the tiles' token counts, one kernel that puts the tiles' results side by side, and ONE read-back
+ *      per piece: the tokens after the stage and the raw tiles.
+ *   4. No raw tile: the piece is done.  Otherwise the passes above go on from that stream; every chunk of a resident
+ *      tile is at its fixed point (a dropped instance stays dropped: it is a function of seed, byte start and id), so
+ *      they finish the long chunks only.
+ * n_passes_out is then 1 for the stage plus the passes that followed it, and mbpe_encoder_pass_tokens reports [0] =
+ * the pieces' bytes and then the following passes' entries.  With "dedup" 1 the stage runs over the unique text.
+ * Device memory: 12 bytes per tile more, which is 0.016 bytes per text byte -- a piece then costs 13.25 bytes per text
+ * byte in rank order, still below the divisor 14 of "piece_bytes" -- allocated by the first call that needs them.
+ *   mbpe_encoder_resident_stats  the latest call, summed over its pieces: the tiles, the raw ones among them, and the
+ *                                tokens that left the stage (the call's token count when no tile was raw); any pointer
+ *                                may be NULL.  MBPE_ERR_STATE when the latest call did not run the stage (the option was
+ *                                0, or the text was empty).
+ * Use it in rank order and above all with dropout, where "dedup" is refused and every epoch encodes again; it gains
+ * nothing on a text that is one chunk or whose chunks are longer than 256 bytes, which pays the stage and then runs
+ * every pass (README, "Encoding with the rounds on the chip"). */
+MBPE_API int  mbpe_encoder_resident_stats(const mbpe_encoder *e, uint64_t *n_tiles_out, uint64_t *n_raw_tiles_out,
+                                          uint64_t *n_tokens_after_out);
 
 /* ---- fixed-length id matrices --------------------------------------------- */
 

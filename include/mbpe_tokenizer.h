@@ -308,6 +308,13 @@ MBPE_API int mbpe_tok_set_train_limits(mbpe_tokenizer *t, int64_t min_frequency,
  * so equal chunks do not share tokens, and the route is never switched silently. */
 MBPE_API int mbpe_tok_set_encode_dedup(mbpe_tokenizer *t, int on);
 
+/* The merge rounds of the short chunks on the chip: 0 (the default) or 1; anything else is MBPE_ERR_ARG.  While it is
+ * on, every call that runs the kept device encoder (mbpe_tok_encode_device, the batch, byte-range and count calls on a
+ * device) runs it with its option "resident" (mbpe.h, mbpe_encoder_resident_stats): the same tokens, offsets and
+ * matrices, in both orders, with dropout, with the host and the device split and with mbpe_tok_set_encode_dedup.  The
+ * encoder is re-configured, not re-created.  The host loop (mbpe_tok_encode) is unaffected. */
+MBPE_API int mbpe_tok_set_encode_resident(mbpe_tokenizer *t, int on);
+
 /* Token frequency tables: how often every token id is used on a corpus, without a token leaving the device.
  * mbpe_tok_count_tokens splits the documents as mbpe_tok_encode_batch_device does (special tokens first, each document on
  * its own) and adds what mbpe_tok_encode would return for each, `repeat` times (at least 1: 0 is MBPE_ERR_ARG), to a

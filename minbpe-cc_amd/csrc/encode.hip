@@ -60,6 +60,7 @@
 #include "pack.h"
 #include "pack_fit.h"
 #include "rank.h"
+#include "resident.h"
 #include "span.h"
 
 #include <algorithm>
@@ -290,6 +291,182 @@ __global__ __launch_bounds__(kSpanThreads) void k_enc_scatter_org(const uint32_t
     span_scatter_carry<true>(val, n, span_off, out, org, org_out);
 }
 
+// ---- option "resident": every round of the short chunks in one kernel (resident.h has the tiles) -----------------
+// One wave owns one tile of whole chunks and a private region of LDS: the tile's tokens and, DROP, their byte starts
+// relative to the tile.  A round is the pass above on that region -- look up, (DROP) drop, (RANK) the chunks' minimum
+// and the filter, run parity, decide as k_enc_match does, compact to the front -- with every link between spans the
+// identity: nothing reaches a tile of whole chunks from either side (no candidate run, no open chunk).  All of a
+// round's reads are in registers before its first write; the waves of a workgroup never meet and no workgroup waits
+// for another.  Rounds repeat until one replaces nothing (the first always compacts: it removes kDrop); a round that
+// replaces shortens the tile, so len + 1 rounds bound the loop whatever the table holds.  A raw tile is left as widen
+// and single wrote it and counted.  The result goes back in place: a tile reads and writes its own range only.
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ uint32_t wave_first(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, 0); }
+__device__ __forceinline__ uint32_t wave_last(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, kWave - 1); }
+
+// raw[0] counts the raw tiles; the counting build (MBPE_RESIDENT_ROUNDS) adds raw[1], the rounds of all resident tiles,
+// the one that finds nothing included, and raw[2], the most of one
+template <bool RANK, bool DROP>
+__global__ __launch_bounds__(kSpanThreads) void k_enc_resident(uint32_t *__restrict__ tok, uint32_t *__restrict__ org,
+                                                               const uint32_t *__restrict__ mask, uint64_t pn,
+                                                               uint64_t n_tiles, EncLut lut, EncDrop drop,
+                                                               uint32_t *__restrict__ tile_cnt,
+                                                               unsigned long long *__restrict__ raw) {
+    __shared__ uint32_t sh_tok[kSpanWaves][kSpan];
+    __shared__ uint16_t sh_org[DROP ? kSpanWaves : 1][DROP ? kSpan : 1];
+    const uint64_t tile = span_index();
+    if (tile >= n_tiles) return;                                     // (whole waves leave together)
+    const uint32_t lane = lane_id();
+    const unsigned long long lt = lanes_below(lane);
+    const ResTile g = res_tile(mask, pn, tile);
+    if (!g.resident) {
+        if (lane == 0) {
+            tile_cnt[tile] = g.len;
+            atomicAdd(raw, 1ull);
+        }
+        return;
+    }
+    uint32_t *l_tok = sh_tok[threadIdx.x / kWave];
+    uint16_t *l_org = sh_org[DROP ? threadIdx.x / kWave : 0];
+    uint32_t len = g.len;                                            // the live prefix of the region; wave-uniform
+    for (uint32_t i = lane; i < len; i += kWave) {
+        l_tok[i] = tok[g.lo + i];
+        if (DROP) l_org[i] = (uint16_t)i;
+    }
+    wave_lds_sync();
+    const uint32_t max_rounds = len + 1;
+    uint32_t round = 0;
+    for (; round < max_rounds && len; ++round) {
+        // 1: the live prefix in the span layout, the right neighbours from LDS, the candidates
+        uint32_t t[kSpanIters], f[kSpanIters], s[kSpanIters];
+        unsigned long long E[kSpanIters];
+        uint32_t nx_end = 0;                                         // bit `it`: the right neighbour ends its chunk
+#pragma unroll
+        for (int it = 0; it < kSpanIters; ++it) {
+            t[it] = kDrop;
+            f[it] = kTokNone;
+            s[it] = 0;
+            E[it] = 0ull;
+            if ((uint32_t)it * kWave < len) {
+                const uint32_t i = (uint32_t)it * kWave + lane;
+                const uint32_t tt = i < len ? l_tok[i] : kDrop;
+                const uint32_t nx = i + 1 < len ? l_tok[i + 1] : kDrop;
+                uint32_t c = kTokNone;
+                if (i < len && !(tt & kTokEnd) && tt != kDrop && nx != kDrop) c = enc_lookup(lut, tt, nx & kTokIdMask);
+                if (DROP) {
+                    s[it] = i < len ? l_org[i] : 0u;
+                    if (c != kTokNone && dropout_dropped(drop.seed, drop.piece_base + g.lo + s[it], c, drop.threshold))
+                        c = kTokNone;
+                }
+                t[it] = tt;
+                f[it] = c;
+                nx_end |= (nx >> 31) << it;
+                if (RANK) E[it] = __ballot(i < len && (tt & kTokEnd));
+            }
+        }
+        // 2, RANK: only the candidates that equal their chunk's minimum stay (k_enc_rank_filter; nothing comes in)
+        if (RANK) {
+            uint32_t m[kSpanIters], tail[kSpanIters], right[kSpanIters];
+            uint32_t run = kTokNone;
+#pragma unroll
+            for (int it = kSpanIters - 1; it >= 0; --it) {
+                m[it] = kTokNone;
+                tail[it] = kTokNone;
+                right[it] = run;
+                if ((uint32_t)it * kWave < len) {
+                    m[it] = group_seg_min(f[it], E[it], lt, lane);
+                    tail[it] = E[it] >> 63 ? kTokNone : wave_last(m[it]);
+                    run = rank_carry(run, E[it] != 0ull, wave_first(m[it]));
+                }
+            }
+            run = kTokNone;
+#pragma unroll
+            for (int it = 0; it < kSpanIters; ++it) {
+                if ((uint32_t)it * kWave < len) {
+                    uint32_t v = m[it];
+                    if (rank_open_left(E[it], lt)) v = rank_min(v, run);
+                    if (rank_open_right(E[it], lt)) v = rank_min(v, right[it]);
+                    if (f[it] != v) f[it] = kTokNone;
+                    run = rank_carry(run, E[it] != 0ull, tail[it]);
+                }
+            }
+        }
+        // 3: run parity and the decision of k_enc_match; f becomes what the position gives the next round
+        uint32_t carry = 0;
+        unsigned long long any = 0ull;
+#pragma unroll
+        for (int it = 0; it < kSpanIters; ++it) {
+            if ((uint32_t)it * kWave < len) {
+                const uint32_t i = (uint32_t)it * kWave + lane;
+                const unsigned long long M = __ballot(f[it] != kTokNone);
+                const bool odd = run_below(M, lt, lane, carry) & 1u;
+                uint32_t v = kTokNone;
+                if (i < len && !odd && t[it] != kDrop)
+                    v = f[it] != kTokNone ? (f[it] | (((nx_end >> it) & 1u) << 31)) : t[it];
+                f[it] = v;
+                any |= M;
+                carry = run_carry(M, carry);
+            }
+        }
+        if (any == 0ull && round > 0) break;                         // nothing replaced, nothing to drop: a fixed point
+        // 4: the kept values to the front of the region, a merged token with its left token's byte start
+        wave_lds_sync();
+        uint32_t o = 0;
+#pragma unroll
+        for (int it = 0; it < kSpanIters; ++it) {
+            if ((uint32_t)it * kWave < len) {
+                const WaveKeep k = wave_keep(f[it] != kTokNone, lt);
+                if (f[it] != kTokNone) {
+                    l_tok[o + k.rank] = f[it];
+                    if (DROP) l_org[o + k.rank] = (uint16_t)s[it];
+                }
+                o += k.count;
+            }
+        }
+        wave_lds_sync();
+        len = o;
+        if (any == 0ull) break;
+    }
+    for (uint32_t i = lane; i < len; i += kWave) {
+        tok[g.lo + i] = l_tok[i];
+        if (DROP) org[g.lo + i] = (uint32_t)g.lo + l_org[i];
+    }
+    if (lane == 0) {
+        tile_cnt[tile] = len;
+#ifdef MBPE_RESIDENT_ROUNDS
+        atomicAdd(raw + 1, (unsigned long long)round + 1ull);
+        atomicMax(raw + 2, (unsigned long long)round + 1ull);
+#endif
+    }
+}
+
+// the tiles' results, which lie at their tiles' starts in tok_in, side by side in tok_out (ORG: the byte starts too);
+// tile_off = the exclusive sums of tile_cnt
+template <bool ORG>
+__global__ __launch_bounds__(kSpanThreads) void k_enc_tile_gather(const uint32_t *__restrict__ tok_in,
+                                                                  const uint32_t *__restrict__ org_in,
+                                                                  const uint32_t *__restrict__ mask, uint64_t pn,
+                                                                  uint64_t n_tiles,
+                                                                  const uint32_t *__restrict__ tile_cnt,
+                                                                  const unsigned long long *__restrict__ tile_off,
+                                                                  uint32_t *__restrict__ tok_out,
+                                                                  uint32_t *__restrict__ org_out) {
+    const uint64_t tile = span_index();
+    if (tile >= n_tiles) return;
+    const uint64_t lo = res_bound(mask, pn, tile).lo;
+    const unsigned long long off = tile_off[tile];
+    const uint32_t cnt = tile_cnt[tile];
+    for (uint32_t i = lane_id(); i < cnt; i += kWave) {
+        tok_out[off + i] = tok_in[lo + i];
+        if (ORG) org_out[off + i] = org_in[lo + i];
+    }
+}
+
 // ---- the finishing kernels: what leaves the passes becomes what the caller asked for ----------------------------
 
 // chunk starts whose byte is NUL, for a text that lives on the device (the host runs stoi_value on those chunks):
@@ -484,6 +661,11 @@ constexpr uint64_t kPieceCost = 14;
 constexpr uint64_t kPieceCostDropout = 8;  // more while dropout is on: the two org arrays, one uint32_t per token each
 constexpr uint64_t kPieceMaxDropout = 1ull << 32;   // ... and the most bytes of a piece then: org is 32 bits
 constexpr uint64_t kPieceCostByteOff = 8;  // more with byte offsets for the host: one uint64_t per token, at most per byte
+#ifdef MBPE_RESIDENT_ROUNDS
+constexpr size_t kResWords = 6;             // entries of d_res: [4], [5] are the counting build's rounds
+#else
+constexpr size_t kResWords = 4;
+#endif
 constexpr uint64_t kNulListMin = 4096;     // entries the list of NUL-led chunk starts begins with
 constexpr uint64_t kNulCopyEach = 256;     // up to this many NUL-led chunks are copied back one by one
 
@@ -494,6 +676,7 @@ struct mbpe_encoder : DevQueue {
     float last_ms = 0.f;
     uint64_t piece_bytes = 0;                 // option "piece_bytes"; 0 = from the free device memory
     bool rank_order = false;                  // option "rank_order": a pass applies every chunk's lowest merge only
+    bool resident = false;                    // option "resident": the short chunks' rounds in one kernel, then the passes
     unsigned long long drop_threshold = 0;    // mbpe_encoder_set_dropout: 0 = off, 2^32 = every instance is dropped
     unsigned long long drop_seed = 0;
     uint32_t n_merges = 0;
@@ -508,7 +691,17 @@ struct mbpe_encoder : DevQueue {
     DevBuf<RankSum> rank_sum;                 // rank order only: the spans' summaries, and what reaches every span
     DevBuf<uint32_t> rank_in;                 // from the left [0 .. n_spans) and from the right [n_spans .. 2 n_spans)
     DevBuf<uint32_t> org[2];                  // dropout only: the tokens' byte starts in the piece, beside tok[0 / 1]
-    DevBuf<unsigned long long> d_res;         // [0] total of a sum scan, [1] NUL-led chunk starts found, [2] end bits of the mask
+    DevBuf<unsigned long long> d_res;         // [0] total of a sum scan, [1] NUL-led chunk starts found, [2] end bits of the mask,
+                                              // [3] raw tiles of the resident stage
+    // option "resident" (nothing of this exists while it is 0): the tiles' token counts and their exclusive sums; the
+    // latest call's tiles, raw tiles and tokens after the stage, summed over its pieces, and whether the stage ran
+    DevBuf<uint32_t> tile_cnt;
+    DevBuf<unsigned long long> tile_off;
+    bool res_ran = false;
+    uint64_t res_tiles = 0, res_raw = 0, res_tokens = 0;
+#ifdef MBPE_RESIDENT_ROUNDS
+    uint64_t res_rounds = 0, res_rounds_max = 0;   // the counting build: see mbpe_encoder_resident_rounds
+#endif
     DevBuf<SingleChunk> d_singles;
     DevBuf<unsigned long long> d_nul;         // starts of NUL-led chunks of a device text
     DevBuf<unsigned long long> d_ends;        // chunk ends, only when chunks are shorter than two bytes on average
@@ -590,7 +783,17 @@ namespace {
 uint64_t enc_held(const mbpe_encoder *e) {
     return e->d_text.bytes() + e->d_mask.bytes() + e->tok[0].bytes() + e->tok[1].bytes() + e->cand.bytes() +
            e->span_a.bytes() + e->span_b.bytes() + e->span_off.bytes() + e->rank_sum.bytes() + e->rank_in.bytes() +
-           e->org[0].bytes() + e->org[1].bytes();
+           e->org[0].bytes() + e->org[1].bytes() + e->tile_cnt.bytes() + e->tile_off.bytes();
+}
+
+// what a call reports of its passes starts empty (mbpe_encoder_pass_tokens, mbpe_encoder_resident_stats)
+void passes_reset(mbpe_encoder *e) {
+    e->pass_tokens.clear();
+    e->res_ran = false;
+    e->res_tiles = e->res_raw = e->res_tokens = 0;
+#ifdef MBPE_RESIDENT_ROUNDS
+    e->res_rounds = e->res_rounds_max = 0;
+#endif
 }
 
 struct Piece { uint64_t c0, c1; };            // chunks [c0, c1)
@@ -776,6 +979,10 @@ int piece_upload(mbpe_encoder *e, const EncCall &a, Piece p, PieceRun *r) {
         rc = e->org[0].reserve(pn * 4, e->mem);
         if (rc == MBPE_OK) rc = e->org[1].reserve(pn * 4, e->mem);
     }
+    if (rc == MBPE_OK && e->resident) {       // (4/3 as many tiles as spans: span_a and span_off do not hold them)
+        rc = e->tile_cnt.reserve(res_tile_count(pn) * 4, e->mem);
+        if (rc == MBPE_OK) rc = e->tile_off.reserve(res_tile_count(pn) * 8, e->mem);
+    }
     if (rc != MBPE_OK) return rc;
     // the piece's NUL-led chunks (e->singles is sorted by start), relative to the piece
     e->piece_singles.clear();
@@ -815,25 +1022,10 @@ int piece_upload(mbpe_encoder *e, const EncCall &a, Piece p, PieceRun *r) {
     return MBPE_OK;
 }
 
-// ev0, bytes -> tokens, then passes until one changes nothing.  piece_base = the piece's first byte in the call's text
-int piece_passes(mbpe_encoder *e, uint64_t piece_base, PieceRun *r) {
-    const uint64_t pn = r->pn;
+// the passes over tok[cur][0 .. n) (and org[cur]) until one changes nothing; `passes` stream passes came before
+int pass_loop(mbpe_encoder *e, uint64_t piece_base, PieceRun *r, int cur, uint64_t n, uint32_t passes) {
     const bool drop = e->drop_threshold != 0;
-    ECHK(hipEventRecord(e->ev0, e->stream));
-    const int wblocks = (int)std::min<uint64_t>((pn + 255) / 256, 8192);
-    if (drop)
-        hipLaunchKernelGGL(k_enc_widen<true>, dim3(wblocks), dim3(256), 0, e->stream, r->d_text, pn,
-                           r->d_mask, e->tok[0], e->org[0]);
-    else
-        hipLaunchKernelGGL(k_enc_widen<false>, dim3(wblocks), dim3(256), 0, e->stream, r->d_text, pn,
-                           r->d_mask, e->tok[0], nullptr);
-    if (!e->piece_singles.empty())
-        hipLaunchKernelGGL(k_enc_single, dim3((uint32_t)e->piece_singles.size()), dim3(64), 0, e->stream, e->d_singles,
-                           (uint32_t)e->piece_singles.size(), e->tok[0]);
-    uint64_t n = pn;
-    int cur = 0;
-    uint32_t passes = 0;
-    for (;;) {
+    while (n) {
         const uint64_t n_spans = span_count(n);
         const dim3 grid(span_grid(n)), block(kSpanThreads);
         if (drop)
@@ -869,11 +1061,81 @@ int piece_passes(mbpe_encoder *e, uint64_t piece_base, PieceRun *r) {
         if (total == n) break;                 // the pass changed nothing: tok[cur] is the result (so is tok[1 - cur])
         n = total;
         cur = 1 - cur;
-        if (n == 0) break;
     }
     r->n = n;
     r->cur = cur;
     r->passes = passes;
+    return MBPE_OK;
+}
+
+// option "resident": the stage that stands for the passes of every chunk no longer than the search bound.  tok[0] (and
+// org[0]) as widen and single left them -> the tiles' rounds in place -> the tiles' counts summed -> the results side by
+// side in tok[1] (org[1]); one read-back: the tokens after the stage and the raw tiles.  *n = those tokens
+int resident_stage(mbpe_encoder *e, uint64_t piece_base, const PieceRun &r, uint64_t *n, uint64_t *raw_tiles) {
+    const uint64_t pn = r.pn, n_tiles = res_tile_count(pn);
+    const bool drop = e->drop_threshold != 0;
+    const uint32_t *mask = reinterpret_cast<const uint32_t *>(r.d_mask);
+    const dim3 grid(res_grid(pn)), block(kSpanThreads);
+    const EncDrop dr = {nullptr, piece_base, e->drop_seed, e->drop_threshold};
+    unsigned long long *raw = e->d_res + 3;
+    ECHK(hipMemsetAsync(raw, 0, (kResWords - 3) * 8, e->stream));
+    auto stage = [&](auto rank, auto dropped) {
+        hipLaunchKernelGGL((k_enc_resident<rank(), dropped()>), grid, block, 0, e->stream, e->tok[0].get(),
+                           dropped() ? e->org[0].get() : nullptr, mask, pn, n_tiles, e->lut, dr, e->tile_cnt.get(), raw);
+    };
+    if (drop) stage(std::true_type(), std::true_type());      // (dropout is rank order: drop_check)
+    else if (e->rank_order) stage(std::true_type(), std::false_type());
+    else stage(std::false_type(), std::false_type());
+    hipLaunchKernelGGL(k_enc_scan_sum, dim3(1), dim3(kScanThreads), 0, e->stream, e->tile_cnt, n_tiles, e->tile_off,
+                       e->d_res);
+    if (drop)
+        hipLaunchKernelGGL(k_enc_tile_gather<true>, grid, block, 0, e->stream, e->tok[0], e->org[0], mask, pn, n_tiles,
+                           e->tile_cnt, e->tile_off, e->tok[1], e->org[1]);
+    else
+        hipLaunchKernelGGL(k_enc_tile_gather<false>, grid, block, 0, e->stream, e->tok[0], nullptr, mask, pn, n_tiles,
+                           e->tile_cnt, e->tile_off, e->tok[1], nullptr);
+    unsigned long long res[kResWords] = {};
+    ECHK(hipMemcpyAsync(res, e->d_res, sizeof(res), hipMemcpyDeviceToHost, e->stream));
+    ECHK(hipStreamSynchronize(e->stream));
+    ECHK(hipGetLastError());
+    *n = res[0];
+    *raw_tiles = res[3];
+    e->res_ran = true;
+    e->res_tiles += n_tiles;
+    e->res_raw += res[3];
+    e->res_tokens += res[0];
+#ifdef MBPE_RESIDENT_ROUNDS
+    e->res_rounds += res[4];
+    e->res_rounds_max = std::max<uint64_t>(e->res_rounds_max, res[5]);
+#endif
+    if (e->pass_tokens.empty()) e->pass_tokens.resize(1, 0);
+    e->pass_tokens[0] += pn;
+    return MBPE_OK;
+}
+
+// ev0, bytes -> tokens, then passes until one changes nothing (option "resident": the stage, then the passes only where
+// a tile was raw).  piece_base = the piece's first byte in the call's text
+int piece_passes(mbpe_encoder *e, uint64_t piece_base, PieceRun *r) {
+    const uint64_t pn = r->pn;
+    const bool drop = e->drop_threshold != 0;
+    ECHK(hipEventRecord(e->ev0, e->stream));
+    const int wblocks = (int)std::min<uint64_t>((pn + 255) / 256, 8192);
+    if (drop)
+        hipLaunchKernelGGL(k_enc_widen<true>, dim3(wblocks), dim3(256), 0, e->stream, r->d_text, pn,
+                           r->d_mask, e->tok[0], e->org[0]);
+    else
+        hipLaunchKernelGGL(k_enc_widen<false>, dim3(wblocks), dim3(256), 0, e->stream, r->d_text, pn,
+                           r->d_mask, e->tok[0], nullptr);
+    if (!e->piece_singles.empty())
+        hipLaunchKernelGGL(k_enc_single, dim3((uint32_t)e->piece_singles.size()), dim3(64), 0, e->stream, e->d_singles,
+                           (uint32_t)e->piece_singles.size(), e->tok[0]);
+    if (!e->resident) return pass_loop(e, piece_base, r, 0, pn, 0);
+    uint64_t n = 0, raw_tiles = 0;
+    if (const int rc = resident_stage(e, piece_base, *r, &n, &raw_tiles)) return rc;
+    if (raw_tiles) return pass_loop(e, piece_base, r, 1, n, 1);
+    r->n = n;
+    r->cur = 1;
+    r->passes = 1;
     return MBPE_OK;
 }
 
@@ -1456,7 +1718,7 @@ int enc_run_body(mbpe_encoder *e, EncCall a) {
     if (int rc0 = boff_begin(e, a)) return rc0;
     if (int rc0 = count_begin(e, a)) return rc0;
     e->last_ms = 0.f;
-    e->pass_tokens.clear();
+    passes_reset(e);
     if (e->dedup) return enc_dedup_body(e, a);
 
     // pieces: whole chunks, at most `limit` bytes each
@@ -1493,7 +1755,7 @@ int enc_run_body(mbpe_encoder *e, EncCall a) {
         rc = run_pieces(e, q, pieces, &sum);
         if (rc != MBPE_OK) return rc;
         if (a.cap < sum.n) return enc_report(a, sum, true);
-        e->pass_tokens.clear();                    // (the kernel time keeps both runs, the pass counts one)
+        passes_reset(e);                    // (the kernel time keeps both runs, the pass counts one)
     }
     rc = run_pieces(e, a, pieces, &sum);
     return rc != MBPE_OK ? rc : enc_report(a, sum, sum.too_small);
@@ -1847,7 +2109,7 @@ int enc_endmask_body(mbpe_encoder *e, EncCall a) {
     if (a.doc_off && a.doc_tok_off_out) a.doc_tok_off_out[0] = 0;
     ECHK(hipSetDevice(e->device));
     e->last_ms = 0.f;
-    e->pass_tokens.clear();
+    passes_reset(e);
     e->dd_ran = false;
     if (int rc0 = boff_begin(e, a)) return rc0;
     if (n_bytes == 0) {
@@ -1985,7 +2247,7 @@ int mbpe_encoder_create(int device_id, const uint32_t *merges, uint32_t n_merges
         int rc = e->open(device_id);
         if (rc == MBPE_OK) rc = e->d_keys.reserve((uint64_t)capacity * 8, e->mem);
         if (rc == MBPE_OK) rc = e->d_vals.reserve((uint64_t)capacity * 4, e->mem);
-        if (rc == MBPE_OK) rc = e->d_res.reserve(24, e->mem);
+        if (rc == MBPE_OK) rc = e->d_res.reserve(kResWords * 8, e->mem);
         if (rc != MBPE_OK) return rc;
         ECHK(hipMemcpyAsync(e->d_keys, keys.data(), (size_t)capacity * 8, hipMemcpyHostToDevice, e->stream));
         ECHK(hipMemcpyAsync(e->d_vals, vals.data(), (size_t)capacity * 4, hipMemcpyHostToDevice, e->stream));
@@ -2021,6 +2283,11 @@ int mbpe_encoder_set_option(mbpe_encoder *e, const char *name, int64_t value) {
     if (strcmp(name, "rank_order") == 0) {
         if (value != 0 && value != 1) return fail(MBPE_ERR_ARG, "rank_order must be 0 or 1");
         e->rank_order = value == 1;
+        return MBPE_OK;
+    }
+    if (strcmp(name, "resident") == 0) {
+        if (value != 0 && value != 1) return fail(MBPE_ERR_ARG, "resident must be 0 or 1");
+        e->resident = value == 1;
         return MBPE_OK;
     }
     if (strcmp(name, "dedup") == 0) {
@@ -2472,6 +2739,26 @@ int mbpe_encoder_pass_tokens(const mbpe_encoder *e, uint64_t *tokens_out, uint32
     for (size_t k = 0; k < e->pass_tokens.size(); ++k) tokens_out[k] = e->pass_tokens[k];
     return MBPE_OK;
 }
+
+int mbpe_encoder_resident_stats(const mbpe_encoder *e, uint64_t *n_tiles_out, uint64_t *n_raw_tiles_out,
+                                uint64_t *n_tokens_after_out) {
+    if (!e) return fail(MBPE_ERR_ARG, "mbpe_encoder_resident_stats: NULL argument");
+    if (!e->res_ran) return fail(MBPE_ERR_STATE, "mbpe_encoder_resident_stats: the latest call did not run the resident stage");
+    if (n_tiles_out) *n_tiles_out = e->res_tiles;
+    if (n_raw_tiles_out) *n_raw_tiles_out = e->res_raw;
+    if (n_tokens_after_out) *n_tokens_after_out = e->res_tokens;
+    return MBPE_OK;
+}
+
+#ifdef MBPE_RESIDENT_ROUNDS
+// the counting build only (-DMBPE_RESIDENT_ROUNDS; profiles/r31_encode_resident.md has the command): the rounds of the latest call's resident tiles, all and the most of one
+MBPE_API int mbpe_encoder_resident_rounds(const mbpe_encoder *e, uint64_t *sum_out, uint64_t *max_out) {
+    if (!e || !sum_out || !max_out || !e->res_ran) return fail(MBPE_ERR_STATE, "mbpe_encoder_resident_rounds: nothing to report");
+    *sum_out = e->res_rounds;
+    *max_out = e->res_rounds_max;
+    return MBPE_OK;
+}
+#endif
 
 int mbpe_encoder_dedup_stats(const mbpe_encoder *e, uint64_t *n_chunks_out, uint64_t *n_unique_out,
                              uint64_t *n_unique_bytes_out, uint64_t *n_unique_tokens_out, float *expand_ms_out) {

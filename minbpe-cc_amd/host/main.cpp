@@ -84,6 +84,9 @@ void usage() {
                  "  --byte-ranges-out TEXT      When encoding, also write one line \"start end\" per token to this file: the bytes\n"
                  "                              of the input the token stands for (a special token: its name's occurrence);\n"
                  "                              on the host, with --device-encode, --device-split and --rank-order alike\n"
+                 "  --resident                  With --encode --device-encode: run the merge rounds of every chunk of at most 256\n"
+                 "                              bytes in one kernel on the chip instead of passes over the whole stream: the\n"
+                 "                              same output, with every other option; meant for --rank-order and --dropout\n"
                  "  --dedup                     With --train: split as asked, then train on the distinct chunks with their counts\n"
                  "                              (deduplicated on the HIP device): the same model.  One pass over the unique\n"
                  "                              chunks per merge: meant for -c first, for vocabularies beyond 65,536 and for\n"
@@ -150,7 +153,7 @@ int main(int argc, char *argv[]) {
     std::vector<std::string> counts_paths;
     std::string conflict_resolution_str = "first";
     bool train = false, decode = false, encode = false, write_vocab = false, verbose = false, device_encode = false,
-         device_decode = false, device_split = false, split_unicode = false, rank_order = false, dedup = false,
+         device_decode = false, device_split = false, split_unicode = false, rank_order = false, dedup = false, resident = false,
          count = false;
     int vocab_size = 512, device = 0;
     long long min_frequency = 0, max_token_length = 0;
@@ -226,6 +229,7 @@ int main(int argc, char *argv[]) {
         else if (arg == "--device-split-unicode") device_split = split_unicode = true;
         else if (arg == "--rank-order") rank_order = true;
         else if (arg == "--dedup") dedup = true;
+        else if (arg == "--resident") resident = true;
         else if (arg == "--count") count = true;
         else if (arg == "-v" || arg == "--verbose") verbose = true;
         else { std::cerr << "The following argument was not expected: " << arg << "\n"; return 109; }
@@ -240,6 +244,7 @@ int main(int argc, char *argv[]) {
         if (!rank_order) { std::cerr << "--dropout requires --rank-order\n"; return 107; }
     }
 
+    if (resident && !(encode && device_encode)) { std::cerr << "--resident requires --encode --device-encode\n"; return 107; }
     if (have_limits && !train) { std::cerr << "--min-frequency and --max-token-length require --train\n"; return 107; }
 
     if (!token_counts_path.empty() && (!encode || train || decode)) { std::cerr << "--token-counts-out requires --encode\n"; return 107; }
@@ -449,6 +454,7 @@ int main(int argc, char *argv[]) {
         if (have_dropout) mbpe_tok_set_encode_dropout(rt, drop_threshold, seed);
         if (split_unicode) mbpe_tok_set_split_unicode(rt, 1);
         if (dedup && device_encode) mbpe_tok_set_encode_dedup(rt, 1);
+        if (resident) mbpe_tok_set_encode_resident(rt, 1);
         if (pieces.empty()) pieces.push_back(Piece{input_path, 1});
         uint64_t total = 0;
         for (size_t k = 0; k < pieces.size() && rc == 0; ++k) {
@@ -499,6 +505,7 @@ int main(int argc, char *argv[]) {
             if (have_dropout) mbpe_tok_set_encode_dropout(rt, drop_threshold, seed);
             if (split_unicode) mbpe_tok_set_split_unicode(rt, 1);
             if (dedup && device_encode) mbpe_tok_set_encode_dedup(rt, 1);
+            if (resident) mbpe_tok_set_encode_resident(rt, 1);
             std::vector<uint64_t> ranges(byte_ranges_path.empty() ? 0 : 2 * encoded.size());
             const int erc = !byte_ranges_path.empty()
                                 ? mbpe_tok_encode_byteoff(rt, in, input.size(), verbose, device_encode ? device : -1,

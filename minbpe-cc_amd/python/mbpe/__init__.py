@@ -43,7 +43,7 @@ EXPORTS = [
     "mbpe_dedup_create", "mbpe_dedup_destroy", "mbpe_dedup_chunks_endmask", "mbpe_dedup_chunks", "mbpe_dedup_result",
     "mbpe_dedup_get", "mbpe_dedup_set_option", "mbpe_dedup_kernel_ms", "mbpe_dedup_alloc_count",
     "mbpe_load_corpus_weighted", "mbpe_load_corpus_endmask_weighted",
-    "mbpe_dedup_map", "mbpe_dedup_get_map", "mbpe_encoder_dedup_stats",
+    "mbpe_dedup_map", "mbpe_dedup_get_map", "mbpe_encoder_dedup_stats", "mbpe_encoder_resident_stats",
     "mbpe_wordcount_create", "mbpe_wordcount_destroy", "mbpe_wordcount_add_endmask", "mbpe_wordcount_add",
     "mbpe_wordcount_result", "mbpe_wordcount_get", "mbpe_wordcount_stats", "mbpe_wordcount_reset",
     "mbpe_wordcount_set_option", "mbpe_wordcount_kernel_ms", "mbpe_wordcount_alloc_count",
@@ -68,7 +68,8 @@ TOK_EXPORTS = [
     "mbpe_tok_train_split_device", "mbpe_tok_set_encode_split", "mbpe_tok_set_split_unicode",
     "mbpe_tok_set_encode_order", "mbpe_tok_train_continue", "mbpe_tok_encode_byteoff",
     "mbpe_tok_encode_batch_byteoff_device", "mbpe_tok_set_encode_dropout", "mbpe_tok_set_train_dedup",
-    "mbpe_tok_set_encode_dedup", "mbpe_tok_train_pieces_begin", "mbpe_tok_train_pieces_add",
+    "mbpe_tok_set_encode_dedup", "mbpe_tok_set_encode_resident",
+    "mbpe_tok_train_pieces_begin", "mbpe_tok_train_pieces_add",
     "mbpe_tok_train_pieces_finish", "mbpe_tok_train_pieces_abort", "mbpe_tok_set_train_limits",
     "mbpe_tok_train_pieces_export_size", "mbpe_tok_train_pieces_export", "mbpe_tok_train_pieces_merge",
     "mbpe_tok_encode_batch_windows_device", "mbpe_tok_count_tokens", "mbpe_tok_token_counts",
@@ -344,6 +345,8 @@ def lib():
     L.mbpe_dedup_get_map.argtypes = [vp, vp, u64, vp]
     L.mbpe_encoder_dedup_stats.argtypes = [vp, vp, vp, vp, vp, vp]
     L.mbpe_tok_set_encode_dedup.argtypes = [vp, i32]
+    L.mbpe_encoder_resident_stats.argtypes = [vp, vp, vp, vp]
+    L.mbpe_tok_set_encode_resident.argtypes = [vp, i32]
     L.mbpe_wordcount_create.argtypes = [i32, ctypes.POINTER(vp)]
     L.mbpe_wordcount_destroy.argtypes = [vp]
     L.mbpe_wordcount_destroy.restype = None
@@ -1209,7 +1212,8 @@ class Encoder:
     """One mbpe_encoder: internal_encode (Tokenizer.h:325-377) on a HIP device with the lookup table, the stream and
     the work buffers kept between calls."""
 
-    def __init__(self, merges, device=0, rank_order=False, dropout=0.0, seed=0, dedup=False, count_ids=None):
+    def __init__(self, merges, device=0, rank_order=False, dropout=0.0, seed=0, dedup=False, count_ids=None,
+                 resident=False):
         """count_ids: the option "count_ids" from the start: the table of count() has max(256 + n_merges, count_ids) bins.
         rank_order: the option "rank_order" from the start (set_option changes it between calls).
         dropout, seed: BPE-dropout from the start (set_dropout changes it between calls); needs rank_order.
@@ -1226,6 +1230,8 @@ class Encoder:
             self.set_dropout(dropout, seed)
         if dedup:
             self.set_option("dedup", 1)
+        if resident:
+            self.set_option("resident", 1)
         if count_ids is not None:
             self.set_option("count_ids", count_ids)
 
@@ -1720,6 +1726,14 @@ class Encoder:
         n = ctypes.c_uint64()
         _check(lib().mbpe_encoder_alloc_count(self._h, ctypes.byref(n)))
         return n.value
+
+    def resident_stats(self):
+        """The latest call with the option "resident" (mbpe_encoder_resident_stats) -> dict: tiles, raw_tiles (those at
+        or inside a chunk longer than the search bound, which the passes finish), tokens_after_stage.
+        MbpeError(ERR_STATE) when that call did not run the stage."""
+        v = [ctypes.c_uint64() for _ in range(3)]
+        _check(lib().mbpe_encoder_resident_stats(self._h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("tiles", "raw_tiles", "tokens_after_stage"), (int(x.value) for x in v)))
 
     def dedup_stats(self):
         """The latest call on the "dedup" route (mbpe_encoder_dedup_stats) -> dict: n_chunks (those the deduper kept),
@@ -2610,10 +2624,12 @@ class Tokenizer:
     def load(self, path, verbose=False):
         _check(lib().mbpe_tok_load(self._h, os.fsencode(path), int(verbose)))
 
-    def _encode_split(self, device_split, order="greedy", dropout=0.0, seed=0, dedup=False, fim=None, mlm=None):
+    def _encode_split(self, device_split, order="greedy", dropout=0.0, seed=0, dedup=False, fim=None, mlm=None,
+                      resident=False):
         if order not in ("greedy", "rank"):
             raise ValueError('order must be "greedy" or "rank"')
         _check(lib().mbpe_tok_set_encode_dedup(self._h, int(bool(dedup))))
+        _check(lib().mbpe_tok_set_encode_resident(self._h, int(bool(resident))))
         _check(lib().mbpe_tok_set_encode_order(self._h, int(order == "rank")))
         _check(lib().mbpe_tok_set_encode_dropout(self._h, dropout_threshold(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF))
         _check(lib().mbpe_tok_set_encode_split(self._h, int(bool(device_split))))
@@ -2627,7 +2643,7 @@ class Tokenizer:
         return _fim_info(lib().mbpe_tok_encode_fim_info, self._h)
 
     def encode(self, data, device=None, device_split=False, order="greedy", byte_ranges=False, dropout=0.0, seed=0,
-               dedup=False):
+               dedup=False, resident=False):
         """device None: internal_encode on the host; an int: on that HIP device (mbpe_tok_encode_device).
         device_split (here and in the batch calls; only with a device): the text is cut at the special tokens and split
         into chunks on the device too (mbpe_tok_set_encode_split); same tokens, gpt2 / gpt4 patterns only.  "unicode"
@@ -2644,8 +2660,11 @@ class Tokenizer:
         data[ranges[j, 0]:ranges[j, 1]] (a special token: the occurrence of its name).
         dedup=True (here and in the batch calls; only with a device; mbpe_tok_set_encode_dedup): the chunks are
         deduplicated on the device, the distinct ones encoded once and their tokens copied to every occurrence; same
-        tokens.  With byte_ranges or dropout > 0 the library's error is raised."""
-        self._encode_split(device_split, order, dropout, seed, dedup)
+        tokens.  With byte_ranges or dropout > 0 the library's error is raised.
+        resident=True (here and in the batch calls; only with a device; mbpe_tok_set_encode_resident): the merge rounds
+        of every chunk of at most 256 bytes run in one kernel on the chip (the encoder's option "resident"); same
+        tokens, with every other argument as it is."""
+        self._encode_split(device_split, order, dropout, seed, dedup, resident=resident)
         text = _u8(data)
         n = ctypes.c_uint64()
         out = np.zeros(max(len(text), 1), dtype=np.uint32)
@@ -2664,11 +2683,11 @@ class Tokenizer:
         return out[:n.value].copy()
 
     def encode_batch(self, texts, device=0, device_split=False, order="greedy", byte_ranges=False, dropout=0.0,
-                     seed=0, dedup=False):
+                     seed=0, dedup=False, resident=False):
         """encode() of every text in one device call (mbpe_tok_encode_batch_device) -> list of uint32 arrays; with
         byte_ranges=True (mbpe_tok_encode_batch_byteoff_device) a list of (tokens, ranges[n, 2] uint64) pairs, the
         ranges relative to each text's first byte.  With dropout, positions run over the texts laid end to end."""
-        self._encode_split(device_split, order, dropout, seed, dedup)
+        self._encode_split(device_split, order, dropout, seed, dedup, resident=resident)
         parts = [bytes(_u8(t)) for t in texts]
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
         if parts:
@@ -2689,14 +2708,14 @@ class Tokenizer:
                                                   ctypes.byref(n)))
         return [out[int(a):int(b)].copy() for a, b in zip(tok_off[:-1], tok_off[1:])]
 
-    def token_counts(self, texts, device=0, device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False,
+    def token_counts(self, texts, device=0, device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False, resident=False,
                      repeats=None, batch_bytes=1 << 28):
         """How often every token id is used on `texts` (any iterable of texts) -> uint64[n_ids], n_ids = max(256 +
         merges, largest special id + 1): the bincount of encode() of every text, text i counted repeats[i] times
         (mbpe_tok_count_tokens).  With a device no token leaves it: the texts go there in batches of whole texts of at
         most batch_bytes (a longer text is a batch of its own), and only the table comes back.  device=None is the host
-        loop.  device_split, order, dropout, seed and dedup as for encode_batch.  The table is reset first."""
-        self._encode_split(device_split, order, dropout, seed, dedup)
+        loop.  device_split, order, dropout, seed, dedup and resident as for encode_batch.  The table is reset first."""
+        self._encode_split(device_split, order, dropout, seed, dedup, resident=resident)
         _check(lib().mbpe_tok_token_counts_reset(self._h))
         dev = -1 if device is None else device
 
@@ -2728,7 +2747,7 @@ class Tokenizer:
 
     def encode_batch_padded(self, texts, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
                             pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
-                            device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False, fim=None):
+                            device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False, resident=False, fim=None):
         """Every text split like encode(), encoded and packed in one device call
         (mbpe_tok_encode_batch_packed_device) -> (ids [n_rows, seq_len], lengths [n_rows]) as numpy arrays; with
         out_ptr= and len_ptr= (device memory for cap_rows rows) the matrix stays on the device and the row count is
@@ -2737,7 +2756,7 @@ class Tokenizer:
         tokens go through the fill-in-the-middle transform on the device before they are packed; its sentinel ids may
         be special-token ids; fim_info() tells what was done to each text.  With "padded" rows and truncation a
         transformed text that does not fit loses its middle: use max_tokens, windows, "packed" or fit there."""
-        self._encode_split(device_split, order, dropout, seed, dedup, fim)
+        self._encode_split(device_split, order, dropout, seed, dedup, fim, resident=resident)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         parts = [bytes(_u8(t)) for t in texts]
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
@@ -2762,7 +2781,7 @@ class Tokenizer:
 
     def encode_batch_denoise(self, texts, enc_len, dec_len, denoise, device=0, out_bits=32, pad_id=0, eos_id=None,
                              decoder_start_id=None, ignore_label=-100, labels=True, row_doc=True, ptrs=None,
-                             cap_rows=None, device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False):
+                             cap_rows=None, device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False, resident=False):
         """Every text split like encode(), encoded, span-corrupted (T5 / UL2; denoise: a DenoiseSpec from
         denoise_spec()) and packed into the two matrices of an encoder-decoder batch in one device call
         (mbpe_tok_encode_batch_denoise_device) -> the dict of Encoder.encode_batch_denoise, as numpy arrays or -- ptrs=,
@@ -2770,7 +2789,7 @@ class Tokenizer:
         also where cap_rows is too small).  One row per unit: with denoise.segment_tokens a long text becomes several
         rows and "row_doc" says whose.  eos_id, decoder_start_id and the sentinels may be special-token ids.  The
         tokens encoded: self.n_tokens."""
-        self._encode_split(device_split, order, dropout, seed, dedup)
+        self._encode_split(device_split, order, dropout, seed, dedup, resident=resident)
         es, ds = _denoise_specs(enc_len, dec_len, out_bits, pad_id, eos_id, decoder_start_id)
         parts = [bytes(_u8(t)) for t in texts]
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
@@ -2796,7 +2815,7 @@ class Tokenizer:
                          pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
                          labels=False, positions=False, segments=False, cu_seqlens=False, ignore_label=-100,
                          labels_ptr=None, pos_ptr=None, seg_ptr=None, device_split=False, order="greedy", dropout=0.0,
-                         seed=0, dedup=False, fim=None, mlm=None):
+                         seed=0, dedup=False, resident=False, fim=None, mlm=None):
         """encode_batch_padded plus labels, positions, segments and cu_seqlens (mbpe_tok_encode_batch_aux_device): its
         arguments and those of pack_tokens_aux, whose dict (or, with out_ptr=, row count) is returned.  The documents'
         token offsets of the call (with fim: after the transform): self.doc_tok_off.
@@ -2804,7 +2823,7 @@ class Tokenizer:
         through masked-LM corruption on the device before they are packed: "ids" are the corrupted ids, "labels" the
         targets (ignore_label in every other cell).  whole_word masks the chunks of the split pattern as wholes and
         needs out_bits 32 or 64.  Not together with fim."""
-        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm)
+        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm, resident=resident)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label)
         parts = [bytes(_u8(t)) for t in texts]
@@ -2840,13 +2859,13 @@ class Tokenizer:
                              eos_id=None, device=0, out_ptr=None, len_ptr=None, cap_rows=None, labels=False,
                              positions=False, segments=False, ignore_label=-100, labels_ptr=None, pos_ptr=None,
                              seg_ptr=None, row_doc=False, row_tok0=False, row_doc_ptr=None, row_tok0_ptr=None,
-                             device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False, fim=None,
+                             device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False, resident=False, fim=None,
                              mlm=None):
         """encode_batch_aux for the window layout (mbpe_tok_encode_batch_windows_device): every text split like
         encode(), encoded, and cut into rows of seq_len that share `stride` tokens where a text does not fit one --
         the keywords and the result of pack_windows ("row_doc" maps a row back to its text).  The texts' token
         offsets of the call: self.doc_tok_off."""
-        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm)
+        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm, resident=resident)
         spec = pack_spec(seq_len, "padded", out_bits, pad_id, bos_id, eos_id)
         call = _WinCall(spec, stride, score_once, labels, positions, segments, ignore_label, row_doc, row_tok0)
         parts = [bytes(_u8(t)) for t in texts]
@@ -2869,12 +2888,12 @@ class Tokenizer:
                          len_ptr=None, cap_rows=None, labels=False, positions=False, segments=False, cu_seqlens=False,
                          ignore_label=-100, labels_ptr=None, pos_ptr=None, seg_ptr=None, doc_row=False, doc_col=False,
                          doc_row_ptr=None, doc_col_ptr=None, device_split=False, order="greedy", dropout=0.0, seed=0,
-                         dedup=False, fim=None, mlm=None):
+                         dedup=False, resident=False, fim=None, mlm=None):
         """encode_batch_aux for the fit layout (mbpe_tok_encode_batch_fit_device): every text split like encode(),
         encoded, and packed whole into rows of seq_len by best fit; only a text longer than a row is cut -- the
         keywords and the result of pack_fit ("doc_row" / "doc_col" say where a text's last piece begins, "segments"
         holds the text's number + 1 in every cell).  The texts' token offsets of the call: self.doc_tok_off."""
-        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm)
+        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm, resident=resident)
         spec = _fit_spec(seq_len, out_bits, pad_id, bos_id, eos_id)
         call = _FitCall(spec, labels, positions, segments, cu_seqlens, ignore_label, doc_row, doc_col)
         parts = [bytes(_u8(t)) for t in texts]

@@ -21,6 +21,9 @@ time limit; when one fails, nothing after it is started.
   batch     Tokenizer.encode_batch of shakespeare cut into its lines against a Python loop of
             Tokenizer.encode(line, device=0) on the same build.
 
+  resident  (only with --step resident --text ...: not part of the sequence above) the option "resident" off and on,
+            alternately, on one text in both orders and with dropout -- see step_resident.
+
     python tools/encode_time.py --parent-root <checkout of the parent commit> --json profiles/r07_encode.json
 """
 import argparse
@@ -204,7 +207,81 @@ def step_batch(args):
                       "python_loop_device_s": loop_s, "python_loop_host_s": host_s}))
 
 
-STEPS = {"kernel": step_kernel, "splitmix": step_splitmix, "wall": step_wall, "batch": step_batch}
+def step_resident(args):
+    """Kernel time of Encoder.encode_endmask (text, mask and output on the device) with the option "resident" off and
+    on, alternately, --rounds times --reps calls each, for greedy order, rank order and rank order with p = 0.1, on one
+    text: shakespeare x 1024 or taylorswift with their gpt4 models, or 1 GiB of SplitMix64 bytes cut every 8 bytes.  The
+    two outputs are compared on the device.  --root: a checkout of the parent commit with its libmbpe.so built is timed
+    with the option off alone (it has none)."""
+    use_tree(args.root)
+    import numpy as np
+    import torch
+    import mbpe
+    import oracle as O
+    dev = torch.device("cuda", 0)
+    golden = os.path.join(ROOT, "tests", "golden")
+    if args.text == "random":
+        n = 1 << 30
+        text = torch.from_numpy(O.splitmix64_bytes(42, n)).to(dev)
+        ends = torch.arange(7, n, 8, device=dev)
+        merges = O.parse_model(open(MODEL, "rb").read())[2]
+    else:
+        name, rep = ("shakespeare", 1024) if args.text == "shakespeare" else ("taylorswift", 1)
+        raw = open(os.path.join(golden, "data", name + ".txt"), "rb").read()
+        merges = O.parse_model(open(os.path.join(golden, name + "_gpt4_lexical_512.model"), "rb").read())[2]
+        one = mbpe.presplit(O.GPT4_SPLIT_PATTERN, raw)
+        text = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(dev).repeat(rep)
+        n = text.numel()
+        ends = torch.from_numpy(tiled(one, len(raw), rep)[1:].astype(np.int64)).to(dev) - 1
+    bits = torch.zeros(mbpe.Splitter.mask_bytes(n) * 8, dtype=torch.uint8, device=dev)
+    bits[ends] = 1
+    weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.int32, device=dev)
+    mask = (bits.view(-1, 8).to(torch.int32) * weights).sum(1).to(torch.uint8)
+    n_chunks = int(ends.numel())
+    del bits, ends
+    torch.cuda.synchronize()                                     # (the encoder has a stream of its own)
+    out = [torch.zeros(n + 1, dtype=torch.int32, device=dev) for _ in range(2)]
+    rows = []
+    with mbpe.Encoder(merges) as enc:
+        has_option = hasattr(mbpe.lib(), "mbpe_encoder_resident_stats")
+        for mode, rank, p in (("greedy", 0, 0.0), ("rank", 1, 0.0), ("rank_p0.1", 1, 0.1)):
+            enc.set_option("rank_order", rank)
+            enc.set_dropout(p, 7)
+            ms = {0: [], 1: []}
+            info = {}
+            for rnd in range(args.rounds + 1):                   # round 0 warms both up
+                for on in ((0, 1) if has_option else (0,)):
+                    if has_option:
+                        enc.set_option("resident", on)
+                    for _ in range(args.reps if rnd else 1):
+                        n_out, _ = enc.encode_endmask(text.data_ptr(), n, mask.data_ptr(), out_ptr=out[on].data_ptr(), cap=n)
+                        if rnd:
+                            ms[on].append(enc.kernel_ms())
+                    info[on] = {"tokens": n_out, "passes": enc.n_passes, "pass_tokens": enc.pass_tokens()}
+                    if on:
+                        info[on]["stats"] = enc.resident_stats()
+                        if hasattr(mbpe.lib(), "mbpe_encoder_resident_rounds"):
+                            import ctypes
+                            a, b = ctypes.c_uint64(), ctypes.c_uint64()
+                            mbpe.lib().mbpe_encoder_resident_rounds(enc._h, ctypes.byref(a), ctypes.byref(b))
+                            info[on]["rounds_sum"], info[on]["rounds_max"] = a.value, b.value
+            row = {"text": args.text, "mode": mode, "text_bytes": n, "chunks": n_chunks, "off": info[0]}
+            for on in ms:
+                if ms[on]:
+                    row["ms_on" if on else "ms_off"] = {"median": statistics.median(ms[on]), "min": min(ms[on]),
+                                                         "max": max(ms[on]), "n": len(ms[on]), "all": ms[on]}
+            if has_option:
+                row["on"] = info[1]
+                row["same_tokens"] = info[0]["tokens"] == info[1]["tokens"] and bool(torch.equal(out[0][:n_out], out[1][:n_out]))
+                row["gain"] = row["ms_off"]["median"] / row["ms_on"]["median"]
+                row["gain_beyond_spread"] = row["ms_off"]["median"] - row["ms_on"]["median"] > \
+                    row["ms_off"]["max"] - row["ms_off"]["min"]
+            rows.append(row)
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "lib": mbpe.LIB_PATH and os.path.relpath(mbpe.LIB_PATH, ROOT),
+                      "rows": rows}))
+
+
+STEPS = {"resident": step_resident, "kernel": step_kernel, "splitmix": step_splitmix, "wall": step_wall, "batch": step_batch}
 
 
 def child(step, limit, extra, log):
@@ -232,6 +309,8 @@ def main():
     ap.add_argument("--root", default=ROOT)
     ap.add_argument("--api", choices=("encoder", "oneshot"), default="encoder")
     ap.add_argument("--skip", default="", help="comma-separated steps to leave out")
+    ap.add_argument("--text", choices=("shakespeare", "taylorswift", "random"), default="shakespeare",
+                    help="--step resident: the text to time the option \"resident\" on")
     ap.add_argument("--rank-order", action="store_true",
                     help="kernel and splitmix steps: time every case in rank order too (option \"rank_order\")")
     args = ap.parse_args()
