@@ -462,8 +462,36 @@ MBPE_API int mbpe_compact(mbpe_ctx *ctx);
  *                   makes one pass over the loaded corpus per merge: load the distinct chunks with their counts
  *                   (mbpe_dedup_*, mbpe_load_corpus_*_weighted), or it is correct and slow.  The route is never
  *                   switched beyond this.  Device memory beside the loop's: 4 B per token id for the lengths.
+ *   "resident"      0 (default) | 1; any other value is MBPE_ERR_ARG.  A speed option of the 32-bit loop (csrc/wide.h),
+ *                   which every training on chunk weights, from word counts, with the `first` tie-break beyond the slot
+ *                   format, beyond 65,534 ids or resumed there ends on: with 1, a group of merges over a SHORT stream
+ *                   runs in one launch of one workgroup (csrc/wide_resident.h) instead of seven to ten launches per
+ *                   merge.  Never changes a merge, a count, the stream or the pair table.  With 0 nothing is allocated
+ *                   or launched differently.  Read by every mbpe_train_steps; a group runs resident when the training
+ *                   has no stopping rule ("min_frequency", "max_token_length": those keep the launches), the stream
+ *                   holds at most "resident_max_tokens" tokens at that moment -- a training handed over from the slot
+ *                   stream or continued from prior merges becomes resident once it is that short --, the pair table has
+ *                   at most 2^21 slots (every launch scans it once, and the table is never erased: a short stream may
+ *                   come with a huge one) and no chunk is longer than 65,536 tokens (found by the first launch, which
+ *                   then does nothing).  A short training pays most for that scan: early merges leave room for groups
+ *                   of 16 only.  One rank.
+ *   "resident_max_tokens"
+ *                   0 .. 1,048,576 (beyond: MBPE_ERR_ARG): the longest stream "resident" takes on.  One workgroup walks
+ *                   it per merge, so beyond some length the launches over the whole chip win again; the default is
+ *                   where that was measured (profiles/r32_train_resident.md), 0 = never.
  */
 MBPE_API int mbpe_set_option(mbpe_ctx *ctx, const char *name, int64_t value);
+
+/* What "resident" did in the training under way or just finished: the merges made by its launches (the zero-count tail of
+ * a lexical training that ended in them included), those launches, and the slices of the pair table their argmax
+ * rescanned (a full scan per merge would be launches' worth of 64 .. 2,048 each).  All zero: nothing ran resident.  Any
+ * out pointer may be NULL. */
+MBPE_API int mbpe_train_resident_stats(mbpe_ctx *ctx, uint64_t *n_merges_resident_out, uint64_t *n_launches_out,
+                                       uint64_t *n_slices_rescanned_out);
+/* DIAGNOSTICS, for tools/train_resident_time.py; not part of the training interface and free to change.  Where the
+ * kernel spent its time, in wall-clock ticks of 10 ns summed over the launches: the argmax, the `first` position
+ * search, the walks over the stream.  Thread 0 reads the clock at the three phase boundaries of every merge. */
+MBPE_API int mbpe_train_resident_ticks(mbpe_ctx *ctx, uint64_t *argmax_out, uint64_t *first_out, uint64_t *walk_out);
 
 /* ---- encode on the device ----------------------------------------------- */
 

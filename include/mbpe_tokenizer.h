@@ -297,6 +297,15 @@ MBPE_API int mbpe_tok_set_train_dedup(mbpe_tokenizer *t, int on);
  * MBPE_ERR_OOM, as for mbpe_tok_train_continue. */
 MBPE_API int mbpe_tok_set_train_limits(mbpe_tokenizer *t, int64_t min_frequency, int64_t max_token_length);
 
+/* The trainings from here on (the calls above) set the training context's option "resident" (mbpe.h) to `on`: 0 (the
+ * default) or 1; anything else is MBPE_ERR_ARG.  Where a training runs the 32-bit loop on a short stream -- with
+ * mbpe_tok_set_train_dedup, from word counts, with the `first` tie-break or continued -- a group of merges is then one
+ * kernel launch -- for streams of at most "resident_max_tokens" tokens.  That bound's default is 0 and the tokenizer
+ * does not set it, so TODAY THIS SWITCH CHANGES NOTHING: it is kept for the day the default is raised
+ * (profiles/r32_train_resident.md); a caller who wants the kernel uses the training context with the bound set.  Same
+ * merges, counts, .model and .vocab.  With stopping rules set the loop keeps its launches. */
+MBPE_API int mbpe_tok_set_train_resident(mbpe_tokenizer *t, int on);
+
 /* Encoding through the distinct chunks: 0 (the default) or 1; anything else is MBPE_ERR_ARG.  While it is on,
  * mbpe_tok_encode_device and the three batch calls (mbpe_tok_encode_batch_device, _batch_packed_device,
  * _batch_aux_device) run the kept device encoder with its option "dedup" (mbpe.h: the chunks are deduplicated on the

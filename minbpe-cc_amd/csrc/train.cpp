@@ -241,6 +241,8 @@ struct mbpe_ctx {
     int64_t opt_resume_wide = 0;     // 1: mbpe_train_begin_from may continue on 32-bit tokens (0: MBPE_ERR_VOCAB, as before)
     int64_t opt_min_frequency = 0;   // stopping rules (wide.h), read by the next begin: either non-zero and the training runs
     int64_t opt_max_token_length = 0;   // on 32-bit tokens from its first new merge, like one on a weighted corpus
+    int64_t opt_resident = 0;        // 1: the 32-bit loop runs short streams in one workgroup (wide_resident.h)
+    int64_t opt_resident_max = kResidentMaxDefault;   // ... "resident_max_tokens": what a short stream is
     bool wide_direct = false;        // the training began on 32-bit tokens (begin_wide_direct): no slot stream, no best[]
     std::vector<uint32_t> h_prior_raw;   // ... and its prior merges, (a, b) as given: their ids may need more than 16 bits
 
@@ -251,7 +253,9 @@ struct mbpe_ctx {
 namespace {
 
 // what the 32-bit loop's calls get of the context
-WideDev wide_dev(mbpe_ctx *c) { return WideDev{c->stream, c->ev0, c->ev1, c->pool, c->n_cus, c->stats}; }
+WideDev wide_dev(mbpe_ctx *c) {
+    return WideDev{c->stream, c->ev0, c->ev1, c->pool, c->n_cus, c->stats, c->opt_resident != 0, (uint64_t)c->opt_resident_max};
+}
 
 int sync_ctl(mbpe_ctx *c) {
     HIPCHK(hipMemcpyAsync(&c->h_ctl, c->ctl, sizeof(DevCtl), hipMemcpyDeviceToHost, c->stream));
@@ -591,6 +595,17 @@ int mbpe_set_option(mbpe_ctx *c, const char *name, int64_t value) {
             return MBPE_ERR_ARG;
         }
         c->opt_max_token_length = value;
+    }
+    else if (n == "resident") {                                                // (read by every mbpe_train_steps)
+        if (value != 0 && value != 1) { mbpe_host::set_last_error("resident: 0 or 1"); return MBPE_ERR_ARG; }
+        c->opt_resident = value;
+    }
+    else if (n == "resident_max_tokens") {                                     // (likewise)
+        if (value < 0 || value > (int64_t)kResMaxTokens) {
+            mbpe_host::set_last_error("resident_max_tokens: 0 .. " + std::to_string(kResMaxTokens));
+            return MBPE_ERR_ARG;
+        }
+        c->opt_resident_max = value;
     }
     else if (n == "pc_repeat") c->opt_pc_repeat = std::min<int64_t>(std::max<int64_t>(1, value), 1000);
     else { mbpe_host::set_last_error("unknown option " + n); return MBPE_ERR_ARG; }
@@ -2070,6 +2085,25 @@ int mbpe_get_stats(mbpe_ctx *c, mbpe_stats *out) {
     c->stats.n_skip_cut = c->begun ? c->h_ctl.n_skip_cut : 0;
     if (c->begun && c->wr.active) c->wr.add_stats(&c->stats);
     *out = c->stats;
+    return MBPE_OK;
+}
+
+// what the option "resident" did in the training under way or just finished (zeros: nothing ran resident)
+int mbpe_train_resident_stats(mbpe_ctx *c, uint64_t *n_merges_resident_out, uint64_t *n_launches_out,
+                              uint64_t *n_slices_rescanned_out) {
+    if (!c) return MBPE_ERR_ARG;
+    if (n_merges_resident_out) *n_merges_resident_out = c->wr.res_merges;
+    if (n_launches_out) *n_launches_out = c->wr.res_launches;
+    if (n_slices_rescanned_out) *n_slices_rescanned_out = c->wr.h_res.n_rescanned;
+    return MBPE_OK;
+}
+
+// ... and where its kernel spent its time: wall-clock ticks of 10 ns in the argmax, the `first` search and the walks
+int mbpe_train_resident_ticks(mbpe_ctx *c, uint64_t *argmax_out, uint64_t *first_out, uint64_t *walk_out) {
+    if (!c || !argmax_out || !first_out || !walk_out) return MBPE_ERR_ARG;
+    *argmax_out = c->wr.h_res.t_argmax;
+    *first_out = c->wr.h_res.t_first;
+    *walk_out = c->wr.h_res.t_walk;
     return MBPE_OK;
 }
 

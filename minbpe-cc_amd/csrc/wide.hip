@@ -1,5 +1,6 @@
 // Kernels of the 32-bit continuation of a training: see wide.h.  gfx950, wave64.
 #include "wide.h"
+#include "wide_dev.h"
 
 #include <hip/hip_runtime.h>
 
@@ -7,28 +8,6 @@
 
 namespace mbpe {
 namespace {
-
-// create_or_modify_pair, PairCount.h:249-260: find the pair and add `delta`, or insert it with `delta`.  Entries are
-// never removed.  Concurrent inserts of one key meet at the same free slot and the CAS lets exactly one of them in.
-__device__ void wide_add(const WideTable &t, WideCtl *ctl, unsigned long long key, int32_t delta) {
-    uint32_t h = pair_hash(key, t.shift);
-    for (uint32_t probe = 0; probe <= t.mask; ++probe) {
-        unsigned long long k = t.keys[h];
-        if (k == kWideEmpty) {
-            k = atomicCAS(&t.keys[h], kWideEmpty, key);
-            if (k == kWideEmpty) {
-                atomicAdd(&ctl->n_entries, 1u);
-                k = key;
-            }
-        }
-        if (k == key) {
-            atomicAdd(&t.cnts[h], delta);
-            return;
-        }
-        h = (h + 1) & t.mask;
-    }
-    atomicOr(&ctl->err, 1u);
-}
 
 __global__ void k_wide_table_clear(WideTable t) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -197,33 +176,7 @@ __global__ void k_wide_resume_check(const WideTally *tally, WideCtl *ctl) {
     if (tally->total != tally->positions || tally->top >= 0x80000000u) atomicOr(&ctl->err, kWideErrCount);
 }
 
-// ---- argmax: (count desc, first asc, second asc) = the larger of (count, ~key) -------------------------------
-struct Cand128 { long long count; unsigned long long nkey; };      // count = -1: nothing
-__device__ __forceinline__ bool better(const Cand128 &a, const Cand128 &b) {
-    return a.count > b.count || (a.count == b.count && a.nkey > b.nkey);
-}
-__device__ __forceinline__ Cand128 wave_best(Cand128 v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        Cand128 o;
-        o.count = ((long long)__shfl_xor((int)(v.count >> 32), d, kWave) << 32) | (uint32_t)__shfl_xor((int)v.count, d, kWave);
-        o.nkey = ((unsigned long long)(uint32_t)__shfl_xor((int)(v.nkey >> 32), d, kWave) << 32) |
-                 (uint32_t)__shfl_xor((int)v.nkey, d, kWave);
-        if (better(o, v)) v = o;
-    }
-    return v;
-}
-__device__ Cand128 block_best(Cand128 v, Cand128 *sh) {
-    v = wave_best(v);
-    __syncthreads();
-    if (lane_id() == 0) sh[threadIdx.x / kWave] = v;
-    __syncthreads();
-    Cand128 r = sh[0];
-    for (uint32_t w = 1; w < blockDim.x / kWave; ++w)
-        if (better(sh[w], r)) r = sh[w];
-    return r;
-}
-
+// ---- argmax: the order and its reductions are in wide_dev.h --------------------------------------------------------
 // ---- stopping rules (wide.h): which pairs the argmax may choose ------------------------------------------------------
 // len[a] + len[b] <= max_len; the entries saturate at kWideLenMax, so the sum does not wrap.  Every id of a key in the
 // table or of a token in the stream lies below the training's vocab_size, which is how many entries len[] has.
@@ -289,21 +242,7 @@ __global__ __launch_bounds__(kArgBlocks) void k_wide_argmax_final(const unsigned
     }
 }
 
-// ---- `first` tie-break (see wide.h) ----------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t first_bit(unsigned long long key) { return pair_hash(key, 48); }   // 16 bits
-
-// count of `key`, or -1 when the pair was never inserted
-__device__ __forceinline__ int32_t wide_lookup(const WideTable &t, unsigned long long key) {
-    uint32_t h = pair_hash(key, t.shift);
-    for (uint32_t probe = 0; probe <= t.mask; ++probe) {
-        const unsigned long long k = t.keys[h];
-        if (k == key) return t.cnts[h];
-        if (k == kWideEmpty) return -1;
-        h = (h + 1) & t.mask;
-    }
-    return -1;
-}
-
+// ---- `first` tie-break (see wide.h; first_bit and wide_lookup are in wide_dev.h) -------------------------------------
 // the grid and stride of k_wide_argmax_partial: block b walks the slice whose maximum is part[2 b].
 // LIM: n_tie and the bitmap hold eligible pairs only (part[] is the eligible maximum already)
 template <bool LIM>
@@ -468,11 +407,7 @@ __global__ __launch_bounds__(kSpanThreads) void k_wide_from_slots(const uint16_t
     if (lane == 0) span_keep[span] = kept;
 }
 
-// ---- one merge ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool is_cand(uint32_t t, uint32_t nx, uint32_t a, uint32_t b) {
-    return !(t & kTokEnd) && t == a && (nx & kTokIdMask) == b;      // (t carries no end flag here, so t == a compares ids)
-}
-
+// ---- one merge (is_cand: wide_dev.h) ------------------------------------------------------------------------------
 __global__ __launch_bounds__(kSpanThreads) void k_wide_cand(const uint32_t *__restrict__ tok, const WideCtl *ctl,
                                                             uint32_t *__restrict__ span_sum) {
     if (ctl->k >= ctl->k_limit || !ctl->live) return;

@@ -12,7 +12,7 @@ namespace mbpe {
 void WideRun::release(DevPool &pool) {
     pool.free(tok[0]); pool.free(tok[1]); pool.free(val); pool.free(scratch); pool.free(wt[0]); pool.free(wt[1]);
     pool.free(tab.keys); pool.free(tab.cnts); pool.free(ctl); pool.free(best); pool.free(arg);
-    pool.free(fs); pool.free(tally); pool.free(lim.len);
+    pool.free(fs); pool.free(tally); pool.free(lim.len); pool.free(res);
     *this = WideRun{};
 }
 
@@ -173,23 +173,55 @@ int WideRun::begin_from(const WideDev &d, const WideTokens &src, const WideGoal 
     return MBPE_OK;
 }
 
+// The option "resident": does the next group of merges run in the one workgroup of wide_resident.h?  Only a training
+// without stopping rules (the kernel has none), on a stream of at most "resident_max_tokens" tokens and a pair table
+// of at most kResMaxSlots slots (every launch scans it once), whose chunks each fit a region -- which the launch
+// itself finds out (res_refused).
+bool WideRun::resident_now(const WideDev &d) const {
+    return d.resident && !res_refused && !lim.len && !lim.min_count && n_upper <= d.resident_max &&
+           n_upper <= kResMaxTokens && (uint64_t)tab.mask + 1 <= kResMaxSlots;
+}
+
+// How many merges a resident launch takes on: as many as the table has room for at load factor 1/2 (16 at least:
+// the caller grows the table for them, as it always did), and no more than run in some 20 ms at the time per merge
+// measured over the launch before (64 for the first).
+uint32_t WideRun::resident_group(uint32_t left, unsigned long long top) const {
+    const double cap = res_us_per_merge > 0 ? 20000.0 / res_us_per_merge : 64.0;
+    const uint32_t want = std::min<uint32_t>(left, (uint32_t)std::min(std::max(cap, 16.0), 4096.0));
+    const uint64_t room = ((uint64_t)tab.mask + 1) / 2, used = h_ctl.n_entries;
+    const uint64_t fit = room > used ? (room - used) / wide_headroom(top, n_upper, 1) : 0;
+    return (uint32_t)std::max<uint64_t>(std::min<uint64_t>(want, fit), std::min<uint32_t>(want, 16u));
+}
+
 int WideRun::steps(const WideDev &d, uint32_t n_steps, uint32_t *done_out) {
     *done_out = 0;
     const uint32_t n_wide = goal.n_wide;
     uint32_t done = 0;
     unsigned long long top = h_best.empty() ? top0 : (unsigned long long)h_best.back().count;
     while (done < n_steps && k < n_wide) {
-        const uint32_t group = std::min<uint32_t>({16u, n_steps - done, n_wide - k});
+        const bool resident = resident_now(d);
+        const uint32_t left = std::min<uint32_t>(n_steps - done, n_wide - k);
+        const uint32_t group = resident ? resident_group(left, top) : std::min<uint32_t>(16u, left);
+        if (resident && !res) {
+            HIPCHK(d.pool.alloc(&res, sizeof(WideResident)));
+            HIPCHK(hipMemsetAsync(res, 0, sizeof(WideResident), d.stream));
+        }
         // room for what this group can insert (load factor 1/2 at most)
         const uint64_t need = (uint64_t)h_ctl.n_entries + wide_headroom(top, n_upper, group);
         if (2 * need > (uint64_t)tab.mask + 1) {
             const int rc = regrow(d, 2 * need);
             if (rc != MBPE_OK) return rc;
             d.stats.n_table_grows++;
+            if (resident && !resident_now(d)) continue;      // (grown beyond what a launch scans: sized again, as launches)
         }
         HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&ctl->k_limit), (int)(k + group), 1, d.stream));
         HIPCHK(hipEventRecord(d.ev0, d.stream));
-        for (uint32_t g = 0; g < group; ++g) {
+        if (resident) {
+            launch_wide_resident(d.stream, tok[cur], tok[cur ^ 1], wt[cur], wt[cur ^ 1], tab, ctl, best, goal.new_id_base,
+                                 goal.first, res);
+            HIPCHK(hipMemcpyAsync(&h_res, res, sizeof(WideResident), hipMemcpyDeviceToHost, d.stream));
+        }
+        for (uint32_t g = 0; g < group && !resident; ++g) {
             const int src = cur ^ (int)(g & 1), dst = src ^ 1;
             launch_wide_argmax(d.stream, tab, ctl, best, arg, lim);
             if (goal.first) launch_wide_first(d.stream, tok[src], n_upper, tab, ctl, best, arg, fs, lim);
@@ -201,13 +233,22 @@ int WideRun::steps(const WideDev &d, uint32_t n_steps, uint32_t *done_out) {
         float ms = 0;
         HIPCHK(hipEventElapsedTime(&ms, d.ev0, d.ev1));
         d.stats.ms_steps += ms;
+        if (resident && !h_res.ok) {           // a chunk longer than a region takes: nothing ran, this group again
+            res_refused = true;
+            continue;
+        }
         const uint32_t ran = h_ctl.k - k;
+        if (resident) {
+            res_launches++;
+            res_merges += ran;
+            if (ran) res_us_per_merge = 1000.0 * ms / ran;
+        }
         // empty table (Tokenizer.h:586-588): cannot happen after a 16-bit part that merged -- except in `first` mode, where
         // it means no pair is left: the loop ends there, with fewer merges than the vocabulary asks for
         if (ran == 0) break;
         h_best.resize((size_t)k + ran);
         HIPCHK(hipMemcpy(h_best.data() + k, best + k, (size_t)ran * sizeof(WideBest), hipMemcpyDeviceToHost));
-        cur ^= (int)(ran & 1u);
+        cur ^= resident ? 1 : (int)(ran & 1u);      // (a resident launch closes its regions up into the other buffer)
         n_upper = h_ctl.n;
         k += ran;
         done += ran;
@@ -219,6 +260,7 @@ int WideRun::steps(const WideDev &d, uint32_t n_steps, uint32_t *done_out) {
             h_best.resize((size_t)k + fill, h_best.back());
             k += fill;
             done += fill;
+            if (resident) res_merges += fill;
             HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&ctl->k), (int)k, 1, d.stream));
             HIPCHK(hipStreamSynchronize(d.stream));
             h_ctl.k = k;

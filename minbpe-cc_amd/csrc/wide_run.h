@@ -8,13 +8,18 @@
 #include "dev_pool.h"
 #include "mbpe.h"
 #include "wide.h"
+#include "wide_resident.h"
 
 #include <vector>
 
 namespace mbpe {
 
-// the context's side of every call: its stream, its two timing events, its pool, and the stats the loop adds to
-struct WideDev { hipStream_t stream; hipEvent_t ev0, ev1; DevPool &pool; int n_cus; mbpe_stats &stats; };
+// the context's side of every call: its stream, its two timing events, its pool, the stats the loop adds to, and the
+// options "resident" and "resident_max_tokens" as they stand
+struct WideDev {
+    hipStream_t stream; hipEvent_t ev0, ev1; DevPool &pool; int n_cus; mbpe_stats &stats;
+    bool resident; uint64_t resident_max;
+};
 
 // what a begin says of the loop ahead: the merges it may make, the id of its first one, the tie-break
 struct WideGoal { uint32_t n_wide, new_id_base; bool first; };
@@ -55,6 +60,12 @@ struct WideRun {
     WideCtl h_ctl = {};
     std::vector<WideBest> h_best;    // ... and what they were
     bool active = false;             // the training's stream, table and merge counter live here
+    // the option "resident" (wide_resident.h): what its launches left, and what mbpe_train_resident_stats reports
+    WideResident *res = nullptr;
+    WideResident h_res = {};
+    bool res_refused = false;        // a chunk was longer than a region takes: the launches of wide.h from there on
+    double res_us_per_merge = 0;     // measured over the latest resident launch (0: none yet); sizes the next group
+    uint64_t res_merges = 0, res_launches = 0;
 
     void release(DevPool &pool);     // every buffer back to the pool, every member as it is declared above
     int convert(const WideDev &d, const WideSlots &src, const WideGoal &goal);
@@ -76,6 +87,8 @@ private:
     int sync(const WideDev &d);
     int alloc_loop(const WideDev &d, uint64_t n_tok, uint64_t n_val, uint64_t n_init);
     int begin_limits(const WideDev &d, const WideTokens &src);
+    bool resident_now(const WideDev &d) const;
+    uint32_t resident_group(uint32_t left, unsigned long long top) const;
 };
 
 }  // namespace mbpe

@@ -86,7 +86,11 @@ void usage() {
                  "                              on the host, with --device-encode, --device-split and --rank-order alike\n"
                  "  --resident                  With --encode --device-encode: run the merge rounds of every chunk of at most 256\n"
                  "                              bytes in one kernel on the chip instead of passes over the whole stream: the\n"
-                 "                              same output, with every other option; meant for --rank-order and --dropout\n"
+                 "                              same output, with every other option; meant for --rank-order and --dropout.\n"
+                 "                              With --train: where the training runs the 32-bit loop on a short stream (--dedup,\n"
+                 "                              --input-list, --counts, `first`, --continue-from) a group of merges is one kernel\n"
+                 "                              launch of one workgroup, for streams up to the library's bound -- whose default is\n"
+                 "                              0, so today the flag changes nothing here: the same model\n"
                  "  --dedup                     With --train: split as asked, then train on the distinct chunks with their counts\n"
                  "                              (deduplicated on the HIP device): the same model.  One pass over the unique\n"
                  "                              chunks per merge: meant for -c first, for vocabularies beyond 65,536 and for\n"
@@ -244,7 +248,10 @@ int main(int argc, char *argv[]) {
         if (!rank_order) { std::cerr << "--dropout requires --rank-order\n"; return 107; }
     }
 
-    if (resident && !(encode && device_encode)) { std::cerr << "--resident requires --encode --device-encode\n"; return 107; }
+    if (resident && !(encode && device_encode) && !train) {
+        std::cerr << "--resident requires --train, or --encode --device-encode\n";
+        return 107;
+    }
     if (have_limits && !train) { std::cerr << "--min-frequency and --max-token-length require --train\n"; return 107; }
 
     if (!token_counts_path.empty() && (!encode || train || decode)) { std::cerr << "--token-counts-out requires --encode\n"; return 107; }
@@ -329,6 +336,7 @@ int main(int argc, char *argv[]) {
         mbpe_tok_destroy(rt);
         return 105;
     }
+    if (train && resident) mbpe_tok_set_train_resident(rt, 1);
     // --counts and --input-list: opens the pieces session, merges the counts files in the order given, then reads the
     // pieces one at a time.  false: a file could not be used (said on stderr; counts_failed for a counts file);
     // *trc: the code of the library call that failed, if one did

@@ -314,6 +314,7 @@ int Tokenizer::run_training(mbpe_ctx *ctx, int rc, int vocab_size, CONFLICT_RESO
     // (the stopping rules, mbpe_tok_set_train_limits: either non-zero and the training runs on 32-bit tokens throughout)
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "min_frequency", train_min_frequency_);
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "max_token_length", train_max_token_length_);
+    if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "resident", train_resident_ ? 1 : 0);      // (mbpe_tok_set_train_resident)
     if (rc == MBPE_OK) rc = mbpe_train_begin_from(ctx, static_cast<uint32_t>(vocab_size), prior.data(), n_prior_of(prior));
     if (rc == MBPE_OK) rc = mbpe_train_steps(ctx, cap, nullptr);
     if (rc == MBPE_OK) rc = mbpe_train_result(ctx, out->flat.data(), out->had.data(), cap, &out->n_merges);
@@ -1448,6 +1449,16 @@ int mbpe_tok_set_encode_dedup(mbpe_tokenizer *t, int on) {
         return MBPE_ERR_ARG;
     }
     t->t->set_encode_dedup(on == 1);
+    return MBPE_OK;
+}
+
+int mbpe_tok_set_train_resident(mbpe_tokenizer *t, int on) {
+    if (!t) return MBPE_ERR_ARG;
+    if (on != 0 && on != 1) {
+        mbpe_host::set_last_error("mbpe_tok_set_train_resident: on must be 0 or 1");
+        return MBPE_ERR_ARG;
+    }
+    t->t->set_train_resident(on == 1);
     return MBPE_OK;
 }
 

@@ -140,6 +140,8 @@ public:
         train_min_frequency_ = min_frequency;
         train_max_token_length_ = max_token_length;
     }
+    // every training from here on sets the context option "resident" (mbpe_tok_set_train_resident)
+    void set_train_resident(bool on) { train_resident_ = on; }
     // the device encode calls from here on go through the encoder's "dedup" route (mbpe_tok_set_encode_dedup)
     void set_encode_dedup(bool on) { encode_dedup_ = on; }
     // ... and run the kept encoder with its option "resident" (mbpe_tok_set_encode_resident)
@@ -254,7 +256,7 @@ private:
     } pieces_;
     bool encode_split_ = false;
     bool split_unicode_ = false;
-    bool train_dedup_ = false;
+    bool train_dedup_ = false, train_resident_ = false;
     int64_t train_min_frequency_ = 0, train_max_token_length_ = 0;
     bool encode_dedup_ = false;
     bool encode_resident_ = false;

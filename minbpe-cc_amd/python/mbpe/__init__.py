@@ -22,7 +22,7 @@ COMM_ID_BYTES = 128
 EXPORTS = [
     "mbpe_last_error", "mbpe_version", "mbpe_create", "mbpe_destroy", "mbpe_load_corpus",
     "mbpe_pair_count_u8", "mbpe_train_begin", "mbpe_train_steps", "mbpe_train_sequences", "mbpe_train_result",
-    "mbpe_train_lexical", "mbpe_train", "mbpe_get_stats", "mbpe_get_stream", "mbpe_stream_device", "mbpe_table_device", "mbpe_get_pairs", "mbpe_compact",
+    "mbpe_train_lexical", "mbpe_train", "mbpe_get_stats", "mbpe_train_resident_stats", "mbpe_train_resident_ticks", "mbpe_get_stream", "mbpe_stream_device", "mbpe_table_device", "mbpe_get_pairs", "mbpe_compact",
     "mbpe_set_option", "mbpe_comm_unique_id", "mbpe_comm_init", "mbpe_comm_init_external",
     "mbpe_comm_exchange_buffer", "mbpe_comm_exchange_done", "mbpe_presplit",
     "mbpe_split_count", "mbpe_split_offsets", "mbpe_split_has_gaps", "mbpe_split_starts", "mbpe_split_ends",
@@ -68,7 +68,7 @@ TOK_EXPORTS = [
     "mbpe_tok_train_split_device", "mbpe_tok_set_encode_split", "mbpe_tok_set_split_unicode",
     "mbpe_tok_set_encode_order", "mbpe_tok_train_continue", "mbpe_tok_encode_byteoff",
     "mbpe_tok_encode_batch_byteoff_device", "mbpe_tok_set_encode_dropout", "mbpe_tok_set_train_dedup",
-    "mbpe_tok_set_encode_dedup", "mbpe_tok_set_encode_resident",
+    "mbpe_tok_set_encode_dedup", "mbpe_tok_set_encode_resident", "mbpe_tok_set_train_resident",
     "mbpe_tok_train_pieces_begin", "mbpe_tok_train_pieces_add",
     "mbpe_tok_train_pieces_finish", "mbpe_tok_train_pieces_abort", "mbpe_tok_set_train_limits",
     "mbpe_tok_train_pieces_export_size", "mbpe_tok_train_pieces_export", "mbpe_tok_train_pieces_merge",
@@ -230,6 +230,8 @@ def lib():
     L.mbpe_train_begin_from.argtypes = [vp, u32, vp, u32]
     L.mbpe_train_from.argtypes = [vp, vp, u64, vp, u64, u32, i32, vp, u32, vp, vp, vp, vp]
     L.mbpe_get_stats.argtypes = [vp, vp]
+    L.mbpe_train_resident_stats.argtypes = [vp, vp, vp, vp]
+    L.mbpe_train_resident_ticks.argtypes = [vp, vp, vp, vp]
     L.mbpe_get_stream.argtypes = [vp, vp, vp, u64, vp]
     L.mbpe_stream_device.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(u32), ctypes.POINTER(u32),
                                      ctypes.POINTER(u32)]
@@ -347,6 +349,7 @@ def lib():
     L.mbpe_tok_set_encode_dedup.argtypes = [vp, i32]
     L.mbpe_encoder_resident_stats.argtypes = [vp, vp, vp, vp]
     L.mbpe_tok_set_encode_resident.argtypes = [vp, i32]
+    L.mbpe_tok_set_train_resident.argtypes = [vp, i32]
     L.mbpe_wordcount_create.argtypes = [i32, ctypes.POINTER(vp)]
     L.mbpe_wordcount_destroy.argtypes = [vp]
     L.mbpe_wordcount_destroy.restype = None
@@ -2393,6 +2396,21 @@ class Trainer:
         _check(lib().mbpe_get_stats(self._h, ctypes.byref(st)))
         return st.as_dict()
 
+    def resident_stats(self):
+        """What the option "resident" did in the latest training (mbpe_train_resident_stats) -> (merges made by its
+        launches, launches, slices of the pair table its argmax rescanned); all 0: every group took the launches
+        of the 32-bit loop."""
+        v = [ctypes.c_uint64() for _ in range(3)]
+        _check(lib().mbpe_train_resident_stats(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def resident_ticks(self):
+        """Diagnostics for tools/train_resident_time.py (mbpe_train_resident_ticks): the kernel's time in 10 ns ticks
+        -> (argmax, `first` search, stream walks)."""
+        v = [ctypes.c_uint64() for _ in range(3)]
+        _check(lib().mbpe_train_resident_ticks(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     def stream(self):
         n = ctypes.c_uint64()
         _check(lib().mbpe_get_stream(self._h, None, None, 0, ctypes.byref(n)))
@@ -2482,8 +2500,13 @@ class Tokenizer:
         _check(lib().mbpe_tok_set_special_tokens(self._h, b, len(b)))
 
     def train(self, data, vocab_size, conflict_resolution=1, verbose=False, device=0, device_split=False,
-              resume=False, dedup=False, min_frequency=0, max_token_length=0):
-        """min_frequency, max_token_length (here, in train_from_iterator and train_files; mbpe_tok_set_train_limits):
+              resume=False, dedup=False, min_frequency=0, max_token_length=0, resident=False):
+        """resident (here, in train_from_iterator, train_files and train_from_counts; mbpe_tok_set_train_resident): the
+        training context's option "resident": where the training runs the 32-bit loop on a short stream (dedup, word
+        counts, `first`, resume) a group of merges is one kernel launch, for streams of at most "resident_max_tokens"
+        tokens.  That bound's default is 0 and the Tokenizer does not set it, so today the switch changes nothing
+        here; Trainer.set_option sets both.  Same merges; a speed option.
+        min_frequency, max_token_length (here, in train_from_iterator and train_files; mbpe_tok_set_train_limits):
         the stopping rules.  The training ends when the best pair left occurs fewer than min_frequency times, and no
         new token is longer than max_token_length bytes (at least 2; the merges a resumed training starts from stay):
         pairs that would make one are never chosen, and the training ends when no other pair is left.  0: off.  The
@@ -2503,6 +2526,7 @@ class Tokenizer:
         _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
         _check(lib().mbpe_tok_set_train_dedup(self._h, int(bool(dedup))))
         _check(lib().mbpe_tok_set_train_limits(self._h, int(min_frequency), int(max_token_length)))
+        _check(lib().mbpe_tok_set_train_resident(self._h, int(bool(resident))))
         if resume:
             _check(lib().mbpe_tok_train_continue(self._h, text.ctypes.data if len(text) else None, len(text), vocab_size,
                                                  conflict_resolution, int(verbose), device, int(bool(device_split))))
@@ -2512,16 +2536,17 @@ class Tokenizer:
                   int(verbose), device))
 
     def train_from_iterator(self, texts, vocab_size, conflict_resolution=1, verbose=False, device=0, device_split=False,
-                            resume=False, repeats=None, min_frequency=0, max_token_length=0):
+                            resume=False, repeats=None, min_frequency=0, max_token_length=0, resident=False):
         """Train on a corpus that arrives in pieces (mbpe_tok_train_pieces_*): every text is split on its own and its
         chunks are counted on the device (mbpe_wordcount_*), then the training runs on the table -- the merges of a
         training on the pieces' chunk lists laid end to end, for both tie-breaks, with one piece in host memory at a
         time.  A piece boundary is a chunk boundary: to get a whole file's result, cut it where a letter or digit is
         followed by whitespace.  repeats: one count per text (default 1), the text counted that many times.
-        device_split, resume, min_frequency, max_token_length: as for train().  The tokenizer's merges stay as they are until the training has
+        device_split, resume, min_frequency, max_token_length, resident: as for train().  The tokenizer's merges stay as they are until the training has
         succeeded; the session is aborted when the iterator or a call raises."""
         _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
         _check(lib().mbpe_tok_set_train_limits(self._h, int(min_frequency), int(max_token_length)))
+        _check(lib().mbpe_tok_set_train_resident(self._h, int(bool(resident))))
         _check(lib().mbpe_tok_train_pieces_begin(self._h, device, int(bool(device_split))))
         try:
             reps = None if repeats is None else iter(repeats)
@@ -2584,7 +2609,7 @@ class Tokenizer:
         return self.count_from_iterator(read(), **kw)
 
     def train_from_counts(self, blobs, vocab_size, conflict_resolution=1, verbose=False, device=0, resume=False,
-                          min_frequency=0, max_token_length=0, texts=None, device_split=False):
+                          min_frequency=0, max_token_length=0, texts=None, device_split=False, resident=False):
         """The training stage on counts made elsewhere: the blobs of count_from_iterator are merged in the order given,
         then any `texts` are added as train_from_iterator adds them (device_split: how these are split), then the
         training runs -- merges, counts, .model, .vocab and verbose lines of train_from_iterator on all the pieces in
@@ -2594,6 +2619,7 @@ class Tokenizer:
         the training has succeeded."""
         _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
         _check(lib().mbpe_tok_set_train_limits(self._h, int(min_frequency), int(max_token_length)))
+        _check(lib().mbpe_tok_set_train_resident(self._h, int(bool(resident))))
         _check(lib().mbpe_tok_train_pieces_begin(self._h, device, int(bool(device_split))))
         try:
             for blob in blobs:
