@@ -125,6 +125,10 @@ typedef struct {
     uint32_t log_passes;       /* "pair_cells": stream passes whose count deltas went through the delta log (this training) */
     uint32_t log_refills;      /* "pair_cells": log chunks taken by waves that had filled an earlier one (this training) */
     uint32_t pad3_;
+    uint32_t n_tt_split;       /* "tt_split": fused passes that ran plain and left the tiles with a run of a (t,t) member's
+                                  token to the list pass (this training) */
+    uint32_t pad4_;
+    uint64_t tt_deferred_tiles; /* "tt_split": tiles those passes handed to the list pass */
 } mbpe_stats;
 
 MBPE_API const char *mbpe_last_error(void);
@@ -414,6 +418,11 @@ MBPE_API int mbpe_compact(mbpe_ctx *ctx);
  *                   kernels that sequence needs (one event wait per sequence, ~12 launches instead of ~27), 0 = it
  *                   enqueues whole groups of sequences with every kernel variant and the device decides which work;
  *                   -1 (default): 1 for streams of up to 32 Mi slots on one rank, 0 otherwise.  Same results.
+ *   "tt_split"      a fused pass whose batch has (t,t) members, all pairs of raw bytes: 1 = the pass runs without the
+ *                   (t,t) code, which slows every tile down, and a second, short pass does the tiles that hold a run of a
+ *                   member's token (not for frequent pairs, not while the pass logs); 0 = never; -1 (default) = as 1
+ *                   when the members' counts sum to less than one per 16 tiles.  Same results; mbpe_stats counts
+ *                   the passes and the tiles (n_tt_split, tt_deferred_tiles).
  *   "pair_cells"    a match whose two neighbours are raw bytes, with no other match touching it, costs the stream pass
  *                   one 4-byte record in a log instead of two atomics on its pair's delta rows; three small kernels
  *                   around the pass sort the records into buckets of 64 pairs and count them in LDS (the name is that

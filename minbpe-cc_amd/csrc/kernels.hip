@@ -2956,8 +2956,8 @@ __device__ __forceinline__ void log_finish(const LogWave &lw, __amdgpu_buffer_rs
     }
 }
 
-// (defined with k_fused_batch; WRITE false = count and mark only)
-template <int MODE, int DIAG, bool WRITE, bool TT, class DC>
+// (defined with k_fused_batch; WRITE false = count and mark only; DEFER: see there)
+template <int MODE, int DIAG, bool WRITE, bool TT, bool DEFER = false, class DC = void>
 __device__ __forceinline__ uint4 fused_tile_pf(const uint4 q_orig, const uint32_t s[8], const Halo h,
                                                uint32_t old_x, uint32_t old_y, uint32_t old_z, const BatchLut &lut,
                                                uint32_t X0, uint32_t tile, TileSum *sout, uint32_t *hdr_adj, uint32_t *LR,
@@ -3075,7 +3075,10 @@ __global__ __launch_bounds__(kLutThreads) void k_scan_batch(const uint16_t *tok0
 // a second token counts for the pair of the slot before it, a first token right after a match for the pair two slots
 // back (ADJ).  Everything else (neighbours, deltas, the new tile and its summary) is only done where a match is.
 // (t,t) members: the caller renames the tile first where a run of a member's token needs it (tt_rename; `renamed`).
-template <int MODE, int DIAG, bool WRITE, bool TT, class DC>
+// DEFER (never with TT; byte table only): the batch has (t,t) members but this instantiation holds none of their code.  It
+// looks for the same markers as TT does, and a tile that shows one is left exactly as it is and reported through
+// `need_rename`: the caller lists it for the list pass (k_fused_tt_list), which is the TT code on those tiles alone.
+template <int MODE, int DIAG, bool WRITE, bool TT, bool DEFER, class DC>
 __device__ __forceinline__ uint4 fused_tile_pf(const uint4 q_orig, const uint32_t s[8], const Halo h,
                                                uint32_t old_x, uint32_t old_y, uint32_t old_z, const BatchLut &lut,
                                                uint32_t X0, uint32_t tile, TileSum *sout, uint32_t *hdr_adj, uint32_t *LR,
@@ -3117,16 +3120,24 @@ __device__ __forceinline__ uint4 fused_tile_pf(const uint4 q_orig, const uint32_
     // The batch index of the match every slot starts (kNone: none) -- and of the three matches across the tile's edges,
     // which lanes 0, 1, 2 look up in a ninth read: (p1, first token), (p2, p1), (last token, n1).
     // ((t,t) members, byte table: lane 3 looks up (n1, n2) as well -- only for the marker of "a run of a member's token")
-    const uint32_t ef = lane == 0 ? h.p1 : lane == 1 ? h.p2 : lane == 2 ? tile_last : (TT && lane == 3) ? h.n1 : kHole;
-    const uint32_t es = (lane == 0 ? tile_first : lane == 1 ? h.p1 : (TT && lane == 3) ? h.n2 : h.n1) & idmask;
+    const uint32_t ef = lane == 0 ? h.p1 : lane == 1 ? h.p2 : lane == 2 ? tile_last : ((TT || DEFER) && lane == 3) ? h.n1 : kHole;
+    const uint32_t es = (lane == 0 ? tile_first : lane == 1 ? h.p1 : ((TT || DEFER) && lane == 3) ? h.n2 : h.n1) & idmask;
     uint32_t idx[8], eidx;
-    if (lut.bytes) {             // (uniform) the byte table: the entry is the index
+    if (DEFER || lut.bytes) {    // (uniform) the byte table: the entry is the index
 #pragma unroll
         for (int j = 0; j < 8; ++j) idx[j] = byte_entry<TT>(lut, s[j], MODE == 1 ? n[j] & idmask : n[j], idmask);
         eidx = byte_entry<TT>(lut, ef, es, idmask);
         // nearly every tile of a small batch: no match anywhere (indices are 16-bit: all kNone iff their AND is)
         const uint32_t all = idx[0] & idx[1] & idx[2] & idx[3] & idx[4] & idx[5] & idx[6] & idx[7] & eidx;
         if (__ballot(all != kNone) == 0ull && DIAG != 3 && DIAG != 5) return q_orig;
+        if (DEFER) {
+            // the same markers, the same nine lookups: this tile is deferred exactly when the TT code would rename it
+            bool mark = eidx == kTTMark;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) mark = mark || idx[j] == kTTMark;
+            if (__ballot(mark) != 0ull) { need_rename = true; return q_orig; }
+            eidx = lane == 3 ? kNone : eidx;
+        }
         if (TT) {
             // a run of a (t,t) member's token somewhere in or around the tile: the caller renames (tt_rename) and comes
             // back; afterwards no two of them are side by side, a marker that still shows up is "no match"
@@ -3315,7 +3326,10 @@ __device__ __forceinline__ uint4 fused_tile_pf(const uint4 q_orig, const uint32_
 #ifndef MBPE_FUSED_WAVES
 #define MBPE_FUSED_WAVES 4
 #endif
-template <int MODE, bool HOT, bool TT, int DIAG = 0, bool LOG = false>
+// DEFER (plain, no log, byte table: the split route of a batch with (t,t) members, see k_tt_split_plan): the plain tile
+// function on every tile; a tile in or next to a run of a member's token is copied as it is and appended to the tile
+// list, which this instantiation receives in place of the tile marks (`chg`: a fused pass sets none).
+template <int MODE, bool HOT, bool TT, int DIAG = 0, bool LOG = false, bool DEFER = false>
 __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) void k_fused_batch(uint16_t *tok0, uint16_t *tok1,
                                                                const TileSum *__restrict__ sin,
                                                                TileSum *__restrict__ sout, uint32_t n_tiles,
@@ -3333,7 +3347,12 @@ __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) 
     const uint32_t n_keys = ctl->batch_n;
     if (n_keys < 2 || !ctl->fused) return;
     // (the instantiation with the (t,t) code only runs for batches that have such a member, like HOT)
-    if ((bs->tt_index != kNoTT) != TT) return;
+    static_assert(!DEFER || (!TT && !HOT && !LOG && DIAG == 0), "the deferring pass is a plain one");
+    if (DEFER ? ctl->tt_split == 0u : (bs->tt_index != kNoTT) != TT) return;
+    if (DEFER && bs->tt_index == kNoTT) {        // (k_tt_split_restore has not run: the table would carry no markers)
+        if (threadIdx.x == 0) atomicOr(&ctl->err, kErrTTSplit);
+        return;
+    }
     __shared__ TTInfo ti;
     __shared__ __attribute__((aligned(16))) uint16_t stage_mem[kLutThreads / kWave][kTileSlots];
     uint16_t *stage = stage_mem[threadIdx.x / kWave];
@@ -3341,11 +3360,11 @@ __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) 
     const uint16_t *tok = ctl->cur ? tok1 : tok0;
     uint16_t *dst = ctl->cur ? tok0 : tok1;
     const uint32_t X0 = 256u + ctl->k_done;
-    if (hot_mismatch<HOT>(bs->packed[0] >> 32, ctl, hot_launched)) return;     // (see k_merge)
+    if (!DEFER && hot_mismatch<HOT>(bs->packed[0] >> 32, ctl, hot_launched)) return;     // (see k_merge)
     constexpr bool dc_on = HOT;
     if (dc_on) dc_init(dc);
     BatchLut lut(&lut_mem, bs, idmask);
-    lut_build(lut, bs, n_keys, idmask - 1u, TT);
+    lut_build(lut, bs, n_keys, idmask - 1u, TT || DEFER);
     if (TT) tt_build(ti, bs, n_keys, idmask - 1u);
     if (blockIdx.x == 0 && threadIdx.x == 0) ctl->marks_all = 1;
     uint32_t tile = rfl(blockIdx.x * waves_per_block + threadIdx.x / kWave);
@@ -3422,9 +3441,13 @@ __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) 
                     renamed = true;
                 }
             }
-            outq = fused_tile_pf<MODE, DIAG, true, TT>(t0.q, s, h, old_x, old_y, old_z, lut, X0, tile, sout, hdr_adj, LR, dc,
+            outq = fused_tile_pf<MODE, DIAG, true, TT, DEFER>(t0.q, s, h, old_x, old_y, old_z, lut, X0, tile, sout, hdr_adj, LR, dc,
                                                        dc_on, wave_rm, wrote_sum, lr_rsrc, adj_pitch, stage, chg, renamed, &ti,
                                                        need_rename, log_rsrc, use_log, &lw);
+            if (DEFER && need_rename && lane == 0) {     // (uniform, rare) for the list pass; at most every tile once
+                const uint32_t at = atomicAdd(&ctl->tt_list_n, 1u);
+                if (at < n_tiles) chg[at] = tile;
+            }
             if (TT && need_rename) {             // (uniform, rare)
                 tt_rename<MODE>(s, h, ti, run_in[tile]);
                 outq = fused_tile_pf<MODE, DIAG, true, TT>(t0.q, s, h, old_x, old_y, old_z, lut, X0, tile, sout, hdr_adj, LR,
@@ -3452,6 +3475,139 @@ __global__ __launch_bounds__(kLutThreads, MBPE_FUSED_WAVES * 256 / kLutThreads) 
     if (TT) {                           // matches of the (t,t) member: its count is not simply the pair's count
         tt_flush(ti, hdr_m);
     }
+}
+
+// ---- (t,t) members of a byte batch: the split route ------------------------------------------------
+// The (t,t) code makes every tile of a pass slower (the compiler's registers) while a fraction of
+// a percent of the tiles holds a run of a member's token.  So where such tiles are rare the pass is split: the DEFER
+// instantiation of k_fused_batch does every tile the plain way and lists the tiles that show a marker, and
+// k_fused_tt_list, right behind it, runs the (t,t) tile path on the listed tiles.  Both read the old buffer and the old
+// summaries only, so a listed tile's neighbours do not care which of the two wrote it.
+// k_tt_split_plan decides (one wave, enqueued between the plain and the (t,t) instantiations of the whole-stream pass):
+// option "tt_split" 0 never; 1 whenever the batch has (t,t) members, uses the byte table, does not log and is not the
+// frequent-pair instantiation's; -1 also asks that the members' counts sum to less than one per 16 tiles.  The
+// whole-stream instantiations are not asked to know about any of this: for a split pass the plan takes
+// BatchState::tt_index away while they are dispatched -- the plain one has returned because of it, the (t,t) ones
+// return without it -- and k_tt_split_restore puts it back before the two kernels of the split route run.
+// (one whole wave; everything but the delta log's say, which k_log_plan has only after k_seq_info asks)
+__device__ __forceinline__ bool tt_split_wanted(const DevCtl *ctl, const BatchState *bs, int mode, uint32_t n_tiles) {
+    const uint32_t n = ctl->batch_n;
+    const uint32_t first = bs->tt_index;
+    if (mode == 0 || n < 2u || ctl->fused == 0u || first == kNoTT || bs->byte_lut == 0u) return false;
+    if (dc_wanted(bs->packed[0] >> 32, ctl->n_live * ctl->n_ranks)) return false;
+    if (mode > 0) return true;
+    unsigned long long cnt = 0;          // (this lane's share of the members' counts)
+    for (uint32_t j = first + lane_id(); j < n; j += kWave)
+        if ((bs->key[j] >> 16) == (bs->key[j] & 0xFFFFu)) cnt += bs->packed[j] >> 32;
+    for (int d = kWave / 2; d > 0; d >>= 1) cnt += __shfl_xor(cnt, d, kWave);
+    return cnt * 16ull < (unsigned long long)n_tiles * ctl->n_ranks;
+}
+
+__global__ __launch_bounds__(kWave) void k_tt_split_plan(DevCtl *ctl, BatchState *bs, const LogState *ls, int mode,
+                                                         uint32_t n_tiles) {
+    const uint32_t first = bs->tt_index;
+    const bool split = tt_split_wanted(ctl, bs, mode, n_tiles) && !(ls != nullptr && ls->on != 0u);
+    if (threadIdx.x != 0) return;
+    ctl->tt_split = split ? 1u : 0u;
+    ctl->tt_list_n = 0;
+    if (split) {
+        ctl->tt_saved_index = first;
+        bs->tt_index = kNoTT;
+        ctl->n_tt_split += 1u;
+    }
+}
+
+__global__ void k_tt_split_restore(const DevCtl *ctl, BatchState *bs) {
+    if (blockIdx.x || threadIdx.x) return;
+    if (ctl->tt_split) bs->tt_index = ctl->tt_saved_index;
+}
+
+// The list pass: k_fused_batch's (t,t) tile path (byte table, no delta log, no delta cache) over the tiles the deferring
+// pass listed, walked like k_rewrite_marked walks its list.  The deferring pass has stored every listed tile and its
+// old summary already; this pass stores them again as they come out.
+template <int MODE>
+__global__ __launch_bounds__(kLutThreads) void k_fused_tt_list(uint16_t *tok0, uint16_t *tok1,
+                                                                 const TileSum *__restrict__ sin,
+                                                                 TileSum *__restrict__ sout, uint32_t n_tiles,
+                                                                 const uint32_t *__restrict__ list, const BatchState *bs,
+                                                                 uint32_t *hdr_adj, uint32_t *LR, DevCtl *ctl,
+                                                                 const RankEdge *le, const RankEdge *re, uint32_t *hdr_m,
+                                                                 const uint32_t *__restrict__ run_in) {
+    constexpr uint32_t idmask = MODE == 1 ? 0x7FFFu : 0xFFFFu;
+    __shared__ BatchLutMem lut_mem;
+    __shared__ TTInfo ti;
+    __shared__ __attribute__((aligned(16))) uint16_t stage_mem[kLutThreads / kWave][kTileSlots];
+    if (!ctl->tt_split) return;
+    if (bs->tt_index == kNoTT) {                 // (as in the deferring pass)
+        if (threadIdx.x == 0) atomicOr(&ctl->err, kErrTTSplit);
+        return;
+    }
+    const uint32_t n_list = ctl->tt_list_n < n_tiles ? ctl->tt_list_n : n_tiles;
+    const uint32_t waves_per_block = kLutThreads / kWave;
+    if (blockIdx.x * waves_per_block >= n_list) return;          // (the whole workgroup: nothing listed for it)
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctl->tt_deferred_tiles += n_list;
+    uint16_t *stage = stage_mem[threadIdx.x / kWave];
+    const uint16_t *tok = ctl->cur ? tok1 : tok0;
+    uint16_t *dst = ctl->cur ? tok0 : tok1;
+    const uint32_t n_keys = ctl->batch_n;
+    const uint32_t X0 = 256u + ctl->k_done;
+    const uint32_t adj_pitch = rfl(ctl->adj_pitch);
+    BatchLut lut(&lut_mem, bs, idmask);
+    lut_build(lut, bs, n_keys, idmask - 1u, true);
+    tt_build(ti, bs, n_keys, idmask - 1u);
+    const uint32_t lane = lane_id();
+    const uint32_t n_waves = gridDim.x * waves_per_block;
+    uint32_t i = rfl(blockIdx.x * waves_per_block + threadIdx.x / kWave);
+    uint32_t wave_rm = 0;        // uniform
+    if (i < n_list) {
+    const __amdgpu_buffer_rsrc_t sums_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<TileSum *>(sin), 0, n_tiles * 16u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t lr_rsrc = __builtin_amdgcn_make_buffer_rsrc(LR, 0, 0xFFFFFFFCu, 0x00020000);
+    const uint32_t last = n_list - 1;
+    const uint32_t last_tile = n_tiles - 1;
+    auto tile_at = [&](uint64_t k) { const uint32_t t = list[k < n_list ? k : last]; return t < n_tiles ? t : last_tile; };
+    uint32_t tile0 = tile_at(i), tile1 = tile_at((uint64_t)i + n_waves);
+    TileIn t0 = tile_issue(tok, sums_rsrc, tile0);
+    for (;;) {
+        const bool has_next = (uint64_t)i + n_waves < n_list;
+        const uint32_t tile2 = tile_at((uint64_t)i + 2ull * n_waves);
+        const TileIn t1 = tile_issue(tok, sums_rsrc, tile1);
+
+        const uint32_t tile = tile0;
+        const uint32_t old_x = rlane(t0.smw, 4), old_y = rlane(t0.smw, 5), old_z = rlane(t0.smw, 6);
+        uint32_t s[8];
+        unpack8(t0.q, s);
+        Halo h;
+        const uint32_t pw1 = rlane(t0.smw, 1), pw2 = rlane(t0.smw, 2);
+        const uint32_t nw0 = rlane(t0.smw, 8), nw2 = rlane(t0.smw, 10);
+        const bool fast = tile > 0 && tile + 1 < n_tiles && (pw2 & 0xFFFFu) >= 2 && (nw2 & 0xFFFFu) >= 2;
+        if (fast) {
+            h.p1 = pw1 >> 16; h.p2 = pw1 & 0xFFFFu;
+            h.n1 = nw0 & 0xFFFFu; h.n2 = nw0 >> 16;
+        } else {
+            h = halo_slow(sin, n_tiles, tile, le, re);
+        }
+        bool wrote_sum = false, need_rename = false;     // uniform
+        DeltaCacheSmall no_dc;       // (never touched: dc_on is false)
+        uint4 outq = fused_tile_pf<MODE, 0, true, true>(t0.q, s, h, old_x, old_y, old_z, lut, X0, tile, sout, hdr_adj, LR,
+                                                        no_dc, false, wave_rm, wrote_sum, lr_rsrc, adj_pitch, stage, nullptr,
+                                                        false, &ti, need_rename);
+        if (need_rename) {           // (every listed tile, unless the list is stale)
+            tt_rename<MODE>(s, h, ti, run_in[tile]);
+            outq = fused_tile_pf<MODE, 0, true, true>(t0.q, s, h, old_x, old_y, old_z, lut, X0, tile, sout, hdr_adj, LR,
+                                                      no_dc, false, wave_rm, wrote_sum, lr_rsrc, adj_pitch, stage, nullptr,
+                                                      true, &ti, need_rename);
+        }
+        if (wrote_sum) reinterpret_cast<uint4 *>(dst)[(uint64_t)tile * kWave + lane] = outq;
+
+        if (!has_next) break;
+        i += n_waves;
+        tile0 = tile1; tile1 = tile2;
+        t0 = t1;
+    }
+    }
+    if (lane == 0 && wave_rm) atomicAdd(&ctl->rm, wave_rm);
+    tt_flush(ti, hdr_m);
 }
 
 // ---- the delta log: behind (and before) the pass ------------------------------------------------
@@ -4190,6 +4346,9 @@ __global__ void k_seq_finish(DevCtl *ctl, uint32_t *fused_flag, const BatchState
         ctl->skip_penalty /= 2u;
     }
     ctl->skip_failed = 0;
+    // (the split route's state is one pass's: a sequence whose host enqueues no plan must not see the last one's)
+    ctl->tt_split = 0;
+    ctl->tt_list_n = 0;
     // the delta log: once fewer than half of a large batch's matches lay between two raw bytes the stream is past the
     // stage where it pays (the share only falls as tokens replace bytes)
     // (a pass that k_log_plan kept from logging for want of room counted no such match: it has no say)
@@ -4905,7 +5064,7 @@ void launch_select_batch(const StreamView &v, const BatchView &b, PairTable t, u
                            a.fused_min, (uint32_t)v.n_ranks);
 }
 
-void launch_fused_batch(const StreamView &v, const BatchView &b, const Inst &w) {
+void launch_fused_batch(const StreamView &v, const BatchView &b, const Inst &w, int tt_split) {
     if (!v.n_tiles) return;
     static const int occ[3] = {resident_blocks(k_fused_batch<0, false, false, 0>, kLutThreads),
                                resident_blocks(k_fused_batch<1, false, false, 0>, kLutThreads),
@@ -4929,11 +5088,34 @@ void launch_fused_batch(const StreamView &v, const BatchView &b, const Inst &w) 
     MBPE_FUSED_DIAG_CASE(6)
 #undef MBPE_FUSED_DIAG_CASE
 #endif
+    // The split route of a batch with (t,t) members (k_tt_split_plan): the plan goes behind the plain instantiation and
+    // before the (t,t) ones, which it can keep from working; the deferring pass and the list pass follow them.
+    const bool may_split = tt_split != 0 && inst_may_split(w);
     // (the plain instantiations exist with and without the delta log's code: see k_fused_batch, LOG)
-    if (b.dlog)
-        MBPE_BY_MODE(v.endbit, MBPE_BY_INST(w, hipLaunchKernelGGL((k_fused_batch<M, HOT, TT, 0, !HOT>), grid, block, 0, v.stream, MBPE_FUSED_ARGS)));
-    else
-        MBPE_BY_MODE(v.endbit, MBPE_BY_INST(w, hipLaunchKernelGGL((k_fused_batch<M, HOT, TT, 0, false>), grid, block, 0, v.stream, MBPE_FUSED_ARGS)));
+#define MBPE_FUSED_INST(TT, HOT)                                                                                            \
+    if (inst_takes(w, TT, HOT)) {                                                                                           \
+        if (b.dlog) MBPE_BY_MODE(v.endbit, hipLaunchKernelGGL((k_fused_batch<M, HOT, TT, 0, !HOT>), grid, block, 0, v.stream, MBPE_FUSED_ARGS)); \
+        else MBPE_BY_MODE(v.endbit, hipLaunchKernelGGL((k_fused_batch<M, HOT, TT, 0, false>), grid, block, 0, v.stream, MBPE_FUSED_ARGS)); \
+    }
+    MBPE_FUSED_INST(false, false)
+    if (may_split)
+        hipLaunchKernelGGL(k_tt_split_plan, dim3(1), dim3(kWave), 0, v.stream, v.ctl, b.bs, b.dlog ? b.ls : nullptr, tt_split,
+                           v.n_tiles);
+    MBPE_FUSED_INST(true, false)
+    MBPE_FUSED_INST(false, true)
+    MBPE_FUSED_INST(true, true)
+#undef MBPE_FUSED_INST
+    if (may_split) {
+        hipLaunchKernelGGL(k_tt_split_restore, dim3(1), dim3(kWave), 0, v.stream, v.ctl, b.bs);
+        const dim3 lgrid(tile_grid(v.n_tiles, v.n_cus, 1, kLutThreads));
+        MBPE_BY_MODE(v.endbit, {
+            hipLaunchKernelGGL((k_fused_batch<M, false, false, 0, false, true>), grid, block, 0, v.stream, v.tok, v.tok_other,
+                               v.sums, v.side, v.n_tiles, v.tile_list, b.bs, b.hdr_adj, b.LR, v.ctl, v.left_edge, v.right_edge,
+                               b.hdr_m, v.run_in, hot_launched, b.dlog, b.ls);
+            hipLaunchKernelGGL((k_fused_tt_list<M>), lgrid, block, 0, v.stream, v.tok, v.tok_other, v.sums, v.side, v.n_tiles,
+                               v.tile_list, b.bs, b.hdr_adj, b.LR, v.ctl, v.left_edge, v.right_edge, b.hdr_m, v.run_in);
+        });
+    }
 #undef MBPE_FUSED_ARGS
 }
 
@@ -5014,7 +5196,10 @@ void launch_rewrite_marked(const StreamView &v, const BatchView &b, const Inst &
 // What the selection of the sequence under way decided, for a host that enqueues only the kernels this sequence needs
 // (small corpora, train.cpp: lockstep): merges done, pairs in the batch, fused pass or not, a (t,t) pair in it, and whether
 // the pass is the frequent-pair instantiation's (dc_wanted, exactly as the stream kernels decide it).
-__global__ void k_seq_info(const DevCtl *ctl, const BatchState *bs, const unsigned long long *best, uint32_t *out) {
+__global__ __launch_bounds__(kWave) void k_seq_info(const DevCtl *ctl, const BatchState *bs, const unsigned long long *best,
+                                                    uint32_t *out, int tt_split, uint32_t n_tiles) {
+    // (a fused pass with (t,t) members may take the split route: k_tt_split_plan, which also hears the delta log)
+    const bool split = tt_split_wanted(ctl, bs, tt_split, n_tiles);
     if (blockIdx.x || threadIdx.x) return;
     const uint32_t n = ctl->batch_n;
     unsigned long long top = 0;
@@ -5035,11 +5220,11 @@ __global__ void k_seq_info(const DevCtl *ctl, const BatchState *bs, const unsign
     out[4] = dc_wanted(top, ctl->n_live * ctl->n_ranks) ? 1u : 0u;
     out[5] = ctl->k_limit;
     out[6] = ctl->sel_ok;            // (the selection's first attempt chose the batch: the others are not needed)
-    out[7] = 0;
+    out[7] = split ? 1u : 0u;
 }
 
-void launch_seq_info(const StreamView &v, const BatchView &b, const unsigned long long *best, uint32_t *out) {
-    hipLaunchKernelGGL(k_seq_info, dim3(1), dim3(64), 0, v.stream, v.ctl, b.bs, best, out);
+void launch_seq_info(const StreamView &v, const BatchView &b, const unsigned long long *best, uint32_t *out, int tt_split) {
+    hipLaunchKernelGGL(k_seq_info, dim3(1), dim3(kWave), 0, v.stream, v.ctl, b.bs, best, out, tt_split, v.n_tiles);
 }
 
 void launch_seq_finish(const StreamView &v, const BatchView &b, uint32_t *fused_flag) {

@@ -150,7 +150,13 @@ struct DevCtl {
     uint32_t log_refills;       // chunks taken by waves that had used one up before (statistics)
     uint32_t log_refused;       // (k_log_plan) the pass under way would have logged, but its pairs' counts exceed the
                                 //   partition buffer: it says nothing about the share of byte neighbours (k_seq_finish)
-
+    // ---- (t,t) members of a byte batch: the split route (kernels.hip: k_tt_split_plan) ----
+    uint32_t tt_split;          // (k_tt_split_plan) the fused pass under way runs plain and defers the tiles that hold a run
+                                //   of a member's token to the list pass
+    uint32_t tt_list_n;         // tiles deferred so far (entries of the tile list)
+    uint32_t tt_saved_index;    // BatchState::tt_index while the plan keeps it from the whole-stream instantiations
+    uint32_t n_tt_split;        // passes that took the split route (statistics)
+    unsigned long long tt_deferred_tiles;      // tiles they handed to the list pass (statistics)
 };
 
 // A batch holds up to kBatchMax pairs that can be merged in ONE pass over the
@@ -219,6 +225,10 @@ struct BatchState {
     uint32_t adj_out[kBatchMax];  // sum_q ADJ[j][q]
     // (t,t) members (at most kTTMax per batch, in batch order): index and token of the first one (kNoTT: none) and
     // their number; their matches are every second token of a run of t, see tt_rename in kernels.hip
+    // CAUTION: for a pass that takes the split route, tt_index reads kNoTT between k_tt_split_plan and
+    // k_tt_split_restore (launch_fused_batch: the whole-stream (t,t) instantiations are dispatched there and return
+    // because of it; the true value waits in DevCtl::tt_saved_index).  Only those instantiations may be enqueued
+    // between the two: any other reader of tt_index, tt_token or tt_n would take the batch for one without members.
     uint32_t tt_index;
     uint32_t tt_token;
     uint32_t tt_n;
@@ -254,6 +264,8 @@ constexpr uint32_t kErrCountRange  = 8u;   // a pair count does not fit 31 bits 
 constexpr uint32_t kErrHotSkipped  = 16u;  // a pass needed the frequent-pair instantiation of a stream kernel, which the host
                                            //   had ruled out and not launched (kernels.hip: hot_mismatch)
 constexpr uint32_t kErrLog         = 32u;  // the delta log held more records of a bucket than its pairs' counts allow
+constexpr uint32_t kErrTTSplit     = 64u;  // the deferring pass or the list pass of the split route started while
+                                           //   BatchState::tt_index was still hidden (k_tt_split_restore has not run)
 
 // packed argmax word: (count << 32) | ~key  -- larger is better:
 // count descending, then key ascending == (first, second) ascending,
@@ -300,9 +312,11 @@ struct BatchView {
 // frequent pair (delta cache) yes / no, and each returns at once unless the pass is its case.  Not known: all of them, the
 // frequent-pair ones only if `hot` (0: they cannot be needed).  Known (launch_seq_info told the host): exactly the one
 // with this `tt` and `hot`.  `hot` is also what the kernels are told was launched (kErrHotSkipped: hot_mismatch).
-struct Inst { bool known, tt, hot; };
-inline Inst inst_any(bool hot_possible) { return Inst{false, false, hot_possible}; }
-inline Inst inst_known(bool tt, bool hot) { return Inst{true, tt, hot}; }
+// `split` (known only): the fused pass of this batch may take the split route of its (t,t) members (k_tt_split_plan).
+struct Inst { bool known, tt, hot, split; };
+inline Inst inst_any(bool hot_possible) { return Inst{false, false, hot_possible, false}; }
+inline Inst inst_known(bool tt, bool hot, bool split = false) { return Inst{true, tt, hot, split}; }
+inline bool inst_may_split(const Inst &w) { return !w.known || (w.tt && !w.hot && w.split); }
 // is the (tt, hot) instantiation among those `w` enqueues / any that handles a (t,t) pair?
 inline bool inst_takes(const Inst &w, bool tt, bool hot) { return w.known ? w.tt == tt && w.hot == hot : !hot || w.hot; }
 inline bool inst_may_tt(const Inst &w) { return !w.known || w.tt; }
@@ -386,7 +400,9 @@ void launch_select_batch(const StreamView &v, const BatchView &b, PairTable t, u
 // small batch: count the deltas and mark the tiles (the rewrite follows validation)
 void launch_scan_batch(const StreamView &v, const BatchView &b, const Inst &w);
 // large batch (ctl->fused): count the deltas and write the merged stream to the other buffer
-void launch_fused_batch(const StreamView &v, const BatchView &b, const Inst &w);
+// tt_split: the option of that name (mbpe.h) -- with it the plan, the deferring pass and the list pass of the split route
+// are enqueued next to the whole-stream instantiations (v.tile_list is their list)
+void launch_fused_batch(const StreamView &v, const BatchView &b, const Inst &w, int tt_split);
 // the delta log before / behind the pass (see BatchView; nothing to do without the log)
 void launch_log_plan(const StreamView &v, const BatchView &b);
 void launch_log_consume(const StreamView &v, const BatchView &b);
@@ -397,8 +413,9 @@ void launch_batch_tables(const StreamView &v, const BatchView &b, PairTable t, u
 void launch_rewrite_marked(const StreamView &v, const BatchView &b, const Inst &w);
 // what the selection decided, for a host that enqueues only the kernels a sequence needs: out[0] merges done, [1] pairs
 // in the batch, [2] fused pass, [3] a (t,t) pair among them, [4] frequent-pair instantiation, [5] merge limit,
-// [6] the batch was chosen by a gather + pick attempt (0 after the first attempt alone: enqueue the others and the fallback)
-void launch_seq_info(const StreamView &v, const BatchView &b, const unsigned long long *best, uint32_t *out);
+// [6] the batch was chosen by a gather + pick attempt (0 after the first attempt alone: enqueue the others and the fallback),
+// [7] its fused pass may take the split route of (t,t) members (tt_split: the option; the delta log has its say later)
+void launch_seq_info(const StreamView &v, const BatchView &b, const unsigned long long *best, uint32_t *out, int tt_split);
 // fused_flag (optional, 4 words): [0] = 1 when this sequence ran the fused pass, [1..2] = live tokens of the shard after
 // the sequence, [3] = merges it committed
 void launch_seq_finish(const StreamView &v, const BatchView &b, uint32_t *fused_flag);

@@ -225,6 +225,8 @@ struct mbpe_ctx {
     LogState h_log = {};            // what mbpe_train_begin sets the device's LogState to
     int64_t opt_lockstep = -1;      // small corpora: the host waits for every selection and enqueues only the kernels that
                                     //   sequence needs (-1: when the stream is short enough, 0 never, 1 always)
+    int64_t opt_tt_split = -1;      // fused passes of byte batches with (t,t) members: plain pass + list pass (mbpe.h:
+                                    //   -1 where the members' runs are rare, 0 never, 1 wherever the route exists)
     hipEvent_t ev_sel = nullptr;
     std::vector<hipEvent_t> kev;    // event pool for opt_time_kernels
     std::vector<hipEvent_t> kev_f;  // ... around the fused pass alone
@@ -268,7 +270,8 @@ int sync_ctl(mbpe_ctx *c) {
         char buf[320];
         snprintf(buf, sizeof(buf), "device error flags 0x%x (1=pair table full, 2=negative count, 4=missing pair, "
                                    "8=a pair occurs 2^31 times or more, or the byte-pair counts do not add up to the "
-                                   "pairs scanned (a count reached 2^32), 16=a stream pass was skipped, 32=delta log overflow)",
+                                   "pairs scanned (a count reached 2^32), 16=a stream pass was skipped, 32=delta log overflow, "
+                                   "64=the split pass ran without its (t,t) members)",
                  c->h_ctl.err);
         mbpe_host::set_last_error(buf);
         return MBPE_ERR_OVERFLOW;
@@ -576,6 +579,7 @@ int mbpe_set_option(mbpe_ctx *c, const char *name, int64_t value) {
     else if (n == "sel_cap") c->opt_sel_cap = std::min<int64_t>(std::max<int64_t>(64, value), kSelCap);
     else if (n == "byte_table") c->opt_byte_table = value != 0;
     else if (n == "lockstep") c->opt_lockstep = value < 0 ? -1 : value != 0;
+    else if (n == "tt_split") c->opt_tt_split = value < 0 ? -1 : value != 0;
     else if (n == "pair_cells") c->opt_pair_cells = value < 0 ? -1 : value != 0;      // (read by the next mbpe_train_begin)
     else if (n == "log_cap") c->opt_log_cap = value < 0 ? 0 : std::min<int64_t>(value, 1ll << 29);       // (likewise; 0: default)
     else if (n == "log_chunk") c->opt_log_chunk = value < 0 ? 0 : std::min<int64_t>(value, 1ll << 16);   // (likewise)
@@ -1337,7 +1341,7 @@ static int seq_lockstep(mbpe_ctx *c, int ev_slot, bool *nothing_left) {
     launch_select_batch(v, b, c->tab, c->best, sa, stepwise ? 1 : c->sel_attempts, 0, !stepwise);
     if (!c->d_seq_info) HIPCHK(hipMalloc(&c->d_seq_info, 32));
     for (int round = 0;; ++round) {
-        launch_seq_info(v, b, c->best, c->d_seq_info);
+        launch_seq_info(v, b, c->best, c->d_seq_info, (int)c->opt_tt_split);
         HIPCHK(hipMemcpyAsync(c->h_seq + 8, c->d_seq_info, 32, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipEventRecord(c->ev_sel, c->stream));
         HIPCHK(hipEventSynchronize(c->ev_sel));
@@ -1345,7 +1349,7 @@ static int seq_lockstep(mbpe_ctx *c, int ev_slot, bool *nothing_left) {
         launch_select_batch(v, b, c->tab, c->best, sa, 3, 1, true);
     }
     const uint32_t batch_n = c->h_seq[9], fused = c->h_seq[10];
-    const Inst w = inst_known(c->h_seq[11] != 0, c->h_seq[12] != 0);
+    const Inst w = inst_known(c->h_seq[11] != 0, c->h_seq[12] != 0, c->h_seq[15] != 0);
     if (ev_slot >= 0) { (void)hipEventRecord(c->kev[2 * ev_slot], c->stream); (void)hipEventRecord(c->kev_f[2 * ev_slot], c->stream); }
     if (batch_n == 0) {                        // the merge limit is reached (or the table is empty): nothing to enqueue
         if (ev_slot >= 0) { (void)hipEventRecord(c->kev_f[2 * ev_slot + 1], c->stream); (void)hipEventRecord(c->kev[2 * ev_slot + 1], c->stream); }
@@ -1359,7 +1363,7 @@ static int seq_lockstep(mbpe_ctx *c, int ev_slot, bool *nothing_left) {
         //  ordinary enqueue-everything flow)
         if (w.tt) launch_run_lengths(v, b.bs, c->best, 1);
         launch_log_plan(v, b);
-        if (fused) launch_fused_batch(v, b, w);
+        if (fused) launch_fused_batch(v, b, w, (int)c->opt_tt_split);
         else launch_scan_batch(v, b, w);
         launch_log_consume(v, b);
     }
@@ -1395,7 +1399,7 @@ static int seq_stage_a(mbpe_ctx *c, int ev_slot) {       // up to the delta exch
     launch_log_plan(v, b);
     launch_scan_batch(v, b, w);
     if (ev_slot >= 0) (void)hipEventRecord(c->kev_f[2 * ev_slot], c->stream);
-    launch_fused_batch(v, b, w);
+    launch_fused_batch(v, b, w, (int)c->opt_tt_split);
     // (the logged records become L / R counts before anything reads the rows: the exchange of several ranks, validation,
     //  apply.  Inside the events: the log's consumers are part of what the pass costs)
     launch_log_consume(v, b);
@@ -2077,6 +2081,8 @@ int mbpe_get_stats(mbpe_ctx *c, mbpe_stats *out) {
     c->stats.log_spilled = c->begun ? c->h_ctl.log_spilled : 0;
     c->stats.log_passes = c->begun ? c->h_ctl.log_passes : 0;
     c->stats.log_refills = c->begun ? c->h_ctl.log_refills : 0;
+    c->stats.n_tt_split = c->begun ? c->h_ctl.n_tt_split : 0;
+    c->stats.tt_deferred_tiles = c->begun ? c->h_ctl.tt_deferred_tiles : 0;
     c->stats.n_sel_retry = c->begun ? c->h_ctl.n_sel_retry : 0;
     c->stats.adapt_limit = c->begun ? c->h_ctl.adapt_limit : 0;
     c->stats.n_sel_blocks = c->begun ? c->h_ctl.n_sel_blocks : 0;

@@ -95,6 +95,7 @@ class Stats(ctypes.Structure):
         ("exchange_words", ctypes.c_uint64), ("exchanges", ctypes.c_uint32), ("log_spilled", ctypes.c_uint32),
         ("fused_live_tokens", ctypes.c_uint64), ("ms_pair_count_kernel", ctypes.c_float), ("log_passes", ctypes.c_uint32),
         ("log_refills", ctypes.c_uint32), ("pad3_", ctypes.c_uint32),
+        ("n_tt_split", ctypes.c_uint32), ("pad4_", ctypes.c_uint32), ("tt_deferred_tiles", ctypes.c_uint64),
     ]
 
     def as_dict(self):
