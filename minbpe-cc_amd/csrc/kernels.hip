@@ -21,6 +21,7 @@
 // needs a workgroup barrier.  Waves walk the tiles with a grid stride and
 // prefetch their next tile while working on the current one.
 #include "mbpe_dev.h"
+#include "run_before.h"
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -1121,14 +1122,28 @@ __device__ __forceinline__ RunSeg run_chunk_join(const TileSum *sin, uint32_t n_
     return mine;
 }
 
+// A fused pass that takes the split route (k_tt_split_plan) asks for the run before a fraction of a percent of the tiles:
+// its list pass walks back from each of them (run_before_tile_wave) and the scan over every tile is skipped.  The run
+// kernels are enqueued before the plan, so they ask what the plan will ask: tt_split_wanted and the delta log's say
+// (k_log_plan runs before them).  k_run_final leaves DevCtl::run_skipped for whoever else reads run_in in this sequence.
+// (every wave evaluates it: tt_split_wanted is a whole-wave function)
+__device__ __forceinline__ bool tt_split_wanted(const DevCtl *ctl, const BatchState *bs, int mode, uint32_t n_tiles);
+__device__ __forceinline__ bool run_scan_skipped(const DevCtl *ctl, const BatchState *bs, const LogState *ls, int seq,
+                                                 int tt_mode, uint32_t n_tiles) {
+    if (!seq || bs == nullptr || tt_mode == 0) return false;
+    return tt_split_wanted(ctl, bs, tt_mode, n_tiles) && !(ls != nullptr && ls->on != 0u);
+}
+
 __global__ __launch_bounds__(kRunThreads) void k_run_partial(const TileSum *__restrict__ sin, uint32_t n_tiles,
                                                              const unsigned long long *best_ptr, const DevCtl *ctl,
                                                              int seq, const BatchState *bs,
-                                                             unsigned long long *__restrict__ part) {
+                                                             unsigned long long *__restrict__ part, const LogState *ls,
+                                                             int tt_mode) {
     __shared__ unsigned long long segs[kRunChunk];
     __shared__ unsigned long long sh[kRunThreads];
     const uint32_t t = run_token(best_ptr, ctl, seq, bs);
     if (t == 0xFFFFFFFFu) return;
+    if (run_scan_skipped(ctl, bs, ls, seq, tt_mode, n_tiles)) return;
     run_chunk_join(sin, n_tiles, (uint64_t)blockIdx.x * kRunChunk, segs, sh);
     if (threadIdx.x == 0) {
         RunSeg acc = run_none();
@@ -1138,15 +1153,20 @@ __global__ __launch_bounds__(kRunThreads) void k_run_partial(const TileSum *__re
 }
 
 __global__ __launch_bounds__(kRunThreads) void k_run_final(const TileSum *__restrict__ sin, uint32_t n_tiles,
-                                                           const unsigned long long *best_ptr, const DevCtl *ctl,
+                                                           const unsigned long long *best_ptr, DevCtl *ctl,
                                                            int seq, const BatchState *bs,
                                                            const unsigned long long *__restrict__ part,
-                                                           const RankEdge *le, uint32_t *__restrict__ run_in) {
+                                                           const RankEdge *le, uint32_t *__restrict__ run_in,
+                                                           const LogState *ls, int tt_mode) {
     __shared__ unsigned long long segs[kRunChunk];
     __shared__ unsigned long long sh[kRunThreads];
     __shared__ unsigned long long pre[kRunThreads];
     const uint32_t t = run_token(best_ptr, ctl, seq, bs);
     if (t == 0xFFFFFFFFu) return;
+    if (run_scan_skipped(ctl, bs, ls, seq, tt_mode, n_tiles)) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) ctl->run_skipped = 1u;     // (run_in keeps an earlier sequence's values)
+        return;
+    }
     // everything before this chunk: each thread joins a slice of the chunk aggregates, thread 0 the slices
     const uint32_t nb = blockIdx.x, per = (nb + kRunThreads - 1) / kRunThreads;
     RunSeg acc = run_none();
@@ -1180,6 +1200,38 @@ __global__ __launch_bounds__(kRunThreads) void k_run_final(const TileSum *__rest
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < kRunChunk; i += kRunThreads)
         if (base + i < n_tiles) run_in[base + i] = (uint32_t)segs[i];
+}
+
+// run_in[tile] without the scan (run_before.h: the same walk), by the wave that holds the tile.  `smw` carries the summary
+// of tile - 1 in lanes 0..3 (tile_issue; zeros, an empty tile, for tile 0): unless that tile is one whole run or empty, its
+// trailing run is the answer and nothing is loaded.  Otherwise the wave walks back, 64 summaries per load, and takes
+// them one by one until the run ends -- exact for any input, and short for a split pass: its members' counts are below
+// one per 16 tiles, and compaction bounds stretches of empty tiles.  Uniform result.
+__device__ __forceinline__ uint32_t run_before_tile_wave(uint32_t smw, const TileSum *sin, uint32_t n_tiles, uint32_t tile,
+                                                         const RankEdge *le) {
+    RunWalk w = run_walk_begin();
+    uint32_t next = tile < n_tiles ? tile : n_tiles;       // the tiles below `next` have not been looked at
+    bool go = next > 0u;
+    if (go) {
+        const uint32_t w1 = rlane(smw, 1), w2 = rlane(smw, 2);
+        go = run_walk_take(w, w1 >> 16, w2 >> 16, w2 & 0xFFFFu);
+        next -= 1u;
+    }
+    const uint32_t lane = lane_id();
+    while (go && next > 0u) {
+        const uint32_t n = next < (uint32_t)kWave ? next : (uint32_t)kWave;
+        uint32_t w1 = 0, w2 = 0;              // lane k: tile next - 1 - k (tail1 | tail0 << 16, n_live | tail_run << 16)
+        if (lane < n) {
+            const uint4 q = reinterpret_cast<const uint4 *>(sin)[next - 1u - lane];
+            w1 = q.y, w2 = q.z;
+        }
+        for (uint32_t k = 0; k < n && go; ++k) {
+            const uint32_t a = rlane(w1, k), b = rlane(w2, k);
+            go = run_walk_take(w, a >> 16, b >> 16, b & 0xFFFFu);
+        }
+        next -= n;
+    }
+    return run_walk_result(w, le);
 }
 
 __global__ __launch_bounds__(kMergeThreads) void k_summarize(const uint16_t *__restrict__ tok,
@@ -3531,8 +3583,7 @@ __global__ __launch_bounds__(kLutThreads) void k_fused_tt_list(uint16_t *tok0, u
                                                                  TileSum *__restrict__ sout, uint32_t n_tiles,
                                                                  const uint32_t *__restrict__ list, const BatchState *bs,
                                                                  uint32_t *hdr_adj, uint32_t *LR, DevCtl *ctl,
-                                                                 const RankEdge *le, const RankEdge *re, uint32_t *hdr_m,
-                                                                 const uint32_t *__restrict__ run_in) {
+                                                                 const RankEdge *le, const RankEdge *re, uint32_t *hdr_m) {
     constexpr uint32_t idmask = MODE == 1 ? 0x7FFFu : 0xFFFFu;
     __shared__ BatchLutMem lut_mem;
     __shared__ TTInfo ti;
@@ -3593,7 +3644,8 @@ __global__ __launch_bounds__(kLutThreads) void k_fused_tt_list(uint16_t *tok0, u
                                                         no_dc, false, wave_rm, wrote_sum, lr_rsrc, adj_pitch, stage, nullptr,
                                                         false, &ti, need_rename);
         if (need_rename) {           // (every listed tile, unless the list is stale)
-            tt_rename<MODE>(s, h, ti, run_in[tile]);
+            // (the run before the tile: the scan was skipped for this pass, see run_scan_skipped)
+            tt_rename<MODE>(s, h, ti, run_before_tile_wave(t0.smw, sin, n_tiles, tile, le));
             outq = fused_tile_pf<MODE, 0, true, true>(t0.q, s, h, old_x, old_y, old_z, lut, X0, tile, sout, hdr_adj, LR,
                                                       no_dc, false, wave_rm, wrote_sum, lr_rsrc, adj_pitch, stage, nullptr,
                                                       true, &ti, need_rename);
@@ -4255,6 +4307,8 @@ __global__ __launch_bounds__(kLutThreads) void k_rewrite_marked(uint16_t *tok0, 
     const uint32_t X0 = 256u + ctl->k_done;
     const uint32_t n_list = ctl->n_marked;
     const bool marks_all = ctl->marks_all != 0u;
+    // (an abandoned split pass: the run scan was skipped for it, and the runs are walked as its list pass walked them)
+    const bool walk_runs = TT && ctl->run_skipped != 0u;
     BatchLut lut(&lut_mem, bs, idmask);
     lut_build(lut, bs, n_keys, idmask - 1u);
     if (TT) tt_build(ti, bs, n_keys, idmask - 1u);
@@ -4295,7 +4349,7 @@ __global__ __launch_bounds__(kLutThreads) void k_rewrite_marked(uint16_t *tok0, 
         bool wrote = false;          // uniform: the tile changed (its new summary is in the side array)
         bool no_rename = false;
         DeltaCacheSmall no_dc;       // (never touched: no deltas in this instantiation)
-        if (TT) tt_rename<MODE>(s, h, ti, run_in[tile]);
+        if (TT) tt_rename<MODE>(s, h, ti, walk_runs ? run_before_tile_wave(t0.smw, sin, n_tiles, tile, le) : run_in[tile]);
         const uint4 qn = fused_tile_pf<MODE, 2, true, TT>(t0.q, s, h, rlane(t0.smw, 4), rlane(t0.smw, 5), rlane(t0.smw, 6), lut,
                                                           X0, tile, sout, nullptr, nullptr, no_dc, false, rm, wrote,
                                                           __amdgpu_buffer_rsrc_t(), 0u, stage, chg, TT, &ti, no_rename);
@@ -4349,6 +4403,7 @@ __global__ void k_seq_finish(DevCtl *ctl, uint32_t *fused_flag, const BatchState
     // (the split route's state is one pass's: a sequence whose host enqueues no plan must not see the last one's)
     ctl->tt_split = 0;
     ctl->tt_list_n = 0;
+    ctl->run_skipped = 0;
     // the delta log: once fewer than half of a large batch's matches lay between two raw bytes the stream is past the
     // stage where it pays (the share only falls as tokens replace bytes)
     // (a pass that k_log_plan kept from logging for want of room counted no such match: it has no say)
@@ -4982,21 +5037,22 @@ void launch_first_tiebreak(const StreamView &v, PairTable t, unsigned long long 
 }
 
 // runs of t before every tile, for the (t,t) pair of a single merge or the (t,t) member(s) of a batch
-void launch_run_lengths(const StreamView &v, const BatchState *bs, const unsigned long long *best, int seq) {
+void launch_run_lengths(const StreamView &v, const BatchView &b, const unsigned long long *best, int seq, int tt_split) {
     if (!v.n_tiles) return;
     const uint32_t n_chunks = (v.n_tiles + kRunChunk - 1) / kRunChunk;
+    const BatchState *bs = seq ? b.bs : nullptr;       // (a batch may hold a (t,t) member)
+    const LogState *ls = b.dlog ? b.ls : nullptr;      // (as k_tt_split_plan hears it)
     hipLaunchKernelGGL(k_run_partial, dim3(n_chunks), dim3(kRunThreads), 0, v.stream, v.sums, v.n_tiles, best, v.ctl, seq, bs,
-                       v.run_part);
+                       v.run_part, ls, tt_split);
     hipLaunchKernelGGL(k_run_final, dim3(n_chunks), dim3(kRunThreads), 0, v.stream, v.sums, v.n_tiles, best, v.ctl, seq, bs,
-                       v.run_part, v.left_edge, v.run_in);
+                       v.run_part, v.left_edge, v.run_in, ls, tt_split);
 }
 
 void launch_merge(const StreamView &v, const BatchView &b, const unsigned long long *best, uint32_t new_id,
-                  uint32_t *m_adj, int seq, const Inst &w) {
+                  uint32_t *m_adj, int seq, const Inst &w, int tt_split) {
     if (!v.n_tiles) return;
-    const BatchState *bs = seq ? b.bs : nullptr;       // (a batch may hold a (t,t) member)
     // runs of t before every tile, for a (t,t) pair (the kernels return at once for any other pair)
-    if (inst_may_tt(w)) launch_run_lengths(v, bs, best, seq);
+    if (inst_may_tt(w)) launch_run_lengths(v, b, best, seq, tt_split);
     static const int occ[3] = {resident_blocks(k_merge<0, false, 0>), resident_blocks(k_merge<1, false, 0>),
                                resident_blocks(k_merge<2, false, 0>)};
     const dim3 grid(tile_grid(v.n_tiles, v.n_cus, occ[slot_mode(v.endbit)])), block(kMergeThreads);
@@ -5107,13 +5163,16 @@ void launch_fused_batch(const StreamView &v, const BatchView &b, const Inst &w, 
 #undef MBPE_FUSED_INST
     if (may_split) {
         hipLaunchKernelGGL(k_tt_split_restore, dim3(1), dim3(kWave), 0, v.stream, v.ctl, b.bs);
+        // (the list pass, chip-wide: a wave takes ~12 us per listed tile, so the pass is bound by how many waves share
+        //  the list, not by the table every workgroup builds -- a grid sized to the list, with fewer and fuller workgroups,
+        //  measured 2.3 to 8 times slower: profiles/r34_tt_side_work.md)
         const dim3 lgrid(tile_grid(v.n_tiles, v.n_cus, 1, kLutThreads));
         MBPE_BY_MODE(v.endbit, {
             hipLaunchKernelGGL((k_fused_batch<M, false, false, 0, false, true>), grid, block, 0, v.stream, v.tok, v.tok_other,
                                v.sums, v.side, v.n_tiles, v.tile_list, b.bs, b.hdr_adj, b.LR, v.ctl, v.left_edge, v.right_edge,
                                b.hdr_m, v.run_in, hot_launched, b.dlog, b.ls);
             hipLaunchKernelGGL((k_fused_tt_list<M>), lgrid, block, 0, v.stream, v.tok, v.tok_other, v.sums, v.side, v.n_tiles,
-                               v.tile_list, b.bs, b.hdr_adj, b.LR, v.ctl, v.left_edge, v.right_edge, b.hdr_m, v.run_in);
+                               v.tile_list, b.bs, b.hdr_adj, b.LR, v.ctl, v.left_edge, v.right_edge, b.hdr_m);
         });
     }
 #undef MBPE_FUSED_ARGS

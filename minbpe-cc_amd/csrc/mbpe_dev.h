@@ -157,6 +157,9 @@ struct DevCtl {
     uint32_t tt_saved_index;    // BatchState::tt_index while the plan keeps it from the whole-stream instantiations
     uint32_t n_tt_split;        // passes that took the split route (statistics)
     unsigned long long tt_deferred_tiles;      // tiles they handed to the list pass (statistics)
+    uint32_t run_skipped;       // (k_run_final) the run scan of the sequence under way was skipped because its fused pass
+                                //   takes the split route: run_in is stale, whoever needs a run walks (run_before.h);
+                                //   k_seq_finish clears it
 };
 
 // A batch holds up to kBatchMax pairs that can be merged in ONE pass over the
@@ -369,10 +372,12 @@ void launch_first_tiebreak(const StreamView &v, PairTable t, unsigned long long 
 // (launch_apply folds them into sums).  seq != 0: the kernel runs inside a batch sequence: it reads the merge index
 // from ctl->k_done and returns at once unless the selected batch has one pair (which may be a (t,t) member of b.bs).
 // m_adj: the [m, adj] accumulators.  w.tt: the pair is a (t,t) pair (run kernels).
+// tt_split (seq != 0): the option of that name -- the run kernels return at once for a batch whose fused pass will take
+// the split route, so launch_log_plan must be on the stream BEFORE this (they ask what k_tt_split_plan will ask)
 void launch_merge(const StreamView &v, const BatchView &b, const unsigned long long *best, uint32_t new_id,
-                  uint32_t *m_adj, int seq, const Inst &w);
+                  uint32_t *m_adj, int seq, const Inst &w, int tt_split = 0);
 // the run kernels launch_merge starts with, alone (a host that enqueues a batch's pass by itself: train.cpp, lockstep)
-void launch_run_lengths(const StreamView &v, const BatchState *bs, const unsigned long long *best, int seq);
+void launch_run_lengths(const StreamView &v, const BatchView &b, const unsigned long long *best, int seq, int tt_split);
 
 // fold the merge's count deltas (L, R, m, adj) into the pair table; gm_gadj: the [m, adj] summed over the ranks, or NULL;
 // new_id: the id of the new token, or (seq != 0) an upper bound of it

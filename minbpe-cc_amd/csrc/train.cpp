@@ -1359,10 +1359,11 @@ static int seq_lockstep(mbpe_ctx *c, int ev_slot, bool *nothing_left) {
     if (batch_n == 1) {
         launch_merge(v, b, c->best, 0, &c->ctl->m, 1, w);
     } else {
-        // (a batch with a (t,t) member: the runs of its token before every tile, which launch_merge computes in the
-        //  ordinary enqueue-everything flow)
-        if (w.tt) launch_run_lengths(v, b.bs, c->best, 1);
         launch_log_plan(v, b);
+        // (a batch with a (t,t) member: the runs of its token before every tile, which launch_merge computes in the
+        //  ordinary enqueue-everything flow -- behind the log's plan: a fused pass that will take the split route skips
+        //  the scan, and whether it will hangs on the log too)
+        if (w.tt) launch_run_lengths(v, b, c->best, 1, fused ? (int)c->opt_tt_split : 0);
         if (fused) launch_fused_batch(v, b, w, (int)c->opt_tt_split);
         else launch_scan_batch(v, b, w);
         launch_log_consume(v, b);
@@ -1395,8 +1396,9 @@ static int seq_stage_a(mbpe_ctx *c, int ev_slot) {       // up to the delta exch
     }
     if (ev_slot >= 0) (void)hipEventRecord(c->kev[2 * ev_slot], c->stream);
     // (the [m, adj] of a single pair: with several ranks in the exchange header, which is summed over them)
-    launch_merge(v, b, c->best, 0, is_multi(c) ? c->xb : &c->ctl->m, 1, w);
+    // (the log's plan first: the run kernels of launch_merge ask it whether the fused pass will take the split route)
     launch_log_plan(v, b);
+    launch_merge(v, b, c->best, 0, is_multi(c) ? c->xb : &c->ctl->m, 1, w, (int)c->opt_tt_split);
     launch_scan_batch(v, b, w);
     if (ev_slot >= 0) (void)hipEventRecord(c->kev_f[2 * ev_slot], c->stream);
     launch_fused_batch(v, b, w, (int)c->opt_tt_split);
