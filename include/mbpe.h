@@ -488,6 +488,20 @@ MBPE_API int mbpe_compact(mbpe_ctx *ctx);
  *                   0 .. 1,048,576 (beyond: MBPE_ERR_ARG): the longest stream "resident" takes on.  One workgroup walks
  *                   it per merge, so beyond some length the launches over the whole chip win again; the default is
  *                   where that was measured (profiles/r32_train_resident.md), 0 = never.
+ *   "regions"       0 (default) | 1; any other value is MBPE_ERR_ARG.  The second speed option of the 32-bit loop, for
+ *                   streams that outnumber the one workgroup of "resident": with 1, a group of merges runs on regions of
+ *                   whole chunks that waves own and rewrite in place (csrc/wide_regions.h) -- two launches per merge,
+ *                   four with the `first` tie-break, and three more per group, instead of seven to ten per merge.  Never
+ *                   changes a merge, a count, the stream or the pair table.  With 0 nothing is allocated or launched
+ *                   differently; with 1, 1 MiB of device memory for the regions.  Read by every mbpe_train_steps; a
+ *                   group runs in regions when the training has no stopping rule ("min_frequency", "max_token_length":
+ *                   those keep the launches), the stream holds at most 2^26 tokens at that moment and no chunk is
+ *                   longer than 65,536 tokens (found by the first group's cutter; that group's launches then do
+ *                   nothing).  Where "resident" is on as well and takes the stream, resident runs: a training moves
+ *                   from regions to resident as its stream shrinks.  One rank.
+ *   "region_tokens" 64 .. 65,536 (outside: MBPE_ERR_ARG): about how many tokens a region of "regions" holds, before its
+ *                   ends move to chunk ends; a stream of more than 65,536 times as many gets larger regions.  The
+ *                   default, 256, is the best of a sweep on 110,918 tokens (profiles/r35_train_regions.md).
  */
 MBPE_API int mbpe_set_option(mbpe_ctx *ctx, const char *name, int64_t value);
 
@@ -497,6 +511,11 @@ MBPE_API int mbpe_set_option(mbpe_ctx *ctx, const char *name, int64_t value);
  * out pointer may be NULL. */
 MBPE_API int mbpe_train_resident_stats(mbpe_ctx *ctx, uint64_t *n_merges_resident_out, uint64_t *n_launches_out,
                                        uint64_t *n_slices_rescanned_out);
+/* What "regions" did in the training under way or just finished: the merges made by its groups (the zero-count tail of
+ * a lexical training that ended in them included), those groups, and the regions of the latest one.  All zero: nothing
+ * ran in regions.  Any out pointer may be NULL. */
+MBPE_API int mbpe_train_regions_stats(mbpe_ctx *ctx, uint64_t *n_merges_regions_out, uint64_t *n_groups_out,
+                                      uint64_t *n_regions_last_out);
 /* DIAGNOSTICS, for tools/train_resident_time.py; not part of the training interface and free to change.  Where the
  * kernel spent its time, in wall-clock ticks of 10 ns summed over the launches: the argmax, the `first` position
  * search, the walks over the stream.  Thread 0 reads the clock at the three phase boundaries of every merge. */

@@ -306,6 +306,13 @@ MBPE_API int mbpe_tok_set_train_limits(mbpe_tokenizer *t, int64_t min_frequency,
  * merges, counts, .model and .vocab.  With stopping rules set the loop keeps its launches. */
 MBPE_API int mbpe_tok_set_train_resident(mbpe_tokenizer *t, int on);
 
+/* Likewise the training context's option "regions" (mbpe.h): 0 (the default) or 1; anything else is MBPE_ERR_ARG.  Where
+ * a training runs the 32-bit loop -- with mbpe_tok_set_train_dedup, from word counts, with the `first` tie-break or
+ * continued -- its merges then run on wave-owned regions of the stream, two to four kernel launches per merge instead
+ * of seven to ten.  "region_tokens" stays at its default.  Same merges, counts, .model and .vocab.  With stopping rules
+ * set, or a chunk of more than 65,536 tokens, the loop keeps its launches. */
+MBPE_API int mbpe_tok_set_train_regions(mbpe_tokenizer *t, int on);
+
 /* Encoding through the distinct chunks: 0 (the default) or 1; anything else is MBPE_ERR_ARG.  While it is on,
  * mbpe_tok_encode_device and the three batch calls (mbpe_tok_encode_batch_device, _batch_packed_device,
  * _batch_aux_device) run the kept device encoder with its option "dedup" (mbpe.h: the chunks are deduplicated on the

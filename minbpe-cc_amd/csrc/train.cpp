@@ -245,6 +245,8 @@ struct mbpe_ctx {
     int64_t opt_max_token_length = 0;   // on 32-bit tokens from its first new merge, like one on a weighted corpus
     int64_t opt_resident = 0;        // 1: the 32-bit loop runs short streams in one workgroup (wide_resident.h)
     int64_t opt_resident_max = kResidentMaxDefault;   // ... "resident_max_tokens": what a short stream is
+    int64_t opt_regions = 0;         // 1: the 32-bit loop runs groups of merges on wave-owned regions (wide_regions.h)
+    int64_t opt_region_tokens = kRegTokensDefault;    // ... "region_tokens": about how many tokens a region holds
     bool wide_direct = false;        // the training began on 32-bit tokens (begin_wide_direct): no slot stream, no best[]
     std::vector<uint32_t> h_prior_raw;   // ... and its prior merges, (a, b) as given: their ids may need more than 16 bits
 
@@ -256,7 +258,8 @@ namespace {
 
 // what the 32-bit loop's calls get of the context
 WideDev wide_dev(mbpe_ctx *c) {
-    return WideDev{c->stream, c->ev0, c->ev1, c->pool, c->n_cus, c->stats, c->opt_resident != 0, (uint64_t)c->opt_resident_max};
+    return WideDev{c->stream, c->ev0, c->ev1, c->pool, c->n_cus, c->stats, c->opt_resident != 0, (uint64_t)c->opt_resident_max,
+                   c->opt_regions != 0, (uint32_t)c->opt_region_tokens};
 }
 
 int sync_ctl(mbpe_ctx *c) {
@@ -610,6 +613,17 @@ int mbpe_set_option(mbpe_ctx *c, const char *name, int64_t value) {
             return MBPE_ERR_ARG;
         }
         c->opt_resident_max = value;
+    }
+    else if (n == "regions") {                                                 // (read by every mbpe_train_steps)
+        if (value != 0 && value != 1) { mbpe_host::set_last_error("regions: 0 or 1"); return MBPE_ERR_ARG; }
+        c->opt_regions = value;
+    }
+    else if (n == "region_tokens") {                                           // (likewise)
+        if (value < (int64_t)kRegTokensMin || value > (int64_t)kRegTokensMax) {
+            mbpe_host::set_last_error("region_tokens: " + std::to_string(kRegTokensMin) + " .. " + std::to_string(kRegTokensMax));
+            return MBPE_ERR_ARG;
+        }
+        c->opt_region_tokens = value;
     }
     else if (n == "pc_repeat") c->opt_pc_repeat = std::min<int64_t>(std::max<int64_t>(1, value), 1000);
     else { mbpe_host::set_last_error("unknown option " + n); return MBPE_ERR_ARG; }
@@ -2103,6 +2117,15 @@ int mbpe_train_resident_stats(mbpe_ctx *c, uint64_t *n_merges_resident_out, uint
     if (n_merges_resident_out) *n_merges_resident_out = c->wr.res_merges;
     if (n_launches_out) *n_launches_out = c->wr.res_launches;
     if (n_slices_rescanned_out) *n_slices_rescanned_out = c->wr.h_res.n_rescanned;
+    return MBPE_OK;
+}
+
+// what the option "regions" did in the training under way or just finished (zeros: nothing ran in regions)
+int mbpe_train_regions_stats(mbpe_ctx *c, uint64_t *n_merges_regions_out, uint64_t *n_groups_out, uint64_t *n_regions_last_out) {
+    if (!c) return MBPE_ERR_ARG;
+    if (n_merges_regions_out) *n_merges_regions_out = c->wr.reg_merges;
+    if (n_groups_out) *n_groups_out = c->wr.reg_groups;
+    if (n_regions_last_out) *n_regions_last_out = c->wr.reg_regions_last;
     return MBPE_OK;
 }
 

@@ -168,6 +168,10 @@ void launch_wide_argmax(hipStream_t s, WideTable t, WideCtl *ctl, WideBest *best
 // lim: what launch_wide_argmax was given
 void launch_wide_first(hipStream_t s, const uint32_t *src, uint64_t n_upper, WideTable t, WideCtl *ctl, WideBest *best,
                        const unsigned long long *scratch, WideFirst *fs, WideLimits lim = WideLimits{});
+// its first stage alone, k_wide_first_gather: fs->n_tie and the bitmap of the pairs whose count is ctl->count (the
+// regions of wide_regions.h search the stream their own way)
+void launch_wide_first_gather(hipStream_t s, WideTable t, const WideCtl *ctl, const unsigned long long *scratch,
+                              WideFirst *fs, WideLimits lim = WideLimits{});
 // one merge (ctl->a, ctl->b) -> new_id_base + ctl->k over the stream src (ctl->n tokens, at most n_upper) into dst;
 // advances ctl->k, sets ctl->n.  Does nothing when ctl->k >= ctl->k_limit or the table is empty.
 // wsrc / wdst: NULL, or the weights of the tokens of src and the array that receives those of dst.

@@ -189,7 +189,7 @@ __device__ __forceinline__ void wide_new_len(const WideLimits &lim, const WideCt
     lim.len[lim.new_id_base + ctl->k] = l < kWideLenMax ? l : kWideLenMax;
 }
 
-constexpr int kArgBlocks = 1024;
+constexpr int kArgBlocks = kWideArgBlocks;
 // LIM: only eligible pairs.  A pair is tested once it beats the thread's best so far, so the two gathers of the test
 // are paid a few times per thread, not per entry (unless ineligible pairs lead the table, where every leader is
 // tested once).
@@ -590,13 +590,19 @@ void launch_wide_argmax(hipStream_t s, WideTable t, WideCtl *ctl, WideBest *best
         hipLaunchKernelGGL(k_wide_argmax_final<false>, dim3(1), dim3(kArgBlocks), 0, s, scratch, ctl, best, lim);
 }
 
-void launch_wide_first(hipStream_t s, const uint32_t *src, uint64_t n_upper, WideTable t, WideCtl *ctl, WideBest *best,
-                       const unsigned long long *scratch, WideFirst *fs, WideLimits lim) {
+void launch_wide_first_gather(hipStream_t s, WideTable t, const WideCtl *ctl, const unsigned long long *scratch,
+                              WideFirst *fs, WideLimits lim) {
     const uint32_t *len = lim.len;
     if (len)
         hipLaunchKernelGGL(k_wide_first_gather<true>, dim3(kArgBlocks), dim3(256), 0, s, t, ctl, scratch, fs, len, lim.max_len);
     else
         hipLaunchKernelGGL(k_wide_first_gather<false>, dim3(kArgBlocks), dim3(256), 0, s, t, ctl, scratch, fs, len, 0u);
+}
+
+void launch_wide_first(hipStream_t s, const uint32_t *src, uint64_t n_upper, WideTable t, WideCtl *ctl, WideBest *best,
+                       const unsigned long long *scratch, WideFirst *fs, WideLimits lim) {
+    const uint32_t *len = lim.len;
+    launch_wide_first_gather(s, t, ctl, scratch, fs, lim);
     if (n_upper) {
         const uint32_t blocks = std::min<uint32_t>(span_grid(n_upper), kPosBlocks);
         if (len)

@@ -1,4 +1,4 @@
-// Device helpers that the kernels of the 32-bit training loop share (wide.hip, wide_resident.hip): the concurrent
+// Device helpers that the kernels of the 32-bit training loop share (wide.hip, wide_resident.hip, wide_regions.hip): the concurrent
 // insert-or-add and the lookup of the 64-bit-key pair table, the (count, ~key) order of the argmax and its wave and
 // workgroup reductions, the bitmap hash of the `first` tie-break and the match test of a merge.  See wide.h.
 #ifndef MBPE_WIDE_DEV_H
@@ -47,6 +47,7 @@ __device__ __forceinline__ int32_t wide_lookup(const WideTable &t, unsigned long
 }
 
 // ---- argmax: (count desc, first asc, second asc) = the larger of (count, ~key) -------------------------------
+constexpr int kWideArgBlocks = 1024;      // workgroups of the scan = partials the final stage reduces (wide.hip, wide_regions.hip)
 struct Cand128 { long long count; unsigned long long nkey; };      // count = -1: nothing
 __device__ __forceinline__ bool better(const Cand128 &a, const Cand128 &b) {
     return a.count > b.count || (a.count == b.count && a.nkey > b.nkey);

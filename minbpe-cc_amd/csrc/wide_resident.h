@@ -56,18 +56,28 @@ struct WideResident {
 };
 
 // ---- the region cutter: plain arithmetic, host and device --------------------------------------------------------
-// Boundary r of kResRegions + 1 over the n flagged tokens of tok: the target r * ceil(n / kResRegions), moved
-// forward to just behind the next chunk end (bit 31) at or after the token before it; 0 for r = 0, n for the last
-// and where no chunk end follows.  Ascending in r, because the targets are.
-MBPE_HD uint32_t resident_boundary(const uint32_t *tok, uint32_t n, uint32_t r) {
+// Boundary r of n_regions + 1 over the n flagged tokens of tok, for regions of `per` tokens (per * n_regions >= n):
+// the target r * per, moved forward to just behind the next chunk end (bit 31) at or after the token before it; 0
+// for r = 0, n for the last and where no chunk end follows.  Ascending in r, because the targets are.  The one
+// statement of the rule: the cutters of wide_resident.hip and wide_regions.hip and the host checks all call it.
+// reach: how far forward the scan looks (n: to the end).  A scan that gives up returns kRegionNoBoundary; the chunk
+// it stood in is longer than `reach` tokens, and so is the region that holds it.
+constexpr uint32_t kRegionNoBoundary = 0xFFFFFFFFu;
+MBPE_HD uint32_t region_boundary(const uint32_t *tok, uint32_t n, uint32_t per, uint32_t n_regions, uint32_t r,
+                                 uint32_t reach) {
     if (r == 0) return 0;
-    if (r >= kResRegions) return n;
-    const uint32_t per = (n + kResRegions - 1) / kResRegions;
+    if (r >= n_regions) return n;
     uint64_t i = (uint64_t)per * r;
     if (i == 0 || i >= n) return n;
-    for (--i; i < n; ++i)
+    const uint64_t stop = i + reach < n ? i + reach : n;
+    for (--i; i < stop; ++i)
         if (tok[i] & kTokEnd) return (uint32_t)i + 1;
-    return n;
+    return stop < n ? kRegionNoBoundary : n;
+}
+
+// ... of the kResRegions + 1 of a resident launch: balanced by tokens, per = ceil(n / kResRegions)
+MBPE_HD uint32_t resident_boundary(const uint32_t *tok, uint32_t n, uint32_t r) {
+    return region_boundary(tok, n, (n + kResRegions - 1) / kResRegions, kResRegions, r, n);
 }
 
 // All of them; false when a region would hold more than `cap` tokens (a chunk longer than a region takes).

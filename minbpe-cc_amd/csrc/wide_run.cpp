@@ -13,6 +13,7 @@ void WideRun::release(DevPool &pool) {
     pool.free(tok[0]); pool.free(tok[1]); pool.free(val); pool.free(scratch); pool.free(wt[0]); pool.free(wt[1]);
     pool.free(tab.keys); pool.free(tab.cnts); pool.free(ctl); pool.free(best); pool.free(arg);
     pool.free(fs); pool.free(tally); pool.free(lim.len); pool.free(res);
+    pool.free(reg.hdr); pool.free(reg.off); pool.free(reg.len); pool.free(reg.to);
     *this = WideRun{};
 }
 
@@ -182,11 +183,18 @@ bool WideRun::resident_now(const WideDev &d) const {
            n_upper <= kResMaxTokens && (uint64_t)tab.mask + 1 <= kResMaxSlots;
 }
 
-// How many merges a resident launch takes on: as many as the table has room for at load factor 1/2 (16 at least:
-// the caller grows the table for them, as it always did), and no more than run in some 20 ms at the time per merge
-// measured over the launch before (64 for the first).
-uint32_t WideRun::resident_group(uint32_t left, unsigned long long top) const {
-    const double cap = res_us_per_merge > 0 ? 20000.0 / res_us_per_merge : 64.0;
+// The option "regions": does the next group of merges run on wave-owned regions (wide_regions.h)?  Only a training
+// without stopping rules (those kernels have none) on a stream that kRegMaxRegions regions hold, whose chunks each fit
+// a region -- which the group's cutter finds out (reg_refused).  Where resident_now() holds too, resident goes first.
+bool WideRun::regions_now(const WideDev &d) const {
+    return d.regions && !reg_refused && !lim.len && !lim.min_count && n_upper <= kRegMaxTokens;
+}
+
+// How many merges a resident launch or a group in regions takes on: as many as the table has room for at load factor
+// 1/2 (16 at least: the caller grows the table for them, as it always did), and no more than run in some 20 ms at the
+// time per merge measured over the one before (64 for the first).
+uint32_t WideRun::resident_group(uint32_t left, unsigned long long top, double us_per_merge) const {
+    const double cap = us_per_merge > 0 ? 20000.0 / us_per_merge : 64.0;
     const uint32_t want = std::min<uint32_t>(left, (uint32_t)std::min(std::max(cap, 16.0), 4096.0));
     const uint64_t room = ((uint64_t)tab.mask + 1) / 2, used = h_ctl.n_entries;
     const uint64_t fit = room > used ? (room - used) / wide_headroom(top, n_upper, 1) : 0;
@@ -201,10 +209,20 @@ int WideRun::steps(const WideDev &d, uint32_t n_steps, uint32_t *done_out) {
     while (done < n_steps && k < n_wide) {
         const bool resident = resident_now(d);
         const uint32_t left = std::min<uint32_t>(n_steps - done, n_wide - k);
-        const uint32_t group = resident ? resident_group(left, top) : std::min<uint32_t>(16u, left);
+        const bool regions = !resident && regions_now(d);
+        const uint32_t group = resident  ? resident_group(left, top, res_us_per_merge)
+                               : regions ? resident_group(left, top, reg_us_per_merge)
+                                         : std::min<uint32_t>(16u, left);
         if (resident && !res) {
             HIPCHK(d.pool.alloc(&res, sizeof(WideResident)));
             HIPCHK(hipMemsetAsync(res, 0, sizeof(WideResident), d.stream));
+        }
+        if (regions && !reg.hdr) {           // (sized for the most regions there can be: 1 MiB)
+            HIPCHK(d.pool.alloc(&reg.hdr, sizeof(WideRegions)));
+            HIPCHK(d.pool.alloc(&reg.off, ((size_t)kRegMaxRegions + 1) * 4));
+            HIPCHK(d.pool.alloc(&reg.len, (size_t)kRegMaxRegions * 4));
+            HIPCHK(d.pool.alloc(&reg.to, (size_t)kRegMaxRegions * 8));
+            HIPCHK(hipMemsetAsync(reg.hdr, 0, sizeof(WideRegions), d.stream));
         }
         // room for what this group can insert (load factor 1/2 at most)
         const uint64_t need = (uint64_t)h_ctl.n_entries + wide_headroom(top, n_upper, group);
@@ -221,7 +239,18 @@ int WideRun::steps(const WideDev &d, uint32_t n_steps, uint32_t *done_out) {
                                  goal.first, res);
             HIPCHK(hipMemcpyAsync(&h_res, res, sizeof(WideResident), hipMemcpyDeviceToHost, d.stream));
         }
-        for (uint32_t g = 0; g < group && !resident; ++g) {
+        const RegionPlan plan = region_plan(n_upper, d.region_tokens);
+        WideRegions h_reg = {};
+        if (regions) {
+            // cut once, rewrite in place merge after merge, close up into the other buffer once
+            launch_wide_regions_cut(d.stream, tok[cur], ctl, plan, reg);
+            for (uint32_t g = 0; g < group; ++g)
+                launch_wide_regions_merge(d.stream, tok[cur], wt[cur], plan, reg, tab, ctl, best, arg,
+                                          goal.first ? fs : nullptr, goal.new_id_base);
+            launch_wide_regions_close(d.stream, tok[cur], tok[cur ^ 1], wt[cur], wt[cur ^ 1], plan, reg, ctl);
+            HIPCHK(hipMemcpyAsync(&h_reg, reg.hdr, sizeof(WideRegions), hipMemcpyDeviceToHost, d.stream));
+        }
+        for (uint32_t g = 0; g < group && !resident && !regions; ++g) {
             const int src = cur ^ (int)(g & 1), dst = src ^ 1;
             launch_wide_argmax(d.stream, tab, ctl, best, arg, lim);
             if (goal.first) launch_wide_first(d.stream, tok[src], n_upper, tab, ctl, best, arg, fs, lim);
@@ -237,7 +266,17 @@ int WideRun::steps(const WideDev &d, uint32_t n_steps, uint32_t *done_out) {
             res_refused = true;
             continue;
         }
+        if (regions && h_reg.bad) {            // likewise: no launch of the group did anything
+            reg_refused = true;
+            continue;
+        }
         const uint32_t ran = h_ctl.k - k;
+        if (regions) {
+            reg_groups++;
+            reg_merges += ran;
+            reg_regions_last = plan.count;
+            if (ran) reg_us_per_merge = 1000.0 * ms / ran;
+        }
         if (resident) {
             res_launches++;
             res_merges += ran;
@@ -248,7 +287,7 @@ int WideRun::steps(const WideDev &d, uint32_t n_steps, uint32_t *done_out) {
         if (ran == 0) break;
         h_best.resize((size_t)k + ran);
         HIPCHK(hipMemcpy(h_best.data() + k, best + k, (size_t)ran * sizeof(WideBest), hipMemcpyDeviceToHost));
-        cur ^= resident ? 1 : (int)(ran & 1u);      // (a resident launch closes its regions up into the other buffer)
+        cur ^= resident || regions ? 1 : (int)(ran & 1u);      // (regions are closed up into the other buffer)
         n_upper = h_ctl.n;
         k += ran;
         done += ran;
@@ -261,6 +300,7 @@ int WideRun::steps(const WideDev &d, uint32_t n_steps, uint32_t *done_out) {
             k += fill;
             done += fill;
             if (resident) res_merges += fill;
+            if (regions) reg_merges += fill;
             HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&ctl->k), (int)k, 1, d.stream));
             HIPCHK(hipStreamSynchronize(d.stream));
             h_ctl.k = k;

@@ -8,6 +8,7 @@
 #include "dev_pool.h"
 #include "mbpe.h"
 #include "wide.h"
+#include "wide_regions.h"
 #include "wide_resident.h"
 
 #include <vector>
@@ -15,10 +16,11 @@
 namespace mbpe {
 
 // the context's side of every call: its stream, its two timing events, its pool, the stats the loop adds to, and the
-// options "resident" and "resident_max_tokens" as they stand
+// options "resident", "resident_max_tokens", "regions" and "region_tokens" as they stand
 struct WideDev {
     hipStream_t stream; hipEvent_t ev0, ev1; DevPool &pool; int n_cus; mbpe_stats &stats;
     bool resident; uint64_t resident_max;
+    bool regions; uint32_t region_tokens;
 };
 
 // what a begin says of the loop ahead: the merges it may make, the id of its first one, the tie-break
@@ -66,6 +68,11 @@ struct WideRun {
     bool res_refused = false;        // a chunk was longer than a region takes: the launches of wide.h from there on
     double res_us_per_merge = 0;     // measured over the latest resident launch (0: none yet); sizes the next group
     uint64_t res_merges = 0, res_launches = 0;
+    // the option "regions" (wide_regions.h): its device state, and what mbpe_train_regions_stats reports
+    RegionBufs reg = {};
+    bool reg_refused = false;        // a chunk was longer than a region takes: the launches of wide.h from there on
+    double reg_us_per_merge = 0;     // measured over the latest group in regions (0: none yet); sizes the next
+    uint64_t reg_merges = 0, reg_groups = 0, reg_regions_last = 0;
 
     void release(DevPool &pool);     // every buffer back to the pool, every member as it is declared above
     int convert(const WideDev &d, const WideSlots &src, const WideGoal &goal);
@@ -88,7 +95,8 @@ private:
     int alloc_loop(const WideDev &d, uint64_t n_tok, uint64_t n_val, uint64_t n_init);
     int begin_limits(const WideDev &d, const WideTokens &src);
     bool resident_now(const WideDev &d) const;
-    uint32_t resident_group(uint32_t left, unsigned long long top) const;
+    bool regions_now(const WideDev &d) const;
+    uint32_t resident_group(uint32_t left, unsigned long long top, double us_per_merge) const;
 };
 
 }  // namespace mbpe

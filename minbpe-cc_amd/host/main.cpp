@@ -91,6 +91,10 @@ void usage() {
                  "                              --input-list, --counts, `first`, --continue-from) a group of merges is one kernel\n"
                  "                              launch of one workgroup, for streams up to the library's bound -- whose default is\n"
                  "                              0, so today the flag changes nothing here: the same model\n"
+                 "  --regions                   With --train: where the training runs the 32-bit loop (--dedup, --input-list,\n"
+                 "                              --counts, `first`, --continue-from) its merges run on regions of the stream\n"
+                 "                              that waves own and rewrite in place, two to four kernel launches per merge\n"
+                 "                              instead of seven to ten: the same model\n"
                  "  --dedup                     With --train: split as asked, then train on the distinct chunks with their counts\n"
                  "                              (deduplicated on the HIP device): the same model.  One pass over the unique\n"
                  "                              chunks per merge: meant for -c first, for vocabularies beyond 65,536 and for\n"
@@ -158,7 +162,7 @@ int main(int argc, char *argv[]) {
     std::string conflict_resolution_str = "first";
     bool train = false, decode = false, encode = false, write_vocab = false, verbose = false, device_encode = false,
          device_decode = false, device_split = false, split_unicode = false, rank_order = false, dedup = false, resident = false,
-         count = false;
+         regions = false, count = false;
     int vocab_size = 512, device = 0;
     long long min_frequency = 0, max_token_length = 0;
     bool have_limits = false;
@@ -234,6 +238,7 @@ int main(int argc, char *argv[]) {
         else if (arg == "--rank-order") rank_order = true;
         else if (arg == "--dedup") dedup = true;
         else if (arg == "--resident") resident = true;
+        else if (arg == "--regions") regions = true;
         else if (arg == "--count") count = true;
         else if (arg == "-v" || arg == "--verbose") verbose = true;
         else { std::cerr << "The following argument was not expected: " << arg << "\n"; return 109; }
@@ -250,6 +255,10 @@ int main(int argc, char *argv[]) {
 
     if (resident && !(encode && device_encode) && !train) {
         std::cerr << "--resident requires --train, or --encode --device-encode\n";
+        return 107;
+    }
+    if (regions && !train) {
+        std::cerr << "--regions requires --train\n";
         return 107;
     }
     if (have_limits && !train) { std::cerr << "--min-frequency and --max-token-length require --train\n"; return 107; }
@@ -337,6 +346,7 @@ int main(int argc, char *argv[]) {
         return 105;
     }
     if (train && resident) mbpe_tok_set_train_resident(rt, 1);
+    if (train && regions) mbpe_tok_set_train_regions(rt, 1);
     // --counts and --input-list: opens the pieces session, merges the counts files in the order given, then reads the
     // pieces one at a time.  false: a file could not be used (said on stderr; counts_failed for a counts file);
     // *trc: the code of the library call that failed, if one did

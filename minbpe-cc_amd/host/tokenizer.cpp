@@ -315,6 +315,7 @@ int Tokenizer::run_training(mbpe_ctx *ctx, int rc, int vocab_size, CONFLICT_RESO
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "min_frequency", train_min_frequency_);
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "max_token_length", train_max_token_length_);
     if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "resident", train_resident_ ? 1 : 0);      // (mbpe_tok_set_train_resident)
+    if (rc == MBPE_OK) rc = mbpe_set_option(ctx, "regions", train_regions_ ? 1 : 0);        // (mbpe_tok_set_train_regions)
     if (rc == MBPE_OK) rc = mbpe_train_begin_from(ctx, static_cast<uint32_t>(vocab_size), prior.data(), n_prior_of(prior));
     if (rc == MBPE_OK) rc = mbpe_train_steps(ctx, cap, nullptr);
     if (rc == MBPE_OK) rc = mbpe_train_result(ctx, out->flat.data(), out->had.data(), cap, &out->n_merges);
@@ -1459,6 +1460,16 @@ int mbpe_tok_set_train_resident(mbpe_tokenizer *t, int on) {
         return MBPE_ERR_ARG;
     }
     t->t->set_train_resident(on == 1);
+    return MBPE_OK;
+}
+
+int mbpe_tok_set_train_regions(mbpe_tokenizer *t, int on) {
+    if (!t) return MBPE_ERR_ARG;
+    if (on != 0 && on != 1) {
+        mbpe_host::set_last_error("mbpe_tok_set_train_regions: on must be 0 or 1");
+        return MBPE_ERR_ARG;
+    }
+    t->t->set_train_regions(on == 1);
     return MBPE_OK;
 }
 

@@ -142,6 +142,8 @@ public:
     }
     // every training from here on sets the context option "resident" (mbpe_tok_set_train_resident)
     void set_train_resident(bool on) { train_resident_ = on; }
+    // ... and the option "regions" (mbpe_tok_set_train_regions)
+    void set_train_regions(bool on) { train_regions_ = on; }
     // the device encode calls from here on go through the encoder's "dedup" route (mbpe_tok_set_encode_dedup)
     void set_encode_dedup(bool on) { encode_dedup_ = on; }
     // ... and run the kept encoder with its option "resident" (mbpe_tok_set_encode_resident)
@@ -256,7 +258,7 @@ private:
     } pieces_;
     bool encode_split_ = false;
     bool split_unicode_ = false;
-    bool train_dedup_ = false, train_resident_ = false;
+    bool train_dedup_ = false, train_resident_ = false, train_regions_ = false;
     int64_t train_min_frequency_ = 0, train_max_token_length_ = 0;
     bool encode_dedup_ = false;
     bool encode_resident_ = false;

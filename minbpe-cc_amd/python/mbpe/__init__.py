@@ -22,7 +22,7 @@ COMM_ID_BYTES = 128
 EXPORTS = [
     "mbpe_last_error", "mbpe_version", "mbpe_create", "mbpe_destroy", "mbpe_load_corpus",
     "mbpe_pair_count_u8", "mbpe_train_begin", "mbpe_train_steps", "mbpe_train_sequences", "mbpe_train_result",
-    "mbpe_train_lexical", "mbpe_train", "mbpe_get_stats", "mbpe_train_resident_stats", "mbpe_train_resident_ticks", "mbpe_get_stream", "mbpe_stream_device", "mbpe_table_device", "mbpe_get_pairs", "mbpe_compact",
+    "mbpe_train_lexical", "mbpe_train", "mbpe_get_stats", "mbpe_train_resident_stats", "mbpe_train_resident_ticks", "mbpe_train_regions_stats", "mbpe_get_stream", "mbpe_stream_device", "mbpe_table_device", "mbpe_get_pairs", "mbpe_compact",
     "mbpe_set_option", "mbpe_comm_unique_id", "mbpe_comm_init", "mbpe_comm_init_external",
     "mbpe_comm_exchange_buffer", "mbpe_comm_exchange_done", "mbpe_presplit",
     "mbpe_split_count", "mbpe_split_offsets", "mbpe_split_has_gaps", "mbpe_split_starts", "mbpe_split_ends",
@@ -68,7 +68,7 @@ TOK_EXPORTS = [
     "mbpe_tok_train_split_device", "mbpe_tok_set_encode_split", "mbpe_tok_set_split_unicode",
     "mbpe_tok_set_encode_order", "mbpe_tok_train_continue", "mbpe_tok_encode_byteoff",
     "mbpe_tok_encode_batch_byteoff_device", "mbpe_tok_set_encode_dropout", "mbpe_tok_set_train_dedup",
-    "mbpe_tok_set_encode_dedup", "mbpe_tok_set_encode_resident", "mbpe_tok_set_train_resident",
+    "mbpe_tok_set_encode_dedup", "mbpe_tok_set_encode_resident", "mbpe_tok_set_train_resident", "mbpe_tok_set_train_regions",
     "mbpe_tok_train_pieces_begin", "mbpe_tok_train_pieces_add",
     "mbpe_tok_train_pieces_finish", "mbpe_tok_train_pieces_abort", "mbpe_tok_set_train_limits",
     "mbpe_tok_train_pieces_export_size", "mbpe_tok_train_pieces_export", "mbpe_tok_train_pieces_merge",
@@ -233,6 +233,7 @@ def lib():
     L.mbpe_get_stats.argtypes = [vp, vp]
     L.mbpe_train_resident_stats.argtypes = [vp, vp, vp, vp]
     L.mbpe_train_resident_ticks.argtypes = [vp, vp, vp, vp]
+    L.mbpe_train_regions_stats.argtypes = [vp, vp, vp, vp]
     L.mbpe_get_stream.argtypes = [vp, vp, vp, u64, vp]
     L.mbpe_stream_device.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(u32), ctypes.POINTER(u32),
                                      ctypes.POINTER(u32)]
@@ -351,6 +352,7 @@ def lib():
     L.mbpe_encoder_resident_stats.argtypes = [vp, vp, vp, vp]
     L.mbpe_tok_set_encode_resident.argtypes = [vp, i32]
     L.mbpe_tok_set_train_resident.argtypes = [vp, i32]
+    L.mbpe_tok_set_train_regions.argtypes = [vp, i32]
     L.mbpe_wordcount_create.argtypes = [i32, ctypes.POINTER(vp)]
     L.mbpe_wordcount_destroy.argtypes = [vp]
     L.mbpe_wordcount_destroy.restype = None
@@ -2405,6 +2407,13 @@ class Trainer:
         _check(lib().mbpe_train_resident_stats(self._h, *[ctypes.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    def regions_stats(self):
+        """What the option "regions" did in the latest training (mbpe_train_regions_stats) -> (merges made by its
+        groups, groups, regions of the latest group); all 0: every group took the launches of the 32-bit loop."""
+        v = [ctypes.c_uint64() for _ in range(3)]
+        _check(lib().mbpe_train_regions_stats(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     def resident_ticks(self):
         """Diagnostics for tools/train_resident_time.py (mbpe_train_resident_ticks): the kernel's time in 10 ns ticks
         -> (argmax, `first` search, stream walks)."""
@@ -2501,8 +2510,13 @@ class Tokenizer:
         _check(lib().mbpe_tok_set_special_tokens(self._h, b, len(b)))
 
     def train(self, data, vocab_size, conflict_resolution=1, verbose=False, device=0, device_split=False,
-              resume=False, dedup=False, min_frequency=0, max_token_length=0, resident=False):
-        """resident (here, in train_from_iterator, train_files and train_from_counts; mbpe_tok_set_train_resident): the
+              resume=False, dedup=False, min_frequency=0, max_token_length=0, resident=False,
+              regions=False):
+        """regions (here, in train_from_iterator, train_files and train_from_counts; mbpe_tok_set_train_regions): the
+        training context's option "regions": where the training runs the 32-bit loop (dedup, word counts, `first`,
+        resume) its merges run on wave-owned regions of the stream, two to four kernel launches per merge instead of
+        seven to ten.  Same merges; a speed option.
+        resident (here, in train_from_iterator, train_files and train_from_counts; mbpe_tok_set_train_resident): the
         training context's option "resident": where the training runs the 32-bit loop on a short stream (dedup, word
         counts, `first`, resume) a group of merges is one kernel launch, for streams of at most "resident_max_tokens"
         tokens.  That bound's default is 0 and the Tokenizer does not set it, so today the switch changes nothing
@@ -2528,6 +2542,7 @@ class Tokenizer:
         _check(lib().mbpe_tok_set_train_dedup(self._h, int(bool(dedup))))
         _check(lib().mbpe_tok_set_train_limits(self._h, int(min_frequency), int(max_token_length)))
         _check(lib().mbpe_tok_set_train_resident(self._h, int(bool(resident))))
+        _check(lib().mbpe_tok_set_train_regions(self._h, int(bool(regions))))
         if resume:
             _check(lib().mbpe_tok_train_continue(self._h, text.ctypes.data if len(text) else None, len(text), vocab_size,
                                                  conflict_resolution, int(verbose), device, int(bool(device_split))))
@@ -2537,17 +2552,19 @@ class Tokenizer:
                   int(verbose), device))
 
     def train_from_iterator(self, texts, vocab_size, conflict_resolution=1, verbose=False, device=0, device_split=False,
-                            resume=False, repeats=None, min_frequency=0, max_token_length=0, resident=False):
+                            resume=False, repeats=None, min_frequency=0, max_token_length=0, resident=False,
+                            regions=False):
         """Train on a corpus that arrives in pieces (mbpe_tok_train_pieces_*): every text is split on its own and its
         chunks are counted on the device (mbpe_wordcount_*), then the training runs on the table -- the merges of a
         training on the pieces' chunk lists laid end to end, for both tie-breaks, with one piece in host memory at a
         time.  A piece boundary is a chunk boundary: to get a whole file's result, cut it where a letter or digit is
         followed by whitespace.  repeats: one count per text (default 1), the text counted that many times.
-        device_split, resume, min_frequency, max_token_length, resident: as for train().  The tokenizer's merges stay as they are until the training has
+        device_split, resume, min_frequency, max_token_length, resident, regions: as for train().  The tokenizer's merges stay as they are until the training has
         succeeded; the session is aborted when the iterator or a call raises."""
         _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
         _check(lib().mbpe_tok_set_train_limits(self._h, int(min_frequency), int(max_token_length)))
         _check(lib().mbpe_tok_set_train_resident(self._h, int(bool(resident))))
+        _check(lib().mbpe_tok_set_train_regions(self._h, int(bool(regions))))
         _check(lib().mbpe_tok_train_pieces_begin(self._h, device, int(bool(device_split))))
         try:
             reps = None if repeats is None else iter(repeats)
@@ -2610,7 +2627,8 @@ class Tokenizer:
         return self.count_from_iterator(read(), **kw)
 
     def train_from_counts(self, blobs, vocab_size, conflict_resolution=1, verbose=False, device=0, resume=False,
-                          min_frequency=0, max_token_length=0, texts=None, device_split=False, resident=False):
+                          min_frequency=0, max_token_length=0, texts=None, device_split=False, resident=False,
+                          regions=False):
         """The training stage on counts made elsewhere: the blobs of count_from_iterator are merged in the order given,
         then any `texts` are added as train_from_iterator adds them (device_split: how these are split), then the
         training runs -- merges, counts, .model, .vocab and verbose lines of train_from_iterator on all the pieces in
@@ -2621,6 +2639,7 @@ class Tokenizer:
         _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
         _check(lib().mbpe_tok_set_train_limits(self._h, int(min_frequency), int(max_token_length)))
         _check(lib().mbpe_tok_set_train_resident(self._h, int(bool(resident))))
+        _check(lib().mbpe_tok_set_train_regions(self._h, int(bool(regions))))
         _check(lib().mbpe_tok_train_pieces_begin(self._h, device, int(bool(device_split))))
         try:
             for blob in blobs:
