@@ -1427,6 +1427,83 @@ MBPE_API int  mbpe_encoder_encode_batch_endmask_denoise(mbpe_encoder *e, const u
                                                         uint64_t cap_rows, int out_on_device, uint64_t *n_rows_out,
                                                         uint64_t *n_tokens_out);
 
+/* ---- text-pair batches ------------------------------------------------------- */
+
+/* Two texts per example joined into one document, between encode and pack: prompt + response with the loss on the
+ * response (instruction tuning), query + passage truncated so that both fit (cross-encoders, rerankers), and, in two
+ * calls, preference data.  ("Pair" already means a byte pair in this code base, hence the name.)  A call has 2 n
+ * documents; documents 2i and 2i + 1 are A and B of pair i, la and lb tokens long.  An odd document count is
+ * MBPE_ERR_ARG.  Let end = (end_id != MBPE_NO_TOKEN) and K = max_tokens - n_sep - end, the room for text; with
+ * max_tokens == 0 nothing is truncated.  Otherwise (a, b), the tokens kept, are
+ *   LONGEST_FIRST   while a + b > K drop one token from the longer side, on a tie from B (the longest_first rule of
+ *                   other tokenizers).  In closed form: (la, lb) if la + lb <= K; (la, K - la) if la <= lb and
+ *                   2 la <= K; (K - lb, lb) if la > lb and 2 lb <= K; else (ceil(K / 2), floor(K / 2))
+ *   ONLY_FIRST      b = min(lb, K), a = min(la, K - b)
+ *   ONLY_SECOND     a = min(la, K), b = min(lb, K - a)
+ * A side keeps its first tokens, or with keep_tail_a / keep_tail_b its last.  The joined document is
+ *   A' sep.. B' [end]            a + n_sep + b + end ids
+ * and beside it goes a target stream, one uint32 per joined id: target[k] = the id at k + 1 where position k + 1 exists
+ * and -- label_mode SECOND -- holds a token of B' or the end id; MBPE_NO_TOKEN elsewhere.  So with SECOND the last
+ * separator (the last token of A' when n_sep == 0) predicts the first response token, and the end id predicts nothing.
+ * These are next-token labels in the cell of the predicting token: what label_tokens means to
+ * mbpe_pack_tokens_aux_labels, mbpe_pack_windows_labels and mbpe_pack_fit_labels.  Tokens are read as the packers read
+ * them (16-bit plain ids, or 32-bit with bit 31 ignored) and written as plain ids of the same width.
+ * Errors, all before the device is touched: MBPE_ERR_ARG for a NULL spec where one is required, an enum out of range,
+ * n_sep > 2, max_tokens != 0 below n_sep + end, a sep or end id >= 2^31 - 2, an odd document count and bad offsets;
+ * MBPE_ERR_VOCAB for a sep or end id >= 65,536 with 16-bit tokens. */
+#define MBPE_TEXTPAIR_LONGEST_FIRST 0u
+#define MBPE_TEXTPAIR_ONLY_FIRST    1u
+#define MBPE_TEXTPAIR_ONLY_SECOND   2u
+#define MBPE_TEXTPAIR_LABEL_ALL     0u
+#define MBPE_TEXTPAIR_LABEL_SECOND  1u
+typedef struct {
+    uint32_t max_tokens;   /* the most ids a joined pair may have, separators and end id included; 0: no truncation */
+    uint32_t truncation;   /* MBPE_TEXTPAIR_LONGEST_FIRST, _ONLY_FIRST, _ONLY_SECOND */
+    uint32_t keep_tail_a;  /* 0: A keeps its first tokens, 1: its last */
+    uint32_t keep_tail_b;  /* the same for B */
+    uint32_t n_sep;        /* 0 .. 2 ids between A' and B' (BERT: one, RoBERTa: two) */
+    uint32_t sep_id[2];
+    uint32_t end_id;       /* an id behind B'; MBPE_NO_TOKEN: none */
+    uint32_t label_mode;   /* MBPE_TEXTPAIR_LABEL_ALL, _SECOND */
+} mbpe_textpair_spec;      /* 36 bytes */
+
+/* The plan alone, on the host (never MBPE_ERR_NO_DEVICE): doc_tok_off_out (n_docs / 2 + 1, required) = the joined
+ * documents' token offsets; kept_out (2 per pair, or NULL) = a, b.  The ids are checked as for 32-bit tokens. */
+MBPE_API int  mbpe_textpair_plan(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_textpair_spec *spec,
+                                 uint64_t *doc_tok_off_out, uint64_t *kept_out);
+
+/* The join of a flat token stream on HIP device `device_id`, with the conventions of mbpe_fim_tokens: tokens in host or
+ * device memory (tokens_on_device), doc_tok_off (n_docs + 1), doc_tok_off_out (n_docs / 2 + 1, or NULL) and kept_out
+ * (2 per pair, or NULL) on the host; tokens_out (cap ids) and targets_out (cap uint32, or NULL: no targets) both in host
+ * or both in device memory (out_on_device; on the device aligned to their elements).  *n_out = the joined token count.
+ * tokens_out NULL is a query, answered from the host's plan without a device; a cap too small is MBPE_ERR_ARG: nothing
+ * is written and n_out is still reported.  (tokens_out, doc_tok_off_out, targets_out) are what the _labels packers take
+ * as they are.  Kernels (csrc/textpair.hip): k_textpair_plan, one lane per pair, leaves (a, b) and the joined lengths, a
+ * 64-bit scan over spans of 1,024 pairs the offsets; k_textpair_gather writes ids and targets in one pass, a lane per
+ * 16-byte piece of the joined stream.  mbpe_textpair_kernel_ms: the device time of the calling thread's latest such
+ * call. */
+MBPE_API int  mbpe_textpair_tokens(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits,
+                                   int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs,
+                                   const mbpe_textpair_spec *spec, void *tokens_out, uint32_t *targets_out, uint64_t cap,
+                                   int out_on_device, uint64_t *doc_tok_off_out, uint64_t *kept_out, uint64_t *n_out);
+MBPE_API int  mbpe_textpair_kernel_ms(float *ms_out);
+
+/* The join as a stage of the encoder's batch calls; spec NULL turns it off.  It holds from the next call on for every
+ * call that packs (those of mbpe_encoder_set_fim).  The stage runs between the encode and the pack kernel, into buffers
+ * the encoder keeps (a repeat call of no larger size leaves mbpe_encoder_alloc_count as it is).  Behind it a call of
+ * 2 n documents has n: the rows, the window and fit plans, seg and doc_tok_off_out, whose first n + 1 entries are
+ * written and the rest left untouched.  n_tokens_out stays "tokens encoded".  Where aux asks for labels they come from
+ * the target stream, as in the _labels calls; the plain batch call gets the joined ids alone.  MBPE_ERR_ARG from the
+ * batch call, never a silent choice: together with mbpe_encoder_set_fim or _set_mlm, in the _denoise calls, and with an
+ * odd document count.  The sep and end ids are checked against the width of the tokens a call packs from (16 bits with
+ * out_bits 16: MBPE_ERR_VOCAB).  With no spec every call launches and allocates exactly what it does without.
+ * mbpe_encoder_kernel_ms and mbpe_encoder_pack_ms include the stage.
+ * mbpe_encoder_textpair_info: (a, b) of every pair of the latest batch call, on the host: *n_pairs_out = its pairs (0
+ * where the stage was off); kept_out NULL or with room for cap_pairs pairs (fewer: MBPE_ERR_ARG, the count is still
+ * reported). */
+MBPE_API int  mbpe_encoder_set_textpair(mbpe_encoder *e, const mbpe_textpair_spec *spec);
+MBPE_API int  mbpe_encoder_textpair_info(mbpe_encoder *e, uint64_t *kept_out, uint64_t cap_pairs, uint64_t *n_pairs_out);
+
 /* ---- decode on the device ----------------------------------------------- */
 
 /* Tokenizer::decode (Tokenizer.h:725-751) for whole token streams on HIP device `device_id`: per token a byte

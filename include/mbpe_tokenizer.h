@@ -263,6 +263,19 @@ MBPE_API int mbpe_tok_encode_fim_info(mbpe_tokenizer *t, uint8_t *mode_out, uint
  * does not fit one. */
 MBPE_API int mbpe_tok_set_encode_mlm(mbpe_tokenizer *t, const mbpe_mlm_spec *spec);
 
+/* Text pairs for the device batch calls that pack (those of mbpe_tok_set_encode_fim): spec as for
+ * mbpe_encoder_set_textpair (mbpe.h, which holds the rule), NULL turns it off.  While it is on, texts 2i and 2i + 1 of a
+ * call are A and B of pair i and the call's rows, segments and doc_tok_off_out are those of n_docs / 2 joined documents;
+ * the labels of _aux_device, _windows_device and _fit_device come from the stage's targets.  The sep and end ids may be
+ * special-token ids: the stage writes ids and never looks them up.  Errors as for mbpe_encoder_set_textpair; from the
+ * batch call MBPE_ERR_ARG for an odd n_docs and while fill-in-the-middle or masked-LM is on too, MBPE_ERR_VOCAB for a sep
+ * or end id that does not fit a 16-bit matrix.
+ * mbpe_tok_encode_textpair_info: mbpe_encoder_textpair_info of the kept encoder; no pairs before the first device
+ * call. */
+MBPE_API int mbpe_tok_set_encode_textpair(mbpe_tokenizer *t, const mbpe_textpair_spec *spec);
+MBPE_API int mbpe_tok_encode_textpair_info(mbpe_tokenizer *t, uint64_t *kept_out, uint64_t cap_pairs,
+                                           uint64_t *n_pairs_out);
+
 /* The option "unicode" (mbpe_splitter_set_option) of the device splits this tokenizer makes: 0 (the default) or on.
  * It applies to mbpe_tok_train_split_device and, while mbpe_tok_set_encode_split is on, to the mbpe_tok_encode*_device
  * calls, whose kept splitter is re-configured, not re-created.  Same results; otherwise without effect. */

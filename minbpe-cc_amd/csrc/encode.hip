@@ -55,6 +55,7 @@
 #include "expand.h"
 #include "fim.h"
 #include "mlm.h"
+#include "textpair.h"
 #include "hip_host.h"
 #include "hist.h"
 #include "pack.h"
@@ -737,6 +738,14 @@ struct mbpe_encoder : DevQueue {
     DevBuf<void> d_mlm_flat;
     DevBuf<uint32_t> d_mlm_tgt;
     DevBuf<unsigned long long> d_mlm_scr;
+    // mbpe_encoder_set_textpair (nothing of this exists while it is off): the spec; the joined flat buffer, its target
+    // stream and offsets, (a, b) per pair; the pairs of the latest batch call the stage ran in
+    bool tp_on = false;
+    mbpe_textpair_spec tp = {};
+    DevBuf<void> d_tp_flat;
+    DevBuf<uint32_t> d_tp_tgt;
+    DevBuf<unsigned long long> d_tp_off, d_tp_kept;
+    uint64_t tp_pairs = 0;
     // the _denoise calls (nothing of this exists before the first one): the two flat streams the stage writes; its index
     // arrays in one buffer (dn_index); the rows' documents; the decoder side's matrix and lengths that go to the host
     DevBuf<void> d_dn_in, d_dn_tg, d_dn_dec_ids;
@@ -1825,6 +1834,40 @@ int enc_mlm_stage(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool doc
     return MBPE_OK;
 }
 
+// the text-pair stage of a batch call (mbpe_encoder_set_textpair; an even n_docs > 0): e->d_flat and the 2 n documents'
+// offsets -> e->d_tp_flat, e->d_tp_off and -- targets -- e->d_tp_tgt, which the pack step then reads as n documents and
+// their label tokens.  Two waits: one for the kernels' time, one for the joined token count and, to_host, the joined
+// offsets into e->doc_tok
+int enc_textpair_stage(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool docs_on_device, bool to_host, bool targets,
+                       uint64_t *n_new, float *ms) {
+    // (no pair has more ids than its two documents, the separators and the end id)
+    const uint64_t n_pairs = k.n_docs / 2, cap = n_tokens + n_pairs * textpair_extra(e->tp);
+    int rc = e->d_doc_off.reserve((k.n_docs + 1) * 8, e->mem);
+    if (rc == MBPE_OK) rc = e->d_tp_flat.reserve(std::max<uint64_t>(cap, 1) * (k.token_bits() / 8), e->mem);
+    if (rc == MBPE_OK && targets) rc = e->d_tp_tgt.reserve(std::max<uint64_t>(cap, 1) * 4, e->mem);
+    if (rc == MBPE_OK) rc = e->d_tp_off.reserve(textpair_off_bytes(n_pairs), e->mem);
+    if (rc == MBPE_OK) rc = e->d_tp_kept.reserve(n_pairs * 16, e->mem);
+    if (rc != MBPE_OK) return rc;
+    if (!docs_on_device)
+        ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (k.n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
+    const TextpairDst dst = {e->d_tp_flat, targets ? e->d_tp_tgt.get() : nullptr, cap, e->d_tp_off, e->d_tp_kept};
+    ECHK(hipEventRecord(e->ev0, e->stream));
+    textpair_launch(e->stream, e->d_flat, k.token_bits(), e->d_doc_off, n_pairs, e->tp, dst);
+    if ((rc = e->finish(ms)) != MBPE_OK) return rc;
+    e->last_ms += *ms;
+    unsigned long long total = 0;
+    ECHK(hipMemcpyAsync(&total, e->d_tp_off + n_pairs, 8, hipMemcpyDeviceToHost, e->stream));
+    if (to_host) {
+        e->doc_tok.resize(n_pairs + 1);
+        ECHK(hipMemcpyAsync(e->doc_tok.data(), e->d_tp_off, (n_pairs + 1) * 8, hipMemcpyDeviceToHost, e->stream));
+    }
+    ECHK(hipStreamSynchronize(e->stream));
+    if (total >> 40) return fail(MBPE_ERR_ARG, "textpair: more than 2^40 tokens");
+    *n_new = total;
+    e->tp_pairs = n_pairs;
+    return MBPE_OK;
+}
+
 // where the index arrays of the denoise stage lie in e->d_dn_idx, for n_docs documents and room for cap units
 struct DnIndex {
     uint64_t uoff, unit_doc, in_off, tg_off, res, scratch, words;
@@ -1847,6 +1890,7 @@ int enc_denoise_check(const mbpe_encoder *e, const EncPack &k) {
     if (const int rc = denoise_check_spec(dn.spec, k.token_bits(), &msg)) return fail(rc, msg);
     if (e->fim_on || e->mlm_on)
         return fail(MBPE_ERR_ARG, "fill-in-the-middle or masked-LM is on: they do not apply to the denoise calls, turn them off");
+    if (e->tp_on) return fail(MBPE_ERR_ARG, "textpair is on: it does not apply to the denoise calls, turn it off");
     if (const int rc = pack_check_spec(dn.dec_spec, k.token_bits())) return rc;
     if (k.spec->layout != MBPE_PACK_PADDED || dn.dec_spec->layout != MBPE_PACK_PADDED)
         return fail(MBPE_ERR_ARG, "the denoise calls take MBPE_PACK_PADDED specs");
@@ -1943,7 +1987,7 @@ int enc_denoise_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool doc
 int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_on_device) {
     const mbpe_pack_spec &spec = *k.spec;
     const mbpe_pack_aux *aux = k.aux;
-    const uint64_t n_docs = k.n_docs;
+    uint64_t n_docs = k.n_docs;                                  // documents the packers read
     const mbpe_pack_window *win = k.win;
     const struct mbpe_pack_fit *fit = k.fit;
     int rc = MBPE_OK;
@@ -1951,7 +1995,20 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
     float rows_ms = 0.f;                                         // the kernels before the pack kernel
     e->fim_docs = n_docs;
     e->fim_ran = false;
+    e->tp_pairs = 0;
     if (k.dn) return enc_denoise_tail(e, k, n_enc, docs_on_device);
+    const bool tp = e->tp_on && n_docs;                          // (never with fim or mlm, n_docs even: enc_batch_check)
+    const bool tp_labels = tp && aux && aux->labels;
+    if (tp) {
+        // (the host sees the offsets where it asks for them, where the fit plan is made of them, or where a joined
+        // document -- no more than all tokens, one pair's separators and end id, bos and eos -- could be too long for pos)
+        const bool to_host = k.doc_tok_off_out || fit || (aux && n_enc + textpair_extra(e->tp) + 2 >= (1ull << 32));
+        if ((rc = enc_textpair_stage(e, k, n_enc, docs_on_device, to_host, tp_labels, &n_tokens, &rows_ms)) != MBPE_OK)
+            return rc;
+        e->pack_ms = rows_ms;
+        n_docs /= 2;
+        if (aux && to_host && (rc = pack_check_aux(spec, aux, e->doc_tok.data(), n_docs, nullptr, 0)) != MBPE_OK) return rc;
+    }
     const bool fim = e->fim_on && e->fim.rate && n_enc;
     if (fim) {
         const bool to_host = k.doc_tok_off_out || fit || (aux && n_enc + 3 * n_docs + 2 >= (1ull << 32));
@@ -1975,11 +2032,12 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
         rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
         if (rc == MBPE_OK) rc = e->d_row_start.reserve(pack_win_scratch_bytes(n_docs), e->mem);
         if (rc != MBPE_OK) return rc;
-        if (!docs_on_device && !fim && !mlm)
+        if (!docs_on_device && !fim && !mlm && !tp)
             ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
         float win_ms = 0.f;
         ECHK(hipEventRecord(e->ev0, e->stream));
-        pack_launch_win_rows(e->stream, fim ? e->d_fim_off : e->d_doc_off, n_docs, spec, *win, e->d_row_start);
+        pack_launch_win_rows(e->stream, fim ? e->d_fim_off : tp ? e->d_tp_off : e->d_doc_off, n_docs, spec, *win,
+                             e->d_row_start);
         if ((rc = e->finish(&win_ms)) != MBPE_OK) return rc;
         unsigned long long total = 0;
         ECHK(hipMemcpyAsync(&total, e->d_row_start + n_docs, 8, hipMemcpyDeviceToHost, e->stream));
@@ -2021,11 +2079,11 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
         }
     }
     if (rc != MBPE_OK) return rc;
-    if (!docs_on_device && !win && !fim && !mlm)
+    if (!docs_on_device && !win && !fim && !mlm && !tp)
         ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
-    const PackSrc src = {fim ? e->d_fim_flat.get() : mlm ? e->d_mlm_flat.get() : e->d_flat.get(),
-                         fim ? e->d_fim_off : e->d_doc_off, n_docs, n_tokens, k.token_bits(),
-                         mlm ? e->d_mlm_tgt.get() : nullptr};
+    const PackSrc src = {fim ? e->d_fim_flat.get() : mlm ? e->d_mlm_flat.get() : tp ? e->d_tp_flat.get() : e->d_flat.get(),
+                         fim ? e->d_fim_off : tp ? e->d_tp_off : e->d_doc_off, n_docs, n_tokens, k.token_bits(),
+                         mlm ? e->d_mlm_tgt.get() : tp_labels ? e->d_tp_tgt.get() : nullptr};
     const PackDst dst = {k.out_on_device ? k.ids_out : e->d_ids.get(),
                          k.out_on_device || !k.len_out ? k.len_out : e->d_len.get(), n_rows};
     if (fit) {
@@ -2069,6 +2127,13 @@ int enc_batch_check(const mbpe_encoder *e, const EncPack &k) {
         const char *msg = "";
         if (e->fim_on) return fail(MBPE_ERR_ARG, "fill-in-the-middle and masked-LM are both on: turn one of them off");
         if (const int rc = mlm_check_spec(&e->mlm, k.token_bits(), &msg)) return fail(rc, msg);
+    }
+    if (e->tp_on) {
+        const char *msg = "";
+        if (e->fim_on || e->mlm_on)
+            return fail(MBPE_ERR_ARG, "textpair is on together with fill-in-the-middle or masked-LM: turn one of them off");
+        if (k.n_docs & 1) return fail(MBPE_ERR_ARG, "textpair: an odd document count: documents 2i and 2i + 1 are a pair");
+        if (const int rc = textpair_check_spec(&e->tp, k.token_bits(), &msg)) return fail(rc, msg);
     }
     if (k.win) return pack_check_windows(k.spec, k.token_bits(), k.aux, k.win, k.n_docs, k.ids_out, k.out_on_device);
     if (k.fit) return pack_check_fit(k.spec, k.token_bits(), k.aux, k.fit, k.n_docs, k.ids_out, k.out_on_device);
@@ -2364,6 +2429,31 @@ int mbpe_encoder_fim_info(mbpe_encoder *e, uint8_t *mode_out, uint64_t *cut_out,
     ECHK(hipSetDevice(e->device));
     if (mode_out) ECHK(hipMemcpyAsync(mode_out, e->d_fim_mode, n, hipMemcpyDeviceToHost, e->stream));
     if (cut_out) ECHK(hipMemcpyAsync(cut_out, e->d_fim_cut, n * 16, hipMemcpyDeviceToHost, e->stream));
+    ECHK(hipStreamSynchronize(e->stream));
+    return MBPE_OK;
+}
+
+int mbpe_encoder_set_textpair(mbpe_encoder *e, const mbpe_textpair_spec *spec) {
+    if (!e) return fail(MBPE_ERR_ARG, "mbpe_encoder_set_textpair: NULL argument");
+    if (spec) {
+        const char *msg = "";
+        if (const int rc = textpair_check_spec(spec, 32, &msg))
+            return fail(rc, std::string("mbpe_encoder_set_textpair: ") + msg);
+        e->tp = *spec;
+    }
+    e->tp_on = spec != nullptr;
+    return MBPE_OK;
+}
+
+int mbpe_encoder_textpair_info(mbpe_encoder *e, uint64_t *kept_out, uint64_t cap_pairs, uint64_t *n_pairs_out) {
+    if (!e || !n_pairs_out) return fail(MBPE_ERR_ARG, "mbpe_encoder_textpair_info: NULL argument");
+    const uint64_t n = e->tp_pairs;
+    *n_pairs_out = n;
+    if (!kept_out) return MBPE_OK;
+    if (cap_pairs < n) return fail(MBPE_ERR_ARG, "mbpe_encoder_textpair_info: room for fewer pairs than the call had");
+    if (n == 0) return MBPE_OK;
+    ECHK(hipSetDevice(e->device));
+    ECHK(hipMemcpyAsync(kept_out, e->d_tp_kept, n * 16, hipMemcpyDeviceToHost, e->stream));
     ECHK(hipStreamSynchronize(e->stream));
     return MBPE_OK;
 }

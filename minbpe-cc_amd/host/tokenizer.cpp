@@ -6,6 +6,7 @@
 
 #include "dropout.h"
 #include "fim.h"
+#include "textpair.h"
 #include "mlm.h"
 #include "mbpe.h"
 #include "mbpe_tokenizer.h"
@@ -71,6 +72,7 @@ mbpe_encoder *Tokenizer::device_encoder(int device) {
     if (rc == MBPE_OK) rc = mbpe_encoder_set_dropout(encoder_, drop_threshold_, drop_seed_);
     if (rc == MBPE_OK) rc = mbpe_encoder_set_fim(encoder_, fim_on_ ? &fim_ : nullptr);
     if (rc == MBPE_OK) rc = mbpe_encoder_set_mlm(encoder_, mlm_on_ ? &mlm_ : nullptr);
+    if (rc == MBPE_OK) rc = mbpe_encoder_set_textpair(encoder_, textpair_on_ ? &textpair_ : nullptr);
     if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
     return encoder_;
 }
@@ -1417,6 +1419,30 @@ int mbpe_tok_encode_fim_info(mbpe_tokenizer *t, uint8_t *mode_out, uint64_t *cut
     *n_docs_out = 0;
     mbpe_encoder *enc = t->t->kept_encoder();
     return enc ? mbpe_encoder_fim_info(enc, mode_out, cut_out, cap_docs, n_docs_out) : MBPE_OK;
+}
+
+int mbpe_tok_set_encode_textpair(mbpe_tokenizer *t, const mbpe_textpair_spec *spec) {
+    if (!t) return MBPE_ERR_ARG;
+    if (spec) {
+        const char *msg = "";
+        const int rc = mbpe::textpair_check_spec(spec, 32, &msg);
+        if (rc != MBPE_OK) {
+            mbpe_host::set_last_error(std::string("mbpe_tok_set_encode_textpair: ") + msg);
+            return rc;
+        }
+    }
+    t->t->set_textpair(spec);
+    return MBPE_OK;
+}
+
+int mbpe_tok_encode_textpair_info(mbpe_tokenizer *t, uint64_t *kept_out, uint64_t cap_pairs, uint64_t *n_pairs_out) {
+    if (!t || !n_pairs_out) {
+        mbpe_host::set_last_error("mbpe_tok_encode_textpair_info: NULL argument");
+        return MBPE_ERR_ARG;
+    }
+    *n_pairs_out = 0;
+    mbpe_encoder *enc = t->t->kept_encoder();
+    return enc ? mbpe_encoder_textpair_info(enc, kept_out, cap_pairs, n_pairs_out) : MBPE_OK;
 }
 
 int mbpe_tok_set_train_dedup(mbpe_tokenizer *t, int on) {

@@ -129,6 +129,8 @@ public:
     void set_fim(const mbpe_fim_spec *spec) { fim_on_ = spec != nullptr; if (spec) fim_ = *spec; }
     // masked-LM corruption of the same calls (mbpe_tok_set_encode_mlm; mbpe.h holds the rule): NULL = off
     void set_mlm(const mbpe_mlm_spec *spec) { mlm_on_ = spec != nullptr; if (spec) mlm_ = *spec; }
+    // text pairs of the same calls (mbpe_tok_set_encode_textpair; mbpe.h holds the rule): NULL = off
+    void set_textpair(const mbpe_textpair_spec *spec) { textpair_on_ = spec != nullptr; if (spec) textpair_ = *spec; }
     mbpe_encoder *kept_encoder() const { return encoder_; }
     // the option "unicode" of every device split made from here on (mbpe_tok_set_split_unicode)
     void set_split_unicode(bool on) { split_unicode_ = on; }
@@ -268,6 +270,8 @@ private:
     mbpe_fim_spec fim_ = {};
     bool mlm_on_ = false;
     mbpe_mlm_spec mlm_ = {};
+    bool textpair_on_ = false;
+    mbpe_textpair_spec textpair_ = {};
     std::vector<uint64_t> counts_;           // count_tokens: the table, and the weighted token total it has reached
     uint64_t counts_total_ = 0;
 };

@@ -58,6 +58,8 @@ EXPORTS = [
     "mbpe_pack_fit_labels", "mbpe_encoder_set_mlm",
     "mbpe_denoise_plan", "mbpe_denoise_tokens", "mbpe_denoise_kernel_ms", "mbpe_encoder_encode_batch_denoise",
     "mbpe_encoder_encode_batch_endmask_denoise",
+    "mbpe_textpair_plan", "mbpe_textpair_tokens", "mbpe_textpair_kernel_ms", "mbpe_encoder_set_textpair",
+    "mbpe_encoder_textpair_info",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -75,6 +77,7 @@ TOK_EXPORTS = [
     "mbpe_tok_encode_batch_windows_device", "mbpe_tok_count_tokens", "mbpe_tok_token_counts",
     "mbpe_tok_token_counts_reset", "mbpe_tok_encode_batch_fit_device", "mbpe_tok_set_encode_fim",
     "mbpe_tok_encode_fim_info", "mbpe_tok_set_encode_mlm", "mbpe_tok_encode_batch_denoise_device",
+    "mbpe_tok_set_encode_textpair", "mbpe_tok_encode_textpair_info",
 ]
 
 
@@ -152,6 +155,19 @@ class FimSpec(ctypes.Structure):
 
 
 FIM_NONE, FIM_PSM, FIM_SPM = 0, 1, 2      # the modes of fim_plan / fim_info
+
+
+class TextpairSpec(ctypes.Structure):
+    """mbpe_textpair_spec (include/mbpe.h): two texts joined into one document; textpair_spec() makes one."""
+    _fields_ = [
+        ("max_tokens", ctypes.c_uint32), ("truncation", ctypes.c_uint32), ("keep_tail_a", ctypes.c_uint32),
+        ("keep_tail_b", ctypes.c_uint32), ("n_sep", ctypes.c_uint32), ("sep_id", ctypes.c_uint32 * 2),
+        ("end_id", ctypes.c_uint32), ("label_mode", ctypes.c_uint32),
+    ]
+
+
+TEXTPAIR_LONGEST_FIRST, TEXTPAIR_ONLY_FIRST, TEXTPAIR_ONLY_SECOND = 0, 1, 2
+TEXTPAIR_LABEL_ALL, TEXTPAIR_LABEL_SECOND = 0, 1
 
 
 class MlmSpec(ctypes.Structure):
@@ -422,6 +438,13 @@ def lib():
     L.mbpe_pack_fit_labels.argtypes = L.mbpe_pack_fit.argtypes + [vp]
     L.mbpe_encoder_set_mlm.argtypes = [vp, vp]
     L.mbpe_tok_set_encode_mlm.argtypes = [vp, vp]
+    L.mbpe_textpair_plan.argtypes = [vp, u64, vp, vp, vp]
+    L.mbpe_textpair_tokens.argtypes = [i32, vp, u64, u32, i32, vp, u64, vp, vp, vp, u64, i32, vp, vp, vp]
+    L.mbpe_textpair_kernel_ms.argtypes = [vp]
+    L.mbpe_encoder_set_textpair.argtypes = [vp, vp]
+    L.mbpe_encoder_textpair_info.argtypes = [vp, vp, u64, vp]
+    L.mbpe_tok_set_encode_textpair.argtypes = [vp, vp]
+    L.mbpe_tok_encode_textpair_info.argtypes = [vp, vp, u64, vp]
     _lib = L
     return L
 
@@ -622,6 +645,87 @@ def fim_kernel_ms():
     ms = ctypes.c_float()
     _check(lib().mbpe_fim_kernel_ms(ctypes.byref(ms)))
     return ms.value
+
+
+def textpair_spec(max_tokens=0, truncation="longest_first", sep_ids=(), end_id=None, labels="all", keep_tail_a=False,
+                  keep_tail_b=False):
+    """A TextpairSpec: a pair (A, B) becomes A' sep.. B' [end] with at most max_tokens ids (0: no truncation), truncated
+    "longest_first", "only_first" or "only_second", each side keeping its first tokens or -- keep_tail_* -- its last.
+    labels "all" gives next-token targets everywhere, "second" only where B' or the end id is predicted (the loss on
+    the response alone).  The rule: include/mbpe.h, mbpe_textpair_spec."""
+    trunc = {"longest_first": 0, "only_first": 1, "only_second": 2}[truncation]
+    sep = [int(x) for x in sep_ids]                        # (more than two: the library refuses n_sep)
+    return TextpairSpec(max_tokens, trunc, int(bool(keep_tail_a)), int(bool(keep_tail_b)), len(sep),
+                        (ctypes.c_uint32 * 2)(*(sep + [0, 0])[:2]), NO_TOKEN if end_id is None else end_id,
+                        {"all": 0, "second": 1}[labels])
+
+
+def textpair_plan(doc_tok_off, spec):
+    """mbpe_textpair_plan (host only): documents 2i and 2i + 1 of these token offsets joined -> (doc_tok_off of the
+    joined documents [n_pairs + 1], kept uint64[n_pairs, 2] = (a, b))."""
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    n_docs = len(off) - 1
+    new_off = np.zeros(n_docs // 2 + 1, dtype=np.uint64)
+    kept = np.zeros((max(n_docs // 2, 1), 2), dtype=np.uint64)
+    _check(lib().mbpe_textpair_plan(off.ctypes.data, n_docs, ctypes.byref(spec), new_off.ctypes.data, kept.ctypes.data))
+    return new_off, kept[:n_docs // 2]
+
+
+def textpair_tokens(tokens, doc_tok_off, spec, device=0, tokens_ptr=None, n_tokens=None, token_bits=None, out_ptr=None,
+                    targets_ptr=None, cap=0):
+    """mbpe_textpair_tokens: documents 2i and 2i + 1 of a flat token array (uint16 or uint32) joined -> (tokens of the
+    same dtype, targets uint32, doc_tok_off of the joined documents, kept uint64[n_pairs, 2]): what the pack_*
+    calls take with label_tokens=targets.  Device memory: tokens_ptr= / n_tokens= / token_bits= name the tokens there
+    instead of `tokens`; with out_ptr= (room for cap tokens; targets_ptr= for as many uint32, or None) ids and targets
+    are written there and (token count, doc_tok_off, kept) is returned."""
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    if tokens_ptr is None:
+        t = np.ascontiguousarray(tokens)
+        if t.dtype not in (np.dtype(np.uint16), np.dtype(np.uint32)):
+            t = t.astype(np.uint32)
+        t = t.reshape(-1)
+        tp, n_tokens, token_bits, on_dev = (t.ctypes.data if len(t) else None), len(t), t.dtype.itemsize * 8, 0
+    else:
+        tp, on_dev = _ptr(tokens_ptr), 1
+    n_pairs = (len(off) - 1) // 2
+    new_off = np.zeros(n_pairs + 1, dtype=np.uint64)
+    kept = np.zeros((max(n_pairs, 1), 2), dtype=np.uint64)
+    n = ctypes.c_uint64()
+    head = (device, tp, n_tokens, token_bits, on_dev, off.ctypes.data, len(off) - 1, ctypes.byref(spec))
+    tail = (new_off.ctypes.data, kept.ctypes.data, ctypes.byref(n))
+    if out_ptr is not None:
+        _check(lib().mbpe_textpair_tokens(*head, _ptr(out_ptr), _ptr(targets_ptr), cap, 1, *tail))
+        return n.value, new_off, kept[:n_pairs]
+    _check(lib().mbpe_textpair_tokens(*head, None, None, 0, 0, *tail))
+    out = np.zeros(max(n.value, 1), dtype=_ID_DTYPES[token_bits])
+    tgt = np.zeros(max(n.value, 1), dtype=np.uint32)
+    _check(lib().mbpe_textpair_tokens(*head, out.ctypes.data, tgt.ctypes.data, n.value, 0, *tail))
+    return out[:n.value], tgt[:n.value], new_off, kept[:n_pairs]
+
+
+def textpair_kernel_ms():
+    """Device time of the kernels of this thread's latest textpair_tokens (mbpe_textpair_kernel_ms)."""
+    ms = ctypes.c_float()
+    _check(lib().mbpe_textpair_kernel_ms(ctypes.byref(ms)))
+    return ms.value
+
+
+def _batch_parts(texts, textpair):
+    """The texts of a Tokenizer batch call as bytes, and the documents behind the stages: with textpair, `texts` is a
+    sequence of (a, b) and every pair is one document."""
+    if textpair is None:
+        parts = [bytes(_u8(t)) for t in texts]
+        return parts, len(parts)
+    parts = [bytes(_u8(t)) for a, b in texts for t in (a, b)]
+    return parts, len(parts) // 2
+
+
+def _textpair_info(fn, handle):
+    n = ctypes.c_uint64()
+    _check(fn(handle, None, 0, ctypes.byref(n)))
+    kept = np.zeros((max(n.value, 1), 2), dtype=np.uint64)
+    _check(fn(handle, kept.ctypes.data, n.value, ctypes.byref(n)))
+    return kept[:n.value]
 
 
 def denoise_spec(density=0.15, mean_span=3.0, sentinel_id=None, n_sentinels=100, sentinel_down=True, segment_tokens=0,
@@ -1280,6 +1384,20 @@ class Encoder:
         to turn it off.  The matrices hold the corrupted ids and "labels" the targets."""
         _check(lib().mbpe_encoder_set_mlm(self._h, None if spec is None else ctypes.byref(spec)))
 
+    def set_textpair(self, spec):
+        """Text pairs for the batch calls that follow (mbpe_encoder_set_textpair): a TextpairSpec (textpair_spec()), or
+        None to turn it off.  Documents 2i and 2i + 1 of a call are joined into one: rows, segments and doc_tok_off are
+        those of the joined documents, and "labels" come from the stage's targets.  Not together with fim or mlm."""
+        _check(lib().mbpe_encoder_set_textpair(self._h, None if spec is None else ctypes.byref(spec)))
+        self._pairs = spec is not None
+
+    _pairs = False                                 # set_textpair is on: a call's outputs are those of half as many documents
+
+    def textpair_info(self):
+        """(a, b), the tokens kept of each side, of every pair of the latest batch call (mbpe_encoder_textpair_info)
+        -> uint64[n_pairs, 2]; no pairs where the stage was off."""
+        return _textpair_info(lib().mbpe_encoder_textpair_info, self._h)
+
     def fim_info(self):
         """The plan of the latest batch call (mbpe_encoder_fim_info) -> (mode uint8[n_docs], cuts uint64[n_docs, 2]);
         all zero where the stage was off."""
@@ -1370,7 +1488,7 @@ class Encoder:
             _check(rc)
             return n_rows.value
         if spec.layout == PACK_PADDED:
-            n_rows.value = len(docs) - 1              # known without a query
+            n_rows.value = (len(docs) - 1) >> self._pairs     # known without a query
         else:
             _check(lib().mbpe_encoder_encode_batch(*head, None, 0, 0, None, *tail))
         ids, lengths = _matrix(n_rows.value, spec)
@@ -1413,7 +1531,7 @@ class Encoder:
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label)
         head, keep = self._batch_head(texts_or_buffer, chunk_off, doc_chunk_off, text_ptr, n_bytes, spec)
-        n_docs = len(keep[-1]) - 1
+        n_docs = (len(keep[-1]) - 1) >> self._pairs   # the documents behind the stages
         n_rows, n_tok = ctypes.c_uint64(), ctypes.c_uint64()
         doc_tok_off = np.zeros(n_docs + 1, dtype=np.uint64)
         tail = (ctypes.byref(n_rows), ctypes.byref(n_tok))
@@ -1449,7 +1567,7 @@ class Encoder:
         call = _WinCall(spec, stride, score_once, labels, positions, segments, ignore_label, row_doc, row_tok0)
         head, keep = self._batch_head(texts_or_buffer, chunk_off, doc_chunk_off, text_ptr, n_bytes, spec)
         n_tok = ctypes.c_uint64()
-        doc_tok_off = np.zeros(len(keep[-1]), dtype=np.uint64)
+        doc_tok_off = np.zeros(((len(keep[-1]) - 1) >> self._pairs) + 1, dtype=np.uint64)
         tail = lambda n_rows, aux, win: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
                                          doc_tok_off.ctypes.data, ctypes.byref(win))
         try:
@@ -1472,7 +1590,7 @@ class Encoder:
         sg = _singles(singles)
         docs = np.ascontiguousarray(doc_off, dtype=np.uint64)
         n_tok = ctypes.c_uint64()
-        doc_tok_off = np.zeros(len(docs), dtype=np.uint64)
+        doc_tok_off = np.zeros(((len(docs) - 1) >> self._pairs) + 1, dtype=np.uint64)
         head = (self._h, _ptr(text_ptr), n_bytes, _ptr(mask_ptr), sg.ctypes.data if len(sg) else None, len(sg),
                 docs.ctypes.data, len(docs) - 1, ctypes.byref(spec))
         tail = lambda n_rows, aux, win: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
@@ -1497,7 +1615,7 @@ class Encoder:
         call = _FitCall(spec, labels, positions, segments, cu_seqlens, ignore_label, doc_row, doc_col)
         head, keep = self._batch_head(texts_or_buffer, chunk_off, doc_chunk_off, text_ptr, n_bytes, spec)
         n_tok = ctypes.c_uint64()
-        doc_tok_off = np.zeros(len(keep[-1]), dtype=np.uint64)
+        doc_tok_off = np.zeros(((len(keep[-1]) - 1) >> self._pairs) + 1, dtype=np.uint64)
         tail = lambda n_rows, aux, fit: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
                                          doc_tok_off.ctypes.data, ctypes.byref(fit))
         try:
@@ -1519,14 +1637,14 @@ class Encoder:
         sg = _singles(singles)
         docs = np.ascontiguousarray(doc_off, dtype=np.uint64)
         n_tok = ctypes.c_uint64()
-        doc_tok_off = np.zeros(len(docs), dtype=np.uint64)
+        doc_tok_off = np.zeros(((len(docs) - 1) >> self._pairs) + 1, dtype=np.uint64)
         head = (self._h, _ptr(text_ptr), n_bytes, _ptr(mask_ptr), sg.ctypes.data if len(sg) else None, len(sg),
                 docs.ctypes.data, len(docs) - 1, ctypes.byref(spec))
         tail = lambda n_rows, aux, fit: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
                                          doc_tok_off.ctypes.data, ctypes.byref(fit))
         try:
-            out = call.run(lib().mbpe_encoder_encode_batch_endmask_fit, head, tail, len(docs) - 1, lambda: doc_tok_off,
-                           out_ptr, len_ptr, cap_rows, (labels_ptr, pos_ptr, seg_ptr, doc_row_ptr, doc_col_ptr))
+            out = call.run(lib().mbpe_encoder_encode_batch_endmask_fit, head, tail, len(doc_tok_off) - 1,
+                           lambda: doc_tok_off, out_ptr, len_ptr, cap_rows, (labels_ptr, pos_ptr, seg_ptr, doc_row_ptr, doc_col_ptr))
         finally:
             self.n_rows, self.n_tokens, self.doc_tok_off = getattr(call, "n_rows", None), n_tok.value, doc_tok_off
         return out
@@ -1584,7 +1702,7 @@ class Encoder:
         docs = np.ascontiguousarray(doc_off, dtype=np.uint64)
         n_docs = len(docs) - 1
         n_rows, n_tok = ctypes.c_uint64(), ctypes.c_uint64()
-        doc_tok_off = np.zeros(n_docs + 1, dtype=np.uint64)
+        doc_tok_off = np.zeros((n_docs >> self._pairs) + 1, dtype=np.uint64)
         head = (self._h, _ptr(text_ptr), n_bytes, _ptr(mask_ptr), sg.ctypes.data if len(sg) else None, len(sg),
                 docs.ctypes.data, n_docs, ctypes.byref(spec))
         tail = (ctypes.byref(n_rows), ctypes.byref(n_tok))
@@ -1598,7 +1716,7 @@ class Encoder:
             _check(rc)
             return n_rows.value
         if spec.layout == PACK_PADDED:
-            n_rows.value = n_docs                     # known without a query
+            n_rows.value = n_docs >> self._pairs      # known without a query
         else:
             aux = call.device(None, None, None) if call else None
             _check(fn(*head, None, 0, 0, None, *tail, ctypes.byref(aux) if call else None, None))
@@ -2671,7 +2789,7 @@ class Tokenizer:
         _check(lib().mbpe_tok_load(self._h, os.fsencode(path), int(verbose)))
 
     def _encode_split(self, device_split, order="greedy", dropout=0.0, seed=0, dedup=False, fim=None, mlm=None,
-                      resident=False):
+                      resident=False, textpair=None):
         if order not in ("greedy", "rank"):
             raise ValueError('order must be "greedy" or "rank"')
         _check(lib().mbpe_tok_set_encode_dedup(self._h, int(bool(dedup))))
@@ -2682,6 +2800,12 @@ class Tokenizer:
         _check(lib().mbpe_tok_set_split_unicode(self._h, int(device_split == "unicode")))
         _check(lib().mbpe_tok_set_encode_fim(self._h, None if fim is None else ctypes.byref(fim)))
         _check(lib().mbpe_tok_set_encode_mlm(self._h, None if mlm is None else ctypes.byref(mlm)))
+        _check(lib().mbpe_tok_set_encode_textpair(self._h, None if textpair is None else ctypes.byref(textpair)))
+
+    def textpair_info(self):
+        """(a, b) of every pair of the latest batch call with a device (mbpe_tok_encode_textpair_info) ->
+        uint64[n_pairs, 2]: the tokens kept of each side."""
+        return _textpair_info(lib().mbpe_tok_encode_textpair_info, self._h)
 
     def fim_info(self):
         """The fill-in-the-middle plan of the latest batch call with a device (mbpe_tok_encode_fim_info) -> (mode
@@ -2793,7 +2917,8 @@ class Tokenizer:
 
     def encode_batch_padded(self, texts, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
                             pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
-                            device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False, resident=False, fim=None):
+                            device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False, resident=False, fim=None,
+                            textpair=None):
         """Every text split like encode(), encoded and packed in one device call
         (mbpe_tok_encode_batch_packed_device) -> (ids [n_rows, seq_len], lengths [n_rows]) as numpy arrays; with
         out_ptr= and len_ptr= (device memory for cap_rows rows) the matrix stays on the device and the row count is
@@ -2801,10 +2926,14 @@ class Tokenizer:
         fim (here and in _aux, _windows and _fit; mbpe_tok_set_encode_fim): a FimSpec (fim_spec()) -- every text's
         tokens go through the fill-in-the-middle transform on the device before they are packed; its sentinel ids may
         be special-token ids; fim_info() tells what was done to each text.  With "padded" rows and truncation a
-        transformed text that does not fit loses its middle: use max_tokens, windows, "packed" or fit there."""
-        self._encode_split(device_split, order, dropout, seed, dedup, fim, resident=resident)
+        transformed text that does not fit loses its middle: use max_tokens, windows, "packed" or fit there.
+        textpair (here and in _aux, _windows and _fit; mbpe_tok_set_encode_textpair): a TextpairSpec (textpair_spec())
+        -- `texts` is then a sequence of (a, b); each pair is truncated and joined on the device into one document
+        a' sep.. b' [end] before it is packed, and "labels" follow the spec's label mode; its sep and end ids may be
+        special-token ids; textpair_info() tells what was kept of each side.  Not together with fim or mlm."""
+        self._encode_split(device_split, order, dropout, seed, dedup, fim, resident=resident, textpair=textpair)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
-        parts = [bytes(_u8(t)) for t in texts]
+        parts, n_out = _batch_parts(texts, textpair)
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
         if parts:
             doc_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
@@ -2817,7 +2946,7 @@ class Tokenizer:
             _check(lib().mbpe_tok_encode_batch_packed_device(*head, _ptr(out_ptr), cap_rows or 0, 1, _ptr(len_ptr), *tail))
             return n_rows.value
         if spec.layout == PACK_PADDED:
-            n_rows.value = len(parts)
+            n_rows.value = n_out
         else:
             _check(lib().mbpe_tok_encode_batch_packed_device(*head, None, 0, 0, None, *tail))
         ids, lengths = _matrix(n_rows.value, spec)
@@ -2861,7 +2990,7 @@ class Tokenizer:
                          pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
                          labels=False, positions=False, segments=False, cu_seqlens=False, ignore_label=-100,
                          labels_ptr=None, pos_ptr=None, seg_ptr=None, device_split=False, order="greedy", dropout=0.0,
-                         seed=0, dedup=False, resident=False, fim=None, mlm=None):
+                         seed=0, dedup=False, resident=False, fim=None, mlm=None, textpair=None):
         """encode_batch_padded plus labels, positions, segments and cu_seqlens (mbpe_tok_encode_batch_aux_device): its
         arguments and those of pack_tokens_aux, whose dict (or, with out_ptr=, row count) is returned.  The documents'
         token offsets of the call (with fim: after the transform): self.doc_tok_off.
@@ -2869,16 +2998,16 @@ class Tokenizer:
         through masked-LM corruption on the device before they are packed: "ids" are the corrupted ids, "labels" the
         targets (ignore_label in every other cell).  whole_word masks the chunks of the split pattern as wholes and
         needs out_bits 32 or 64.  Not together with fim."""
-        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm, resident=resident)
+        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm, resident=resident, textpair=textpair)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label)
-        parts = [bytes(_u8(t)) for t in texts]
+        parts, n_out = _batch_parts(texts, textpair)
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
         if parts:
             doc_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
         text = np.frombuffer(b"".join(parts), dtype=np.uint8)
         n_rows, n_tok = ctypes.c_uint64(), ctypes.c_uint64()
-        doc_tok_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        doc_tok_off = np.zeros(n_out + 1, dtype=np.uint64)
         head = (self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data, len(parts), 0, device,
                 ctypes.byref(spec))
         tail = (ctypes.byref(n_rows), ctypes.byref(n_tok))
@@ -2890,7 +3019,7 @@ class Tokenizer:
             self.doc_tok_off = doc_tok_off
             return (n_rows.value,) + call.cu_seqlens(doc_tok_off) if cu_seqlens else n_rows.value
         if spec.layout == PACK_PADDED:
-            n_rows.value = len(parts)
+            n_rows.value = n_out
         else:
             aux = call.device(None, None, None)
             _check(fn(*head, None, 0, 0, None, *tail, ctypes.byref(aux), None))
@@ -2906,21 +3035,21 @@ class Tokenizer:
                              positions=False, segments=False, ignore_label=-100, labels_ptr=None, pos_ptr=None,
                              seg_ptr=None, row_doc=False, row_tok0=False, row_doc_ptr=None, row_tok0_ptr=None,
                              device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False, resident=False, fim=None,
-                             mlm=None):
+                             mlm=None, textpair=None):
         """encode_batch_aux for the window layout (mbpe_tok_encode_batch_windows_device): every text split like
         encode(), encoded, and cut into rows of seq_len that share `stride` tokens where a text does not fit one --
         the keywords and the result of pack_windows ("row_doc" maps a row back to its text).  The texts' token
         offsets of the call: self.doc_tok_off."""
-        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm, resident=resident)
+        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm, resident=resident, textpair=textpair)
         spec = pack_spec(seq_len, "padded", out_bits, pad_id, bos_id, eos_id)
         call = _WinCall(spec, stride, score_once, labels, positions, segments, ignore_label, row_doc, row_tok0)
-        parts = [bytes(_u8(t)) for t in texts]
+        parts, n_out = _batch_parts(texts, textpair)
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
         if parts:
             doc_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
         text = np.frombuffer(b"".join(parts), dtype=np.uint8)
         n_tok = ctypes.c_uint64()
-        doc_tok_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        doc_tok_off = np.zeros(n_out + 1, dtype=np.uint64)
         head = (self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data, len(parts), 0, device,
                 ctypes.byref(spec))
         tail = lambda n_rows, aux, win: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
@@ -2934,26 +3063,26 @@ class Tokenizer:
                          len_ptr=None, cap_rows=None, labels=False, positions=False, segments=False, cu_seqlens=False,
                          ignore_label=-100, labels_ptr=None, pos_ptr=None, seg_ptr=None, doc_row=False, doc_col=False,
                          doc_row_ptr=None, doc_col_ptr=None, device_split=False, order="greedy", dropout=0.0, seed=0,
-                         dedup=False, resident=False, fim=None, mlm=None):
+                         dedup=False, resident=False, fim=None, mlm=None, textpair=None):
         """encode_batch_aux for the fit layout (mbpe_tok_encode_batch_fit_device): every text split like encode(),
         encoded, and packed whole into rows of seq_len by best fit; only a text longer than a row is cut -- the
         keywords and the result of pack_fit ("doc_row" / "doc_col" say where a text's last piece begins, "segments"
         holds the text's number + 1 in every cell).  The texts' token offsets of the call: self.doc_tok_off."""
-        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm, resident=resident)
+        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm, resident=resident, textpair=textpair)
         spec = _fit_spec(seq_len, out_bits, pad_id, bos_id, eos_id)
         call = _FitCall(spec, labels, positions, segments, cu_seqlens, ignore_label, doc_row, doc_col)
-        parts = [bytes(_u8(t)) for t in texts]
+        parts, n_out = _batch_parts(texts, textpair)
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
         if parts:
             doc_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
         text = np.frombuffer(b"".join(parts), dtype=np.uint8)
         n_tok = ctypes.c_uint64()
-        doc_tok_off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        doc_tok_off = np.zeros(n_out + 1, dtype=np.uint64)
         head = (self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data, len(parts), 0, device,
                 ctypes.byref(spec))
         tail = lambda n_rows, aux, fit: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
                                          doc_tok_off.ctypes.data, ctypes.byref(fit))
-        out = call.run(lib().mbpe_tok_encode_batch_fit_device, head, tail, len(parts), lambda: doc_tok_off, out_ptr,
+        out = call.run(lib().mbpe_tok_encode_batch_fit_device, head, tail, n_out, lambda: doc_tok_off, out_ptr,
                        len_ptr, cap_rows, (labels_ptr, pos_ptr, seg_ptr, doc_row_ptr, doc_col_ptr))
         self.doc_tok_off = doc_tok_off
         return out
