@@ -628,6 +628,11 @@ MBPE_API int  mbpe_encoder_encode(mbpe_encoder *e, const uint8_t *text, uint64_t
  *   "resident"      0 (default) | 1: the rounds of every chunk of at most 256 bytes run in one kernel, on the chip; the
  *                   result is the same, n_passes_out and mbpe_encoder_pass_tokens count the stage as one pass -- see
  *                   mbpe_encoder_resident_stats.
+ *   "fit_planner"   0 (default: the host planner) | 1 (the device planner); any other value is MBPE_ERR_ARG.  With 1,
+ *                   mbpe_encoder_encode_batch_fit and mbpe_encoder_encode_batch_endmask_fit make the best-fit plan on the
+ *                   device, from the documents' token offsets where they lie: the same rows bit for bit -- see "the
+ *                   device planner" below and mbpe_encoder_fit_stats.  With 0 the encoder allocates and launches what
+ *                   it always did.
  * An unknown name or a negative value is MBPE_ERR_ARG. */
 MBPE_API int  mbpe_encoder_set_option(mbpe_encoder *e, const char *name, int64_t value);
 
@@ -1091,6 +1096,30 @@ struct mbpe_pack_fit {    /* a tag, not a typedef: the call below has the name. 
 MBPE_API int  mbpe_pack_fit_plan(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec,
                                  uint32_t *len_out, uint64_t cap_rows, uint64_t *n_rows_out, uint64_t *doc_row_out,
                                  uint32_t *doc_col_out);
+
+/* The device planner: the same plan, made on a HIP device (csrc/pack_fit_dev.hip).  The rule above is evaluated one
+ * size class at a time -- within the class of size s the sequential rule provably fills the rows with free >= s in
+ * (free, row) order, floor(free / s) tails each, and then opens new rows -- so n_rows, len, doc_row, doc_col, the piece
+ * table and row_first are those of the host planner, bit for bit; the host planner stays the rule's executable form.
+ * It serves seq_len <= MBPE_FIT_DEVICE_MAX_SEQ (what its tables in LDS hold), fewer than 2^32 - 1 documents and fewer than
+ * 2^32 rows; outside these limits the host planner runs in its place, with the same result by construction.
+ *   mbpe_pack_fit_plan_device   mbpe_pack_fit_plan behind a device id: the same arguments, the same checks with the same
+ *                     codes before any device call (an error writes nothing), the same outputs in host memory.  Then
+ *                     MBPE_ERR_NO_DEVICE without a usable device.  The offsets go up, 8 bytes per document; n_rows, len,
+ *                     doc_row and doc_col come back.
+ *   mbpe_encoder_fit_stats      the latest fit call of the encoder (all zero before any): out[0] the planner that ran
+ *                     (0 host, 1 device), out[1] the tails, out[2] the size classes that have tails, out[3] the rows the
+ *                     device planner sorted (a bucket of rows with equal room is put in row order when it is first
+ *                     drawn from; 0 from the host planner).
+ * With the encoder's option "fit_planner" the offsets never cross to the host unless doc_tok_off_out asks for them; 64
+ * bytes of counts come back to size the plan's buffers; doc_row / doc_col are copied device to device where fit names
+ * device memory.  The planner's workspace (about 70 bytes per document) is kept: a repeat call of no larger size leaves
+ * mbpe_encoder_alloc_count as it is. */
+#define MBPE_FIT_DEVICE_MAX_SEQ 8192u
+MBPE_API int  mbpe_pack_fit_plan_device(int device_id, const uint64_t *doc_tok_off, uint64_t n_docs,
+                                        const mbpe_pack_spec *spec, uint32_t *len_out, uint64_t cap_rows,
+                                        uint64_t *n_rows_out, uint64_t *doc_row_out, uint32_t *doc_col_out);
+MBPE_API int  mbpe_encoder_fit_stats(const mbpe_encoder *e, uint64_t out[4]);
 
 /* cu_seqlens and max_seqlen of a fit matrix for variable-length attention, on the host alone, with the conventions of
  * mbpe_pack_cu_seqlens (query, cap rule, required outputs).  The list holds the boundaries of the maximal runs of equal

@@ -344,6 +344,11 @@ MBPE_API int mbpe_tok_set_encode_dedup(mbpe_tokenizer *t, int on);
  * encoder is re-configured, not re-created.  The host loop (mbpe_tok_encode) is unaffected. */
 MBPE_API int mbpe_tok_set_encode_resident(mbpe_tokenizer *t, int on);
 
+/* Where the best-fit plan of mbpe_tok_encode_batch_fit is made: 0 (the default) on the host, 1 on the device (the kept
+ * encoder's option "fit_planner", mbpe.h); anything else is MBPE_ERR_ARG.  The matrices, doc_row and doc_col are the
+ * same.  The encoder is re-configured, not re-created. */
+MBPE_API int mbpe_tok_set_encode_fit_planner(mbpe_tokenizer *t, int on);
+
 /* Token frequency tables: how often every token id is used on a corpus, without a token leaving the device.
  * mbpe_tok_count_tokens splits the documents as mbpe_tok_encode_batch_device does (special tokens first, each document on
  * its own) and adds what mbpe_tok_encode would return for each, `repeat` times (at least 1: 0 is MBPE_ERR_ARG), to a

@@ -60,6 +60,7 @@
 #include "hist.h"
 #include "pack.h"
 #include "pack_fit.h"
+#include "pack_fit_dev.h"
 #include "rank.h"
 #include "resident.h"
 #include "span.h"
@@ -721,6 +722,11 @@ struct mbpe_encoder : DevQueue {
     PackFitPlan fit_plan;
     DevBuf<uint8_t> d_fit_pieces;
     DevBuf<unsigned long long> d_fit_rows;
+    // option "fit_planner" (nothing of fit_dev exists while it is 0): the plan is made on the device, from the offsets
+    // where they lie, straight into d_fit_pieces and d_fit_rows.  fit_stats: mbpe_encoder_fit_stats
+    bool fit_planner = false;
+    PackFitDev fit_dev;
+    uint64_t fit_stats[4] = {0, 0, 0, 0};
     float pack_ms = 0.f;                      // the pack kernel of the latest such call
     // mbpe_encoder_set_fim (nothing of this exists while it is off or its rate 0): the spec; the second flat buffer and
     // offset array the stage writes, the plan beside them; the latest batch call's documents and whether the stage ran
@@ -1981,6 +1987,22 @@ int enc_denoise_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool doc
     return MBPE_OK;
 }
 
+// option "fit_planner": does the device planner make this call's plan?  (its limits: pack_fit_dev.h; a text-pair call
+// plans half as many documents, which the limit on all of them covers)
+bool enc_fit_on_device(const mbpe_encoder *e, const EncPack &k) {
+    return k.fit && e->fit_planner && pack_fit_dev_serves(k.n_docs, k.spec->seq_len);
+}
+
+// doc_row and doc_col of the device planner to where fit names them
+int enc_fit_dev_doc_out(mbpe_encoder *e, const struct mbpe_pack_fit &fit, uint64_t n_docs, int out_on_device) {
+    if (!n_docs || (!fit.doc_row && !fit.doc_col)) return MBPE_OK;
+    const hipMemcpyKind kind = out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (fit.doc_row) ECHK(hipMemcpyAsync(fit.doc_row, e->fit_dev.doc_row, n_docs * 8, kind, e->stream));
+    if (fit.doc_col) ECHK(hipMemcpyAsync(fit.doc_col, e->fit_dev.doc_col, n_docs * 4, kind, e->stream));
+    ECHK(hipStreamSynchronize(e->stream));
+    return MBPE_OK;
+}
+
 // the pack step of the batch calls: the flat tokens in e->d_flat, the documents' token offsets in e->doc_tok (host;
 // docs_on_device: in e->d_doc_off already, and on the host only where doc_tok_off_out asks for them).  With
 // fill-in-the-middle on, the stage comes first and everything below reads what it wrote
@@ -1997,12 +2019,13 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
     e->fim_ran = false;
     e->tp_pairs = 0;
     if (k.dn) return enc_denoise_tail(e, k, n_enc, docs_on_device);
+    const bool fit_dev = enc_fit_on_device(e, k);
     const bool tp = e->tp_on && n_docs;                          // (never with fim or mlm, n_docs even: enc_batch_check)
     const bool tp_labels = tp && aux && aux->labels;
     if (tp) {
         // (the host sees the offsets where it asks for them, where the fit plan is made of them, or where a joined
         // document -- no more than all tokens, one pair's separators and end id, bos and eos -- could be too long for pos)
-        const bool to_host = k.doc_tok_off_out || fit || (aux && n_enc + textpair_extra(e->tp) + 2 >= (1ull << 32));
+        const bool to_host = k.doc_tok_off_out || (fit && !fit_dev) || (aux && n_enc + textpair_extra(e->tp) + 2 >= (1ull << 32));
         if ((rc = enc_textpair_stage(e, k, n_enc, docs_on_device, to_host, tp_labels, &n_tokens, &rows_ms)) != MBPE_OK)
             return rc;
         e->pack_ms = rows_ms;
@@ -2011,7 +2034,7 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
     }
     const bool fim = e->fim_on && e->fim.rate && n_enc;
     if (fim) {
-        const bool to_host = k.doc_tok_off_out || fit || (aux && n_enc + 3 * n_docs + 2 >= (1ull << 32));
+        const bool to_host = k.doc_tok_off_out || (fit && !fit_dev) || (aux && n_enc + 3 * n_docs + 2 >= (1ull << 32));
         if ((rc = enc_fim_stage(e, k, n_enc, docs_on_device, to_host, &n_tokens, &rows_ms)) != MBPE_OK) return rc;
         e->pack_ms = rows_ms;
         if (aux && to_host && (rc = pack_check_aux(spec, aux, e->doc_tok.data(), n_docs, nullptr, 0)) != MBPE_OK) return rc;
@@ -2022,11 +2045,46 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
         e->pack_ms = rows_ms;
     }
     uint64_t n_rows = win ? 0 : pack_rows(spec, n_tokens, n_docs);
-    if (fit) {
+    bool fit_planned = false;                                    // the device planner has made the plan
+    if (fit_dev) {
+        // the offsets are planned where they lie (a batch call with host offsets sends them up first)
+        const bool upload = !docs_on_device && !fim && !mlm && !tp;
+        if (upload) {
+            if ((rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem)) != MBPE_OK) return rc;
+            ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
+        }
+        const unsigned long long *off = fim ? e->d_fim_off : tp ? e->d_tp_off : e->d_doc_off;
+        float plan_ms = 0.f;
+        ECHK(hipEventRecord(e->ev0, e->stream));
+        rc = pack_fit_dev_plan(e->stream, e->mem, &e->fit_dev, off, n_docs, spec.seq_len,
+                               (spec.bos_id != MBPE_NO_TOKEN) + (spec.eos_id != MBPE_NO_TOKEN), false, &e->d_fit_pieces,
+                               &e->d_fit_rows, &n_rows, &fit_planned);
+        if (rc == MBPE_OK) rc = e->finish(&plan_ms);
+        if (rc != MBPE_OK) return rc;
+        rows_ms += plan_ms;
+        e->pack_ms = rows_ms;
+        e->last_ms += plan_ms;
+        if (fit_planned) std::copy(e->fit_dev.stats, e->fit_dev.stats + 4, e->fit_stats);
+        else if (!upload) {                                      // 2^32 rows: the host planner needs the offsets
+            e->doc_tok.resize(n_docs + 1);
+            ECHK(hipMemcpyAsync(e->doc_tok.data(), off, (n_docs + 1) * 8, hipMemcpyDeviceToHost, e->stream));
+            ECHK(hipStreamSynchronize(e->stream));
+        }
+    }
+    if (fit && !fit_planned) {
         // the rows depend on the plan, and the plan is host work: from e->doc_tok, which both callers have filled
         if ((rc = pack_fit_make(e->doc_tok.data(), n_docs, spec, &e->fit_plan)) != MBPE_OK) return rc;
         n_rows = e->fit_plan.n_rows;
+        uint64_t classes = 0;                                    // (the tails lie by size)
+        for (size_t t = 0; t < e->fit_plan.tails.size(); ++t)
+            classes += t == 0 || e->fit_plan.tails[t].size != e->fit_plan.tails[t - 1].size;
+        const uint64_t st[4] = {0, e->fit_plan.tails.size(), classes, 0};
+        std::copy(st, st + 4, e->fit_stats);
     }
+    auto fit_doc_out = [&]() -> int {
+        return fit_planned ? enc_fit_dev_doc_out(e, *fit, n_docs, k.out_on_device)
+                           : pack_fit_doc_out(e->stream, *fit, e->fit_plan, k.out_on_device);
+    };
     if (win && n_docs) {
         // the row count depends on the tokens: k_win_rows, the scan and k_win_offsets over the device's offsets, then the total
         rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
@@ -2053,10 +2111,10 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
     if (k.ids_out && k.cap_rows < n_rows) return fail(MBPE_ERR_ARG, "ids_out too small");
     if (k.doc_tok_off_out) std::copy(e->doc_tok.begin(), e->doc_tok.end(), k.doc_tok_off_out);   // (filled in both cases)
     if (!k.ids_out) return MBPE_OK;                              // the query
-    if (n_rows == 0) return fit ? pack_fit_doc_out(e->stream, *fit, e->fit_plan, k.out_on_device) : MBPE_OK;
+    if (n_rows == 0) return fit ? fit_doc_out() : MBPE_OK;
     const uint64_t id_bytes = n_rows * spec.seq_len * (spec.out_bits / 8), cell_bytes = n_rows * spec.seq_len * 4;
     rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
-    if (rc == MBPE_OK && fit) {
+    if (rc == MBPE_OK && fit && !fit_planned) {
         rc = e->d_fit_pieces.reserve(pack_fit_piece_bytes(e->fit_plan), e->mem);
         if (rc == MBPE_OK) rc = e->d_fit_rows.reserve((n_rows + 1) * 8, e->mem);
     }
@@ -2079,14 +2137,14 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
         }
     }
     if (rc != MBPE_OK) return rc;
-    if (!docs_on_device && !win && !fim && !mlm && !tp)
+    if (!docs_on_device && !win && !fim && !mlm && !tp && !fit_dev)
         ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
     const PackSrc src = {fim ? e->d_fim_flat.get() : mlm ? e->d_mlm_flat.get() : tp ? e->d_tp_flat.get() : e->d_flat.get(),
                          fim ? e->d_fim_off : tp ? e->d_tp_off : e->d_doc_off, n_docs, n_tokens, k.token_bits(),
                          mlm ? e->d_mlm_tgt.get() : tp_labels ? e->d_tp_tgt.get() : nullptr};
     const PackDst dst = {k.out_on_device ? k.ids_out : e->d_ids.get(),
                          k.out_on_device || !k.len_out ? k.len_out : e->d_len.get(), n_rows};
-    if (fit) {
+    if (fit && !fit_planned) {
         ECHK(hipMemcpyAsync(e->d_fit_pieces, e->fit_plan.pieces.data(), pack_fit_piece_bytes(e->fit_plan),
                             hipMemcpyHostToDevice, e->stream));
         ECHK(hipMemcpyAsync(e->d_fit_rows, e->fit_plan.row_first.data(), (n_rows + 1) * 8, hipMemcpyHostToDevice, e->stream));
@@ -2109,7 +2167,7 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
         if (win && win->row_tok0) ECHK(hipMemcpyAsync(win->row_tok0, e->d_row_tok0, n_rows * 8, hipMemcpyDeviceToHost, e->stream));
         ECHK(hipStreamSynchronize(e->stream));
     }
-    return fit ? pack_fit_doc_out(e->stream, *fit, e->fit_plan, k.out_on_device) : MBPE_OK;
+    return fit ? fit_doc_out() : MBPE_OK;
 }
 
 // what the batch calls check alike once their own arguments are in order (the document lengths: after the encode)
@@ -2353,6 +2411,11 @@ int mbpe_encoder_set_option(mbpe_encoder *e, const char *name, int64_t value) {
     if (strcmp(name, "resident") == 0) {
         if (value != 0 && value != 1) return fail(MBPE_ERR_ARG, "resident must be 0 or 1");
         e->resident = value == 1;
+        return MBPE_OK;
+    }
+    if (strcmp(name, "fit_planner") == 0) {
+        if (value != 0 && value != 1) return fail(MBPE_ERR_ARG, "fit_planner must be 0 (host) or 1 (device)");
+        e->fit_planner = value == 1;
         return MBPE_OK;
     }
     if (strcmp(name, "dedup") == 0) {
@@ -2634,7 +2697,7 @@ static int enc_batch_endmask(const std::string &who, mbpe_encoder *e, const uint
         if (rc != MBPE_OK) return rc;
         // the offsets stay on the device; the host sees them where it asks for them, or where a document could be too
         // long for pos (only a text of 2^32 bytes or more), or where the fit plan is made of them
-        const bool to_host = doc_tok_off_out || fit || (aux && n_bytes + 2 >= (1ull << 32));
+        const bool to_host = doc_tok_off_out || (fit && !enc_fit_on_device(e, k)) || (aux && n_bytes + 2 >= (1ull << 32));
         e->doc_tok.assign(n_docs + 1, 0);
         a.doc_tok_off_out = to_host ? e->doc_tok.data() : nullptr;
         rc = enc_endmask_body(e, a);
@@ -2827,6 +2890,12 @@ int mbpe_encoder_pass_tokens(const mbpe_encoder *e, uint64_t *tokens_out, uint32
     if (!tokens_out) return MBPE_OK;
     if (cap < e->pass_tokens.size()) return fail(MBPE_ERR_ARG, "tokens_out too small");
     for (size_t k = 0; k < e->pass_tokens.size(); ++k) tokens_out[k] = e->pass_tokens[k];
+    return MBPE_OK;
+}
+
+int mbpe_encoder_fit_stats(const mbpe_encoder *e, uint64_t out[4]) {
+    if (!e || !out) return fail(MBPE_ERR_ARG, "mbpe_encoder_fit_stats: NULL argument");
+    std::copy(e->fit_stats, e->fit_stats + 4, out);
     return MBPE_OK;
 }
 

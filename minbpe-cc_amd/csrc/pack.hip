@@ -33,6 +33,7 @@
 
 #include "hip_host.h"
 #include "pack_fit.h"
+#include "pack_fit_dev.h"
 #include "pack_host.h"
 #include "span.h"
 
@@ -1267,6 +1268,39 @@ int mbpe_pack_fit_plan(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_
     } catch (const std::bad_alloc &) {
         return fail(MBPE_ERR_OOM, "mbpe_pack_fit_plan: host allocation failed");
     }
+}
+
+int mbpe_pack_fit_plan_device(int device_id, const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec,
+                              uint32_t *len_out, uint64_t cap_rows, uint64_t *n_rows_out, uint64_t *doc_row_out,
+                              uint32_t *doc_col_out) {
+    if (n_rows_out) *n_rows_out = 0;
+    if (!doc_tok_off || !spec || !n_rows_out) return fail(MBPE_ERR_ARG, "mbpe_pack_fit_plan_device: NULL argument");
+    int rc = fit_host_check(doc_tok_off, n_docs, spec);
+    if (rc != MBPE_OK) return rc;
+    if ((rc = find_device(device_id)) != MBPE_OK) return rc;
+    if (!pack_fit_dev_serves(n_docs, spec->seq_len))             // (beyond the planner's limits: the same plan from the host)
+        return mbpe_pack_fit_plan(doc_tok_off, n_docs, spec, len_out, cap_rows, n_rows_out, doc_row_out, doc_col_out);
+    OneShot dev;
+    if ((rc = dev.open(device_id)) != MBPE_OK) return rc;
+    void *d_off = nullptr;
+    if ((rc = dev.alloc(&d_off, (n_docs + 1) * 8, doc_tok_off)) != MBPE_OK) return rc;
+    PackFitDev w;
+    DevBuf<uint8_t> d_pieces;
+    DevBuf<unsigned long long> d_rows;
+    uint64_t n_rows = 0;
+    bool served = false;
+    rc = pack_fit_dev_plan(dev.stream, dev.mem, &w, static_cast<const unsigned long long *>(d_off), n_docs, spec->seq_len,
+                           (spec->bos_id != MBPE_NO_TOKEN) + (spec->eos_id != MBPE_NO_TOKEN), len_out != nullptr, &d_pieces,
+                           &d_rows, &n_rows, &served);
+    if (rc != MBPE_OK) return rc;
+    if (!served) return mbpe_pack_fit_plan(doc_tok_off, n_docs, spec, len_out, cap_rows, n_rows_out, doc_row_out, doc_col_out);
+    *n_rows_out = n_rows;
+    if (len_out && cap_rows < n_rows) return fail(MBPE_ERR_ARG, "len_out too small");
+    if (len_out && n_rows) PCHK(hipMemcpyAsync(len_out, w.d_len, n_rows * 4, hipMemcpyDeviceToHost, dev.stream));
+    if (doc_row_out && n_docs) PCHK(hipMemcpyAsync(doc_row_out, w.doc_row, n_docs * 8, hipMemcpyDeviceToHost, dev.stream));
+    if (doc_col_out && n_docs) PCHK(hipMemcpyAsync(doc_col_out, w.doc_col, n_docs * 4, hipMemcpyDeviceToHost, dev.stream));
+    PCHK(hipStreamSynchronize(dev.stream));
+    return MBPE_OK;
 }
 
 int mbpe_pack_fit_cu_seqlens(const uint64_t *doc_tok_off, uint64_t n_docs, const mbpe_pack_spec *spec, int32_t *cu_out,

@@ -69,6 +69,7 @@ mbpe_encoder *Tokenizer::device_encoder(int device) {
     int rc = mbpe_encoder_set_option(encoder_, "rank_order", rank_order_ ? 1 : 0);
     if (rc == MBPE_OK) rc = mbpe_encoder_set_option(encoder_, "dedup", encode_dedup_ ? 1 : 0);
     if (rc == MBPE_OK) rc = mbpe_encoder_set_option(encoder_, "resident", encode_resident_ ? 1 : 0);
+    if (rc == MBPE_OK) rc = mbpe_encoder_set_option(encoder_, "fit_planner", encode_fit_planner_ ? 1 : 0);
     if (rc == MBPE_OK) rc = mbpe_encoder_set_dropout(encoder_, drop_threshold_, drop_seed_);
     if (rc == MBPE_OK) rc = mbpe_encoder_set_fim(encoder_, fim_on_ ? &fim_ : nullptr);
     if (rc == MBPE_OK) rc = mbpe_encoder_set_mlm(encoder_, mlm_on_ ? &mlm_ : nullptr);
@@ -1506,6 +1507,16 @@ int mbpe_tok_set_encode_resident(mbpe_tokenizer *t, int on) {
         return MBPE_ERR_ARG;
     }
     t->t->set_encode_resident(on == 1);
+    return MBPE_OK;
+}
+
+int mbpe_tok_set_encode_fit_planner(mbpe_tokenizer *t, int on) {
+    if (!t) return MBPE_ERR_ARG;
+    if (on != 0 && on != 1) {
+        mbpe_host::set_last_error("mbpe_tok_set_encode_fit_planner: on must be 0 (host) or 1 (device)");
+        return MBPE_ERR_ARG;
+    }
+    t->t->set_encode_fit_planner(on == 1);
     return MBPE_OK;
 }
 

@@ -150,6 +150,8 @@ public:
     void set_encode_dedup(bool on) { encode_dedup_ = on; }
     // ... and run the kept encoder with its option "resident" (mbpe_tok_set_encode_resident)
     void set_encode_resident(bool on) { encode_resident_ = on; }
+    // ... and with its option "fit_planner" (mbpe_tok_set_encode_fit_planner)
+    void set_encode_fit_planner(bool on) { encode_fit_planner_ = on; }
     // :725-751; device >= 0 expands the tokens on that HIP device (mbpe_decode_tokens) instead of the host loop
     std::string decode(const std::vector<Token> &tokens, bool verbose, int device = -1);
     // decode() of every token list, [i] == decode(docs[i], false, -1), in one mbpe_decode_batch on HIP device `device`
@@ -264,6 +266,7 @@ private:
     int64_t train_min_frequency_ = 0, train_max_token_length_ = 0;
     bool encode_dedup_ = false;
     bool encode_resident_ = false;
+    bool encode_fit_planner_ = false;
     bool rank_order_ = false;
     uint64_t drop_threshold_ = 0, drop_seed_ = 0;
     bool fim_on_ = false;

@@ -51,7 +51,7 @@ EXPORTS = [
     "mbpe_pack_windows", "mbpe_encoder_encode_batch_windows", "mbpe_encoder_encode_batch_endmask_windows",
     "mbpe_token_counts", "mbpe_token_counts_kernel_ms", "mbpe_encoder_count", "mbpe_encoder_count_endmask",
     "mbpe_encoder_counts", "mbpe_encoder_counts_reset",
-    "mbpe_pack_fit", "mbpe_pack_fit_plan", "mbpe_pack_fit_cu_seqlens", "mbpe_encoder_encode_batch_fit",
+    "mbpe_pack_fit", "mbpe_pack_fit_plan", "mbpe_pack_fit_plan_device", "mbpe_encoder_fit_stats", "mbpe_pack_fit_cu_seqlens", "mbpe_encoder_encode_batch_fit",
     "mbpe_encoder_encode_batch_endmask_fit",
     "mbpe_fim_plan", "mbpe_fim_tokens", "mbpe_fim_kernel_ms", "mbpe_encoder_set_fim", "mbpe_encoder_fim_info",
     "mbpe_mlm_plan", "mbpe_mlm_tokens", "mbpe_mlm_kernel_ms", "mbpe_pack_tokens_aux_labels", "mbpe_pack_windows_labels",
@@ -70,7 +70,7 @@ TOK_EXPORTS = [
     "mbpe_tok_train_split_device", "mbpe_tok_set_encode_split", "mbpe_tok_set_split_unicode",
     "mbpe_tok_set_encode_order", "mbpe_tok_train_continue", "mbpe_tok_encode_byteoff",
     "mbpe_tok_encode_batch_byteoff_device", "mbpe_tok_set_encode_dropout", "mbpe_tok_set_train_dedup",
-    "mbpe_tok_set_encode_dedup", "mbpe_tok_set_encode_resident", "mbpe_tok_set_train_resident", "mbpe_tok_set_train_regions",
+    "mbpe_tok_set_encode_dedup", "mbpe_tok_set_encode_resident", "mbpe_tok_set_encode_fit_planner", "mbpe_tok_set_train_resident", "mbpe_tok_set_train_regions",
     "mbpe_tok_train_pieces_begin", "mbpe_tok_train_pieces_add",
     "mbpe_tok_train_pieces_finish", "mbpe_tok_train_pieces_abort", "mbpe_tok_set_train_limits",
     "mbpe_tok_train_pieces_export_size", "mbpe_tok_train_pieces_export", "mbpe_tok_train_pieces_merge",
@@ -111,6 +111,7 @@ class Stats(ctypes.Structure):
 PACK_PADDED, PACK_PACKED = 0, 1
 SPLIT_BLOCK, SPLIT_TILE, SPLIT_MAX_SPAN = 64, 16384, 4096      # MBPE_SPLIT_BLOCK, _TILE, _MAX_SPAN
 NO_TOKEN = 0xFFFFFFFF
+FIT_DEVICE_MAX_SEQ = 8192                    # MBPE_FIT_DEVICE_MAX_SEQ: the longest rows the device fit planner serves
 
 
 class PackSpec(ctypes.Structure):
@@ -302,6 +303,8 @@ def lib():
     L.mbpe_tok_encode_batch_windows_device.argtypes = L.mbpe_tok_encode_batch_aux_device.argtypes + [vp]
     L.mbpe_pack_fit.argtypes = L.mbpe_pack_tokens_aux.argtypes + [vp]
     L.mbpe_pack_fit_plan.argtypes = [vp, u64, vp, vp, u64, vp, vp, vp]
+    L.mbpe_pack_fit_plan_device.argtypes = [i32, vp, u64, vp, vp, u64, vp, vp, vp]
+    L.mbpe_encoder_fit_stats.argtypes = [vp, vp]
     L.mbpe_pack_fit_cu_seqlens.argtypes = L.mbpe_pack_cu_seqlens.argtypes
     L.mbpe_encoder_encode_batch_fit.argtypes = L.mbpe_encoder_encode_batch_aux.argtypes + [vp]
     L.mbpe_tok_encode_batch_fit_device.argtypes = L.mbpe_tok_encode_batch_aux_device.argtypes + [vp]
@@ -367,6 +370,7 @@ def lib():
     L.mbpe_tok_set_encode_dedup.argtypes = [vp, i32]
     L.mbpe_encoder_resident_stats.argtypes = [vp, vp, vp, vp]
     L.mbpe_tok_set_encode_resident.argtypes = [vp, i32]
+    L.mbpe_tok_set_encode_fit_planner.argtypes = [vp, i32]
     L.mbpe_tok_set_train_resident.argtypes = [vp, i32]
     L.mbpe_tok_set_train_regions.argtypes = [vp, i32]
     L.mbpe_wordcount_create.argtypes = [i32, ctypes.POINTER(vp)]
@@ -1151,27 +1155,37 @@ def _fit_spec(seq_len, out_bits=32, pad_id=0, bos_id=None, eos_id=None):
     return pack_spec(seq_len, "packed", out_bits, pad_id, bos_id, eos_id)
 
 
-def pack_fit_plan(doc_tok_off, seq_len, bos_id=None, eos_id=None):
+def _fit_planner_flag(planner):
+    if planner not in ("host", "device"):
+        raise ValueError('fit_planner must be "host" or "device"')
+    return int(planner == "device")
+
+
+def pack_fit_plan(doc_tok_off, seq_len, bos_id=None, eos_id=None, device=None):
     """mbpe_pack_fit_plan: where best-fit packing puts documents of these token offsets into rows of seq_len -> a
     dict with "n_rows", "lengths" (uint32, the cells used per row), "doc_row" (uint64) and "doc_col" (uint32): the cell
     of the first element of every document's last piece (2^64 - 1 and 0 for a document without elements).  Host
-    arithmetic alone: needs no device."""
+    arithmetic alone: needs no device.  device=<id>: mbpe_pack_fit_plan_device, the same plan made by the device planner
+    (seq_len up to FIT_DEVICE_MAX_SEQ; beyond its limits the host planner answers)."""
     spec = _fit_spec(seq_len, bos_id=bos_id, eos_id=eos_id)
     off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
     n_docs = len(off) - 1
     n_rows = ctypes.c_uint64()
     head = (off.ctypes.data, n_docs, ctypes.byref(spec))
+    plan = lib().mbpe_pack_fit_plan
+    if device is not None:
+        plan = lambda *a: lib().mbpe_pack_fit_plan_device(int(device), *a)
     # one plan, not a query and a plan: there are no more rows than pieces.  (A count beyond reason -- offsets that
     # descend wrap to one -- goes to the query, which refuses what the library refuses)
     T = np.diff(off) + np.uint64((bos_id is not None) + (eos_id is not None))
     cap = int((T // np.uint64(max(seq_len, 1))).sum() + np.count_nonzero(T)) if n_docs > 0 else 0
     if cap >> 32:
-        _check(lib().mbpe_pack_fit_plan(*head, None, 0, ctypes.byref(n_rows), None, None))
+        _check(plan(*head, None, 0, ctypes.byref(n_rows), None, None))
         cap = n_rows.value
     lengths = np.zeros(cap, dtype=np.uint32)
     doc_row, doc_col = np.zeros(n_docs, dtype=np.uint64), np.zeros(n_docs, dtype=np.uint32)
     ptr = lambda a: a.ctypes.data if len(a) else None
-    _check(lib().mbpe_pack_fit_plan(*head, ptr(lengths), len(lengths), ctypes.byref(n_rows), ptr(doc_row), ptr(doc_col)))
+    _check(plan(*head, ptr(lengths), len(lengths), ctypes.byref(n_rows), ptr(doc_row), ptr(doc_col)))
     return {"n_rows": n_rows.value, "lengths": lengths[:n_rows.value], "doc_row": doc_row, "doc_col": doc_col}
 
 
@@ -1323,8 +1337,10 @@ class Encoder:
     the work buffers kept between calls."""
 
     def __init__(self, merges, device=0, rank_order=False, dropout=0.0, seed=0, dedup=False, count_ids=None,
-                 resident=False):
-        """count_ids: the option "count_ids" from the start: the table of count() has max(256 + n_merges, count_ids) bins.
+                 resident=False, fit_planner="host"):
+        """fit_planner: "host" (default) or "device": the option "fit_planner" from the start: who makes the best-fit plan
+        of encode_batch_fit and encode_batch_endmask_fit (the same rows; fit_stats() says who did).
+        count_ids: the option "count_ids" from the start: the table of count() has max(256 + n_merges, count_ids) bins.
         rank_order: the option "rank_order" from the start (set_option changes it between calls).
         dropout, seed: BPE-dropout from the start (set_dropout changes it between calls); needs rank_order.
         dedup: the option "dedup" from the start: every call dedups its chunks on the device, encodes the distinct
@@ -1342,6 +1358,8 @@ class Encoder:
             self.set_option("dedup", 1)
         if resident:
             self.set_option("resident", 1)
+        if _fit_planner_flag(fit_planner):
+            self.set_option("fit_planner", 1)
         if count_ids is not None:
             self.set_option("count_ids", count_ids)
 
@@ -1850,6 +1868,13 @@ class Encoder:
         n = ctypes.c_uint64()
         _check(lib().mbpe_encoder_alloc_count(self._h, ctypes.byref(n)))
         return n.value
+
+    def fit_stats(self):
+        """The latest fit call (mbpe_encoder_fit_stats) -> (planner that ran: 0 host, 1 device; tails; size classes with
+        tails; rows the device planner sorted).  All zero before any."""
+        v = (ctypes.c_uint64 * 4)()
+        _check(lib().mbpe_encoder_fit_stats(self._h, v))
+        return tuple(int(x) for x in v)
 
     def resident_stats(self):
         """The latest call with the option "resident" (mbpe_encoder_resident_stats) -> dict: tiles, raw_tiles (those at
@@ -2770,6 +2795,11 @@ class Tokenizer:
         except BaseException:
             lib().mbpe_tok_train_pieces_abort(self._h)
             raise
+
+    def set_fit_planner(self, planner):
+        """"host" (default) or "device": who makes the best-fit plan of encode_batch_fit from here on
+        (mbpe_tok_set_encode_fit_planner); the same matrices either way."""
+        _check(lib().mbpe_tok_set_encode_fit_planner(self._h, _fit_planner_flag(planner)))
 
     def set_merges(self, merges):
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1, 2)
