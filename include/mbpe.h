@@ -1533,6 +1533,93 @@ MBPE_API int  mbpe_textpair_kernel_ms(float *ms_out);
 MBPE_API int  mbpe_encoder_set_textpair(mbpe_encoder *e, const mbpe_textpair_spec *spec);
 MBPE_API int  mbpe_encoder_textpair_info(mbpe_encoder *e, uint64_t *kept_out, uint64_t cap_pairs, uint64_t *n_pairs_out);
 
+/* ---- multi-turn conversation batches ----------------------------------------- */
+
+/* Chat data joined into one document per conversation, between encode and pack: a system prompt and any number of user
+ * and assistant turns, an end-of-turn id behind each turn, the loss on the assistant turns, and -- where a conversation
+ * does not fit -- its oldest turns dropped whole.  A call has n_docs documents, the TURNS, and two host arrays:
+ *   turn_off[n_convs + 1]  ascending, turn_off[0] == 0, turn_off[n_convs] == n_docs: conversation c owns the turns
+ *                          turn_off[c] .. turn_off[c + 1]; it may have none
+ *   flags[n_docs]          MBPE_TURN_TRAIN: the turn is trained; MBPE_TURN_NO_END: no turn-end id behind it (a role
+ *                          header such as "<|assistant|>\n" is a turn of its own with NO_END and without TRAIN)
+ * The FULL STREAM of a conversation of m turns: each turn's tokens, then turn_end_id where it is set and the turn lacks
+ * NO_END; behind all turns end_id where it is set.  It has N ids.  An id is TRAINED iff it is a token or the turn-end id
+ * of a turn with TRAIN; end_id is trained iff the conversation's last turn has TRAIN (never with m == 0).
+ * Truncation with K = max_tokens != 0 (0: the full stream):
+ *   RIGHT        the first min(N, K) ids
+ *   LEFT         the last min(N, K) ids
+ *   DROP_OLDEST  with h = min(head_turns, m) and F(j) = the ids of turns [0, h) + the ids of turns [j, m) (turn-end ids
+ *                included) + the end id: take the smallest j in [h, m] with F(j) <= K, j = m where there is none; then,
+ *                while j < m and turn j has TRAIN, ++j (a kept history never opens on an answer without its question;
+ *                this step also runs where nothing had to be dropped).  The stream is the head, turns [j, m) and the end
+ *                id, cut RIGHT to K -- which only bites when the head alone is too long
+ * Beside the kept stream goes a target stream, one uint32 per kept id: target[k] = the id at k + 1 where position k + 1
+ * exists in the kept stream and -- LABEL_TRAINED -- is trained; MBPE_NO_TOKEN elsewhere.  These are next-token labels in
+ * the cell of the predicting token: what label_tokens means to the _labels packers.  Info per conversation is (dropped,
+ * cut): the whole turns dropped, j - h (0 in the other modes), and the ids the RIGHT or LEFT cut removed.  Tokens are
+ * read as the packers read them (16-bit plain ids, or 32-bit with bit 31 ignored) and written as plain ids of the same
+ * width.  Errors, all before the device is touched: MBPE_ERR_ARG for NULL where something is required, an enum out of
+ * range, a flag bit above 1, a bad turn_off, bad token offsets and a turn_end_id or end_id >= 2^31 - 2; MBPE_ERR_VOCAB for
+ * such an id >= 65,536 with 16-bit tokens. */
+#define MBPE_TURN_TRAIN         1u
+#define MBPE_TURN_NO_END        2u
+#define MBPE_TURNS_RIGHT        0u
+#define MBPE_TURNS_LEFT         1u
+#define MBPE_TURNS_DROP_OLDEST  2u
+#define MBPE_TURNS_LABEL_ALL     0u
+#define MBPE_TURNS_LABEL_TRAINED 1u
+typedef struct {
+    uint32_t max_tokens;   /* the most ids a joined conversation may have, every added id included; 0: no truncation */
+    uint32_t truncation;   /* MBPE_TURNS_RIGHT, _LEFT, _DROP_OLDEST */
+    uint32_t head_turns;   /* leading turns DROP_OLDEST never drops (the system prompt); ignored by the other modes */
+    uint32_t turn_end_id;  /* an id behind every turn without NO_END; MBPE_NO_TOKEN: none */
+    uint32_t end_id;       /* an id behind the last turn; MBPE_NO_TOKEN: none */
+    uint32_t label_mode;   /* MBPE_TURNS_LABEL_ALL, _TRAINED */
+} mbpe_turns_spec;         /* 24 bytes */
+
+/* The plan alone, on the host (never MBPE_ERR_NO_DEVICE): doc_tok_off (n_docs + 1) the turns' token offsets;
+ * doc_tok_off_out (n_convs + 1, required) = the joined documents' token offsets; kept_out (2 per conversation, or NULL)
+ * = dropped, cut.  The ids are checked as for 32-bit tokens. */
+MBPE_API int  mbpe_turns_plan(const uint64_t *doc_tok_off, uint64_t n_docs, const uint64_t *turn_off, uint64_t n_convs,
+                              const uint8_t *flags, const mbpe_turns_spec *spec, uint64_t *doc_tok_off_out,
+                              uint64_t *kept_out);
+
+/* The join of a flat token stream on HIP device `device_id`, with the conventions of mbpe_textpair_tokens: tokens in
+ * host or device memory (tokens_on_device); doc_tok_off, turn_off, flags, doc_tok_off_out (n_convs + 1, or NULL) and
+ * kept_out (2 per conversation, or NULL) on the host; tokens_out (cap ids) and targets_out (cap uint32, or NULL: no
+ * targets) both in host or both in device memory (out_on_device; on the device aligned to their elements).  *n_out = the
+ * joined token count.  tokens_out NULL is a query, answered from the host's plan without a device; a cap too small is
+ * MBPE_ERR_ARG: nothing is written and n_out is still reported.  Kernels (csrc/turns.hip): the turns' widths and a 64-bit
+ * scan give every turn's start in the concatenation of all full streams; k_turns_plan, one lane per conversation, the
+ * kept ranges -- DROP_OLDEST by a binary search of those starts -- and a second scan the offsets; k_turns_place one
+ * 16-byte record per turn and end id; k_turns_gather ids and targets in one pass, a lane per 16-byte piece of the joined
+ * stream, the records of a wave's span in LDS.  mbpe_turns_kernel_ms: the device time of the calling thread's latest
+ * such call. */
+MBPE_API int  mbpe_turns_tokens(int device_id, const void *tokens, uint64_t n_tokens, uint32_t token_bits,
+                                int tokens_on_device, const uint64_t *doc_tok_off, uint64_t n_docs, const uint64_t *turn_off,
+                                uint64_t n_convs, const uint8_t *flags, const mbpe_turns_spec *spec, void *tokens_out,
+                                uint32_t *targets_out, uint64_t cap, int out_on_device, uint64_t *doc_tok_off_out,
+                                uint64_t *kept_out, uint64_t *n_out);
+MBPE_API int  mbpe_turns_kernel_ms(float *ms_out);
+
+/* The join as a stage of the encoder's batch calls; spec NULL turns it off (turn_off and flags are then ignored).  The
+ * arrays are copied and hold, like the spec, from the next call on until replaced, for every call that packs (those of
+ * mbpe_encoder_set_fim).  A batch call whose document count is not turn_off[n_convs] is MBPE_ERR_ARG.  The stage runs
+ * between the encode and the pack kernel, into buffers the encoder keeps (a repeat call of no larger size leaves
+ * mbpe_encoder_alloc_count as it is).  Behind it a call has n_convs documents: the rows, the window and fit plans, seg
+ * and doc_tok_off_out, which then has n_convs + 1 entries.  n_tokens_out stays "tokens encoded".  Where aux asks for
+ * labels they come from the target stream, as in the _labels calls; the plain batch call gets the joined ids alone.
+ * MBPE_ERR_ARG from the batch call, never a silent choice: together with mbpe_encoder_set_fim, _set_mlm or
+ * _set_textpair, and in the _denoise calls.  The ids are checked against the width of the tokens a call packs from (16
+ * bits with out_bits 16: MBPE_ERR_VOCAB).  With no spec every call launches and allocates exactly what it does without.
+ * mbpe_encoder_kernel_ms and mbpe_encoder_pack_ms include the stage.
+ * mbpe_encoder_turns_info: (dropped, cut) of every conversation of the latest batch call, on the host: *n_convs_out =
+ * its conversations (0 where the stage was off); kept_out NULL or with room for cap_convs conversations (fewer:
+ * MBPE_ERR_ARG, the count is still reported). */
+MBPE_API int  mbpe_encoder_set_turns(mbpe_encoder *e, const mbpe_turns_spec *spec, const uint64_t *turn_off, uint64_t n_convs,
+                                     const uint8_t *flags);
+MBPE_API int  mbpe_encoder_turns_info(mbpe_encoder *e, uint64_t *kept_out, uint64_t cap_convs, uint64_t *n_convs_out);
+
 /* ---- decode on the device ----------------------------------------------- */
 
 /* Tokenizer::decode (Tokenizer.h:725-751) for whole token streams on HIP device `device_id`: per token a byte

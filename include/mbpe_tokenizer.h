@@ -276,6 +276,20 @@ MBPE_API int mbpe_tok_set_encode_textpair(mbpe_tokenizer *t, const mbpe_textpair
 MBPE_API int mbpe_tok_encode_textpair_info(mbpe_tokenizer *t, uint64_t *kept_out, uint64_t cap_pairs,
                                            uint64_t *n_pairs_out);
 
+/* Multi-turn conversations for the same calls: spec, turn_off, n_convs and flags as for mbpe_encoder_set_turns (mbpe.h,
+ * which holds the rule); spec NULL turns it off.  The arrays are copied and hold until replaced.  While it is on, the
+ * texts of a call are the turns -- a call whose n_docs is not turn_off[n_convs] is MBPE_ERR_ARG -- and the call's rows,
+ * segments and doc_tok_off_out (n_convs + 1 entries) are those of the n_convs joined conversations; the labels of
+ * _aux_device, _windows_device and _fit_device come from the stage's targets.  turn_end_id and end_id may be special-token
+ * ids: the stage writes ids and never looks them up.  Errors as for mbpe_encoder_set_turns; from the batch call
+ * MBPE_ERR_ARG while fill-in-the-middle, masked-LM or textpair is on too and in the _denoise_device call, MBPE_ERR_VOCAB
+ * for an id that does not fit a 16-bit matrix.
+ * mbpe_tok_encode_turns_info: mbpe_encoder_turns_info of the kept encoder; no conversations before the first device
+ * call. */
+MBPE_API int mbpe_tok_set_encode_turns(mbpe_tokenizer *t, const mbpe_turns_spec *spec, const uint64_t *turn_off,
+                                       uint64_t n_convs, const uint8_t *flags);
+MBPE_API int mbpe_tok_encode_turns_info(mbpe_tokenizer *t, uint64_t *kept_out, uint64_t cap_convs, uint64_t *n_convs_out);
+
 /* The option "unicode" (mbpe_splitter_set_option) of the device splits this tokenizer makes: 0 (the default) or on.
  * It applies to mbpe_tok_train_split_device and, while mbpe_tok_set_encode_split is on, to the mbpe_tok_encode*_device
  * calls, whose kept splitter is re-configured, not re-created.  Same results; otherwise without effect. */

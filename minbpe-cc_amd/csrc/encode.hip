@@ -56,6 +56,7 @@
 #include "fim.h"
 #include "mlm.h"
 #include "textpair.h"
+#include "turns.h"
 #include "hip_host.h"
 #include "hist.h"
 #include "pack.h"
@@ -752,6 +753,19 @@ struct mbpe_encoder : DevQueue {
     DevBuf<uint32_t> d_tp_tgt;
     DevBuf<unsigned long long> d_tp_off, d_tp_kept;
     uint64_t tp_pairs = 0;
+    // mbpe_encoder_set_turns (nothing on the device exists while it is off): the spec and the call's arrays, copied; the
+    // arrays on the device; the joined flat buffer, its target stream and offsets; the turns' starts, the plan, (dropped,
+    // cut) and the records of turns.hip; the conversations of the latest batch call the stage ran in
+    bool tn_on = false;
+    mbpe_turns_spec tn = {};
+    std::vector<uint64_t> tn_turn_off;
+    std::vector<uint8_t> tn_flags;
+    DevBuf<unsigned long long> d_tn_turn_off;
+    DevBuf<uint8_t> d_tn_flags;
+    DevBuf<void> d_tn_flat;
+    DevBuf<uint32_t> d_tn_tgt;
+    DevBuf<unsigned long long> d_tn_pos, d_tn_off, d_tn_plan, d_tn_info, d_tn_rec;
+    uint64_t tn_convs = 0;
     // the _denoise calls (nothing of this exists before the first one): the two flat streams the stage writes; its index
     // arrays in one buffer (dn_index); the rows' documents; the decoder side's matrix and lengths that go to the host
     DevBuf<void> d_dn_in, d_dn_tg, d_dn_dec_ids;
@@ -1874,6 +1888,53 @@ int enc_textpair_stage(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, boo
     return MBPE_OK;
 }
 
+// the conversation stage of a batch call (mbpe_encoder_set_turns; n_convs > 0, the call's documents are its turns):
+// e->d_flat and the turns' offsets -> e->d_tn_flat, e->d_tn_off and -- targets -- e->d_tn_tgt, which the pack step then
+// reads as n_convs documents and their label tokens.  Two waits, as in enc_textpair_stage
+int enc_turns_stage(mbpe_encoder *e, const EncPack &k, uint64_t n_tokens, bool docs_on_device, bool to_host, bool targets,
+                    uint64_t *n_new, float *ms) {
+    // (no stream has more ids than all tokens, a turn-end id per turn and an end id per conversation)
+    const uint64_t n_docs = k.n_docs, n_convs = e->tn_turn_off.size() - 1, cap = n_tokens + n_docs + n_convs;
+    int rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
+    if (rc == MBPE_OK) rc = e->d_tn_turn_off.reserve((n_convs + 1) * 8, e->mem);
+    if (rc == MBPE_OK) rc = e->d_tn_flags.reserve(std::max<uint64_t>(n_docs, 1), e->mem);
+    if (rc == MBPE_OK) rc = e->d_tn_flat.reserve(cap * (k.token_bits() / 8), e->mem);
+    if (rc == MBPE_OK && targets) rc = e->d_tn_tgt.reserve(cap * 4, e->mem);
+    if (rc == MBPE_OK) rc = e->d_tn_pos.reserve(turns_pos_bytes(n_docs), e->mem);
+    if (rc == MBPE_OK) rc = e->d_tn_off.reserve(turns_off_bytes(n_convs), e->mem);
+    if (rc == MBPE_OK) rc = e->d_tn_plan.reserve(n_convs * 32, e->mem);
+    if (rc == MBPE_OK) rc = e->d_tn_info.reserve(n_convs * 16, e->mem);
+    if (rc == MBPE_OK) rc = e->d_tn_rec.reserve(turns_rec_bytes(n_docs, n_convs), e->mem);
+    if (rc != MBPE_OK) return rc;
+    if (!docs_on_device)
+        ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
+    ECHK(hipMemcpyAsync(e->d_tn_turn_off, e->tn_turn_off.data(), (n_convs + 1) * 8, hipMemcpyHostToDevice, e->stream));
+    if (n_docs) ECHK(hipMemcpyAsync(e->d_tn_flags, e->tn_flags.data(), n_docs, hipMemcpyHostToDevice, e->stream));
+    const TurnsSrc src = {e->d_flat, k.token_bits(), e->d_doc_off, n_docs, e->d_tn_turn_off, n_convs, e->d_tn_flags};
+    const TurnsDst dst = {e->d_tn_flat, targets ? e->d_tn_tgt.get() : nullptr, cap, e->d_tn_pos, e->d_tn_off,
+                          e->d_tn_plan, e->d_tn_info, e->d_tn_rec};
+    ECHK(hipEventRecord(e->ev0, e->stream));
+    turns_launch(e->stream, src, e->tn, dst);
+    if ((rc = e->finish(ms)) != MBPE_OK) return rc;
+    e->last_ms += *ms;
+    unsigned long long total = 0;
+    ECHK(hipMemcpyAsync(&total, e->d_tn_off + n_convs, 8, hipMemcpyDeviceToHost, e->stream));
+    if (to_host) {
+        e->doc_tok.resize(n_convs + 1);
+        ECHK(hipMemcpyAsync(e->doc_tok.data(), e->d_tn_off, (n_convs + 1) * 8, hipMemcpyDeviceToHost, e->stream));
+    }
+    ECHK(hipStreamSynchronize(e->stream));
+    if (total >> 40) return fail(MBPE_ERR_ARG, "turns: more than 2^40 tokens");
+    *n_new = total;
+    e->tn_convs = n_convs;
+    return MBPE_OK;
+}
+
+// the documents the packers of a batch call see: its conversations, its pairs or its documents
+uint64_t enc_docs_behind(const mbpe_encoder *e, uint64_t n_docs) {
+    return e->tn_on ? e->tn_turn_off.size() - 1 : n_docs;
+}
+
 // where the index arrays of the denoise stage lie in e->d_dn_idx, for n_docs documents and room for cap units
 struct DnIndex {
     uint64_t uoff, unit_doc, in_off, tg_off, res, scratch, words;
@@ -1897,6 +1958,7 @@ int enc_denoise_check(const mbpe_encoder *e, const EncPack &k) {
     if (e->fim_on || e->mlm_on)
         return fail(MBPE_ERR_ARG, "fill-in-the-middle or masked-LM is on: they do not apply to the denoise calls, turn them off");
     if (e->tp_on) return fail(MBPE_ERR_ARG, "textpair is on: it does not apply to the denoise calls, turn it off");
+    if (e->tn_on) return fail(MBPE_ERR_ARG, "turns is on: it does not apply to the denoise calls, turn it off");
     if (const int rc = pack_check_spec(dn.dec_spec, k.token_bits())) return rc;
     if (k.spec->layout != MBPE_PACK_PADDED || dn.dec_spec->layout != MBPE_PACK_PADDED)
         return fail(MBPE_ERR_ARG, "the denoise calls take MBPE_PACK_PADDED specs");
@@ -1990,7 +2052,7 @@ int enc_denoise_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool doc
 // option "fit_planner": does the device planner make this call's plan?  (its limits: pack_fit_dev.h; a text-pair call
 // plans half as many documents, which the limit on all of them covers)
 bool enc_fit_on_device(const mbpe_encoder *e, const EncPack &k) {
-    return k.fit && e->fit_planner && pack_fit_dev_serves(k.n_docs, k.spec->seq_len);
+    return k.fit && e->fit_planner && pack_fit_dev_serves(enc_docs_behind(e, k.n_docs), k.spec->seq_len);
 }
 
 // doc_row and doc_col of the device planner to where fit names them
@@ -2018,6 +2080,7 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
     e->fim_docs = n_docs;
     e->fim_ran = false;
     e->tp_pairs = 0;
+    e->tn_convs = 0;
     if (k.dn) return enc_denoise_tail(e, k, n_enc, docs_on_device);
     const bool fit_dev = enc_fit_on_device(e, k);
     const bool tp = e->tp_on && n_docs;                          // (never with fim or mlm, n_docs even: enc_batch_check)
@@ -2030,6 +2093,17 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
             return rc;
         e->pack_ms = rows_ms;
         n_docs /= 2;
+        if (aux && to_host && (rc = pack_check_aux(spec, aux, e->doc_tok.data(), n_docs, nullptr, 0)) != MBPE_OK) return rc;
+    }
+    const bool tn = e->tn_on && e->tn_turn_off.size() > 1;       // (never with fim, mlm or textpair: enc_batch_check)
+    const bool tn_labels = tn && aux && aux->labels;
+    if (tn) {
+        // (a joined conversation has no more than all tokens, a turn-end id per turn, its end id, bos and eos)
+        const bool to_host = k.doc_tok_off_out || (fit && !fit_dev) || (aux && n_enc + n_docs + 3 >= (1ull << 32));
+        if ((rc = enc_turns_stage(e, k, n_enc, docs_on_device, to_host, tn_labels, &n_tokens, &rows_ms)) != MBPE_OK)
+            return rc;
+        e->pack_ms = rows_ms;
+        n_docs = e->tn_convs;
         if (aux && to_host && (rc = pack_check_aux(spec, aux, e->doc_tok.data(), n_docs, nullptr, 0)) != MBPE_OK) return rc;
     }
     const bool fim = e->fim_on && e->fim.rate && n_enc;
@@ -2048,12 +2122,12 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
     bool fit_planned = false;                                    // the device planner has made the plan
     if (fit_dev) {
         // the offsets are planned where they lie (a batch call with host offsets sends them up first)
-        const bool upload = !docs_on_device && !fim && !mlm && !tp;
+        const bool upload = !docs_on_device && !fim && !mlm && !tp && !tn;
         if (upload) {
             if ((rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem)) != MBPE_OK) return rc;
             ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
         }
-        const unsigned long long *off = fim ? e->d_fim_off : tp ? e->d_tp_off : e->d_doc_off;
+        const unsigned long long *off = fim ? e->d_fim_off : tp ? e->d_tp_off : tn ? e->d_tn_off : e->d_doc_off;
         float plan_ms = 0.f;
         ECHK(hipEventRecord(e->ev0, e->stream));
         rc = pack_fit_dev_plan(e->stream, e->mem, &e->fit_dev, off, n_docs, spec.seq_len,
@@ -2090,11 +2164,11 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
         rc = e->d_doc_off.reserve((n_docs + 1) * 8, e->mem);
         if (rc == MBPE_OK) rc = e->d_row_start.reserve(pack_win_scratch_bytes(n_docs), e->mem);
         if (rc != MBPE_OK) return rc;
-        if (!docs_on_device && !fim && !mlm && !tp)
+        if (!docs_on_device && !fim && !mlm && !tp && !tn)
             ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
         float win_ms = 0.f;
         ECHK(hipEventRecord(e->ev0, e->stream));
-        pack_launch_win_rows(e->stream, fim ? e->d_fim_off : tp ? e->d_tp_off : e->d_doc_off, n_docs, spec, *win,
+        pack_launch_win_rows(e->stream, fim ? e->d_fim_off : tp ? e->d_tp_off : tn ? e->d_tn_off : e->d_doc_off, n_docs, spec, *win,
                              e->d_row_start);
         if ((rc = e->finish(&win_ms)) != MBPE_OK) return rc;
         unsigned long long total = 0;
@@ -2137,11 +2211,13 @@ int enc_pack_tail(mbpe_encoder *e, const EncPack &k, uint64_t n_enc, bool docs_o
         }
     }
     if (rc != MBPE_OK) return rc;
-    if (!docs_on_device && !win && !fim && !mlm && !tp && !fit_dev)
+    if (!docs_on_device && !win && !fim && !mlm && !tp && !tn && !fit_dev)
         ECHK(hipMemcpyAsync(e->d_doc_off, e->doc_tok.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream));
-    const PackSrc src = {fim ? e->d_fim_flat.get() : mlm ? e->d_mlm_flat.get() : tp ? e->d_tp_flat.get() : e->d_flat.get(),
-                         fim ? e->d_fim_off : tp ? e->d_tp_off : e->d_doc_off, n_docs, n_tokens, k.token_bits(),
-                         mlm ? e->d_mlm_tgt.get() : tp_labels ? e->d_tp_tgt.get() : nullptr};
+    const PackSrc src = {fim ? e->d_fim_flat.get() : mlm ? e->d_mlm_flat.get() : tp ? e->d_tp_flat.get()
+                                                                              : tn ? e->d_tn_flat.get() : e->d_flat.get(),
+                         fim ? e->d_fim_off : tp ? e->d_tp_off : tn ? e->d_tn_off : e->d_doc_off, n_docs, n_tokens,
+                         k.token_bits(),
+                         mlm ? e->d_mlm_tgt.get() : tp_labels ? e->d_tp_tgt.get() : tn_labels ? e->d_tn_tgt.get() : nullptr};
     const PackDst dst = {k.out_on_device ? k.ids_out : e->d_ids.get(),
                          k.out_on_device || !k.len_out ? k.len_out : e->d_len.get(), n_rows};
     if (fit && !fit_planned) {
@@ -2193,9 +2269,18 @@ int enc_batch_check(const mbpe_encoder *e, const EncPack &k) {
         if (k.n_docs & 1) return fail(MBPE_ERR_ARG, "textpair: an odd document count: documents 2i and 2i + 1 are a pair");
         if (const int rc = textpair_check_spec(&e->tp, k.token_bits(), &msg)) return fail(rc, msg);
     }
-    if (k.win) return pack_check_windows(k.spec, k.token_bits(), k.aux, k.win, k.n_docs, k.ids_out, k.out_on_device);
-    if (k.fit) return pack_check_fit(k.spec, k.token_bits(), k.aux, k.fit, k.n_docs, k.ids_out, k.out_on_device);
-    return k.aux ? pack_check_aux(*k.spec, k.aux, nullptr, k.n_docs, k.ids_out, k.out_on_device) : MBPE_OK;
+    if (e->tn_on) {
+        const char *msg = "";
+        if (e->fim_on || e->mlm_on || e->tp_on)
+            return fail(MBPE_ERR_ARG, "turns is on together with fill-in-the-middle, masked-LM or textpair: turn one of them off");
+        if (k.n_docs != e->tn_turn_off.back())
+            return fail(MBPE_ERR_ARG, "turns: the call's document count is not turn_off[n_convs]");
+        if (const int rc = turns_check_spec(&e->tn, k.token_bits(), &msg)) return fail(rc, msg);
+    }
+    const uint64_t n_behind = enc_docs_behind(e, k.n_docs);
+    if (k.win) return pack_check_windows(k.spec, k.token_bits(), k.aux, k.win, n_behind, k.ids_out, k.out_on_device);
+    if (k.fit) return pack_check_fit(k.spec, k.token_bits(), k.aux, k.fit, n_behind, k.ids_out, k.out_on_device);
+    return k.aux ? pack_check_aux(*k.spec, k.aux, nullptr, n_behind, k.ids_out, k.out_on_device) : MBPE_OK;
 }
 
 // the flat buffer both batch calls encode into, as the request's output
@@ -2517,6 +2602,42 @@ int mbpe_encoder_textpair_info(mbpe_encoder *e, uint64_t *kept_out, uint64_t cap
     if (n == 0) return MBPE_OK;
     ECHK(hipSetDevice(e->device));
     ECHK(hipMemcpyAsync(kept_out, e->d_tp_kept, n * 16, hipMemcpyDeviceToHost, e->stream));
+    ECHK(hipStreamSynchronize(e->stream));
+    return MBPE_OK;
+}
+
+int mbpe_encoder_set_turns(mbpe_encoder *e, const mbpe_turns_spec *spec, const uint64_t *turn_off, uint64_t n_convs,
+                           const uint8_t *flags) {
+    if (!e) return fail(MBPE_ERR_ARG, "mbpe_encoder_set_turns: NULL argument");
+    if (spec) {
+        const char *msg = "";
+        int rc = turns_check_spec(spec, 32, &msg);
+        if (rc == MBPE_OK && (!turn_off || n_convs >> 40)) { rc = MBPE_ERR_ARG; msg = "NULL turn_off or more than 2^40 conversations"; }
+        if (rc == MBPE_OK) rc = turns_check_arrays(turn_off, n_convs, flags, turn_off[n_convs], &msg);
+        if (rc != MBPE_OK) return fail(rc, std::string("mbpe_encoder_set_turns: ") + msg);
+        try {
+            std::vector<uint64_t> to(turn_off, turn_off + n_convs + 1);
+            std::vector<uint8_t> fl(flags, flags + turn_off[n_convs]);
+            e->tn_turn_off.swap(to);
+            e->tn_flags.swap(fl);
+        } catch (const std::bad_alloc &) {
+            return fail(MBPE_ERR_OOM, "mbpe_encoder_set_turns: host allocation failed");
+        }
+        e->tn = *spec;
+    }
+    e->tn_on = spec != nullptr;
+    return MBPE_OK;
+}
+
+int mbpe_encoder_turns_info(mbpe_encoder *e, uint64_t *kept_out, uint64_t cap_convs, uint64_t *n_convs_out) {
+    if (!e || !n_convs_out) return fail(MBPE_ERR_ARG, "mbpe_encoder_turns_info: NULL argument");
+    const uint64_t n = e->tn_convs;
+    *n_convs_out = n;
+    if (!kept_out) return MBPE_OK;
+    if (cap_convs < n) return fail(MBPE_ERR_ARG, "mbpe_encoder_turns_info: room for fewer conversations than the call had");
+    if (n == 0) return MBPE_OK;
+    ECHK(hipSetDevice(e->device));
+    ECHK(hipMemcpyAsync(kept_out, e->d_tn_info, n * 16, hipMemcpyDeviceToHost, e->stream));
     ECHK(hipStreamSynchronize(e->stream));
     return MBPE_OK;
 }

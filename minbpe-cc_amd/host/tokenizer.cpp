@@ -7,6 +7,7 @@
 #include "dropout.h"
 #include "fim.h"
 #include "textpair.h"
+#include "turns.h"
 #include "mlm.h"
 #include "mbpe.h"
 #include "mbpe_tokenizer.h"
@@ -74,6 +75,9 @@ mbpe_encoder *Tokenizer::device_encoder(int device) {
     if (rc == MBPE_OK) rc = mbpe_encoder_set_fim(encoder_, fim_on_ ? &fim_ : nullptr);
     if (rc == MBPE_OK) rc = mbpe_encoder_set_mlm(encoder_, mlm_on_ ? &mlm_ : nullptr);
     if (rc == MBPE_OK) rc = mbpe_encoder_set_textpair(encoder_, textpair_on_ ? &textpair_ : nullptr);
+    if (rc == MBPE_OK)
+        rc = mbpe_encoder_set_turns(encoder_, turns_on_ ? &turns_ : nullptr, turns_off_.data(),
+                                    turns_on_ ? turns_off_.size() - 1 : 0, turns_flags_.data());
     if (rc != MBPE_OK) throw mbpe_host::CodedError(rc, mbpe_last_error());
     return encoder_;
 }
@@ -1444,6 +1448,38 @@ int mbpe_tok_encode_textpair_info(mbpe_tokenizer *t, uint64_t *kept_out, uint64_
     *n_pairs_out = 0;
     mbpe_encoder *enc = t->t->kept_encoder();
     return enc ? mbpe_encoder_textpair_info(enc, kept_out, cap_pairs, n_pairs_out) : MBPE_OK;
+}
+
+int mbpe_tok_set_encode_turns(mbpe_tokenizer *t, const mbpe_turns_spec *spec, const uint64_t *turn_off, uint64_t n_convs,
+                              const uint8_t *flags) {
+    if (!t) return MBPE_ERR_ARG;
+    if (spec) {
+        const char *msg = "";
+        int rc = mbpe::turns_check_spec(spec, 32, &msg);
+        if (rc == MBPE_OK && (!turn_off || n_convs >> 40)) { rc = MBPE_ERR_ARG; msg = "NULL turn_off or more than 2^40 conversations"; }
+        if (rc == MBPE_OK) rc = mbpe::turns_check_arrays(turn_off, n_convs, flags, turn_off[n_convs], &msg);
+        if (rc != MBPE_OK) {
+            mbpe_host::set_last_error(std::string("mbpe_tok_set_encode_turns: ") + msg);
+            return rc;
+        }
+    }
+    try {
+        t->t->set_turns(spec, turn_off, n_convs, flags);
+    } catch (const std::bad_alloc &) {
+        mbpe_host::set_last_error("mbpe_tok_set_encode_turns: host allocation failed");
+        return MBPE_ERR_OOM;
+    }
+    return MBPE_OK;
+}
+
+int mbpe_tok_encode_turns_info(mbpe_tokenizer *t, uint64_t *kept_out, uint64_t cap_convs, uint64_t *n_convs_out) {
+    if (!t || !n_convs_out) {
+        mbpe_host::set_last_error("mbpe_tok_encode_turns_info: NULL argument");
+        return MBPE_ERR_ARG;
+    }
+    *n_convs_out = 0;
+    mbpe_encoder *enc = t->t->kept_encoder();
+    return enc ? mbpe_encoder_turns_info(enc, kept_out, cap_convs, n_convs_out) : MBPE_OK;
 }
 
 int mbpe_tok_set_train_dedup(mbpe_tokenizer *t, int on) {

@@ -131,6 +131,15 @@ public:
     void set_mlm(const mbpe_mlm_spec *spec) { mlm_on_ = spec != nullptr; if (spec) mlm_ = *spec; }
     // text pairs of the same calls (mbpe_tok_set_encode_textpair; mbpe.h holds the rule): NULL = off
     void set_textpair(const mbpe_textpair_spec *spec) { textpair_on_ = spec != nullptr; if (spec) textpair_ = *spec; }
+    // conversations of the same calls (mbpe_tok_set_encode_turns; mbpe.h holds the rule): NULL = off; the arrays
+    // (checked by the caller) are copied and hold until replaced
+    void set_turns(const mbpe_turns_spec *spec, const uint64_t *turn_off, uint64_t n_convs, const uint8_t *flags) {
+        turns_on_ = spec != nullptr;
+        if (!spec) return;
+        turns_ = *spec;
+        turns_off_.assign(turn_off, turn_off + n_convs + 1);
+        turns_flags_.assign(flags, flags + turn_off[n_convs]);
+    }
     mbpe_encoder *kept_encoder() const { return encoder_; }
     // the option "unicode" of every device split made from here on (mbpe_tok_set_split_unicode)
     void set_split_unicode(bool on) { split_unicode_ = on; }
@@ -275,7 +284,11 @@ private:
     mbpe_mlm_spec mlm_ = {};
     bool textpair_on_ = false;
     mbpe_textpair_spec textpair_ = {};
-    std::vector<uint64_t> counts_;           // count_tokens: the table, and the weighted token total it has reached
+    bool turns_on_ = false;
+    mbpe_turns_spec turns_ = {};
+    std::vector<uint64_t> turns_off_;
+    std::vector<uint8_t> turns_flags_;
+    std::vector<uint64_t> counts_;          // count_tokens: the table, and the weighted token total it has reached
     uint64_t counts_total_ = 0;
 };
 

@@ -60,6 +60,7 @@ EXPORTS = [
     "mbpe_encoder_encode_batch_endmask_denoise",
     "mbpe_textpair_plan", "mbpe_textpair_tokens", "mbpe_textpair_kernel_ms", "mbpe_encoder_set_textpair",
     "mbpe_encoder_textpair_info",
+    "mbpe_turns_plan", "mbpe_turns_tokens", "mbpe_turns_kernel_ms", "mbpe_encoder_set_turns", "mbpe_encoder_turns_info",
 ]
 # include/mbpe_tokenizer.h
 TOK_EXPORTS = [
@@ -78,6 +79,7 @@ TOK_EXPORTS = [
     "mbpe_tok_token_counts_reset", "mbpe_tok_encode_batch_fit_device", "mbpe_tok_set_encode_fim",
     "mbpe_tok_encode_fim_info", "mbpe_tok_set_encode_mlm", "mbpe_tok_encode_batch_denoise_device",
     "mbpe_tok_set_encode_textpair", "mbpe_tok_encode_textpair_info",
+    "mbpe_tok_set_encode_turns", "mbpe_tok_encode_turns_info",
 ]
 
 
@@ -169,6 +171,19 @@ class TextpairSpec(ctypes.Structure):
 
 TEXTPAIR_LONGEST_FIRST, TEXTPAIR_ONLY_FIRST, TEXTPAIR_ONLY_SECOND = 0, 1, 2
 TEXTPAIR_LABEL_ALL, TEXTPAIR_LABEL_SECOND = 0, 1
+
+
+class TurnsSpec(ctypes.Structure):
+    """mbpe_turns_spec (include/mbpe.h): the turns of a conversation joined into one document; turns_spec() makes one."""
+    _fields_ = [
+        ("max_tokens", ctypes.c_uint32), ("truncation", ctypes.c_uint32), ("head_turns", ctypes.c_uint32),
+        ("turn_end_id", ctypes.c_uint32), ("end_id", ctypes.c_uint32), ("label_mode", ctypes.c_uint32),
+    ]
+
+
+TURN_TRAIN, TURN_NO_END = 1, 2            # the bits of a turn's flags
+TURNS_RIGHT, TURNS_LEFT, TURNS_DROP_OLDEST = 0, 1, 2
+TURNS_LABEL_ALL, TURNS_LABEL_TRAINED = 0, 1
 
 
 class MlmSpec(ctypes.Structure):
@@ -449,6 +464,13 @@ def lib():
     L.mbpe_encoder_textpair_info.argtypes = [vp, vp, u64, vp]
     L.mbpe_tok_set_encode_textpair.argtypes = [vp, vp]
     L.mbpe_tok_encode_textpair_info.argtypes = [vp, vp, u64, vp]
+    L.mbpe_turns_plan.argtypes = [vp, u64, vp, u64, vp, vp, vp, vp]
+    L.mbpe_turns_tokens.argtypes = [i32, vp, u64, u32, i32, vp, u64, vp, u64, vp, vp, vp, vp, u64, i32, vp, vp, vp]
+    L.mbpe_turns_kernel_ms.argtypes = [vp]
+    L.mbpe_encoder_set_turns.argtypes = [vp, vp, vp, u64, vp]
+    L.mbpe_encoder_turns_info.argtypes = [vp, vp, u64, vp]
+    L.mbpe_tok_set_encode_turns.argtypes = [vp, vp, vp, u64, vp]
+    L.mbpe_tok_encode_turns_info.argtypes = [vp, vp, u64, vp]
     _lib = L
     return L
 
@@ -714,9 +736,91 @@ def textpair_kernel_ms():
     return ms.value
 
 
-def _batch_parts(texts, textpair):
+def turns_spec(max_tokens=0, truncation="right", head_turns=0, turn_end_id=None, end_id=None, labels="trained"):
+    """A TurnsSpec: a conversation becomes turn [turn_end] turn [turn_end] .. [end] with at most max_tokens ids (0: no
+    truncation), truncated "right", "left" or "drop_oldest" (whole turns go, oldest first, but never the first
+    head_turns).  labels "trained" gives next-token targets only where a trained id is predicted (the loss on the
+    assistant turns), "all" everywhere.  The rule: include/mbpe.h, mbpe_turns_spec."""
+    return TurnsSpec(max_tokens, {"right": 0, "left": 1, "drop_oldest": 2}[truncation], head_turns,
+                     NO_TOKEN if turn_end_id is None else turn_end_id, NO_TOKEN if end_id is None else end_id,
+                     {"all": 0, "trained": 1}[labels])
+
+
+def _turn_arrays(turn_off, flags):
+    to = np.ascontiguousarray(turn_off, dtype=np.uint64)
+    fl = np.ascontiguousarray(flags, dtype=np.uint8)
+    return to, fl, len(to) - 1, (fl.ctypes.data if len(fl) else None)
+
+
+def turns_plan(doc_tok_off, turn_off, flags, spec):
+    """mbpe_turns_plan (host only): the turns with these token offsets, conversation c owning turns turn_off[c] ..
+    turn_off[c + 1], flags[t] = TURN_TRAIN | TURN_NO_END -> (doc_tok_off of the joined conversations [n_convs + 1], info
+    uint64[n_convs, 2] = (dropped, cut))."""
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    to, fl, n_convs, fp = _turn_arrays(turn_off, flags)
+    new_off = np.zeros(n_convs + 1, dtype=np.uint64)
+    info = np.zeros((max(n_convs, 1), 2), dtype=np.uint64)
+    _check(lib().mbpe_turns_plan(off.ctypes.data, len(off) - 1, to.ctypes.data, n_convs, fp, ctypes.byref(spec),
+                                 new_off.ctypes.data, info.ctypes.data))
+    return new_off, info[:n_convs]
+
+
+def turns_tokens(tokens, doc_tok_off, turn_off, flags, spec, device=0, tokens_ptr=None, n_tokens=None, token_bits=None,
+                 out_ptr=None, targets_ptr=None, cap=0):
+    """mbpe_turns_tokens: the turns of a flat token array (uint16 or uint32) joined by conversation -> (tokens of the
+    same dtype, targets uint32, doc_tok_off of the joined conversations, info uint64[n_convs, 2] = (dropped, cut)): what
+    the pack_* calls take with label_tokens=targets.  Device memory as for textpair_tokens: tokens_ptr= / n_tokens= /
+    token_bits= name the tokens there; with out_ptr= (room for cap tokens; targets_ptr= for as many uint32, or None) ids
+    and targets are written there and (token count, doc_tok_off, info) is returned."""
+    off = np.ascontiguousarray(doc_tok_off, dtype=np.uint64)
+    to, fl, n_convs, fp = _turn_arrays(turn_off, flags)
+    if tokens_ptr is None:
+        t = np.ascontiguousarray(tokens)
+        if t.dtype not in (np.dtype(np.uint16), np.dtype(np.uint32)):
+            t = t.astype(np.uint32)
+        t = t.reshape(-1)
+        tp, n_tokens, token_bits, on_dev = (t.ctypes.data if len(t) else None), len(t), t.dtype.itemsize * 8, 0
+    else:
+        tp, on_dev = _ptr(tokens_ptr), 1
+    new_off = np.zeros(n_convs + 1, dtype=np.uint64)
+    info = np.zeros((max(n_convs, 1), 2), dtype=np.uint64)
+    n = ctypes.c_uint64()
+    head = (device, tp, n_tokens, token_bits, on_dev, off.ctypes.data, len(off) - 1, to.ctypes.data, n_convs, fp,
+            ctypes.byref(spec))
+    tail = (new_off.ctypes.data, info.ctypes.data, ctypes.byref(n))
+    if out_ptr is not None:
+        _check(lib().mbpe_turns_tokens(*head, _ptr(out_ptr), _ptr(targets_ptr), cap, 1, *tail))
+        return n.value, new_off, info[:n_convs]
+    _check(lib().mbpe_turns_tokens(*head, None, None, 0, 0, *tail))
+    out = np.zeros(max(n.value, 1), dtype=_ID_DTYPES[token_bits])
+    tgt = np.zeros(max(n.value, 1), dtype=np.uint32)
+    _check(lib().mbpe_turns_tokens(*head, out.ctypes.data, tgt.ctypes.data, n.value, 0, *tail))
+    return out[:n.value], tgt[:n.value], new_off, info[:n_convs]
+
+
+def turns_kernel_ms():
+    """Device time of the kernels of this thread's latest turns_tokens (mbpe_turns_kernel_ms)."""
+    ms = ctypes.c_float()
+    _check(lib().mbpe_turns_kernel_ms(ctypes.byref(ms)))
+    return ms.value
+
+
+def _turn_parts(convs):
+    """Conversations, each a sequence of (text, train) or (text, train, no_end) -> (the turns' bytes, turn_off, flags)."""
+    parts, turn_off, flags = [], [0], []
+    for conv in convs:
+        for turn in conv:
+            parts.append(bytes(_u8(turn[0])))
+            flags.append((TURN_TRAIN if turn[1] else 0) | (TURN_NO_END if len(turn) > 2 and turn[2] else 0))
+        turn_off.append(len(parts))
+    return parts, np.array(turn_off, dtype=np.uint64), np.array(flags, dtype=np.uint8)
+
+
+def _batch_parts(texts, textpair, turns=None):
     """The texts of a Tokenizer batch call as bytes, and the documents behind the stages: with textpair, `texts` is a
-    sequence of (a, b) and every pair is one document."""
+    sequence of (a, b) and every pair is one document; with turns, a sequence of conversations (_turn_parts)."""
+    if turns is not None:
+        return _turn_parts(texts)[0], len(texts)
     if textpair is None:
         parts = [bytes(_u8(t)) for t in texts]
         return parts, len(parts)
@@ -1410,6 +1514,30 @@ class Encoder:
         self._pairs = spec is not None
 
     _pairs = False                                 # set_textpair is on: a call's outputs are those of half as many documents
+    _convs = None                                  # set_turns is on: ... of this many conversations
+
+    def _behind(self, n_docs):
+        """The documents behind the stages of a batch call of n_docs documents."""
+        return n_docs >> self._pairs if self._convs is None else self._convs
+
+    def set_turns(self, spec, turn_off=None, flags=None):
+        """Conversations for the batch calls that follow (mbpe_encoder_set_turns): a TurnsSpec (turns_spec()) with
+        turn_off [n_convs + 1] and flags [n_docs] (TURN_TRAIN | TURN_NO_END), which are copied; None turns it off.  The
+        documents of a call are then the turns, conversation c owning turns turn_off[c] .. turn_off[c + 1]: rows,
+        segments and doc_tok_off are those of the joined conversations, and "labels" come from the stage's targets.
+        Not together with fim, mlm or textpair."""
+        if spec is None:
+            _check(lib().mbpe_encoder_set_turns(self._h, None, None, 0, None))
+            self._convs = None
+            return
+        to, fl, n_convs, fp = _turn_arrays(turn_off, flags)
+        _check(lib().mbpe_encoder_set_turns(self._h, ctypes.byref(spec), to.ctypes.data, n_convs, fp))
+        self._convs = n_convs
+
+    def turns_info(self):
+        """(dropped, cut) of every conversation of the latest batch call (mbpe_encoder_turns_info) -> uint64[n_convs, 2];
+        no conversations where the stage was off."""
+        return _textpair_info(lib().mbpe_encoder_turns_info, self._h)
 
     def textpair_info(self):
         """(a, b), the tokens kept of each side, of every pair of the latest batch call (mbpe_encoder_textpair_info)
@@ -1506,7 +1634,7 @@ class Encoder:
             _check(rc)
             return n_rows.value
         if spec.layout == PACK_PADDED:
-            n_rows.value = (len(docs) - 1) >> self._pairs     # known without a query
+            n_rows.value = self._behind(len(docs) - 1)      # known without a query
         else:
             _check(lib().mbpe_encoder_encode_batch(*head, None, 0, 0, None, *tail))
         ids, lengths = _matrix(n_rows.value, spec)
@@ -1549,7 +1677,7 @@ class Encoder:
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label)
         head, keep = self._batch_head(texts_or_buffer, chunk_off, doc_chunk_off, text_ptr, n_bytes, spec)
-        n_docs = (len(keep[-1]) - 1) >> self._pairs   # the documents behind the stages
+        n_docs = self._behind(len(keep[-1]) - 1)    # the documents behind the stages
         n_rows, n_tok = ctypes.c_uint64(), ctypes.c_uint64()
         doc_tok_off = np.zeros(n_docs + 1, dtype=np.uint64)
         tail = (ctypes.byref(n_rows), ctypes.byref(n_tok))
@@ -1585,7 +1713,7 @@ class Encoder:
         call = _WinCall(spec, stride, score_once, labels, positions, segments, ignore_label, row_doc, row_tok0)
         head, keep = self._batch_head(texts_or_buffer, chunk_off, doc_chunk_off, text_ptr, n_bytes, spec)
         n_tok = ctypes.c_uint64()
-        doc_tok_off = np.zeros(((len(keep[-1]) - 1) >> self._pairs) + 1, dtype=np.uint64)
+        doc_tok_off = np.zeros(self._behind(len(keep[-1]) - 1) + 1, dtype=np.uint64)
         tail = lambda n_rows, aux, win: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
                                          doc_tok_off.ctypes.data, ctypes.byref(win))
         try:
@@ -1608,7 +1736,7 @@ class Encoder:
         sg = _singles(singles)
         docs = np.ascontiguousarray(doc_off, dtype=np.uint64)
         n_tok = ctypes.c_uint64()
-        doc_tok_off = np.zeros(((len(docs) - 1) >> self._pairs) + 1, dtype=np.uint64)
+        doc_tok_off = np.zeros(self._behind(len(docs) - 1) + 1, dtype=np.uint64)
         head = (self._h, _ptr(text_ptr), n_bytes, _ptr(mask_ptr), sg.ctypes.data if len(sg) else None, len(sg),
                 docs.ctypes.data, len(docs) - 1, ctypes.byref(spec))
         tail = lambda n_rows, aux, win: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
@@ -1633,7 +1761,7 @@ class Encoder:
         call = _FitCall(spec, labels, positions, segments, cu_seqlens, ignore_label, doc_row, doc_col)
         head, keep = self._batch_head(texts_or_buffer, chunk_off, doc_chunk_off, text_ptr, n_bytes, spec)
         n_tok = ctypes.c_uint64()
-        doc_tok_off = np.zeros(((len(keep[-1]) - 1) >> self._pairs) + 1, dtype=np.uint64)
+        doc_tok_off = np.zeros(self._behind(len(keep[-1]) - 1) + 1, dtype=np.uint64)
         tail = lambda n_rows, aux, fit: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
                                          doc_tok_off.ctypes.data, ctypes.byref(fit))
         try:
@@ -1655,7 +1783,7 @@ class Encoder:
         sg = _singles(singles)
         docs = np.ascontiguousarray(doc_off, dtype=np.uint64)
         n_tok = ctypes.c_uint64()
-        doc_tok_off = np.zeros(((len(docs) - 1) >> self._pairs) + 1, dtype=np.uint64)
+        doc_tok_off = np.zeros(self._behind(len(docs) - 1) + 1, dtype=np.uint64)
         head = (self._h, _ptr(text_ptr), n_bytes, _ptr(mask_ptr), sg.ctypes.data if len(sg) else None, len(sg),
                 docs.ctypes.data, len(docs) - 1, ctypes.byref(spec))
         tail = lambda n_rows, aux, fit: (ctypes.byref(n_rows), ctypes.byref(n_tok), ctypes.byref(aux),
@@ -1720,7 +1848,7 @@ class Encoder:
         docs = np.ascontiguousarray(doc_off, dtype=np.uint64)
         n_docs = len(docs) - 1
         n_rows, n_tok = ctypes.c_uint64(), ctypes.c_uint64()
-        doc_tok_off = np.zeros((n_docs >> self._pairs) + 1, dtype=np.uint64)
+        doc_tok_off = np.zeros(self._behind(n_docs) + 1, dtype=np.uint64)
         head = (self._h, _ptr(text_ptr), n_bytes, _ptr(mask_ptr), sg.ctypes.data if len(sg) else None, len(sg),
                 docs.ctypes.data, n_docs, ctypes.byref(spec))
         tail = (ctypes.byref(n_rows), ctypes.byref(n_tok))
@@ -1734,7 +1862,7 @@ class Encoder:
             _check(rc)
             return n_rows.value
         if spec.layout == PACK_PADDED:
-            n_rows.value = n_docs >> self._pairs      # known without a query
+            n_rows.value = self._behind(n_docs)       # known without a query
         else:
             aux = call.device(None, None, None) if call else None
             _check(fn(*head, None, 0, 0, None, *tail, ctypes.byref(aux) if call else None, None))
@@ -2819,7 +2947,7 @@ class Tokenizer:
         _check(lib().mbpe_tok_load(self._h, os.fsencode(path), int(verbose)))
 
     def _encode_split(self, device_split, order="greedy", dropout=0.0, seed=0, dedup=False, fim=None, mlm=None,
-                      resident=False, textpair=None):
+                      resident=False, textpair=None, turns=None, convs=()):
         if order not in ("greedy", "rank"):
             raise ValueError('order must be "greedy" or "rank"')
         _check(lib().mbpe_tok_set_encode_dedup(self._h, int(bool(dedup))))
@@ -2831,6 +2959,17 @@ class Tokenizer:
         _check(lib().mbpe_tok_set_encode_fim(self._h, None if fim is None else ctypes.byref(fim)))
         _check(lib().mbpe_tok_set_encode_mlm(self._h, None if mlm is None else ctypes.byref(mlm)))
         _check(lib().mbpe_tok_set_encode_textpair(self._h, None if textpair is None else ctypes.byref(textpair)))
+        if turns is None:
+            _check(lib().mbpe_tok_set_encode_turns(self._h, None, None, 0, None))
+        else:
+            _, to, fl = _turn_parts(convs)
+            _check(lib().mbpe_tok_set_encode_turns(self._h, ctypes.byref(turns), to.ctypes.data, len(to) - 1,
+                                                   fl.ctypes.data if len(fl) else None))
+
+    def turns_info(self):
+        """(dropped, cut) of every conversation of the latest batch call with a device (mbpe_tok_encode_turns_info) ->
+        uint64[n_convs, 2]."""
+        return _textpair_info(lib().mbpe_tok_encode_turns_info, self._h)
 
     def textpair_info(self):
         """(a, b) of every pair of the latest batch call with a device (mbpe_tok_encode_textpair_info) ->
@@ -2948,7 +3087,7 @@ class Tokenizer:
     def encode_batch_padded(self, texts, seq_len, layout="padded", out_bits=32, pad_id=0, bos_id=None, eos_id=None,
                             pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
                             device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False, resident=False, fim=None,
-                            textpair=None):
+                            turns=None, textpair=None):
         """Every text split like encode(), encoded and packed in one device call
         (mbpe_tok_encode_batch_packed_device) -> (ids [n_rows, seq_len], lengths [n_rows]) as numpy arrays; with
         out_ptr= and len_ptr= (device memory for cap_rows rows) the matrix stays on the device and the row count is
@@ -2960,10 +3099,17 @@ class Tokenizer:
         textpair (here and in _aux, _windows and _fit; mbpe_tok_set_encode_textpair): a TextpairSpec (textpair_spec())
         -- `texts` is then a sequence of (a, b); each pair is truncated and joined on the device into one document
         a' sep.. b' [end] before it is packed, and "labels" follow the spec's label mode; its sep and end ids may be
-        special-token ids; textpair_info() tells what was kept of each side.  Not together with fim or mlm."""
-        self._encode_split(device_split, order, dropout, seed, dedup, fim, resident=resident, textpair=textpair)
+        special-token ids; textpair_info() tells what was kept of each side.  Not together with fim or mlm.
+        turns (here and in _aux, _windows and _fit; mbpe_tok_set_encode_turns): a TurnsSpec (turns_spec()) -- `texts`
+        is then a sequence of conversations, each a sequence of turns (text, train) or (text, train, no_end); every
+        conversation is joined on the device into one document with its turn-end and end ids, truncated by the spec's
+        rule, and "labels" follow its label mode.  A role header such as "<|assistant|>\n" is a turn of its own with
+        train=False, no_end=True.  The ids may be special-token ids; turns_info() tells what was dropped and cut.  Not
+        together with fim, mlm or textpair."""
+        self._encode_split(device_split, order, dropout, seed, dedup, fim, resident=resident, textpair=textpair,
+                           turns=turns, convs=texts)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
-        parts, n_out = _batch_parts(texts, textpair)
+        parts, n_out = _batch_parts(texts, textpair, turns)
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
         if parts:
             doc_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
@@ -3020,7 +3166,7 @@ class Tokenizer:
                          pad_left=False, trunc_left=False, device=0, out_ptr=None, len_ptr=None, cap_rows=None,
                          labels=False, positions=False, segments=False, cu_seqlens=False, ignore_label=-100,
                          labels_ptr=None, pos_ptr=None, seg_ptr=None, device_split=False, order="greedy", dropout=0.0,
-                         seed=0, dedup=False, resident=False, fim=None, mlm=None, textpair=None):
+                         seed=0, dedup=False, resident=False, fim=None, mlm=None, turns=None, textpair=None):
         """encode_batch_padded plus labels, positions, segments and cu_seqlens (mbpe_tok_encode_batch_aux_device): its
         arguments and those of pack_tokens_aux, whose dict (or, with out_ptr=, row count) is returned.  The documents'
         token offsets of the call (with fim: after the transform): self.doc_tok_off.
@@ -3028,10 +3174,11 @@ class Tokenizer:
         through masked-LM corruption on the device before they are packed: "ids" are the corrupted ids, "labels" the
         targets (ignore_label in every other cell).  whole_word masks the chunks of the split pattern as wholes and
         needs out_bits 32 or 64.  Not together with fim."""
-        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm, resident=resident, textpair=textpair)
+        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm, resident=resident, textpair=textpair,
+                           turns=turns, convs=texts)
         spec = pack_spec(seq_len, layout, out_bits, pad_id, bos_id, eos_id, pad_left, trunc_left)
         call = _AuxCall(spec, labels, positions, segments, cu_seqlens, ignore_label)
-        parts, n_out = _batch_parts(texts, textpair)
+        parts, n_out = _batch_parts(texts, textpair, turns)
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
         if parts:
             doc_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
@@ -3065,15 +3212,16 @@ class Tokenizer:
                              positions=False, segments=False, ignore_label=-100, labels_ptr=None, pos_ptr=None,
                              seg_ptr=None, row_doc=False, row_tok0=False, row_doc_ptr=None, row_tok0_ptr=None,
                              device_split=False, order="greedy", dropout=0.0, seed=0, dedup=False, resident=False, fim=None,
-                             mlm=None, textpair=None):
+                             mlm=None, turns=None, textpair=None):
         """encode_batch_aux for the window layout (mbpe_tok_encode_batch_windows_device): every text split like
         encode(), encoded, and cut into rows of seq_len that share `stride` tokens where a text does not fit one --
         the keywords and the result of pack_windows ("row_doc" maps a row back to its text).  The texts' token
         offsets of the call: self.doc_tok_off."""
-        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm, resident=resident, textpair=textpair)
+        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm, resident=resident, textpair=textpair,
+                           turns=turns, convs=texts)
         spec = pack_spec(seq_len, "padded", out_bits, pad_id, bos_id, eos_id)
         call = _WinCall(spec, stride, score_once, labels, positions, segments, ignore_label, row_doc, row_tok0)
-        parts, n_out = _batch_parts(texts, textpair)
+        parts, n_out = _batch_parts(texts, textpair, turns)
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
         if parts:
             doc_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
@@ -3093,15 +3241,16 @@ class Tokenizer:
                          len_ptr=None, cap_rows=None, labels=False, positions=False, segments=False, cu_seqlens=False,
                          ignore_label=-100, labels_ptr=None, pos_ptr=None, seg_ptr=None, doc_row=False, doc_col=False,
                          doc_row_ptr=None, doc_col_ptr=None, device_split=False, order="greedy", dropout=0.0, seed=0,
-                         dedup=False, resident=False, fim=None, mlm=None, textpair=None):
+                         dedup=False, resident=False, fim=None, mlm=None, turns=None, textpair=None):
         """encode_batch_aux for the fit layout (mbpe_tok_encode_batch_fit_device): every text split like encode(),
         encoded, and packed whole into rows of seq_len by best fit; only a text longer than a row is cut -- the
         keywords and the result of pack_fit ("doc_row" / "doc_col" say where a text's last piece begins, "segments"
         holds the text's number + 1 in every cell).  The texts' token offsets of the call: self.doc_tok_off."""
-        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm, resident=resident, textpair=textpair)
+        self._encode_split(device_split, order, dropout, seed, dedup, fim, mlm, resident=resident, textpair=textpair,
+                           turns=turns, convs=texts)
         spec = _fit_spec(seq_len, out_bits, pad_id, bos_id, eos_id)
         call = _FitCall(spec, labels, positions, segments, cu_seqlens, ignore_label, doc_row, doc_col)
-        parts, n_out = _batch_parts(texts, textpair)
+        parts, n_out = _batch_parts(texts, textpair, turns)
         doc_off = np.zeros(len(parts) + 1, dtype=np.uint64)
         if parts:
             doc_off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
